@@ -2,6 +2,7 @@
 """bench.py — headline benchmark: Mpixels/s shaded, deferred PBR, 1920x1080, ~100k meshlets.
 
     python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py ... --dump-outputs DIR               (+ the last timed frame's outputs as DIR/<name>.npy: see dump_outputs)
 
 A step is one full frame of the hot path on synthetic, HBM-resident input, INCLUDING the engine's per-frame uniform work
 (UpdateUniformBuffer, ZE:4585-4664: the point lights ride their spiral, XkView is rebuilt and uploaded every frame):
@@ -152,7 +153,13 @@ def main():
     ap.add_argument("--textured", action="store_true", help="profiling: config 3 with seven sampled 512^2 material images in the main loop "
                                                              "(the default line reports this variant as value_textured)")
     ap.add_argument("--serial", action="store_true", help="profiling: the whole frame on ONE stream (ZR_FLAG_SERIAL_PASSES), every kernel alone on the GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed frame computed to DIR/<name>.npy (float32, <= 64 MB in all): the lit "
+                         "frame, and for one GPU its GBuffer depth and shadow map; the same arguments give the same inputs, so two builds can "
+                         "be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` by itself: start the N ranks as a CHILD process (torch.distributed.run, one rank per GPU) and relay
@@ -282,6 +289,14 @@ def main():
     mlt, _, _ = r.mesh_get_meshlets(0)
     mesh = {"geo": float(np.mean(mlt["VertexCount"] * 44.0 + mlt["TriangleCount"] * 3.0 + 96.0)),
             "n_verts": len(cfg["objects"][0]["mesh"][0]), "n_idx": len(cfg["objects"][0]["mesh"][1])}
+    if args.dump_outputs and rank == 0:
+        # the last timed frame, before any other loop renders: the composited frame on rank 0; the depth and the shadow map are whole
+        # only on one GPU
+        arrays = {"color": r.color()}
+        if world == 1:
+            arrays["depth"] = r.gbuffer(0)
+            arrays["shadowmap"] = r.shadowmap()
+        dump_outputs(args.dump_outputs, arrays)
 
     extras = {}
     if not args.no_extras:
@@ -484,6 +499,28 @@ def main():
     if world > 1:
         barrier()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """arrays (name -> H x W [x C] numpy array) -> out_dir/<name>.npy as float32 (exact for the frame's 8-bit channels, the depth and
+    the shadow map).  When they would exceed `limit` bytes together, each array keeps a fixed, seeded sample of its pixels (the rows
+    of <name>.npy, [N, C]) and <name>_index.npy (float64) holds the flat pixel index of each row."""
+    os.makedirs(out_dir, exist_ok=True)
+    f32 = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes + 128 for v in f32.values())          # + each file's .npy header
+    if total <= limit:
+        for k, v in f32.items():
+            np.save(os.path.join(out_dir, k + ".npy"), v)
+        return
+    for k, v in f32.items():
+        px = v.reshape(v.shape[0] * v.shape[1], -1)
+        keep = max(1, int(len(px) * (limit * 0.95 / total) * px.itemsize * px.shape[1] / (px.itemsize * px.shape[1] + 8)))
+        idx = np.sort(np.random.default_rng(seed).choice(len(px), size=min(keep, len(px)), replace=False))
+        np.save(os.path.join(out_dir, k + ".npy"), px[idx])
+        np.save(os.path.join(out_dir, k + "_index.npy"), idx.astype(np.float64))
 
 
 def gather_json(obj, world, dist, torch):

@@ -1,6 +1,7 @@
 """Replay one seed of tests/test_gpu_fuzz.py and list the pixels whose depth differs from the oracle: python tests/fuzz_repro.py <seed> [flags]"""
+import os
 import sys
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np
 import test_gpu_fuzz as t
 from oracle import pyoracle

@@ -11,8 +11,11 @@ code with the product or its Python twins:
   :520-535); digest = vertex / index counts + sha256 of the XkVertex array (44 B records) and of the uint32 index array.
 
 Only the digests are committed (data: sizes, counts, hashes) - no byte of the content itself and no line of the reference's source.
-`tests/test_content_pins.py` holds `zr_load_png_rgba8` / `zr_load_obj` and `assets.load_obj` / `load_image_rgba8` to them wherever the
-content tree is present (it is not on the GPU box: CPU suite, skipped there).
+`tests/test_content_pins.py` asserts the known answers they carry; the content itself does not travel, so the suite holds
+`zr_load_png_rgba8` / `zr_load_obj` and `assets.load_obj` / `load_image_rgba8` to the stored fixtures of make_golden_content_fixtures.py,
+which carry the same format features.
+
+    python tests/golden/make_golden_content.py <the engine's Content directory>
 """
 import hashlib
 import json
@@ -23,7 +26,6 @@ import sys
 import numpy as np
 from PIL import Image
 
-CONTENT = "/root/reference/Engine/ZeldaEngine/Content"
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -67,15 +69,16 @@ def digest_obj(path):
 
 
 def main():
-    if not os.path.isdir(CONTENT):
-        sys.exit("no content tree at %s (build container only)" % CONTENT)
+    if len(sys.argv) != 2 or not os.path.isdir(sys.argv[1]):
+        sys.exit("usage: make_golden_content.py <Engine/ZeldaEngine/Content of the engine's tree>")
+    content = sys.argv[1]
     d = {"source": "Engine/ZeldaEngine/Content (reference tree, read-only)", "textures": {}, "models": {}}
-    for name in sorted(os.listdir(os.path.join(CONTENT, "Textures"))):
+    for name in sorted(os.listdir(os.path.join(content, "Textures"))):
         if name.endswith(".png"):
-            d["textures"][name] = digest_png(os.path.join(CONTENT, "Textures", name))
-    for name in sorted(os.listdir(os.path.join(CONTENT, "Models"))):
+            d["textures"][name] = digest_png(os.path.join(content, "Textures", name))
+    for name in sorted(os.listdir(os.path.join(content, "Models"))):
         if name.endswith(".obj"):
-            d["models"][name] = digest_obj(os.path.join(CONTENT, "Models", name))
+            d["models"][name] = digest_obj(os.path.join(content, "Models", name))
     with open(os.path.join(HERE, "content_digests.json"), "w") as f:
         json.dump(d, f, indent=1, sort_keys=True)
         f.write("\n")

@@ -1,6 +1,7 @@
 """A hunt with tests/test_gpu_fuzz.py's scenes at LARGE target and shadow-map sizes (overflows are reported with the statistics, mismatches with the targets): python tests/hunt_fuzz_large.py <first seed> <last seed>"""
+import os
 import sys
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np
 import test_gpu_fuzz as t
 from parity_util import compare_all

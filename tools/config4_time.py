@@ -1,6 +1,6 @@
 """Frame time and culling counters of config 4 (1 M instances, 3840x2160, 16 lights) / config 5 (256 lights): python tools/config4_time.py [n_point]"""
-import sys, time
-sys.path.insert(0, '/root/repo')
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from zeldaengine_amd import engine as gpu_engine, scenes
 n_point = int(sys.argv[1]) if len(sys.argv) > 1 else 16
 cfg = scenes.config4(1000000, n_point)

@@ -1,6 +1,6 @@
 """Where the camera pass's culls drop their meshlet-instances (config 3 / 4 / 5): python tools/cull_stats.py [3|4|5 ...]"""
-import sys
-sys.path.insert(0, '/root/repo')
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from zeldaengine_amd import engine, scenes
 for c in [int(x) for x in sys.argv[1:]] or [3, 4]:
     cfg = scenes.config3(10000) if c == 3 else scenes.config4(1000000, 256 if c == 5 else 16)

@@ -1,7 +1,7 @@
 """GPU period of every frame from the very first one after scene load (does the start of a run differ from its steady state?).
 Usage: python tools/early_frames.py [frames] [idle_ms between scene load and the first frame] [update: 1 = uniforms rebuilt every frame]"""
-import sys, time
-sys.path.insert(0, '/root/repo')
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from zeldaengine_amd import engine as gpu_engine, scenes
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 60

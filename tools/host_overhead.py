@@ -1,5 +1,5 @@
-import sys, time
-sys.path.insert(0, "/root/repo")
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from zeldaengine_amd import dist as zdist, engine, scenes
 cfg = scenes.config3()

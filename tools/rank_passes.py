@@ -1,7 +1,7 @@
 """Pass times of ONE rank's context of an N-rank job, alone on the GPU (where does a rank's frame go when N grows?).
 Usage: python tools/rank_passes.py [world] [rank] [config] [serial|lanes] [replicated|tiles|split]"""
-import sys, time
-sys.path.insert(0, '/root/repo')
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from zeldaengine_amd import engine, scenes, abi
 world = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 rank = int(sys.argv[2]) if len(sys.argv) > 2 else 3

@@ -1,7 +1,7 @@
 """Frame rate of the textured variant of the benchmark scene (seven 512^2 material images) under the current environment.
 Usage: [ENV=..] python tools/textured_ab.py [flags]"""
-import sys, time
-sys.path.insert(0, '/root/repo')
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from zeldaengine_amd import engine as gpu_engine, scenes, abi
 flags = int(sys.argv[1]) if len(sys.argv) > 1 else 0
 cfg = scenes.config3(10000, cube_dim=1024, textured=True)

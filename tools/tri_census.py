@@ -1,8 +1,8 @@
 """Float64 census of the benchmark frame's triangles (CPU, no GPU): for a sample of config 3's instances, every front-facing triangle whose snapped
 box holds a pixel centre - box size, pixels covered (exact integer edge functions, top-left rule).  What the camera pass's records are: DESIGN.md section 5.
     python tools/tri_census.py"""
-import numpy as np, sys
-sys.path.insert(0,'/root/repo')
+import os, numpy as np, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from zeldaengine_amd import scenes, abi
 cfg = scenes.config3()
 W,H = cfg["width"], cfg["height"]
