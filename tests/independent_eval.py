@@ -6,8 +6,12 @@ SH/BaseInstanced.vert:38-76, SH/BaseScene.frag:26-48, SH/BaseLighting.frag:147-2
 shares no code with them: different language, different precision (float64), different transcendentals (libm), naive evaluation
 order, exact sRGB / UNORM / fp16 conversions by definition instead of by table.
 
-What it takes as GIVEN (and therefore does not check): which primitive owns each pixel (the oracle's visibility buffer: raster
-rules, depth test, clipping) and, for the lighting pass, the GBuffer and the shadow map themselves.  What it recomputes: the vertex
+What it takes as GIVEN: which primitive owns each pixel and, for the lighting pass, the GBuffer, the shadow map and the frame's
+matrices.  These are no longer unchecked: tests/independent_geometry.py states the uniforms (UpdateUniformBuffer), the camera pass's
+winner and depth and the shadow map in float64 from the host code and the Vulkan text, and tests/test_oracle_geometry.py /
+tests/test_gpu_independent.py hold the oracle and the HIP renderer to it outside a derived ambiguity mask; the GPU test also feeds that
+statement's winners to base_scene() below, so the chain runs without the oracle.  Still unpinned: the 1/256-pixel snap, the clipper's
+re-snapped intersections and the depth-bias r of a clipped primitive (the implementation's choices).  What it recomputes: the vertex
 stage, perspective-correct interpolation, the 2x2-quad derivatives, ComputeNormal, every output of BaseScene.frag with its format
 conversion, and the whole lighting shader per pixel.  Material and cubemap textures are constant per slot / per face in the scenes
 it is used on, so no texture-filtering choice enters.

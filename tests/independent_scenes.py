@@ -1,0 +1,219 @@
+"""The scenes the independent statements are evaluated on (tests/independent_eval.py, tests/independent_geometry.py).  TEST INFRASTRUCTURE.
+
+`Scene` collects draws for the oracle, the HIP renderer (same method names) and the evaluators; `SCENES` are the three named and ten
+random scenes of tests/test_oracle_independent.py; `EDGE_SCENES` are the geometry edges of tests/test_oracle_geometry.py and
+tests/test_gpu_independent.py (each returns a `Case`).
+"""
+import collections
+import math
+
+import numpy as np
+
+from zeldaengine_amd import abi, scenes
+
+DEFAULT_TEXELS = [(127, 127, 127, 255), (0, 0, 0, 255), (255, 255, 255, 255), (127, 127, 255, 255), (255, 255, 255, 255), (0, 0, 0, 255),
+                  (255, 255, 255, 255)]                      # default_{grey,black,white,normal,white,black,white}.png, ZE:4951-4978
+FACES = [(200, 60, 40, 255), (40, 180, 70, 255), (50, 80, 210, 255), (220, 200, 60, 255), (150, 150, 160, 255), (30, 30, 35, 255)]
+
+
+def _const(rgba, n=2):
+    return np.tile(np.array(rgba, dtype=np.uint8), (n, n, 1))
+
+
+class Scene:
+    """Collects draws for both the oracle and the independent evaluator (engine draw order: non-instanced first, ZE:3445-3476)."""
+
+    def __init__(self):
+        self.items = []
+
+    def add(self, mesh, texels=None, instances=None):
+        self.items.append({"verts": mesh[0], "idx": mesh[1], "texel": list(texels or DEFAULT_TEXELS), "instances": instances})
+
+    def load(self, o):
+        o.set_cubemap([_const(c, 4) for c in FACES])
+        self._keep = []
+        for it in self.items:
+            mat = None
+            if it["texel"] != DEFAULT_TEXELS:
+                mat, k = abi.make_material([_const(t) for t in it["texel"]])
+                self._keep.append(k)
+            o.object_add(o.mesh_create(it["verts"], it["idx"]), mat, it["instances"])
+
+    def draws(self):
+        out, base = [], 0
+        for instanced in (False, True):
+            for it in self.items:
+                if (it["instances"] is not None) != instanced:
+                    continue
+                d = dict(it)
+                d["prim_base"] = base
+                base += (len(it["idx"]) // 3) * (1 if it["instances"] is None else len(it["instances"]))
+                out.append(d)
+        return out
+
+
+def _lights(n_dir, n_point):
+    w = scenes.sample_world()
+    d, _, s = scenes.lights_from_world(w)
+    w["PointLights"] = scenes.sample_point_lights(n_point)
+    _, p, _ = scenes.lights_from_world(w)
+    for l in p:
+        l["Direction"][3] = 6.0           # a radius that reaches the geometry
+    return d[:n_dir], p, s
+
+
+def scene_mixed():
+    s = Scene()
+    s.add(scenes.grid_plane(14.0, 3, 0.0))
+    s.add(scenes.box((0.9, 0.6, 0.5), (1.2, -0.8, 0.5)), [(200, 40, 30, 255), (255, 255, 255, 255), (90, 90, 90, 255), (127, 127, 255, 255),
+                                                            (180, 180, 180, 255), (0, 20, 40, 255), (255, 255, 255, 255)])
+    s.add(scenes.uv_sphere(12, 6, 0.6), None, scenes.generate_instances(12, 1.0, 4.5, 0.5, 1.2, seed=3))
+    return s, abi.make_camera((5.0, 4.0, 3.5), (0.0, 0.0, 0.4)), _lights(1, 4), 0.0
+
+
+def scene_single_sphere_no_sun():
+    """config 2's shape: no directional light -> lookAt(0, 0) = NaN shadow matrices -> every PCF tap returns 1"""
+    s = Scene()
+    s.add(scenes.uv_sphere(16, 8, 1.0))
+    return s, abi.make_camera((1.9, 1.7, 1.3), (0.0, 0.0, 0.0)), _lights(0, 1), 0.0
+
+
+def scene_rolled_and_clipped():
+    """a rotated stage (model != identity), metallic / rough materials, instanced boxes, the ground crossing the near plane"""
+    s = Scene()
+    s.add(scenes.grid_plane(40.0, 2, 0.0), [(90, 140, 60, 255), (0, 0, 0, 255), (200, 200, 200, 255), (127, 127, 255, 255), (255, 255, 255, 255),
+                                             (0, 0, 0, 255), (255, 255, 255, 255)])
+    s.add(scenes.box((0.4, 0.4, 0.9), (0, 0, 0.9)), [(220, 220, 230, 255), (230, 230, 230, 255), (60, 60, 60, 255), (140, 120, 250, 255),
+                                                      (255, 255, 255, 255), (10, 0, 0, 255), (255, 255, 255, 255)],
+          scenes.generate_instances(9, 1.5, 5.0, 0.6, 1.4, seed=21))
+    s.add(scenes.uv_sphere(10, 5, 0.8), None, scenes.generate_instances(5, 1.0, 3.0, 0.5, 1.0, seed=4))
+    return s, abi.make_camera((3.0, -4.0, 1.2), (0.0, 0.0, 0.6), fov=60.0), _lights(1, 16), 0.35
+
+
+def scene_random(seed):
+    """seeded mixtures: 2-5 draws of plane / box / sphere with random constant materials (metallic, rough, emissive, masked, odd normal
+    texels), with and without instances, 0-1 directional and 0-24 point lights, the camera anywhere around, the stage rolled"""
+    rng = np.random.default_rng(7000 + seed)
+    s = Scene()
+
+    def texels():
+        if rng.random() < 0.3:
+            return None
+        t = [tuple(int(x) for x in rng.integers(0, 256, 3)) + (255,) for _ in range(7)]
+        t[3] = (int(rng.integers(100, 156)), int(rng.integers(100, 156)), int(rng.integers(200, 256)), 255)      # a plausible normal texel
+        t[6] = (int(rng.choice([255, 255, 255, 0, 128])), 0, 0, 255)                                              # the lighting mask
+        return t
+    s.add(scenes.grid_plane(float(rng.choice([10.0, 24.0, 60.0])), int(rng.integers(2, 5)), 0.0), texels())
+    for _ in range(int(rng.integers(1, 5))):
+        kind = int(rng.integers(0, 3))
+        mesh = [scenes.uv_sphere(12, 6, 0.6), scenes.uv_sphere(16, 8, 0.9), scenes.box((0.7, 0.5, 0.6), (0.0, 0.0, 0.6))][kind]
+        inst = scenes.generate_instances(int(rng.integers(2, 20)), 0.8, float(rng.uniform(3.0, 9.0)), 0.4, 1.3, seed=int(rng.integers(1, 1 << 30))) if rng.random() < 0.7 else None
+        s.add(mesh, texels(), inst)
+    a, rad = rng.uniform(0, 2 * math.pi), float(rng.choice([3.5, 6.0, 11.0]))
+    cam = abi.make_camera((rad * math.cos(a), rad * math.sin(a), float(rng.choice([0.6, 2.0, 5.0]))), (float(rng.uniform(-1, 1)), float(rng.uniform(-1, 1)), 0.4),
+                          fov=float(rng.choice([40.0, 55.0, 70.0])))
+    return s, cam, _lights(int(rng.integers(0, 2)), int(rng.choice([0, 1, 3, 8, 24]))), float(rng.uniform(0.0, 1.0))
+
+
+SCENES = {"mixed": scene_mixed, "single_sphere_no_sun": scene_single_sphere_no_sun, "rolled_and_clipped": scene_rolled_and_clipped}
+for _k in range(10):
+    SCENES["random_%02d" % _k] = (lambda k: (lambda: scene_random(k)))(_k)
+
+
+# ---------------------------------------------------------------------------------------------------------------- geometry edge cases
+
+Case = collections.namedtuple("Case", "scene cam lights roll_stage roll_light W H SD")
+
+
+def case(name, W=192, H=128, SD=256):
+    """One of SCENES (roll_light 0) or EDGE_SCENES as a Case; the edge scenes carry their own size."""
+    if name in EDGE_SCENES:
+        return EDGE_SCENES[name]()
+    s, cam, lights, roll = SCENES[name]()
+    return Case(s, cam, lights, roll, 0.0, W, H, SD)
+
+
+def _sun_at(lights, elevation, azimuth=0.0, distance=28.0):
+    """the first directional light moved to (elevation, azimuth) at `distance`: its Position is the shadow camera's eye (ZE:4606-4612)"""
+    d, p, s = lights
+    d = d.copy()
+    ce = 0.0 if elevation == math.pi / 2 else math.cos(elevation)          # the zenith exactly: cos(pi / 2) is 6e-17 in float64
+    d[0]["Position"][:3] = (distance * ce * math.cos(azimuth), distance * ce * math.sin(azimuth), distance * math.sin(elevation))
+    return d, p, s
+
+
+def _props(s, n_boxes=14, n_spheres=8, seed=5, radius=4.0):
+    s.add(scenes.box((0.5, 0.4, 0.6), (0.0, 0.0, 0.6)), None, scenes.generate_instances(n_boxes, 0.8, radius, 0.5, 1.3, seed=seed))
+    s.add(scenes.uv_sphere(12, 6, 0.6), None, scenes.generate_instances(n_spheres, 1.0, radius, 0.5, 1.2, seed=seed + 1))
+
+
+def edge_rolled_stage_and_light():
+    """roll_stage and roll_light both nonzero: the stage rolls in both Model matrices, the point-light spiral turns (ZE:4606-4646)"""
+    s = Scene()
+    s.add(scenes.grid_plane(14.0, 3, 0.0))
+    _props(s)
+    return Case(s, abi.make_camera((5.0, 4.0, 3.5), (0.0, 0.0, 0.4)), _lights(1, 12), 0.6, 0.8, 192, 128, 256)
+
+
+def edge_grazing_sun():
+    """the sun 0.15 rad above the horizon, a 1024-texel map: long, steep shadow-space slopes (the 7.5 m term dominates)"""
+    s = Scene()
+    s.add(scenes.grid_plane(20.0, 4, 0.0))
+    _props(s, seed=9)
+    return Case(s, abi.make_camera((6.0, -3.0, 3.0), (0.0, 0.0, 0.3)), _sun_at(_lights(1, 4), 0.15, 0.4), 0.2, 0.0, 192, 128, 1024)
+
+
+def edge_sun_at_zenith():
+    """the sun straight above the stage: lookAt(eye, 0, up) with up parallel to the view direction -> normalize(cross(f, up)) = 0 / 0"""
+    s = Scene()
+    s.add(scenes.grid_plane(14.0, 3, 0.0))
+    _props(s, seed=13)
+    return Case(s, abi.make_camera((5.0, 4.0, 3.5), (0.0, 0.0, 0.4)), _sun_at(_lights(1, 4), math.pi / 2, 0.0, 28.0), 0.0, 0.0, 192, 128, 256)
+
+
+def _mirrored(inst):
+    inst = inst.copy()
+    inst["InstancePScale"] *= -1.0
+    return inst
+
+
+def edge_mirrored_instances():
+    """negative InstancePScale: the instance transform mirrors, so the winding flips and BACK culling keeps the inner faces"""
+    s = Scene()
+    s.add(scenes.grid_plane(14.0, 3, 0.0))
+    s.add(scenes.box((0.5, 0.4, 0.6), (0.0, 0.0, 0.6)), None, _mirrored(scenes.generate_instances(12, 0.8, 4.0, 0.5, 1.3, seed=17)))
+    s.add(scenes.uv_sphere(12, 6, 0.6), None, _mirrored(scenes.generate_instances(6, 1.0, 4.0, 0.5, 1.2, seed=18)))
+    s.add(scenes.uv_sphere(12, 6, 0.6), None, scenes.generate_instances(4, 1.0, 4.0, 0.5, 1.2, seed=19))
+    return Case(s, abi.make_camera((5.0, 4.0, 3.5), (0.0, 0.0, 0.4)), _lights(1, 4), 0.1, 0.0, 192, 128, 256)
+
+
+def edge_low_camera():
+    """the camera 0.25 above a 30-unit ground plane, znear 0.05, fov 70: triangles cross the near plane and the 4x guard band"""
+    s = Scene()
+    s.add(scenes.grid_plane(30.0, 12, 0.0))
+    _props(s, n_boxes=10, n_spheres=6, seed=23, radius=6.0)
+    return Case(s, abi.make_camera((0.4, -0.3, 0.25), (6.0, 4.0, 0.1), fov=70.0, znear=0.05, zfar=80.0), _lights(1, 4), 0.0, 0.0, 192, 128, 256)
+
+
+def edge_repeated_draw():
+    """the same box drawn twice, and the same instanced draw twice: exactly equal depths, so LESS keeps the FIRST draw's primitive"""
+    s = Scene()
+    s.add(scenes.grid_plane(14.0, 3, 0.0))
+    box = scenes.box((0.9, 0.6, 0.5), (1.2, -0.8, 0.5))
+    s.add(box)
+    s.add(box)
+    inst = scenes.generate_instances(10, 1.0, 4.5, 0.5, 1.2, seed=29)
+    s.add(scenes.uv_sphere(12, 6, 0.6), None, inst)
+    s.add(scenes.uv_sphere(12, 6, 0.6), None, inst)
+    return Case(s, abi.make_camera((5.0, 4.0, 3.5), (0.0, 0.0, 0.4)), _lights(1, 4), 0.0, 0.0, 192, 128, 256)
+
+
+def edge_odd_size():
+    """257 x 131 with a 100-texel map: no size is a multiple of the 32-pixel tile or a power of two"""
+    s, cam, lights, roll = scene_mixed()
+    return Case(s, cam, lights, roll, 0.0, 257, 131, 100)
+
+
+EDGE_SCENES = {"rolled_stage_and_light": edge_rolled_stage_and_light, "grazing_sun": edge_grazing_sun, "sun_at_zenith": edge_sun_at_zenith,
+               "mirrored_instances": edge_mirrored_instances, "low_camera": edge_low_camera, "repeated_draw": edge_repeated_draw,
+               "odd_size": edge_odd_size}
