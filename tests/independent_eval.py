@@ -13,10 +13,16 @@ tests/test_gpu_independent.py hold the oracle and the HIP renderer to it outside
 statement's winners to base_scene() below, so the chain runs without the oracle.  Still unpinned: the 1/256-pixel snap, the clipper's
 re-snapped intersections and the depth-bias r of a clipped primitive (the implementation's choices).  What it recomputes: the vertex
 stage, perspective-correct interpolation, the 2x2-quad derivatives, ComputeNormal, every output of BaseScene.frag with its format
-conversion, and the whole lighting shader per pixel.  Material and cubemap textures are constant per slot / per face in the scenes
-it is used on, so no texture-filtering choice enters.
+conversion, and the whole lighting shader per pixel.  Material slots are either constant texels or images sampled through
+tests/independent_sampler.py (its own mip chains, the quad's derivatives, REPEAT, the specification's anisotropic scheme), and the
+reflection cubemap either one colour per face or a chain sampled at ComputeReflectionMipFromRoughness; for sampled slots base_scene()
+also states the range the value spans over the snap and float32 error budget and which pixels' tap count is not decided
+(tests/test_oracle_textured.py).  Still unpinned on the texture side: cube seam filtering (CLAMP_TO_EDGE inside a face, a stated
+choice) and the skydome / background passes.
 """
 import numpy as np
+
+import independent_sampler as isamp
 
 F64 = np.float64
 
@@ -90,16 +96,56 @@ def compute_normal(pos_dx, pos_dy, st1, st2, frag_normal, tex_normal):
     return normalize(T * ts[..., 0:1] + B * ts[..., 1:2] + N * ts[..., 2:3])        # TBN * v, TBN = mat3(T, B, N) (columns)
 
 
-def base_scene(draws, cam, prim_ids, W, H):
+# The sampled slots' error budget.  An implementation's fragment sees UV0 and the quad differences st1 / st2 after
+# two steps this statement does not take: the 1/256-pixel vertex snap and float32 interpolation.
+F32_INTERP = 8 * 2.0 ** -24      # |uv| relative: three products and two sums (half an ulp each) over barycentrics good to ~4 ulp
+SNAP = 1.0 / 256.0               # pixels
+GUARD = 4.0                      # the clipper's guard band, in viewports
+
+
+def _sampled_slot(chain, srgb, UV0, st1, st2, tri_uv, alt_px, control):
+    """texture(sampler, UV0) with the quad's derivatives, and the range the float64 value spans over the error budget.
+    -> value (k, 4), range (k, 4), ambiguous (k,): Pmax / Pmin within the derivative error of an integer below 16 (N or N + 1 taps)"""
+    dec = [isamp.decode(l, srgb) for l in chain]
+    duv = np.hstack([st1, st2])
+    val, _, _, margin, ratio = isamp.sample_2d_array(chain, srgb, UV0, duv, control, dec)
+    e_uv = F32_INTERP * np.abs(tri_uv).max(axis=1)                               # (k, 2): interpolation error of u and v
+    with np.errstate(divide="ignore", invalid="ignore"):
+        # the two derivative vectors: a float32 quad difference (two interpolation errors) relative to the shorter one, plus what
+        # moving the triangle's vertices by half a snap step each does to its screen gradient: 2 x (SNAP / 2) over its smallest altitude
+        rel = 2.0 * np.hypot(*e_uv.T) / np.minimum(np.hypot(*st1.T), np.hypot(*st2.T)) + SNAP / alt_px
+    rel = np.where(np.isfinite(rel), rel, np.inf)
+    bad = rel > 0.2
+    r = np.where(bad, 0.0, rel)[:, None]
+    # uv: the snap budget, the interpolation error, and the tap positions (off * major axis, |off| < 1/2) moved by the derivative error
+    d_uv = (np.abs(st1) + np.abs(st2)) * (SNAP + 0.5 * r) + e_uv
+    lo, hi = val.copy(), val.copy()
+    for su, sv in ((1, 1), (1, -1), (-1, 1), (-1, -1)):
+        v = isamp.sample_2d_array(chain, srgb, UV0 + d_uv * (su, sv), duv, control, dec)[0]
+        lo, hi = np.minimum(lo, v), np.maximum(hi, v)
+    for a, b in ((1, -1), (-1, 1), (1, 1), (-1, -1)):                              # Pmax / Pmin and lambda at their extremes
+        v = isamp.sample_2d_array(chain, srgb, UV0, np.hstack([st1 * (1 + a * r), st2 * (1 + b * r)]), control, dec)[0]
+        lo, hi = np.minimum(lo, v), np.maximum(hi, v)
+    # Pmax / Pmin moves by a factor within (1 +- r) / (1 -+ r), i.e. by less than 2.5 r of itself for r <= 0.2
+    amb = bad | ((ratio < isamp.MAX_ANISO) & (margin <= 2.5 * rel * ratio))
+    return val, hi - lo, amb
+
+
+def base_scene(draws, cam, prim_ids, W, H, control=None):
     """BaseScene.frag:26-48 for every covered pixel.
 
-    draws: list of dicts in the engine's draw order {verts, idx, instances (or None), texel (7 RGBA8 tuples), prim_base}
+    draws: list of dicts in the engine's draw order {verts, idx, instances (or None), texel (7 RGBA8 tuples), prim_base, images (optional:
+    7 entries, each None - the slot's constant texel - or an (h, w, 4) uint8 image sampled through its mip chain)}
     cam: XkUniformBufferMVP (numpy record); prim_ids: (H, W) winning primitive per pixel (0xFFFFFFFF: none)
-    -> dict of float arrays over the covered pixels + their (y, x) coordinates
+    control: a misreading for the negative controls - "slot0_unorm", or one of independent_sampler's
+    -> dict of float arrays over the covered pixels + their (y, x) coordinates; for sampled slots also "range_<target>" (the span of
+    the float64 value over the error budget, per channel) and "ambiguous" (per pixel)
     """
     model, view, proj = mat(cam["Model"]), mat(cam["View"]), mat(cam["Proj"])
     ys, xs = np.nonzero(prim_ids != 0xFFFFFFFF)
-    out = {k: np.zeros((len(ys), n)) for k, n in (("scene_color", 4), ("a", 4), ("b", 4), ("c", 4), ("d", 4), ("d_per_pixel", 3), ("normal", 3))}
+    out = {k: np.zeros((len(ys), n)) for k, n in (("scene_color", 4), ("a", 4), ("b", 4), ("c", 4), ("d", 4), ("d_per_pixel", 3), ("normal", 3),
+                                                   ("range_scene_color", 4), ("range_b", 4), ("range_c", 4))}
+    out["ambiguous"] = np.zeros(len(ys), bool)
     pid = prim_ids[ys, xs].astype(np.int64)
     for d in draws:
         n_tris = len(d["idx"]) // 3
@@ -110,9 +156,8 @@ def base_scene(draws, cam, prim_ids, W, H):
         local = pid[sel] - d["prim_base"]
         inst_i, tri = local // n_tris, local % n_tris
         tex = np.asarray(d["texel"], dtype=F64)              # 7 x RGBA8
-        base_color = srgb_to_linear(tex[0, :3])              # sampler1 is R8G8B8A8_SRGB (ZE:5878); the others UNORM
-        metallic, rough = tex[1, 0] / 255.0, tex[2, 0] / 255.0
-        tex_n, ao, emissive, mask = tex[3, :3] / 255.0, tex[4, 0] / 255.0, tex[5, :3] / 255.0, tex[6, 0] / 255.0
+        images = d.get("images") or [None] * 7
+        chains = [None if im is None else isamp.mip_chain(im, i == 0 and control != "slot0_unorm", control) for i, im in enumerate(images)]
         for ii in np.unique(inst_i):
             m = sel[inst_i == ii]
             t = tri[inst_i == ii]
@@ -140,18 +185,55 @@ def base_scene(draws, cam, prim_ids, W, H):
             Pv, _, UVv = varyings(px, py - sy)
             pos_dx, pos_dy = (P0 - Ph) * sx[:, None], (P0 - Pv) * sy[:, None]
             st1, st2 = (UV0 - UVh) * sx[:, None], (UV0 - UVv) * sy[:, None]
-            normal = compute_normal(pos_dx, pos_dy, st1, st2, N0, np.broadcast_to(tex_n, P0.shape))
-            packed = (normalize(normal) + 1.0) / 2.0
             k = len(m)
-            out["scene_color"][m] = np.hstack([np.broadcast_to(emissive, (k, 3)), np.full((k, 1), mask)])
+            smp, rng = np.broadcast_to(tex / 255.0, (k, 7, 4)).copy(), np.zeros((k, 7, 4))
+            if control != "slot0_unorm":
+                smp[:, 0, :3] = srgb_to_linear(tex[0, :3])          # sampler1 is R8G8B8A8_SRGB (ZE:5878); the others UNORM
+            if any(c is not None for c in chains):
+                w = c3[..., 3]
+                clipped = np.any((w <= 0.0) | (c3[..., 2] < 0.0) | (np.abs(c3[..., 0]) > GUARD * w) | (np.abs(c3[..., 1]) > GUARD * w), axis=1)
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    sp = (c3[..., :2] / w[..., None] + 1.0) * 0.5 * np.array([W, H])               # (k, 3, 2) screen positions
+                    e = [sp[:, (j + 1) % 3] - sp[:, j] for j in range(3)]
+                    area2 = np.abs(e[0][:, 0] * e[1][:, 1] - e[0][:, 1] * e[1][:, 0])
+                    alt = np.min([area2 / np.hypot(*ej.T) for ej in e], axis=0)                  # smallest altitude, pixels
+                alt = np.where(clipped | ~np.isfinite(alt), 0.0, alt)          # clipped: the clipper's re-snapped vertices are its own
+                for i, ch in enumerate(chains):
+                    if ch is not None:
+                        smp[:, i], rng[:, i], amb = _sampled_slot(ch, i == 0 and control != "slot0_unorm", UV0, st1, st2, uv[corner], alt, control)
+                        out["ambiguous"][m] |= amb
+            base_color, metallic, rough = smp[:, 0, :3], smp[:, 1, 0], smp[:, 2, 0]
+            tex_n, ao, emissive, mask = smp[:, 3, :3], smp[:, 4, 0], smp[:, 5, :3], smp[:, 6, 0]
+            normal = compute_normal(pos_dx, pos_dy, st1, st2, N0, tex_n)
+            packed = (normalize(normal) + 1.0) / 2.0
+            out["scene_color"][m] = np.hstack([emissive, mask[:, None]])
             out["a"][m] = np.hstack([packed, np.ones((k, 1))])
             out["normal"][m] = normal                                       # ComputeNormal()'s result as Base.frag uses it (forward variant)
-            out["b"][m] = np.broadcast_to([metallic, 1.0, max(0.01, rough), 1.0], (k, 4))
-            out["c"][m] = np.hstack([np.broadcast_to(base_color, (k, 3)), np.full((k, 1), ao)])
+            out["b"][m] = np.stack([metallic, np.ones(k), np.maximum(0.01, rough), np.ones(k)], axis=1)
+            out["c"][m] = np.hstack([base_color, ao[:, None]])
             out["d"][m] = np.hstack([P0, np.ones((k, 1))])
             out["d_per_pixel"][m] = np.abs(pos_dx) + np.abs(pos_dy)       # how far the position moves per pixel step (x plus y)
+            out["range_scene_color"][m] = np.hstack([rng[:, 5, :3], rng[:, 6, :1]])
+            out["range_b"][m] = np.stack([rng[:, 1, 0], np.zeros(k), rng[:, 2, 0], np.zeros(k)], axis=1)
+            out["range_c"][m] = np.hstack([rng[:, 0, :3], rng[:, 4, :1]])
     out["yx"] = (ys, xs)
     return out
+
+
+def check_sampled_targets(mine, got):
+    """GBuffer targets 1, 3 and 4 (scene colour, B, C) against base_scene()'s values: every channel of every unambiguous pixel within
+    the range its float64 value spans over the error budget plus one code of output rounding (constant slots: range 0 - exact to the
+    rounding).  got: the (k, 4) codes at mine["yx"].  -> dict ok, ambiguous (fraction), worst (largest error / tolerance), bad (pixel-target pairs outside)"""
+    amb = mine["ambiguous"]
+    worst, bad = 0.0, 0
+    for k in ("scene_color", "b", "c"):
+        err = np.abs(got[k] - mine[k] * 255.0)
+        tol = mine["range_" + k] * 255.0 + 1.0
+        r = (err / tol)[~amb]
+        if r.size:
+            worst = max(worst, float(r.max()))
+            bad += int((r > 1.0).any(axis=1).sum())
+    return {"ok": bad == 0, "ambiguous": float(amb.mean()) if len(amb) else 0.0, "worst": worst, "bad": bad}
 
 
 # ----------------------------------------------------------------------------------------------- formats
@@ -238,12 +320,35 @@ def bxdf(diffuse_color, roughness, LoH, NoV, NoL, NoH):
     return diffuse_color * (1.0 - F)[..., None] * Fd[..., None] + Fr[..., None]
 
 
-def lighting(gb, shadow_map, view, cube_face_colors, W, H, pcf_eps=0.0, forward=False):
+def reflection_mip(roughness, cubemap_max_mip, control=None):
+    """ComputeReflectionMipFromRoughness, SH/Common.glsl:191-198 (REFLECTION_CAPTURE_ROUGHEST_MIP 1, ..._ROUGHNESS_MIP_SCALE 1.2)"""
+    level_from_1x1 = 1.0 - 1.2 * np.log2(np.maximum(roughness, 0.001))
+    return (cubemap_max_mip if control == "cube_lod_max_mip" else cubemap_max_mip - 1.0) - level_from_1x1
+
+
+# What the normal's error does to the reflected direction.  The normal reaches the deferred lighting pass as A2R10G10B10 codes: half a
+# code is 1 / 1023 per component, sqrt(3) / 1023 in length; refract() moves R by at most about twice that for a unit V.  The forward
+# variant's normal is unquantised, but a float32 implementation's differs from this statement's by less (the snap and float32 rounding).
+R_ERR = 2.0 * np.sqrt(3.0) / 1023.0
+
+
+def cube_boundary(R):
+    """lookups whose face R does not decide: the two largest |R| components closer than R_ERR can move them (twice R_ERR)"""
+    a = np.sort(np.abs(R), axis=-1)
+    return (a[..., 2] - a[..., 1]) <= 2.0 * R_ERR
+
+
+def lighting(gb, shadow_map, view, cube, W, H, pcf_eps=0.0, forward=False, control=None, out=None, r_offset=None):
     """BaseLighting.frag:147-227 + case 0 of the switch for every pixel of the W x H quad.
     forward=True: Base.frag:46-123 instead - the same text except that N is used as ComputeNormal() returned it, AO is not saturated,
     there is no Mask, and case 0 shows FinalColor * ShadowFactor (after the gamma); gb then holds the fragment's unquantised inputs.
 
     gb: dict scene_color / a / b / c (float RGBA as texture() returns them) and d (fp16 values), each (H, W, 4); view: XkView record
+    cube: the six face colours of a cubemap whose faces are each ONE colour (no filter or lod choice matters), or the cubemap's mip
+    chain (independent_sampler.cube_chain): textureLod at ComputeReflectionMipFromRoughness(Roughness, SKY_MAXMIPS), SKY_MAXMIPS =
+    view.LightsCount[3].  control: "cube_lod_max_mip" or one of independent_sampler's (negative controls).  out: a dict that receives
+    R (the reflected direction the cubemap is sampled with).  r_offset: a vector added to R before the cubemap lookup (a caller that
+    wants to know what R's own error does evaluates with offsets of that size, as with pcf_eps)
     pcf_eps: added to the reference depth of the 25 shadow comparisons - the shader's one discontinuity: a caller that wants to know
     which pixels sit on it evaluates with +-eps and looks at the spread
     -> (H, W, 3) float colour before the UNORM store
@@ -320,7 +425,15 @@ def lighting(gb, shadow_map, view, cube_face_colors, W, H, pcf_eps=0.0, forward=
         dNI = dot(Nn, V)
         k = 1.0 - eta * eta * (1.0 - dNI * dNI)
         R = np.where((k < 0.0)[..., None], 0.0, eta * V - (eta * dNI + np.sqrt(np.maximum(k, 0.0)))[..., None] * Nn)
-        refl_l = cube_face_constant(cube_face_colors, R) * 10.0
+        if out is not None:
+            out["R"] = R
+        if r_offset is not None:
+            R = R + np.asarray(r_offset, F64)
+        if np.asarray(cube[0]).ndim == 4:
+            lod = reflection_mip(roughness, float(np.uint32(view["LightsCount"][3])), control)
+            refl_l = isamp.sample_cube_array(cube, R.reshape(-1, 3), lod.reshape(-1), control).reshape(R.shape) * 10.0
+        else:
+            refl_l = cube_face_constant(cube, R) * 10.0
         refl_v = saturate(np.power(NdotV + ao, roughness * roughness) - 1.0 + ao)
         refl = refl_l * refl_v[..., None] * refl_brdf
 

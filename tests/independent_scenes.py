@@ -23,21 +23,38 @@ def _const(rgba, n=2):
 class Scene:
     """Collects draws for both the oracle and the independent evaluator (engine draw order: non-instanced first, ZE:3445-3476)."""
 
-    def __init__(self):
+    def __init__(self, cube=None):
         self.items = []
+        self.cube = cube                 # six (d, d, 4) uint8 faces, or None: FACES, one colour per 4 x 4 face
 
-    def add(self, mesh, texels=None, instances=None):
-        self.items.append({"verts": mesh[0], "idx": mesh[1], "texel": list(texels or DEFAULT_TEXELS), "instances": instances})
+    def add(self, mesh, texels=None, instances=None, images=None):
+        """texels: 7 constant RGBA8 slots (None: the engine's defaults); images: 7 entries, each None (the engine's default texel) or an
+        (h, w, 4) uint8 image, given to the renderer as it is (the statement samples the images that are not constant)"""
+        given = sampled = None
+        if images is not None:
+            given = [None if im is None else np.ascontiguousarray(im, np.uint8) for im in images]
+            texels = [DEFAULT_TEXELS[i] if im is None else tuple(int(x) for x in im[0, 0]) for i, im in enumerate(given)]
+            sampled = [None if im is None or (im == im[0, 0]).all() else im for im in given]
+        self.items.append({"verts": mesh[0], "idx": mesh[1], "texel": list(texels or DEFAULT_TEXELS), "instances": instances,
+                           "images": sampled, "given": given})
 
     def load(self, o):
-        o.set_cubemap([_const(c, 4) for c in FACES])
+        o.set_cubemap(self.cube if self.cube is not None else [_const(c, 4) for c in FACES])
         self._keep = []
         for it in self.items:
             mat = None
-            if it["texel"] != DEFAULT_TEXELS:
+            if it["given"] is not None:
+                mat, k = abi.make_material(it["given"])
+                self._keep.append(k)
+            elif it["texel"] != DEFAULT_TEXELS:
                 mat, k = abi.make_material([_const(t) for t in it["texel"]])
                 self._keep.append(k)
             o.object_add(o.mesh_create(it["verts"], it["idx"]), mat, it["instances"])
+
+    def cube_statement(self):
+        """what lighting() takes for this scene's cubemap: the face colours, or the chain of a sampled cubemap"""
+        import independent_sampler as isamp
+        return FACES if self.cube is None else isamp.cube_chain(self.cube)
 
     def draws(self):
         out, base = [], 0
@@ -217,3 +234,94 @@ def edge_odd_size():
 EDGE_SCENES = {"rolled_stage_and_light": edge_rolled_stage_and_light, "grazing_sun": edge_grazing_sun, "sun_at_zenith": edge_sun_at_zenith,
                "mirrored_instances": edge_mirrored_instances, "low_camera": edge_low_camera, "repeated_draw": edge_repeated_draw,
                "odd_size": edge_odd_size}
+
+
+# ---------------------------------------------------------------------------------------------------------------- textured scenes
+# Sampled materials and a sampled cubemap (tests/test_oracle_textured.py, tests/test_gpu_independent.py): images of noise, smooth
+# gradients and a one-texel checker; all seven slots of one power-of-two size (the renderer's packed-material form), mixed sizes with
+# non-powers of two, and materials with default and constant slots; a grazing ground plane whose UVs leave [0, 1] (REPEAT, up to 16
+# anisotropic taps, deep minification), a magnified close-up, instanced spheres whose silhouettes put helper lanes off the triangle; a
+# 32-texel noise cubemap and roughness images spanning 0.01-1, so that reflection lods 0-4 all occur.
+
+def _noise(w, h, seed, lo=0, hi=256):
+    return np.random.default_rng(seed).integers(lo, hi, (h, w, 4), dtype=np.uint8)
+
+
+def _gradient(w, h, lo=3, hi=255, seed=0):
+    """smooth: R along x, G along y, B along the diagonal, A opaque - R spans lo..hi (roughness 0.01 .. 1 for lo = 3)"""
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    fx, fy = (xx + 0.5) / w, (yy + 0.5) / h
+    img = np.stack([lo + (hi - lo) * fx, lo + (hi - lo) * fy, lo + (hi - lo) * 0.5 * (fx + fy), np.full_like(fx, 255.0)], axis=-1)
+    if seed:
+        img[..., :3] = np.roll(img[..., :3], seed, axis=-1)
+    return np.round(img).astype(np.uint8)
+
+
+def _checker(w, h, a=(250, 250, 250, 255), b=(20, 40, 60, 255), period=1):
+    yy, xx = np.mgrid[0:h, 0:w]
+    odd = ((xx // period + yy // period) & 1).astype(bool)
+    return np.where(odd[..., None], np.array(b, np.uint8), np.array(a, np.uint8)).astype(np.uint8)
+
+
+def _normal_map(w, h, seed):
+    """plausible tangent-space normals: x, y around 0, z towards the viewer"""
+    img = _noise(w, h, seed, 70, 186)
+    img[..., 2] = np.random.default_rng(seed + 1).integers(200, 256, (h, w), dtype=np.uint8)
+    img[..., 3] = 255
+    return img
+
+
+def _uv_affine(mesh, scale, offset):
+    v, idx = mesh
+    v = v.copy()
+    v["TexCoord"] = v["TexCoord"] * np.float32(scale) + np.asarray(offset, np.float32)
+    return v, idx
+
+
+def _noise_cube(d=32, seed=61):
+    return [_noise(d, d, seed + f) for f in range(6)]
+
+
+def _packed_material(seed):
+    """seven 64 x 64 images: the packed form"""
+    return [_noise(64, 64, seed), _gradient(64, 64, 0, 255, 1), _gradient(64, 64), _normal_map(64, 64, seed + 2),
+            _checker(64, 64, (255, 255, 255, 255), (90, 90, 90, 255)), _noise(64, 64, seed + 3, 0, 60), _checker(64, 64, (255, 0, 0, 255), (150, 0, 0, 255), 4)]
+
+
+def _textured_lights():
+    return _lights(1, 6)
+
+
+def tex_packed(W=192, H=128, SD=256):
+    """a grazing ground plane (UVs x 6, offset: REPEAT, N up to 16, deep minification) and textured instanced spheres"""
+    s = Scene(_noise_cube())
+    s.add(_uv_affine(scenes.grid_plane(16.0, 2, 0.0), 8.0, (-2.3, 0.7)), images=_packed_material(71))
+    s.add(_uv_affine(scenes.uv_sphere(16, 8, 0.7), 2.0, (0.25, -0.5)), None, scenes.generate_instances(10, 1.0, 5.0, 0.6, 1.2, seed=72),
+          images=_packed_material(81))
+    return Case(s, abi.make_camera((0.5, -12.0, 1.4), (0.0, 2.0, -0.4), fov=60.0), _textured_lights(), 0.0, 0.0, W, H, SD)
+
+
+def tex_mixed_sizes(W=192, H=128, SD=256):
+    """per-slot sizes 48 x 20, 33 x 7, 1 x 16, 64 x 64, 16 x 32, 128 x 4, 8 x 8: a magnified close-up of a box, a sphere and the ground"""
+    mat = [_noise(48, 20, 91), _gradient(33, 7, 0, 255, 2), _gradient(1, 16, seed=2), _normal_map(64, 64, 93), _checker(16, 32, period=2),
+           _noise(128, 4, 94, 0, 80), _checker(8, 8, (255, 0, 0, 255), (120, 0, 0, 255))]
+    s = Scene(_noise_cube(32, 95))
+    s.add(_uv_affine(scenes.grid_plane(10.0, 8, 0.0), 3.0, (0.1, 0.3)), images=mat)
+    s.add(scenes.box((0.6, 0.6, 0.6), (0.0, 0.0, 0.6)), images=mat)
+    s.add(_uv_affine(scenes.uv_sphere(16, 8, 0.5), 1.0, (0.0, 0.0)), None, scenes.generate_instances(3, 1.0, 2.5, 0.8, 1.0, seed=96), images=mat)
+    return Case(s, abi.make_camera((1.25, -1.55, 1.5), (0.0, 0.0, 0.7), fov=60.0), _textured_lights(), 0.0, 0.0, W, H, SD)
+
+
+def tex_partial(W=192, H=128, SD=256):
+    """default (None) and constant slots next to sampled ones: the renderer's per-slot path"""
+    mat = [_checker(32, 32, (230, 200, 40, 255), (40, 60, 200, 255)), None, _gradient(16, 16, 3, 255, 0), None, _const((200, 0, 0, 255), 4),
+           _noise(8, 8, 97, 0, 50), None]
+    mat2 = [None, _const((255, 0, 0, 255), 8), _noise(32, 16, 98, 3, 256), _normal_map(16, 16, 99), None, None, _const((255, 0, 0, 255), 2)]
+    s = Scene(_noise_cube(32, 101))
+    s.add(_uv_affine(scenes.grid_plane(16.0, 8, 0.0), 4.0, (-0.6, -1.4)), images=mat)
+    s.add(_uv_affine(scenes.uv_sphere(16, 8, 0.7), 3.0, (0.0, 0.0)), None, scenes.generate_instances(14, 1.0, 4.5, 0.5, 1.3, seed=102), images=mat2)
+    return Case(s, abi.make_camera((5.5, -4.0, 3.0), (0.0, 0.0, 0.3), fov=55.0), _textured_lights(), 0.0, 0.0, W, H, SD)
+
+
+TEXTURED_SCENES = {"tex_packed": tex_packed, "tex_mixed_sizes": tex_mixed_sizes, "tex_partial": tex_partial,
+                   "tex_packed_257x131": lambda: tex_packed(257, 131, 100), "tex_mixed_sizes_33x17": lambda: tex_mixed_sizes(33, 17, 64)}

@@ -12,7 +12,7 @@ import pytest
 
 import independent_eval as ie
 import independent_geometry as ig
-from independent_scenes import EDGE_SCENES, FACES, SCENES, Case, Scene, _lights, _sun_at, case
+from independent_scenes import EDGE_SCENES, FACES, SCENES, TEXTURED_SCENES, Case, Scene, _lights, _sun_at, case, tex_packed
 from zeldaengine_amd import abi, scenes
 
 pytestmark = pytest.mark.gpu
@@ -184,3 +184,84 @@ def test_second_frame_with_hiz_history_against_the_statements(gpu_engine):
     finally:
         g.close()
 
+
+
+# ---------------------------------------------------------------------------------------------------------------- sampled materials
+# The textured scenes of tests/test_oracle_textured.py on the renderer, plus one at 1280 x 720: the packed-material form (seven slots of
+# one size), the per-slot path (mixed sizes, non-powers of two, default and constant slots), the sampled resolve at odd frame sizes,
+# and the sampled cubemap in both shading modes.  The geometry statement's winners drive base_scene(), which is held to the renderer's
+# GBuffer within the derived tolerance; the lighting pass (deferred: over the renderer's GBuffer; forward: over the statement's own
+# surface) to its frame at the thresholds of tests/test_oracle_textured.py.
+
+TEXTURED_SHAPES = dict(TEXTURED_SCENES)
+TEXTURED_SHAPES["tex_packed_1280x720"] = lambda: tex_packed(1280, 720, 2048)
+TEXTURED_CAPS = {"tex_packed_1280x720": (0.067, 0.014)}        # measured 0.0441, 0.0091; headroom as in tests/test_oracle_textured.py
+_textured = {}
+
+
+def _textured_statement(name):
+    """(case, frame_uniforms, camera raster, shadow raster, base_scene over the unambiguous winners), once per shape"""
+    if name not in _textured:
+        c = TEXTURED_SHAPES[name]()
+        d, p, sp = c.lights
+        fu = ig.frame_uniforms(c.cam, d, p, c.W, c.H, c.roll_stage, c.roll_light, sp, c.scene.cube[0].shape[0])
+        draws = c.scene.draws()
+        st_cam = ig.raster(draws, fu["cam"], c.W, c.H)
+        prim = np.where(st_cam["covered"] & ~st_cam["ambiguous"], st_cam["prim"], np.uint32(0xFFFFFFFF)).astype(np.uint32)
+        mine = ie.base_scene(draws, _ubo_record(fu["cam"]), prim, c.W, c.H)
+        _textured[name] = (c, fu, st_cam, ig.raster(draws, fu["shadow"], c.SD, c.SD, shadow=True), mine)
+    return _textured[name]
+
+
+@pytest.mark.parametrize("forward", [False, True], ids=["deferred", "forward"])
+@pytest.mark.parametrize("flags", [0, NO_CULL], ids=["culled", "no_cull"])
+@pytest.mark.parametrize("name", list(TEXTURED_SHAPES))
+def test_renderer_textured_against_the_independent_statements(gpu_engine, name, flags, forward):
+    from test_oracle_textured import AMBIGUITY_CAPS as TEX_CAPS, check_lit, check_scene_pass, gbuffer_codes, _R
+    c, fu, st_cam, st_sh, mine = _textured_statement(name)
+    cap_s, cap_c = TEXTURED_CAPS.get(name) or TEX_CAPS[name]
+    W, H = c.W, c.H
+    g = gpu_engine.Renderer(W, H, c.SD, flags=flags)
+    try:
+        c.scene.load(g)
+        d, p, sp = c.lights
+        g.update_uniforms(c.cam, d, p, sp, c.roll_stage, c.roll_light, 0.0)
+        g.set_shading(forward)
+        g.render()
+        g.finish()
+        frame = g.get_frame()
+        bad = ig.check_uniforms(frame, fu, d, p)
+        assert not bad, "%s: zr_get_frame differs from UpdateUniformBuffer's: %s" % (name, bad)
+        rc, rs_ = ig.check_camera(st_cam, g.gbuffer(0)), ig.check_shadow(st_sh, g.shadowmap())
+        assert rc["ok"] and rs_["ok"], (name, rc, rs_)
+        ys, xs = mine["yx"]
+        assert len(ys) > 0.3 * st_cam["covered"].sum()
+        view, cube, smap = frame[2], c.scene.cube_statement(), g.shadowmap()
+        have = g.color().astype(np.int64)
+        assert (have[..., 3] == 255).all()
+        if not forward:
+            r = check_scene_pass(mine, gbuffer_codes(g, ys, xs))
+            d_vals, _ = ie.unpack_rgba16f(g.gbuffer(5))
+            gb = {"scene_color": ie.unpack_rgba8(g.gbuffer(1)) / 255.0, "b": ie.unpack_rgba8(g.gbuffer(3)) / 255.0, "c": ie.unpack_rgba8(g.gbuffer(4)) / 255.0,
+                  "a": ie.unpack_a2r10g10b10(g.gbuffer(2)) / np.array([1023.0, 1023.0, 1023.0, 3.0]), "d": d_vals}
+            shade = lambda eps, off: ie.unorm(ie.lighting(gb, smap, view, cube, W, H, pcf_eps=eps), 8)      # noqa: E731
+            frac, cube_amb, on_edge = check_lit(have, shade, _R(gb, smap, view, cube, c))
+            print("%s flags %d %dx%d deferred: %d pixels from the statement's winners, sampled ambiguous %.4f worst %.3f tol, normals %.5f | "
+                  "lit %.5f, cube boundary %.4f, PCF on edge %.4f" % (name, flags, W, H, len(ys), r["ambiguous"], r["worst"], r["normals"], frac, cube_amb, on_edge))
+            assert r["ok"], "%s: %d sampled GBuffer values outside the derived tolerance (worst %.3f x)" % (name, r["bad"], r["worst"])
+            assert r["normals"] >= 0.999 and r["ambiguous"] <= cap_s, (name, r)
+        else:
+            gb = {k: np.zeros((H, W, 4)) for k in ("scene_color", "a", "b", "c", "d")}
+            for k in ("scene_color", "b", "c", "d"):
+                gb[k][ys, xs] = mine[k]
+            gb["a"][ys, xs, :3] = (mine["normal"] + 1.0) / 2.0
+            unexcused = np.zeros((H, W), bool)
+            unexcused[ys[~mine["ambiguous"]], xs[~mine["ambiguous"]]] = True
+            shade = lambda eps, off: ie.unorm(ie.lighting(gb, smap, view, cube, W, H, pcf_eps=eps, forward=True, r_offset=off), 8)      # noqa: E731
+            frac, cube_amb, on_edge = check_lit(have, shade, _R(gb, smap, view, cube, c, True), unexcused, r_spread=True)
+            print("%s flags %d %dx%d forward: lit %.5f of %d pixels from the statement's winners, cube boundary %.4f, PCF on edge %.4f" % (
+                name, flags, W, H, frac, unexcused.sum(), cube_amb, on_edge))
+        assert on_edge < 0.1 and cube_amb <= cap_c, (name, on_edge, cube_amb)
+        assert frac >= 0.999, "%s lit colour: only %.4f of the pixels within one LSB" % (name, frac)
+    finally:
+        g.close()

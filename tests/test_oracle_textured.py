@@ -1,0 +1,226 @@
+"""The CPU oracle's sampled materials and reflection cubemap against the INDEPENDENT float64 statement (tests/independent_eval.py with
+tests/independent_sampler.py), on the textured scenes of tests/independent_scenes.py, deferred and forward.
+
+tests/test_oracle_independent.py holds the frame to the statement on materials that are constant per slot and a cubemap that is one
+colour per face, where no filtering choice can show.  Here every slot may be an image (noise, gradients, a one-texel checker; one
+power-of-two size, mixed sizes with non-powers of two, default and constant slots) and the cubemap is noise, so the derivatives a frame
+hands to texture(), the per-slot formats, mip selection, the anisotropic tap count and axis, REPEAT, the reflection lod and the cube
+face orientation all reach the compared codes.  The GBuffer targets that carry sampled values must lie within the range the float64
+value spans over the stated error budget plus one code (independent_eval.check_sampled_targets); pixels whose tap count or cube face a
+float32 implementation may legitimately decide otherwise are excused, and the excused fractions are capped per scene.  Each negative
+control states one sampling rule the way the engine's text rules out and must make its comparison FAIL.
+"""
+import math
+
+import numpy as np
+import pytest
+
+import independent_eval as ie
+import independent_sampler as isamp
+from independent_scenes import TEXTURED_SCENES
+
+# Caps on the excused fractions (sampled GBuffer pixels; lit pixels on a cube face boundary, deferred or forward), from the fractions measured when the test
+# was written (printed below, quoted in DESIGN.md section 6) with headroom: the larger of 1.5 x and + 0.05 %, rounded up to 0.1 %.
+AMBIGUITY_CAPS = {
+    "tex_packed": (0.031, 0.004), "tex_mixed_sizes": (0.066, 0.019), "tex_partial": (0.02, 0.02), "tex_packed_257x131": (0.029, 0.008),
+    "tex_mixed_sizes_33x17": (0.25, 0.016),
+}
+
+
+def _within_one(a, b):
+    return np.all(np.abs(a - b) <= 1, axis=-1)
+
+
+def _render(oracle_lib, c, forward=False):
+    o = oracle_lib.Oracle(c.W, c.H, c.SD)
+    c.scene.load(o)
+    d, p, sp = c.lights
+    o.update_uniforms(c.cam, d, p, sp, c.roll_stage, c.roll_light, 0.0)
+    o.set_shading(forward)
+    o.render(0)
+    return o
+
+
+def gbuffer_codes(r, ys, xs):
+    return {"scene_color": ie.unpack_rgba8(r.gbuffer(1))[ys, xs], "a": ie.unpack_a2r10g10b10(r.gbuffer(2))[ys, xs],
+            "b": ie.unpack_rgba8(r.gbuffer(3))[ys, xs], "c": ie.unpack_rgba8(r.gbuffer(4))[ys, xs]}
+
+
+def check_scene_pass(mine, got):
+    """BaseScene.frag's targets: 1, 3, 4 within the derived tolerance; the normal within one code on 99.9 % of the unexcused pixels"""
+    r = ie.check_sampled_targets(mine, got)
+    want_a = np.concatenate([ie.unorm(mine["a"][:, :3], 10), ie.unorm(mine["a"][:, 3:], 2)], axis=1)
+    ok_a = _within_one(got["a"], want_a)[~mine["ambiguous"]]
+    r["normals"] = float(ok_a.mean()) if ok_a.size else 1.0
+    return r
+
+
+R_OFFSETS = [np.eye(3)[i] * s * ie.R_ERR for i in range(3) for s in (-1.0, 1.0)]
+
+
+def check_lit(have, shade, R, mask=None, r_spread=False):
+    """the lit colour within one LSB on 99.9 % of the pixels, with the PCF ties of tests/test_oracle_independent.py; lookups on a cube
+    face boundary (ie.cube_boundary) excused.  shade(eps, r_offset) -> codes.  r_spread: also accept what R moved by ie.R_ERR along
+    each axis spans (the forward variant, whose normal is this statement's own).  -> (fraction ok, cube-excused fraction, PCF on-edge
+    fraction)"""
+    want, pcf = shade(0.0, None), [shade(-4e-7, None), shade(4e-7, None)]
+    on_edge = (pcf[0] != pcf[1]).any(axis=-1)
+    spread = pcf + ([shade(0.0, off) for off in R_OFFSETS] if r_spread else [])
+    lo, hi = np.minimum.reduce(spread + [want]) - 1, np.maximum.reduce(spread + [want]) + 1
+    moved = (lo + 1 != hi - 1).any(axis=-1)
+    ok = _within_one(have[..., :3], want) | (moved & np.all((have[..., :3] >= lo) & (have[..., :3] <= hi), axis=-1))
+    boundary = ie.cube_boundary(R)
+    sel = ~boundary if mask is None else (~boundary & mask)
+    return float(ok[sel].mean()), float(boundary[mask if mask is not None else slice(None)].mean()), float(on_edge.mean())
+
+
+def deferred(oracle_lib, c, control=None, o=None):
+    """the deferred frame: BaseScene.frag from the oracle's visibility buffer, then the lighting pass over the oracle's GBuffer"""
+    o = o or _render(oracle_lib, c)
+    mvp, _sh, view = o.get_frame()
+    mine = ie.base_scene(c.scene.draws(), mvp, o.visibility(), c.W, c.H, control=control)
+    ys, xs = mine["yx"]
+    rs = check_scene_pass(mine, gbuffer_codes(o, ys, xs))
+    d_vals, _ = ie.unpack_rgba16f(o.gbuffer(5))
+    gb = {"scene_color": ie.unpack_rgba8(o.gbuffer(1)) / 255.0, "b": ie.unpack_rgba8(o.gbuffer(3)) / 255.0, "c": ie.unpack_rgba8(o.gbuffer(4)) / 255.0,
+          "a": ie.unpack_a2r10g10b10(o.gbuffer(2)) / np.array([1023.0, 1023.0, 1023.0, 3.0]), "d": d_vals}
+    cube = c.scene.cube_statement()
+    shade = lambda eps, off: ie.unorm(ie.lighting(gb, o.shadowmap(), view, cube, c.W, c.H, pcf_eps=eps, control=control), 8)  # noqa: E731
+    lit = check_lit(o.color().astype(np.int64), shade, _R(gb, o.shadowmap(), view, cube, c))
+    return o, mine, rs, lit
+
+
+def _R(gb, smap, view, cube, c, forward=False):
+    """the direction the lighting pass samples the cubemap with"""
+    aux = {}
+    ie.lighting(gb, smap, view, cube, c.W, c.H, forward=forward, out=aux)
+    return aux["R"]
+
+
+@pytest.mark.parametrize("name", list(TEXTURED_SCENES))
+def test_oracle_textured_deferred_against_the_statement(oracle_lib, name):
+    c = TEXTURED_SCENES[name]()
+    o, mine, rs, (frac, cube_amb, on_edge) = deferred(oracle_lib, c)
+    print("%s %dx%d deferred: %d covered, sampled ambiguous %.4f worst %.3f tol, normals %.5f | lit %.5f, cube boundary %.4f, PCF on edge %.4f" % (
+        name, c.W, c.H, len(mine["yx"][0]), rs["ambiguous"], rs["worst"], rs["normals"], frac, cube_amb, on_edge))
+    assert rs["ok"], "%s: %d sampled GBuffer pixels outside the derived tolerance (worst %.3f x)" % (name, rs["bad"], rs["worst"])
+    assert rs["normals"] >= 0.999, "normals (A2R10G10B10): only %.4f within one code" % rs["normals"]
+    assert on_edge < 0.1
+    assert frac >= 0.999, "lit colour: only %.4f of the pixels within one LSB" % frac
+    cap_s, cap_c = AMBIGUITY_CAPS[name]
+    assert rs["ambiguous"] <= cap_s and cube_amb <= cap_c, (name, rs["ambiguous"], cube_amb)
+    assert (o.color()[..., 3] == 255).all()
+    if c.W * c.H >= 10000:
+        assert len(mine["yx"][0]) > 3000
+
+
+@pytest.mark.parametrize("name", list(TEXTURED_SCENES))
+def test_oracle_textured_forward_against_the_statement(oracle_lib, name):
+    """Base.frag: the statement shades its own sampled inputs (unsnapped, float64), so the sampled values' tolerance is not carried
+    into the lighting: pixels the sampled slots excuse are left out, the rest within one LSB on 99.9 %"""
+    c = TEXTURED_SCENES[name]()
+    o = _render(oracle_lib, c, forward=True)
+    mvp, _sh, view = o.get_frame()
+    prim = o.visibility()
+    mine = ie.base_scene(c.scene.draws(), mvp, prim, c.W, c.H)
+    ys, xs = mine["yx"]
+    W, H = c.W, c.H
+    gb = {k: np.zeros((H, W, 4)) for k in ("scene_color", "a", "b", "c", "d")}
+    for k in ("scene_color", "b", "c", "d"):
+        gb[k][ys, xs] = mine[k]
+    gb["a"][ys, xs, :3] = (mine["normal"] + 1.0) / 2.0          # lighting() undoes exactly this
+    cube = c.scene.cube_statement()
+    shade = lambda eps, off: ie.unorm(ie.lighting(gb, o.shadowmap(), view, cube, W, H, pcf_eps=eps, forward=True, r_offset=off), 8)  # noqa: E731
+    have = o.color().astype(np.int64)
+    covered = prim != 0xFFFFFFFF
+    assert (have[~covered] == (0, 0, 0, 255)).all()
+    unexcused = covered.copy()
+    unexcused[ys[mine["ambiguous"]], xs[mine["ambiguous"]]] = False
+    frac, cube_amb, on_edge = check_lit(have, shade, _R(gb, o.shadowmap(), view, cube, c, True), unexcused, r_spread=True)
+    print("%s %dx%d forward: lit %.5f of %d, cube boundary %.4f, PCF on edge %.4f" % (name, W, H, frac, unexcused.sum(), cube_amb, on_edge))
+    assert frac >= 0.999, "forward colour: only %.4f of the covered pixels within one LSB" % frac
+    assert cube_amb <= AMBIGUITY_CAPS[name][1] and on_edge < 0.1
+    assert (have[..., 3] == 255).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------- the statement's parts
+
+def test_vectorized_samplers_agree_with_the_scalar_forms():
+    """sample_2d_array / sample_cube_array against sample_2d / sample_cube to 1e-12, on the 600 footprints of
+    test_material_sampler_against_float64 and the directions and lods of test_cubemap_chain_and_textureLod_against_float64"""
+    for srgb in (0, 1):
+        rng = np.random.default_rng(77 + srgb)
+        img = np.random.default_rng(5 + srgb).integers(0, 256, (32, 64, 4), dtype=np.uint8)
+        chain = isamp.mip_chain(img, srgb)
+        uvs, duvs = [], []
+        for k in range(600):
+            uv = rng.uniform(-2.0, 3.0, 2)
+            scale = 2.0 ** rng.uniform(-9.0, -1.0)
+            ang = rng.uniform(0, 2 * math.pi)
+            ratio = rng.choice([1.0, 1.37, 2.4, 5.5, 11.3, 15.6, 40.0])
+            major = np.array([math.cos(ang), math.sin(ang)]) * scale
+            minor = np.array([-math.sin(ang), math.cos(ang)]) * scale / ratio
+            duv = (major[0], major[1], minor[0], minor[1]) if k % 2 else (minor[0], minor[1], major[0], major[1])
+            if k % 10 == 0:
+                t = np.float32(2.0 ** rng.uniform(-3.0, 5.0))
+                duv = (t / 64, 0.0, 0.0, t / 32)
+            uvs.append(np.asarray(uv, np.float32).astype(np.float64)); duvs.append(np.asarray(duv, np.float32).astype(np.float64))
+        val, n, lam, margin, _ = isamp.sample_2d_array(chain, srgb, np.array(uvs), np.array(duvs))
+        taps = set()
+        for k in range(600):
+            want, wn, wlam, wmargin = isamp.sample_2d(chain, srgb, uvs[k], duvs[k])
+            assert np.abs(val[k] - want).max() <= 1e-12 and n[k] == wn and abs(lam[k] - wlam) <= 1e-12 and abs(margin[k] - wmargin) <= 1e-12, k
+            taps.add(wn)
+        assert {1, 2, 3, 6, 12, 16} <= taps
+    rng = np.random.default_rng(3)
+    chain = isamp.cube_chain([rng.integers(0, 256, (32, 32, 4), dtype=np.uint8) for _ in range(6)])
+    dirs = np.array(list(rng.normal(size=(400, 3))) + [(1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1), (1, 1, 0.3), (1, 0.2, 1),
+                                                       (0.1, 1, 1), (1, 1, 1), (-1, 1, -1), (2, -2, 0.5)], np.float32).astype(np.float64)
+    for lod in (0.0, 0.37, 1.0, 2.5, 4.99, 5.0, 7.0, -1.0):
+        got = isamp.sample_cube_array(chain, dirs, np.full(len(dirs), np.float64(np.float32(lod))))
+        for k, r in enumerate(dirs):
+            assert np.abs(got[k] - isamp.sample_cube(chain, r, np.float32(lod))).max() <= 1e-12, (k, lod)
+
+
+def test_chain_builders_round_the_blits():
+    """mip_chain / cube_chain: level counts and sizes of RHIGenerateMipmaps (ZE:6887), every code the rounding of the blit"""
+    img = np.random.default_rng(9).integers(0, 256, (20, 48, 4), dtype=np.uint8)
+    for srgb in (0, 1):
+        chain = isamp.mip_chain(img, srgb)
+        assert [l.shape[:2] for l in chain] == [(20, 48), (10, 24), (5, 12), (2, 6), (1, 3), (1, 1)]
+        for l in range(1, len(chain)):
+            assert np.abs(chain[l] - isamp.blit_half_real(chain[l - 1], srgb)).max() <= 0.5 + 1e-6
+    cube = isamp.cube_chain([np.full((32, 32, 4), (10 * f, 200, 30, 255), np.uint8) for f in range(6)])
+    assert [l.shape for l in cube] == [(6, d, d, 4) for d in (32, 16, 8, 4, 2, 1)]
+    assert all((l[f] == (10 * f, 200, 30, 255)).all() for l in cube for f in range(6))
+
+
+def test_reflection_mips_reach_every_level():
+    """ComputeReflectionMipFromRoughness(r, 6) for a 32-texel cubemap: roughness 0.01 .. 1 spans lods below 0 up to 4"""
+    r = np.array([0.01, 0.1, 0.25, 0.5, 0.7, 1.0])
+    lod = ie.reflection_mip(r, 6.0)
+    assert np.allclose(lod, 5.0 - (1.0 - 1.2 * np.log2(r)))
+    assert lod[0] < 0.0 and lod[-1] == 4.0 and set(np.floor(np.clip(lod, 0, 4)).astype(int)) == {0, 1, 2, 3, 4}
+
+
+# ---------------------------------------------------------------------------------------------------------------- negative controls
+
+@pytest.mark.parametrize("control,name", [("no_aniso", "tex_packed"), ("slot0_unorm", "tex_partial"), ("srgb_space_blit", "tex_packed"),
+                                          ("clamp", "tex_packed")])
+def test_control_material_sampling(oracle_lib, control, name):
+    """anisotropy off (N = 1); slot 0 read as UNORM (its format is R8G8B8A8_SRGB, ZE:5878); the chain blitted in sRGB space (the blit
+    filters in linear light); CLAMP_TO_EDGE (the samplers REPEAT, ZE:6523-6557): each must put sampled GBuffer pixels outside the tolerance"""
+    c = TEXTURED_SCENES[name]()
+    _, _, rs, _ = deferred(oracle_lib, c, control=control)
+    print("control %s on %s:" % (control, name), rs)
+    assert not rs["ok"] and rs["bad"] > 20
+
+
+@pytest.mark.parametrize("control", ["cube_lod_max_mip", "y_faces_tc_flipped"])
+def test_control_reflection_cubemap(oracle_lib, control):
+    """the lod with cubemap_max_mip instead of cubemap_max_mip - 1 (SH/Common.glsl:197); the +-Y rows of the face table with tc negated:
+    each must move lit pixels by more than one LSB"""
+    c = TEXTURED_SCENES["tex_partial"]()
+    _, _, _, (frac, _, _) = deferred(oracle_lib, c, control=control)
+    print("control %s: lit within one LSB on %.4f" % (control, frac))
+    assert frac < 0.99
