@@ -1048,7 +1048,7 @@ static void zo_gbuffer_texel(const zo_ctx* c, int x, int y, zo_gtexel* t)
 
 static int zo_wrap(int i, int n) { int m = i % n; return m < 0 ? m + n : m; }
 
-static void zo_gbuffer_sample(const zo_ctx* c, float u, float v, zo_gtexel* out)
+static void zo_gbuffer_bilinear(const zo_ctx* c, float u, float v, zo_gtexel* out)
 {
     float x = fmaf(u, (float)c->W, -0.5f), y = fmaf(v, (float)c->H, -0.5f);
     if (!(fabsf(x) < 1.0e9f)) x = 0.0f;
@@ -1066,6 +1066,34 @@ static void zo_gbuffer_sample(const zo_ctx* c, float u, float v, zo_gtexel* out)
         float top = fmaf(ax, s10[k] - s00[k], s00[k]), bot = fmaf(ax, s11[k] - s01[k], s01[k]);
         o[k] = fmaf(ay, bot - top, top);
     }
+}
+
+/* texture() of the GBuffer attachments in GBufferVis (SH/BaseLighting.frag:47-53).  Their samplers are RHICreateSampler's defaults
+ * (ZE:6520-6560): LINEAR, REPEAT, anisotropyEnable, one mip level; the footprint is 3 / (1 - EmptyRatio) texels per pixel on each axis.
+ * CONTRACT (oracle/CONTRACT.md row 7): one bilinear tap, whatever Pmax / Pmin is.  ZO_LITERAL: the scheme zo_tex_sample applies to the
+ * material samplers, N = ceil(Pmax / Pmin) taps along the major axis - N = 2 as soon as the editor bars differ in proportion. */
+static void zo_gbuffer_sample(const zo_ctx* c, float u, float v, float ax, float by, zo_gtexel* out)
+{
+#ifdef ZO_LITERAL
+    int N, xmajor; float lambda;
+    zo_aniso_setup(ax, 0.0f, 0.0f, by, 1, &N, &lambda, &xmajor);
+    if (N > 1) {
+        float du = xmajor ? ax / (float)c->W : 0.0f, dv = xmajor ? 0.0f : by / (float)c->H;
+        float acc[20] = {0};
+        for (int i = 1; i <= N; ++i) {
+            float off = (float)i / (float)(N + 1) - 0.5f;
+            zo_gtexel s; zo_gbuffer_bilinear(c, fmaf(du, off, u), fmaf(dv, off, v), &s);
+            const float* sp = (const float*)&s;          /* the five vec4s are contiguous */
+            for (int k = 0; k < 20; ++k) acc[k] += sp[k];
+        }
+        float* op = (float*)out;
+        for (int k = 0; k < 20; ++k) op[k] = acc[k] / (float)N;
+        return;
+    }
+#else
+    (void)ax; (void)by;
+#endif
+    zo_gbuffer_bilinear(c, u, v, out);
 }
 
 static float zo_pcf(const zo_ctx* c, const float* SB, zo_v3 P, float dxy)
@@ -1098,7 +1126,7 @@ static zo_v3 zo_gbuffer_vis(const zo_ctx* c, uint32_t px, uint32_t py, zo_v3 Fin
     else if (tx < Sx * 3.0f && tx > Sx * 2.0f && ty < Sy * 3.0f && ty > Sy * 2.0f) { cell = 7; bx = 3.0f; by = 3.0f; }
     if (cell < 0) return FinalColor;
     if (tx > Sx * (bx - ERx) || ty > Sy * (by - ERy)) return zo_v3make(1.0f, 1.0f, 1.0f);
-    zo_gtexel g; zo_gbuffer_sample(c, UVx, UVy, &g);
+    zo_gtexel g; zo_gbuffer_sample(c, UVx, UVy, 3.0f / (1.0f - ERx), 3.0f / (1.0f - ERy), &g);
     zo_v3 BaseColor = zo_v3make(g.c[0], g.c[1], g.c[2]);
     float Metallic = zo_saturate(g.b[0]);
     float Roughness = fmaxf(0.01f, zo_saturate(g.b[2]));

@@ -18,7 +18,7 @@ tests/independent_sampler.py (its own mip chains, the quad's derivatives, REPEAT
 reflection cubemap either one colour per face or a chain sampled at ComputeReflectionMipFromRoughness; for sampled slots base_scene()
 also states the range the value spans over the snap and float32 error budget and which pixels' tap count is not decided
 (tests/test_oracle_textured.py).  Still unpinned on the texture side: cube seam filtering (CLAMP_TO_EDGE inside a face, a stated
-choice) and the skydome / background passes.
+choice).  The skydome and background passes are tests/independent_sky.py's; the debug views are lighting()'s switch and gbuffer_vis().
 """
 import numpy as np
 
@@ -103,6 +103,54 @@ SNAP = 1.0 / 256.0               # pixels
 GUARD = 4.0                      # the clipper's guard band, in viewports
 
 
+# the clip volume with the guard band: 0 <= z <= w, |x|, |y| <= GUARD w (the planes a clipper may cut with)
+_PLANES = [np.array(p, dtype=F64) for p in ((0, 0, 1, 0), (0, 0, -1, 1), (-1, 0, 0, GUARD), (1, 0, 0, GUARD), (0, -1, 0, GUARD),
+                                            (0, 1, 0, GUARD))]
+
+
+def clipped_altitude(tri, W, H):
+    """the smallest altitude (pixels) over every three vertices of the triangle's polygon after clipping (Sutherland-Hodgman)"""
+    poly = [p for p in tri]
+    for pl in _PLANES:
+        out = []
+        for i in range(len(poly)):
+            a, b = poly[i], poly[(i + 1) % len(poly)]
+            da, db = float(pl @ a), float(pl @ b)
+            if da >= 0:
+                out.append(a)
+            if (da >= 0) != (db >= 0):
+                out.append(a + (b - a) * (da / (da - db)))
+        poly = out
+        if len(poly) < 3:
+            return 0.0
+    sp = np.array([[(p[0] / p[3] + 1.0) * 0.5 * W, (p[1] / p[3] + 1.0) * 0.5 * H] for p in poly])
+    best = np.inf
+    n = len(sp)
+    for i in range(n):
+        for j in range(i + 1, n):
+            for k in range(j + 1, n):
+                e = [sp[j] - sp[i], sp[k] - sp[j], sp[i] - sp[k]]
+                area2 = abs(e[0][0] * e[1][1] - e[0][1] * e[1][0])
+                best = min(best, area2 / max(np.hypot(*e[m]) for m in range(3)))
+    return float(best)
+
+
+def altitudes(c3, W, H):
+    """per triangle: its smallest screen altitude, or for a clipped one the clipped polygon's (see clipped_altitude).
+    -> altitudes (T,), clipped (T,): the triangle crosses the near or far plane, w = 0 or the guard band"""
+    w = c3[..., 3]
+    clipped = np.any((w <= 0.0) | (c3[..., 2] < 0.0) | (c3[..., 2] > w) | (np.abs(c3[..., 0]) > GUARD * w) | (np.abs(c3[..., 1]) > GUARD * w), axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sp = (c3[..., :2] / w[..., None] + 1.0) * 0.5 * np.array([W, H])
+        e = [sp[:, (j + 1) % 3] - sp[:, j] for j in range(3)]
+        area2 = np.abs(e[0][:, 0] * e[1][:, 1] - e[0][:, 1] * e[1][:, 0])
+        alt = np.min([area2 / np.hypot(*ej.T) for ej in e], axis=0)
+    alt = np.where(np.isfinite(alt), alt, 0.0)
+    for k in np.nonzero(clipped)[0]:
+        alt[k] = clipped_altitude(c3[k], W, H)
+    return alt, clipped
+
+
 def _sampled_slot(chain, srgb, UV0, st1, st2, tri_uv, alt_px, control):
     """texture(sampler, UV0) with the quad's derivatives, and the range the float64 value spans over the error budget.
     -> value (k, 4), range (k, 4), ambiguous (k,): Pmax / Pmin within the derivative error of an integer below 16 (N or N + 1 taps)"""
@@ -143,9 +191,10 @@ def base_scene(draws, cam, prim_ids, W, H, control=None):
     """
     model, view, proj = mat(cam["Model"]), mat(cam["View"]), mat(cam["Proj"])
     ys, xs = np.nonzero(prim_ids != 0xFFFFFFFF)
-    out = {k: np.zeros((len(ys), n)) for k, n in (("scene_color", 4), ("a", 4), ("b", 4), ("c", 4), ("d", 4), ("d_per_pixel", 3), ("normal", 3),
+    out = {k: np.zeros((len(ys), n)) for k, n in (("scene_color", 4), ("a", 4), ("b", 4), ("c", 4), ("d", 4), ("d_per_pixel", 3), ("normal", 3), ("vertex_color", 3), ("ao_rgb", 3),
                                                    ("range_scene_color", 4), ("range_b", 4), ("range_c", 4))}
     out["ambiguous"] = np.zeros(len(ys), bool)
+    out["clipped"] = np.zeros(len(ys), bool)          # the pixel's triangle crosses the near / far plane, w = 0 or the guard band
     pid = prim_ids[ys, xs].astype(np.int64)
     for d in draws:
         n_tris = len(d["idx"]) // 3
@@ -179,6 +228,7 @@ def base_scene(draws, cam, prim_ids, W, H, control=None):
                 return (np.einsum("ki,kij->kj", l, wp[corner]), np.einsum("ki,kij->kj", l, wn[corner]), np.einsum("ki,kij->kj", l, uv[corner]))
             px, py = xs[m].astype(F64), ys[m].astype(F64)
             P0, N0, UV0 = varyings(px, py)
+            out["vertex_color"][m] = np.einsum("ki,kij->kj", weights(px, py), np.asarray(d["verts"]["Color"], dtype=F64)[corner])
             # dFdx / dFdy: differences inside the 2x2 quad, the partner invocation extrapolating THIS triangle (helper lane)
             sx, sy = np.where(xs[m] & 1, 1.0, -1.0), np.where(ys[m] & 1, 1.0, -1.0)
             Ph, _, UVh = varyings(px - sx, py)
@@ -190,14 +240,12 @@ def base_scene(draws, cam, prim_ids, W, H, control=None):
             if control != "slot0_unorm":
                 smp[:, 0, :3] = srgb_to_linear(tex[0, :3])          # sampler1 is R8G8B8A8_SRGB (ZE:5878); the others UNORM
             if any(c is not None for c in chains):
-                w = c3[..., 3]
-                clipped = np.any((w <= 0.0) | (c3[..., 2] < 0.0) | (np.abs(c3[..., 0]) > GUARD * w) | (np.abs(c3[..., 1]) > GUARD * w), axis=1)
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    sp = (c3[..., :2] / w[..., None] + 1.0) * 0.5 * np.array([W, H])               # (k, 3, 2) screen positions
-                    e = [sp[:, (j + 1) % 3] - sp[:, j] for j in range(3)]
-                    area2 = np.abs(e[0][:, 0] * e[1][:, 1] - e[0][:, 1] * e[1][:, 0])
-                    alt = np.min([area2 / np.hypot(*ej.T) for ej in e], axis=0)                  # smallest altitude, pixels
-                alt = np.where(clipped | ~np.isfinite(alt), 0.0, alt)          # clipped: the clipper's re-snapped vertices are its own
+                # the smallest altitude of the triangle, or of the polygon the clipper leaves of it (its re-snapped vertices move the
+                # interpolation plane as the snap moves a triangle's): a clipped triangle is no longer excused as a whole
+                ut, inv = np.unique(t, return_inverse=True)
+                alt, cut = altitudes(clip[np.asarray(d["idx"], dtype=np.int64).reshape(-1, 3)[ut]], W, H)
+                alt = alt[inv.reshape(-1)]
+                out["clipped"][m] = cut[inv.reshape(-1)]
                 for i, ch in enumerate(chains):
                     if ch is not None:
                         smp[:, i], rng[:, i], amb = _sampled_slot(ch, i == 0 and control != "slot0_unorm", UV0, st1, st2, uv[corner], alt, control)
@@ -209,6 +257,7 @@ def base_scene(draws, cam, prim_ids, W, H, control=None):
             out["scene_color"][m] = np.hstack([emissive, mask[:, None]])
             out["a"][m] = np.hstack([packed, np.ones((k, 1))])
             out["normal"][m] = normal                                       # ComputeNormal()'s result as Base.frag uses it (forward variant)
+            out["ao_rgb"][m] = smp[:, 4, :3]                                # Base.frag's AmbientOcclution.rgb (its debug view 5)
             out["b"][m] = np.stack([metallic, np.ones(k), np.maximum(0.01, rough), np.ones(k)], axis=1)
             out["c"][m] = np.hstack([base_color, ao[:, None]])
             out["d"][m] = np.hstack([P0, np.ones((k, 1))])
@@ -338,35 +387,8 @@ def cube_boundary(R):
     return (a[..., 2] - a[..., 1]) <= 2.0 * R_ERR
 
 
-def lighting(gb, shadow_map, view, cube, W, H, pcf_eps=0.0, forward=False, control=None, out=None, r_offset=None):
-    """BaseLighting.frag:147-227 + case 0 of the switch for every pixel of the W x H quad.
-    forward=True: Base.frag:46-123 instead - the same text except that N is used as ComputeNormal() returned it, AO is not saturated,
-    there is no Mask, and case 0 shows FinalColor * ShadowFactor (after the gamma); gb then holds the fragment's unquantised inputs.
-
-    gb: dict scene_color / a / b / c (float RGBA as texture() returns them) and d (fp16 values), each (H, W, 4); view: XkView record
-    cube: the six face colours of a cubemap whose faces are each ONE colour (no filter or lod choice matters), or the cubemap's mip
-    chain (independent_sampler.cube_chain): textureLod at ComputeReflectionMipFromRoughness(Roughness, SKY_MAXMIPS), SKY_MAXMIPS =
-    view.LightsCount[3].  control: "cube_lod_max_mip" or one of independent_sampler's (negative controls).  out: a dict that receives
-    R (the reflected direction the cubemap is sampled with).  r_offset: a vector added to R before the cubemap lookup (a caller that
-    wants to know what R's own error does evaluates with offsets of that size, as with pcf_eps)
-    pcf_eps: added to the reference depth of the 25 shadow comparisons - the shader's one discontinuity: a caller that wants to know
-    which pixels sit on it evaluates with +-eps and looks at the spread
-    -> (H, W, 3) float colour before the UNORM store
-    """
-    PI = 3.14159265359
-    base_color = gb["c"][..., :3]
-    metallic = saturate(gb["b"][..., 0])
-    roughness = np.maximum(0.01, saturate(gb["b"][..., 2]))
-    normal = gb["a"][..., :3] * 2.0 - 1.0
-    ao = gb["c"][..., 3] if forward else saturate(gb["c"][..., 3])
-    mask = gb["scene_color"][..., 3]
-    N = normal if forward else normalize(normal)
-    P = gb["d"][..., :3]
-    cam = np.asarray(view["CameraInfo"], dtype=F64)[:3]
-    V = normalize(cam - P)
-    NdotV = saturate(dot(N, V))
-
-    # ComputeShadowCoord + ComputePCF(sampler, ShadowCoord / ShadowCoord.w, 2), SH/Common.glsl:294-342
+def pcf(P, shadow_map, view, pcf_eps=0.0):
+    """ComputeShadowCoord + ComputePCF(sampler, ShadowCoord / ShadowCoord.w, 2), SH/Common.glsl:294-342, at the positions P (..., 3)"""
     bias = np.array([[0.5, 0, 0, 0.5], [0, 0.5, 0, 0.5], [0, 0, 1, 0], [0, 0, 0, 1]], dtype=F64)      # BiasMat (columns as written in the GLSL)
     SB = bias @ mat(view["ShadowmapSpace"])
     with np.errstate(invalid="ignore", divide="ignore"):
@@ -382,7 +404,96 @@ def lighting(gb, shadow_map, view, cube, W, H, pcf_eps=0.0, forward=False, contr
                 dist = texture_linear_clamp(shadow_map.astype(F64), sc[..., 0] + dx * x, sc[..., 1] + dx * y)
                 f = np.where(inside & (sc[..., 3] > 0.0) & (dist < sc[..., 2] + pcf_eps), 0.1, f)
                 total += f
-        shadow = total / 25.0
+        return total / 25.0
+
+
+def refract_view(N, P, view):
+    """refract(V, normalize(N), 1.00 / 1.52) with V = normalize(cameraInfo.xyz - P)"""
+    V = normalize(np.asarray(view["CameraInfo"], dtype=F64)[:3] - P)
+    eta = 1.00 / 1.52
+    with np.errstate(invalid="ignore", divide="ignore"):
+        Nn = normalize(N)
+        dNI = dot(Nn, V)
+        k = 1.0 - eta * eta * (1.0 - dNI * dNI)
+        return np.where((k < 0.0)[..., None], 0.0, eta * V - (eta * dNI + np.sqrt(np.maximum(k, 0.0)))[..., None] * Nn)
+
+
+def quad_vertex_colour(W, H):
+    """fragColor of the lighting quad (debug view 6): Background.vert's six vertices (two triangles, colours red / blue / green and
+    red / green / blue) drawn at w = 1, interpolated with the barycentrics of each pixel centre in the triangle that contains it"""
+    pos = np.array([(-1.0, -1.0), (-1.0, 1.0), (1.0, 1.0), (-1.0, -1.0), (1.0, 1.0), (1.0, -1.0)])
+    col = np.array([(1.0, 0.0, 0.0), (0.0, 0.0, 1.0), (0.0, 1.0, 0.0), (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0)])
+    yy, xx = np.mgrid[0:H, 0:W].astype(F64)
+    X, Y = (xx + 0.5) / W * 2.0 - 1.0, (yy + 0.5) / H * 2.0 - 1.0
+    out = np.zeros((H, W, 3))
+    done = np.zeros((H, W), bool)
+    for t in (0, 1):
+        p, c = pos[3 * t:3 * t + 3], col[3 * t:3 * t + 3]
+        A = np.array([[p[0, 0], p[1, 0], p[2, 0]], [p[0, 1], p[1, 1], p[2, 1]], [1.0, 1.0, 1.0]])
+        lam = np.einsum("ij,jhw->ihw", np.linalg.inv(A), np.stack([X, Y, np.ones_like(X)]))
+        inside = np.all(lam >= -1e-12, axis=0) & ~done
+        out[inside] = np.einsum("ihw,ic->hwc", lam, c)[inside]
+        done |= inside
+    return out
+
+
+# ----------------------------------------------------------------------------------------------- comparisons of lit frames
+
+def _within_one(a, b):
+    return np.all(np.abs(a - b) <= 1, axis=-1)
+
+
+R_OFFSETS = [np.eye(3)[i] * s * R_ERR for i in range(3) for s in (-1.0, 1.0)]
+
+
+def check_lit(have, shade, R, mask=None, r_spread=False):
+    """the lit colour within one LSB on 99.9 % of the pixels, with the PCF ties of tests/test_oracle_independent.py; lookups on a cube
+    face boundary (cube_boundary) excused.  shade(eps, r_offset) -> codes.  r_spread: also accept what R moved by ie.R_ERR along
+    each axis spans (the forward variant, whose normal is this statement's own).  -> (fraction ok, cube-excused fraction, PCF on-edge
+    fraction)"""
+    want, pcf = shade(0.0, None), [shade(-4e-7, None), shade(4e-7, None)]
+    on_edge = (pcf[0] != pcf[1]).any(axis=-1)
+    spread = pcf + ([shade(0.0, off) for off in R_OFFSETS] if r_spread else [])
+    lo, hi = np.minimum.reduce(spread + [want]) - 1, np.maximum.reduce(spread + [want]) + 1
+    moved = (lo + 1 != hi - 1).any(axis=-1)
+    ok = _within_one(have[..., :3], want) | (moved & np.all((have[..., :3] >= lo) & (have[..., :3] <= hi), axis=-1))
+    boundary = cube_boundary(R)
+    sel = ~boundary if mask is None else (~boundary & mask)
+    return float(ok[sel].mean()), float(boundary[mask if mask is not None else slice(None)].mean()), float(on_edge.mean())
+
+
+def lighting(gb, shadow_map, view, cube, W, H, pcf_eps=0.0, forward=False, control=None, out=None, r_offset=None, debug_view=0):
+    """BaseLighting.frag:147-254 for every pixel of the W x H quad, the switch on SPEC_CONSTANTS included (debug_view).
+    forward=True: Base.frag:46-123 instead - the same text except that N is used as ComputeNormal() returned it, AO is not saturated,
+    there is no Mask, and case 0 shows FinalColor * ShadowFactor (after the gamma); gb then holds the fragment's unquantised inputs.
+
+    gb: dict scene_color / a / b / c (float RGBA as texture() returns them) and d (fp16 values), each (H, W, 4); view: XkView record
+    cube: the six face colours of a cubemap whose faces are each ONE colour (no filter or lod choice matters), or the cubemap's mip
+    chain (independent_sampler.cube_chain): textureLod at ComputeReflectionMipFromRoughness(Roughness, SKY_MAXMIPS), SKY_MAXMIPS =
+    view.LightsCount[3].  control: "cube_lod_max_mip" or one of independent_sampler's (negative controls).  out: a dict that receives
+    R (the reflected direction the cubemap is sampled with).  r_offset: a vector added to R before the cubemap lookup (a caller that
+    wants to know what R's own error does evaluates with offsets of that size, as with pcf_eps)
+    pcf_eps: added to the reference depth of the 25 shadow comparisons - the shader's one discontinuity: a caller that wants to know
+    which pixels sit on it evaluates with +-eps and looks at the spread
+    debug_view: 0-8 and >= 10 (the default case, FinalColor * ShadowFactor); view 9 is gbuffer_vis()'s, which this calls with
+    FinalColor.  Forward: Base.frag:123-143's own table (base colour without gamma, AmbientOcclution.rgb = gb["ao_rgb"], the
+    interpolated vertex colour gb["vertex_color"], and case 9 = the default).
+    -> (H, W, 3) float colour before the UNORM store
+    """
+    PI = 3.14159265359
+    base_color = gb["c"][..., :3]
+    metallic = saturate(gb["b"][..., 0])
+    roughness = np.maximum(0.01, saturate(gb["b"][..., 2]))
+    normal = gb["a"][..., :3] * 2.0 - 1.0
+    ao = gb["c"][..., 3] if forward else saturate(gb["c"][..., 3])
+    mask = gb["scene_color"][..., 3]
+    N = normal if forward else normalize(normal)
+    P = gb["d"][..., :3]
+    cam = np.asarray(view["CameraInfo"], dtype=F64)[:3]
+    V = normalize(cam - P)
+    NdotV = saturate(dot(N, V))
+
+    shadow = pcf(P, shadow_map, view, pcf_eps)
 
     direct = np.zeros(P.shape)
     diffuse_color = base_color * (1.0 - metallic)[..., None]
@@ -438,8 +549,114 @@ def lighting(gb, shadow_map, view, cube, W, H, pcf_eps=0.0, forward=False, contr
         refl = refl_l * refl_v[..., None] * refl_brdf
 
         if forward:
-            final = np.power(direct + indirect + refl, 0.4545) * shadow[..., None]
+            final = np.power(direct + indirect + refl, 0.4545)
         else:
             final = (direct + indirect + refl) * mask[..., None]
             final = np.power(final, 0.4545)
-    return final
+    v3 = lambda x: np.repeat(np.asarray(x)[..., None], 3, axis=-1)      # noqa: E731  vec3(float)
+    if forward:                                                         # Base.frag:123-143
+        table = {1: base_color, 2: v3(metallic), 3: v3(roughness), 4: normal, 7: refl, 8: v3(shadow),
+                 5: gb["ao_rgb"] if debug_view == 5 else None, 6: gb["vertex_color"] if debug_view == 6 else None}
+        return table[debug_view] if debug_view in table else final * shadow[..., None]
+    table = {0: final, 2: v3(metallic), 3: v3(roughness), 4: normal, 5: v3(ao), 7: refl, 8: v3(shadow)}       # BaseLighting.frag:228-253
+    if debug_view in table:
+        return table[debug_view]
+    if debug_view == 1:
+        return np.power(base_color, 0.4545)
+    if debug_view == 6:
+        return quad_vertex_colour(W, H)
+    if debug_view == 9:
+        return gbuffer_vis(gb, shadow_map, view, cube, W, H, final)["colour"]
+    return final * shadow[..., None]
+
+
+# ----------------------------------------------------------------------------------------------- BaseLighting.frag: GBufferVis
+
+U32 = 2.0 ** -24
+# The mosaic's thresholds: fragTexCoord = (x + 1/2) / W is one correctly rounded division; Step = (1 - zw / xy) / 3 and Step * (k - EmptyRatio)
+# are at most five float32 roundings of quantities below 4: a pixel whose fragTexCoord lies within 8u of a threshold is not decided.
+THRESHOLD_ULPS = 8.0
+# The re-sampling position: UV = fragTexCoord * 3 / (1 - EmptyRatio) carries <= 4u of |UV|; bilinear weights are an implementation's
+# sub-texel precision (this build: 8 bits, Vulkan's subTexelPrecisionBits), i.e. the position moves by up to 1/512 texel.
+SUBTEXEL = 1.0 / 512.0
+
+
+def gbuffer_vis(gb, shadow_map, view, cube, W, H, final, control=None, pcf_eps=4e-7, aniso=True):
+    """GBufferVis(FinalColor), SH/BaseLighting.frag:42-145, word for word, for every pixel of the W x H quad.
+
+    gb: the GBuffer as texture() sees its texels (lighting()'s dict: scene_color / a / b / c float, d fp16 values, (H, W, 4)).  The
+    attachments are re-sampled with RHICreateSampler's state (ZE:6520-6560): LINEAR, REPEAT, anisotropyEnable with the device's
+    maxAnisotropy, one mip level - through independent_sampler's scheme, N = ceil(Pmax / Pmin) taps along the major axis, the
+    footprint 3 / (1 - EmptyRatio) texels per pixel on each axis.  aniso=False: one bilinear tap (oracle/CONTRACT.md row 7).
+    final: FinalColor (H, W, 3).  control: "mosaic_no_aniso" or "cell6_step_y" (Step.y * 3 in the sixth cell: the shader has Step.x).
+    -> dict: colour (H, W, 3), tol (H, W, 3) (the span over the error budget: sub-texel position, PCF ties), cell (H, W) (0-7 the
+    branch, 8 its white frame, -1 FinalColor), excused (H, W) (fragTexCoord on a threshold, a refraction on a cube face boundary)
+    """
+    vi = np.asarray(view["ViewportInfo"], dtype=F64)
+    ERx, ERy = vi[2] / vi[0], vi[3] / vi[1]
+    yy, xx = np.mgrid[0:H, 0:W].astype(F64)
+    tx, ty = (xx + 0.5) / W, (yy + 0.5) / H
+    Sx, Sy = (1.0 - ERx) / 3.0, (1.0 - ERy) / 3.0
+    s6 = Sy if control == "cell6_step_y" else Sx
+    branches = [((tx < Sx) & (ty < Sy), 1, 1), ((tx < Sx * 2) & (ty < Sy), 2, 1), ((tx < Sx * 3) & (ty < Sy), 3, 1),
+                ((tx < Sx) & (ty < Sy * 2), 1, 2), ((tx < 1.0) & (ty < Sy * 2) & (tx > Sx * 2), 3, 2),
+                ((tx < Sx) & (ty < s6 * 3), 1, 3),                                          # the shader's own `Step.x * 3.0f`
+                ((tx < Sx * 2) & (tx > Sx) & (ty < Sy * 3) & (ty > Sy * 2), 2, 3),
+                ((tx < Sx * 3) & (tx > Sx * 2) & (ty < Sy * 3) & (ty > Sy * 2), 3, 3)]
+    cell = np.full((H, W), -1)
+    for k, (cond, bx, by) in enumerate(branches):
+        new = cond & (cell == -1)
+        cell[new] = k
+        cell[new & ((tx > Sx * (bx - ERx)) | (ty > Sy * (by - ERy)))] = 8
+    thr_x = [Sx, Sx * 2, Sx * 3, 1.0] + [Sx * (k - ERx) for k in (1, 2, 3)]
+    thr_y = [Sy, Sy * 2, Sy * 3, Sx * 3] + [Sy * (k - ERy) for k in (1, 2, 3)]
+    excused = np.zeros((H, W), bool)
+    for thr, t in ((thr_x, tx), (thr_y, ty)):
+        for v in thr:
+            excused |= np.abs(t - v) <= THRESHOLD_ULPS * U32
+    colour, tol = np.array(final, dtype=F64), np.zeros((H, W, 3))
+    colour[cell == 8] = 1.0
+    colour[cell == 5] = 0.0
+    ys, xs = np.nonzero((cell >= 0) & (cell <= 7) & (cell != 5))
+    k = len(ys)
+    if not k:
+        return {"colour": colour, "tol": tol, "cell": cell, "excused": excused}
+    UV = np.stack([tx[ys, xs] * 3.0 / (1.0 - ERx), ty[ys, xs] * 3.0 / (1.0 - ERy)], axis=1)
+    duv = np.broadcast_to([3.0 / (1.0 - ERx) / W, 0.0, 0.0, 3.0 / (1.0 - ERy) / H], (k, 4))
+    no_aniso = control == "mosaic_no_aniso" or not aniso
+    shift = (SUBTEXEL + 4.0 * U32 * np.abs(UV) * np.array([W, H])) / np.array([W, H])
+    c_k = cell[ys, xs]
+
+    def evaluate(uv, eps):
+        t = {n: isamp.sample_2d_array([gb[n]], 0, uv, duv, "no_aniso" if no_aniso else None, [np.asarray(gb[n], F64)])[0]
+             for n in ("scene_color", "a", "b", "c", "d")}
+        N = normalize(t["a"][:, :3] * 2.0 - 1.0)
+        P = t["d"][:, :3]
+        out = np.zeros((k, 3))
+        sel = lambda c: c_k == c                                                      # noqa: E731
+        out[sel(0)] = np.power(np.maximum(t["c"][:, :3], 0.0), 0.4545)[sel(0)]
+        out[sel(1)] = saturate(t["b"][:, 0:1])[sel(1)]
+        out[sel(2)] = np.maximum(0.01, saturate(t["b"][:, 2:3]))[sel(2)]
+        out[sel(3)] = N[sel(3)]
+        out[sel(4)] = saturate(t["c"][:, 3:4])[sel(4)]
+        R = refract_view(N, P, view)
+        if np.any(sel(6)):
+            if np.asarray(cube[0]).ndim == 4:
+                L = isamp.sample_cube_array(cube, R[sel(6)], np.zeros(int(sel(6).sum())))
+            else:
+                L = cube_face_constant(cube, R[sel(6)])
+            out[sel(6)] = L * 10.0
+        if np.any(sel(7)):
+            out[sel(7)] = pcf(P[sel(7)], shadow_map, view, eps)[:, None]
+        return out, R
+    mid, R = evaluate(UV, 0.0)
+    lo, hi = mid.copy(), mid.copy()
+    for su, sv in ((1, 1), (1, -1), (-1, 1), (-1, -1)):
+        v = evaluate(UV + shift * (su, sv), 0.0)[0]
+        lo, hi = np.minimum(lo, v), np.maximum(hi, v)
+    for eps in (-pcf_eps, pcf_eps):
+        v = evaluate(UV, eps)[0]
+        lo, hi = np.minimum(lo, v), np.maximum(hi, v)
+    colour[ys, xs], tol[ys, xs] = mid, hi - lo
+    excused[ys, xs] |= (c_k == 6) & cube_boundary(R)
+    return {"colour": colour, "tol": tol, "cell": cell, "excused": excused}

@@ -307,12 +307,16 @@ def _boxes(tris, x0, x1, y0, y1, budget=1 << 19):
             yield np.array([t]), np.array([x0[t]]), np.array([ys]), w_, min(rows, int(y1[t]) - ys + 1)
 
 
-def raster(draws, ubo, W, H, shadow=False, slope=7.5, depth_op="less"):
+def raster(draws, ubo, W, H, shadow=False, slope=7.5, depth_op="less", cull="back", start=None):
     """Rasterise the whole frame in float64.
 
     draws: independent_scenes.Scene.draws(); ubo: frame_uniforms(...)["cam"] or ["shadow"] (W = H = the map size for the shadow pass)
-    slope / depth_op: the statement's depth-bias slope factor and the camera pass's compare op ("less" or "less_equal"); anything but
-    7.5 / "less" is a deliberately wrong statement for the negative controls.
+    slope / depth_op / cull: the statement's depth-bias slope factor, the camera pass's compare op ("less" or "less_equal") and cull mode
+    ("back" or "front"); anything but 7.5 / "less" / "back" is a deliberately wrong statement for the negative controls.
+    start: None (the depth clear 1.0), or a depth buffer the draws are tested against and written over, as a later pass of the same
+    render pass sees it (the skydome against the copied deferred depth): {"depth", "tol", "ambiguous"} (H, W), e.g. an earlier raster().
+    Its values act as fragments drawn before every primitive (they keep a tie under LESS), and its ambiguous pixels stay ambiguous;
+    "prim" is 0xFFFFFFFF and "covered" False where such a value still wins.
     -> {"depth": (H, W) the winner's depth (camera) or the biased map value (shadow), 1.0 where nothing is drawn,
         "tol": (H, W) its tolerance, "prim": (H, W) winning primitive id, 0xFFFFFFFF for none (camera pass),
         "covered": (H, W), "ambiguous": (H, W) bool}
@@ -327,7 +331,7 @@ def raster(draws, ubo, W, H, shadow=False, slope=7.5, depth_op="less"):
     facing_unsure = np.zeros(T, dtype=bool)
     if not shadow:
         facing_unsure = ok & (np.abs(det) <= ddet)
-        ok &= (det < 0) | facing_unsure
+        ok &= ((det > 0) if cull == "front" else (det < 0)) | facing_unsure
         # an exact repeat of an earlier triangle (same clip coordinates: the same float32 inputs through the same matrices) ties
         # EXACTLY in any arithmetic: under LESS it never wins and adds no doubt; under LESS_OR_EQUAL the last repeat wins
         if T:
@@ -341,6 +345,15 @@ def raster(draws, ubo, W, H, shadow=False, slope=7.5, depth_op="less"):
     pix = f["pix"].astype(np.int64)
     z, tol, certain = f["z"], f["tol"], f["certain"].astype(bool)
     prim = ids[f["tri"].astype(np.int64)] if len(pix) else np.zeros(0, dtype=np.int64)
+    if start is not None:
+        # the starting depth buffer as certain fragments with primitive id -1: first in draw order, so they keep a tie under LESS
+        d0 = np.asarray(start["depth"], dtype=F64).reshape(-1)
+        s_pix = np.nonzero(d0 < 1.0)[0]
+        pix = np.concatenate([pix, s_pix])
+        z = np.concatenate([z, d0[s_pix]])
+        tol = np.concatenate([tol, np.asarray(start["tol"], dtype=F64).reshape(-1)[s_pix]])
+        certain = np.concatenate([certain, np.ones(len(s_pix), dtype=bool)])
+        prim = np.concatenate([prim, np.full(len(s_pix), -1, dtype=np.int64)])
     # the nearest certain fragment per pixel (ties: the first drawn under LESS, the last under LESS_OR_EQUAL)
     c = np.nonzero(certain)[0]
     order = c[np.lexsort((prim[c] if depth_op == "less" else -prim[c], z[c], pix[c]))]
@@ -370,6 +383,10 @@ def raster(draws, ubo, W, H, shadow=False, slope=7.5, depth_op="less"):
             amb |= lowest < depth + dtol
     if not shadow:
         covered &= depth < 1.0
+    if start is not None:
+        amb |= np.asarray(start["ambiguous"], dtype=bool).reshape(-1)
+        covered &= win >= 0
+        win[win < 0] = 0xFFFFFFFF
     return {"depth": depth.reshape(H, W), "tol": dtol.reshape(H, W), "prim": win.reshape(H, W).astype(np.uint32),
             "covered": covered.reshape(H, W), "ambiguous": amb.reshape(H, W)}
 

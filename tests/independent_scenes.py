@@ -323,5 +323,69 @@ def tex_partial(W=192, H=128, SD=256):
     return Case(s, abi.make_camera((5.5, -4.0, 3.0), (0.0, 0.0, 0.3), fov=55.0), _textured_lights(), 0.0, 0.0, W, H, SD)
 
 
-TEXTURED_SCENES = {"tex_packed": tex_packed, "tex_mixed_sizes": tex_mixed_sizes, "tex_partial": tex_partial,
+def tex_clipped(W=192, H=128, SD=256):
+    """a coarse 40-unit ground plane (two triangles a side) under a camera 0.3 above it, znear 0.05: every visible ground triangle
+    crosses the near plane, so its sampled slots are held to the clipped polygon's budget, not excused"""
+    s = Scene(_noise_cube(32, 103))
+    s.add(_uv_affine(scenes.grid_plane(40.0, 2, 0.0), 10.0, (0.3, -0.2)), images=_packed_material(104))
+    s.add(_uv_affine(scenes.uv_sphere(16, 8, 0.7), 2.0, (0.0, 0.0)), None, scenes.generate_instances(6, 1.0, 4.0, 0.6, 1.2, seed=105),
+          images=_packed_material(106))
+    return Case(s, abi.make_camera((0.4, -0.3, 0.3), (6.0, 4.0, 0.0), fov=70.0, znear=0.05, zfar=80.0), _textured_lights(), 0.0, 0.0, W, H, SD)
+
+
+TEXTURED_SCENES = {"tex_clipped": tex_clipped, "tex_packed": tex_packed, "tex_mixed_sizes": tex_mixed_sizes, "tex_partial": tex_partial,
                    "tex_packed_257x131": lambda: tex_packed(257, 131, 100), "tex_mixed_sizes_33x17": lambda: tex_mixed_sizes(33, 17, 64)}
+
+
+# ---------------------------------------------------------------------------------------------------------------- skydome and background
+# The skydome and background passes (tests/test_oracle_sky.py, tests/test_gpu_independent.py): the dome of scenes.sky_dome() and a coarse
+# 16 x 8 one whose visible triangles straddle the camera's plane (the near plane cuts them), a zFar that cuts the dome, a rolled stage,
+# a camera looking near the pole (the longitude lines converge: large, anisotropic derivatives, N clamps at 16), noise and NPOT sky
+# images (a smooth gradient would not tell one lod from another), background images magnified on one axis and minified on the other.
+# The sizes: 192 x 128, 257 x 131, 33 x 17, 64 x 64 (pixel centres on the diagonal of the lighting quad, view 6) and 200 x 120 with
+# unequal editor bars (view 9's mosaic, ViewportInfo.zw = 37, 21).
+
+SkyCase = collections.namedtuple("SkyCase", "case sky sky_image background bars")
+
+
+def _sky_case(W, H, SD=128, cam=None, roll=0.0, dome=None, sky_image=None, background=None, bars=(0.0, 0.0), no_dome=False):
+    s, cam0, lights, _ = scene_mixed()
+    return SkyCase(Case(s, cam or cam0, lights, roll, 0.0, W, H, SD), None if no_dome else dome if dome is not None else scenes.sky_dome(),
+                   sky_image if sky_image is not None else _noise(256, 128, 111), background, bars)
+
+
+def sky_dome_noise(W=192, H=128):
+    """the engine's dome stand-in with a noise sky; zFar 26 cuts it where it is farthest (the background shows there); the background
+    minified in x, magnified in y"""
+    return _sky_case(W, H, cam=abi.make_camera((6.0, 5.0, 2.0), (0.0, 0.0, 1.5), zfar=26.0), background=_noise(410, 40, 112))
+
+
+def sky_coarse_clipped(W=192, H=128):
+    """a 16 x 8 dome (8-unit triangles), the camera 2.5 from its wall looking along it: the triangles around the camera straddle its
+    plane, and the near plane cuts half of what is visible"""
+    return _sky_case(W, H, cam=abi.make_camera((18.0, 0.0, 3.0), (18.0, 10.0, 5.0), fov=90.0, znear=0.1, zfar=100.0),
+                     dome=scenes.sky_dome(20.48, 16, 8), sky_image=_noise(128, 64, 113), background=_noise(40, 300, 114))
+
+
+def sky_rolled_npot(W=192, H=128):
+    """the stage rolled by 0.6 (the dome's Model), an NPOT 200 x 75 sky, no background"""
+    return _sky_case(W, H, cam=abi.make_camera((5.0, 4.0, 3.5), (0.0, 0.0, 0.4), zfar=100.0), roll=0.6, sky_image=_noise(200, 75, 115))
+
+
+def sky_pole(W=192, H=128):
+    """a camera looking almost straight up at the pole: the longitude lines converge, derivatives large and anisotropic; with a wide
+    1024 x 48 sky (u spans 1024 texels, v 48) Pmax / Pmin reaches 57 and exceeds 16 on ~9 % of the dome's pixels, where N clamps"""
+    return _sky_case(W, H, cam=abi.make_camera((0.5, 0.3, 2.0), (0.52, 0.35, 12.0), fov=70.0, zfar=100.0), sky_image=_noise(1024, 48, 116),
+                     background=_noise(64, 64, 117))
+
+
+def background_only(W=192, H=128):
+    """no dome: the background behind the scene on every empty pixel, its right and bottom columns included (REPEAT wraps the
+    bilinear footprint there); 410 x 40 texels: minified in x, magnified in y"""
+    return _sky_case(W, H, background=_noise(410, 40, 118), no_dome=True)
+
+
+SKY_SCENES = {"background_only": background_only, "sky_dome_noise": sky_dome_noise, "sky_coarse_clipped": sky_coarse_clipped, "sky_rolled_npot": sky_rolled_npot, "sky_pole": sky_pole,
+              "sky_dome_257x131": lambda: sky_dome_noise(257, 131), "sky_coarse_33x17": lambda: sky_coarse_clipped(33, 17),
+              "sky_rolled_64x64": lambda: sky_rolled_npot(64, 64),
+              "sky_bars_200x120": lambda: sky_dome_noise(200, 120)._replace(bars=(37.0, 21.0))}

@@ -12,7 +12,9 @@ import pytest
 
 import independent_eval as ie
 import independent_geometry as ig
-from independent_scenes import EDGE_SCENES, FACES, SCENES, TEXTURED_SCENES, Case, Scene, _lights, _sun_at, case, tex_packed
+import independent_sky as isky
+from independent_scenes import EDGE_SCENES, FACES, SCENES, SKY_SCENES, TEXTURED_SCENES, Case, Scene, _lights, _sun_at, case, sky_dome_noise, tex_packed
+from independent_sky_checks import SKY_CAPS, VIEW_SCENES, check_frame, forward_surface, gbuffer_of, load, statement
 from zeldaengine_amd import abi, scenes
 
 pytestmark = pytest.mark.gpu
@@ -265,3 +267,126 @@ def test_renderer_textured_against_the_independent_statements(gpu_engine, name, 
         assert frac >= 0.999, "%s lit colour: only %.4f of the pixels within one LSB" % (name, frac)
     finally:
         g.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- skydome, background, debug views
+# The scenes of tests/test_oracle_sky.py on the renderer, plus the dome at 1280 x 720: k_sky_tiles and the background in view 0, the view
+# switch of k_lighting / k_forward and k_gbuffer_vis in views 1-10, held to tests/independent_sky.py and independent_eval's switch from
+# the geometry statement's winners and depth - never through the oracle.  With every cull on and every cull off, deferred and forward;
+# then the rank contexts of a 3-rank tile partition (k_sky_tiles walks the rank's owned tiles), and a queued sequence that toggles the
+# dome and the background across frames in flight (the overlay plane is kept per GBuffer parity).
+
+SKY_SHAPES = dict(SKY_SCENES)
+SKY_SHAPES["sky_dome_1280x720"] = lambda: sky_dome_noise(1280, 720)
+SKY_GPU_CAPS = {"sky_dome_1280x720": 0.048}        # measured 0.0318; headroom as in independent_sky_checks.SKY_CAPS
+
+
+def _sky_render(gpu_engine, c, flags, forward, views):
+    """-> {view: (H, W, 4) codes}, the renderer's GBuffer dict (deferred) or None, its shadow map and XkView, the uniforms check"""
+    k = c.case
+    g = gpu_engine.Renderer(k.W, k.H, k.SD, flags=flags)
+    try:
+        load(g, c, forward)
+        out = {}
+        for v in views:
+            g.render(v)
+            g.finish()
+            out[v] = g.color().astype(np.int64).copy()
+        return out, (None if forward else gbuffer_of(g)), g.shadowmap().copy(), g.get_frame(), g.gbuffer(0).copy()
+    finally:
+        g.close()
+
+
+@pytest.mark.parametrize("forward", [False, True], ids=["deferred", "forward"])
+@pytest.mark.parametrize("flags", [0, NO_CULL], ids=["culled", "no_cull"])
+@pytest.mark.parametrize("name", list(SKY_SHAPES))
+def test_renderer_sky_and_views_against_the_independent_statements(gpu_engine, name, flags, forward):
+    c = SKY_SHAPES[name]()
+    k = c.case
+    fu, st, sky, bg = statement(name, c)
+    views = list(range(11)) if name in VIEW_SCENES else [0]
+    frames, gb, smap, frame, depth = _sky_render(gpu_engine, c, flags, forward, views)
+    d, p, _sp = k.lights
+    if not any(c.bars):
+        bad = ig.check_uniforms(frame, fu, d, p)
+        assert not bad, "%s: zr_get_frame differs from UpdateUniformBuffer's: %s" % (name, bad)
+    rc = ig.check_camera(st, depth)
+    assert rc["ok"], (name, rc)
+    view = frame[2]
+    covered = excused = None
+    if forward:
+        prim = np.where(st["covered"] & ~st["ambiguous"], st["prim"], np.uint32(0xFFFFFFFF)).astype(np.uint32)
+        gb, excused = forward_surface(c, prim, _ubo_record(fu["cam"]))
+        covered, excused = st["covered"], excused | st["ambiguous"]
+    for v in views:
+        r = check_frame(frames[v], c, gb, smap, view, v, forward, sky, bg, covered, excused, aniso=False)
+        print(name, "flags", flags, "forward" if forward else "deferred", "view", v, {key: r[key] for key in r if key != "ok"})
+        assert r["ok"], (name, v, r)
+        if v == 0:
+            assert r["sky_excused"] <= SKY_GPU_CAPS.get(name, SKY_CAPS.get(name, 0.0)), (name, r["sky_excused"])
+
+
+@pytest.mark.parametrize("forward", [False, True], ids=["deferred", "forward"])
+def test_renderer_sky_on_tile_partitioned_ranks(gpu_engine, forward):
+    """three rank contexts of a tile partition: each rank's packed tiles, assembled, hold the dome and the background of the statement"""
+    from zeldaengine_amd import dist as zdist
+    name = "sky_dome_257x131"
+    c = SKY_SHAPES[name]()
+    k = c.case
+    _fu, _st, sky, bg = statement(name, c)
+    tiles = []
+    for r in range(3):
+        g = gpu_engine.Renderer(k.W, k.H, k.SD, tile_rank=r, tile_world=3)
+        try:
+            load(g, c, forward)
+            g.render()
+            g.render()
+            g.finish()
+            tiles.append(np.asarray(g.read_tiles()).copy())
+        finally:
+            g.close()
+    have = zdist.untile(np.stack(tiles), k.W, k.H).astype(np.int64)
+    colour, tol, overlay, amb = isky.compose(np.zeros((k.H, k.W, 3)), sky, bg, 0)
+    r = isky.check_overlay(have, colour, tol, overlay, amb)
+    print(name, "3 ranks", "forward" if forward else "deferred", r)
+    assert r["ok"] and r["n"] > 0.4 * k.W * k.H, r
+
+
+def test_queued_frames_toggle_the_dome_and_the_background(gpu_engine):
+    """frames enqueued back to back, each copied out on the device in stream order, while the dome and the background are switched on
+    and off: every frame's sky / background pixels against the statement of ITS flags, and every other pixel the lit frame"""
+    import torch
+    name = "sky_dome_noise"
+    c = SKY_SHAPES[name]()
+    k = c.case
+    W, H = k.W, k.H
+    _fu, st, sky, bg = statement(name, c)
+    bg_alone = isky.background(c.background, st, W, H)
+    flags_seq = [(1, 1), (0, 1), (1, 0), (0, 0), (1, 1), (1, 1), (0, 0), (1, 0), (0, 1), (1, 1), (0, 0), (0, 1)]
+    g = gpu_engine.Renderer(W, H, k.SD)
+    dev = torch.device("cuda", 0)
+    col = [torch.zeros(W * H, dtype=torch.int32, device=dev) for _ in flags_seq]
+    sha = [torch.zeros(k.SD * k.SD, dtype=torch.int32, device=dev) for _ in flags_seq]
+    try:
+        load(g, c)
+        g.set_sky_flags(False, False)
+        g.render()
+        g.finish()
+        lit = g.color().astype(np.int64).copy()
+        torch.cuda.synchronize()
+        for i, (s_on, b_on) in enumerate(flags_seq):
+            g.set_sky_flags(bool(s_on), bool(b_on))
+            g.render()
+            g.copy_frame_async(col[i].data_ptr(), sha[i].data_ptr())
+        g.finish()
+    finally:
+        g.close()
+    for i, (s_on, b_on) in enumerate(flags_seq):
+        have = col[i].cpu().numpy().view(np.uint8).reshape(H, W, 4).astype(np.int64)
+        colour, tol, overlay, amb = isky.compose(np.zeros((H, W, 3)), sky if s_on else None, (bg if s_on else bg_alone) if b_on else None, 0)
+        r = isky.check_overlay(have, colour, tol, overlay, amb)
+        rest = ~overlay & ~amb
+        stale = int((have[rest] != lit[rest]).any(axis=-1).sum())
+        print("queued frame %d sky %d background %d:" % (i, s_on, b_on), r, "non-overlay pixels off the lit frame:", stale)
+        assert r["ok"] and stale == 0, (i, s_on, b_on, r, stale)
+        assert r["n"] > (0.3 * W * H if s_on or b_on else -1)
