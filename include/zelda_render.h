@@ -37,7 +37,7 @@ extern "C" {
 
 /* Version of this header's structs and entry points.  A host checks zr_abi_version() == ZR_ABI_VERSION after loading the library
  * (INTEGRATION.md); structs that may grow (zr_stats) are passed with their size as the caller knows it and only ever grow at the end. */
-#define ZR_ABI_VERSION 6u
+#define ZR_ABI_VERSION 7u
 
 #ifndef ZR_TILE
 #define ZR_TILE 32            /* screen tile edge in pixels (raster + multi-GPU partition unit); 32 or 64 */
@@ -229,6 +229,43 @@ int  zr_read_shadowmap(zr_ctx* ctx, float* dst, size_t bytes);        /* dim*dim
  * stream order, without synchronising the host: the copies run behind that frame's lighting pass and ahead of anything the next
  * zr_render puts on the render stream - what a presenting host with two frames in flight uses instead of zr_read_color. */
 int  zr_copy_frame_async(zr_ctx* ctx, void* color_dev, void* shadow_dev);
+
+/* --- object identity of the last frame (which object won each pixel: picking, box selection, per-instance coverage) ---
+ * What is reported is the deferred-scene pass's depth-test winner, i.e. what the GBuffer holds: the same in deferred and forward
+ * shading and in every debug view.  The skydome and the background are not objects: they never appear and never hide a scene winner.
+ * Every query describes the frame enqueued last (as zr_read_gbuffer).  The synchronous ones call zr_finish first and pass its error on
+ * (an overflowed frame: ZR_ERR_OVERFLOW).  ZR_ERR_STATE when no frame has been rendered, when the last frame was rendered without
+ * capture, when the scene changed after it (zr_object_add, zr_scene_clear, a world load) with no frame since, or between the stages of
+ * a frame.  A rank context (tile_world > 1) reports its owned tiles only: pixels of other ranks' tiles read as none.
+ * Summed over all slots, zr_instance_coverage equals zr_stats.covered_pixels. */
+/* Keep the deferred-scene pass's per-pixel winner, from the next frame on; default off (one 4-byte store per pixel and frame).
+ * Between the stages of a frame: ZR_ERR_STATE (as zr_set_shading). */
+int  zr_set_id_capture(zr_ctx* ctx, int enable);
+
+#define ZR_IDS_PRIMITIVE 0  /* W*H*4: global draw-order primitive id (non-instanced draws first, then instanced; per draw
+                               instance * triangles + triangle), 0xFFFFFFFF = none */
+#define ZR_IDS_OBJECT    1  /* W*H*8: {object, instance} per pixel; object = add order (as zr_object_get_instances),
+                               instance = 0 for a non-instanced draw; {0xFFFFFFFF, 0xFFFFFFFF} = none */
+int  zr_read_ids(zr_ctx* ctx, int kind, void* dst, size_t bytes);
+
+typedef struct zr_hit {          /* 32 bytes */
+    uint32_t object, instance;   /* as ZR_IDS_OBJECT */
+    uint32_t pixels;             /* pixels of the rectangle this instance won */
+    uint32_t triangle;           /* primitive id within the instance at the nearest pixel */
+    uint32_t x, y;               /* the nearest pixel: least depth, ties to the least y*W + x */
+    float    depth;              /* its D32F depth (GBuffer target 0) */
+    uint32_t reserved;           /* 0 */
+} zr_hit;
+/* Distinct (object, instance) winners in the rectangle, clipped to the frame.  Sorted by depth, then object, then instance.
+ * *n = the total count; min(*n, cap) entries are written.  w == 0 or h == 0: ZR_ERR_ARG.  w = h = 1 is a point pick. */
+int  zr_pick(zr_ctx* ctx, uint32_t x, uint32_t y, uint32_t w, uint32_t h, zr_hit* hits, uint32_t cap, uint32_t* n);
+
+/* Pixels each instance won in the last frame.  One uint32 per instance slot: objects in add order, then their instances in order;
+ * a non-instanced draw has one slot.  bytes = 4 * sum over objects of max(1, instances). */
+int  zr_instance_coverage(zr_ctx* ctx, uint32_t* counts, size_t bytes);
+/* The same counts into a caller-owned DEVICE buffer, stream-ordered on the render stream behind the frame enqueued last, with no host
+ * sync (the pattern of zr_copy_frame_async).  The frame after next, which reuses that frame's winner plane, waits for it. */
+int  zr_instance_coverage_async(zr_ctx* ctx, void* counts_dev, size_t bytes);
 
 /* --- multi-GPU screen-tile partition --- */
 /* Owner of tile (tx, ty) in a world of `world` ranks, and the list of tiles a rank owns in increasing tile index (= its slot order

@@ -7,6 +7,9 @@
 //
 //   zelda_headless --root DIR [--world FILE.json] [--livelink PORT [--wait-ms MS]] [--meshlet FILE.meshlet --profab NAME]
 //                  [--size WxH] [--shadow N] [--frames N] [--roll-light-step F] [--debug-view V] [--out FRAME.ppm] [--device D]
+//                  [--pick X,Y[,W,H]]
+// --pick keeps the last frame's per-pixel winners (zr_set_id_capture) and prints what zr_pick finds in the rectangle (default 1 x 1),
+// one JSON line per hit, nearest first - what an editor does on a click.
 #include "../include/zelda_render.h"
 
 #include <chrono>
@@ -30,6 +33,7 @@ int main(int argc, char** argv)
     uint32_t W = 1920, H = 1080, SD = 1024, frames = 1, debug_view = 0;
     int port = -1, wait_ms = 10000, device = 0;
     float roll_step = 0.0f;
+    bool pick = false; uint32_t px = 0, py = 0, pw = 1, ph = 1;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
@@ -46,6 +50,11 @@ int main(int argc, char** argv)
         else if (a == "--wait-ms") wait_ms = atoi(next());
         else if (a == "--device") device = atoi(next());
         else if (a == "--roll-light-step") roll_step = (float)atof(next());
+        else if (a == "--pick") {
+            const int got = sscanf(next(), "%u,%u,%u,%u", &px, &py, &pw, &ph);
+            if (got != 2 && got != 4) { fprintf(stderr, "--pick X,Y[,W,H]\n"); return 2; }
+            pick = true;
+        }
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     zr_config cfg; memset(&cfg, 0, sizeof cfg);
@@ -76,6 +85,7 @@ int main(int argc, char** argv)
     }
     if (!have_world) { fprintf(stderr, "zelda_headless: no world (give --world FILE or send one to --livelink PORT)\n"); zr_destroy(c); return 1; }
 
+    if (pick && (rc = zr_set_id_capture(c, 1))) return fail(c, "zr_set_id_capture", rc);
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t f = 0; f < frames; ++f) {
         int reloaded = 0;
@@ -90,6 +100,15 @@ int main(int argc, char** argv)
     uint32_t n_obj = 0; zr_object_count(c, &n_obj);
     printf("frames %u  %.3f ms/frame  objects %u  meshlet-instances %llu  camera survivors %llu  covered pixels %llu\n", frames, ms / frames, n_obj,
            (unsigned long long)st.work_items[1], (unsigned long long)st.survivors[1], (unsigned long long)st.covered_pixels);
+    if (pick) {
+        uint32_t n = 0;
+        if ((rc = zr_pick(c, px, py, pw, ph, nullptr, 0, &n))) return fail(c, "zr_pick", rc);
+        std::vector<zr_hit> hits(n);
+        if (n && (rc = zr_pick(c, px, py, pw, ph, hits.data(), n, &n))) return fail(c, "zr_pick", rc);
+        for (const zr_hit& h : hits)
+            printf("{\"object\": %u, \"instance\": %u, \"pixels\": %u, \"triangle\": %u, \"x\": %u, \"y\": %u, \"depth\": %.9g}\n",
+                   h.object, h.instance, h.pixels, h.triangle, h.x, h.y, (double)h.depth);
+    }
     if (!out.empty()) {
         std::vector<uint8_t> rgba((size_t)W * H * 4);
         if ((rc = zr_read_color(c, rgba.data(), rgba.size()))) return fail(c, "zr_read_color", rc);

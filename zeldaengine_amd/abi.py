@@ -58,7 +58,23 @@ class Stats(C.Structure):
                 ("hiz_culled_geom", C.c_uint32), ("struct_bytes", C.c_uint32)]
 
 
-ABI_VERSION = 6      # ZR_ABI_VERSION of include/zelda_render.h
+ABI_VERSION = 7      # ZR_ABI_VERSION of include/zelda_render.h
+
+# object identity of the last frame (zr_read_ids / zr_pick)
+IDS_PRIMITIVE = 0     # ZR_IDS_PRIMITIVE: (H, W) uint32 global draw-order primitive id, 0xFFFFFFFF = none
+IDS_OBJECT = 1        # ZR_IDS_OBJECT: (H, W, 2) uint32 {object (add order), instance}, all ones = none
+NO_ID = 0xFFFFFFFF
+Hit = np.dtype([("object", "<u4"), ("instance", "<u4"), ("pixels", "<u4"), ("triangle", "<u4"), ("x", "<u4"), ("y", "<u4"),
+                ("depth", "<f4"), ("reserved", "<u4")])
+
+
+class HitC(C.Structure):
+    """ctypes mirror of zr_hit (the same 32 bytes as Hit)"""
+    _fields_ = [("object", C.c_uint32), ("instance", C.c_uint32), ("pixels", C.c_uint32), ("triangle", C.c_uint32),
+                ("x", C.c_uint32), ("y", C.c_uint32), ("depth", C.c_float), ("reserved", C.c_uint32)]
+
+
+assert Hit.itemsize == 32 and C.sizeof(HitC) == 32
 
 
 PASS_NAMES = ["cull_shadow", "shadow", "cull_camera", "gbuffer", "hiz", "gbuffer2", "resolve", "lighting", "composite", "total"]

@@ -10,6 +10,7 @@
 #include <thread>
 #include <vector>
 
+#include "zr_ids.h"
 #include "zr_meshlet.h"
 #include "zr_types.h"
 
@@ -150,6 +151,16 @@ struct zr_ctx {
     // (k_scan), so it does not wait for the camera lane's k_frame_begin, and the camera lane does not wait for it.
     ZrDevStats* d_sstats = nullptr; uint32_t list_rebuild_mask = 0;
     uint64_t last_work[2] = { 0, 0 };
+
+    // object identity of the last frame (zr_set_id_capture, zr_ids.hip).  The winner planes are d_prim_b, shared with the forward variant.
+    bool id_capture = false;             // the next frames keep their winner plane (Gb[i].prim set)
+    bool ids_frame = false, ids_this = false;      // the frame enqueued last kept it / the frame being enqueued does
+    uint64_t scene_gen = 0, ids_gen = 0, ids_table_gen = ~0ull;      // objects added or cleared; the scene of the last frame / of the table
+    ZrIdsDraw* d_ids_draws = nullptr; uint32_t ids_n_draws = 0, ids_n_slots = 0, ids_slot_cap = 0;
+    uint32_t *d_ids_counts = nullptr, *d_ids_cov = nullptr, *d_ids_list = nullptr, *d_ids_n = nullptr;
+    unsigned long long* d_ids_keys = nullptr; zr_hit* d_ids_hits = nullptr; uint2* d_ids_obj = nullptr;
+    // a census enqueued against copy i (zr_instance_coverage_async): the frame that writes copy i next waits for it
+    hipEvent_t ev_ids[2] = { nullptr, nullptr }; bool ids_wait[2] = { false, false };
 
     std::vector<uint8_t*> d_cube; CubeDesc cube = {}; uint32_t cube_dim = 0, cube_levels = 0;
     float lut[256]; float* d_lut = nullptr;

@@ -7,6 +7,7 @@
 #include "zr_ctx.h"
 #include "zr_math.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstddef>
@@ -103,6 +104,7 @@ extern "C" int zr_create(const zr_config* cfg, zr_ctx** out)
     c->stream = c->own_stream;
     for (auto& fr : c->evr) for (auto& e : fr) ok &= hipEventCreate(&e) == hipSuccess;
     for (auto& e : c->ev_end) ok &= hipEventCreate(&e) == hipSuccess;
+    for (auto& e : c->ev_ids) ok &= hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
     const size_t n = (size_t)c->W * c->H;
     for (int b = 0; b < 2; ++b) {       // two frames in flight: see zr_ctx.h
         GBufferPtrs& G = c->Gb[b];
@@ -288,7 +290,7 @@ static void free_tri_bins(zr_ctx* c)
 static void free_scene(zr_ctx* c)
 {
     for (auto& o : c->objects) { dev_free(o.d_inst); for (auto& t : o.d_tex) dev_free(t); }
-    c->objects.clear();
+    c->objects.clear(); c->scene_gen++;
     for (auto& m : c->meshes) {
         dev_free(m.d_v); dev_free(m.d_rv); dev_free(m.d_rt); dev_free(m.d_idx); dev_free(m.d_meshlets); dev_free(m.d_mpos); dev_free(m.d_mbox); dev_free(m.d_mtri); dev_free(m.d_tri_meshlet);
     }
@@ -330,6 +332,9 @@ extern "C" void zr_destroy(zr_ctx* c)
     free_tri_bins(c);
     for (auto& fr : c->evr) for (auto& e : fr) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->ev_end) if (e) (void)hipEventDestroy(e);
+    for (auto& e : c->ev_ids) if (e) (void)hipEventDestroy(e);
+    dev_free(c->d_ids_draws); dev_free(c->d_ids_counts); dev_free(c->d_ids_cov); dev_free(c->d_ids_list); dev_free(c->d_ids_n);
+    dev_free(c->d_ids_keys); dev_free(c->d_ids_hits); dev_free(c->d_ids_obj);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
@@ -629,7 +634,7 @@ int zr_object_add_internal(zr_ctx* c, uint32_t mesh_id, const ZrMaterialHost& ma
     dev_free(d_raw);
     if (e != hipSuccess) { cleanup(); return zr_fail(c, ZR_ERR_DEVICE, hipGetErrorString(e)); }
     c->objects.push_back(std::move(o));
-    c->scene_dirty = true;
+    c->scene_dirty = true; c->scene_gen++;
     return ZR_OK;
 }
 
@@ -1098,7 +1103,7 @@ static int zr_set_shading_impl(zr_ctx* c, uint32_t mode)
             HIPCHK(c, hipMemset(c->d_prim_b[b], 0xFF, n * 4));
             HIPCHK(c, hipDeviceSynchronize());      // (a null-stream fill; the frames run on non-blocking streams)
         }
-        c->Gb[b].prim = mode == ZR_SHADING_FORWARD ? c->d_prim_b[b] : nullptr;
+        c->Gb[b].prim = (mode == ZR_SHADING_FORWARD || c->id_capture) ? c->d_prim_b[b] : nullptr;      // (id capture: zr_set_id_capture)
     }
     c->shading = mode;
     return ZR_OK;
@@ -1250,6 +1255,46 @@ static inline float* shadow_buf(zr_ctx* c) { return c->d_shadow_ext ? c->d_shado
 //   zr_render_gbuffer   deferred-scene pass (ZE:3417-3480): cull + bin + raster + resolve of the owned tiles
 //   zr_render_lighting  deferred-lighting pass (ZE:3531-3540) [+ skydome / background overlay]
 // zr_render = all three.
+// Object identity (zr_set_id_capture): the census's draw table - draw order, as finalize_scene numbers primitives, with each draw's add-order
+// object index and first instance slot - and the per-slot arrays of the queries.  Built at the start of a captured frame, when the
+// scene's objects changed since.
+static int ids_prepare(zr_ctx* c)
+{
+    if (c->ids_table_gen == c->scene_gen && c->d_ids_draws) return ZR_OK;
+    std::vector<uint32_t> slot_base(c->objects.size());
+    uint32_t slots = 0;
+    for (size_t i = 0; i < c->objects.size(); ++i) { slot_base[i] = slots; slots += c->objects[i].n_inst; }
+    std::vector<ZrIdsDraw> tab;
+    uint32_t prim = 0;
+    for (int pass = 0; pass < 2; ++pass)                 // the draw order of finalize_scene (ZE:3445-3476)
+        for (size_t i = 0; i < c->objects.size(); ++i) {
+            const ZrSceneObject& o = c->objects[i];
+            if ((int)o.instanced != pass) continue;
+            const uint32_t nt = (uint32_t)(c->meshes[o.mesh].idx.size() / 3);
+            tab.push_back({ prim, nt ? nt : 1u, (uint32_t)i, slot_base[i] });
+            prim += nt * o.n_inst;
+        }
+    tab.push_back({ prim, 1u, 0xFFFFFFFFu, slots });     // sentinel: the end of the last draw
+    HIPCHK(c, zr_sync_all(c));                           // (queries of an earlier scene may still read the old table)
+    dev_free(c->d_ids_draws);
+    HIPCHK(c, upload(&c->d_ids_draws, tab));
+    c->ids_n_draws = (uint32_t)tab.size() - 1u;
+    c->ids_n_slots = slots;
+    if (slots > c->ids_slot_cap || !c->d_ids_counts) {
+        dev_free(c->d_ids_counts); dev_free(c->d_ids_cov); dev_free(c->d_ids_list); dev_free(c->d_ids_n); dev_free(c->d_ids_keys); dev_free(c->d_ids_hits);
+        c->ids_slot_cap = 0;
+        const size_t cap = std::max<uint32_t>(slots, 1u);
+        HIPCHK(c, dev_alloc(&c->d_ids_counts, cap)); HIPCHK(c, dev_alloc(&c->d_ids_cov, cap)); HIPCHK(c, dev_alloc(&c->d_ids_list, cap));
+        HIPCHK(c, dev_alloc(&c->d_ids_n, 1)); HIPCHK(c, dev_alloc(&c->d_ids_keys, cap)); HIPCHK(c, dev_alloc(&c->d_ids_hits, cap));
+        // between queries: counts 0, keys all ones, no listed slot (k_id_hits restores this after every pick)
+        HIPCHK(c, hipMemset(c->d_ids_counts, 0, cap * 4)); HIPCHK(c, hipMemset(c->d_ids_keys, 0xFF, cap * 8)); HIPCHK(c, hipMemset(c->d_ids_n, 0, 4));
+        HIPCHK(c, hipDeviceSynchronize());      // (null-stream fills; the frames and queries run on non-blocking streams)
+        c->ids_slot_cap = (uint32_t)cap;
+    }
+    c->ids_table_gen = c->scene_gen;
+    return ZR_OK;
+}
+
 // Start of a frame on stream s: pick this frame's copies of the double-buffered resources, make s wait until the lighting pass
 // that last read them (two frames ago) and the previous frame's shadow pipeline (it shares d_stats) are done, reset the
 // statistics, upload the uniforms if this copy does not hold them yet.
@@ -1263,11 +1308,15 @@ static int frame_begin(zr_ctx* c, hipStream_t s)
     int rc = finalize_scene(c);
     if (rc) return rc;
     if (c->view.LightsCount[3] != (int32_t)c->cube_levels) { c->view.LightsCount[3] = (int32_t)c->cube_levels; c->view_dirty = true; }
+    c->ids_frame = false; c->ids_this = c->id_capture;      // (the frame enqueued last is about to be this one)
+    if (c->id_capture) { rc = ids_prepare(c); if (rc) return rc; }
     const int par = (int)(c->frame_no & 1u);
     c->G = c->Gb[par]; c->d_shadow = c->d_shadow_b[par]; c->d_view = c->d_view_b[par]; c->d_empty_rgba = c->d_empty_b[par];
     // (two lanes: this frame's copies of the double-buffered resources were last read by the lighting pass of two frames ago, on the
     // host's stream.  Nothing else ties the lanes together here: the shadow pipeline keeps statistics of its own)
     if (s != c->stream && c->frame_no >= 2) HIPCHK(c, hipStreamWaitEvent(s, c->ev_end[(c->frame_no - 2) % zr_ctx::END_RING], 0));
+    // ... and by an identity census enqueued against them since (zr_instance_coverage_async, on the host's stream)
+    if (c->ids_wait[par]) { if (s != c->stream) HIPCHK(c, hipStreamWaitEvent(s, c->ev_ids[par], 0)); c->ids_wait[par] = false; }
     c->timing_now = c->timing_interval != 0 && c->frame_no % c->timing_interval == 0;     // pass events cost ~6 us of stream bubble each
     hipEvent_t* ev = c->timing_now ? c->evr[c->sample_no % zr_ctx::EV_RING] : nullptr;
     if (ev) HIPCHK(c, hipEventRecord(ev[0], s));
@@ -1552,6 +1601,7 @@ static int lighting_pass(zr_ctx* c, hipStream_t s)
     HIPCHK(c, hipGetLastError());
     if (c->timing_now) c->sample_no++;
     c->rendered = true; c->frame_no++; c->stage = 0;
+    c->ids_frame = c->ids_this; c->ids_gen = c->scene_gen;
     return ZR_OK;
 }
 
@@ -1877,6 +1927,146 @@ extern "C" int zr_copy_frame_async(zr_ctx* c, void* color_dev, void* shadow_dev)
     HIPCHK(c, hipSetDevice(c->device));
     if (color_dev) HIPCHK(c, hipMemcpyAsync(color_dev, c->d_color, (size_t)c->W * c->H * 4, hipMemcpyDeviceToDevice, c->stream));
     if (shadow_dev) HIPCHK(c, hipMemcpyAsync(shadow_dev, shadow_buf(c), (size_t)c->SD * c->SD * 4, hipMemcpyDeviceToDevice, c->stream));
+    return ZR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ object identity (zelda_render.h)
+
+static int zr_set_id_capture_impl(zr_ctx* c, int enable)
+{
+    if (!c) return ZR_ERR_ARG;
+    if (c->stage != 0) return zr_fail(c, ZR_ERR_STATE, "zr_set_id_capture between the stages of a frame");
+    const bool on = enable != 0;
+    if (on == c->id_capture) return ZR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = (size_t)c->W * c->H;
+    for (int b = 0; b < 2; ++b) {
+        if (on && !c->d_prim_b[b]) {             // the forward variant's planes, allocated as zr_set_shading does
+            if (dev_alloc(&c->d_prim_b[b], n) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "zr_set_id_capture: out of device memory");
+            HIPCHK(c, hipMemset(c->d_prim_b[b], 0xFF, n * 4));      // (pixels of other ranks' tiles stay "none")
+            HIPCHK(c, hipDeviceSynchronize());
+        }
+        c->Gb[b].prim = (on || c->shading == ZR_SHADING_FORWARD) ? c->d_prim_b[b] : nullptr;
+    }
+    c->id_capture = on;
+    return ZR_OK;
+}
+extern "C" int zr_set_id_capture(zr_ctx* c, int enable)
+{
+    return zr_guard(c, [&]() { return zr_set_id_capture_impl(c, enable); });
+}
+
+// The frame enqueued last kept its winners and still describes the scene; `sync`: finish it first (its overflow is the query's error).
+static int ids_ready(zr_ctx* c, const char* what, bool sync)
+{
+    if (!c->rendered || c->stage != 0) return zr_fail(c, ZR_ERR_STATE, std::string(what) + ": no finished frame enqueued");
+    if (!c->ids_frame) return zr_fail(c, ZR_ERR_STATE, std::string(what) + ": the last frame was rendered without id capture (zr_set_id_capture)");
+    if (c->ids_gen != c->scene_gen) return zr_fail(c, ZR_ERR_STATE, std::string(what) + ": the scene changed after the last frame");
+    HIPCHK(c, hipSetDevice(c->device));
+    return sync ? zr_finish(c) : ZR_OK;
+}
+static ZrIdsArgs ids_args(zr_ctx* c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h)
+{
+    const int last = (int)((c->frame_no - 1u) & 1u);          // the copy the frame enqueued last wrote
+    ZrIdsArgs A; memset(&A, 0, sizeof A);
+    A.prim = c->d_prim_b[last]; A.depth = c->Gb[last].depth;
+    A.draws = c->d_ids_draws; A.n_draws = c->ids_n_draws;
+    A.W = c->W; A.x0 = x0; A.y0 = y0; A.w = w; A.h = h;
+    A.counts = c->d_ids_counts; A.keys = c->d_ids_keys; A.hit_list = c->d_ids_list; A.n_hits = c->d_ids_n;
+    return A;
+}
+
+extern "C" int zr_read_ids(zr_ctx* c, int kind, void* dst, size_t bytes)
+{
+    if (!c) return ZR_ERR_ARG;
+    ARGCHK(c, dst && (kind == ZR_IDS_PRIMITIVE || kind == ZR_IDS_OBJECT));
+    ARGCHK(c, bytes == (size_t)c->W * c->H * (kind == ZR_IDS_OBJECT ? 8 : 4));
+    int rc = ids_ready(c, "zr_read_ids", true);
+    if (rc) return rc;
+    const ZrIdsArgs A0 = ids_args(c, 0, 0, c->W, c->H);
+    if (kind == ZR_IDS_PRIMITIVE) { HIPCHK(c, hipMemcpy(dst, A0.prim, bytes, hipMemcpyDeviceToHost)); return ZR_OK; }
+    if (!c->d_ids_obj) HIPCHK(c, dev_alloc(&c->d_ids_obj, (size_t)c->W * c->H));
+    ZrIdsArgs A = A0; A.obj_plane = c->d_ids_obj;
+    zr_launch_id_census(A, ZR_IDS_OBJECTS, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(dst, c->d_ids_obj, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZR_OK;
+}
+
+static int zr_pick_impl(zr_ctx* c, uint32_t x, uint32_t y, uint32_t w, uint32_t h, zr_hit* hits, uint32_t cap, uint32_t* n)
+{
+    if (!c) return ZR_ERR_ARG;
+    ARGCHK(c, n && w > 0 && h > 0 && (hits || cap == 0));
+    *n = 0;
+    int rc = ids_ready(c, "zr_pick", true);
+    if (rc) return rc;
+    if (x >= c->W || y >= c->H) return ZR_OK;                  // wholly outside the frame
+    ZrIdsArgs A = ids_args(c, x, y, std::min(w, c->W - x), std::min(h, c->H - y));
+    zr_launch_id_census(A, ZR_IDS_PICK, c->stream);
+    HIPCHK(c, hipGetLastError());
+    uint32_t total = 0;
+    HIPCHK(c, hipMemcpyAsync(&total, c->d_ids_n, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (total > c->ids_n_slots) return zr_fail(c, ZR_ERR_DEVICE, "zr_pick: hit list longer than the slot count");
+    std::vector<zr_hit> all(total);
+    zr_launch_id_hits(A, total, c->d_ids_hits, c->stream);       // (also clears the listed slots)
+    HIPCHK(c, hipGetLastError());
+    if (total) HIPCHK(c, hipMemcpyAsync(all.data(), c->d_ids_hits, sizeof(zr_hit) * total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_ids_n, 0, 4, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::sort(all.begin(), all.end(), [](const zr_hit& a, const zr_hit& b) {
+        if (a.depth != b.depth) return a.depth < b.depth;
+        if (a.object != b.object) return a.object < b.object;
+        return a.instance < b.instance;
+    });
+    if (total) memcpy(hits, all.data(), sizeof(zr_hit) * std::min(total, cap));
+    *n = total;
+    return ZR_OK;
+}
+extern "C" int zr_pick(zr_ctx* c, uint32_t x, uint32_t y, uint32_t w, uint32_t h, zr_hit* hits, uint32_t cap, uint32_t* n)
+{
+    return zr_guard(c, [&]() { return zr_pick_impl(c, x, y, w, h, hits, cap, n); });
+}
+
+static size_t ids_slot_bytes(const zr_ctx* c)
+{
+    size_t slots = 0;
+    for (const auto& o : c->objects) slots += o.n_inst;      // (n_inst = max(1, instances))
+    return 4 * slots;
+}
+// The whole-frame census into a count array on the device (cleared first), on the host's stream.
+static int ids_coverage(zr_ctx* c, uint32_t* counts_dev, size_t bytes)
+{
+    if (bytes) HIPCHK(c, hipMemsetAsync(counts_dev, 0, bytes, c->stream));
+    ZrIdsArgs A = ids_args(c, 0, 0, c->W, c->H);
+    A.counts = counts_dev;
+    if (bytes) zr_launch_id_census(A, ZR_IDS_COVERAGE, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return ZR_OK;
+}
+extern "C" int zr_instance_coverage(zr_ctx* c, uint32_t* counts, size_t bytes)
+{
+    if (!c) return ZR_ERR_ARG;
+    ARGCHK(c, (counts || bytes == 0) && bytes == ids_slot_bytes(c));
+    int rc = ids_ready(c, "zr_instance_coverage", true);
+    if (rc == ZR_OK) rc = ids_coverage(c, c->d_ids_cov, bytes);
+    if (rc) return rc;
+    if (bytes) HIPCHK(c, hipMemcpyAsync(counts, c->d_ids_cov, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZR_OK;
+}
+extern "C" int zr_instance_coverage_async(zr_ctx* c, void* counts_dev, size_t bytes)
+{
+    if (!c) return ZR_ERR_ARG;
+    ARGCHK(c, (counts_dev || bytes == 0) && bytes == ids_slot_bytes(c));
+    int rc = ids_ready(c, "zr_instance_coverage_async", false);
+    if (rc == ZR_OK) rc = ids_coverage(c, (uint32_t*)counts_dev, bytes);
+    if (rc) return rc;
+    // the census reads the winner plane of copy `last`: the frame that writes that copy next (the one after next) waits for it
+    const int last = (int)((c->frame_no - 1u) & 1u);
+    HIPCHK(c, hipEventRecord(c->ev_ids[last], c->stream));
+    c->ids_wait[last] = true;
     return ZR_OK;
 }
 

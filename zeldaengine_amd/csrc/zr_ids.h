@@ -1,0 +1,28 @@
+// zr_ids.h — object identity of the last frame (zr_set_id_capture, zr_read_ids, zr_pick, zr_instance_coverage): the tables the
+// census kernels (zr_ids.hip) read.  Kept apart from ZrPass / ZrObject / GBufferPtrs, so that no existing kernel sees them.
+#pragma once
+
+#include "zr_types.h"
+
+// One record per scene draw, in draw order (non-instanced draws, then instanced ones: ZE:3445-3476), plus a sentinel whose prim_base is
+// the scene's primitive count.  object = add order, slot_base = that object's first instance slot (zr_instance_coverage).
+struct ZrIdsDraw { uint32_t prim_base, n_tris, object, slot_base; };
+
+struct ZrIdsArgs {
+    const uint32_t* prim;            // the frame's winner plane (W*H, ZR_EMPTY_PRIM = none)
+    const float* depth;              // the same frame's GBuffer target 0
+    const ZrIdsDraw* draws; uint32_t n_draws;
+    uint32_t W, x0, y0, w, h;        // the rectangle (already clipped to the frame)
+    uint32_t* counts;                // per slot: pixels won (zeroed between queries)
+    unsigned long long* keys;        // per slot: least depth_bits << 32 | y*W + x (all ones between queries)
+    uint32_t* hit_list; uint32_t* n_hits;      // the slots the rectangle touched, in no particular order
+    uint2* obj_plane;                // ZR_IDS_OBJECT (W*H)
+};
+
+#define ZR_IDS_COVERAGE 0            // counts only
+#define ZR_IDS_PICK     1            // counts + nearest pixel + hit list
+#define ZR_IDS_OBJECTS  2            // the {object, instance} plane only
+
+void zr_launch_id_census(const ZrIdsArgs& A, int mode, hipStream_t s);
+// the listed slots -> zr_hit records (unsorted), and those slots cleared for the next query
+void zr_launch_id_hits(const ZrIdsArgs& A, uint32_t n, zr_hit* out, hipStream_t s);

@@ -280,7 +280,7 @@ int apply_world(zr_ctx* c, const ZrWorld& w)
             if (o.d_inst) { (void)hipFree(o.d_inst); o.d_inst = nullptr; }
             for (auto& t : o.d_tex) if (t) { (void)hipFree(t); t = nullptr; }
         }
-        c->objects.clear(); c->scene_dirty = true;
+        c->objects.clear(); c->scene_dirty = true; c->scene_gen++;
         c->meshes = std::move(keep_m); c->profabs = std::move(keep_p);
     }
     c->world = w;

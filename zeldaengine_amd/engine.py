@@ -79,6 +79,11 @@ def lib():
         "zr_read_gbuffer": [vp, C.c_int, vp, sz],
         "zr_read_shadowmap": [vp, vp, sz],
         "zr_copy_frame_async": [vp, vp, vp],
+        "zr_set_id_capture": [vp, C.c_int],
+        "zr_read_ids": [vp, C.c_int, vp, sz],
+        "zr_pick": [vp, u32, u32, u32, u32, vp, u32, C.POINTER(u32)],
+        "zr_instance_coverage": [vp, vp, sz],
+        "zr_instance_coverage_async": [vp, vp, sz],
         "zr_tiles_device_buffer": [vp, C.POINTER(vp), C.POINTER(sz)],
         "zr_composite": [vp, vp],
         "zr_read_tiles": [vp, vp, sz],
@@ -473,6 +478,48 @@ class Renderer:
     def copy_frame_async(self, color_dev=None, shadow_dev=None):
         """The frame enqueued last -> caller-owned device buffers (addresses), in stream order, no host synchronisation."""
         self._chk(self.L.zr_copy_frame_async(self.h, C.c_void_p(color_dev) if color_dev else None, C.c_void_p(shadow_dev) if shadow_dev else None))
+
+    # ---- object identity of the last frame
+    def set_id_capture(self, on=True):
+        """Keep the deferred-scene pass's per-pixel winner from the next frame on (default off)."""
+        self._chk(self.L.zr_set_id_capture(self.h, 1 if on else 0))
+
+    def read_ids(self, kind=abi.IDS_PRIMITIVE):
+        """IDS_PRIMITIVE: (H, W) uint32 primitive ids; IDS_OBJECT: (H, W, 2) uint32 {object, instance}; all ones = none."""
+        out = np.zeros((self.H, self.W) if kind == abi.IDS_PRIMITIVE else (self.H, self.W, 2), dtype=np.uint32)
+        self._chk(self.L.zr_read_ids(self.h, kind, _ptr(out), out.nbytes))
+        return out
+
+    def pick(self, x, y, w=1, h=1, cap=None):
+        """Distinct (object, instance) winners in the rectangle: (abi.Hit array of min(total, cap), total)."""
+        n = C.c_uint32()
+        if cap is None:
+            self._chk(self.L.zr_pick(self.h, x, y, w, h, None, 0, C.byref(n)))
+            cap = n.value
+        hits = np.zeros(cap, dtype=abi.Hit)
+        self._chk(self.L.zr_pick(self.h, x, y, w, h, _ptr(hits) if cap else None, cap, C.byref(n)))
+        return hits[:min(cap, n.value)], n.value
+
+    def instance_slots(self):
+        """The first instance slot of every object (add order) and the slot count: one slot per instance, one per non-instanced object."""
+        base, k = [], 0
+        for i in range(self.object_count()):
+            _, inst = self.object_get_instances(i)
+            base.append(k)
+            k += max(1, 0 if inst is None else len(inst))
+        return np.array(base, dtype=np.int64), k
+
+    def instance_coverage(self):
+        """Pixels each instance slot won in the last frame (uint32 per slot)."""
+        out = np.zeros(self.instance_slots()[1], dtype=np.uint32)
+        self._chk(self.L.zr_instance_coverage(self.h, _ptr(out) if out.size else None, out.nbytes))
+        return out
+
+    def instance_coverage_async(self, dev_ptr, n_slots=None):
+        """The same counts into a device buffer (address) of n_slots uint32, on the render stream, without a host sync."""
+        if n_slots is None:
+            n_slots = self.instance_slots()[1]
+        self._chk(self.L.zr_instance_coverage_async(self.h, C.c_void_p(dev_ptr) if dev_ptr else None, 4 * n_slots))
 
     # ---- multi-GPU
     def tiles_device_buffer(self):
