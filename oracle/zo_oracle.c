@@ -10,7 +10,8 @@
  *   - sub-pixel precision: 8 bits (vertices snapped to 1/256 px), exact int64 edge functions;
  *   - depth and attributes are plane equations anchored at vertex 0;
  *   - clipping: near plane (z >= 0) + a 4x guard band in x,y; the far plane and z < 0 with
- *     w > 0 are per-fragment depth clips (equivalent for planar primitives);
+ *     w > 0 are per-fragment depth clips (equivalent for planar primitives; the depth bias's r
+ *     counts a vertex depth beyond the far plane as 1, the far-clipped primitive's);
  *   - derivatives: fine, with helper invocations extrapolating the same triangle;
  *   - bilinear weights in full fp32; cube faces are clamp-to-edge, not seamless.
  */
@@ -589,11 +590,14 @@ static float zo_depth_at(const zo_setup* s, int32_t Px, int32_t Py)
     return z + 0.0f;
 }
 
-/* D32 depth bias, vkCmdSetDepthBias(1.25, 0, 7.5) (ZE:3280-3287): o = m*slope + r*constant */
+/* D32 depth bias, vkCmdSetDepthBias(1.25, 0, 7.5) (ZE:3280-3287): o = m*slope + r*constant.  r is that of the primitive clipped
+   to z <= w (Vulkan 1.3 "Depth Bias", "Primitive Clipping"): the far plane is clipped per fragment here, so a vertex depth beyond
+   it counts as 1, the far-clipped polygon's largest depth */
 static float zo_depth_bias(const zo_setup* s, const zo_sv v[3])
 {
     float m = fmaxf(fabsf(s->gx), fabsf(s->gy)) * 256.0f;
     float zm = fmaxf(fmaxf(fabsf(v[0].z), fabsf(v[1].z)), fabsf(v[2].z));
+    zm = zm > 1.0f ? 1.0f : zm;
     uint32_t e = zo_f2u(zm) & 0x7F800000u;
     float r = (e > (23u << 23) && e < 0x7F800000u) ? zo_u2f(e - (23u << 23)) : 0.0f;
     return fmaf(m, 7.5f, r * 1.25f);

@@ -31,8 +31,13 @@ otherwise, and every bound below is derived, not tuned:
 * depth: the nearest candidate could be overtaken - the second-nearest certain fragment, or any uncertain one (near an edge, near the
   depth clip, facing undecidable) - within the sum of their depth tolerances, each |grad z| tau plus the propagated vertex-depth error
   plus a few float32 ulps of the plane evaluation;
-* shadow pass: a covering triangle is clipped in depth (near or far plane, or w <= 0): the r of a clipped primitive is the
-  implementation's (Vulkan 1.3 "Depth Bias": r is defined on the primitive being rasterised, i.e. after clipping).
+* shadow pass, a caster clipped in depth (near or far plane, or w <= 0): not excused, but held to a derived bias budget
+  (`_clipped_bias`, which quotes Vulkan 1.3 "Depth Bias" and "Primitive Clipping"): r anywhere in [0, r_hi] - the polygon clipped to
+  0 <= z <= w, any piece of it, the float32 rounding of an intersection depth across a power of two; an unclipped vertex beyond the far
+  plane is not admissible - and m the plane's, within 3 dz / h of any fan of the clipped polygon (h its smallest altitude over every
+  three vertices; a bound that fails when h is under the snap leaves the caster uncertain).  A texel stays excused only where such a
+  caster's budget reaches below the nearest fragment's tolerance, as an uncertain fragment's would.  raster() reports what the old rule
+  (every depth-clipped caster excused) excused because of clipping alone, "clip_excused".
 """
 import math
 
@@ -178,6 +183,104 @@ def _triangles(draws, ubo):
     return np.concatenate(clips), np.concatenate(eyes), np.concatenate(projs), np.concatenate(ids)
 
 
+# ---------------------------------------------------------------------------------------------------------------- the clipper, restated
+# Vulkan 1.3, "Primitive Clipping": primitives are clipped to the clip volume -w <= x <= w, -w <= y <= w, z_m <= z <= w (z_m = 0), and
+# "if the primitive is clipped, the new vertices ... are computed by linear interpolation in clip space".  This build clips x / y at a
+# guard band of GUARD w instead (equivalent coverage); the float64 polygon below is what any such clipper approximates.
+
+PLANES_DEPTH = ((0.0, 0.0, 1.0, 0.0), (0.0, 0.0, -1.0, 1.0), (0.0, 0.0, 0.0, 1.0))              # z >= 0, z <= w, w >= 0
+PLANES_GUARD = ((1.0, 0.0, 0.0, GUARD), (-1.0, 0.0, 0.0, GUARD), (0.0, 1.0, 0.0, GUARD), (0.0, -1.0, 0.0, GUARD))
+
+
+def clip_polygon(c, planes):
+    """Sutherland-Hodgman in float64, in clip space: c (n, 4) -> the polygon (m, 4) inside every plane (a . c >= 0), m = 0 if nothing
+    is left"""
+    poly = np.asarray(c, dtype=F64)
+    for a in planes:
+        if len(poly) == 0:
+            break
+        d = poly @ np.asarray(a)
+        out = []
+        for i in range(len(poly)):
+            j = (i + 1) % len(poly)
+            if d[i] >= 0:
+                out.append(poly[i])
+            if (d[i] >= 0) != (d[j] >= 0):
+                out.append(poly[i] + d[i] / (d[i] - d[j]) * (poly[j] - poly[i]))
+        poly = np.array(out).reshape(-1, 4)
+    return poly if len(poly) >= 3 else np.zeros((0, 4))
+
+
+def min_altitude(poly, W, H):
+    """the smallest altitude, in pixels, of any three vertices of a clipped polygon (w > 0): a fan of it, whichever vertex it starts
+    from, and any other triangulation, is made of such triples.  0 for fewer than three vertices."""
+    if len(poly) < 3:
+        return 0.0
+    p = np.stack([poly[:, 0] / poly[:, 3] * W / 2.0, poly[:, 1] / poly[:, 3] * H / 2.0], axis=1)
+    best = np.inf
+    n = len(p)
+    for i in range(n):
+        for j in range(i + 1, n):
+            for k in range(j + 1, n):
+                a, b, c = p[i], p[j], p[k]
+                area2 = abs((b[0] - a[0]) * (c[1] - a[1]) - (c[0] - a[0]) * (b[1] - a[1]))
+                longest = max(np.hypot(*(b - a)), np.hypot(*(c - b)), np.hypot(*(a - c)))
+                best = min(best, area2 / longest if longest > 0 else 0.0)
+    return float(best)
+
+
+def _clipped_bias(c, gz, W, H, control=None):
+    """The depth bias of a primitive clipped in depth, c (3, 4) its clip coordinates, gz = |grad z| of its plane per pixel.
+    -> (r_hi, dm_clip): every admissible r lies in [0, r_hi]; an implementation's m of any piece of its fan is within dm_clip of the
+    plane's (inf: not bounded, a piece may be degenerate after the snap).
+
+    r (Vulkan 1.3 "Depth Bias"): "the minimum resolvable difference for a given polygon is dependent on the maximum exponent, e, in the
+    range of z values spanned by the primitive", r = 2^(e - n), and the primitive is the one rasterised: "Primitive Clipping" clips it to
+    z_m <= z_c <= w_c first.  So r is that of the polygon clipped to 0 <= z <= w, or of any piece of it (its depths lie in the polygon's
+    range: r in [0, r_poly]), or the float32 rounding of an intersection depth across a power of two (r_hi = 2 r_poly there).  An
+    UNCLIPPED vertex beyond the far plane (z / w up to far / (far - near)) is not part of that primitive: an implementation that clips
+    z > w per fragment must still take r from depths <= 1, and r from such a vertex is not admissible.
+    m: the plane's, which clipping does not change; a fan evaluates it on re-snapped pieces.  Each piece vertex is off the plane by at
+    most |grad z| (sqrt(2)/512 px of snap + the intersection's float32 position) + its float32 depth; that moves the gradient by at most
+    sum_i dz_i / h_i <= 3 dz / h, h the smallest altitude over every three vertices of the clipped polygon (clipped with and without
+    the far plane: a per-fragment far clip fans the latter), less the same displacement twice; the setup's own rounding adds
+    8u |grad z| L / h, L the polygon's diameter."""
+    near = (0.0, 0.0, 1.0, 1.0) if control == "gl_near" else PLANES_DEPTH[0]
+    depth = (near,) + PLANES_DEPTH[1:]
+    poly = clip_polygon(c, depth)
+    if len(poly) == 0:
+        return 0.0, 0.0
+    zmax = float(np.max(np.abs(poly[:, 2] / poly[:, 3])))
+    # the float32 intersection depth: the clip coordinates' error and the lerp and the division
+    zup = zmax * (1.0 + (K_EYE + K_PROJ + K_PLANE) * U) + (K_EYE + K_PROJ + K_PLANE) * U
+    r_hi = math.ldexp(1.0, math.frexp(zup)[1] - 1 - 23)
+    pieces = [clip_polygon(c, depth + PLANES_GUARD), clip_polygon(c, (near, PLANES_DEPTH[2]) + PLANES_GUARD)]
+    pieces = [p for p in pieces if len(p)]
+    if not pieces:
+        return r_hi, 0.0
+    h = min(min_altitude(p, W, H) for p in pieces)
+    scr = np.vstack([np.stack([p[:, 0] / p[:, 3] * W / 2.0, p[:, 1] / p[:, 3] * H / 2.0], axis=1) for p in pieces])
+    diam = float(np.max(np.hypot(*(scr[:, None, :] - scr[None, :, :]).transpose(2, 0, 1))))
+    zfar = float(np.max(np.abs(np.vstack(pieces)[:, 2] / np.vstack(pieces)[:, 3])))
+    e_pos = math.sqrt(2.0) / 512.0 + (K_EYE + K_PROJ) * U * GUARD * max(W, H)
+    dz = gz * e_pos + (K_EYE + K_PROJ + K_PLANE) * U * zfar
+    h_eff = h - 2.0 * e_pos
+    if not h_eff > 0.0:
+        return r_hi, np.inf
+    return r_hi, 3.0 * dz / h_eff + K_PLANE * U * gz * diam / h_eff
+
+
+def _ndc_pieces(c):
+    """control "ndc_lerp": the clipper's intersections interpolated AFTER the perspective divide - (x/w, y/w, z/w) clipped linearly
+    against 0 <= z <= 1 and the guard band, fanned - as primitives with w = 1"""
+    with np.errstate(all="ignore"):
+        ndc = np.hstack([c[:, :3] / c[:, 3:4], np.ones((3, 1))])
+    if not np.all(np.isfinite(ndc)):
+        return []
+    poly = clip_polygon(ndc, PLANES_DEPTH[:2] + PLANES_GUARD)
+    return [np.stack([poly[0], poly[i], poly[i + 1]]) for i in range(1, len(poly) - 1)]
+
+
 # ---------------------------------------------------------------------------------------------------------------- rasterisation
 
 def _setup(C, Ee, Dp, P, W, H):
@@ -208,14 +311,16 @@ def _setup(C, Ee, Dp, P, W, H):
             "dsnap": np.abs(g3[:, 0:1]) * snap / W + np.abs(g3[:, 1:2]) * snap / H}
 
 
-def _fragments(C, S, W, H, shadow, slope, tri_ok, facing_unsure):
+def _fragments(C, S, W, H, shadow, slope, tri_ok, facing_unsure, control=None):
     """All fragments - certain and uncertain - of the triangles `tri_ok` of C (clip, (T, 3, 4)); S = _setup(...).
-    -> dict of flat arrays: pix, z (biased and clamped in the shadow pass), tol, certain, tri"""
+    -> dict of flat arrays: pix, z (biased and clamped in the shadow pass), tol, certain, tri; in the shadow pass also z_old, tol_old,
+    certain_old (the rule that excused every depth-clipped caster), certain_plain (those casters certain, with the old bias) and clipped
+    (the fragment's caster is clipped in depth)"""
     Minv, L, cz, g3 = S["Minv"], S["L"], S["cz"], S["g3"]
     Z = C[:, :, 2]
     w = C[:, :, 3]
     big = float(max(W, H))
-    out = {k: [] for k in ("pix", "z", "tol", "certain", "tri")}
+    out = {k: [] for k in ("pix", "z", "tol", "certain", "tri", "z_old", "tol_old", "certain_old", "certain_plain", "clipped")}
     ok = tri_ok.copy()
     with np.errstate(all="ignore"):
         # clipping: in depth (0 <= z <= w, w > 0), in x / y, and beyond the guard band
@@ -238,7 +343,7 @@ def _fragments(C, S, W, H, shadow, slope, tri_ok, facing_unsure):
         gz = np.hypot(gx_px, gy_px)
         g = np.hypot(Minv[:, :, 0] * 2.0 / W, Minv[:, :, 1] * 2.0 / H)           # |grad lambda_k| per pixel
         if shadow:
-            # r: the largest exponent of the vertex depths (unclipped primitives; depth-clipped ones are excused below)
+            # r: the largest exponent of the vertex depths; m and its error on the unclipped plane
             zmax = np.max(np.abs(Z / np.where(w != 0, w, 1.0)), axis=1)
             e = np.frexp(np.where(zmax > 0, zmax, 1.0))[1] - 1                    # zmax = 1.f * 2^e
             r = np.where(zmax > 0, np.ldexp(1.0, e - 23), 0.0)
@@ -250,6 +355,21 @@ def _fragments(C, S, W, H, shadow, slope, tri_ok, facing_unsure):
             # 0.5 r: a float32 vertex depth may round across a power of two; an x / y clipped primitive has vertex depths between the
             # unclipped ones, so its r lies in [0, r]
             bias_tol = slope * dm + 0.5 * r + np.where(xy_clipped, 1.25 * r, 0.0)
+            # the rule this statement had before: a depth-clipped caster excused outright (kept to report what it excused)
+            bias_old, bias_tol_old = bias.copy(), bias_tol.copy()
+            # a depth-clipped caster: r of the clipped polygon and m of the plane, with the fan's error (_clipped_bias)
+            unbounded = np.zeros(len(C), dtype=bool)
+            for t in np.nonzero(depth_clipped & ok)[0]:
+                r_hi, dm_clip = _clipped_bias(C[t], gz[t], W, H, control)
+                unbounded[t] = not np.isfinite(dm_clip)
+                bias[t] = slope * m[t] + 0.625 * r_hi                             # any r in [0, r_hi]
+                bias_tol[t] = slope * (dm[t] + dm_clip) + 0.625 * r_hi
+                if control == "clipped_unbiased":
+                    bias[t] = 0.0
+                elif control == "far_vertex_r" and np.any(Z[t] > w[t]):
+                    bias[t] = slope * m[t] + 1.25 * r[t]
+                    bias_tol[t] = slope * (dm[t] + dm_clip) + 0.5 * r[t]
+        z_lo = -1.0 if control == "gl_near" else 0.0                              # the clip volume's z_m
     for t_sel, x0s, y0s, gw, gh in _boxes(np.nonzero(ok)[0], x0, x1, y0, y1):
         gxs, gys = np.meshgrid(np.arange(gw), np.arange(gh))
         ix = x0s[:, None] + gxs.reshape(1, -1)
@@ -272,19 +392,44 @@ def _fragments(C, S, W, H, shadow, slope, tri_ok, facing_unsure):
             tol = (gz[t_sel, None] * (SNAP + tau_clip[t_sel, None])
                    + np.einsum("tkp,tk->tp", alam, cz[t_sel])
                    + K_PLANE * U * (np.abs(z) + gz[t_sel, None] * GUARD * big))
-            cand = (inside | near) & valid & (z > -tol) & (z < 1.0 + tol)
-            certain = inside & ~near & (z >= tol) & (z <= 1.0 - tol) & ~facing_unsure[t_sel, None]
+            cand = (inside | near) & valid & (z > z_lo - tol) & (z < 1.0 + tol)
+            certain = inside & ~near & (z >= z_lo + tol) & (z <= 1.0 - tol) & ~facing_unsure[t_sel, None]
             if shadow:
-                certain &= ~depth_clipped[t_sel, None]
-                z = np.clip(z + bias[t_sel, None], 0.0, 1.0)
+                z_raw = z
+                z = np.clip(z_raw + bias[t_sel, None], 0.0, 1.0)
+                z_old = np.clip(z_raw + bias_old[t_sel, None], 0.0, 1.0)
+                tol_old = tol + bias_tol_old[t_sel, None]
                 tol = tol + bias_tol[t_sel, None]
+                certain_plain = certain
+                certain_old = certain & ~depth_clipped[t_sel, None]
+                certain = certain & ~unbounded[t_sel, None]
         tt, pp = np.nonzero(cand)
         out["pix"].append(iy[tt, pp] * W + ix[tt, pp])
         out["z"].append(z[tt, pp])
         out["tol"].append(tol[tt, pp])
         out["certain"].append(certain[tt, pp])
         out["tri"].append(t_sel[tt])
+        if shadow:
+            clipped = np.broadcast_to(depth_clipped[t_sel, None], cand.shape)
+            for k, v in (("z_old", z_old), ("tol_old", tol_old), ("certain_old", certain_old), ("certain_plain", certain_plain),
+                         ("clipped", clipped)):
+                out[k].append(v[tt, pp])
     return {k: (np.concatenate(v) if v else np.zeros(0)) for k, v in out.items()}
+
+
+def _ndc_lerp(C, Ee, Dp, ids):
+    """control "ndc_lerp": every depth-clipped triangle replaced by the pieces _ndc_pieces makes of it (their error: the projection's
+    rounding of an NDC coordinate)"""
+    with np.errstate(all="ignore"):
+        clipped = np.any((C[:, :, 3] <= 0) | (C[:, :, 2] < 0) | (C[:, :, 2] > C[:, :, 3]), axis=1)
+    keep = np.nonzero(~clipped)[0]
+    extra = [(p, t) for t in np.nonzero(clipped)[0] for p in _ndc_pieces(C[t])]
+    if not extra:
+        return C[keep], Ee[keep], Dp[keep], ids[keep]
+    P = np.array([p for p, _ in extra])
+    src = np.array([t for _, t in extra])
+    return (np.concatenate([C[keep], P]), np.concatenate([Ee[keep], np.zeros((len(P), 3, 3))]),
+            np.concatenate([Dp[keep], K_PROJ * U * np.abs(P)]), np.concatenate([ids[keep], ids[src]]))
 
 
 def _boxes(tris, x0, x1, y0, y1, budget=1 << 19):
@@ -307,7 +452,10 @@ def _boxes(tris, x0, x1, y0, y1, budget=1 << 19):
             yield np.array([t]), np.array([x0[t]]), np.array([ys]), w_, min(rows, int(y1[t]) - ys + 1)
 
 
-def raster(draws, ubo, W, H, shadow=False, slope=7.5, depth_op="less", cull="back", start=None):
+SHADOW_CONTROLS = ("gl_near", "clipped_unbiased", "ndc_lerp", "far_vertex_r")
+
+
+def raster(draws, ubo, W, H, shadow=False, slope=7.5, depth_op="less", cull="back", start=None, control=None):
     """Rasterise the whole frame in float64.
 
     draws: independent_scenes.Scene.draws(); ubo: frame_uniforms(...)["cam"] or ["shadow"] (W = H = the map size for the shadow pass)
@@ -317,11 +465,15 @@ def raster(draws, ubo, W, H, shadow=False, slope=7.5, depth_op="less", cull="bac
     render pass sees it (the skydome against the copied deferred depth): {"depth", "tol", "ambiguous"} (H, W), e.g. an earlier raster().
     Its values act as fragments drawn before every primitive (they keep a tie under LESS), and its ambiguous pixels stay ambiguous;
     "prim" is 0xFFFFFFFF and "covered" False where such a value still wins.
+    control: None, or one of SHADOW_CONTROLS - a deliberately wrong reading of clipping for the negative controls (shadow pass).
     -> {"depth": (H, W) the winner's depth (camera) or the biased map value (shadow), 1.0 where nothing is drawn,
         "tol": (H, W) its tolerance, "prim": (H, W) winning primitive id, 0xFFFFFFFF for none (camera pass),
-        "covered": (H, W), "ambiguous": (H, W) bool}
+        "covered": (H, W), "ambiguous": (H, W) bool; shadow pass also "ambiguous_old" (the mask of the rule that excused every
+        depth-clipped caster) and "clip_excused" (what that rule excused only because the caster was clipped)}
     """
     C, Ee, Dp, ids = _triangles(draws, ubo)
+    if control == "ndc_lerp":
+        C, Ee, Dp, ids = _ndc_lerp(C, Ee, Dp, ids)
     T = len(C)
     S = _setup(C, Ee, Dp, ubo["Proj"], W, H)
     det, ddet, ok = S["det"], S["ddet"], S["ok"].copy()
@@ -340,11 +492,25 @@ def raster(draws, ubo, W, H, shadow=False, slope=7.5, depth_op="less", cull="bac
             keep = np.zeros(T, dtype=bool)
             keep[first if depth_op == "less" else T - 1 - last] = True
             ok &= keep
-    f = _fragments(C, S, W, H, shadow, slope, ok, facing_unsure)
+    f = _fragments(C, S, W, H, shadow, slope, ok, facing_unsure, control)
     n = W * H
     pix = f["pix"].astype(np.int64)
-    z, tol, certain = f["z"], f["tol"], f["certain"].astype(bool)
     prim = ids[f["tri"].astype(np.int64)] if len(pix) else np.zeros(0, dtype=np.int64)
+    certain = f["certain"].astype(bool)
+    compete = certain & f["clipped"].astype(bool) if shadow else None
+    out = _resolve(n, pix, f["z"], f["tol"], certain, prim, shadow, depth_op, start, compete)
+    if shadow:
+        # the rule before (every depth-clipped caster excused), and the same casters certain under it: what clipping alone excused
+        old = _resolve(n, pix, f["z_old"], f["tol_old"], f["certain_old"].astype(bool), prim, shadow, depth_op, start)
+        plain = _resolve(n, pix, f["z_old"], f["tol_old"], f["certain_plain"].astype(bool), prim, shadow, depth_op, start)
+        out["ambiguous_old"] = old["ambiguous"]
+        out["clip_excused"] = old["ambiguous"] & ~plain["ambiguous"]
+    return {k: v.reshape(H, W) if k != "prim" else v.reshape(H, W).astype(np.uint32) for k, v in out.items()}
+
+
+def _resolve(n, pix, z, tol, certain, prim, shadow, depth_op, start, compete=None):
+    """the fragments' depth test: the nearest certain fragment per pixel and the ambiguity mask (see raster).  compete: certain
+    fragments whose lowest value counts as an uncertain fragment's does (the shadow pass's depth-clipped casters)"""
     if start is not None:
         # the starting depth buffer as certain fragments with primitive id -1: first in draw order, so they keep a tie under LESS
         d0 = np.asarray(start["depth"], dtype=F64).reshape(-1)
@@ -372,8 +538,10 @@ def raster(draws, ubo, W, H, shadow=False, slope=7.5, depth_op="less", cull="bac
             s2 = order[np.r_[False, ~head[1:] & head[:-1]]]
             close = z[s2] - tol[s2] <= depth[pix[s2]] + dtol[pix[s2]]
             amb[pix[s2[close]]] = True
-    # an uncertain fragment could come in front of (or, in the shadow pass, below the tolerance of) what the certain ones give
-    u = np.nonzero(~certain)[0]
+    # an uncertain fragment could come in front of (or, in the shadow pass, below the tolerance of) what the certain ones give; in the
+    # shadow pass the map holds the least of the fragments' values, so a certain fragment of a depth-clipped caster (whose bias budget
+    # can reach below the nearest one's tolerance) counts as well
+    u = np.nonzero(~certain if compete is None else ~certain | compete)[0]
     if len(u):
         lowest = np.full(n, np.inf)
         np.minimum.at(lowest, pix[u], z[u] - tol[u])
@@ -387,8 +555,7 @@ def raster(draws, ubo, W, H, shadow=False, slope=7.5, depth_op="less", cull="bac
         amb |= np.asarray(start["ambiguous"], dtype=bool).reshape(-1)
         covered &= win >= 0
         win[win < 0] = 0xFFFFFFFF
-    return {"depth": depth.reshape(H, W), "tol": dtol.reshape(H, W), "prim": win.reshape(H, W).astype(np.uint32),
-            "covered": covered.reshape(H, W), "ambiguous": amb.reshape(H, W)}
+    return {"depth": depth, "tol": dtol, "prim": win, "covered": covered, "ambiguous": amb}
 
 
 # ---------------------------------------------------------------------------------------------------------------- comparisons

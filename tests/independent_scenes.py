@@ -231,9 +231,73 @@ def edge_odd_size():
     return Case(s, cam, lights, roll, 0.0, 257, 131, 100)
 
 
+def _light_mesh(eye, pts, tris):
+    """a mesh of points given in the frame of a light at `eye` looking at the origin with up +Z (glm::lookAt, ZE:4610): (a, b, d) ->
+    eye + a s + b u + d f, f = normalize(-eye), s = normalize(f x Z), u = s x f"""
+    eye = np.asarray(eye, dtype=np.float64)
+    f = -eye / np.linalg.norm(eye)
+    s = np.cross(f, (0.0, 0.0, 1.0))
+    s /= np.linalg.norm(s)
+    u = np.cross(s, f)
+    world = [tuple(eye + a * s + b * u + d * f) for a, b, d in pts]
+    return scenes._ingest(world, [(0.0, 0.0, 1.0)] * len(world), [(0.0, 0.0)] * len(world), [tuple((i, 0) for i in t) for t in tris])
+
+
+def edge_shadow_near_sliver():
+    """the light's near plane (zNear 6.0005, the camera's) just beyond the look-at point, which is a vertex of a 30-unit ground plane
+    in 24 x 24 cells under a sun 74 degrees high and 6 away: the plane crosses the near plane at 16 degrees, the vertex at the origin
+    lies 0.0005 behind it, and the clipper's polygons around it hold three vertices whose triangle is under 1/8 texel high on the
+    1024-texel map (tests/test_oracle_geometry.py computes it)"""
+    s = Scene()
+    s.add(scenes.grid_plane(30.0, 24, 0.0))
+    _props(s, n_boxes=8, n_spheres=4, seed=31, radius=3.0)
+    return Case(s, abi.make_camera((6.5, -5.0, 4.5), (0.0, 0.0, 0.0), znear=6.0005, zfar=60.0), _sun_at(_lights(1, 4), 1.3, 0.7, 6.0),
+                0.0, 0.0, 192, 128, 1024)
+
+
+def edge_shadow_behind_light():
+    """a 160-unit ground plane in 4 x 4 cells under a sun 0.45 rad high at 28: the plane runs on behind the light, where w <= 0, so
+    the triangles under the light cross w = 0 and the near plane"""
+    s = Scene()
+    s.add(scenes.grid_plane(160.0, 4, 0.0))
+    _props(s, n_boxes=10, n_spheres=6, seed=37)
+    return Case(s, abi.make_camera((5.0, 4.0, 3.5), (0.0, 0.0, 0.4), zfar=120.0), _sun_at(_lights(1, 4), 0.45, 2.2, 28.0), 0.0, 0.0, 192, 128, 512)
+
+
+SLAB = (63.5, 64.0)       # zNear, zFar: far / (far - near) = 128, so z / w reaches 64 at twice the near distance
+
+
+def _slab(caster):
+    """the camera and the sun at the same eye, 5 from the origin, 85 degrees high, fov 20, zNear 63.5, zFar 64: a 12-unit square held
+    in the slab 63.75 along the eye's axis (the origin stays near the eye, so the matrices' translations do not cancel), and `caster`,
+    three points in the eye's frame (a, b, depth along the axis)"""
+    lights = _sun_at(_lights(1, 4), 1.48, 0.3, 5.0)
+    eye = lights[0][0]["Position"][:3]
+    grid = [(a, b, 63.75 + 0.02 * a) for b in (-6.0, -2.0, 2.0, 6.0) for a in (-6.0, -2.0, 2.0, 6.0)]
+    quads = [(4 * i + j, 4 * i + j + 1, 4 * i + j + 5) for i in range(3) for j in range(3)] + \
+            [(4 * i + j, 4 * i + j + 5, 4 * i + j + 4) for i in range(3) for j in range(3)]
+    s = Scene()
+    s.add(_light_mesh(eye, grid, quads))
+    s.add(_light_mesh(eye, caster, [(0, 1, 2)]))
+    return Case(s, abi.make_camera(tuple(float(x) for x in eye), (0.0, 0.0, 0.0), fov=20.0, znear=SLAB[0], zfar=SLAB[1]), lights,
+                0.0, 0.0, 192, 128, 1024)
+
+
+def edge_shadow_far_cut():
+    """a caster beside the slab's square from 63.6 to 128 along the axis: its far vertex at z / w = 64.5, x / w = 3 (inside the guard
+    band), so r from that vertex is 2^6 times the far-clipped polygon's"""
+    return _slab([(7.0, -6.0, 63.6), (7.0, 6.0, 63.6), (67.6, 0.0, 128.0)])
+
+
+def edge_shadow_both_planes():
+    """one triangle from 63.2 (in front of the near plane) to 100 (beyond the far plane) beside the slab's square: clipped by both"""
+    return _slab([(-7.0, -6.0, 63.2), (-7.0, 6.0, 63.2), (-30.0, 0.0, 100.0)])
+
+
 EDGE_SCENES = {"rolled_stage_and_light": edge_rolled_stage_and_light, "grazing_sun": edge_grazing_sun, "sun_at_zenith": edge_sun_at_zenith,
                "mirrored_instances": edge_mirrored_instances, "low_camera": edge_low_camera, "repeated_draw": edge_repeated_draw,
-               "odd_size": edge_odd_size}
+               "odd_size": edge_odd_size, "shadow_near_sliver": edge_shadow_near_sliver, "shadow_behind_light": edge_shadow_behind_light,
+               "shadow_far_cut": edge_shadow_far_cut, "shadow_both_planes": edge_shadow_both_planes}
 
 
 # ---------------------------------------------------------------------------------------------------------------- textured scenes

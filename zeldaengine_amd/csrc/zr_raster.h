@@ -116,9 +116,11 @@ __device__ __forceinline__ void raster_sub(const SV& v0, const SV& v1, const SV&
     const float zlo = __builtin_fminf(__builtin_fminf(v0.z, v1.z), v2.z), zhi = __builtin_fmaxf(__builtin_fmaxf(v0.z, v1.z), v2.z);
     float bias = 0.0f;
     if (MODE == ZR_MODE_SHADOW) {
-        // vkCmdSetDepthBias(1.25, 0, 7.5) on D32 (ZE:3280-3287): o = m * slope + r * constant, r = 2^(e - 23)
+        // vkCmdSetDepthBias(1.25, 0, 7.5) on D32 (ZE:3280-3287): o = m * slope + r * constant, r = 2^(e - 23) of the primitive
+        // clipped to z <= w: the far plane is clipped per fragment, so a vertex depth beyond it counts as 1 (as the oracle)
         const float m = __builtin_fmaxf(__builtin_fabsf(gx), __builtin_fabsf(gy)) * 256.0f;
-        const float zm = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(v0.z), __builtin_fabsf(v1.z)), __builtin_fabsf(v2.z));
+        const float zm0 = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(v0.z), __builtin_fabsf(v1.z)), __builtin_fabsf(v2.z));
+        const float zm = zm0 > 1.0f ? 1.0f : zm0;
         const uint32_t e = zr_f2u(zm) & 0x7F800000u;
         const float r = (e > (23u << 23) && e < 0x7F800000u) ? zr_u2f(e - (23u << 23)) : 0.0f;
         bias = __builtin_fmaf(m, 7.5f, r * 1.25f);
