@@ -162,6 +162,19 @@ int  zr_scene_clear(zr_ctx* ctx);                   /* CleanupBasePass, ZE:4142 
 int  zr_object_count(zr_ctx* ctx, uint32_t* n);
 /* Copy out the instance array of object `index` (add order); *n = 0 for a non-instanced draw.  dst may be NULL. */
 int  zr_object_get_instances(zr_ctx* ctx, uint32_t index, uint32_t* mesh_id, XkInstanceData* dst, uint32_t* n);
+/* Moving instances.  Replace instances [first, first + n) of instanced object `index` (add order, as
+ * zr_object_get_instances).  Takes effect with the next zr_render; frames already enqueued still draw the old values.  `data` may be
+ * reused when the call returns.  The instance count is fixed at zr_object_add.  Neither call changes the scene (the identity queries
+ * go on describing the last frame); a non-instanced object or a range beyond the instance count: ZR_ERR_ARG; between the stages of a
+ * frame: ZR_ERR_STATE. */
+int  zr_object_set_instances(zr_ctx* ctx, uint32_t index, uint32_t first, const XkInstanceData* data, uint32_t n);
+/* The same from caller-owned DEVICE memory, in the order of hip_stream (NULL = the render stream): data_dev[i] replaces instance
+ * idx_dev[i] (idx_dev NULL = instances first .. first + n - 1; with idx_dev the indices are the object's own and `first` only enters
+ * the range check).  The library reads both buffers only inside hip_stream's order: a caller may overwrite them with work enqueued on
+ * hip_stream after this call.  Device indices >= the object's instance count are ignored; an index listed twice in one call gets one
+ * of its values.  Both buffers 4-byte aligned.  No host synchronisation (zr_object_get_instances reads back with one). */
+int  zr_object_update_instances_async(zr_ctx* ctx, uint32_t index, uint32_t first, const uint32_t* idx_dev,
+                                      const XkInstanceData* data_dev, uint32_t n, void* hip_stream);
 /* 6 RGBA8 sRGB faces in Vulkan layer order +X,-X,+Y,-Y,+Z,-Z (RHICreateTextureCubeResource ZE:5908-6150);
  * mips are generated like RHIGenerateMipmaps (ZE:6348-6433).  faces == NULL: built-in 1x1 grey. */
 int  zr_set_cubemap(zr_ctx* ctx, const uint8_t* const faces[6], uint32_t dim);

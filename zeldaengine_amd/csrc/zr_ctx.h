@@ -34,7 +34,12 @@ struct ZrMaterialHost {
 struct ZrSceneObject {
     uint32_t mesh = 0, n_inst = 1; bool instanced = false;
     std::vector<XkInstanceData> inst;    // host copy (zr_object_get_instances)
-    ZrInstance* d_inst = nullptr;
+    ZrInstance* d_inst = nullptr;        // the instance records: what every frame reads until an update, then the parity-0 plane
+    XkInstanceData* d_raw = nullptr;     // instanced objects: the raw values on the device (written only by the update calls)
+    // Instance updates (zr_instances_host.cpp), set up at the object's first update: upd.plane[0] = d_inst, plane[1] its parity-1 twin.
+    // pending[p]: an upper bound of list p's length on the device; tab1 = the parity-1 draw table points at plane[1];
+    // host_stale = a device-form update came after `inst` (zr_object_get_instances reads back); draw = the record in the draw table.
+    ZrInstanceState upd = {}; uint32_t pending[2] = { 0, 0 }; bool tab1 = false, host_stale = false; uint32_t draw = 0;
     uint32_t texel[7]; float bc_linear[3];
     uint8_t* d_tex[8] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };   // [7]: the packed material (ZrObject::packed)
     uint32_t tex_w[8] = { 0 }, tex_h[8] = { 0 }, tex_levels[8] = { 0 };
@@ -68,7 +73,19 @@ struct zr_ctx {
     std::vector<ZrMesh> meshes;
     std::vector<ZrSceneObject> objects;
     bool scene_dirty = true;
-    ZrObject* d_objs = nullptr; uint32_t n_objs = 0, n_work = 0;
+    ZrObject* d_objs = nullptr; uint32_t n_objs = 0, n_work = 0;     // d_objs: the draw table of the frame enqueued last (an alias)
+    // Draw tables: [0] made by finalize_scene (every object's d_inst), [1] the parity-1 table, once an instance has been updated: it
+    // differs only where an updated object points at its parity-1 plane.  A frame reads the table and the planes of its parity.
+    ZrObject* d_objs_b[2] = { nullptr, nullptr };
+    // Instance updates (zr_instances_host.cpp): inst_reader[p] = 1 + the last frame that read the table / planes of parity p (0: none);
+    // ev_scatter follows the last update (on scatter_s), ev_apply the last frame-head apply (on apply_s); a pinned staging ring for the
+    // host form.  Made at the first update: a scene that never moves an instance has none of it.
+    uint64_t inst_reader[2] = { 0, 0 };
+    hipEvent_t ev_scatter = nullptr, ev_apply = nullptr; hipStream_t scatter_s = nullptr, apply_s = nullptr;
+    bool scatter_wait[2] = { false, false }, apply_done = false, inst_dual = false;      // scatter_wait[p]: the next frame of parity p waits for ev_scatter
+    static constexpr int INST_RING = 4;
+    struct InstStage { XkInstanceData* h = nullptr; XkInstanceData* d = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; } inst_ring[INST_RING];
+    uint32_t inst_slot = 0;
     // this frame's two geometry passes (0 shadow, 1 camera), built at frame begin; the passes' work lists (k_cull_instances) are kept
     // while the pass block and the scene stand still: list_key = the block the list on the device was built from
     ZrPass pass[2]; bool pass_live[2] = { false, false }, list_reuse[2] = { false, false }, list_valid[2] = { false, false };
@@ -183,6 +200,19 @@ struct zr_ctx {
 };
 
 int zr_fail(zr_ctx* c, int code, const std::string& msg);      // records the message (never throws), returns code
+// an object's device memory (its instance records, raw values, update state, material images)
+inline void zr_object_free_device(ZrSceneObject& o)
+{
+    ZrInstance* plane1 = o.upd.plane[1];
+    for (void* p : { (void*)o.d_inst, (void*)o.d_raw, (void*)plane1, (void*)o.upd.dirty }) if (p) (void)hipFree(p);
+    o.d_inst = nullptr; o.d_raw = nullptr; o.upd = ZrInstanceState{}; o.tab1 = false;
+    for (auto& t : o.d_tex) if (t) { (void)hipFree(t); t = nullptr; }
+}
+// zr_instances_host.cpp
+int zr_instances_frame(zr_ctx* c, hipStream_t s, int par);       // frame head: this frame's draw table, the updates that are due
+int zr_instances_table(zr_ctx* c);                               // finalize_scene: the parity-1 table of a new draw table
+int zr_instances_sync_host(zr_ctx* c, ZrSceneObject& o);         // zr_object_get_instances after a device-form update
+void zr_instances_destroy(zr_ctx* c);
 // No exception crosses the C-ABI: entry points that build host-side containers run their body through this.
 template <typename F> static inline int zr_guard(zr_ctx* c, F&& body) noexcept
 {

@@ -6,7 +6,6 @@
 
 // ------------------------------------------------------------------------------------------------ instance prep
 
-// MakeRotMatrix (SH/Common.glsl:60-87): rotMat = mz * my * mx; mx(R.x) turns about Y, my(R.y) about Z, mz(R.z) about X
 __global__ void k_instance_prep(const XkInstanceData* __restrict__ in, ZrInstance* __restrict__ out, uint32_t n, uint32_t instanced)
 {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -15,21 +14,8 @@ __global__ void k_instance_prep(const XkInstanceData* __restrict__ in, ZrInstanc
     if (!instanced) {
         for (int k = 0; k < 9; ++k) I.R[k] = (k % 4 == 0) ? 1.0f : 0.0f;
         I.t[0] = I.t[1] = I.t[2] = 0.0f; I.s = 1.0f;
-    } else {
-        XkInstanceData d = in[i];
-        float s, c, mx[9], my[9], mz[9], t[9];
-        zr_sincos(d.InstanceRotation[0], s, c);
-        mx[0] = c; mx[1] = 0; mx[2] = s;  mx[3] = 0; mx[4] = 1; mx[5] = 0;  mx[6] = -s; mx[7] = 0; mx[8] = c;
-        zr_sincos(d.InstanceRotation[1], s, c);
-        my[0] = c; my[1] = s; my[2] = 0;  my[3] = -s; my[4] = c; my[5] = 0;  my[6] = 0; my[7] = 0; my[8] = 1;
-        zr_sincos(d.InstanceRotation[2], s, c);
-        mz[0] = 1; mz[1] = 0; mz[2] = 0;  mz[3] = 0; mz[4] = c; mz[5] = s;  mz[6] = 0; mz[7] = -s; mz[8] = c;
-        zr_mat3_mul(mz, my, t);
-        zr_mat3_mul(t, mx, I.R);
-        I.t[0] = d.InstancePosition[0]; I.t[1] = d.InstancePosition[1]; I.t[2] = d.InstancePosition[2];
-        I.s = d.InstancePScale;
-    }
-    I._pad[0] = I._pad[1] = I._pad[2] = 0.0f;
+        I._pad[0] = I._pad[1] = I._pad[2] = 0.0f;
+    } else I = instance_record(in[i]);      // (zr_dev.h: shared with k_instance_apply)
     out[i] = I;
 }
 

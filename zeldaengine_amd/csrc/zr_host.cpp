@@ -31,6 +31,7 @@ hipError_t zr_sync_all(zr_ctx* c)
     if (e == hipSuccess && c->cam_s) e = hipStreamSynchronize(c->cam_s);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // (the host's stream may have been made to wait for the lanes)
     if (e == hipSuccess) e = zr_dist_sync(c);           // the native multi-GPU host's collective stream, if any
+    if (e == hipSuccess && c->ev_scatter) e = hipEventSynchronize(c->ev_scatter);      // the last instance update (on a caller's stream)
     return e;
 }
 
@@ -289,14 +290,15 @@ static void free_tri_bins(zr_ctx* c)
 
 static void free_scene(zr_ctx* c)
 {
-    for (auto& o : c->objects) { dev_free(o.d_inst); for (auto& t : o.d_tex) dev_free(t); }
+    for (auto& o : c->objects) zr_object_free_device(o);
     c->objects.clear(); c->scene_gen++;
     for (auto& m : c->meshes) {
         dev_free(m.d_v); dev_free(m.d_rv); dev_free(m.d_rt); dev_free(m.d_idx); dev_free(m.d_meshlets); dev_free(m.d_mpos); dev_free(m.d_mbox); dev_free(m.d_mtri); dev_free(m.d_tri_meshlet);
     }
     c->meshes.clear();
     c->profabs.clear();
-    dev_free(c->d_objs); c->n_objs = 0; c->n_work = 0; c->scene_dirty = true;
+    dev_free(c->d_objs_b[0]); dev_free(c->d_objs_b[1]); c->d_objs = nullptr; c->inst_dual = false;
+    c->n_objs = 0; c->n_work = 0; c->scene_dirty = true;
 }
 
 extern "C" void zr_destroy(zr_ctx* c)
@@ -307,6 +309,7 @@ extern "C" void zr_destroy(zr_ctx* c)
     (void)zr_sync_all(c);                      // including a geometry stage whose lighting pass never came
     zr_dist_destroy(c);
     free_scene(c);
+    zr_instances_destroy(c);
     free_mesh_buffers(c->sky_mesh); dev_free(c->sky_obj.d_inst); for (auto& t : c->sky_obj.d_tex) dev_free(t); dev_free(c->d_bg);
     for (auto p : c->d_cube) if (p) (void)hipFree(p);
     for (int b = 0; b < 2; ++b) {
@@ -590,7 +593,7 @@ int zr_object_add_internal(zr_ctx* c, uint32_t mesh_id, const ZrMaterialHost& ma
     memcpy(o.texel, mat.texel, sizeof o.texel); memcpy(o.bc_linear, mat.bc_linear, sizeof o.bc_linear);
     if (n_inst) o.inst.assign(inst, inst + n_inst);
     HIPCHK(c, hipSetDevice(c->device));
-    auto cleanup = [&]() { dev_free(o.d_inst); for (auto& t : o.d_tex) dev_free(t); };
+    auto cleanup = [&]() { zr_object_free_device(o); };
     std::vector<uint8_t> chains[7];
     int lead = -1;                                          // first slot that holds an image
     for (int t = 0; t < 7; ++t) {
@@ -631,7 +634,7 @@ int zr_object_add_internal(zr_ctx* c, uint32_t mesh_id, const ZrMaterialHost& ma
     }
     zr_launch_instance_prep(d_raw, o.d_inst, o.n_inst, o.instanced ? 1u : 0u, c->stream);
     hipError_t e = zr_sync_all(c);
-    dev_free(d_raw);
+    o.d_raw = d_raw;                    // (kept: the authoritative values of zr_object_set_instances / zr_object_update_instances_async)
     if (e != hipSuccess) { cleanup(); return zr_fail(c, ZR_ERR_DEVICE, hipGetErrorString(e)); }
     c->objects.push_back(std::move(o));
     c->scene_dirty = true; c->scene_gen++;
@@ -759,8 +762,9 @@ static int finalize_scene(zr_ctx* c)
     if (sky) { int rc = upload_mesh(c, c->sky_mesh); if (rc) return rc; }
     std::vector<ZrObject> tab;
     uint64_t work = 0, prim = 0, inst_total = 0;
-    auto emit = [&](const ZrSceneObject& o, const ZrMesh& m, uint32_t flags) {
+    auto emit = [&](ZrSceneObject& o, const ZrMesh& m, uint32_t flags) {
         ZrObject d; memset(&d, 0, sizeof d);
+        o.draw = (uint32_t)tab.size();
         d.verts = m.d_v; d.rverts = m.d_rv; d.rtris = m.d_rt; d.indices = m.d_idx; d.meshlets = m.d_meshlets; d.mpos = m.d_mpos; d.mbox = m.d_mbox; d.mtri = m.d_mtri; d.tri_meshlet = m.d_tri_meshlet;
         d.inst = o.d_inst;
         d.n_meshlets = (uint32_t)m.ms.meshlets.size(); d.n_tris = (uint32_t)(m.idx.size() / 3);
@@ -794,9 +798,11 @@ static int finalize_scene(zr_ctx* c)
     const uint64_t scene_work = work, scene_inst = inst_total;
     if (sky) emit(c->sky_obj, c->sky_mesh, ZR_OBJ_SKY);
     if (work >= 0xFFFFFFFFull || prim >= 0xFFFFFFFFull) return zr_fail(c, ZR_ERR_OVERFLOW, "scene exceeds 2^32 meshlet-instances or primitives");
-    dev_free(c->d_objs);
-    HIPCHK(c, upload(&c->d_objs, tab));
+    dev_free(c->d_objs_b[0]);
+    HIPCHK(c, upload(&c->d_objs_b[0], tab));
+    c->d_objs = c->d_objs_b[0];
     c->n_objs = (uint32_t)tab.size(); c->n_work = (uint32_t)scene_work; c->n_inst_total = (uint32_t)scene_inst;
+    { int rc = zr_instances_table(c); if (rc) return rc; }      // (objects with updated instances: the parity-1 table, n_objs records)
     c->sky_object = sky ? (uint32_t)tab.size() - 1u : 0u;
     if (sky && !c->d_sky_keys) HIPCHK(c, dev_alloc(&c->d_sky_keys, (size_t)c->W * c->H));
     if (c->n_work > c->work_capacity) {
@@ -1317,6 +1323,9 @@ static int frame_begin(zr_ctx* c, hipStream_t s)
     if (s != c->stream && c->frame_no >= 2) HIPCHK(c, hipStreamWaitEvent(s, c->ev_end[(c->frame_no - 2) % zr_ctx::END_RING], 0));
     // ... and by an identity census enqueued against them since (zr_instance_coverage_async, on the host's stream)
     if (c->ids_wait[par]) { if (s != c->stream) HIPCHK(c, hipStreamWaitEvent(s, c->ev_ids[par], 0)); c->ids_wait[par] = false; }
+    // this frame's draw table; instance updates since the last frame of this parity go into its planes (zr_instances_host.cpp)
+    rc = zr_instances_frame(c, s, par);
+    if (rc) return rc;
     c->timing_now = c->timing_interval != 0 && c->frame_no % c->timing_interval == 0;     // pass events cost ~6 us of stream bubble each
     hipEvent_t* ev = c->timing_now ? c->evr[c->sample_no % zr_ctx::EV_RING] : nullptr;
     if (ev) HIPCHK(c, hipEventRecord(ev[0], s));

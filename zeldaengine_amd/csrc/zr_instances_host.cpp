@@ -1,0 +1,222 @@
+// zr_instances_host.cpp — moving instances between frames: zr_object_set_instances (host data, through a pinned staging ring) and
+// zr_object_update_instances_async (caller-owned device data, in the order of the caller's stream).  Kernels: zr_instances.hip.
+//
+// Ordering ("Moving instances").  A frame of parity p reads the draw table and the instance planes of parity p; an update
+// writes only the raw values and the stale lists, and the records of plane p are rebuilt at the head of the next frame of parity p, after
+// the last frame that read plane p has finished.  So a frame already enqueued keeps the values it was enqueued with, and no update waits
+// for a frame.  Raw values are written by k_instance_scatter and read by k_instance_apply: every scatter is ordered after the last apply
+// (ev_apply), and every apply after the last scatter (ev_scatter).
+#include <algorithm>
+#include <cstring>
+
+#include "zr_ctx.h"
+
+#define HIPCHK(c, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) \
+    return zr_fail((c), ZR_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); } while (0)
+
+static int inst_init_ctx(zr_ctx* c)
+{
+    if (c->ev_scatter) return ZR_OK;
+    HIPCHK(c, hipEventCreateWithFlags(&c->ev_apply, hipEventDisableTiming));
+    for (auto& r : c->inst_ring) HIPCHK(c, hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
+    HIPCHK(c, hipEventCreateWithFlags(&c->ev_scatter, hipEventDisableTiming));      // (last: it marks the set as made)
+    return ZR_OK;
+}
+
+// An object's first update: the parity-1 plane (a copy of the records every frame has read so far), the stale bits and lists, on x.
+static int inst_init_object(zr_ctx* c, ZrSceneObject& o, hipStream_t x)
+{
+    if (o.upd.plane[1]) return ZR_OK;
+    const size_t n = o.n_inst;
+    ZrInstanceState S = {};
+    S.raw = o.d_raw; S.plane[0] = o.d_inst; S.n_inst = o.n_inst;
+    hipError_t e = hipMalloc((void**)&S.plane[1], n * sizeof(ZrInstance));
+    if (e == hipSuccess) e = hipMalloc((void**)&S.dirty, (3 * n + 2) * sizeof(uint32_t));
+    if (e != hipSuccess) {
+        if (S.plane[1]) (void)hipFree(S.plane[1]);
+        return zr_fail(c, ZR_ERR_OOM, std::string("instance update state: ") + hipGetErrorString(e));
+    }
+    S.list[0] = S.dirty + n; S.list[1] = S.dirty + 2 * n; S.count = S.dirty + 3 * n;
+    o.upd = S; o.pending[0] = o.pending[1] = 0; o.tab1 = false;
+    HIPCHK(c, hipMemsetAsync(S.dirty, 0, n * sizeof(uint32_t), x));
+    HIPCHK(c, hipMemsetAsync(S.count, 0, 2 * sizeof(uint32_t), x));
+    // (plane 0 is written only by applies of this object, and there has been none)
+    HIPCHK(c, hipMemcpyAsync(S.plane[1], o.d_inst, n * sizeof(ZrInstance), hipMemcpyDeviceToDevice, x));
+    if (!c->inst_dual && !c->scene_dirty) {
+        // the parity-1 draw table: table 0 as it stands (nothing writes it); the frame head points it at the parity-1 planes.  (A dirty
+        // scene gets both tables from finalize_scene, before its next frame.)
+        HIPCHK(c, hipMalloc((void**)&c->d_objs_b[1], (size_t)c->n_objs * sizeof(ZrObject)));
+        HIPCHK(c, hipMemcpyAsync(c->d_objs_b[1], c->d_objs_b[0], (size_t)c->n_objs * sizeof(ZrObject), hipMemcpyDeviceToDevice, x));
+        c->inst_dual = true;
+    }
+    return ZR_OK;
+}
+
+static int inst_object(zr_ctx* c, uint32_t index, uint32_t first, uint32_t n, const char* what, ZrSceneObject** out)
+{
+    if (c->stage != 0) return zr_fail(c, ZR_ERR_STATE, std::string(what) + " between the stages of a frame (finish it with zr_render_lighting first)");
+    if (index >= c->objects.size()) return zr_fail(c, ZR_ERR_ARG, std::string(what) + ": bad object index");
+    ZrSceneObject& o = c->objects[index];
+    if (!o.instanced || !o.d_raw) return zr_fail(c, ZR_ERR_ARG, std::string(what) + ": object " + std::to_string(index) + " is not instanced");
+    if ((uint64_t)first + n > o.n_inst)
+        return zr_fail(c, ZR_ERR_ARG, std::string(what) + ": instances [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + n) +
+                                      ") beyond the object's " + std::to_string(o.n_inst));
+    *out = &o;
+    return ZR_OK;
+}
+
+// k_instance_scatter of (idx, data) on stream x, behind the last apply and the last update
+static int inst_enqueue(zr_ctx* c, ZrSceneObject& o, hipStream_t x, const uint32_t* idx, const XkInstanceData* data, uint32_t first, uint32_t n)
+{
+    int rc = inst_init_ctx(c);
+    if (rc == ZR_OK) rc = inst_init_object(c, o, x);
+    if (rc) return rc;
+    if (c->apply_done && c->apply_s != x) HIPCHK(c, hipStreamWaitEvent(x, c->ev_apply, 0));       // it read the raw values
+    if (c->scatter_s && c->scatter_s != x) HIPCHK(c, hipStreamWaitEvent(x, c->ev_scatter, 0));    // updates land in call order
+    zr_launch_instance_scatter(idx, data, first, n, o.upd, x);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev_scatter, x));
+    c->scatter_s = x; c->scatter_wait[0] = c->scatter_wait[1] = true;
+    for (auto& p : o.pending) p = (uint32_t)std::min<uint64_t>(o.n_inst, (uint64_t)p + n);
+    // The passes' work lists (k_cull_instances) hold the instances that passed the whole-mesh test: rebuilt by the next frame.  The visibility
+    // history, the bucket plan and the shadow flags stay: the frame does not depend on them.
+    c->list_valid[0] = c->list_valid[1] = false;
+    return ZR_OK;
+}
+
+static int zr_object_set_instances_impl(zr_ctx* c, uint32_t index, uint32_t first, const XkInstanceData* data, uint32_t n)
+{
+    if (!c) return ZR_ERR_ARG;
+    ZrSceneObject* o = nullptr;
+    int rc = inst_object(c, index, first, n, "zr_object_set_instances", &o);
+    if (rc) return rc;
+    if (n == 0) return ZR_OK;
+    if (!data) return zr_fail(c, ZR_ERR_ARG, "zr_object_set_instances: no data");
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = inst_init_ctx(c);
+    if (rc) return rc;
+    // the camera lane: an update that follows frame k is then ordered behind frame k's camera pipeline and ahead of frame k + 1's, with no
+    // extra wait on the host's stream, where frame k's lighting runs
+    hipStream_t x = c->cam_s ? c->cam_s : c->stream;
+    zr_ctx::InstStage& r = c->inst_ring[c->inst_slot++ % zr_ctx::INST_RING];
+    HIPCHK(c, hipEventSynchronize(r.ev));          // the copy and the scatter that used this slot last are done
+    if (r.cap < n) {
+        if (r.h) { (void)hipHostFree(r.h); r.h = nullptr; }
+        if (r.d) { (void)hipFree(r.d); r.d = nullptr; }
+        r.cap = 0;
+        size_t cap = 4096; while (cap < n) cap *= 2;
+        HIPCHK(c, hipHostMalloc((void**)&r.h, cap * sizeof(XkInstanceData), hipHostMallocDefault));
+        HIPCHK(c, hipMalloc((void**)&r.d, cap * sizeof(XkInstanceData)));
+        r.cap = cap;
+    }
+    memcpy(r.h, data, (size_t)n * sizeof(XkInstanceData));
+    HIPCHK(c, hipMemcpyAsync(r.d, r.h, (size_t)n * sizeof(XkInstanceData), hipMemcpyHostToDevice, x));
+    rc = inst_enqueue(c, *o, x, nullptr, r.d, first, n);
+    if (rc) return rc;
+    HIPCHK(c, hipEventRecord(r.ev, x));
+    if (!o->host_stale) memcpy(o->inst.data() + first, data, (size_t)n * sizeof(XkInstanceData));      // (else the read-back brings it)
+    return ZR_OK;
+}
+extern "C" int zr_object_set_instances(zr_ctx* c, uint32_t index, uint32_t first, const XkInstanceData* data, uint32_t n)
+{
+    return zr_guard(c, [&]() { return zr_object_set_instances_impl(c, index, first, data, n); });
+}
+
+static int zr_object_update_instances_async_impl(zr_ctx* c, uint32_t index, uint32_t first, const uint32_t* idx_dev,
+                                                 const XkInstanceData* data_dev, uint32_t n, void* hip_stream)
+{
+    if (!c) return ZR_ERR_ARG;
+    ZrSceneObject* o = nullptr;
+    int rc = inst_object(c, index, first, n, "zr_object_update_instances_async", &o);
+    if (rc) return rc;
+    if (n == 0) return ZR_OK;
+    if (!data_dev || ((uintptr_t)data_dev & 3u) || ((uintptr_t)idx_dev & 3u))
+        return zr_fail(c, ZR_ERR_ARG, "zr_object_update_instances_async: data_dev missing, or a buffer not 4-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t x = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    rc = inst_enqueue(c, *o, x, idx_dev, data_dev, first, n);
+    if (rc) return rc;
+    o->host_stale = true;
+    return ZR_OK;
+}
+extern "C" int zr_object_update_instances_async(zr_ctx* c, uint32_t index, uint32_t first, const uint32_t* idx_dev,
+                                                const XkInstanceData* data_dev, uint32_t n, void* hip_stream)
+{
+    return zr_guard(c, [&]() { return zr_object_update_instances_async_impl(c, index, first, idx_dev, data_dev, n, hip_stream); });
+}
+
+int zr_instances_sync_host(zr_ctx* c, ZrSceneObject& o)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->ev_scatter) HIPCHK(c, hipEventSynchronize(c->ev_scatter));      // the last update has landed in the raw values
+    HIPCHK(c, hipMemcpy(o.inst.data(), o.d_raw, (size_t)o.n_inst * sizeof(XkInstanceData), hipMemcpyDeviceToHost));
+    o.host_stale = false;
+    return ZR_OK;
+}
+
+// finalize_scene, after a full synchronisation and a new table 0: the parity-1 table, when some object has been updated
+int zr_instances_table(zr_ctx* c)
+{
+    if (c->d_objs_b[1]) { (void)hipFree(c->d_objs_b[1]); c->d_objs_b[1] = nullptr; }
+    c->inst_dual = false;
+    c->inst_reader[0] = c->inst_reader[1] = 0;      // (nothing is in flight)
+    bool any = false;
+    for (auto& o : c->objects) { o.tab1 = false; any |= o.upd.plane[1] != nullptr; }
+    if (!any) return ZR_OK;
+    HIPCHK(c, hipMalloc((void**)&c->d_objs_b[1], (size_t)c->n_objs * sizeof(ZrObject)));
+    HIPCHK(c, hipMemcpy(c->d_objs_b[1], c->d_objs_b[0], (size_t)c->n_objs * sizeof(ZrObject), hipMemcpyDeviceToDevice));
+    c->inst_dual = true;
+    return ZR_OK;
+}
+
+// frame_begin on stream s, after its wait for the frame two before: this frame's draw table; the updates due in this parity's planes
+int zr_instances_frame(zr_ctx* c, hipStream_t s, int par)
+{
+    if (!c->inst_dual) {       // (no update since the scene was made: every frame reads table 0)
+        c->d_objs = c->d_objs_b[0]; c->inst_reader[0] = c->frame_no + 1;
+        return ZR_OK;
+    }
+    bool work = false;
+    for (const auto& o : c->objects) work |= o.pending[par] != 0 || (par == 1 && o.upd.plane[1] && !o.tab1);
+    if (c->scatter_wait[par]) {       // the raw values and lists as the last update left them
+        if (c->scatter_s != s) HIPCHK(c, hipStreamWaitEvent(s, c->ev_scatter, 0));
+        c->scatter_wait[par] = false;
+    }
+    if (work) {
+        // The last frame that read this parity's table and planes: two lanes wait for the frame two before only (frame_begin), but until
+        // the first update every frame read parity 0's, the one before this frame among them.  (On the host's stream every frame's
+        // lighting pass - its last reader - is ahead of this point.)
+        const uint64_t r = c->inst_reader[par];
+        if (r && s != c->stream && (c->frame_no < 2 || r - 1 > c->frame_no - 2))
+            HIPCHK(c, hipStreamWaitEvent(s, c->ev_end[(r - 1) % zr_ctx::END_RING], 0));
+        if (c->apply_done && c->apply_s != s) HIPCHK(c, hipStreamWaitEvent(s, c->ev_apply, 0));      // (ev_apply keeps covering every apply)
+        for (auto& o : c->objects) {
+            if (o.draw >= c->n_objs) return zr_fail(c, ZR_ERR_STATE, "instance update: object outside the draw table");
+            if (par == 1 && o.upd.plane[1] && !o.tab1) { zr_launch_table_set_inst(c->d_objs_b[1], o.draw, o.upd.plane[1], s); o.tab1 = true; }
+            if (o.pending[par]) {
+                zr_launch_instance_apply(o.upd, (uint32_t)par, o.pending[par], s);
+                HIPCHK(c, hipMemsetAsync(o.upd.count + par, 0, sizeof(uint32_t), s));
+                o.pending[par] = 0;
+            }
+        }
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(c->ev_apply, s));
+        c->apply_s = s; c->apply_done = true;
+        if (s != c->stream) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_apply, 0));      // the shadow pipeline reads them there
+    }
+    c->d_objs = c->d_objs_b[par]; c->inst_reader[par] = c->frame_no + 1;
+    return ZR_OK;
+}
+
+void zr_instances_destroy(zr_ctx* c)
+{
+    for (auto& r : c->inst_ring) {
+        if (r.h) (void)hipHostFree(r.h);
+        if (r.d) (void)hipFree(r.d);
+        if (r.ev) (void)hipEventDestroy(r.ev);
+        r = zr_ctx::InstStage{};
+    }
+    if (c->ev_scatter) (void)hipEventDestroy(c->ev_scatter);
+    if (c->ev_apply) (void)hipEventDestroy(c->ev_apply);
+    c->ev_scatter = c->ev_apply = nullptr;
+}

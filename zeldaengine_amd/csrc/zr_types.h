@@ -196,8 +196,23 @@ struct GBufferPtrs {
 // Cubemap mip chain, level l = 6 faces of (dim >> l)^2 RGBA8 sRGB texels, face-major.
 struct CubeDesc { const uint8_t* levels[16]; };
 
-// launchers: each defined in the .hip of its pass (zr_cull / zr_shadow / zr_camera / zr_resolve / zr_lighting / zr_forward / zr_frame)
+// Device state of an instanced object that has been updated (zr_instances.hip): raw values, the two parity planes, per parity the list
+// of instances whose record in that plane is stale (dirty: bit p = on list p; count[p] = length of list p).
+struct ZrInstanceState {
+    XkInstanceData* raw;
+    ZrInstance* plane[2];
+    uint32_t* dirty;
+    uint32_t* list[2];
+    uint32_t* count;
+    uint32_t n_inst;
+};
+
+// launchers: each defined in the .hip of its pass (zr_cull / zr_shadow / zr_camera / zr_resolve / zr_lighting / zr_forward / zr_frame /
+// zr_instances)
 void zr_launch_instance_prep(const XkInstanceData* in, ZrInstance* out, uint32_t n, uint32_t instanced, hipStream_t s);
+void zr_launch_instance_scatter(const uint32_t* idx, const XkInstanceData* data, uint32_t first, uint32_t n, const ZrInstanceState& S, hipStream_t s);
+void zr_launch_instance_apply(const ZrInstanceState& S, uint32_t par, uint32_t bound, hipStream_t s);
+void zr_launch_table_set_inst(ZrObject* tab, uint32_t draw, const ZrInstance* plane, hipStream_t s);
 void zr_launch_cull(const ZrPass& P, const ZrObject* objs, uint32_t* work, uint32_t* rects, const ZrHiz& Z, ZrDevStats* stats,
                     int slot, uint32_t n_waves, hipStream_t s);
 void zr_launch_bin_count(const ZrPass& P, const uint32_t* work, uint32_t* rects, uint32_t* tile_count, const ZrHiz& Z, ZrDevStats* stats,

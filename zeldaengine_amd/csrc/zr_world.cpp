@@ -276,10 +276,7 @@ int apply_world(zr_ctx* c, const ZrWorld& w)
     int rc = ZR_OK;
     {
         auto keep_m = std::move(c->meshes); auto keep_p = std::move(c->profabs);
-        for (auto& o : c->objects) {
-            if (o.d_inst) { (void)hipFree(o.d_inst); o.d_inst = nullptr; }
-            for (auto& t : o.d_tex) if (t) { (void)hipFree(t); t = nullptr; }
-        }
+        for (auto& o : c->objects) zr_object_free_device(o);
         c->objects.clear(); c->scene_dirty = true; c->scene_gen++;
         c->meshes = std::move(keep_m); c->profabs = std::move(keep_p);
     }
@@ -485,6 +482,7 @@ extern "C" int zr_object_get_instances(zr_ctx* c, uint32_t index, uint32_t* mesh
     const ZrSceneObject& o = c->objects[index];
     if (mesh_id) *mesh_id = o.mesh;
     *n = o.instanced ? o.n_inst : 0;
+    if (dst && o.instanced && o.host_stale) { int rc = zr_instances_sync_host(c, c->objects[index]); if (rc) return rc; }
     if (dst && o.instanced) memcpy(dst, o.inst.data(), sizeof(XkInstanceData) * o.n_inst);
     return ZR_OK;
 }

@@ -53,6 +53,8 @@ def lib():
         "zr_set_bucket_share": [vp, u32],
         "zr_object_count": [vp, C.POINTER(u32)],
         "zr_object_get_instances": [vp, u32, C.POINTER(u32), vp, C.POINTER(u32)],
+        "zr_object_set_instances": [vp, u32, u32, vp, u32],
+        "zr_object_update_instances_async": [vp, u32, u32, vp, vp, u32, vp],
         "zr_set_cubemap": [vp, vp, u32],
         "zr_set_skydome": [vp, vp, u32, vp, u32, vp],
         "zr_set_background": [vp, vp],
@@ -323,6 +325,26 @@ class Renderer:
         if n.value:
             self._chk(self.L.zr_object_get_instances(self.h, index, C.byref(mesh), _ptr(inst), C.byref(n)))
         return mesh.value, (inst if n.value else None)
+
+    def object_set_instances(self, index, instances, first=0):
+        """Replace instances [first, first + len(instances)) of instanced object `index` (an abi.XkInstanceData array) from the next
+        frame on (zr_object_set_instances); frames already enqueued keep the old values."""
+        inst = np.ascontiguousarray(instances)
+        assert inst.dtype == abi.XkInstanceData
+        self._chk(self.L.zr_object_set_instances(self.h, index, first, _ptr(inst), inst.size))
+
+    def object_update_instances_async(self, index, data, idx=None, first=0, stream=None):
+        """The same from device tensors, in the order of `stream` (a torch.cuda.Stream or a HIP stream handle; None = the render stream):
+        data = uint8 [n, 32] (or any contiguous view of n XkInstanceData), idx = None (instances first .. first + n - 1) or int32 [n]
+        (the object's own indices; those >= its instance count are ignored).  Both may be overwritten by work enqueued on `stream`
+        afterwards (zr_object_update_instances_async)."""
+        assert data.is_cuda and data.is_contiguous() and data.numel() * data.element_size() % abi.XkInstanceData.itemsize == 0
+        n = data.numel() * data.element_size() // abi.XkInstanceData.itemsize
+        if idx is not None:
+            assert idx.is_cuda and idx.is_contiguous() and idx.element_size() == 4 and idx.numel() == n
+        h = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        self._chk(self.L.zr_object_update_instances_async(self.h, index, first, C.c_void_p(idx.data_ptr()) if idx is not None else None,
+                                                          C.c_void_p(data.data_ptr()) if n else None, n, C.c_void_p(h) if h else None))
 
     def set_cubemap(self, faces):
         if faces is None:
