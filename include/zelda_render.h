@@ -60,8 +60,7 @@ typedef struct zr_ctx zr_ctx;
 #define ZR_FLAG_NO_HIZ          8u  /* disable two-pass Hi-Z occlusion culling of the camera pass (parity A/B) */
 #define ZR_FLAG_SERIAL_PASSES   16u /* zr_render: shadow and camera pipelines on the one stream instead of side by side */
 #define ZR_FLAG_PACKED_TILES    32u /* tile_world == 1: still light into the packed tile buffer (the multi-GPU data path on one GPU) */
-#define ZR_FLAG_MESHLET_BINS   128u /* -DZR_DIAG builds only (zr_create: ZR_ERR_UNSUPPORTED otherwise): camera pass through the meshlet-binned
-                                     * rasteriser the shadow pass uses, instead of the triangle-binned one (A/B measurements) */
+#define ZR_FLAG_MESHLET_BINS   128u /* reserved: zr_create answers it with ZR_ERR_UNSUPPORTED */
 #define ZR_FLAG_NO_RECT_CULL    64u /* tile_world > 1: do not reject meshlets by the rank's owned screen region before stage B (parity A/B) */
 #define ZR_FLAG_NO_LIST_REUSE  256u /* rebuild the passes' instance-level work lists every frame instead of only when camera / light matrices or the
                                      * scene change (parity A/B; the lists are an acceleration structure, never pixels) */
@@ -90,13 +89,11 @@ typedef struct zr_camera { float Position[3]; float Lookat[3]; float Speed, FOV,
 
 /* Per-pass GPU timings of the last zr_render, milliseconds (hipEvents on the render stream). */
 enum { ZR_PASS_CULL_SHADOW = 0,   /* k_cull_box<SHADOW> + k_bin_count + k_scan + k_bin_fill (the map's clear rides in the previous lighting pass) */
-       ZR_PASS_SHADOW,            /* k_raster_chunks<SHADOW> + k_tile_slow<SHADOW> (clipped triangles) */
-       ZR_PASS_CULL_CAMERA,       /* k_cull_box<GBUFFER> (also compacts round 1's list: last frame's visible set)
-                                     [ZR_FLAG_MESHLET_BINS: k_cull<GBUFFER> + k_bin_count + k_scan + k_bin_fill] */
-       ZR_PASS_GBUFFER,           /* round 1 (the whole pass when the frame runs in one round): k_geom + k_scan_tri + k_index + k_tile
-                                     [ZR_FLAG_MESHLET_BINS: k_raster_chunks<GBUFFER>] */
-       ZR_PASS_HIZ,               /* k_hiz_build + round 2's k_select [.. k_bin_count + k_scan + k_bin_fill] (0 in a one-round frame) */
-       ZR_PASS_GBUFFER2,          /* round 2: k_geom<Hi-Z> + k_scan_tri + k_index + k_tile (the last round also draws both rounds' clipped triangles) [.. k_raster_chunks<GBUFFER, Hi-Z>] */
+       ZR_PASS_SHADOW,            /* k_raster_chunks + k_tile_slow<SHADOW> (clipped triangles) */
+       ZR_PASS_CULL_CAMERA,       /* k_cull_box<GBUFFER> (also compacts round 1's list: last frame's visible set) */
+       ZR_PASS_GBUFFER,           /* round 1 (the whole pass when the frame runs in one round): k_geom + k_tile */
+       ZR_PASS_HIZ,               /* k_hiz_build + round 2's k_select (0 in a one-round frame) */
+       ZR_PASS_GBUFFER2,          /* round 2: k_geom<Hi-Z> + k_tile (the last round also draws both rounds' clipped triangles) */
        ZR_PASS_RESOLVE,           /* k_resolve_gbuffer: the GBuffer write */
        ZR_PASS_LIGHTING,          /* k_lighting */
        ZR_PASS_COMPOSITE, ZR_PASS_TOTAL, ZR_PASS_COUNT };

@@ -333,8 +333,7 @@ def test_config5_reduced_against_the_oracle_with_a_moving_camera(oracle_lib, gpu
 def test_camera_pass_against_the_oracle_with_and_without_hiz_rounds(oracle_lib, gpu_engine):
     """The triangle-binned camera pass (k_cull_box, k_geom, k_tile) over the history sequence, with and without the Hi-Z rounds:
     both must give the oracle's frame, and the slow-triangle list must be exercised (the ground plane crosses the near plane; the
-    wall's triangles are longer than 64 pixels).  (The meshlet-binned A/B rasteriser for the camera pass exists in -DZR_DIAG builds only:
-    the product library refuses ZR_FLAG_MESHLET_BINS.)"""
+    wall's triangles are longer than 64 pixels).  (ZR_FLAG_MESHLET_BINS is a reserved bit: the library refuses it.)"""
     W, H, SD = 384, 216, 256
     o = oracle_lib.Oracle(W, H, SD)
     gs = [gpu_engine.Renderer(W, H, SD, flags=f) for f in (0, abi.FLAG_NO_HIZ)]

@@ -37,6 +37,7 @@ SHORT = {"k_raster_chunks<0, false>": "k_raster<GBUFFER>", "k_raster_chunks<0, t
          "k_raster_chunks<1, false>": "k_raster<SHADOW>", "k_raster_chunks<1, false, true>": "k_raster<SHADOW>", "k_raster_chunks<1, false, false>": "k_raster<SHADOW>",
          "k_raster_chunks<1, false, true, false>": "k_raster<SHADOW>", "k_raster_chunks<1, false, false, false>": "k_raster<SHADOW>",
          "k_raster_chunks<1, false, true, true>": "k_raster<SHADOW,late>", "k_raster_chunks<1, false, false, true>": "k_raster<SHADOW,late>",      # after k_shadow_occlusion
+         "k_raster_chunks<false>": "k_raster<SHADOW>", "k_raster_chunks<true>": "k_raster<SHADOW,late>",      # (the shadow rasteriser's one form, <LATE>)
          "k_shadow_occlusion<true>": "k_shadow_occlusion", "k_shadow_occlusion<false>": "k_shadow_occlusion",
          "k_raster_chunks<0, false, false>": "k_raster<GBUFFER>", "k_raster_chunks<0, true, false>": "k_raster<GBUFFER,HiZ>",
          "k_tile_slow<0, false>": "k_tile_slow<GBUFFER>", "k_tile_slow<1, true>": "k_tile_slow<SHADOW>",

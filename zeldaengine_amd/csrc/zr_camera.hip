@@ -64,15 +64,14 @@ __global__ __launch_bounds__(256) void k_hiz_build(const unsigned long long* __r
 
 // ------------------------------------------------------------------------------------------------ triangle-binned camera pass
 //
-// A meshlet-binned rasteriser re-transforms a meshlet's vertices and re-tests all of its triangles in every tile the meshlet touches
-// (2.5 on average in the camera pass) and walks the survivors in whatever mix of sizes the queue hands a wave.
+// A meshlet-binned rasteriser (the shadow pass's) re-transforms a meshlet's vertices and re-tests all of its triangles in every tile the
+// meshlet touches (2.5 on average in the camera pass) and walks the survivors in whatever mix of sizes the queue hands a wave.
 // Here a meshlet is processed ONCE: k_geom transforms its vertices, applies the exact per-triangle tests (facing, degenerate, no
 // pixel centre, Hi-Z in round 2) and appends one 32-byte record per (triangle, owned tile) - vertices relative to the tile, three depths,
 // the primitive id - to that tile's BUCKET of the record arrays (laid out by k_plan from the previous frame's counts: "triangle records"
-// below); k_tile's lanes read a bucket as one run and do nothing but edge setup + walk on live triangles.  Same arithmetic, same keys as the
-// meshlet-binned path (kept in -DZR_DIAG builds for A/B): the frame is the same bit for bit.
+// below); k_tile's lanes read a bucket as one run and do nothing but edge setup + walk on live triangles.
 
-// Which meshlet-instances does this round draw?  (The split of the two-pass occlusion culling, as k_bin_count makes it.)
+// Which meshlet-instances does this round draw?  (The split of the two-pass occlusion culling.)
 // Compacted per workgroup: one global atomic per 1024 work items (atomics on one address run at ~10 ns apiece on this part).
 #define ZR_SELECT_THREADS 256
 __global__ __launch_bounds__(256) void k_select(ZrPass P, const ZrObject* __restrict__ objs, const uint32_t* __restrict__ work,

@@ -111,9 +111,11 @@ struct zr_ctx {
     uint32_t *d_sowned_rank = nullptr, *d_stile_map = nullptr;
     uint32_t* d_tiles_ext = nullptr;     // caller-owned packed tile buffer for the next frames (zr_set_tiles_buffer), or null
 
-    // cull / bin scratch, one set per geometry pass (0 shadow, 1 camera) so that the two pipelines can run on two streams
-    struct Scratch { uint32_t *rects = nullptr, *tile_count = nullptr, *tile_offset = nullptr, *tile_cursor = nullptr, *chunk_offset = nullptr,
-                     *work = nullptr; ZrBinEntry* bins = nullptr; uint4* chunk_tab = nullptr; } sc[2];
+    // the cull's output, one set per geometry pass (0 shadow, 1 camera) so that the two pipelines can run on two streams
+    struct CullList { uint32_t *rects = nullptr, *work = nullptr; } sc[2];
+    // the shadow pass's meshlet bins: per-tile counts, list offsets, fill cursors and work-unit offsets; the lists; the work units
+    struct ShadowBins { uint32_t *tile_count = nullptr, *tile_offset = nullptr, *tile_cursor = nullptr, *chunk_offset = nullptr;
+                        ZrBinEntry* bins = nullptr; uint4* chunk_tab = nullptr; } sb;
     uint32_t bucket_pct = 100;                              // zr_set_bucket_share: every planned bucket at that share of its size
     bool plan_valid = false, plan_two_round = false;      // the record buckets' plan (k_plan): made at all / by a frame that drew two rounds
     ZrTriBins tb = {};                    // triangle-binned camera pass: selection list, records (as emitted / in tile order), slow list
@@ -121,8 +123,8 @@ struct zr_ctx {
     uint32_t n_inst_total = 0;
     // one pixel holding the clear value of every GBuffer target, and the colour the lighting shader gives it this frame
     uint8_t* d_clear_px = nullptr; GBufferPtrs Gclear = {}; uint32_t* d_empty_rgba = nullptr; bool empty_ready = false;
-    // diagnostics / A-B switches read from the environment once, at zr_create (never needed for a correct frame)
-    uint32_t env_skip = 0, env_skip_light = 0; int32_t env_light_list_min = 4; bool env_no_empty_px = false, env_serial = false;
+    // diagnostics read from the environment once, at zr_create, by -DZR_DIAG builds (never needed for a correct frame)
+    uint32_t env_skip = 0, env_skip_light = 0; int32_t env_light_list_min = 4; bool env_no_empty_px = false;
     // XkView upload: a pageable-memory hipMemcpyAsync blocks the host until the stream has drained (~0.3 ms per frame here),
     // so the uniforms go through a small ring of pinned copies, and only when they changed
     static constexpr int VIEW_RING = 4;
@@ -134,10 +136,6 @@ struct zr_ctx {
     // d_view, d_empty_rgba are aliases of the current frame's copies (set at frame begin, so the read-back entry points see the
     // frame rendered last).
     hipStream_t cam_s = nullptr; bool camera_on_lane = false;
-    // Experiment kept behind ZR_LANES=3 (zr_render only, not the staged entry points): the shadow pipeline and the lighting pass on
-    // streams of their own as well, so that frame N's lighting, frame N + 1's shadow pipeline and frame N + 1's camera pipeline all run
-    // side by side and the host's stream only joins the finished frame.  Measured SLOWER than two lanes: the
-    // camera pipeline - a chain of short kernels - is then starved by two heavy neighbours instead of one.
     bool in_render = false;
     hipEvent_t ev_join = nullptr, ev_cam = nullptr;
     unsigned long long* d_sky_keys = nullptr; uint32_t sky_object = 0;      // the skydome's key plane (k_sky_tiles) and its draw record
@@ -150,7 +148,7 @@ struct zr_ctx {
     uint32_t* d_empty_b[2] = { nullptr, nullptr };
     bool overlay_dirty[2] = { false, false };       // Gb[i].overlay may hold skydome pixels of an earlier frame
     bool shadow_cleared[2] = { false, false };      // d_shadow_b[i] already holds depth 1.0 (cleared by the previous lighting pass)
-    unsigned long long* d_vis = nullptr; uint32_t raster_blocks = 2048, shadow_blocks = 2048; bool env_shadow_box = true, env_shadow_defer = true;
+    unsigned long long* d_vis = nullptr; uint32_t raster_blocks = 2048, shadow_blocks = 2048;
     uint4* d_slow0 = nullptr; uint32_t slow0_cap = 1u << 18;      // shadow pass: triangles for the clipper (k_tile_slow)
     uint32_t work_capacity = 0, bin_capacity = 0; bool any_images = false, mixed_images = false;
     uint32_t limit_record_chunks = 0, limit_slow_triangles = 0;      // zr_set_limits (0 = defaults)

@@ -1,7 +1,7 @@
 // zr_cull.hip — scene preparation and culling: k_instance_prep (XkInstanceData -> ZrInstance, once per zr_object_add), k_cull_instances
 // (big scenes: whole-mesh sphere vs frustum per instance -> compacted work list), k_cull_box<MODE> (lane per meshlet-instance: frustum,
 // normal cone, owned region, then the 8 corners of the meshlet's box -> a tile rect / pixel box / least depth that BOUND the exact ones;
-// compacts the camera pass's round-1 list) and, in -DZR_DIAG builds, the exact wave-per-survivor k_cull<MODE>.  See zr_dev.h for the map.
+// compacts the camera pass's round-1 list).  See zr_dev.h for the map.
 #include "zr_dev.h"
 
 // ------------------------------------------------------------------------------------------------ instance prep
@@ -165,24 +165,9 @@ __global__ __launch_bounds__(ZR_CI_THREADS) void k_cull_instances(ZrPass P, cons
     for (uint32_t j = 0; j < ZR_CI_PER; ++j) { for (uint32_t m = 0; m < nm[j]; ++m) work[off + m] = wbase[j] + m; off += nm[j]; }
 }
 
-// Level 2, in two stages inside one wavefront that owns ZR_CULL_GROUP consecutive work items (every rejection is exact or conservative:
-// sphere-vs-frustum and the normal-cone test use inflated bounds; "all vertices outside one clip plane"
-// and "snapped bounding box holds no pixel centre" are exact):
-//   A  lane per meshlet-instance: decode, load the meshlet record and the instance, shadow-pass filters, bounding sphere
-//      against the frustum, normal cone against the eye;
-//   B  wave per survivor, ZR_CULL_BATCH of them at a time: the batch's vertex loads are issued together, then each survivor
-//      gets the lane-per-vertex transform exactly as the rasteriser will redo it, its clip flags and its snapped bounding box.
-// A wave therefore waits for memory a few times per group instead of three times per meshlet.
-// Outputs per work item k: rects[k] (packed tile rect or ZR_RECT_CULLED) and, for the camera pass, the pixel box and the least
-// vertex depth the Hi-Z test uses (zmin < 0: not testable).
-#ifndef ZR_CULL_BATCH
-#define ZR_CULL_BATCH 2
-#endif
-#ifndef ZR_CULL_GROUP
-#define ZR_CULL_GROUP 8u                     // work items per wave (stage A uses that many lanes): enough waves to fill the chip
-#endif
-
-// Stage A for one work item k (the calling lane's): decode, sphere vs frustum, normal cone, owned-region reject.
+// Level 2 (every rejection is exact or conservative: sphere-vs-frustum and the normal-cone test use inflated bounds, DESIGN.md
+// section 5), stage A for one work item k (the calling lane's): decode, load the meshlet record and the instance, shadow-pass filters,
+// bounding sphere against the frustum, normal cone against the eye, owned-region reject.  k_cull_box then bounds the survivor's box.
 struct CullItem {
     const float4* mposv;          // first vertex of the meshlet in the flattened position array
     const ZrObject* O;
@@ -246,110 +231,10 @@ __device__ __forceinline__ bool cull_stage_a(const ZrPass& P, const ZrObject* __
     return alive;
 }
 
-#ifdef ZR_DIAG      // the exact 64-lane cull: A/B builds only (ZR_SHADOW_BOX_CULL=0, ZR_FLAG_MESHLET_BINS)
-template <int MODE, bool WORKLIST>
-__global__ __launch_bounds__(256) void k_cull(ZrPass P, const ZrObject* __restrict__ objs, const uint32_t* __restrict__ work,
-                                              uint32_t* __restrict__ rects, uint2* __restrict__ pxrect, float* __restrict__ zmin,
-                                              uint8_t* __restrict__ vis_clear, const ZrDevStats* __restrict__ stats, int slot)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t n = WORKLIST ? stats->n_vis_work[slot] : P.n_work;
-    const uint32_t wave0 = wave_uniform(blockIdx.x * 4u + (threadIdx.x >> 6)), n_waves = gridDim.x * 4u;
-    for (uint32_t base = wave0 * ZR_CULL_GROUP; base < n; base += n_waves * ZR_CULL_GROUP) {
-        const uint32_t k = base + lane;
-        // ---------------------------------------------------------------- stage A: lane per meshlet-instance
-        const bool mine = lane < ZR_CULL_GROUP && k < n;
-        CullItem it;
-        it.mposv = nullptr; it.O = nullptr; it.vcount = 0; it.instanced = 0; it.m = 0; it.inst_i = 0; it.w = 0; it.tcount = 0; it.tri_base = 0;
-        for (int i = 0; i < 9; ++i) it.I.R[i] = 0.0f;
-        it.I.t[0] = it.I.t[1] = it.I.t[2] = 0.0f; it.I.s = 1.0f;
-        const bool alive = mine && cull_stage_a<MODE, WORKLIST>(P, objs, work, vis_clear, k, it);
-        const float4* mposv = it.mposv;
-        const uint32_t vcount = it.vcount, instanced = it.instanced;
-        const ZrInstance& I = it.I;
-        uint32_t out_rect = ZR_RECT_CULLED; uint2 out_px = make_uint2(0u, 0u); float out_z = -1.0f;
-        const uint32_t mp_lo = (uint32_t)(unsigned long long)mposv, mp_hi = (uint32_t)((unsigned long long)mposv >> 32);
-
-        // ---------------------------------------------------------------- stage B: wave per survivor, batched
-        unsigned long long live = __ballot(alive);
-        while (live) {
-            uint32_t src[ZR_CULL_BATCH]; float4 pp[ZR_CULL_BATCH];
-#pragma unroll
-            for (int c = 0; c < ZR_CULL_BATCH; ++c) {
-                src[c] = 64u;
-                if (live) { src[c] = (uint32_t)__builtin_ctzll(live); live &= live - 1ull; }
-                pp[c] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-                if (src[c] < 64u) {
-                    const float4* __restrict__ mp = (const float4*)(((unsigned long long)lane_bcast(mp_hi, src[c]) << 32) | lane_bcast(mp_lo, src[c]));
-                    if (lane < lane_bcast(vcount, src[c])) pp[c] = mp[lane];
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < ZR_CULL_BATCH; ++c) {
-                if (src[c] >= 64u) break;
-                ZrInstance J;
-                for (int i = 0; i < 9; ++i) J.R[i] = lane_bcast(I.R[i], src[c]);
-                J.t[0] = lane_bcast(I.t[0], src[c]); J.t[1] = lane_bcast(I.t[1], src[c]); J.t[2] = lane_bcast(I.t[2], src[c]);
-                J.s = lane_bcast(I.s, src[c]);
-                const bool inst = lane_bcast(instanced, src[c]) != 0u;
-                const uint32_t vc = lane_bcast(vcount, src[c]);
-                // The clip tests of vertex_flags() as wave-wide votes: a comparison IS a 64-lane mask on this machine, so "every vertex
-                // outside plane k" / "some vertex needs the clipper" / "some vertex is not finite" cost one v_cmp each and no cross-lane
-                // reduction.  For a plain vertex the first / last pixel centre its snapped position can bound is formed per lane
-                // ((X - 128 + 255) >> 8 and (X - 128) >> 8 are monotonic, so min / max commute with them); the four box sides travel as
-                // two packed int16 pairs: 2 wave reductions (+ 1 for the depth).
-                const bool valid = lane < vc;
-                const zf4 cl = zr_mat4_point(P.PVM, vs_position(zr3(pp[c].x, pp[c].y, pp[c].z), J, inst));
-                const float FM = 3.402823466e38f;
-                const bool fin = __builtin_fabsf(cl.x) <= FM && __builtin_fabsf(cl.y) <= FM && __builtin_fabsf(cl.z) <= FM && __builtin_fabsf(cl.w) <= FM;
-                const float gb = ZR_GUARD * cl.w;
-                const bool clip = cl.z < 0.0f || !(cl.w > 0.0f) || __builtin_fabsf(cl.x) > gb || __builtin_fabsf(cl.y) > gb;
-                const unsigned long long vm = __ballot(valid);
-                const bool any_nonfinite = __ballot(valid && !fin) != 0ull;
-                const bool any_clip = __ballot(valid && clip) != 0ull;
-                const bool all_outside = __ballot(valid && cl.x < -cl.w) == vm || __ballot(valid && cl.x > cl.w) == vm ||
-                                         __ballot(valid && cl.y < -cl.w) == vm || __ballot(valid && cl.y > cl.w) == vm ||
-                                         __ballot(valid && cl.z < 0.0f) == vm || __ballot(valid && cl.z > cl.w) == vm;
-                int lo2 = 0x7FFF7FFF, hi2 = (int)0x80008000;
-                int zb = 0x7FFFFFFF;           // least NDC depth over the vertices, as ordered int bits (depths here are >= 0)
-                if (valid && fin && !clip) {
-                    const SV sv = project(cl, P.hw, P.hh);
-                    lo2 = (clamp16((sv.X - 128 + 255) >> 8) & 0xFFFF) | (clamp16((sv.Y - 128 + 255) >> 8) << 16);
-                    hi2 = (clamp16((sv.X - 128) >> 8) & 0xFFFF) | (clamp16((sv.Y - 128) >> 8) << 16);
-                    zb = (int)zr_f2u(sv.z + 0.0f);
-                }
-                uint32_t r = ZR_RECT_CULLED; uint2 pr = make_uint2(0u, 0u); float zm = -1.0f;
-                if (any_nonfinite || !all_outside) {
-                    int px0 = 0, py0 = 0, px1 = (int)P.W - 1, py1 = (int)P.H - 1;
-                    bool any = true;
-                    if (!any_nonfinite && !any_clip) {
-                        const int lo = wave_pkmin16(lo2), hi = wave_pkmax16(hi2);
-                        px0 = max(px0, (int)(short)(lo & 0xFFFF)); py0 = max(py0, lo >> 16);
-                        px1 = min(px1, (int)(short)(hi & 0xFFFF)); py1 = min(py1, hi >> 16);
-                        any = px0 <= px1 && py0 <= py1;
-                        if (any && MODE == ZR_MODE_GBUFFER) {      // unclipped meshlet (so every z >= 0): usable for the Hi-Z test
-                            zm = zr_u2f((uint32_t)wave_min(zb));
-                            pr = make_uint2((uint32_t)px0 | (uint32_t)py0 << 16, (uint32_t)px1 | (uint32_t)py1 << 16);
-                        }
-                    }
-                    if (any) r = pack_tile_rect<MODE>(px0, py0, px1, py1);
-                }
-                if (lane == src[c]) { out_rect = r; out_px = pr; out_z = zm; }
-            }
-        }
-        if (mine) {
-            rects[k] = out_rect;
-            if (MODE == ZR_MODE_GBUFFER && pxrect) { pxrect[k] = out_px; zmin[k] = out_z; }
-        }
-    }
-}
-
-#endif   // ZR_DIAG
-
 // The triangle-binned camera pass needs no tile rectangle from the cull - k_geom tests every triangle exactly - only "is it gone" and,
 // for the Hi-Z test of round 2, a pixel box and a least depth that BOUND the meshlet's.  Those come from the eight corners of the
-// meshlet's object-space box instead of its 64 vertices, a lane per meshlet-instance instead of a wave: about a twentieth of
-// k_cull<GBUFFER>'s instructions.  The bounds are conservative by construction: a vertex lies in the box, the transforms are affine up
+// meshlet's object-space box instead of its 64 vertices, a lane per meshlet-instance instead of a wave per vertex set: about a
+// twentieth of the instructions.  The bounds are conservative by construction: a vertex lies in the box, the transforms are affine up
 // to rounding, and the rounding of both the corners' and the vertices' arithmetic is covered by an explicit margin (8 ulps of the
 // magnitudes involved, carried through the divide; at least one pixel) - culling more is never possible, only a little less.
 template <int MODE, bool WORKLIST>
@@ -497,28 +382,6 @@ void zr_launch_instance_prep(const XkInstanceData* in, ZrInstance* out, uint32_t
 {
     hipLaunchKernelGGL(k_instance_prep, dim3((n + 255) / 256), dim3(256), 0, s, in, out, n, instanced);
 }
-#ifdef ZR_DIAG
-void zr_launch_cull(const ZrPass& P, const ZrObject* objs, uint32_t* work, uint32_t* rects, const ZrHiz& Z, ZrDevStats* stats,
-                    int slot, uint32_t n_waves, hipStream_t s)
-{
-    if (P.n_work == 0) return;
-    const dim3 gi((P.n_inst_total + ZR_CI_THREADS * ZR_CI_PER - 1u) / (ZR_CI_THREADS * ZR_CI_PER)), bi(ZR_CI_THREADS), b(256);
-    // one wave per ZR_CULL_GROUP work items; with the work list the count is only known on the device: a fixed grid strides over it
-    const uint32_t all = (uint32_t)(((uint64_t)P.n_work + 4u * ZR_CULL_GROUP - 1) / (4u * ZR_CULL_GROUP));
-    const uint32_t blocks = P.use_worklist ? std::min<uint32_t>(all, std::max<uint32_t>(1u, n_waves / 4u)) : all;
-    if (P.mode == ZR_MODE_GBUFFER) {
-        if (P.use_worklist) {
-            hipLaunchKernelGGL(k_cull_instances<ZR_MODE_GBUFFER>, gi, bi, 0, s, P, objs, work, stats, slot);
-            hipLaunchKernelGGL((k_cull<ZR_MODE_GBUFFER, true>), dim3(blocks), b, 0, s, P, objs, work, rects, Z.pxrect, Z.zmin, Z.vis_now, stats, slot);
-        } else hipLaunchKernelGGL((k_cull<ZR_MODE_GBUFFER, false>), dim3(blocks), b, 0, s, P, objs, work, rects, Z.pxrect, Z.zmin, Z.vis_now, stats, slot);
-    } else {
-        if (P.use_worklist) {
-            hipLaunchKernelGGL(k_cull_instances<ZR_MODE_SHADOW>, gi, bi, 0, s, P, objs, work, stats, slot);
-            hipLaunchKernelGGL((k_cull<ZR_MODE_SHADOW, true>), dim3(blocks), b, 0, s, P, objs, work, rects, (uint2*)nullptr, (float*)nullptr, (uint8_t*)nullptr, stats, slot);
-        } else hipLaunchKernelGGL((k_cull<ZR_MODE_SHADOW, false>), dim3(blocks), b, 0, s, P, objs, work, rects, (uint2*)nullptr, (float*)nullptr, (uint8_t*)nullptr, stats, slot);
-    }
-}
-#endif
 void zr_launch_cull_box(const ZrPass& P, const ZrObject* objs, uint32_t* work, uint32_t* rects, const ZrHiz& Z, ZrDevStats* stats,
                         int slot, hipStream_t s, ZrBinEntry* sel, const uint8_t* vis_prev, bool reuse_list)
 {

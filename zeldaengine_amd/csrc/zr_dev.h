@@ -2,10 +2,10 @@
 // (Base.vert / BaseInstanced.vert / Shadowmap*.vert), wave reductions on the DPP network, the Hi-Z tests, the per-pixel kernels' grid shape.
 //
 // The render path is one .hip per pass; each compiles alone (-fno-gpu-rdc), what they share is header-only and inlined:
-//   zr_cull.hip      k_instance_prep, k_cull_instances, k_cull_box<MODE> (+ the exact k_cull<MODE> of -DZR_DIAG builds)
-//   zr_shadow.hip    shadow pass, meshlet-level binning: k_bin_count / k_scan / k_bin_fill, k_raster_chunks<MODE, HIZ, DEFER, LATE>,
+//   zr_cull.hip      k_instance_prep, k_cull_instances, k_cull_box<MODE>
+//   zr_shadow.hip    shadow pass, meshlet-level binning: k_bin_count / k_scan / k_bin_fill, k_raster_chunks<LATE>,
 //                    k_shadow_occlusion, k_count_shadow
-//   zr_camera.hip    camera pass, triangle-level binning: k_hiz_build, k_select, k_geom<HIZ>, k_scan_tri, k_index, k_tile, k_sky_tiles
+//   zr_camera.hip    camera pass, triangle-level binning: k_hiz_build, k_select, k_geom<HIZ, COUNT>, k_plan, k_tile, k_sky_tiles
 //   zr_resolve.hip   k_resolve_gbuffer: BaseScene.frag per pixel from the key buffer into the SoA GBuffer planes
 //   zr_lighting.hip  k_lighting (BaseLighting.frag), k_gbuffer_vis (debug view 9)
 //   zr_forward.hip   k_forward: the forward variant, Base.frag
@@ -42,11 +42,8 @@
 #define QCAP 128u
 #define RW (ZR_TILE >= 64 ? 8 : 4)          // waves per rasteriser workgroup: one 64x64 tile's keys (32 KB) are shared by 8 waves
 #define RTHREADS (RW * WAVE)
-#ifndef ZR_RASTER_WAVES
-#define ZR_RASTER_WAVES 4                    // waves per SIMD the tile rasteriser is compiled for (5 fits only with ~25 VGPRs spilled to scratch: +100 MB of traffic per frame for 2 % less time alone, nothing side by side)
-#endif
 #ifndef ZR_RASTER_WAVES_DEFER
-#define ZR_RASTER_WAVES_DEFER 6              // ... and the variant without the clipper in its loop (DEFER)
+#define ZR_RASTER_WAVES_DEFER 6              // waves per SIMD the shadow rasteriser is compiled for (the clipper is not in its loop: k_tile_slow)
 #endif
 // Diagnostic work-skipping switches (attribution of kernel time) exist only in -DZR_DIAG builds: the product library has none.
 #ifdef ZR_DIAG
@@ -251,18 +248,6 @@ __device__ __forceinline__ bool hiz_occluded(const ZrHiz& Z, uint2 pr, float zmi
             hmax = __builtin_fmaxf(hmax, L[(size_t)min(ty0 + j, ty1) * hw + min(tx0 + i, tx1)]);
     // fragment depths are clamped to their triangle's vertex depths (shade_key), so zmin bounds them exactly
     return zmin > hmax;
-}
-
-// Round 2, per (meshlet-instance, tile) pair: the pyramid level whose texels are the raster tiles tells whether the whole
-// tile is already nearer than anything the meshlet can produce.  k_bin_count and k_bin_fill must agree: both call these.
-__device__ __forceinline__ float tile_test_depth(const ZrHiz& Z, uint32_t k)
-{
-    if (TILE != 32 || Z.phase != 2u) return -1.0f;
-    return Z.zmin[k];                                   // < 0: the meshlet is not occlusion-tested
-}
-__device__ __forceinline__ bool tile_hides(const ZrHiz& Z, float zt, uint32_t tile)
-{
-    return zt >= 0.0f && zt > Z.lvl[2][tile];           // level 2 = 32 x 32 pixel blocks = tiles, same row pitch (tiles_x)
 }
 
 // Shape of the per-pixel kernels' grids (A/B'd on the whole two-lane frame, not on the kernel alone: what counts is what the pass

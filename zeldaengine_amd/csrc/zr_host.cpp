@@ -92,9 +92,7 @@ extern "C" int zr_create(const zr_config* cfg, zr_ctx** out)
     c->device = cfg->device;
     c->W = cfg->width; c->H = cfg->height; c->SD = cfg->shadow_dim ? cfg->shadow_dim : XK_SHADOWMAP_DIM;
     if (c->SD > 255u * ZR_TILE) { delete c; return ZR_ERR_ARG; }
-#ifndef ZR_DIAG
-    if (c->cfg.flags & ZR_FLAG_MESHLET_BINS) { delete c; return ZR_ERR_UNSUPPORTED; }      // the A/B rasteriser exists in -DZR_DIAG builds only (refused before anything is allocated)
-#endif
+    if (c->cfg.flags & ZR_FLAG_MESHLET_BINS) { delete c; return ZR_ERR_UNSUPPORTED; }      // a reserved bit (refused before anything is allocated)
     c->debug_view = cfg->debug_view;
     memset(&c->cam, 0, sizeof c->cam); memset(&c->shadow, 0, sizeof c->shadow); memset(&c->view, 0, sizeof c->view);
     default_lights(&c->view);
@@ -166,15 +164,13 @@ extern "C" int zr_create(const zr_config* cfg, zr_ctx** out)
     if (ok && !owned.empty()) ok &= hipMemcpy(c->d_owned, owned.data(), owned.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
     if (ok) ok &= hipMemcpy(c->d_sowned, sowned.data(), sowned.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
     if (ok) ok &= hipMemset(c->d_tiles, 0, (size_t)c->slots_per_rank * ZR_TILE * ZR_TILE * 4) == hipSuccess;
-    const uint32_t mt = (c->n_tiles > c->sn_tiles ? c->n_tiles : c->sn_tiles) * ZR_TSTRIDE + 1;     // (the triangle-binned pass spreads its counters)
-    for (auto& sc : c->sc) {
-        ok &= dev_alloc(&sc.tile_count, mt) == hipSuccess;
-        ok &= dev_alloc(&sc.tile_offset, mt) == hipSuccess;
-        ok &= dev_alloc(&sc.tile_cursor, mt) == hipSuccess;
-        ok &= dev_alloc(&sc.chunk_offset, mt) == hipSuccess;
-        if (ok) ok &= hipMemset(sc.tile_count, 0, mt * 4) == hipSuccess;       // k_geom counts into zeroes, k_index advances cursors from zero:
-        if (ok) ok &= hipMemset(sc.tile_cursor, 0, mt * 4) == hipSuccess;      // k_tile leaves both that way for the next round
-    }
+    const uint32_t mt = (c->n_tiles > c->sn_tiles ? c->n_tiles : c->sn_tiles) * ZR_TSTRIDE + 1;     // (the bins use the first sn_tiles + 1 words)
+    ok &= dev_alloc(&c->sb.tile_count, mt) == hipSuccess;
+    ok &= dev_alloc(&c->sb.tile_offset, mt) == hipSuccess;
+    ok &= dev_alloc(&c->sb.tile_cursor, mt) == hipSuccess;
+    ok &= dev_alloc(&c->sb.chunk_offset, mt) == hipSuccess;
+    if (ok) ok &= hipMemset(c->sb.tile_count, 0, mt * 4) == hipSuccess;       // k_bin_count counts into zeroes (k_scan zeroes the counts
+    if (ok) ok &= hipMemset(c->sb.tile_cursor, 0, mt * 4) == hipSuccess;      // and the cursors again for the fill and the next frame)
     {   // the clear values of ZE:3427-3433, as resolve_pixel writes them for an empty pixel
         ok &= dev_alloc(&c->d_clear_px, 64) == hipSuccess;
         uint32_t px[16] = { 0 };
@@ -188,15 +184,12 @@ extern "C" int zr_create(const zr_config* cfg, zr_ctx** out)
         c->Gclear.gD = (uint2*)(w + 6); c->Gclear.overlay = w + 8;
     }
     {   // environment switches, read once
-#ifdef ZR_DIAG       // work-skipping / A-B switches: diagnostic builds only (zeldaengine_amd.build.build(extra_flags=["-DZR_DIAG"]))
+#ifdef ZR_DIAG       // work-skipping / printing switches: diagnostic builds only (zeldaengine_amd.build.build(extra_flags=["-DZR_DIAG"]))
         const char* e;
         if ((e = getenv("ZR_DEBUG_SKIP"))) c->env_skip = (uint32_t)atoi(e);                 // 1: no pixel walk, 2: no triangle phase
         if ((e = getenv("ZR_DEBUG_SKIP_LIGHT"))) c->env_skip_light = (uint32_t)atoi(e);     // bits: 1 PCF, 2 lights, 4 reflection
         if ((e = getenv("ZR_LIGHT_LIST_MIN"))) c->env_light_list_min = atoi(e);
         c->env_no_empty_px = getenv("ZR_NO_EMPTY_PIXEL") != nullptr;
-        c->env_serial = getenv("ZR_SERIAL_PASSES") != nullptr;      // same frame, one stream (= ZR_FLAG_SERIAL_PASSES)
-        if ((e = getenv("ZR_SHADOW_BOX_CULL"))) c->env_shadow_box = atoi(e) != 0;
-        if ((e = getenv("ZR_SHADOW_DEFER"))) c->env_shadow_defer = atoi(e) != 0;
 #endif
     }
     ok &= hipHostMalloc((void**)&c->h_view_ring, sizeof(XkView) * zr_ctx::VIEW_RING, hipHostMallocDefault) == hipSuccess;
@@ -208,22 +201,6 @@ extern "C" int zr_create(const zr_config* cfg, zr_ctx** out)
         // took from the host lane what it saved itself (5 300 Mpixel/s), at the lowest the host lane keeps its share (5 540; normal: 5 470).
         int least = 0, greatest = 0;
         (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-#ifdef ZR_DIAG
-        // experiment: CU partition between the lanes.  ZR_CU_MASK_CAM / ZR_CU_MASK_HOST = "lo-hi" CU ranges (of 256), or "xN:k" = the first k
-        // CUs of every group of N; the host's stream is then the library's own masked stream (only when the caller sets none)
-        auto make_masked = [&](const char* spec, hipStream_t* out) -> bool {
-            uint32_t mask[8] = { 0 };
-            int a = 0, b = 0;
-            if (sscanf(spec, "x%d:%d", &a, &b) == 2 && a > 0) { for (int i = 0; i < 256; ++i) if (i % a < b) mask[i >> 5] |= 1u << (i & 31); }
-            else if (sscanf(spec, "%d-%d", &a, &b) == 2) { for (int i = a; i <= b && i < 256; ++i) if (i >= 0) mask[i >> 5] |= 1u << (i & 31); }
-            else return false;
-            return hipExtStreamCreateWithCUMask(out, 8, mask) == hipSuccess;
-        };
-        const char* mc = getenv("ZR_CU_MASK_CAM"); const char* mh = getenv("ZR_CU_MASK_HOST");
-        if (mh) { hipStream_t hs = nullptr; if (make_masked(mh, &hs)) { (void)hipStreamDestroy(c->own_stream); c->own_stream = hs; c->stream = hs; } }
-        if (mc && make_masked(mc, &c->cam_s)) { }
-        else
-#endif
         ok &= hipStreamCreateWithPriority(&c->cam_s, hipStreamNonBlocking, least) == hipSuccess;
     }
     ok &= hipEventCreateWithFlags(&c->ev_cam, hipEventDisableTiming) == hipSuccess;
@@ -319,10 +296,9 @@ extern "C" void zr_destroy(zr_ctx* c)
     }
     dev_free(c->d_color); dev_free(c->d_stats); dev_free(c->d_sstats); dev_free(c->d_lut); dev_free(c->d_unorm_lut); dev_free(c->d_sky_keys);
     dev_free(c->d_owned); dev_free(c->d_sowned); dev_free(c->d_tiles); dev_free(c->d_tile_map); dev_free(c->d_sowned_rank); dev_free(c->d_stile_map);
-    for (auto& sc : c->sc) {
-        dev_free(sc.tile_count); dev_free(sc.tile_offset); dev_free(sc.tile_cursor); dev_free(sc.chunk_offset);
-        dev_free(sc.rects); dev_free(sc.bins); dev_free(sc.work); dev_free(sc.chunk_tab);
-    }
+    for (auto& sc : c->sc) { dev_free(sc.rects); dev_free(sc.work); }
+    dev_free(c->sb.tile_count); dev_free(c->sb.tile_offset); dev_free(c->sb.tile_cursor); dev_free(c->sb.chunk_offset);
+    dev_free(c->sb.bins); dev_free(c->sb.chunk_tab);
     dev_free(c->d_clear_px);
     if (c->h_view_ring) (void)hipHostFree(c->h_view_ring);
     for (auto& e : c->view_ev) if (e) (void)hipEventDestroy(e);
@@ -806,7 +782,8 @@ static int finalize_scene(zr_ctx* c)
     c->sky_object = sky ? (uint32_t)tab.size() - 1u : 0u;
     if (sky && !c->d_sky_keys) HIPCHK(c, dev_alloc(&c->d_sky_keys, (size_t)c->W * c->H));
     if (c->n_work > c->work_capacity) {
-        for (auto& sc : c->sc) { dev_free(sc.rects); dev_free(sc.bins); dev_free(sc.work); dev_free(sc.chunk_tab); }
+        for (auto& sc : c->sc) { dev_free(sc.rects); dev_free(sc.work); }
+        dev_free(c->sb.bins); dev_free(c->sb.chunk_tab);
         dev_free(c->d_pxrect); dev_free(c->d_zmin); dev_free(c->d_visflag[0]); dev_free(c->d_visflag[1]);
         dev_free(c->d_spxrect); dev_free(c->d_szmin); dev_free(c->d_sflag);
         // (a failed allocation below returns with scene_dirty still set and work_capacity 0: the next frame tries again instead of
@@ -819,9 +796,9 @@ static int finalize_scene(zr_ctx* c)
         for (auto& sc : c->sc) {
             HIPCHK(c, dev_alloc(&sc.rects, cap_w));
             HIPCHK(c, dev_alloc(&sc.work, cap_w));
-            HIPCHK(c, dev_alloc(&sc.bins, c->bin_capacity));
-            HIPCHK(c, dev_alloc(&sc.chunk_tab, c->chunk_capacity));
         }
+        HIPCHK(c, dev_alloc(&c->sb.bins, c->bin_capacity));
+        HIPCHK(c, dev_alloc(&c->sb.chunk_tab, c->chunk_capacity));
         // triangle-binned camera pass: triangle records (32 B) live in per-tile BUCKETS of two 16-byte planes, laid out every frame by
         // k_plan from the previous frame's per-tile counts; what lies behind the last bucket is the frame's overflow region (what a tile gets
         // beyond its bucket).  Sized from the scene: 16 records per meshlet-instance, at least 32 Mi - 1 GB of 288 reserved, touched as far as a frame
@@ -1208,22 +1185,24 @@ static bool build_pass(const zr_ctx* c, const XkUniformBufferMVP& u, int mode, Z
 
 // ------------------------------------------------------------------------------------------------ the frame
 
-// cull -> count -> scan -> fill -> raster of one pass.  Z.phase selects the share of the camera pass drawn (0 = all of it).
-static void bin_and_raster(zr_ctx* c, const ZrPass& P, const ZrHiz& Z, int slot, uint32_t n_tiles, hipStream_t s)
+static inline float* shadow_buf(zr_ctx* c) { return c->d_shadow_ext ? c->d_shadow_ext : c->d_shadow; }
+
+// count -> scan -> fill of the shadow pass's meshlet bins, from the cull's rects.  Z.phase 1 (occlusion culling): only the
+// meshlet-instances flagged last frame are binned.
+static void shadow_bin(zr_ctx* c, const ZrPass& P, const ZrHiz& Z, hipStream_t s)
 {
-    const zr_ctx::Scratch& sc = c->sc[slot ? 1 : 0];
-    ZrDevStats* st = slot ? c->d_stats : c->d_sstats;        // the shadow pipeline (slot 0) has a block of its own
-    zr_launch_bin_count(P, sc.work, sc.rects, sc.tile_count, Z, st, slot, s);
+    const zr_ctx::ShadowBins& sb = c->sb;
+    const uint32_t *work = c->sc[0].work, *rects = c->sc[0].rects;
+    zr_launch_bin_count(P, work, rects, sb.tile_count, Z, c->d_sstats, s);
     // A rank that owns a share of the shadow MAP (zr_set_shadow_tiles, four ranks or more) has a small pass beside a camera lane that is as
     // busy as ever: units of 128 entries on half the persistent grid leave that lane more of the machine (a rank of eight at config 4:
     // 0.779 -> 0.752 ms; 32 / 16 entries: 0.88 / 1.05 ms; 256: 0.754).  Units only get bigger here: the chunk table's capacity holds.
-    const uint32_t chunk = (slot == 0 && c->stile_world >= 4u) ? 2u * ZR_CHUNK : ZR_CHUNK;
-    zr_launch_scan(sc.tile_count, sc.tile_offset, sc.tile_cursor, sc.chunk_offset, sc.chunk_tab, c->chunk_capacity, n_tiles, c->bin_capacity, st, slot, s, chunk);
-    zr_launch_bin_fill(P, c->d_objs, sc.work, sc.rects, sc.tile_offset, sc.tile_cursor, sc.bins, Z, st, slot, s);
+    const uint32_t chunk = c->stile_world >= 4u ? 2u * ZR_CHUNK : ZR_CHUNK;
+    zr_launch_scan(sb.tile_count, sb.tile_offset, sb.tile_cursor, sb.chunk_offset, sb.chunk_tab, c->chunk_capacity, c->sn_tiles, c->bin_capacity,
+                   c->d_sstats, 0, s, chunk);
+    zr_launch_bin_fill(P, c->d_objs, work, rects, sb.tile_offset, sb.tile_cursor, sb.bins, Z, c->d_sstats, s);
 }
-// One round of the triangle-binned camera pass: which meshlet-instances (k_select: timed with the cull), then their triangles as
-// records (k_geom), the records' places per tile (k_scan, k_index) and the tile kernel: those four are what the meshlet-binned
-// path's one raster launch does, and are timed as the raster.
+// Which meshlet-instances round 2 of the camera pass draws (k_select: timed with the Hi-Z build; round 1's list comes from the cull).
 static void tri_select(zr_ctx* c, const ZrPass& P, const ZrHiz& Z, int slot, hipStream_t s)
 {
     zr_launch_select(P, c->d_objs, c->sc[1].work, c->sc[1].rects, Z, c->tb, c->d_stats, slot, s);
@@ -1243,18 +1222,12 @@ static void tri_raster(zr_ctx* c, const ZrPass& P, const ZrHiz& Z, int slot, hip
     // (the frame's last round also draws the slow triangles of both rounds: k_tile<LAST>)
     zr_launch_tile(P, c->tb, c->d_stats, slot, c->d_vis, c->raster_blocks, s, last, c->d_owned, c->n_owned);
 }
-static void raster(zr_ctx* c, const ZrPass& P, const ZrHiz& Z, int slot, hipStream_t s, int stage = 0)
+// the shadow rasteriser over the bins (stage: see zr_launch_raster_chunks)
+static void raster(zr_ctx* c, const ZrPass& P, hipStream_t s, int stage)
 {
-    const bool shadow = slot == 0;
-    const zr_ctx::Scratch& sc = c->sc[shadow ? 0 : 1];
-    const bool defer = shadow && c->env_shadow_defer && c->d_slow0 != nullptr;
-    zr_launch_raster_chunks(P, c->d_objs, sc.chunk_tab, sc.bins, shadow ? c->d_sstats : c->d_stats, slot, c->d_vis,
-                            (uint32_t*)(c->d_shadow_ext ? c->d_shadow_ext : c->d_shadow),
-                            shadow ? (c->stile_world >= 4u ? c->shadow_blocks / 2u : c->shadow_blocks) : c->raster_blocks, Z, s,
-                            defer ? c->d_slow0 : nullptr, c->slow0_cap, c->d_sowned, c->sn_tiles, stage);
+    zr_launch_raster_chunks(P, c->d_objs, c->sb.chunk_tab, c->sb.bins, c->d_sstats, 0, (uint32_t*)shadow_buf(c),
+                            c->stile_world >= 4u ? c->shadow_blocks / 2u : c->shadow_blocks, s, c->d_slow0, c->slow0_cap, c->d_sowned, c->sn_tiles, stage);
 }
-
-static inline float* shadow_buf(zr_ctx* c) { return c->d_shadow_ext ? c->d_shadow_ext : c->d_shadow; }
 
 // The frame in three stages so that a multi-GPU host can put collectives between them (zeldaengine_amd/dist.py):
 //   zr_render_shadow    shadow pass (ZE:3239-3393) of this rank's share of the instances
@@ -1373,32 +1346,22 @@ static int shadow_pass(zr_ctx* c, hipStream_t s)
     // It pays when casters pile up behind each other: the test + the late launch cost what a quarter of config 3's rasteriser does
     // (0.1 meshlet-instances per texel: 25 % hidden, frame 2.7 % slower); the same spheres at 0.21 / 0.31 / 0.52 per texel: frame 2 /
     // 8 / 10.5 % faster (tools/occlusion_threshold.py); 1 M instances (10 per texel): 10 % - on by itself from one per five texels.
-    bool occl = !(c->cfg.flags & ZR_FLAG_NO_SHADOW_OCCLUSION) && P.n_work != 0 && ZR_TILE == 32 && c->SD >= 4u &&
-                ((c->cfg.flags & ZR_FLAG_SHADOW_OCCLUSION) || 5ull * P.n_work >= (uint64_t)c->SD * c->SD);
-#ifdef ZR_DIAG
-    if (!c->env_shadow_box) {      // (A/B only: the exact cull always rebuilds its list, in the camera lane's block)
-        occl = false; c->list_valid[0] = false;
-        if (P.use_worklist) zr_launch_fill32(&c->d_stats->n_vis_work[0], 0u, 1, s);
-        zr_launch_cull(P, c->d_objs, c->sc[0].work, c->sc[0].rects, Z, c->d_stats, 0, c->raster_blocks * 4u, s);
-    }
-    else
-#endif
-    {
-        if (occl) { Z.pxrect = c->d_spxrect; Z.zmin = c->d_szmin; Z.vis_prev = c->d_sflag; Z.vis_stamp = 1u; Z.phase = 1u; }      // (the pass's own flags are 0 / 1)
-        // a rebuilt work list starts from length 0 - zeroed HERE, in stream order behind the previous frame's shadow pipeline (k_cull_instances
-        // grows it, every later kernel of the pipeline reads it)
-        if (c->list_rebuild_mask & 1u) zr_launch_fill32(&c->d_sstats->n_vis_work[0], 0u, 1, s);
-        zr_launch_cull_box(P, c->d_objs, c->sc[0].work, c->sc[0].rects, Z, c->d_sstats, 0, s, nullptr, nullptr, c->list_reuse[0]);
-        if (c->list_rebuild_mask & 1u) c->list_valid[0] = true;
-    }
-    bin_and_raster(c, P, Z, 0, c->sn_tiles, s);
+    const bool occl = !(c->cfg.flags & ZR_FLAG_NO_SHADOW_OCCLUSION) && P.n_work != 0 && ZR_TILE == 32 && c->SD >= 4u &&
+                      ((c->cfg.flags & ZR_FLAG_SHADOW_OCCLUSION) || 5ull * P.n_work >= (uint64_t)c->SD * c->SD);
+    if (occl) { Z.pxrect = c->d_spxrect; Z.zmin = c->d_szmin; Z.vis_prev = c->d_sflag; Z.vis_stamp = 1u; Z.phase = 1u; }      // (the pass's own flags are 0 / 1)
+    // a rebuilt work list starts from length 0 - zeroed HERE, in stream order behind the previous frame's shadow pipeline (k_cull_instances
+    // grows it, every later kernel of the pipeline reads it)
+    if (c->list_rebuild_mask & 1u) zr_launch_fill32(&c->d_sstats->n_vis_work[0], 0u, 1, s);
+    zr_launch_cull_box(P, c->d_objs, c->sc[0].work, c->sc[0].rects, Z, c->d_sstats, 0, s, nullptr, nullptr, c->list_reuse[0]);
+    if (c->list_rebuild_mask & 1u) c->list_valid[0] = true;
+    shadow_bin(c, P, Z, s);
     if (ev) HIPCHK(c, hipEventRecord(ev[1], s));
-    raster(c, P, Z, 0, s, occl ? 1 : 0);
+    raster(c, P, s, occl ? 1 : 0);
     if (occl) {
         zr_launch_shadow_occlusion(P, c->d_objs, c->sc[0].work, c->sc[0].rects, c->d_spxrect, c->d_szmin, c->d_sflag, (const uint32_t*)shadow_buf(c),
-                                   c->sc[0].bins, c->d_sstats, c->shadow_blocks * 8u, c->sflag_history ? (uint32_t)(c->frame_no & 3u) : 4u, s);
+                                   c->sb.bins, c->d_sstats, c->shadow_blocks * 8u, c->sflag_history ? (uint32_t)(c->frame_no & 3u) : 4u, s);
         c->sflag_history = true;
-        raster(c, P, Z, 0, s, 2);
+        raster(c, P, s, 2);
     }
     if (ev) HIPCHK(c, hipEventRecord(ev[2], s));
     HIPCHK(c, hipGetLastError());
@@ -1424,42 +1387,27 @@ static int gbuffer_pass(zr_ctx* c, hipStream_t s)
     const uint32_t vis_mark = 1u + (uint32_t)(c->frame_no % 255u);
     Z.vis_stamp = c->vis_mark_prev;
     Z.phase = 0;
-#ifdef ZR_DIAG
-    const bool tri_bins = !(c->cfg.flags & ZR_FLAG_MESHLET_BINS) && ZR_TILE == 32;      // A/B: the meshlet-binned rasteriser for the camera pass too
-#else
-    constexpr bool tri_bins = true;
     static_assert(ZR_TILE == 32, "the triangle-binned camera pass is written for 32 x 32 tiles");
-#endif
     c->last_two_round = hiz_on && c->vis_history;
-    // (triangle-binned pass: the cull kernel also compacts round 1's list - the survivors that owned a pixel last frame, or all of them)
-#ifdef ZR_DIAG
-    if (!tri_bins) zr_launch_cull(P, c->d_objs, c->sc[1].work, c->sc[1].rects, Z, c->d_stats, 1, c->raster_blocks * 4u, s);
-    else
-#endif
-    {
-        zr_launch_cull_box(P, c->d_objs, c->sc[1].work, c->sc[1].rects, Z, c->d_stats, 1, s, c->tb.sel, c->last_two_round ? Z.vis_prev : nullptr, c->list_reuse[1]);
-        if (c->list_rebuild_mask & 2u) c->list_valid[1] = true;
-    }
+    // (the cull kernel also compacts round 1's list - the survivors that owned a pixel last frame, or all of them)
+    zr_launch_cull_box(P, c->d_objs, c->sc[1].work, c->sc[1].rects, Z, c->d_stats, 1, s, c->tb.sel, c->last_two_round ? Z.vis_prev : nullptr, c->list_reuse[1]);
+    if (c->list_rebuild_mask & 2u) c->list_valid[1] = true;
     const bool two = c->last_two_round;
-    auto bin = [&](int slot) { if (!tri_bins) bin_and_raster(c, P, Z, slot, c->n_tiles, s); else if (slot == 2) tri_select(c, P, Z, slot, s); };
     // (the record buckets are planned from the previous frame: see tri_raster)
     const bool count_first = !c->plan_valid || (!two && c->plan_two_round);
-    auto rast = [&](int slot) { if (tri_bins) tri_raster(c, P, Z, slot, s, slot == 2 || !two, slot == 1 && count_first); else raster(c, P, Z, slot, s); };
-    if (c->last_two_round) {
+    if (two) {
         Z.phase = 1;
-        bin(1);
         if (ev) HIPCHK(c, hipEventRecord(ev[3], s));
-        rast(1);
+        tri_raster(c, P, Z, 1, s, false, count_first);
         if (ev) HIPCHK(c, hipEventRecord(ev[4], s));
         zr_launch_hiz_build(c->d_vis, c->W, c->H, Z, c->d_hiz_regions, c->n_hiz_regions, s);
         Z.phase = 2;
-        bin(2);
+        tri_select(c, P, Z, 2, s);
         if (ev) HIPCHK(c, hipEventRecord(ev[5], s));
-        rast(2);
+        tri_raster(c, P, Z, 2, s, true, false);
     } else {
-        bin(1);
         if (ev) HIPCHK(c, hipEventRecord(ev[3], s));
-        rast(1);
+        tri_raster(c, P, Z, 1, s, true, count_first);
         if (ev) { HIPCHK(c, hipEventRecord(ev[4], s)); HIPCHK(c, hipEventRecord(ev[5], s)); }
     }
     {   // the overlay plane (skydome pixels) is written only when a skydome is drawn, or once more to wipe one that was
@@ -1474,7 +1422,7 @@ static int gbuffer_pass(zr_ctx* c, hipStream_t s)
     zr_launch_resolve_gbuffer(P, c->d_objs, c->d_owned, c->n_owned, c->d_vis, c->G, c->d_lut, c->d_unorm_lut, Z.vis_now, c->d_stats, s, vis_mark);
     c->vis_mark_prev = vis_mark;
     if (ev) HIPCHK(c, hipEventRecord(ev[7], s));
-    if (tri_bins && P.n_work != 0) {     // the next frame's buckets, from this frame's counts: nothing on this lane waits for it
+    if (P.n_work != 0) {     // the next frame's buckets, from this frame's counts: nothing on this lane waits for it
         zr_launch_plan(c->tb, c->d_owned, c->n_owned, c->d_stats, false, c->bucket_pct, s);
         c->plan_valid = true; c->plan_two_round = two;
     }
@@ -1514,7 +1462,7 @@ extern "C" int zr_render_gbuffer(zr_ctx* c)
 // a third only takes occupancy from the other two (measured).
 static int geometry_passes(zr_ctx* c)
 {
-    const bool lanes = !(c->cfg.flags & ZR_FLAG_SERIAL_PASSES) && c->cam_s != nullptr && !c->env_serial;
+    const bool lanes = !(c->cfg.flags & ZR_FLAG_SERIAL_PASSES) && c->cam_s != nullptr;
     int rc;
     c->camera_on_lane = false;
     if (lanes) {

@@ -9,30 +9,14 @@ struct TileCtx {
     int W, H;                     // target extent
 };
 
-// Cheap per-triangle rejection, identical in effect to the early-outs of raster_sub: degenerate or back-facing
-// (GBUFFER only), or no pixel centre of this tile inside the snapped bounding box.
-// HIZ (camera pass, round 2): hz[] holds the tile's 4 x 4 pyramid texels (max depth per 8 x 8 pixel block after round 1); a
-// triangle whose least vertex depth lies behind every block its clipped box touches cannot win a pixel (fragment depths
-// are clamped to the vertex depths).
-template <int MODE, bool HIZ = false>
-__device__ __forceinline__ bool tri_prefilter(int X0, int Y0, int X1, int Y1, int X2, int Y2, const TileCtx& T,
-                                              float zmin = 0.0f, const float* __restrict__ hz = nullptr)
+// Cheap per-triangle rejection, identical in effect to raster_sub's box test: no pixel centre of the tile's key window inside the
+// snapped bounding box.  (Its caller is the shadow rasteriser, which is two-sided: the rare degenerate triangles are left to raster_sub.)
+template <int MODE>
+__device__ __forceinline__ bool tri_prefilter(int X0, int Y0, int X1, int Y1, int X2, int Y2, const TileCtx& T)
 {
-    if (MODE == ZR_MODE_GBUFFER) {      // the shadow pass is two-sided: its (rare) degenerate triangles are left to raster_sub
-        const long long A = (long long)(X1 - X0) * (Y2 - Y0) - (long long)(X2 - X0) * (Y1 - Y0);
-        if (A >= 0) return false;
-    }
     const int x0 = max((imin3(X0, X1, X2) - 128 + 255) >> 8, T.px0), x1 = min((imax3(X0, X1, X2) - 128) >> 8, min(T.px0 + SPAN(MODE) - 1, T.W - 1));
     const int y0 = max((imin3(Y0, Y1, Y2) - 128 + 255) >> 8, T.py0), y1 = min((imax3(Y0, Y1, Y2) - 128) >> 8, min(T.py0 + SPAN(MODE) - 1, T.H - 1));
-    if (!(x0 <= x1 && y0 <= y1)) return false;
-    if (HIZ) {
-        const int bx0 = (x0 - T.px0) >> 3, bx1 = (x1 - T.px0) >> 3, by0 = (y0 - T.py0) >> 3, by1 = (y1 - T.py0) >> 3;
-        float h = 0.0f;
-        for (int by = by0; by <= by1; ++by)
-            for (int bx = bx0; bx <= bx1; ++bx) h = __builtin_fmaxf(h, hz[by * (TILE / 8) + bx]);
-        if (zmin > h) return false;
-    }
-    return true;
+    return x0 <= x1 && y0 <= y1;
 }
 
 template <int MODE>

@@ -1,53 +1,34 @@
 // zr_shadow.hip — the shadow pass (ZE:3239-3393) as meshlet-level binning: k_bin_count / k_scan / k_bin_fill (per-tile lists of
-// self-contained 32-byte meshlet records), k_raster_chunks<MODE, HIZ, DEFER, LATE> (persistent workgroups, a 44 x 44 key window in LDS),
+// self-contained 32-byte meshlet records), k_raster_chunks<LATE> (persistent workgroups, a 44 x 44 key window in LDS),
 // k_shadow_occlusion (the map as a running minimum hides casters), k_count_shadow.  See zr_dev.h for the map of the kernel files.
 #include "zr_dev.h"
 #include "zr_raster.h"
 
 // Per-tile entry counts from the rects.  Counting goes through an LDS histogram per 1024 work items so that a hot
 // tile costs one global atomic per workgroup instead of one per meshlet-instance (same-address atomics serialise).
-__global__ __launch_bounds__(1024) void k_bin_count(ZrPass P, const uint32_t* __restrict__ work, uint32_t* __restrict__ rects,
-                                                    uint32_t* __restrict__ tile_count, ZrHiz Z, ZrDevStats* __restrict__ stats, int slot)
+// (Ownership of the map's tiles was decided per meshlet by k_cull_box: an accepted meshlet is listed in every tile of its rect.)
+// Z.phase 1 (occlusion culling, see k_shadow_occlusion): only the meshlet-instances flagged last frame are listed.
+__global__ __launch_bounds__(1024) void k_bin_count(ZrPass P, const uint32_t* __restrict__ work, const uint32_t* __restrict__ rects,
+                                                    uint32_t* __restrict__ tile_count, ZrHiz Z, const ZrDevStats* __restrict__ stats)
 {
     extern __shared__ uint32_t hist[];
     const uint32_t n_tiles = P.tiles_x * P.tiles_y;
-    const int vslot = slot > 1 ? 1 : slot;               // camera rounds 1 and 2 share the cull results of slot 1
-    const uint32_t n_vis = P.use_worklist ? stats->n_vis_work[vslot] : P.n_work;
+    const uint32_t n_vis = P.use_worklist ? stats->n_vis_work[0] : P.n_work;
     if (blockIdx.x * 1024u >= n_vis) return;            // the grid is sized for every meshlet-instance of the scene
-    // (shadow pass: ownership of the map's tiles was decided per meshlet by k_cull_box - an accepted meshlet is listed in every tile of its rect)
-    const bool shadow = P.mode == ZR_MODE_SHADOW;
     for (uint32_t i = threadIdx.x; i < n_tiles; i += 1024u) hist[i] = 0;
     __syncthreads();
     const uint32_t w = blockIdx.x * 1024u + threadIdx.x;
-    uint32_t occluded = 0;
     if (w < n_vis) {
         uint32_t r = rects[w];
-        if (r != ZR_RECT_CULLED && Z.phase) {            // two-pass occlusion culling: who is drawn in this round?
-            const bool was_visible = Z.vis_prev[P.use_worklist ? work[w] : w] == (uint8_t)Z.vis_stamp;
-            if (Z.phase == 1u) { if (!was_visible) r = ZR_RECT_CULLED; }
-            else if (was_visible) r = ZR_RECT_CULLED;     // drawn in round 1
-            else if (hiz_occluded(Z, Z.pxrect[w], Z.zmin[w])) { r = ZR_RECT_CULLED; rects[w] = r; occluded = 1; }
-        }
+        if (r != ZR_RECT_CULLED && Z.phase && Z.vis_prev[P.use_worklist ? work[w] : w] != (uint8_t)Z.vis_stamp) r = ZR_RECT_CULLED;
         if (r != ZR_RECT_CULLED) {
             const uint32_t tx0 = r & 255u, ty0 = (r >> 8) & 255u, tx1 = (r >> 16) & 255u, ty1 = r >> 24;
-            const float zt = tile_test_depth(Z, w);
             for (uint32_t ty = ty0; ty <= ty1; ++ty)
-                for (uint32_t tx = tx0; tx <= tx1; ++tx) {
-                    const uint32_t t = ty * P.tiles_x + tx;
-                    if ((shadow || tile_owner(tx, ty, P.tile_world) == P.tile_rank) && !tile_hides(Z, zt, t)) atomicAdd(&hist[t], 1u);
-                }
+                for (uint32_t tx = tx0; tx <= tx1; ++tx) atomicAdd(&hist[ty * P.tiles_x + tx], 1u);
         }
     }
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < n_tiles; i += 1024u) { const uint32_t c = hist[i]; if (c) atomicAdd(&tile_count[i], c); }
-    // statistics: one global atomic per workgroup (same-address atomics serialise)
-    __shared__ uint32_t tally;
-    if (threadIdx.x == 0) tally = 0;
-    __syncthreads();
-    const uint32_t nocc = (uint32_t)__popcll(__ballot(occluded != 0));
-    if ((threadIdx.x & 63u) == 0 && nocc) atomicAdd(&tally, nocc);
-    __syncthreads();
-    if (threadIdx.x == 0 && tally) atomicAdd(&stats->hiz_culled, tally);
 }
 
 // Exclusive scan of tile_count[0..n) into tile_offset[0..n] and of the per-tile work-unit counts ceil(count / chunk)
@@ -104,8 +85,9 @@ __global__ __launch_bounds__(1024) void k_scan(uint32_t* __restrict__ tile_count
         // what the kernels after this one accumulate for the pass starts from zero here: the shadow pipeline's block is not touched by
         // k_frame_begin (the pipeline does not wait for the camera lane)
         stats->survivors[slot] = 0; stats->n_slow[slot] = 0;
-        if (slot == 0) stats->overflow = part[1023] > capacity ? 1u : 0u;      // the pipeline's own block: reset here.  (Camera slots - A/B builds -
-        else if (part[1023] > capacity) stats->overflow = 1u;                  // share the lane's block: round 2 must not clear round 1's flag)
+        // (the shadow pass launches this with slot 0 only; the other branches keep the kernel's code as it was measured)
+        if (slot == 0) stats->overflow = part[1023] > capacity ? 1u : 0u;      // the pipeline's own block: reset here
+        else if (part[1023] > capacity) stats->overflow = 1u;
         if (slot == 0) { stats->n_chunks[1] = 0; stats->chunk_counter[1] = 0; stats->shadow_late = 0; }      // (k_shadow_occlusion's late units)
         if (part[1023] > capacity) stats->overflow_sticky = ZR_OVF_BINS;
     }
@@ -116,15 +98,13 @@ __global__ __launch_bounds__(1024) void k_scan(uint32_t* __restrict__ tile_count
 __global__ __launch_bounds__(1024) void k_bin_fill(ZrPass P, const ZrObject* __restrict__ objs, const uint32_t* __restrict__ work,
                                                    const uint32_t* __restrict__ rects,
                                                    const uint32_t* __restrict__ tile_offset, uint32_t* __restrict__ tile_cursor,
-                                                   ZrBinEntry* __restrict__ bins, ZrHiz Z, ZrDevStats* __restrict__ stats, int slot)
+                                                   ZrBinEntry* __restrict__ bins, ZrHiz Z, ZrDevStats* __restrict__ stats)
 {
     extern __shared__ uint32_t hist[];
     __shared__ uint32_t tot;
     const uint32_t n_tiles = P.tiles_x * P.tiles_y;
-    const int vslot = slot > 1 ? 1 : slot;
-    const uint32_t n_vis = P.use_worklist ? stats->n_vis_work[vslot] : P.n_work;
+    const uint32_t n_vis = P.use_worklist ? stats->n_vis_work[0] : P.n_work;
     if (blockIdx.x * 1024u >= n_vis) return;
-    const bool shadow = P.mode == ZR_MODE_SHADOW;       // (as in k_bin_count)
     for (uint32_t i = threadIdx.x; i < n_tiles; i += 1024u) hist[i] = 0;
     if (threadIdx.x == 0) tot = 0;
     __syncthreads();
@@ -132,20 +112,12 @@ __global__ __launch_bounds__(1024) void k_bin_fill(ZrPass P, const ZrObject* __r
     uint32_t r = ZR_RECT_CULLED, w = 0;
     if (k < n_vis) {
         r = rects[k]; w = P.use_worklist ? work[k] : k;
-        if (r != ZR_RECT_CULLED && Z.phase) {            // same split as k_bin_count (round 2's occluded items were marked CULLED there)
-            const bool was_visible = Z.vis_prev[w] == (uint8_t)Z.vis_stamp;
-            if ((Z.phase == 1u) != was_visible) r = ZR_RECT_CULLED;
-        }
+        if (r != ZR_RECT_CULLED && Z.phase && Z.vis_prev[w] != (uint8_t)Z.vis_stamp) r = ZR_RECT_CULLED;      // (as in k_bin_count)
     }
     const uint32_t tx0 = r & 255u, ty0 = (r >> 8) & 255u, tx1 = (r >> 16) & 255u, ty1 = r >> 24;
-    if (r != ZR_RECT_CULLED) {
-        const float zt = tile_test_depth(Z, k);
+    if (r != ZR_RECT_CULLED)
         for (uint32_t ty = ty0; ty <= ty1; ++ty)
-            for (uint32_t tx = tx0; tx <= tx1; ++tx) {
-                const uint32_t t = ty * P.tiles_x + tx;
-                if ((shadow || tile_owner(tx, ty, P.tile_world) == P.tile_rank) && !tile_hides(Z, zt, t)) atomicAdd(&hist[t], 1u);
-            }
-    }
+            for (uint32_t tx = tx0; tx <= tx1; ++tx) atomicAdd(&hist[ty * P.tiles_x + tx], 1u);
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < n_tiles; i += 1024u) {
         const uint32_t c = hist[i];
@@ -163,43 +135,36 @@ __global__ __launch_bounds__(1024) void k_bin_fill(ZrPass P, const ZrObject* __r
         be.mpos = O->mpos + mh.x; be.mtri = O->mtri + ld_global(&ml->BindlessContext); be.inst = O->inst + inst_i;
         be.counts = mh.y | mh.w << 8 | (O->instanced ? 1u << 16 : 0u);
         be.prim_base = O->prim_base + inst_i * O->n_tris;
-        const float zt = tile_test_depth(Z, k);
         for (uint32_t ty = ty0; ty <= ty1; ++ty)
             for (uint32_t tx = tx0; tx <= tx1; ++tx) {
-                const uint32_t t = ty * P.tiles_x + tx;
-                if ((!shadow && tile_owner(tx, ty, P.tile_world) != P.tile_rank) || tile_hides(Z, zt, t)) continue;
-                const uint32_t pos = atomicAdd(&hist[t], 1u);
+                const uint32_t pos = atomicAdd(&hist[ty * P.tiles_x + tx], 1u);
                 if (pos < P.bin_capacity) bins[pos] = be;
             }
     }
     const uint32_t cnt = (uint32_t)__popcll(__ballot(r != ZR_RECT_CULLED));
     if ((threadIdx.x & 63u) == 0 && cnt) atomicAdd(&tot, cnt);
     __syncthreads();
-    if (threadIdx.x == 0 && tot) atomicAdd(&stats->survivors[slot], tot);
+    if (threadIdx.x == 0 && tot) atomicAdd(&stats->survivors[0], tot);
 }
 
 // Persistent chunk rasteriser.  A chunk = up to ZR_CHUNK consecutive entries of ONE tile's bin list, so a hot tile is
 // spread over many workgroups and the pass is bounded by total work, not by the fullest tile.  Every workgroup pulls
 // chunk ids from one device counter until they run out (each wave reaches the exit test).  Per chunk: clear the
-// tile's LDS keys, 4 waves rasterise the chunk's meshlets into them (ds_min), then the touched keys are merged into
-// the frame-sized key buffer in HBM with global atomic min (skipped when the resident key already wins).
-//   GBUFFER: vis64[W*H] (depth bits << 32 | prim), resolved later by k_resolve_gbuffer
-//   SHADOW : the shadow map itself (float bits as uint): the merge IS the LESS_OR_EQUAL depth write
-// DEFER: triangles that need the clipper (or the 64-bit walk) are not rasterised here but appended, with their tile, to `slow` for
+// window's LDS keys, 4 waves rasterise the chunk's meshlets into them (ds_min), then the touched keys are merged into
+// the shadow map in HBM (float bits as uint) with global atomic min: the merge IS the LESS_OR_EQUAL depth write.
+// Triangles that need the clipper (or the 64-bit walk) are not rasterised here but appended, with their tile, to `slow` for
 // k_tile_slow: without the call to raster_clipped in its loop the kernel needs half the registers, i.e. twice the waves per SIMD
 // fit - next to each other and next to the other lane's kernels.
-// LATE (shadow pass, after k_shadow_occlusion): unit u is the ONE entry bins[bin_capacity - 1 - u], its tile in the record's prim_base
+// LATE (after k_shadow_occlusion): unit u is the ONE entry bins[bin_capacity - 1 - u], its tile in the record's prim_base
 // (the shadow pass has no use for a primitive id); the units are counted in slot 1 of the pipeline's block, slow triangles stay in `slot`.
-template <int MODE, bool HIZ, bool DEFER, bool LATE = false>
-__global__ __launch_bounds__(RTHREADS) __attribute__((amdgpu_waves_per_eu(DEFER ? ZR_RASTER_WAVES_DEFER : ZR_RASTER_WAVES)))
+template <bool LATE>
+__global__ __launch_bounds__(RTHREADS) __attribute__((amdgpu_waves_per_eu(ZR_RASTER_WAVES_DEFER)))
 void k_raster_chunks(ZrPass P, const ZrObject* __restrict__ objs, const uint4* __restrict__ chunk_tab,
                      const ZrBinEntry* __restrict__ bins, ZrDevStats* __restrict__ stats, int slot,
-                     unsigned long long* __restrict__ vis64, uint32_t* __restrict__ shadow_bits,
-                     const float* __restrict__ hiz0, uint32_t hiz0_w, uint32_t hiz0_h, uint4* __restrict__ slow, uint32_t slow_cap)
+                     uint32_t* __restrict__ shadow_bits, uint4* __restrict__ slow, uint32_t slow_cap)
 {
-    __shared__ float hz[HIZ ? (TILE / 8) * (TILE / 8) : 1];
-    __shared__ unsigned long long keys64[MODE == ZR_MODE_GBUFFER ? TILE_PIX : 1];
-    __shared__ uint32_t keys32[MODE == ZR_MODE_SHADOW ? SPAN_PIX(MODE) : 1];
+    constexpr uint32_t WIN = SPAN(ZR_MODE_SHADOW), WIN_PIX = WIN * WIN;      // the key window: edge, texels
+    __shared__ uint32_t keys32[WIN_PIX];
     __shared__ int4 vstage[RW][WAVE];
     // per-wave ring of surviving triangles, SoA: 3 x (tile-relative X | Y << 16, z) + prim.  Only small triangles (edges under 64 px)
     // that reach the tile are queued, so a relative coordinate lies within [-16384, 24576] sub-pixel units and fits 16 bits.
@@ -219,10 +184,7 @@ void k_raster_chunks(ZrPass P, const ZrObject* __restrict__ objs, const uint4* _
     bool first = true;
     for (;;) {
         if (chunk >= n_chunks) break;
-        for (uint32_t i = tid; i < (uint32_t)SPAN_PIX(MODE); i += RTHREADS) {
-            if (MODE == ZR_MODE_GBUFFER) keys64[i] = (unsigned long long)0x3F800000u << 32 | ZR_EMPTY_PRIM;
-            else keys32[i] = 0x3F800000u;
-        }
+        for (uint32_t i = tid; i < WIN_PIX; i += RTHREADS) keys32[i] = 0x3F800000u;
         __syncthreads();
         // this work unit: (tile, first entry, end) as k_scan laid it out: one load, not a search over the tiles' chunk offsets
         uint4 ct;
@@ -235,13 +197,6 @@ void k_raster_chunks(ZrPass P, const ZrObject* __restrict__ objs, const uint4* _
         const int ox = tpx0 * 256, oy = tpy0 * 256;
         TileCtx T;
         T.px0 = 0; T.py0 = 0; T.W = (int)P.W - tpx0; T.H = (int)P.H - tpy0;
-        if (HIZ) {      // this tile's finest pyramid texels (blocks past the target's edge hold no pixel: 0 = "hides everything")
-            if (tid < (TILE / 8) * (TILE / 8)) {
-                const uint32_t bx = (uint32_t)tpx0 / 8u + tid % (TILE / 8), by = (uint32_t)tpy0 / 8u + tid / (TILE / 8);
-                hz[tid] = (bx < hiz0_w && by < hiz0_h) ? hiz0[(size_t)by * hiz0_w + bx] : 0.0f;
-            }
-            __syncthreads();
-        }
 
         uint32_t qhead = 0, qn = 0;
         // The next entry's 32-byte record is fetched (vector loads, vmcnt-ordered) while the current one is processed; every
@@ -304,24 +259,20 @@ void k_raster_chunks(ZrPass P, const ZrObject* __restrict__ objs, const uint4* _
                     // (it leaves a triangle that needs no clipping as it is, so the pixels are the same) - but only for the windows its
                     // snapped box reaches: a ground triangle under a 2048^2 map is met in thousands of tiles' lists and touches a few
                     if (cls == 1 && !tri_is_small(r0.x, r0.y, r1.x, r1.y, r2.x, r2.y))
-                        cls = tri_prefilter<MODE, false>(r0.x, r0.y, r1.x, r1.y, r2.x, r2.y, T) ? 2 : 0;
-                    if (cls == 1) {
-                        const float tz = HIZ ? __builtin_fminf(__builtin_fminf(zr_u2f((uint32_t)r0.z), zr_u2f((uint32_t)r1.z)), zr_u2f((uint32_t)r2.z)) : 0.0f;
-                        alive = tri_prefilter<MODE, HIZ>(r0.x, r0.y, r1.x, r1.y, r2.x, r2.y, T, tz, hz);
-                    } else if (cls == 2) {
+                        cls = tri_prefilter<ZR_MODE_SHADOW>(r0.x, r0.y, r1.x, r1.y, r2.x, r2.y, T) ? 2 : 0;
+                    if (cls == 1) alive = tri_prefilter<ZR_MODE_SHADOW>(r0.x, r0.y, r1.x, r1.y, r2.x, r2.y, T);
+                    else if (cls == 2) {
                         zf4 cc[3];
                         const uint32_t li[3] = { i0, i1, i2 };
                         for (int k = 0; k < 3; ++k) {
                             const float4 pk = ld_global(mp + li[k]);
                             cc[k] = zr_mat4_point(P.PVM, vs_position(zr3(pk.x, pk.y, pk.z), I, instanced));
                         }
-                        if (DEFER) {
-                            const uint32_t pos = atomicAdd(&stats->n_slow[slot], 1u);          // rare: one atomic apiece does
-                            if (pos < slow_cap) {
-                                for (int k = 0; k < 3; ++k) slow[4u * pos + (uint32_t)k] = make_uint4(zr_f2u(cc[k].x), zr_f2u(cc[k].y), zr_f2u(cc[k].z), zr_f2u(cc[k].w));
-                                slow[4u * pos + 3u] = make_uint4(prim, tile, 0u, 0u);
-                            } else { stats->overflow = 1u; stats->overflow_sticky = ZR_OVF_SLOW; }
-                        } else raster_clipped<MODE>(cc[0], cc[1], cc[2], prim, T, P.hw, P.hh, ox, oy, keys64, keys32);
+                        const uint32_t pos = atomicAdd(&stats->n_slow[slot], 1u);          // rare: one atomic apiece does
+                        if (pos < slow_cap) {
+                            for (int k = 0; k < 3; ++k) slow[4u * pos + (uint32_t)k] = make_uint4(zr_f2u(cc[k].x), zr_f2u(cc[k].y), zr_f2u(cc[k].z), zr_f2u(cc[k].w));
+                            slow[4u * pos + 3u] = make_uint4(prim, tile, 0u, 0u);
+                        } else { stats->overflow = 1u; stats->overflow_sticky = ZR_OVF_SLOW; }
                     }
                 }
                 const unsigned long long mask = __ballot(alive);
@@ -342,7 +293,7 @@ void k_raster_chunks(ZrPass P, const ZrObject* __restrict__ objs, const uint4* _
                     a.X = (short)q[0 * QCAP]; a.Y = q[0 * QCAP] >> 16; a.z = zr_u2f((uint32_t)q[1 * QCAP]); a.rw = 0.0f;
                     b.X = (short)q[2 * QCAP]; b.Y = q[2 * QCAP] >> 16; b.z = zr_u2f((uint32_t)q[3 * QCAP]); b.rw = 0.0f;
                     c.X = (short)q[4 * QCAP]; c.Y = q[4 * QCAP] >> 16; c.z = zr_u2f((uint32_t)q[5 * QCAP]); c.rw = 0.0f;
-                    raster_sub<MODE, true>(a, b, c, (uint32_t)q[6 * QCAP], T, keys64, keys32);
+                    raster_sub<ZR_MODE_SHADOW, true>(a, b, c, (uint32_t)q[6 * QCAP], T, nullptr, keys32);
                     qhead = (qhead + WAVE) & (QCAP - 1u); qn -= WAVE;
                 }
             }
@@ -355,26 +306,21 @@ void k_raster_chunks(ZrPass P, const ZrObject* __restrict__ objs, const uint4* _
                 a.X = (short)q[0 * QCAP]; a.Y = q[0 * QCAP] >> 16; a.z = zr_u2f((uint32_t)q[1 * QCAP]); a.rw = 0.0f;
                 b.X = (short)q[2 * QCAP]; b.Y = q[2 * QCAP] >> 16; b.z = zr_u2f((uint32_t)q[3 * QCAP]); b.rw = 0.0f;
                 c.X = (short)q[4 * QCAP]; c.Y = q[4 * QCAP] >> 16; c.z = zr_u2f((uint32_t)q[5 * QCAP]); c.rw = 0.0f;
-                raster_sub<MODE, true>(a, b, c, (uint32_t)q[6 * QCAP], T, keys64, keys32);
+                raster_sub<ZR_MODE_SHADOW, true>(a, b, c, (uint32_t)q[6 * QCAP], T, nullptr, keys32);
             }
             qhead = (qhead + qn) & (QCAP - 1u); qn = 0;
         }
         __syncthreads();
 
         // merge the touched keys into HBM
-        for (uint32_t i = tid; i < (uint32_t)SPAN_PIX(MODE); i += RTHREADS) {
-            const int px = tpx0 + (int)(i % (uint32_t)SPAN(MODE)), py = tpy0 + (int)(i / (uint32_t)SPAN(MODE));
+        for (uint32_t i = tid; i < WIN_PIX; i += RTHREADS) {
+            const int px = tpx0 + (int)(i % WIN), py = tpy0 + (int)(i / WIN);
             if (px >= (int)P.W || py >= (int)P.H) continue;
             const size_t p = (size_t)py * P.W + (size_t)px;
-            if (MODE == ZR_MODE_GBUFFER) {
-                const unsigned long long k = keys64[i];
-                if ((uint32_t)k != ZR_EMPTY_PRIM && k < vis64[p]) atomicMin(&vis64[p], k);
-            } else {
-                // (a key still at its clear value 1.0 cannot lower the map, whose texels never exceed 1.0: its texel is not even read - the
-                // untouched four fifths of a window's 1 936 texels were 15 MB of the pass's 25 MB of reads, profiles/r06_shadow_tcc.txt)
-                const uint32_t k = keys32[i];
-                if (k != 0x3F800000u && k < shadow_bits[p]) atomicMin(&shadow_bits[p], k);
-            }
+            // (a key still at its clear value 1.0 cannot lower the map, whose texels never exceed 1.0: its texel is not even read - the
+            // untouched four fifths of a window's 1 936 texels were 15 MB of the pass's 25 MB of reads, profiles/r06_shadow_tcc.txt)
+            const uint32_t k = keys32[i];
+            if (k != 0x3F800000u && k < shadow_bits[p]) atomicMin(&shadow_bits[p], k);
         }
         // (the next unit is claimed only when this one is done: claiming early costs more in tail balance than the atomic's latency)
         // ... and the second unit of a workgroup is fixed like the first (b + grid): claims on one counter queue up for ~10 ns apiece
@@ -526,12 +472,12 @@ __global__ void k_count_shadow(const uint32_t* __restrict__ bits, size_t n, ZrDe
 
 // ------------------------------------------------------------------------------------------------ launchers (C++ linkage, used by zr_host.cpp)
 
-void zr_launch_bin_count(const ZrPass& P, const uint32_t* work, uint32_t* rects, uint32_t* tile_count, const ZrHiz& Z, ZrDevStats* stats,
-                         int slot, hipStream_t s)
+void zr_launch_bin_count(const ZrPass& P, const uint32_t* work, const uint32_t* rects, uint32_t* tile_count, const ZrHiz& Z, const ZrDevStats* stats,
+                         hipStream_t s)
 {
     if (P.n_work == 0) return;
     const uint32_t n_tiles = P.tiles_x * P.tiles_y;
-    hipLaunchKernelGGL(k_bin_count, dim3((P.n_work + 1023) / 1024), dim3(1024), n_tiles * sizeof(uint32_t), s, P, work, rects, tile_count, Z, stats, slot);
+    hipLaunchKernelGGL(k_bin_count, dim3((P.n_work + 1023) / 1024), dim3(1024), n_tiles * sizeof(uint32_t), s, P, work, rects, tile_count, Z, stats);
 }
 void zr_launch_scan(uint32_t* tile_count, uint32_t* tile_offset, uint32_t* tile_cursor, uint32_t* chunk_offset, uint4* chunk_tab,
                     uint32_t chunk_cap, uint32_t n, uint32_t capacity, ZrDevStats* stats, int slot, hipStream_t s,
@@ -540,38 +486,21 @@ void zr_launch_scan(uint32_t* tile_count, uint32_t* tile_offset, uint32_t* tile_
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, tile_count, tile_offset, tile_cursor, chunk_offset, chunk_tab, chunk_cap, n, capacity, stats, slot, chunk);
 }
 void zr_launch_bin_fill(const ZrPass& P, const ZrObject* objs, const uint32_t* work, const uint32_t* rects, const uint32_t* tile_offset,
-                        uint32_t* tile_cursor, ZrBinEntry* bins, const ZrHiz& Z, ZrDevStats* stats, int slot, hipStream_t s)
+                        uint32_t* tile_cursor, ZrBinEntry* bins, const ZrHiz& Z, ZrDevStats* stats, hipStream_t s)
 {
     if (P.n_work == 0) return;
     const uint32_t n_tiles = P.tiles_x * P.tiles_y;
     hipLaunchKernelGGL(k_bin_fill, dim3((P.n_work + 1023) / 1024), dim3(1024), n_tiles * sizeof(uint32_t), s, P, objs, work, rects,
-                       tile_offset, tile_cursor, bins, Z, stats, slot);
+                       tile_offset, tile_cursor, bins, Z, stats);
 }
-void zr_launch_raster_chunks(const ZrPass& P, const ZrObject* objs, const uint4* chunk_tab,
-                             const ZrBinEntry* bins, ZrDevStats* stats, int slot, unsigned long long* vis64, uint32_t* shadow_bits,
-                             uint32_t n_blocks, const ZrHiz& Z, hipStream_t s, uint4* slow, uint32_t slow_cap, const uint32_t* tiles, uint32_t n_tiles, int stage)
+void zr_launch_raster_chunks(const ZrPass& P, const ZrObject* objs, const uint4* chunk_tab, const ZrBinEntry* bins, ZrDevStats* stats, int slot,
+                             uint32_t* shadow_bits, uint32_t n_blocks, hipStream_t s, uint4* slow, uint32_t slow_cap, const uint32_t* tiles,
+                             uint32_t n_tiles, int stage)
 {
-    const float* none = nullptr;
-#ifdef ZR_DIAG      // the camera pass through this rasteriser: A/B builds only (ZR_FLAG_MESHLET_BINS)
-    if (P.mode == ZR_MODE_GBUFFER && Z.phase == 2u) {
-        hipLaunchKernelGGL((k_raster_chunks<ZR_MODE_GBUFFER, true, false>), dim3(n_blocks), dim3(RTHREADS), 0, s, P, objs, chunk_tab, bins, stats, slot, vis64, shadow_bits, (const float*)Z.lvl[0], Z.hw[0], Z.hh[0], (uint4*)nullptr, 0u);
-        return;
-    }
-    if (P.mode == ZR_MODE_GBUFFER) {
-        hipLaunchKernelGGL((k_raster_chunks<ZR_MODE_GBUFFER, false, false>), dim3(n_blocks), dim3(RTHREADS), 0, s, P, objs, chunk_tab, bins, stats, slot, vis64, shadow_bits, none, 0u, 0u, (uint4*)nullptr, 0u);
-        return;
-    }
-#endif
-    if (P.mode == ZR_MODE_GBUFFER) return;      // (not reached: the product's camera pass is triangle-binned)
-    if (slow) {    // shadow pass: clipped triangles go through a list + k_tile_slow
-        if (stage == 2) hipLaunchKernelGGL((k_raster_chunks<ZR_MODE_SHADOW, false, true, true>), dim3(n_blocks), dim3(RTHREADS), 0, s, P, objs, chunk_tab, bins, stats, slot, vis64, shadow_bits, none, 0u, 0u, slow, slow_cap);
-        else hipLaunchKernelGGL((k_raster_chunks<ZR_MODE_SHADOW, false, true>), dim3(n_blocks), dim3(RTHREADS), 0, s, P, objs, chunk_tab, bins, stats, slot, vis64, shadow_bits, none, 0u, 0u, slow, slow_cap);
-        if (n_tiles && stage != 1) hipLaunchKernelGGL((k_tile_slow<ZR_MODE_SHADOW, true>), dim3(std::min<uint32_t>(n_tiles, ZR_SLOW_BLOCKS)), dim3(256), 0, s, P, tiles, n_tiles, slow, slow_cap, stats, slot,
-                                        (unsigned long long*)nullptr, shadow_bits, (const uint32_t*)nullptr, 0u);
-    } else if (stage == 2)
-        hipLaunchKernelGGL((k_raster_chunks<ZR_MODE_SHADOW, false, false, true>), dim3(n_blocks), dim3(RTHREADS), 0, s, P, objs, chunk_tab, bins, stats, slot, vis64, shadow_bits, none, 0u, 0u, (uint4*)nullptr, 0u);
-    else
-        hipLaunchKernelGGL((k_raster_chunks<ZR_MODE_SHADOW, false, false>), dim3(n_blocks), dim3(RTHREADS), 0, s, P, objs, chunk_tab, bins, stats, slot, vis64, shadow_bits, none, 0u, 0u, (uint4*)nullptr, 0u);
+    if (stage == 2) hipLaunchKernelGGL(k_raster_chunks<true>, dim3(n_blocks), dim3(RTHREADS), 0, s, P, objs, chunk_tab, bins, stats, slot, shadow_bits, slow, slow_cap);
+    else hipLaunchKernelGGL(k_raster_chunks<false>, dim3(n_blocks), dim3(RTHREADS), 0, s, P, objs, chunk_tab, bins, stats, slot, shadow_bits, slow, slow_cap);
+    if (n_tiles && stage != 1) hipLaunchKernelGGL((k_tile_slow<ZR_MODE_SHADOW, true>), dim3(std::min<uint32_t>(n_tiles, ZR_SLOW_BLOCKS)), dim3(256), 0, s, P, tiles, n_tiles, slow, slow_cap, stats, slot,
+                                    (unsigned long long*)nullptr, shadow_bits, (const uint32_t*)nullptr, 0u);
 }
 void zr_launch_shadow_occlusion(const ZrPass& P, const ZrObject* objs, const uint32_t* work, const uint32_t* rects, const uint2* pxrect,
                                 const float* zmin, uint8_t* flags, const uint32_t* shadow_bits, ZrBinEntry* bins, ZrDevStats* stats,
