@@ -2,19 +2,79 @@
 #pragma once
 
 #include <atomic>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <new>
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "zr_ids.h"
 #include "zr_meshlet.h"
 #include "zr_types.h"
 
+// The owner of one lifetime's HIP resources: device memory, pinned host memory, events and streams are made through it, and it frees
+// what it made, newest first, on release() and when it is destroyed.  The kernel-argument structs keep their raw pointers: views into
+// owned memory.  (Hidden: no exported symbol.)
+class __attribute__((visibility("hidden"))) ZrOwn {
+public:
+    ZrOwn() = default;
+    ZrOwn(ZrOwn&& o) noexcept : items_(std::move(o.items_)) { o.items_.clear(); }
+    ZrOwn& operator=(ZrOwn&& o) noexcept { if (this != &o) { release(); items_.swap(o.items_); } return *this; }
+    ~ZrOwn() { release(); }
+
+    template <typename T> hipError_t alloc(T** p, size_t n) { return keep(Dev, p, room() ? hipMalloc((void**)p, (n ? n : 1) * sizeof(T)) : hipErrorOutOfMemory); }
+    // Images that kernels gather from at random (material textures, skydome, background): allocated in whole 2 MiB units, so that the
+    // driver maps them with large page fragments whatever the allocator's pools look like at the time - a 1.4 MiB texture that lands
+    // in 4 KiB-mapped memory costs the sampled resolve a third of its speed (seen as two modes of `value_textured`, run to run).
+    hipError_t alloc_image(uint8_t** p, size_t bytes) { return alloc(p, (bytes + (2u << 20) - 1) / (2u << 20) * (2u << 20)); }
+    template <typename T> hipError_t host(T** p, size_t n) { return keep(Host, p, room() ? hipHostMalloc((void**)p, n * sizeof(T), hipHostMallocDefault) : hipErrorOutOfMemory); }
+    hipError_t event(hipEvent_t* e, unsigned flags = hipEventDefault) { return keep(Event, e, room() ? hipEventCreateWithFlags(e, flags) : hipErrorOutOfMemory); }
+    hipError_t stream(hipStream_t* s) { return keep(Stream, s, room() ? hipStreamCreateWithFlags(s, hipStreamNonBlocking) : hipErrorOutOfMemory); }
+    hipError_t stream(hipStream_t* s, int priority) { return keep(Stream, s, room() ? hipStreamCreateWithPriority(s, hipStreamNonBlocking, priority) : hipErrorOutOfMemory); }
+    void adopt(ZrOwn&& o) { items_.insert(items_.end(), o.items_.begin(), o.items_.end()); o.items_.clear(); }      // o's, released before ours
+    void release() noexcept
+    {
+        for (auto it = items_.rbegin(); it != items_.rend(); ++it)
+            switch (it->kind) {
+            case Dev: (void)hipFree(it->p); break;
+            case Host: (void)hipHostFree(it->p); break;
+            case Event: (void)hipEventDestroy((hipEvent_t)it->p); break;
+            case Stream: (void)hipStreamDestroy((hipStream_t)it->p); break;
+            }
+        items_.clear();
+    }
+
+private:
+    enum Kind : uint8_t { Dev, Host, Event, Stream };
+    struct Item { Kind kind; void* p; };
+    std::vector<Item> items_;
+    bool room() noexcept             // a place for the next record, made before the resource: keeping it cannot throw
+    {
+        if (items_.size() < items_.capacity()) return true;
+        try { items_.reserve(2 * items_.size() + 16); return true; } catch (...) { return false; }
+    }
+    template <typename H> hipError_t keep(Kind k, H* h, hipError_t e) noexcept { if (e == hipSuccess && *h) items_.push_back({ k, (void*)*h }); return e; }
+};
+
+// hipMemset of device memory is ordered on the NULL stream and need not be complete when it returns; the library's streams are
+// non-blocking ones (no implicit ordering with the null stream): the fills are through before this returns, so before anything that
+// follows is enqueued on them.
+struct ZrFill { void* p; int value; size_t bytes; };
+static inline hipError_t zr_fill_sync(std::initializer_list<ZrFill> fills)
+{
+    for (const ZrFill& f : fills) {
+        const hipError_t e = hipMemset(f.p, f.value, f.bytes);
+        if (e != hipSuccess) return e;
+    }
+    return hipDeviceSynchronize();
+}
+
 struct ZrMesh {
+    ZrOwn mem;                           // the device buffers below (made by upload_mesh)
     std::vector<XkVertex> v;
     std::vector<uint32_t> idx;           // draw-order index buffer
     ZrMeshletSet ms;
@@ -32,6 +92,7 @@ struct ZrMaterialHost {
 };
 
 struct ZrSceneObject {
+    ZrOwn mem;                           // the device memory below: instance records, raw values, update state, material images
     uint32_t mesh = 0, n_inst = 1; bool instanced = false;
     std::vector<XkInstanceData> inst;    // host copy (zr_object_get_instances)
     ZrInstance* d_inst = nullptr;        // the instance records: what every frame reads until an update, then the parity-0 plane
@@ -64,7 +125,12 @@ struct ZrWorld {
 };
 struct ZrProfab { uint32_t mesh; ZrMaterialHost mat; };
 
+// Every HIP resource of the context is made through the owner of its lifetime: `own` (the context: what zr_create makes, its streams
+// first, and what later calls add for good), then one owner per group that is re-made or dropped as a whole (work pools, draw tables,
+// ids, skydome, background, cubemap, shadow tiles; the scene's in its meshes and objects; each staging slot).  `own` is declared first,
+// so zr_destroy's `delete` releases it last, after every other owner - and its streams last of all.
 struct zr_ctx {
+    ZrOwn own;
     zr_config cfg;
     int device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
@@ -76,7 +142,7 @@ struct zr_ctx {
     ZrObject* d_objs = nullptr; uint32_t n_objs = 0, n_work = 0;     // d_objs: the draw table of the frame enqueued last (an alias)
     // Draw tables: [0] made by finalize_scene (every object's d_inst), [1] the parity-1 table, once an instance has been updated: it
     // differs only where an updated object points at its parity-1 plane.  A frame reads the table and the planes of its parity.
-    ZrObject* d_objs_b[2] = { nullptr, nullptr };
+    ZrObject* d_objs_b[2] = { nullptr, nullptr }; ZrOwn tables;
     // Instance updates (zr_instances_host.cpp): inst_reader[p] = 1 + the last frame that read the table / planes of parity p (0: none);
     // ev_scatter follows the last update (on scatter_s), ev_apply the last frame-head apply (on apply_s); a pinned staging ring for the
     // host form.  Made at the first update: a scene that never moves an instance has none of it.
@@ -84,7 +150,7 @@ struct zr_ctx {
     hipEvent_t ev_scatter = nullptr, ev_apply = nullptr; hipStream_t scatter_s = nullptr, apply_s = nullptr;
     bool scatter_wait[2] = { false, false }, apply_done = false, inst_dual = false;      // scatter_wait[p]: the next frame of parity p waits for ev_scatter
     static constexpr int INST_RING = 4;
-    struct InstStage { XkInstanceData* h = nullptr; XkInstanceData* d = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; } inst_ring[INST_RING];
+    struct InstStage { ZrOwn mem; XkInstanceData* h = nullptr; XkInstanceData* d = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; } inst_ring[INST_RING];
     uint32_t inst_slot = 0;
     // this frame's two geometry passes (0 shadow, 1 camera), built at frame begin; the passes' work lists (k_cull_instances) are kept
     // while the pass block and the scene stand still: list_key = the block the list on the device was built from
@@ -108,9 +174,12 @@ struct zr_ctx {
     // The shadow MAP owned by light-space super-tiles (zr_set_shadow_tiles): this context draws the casters that can reach a tile of the map
     // it owns; its owned tiles are exact, the others hold leftovers until zr_shadow_unpack scatters every rank's tiles in.
     uint32_t stile_rank = 0, stile_world = 1, s_slots_per_rank = 0, n_sowned_rank = 0;
-    uint32_t *d_sowned_rank = nullptr, *d_stile_map = nullptr;
+    uint32_t *d_sowned_rank = nullptr, *d_stile_map = nullptr; ZrOwn stile_mem;
     uint32_t* d_tiles_ext = nullptr;     // caller-owned packed tile buffer for the next frames (zr_set_tiles_buffer), or null
 
+    // The work pools, sized for work_capacity meshlet-instances by make_work_pools: sc, sb.bins, sb.chunk_tab, tb, d_pxrect, d_zmin,
+    // d_visflag, d_spxrect, d_szmin, d_sflag
+    ZrOwn pools;
     // the cull's output, one set per geometry pass (0 shadow, 1 camera) so that the two pipelines can run on two streams
     struct CullList { uint32_t *rects = nullptr, *work = nullptr; } sc[2];
     // the shadow pass's meshlet bins: per-tile counts, list offsets, fill cursors and work-unit offsets; the lists; the work units
@@ -171,20 +240,21 @@ struct zr_ctx {
     bool id_capture = false;             // the next frames keep their winner plane (Gb[i].prim set)
     bool ids_frame = false, ids_this = false;      // the frame enqueued last kept it / the frame being enqueued does
     uint64_t scene_gen = 0, ids_gen = 0, ids_table_gen = ~0ull;      // objects added or cleared; the scene of the last frame / of the table
+    ZrOwn ids_table, ids_pool;           // d_ids_draws; the slot pools (d_ids_counts ... d_ids_hits)
     ZrIdsDraw* d_ids_draws = nullptr; uint32_t ids_n_draws = 0, ids_n_slots = 0, ids_slot_cap = 0;
     uint32_t *d_ids_counts = nullptr, *d_ids_cov = nullptr, *d_ids_list = nullptr, *d_ids_n = nullptr;
     unsigned long long* d_ids_keys = nullptr; zr_hit* d_ids_hits = nullptr; uint2* d_ids_obj = nullptr;
     // a census enqueued against copy i (zr_instance_coverage_async): the frame that writes copy i next waits for it
     hipEvent_t ev_ids[2] = { nullptr, nullptr }; bool ids_wait[2] = { false, false };
 
-    std::vector<uint8_t*> d_cube; CubeDesc cube = {}; uint32_t cube_dim = 0, cube_levels = 0;
+    ZrOwn cube_mem; CubeDesc cube = {}; uint32_t cube_dim = 0, cube_levels = 0;
     float lut[256]; float* d_lut = nullptr;
     float* d_unorm_lut = nullptr;        // [0..255] = c / 255, [256..1279] = c / 1023 (IEEE quotients, computed on the host)
 
     static constexpr int EV_RING = 64;     // per-pass hipEvents of the last EV_RING timed frames (bench averages over them)
     // skydome + background passes (ZE:2657-2744, 3681-3699)
     ZrMesh sky_mesh; ZrSceneObject sky_obj; bool sky_set = false, sky_enabled = true;
-    uint8_t* d_bg = nullptr; uint32_t bg_w = 0, bg_h = 0, bg_levels = 0; bool bg_set = false, bg_enabled = true;
+    ZrOwn bg_mem; uint8_t* d_bg = nullptr; uint32_t bg_w = 0, bg_h = 0, bg_levels = 0; bool bg_set = false, bg_enabled = true;
 
     hipEvent_t evr[EV_RING][10] = {}; uint64_t frame_no = 0; bool rendered = false;
     uint32_t timing_interval = 1; bool timing_now = true; uint64_t sample_no = 0;    // pass events every interval-th frame
@@ -198,19 +268,10 @@ struct zr_ctx {
 };
 
 int zr_fail(zr_ctx* c, int code, const std::string& msg);      // records the message (never throws), returns code
-// an object's device memory (its instance records, raw values, update state, material images)
-inline void zr_object_free_device(ZrSceneObject& o)
-{
-    ZrInstance* plane1 = o.upd.plane[1];
-    for (void* p : { (void*)o.d_inst, (void*)o.d_raw, (void*)plane1, (void*)o.upd.dirty }) if (p) (void)hipFree(p);
-    o.d_inst = nullptr; o.d_raw = nullptr; o.upd = ZrInstanceState{}; o.tab1 = false;
-    for (auto& t : o.d_tex) if (t) { (void)hipFree(t); t = nullptr; }
-}
 // zr_instances_host.cpp
 int zr_instances_frame(zr_ctx* c, hipStream_t s, int par);       // frame head: this frame's draw table, the updates that are due
 int zr_instances_table(zr_ctx* c);                               // finalize_scene: the parity-1 table of a new draw table
 int zr_instances_sync_host(zr_ctx* c, ZrSceneObject& o);         // zr_object_get_instances after a device-form update
-void zr_instances_destroy(zr_ctx* c);
 // No exception crosses the C-ABI: entry points that build host-side containers run their body through this.
 template <typename F> static inline int zr_guard(zr_ctx* c, F&& body) noexcept
 {

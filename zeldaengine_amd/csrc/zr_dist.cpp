@@ -18,10 +18,12 @@
 #include <rccl/rccl.h>
 
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
 struct ZrDist {
+    ZrOwn mem;                        // the buffers, events and stream below
     void* lib = nullptr;
     ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
     ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
@@ -79,24 +81,10 @@ void zr_dist_destroy(zr_ctx* c)
     if (!d) return;
     if (d->comm_s) (void)hipStreamSynchronize(d->comm_s);
     if (d->comm && d->CommDestroy) (void)d->CommDestroy(d->comm);
-    for (int b = 0; b < 2; ++b) {
-        if (d->tiles[b]) (void)hipFree(d->tiles[b]);
-        if (d->gathered[b]) (void)hipFree(d->gathered[b]);
-        if (d->rendered[b]) (void)hipEventDestroy(d->rendered[b]);
-        if (d->consumed[b]) (void)hipEventDestroy(d->consumed[b]);
-    }
-    if (d->shadow) {
-        if (c->d_shadow_ext == d->shadow) { c->d_shadow_ext = nullptr; c->shadow_rank = 0; c->shadow_world = 1; }      // back to the whole map
-        (void)hipFree(d->shadow);
-    }
+    if (d->shadow && c->d_shadow_ext == d->shadow) { c->d_shadow_ext = nullptr; c->shadow_rank = 0; c->shadow_world = 1; }      // back to the whole map
     if (d->shadow_tiles && c->stile_world > 1) (void)zr_set_shadow_tiles(c, 0, 1);      // back to the whole map
-    if (d->spacked) (void)hipFree(d->spacked);
-    if (d->sgathered) (void)hipFree(d->sgathered);
-    if (d->shadow_packed) (void)hipEventDestroy(d->shadow_packed);
-    if (d->shadow_reduced) (void)hipEventDestroy(d->shadow_reduced);
-    if (d->comm_s) (void)hipStreamDestroy(d->comm_s);
     if (c->d_tiles_ext == d->tiles[0] || c->d_tiles_ext == d->tiles[1]) c->d_tiles_ext = nullptr;
-    delete d;
+    delete d;                         // (its owner releases the buffers, the events and the stream)
     c->dist = nullptr;
 }
 
@@ -115,43 +103,43 @@ extern "C" int zr_dist_prepare(zr_ctx* c, uint32_t rank, uint32_t world, uint32_
     if (world == 1 && !(c->cfg.flags & ZR_FLAG_PACKED_TILES))
         return zr_fail(c, ZR_ERR_ARG, "zr_dist_prepare: a world of one needs ZR_FLAG_PACKED_TILES (the packed tile path)");
     HIPCHK(c, hipSetDevice(c->device));
-    ZrDist* d = new (std::nothrow) ZrDist();
+    // made whole before it becomes c->dist: a failure drops it, and its owner what it made
+    std::unique_ptr<ZrDist> d(new (std::nothrow) ZrDist());
     if (!d) return zr_fail(c, ZR_ERR_OOM, "zr_dist_prepare: out of memory");
-    c->dist = d;
     std::string err;
-    if (!load_rccl(d, &err)) { zr_dist_destroy(c); return zr_fail(c, ZR_ERR_UNSUPPORTED, err); }
-    if ((dist_flags & ZR_DIST_SPLIT_SHADOW) && (dist_flags & ZR_DIST_SHADOW_TILES)) { zr_dist_destroy(c); return zr_fail(c, ZR_ERR_ARG, "zr_dist_prepare: SPLIT_SHADOW and SHADOW_TILES exclude each other"); }
+    if (!load_rccl(d.get(), &err)) return zr_fail(c, ZR_ERR_UNSUPPORTED, err);
+    if ((dist_flags & ZR_DIST_SPLIT_SHADOW) && (dist_flags & ZR_DIST_SHADOW_TILES)) return zr_fail(c, ZR_ERR_ARG, "zr_dist_prepare: SPLIT_SHADOW and SHADOW_TILES exclude each other");
     d->rank = rank; d->world = world; d->split_shadow = (dist_flags & ZR_DIST_SPLIT_SHADOW) != 0 && world > 1;
     d->shadow_tiles = (dist_flags & ZR_DIST_SHADOW_TILES) != 0 && world > 1;
     d->tile_bytes = (size_t)c->slots_per_rank * ZR_TILE * ZR_TILE * 4;
-    auto bail = [&](int code, const std::string& m) { zr_dist_destroy(c); return zr_fail(c, code, m); };
+    ZrOwn& A = d->mem;
     int least = 0, greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-    if (hipStreamCreateWithPriority(&d->comm_s, hipStreamNonBlocking, least) != hipSuccess) return bail(ZR_ERR_DEVICE, "zr_dist_prepare: stream");
+    if (A.stream(&d->comm_s, least) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "zr_dist_prepare: stream");
     for (int b = 0; b < 2; ++b) {
-        if (hipMalloc((void**)&d->tiles[b], d->tile_bytes) != hipSuccess || hipMalloc((void**)&d->gathered[b], d->tile_bytes * world) != hipSuccess ||
-            hipMemset(d->tiles[b], 0, d->tile_bytes) != hipSuccess ||
-            hipEventCreateWithFlags(&d->rendered[b], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&d->consumed[b], hipEventDisableTiming) != hipSuccess) return bail(ZR_ERR_DEVICE, "zr_dist_prepare: buffers");
+        if (A.alloc(&d->tiles[b], d->tile_bytes / 4) != hipSuccess || A.alloc(&d->gathered[b], d->tile_bytes / 4 * world) != hipSuccess ||
+            A.event(&d->rendered[b], hipEventDisableTiming) != hipSuccess ||
+            A.event(&d->consumed[b], hipEventDisableTiming) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "zr_dist_prepare: buffers");
     }
-    if (hipDeviceSynchronize() != hipSuccess) return bail(ZR_ERR_DEVICE, "zr_dist_prepare: fills");      // (null-stream fills; the streams are non-blocking ones)
+    if (zr_fill_sync({ { d->tiles[0], 0, d->tile_bytes }, { d->tiles[1], 0, d->tile_bytes } }) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "zr_dist_prepare: fills");
     if (d->split_shadow) {
-        if (hipMalloc((void**)&d->shadow, (size_t)c->SD * c->SD * 4) != hipSuccess ||
-            hipEventCreateWithFlags(&d->shadow_reduced, hipEventDisableTiming) != hipSuccess) return bail(ZR_ERR_DEVICE, "zr_dist_prepare: shadow buffer");
+        if (A.alloc(&d->shadow, (size_t)c->SD * c->SD) != hipSuccess ||
+            A.event(&d->shadow_reduced, hipEventDisableTiming) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "zr_dist_prepare: shadow buffer");
     }
     if (d->shadow_tiles) {
         // the map's tile partition for `world` ranks: sizes only (the context keeps drawing the whole map until the communicator stands)
         uint32_t n_owned = 0, spr = 0;
-        if (zr_tile_partition(c->SD, c->SD, world, rank, nullptr, &n_owned, &spr) != ZR_OK) return bail(ZR_ERR_ARG, "zr_dist_prepare: shadow tile partition");
+        if (zr_tile_partition(c->SD, c->SD, world, rank, nullptr, &n_owned, &spr) != ZR_OK) return zr_fail(c, ZR_ERR_ARG, "zr_dist_prepare: shadow tile partition");
         d->stile_bytes = (size_t)spr * ZR_TILE * ZR_TILE * 4;
-        if (hipMalloc((void**)&d->spacked, d->stile_bytes) != hipSuccess || hipMalloc((void**)&d->sgathered, d->stile_bytes * world) != hipSuccess ||
-            hipEventCreateWithFlags(&d->shadow_packed, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&d->shadow_reduced, hipEventDisableTiming) != hipSuccess) return bail(ZR_ERR_DEVICE, "zr_dist_prepare: shadow tile buffers");
+        if (A.alloc(&d->spacked, d->stile_bytes / 4) != hipSuccess || A.alloc(&d->sgathered, d->stile_bytes / 4 * world) != hipSuccess ||
+            A.event(&d->shadow_packed, hipEventDisableTiming) != hipSuccess ||
+            A.event(&d->shadow_reduced, hipEventDisableTiming) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "zr_dist_prepare: shadow tile buffers");
         {   // unused slots of a rank with fewer tiles than slots_per_rank are gathered too: depth 1.0, once
             std::vector<uint32_t> ones(d->stile_bytes / 4, 0x3F800000u);
-            if (hipMemcpy(d->spacked, ones.data(), d->stile_bytes, hipMemcpyHostToDevice) != hipSuccess) return bail(ZR_ERR_DEVICE, "zr_dist_prepare: shadow tile buffers");
+            if (hipMemcpy(d->spacked, ones.data(), d->stile_bytes, hipMemcpyHostToDevice) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "zr_dist_prepare: shadow tile buffers");
         }
     }
+    c->dist = d.release();
     return ZR_OK;
 }
 

@@ -54,17 +54,6 @@ static uint8_t srgb_encode8(float l)
     return (uint8_t)floor(s * 255.0 + 0.5);
 }
 
-template <typename T> static hipError_t dev_alloc(T** p, size_t n) { return hipMalloc((void**)p, (n ? n : 1) * sizeof(T)); }
-template <typename T> static void dev_free(T*& p) { if (p) { (void)hipFree((void*)p); p = nullptr; } }
-// Images that kernels gather from at random (material textures, skydome, background): allocated in whole 2 MiB units, so that the
-// driver maps them with large page fragments whatever the allocator's pools look like at the time - a 1.4 MiB texture that lands
-// in 4 KiB-mapped memory costs the sampled resolve a third of its speed (seen as two modes of `value_textured`, run to run).
-static hipError_t dev_alloc_image(uint8_t** p, size_t bytes)
-{
-    const size_t unit = (size_t)2 << 20;
-    return hipMalloc((void**)p, (bytes + unit - 1) / unit * unit);
-}
-
 // ------------------------------------------------------------------------------------------------ lifetime
 
 static void default_lights(XkView* v)
@@ -74,6 +63,143 @@ static void default_lights(XkView* v)
     for (auto& l : v->DirectionalLights) l = d;
     for (auto& l : v->PointLights) l = d;
     for (auto& l : v->SpotLights) l = d;
+}
+
+// zr_create's device half, straight through: it returns at the first failure, and the caller releases the partial context as
+// zr_destroy releases any other
+static int create_device_state(zr_ctx* c)
+{
+    ZrOwn& A = c->own;
+    HIPCHK(c, A.stream(&c->own_stream));
+    c->stream = c->own_stream;
+    for (auto& fr : c->evr) for (auto& e : fr) HIPCHK(c, A.event(&e));
+    for (auto& e : c->ev_end) HIPCHK(c, A.event(&e));
+    for (auto& e : c->ev_ids) HIPCHK(c, A.event(&e, hipEventDisableTiming));
+    const size_t n = (size_t)c->W * c->H;
+    for (int b = 0; b < 2; ++b) {       // two frames in flight: see zr_ctx.h
+        GBufferPtrs& G = c->Gb[b];
+        HIPCHK(c, A.alloc(&G.depth, n)); HIPCHK(c, A.alloc(&G.scene_color, n)); HIPCHK(c, A.alloc(&G.gA, n)); HIPCHK(c, A.alloc(&G.gB, n));
+        HIPCHK(c, A.alloc(&G.gC, n)); HIPCHK(c, A.alloc(&G.gD, n)); HIPCHK(c, A.alloc(&G.overlay, n));
+        HIPCHK(c, A.alloc(&c->d_shadow_b[b], (size_t)c->SD * c->SD)); HIPCHK(c, A.alloc(&c->d_view_b[b], 1)); HIPCHK(c, A.alloc(&c->d_empty_b[b], 1));
+    }
+    c->G = c->Gb[0]; c->d_shadow = c->d_shadow_b[0]; c->d_view = c->d_view_b[0]; c->d_empty_rgba = c->d_empty_b[0];
+    HIPCHK(c, A.alloc(&c->d_color, n)); HIPCHK(c, A.alloc(&c->d_stats, 1));
+    HIPCHK(c, A.alloc(&c->d_sstats, 1));       // the shadow pipeline's own block (see zr_ctx.h)
+    HIPCHK(c, A.alloc(&c->d_lut, 256));
+    HIPCHK(c, hipMemcpy(c->d_lut, c->lut, sizeof c->lut, hipMemcpyHostToDevice));
+    {
+        std::vector<float> ul(1280);
+        for (int i = 0; i < 256; ++i) {
+            ul[(size_t)i] = (float)i / 255.0f;
+            if (fmaf((float)i, ZR_UNORM8_HI, (float)i * ZR_UNORM8_LO) != ul[(size_t)i])        // the packed sampler's division-free decode
+                return zr_fail(c, ZR_ERR_DEVICE, "ZR_UNORM8_HI / ZR_UNORM8_LO do not decode c / 255 exactly");
+        }
+        for (int i = 0; i < 1024; ++i) ul[256 + (size_t)i] = (float)i / 1023.0f;
+        HIPCHK(c, A.alloc(&c->d_unorm_lut, ul.size()));
+        HIPCHK(c, hipMemcpy(c->d_unorm_lut, ul.data(), ul.size() * 4, hipMemcpyHostToDevice));
+    }
+
+    // screen tiles: camera target partitioned t % world == rank; the shadow map is rendered whole on every rank
+    c->tiles_x = (c->W + ZR_TILE - 1) / ZR_TILE; c->tiles_y = (c->H + ZR_TILE - 1) / ZR_TILE; c->n_tiles = c->tiles_x * c->tiles_y;
+    c->stiles_x = (c->SD + ZR_TILE - 1) / ZR_TILE; c->stiles_y = c->stiles_x; c->sn_tiles = c->stiles_x * c->stiles_y;
+    if (c->n_tiles > 16000u || c->sn_tiles > 16000u) return zr_fail(c, ZR_ERR_ARG, "too many tiles");   // binning histograms (4 B per tile, dynamic) + a few static words must fit the default 64 KB of LDS per workgroup
+    // tile ownership (zr_tile_owner): per rank the owned tiles in increasing index = its slots in the packed buffer
+    std::vector<uint32_t> owned, sowned(c->sn_tiles), tile_map(c->n_tiles), counts(c->cfg.tile_world, 0u);
+    for (uint32_t t = 0; t < c->n_tiles; ++t) {
+        const uint32_t o = zr_tile_owner(t % c->tiles_x, t / c->tiles_x, c->cfg.tile_world);
+        tile_map[t] = counts[o]++;                       // slot within its owner, for now
+        if (o == c->cfg.tile_rank) owned.push_back(t);
+    }
+    c->slots_per_rank = 0;
+    for (uint32_t n : counts) c->slots_per_rank = std::max(c->slots_per_rank, n);
+    for (uint32_t t = 0; t < c->n_tiles; ++t)
+        tile_map[t] += zr_tile_owner(t % c->tiles_x, t / c->tiles_x, c->cfg.tile_world) * c->slots_per_rank;
+    HIPCHK(c, A.alloc(&c->d_tile_map, tile_map.size()));
+    HIPCHK(c, hipMemcpy(c->d_tile_map, tile_map.data(), tile_map.size() * 4, hipMemcpyHostToDevice));
+    for (uint32_t t = 0; t < c->sn_tiles; ++t) sowned[t] = t;
+    c->n_owned = (uint32_t)owned.size();
+    HIPCHK(c, A.alloc(&c->d_owned, owned.size())); HIPCHK(c, A.alloc(&c->d_sowned, sowned.size()));
+    HIPCHK(c, A.alloc(&c->d_tiles, (size_t)c->slots_per_rank * ZR_TILE * ZR_TILE));
+    if (!owned.empty()) HIPCHK(c, hipMemcpy(c->d_owned, owned.data(), owned.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_sowned, sowned.data(), sowned.size() * 4, hipMemcpyHostToDevice));
+    const uint32_t mt = (c->n_tiles > c->sn_tiles ? c->n_tiles : c->sn_tiles) * ZR_TSTRIDE + 1;     // (the bins use the first sn_tiles + 1 words)
+    HIPCHK(c, A.alloc(&c->sb.tile_count, mt)); HIPCHK(c, A.alloc(&c->sb.tile_offset, mt));
+    HIPCHK(c, A.alloc(&c->sb.tile_cursor, mt)); HIPCHK(c, A.alloc(&c->sb.chunk_offset, mt));
+    {   // the clear values of ZE:3427-3433, as resolve_pixel writes them for an empty pixel
+        HIPCHK(c, A.alloc(&c->d_clear_px, 64));
+        uint32_t px[16] = { 0 };
+        px[0] = 0x3F800000u;                    // depth 1.0
+        px[1] = 0xFF000000u; px[2] = 0u; px[3] = 0xFF000000u; px[4] = 0xFF000000u;   // SceneColor, A, B, C
+        px[6] = 0u; px[7] = 0x3C000000u;        // D = (0, 0, 0, 1) as fp16
+        px[8] = 0u;                             // overlay
+        HIPCHK(c, hipMemcpy(c->d_clear_px, px, sizeof px, hipMemcpyHostToDevice));
+        uint32_t* w = (uint32_t*)c->d_clear_px;
+        c->Gclear.depth = (float*)w; c->Gclear.scene_color = w + 1; c->Gclear.gA = w + 2; c->Gclear.gB = w + 3; c->Gclear.gC = w + 4;
+        c->Gclear.gD = (uint2*)(w + 6); c->Gclear.overlay = w + 8;
+    }
+    {   // environment switches, read once
+#ifdef ZR_DIAG       // work-skipping / printing switches: diagnostic builds only (zeldaengine_amd.build.build(extra_flags=["-DZR_DIAG"]))
+        const char* e;
+        if ((e = getenv("ZR_DEBUG_SKIP"))) c->env_skip = (uint32_t)atoi(e);                 // 1: no pixel walk, 2: no triangle phase
+        if ((e = getenv("ZR_DEBUG_SKIP_LIGHT"))) c->env_skip_light = (uint32_t)atoi(e);     // bits: 1 PCF, 2 lights, 4 reflection
+        if ((e = getenv("ZR_LIGHT_LIST_MIN"))) c->env_light_list_min = atoi(e);
+        c->env_no_empty_px = getenv("ZR_NO_EMPTY_PIXEL") != nullptr;
+#endif
+    }
+    HIPCHK(c, A.host(&c->h_view_ring, zr_ctx::VIEW_RING));
+    for (auto& e : c->view_ev) HIPCHK(c, A.event(&e, hipEventDisableTiming));
+    {   // The camera lane must not share a hardware queue with the host's stream (HIP multiplexes streams onto a few of them and
+        // two streams on one queue run strictly one after the other).  Streams of different priority come from different queue
+        // pools.  Which priority: the frame's period is the HOST's lane (lighting -> shadow pipeline), and since the camera lane lost its
+        // two scans and two index passes per frame (round 6: tile buckets) it no longer fills the period - at the highest priority it
+        // took from the host lane what it saved itself (5 300 Mpixel/s), at the lowest the host lane keeps its share (5 540; normal: 5 470).
+        int least = 0, greatest = 0;
+        (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+        HIPCHK(c, A.stream(&c->cam_s, least));
+    }
+    HIPCHK(c, A.event(&c->ev_cam, hipEventDisableTiming)); HIPCHK(c, A.event(&c->ev_join, hipEventDisableTiming));
+    HIPCHK(c, A.alloc(&c->d_vis, n));
+    { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) c->raster_blocks = (uint32_t)prop.multiProcessorCount * 12u; }      // k_tile's persistent grid (6 workgroups fit a CU: two rounds of them; A/B 4 / 6 / 8 / 12 / 16 / 32 per CU -> 5 133 / 5 250 / 5 294 / 5 344 / 5 327 / 5 277 Mpixel/s)
+    c->shadow_blocks = c->raster_blocks / 12u * 8u;      // the shadow rasteriser's persistent grid stays at 8 per CU
+    c->slow0_cap = std::max<uint32_t>(c->slow0_cap, 128u * c->sn_tiles);      // (a clipped triangle is listed once per tile of its meshlet)
+    HIPCHK(c, A.alloc(&c->d_slow0, 4ull * c->slow0_cap));
+#ifdef ZR_DIAG
+    if (const char* e = getenv("ZR_RASTER_BLOCKS")) c->raster_blocks = (uint32_t)std::max(1, atoi(e));
+    if (const char* e = getenv("ZR_SHADOW_BLOCKS")) c->shadow_blocks = (uint32_t)std::max(1, atoi(e));
+#endif
+    size_t hiz_texels = 0;
+    {   // Hi-Z pyramid: level l = max depth per (8 << l)^2 pixel block
+        for (int l = 0; l < 4; ++l) { c->hiz.hw[l] = (c->W + (8u << l) - 1) / (8u << l); c->hiz.hh[l] = (c->H + (8u << l) - 1) / (8u << l); hiz_texels += (size_t)c->hiz.hw[l] * c->hiz.hh[l]; }
+        c->hiz.fw = (c->W + 3u) / 4u; c->hiz.fh = (c->H + 3u) / 4u;
+        hiz_texels += (size_t)c->hiz.fw * c->hiz.fh;
+        HIPCHK(c, A.alloc(&c->d_hiz, hiz_texels));
+        static_assert(ZR_TILE == 32 && ZR_SUPERTILE_SHIFT >= 1, "a 64 x 64 region of the pyramid must lie inside one super-tile");
+        std::vector<uint32_t> regions;
+        for (uint32_t ry = 0; ry < (c->H + 63u) / 64u; ++ry)
+            for (uint32_t rx = 0; rx < (c->W + 63u) / 64u; ++rx)
+                if (zr_tile_owner(rx * 2u, ry * 2u, c->cfg.tile_world) == c->cfg.tile_rank) regions.push_back(rx | ry << 16);
+        c->n_hiz_regions = (uint32_t)regions.size();
+        HIPCHK(c, A.alloc(&c->d_hiz_regions, regions.size()));
+        if (!regions.empty()) HIPCHK(c, hipMemcpy(c->d_hiz_regions, regions.data(), regions.size() * 4, hipMemcpyHostToDevice));
+        float* p = c->d_hiz;
+        for (int l = 0; l < 4; ++l) { c->hiz.lvl[l] = p; p += (size_t)c->hiz.hw[l] * c->hiz.hh[l]; }
+        c->hiz.fine = p;
+    }
+    HIPCHK(c, zr_fill_sync({ { c->Gb[0].overlay, 0, n * 4 }, { c->Gb[1].overlay, 0, n * 4 },
+                             { c->d_stats, 0, sizeof(ZrDevStats) }, { c->d_sstats, 0, sizeof(ZrDevStats) }, { c->d_color, 0, n * 4 },
+                             { c->d_tiles, 0, (size_t)c->slots_per_rank * ZR_TILE * ZR_TILE * 4 },
+                             { c->sb.tile_count, 0, mt * 4 },       // k_bin_count counts into zeroes (k_scan zeroes the counts
+                             { c->sb.tile_cursor, 0, mt * 4 },      // and the cursors again for the fill and the next frame)
+                             { c->d_hiz, 0, hiz_texels * sizeof(float) } }));      // texels over other ranks' regions stay 0 ("hidden")
+    zr_launch_fill64(c->d_vis, (unsigned long long)0x3F800000u << 32 | ZR_EMPTY_PRIM, n, c->stream);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    // The runtime backs an event with a signal on its FIRST record and grows that pool in batches, which blocks the host for
+    // milliseconds at unpredictable frames of a short run: record every event once now.
+    for (auto& fr : c->evr) for (auto& e : fr) HIPCHK(c, hipEventRecord(e, c->stream));
+    for (auto& e : c->ev_end) HIPCHK(c, hipEventRecord(e, c->stream));
+    for (auto& e : c->view_ev) HIPCHK(c, hipEventRecord(e, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZR_OK;
 }
 
 extern "C" int zr_create(const zr_config* cfg, zr_ctx** out)
@@ -97,185 +223,11 @@ extern "C" int zr_create(const zr_config* cfg, zr_ctx** out)
     memset(&c->cam, 0, sizeof c->cam); memset(&c->shadow, 0, sizeof c->shadow); memset(&c->view, 0, sizeof c->view);
     default_lights(&c->view);
     for (int i = 0; i < 256; ++i) c->lut[i] = zr_srgb_decode8((uint32_t)i);
-
-    bool ok = true;
-    ok &= hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) == hipSuccess;
-    c->stream = c->own_stream;
-    for (auto& fr : c->evr) for (auto& e : fr) ok &= hipEventCreate(&e) == hipSuccess;
-    for (auto& e : c->ev_end) ok &= hipEventCreate(&e) == hipSuccess;
-    for (auto& e : c->ev_ids) ok &= hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
-    const size_t n = (size_t)c->W * c->H;
-    for (int b = 0; b < 2; ++b) {       // two frames in flight: see zr_ctx.h
-        GBufferPtrs& G = c->Gb[b];
-        ok &= dev_alloc(&G.depth, n) == hipSuccess;
-        ok &= dev_alloc(&G.scene_color, n) == hipSuccess;
-        ok &= dev_alloc(&G.gA, n) == hipSuccess;
-        ok &= dev_alloc(&G.gB, n) == hipSuccess;
-        ok &= dev_alloc(&G.gC, n) == hipSuccess;
-        ok &= dev_alloc(&G.gD, n) == hipSuccess;
-        ok &= dev_alloc(&G.overlay, n) == hipSuccess;
-        if (ok) ok &= hipMemset(G.overlay, 0, n * 4) == hipSuccess;
-        ok &= dev_alloc(&c->d_shadow_b[b], (size_t)c->SD * c->SD) == hipSuccess;
-        ok &= dev_alloc(&c->d_view_b[b], 1) == hipSuccess;
-        ok &= dev_alloc(&c->d_empty_b[b], 1) == hipSuccess;
-    }
-    c->G = c->Gb[0]; c->d_shadow = c->d_shadow_b[0]; c->d_view = c->d_view_b[0]; c->d_empty_rgba = c->d_empty_b[0];
-    ok &= dev_alloc(&c->d_color, n) == hipSuccess;
-    ok &= dev_alloc(&c->d_stats, 1) == hipSuccess;
-    if (ok) ok &= hipMemset(c->d_stats, 0, sizeof(ZrDevStats)) == hipSuccess;
-    ok &= dev_alloc(&c->d_sstats, 1) == hipSuccess;       // the shadow pipeline's own block (see zr_ctx.h)
-    if (ok) ok &= hipMemset(c->d_sstats, 0, sizeof(ZrDevStats)) == hipSuccess;
-    ok &= dev_alloc(&c->d_lut, 256) == hipSuccess;
-    if (ok) ok &= hipMemcpy(c->d_lut, c->lut, sizeof c->lut, hipMemcpyHostToDevice) == hipSuccess;
-    {
-        std::vector<float> ul(1280);
-        for (int i = 0; i < 256; ++i) {
-            ul[(size_t)i] = (float)i / 255.0f;
-            ok &= fmaf((float)i, ZR_UNORM8_HI, (float)i * ZR_UNORM8_LO) == ul[(size_t)i];        // the packed sampler's division-free decode
-        }
-        for (int i = 0; i < 1024; ++i) ul[256 + (size_t)i] = (float)i / 1023.0f;
-        ok &= dev_alloc(&c->d_unorm_lut, ul.size()) == hipSuccess;
-        if (ok) ok &= hipMemcpy(c->d_unorm_lut, ul.data(), ul.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-    }
-    if (ok) ok &= hipMemset(c->d_color, 0, n * 4) == hipSuccess;
-
-    // screen tiles: camera target partitioned t % world == rank; the shadow map is rendered whole on every rank
-    c->tiles_x = (c->W + ZR_TILE - 1) / ZR_TILE; c->tiles_y = (c->H + ZR_TILE - 1) / ZR_TILE; c->n_tiles = c->tiles_x * c->tiles_y;
-    c->stiles_x = (c->SD + ZR_TILE - 1) / ZR_TILE; c->stiles_y = c->stiles_x; c->sn_tiles = c->stiles_x * c->stiles_y;
-    if (c->n_tiles > 16000u || c->sn_tiles > 16000u) { zr_destroy(c); return ZR_ERR_ARG; }   // binning histograms (4 B per tile, dynamic) + a few static words must fit the default 64 KB of LDS per workgroup
-    // tile ownership (zr_tile_owner): per rank the owned tiles in increasing index = its slots in the packed buffer
-    std::vector<uint32_t> owned, sowned(c->sn_tiles), tile_map(c->n_tiles), counts(c->cfg.tile_world, 0u);
-    for (uint32_t t = 0; t < c->n_tiles; ++t) {
-        const uint32_t o = zr_tile_owner(t % c->tiles_x, t / c->tiles_x, c->cfg.tile_world);
-        tile_map[t] = counts[o]++;                       // slot within its owner, for now
-        if (o == c->cfg.tile_rank) owned.push_back(t);
-    }
-    c->slots_per_rank = 0;
-    for (uint32_t n : counts) c->slots_per_rank = std::max(c->slots_per_rank, n);
-    for (uint32_t t = 0; t < c->n_tiles; ++t)
-        tile_map[t] += zr_tile_owner(t % c->tiles_x, t / c->tiles_x, c->cfg.tile_world) * c->slots_per_rank;
-    ok &= dev_alloc(&c->d_tile_map, tile_map.size()) == hipSuccess;
-    if (ok) ok &= hipMemcpy(c->d_tile_map, tile_map.data(), tile_map.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-    for (uint32_t t = 0; t < c->sn_tiles; ++t) sowned[t] = t;
-    c->n_owned = (uint32_t)owned.size();
-    ok &= dev_alloc(&c->d_owned, owned.size()) == hipSuccess;
-    ok &= dev_alloc(&c->d_sowned, sowned.size()) == hipSuccess;
-    ok &= dev_alloc(&c->d_tiles, (size_t)c->slots_per_rank * ZR_TILE * ZR_TILE) == hipSuccess;
-    if (ok && !owned.empty()) ok &= hipMemcpy(c->d_owned, owned.data(), owned.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok) ok &= hipMemcpy(c->d_sowned, sowned.data(), sowned.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok) ok &= hipMemset(c->d_tiles, 0, (size_t)c->slots_per_rank * ZR_TILE * ZR_TILE * 4) == hipSuccess;
-    const uint32_t mt = (c->n_tiles > c->sn_tiles ? c->n_tiles : c->sn_tiles) * ZR_TSTRIDE + 1;     // (the bins use the first sn_tiles + 1 words)
-    ok &= dev_alloc(&c->sb.tile_count, mt) == hipSuccess;
-    ok &= dev_alloc(&c->sb.tile_offset, mt) == hipSuccess;
-    ok &= dev_alloc(&c->sb.tile_cursor, mt) == hipSuccess;
-    ok &= dev_alloc(&c->sb.chunk_offset, mt) == hipSuccess;
-    if (ok) ok &= hipMemset(c->sb.tile_count, 0, mt * 4) == hipSuccess;       // k_bin_count counts into zeroes (k_scan zeroes the counts
-    if (ok) ok &= hipMemset(c->sb.tile_cursor, 0, mt * 4) == hipSuccess;      // and the cursors again for the fill and the next frame)
-    {   // the clear values of ZE:3427-3433, as resolve_pixel writes them for an empty pixel
-        ok &= dev_alloc(&c->d_clear_px, 64) == hipSuccess;
-        uint32_t px[16] = { 0 };
-        px[0] = 0x3F800000u;                    // depth 1.0
-        px[1] = 0xFF000000u; px[2] = 0u; px[3] = 0xFF000000u; px[4] = 0xFF000000u;   // SceneColor, A, B, C
-        px[6] = 0u; px[7] = 0x3C000000u;        // D = (0, 0, 0, 1) as fp16
-        px[8] = 0u;                             // overlay
-        if (ok) ok &= hipMemcpy(c->d_clear_px, px, sizeof px, hipMemcpyHostToDevice) == hipSuccess;
-        uint32_t* w = (uint32_t*)c->d_clear_px;
-        c->Gclear.depth = (float*)w; c->Gclear.scene_color = w + 1; c->Gclear.gA = w + 2; c->Gclear.gB = w + 3; c->Gclear.gC = w + 4;
-        c->Gclear.gD = (uint2*)(w + 6); c->Gclear.overlay = w + 8;
-    }
-    {   // environment switches, read once
-#ifdef ZR_DIAG       // work-skipping / printing switches: diagnostic builds only (zeldaengine_amd.build.build(extra_flags=["-DZR_DIAG"]))
-        const char* e;
-        if ((e = getenv("ZR_DEBUG_SKIP"))) c->env_skip = (uint32_t)atoi(e);                 // 1: no pixel walk, 2: no triangle phase
-        if ((e = getenv("ZR_DEBUG_SKIP_LIGHT"))) c->env_skip_light = (uint32_t)atoi(e);     // bits: 1 PCF, 2 lights, 4 reflection
-        if ((e = getenv("ZR_LIGHT_LIST_MIN"))) c->env_light_list_min = atoi(e);
-        c->env_no_empty_px = getenv("ZR_NO_EMPTY_PIXEL") != nullptr;
-#endif
-    }
-    ok &= hipHostMalloc((void**)&c->h_view_ring, sizeof(XkView) * zr_ctx::VIEW_RING, hipHostMallocDefault) == hipSuccess;
-    for (auto& e : c->view_ev) ok &= hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
-    {   // The camera lane must not share a hardware queue with the host's stream (HIP multiplexes streams onto a few of them and
-        // two streams on one queue run strictly one after the other).  Streams of different priority come from different queue
-        // pools.  Which priority: the frame's period is the HOST's lane (lighting -> shadow pipeline), and since the camera lane lost its
-        // two scans and two index passes per frame (round 6: tile buckets) it no longer fills the period - at the highest priority it
-        // took from the host lane what it saved itself (5 300 Mpixel/s), at the lowest the host lane keeps its share (5 540; normal: 5 470).
-        int least = 0, greatest = 0;
-        (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-        ok &= hipStreamCreateWithPriority(&c->cam_s, hipStreamNonBlocking, least) == hipSuccess;
-    }
-    ok &= hipEventCreateWithFlags(&c->ev_cam, hipEventDisableTiming) == hipSuccess;
-    ok &= hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) == hipSuccess;
-    ok &= dev_alloc(&c->d_vis, n) == hipSuccess;
-    if (ok) { zr_launch_fill64(c->d_vis, (unsigned long long)0x3F800000u << 32 | ZR_EMPTY_PRIM, n, c->stream); ok &= hipStreamSynchronize(c->stream) == hipSuccess; }
-    { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) c->raster_blocks = (uint32_t)prop.multiProcessorCount * 12u; }      // k_tile's persistent grid (6 workgroups fit a CU: two rounds of them; A/B 4 / 6 / 8 / 12 / 16 / 32 per CU -> 5 133 / 5 250 / 5 294 / 5 344 / 5 327 / 5 277 Mpixel/s)
-    c->shadow_blocks = c->raster_blocks / 12u * 8u;      // the shadow rasteriser's persistent grid stays at 8 per CU
-    c->slow0_cap = std::max<uint32_t>(c->slow0_cap, 128u * c->sn_tiles);      // (a clipped triangle is listed once per tile of its meshlet)
-    if (ok) ok &= dev_alloc(&c->d_slow0, 4ull * c->slow0_cap) == hipSuccess;
-#ifdef ZR_DIAG
-    if (const char* e = getenv("ZR_RASTER_BLOCKS")) c->raster_blocks = (uint32_t)std::max(1, atoi(e));
-    if (const char* e = getenv("ZR_SHADOW_BLOCKS")) c->shadow_blocks = (uint32_t)std::max(1, atoi(e));
-#endif
-    {   // Hi-Z pyramid: level l = max depth per (8 << l)^2 pixel block
-        size_t tot = 0;
-        for (int l = 0; l < 4; ++l) { c->hiz.hw[l] = (c->W + (8u << l) - 1) / (8u << l); c->hiz.hh[l] = (c->H + (8u << l) - 1) / (8u << l); tot += (size_t)c->hiz.hw[l] * c->hiz.hh[l]; }
-        c->hiz.fw = (c->W + 3u) / 4u; c->hiz.fh = (c->H + 3u) / 4u;
-        tot += (size_t)c->hiz.fw * c->hiz.fh;
-        ok &= dev_alloc(&c->d_hiz, tot) == hipSuccess;
-        if (ok) ok &= hipMemset(c->d_hiz, 0, tot * sizeof(float)) == hipSuccess;      // texels over other ranks' regions stay 0 ("hidden")
-        static_assert(ZR_TILE == 32 && ZR_SUPERTILE_SHIFT >= 1, "a 64 x 64 region of the pyramid must lie inside one super-tile");
-        std::vector<uint32_t> regions;
-        for (uint32_t ry = 0; ry < (c->H + 63u) / 64u; ++ry)
-            for (uint32_t rx = 0; rx < (c->W + 63u) / 64u; ++rx)
-                if (zr_tile_owner(rx * 2u, ry * 2u, c->cfg.tile_world) == c->cfg.tile_rank) regions.push_back(rx | ry << 16);
-        c->n_hiz_regions = (uint32_t)regions.size();
-        ok &= dev_alloc(&c->d_hiz_regions, regions.size()) == hipSuccess;
-        if (ok && !regions.empty()) ok &= hipMemcpy(c->d_hiz_regions, regions.data(), regions.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-        float* p = c->d_hiz;
-        for (int l = 0; l < 4; ++l) { c->hiz.lvl[l] = p; p += (size_t)c->hiz.hw[l] * c->hiz.hh[l]; }
-        c->hiz.fine = p;
-    }
-    if (ok) {
-        // The runtime backs an event with a signal on its FIRST record and grows that pool in batches, which blocks the host for
-        // milliseconds at unpredictable frames of a short run: record every event once now.
-        for (auto& fr : c->evr) for (auto& e : fr) ok &= hipEventRecord(e, c->stream) == hipSuccess;
-        for (auto& e : c->ev_end) ok &= hipEventRecord(e, c->stream) == hipSuccess;
-        for (auto& e : c->view_ev) ok &= hipEventRecord(e, c->stream) == hipSuccess;
-        // hipMemset of device memory is ordered on the NULL stream and need not be complete when it returns; the library's streams are
-        // non-blocking ones (no implicit ordering with the null stream): nothing may be enqueued on them before the fills above are through
-        ok &= hipDeviceSynchronize() == hipSuccess;
-        ok &= hipStreamSynchronize(c->stream) == hipSuccess;
-    }
-    if (!ok) { zr_destroy(c); return ZR_ERR_DEVICE; }
-    if (zr_set_cubemap(c, nullptr, 0) != ZR_OK) { zr_destroy(c); return ZR_ERR_DEVICE; }
+    int rc = zr_guard(c, [&]() { return create_device_state(c); });
+    if (rc == ZR_OK && zr_set_cubemap(c, nullptr, 0) != ZR_OK) rc = ZR_ERR_DEVICE;
+    if (rc != ZR_OK) { zr_destroy(c); return rc; }
     *out = c;
     return ZR_OK;
-}
-
-static void free_mesh_buffers(ZrMesh& m)
-{
-    dev_free(m.d_v); dev_free(m.d_rv); dev_free(m.d_rt); dev_free(m.d_idx); dev_free(m.d_meshlets); dev_free(m.d_mpos); dev_free(m.d_mbox); dev_free(m.d_mtri); dev_free(m.d_tri_meshlet);
-    m.uploaded = false;
-}
-
-static void free_tri_bins(zr_ctx* c)
-{
-    dev_free(c->tb.sel); dev_free(c->tb.recA); dev_free(c->tb.recB); dev_free(c->tb.tile_base); dev_free(c->tb.tile_cap); dev_free(c->tb.cursor);
-    dev_free(c->tb.over_tile); dev_free(c->tb.plan); dev_free(c->tb.over_cursor); dev_free(c->tb.unit_tab); dev_free(c->tb.n_units);
-    dev_free(c->tb.slow); dev_free(c->tb.wave_culled);
-    c->plan_valid = false;
-}
-
-static void free_scene(zr_ctx* c)
-{
-    for (auto& o : c->objects) zr_object_free_device(o);
-    c->objects.clear(); c->scene_gen++;
-    for (auto& m : c->meshes) {
-        dev_free(m.d_v); dev_free(m.d_rv); dev_free(m.d_rt); dev_free(m.d_idx); dev_free(m.d_meshlets); dev_free(m.d_mpos); dev_free(m.d_mbox); dev_free(m.d_mtri); dev_free(m.d_tri_meshlet);
-    }
-    c->meshes.clear();
-    c->profabs.clear();
-    dev_free(c->d_objs_b[0]); dev_free(c->d_objs_b[1]); c->d_objs = nullptr; c->inst_dual = false;
-    c->n_objs = 0; c->n_work = 0; c->scene_dirty = true;
 }
 
 extern "C" void zr_destroy(zr_ctx* c)
@@ -285,37 +237,7 @@ extern "C" void zr_destroy(zr_ctx* c)
     (void)hipSetDevice(c->device);
     (void)zr_sync_all(c);                      // including a geometry stage whose lighting pass never came
     zr_dist_destroy(c);
-    free_scene(c);
-    zr_instances_destroy(c);
-    free_mesh_buffers(c->sky_mesh); dev_free(c->sky_obj.d_inst); for (auto& t : c->sky_obj.d_tex) dev_free(t); dev_free(c->d_bg);
-    for (auto p : c->d_cube) if (p) (void)hipFree(p);
-    for (int b = 0; b < 2; ++b) {
-        GBufferPtrs& G = c->Gb[b];
-        dev_free(G.depth); dev_free(G.scene_color); dev_free(G.gA); dev_free(G.gB); dev_free(G.gC); dev_free(G.gD); dev_free(G.overlay);
-        dev_free(c->d_shadow_b[b]); dev_free(c->d_view_b[b]); dev_free(c->d_empty_b[b]); dev_free(c->d_prim_b[b]);
-    }
-    dev_free(c->d_color); dev_free(c->d_stats); dev_free(c->d_sstats); dev_free(c->d_lut); dev_free(c->d_unorm_lut); dev_free(c->d_sky_keys);
-    dev_free(c->d_owned); dev_free(c->d_sowned); dev_free(c->d_tiles); dev_free(c->d_tile_map); dev_free(c->d_sowned_rank); dev_free(c->d_stile_map);
-    for (auto& sc : c->sc) { dev_free(sc.rects); dev_free(sc.work); }
-    dev_free(c->sb.tile_count); dev_free(c->sb.tile_offset); dev_free(c->sb.tile_cursor); dev_free(c->sb.chunk_offset);
-    dev_free(c->sb.bins); dev_free(c->sb.chunk_tab);
-    dev_free(c->d_clear_px);
-    if (c->h_view_ring) (void)hipHostFree(c->h_view_ring);
-    for (auto& e : c->view_ev) if (e) (void)hipEventDestroy(e);
-    if (c->cam_s) (void)hipStreamDestroy(c->cam_s);
-    if (c->ev_cam) (void)hipEventDestroy(c->ev_cam);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    dev_free(c->d_vis); dev_free(c->d_slow0);
-    dev_free(c->d_pxrect); dev_free(c->d_zmin); dev_free(c->d_visflag[0]); dev_free(c->d_visflag[1]); dev_free(c->d_hiz); dev_free(c->d_hiz_regions);
-    dev_free(c->d_spxrect); dev_free(c->d_szmin); dev_free(c->d_sflag);
-    free_tri_bins(c);
-    for (auto& fr : c->evr) for (auto& e : fr) if (e) (void)hipEventDestroy(e);
-    for (auto& e : c->ev_end) if (e) (void)hipEventDestroy(e);
-    for (auto& e : c->ev_ids) if (e) (void)hipEventDestroy(e);
-    dev_free(c->d_ids_draws); dev_free(c->d_ids_counts); dev_free(c->d_ids_cov); dev_free(c->d_ids_list); dev_free(c->d_ids_n);
-    dev_free(c->d_ids_keys); dev_free(c->d_ids_hits); dev_free(c->d_ids_obj);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;                                  // every owner releases what it made; the context's own (streams last) after the others
 }
 
 extern "C" const char* zr_last_error(const zr_ctx* c) { return c ? c->err.c_str() : "no context (no usable HIP device?)"; }
@@ -569,16 +491,15 @@ int zr_object_add_internal(zr_ctx* c, uint32_t mesh_id, const ZrMaterialHost& ma
     memcpy(o.texel, mat.texel, sizeof o.texel); memcpy(o.bc_linear, mat.bc_linear, sizeof o.bc_linear);
     if (n_inst) o.inst.assign(inst, inst + n_inst);
     HIPCHK(c, hipSetDevice(c->device));
-    auto cleanup = [&]() { zr_object_free_device(o); };
-    std::vector<uint8_t> chains[7];
+    std::vector<uint8_t> chains[7];         // (a failure below drops `o`, and with it what it has made)
     int lead = -1;                                          // first slot that holds an image
     for (int t = 0; t < 7; ++t) {
         if (mat.image[t].empty()) continue;
         std::vector<uint8_t>& chain = chains[t]; uint32_t levels = 1;
         build_mip_chain(c, mat.image[t], mat.w[t], mat.h[t], t == 0, &chain, &levels);
-        hipError_t e = dev_alloc_image(&o.d_tex[t], chain.size());
+        hipError_t e = o.mem.alloc_image(&o.d_tex[t], chain.size());
         if (e == hipSuccess) e = hipMemcpy(o.d_tex[t], chain.data(), chain.size(), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { cleanup(); return zr_fail(c, ZR_ERR_DEVICE, hipGetErrorString(e)); }
+        if (e != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, hipGetErrorString(e));
         o.tex_w[t] = mat.w[t]; o.tex_h[t] = mat.h[t]; o.tex_levels[t] = levels;
         if (lead < 0) lead = t;
         else if (mat.w[t] != mat.w[lead] || mat.h[t] != mat.h[lead]) o.mixed_sizes = true;
@@ -596,22 +517,20 @@ int zr_object_add_internal(zr_ctx* c, uint32_t mesh_id, const ZrMaterialHost& ma
                 for (int ch = 0; ch < k.n; ++ch)
                     pk[i * 16 + (size_t)k.ch + (size_t)ch] = image ? src[i * 4 + (size_t)ch] : (uint8_t)(mat.texel[k.slot] >> (8 * ch));
         }
-        hipError_t e = dev_alloc_image(&o.d_tex[7], pk.size());
+        hipError_t e = o.mem.alloc_image(&o.d_tex[7], pk.size());
         if (e == hipSuccess) e = hipMemcpy(o.d_tex[7], pk.data(), pk.size(), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { cleanup(); return zr_fail(c, ZR_ERR_DEVICE, hipGetErrorString(e)); }
+        if (e != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, hipGetErrorString(e));
         o.tex_w[7] = mat.w[lead]; o.tex_h[7] = mat.h[lead]; o.tex_levels[7] = o.tex_levels[lead];
     }
-    { hipError_t e = dev_alloc(&o.d_inst, o.n_inst); if (e != hipSuccess) { cleanup(); return zr_fail(c, ZR_ERR_DEVICE, hipGetErrorString(e)); } }
-    XkInstanceData* d_raw = nullptr;
-    if (n_inst) {
-        hipError_t e = dev_alloc(&d_raw, n_inst);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_raw, inst, sizeof(XkInstanceData) * n_inst, hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) { dev_free(d_raw); cleanup(); return zr_fail(c, ZR_ERR_DEVICE, hipGetErrorString(e)); }
+    { hipError_t e = o.mem.alloc(&o.d_inst, o.n_inst); if (e != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, hipGetErrorString(e)); }
+    if (n_inst) {                       // (kept: the authoritative values of zr_object_set_instances / zr_object_update_instances_async)
+        hipError_t e = o.mem.alloc(&o.d_raw, n_inst);
+        if (e == hipSuccess) e = hipMemcpyAsync(o.d_raw, inst, sizeof(XkInstanceData) * n_inst, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, hipGetErrorString(e));
     }
-    zr_launch_instance_prep(d_raw, o.d_inst, o.n_inst, o.instanced ? 1u : 0u, c->stream);
+    zr_launch_instance_prep(o.d_raw, o.d_inst, o.n_inst, o.instanced ? 1u : 0u, c->stream);
     hipError_t e = zr_sync_all(c);
-    o.d_raw = d_raw;                    // (kept: the authoritative values of zr_object_set_instances / zr_object_update_instances_async)
-    if (e != hipSuccess) { cleanup(); return zr_fail(c, ZR_ERR_DEVICE, hipGetErrorString(e)); }
+    if (e != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, hipGetErrorString(e));
     c->objects.push_back(std::move(o));
     c->scene_dirty = true; c->scene_gen++;
     return ZR_OK;
@@ -632,10 +551,13 @@ extern "C" int zr_object_add(zr_ctx* c, uint32_t mesh_id, const zr_material* mat
 }
 
 // Capacities of the triangle-record arrays (chunks of 256 records) and of the clipped-triangle list, for hosts that size them themselves
-// (0 = the default: 16 records per meshlet-instance, at least 32 Mi; 2^18 triangles).  Takes effect at the next frame.
+// (0 = the default: 16 records per meshlet-instance, at least 32 Mi; 2^18 triangles).  Takes effect at the next frame.  The arrays hold at
+// most 2^30 - 1 records (the kernels index them with 32-bit words): record_chunks beyond ZR_MAX_RECORD_CHUNKS is refused.
+static constexpr uint32_t ZR_MAX_RECORD_CHUNKS = 0x3FFFFFFFu / 256u;
 extern "C" int zr_set_limits(zr_ctx* c, uint32_t record_chunks, uint32_t slow_triangles)
 {
     if (!c) return ZR_ERR_ARG;
+    if (record_chunks > ZR_MAX_RECORD_CHUNKS) return zr_fail(c, ZR_ERR_ARG, "zr_set_limits: record_chunks above (2^30 - 1) / 256");
     c->limit_record_chunks = record_chunks; c->limit_slow_triangles = slow_triangles;
     c->work_capacity = 0; c->scene_dirty = true;          // the pools are re-made by the next frame
     return ZR_OK;
@@ -648,6 +570,16 @@ extern "C" int zr_set_bucket_share(zr_ctx* c, uint32_t percent)
     return ZR_OK;
 }
 
+// (every object and mesh releases its device memory as it goes)
+static void free_scene(zr_ctx* c)
+{
+    c->objects.clear(); c->scene_gen++;
+    c->meshes.clear();
+    c->profabs.clear();
+    c->tables.release(); c->d_objs_b[0] = c->d_objs_b[1] = c->d_objs = nullptr; c->inst_dual = false;
+    c->n_objs = 0; c->n_work = 0; c->scene_dirty = true;
+}
+
 extern "C" int zr_scene_clear(zr_ctx* c)
 {
     if (!c) return ZR_ERR_ARG;
@@ -657,9 +589,9 @@ extern "C" int zr_scene_clear(zr_ctx* c)
     return ZR_OK;
 }
 
-template <typename T> static hipError_t upload(T** d, const std::vector<T>& h)
+template <typename T> static hipError_t upload(ZrOwn& own, T** d, const std::vector<T>& h)
 {
-    hipError_t e = dev_alloc(d, h.size());
+    hipError_t e = own.alloc(d, h.size());
     if (e != hipSuccess) return e;
     return h.empty() ? hipSuccess : hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
 }
@@ -667,6 +599,7 @@ template <typename T> static hipError_t upload(T** d, const std::vector<T>& h)
 static int upload_mesh(zr_ctx* c, ZrMesh& m)
 {
     if (m.uploaded) return ZR_OK;
+    m.mem.release();                    // (what an upload that failed part-way made)
     if (!m.has_meshlets) {
         zr_build_meshlets(m.v.data(), (uint32_t)m.v.size(), m.idx.data(), (uint32_t)m.idx.size(), 64, 124, 0.2f, &m.ms);
         m.has_meshlets = true;
@@ -701,8 +634,8 @@ static int upload_mesh(zr_ctx* c, ZrMesh& m)
     // primitive id in one round trip instead of two (index, then vertex) - the kernel waits for its chain of dependent loads, not for arithmetic
     std::vector<ZrRVertex> rt(std::max<size_t>(1, m.idx.size()));
     for (size_t i = 0; i < m.idx.size(); ++i) rt[i] = rv[m.idx[i]];
-    HIPCHK(c, upload(&m.d_rt, rt));
-    HIPCHK(c, upload(&m.d_v, m.v)); HIPCHK(c, upload(&m.d_rv, rv)); HIPCHK(c, upload(&m.d_idx, m.idx)); HIPCHK(c, upload(&m.d_meshlets, m.ms.meshlets));
+    HIPCHK(c, upload(m.mem, &m.d_rt, rt));
+    HIPCHK(c, upload(m.mem, &m.d_v, m.v)); HIPCHK(c, upload(m.mem, &m.d_rv, rv)); HIPCHK(c, upload(m.mem, &m.d_idx, m.idx)); HIPCHK(c, upload(m.mem, &m.d_meshlets, m.ms.meshlets));
     // draw-order triangle -> meshlet (the resolve marks the meshlet-instances that own a pixel)
     std::vector<uint32_t> tri_meshlet(std::max<size_t>(1, m.idx.size() / 3), 0u);
     for (size_t mi = 0; mi < m.ms.meshlets.size(); ++mi) {
@@ -723,8 +656,57 @@ static int upload_mesh(zr_ctx* c, ZrMesh& m)
         }
         mbox[2 * mi] = make_float4(lo[0], lo[1], lo[2], 0.0f); mbox[2 * mi + 1] = make_float4(hi[0], hi[1], hi[2], 0.0f);
     }
-    HIPCHK(c, upload(&m.d_mpos, mpos)); HIPCHK(c, upload(&m.d_mbox, mbox)); HIPCHK(c, upload(&m.d_mtri, mtri)); HIPCHK(c, upload(&m.d_tri_meshlet, tri_meshlet));
+    HIPCHK(c, upload(m.mem, &m.d_mpos, mpos)); HIPCHK(c, upload(m.mem, &m.d_mbox, mbox)); HIPCHK(c, upload(m.mem, &m.d_mtri, mtri)); HIPCHK(c, upload(m.mem, &m.d_tri_meshlet, tri_meshlet));
     m.uploaded = true;
+    return ZR_OK;
+}
+
+// The work pools for cap_w meshlet-instances: the cull's lists, the shadow pass's bins, the camera pass's triangle records, the occlusion
+// tests' boxes and flags.  A failed allocation returns with work_capacity 0 (and the caller's scene_dirty still set): the next frame
+// tries again instead of launching on freed buffers.
+static int make_work_pools(zr_ctx* c, uint32_t cap_w)
+{
+    ZrOwn& P = c->pools;
+    P.release();
+    c->work_capacity = 0; c->plan_valid = false;
+    for (auto& sc : c->sc) sc = {};
+    c->sb.bins = nullptr; c->sb.chunk_tab = nullptr; c->tb = {};
+    c->d_pxrect = nullptr; c->d_zmin = nullptr; c->d_visflag[0] = c->d_visflag[1] = nullptr; c->d_spxrect = nullptr; c->d_szmin = nullptr; c->d_sflag = nullptr;
+    const uint64_t cap = std::max<uint64_t>(1u << 20, 8ull * cap_w);
+    c->bin_capacity = (uint32_t)std::min<uint64_t>(cap, 0x3FFFFFFFull);
+    c->chunk_capacity = c->bin_capacity / ZR_CHUNK + std::max(c->n_tiles, c->sn_tiles) + 1u;
+    for (auto& sc : c->sc) { HIPCHK(c, P.alloc(&sc.rects, cap_w)); HIPCHK(c, P.alloc(&sc.work, cap_w)); }
+    HIPCHK(c, P.alloc(&c->sb.bins, c->bin_capacity)); HIPCHK(c, P.alloc(&c->sb.chunk_tab, c->chunk_capacity));
+    // triangle-binned camera pass: triangle records (32 B) live in per-tile BUCKETS of two 16-byte planes, laid out every frame by
+    // k_plan from the previous frame's per-tile counts; what lies behind the last bucket is the frame's overflow region (what a tile gets
+    // beyond its bucket).  Sized from the scene: 16 records per meshlet-instance, at least 32 Mi - 1 GB of 288 reserved, touched as far as a frame
+    // needs.  Planes that run full are reported like a bin overflow (zr_set_limits sizes them: 256 records per "chunk", at most 2^30 - 1 records).
+    ZrTriBins& T = c->tb;
+    T.n_waves = 8192; T.slow_cap = 1u << 18;
+    // (16 per meshlet-instance: the frame after a camera cut at config 4 puts ~ 60 M records - 5 per meshlet-instance - into the 64
+    // sections of the overflow region, unevenly; with 8 the fullest section ran over.  6 GB of 288 at 1 M instances.)
+    uint64_t n_rec = std::min<uint64_t>(std::max<uint64_t>(32ull << 20, 16ull * cap_w), 0x3FFFFFFFull);
+    if (c->limit_record_chunks) n_rec = 256ull * c->limit_record_chunks;      // zr_set_limits (a host sizing the planes; the overflow tests)
+    if (c->limit_slow_triangles) T.slow_cap = std::max(2u, c->limit_slow_triangles);
+    T.n_rec = (uint32_t)n_rec; T.bucket_max = (uint32_t)(n_rec - n_rec / 8u);
+    T.n_tiles = c->n_tiles;
+    T.unit_cap = T.bucket_max / (ZR_TCHUNK * ZR_TBATCHES) + 2u * c->n_tiles + 1u;
+    HIPCHK(c, P.alloc(&T.sel, cap_w)); HIPCHK(c, P.alloc(&T.recA, (size_t)n_rec)); HIPCHK(c, P.alloc(&T.recB, (size_t)n_rec));
+    HIPCHK(c, P.alloc(&T.over_tile, (size_t)n_rec)); HIPCHK(c, P.alloc(&T.plan, 2));
+    HIPCHK(c, P.alloc(&T.tile_base, c->n_tiles)); HIPCHK(c, P.alloc(&T.tile_cap, c->n_tiles));
+    HIPCHK(c, P.alloc(&T.cursor, (size_t)2 * c->n_tiles * ZR_TSTRIDE));
+    HIPCHK(c, P.alloc(&T.over_cursor, 2 * ZR_OVER_SECTIONS)); HIPCHK(c, P.alloc(&T.n_units, 1));
+    HIPCHK(c, P.alloc(&T.unit_tab, T.unit_cap)); HIPCHK(c, P.alloc(&T.wave_culled, T.n_waves)); HIPCHK(c, P.alloc(&T.slow, 4ull * T.slow_cap));
+    HIPCHK(c, P.alloc(&c->d_pxrect, cap_w)); HIPCHK(c, P.alloc(&c->d_zmin, cap_w));
+    HIPCHK(c, P.alloc(&c->d_visflag[0], cap_w)); HIPCHK(c, P.alloc(&c->d_visflag[1], cap_w));
+    HIPCHK(c, P.alloc(&c->d_spxrect, cap_w)); HIPCHK(c, P.alloc(&c->d_szmin, cap_w)); HIPCHK(c, P.alloc(&c->d_sflag, cap_w));
+    // (no plan yet: every bucket is empty - the first frame counts before it draws, see gbuffer_pass.  A fill that landed after the next
+    // frame's k_plan would wipe the plan - every record then overflows into sections of capacity 0)
+    HIPCHK(c, zr_fill_sync({ { T.tile_base, 0, (size_t)c->n_tiles * 4 }, { T.tile_cap, 0, (size_t)c->n_tiles * 4 },
+                             { T.cursor, 0, (size_t)2 * c->n_tiles * ZR_TSTRIDE * 4 }, { T.over_cursor, 0, 2 * ZR_OVER_SECTIONS * 4 },
+                             { T.n_units, 0, 4 }, { T.plan, 0, 8 },
+                             { c->d_visflag[0], 0, cap_w }, { c->d_visflag[1], 0, cap_w } }));      // (no frame's stamp is 0)
+    c->work_capacity = cap_w;              // every buffer is there
     return ZR_OK;
 }
 
@@ -774,68 +756,14 @@ static int finalize_scene(zr_ctx* c)
     const uint64_t scene_work = work, scene_inst = inst_total;
     if (sky) emit(c->sky_obj, c->sky_mesh, ZR_OBJ_SKY);
     if (work >= 0xFFFFFFFFull || prim >= 0xFFFFFFFFull) return zr_fail(c, ZR_ERR_OVERFLOW, "scene exceeds 2^32 meshlet-instances or primitives");
-    dev_free(c->d_objs_b[0]);
-    HIPCHK(c, upload(&c->d_objs_b[0], tab));
+    c->tables.release(); c->d_objs_b[0] = c->d_objs_b[1] = c->d_objs = nullptr; c->inst_dual = false;     // (zr_instances_table: table 1)
+    HIPCHK(c, upload(c->tables, &c->d_objs_b[0], tab));
     c->d_objs = c->d_objs_b[0];
     c->n_objs = (uint32_t)tab.size(); c->n_work = (uint32_t)scene_work; c->n_inst_total = (uint32_t)scene_inst;
     { int rc = zr_instances_table(c); if (rc) return rc; }      // (objects with updated instances: the parity-1 table, n_objs records)
     c->sky_object = sky ? (uint32_t)tab.size() - 1u : 0u;
-    if (sky && !c->d_sky_keys) HIPCHK(c, dev_alloc(&c->d_sky_keys, (size_t)c->W * c->H));
-    if (c->n_work > c->work_capacity) {
-        for (auto& sc : c->sc) { dev_free(sc.rects); dev_free(sc.work); }
-        dev_free(c->sb.bins); dev_free(c->sb.chunk_tab);
-        dev_free(c->d_pxrect); dev_free(c->d_zmin); dev_free(c->d_visflag[0]); dev_free(c->d_visflag[1]);
-        dev_free(c->d_spxrect); dev_free(c->d_szmin); dev_free(c->d_sflag);
-        // (a failed allocation below returns with scene_dirty still set and work_capacity 0: the next frame tries again instead of
-        // launching on freed buffers)
-        const uint32_t cap_w = c->n_work;
-        c->work_capacity = 0;
-        const uint64_t cap = std::max<uint64_t>(1u << 20, 8ull * c->n_work);
-        c->bin_capacity = (uint32_t)std::min<uint64_t>(cap, 0x3FFFFFFFull);
-        c->chunk_capacity = c->bin_capacity / ZR_CHUNK + std::max(c->n_tiles, c->sn_tiles) + 1u;
-        for (auto& sc : c->sc) {
-            HIPCHK(c, dev_alloc(&sc.rects, cap_w));
-            HIPCHK(c, dev_alloc(&sc.work, cap_w));
-        }
-        HIPCHK(c, dev_alloc(&c->sb.bins, c->bin_capacity));
-        HIPCHK(c, dev_alloc(&c->sb.chunk_tab, c->chunk_capacity));
-        // triangle-binned camera pass: triangle records (32 B) live in per-tile BUCKETS of two 16-byte planes, laid out every frame by
-        // k_plan from the previous frame's per-tile counts; what lies behind the last bucket is the frame's overflow region (what a tile gets
-        // beyond its bucket).  Sized from the scene: 16 records per meshlet-instance, at least 32 Mi - 1 GB of 288 reserved, touched as far as a frame
-        // needs.  Planes that run full are reported like a bin overflow (zr_set_limits sizes them: 256 records per "chunk").
-        free_tri_bins(c);
-        c->tb.n_waves = 8192; c->tb.slow_cap = 1u << 18;
-        // (16 per meshlet-instance: the frame after a camera cut at config 4 puts ~ 60 M records - 5 per meshlet-instance - into the 64
-        // sections of the overflow region, unevenly; with 8 the fullest section ran over.  6 GB of 288 at 1 M instances.)
-        uint64_t n_rec = std::min<uint64_t>(std::max<uint64_t>(32ull << 20, 16ull * c->n_work), 0x3FFFFFFFull);
-        if (c->limit_record_chunks) n_rec = 256ull * c->limit_record_chunks;      // zr_set_limits (a host sizing the planes; the overflow tests)
-        if (c->limit_slow_triangles) c->tb.slow_cap = std::max(2u, c->limit_slow_triangles);
-        c->tb.n_rec = (uint32_t)n_rec; c->tb.bucket_max = (uint32_t)(n_rec - n_rec / 8u);
-        c->tb.n_tiles = c->n_tiles;
-        c->tb.unit_cap = c->tb.bucket_max / (ZR_TCHUNK * ZR_TBATCHES) + 2u * c->n_tiles + 1u;
-        HIPCHK(c, dev_alloc(&c->tb.sel, cap_w));
-        HIPCHK(c, dev_alloc(&c->tb.recA, (size_t)n_rec));
-        HIPCHK(c, dev_alloc(&c->tb.recB, (size_t)n_rec));
-        HIPCHK(c, dev_alloc(&c->tb.over_tile, (size_t)n_rec)); HIPCHK(c, dev_alloc(&c->tb.plan, 2));
-        HIPCHK(c, dev_alloc(&c->tb.tile_base, c->n_tiles)); HIPCHK(c, dev_alloc(&c->tb.tile_cap, c->n_tiles));
-        HIPCHK(c, dev_alloc(&c->tb.cursor, (size_t)2 * c->n_tiles * ZR_TSTRIDE));
-        HIPCHK(c, dev_alloc(&c->tb.over_cursor, 2 * ZR_OVER_SECTIONS)); HIPCHK(c, dev_alloc(&c->tb.n_units, 1));
-        HIPCHK(c, dev_alloc(&c->tb.unit_tab, c->tb.unit_cap));
-        // (no plan yet: every bucket is empty - the first frame counts before it draws, see gbuffer_pass)
-        HIPCHK(c, hipMemset(c->tb.tile_base, 0, (size_t)c->n_tiles * 4)); HIPCHK(c, hipMemset(c->tb.tile_cap, 0, (size_t)c->n_tiles * 4));
-        HIPCHK(c, hipMemset(c->tb.cursor, 0, (size_t)2 * c->n_tiles * ZR_TSTRIDE * 4));
-        HIPCHK(c, hipMemset(c->tb.over_cursor, 0, 2 * ZR_OVER_SECTIONS * 4)); HIPCHK(c, hipMemset(c->tb.n_units, 0, 4)); HIPCHK(c, hipMemset(c->tb.plan, 0, 8));
-        HIPCHK(c, dev_alloc(&c->tb.wave_culled, c->tb.n_waves));
-        HIPCHK(c, dev_alloc(&c->tb.slow, 4ull * c->tb.slow_cap));
-        HIPCHK(c, dev_alloc(&c->d_pxrect, cap_w)); HIPCHK(c, dev_alloc(&c->d_zmin, cap_w));
-        HIPCHK(c, dev_alloc(&c->d_visflag[0], cap_w)); HIPCHK(c, dev_alloc(&c->d_visflag[1], cap_w));
-        HIPCHK(c, hipMemset(c->d_visflag[0], 0, cap_w)); HIPCHK(c, hipMemset(c->d_visflag[1], 0, cap_w));      // (no frame's stamp is 0)
-        HIPCHK(c, dev_alloc(&c->d_spxrect, cap_w)); HIPCHK(c, dev_alloc(&c->d_szmin, cap_w)); HIPCHK(c, dev_alloc(&c->d_sflag, cap_w));
-        // (the fills above sit on the null stream; the frame that follows runs on non-blocking streams: a fill that landed after that
-        // frame's k_plan would wipe the plan - every record then overflows into sections of capacity 0)
-        HIPCHK(c, hipDeviceSynchronize());
-        c->work_capacity = cap_w;              // every buffer is there
-    }
+    if (sky && !c->d_sky_keys) HIPCHK(c, c->own.alloc(&c->d_sky_keys, (size_t)c->W * c->H));
+    if (c->n_work > c->work_capacity) { int rc = make_work_pools(c, c->n_work); if (rc) return rc; }
     c->any_images = c->mixed_images = false;
     for (const ZrObject& d : tab) for (int t = 0; t < 7; ++t) if (d.tex[t].data) c->any_images = true;
     for (const auto& o : c->objects) if (o.mixed_sizes) c->mixed_images = true;      // (the skydome's one image is sampled by itself)
@@ -850,12 +778,12 @@ static int finalize_scene(zr_ctx* c)
 
 // ------------------------------------------------------------------------------------------------ skydome + background
 
-static int upload_texture(zr_ctx* c, const zr_image* tex, bool srgb, uint8_t** d, uint32_t* w, uint32_t* h, uint32_t* levels)
+static int upload_texture(zr_ctx* c, ZrOwn& own, const zr_image* tex, bool srgb, uint8_t** d, uint32_t* w, uint32_t* h, uint32_t* levels)
 {
     if (tex->width == 0 || tex->height == 0 || tex->width > 16384 || tex->height > 16384) return zr_fail(c, ZR_ERR_ARG, "bad image size");
     std::vector<uint8_t> img(tex->rgba8, tex->rgba8 + (size_t)tex->width * tex->height * 4), chain;
     build_mip_chain(c, img, tex->width, tex->height, srgb, &chain, levels);
-    HIPCHK(c, dev_alloc_image(d, chain.size()));
+    HIPCHK(c, own.alloc_image(d, chain.size()));
     HIPCHK(c, hipMemcpy(*d, chain.data(), chain.size(), hipMemcpyHostToDevice));
     *w = tex->width; *h = tex->height;
     return ZR_OK;
@@ -866,9 +794,7 @@ static int zr_set_skydome_impl(zr_ctx* c, const XkVertex* v, uint32_t nv, const 
     if (!c) return ZR_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, zr_sync_all(c));
-    free_mesh_buffers(c->sky_mesh); c->sky_mesh = ZrMesh();
-    dev_free(c->sky_obj.d_inst); for (auto& t : c->sky_obj.d_tex) dev_free(t);
-    c->sky_obj = ZrSceneObject(); c->sky_set = false; c->scene_dirty = true;
+    c->sky_mesh = ZrMesh(); c->sky_obj = ZrSceneObject(); c->sky_set = false; c->scene_dirty = true;      // (releasing the old ones)
     if (!tex || !tex->rgba8) return ZR_OK;
     ARGCHK(c, v && idx && nv > 0 && ni > 0 && ni % 3 == 0);
     for (uint32_t i = 0; i < ni; ++i) if (idx[i] >= nv) return zr_fail(c, ZR_ERR_ARG, "index out of range");
@@ -877,9 +803,9 @@ static int zr_set_skydome_impl(zr_ctx* c, const XkVertex* v, uint32_t nv, const 
     o.mesh = 0; o.instanced = false; o.n_inst = 1;
     for (int t = 0; t < 7; ++t) o.texel[t] = 0xFFFFFFFFu;
     o.bc_linear[0] = o.bc_linear[1] = o.bc_linear[2] = 1.0f;
-    int rc = upload_texture(c, tex, true, &o.d_tex[0], &o.tex_w[0], &o.tex_h[0], &o.tex_levels[0]);   // sRGB by default, ZE:5860
+    int rc = upload_texture(c, o.mem, tex, true, &o.d_tex[0], &o.tex_w[0], &o.tex_h[0], &o.tex_levels[0]);   // sRGB by default, ZE:5860
     if (rc) return rc;
-    HIPCHK(c, dev_alloc(&o.d_inst, 1));
+    HIPCHK(c, o.mem.alloc(&o.d_inst, 1));
     zr_launch_instance_prep(nullptr, o.d_inst, 1, 0u, c->stream);
     HIPCHK(c, zr_sync_all(c));
     c->sky_set = true;
@@ -895,9 +821,9 @@ static int zr_set_background_impl(zr_ctx* c, const zr_image* tex)
     if (!c) return ZR_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, zr_sync_all(c));
-    dev_free(c->d_bg); c->bg_set = false;
+    c->bg_mem.release(); c->d_bg = nullptr; c->bg_set = false;
     if (!tex || !tex->rgba8) return ZR_OK;
-    int rc = upload_texture(c, tex, true, &c->d_bg, &c->bg_w, &c->bg_h, &c->bg_levels);
+    int rc = upload_texture(c, c->bg_mem, tex, true, &c->d_bg, &c->bg_w, &c->bg_h, &c->bg_levels);
     if (rc) return rc;
     c->bg_set = true;
     return ZR_OK;
@@ -926,8 +852,8 @@ static int zr_set_cubemap_impl(zr_ctx* c, const uint8_t* const faces[6], uint32_
     if (faces) for (int f = 0; f < 6; ++f) ARGCHK(c, faces[f] != nullptr);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, zr_sync_all(c));
-    for (auto p : c->d_cube) if (p) (void)hipFree(p);
-    c->d_cube.clear();
+    c->cube_mem.release();
+    memset(&c->cube, 0, sizeof c->cube);
     uint32_t levels = 1; for (uint32_t d = dim; d > 1; d >>= 1) levels++;      // floor(log2(dim)) + 1, ZE:6887
     if (levels > 16) return zr_fail(c, ZR_ERR_ARG, "cubemap too large");
     std::vector<std::vector<uint8_t>> lv(levels);
@@ -955,11 +881,10 @@ static int zr_set_cubemap_impl(zr_ctx* c, const uint8_t* const faces[6], uint32_
         }
         d = nd;
     }
-    memset(&c->cube, 0, sizeof c->cube);
     for (uint32_t l = 0; l < levels; ++l) {
         uint8_t* p = nullptr;
-        HIPCHK(c, upload(&p, lv[l]));
-        c->d_cube.push_back(p); c->cube.levels[l] = p;
+        HIPCHK(c, upload(c->cube_mem, &p, lv[l]));
+        c->cube.levels[l] = p;
     }
     c->cube_dim = dim; c->cube_levels = levels;
     c->view.LightsCount[3] = (int32_t)levels;       // CubemapMaxMips, ZE:4308
@@ -1082,9 +1007,8 @@ static int zr_set_shading_impl(zr_ctx* c, uint32_t mode)
     const size_t n = (size_t)c->W * c->H;
     for (int b = 0; b < 2; ++b) {
         if (mode == ZR_SHADING_FORWARD && !c->d_prim_b[b]) {
-            if (dev_alloc(&c->d_prim_b[b], n) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "zr_set_shading: out of device memory");
-            HIPCHK(c, hipMemset(c->d_prim_b[b], 0xFF, n * 4));
-            HIPCHK(c, hipDeviceSynchronize());      // (a null-stream fill; the frames run on non-blocking streams)
+            if (c->own.alloc(&c->d_prim_b[b], n) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "zr_set_shading: out of device memory");
+            HIPCHK(c, zr_fill_sync({ { c->d_prim_b[b], 0xFF, n * 4 } }));
         }
         c->Gb[b].prim = (mode == ZR_SHADING_FORWARD || c->id_capture) ? c->d_prim_b[b] : nullptr;      // (id capture: zr_set_id_capture)
     }
@@ -1255,19 +1179,19 @@ static int ids_prepare(zr_ctx* c)
         }
     tab.push_back({ prim, 1u, 0xFFFFFFFFu, slots });     // sentinel: the end of the last draw
     HIPCHK(c, zr_sync_all(c));                           // (queries of an earlier scene may still read the old table)
-    dev_free(c->d_ids_draws);
-    HIPCHK(c, upload(&c->d_ids_draws, tab));
+    c->ids_table.release(); c->d_ids_draws = nullptr;
+    HIPCHK(c, upload(c->ids_table, &c->d_ids_draws, tab));
     c->ids_n_draws = (uint32_t)tab.size() - 1u;
     c->ids_n_slots = slots;
     if (slots > c->ids_slot_cap || !c->d_ids_counts) {
-        dev_free(c->d_ids_counts); dev_free(c->d_ids_cov); dev_free(c->d_ids_list); dev_free(c->d_ids_n); dev_free(c->d_ids_keys); dev_free(c->d_ids_hits);
+        ZrOwn& P = c->ids_pool;
+        P.release(); c->d_ids_counts = c->d_ids_cov = c->d_ids_list = c->d_ids_n = nullptr; c->d_ids_keys = nullptr; c->d_ids_hits = nullptr;
         c->ids_slot_cap = 0;
         const size_t cap = std::max<uint32_t>(slots, 1u);
-        HIPCHK(c, dev_alloc(&c->d_ids_counts, cap)); HIPCHK(c, dev_alloc(&c->d_ids_cov, cap)); HIPCHK(c, dev_alloc(&c->d_ids_list, cap));
-        HIPCHK(c, dev_alloc(&c->d_ids_n, 1)); HIPCHK(c, dev_alloc(&c->d_ids_keys, cap)); HIPCHK(c, dev_alloc(&c->d_ids_hits, cap));
+        HIPCHK(c, P.alloc(&c->d_ids_counts, cap)); HIPCHK(c, P.alloc(&c->d_ids_cov, cap)); HIPCHK(c, P.alloc(&c->d_ids_list, cap));
+        HIPCHK(c, P.alloc(&c->d_ids_n, 1)); HIPCHK(c, P.alloc(&c->d_ids_keys, cap)); HIPCHK(c, P.alloc(&c->d_ids_hits, cap));
         // between queries: counts 0, keys all ones, no listed slot (k_id_hits restores this after every pick)
-        HIPCHK(c, hipMemset(c->d_ids_counts, 0, cap * 4)); HIPCHK(c, hipMemset(c->d_ids_keys, 0xFF, cap * 8)); HIPCHK(c, hipMemset(c->d_ids_n, 0, 4));
-        HIPCHK(c, hipDeviceSynchronize());      // (null-stream fills; the frames and queries run on non-blocking streams)
+        HIPCHK(c, zr_fill_sync({ { c->d_ids_counts, 0, cap * 4 }, { c->d_ids_keys, 0xFF, cap * 8 }, { c->d_ids_n, 0, 4 } }));
         c->ids_slot_cap = (uint32_t)cap;
     }
     c->ids_table_gen = c->scene_gen;
@@ -1621,7 +1545,7 @@ static int zr_set_shadow_tiles_impl(zr_ctx* c, uint32_t rank, uint32_t world)
     if (world > 1 && c->shadow_world > 1) return zr_fail(c, ZR_ERR_STATE, "zr_set_shadow_tiles: the casters are already split by instance (zr_set_shadow_partition)");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, zr_sync_all(c));
-    dev_free(c->d_sowned_rank); dev_free(c->d_stile_map);
+    c->stile_mem.release(); c->d_sowned_rank = c->d_stile_map = nullptr;
     c->stile_rank = 0; c->stile_world = 1; c->s_slots_per_rank = c->sn_tiles; c->n_sowned_rank = 0;
     c->list_valid[0] = false;
     if (world == 1) return ZR_OK;
@@ -1634,7 +1558,7 @@ static int zr_set_shadow_tiles_impl(zr_ctx* c, uint32_t rank, uint32_t world)
     uint32_t spr = 0;
     for (uint32_t n : counts) spr = std::max(spr, n);
     for (uint32_t t = 0; t < c->sn_tiles; ++t) map[t] += zr_tile_owner(t % c->stiles_x, t / c->stiles_x, world) * spr;
-    HIPCHK(c, upload(&c->d_sowned_rank, owned)); HIPCHK(c, upload(&c->d_stile_map, map));
+    HIPCHK(c, upload(c->stile_mem, &c->d_sowned_rank, owned)); HIPCHK(c, upload(c->stile_mem, &c->d_stile_map, map));
     c->stile_rank = rank; c->stile_world = world; c->s_slots_per_rank = spr; c->n_sowned_rank = (uint32_t)owned.size();
     return ZR_OK;
 }
@@ -1705,9 +1629,7 @@ extern "C" int zr_finish(zr_ctx* c)
         }
         c->h_stats.covered_shadow = 0;
         if (c->h_stats.overflow_sticky) {     // latched by ANY frame since the last zr_finish, not only the newest one
-            HIPCHK(c, hipMemset(&c->d_stats->overflow_sticky, 0, sizeof(uint32_t)));
-            HIPCHK(c, hipMemset(&c->d_sstats->overflow_sticky, 0, sizeof(uint32_t)));
-            HIPCHK(c, hipDeviceSynchronize());      // (null-stream fills: through before the next frame is enqueued on the library's streams)
+            HIPCHK(c, zr_fill_sync({ { &c->d_stats->overflow_sticky, 0, sizeof(uint32_t) }, { &c->d_sstats->overflow_sticky, 0, sizeof(uint32_t) } }));
             c->h_stats.overflow = 1u;
             static const char* const what[] = { "?", "shadow bin entries", "slow-triangle list (zr_set_limits)", "camera work-unit table", "triangle-record arrays (zr_set_limits)",
                                                 "late shadow bin entries" };
@@ -1899,9 +1821,8 @@ static int zr_set_id_capture_impl(zr_ctx* c, int enable)
     const size_t n = (size_t)c->W * c->H;
     for (int b = 0; b < 2; ++b) {
         if (on && !c->d_prim_b[b]) {             // the forward variant's planes, allocated as zr_set_shading does
-            if (dev_alloc(&c->d_prim_b[b], n) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "zr_set_id_capture: out of device memory");
-            HIPCHK(c, hipMemset(c->d_prim_b[b], 0xFF, n * 4));      // (pixels of other ranks' tiles stay "none")
-            HIPCHK(c, hipDeviceSynchronize());
+            if (c->own.alloc(&c->d_prim_b[b], n) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "zr_set_id_capture: out of device memory");
+            HIPCHK(c, zr_fill_sync({ { c->d_prim_b[b], 0xFF, n * 4 } }));      // (pixels of other ranks' tiles stay "none")
         }
         c->Gb[b].prim = (on || c->shading == ZR_SHADING_FORWARD) ? c->d_prim_b[b] : nullptr;
     }
@@ -1942,7 +1863,7 @@ extern "C" int zr_read_ids(zr_ctx* c, int kind, void* dst, size_t bytes)
     if (rc) return rc;
     const ZrIdsArgs A0 = ids_args(c, 0, 0, c->W, c->H);
     if (kind == ZR_IDS_PRIMITIVE) { HIPCHK(c, hipMemcpy(dst, A0.prim, bytes, hipMemcpyDeviceToHost)); return ZR_OK; }
-    if (!c->d_ids_obj) HIPCHK(c, dev_alloc(&c->d_ids_obj, (size_t)c->W * c->H));
+    if (!c->d_ids_obj) HIPCHK(c, c->own.alloc(&c->d_ids_obj, (size_t)c->W * c->H));
     ZrIdsArgs A = A0; A.obj_plane = c->d_ids_obj;
     zr_launch_id_census(A, ZR_IDS_OBJECTS, c->stream);
     HIPCHK(c, hipGetLastError());

@@ -17,9 +17,9 @@
 static int inst_init_ctx(zr_ctx* c)
 {
     if (c->ev_scatter) return ZR_OK;
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_apply, hipEventDisableTiming));
-    for (auto& r : c->inst_ring) HIPCHK(c, hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_scatter, hipEventDisableTiming));      // (last: it marks the set as made)
+    HIPCHK(c, c->own.event(&c->ev_apply, hipEventDisableTiming));
+    for (auto& r : c->inst_ring) HIPCHK(c, c->own.event(&r.ev, hipEventDisableTiming));
+    HIPCHK(c, c->own.event(&c->ev_scatter, hipEventDisableTiming));      // (last: it marks the set as made)
     return ZR_OK;
 }
 
@@ -30,12 +30,11 @@ static int inst_init_object(zr_ctx* c, ZrSceneObject& o, hipStream_t x)
     const size_t n = o.n_inst;
     ZrInstanceState S = {};
     S.raw = o.d_raw; S.plane[0] = o.d_inst; S.n_inst = o.n_inst;
-    hipError_t e = hipMalloc((void**)&S.plane[1], n * sizeof(ZrInstance));
-    if (e == hipSuccess) e = hipMalloc((void**)&S.dirty, (3 * n + 2) * sizeof(uint32_t));
-    if (e != hipSuccess) {
-        if (S.plane[1]) (void)hipFree(S.plane[1]);
-        return zr_fail(c, ZR_ERR_OOM, std::string("instance update state: ") + hipGetErrorString(e));
-    }
+    ZrOwn mem;                          // (the object's once both are made)
+    hipError_t e = mem.alloc(&S.plane[1], n);
+    if (e == hipSuccess) e = mem.alloc(&S.dirty, 3 * n + 2);
+    if (e != hipSuccess) return zr_fail(c, ZR_ERR_OOM, std::string("instance update state: ") + hipGetErrorString(e));
+    o.mem.adopt(std::move(mem));
     S.list[0] = S.dirty + n; S.list[1] = S.dirty + 2 * n; S.count = S.dirty + 3 * n;
     o.upd = S; o.pending[0] = o.pending[1] = 0; o.tab1 = false;
     HIPCHK(c, hipMemsetAsync(S.dirty, 0, n * sizeof(uint32_t), x));
@@ -45,7 +44,7 @@ static int inst_init_object(zr_ctx* c, ZrSceneObject& o, hipStream_t x)
     if (!c->inst_dual && !c->scene_dirty) {
         // the parity-1 draw table: table 0 as it stands (nothing writes it); the frame head points it at the parity-1 planes.  (A dirty
         // scene gets both tables from finalize_scene, before its next frame.)
-        HIPCHK(c, hipMalloc((void**)&c->d_objs_b[1], (size_t)c->n_objs * sizeof(ZrObject)));
+        HIPCHK(c, c->tables.alloc(&c->d_objs_b[1], c->n_objs));
         HIPCHK(c, hipMemcpyAsync(c->d_objs_b[1], c->d_objs_b[0], (size_t)c->n_objs * sizeof(ZrObject), hipMemcpyDeviceToDevice, x));
         c->inst_dual = true;
     }
@@ -101,12 +100,11 @@ static int zr_object_set_instances_impl(zr_ctx* c, uint32_t index, uint32_t firs
     zr_ctx::InstStage& r = c->inst_ring[c->inst_slot++ % zr_ctx::INST_RING];
     HIPCHK(c, hipEventSynchronize(r.ev));          // the copy and the scatter that used this slot last are done
     if (r.cap < n) {
-        if (r.h) { (void)hipHostFree(r.h); r.h = nullptr; }
-        if (r.d) { (void)hipFree(r.d); r.d = nullptr; }
+        r.mem.release(); r.h = nullptr; r.d = nullptr;
         r.cap = 0;
         size_t cap = 4096; while (cap < n) cap *= 2;
-        HIPCHK(c, hipHostMalloc((void**)&r.h, cap * sizeof(XkInstanceData), hipHostMallocDefault));
-        HIPCHK(c, hipMalloc((void**)&r.d, cap * sizeof(XkInstanceData)));
+        HIPCHK(c, r.mem.host(&r.h, cap));
+        HIPCHK(c, r.mem.alloc(&r.d, cap));
         r.cap = cap;
     }
     memcpy(r.h, data, (size_t)n * sizeof(XkInstanceData));
@@ -154,16 +152,16 @@ int zr_instances_sync_host(zr_ctx* c, ZrSceneObject& o)
     return ZR_OK;
 }
 
-// finalize_scene, after a full synchronisation and a new table 0: the parity-1 table, when some object has been updated
+// finalize_scene, after a full synchronisation and a new table 0 (the draw tables' owner released the old ones): the parity-1 table, when
+// some object has been updated
 int zr_instances_table(zr_ctx* c)
 {
-    if (c->d_objs_b[1]) { (void)hipFree(c->d_objs_b[1]); c->d_objs_b[1] = nullptr; }
     c->inst_dual = false;
     c->inst_reader[0] = c->inst_reader[1] = 0;      // (nothing is in flight)
     bool any = false;
     for (auto& o : c->objects) { o.tab1 = false; any |= o.upd.plane[1] != nullptr; }
     if (!any) return ZR_OK;
-    HIPCHK(c, hipMalloc((void**)&c->d_objs_b[1], (size_t)c->n_objs * sizeof(ZrObject)));
+    HIPCHK(c, c->tables.alloc(&c->d_objs_b[1], c->n_objs));
     HIPCHK(c, hipMemcpy(c->d_objs_b[1], c->d_objs_b[0], (size_t)c->n_objs * sizeof(ZrObject), hipMemcpyDeviceToDevice));
     c->inst_dual = true;
     return ZR_OK;
@@ -206,17 +204,4 @@ int zr_instances_frame(zr_ctx* c, hipStream_t s, int par)
     }
     c->d_objs = c->d_objs_b[par]; c->inst_reader[par] = c->frame_no + 1;
     return ZR_OK;
-}
-
-void zr_instances_destroy(zr_ctx* c)
-{
-    for (auto& r : c->inst_ring) {
-        if (r.h) (void)hipHostFree(r.h);
-        if (r.d) (void)hipFree(r.d);
-        if (r.ev) (void)hipEventDestroy(r.ev);
-        r = zr_ctx::InstStage{};
-    }
-    if (c->ev_scatter) (void)hipEventDestroy(c->ev_scatter);
-    if (c->ev_apply) (void)hipEventDestroy(c->ev_apply);
-    c->ev_scatter = c->ev_apply = nullptr;
 }
