@@ -43,6 +43,33 @@ def test_library_exports_every_declared_symbol():
     assert os.path.dirname(engine.LIB_PATH).endswith("zeldaengine_amd")       # in-tree, not site-packages
 
 
+def test_every_status_entry_point_is_defined_once_behind_the_guard():
+    """No exception crosses the C-ABI (csrc/zr_ctx.h): every `int zr_*` of include/zelda_render.h has exactly one `extern "C" int`
+    definition in csrc/*.cpp, and behind its bare `return ZR_ERR_ARG` argument checks the body is `return zr_guard(...)`.  zr_tile_size is
+    the one `int` export that is no status: it returns a constant and cannot throw.  No `_impl` twin is left, and HIPCHK is defined once."""
+    csrc = os.path.join(ROOT, "zeldaengine_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".cpp", ".h", ".hip"))}
+    cpp = "\n".join(t for f, t in text.items() if f.endswith(".cpp"))
+    hdr = open(os.path.join(ROOT, "include", "zelda_render.h")).read()
+    declared = sorted(set(re.findall(r"^int\s+(zr_[a-z0-9_]+)\s*\(", hdr, re.M)) - {"zr_tile_size"})
+    assert len(declared) >= 80
+    early = re.compile(r"\s*if \([^;{}]*\) return ZR_ERR_ARG;")
+    bad = []
+    for name in declared:
+        defs = list(re.finditer(r'extern "C" int %s\(([^{;]*)\)\s*\{' % name, cpp))
+        if len(defs) != 1:
+            bad.append((name, "%d definitions" % len(defs)))
+            continue
+        body = cpp[defs[0].end():]
+        while early.match(body):
+            body = body[early.match(body).end():]
+        if not body.lstrip().startswith("return zr_guard("):
+            bad.append((name, body.lstrip()[:60]))
+    assert not bad, bad
+    assert not re.findall(r"\b\w+_impl\b", "\n".join(text.values()))
+    assert sum(t.count("#define HIPCHK") for t in text.values()) == 1
+
+
 def test_no_gpu_means_loud_failure_not_fallback():
     """Without a HIP device zr_create fails with ZR_ERR_DEVICE and Renderer raises: there is no CPU path in the product."""
     import torch

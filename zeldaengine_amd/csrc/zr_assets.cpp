@@ -93,33 +93,29 @@ std::string zr_asset_search(const zr_ctx* c, const std::string& name)
     return literal;                                            // as the engine: the caller then fails to open it
 }
 
-static int zr_set_asset_root_impl(zr_ctx* c, const char* dir)
-{
-    if (!c) return ZR_ERR_ARG;
-    c->asset_root = dir ? dir : "";
-    while (c->asset_root.size() > 1 && c->asset_root.back() == '/') c->asset_root.pop_back();
-    c->assets_on = dir != nullptr;
-    return ZR_OK;
-}
 extern "C" int zr_set_asset_root(zr_ctx* c, const char* dir)
 {
-    return zr_guard(c, [&]() { return zr_set_asset_root_impl(c, dir); });
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        c->asset_root = dir ? dir : "";
+        while (c->asset_root.size() > 1 && c->asset_root.back() == '/') c->asset_root.pop_back();
+        c->assets_on = dir != nullptr;
+        return ZR_OK;
+    });
 }
 
-static int zr_asset_path_search_impl(zr_ctx* c, const char* name, char* dst, size_t cap, size_t* len)
-{
-    if (!c || !name || !len) return ZR_ERR_ARG;
-    const std::string r = zr_asset_search(c, name);
-    *len = r.size();
-    if (dst) {
-        if (cap < r.size()) return zr_fail(c, ZR_ERR_ARG, "buffer too small");
-        memcpy(dst, r.data(), r.size());
-    }
-    return ZR_OK;
-}
 extern "C" int zr_asset_path_search(zr_ctx* c, const char* name, char* dst, size_t cap, size_t* len)
 {
-    return zr_guard(c, [&]() { return zr_asset_path_search_impl(c, name, dst, cap, len); });
+    if (!c || !name || !len) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        const std::string r = zr_asset_search(c, name);
+        *len = r.size();
+        if (dst) {
+            if (cap < r.size()) return zr_fail(c, ZR_ERR_ARG, "buffer too small");
+            memcpy(dst, r.data(), r.size());
+        }
+        return ZR_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ OBJ
@@ -198,19 +194,17 @@ bool zr_obj_ingest(const std::string& path, std::vector<XkVertex>* v, std::vecto
     return true;
 }
 
-static int zr_load_obj_impl(const char* path, XkVertex* v, uint32_t* nv, uint32_t* idx, uint32_t* ni)
-{
-    if (!path || !nv || !ni) return ZR_ERR_ARG;
-    std::vector<XkVertex> vv; std::vector<uint32_t> ii; std::string err;
-    if (!zr_obj_ingest(path, &vv, &ii, &err)) return ZR_ERR_IO;
-    if (v) { if (*nv < vv.size()) return ZR_ERR_ARG; memcpy(v, vv.data(), vv.size() * sizeof(XkVertex)); }
-    if (idx) { if (*ni < ii.size()) return ZR_ERR_ARG; memcpy(idx, ii.data(), ii.size() * 4); }
-    *nv = (uint32_t)vv.size(); *ni = (uint32_t)ii.size();
-    return ZR_OK;
-}
 extern "C" int zr_load_obj(const char* path, XkVertex* v, uint32_t* nv, uint32_t* idx, uint32_t* ni)
 {
-    return zr_guard(nullptr, [&]() { return zr_load_obj_impl(path, v, nv, idx, ni); });
+    if (!path || !nv || !ni) return ZR_ERR_ARG;
+    return zr_guard(nullptr, [&]() -> int {
+        std::vector<XkVertex> vv; std::vector<uint32_t> ii; std::string err;
+        if (!zr_obj_ingest(path, &vv, &ii, &err)) return ZR_ERR_IO;
+        if (v) { if (*nv < vv.size()) return ZR_ERR_ARG; memcpy(v, vv.data(), vv.size() * sizeof(XkVertex)); }
+        if (idx) { if (*ni < ii.size()) return ZR_ERR_ARG; memcpy(idx, ii.data(), ii.size() * 4); }
+        *nv = (uint32_t)vv.size(); *ni = (uint32_t)ii.size();
+        return ZR_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ PNG
@@ -332,63 +326,59 @@ bool zr_png_load(const std::string& path, std::vector<uint8_t>* rgba, uint32_t* 
     return true;
 }
 
-static int zr_load_png_rgba8_impl(const char* path, uint8_t* dst, size_t cap, uint32_t* w, uint32_t* h)
-{
-    if (!path || !w || !h) return ZR_ERR_ARG;
-    std::vector<uint8_t> px; std::string err;
-    if (!zr_png_load(path, &px, w, h, &err)) return ZR_ERR_IO;
-    if (dst) { if (cap < px.size()) return ZR_ERR_ARG; memcpy(dst, px.data(), px.size()); }
-    return ZR_OK;
-}
 extern "C" int zr_load_png_rgba8(const char* path, uint8_t* dst, size_t cap, uint32_t* w, uint32_t* h)
 {
-    return zr_guard(nullptr, [&]() { return zr_load_png_rgba8_impl(path, dst, cap, w, h); });
+    if (!path || !w || !h) return ZR_ERR_ARG;
+    return zr_guard(nullptr, [&]() -> int {
+        std::vector<uint8_t> px; std::string err;
+        if (!zr_png_load(path, &px, w, h, &err)) return ZR_ERR_IO;
+        if (dst) { if (cap < px.size()) return ZR_ERR_ARG; memcpy(dst, px.data(), px.size()); }
+        return ZR_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ .meshlet
 
 // LoadMeshletAsset, ZE:7046-7169: five sections, each a size_t count + the raw array (Meshlet 64 B, u32, u8, Vertex 32 B, u32);
 // vertices become XkVertex with colour (1, 1, 1).  Then CreateMeshVertexBuffers<XkMeshIndirect> = zr_mesh_set_meshlets.
-static int zr_load_meshlet_file_impl(zr_ctx* c, const char* path, uint32_t* mesh_id)
-{
-    if (!c || !path || !mesh_id) return ZR_ERR_ARG;
-    const std::string full = rooted(c, path);
-    std::ifstream in(full, std::ios::binary);
-    if (!in) return zr_fail(c, ZR_ERR_IO, "[LoadMeshletAsset] cannot open " + full);
-    struct FileVertex { float x, y, z, nx, ny, nz, u, v; };
-    std::vector<XkMeshlet> ml; std::vector<uint32_t> mv, indices; std::vector<uint8_t> mt; std::vector<FileVertex> fv;
-    // a section's count is checked against the bytes the file still holds BEFORE anything is allocated: a corrupt header cannot ask for
-    // gigabytes
-    in.seekg(0, std::ios::end);
-    const uint64_t file_bytes = (uint64_t)std::max<std::streamoff>(0, in.tellg());
-    in.seekg(0, std::ios::beg);
-    auto section = [&](auto& vec) -> bool {
-        uint64_t n = 0;
-        in.read((char*)&n, 8);
-        if (!in || n > (1ull << 31)) return false;
-        const uint64_t at = (uint64_t)std::max<std::streamoff>(0, in.tellg());
-        if (at > file_bytes || n * sizeof(vec[0]) > file_bytes - at) return false;
-        vec.resize((size_t)n);
-        in.read((char*)vec.data(), (std::streamsize)(n * sizeof(vec[0])));
-        return (bool)in || n == 0;
-    };
-    if (!section(ml) || !section(mv) || !section(mt) || !section(fv) || !section(indices))
-        return zr_fail(c, ZR_ERR_IO, "[LoadMeshletAsset] truncated file " + full);
-    if (ml.empty() || fv.empty() || indices.empty() || indices.size() % 3) return zr_fail(c, ZR_ERR_IO, "[LoadMeshletAsset] empty sections in " + full);
-    std::vector<XkVertex> v(fv.size());
-    for (size_t i = 0; i < fv.size(); ++i) {
-        v[i].Position[0] = fv[i].x; v[i].Position[1] = fv[i].y; v[i].Position[2] = fv[i].z;
-        v[i].Normal[0] = fv[i].nx; v[i].Normal[1] = fv[i].ny; v[i].Normal[2] = fv[i].nz;
-        v[i].Color[0] = v[i].Color[1] = v[i].Color[2] = 1.0f;
-        v[i].TexCoord[0] = fv[i].u; v[i].TexCoord[1] = fv[i].v;
-    }
-    int rc = zr_mesh_create(c, v.data(), (uint32_t)v.size(), indices.data(), (uint32_t)indices.size(), mesh_id);
-    if (rc) return rc;
-    return zr_mesh_set_meshlets(c, *mesh_id, ml.data(), (uint32_t)ml.size(), mv.data(), mv.size(), mt.data(), mt.size());
-}
 extern "C" int zr_load_meshlet_file(zr_ctx* c, const char* path, uint32_t* mesh_id)
 {
-    return zr_guard(c, [&]() { return zr_load_meshlet_file_impl(c, path, mesh_id); });
+    if (!c || !path || !mesh_id) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        const std::string full = rooted(c, path);
+        std::ifstream in(full, std::ios::binary);
+        if (!in) return zr_fail(c, ZR_ERR_IO, "[LoadMeshletAsset] cannot open " + full);
+        struct FileVertex { float x, y, z, nx, ny, nz, u, v; };
+        std::vector<XkMeshlet> ml; std::vector<uint32_t> mv, indices; std::vector<uint8_t> mt; std::vector<FileVertex> fv;
+        // a section's count is checked against the bytes the file still holds BEFORE anything is allocated: a corrupt header cannot ask for
+        // gigabytes
+        in.seekg(0, std::ios::end);
+        const uint64_t file_bytes = (uint64_t)std::max<std::streamoff>(0, in.tellg());
+        in.seekg(0, std::ios::beg);
+        auto section = [&](auto& vec) -> bool {
+            uint64_t n = 0;
+            in.read((char*)&n, 8);
+            if (!in || n > (1ull << 31)) return false;
+            const uint64_t at = (uint64_t)std::max<std::streamoff>(0, in.tellg());
+            if (at > file_bytes || n * sizeof(vec[0]) > file_bytes - at) return false;
+            vec.resize((size_t)n);
+            in.read((char*)vec.data(), (std::streamsize)(n * sizeof(vec[0])));
+            return (bool)in || n == 0;
+        };
+        if (!section(ml) || !section(mv) || !section(mt) || !section(fv) || !section(indices))
+            return zr_fail(c, ZR_ERR_IO, "[LoadMeshletAsset] truncated file " + full);
+        if (ml.empty() || fv.empty() || indices.empty() || indices.size() % 3) return zr_fail(c, ZR_ERR_IO, "[LoadMeshletAsset] empty sections in " + full);
+        std::vector<XkVertex> v(fv.size());
+        for (size_t i = 0; i < fv.size(); ++i) {
+            v[i].Position[0] = fv[i].x; v[i].Position[1] = fv[i].y; v[i].Position[2] = fv[i].z;
+            v[i].Normal[0] = fv[i].nx; v[i].Normal[1] = fv[i].ny; v[i].Normal[2] = fv[i].nz;
+            v[i].Color[0] = v[i].Color[1] = v[i].Color[2] = 1.0f;
+            v[i].TexCoord[0] = fv[i].u; v[i].TexCoord[1] = fv[i].v;
+        }
+        int rc = zr_mesh_create(c, v.data(), (uint32_t)v.size(), indices.data(), (uint32_t)indices.size(), mesh_id);
+        if (rc) return rc;
+        return zr_mesh_set_meshlets(c, *mesh_id, ml.data(), (uint32_t)ml.size(), mv.data(), mv.size(), mt.data(), mt.size());
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ Profabs + overrides
@@ -475,38 +465,34 @@ int zr_world_apply_overrides(zr_ctx* c, const ZrWorld& w)
 // ------------------------------------------------------------------------------------------------ World.json on disk
 
 // XkWorld::Load() from FilePath (ZE:1057-1068; default "Content/World.json", ZE:1027)
-static int zr_world_load_file_impl(zr_ctx* c, const char* path)
-{
-    if (!c) return ZR_ERR_ARG;
-    const std::string full = rooted(c, path ? path : "Content/World.json");
-    std::ifstream in(full, std::ios::binary);
-    if (!in) return zr_fail(c, ZR_ERR_IO, "[WORLD] cannot open " + full);
-    std::stringstream ss; ss << in.rdbuf();
-    const std::string text = ss.str();
-    return zr_world_load_json(c, text.data(), text.size());
-}
 extern "C" int zr_world_load_file(zr_ctx* c, const char* path)
 {
-    return zr_guard(c, [&]() { return zr_world_load_file_impl(c, path); });
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        const std::string full = rooted(c, path ? path : "Content/World.json");
+        std::ifstream in(full, std::ios::binary);
+        if (!in) return zr_fail(c, ZR_ERR_IO, "[WORLD] cannot open " + full);
+        std::stringstream ss; ss << in.rdbuf();
+        const std::string text = ss.str();
+        return zr_world_load_json(c, text.data(), text.size());
+    });
 }
 
 // XkWorld::Save(), ZE:1149-1263
-static int zr_world_save_file_impl(zr_ctx* c, const char* path)
-{
-    if (!c) return ZR_ERR_ARG;
-    size_t n = 0;
-    int rc = zr_world_save_json(c, nullptr, 0, &n);
-    if (rc) return rc;
-    std::string text(n, '\0');
-    rc = zr_world_save_json(c, text.data(), text.size(), &n);
-    if (rc) return rc;
-    const std::string full = rooted(c, path ? path : "Content/World.json");
-    std::ofstream out(full, std::ios::binary | std::ios::trunc);
-    if (!out) return zr_fail(c, ZR_ERR_IO, "[WORLD] cannot write " + full);
-    out.write(text.data(), (std::streamsize)text.size());
-    return out ? ZR_OK : zr_fail(c, ZR_ERR_IO, "[WORLD] short write to " + full);
-}
 extern "C" int zr_world_save_file(zr_ctx* c, const char* path)
 {
-    return zr_guard(c, [&]() { return zr_world_save_file_impl(c, path); });
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        size_t n = 0;
+        int rc = zr_world_save_json(c, nullptr, 0, &n);
+        if (rc) return rc;
+        std::string text(n, '\0');
+        rc = zr_world_save_json(c, text.data(), text.size(), &n);
+        if (rc) return rc;
+        const std::string full = rooted(c, path ? path : "Content/World.json");
+        std::ofstream out(full, std::ios::binary | std::ios::trunc);
+        if (!out) return zr_fail(c, ZR_ERR_IO, "[WORLD] cannot write " + full);
+        out.write(text.data(), (std::streamsize)text.size());
+        return out ? ZR_OK : zr_fail(c, ZR_ERR_IO, "[WORLD] short write to " + full);
+    });
 }

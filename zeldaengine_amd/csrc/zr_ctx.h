@@ -125,6 +125,20 @@ struct ZrWorld {
 };
 struct ZrProfab { uint32_t mesh; ZrMaterialHost mat; };
 
+// Two frames in flight (the reference does: MAX_FRAMES_IN_FLIGHT, ZE:77): what a lighting pass reads is double-buffered, and this is one
+// copy of it.  Frame N uses copy N & 1 (zr_ctx::fcur, set at frame begin, so the read-back entry points see the frame rendered last).
+struct FrameCopy {
+    GBufferPtrs G = {};                  // G.prim: the winner plane below, while the resolve keeps it (forward variant, id capture), else null
+    float* shadow = nullptr; XkView* view = nullptr;
+    uint32_t* empty_rgba = nullptr;      // the colour the lighting shader gives a pixel that holds every target's clear value, this frame
+    uint32_t* prim_plane = nullptr;      // winner ids (zr_set_shading, zr_set_id_capture), made on first use
+    bool overlay_dirty = false;          // G.overlay may hold skydome pixels of an earlier frame
+    bool shadow_cleared = false;         // `shadow` already holds depth 1.0 (cleared by the previous lighting pass)
+    uint64_t view_uploaded = 0;          // which version of the uniforms `view` holds
+    // a census enqueued against this copy (zr_instance_coverage_async): the frame that writes it next waits for it
+    hipEvent_t ev_ids = nullptr; bool ids_wait = false;
+};
+
 // Every HIP resource of the context is made through the owner of its lifetime: `own` (the context: what zr_create makes, its streams
 // first, and what later calls add for good), then one owner per group that is re-made or dropped as a whole (work pools, draw tables,
 // ids, skydome, background, cubemap, shadow tiles; the scene's in its meshes and objects; each staging slot).  `own` is declared first,
@@ -157,7 +171,7 @@ struct zr_ctx {
     ZrPass pass[2]; bool pass_live[2] = { false, false }, list_reuse[2] = { false, false }, list_valid[2] = { false, false };
     ZrPass list_key[2];
 
-    XkUniformBufferMVP cam, shadow; XkView view; XkView* d_view = nullptr; bool frame_valid = false;
+    XkUniformBufferMVP cam, shadow; XkView view; bool frame_valid = false;
     uint32_t debug_view = 0;
     uint32_t shading = 0;                           // ZR_SHADING_*: which scene pipeline shades the frame (zr_set_shading)
 
@@ -167,8 +181,7 @@ struct zr_ctx {
     uint32_t *d_owned = nullptr, *d_sowned = nullptr;
     uint32_t* d_tile_map = nullptr;      // tile -> owner * slots_per_rank + slot (k_untile)
     struct ZrDist* dist = nullptr;       // native multi-GPU host (zr_dist.cpp), or null
-    GBufferPtrs G = {};
-    float* d_shadow = nullptr; uint32_t* d_color = nullptr; uint32_t* d_tiles = nullptr;
+    uint32_t* d_color = nullptr; uint32_t* d_tiles = nullptr;
     float* d_shadow_ext = nullptr;       // caller-owned shadow map (zr_set_shadow_buffer), or null
     uint32_t shadow_rank = 0, shadow_world = 1; int stage = 0;   // stage: 0 idle, 1 shadow done, 2 gbuffer done
     // The shadow MAP owned by light-space super-tiles (zr_set_shadow_tiles): this context draws the casters that can reach a tile of the map
@@ -190,20 +203,19 @@ struct zr_ctx {
     ZrTriBins tb = {};                    // triangle-binned camera pass: selection list, records (as emitted / in tile order), slow list
     uint32_t chunk_capacity = 0;         // raster work units the chunk table holds: bin_capacity / ZR_CHUNK + tiles
     uint32_t n_inst_total = 0;
-    // one pixel holding the clear value of every GBuffer target, and the colour the lighting shader gives it this frame
-    uint8_t* d_clear_px = nullptr; GBufferPtrs Gclear = {}; uint32_t* d_empty_rgba = nullptr; bool empty_ready = false;
+    // one pixel holding the clear value of every GBuffer target; empty_ready: this frame's FrameCopy::empty_rgba has been computed
+    uint8_t* d_clear_px = nullptr; GBufferPtrs Gclear = {}; bool empty_ready = false;
     // diagnostics read from the environment once, at zr_create, by -DZR_DIAG builds (never needed for a correct frame)
     uint32_t env_skip = 0, env_skip_light = 0; int32_t env_light_list_min = 4; bool env_no_empty_px = false;
     // XkView upload: a pageable-memory hipMemcpyAsync blocks the host until the stream has drained (~0.3 ms per frame here),
     // so the uniforms go through a small ring of pinned copies, and only when they changed
     static constexpr int VIEW_RING = 4;
     XkView* h_view_ring = nullptr; hipEvent_t view_ev[VIEW_RING] = {}; uint32_t view_slot = 0; bool view_dirty = true;
-    uint64_t view_version = 1, view_uploaded[2] = { 0, 0 };      // which version of the uniforms each device copy holds
-    // Two frames in flight (the reference does: MAX_FRAMES_IN_FLIGHT, ZE:77): the camera pipeline runs on `cam_s`, the shadow
-    // pipeline and the lighting pass on the host's `stream`; frame N + 1's camera pipeline overlaps frame N's lighting.
-    // What a lighting pass reads is therefore double-buffered (GBuffer, shadow map, XkView, the empty-pixel colour); G, d_shadow,
-    // d_view, d_empty_rgba are aliases of the current frame's copies (set at frame begin, so the read-back entry points see the
-    // frame rendered last).
+    uint64_t view_version = 1;           // of the uniforms (FrameCopy::view_uploaded: the version a device copy holds)
+    // Two frames in flight: the camera pipeline runs on `cam_s`, the shadow pipeline and the lighting pass on the host's `stream`;
+    // frame N + 1's camera pipeline overlaps frame N's lighting.  What a lighting pass reads is therefore double-buffered: fc[fcur] is
+    // the current frame's copy - at stage 0 the one the frame enqueued last wrote - and fc[fcur ^ 1] the next frame's.
+    FrameCopy fc[2]; int fcur = 0;
     hipStream_t cam_s = nullptr; bool camera_on_lane = false;
     bool in_render = false;
     hipEvent_t ev_join = nullptr, ev_cam = nullptr;
@@ -212,11 +224,6 @@ struct zr_ctx {
     // it reuses the double-buffered copies, and consecutive ones give the per-frame GPU period (zr_get_frame_periods) for free.
     static constexpr int END_RING = 512;
     hipEvent_t ev_end[END_RING] = {};
-    uint32_t* d_prim_b[2] = { nullptr, nullptr };   // forward variant: winner ids per GBuffer copy (zr_set_shading)
-    GBufferPtrs Gb[2] = {}; float* d_shadow_b[2] = { nullptr, nullptr }; XkView* d_view_b[2] = { nullptr, nullptr };
-    uint32_t* d_empty_b[2] = { nullptr, nullptr };
-    bool overlay_dirty[2] = { false, false };       // Gb[i].overlay may hold skydome pixels of an earlier frame
-    bool shadow_cleared[2] = { false, false };      // d_shadow_b[i] already holds depth 1.0 (cleared by the previous lighting pass)
     unsigned long long* d_vis = nullptr; uint32_t raster_blocks = 2048, shadow_blocks = 2048;
     uint4* d_slow0 = nullptr; uint32_t slow0_cap = 1u << 18;      // shadow pass: triangles for the clipper (k_tile_slow)
     uint32_t work_capacity = 0, bin_capacity = 0; bool any_images = false, mixed_images = false;
@@ -236,16 +243,14 @@ struct zr_ctx {
     ZrDevStats* d_sstats = nullptr; uint32_t list_rebuild_mask = 0;
     uint64_t last_work[2] = { 0, 0 };
 
-    // object identity of the last frame (zr_set_id_capture, zr_ids.hip).  The winner planes are d_prim_b, shared with the forward variant.
-    bool id_capture = false;             // the next frames keep their winner plane (Gb[i].prim set)
+    // object identity of the last frame (zr_set_id_capture, zr_ids.hip).  The winner planes are FrameCopy::prim_plane, shared with the forward variant.
+    bool id_capture = false;             // the next frames keep their winner plane (FrameCopy::G.prim set)
     bool ids_frame = false, ids_this = false;      // the frame enqueued last kept it / the frame being enqueued does
     uint64_t scene_gen = 0, ids_gen = 0, ids_table_gen = ~0ull;      // objects added or cleared; the scene of the last frame / of the table
     ZrOwn ids_table, ids_pool;           // d_ids_draws; the slot pools (d_ids_counts ... d_ids_hits)
     ZrIdsDraw* d_ids_draws = nullptr; uint32_t ids_n_draws = 0, ids_n_slots = 0, ids_slot_cap = 0;
     uint32_t *d_ids_counts = nullptr, *d_ids_cov = nullptr, *d_ids_list = nullptr, *d_ids_n = nullptr;
     unsigned long long* d_ids_keys = nullptr; zr_hit* d_ids_hits = nullptr; uint2* d_ids_obj = nullptr;
-    // a census enqueued against copy i (zr_instance_coverage_async): the frame that writes copy i next waits for it
-    hipEvent_t ev_ids[2] = { nullptr, nullptr }; bool ids_wait[2] = { false, false };
 
     ZrOwn cube_mem; CubeDesc cube = {}; uint32_t cube_dim = 0, cube_levels = 0;
     float lut[256]; float* d_lut = nullptr;
@@ -268,11 +273,15 @@ struct zr_ctx {
 };
 
 int zr_fail(zr_ctx* c, int code, const std::string& msg);      // records the message (never throws), returns code
+#define HIPCHK(c, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) \
+    return zr_fail((c), ZR_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); } while (0)
+#define ARGCHK(c, cond) do { if (!(cond)) return zr_fail((c), ZR_ERR_ARG, "bad argument: " #cond); } while (0)
 // zr_instances_host.cpp
 int zr_instances_frame(zr_ctx* c, hipStream_t s, int par);       // frame head: this frame's draw table, the updates that are due
 int zr_instances_table(zr_ctx* c);                               // finalize_scene: the parity-1 table of a new draw table
 int zr_instances_sync_host(zr_ctx* c, ZrSceneObject& o);         // zr_object_get_instances after a device-form update
-// No exception crosses the C-ABI: entry points that build host-side containers run their body through this.
+// No exception crosses the C-ABI: every exported function that returns a status runs its body through this, behind nothing but its
+// bare argument checks (tests/test_abi_and_symbols.py holds the sources to it).
 template <typename F> static inline int zr_guard(zr_ctx* c, F&& body) noexcept
 {
     try { return body(); }

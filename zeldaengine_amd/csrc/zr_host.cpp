@@ -14,10 +14,6 @@
 #include <cstring>
 #include <cstdlib>
 
-#define HIPCHK(c, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) \
-    return zr_fail((c), ZR_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); } while (0)
-#define ARGCHK(c, cond) do { if (!(cond)) return zr_fail((c), ZR_ERR_ARG, "bad argument: " #cond); } while (0)
-
 int zr_fail(zr_ctx* c, int code, const std::string& msg)
 {
     if (c) { try { c->err = msg; } catch (...) { c->err.clear(); } }      // (called from catch blocks: must not throw itself)
@@ -65,6 +61,31 @@ static void default_lights(XkView* v)
     for (auto& l : v->SpotLights) l = d;
 }
 
+template <typename T> static hipError_t upload(ZrOwn& own, T** d, const std::vector<T>& h)
+{
+    hipError_t e = own.alloc(d, h.size());
+    if (e != hipSuccess) return e;
+    return h.empty() ? hipSuccess : hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
+// Tile ownership (zr_tile_owner) of a grid of tiles among `world` ranks: the tiles `rank` owns, in increasing index = its slots in the
+// packed buffer; map: tile -> owner * slots_per_rank + slot (k_untile); slots_per_rank: the most tiles any rank owns.
+struct ZrTilePartition { std::vector<uint32_t> owned, map; uint32_t slots_per_rank = 0; };
+static ZrTilePartition zr_partition(uint32_t tiles_x, uint32_t tiles_y, uint32_t world, uint32_t rank)
+{
+    ZrTilePartition P;
+    P.map.resize((size_t)tiles_x * tiles_y);
+    std::vector<uint32_t> counts(world, 0u);
+    for (uint32_t t = 0; t < tiles_x * tiles_y; ++t) {
+        const uint32_t o = zr_tile_owner(t % tiles_x, t / tiles_x, world);
+        P.map[t] = counts[o]++;                          // slot within its owner, for now
+        if (o == rank) P.owned.push_back(t);
+    }
+    for (uint32_t n : counts) P.slots_per_rank = std::max(P.slots_per_rank, n);
+    for (uint32_t t = 0; t < tiles_x * tiles_y; ++t) P.map[t] += zr_tile_owner(t % tiles_x, t / tiles_x, world) * P.slots_per_rank;
+    return P;
+}
+
 // zr_create's device half, straight through: it returns at the first failure, and the caller releases the partial context as
 // zr_destroy releases any other
 static int create_device_state(zr_ctx* c)
@@ -74,15 +95,14 @@ static int create_device_state(zr_ctx* c)
     c->stream = c->own_stream;
     for (auto& fr : c->evr) for (auto& e : fr) HIPCHK(c, A.event(&e));
     for (auto& e : c->ev_end) HIPCHK(c, A.event(&e));
-    for (auto& e : c->ev_ids) HIPCHK(c, A.event(&e, hipEventDisableTiming));
+    for (FrameCopy& F : c->fc) HIPCHK(c, A.event(&F.ev_ids, hipEventDisableTiming));
     const size_t n = (size_t)c->W * c->H;
-    for (int b = 0; b < 2; ++b) {       // two frames in flight: see zr_ctx.h
-        GBufferPtrs& G = c->Gb[b];
+    for (FrameCopy& F : c->fc) {        // two frames in flight: see zr_ctx.h
+        GBufferPtrs& G = F.G;
         HIPCHK(c, A.alloc(&G.depth, n)); HIPCHK(c, A.alloc(&G.scene_color, n)); HIPCHK(c, A.alloc(&G.gA, n)); HIPCHK(c, A.alloc(&G.gB, n));
         HIPCHK(c, A.alloc(&G.gC, n)); HIPCHK(c, A.alloc(&G.gD, n)); HIPCHK(c, A.alloc(&G.overlay, n));
-        HIPCHK(c, A.alloc(&c->d_shadow_b[b], (size_t)c->SD * c->SD)); HIPCHK(c, A.alloc(&c->d_view_b[b], 1)); HIPCHK(c, A.alloc(&c->d_empty_b[b], 1));
+        HIPCHK(c, A.alloc(&F.shadow, (size_t)c->SD * c->SD)); HIPCHK(c, A.alloc(&F.view, 1)); HIPCHK(c, A.alloc(&F.empty_rgba, 1));
     }
-    c->G = c->Gb[0]; c->d_shadow = c->d_shadow_b[0]; c->d_view = c->d_view_b[0]; c->d_empty_rgba = c->d_empty_b[0];
     HIPCHK(c, A.alloc(&c->d_color, n)); HIPCHK(c, A.alloc(&c->d_stats, 1));
     HIPCHK(c, A.alloc(&c->d_sstats, 1));       // the shadow pipeline's own block (see zr_ctx.h)
     HIPCHK(c, A.alloc(&c->d_lut, 256));
@@ -103,25 +123,12 @@ static int create_device_state(zr_ctx* c)
     c->tiles_x = (c->W + ZR_TILE - 1) / ZR_TILE; c->tiles_y = (c->H + ZR_TILE - 1) / ZR_TILE; c->n_tiles = c->tiles_x * c->tiles_y;
     c->stiles_x = (c->SD + ZR_TILE - 1) / ZR_TILE; c->stiles_y = c->stiles_x; c->sn_tiles = c->stiles_x * c->stiles_y;
     if (c->n_tiles > 16000u || c->sn_tiles > 16000u) return zr_fail(c, ZR_ERR_ARG, "too many tiles");   // binning histograms (4 B per tile, dynamic) + a few static words must fit the default 64 KB of LDS per workgroup
-    // tile ownership (zr_tile_owner): per rank the owned tiles in increasing index = its slots in the packed buffer
-    std::vector<uint32_t> owned, sowned(c->sn_tiles), tile_map(c->n_tiles), counts(c->cfg.tile_world, 0u);
-    for (uint32_t t = 0; t < c->n_tiles; ++t) {
-        const uint32_t o = zr_tile_owner(t % c->tiles_x, t / c->tiles_x, c->cfg.tile_world);
-        tile_map[t] = counts[o]++;                       // slot within its owner, for now
-        if (o == c->cfg.tile_rank) owned.push_back(t);
-    }
-    c->slots_per_rank = 0;
-    for (uint32_t n : counts) c->slots_per_rank = std::max(c->slots_per_rank, n);
-    for (uint32_t t = 0; t < c->n_tiles; ++t)
-        tile_map[t] += zr_tile_owner(t % c->tiles_x, t / c->tiles_x, c->cfg.tile_world) * c->slots_per_rank;
-    HIPCHK(c, A.alloc(&c->d_tile_map, tile_map.size()));
-    HIPCHK(c, hipMemcpy(c->d_tile_map, tile_map.data(), tile_map.size() * 4, hipMemcpyHostToDevice));
+    const ZrTilePartition tp = zr_partition(c->tiles_x, c->tiles_y, c->cfg.tile_world, c->cfg.tile_rank);
+    std::vector<uint32_t> sowned(c->sn_tiles);
     for (uint32_t t = 0; t < c->sn_tiles; ++t) sowned[t] = t;
-    c->n_owned = (uint32_t)owned.size();
-    HIPCHK(c, A.alloc(&c->d_owned, owned.size())); HIPCHK(c, A.alloc(&c->d_sowned, sowned.size()));
+    c->slots_per_rank = tp.slots_per_rank; c->n_owned = (uint32_t)tp.owned.size();
+    HIPCHK(c, upload(A, &c->d_tile_map, tp.map)); HIPCHK(c, upload(A, &c->d_owned, tp.owned)); HIPCHK(c, upload(A, &c->d_sowned, sowned));
     HIPCHK(c, A.alloc(&c->d_tiles, (size_t)c->slots_per_rank * ZR_TILE * ZR_TILE));
-    if (!owned.empty()) HIPCHK(c, hipMemcpy(c->d_owned, owned.data(), owned.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_sowned, sowned.data(), sowned.size() * 4, hipMemcpyHostToDevice));
     const uint32_t mt = (c->n_tiles > c->sn_tiles ? c->n_tiles : c->sn_tiles) * ZR_TSTRIDE + 1;     // (the bins use the first sn_tiles + 1 words)
     HIPCHK(c, A.alloc(&c->sb.tile_count, mt)); HIPCHK(c, A.alloc(&c->sb.tile_offset, mt));
     HIPCHK(c, A.alloc(&c->sb.tile_cursor, mt)); HIPCHK(c, A.alloc(&c->sb.chunk_offset, mt));
@@ -185,7 +192,7 @@ static int create_device_state(zr_ctx* c)
         for (int l = 0; l < 4; ++l) { c->hiz.lvl[l] = p; p += (size_t)c->hiz.hw[l] * c->hiz.hh[l]; }
         c->hiz.fine = p;
     }
-    HIPCHK(c, zr_fill_sync({ { c->Gb[0].overlay, 0, n * 4 }, { c->Gb[1].overlay, 0, n * 4 },
+    HIPCHK(c, zr_fill_sync({ { c->fc[0].G.overlay, 0, n * 4 }, { c->fc[1].G.overlay, 0, n * 4 },
                              { c->d_stats, 0, sizeof(ZrDevStats) }, { c->d_sstats, 0, sizeof(ZrDevStats) }, { c->d_color, 0, n * 4 },
                              { c->d_tiles, 0, (size_t)c->slots_per_rank * ZR_TILE * ZR_TILE * 4 },
                              { c->sb.tile_count, 0, mt * 4 },       // k_bin_count counts into zeroes (k_scan zeroes the counts
@@ -205,39 +212,43 @@ static int create_device_state(zr_ctx* c)
 extern "C" int zr_create(const zr_config* cfg, zr_ctx** out)
 {
     if (!cfg || !out) return ZR_ERR_ARG;
-    *out = nullptr;
-    if (cfg->width == 0 || cfg->height == 0 || cfg->width > 255u * ZR_TILE || cfg->height > 255u * ZR_TILE) return ZR_ERR_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ZR_ERR_DEVICE;
-    if (cfg->device < 0 || cfg->device >= ndev) return ZR_ERR_DEVICE;
-    if (hipSetDevice(cfg->device) != hipSuccess) return ZR_ERR_DEVICE;
-    zr_ctx* c = new zr_ctx();
-    c->cfg = *cfg;
-    if (c->cfg.tile_world == 0) c->cfg.tile_world = 1;
-    if (c->cfg.tile_rank >= c->cfg.tile_world) { delete c; return ZR_ERR_ARG; }
-    c->device = cfg->device;
-    c->W = cfg->width; c->H = cfg->height; c->SD = cfg->shadow_dim ? cfg->shadow_dim : XK_SHADOWMAP_DIM;
-    if (c->SD > 255u * ZR_TILE) { delete c; return ZR_ERR_ARG; }
-    if (c->cfg.flags & ZR_FLAG_MESHLET_BINS) { delete c; return ZR_ERR_UNSUPPORTED; }      // a reserved bit (refused before anything is allocated)
-    c->debug_view = cfg->debug_view;
-    memset(&c->cam, 0, sizeof c->cam); memset(&c->shadow, 0, sizeof c->shadow); memset(&c->view, 0, sizeof c->view);
-    default_lights(&c->view);
-    for (int i = 0; i < 256; ++i) c->lut[i] = zr_srgb_decode8((uint32_t)i);
-    int rc = zr_guard(c, [&]() { return create_device_state(c); });
-    if (rc == ZR_OK && zr_set_cubemap(c, nullptr, 0) != ZR_OK) rc = ZR_ERR_DEVICE;
-    if (rc != ZR_OK) { zr_destroy(c); return rc; }
-    *out = c;
-    return ZR_OK;
+    return zr_guard(nullptr, [&]() -> int {
+        *out = nullptr;
+        if (cfg->width == 0 || cfg->height == 0 || cfg->width > 255u * ZR_TILE || cfg->height > 255u * ZR_TILE) return ZR_ERR_ARG;
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ZR_ERR_DEVICE;
+        if (cfg->device < 0 || cfg->device >= ndev) return ZR_ERR_DEVICE;
+        if (hipSetDevice(cfg->device) != hipSuccess) return ZR_ERR_DEVICE;
+        zr_ctx* c = new zr_ctx();
+        c->cfg = *cfg;
+        if (c->cfg.tile_world == 0) c->cfg.tile_world = 1;
+        if (c->cfg.tile_rank >= c->cfg.tile_world) { delete c; return ZR_ERR_ARG; }
+        c->device = cfg->device;
+        c->W = cfg->width; c->H = cfg->height; c->SD = cfg->shadow_dim ? cfg->shadow_dim : XK_SHADOWMAP_DIM;
+        if (c->SD > 255u * ZR_TILE) { delete c; return ZR_ERR_ARG; }
+        if (c->cfg.flags & ZR_FLAG_MESHLET_BINS) { delete c; return ZR_ERR_UNSUPPORTED; }      // a reserved bit (refused before anything is allocated)
+        c->debug_view = cfg->debug_view;
+        memset(&c->cam, 0, sizeof c->cam); memset(&c->shadow, 0, sizeof c->shadow); memset(&c->view, 0, sizeof c->view);
+        default_lights(&c->view);
+        for (int i = 0; i < 256; ++i) c->lut[i] = zr_srgb_decode8((uint32_t)i);
+        int rc = zr_guard(c, [&]() { return create_device_state(c); });      // (a guard of its own: what it throws must not skip zr_destroy)
+        if (rc == ZR_OK && zr_set_cubemap(c, nullptr, 0) != ZR_OK) rc = ZR_ERR_DEVICE;
+        if (rc != ZR_OK) { zr_destroy(c); return rc; }
+        *out = c;
+        return ZR_OK;
+    });
 }
 
 extern "C" void zr_destroy(zr_ctx* c)
 {
     if (!c) return;
-    zr_livelink_stop(c);
-    (void)hipSetDevice(c->device);
-    (void)zr_sync_all(c);                      // including a geometry stage whose lighting pass never came
-    zr_dist_destroy(c);
-    delete c;                                  // every owner releases what it made; the context's own (streams last) after the others
+    try {
+        zr_livelink_stop(c);
+        (void)hipSetDevice(c->device);
+        (void)zr_sync_all(c);                  // including a geometry stage whose lighting pass never came
+        zr_dist_destroy(c);
+        delete c;                              // every owner releases what it made; the context's own (streams last) after the others
+    } catch (...) {}
 }
 
 extern "C" const char* zr_last_error(const zr_ctx* c) { return c ? c->err.c_str() : "no context (no usable HIP device?)"; }
@@ -249,53 +260,43 @@ extern "C" uint32_t zr_tile_owner(uint32_t tx, uint32_t ty, uint32_t world)
     return world <= 1 ? 0u : ((tx >> ZR_SUPERTILE_SHIFT) + (ty >> ZR_SUPERTILE_SHIFT) * ZR_SUPERTILE_SKEW) % world;
 }
 
-static int zr_tile_partition_impl(uint32_t width, uint32_t height, uint32_t world, uint32_t rank, uint32_t* owned, uint32_t* n_owned,
-                                 uint32_t* slots_per_rank)
-{
-    if (!width || !height || !world || rank >= world || !n_owned || !slots_per_rank) return ZR_ERR_ARG;
-    const uint32_t tx = (width + ZR_TILE - 1) / ZR_TILE, ty = (height + ZR_TILE - 1) / ZR_TILE;
-    std::vector<uint32_t> counts(world, 0u);
-    uint32_t n = 0;
-    for (uint32_t t = 0; t < tx * ty; ++t) {
-        const uint32_t o = zr_tile_owner(t % tx, t / tx, world);
-        counts[o]++;
-        if (o == rank) { if (owned) owned[n] = t; ++n; }
-    }
-    *n_owned = n; *slots_per_rank = 0;
-    for (uint32_t k : counts) *slots_per_rank = std::max(*slots_per_rank, k);
-    return ZR_OK;
-}
 extern "C" int zr_tile_partition(uint32_t width, uint32_t height, uint32_t world, uint32_t rank, uint32_t* owned, uint32_t* n_owned, uint32_t* slots_per_rank)
 {
-    return zr_guard(nullptr, [&]() { return zr_tile_partition_impl(width, height, world, rank, owned, n_owned, slots_per_rank); });
+    if (!width || !height || !world || rank >= world || !n_owned || !slots_per_rank) return ZR_ERR_ARG;
+    return zr_guard(nullptr, [&]() -> int {
+        const ZrTilePartition P = zr_partition((width + ZR_TILE - 1) / ZR_TILE, (height + ZR_TILE - 1) / ZR_TILE, world, rank);
+        if (owned) std::copy(P.owned.begin(), P.owned.end(), owned);
+        *n_owned = (uint32_t)P.owned.size(); *slots_per_rank = P.slots_per_rank;
+        return ZR_OK;
+    });
 }
 
 extern "C" int zr_set_stream(zr_ctx* c, void* s)
 {
     if (!c) return ZR_ERR_ARG;
-    hipStream_t ns = s ? (hipStream_t)s : c->own_stream;
-    // frames in flight are ordered by their place on the host's stream (frame_begin relies on it): a change of stream drains them
-    if (ns != c->stream && c->rendered) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, zr_sync_all(c)); }
-    c->stream = ns;
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        hipStream_t ns = s ? (hipStream_t)s : c->own_stream;
+        // frames in flight are ordered by their place on the host's stream (frame_begin relies on it): a change of stream drains them
+        if (ns != c->stream && c->rendered) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, zr_sync_all(c)); }
+        c->stream = ns;
+        return ZR_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ scene
 
-static int zr_mesh_create_impl(zr_ctx* c, const XkVertex* v, uint32_t nv, const uint32_t* idx, uint32_t ni, uint32_t* mesh_id)
-{
-    if (!c) return ZR_ERR_ARG;
-    ARGCHK(c, v && idx && mesh_id && nv > 0 && ni > 0 && ni % 3 == 0);
-    for (uint32_t i = 0; i < ni; ++i) if (idx[i] >= nv) return zr_fail(c, ZR_ERR_ARG, "index out of range");
-    ZrMesh m;
-    m.v.assign(v, v + nv); m.idx.assign(idx, idx + ni);
-    c->meshes.push_back(std::move(m));
-    *mesh_id = (uint32_t)c->meshes.size() - 1;
-    return ZR_OK;
-}
 extern "C" int zr_mesh_create(zr_ctx* c, const XkVertex* v, uint32_t nv, const uint32_t* idx, uint32_t ni, uint32_t* mesh_id)
 {
-    return zr_guard(c, [&]() { return zr_mesh_create_impl(c, v, nv, idx, ni, mesh_id); });
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        ARGCHK(c, v && idx && mesh_id && nv > 0 && ni > 0 && ni % 3 == 0);
+        for (uint32_t i = 0; i < ni; ++i) if (idx[i] >= nv) return zr_fail(c, ZR_ERR_ARG, "index out of range");
+        ZrMesh m;
+        m.v.assign(v, v + nv); m.idx.assign(idx, idx + ni);
+        c->meshes.push_back(std::move(m));
+        *mesh_id = (uint32_t)c->meshes.size() - 1;
+        return ZR_OK;
+    });
 }
 
 static int validate_meshlets(zr_ctx* c, const ZrMesh& m, const XkMeshlet* ml, uint32_t nm, size_t nmv, const uint32_t* mv,
@@ -314,114 +315,102 @@ static int validate_meshlets(zr_ctx* c, const ZrMesh& m, const XkMeshlet* ml, ui
     return ZR_OK;
 }
 
-static int zr_mesh_set_meshlets_impl(zr_ctx* c, uint32_t mesh_id, const XkMeshlet* ml, uint32_t nm,
-                                    const uint32_t* mv, size_t nmv, const uint8_t* mt, size_t nmt)
-{
-    if (!c) return ZR_ERR_ARG;
-    ARGCHK(c, mesh_id < c->meshes.size() && ml && nm && mv && mt);
-    ZrMesh& m = c->meshes[mesh_id];
-    if (m.uploaded) return zr_fail(c, ZR_ERR_STATE, "mesh already in use by a rendered scene");
-    int rc = validate_meshlets(c, m, ml, nm, nmv, mv, nmt, mt);
-    if (rc) return rc;
-    // CreateMeshVertexBuffers<XkMeshIndirect> (ZE:4733-4756): the draw becomes "meshlet by meshlet"; rebuild the
-    // draw-order index buffer accordingly so primitive ids follow meshlet order.
-    m.ms.meshlets.assign(ml, ml + nm); m.ms.mverts.assign(mv, mv + nmv); m.ms.mtris.assign(mt, mt + nmt);
-    // Every cull trusts the bounding sphere to enclose the meshlet's vertices (and the cone to describe its triangles): a record
-    // whose sphere does not is recomputed (ZM:149-166 fills them from meshopt_computeMeshletBounds, so a sound file never is).
-    for (uint32_t i = 0; i < nm; ++i) {
-        XkMeshlet& d = m.ms.meshlets[i];
-        bool ok = std::isfinite(d.BoundsRadius) && d.BoundsRadius >= 0.0f;
-        for (uint32_t k = 0; ok && k < d.VertexCount; ++k) {
-            const float* q = m.v[mv[d.VertexOffset + k]].Position;
-            const double dx = (double)q[0] - d.BoundsCenter[0], dy = (double)q[1] - d.BoundsCenter[1], dz = (double)q[2] - d.BoundsCenter[2];
-            if (!(std::sqrt(dx * dx + dy * dy + dz * dz) <= (double)d.BoundsRadius * (1.0 + 1e-5) + 1e-30)) ok = false;
-        }
-        if (!ok) {
-            XkMeshlet b = d;
-            zr_meshlet_bounds(m.v.data(), mv + d.VertexOffset, d.VertexCount, mt + d.TriangleOffset, d.TriangleCount, &b);
-            d = b;
-        }
-    }
-    m.ms.tri_order.clear(); m.idx.clear();
-    uint32_t base = 0;
-    for (uint32_t i = 0; i < nm; ++i) {
-        XkMeshlet& d = m.ms.meshlets[i];
-        d.BindlessContext = base;
-        for (uint32_t t = 0; t < d.TriangleCount; ++t) {
-            for (int k = 0; k < 3; ++k) m.idx.push_back(mv[d.VertexOffset + mt[d.TriangleOffset + 3u * t + (uint32_t)k]]);
-            m.ms.tri_order.push_back(base + t);
-        }
-        base += d.TriangleCount;
-    }
-    m.has_meshlets = true;
-    return ZR_OK;
-}
 extern "C" int zr_mesh_set_meshlets(zr_ctx* c, uint32_t mesh_id, const XkMeshlet* ml, uint32_t nm, const uint32_t* mv, size_t nmv, const uint8_t* mt, size_t nmt)
 {
-    return zr_guard(c, [&]() { return zr_mesh_set_meshlets_impl(c, mesh_id, ml, nm, mv, nmv, mt, nmt); });
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        ARGCHK(c, mesh_id < c->meshes.size() && ml && nm && mv && mt);
+        ZrMesh& m = c->meshes[mesh_id];
+        if (m.uploaded) return zr_fail(c, ZR_ERR_STATE, "mesh already in use by a rendered scene");
+        int rc = validate_meshlets(c, m, ml, nm, nmv, mv, nmt, mt);
+        if (rc) return rc;
+        // CreateMeshVertexBuffers<XkMeshIndirect> (ZE:4733-4756): the draw becomes "meshlet by meshlet"; rebuild the
+        // draw-order index buffer accordingly so primitive ids follow meshlet order.
+        m.ms.meshlets.assign(ml, ml + nm); m.ms.mverts.assign(mv, mv + nmv); m.ms.mtris.assign(mt, mt + nmt);
+        // Every cull trusts the bounding sphere to enclose the meshlet's vertices (and the cone to describe its triangles): a record
+        // whose sphere does not is recomputed (ZM:149-166 fills them from meshopt_computeMeshletBounds, so a sound file never is).
+        for (uint32_t i = 0; i < nm; ++i) {
+            XkMeshlet& d = m.ms.meshlets[i];
+            bool ok = std::isfinite(d.BoundsRadius) && d.BoundsRadius >= 0.0f;
+            for (uint32_t k = 0; ok && k < d.VertexCount; ++k) {
+                const float* q = m.v[mv[d.VertexOffset + k]].Position;
+                const double dx = (double)q[0] - d.BoundsCenter[0], dy = (double)q[1] - d.BoundsCenter[1], dz = (double)q[2] - d.BoundsCenter[2];
+                if (!(std::sqrt(dx * dx + dy * dy + dz * dz) <= (double)d.BoundsRadius * (1.0 + 1e-5) + 1e-30)) ok = false;
+            }
+            if (!ok) {
+                XkMeshlet b = d;
+                zr_meshlet_bounds(m.v.data(), mv + d.VertexOffset, d.VertexCount, mt + d.TriangleOffset, d.TriangleCount, &b);
+                d = b;
+            }
+        }
+        m.ms.tri_order.clear(); m.idx.clear();
+        uint32_t base = 0;
+        for (uint32_t i = 0; i < nm; ++i) {
+            XkMeshlet& d = m.ms.meshlets[i];
+            d.BindlessContext = base;
+            for (uint32_t t = 0; t < d.TriangleCount; ++t) {
+                for (int k = 0; k < 3; ++k) m.idx.push_back(mv[d.VertexOffset + mt[d.TriangleOffset + 3u * t + (uint32_t)k]]);
+                m.ms.tri_order.push_back(base + t);
+            }
+            base += d.TriangleCount;
+        }
+        m.has_meshlets = true;
+        return ZR_OK;
+    });
 }
 
-static int zr_mesh_build_meshlets_impl(zr_ctx* c, uint32_t mesh_id, uint32_t max_v, uint32_t max_t, float cone_weight)
-{
-    if (!c) return ZR_ERR_ARG;
-    ARGCHK(c, mesh_id < c->meshes.size());
-    if (max_v == 0) max_v = 64;
-    if (max_t == 0) max_t = 124;
-    ARGCHK(c, max_v >= 3 && max_v <= 64 && max_t >= 1 && max_t <= 128);
-    ZrMesh& m = c->meshes[mesh_id];
-    if (m.uploaded) return zr_fail(c, ZR_ERR_STATE, "mesh already in use by a rendered scene");
-    zr_build_meshlets(m.v.data(), (uint32_t)m.v.size(), m.idx.data(), (uint32_t)m.idx.size(), max_v, max_t, cone_weight, &m.ms);
-    m.has_meshlets = true;
-    return ZR_OK;
-}
 extern "C" int zr_mesh_build_meshlets(zr_ctx* c, uint32_t mesh_id, uint32_t max_v, uint32_t max_t, float cone_weight)
 {
-    return zr_guard(c, [&]() { return zr_mesh_build_meshlets_impl(c, mesh_id, max_v, max_t, cone_weight); });
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        ARGCHK(c, mesh_id < c->meshes.size());
+        if (max_v == 0) max_v = 64;
+        if (max_t == 0) max_t = 124;
+        ARGCHK(c, max_v >= 3 && max_v <= 64 && max_t >= 1 && max_t <= 128);
+        ZrMesh& m = c->meshes[mesh_id];
+        if (m.uploaded) return zr_fail(c, ZR_ERR_STATE, "mesh already in use by a rendered scene");
+        zr_build_meshlets(m.v.data(), (uint32_t)m.v.size(), m.idx.data(), (uint32_t)m.idx.size(), max_v, max_t, cone_weight, &m.ms);
+        m.has_meshlets = true;
+        return ZR_OK;
+    });
 }
 
 // Context-free form of the clusteriser: the ZeldaMeshlet tool's BuildMeshlets (ZM:132-172) as a library call.  Pure host
 // code (runs without a GPU).  Pass NULL outputs to query the sizes.  tri_order[k] = index-buffer triangle of slot k.
-static int zr_meshlets_build_impl(const XkVertex* v, uint32_t nv, const uint32_t* idx, uint32_t ni, uint32_t max_v, uint32_t max_t,
-                                 float cone_weight, XkMeshlet* ml, uint32_t* nm, uint32_t* mv, size_t* nmv, uint8_t* mt, size_t* nmt,
-                                 uint32_t* tri_order)
-{
-    if (!v || !idx || !nm || !nmv || !nmt || nv == 0 || ni == 0 || ni % 3) return ZR_ERR_ARG;
-    if (max_v == 0) max_v = 64;
-    if (max_t == 0) max_t = 124;
-    if (max_v < 3 || max_v > 64 || max_t < 1 || max_t > 128) return ZR_ERR_ARG;
-    for (uint32_t i = 0; i < ni; ++i) if (idx[i] >= nv) return ZR_ERR_ARG;
-    ZrMeshletSet ms;
-    zr_build_meshlets(v, nv, idx, ni, max_v, max_t, cone_weight, &ms);
-    *nm = (uint32_t)ms.meshlets.size(); *nmv = ms.mverts.size(); *nmt = ms.mtris.size();
-    if (ml) { memcpy(ml, ms.meshlets.data(), ms.meshlets.size() * sizeof(XkMeshlet)); for (uint32_t i = 0; i < *nm; ++i) ml[i].BindlessContext = 0; }
-    if (mv) memcpy(mv, ms.mverts.data(), ms.mverts.size() * 4);
-    if (mt) memcpy(mt, ms.mtris.data(), ms.mtris.size());
-    if (tri_order) memcpy(tri_order, ms.tri_order.data(), ms.tri_order.size() * 4);
-    return ZR_OK;
-}
 extern "C" int zr_meshlets_build(const XkVertex* v, uint32_t nv, const uint32_t* idx, uint32_t ni, uint32_t max_v, uint32_t max_t, float cone_weight, XkMeshlet* ml, uint32_t* nm, uint32_t* mv, size_t* nmv, uint8_t* mt, size_t* nmt, uint32_t* tri_order)
 {
-    return zr_guard(nullptr, [&]() { return zr_meshlets_build_impl(v, nv, idx, ni, max_v, max_t, cone_weight, ml, nm, mv, nmv, mt, nmt, tri_order); });
+    if (!v || !idx || !nm || !nmv || !nmt || nv == 0 || ni == 0 || ni % 3) return ZR_ERR_ARG;
+    return zr_guard(nullptr, [&]() -> int {
+        if (max_v == 0) max_v = 64;
+        if (max_t == 0) max_t = 124;
+        if (max_v < 3 || max_v > 64 || max_t < 1 || max_t > 128) return ZR_ERR_ARG;
+        for (uint32_t i = 0; i < ni; ++i) if (idx[i] >= nv) return ZR_ERR_ARG;
+        ZrMeshletSet ms;
+        zr_build_meshlets(v, nv, idx, ni, max_v, max_t, cone_weight, &ms);
+        *nm = (uint32_t)ms.meshlets.size(); *nmv = ms.mverts.size(); *nmt = ms.mtris.size();
+        if (ml) { memcpy(ml, ms.meshlets.data(), ms.meshlets.size() * sizeof(XkMeshlet)); for (uint32_t i = 0; i < *nm; ++i) ml[i].BindlessContext = 0; }
+        if (mv) memcpy(mv, ms.mverts.data(), ms.mverts.size() * 4);
+        if (mt) memcpy(mt, ms.mtris.data(), ms.mtris.size());
+        if (tri_order) memcpy(tri_order, ms.tri_order.data(), ms.tri_order.size() * 4);
+        return ZR_OK;
+    });
 }
 
-static int zr_mesh_get_meshlets_impl(zr_ctx* c, uint32_t mesh_id, XkMeshlet* ml, uint32_t* nm, uint32_t* mv, size_t* nmv,
-                                    uint8_t* mt, size_t* nmt)
-{
-    if (!c) return ZR_ERR_ARG;
-    ARGCHK(c, mesh_id < c->meshes.size());
-    const ZrMesh& m = c->meshes[mesh_id];
-    if (nm) *nm = (uint32_t)m.ms.meshlets.size();
-    if (nmv) *nmv = m.ms.mverts.size();
-    if (nmt) *nmt = m.ms.mtris.size();
-    if (ml) { memcpy(ml, m.ms.meshlets.data(), m.ms.meshlets.size() * sizeof(XkMeshlet));
-              for (size_t i = 0; i < m.ms.meshlets.size(); ++i) ml[i].BindlessContext = 0; }
-    if (mv) memcpy(mv, m.ms.mverts.data(), m.ms.mverts.size() * 4);
-    if (mt) memcpy(mt, m.ms.mtris.data(), m.ms.mtris.size());
-    return ZR_OK;
-}
 extern "C" int zr_mesh_get_meshlets(zr_ctx* c, uint32_t mesh_id, XkMeshlet* ml, uint32_t* nm, uint32_t* mv, size_t* nmv, uint8_t* mt, size_t* nmt)
 {
-    return zr_guard(c, [&]() { return zr_mesh_get_meshlets_impl(c, mesh_id, ml, nm, mv, nmv, mt, nmt); });
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        ARGCHK(c, mesh_id < c->meshes.size());
+        const ZrMesh& m = c->meshes[mesh_id];
+        if (nm) *nm = (uint32_t)m.ms.meshlets.size();
+        if (nmv) *nmv = m.ms.mverts.size();
+        if (nmt) *nmt = m.ms.mtris.size();
+        if (ml) { memcpy(ml, m.ms.meshlets.data(), m.ms.meshlets.size() * sizeof(XkMeshlet));
+                  for (size_t i = 0; i < m.ms.meshlets.size(); ++i) ml[i].BindlessContext = 0; }
+        if (mv) memcpy(mv, m.ms.mverts.data(), m.ms.mverts.size() * 4);
+        if (mt) memcpy(mt, m.ms.mtris.data(), m.ms.mtris.size());
+        return ZR_OK;
+    });
 }
 
 int zr_material_prepare(zr_ctx* c, const zr_material* mat, ZrMaterialHost* out)
@@ -448,13 +437,12 @@ static int idx_clamp_h(float f, int hi) { f = fminf(fmaxf(f, 0.0f), (float)hi); 
 
 // RHIGenerateMipmaps (ZE:6348-6433): level l+1 = vkCmdBlitImage(LINEAR) of level l at half size; mipLevels =
 // floor(log2(max(w, h))) + 1 (ZE:6887).  Filtered on decoded values (sRGB for the base-colour slot, ZE:5878), re-encoded.
-static void build_mip_chain(const zr_ctx* c, const std::vector<uint8_t>& img, uint32_t w, uint32_t h, bool srgb,
-                            std::vector<uint8_t>* chain, uint32_t* levels)
+static void build_mip_chain(const zr_ctx* c, const uint8_t* rgba8, uint32_t w, uint32_t h, bool srgb, std::vector<uint8_t>* chain, uint32_t* levels)
 {
     uint32_t m = w > h ? w : h;
     uint32_t nl = 1; while (m > 1) { m >>= 1; nl++; }
     *levels = nl;
-    *chain = img;
+    chain->assign(rgba8, rgba8 + (size_t)w * h * 4);
     size_t src_off = 0;
     uint32_t sw = w, sh = h;
     for (uint32_t l = 1; l < nl; ++l) {
@@ -484,6 +472,25 @@ static void build_mip_chain(const zr_ctx* c, const std::vector<uint8_t>& img, ui
     }
 }
 
+// An image for the kernels to sample: `bytes` into device memory of `own` (ZrOwn::alloc_image)
+static int upload_bytes(zr_ctx* c, ZrOwn& own, const std::vector<uint8_t>& bytes, uint8_t** d)
+{
+    HIPCHK(c, own.alloc_image(d, bytes.size()));
+    HIPCHK(c, hipMemcpy(*d, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
+    return ZR_OK;
+}
+// ... an RGBA8 image with its mip chain; `chain` (optional) keeps the chain on the host, for the packed material
+static int upload_image(zr_ctx* c, ZrOwn& own, const uint8_t* rgba8, uint32_t iw, uint32_t ih, bool srgb, uint8_t** d, uint32_t* w, uint32_t* h,
+                        uint32_t* levels, std::vector<uint8_t>* chain = nullptr)
+{
+    if (iw == 0 || ih == 0 || iw > 16384 || ih > 16384) return zr_fail(c, ZR_ERR_ARG, "bad image size");
+    std::vector<uint8_t> mine;
+    if (!chain) chain = &mine;
+    build_mip_chain(c, rgba8, iw, ih, srgb, chain, levels);
+    *w = iw; *h = ih;
+    return upload_bytes(c, own, *chain, d);
+}
+
 int zr_object_add_internal(zr_ctx* c, uint32_t mesh_id, const ZrMaterialHost& mat, const XkInstanceData* inst, uint32_t n_inst)
 {
     ZrSceneObject o;
@@ -495,12 +502,8 @@ int zr_object_add_internal(zr_ctx* c, uint32_t mesh_id, const ZrMaterialHost& ma
     int lead = -1;                                          // first slot that holds an image
     for (int t = 0; t < 7; ++t) {
         if (mat.image[t].empty()) continue;
-        std::vector<uint8_t>& chain = chains[t]; uint32_t levels = 1;
-        build_mip_chain(c, mat.image[t], mat.w[t], mat.h[t], t == 0, &chain, &levels);
-        hipError_t e = o.mem.alloc_image(&o.d_tex[t], chain.size());
-        if (e == hipSuccess) e = hipMemcpy(o.d_tex[t], chain.data(), chain.size(), hipMemcpyHostToDevice);
-        if (e != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, hipGetErrorString(e));
-        o.tex_w[t] = mat.w[t]; o.tex_h[t] = mat.h[t]; o.tex_levels[t] = levels;
+        int rc = upload_image(c, o.mem, mat.image[t].data(), mat.w[t], mat.h[t], t == 0, &o.d_tex[t], &o.tex_w[t], &o.tex_h[t], &o.tex_levels[t], &chains[t]);
+        if (rc) return rc;
         if (lead < 0) lead = t;
         else if (mat.w[t] != mat.w[lead] || mat.h[t] != mat.h[lead]) o.mixed_sizes = true;
     }
@@ -517,37 +520,32 @@ int zr_object_add_internal(zr_ctx* c, uint32_t mesh_id, const ZrMaterialHost& ma
                 for (int ch = 0; ch < k.n; ++ch)
                     pk[i * 16 + (size_t)k.ch + (size_t)ch] = image ? src[i * 4 + (size_t)ch] : (uint8_t)(mat.texel[k.slot] >> (8 * ch));
         }
-        hipError_t e = o.mem.alloc_image(&o.d_tex[7], pk.size());
-        if (e == hipSuccess) e = hipMemcpy(o.d_tex[7], pk.data(), pk.size(), hipMemcpyHostToDevice);
-        if (e != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, hipGetErrorString(e));
+        int rc = upload_bytes(c, o.mem, pk, &o.d_tex[7]);
+        if (rc) return rc;
         o.tex_w[7] = mat.w[lead]; o.tex_h[7] = mat.h[lead]; o.tex_levels[7] = o.tex_levels[lead];
     }
-    { hipError_t e = o.mem.alloc(&o.d_inst, o.n_inst); if (e != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, hipGetErrorString(e)); }
+    HIPCHK(c, o.mem.alloc(&o.d_inst, o.n_inst));
     if (n_inst) {                       // (kept: the authoritative values of zr_object_set_instances / zr_object_update_instances_async)
-        hipError_t e = o.mem.alloc(&o.d_raw, n_inst);
-        if (e == hipSuccess) e = hipMemcpyAsync(o.d_raw, inst, sizeof(XkInstanceData) * n_inst, hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, hipGetErrorString(e));
+        HIPCHK(c, o.mem.alloc(&o.d_raw, n_inst));
+        HIPCHK(c, hipMemcpyAsync(o.d_raw, inst, sizeof(XkInstanceData) * n_inst, hipMemcpyHostToDevice, c->stream));
     }
     zr_launch_instance_prep(o.d_raw, o.d_inst, o.n_inst, o.instanced ? 1u : 0u, c->stream);
-    hipError_t e = zr_sync_all(c);
-    if (e != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, hipGetErrorString(e));
+    HIPCHK(c, zr_sync_all(c));
     c->objects.push_back(std::move(o));
     c->scene_dirty = true; c->scene_gen++;
     return ZR_OK;
 }
 
-static int zr_object_add_impl(zr_ctx* c, uint32_t mesh_id, const zr_material* mat, const XkInstanceData* inst, uint32_t n_inst)
-{
-    if (!c) return ZR_ERR_ARG;
-    ARGCHK(c, mesh_id < c->meshes.size() && (n_inst == 0 || inst));
-    ZrMaterialHost m;
-    int rc = zr_material_prepare(c, mat, &m);
-    if (rc) return rc;
-    return zr_object_add_internal(c, mesh_id, m, inst, n_inst);
-}
 extern "C" int zr_object_add(zr_ctx* c, uint32_t mesh_id, const zr_material* mat, const XkInstanceData* inst, uint32_t n_inst)
 {
-    return zr_guard(c, [&]() { return zr_object_add_impl(c, mesh_id, mat, inst, n_inst); });
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        ARGCHK(c, mesh_id < c->meshes.size() && (n_inst == 0 || inst));
+        ZrMaterialHost m;
+        int rc = zr_material_prepare(c, mat, &m);
+        if (rc) return rc;
+        return zr_object_add_internal(c, mesh_id, m, inst, n_inst);
+    });
 }
 
 // Capacities of the triangle-record arrays (chunks of 256 records) and of the clipped-triangle list, for hosts that size them themselves
@@ -557,18 +555,24 @@ static constexpr uint32_t ZR_MAX_RECORD_CHUNKS = 0x3FFFFFFFu / 256u;
 extern "C" int zr_set_limits(zr_ctx* c, uint32_t record_chunks, uint32_t slow_triangles)
 {
     if (!c) return ZR_ERR_ARG;
-    if (record_chunks > ZR_MAX_RECORD_CHUNKS) return zr_fail(c, ZR_ERR_ARG, "zr_set_limits: record_chunks above (2^30 - 1) / 256");
-    c->limit_record_chunks = record_chunks; c->limit_slow_triangles = slow_triangles;
-    c->work_capacity = 0; c->scene_dirty = true;          // the pools are re-made by the next frame
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        if (record_chunks > ZR_MAX_RECORD_CHUNKS) return zr_fail(c, ZR_ERR_ARG, "zr_set_limits: record_chunks above (2^30 - 1) / 256");
+        c->limit_record_chunks = record_chunks; c->limit_slow_triangles = slow_triangles;
+        c->work_capacity = 0; c->scene_dirty = true;          // the pools are re-made by the next frame
+        return ZR_OK;
+    });
 }
 
 extern "C" int zr_set_bucket_share(zr_ctx* c, uint32_t percent)
 {
     if (!c || percent < 1u || percent > 100u) return ZR_ERR_ARG;
-    c->bucket_pct = percent;          // (k_plan's argument from the next plan on; a frame that overflows its buckets is the same frame)
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        c->bucket_pct = percent;          // (k_plan's argument from the next plan on; a frame that overflows its buckets is the same frame)
+        return ZR_OK;
+    });
 }
+
+static void drop_draw_tables(zr_ctx* c) { c->tables.release(); c->d_objs_b[0] = c->d_objs_b[1] = c->d_objs = nullptr; c->inst_dual = false; }
 
 // (every object and mesh releases its device memory as it goes)
 static void free_scene(zr_ctx* c)
@@ -576,24 +580,19 @@ static void free_scene(zr_ctx* c)
     c->objects.clear(); c->scene_gen++;
     c->meshes.clear();
     c->profabs.clear();
-    c->tables.release(); c->d_objs_b[0] = c->d_objs_b[1] = c->d_objs = nullptr; c->inst_dual = false;
+    drop_draw_tables(c);
     c->n_objs = 0; c->n_work = 0; c->scene_dirty = true;
 }
 
 extern "C" int zr_scene_clear(zr_ctx* c)
 {
     if (!c) return ZR_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, zr_sync_all(c));
-    free_scene(c);
-    return ZR_OK;
-}
-
-template <typename T> static hipError_t upload(ZrOwn& own, T** d, const std::vector<T>& h)
-{
-    hipError_t e = own.alloc(d, h.size());
-    if (e != hipSuccess) return e;
-    return h.empty() ? hipSuccess : hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+    return zr_guard(c, [&]() -> int {
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, zr_sync_all(c));
+        free_scene(c);
+        return ZR_OK;
+    });
 }
 
 static int upload_mesh(zr_ctx* c, ZrMesh& m)
@@ -756,7 +755,7 @@ static int finalize_scene(zr_ctx* c)
     const uint64_t scene_work = work, scene_inst = inst_total;
     if (sky) emit(c->sky_obj, c->sky_mesh, ZR_OBJ_SKY);
     if (work >= 0xFFFFFFFFull || prim >= 0xFFFFFFFFull) return zr_fail(c, ZR_ERR_OVERFLOW, "scene exceeds 2^32 meshlet-instances or primitives");
-    c->tables.release(); c->d_objs_b[0] = c->d_objs_b[1] = c->d_objs = nullptr; c->inst_dual = false;     // (zr_instances_table: table 1)
+    drop_draw_tables(c);                // (zr_instances_table: table 1)
     HIPCHK(c, upload(c->tables, &c->d_objs_b[0], tab));
     c->d_objs = c->d_objs_b[0];
     c->n_objs = (uint32_t)tab.size(); c->n_work = (uint32_t)scene_work; c->n_inst_total = (uint32_t)scene_inst;
@@ -778,122 +777,107 @@ static int finalize_scene(zr_ctx* c)
 
 // ------------------------------------------------------------------------------------------------ skydome + background
 
-static int upload_texture(zr_ctx* c, ZrOwn& own, const zr_image* tex, bool srgb, uint8_t** d, uint32_t* w, uint32_t* h, uint32_t* levels)
-{
-    if (tex->width == 0 || tex->height == 0 || tex->width > 16384 || tex->height > 16384) return zr_fail(c, ZR_ERR_ARG, "bad image size");
-    std::vector<uint8_t> img(tex->rgba8, tex->rgba8 + (size_t)tex->width * tex->height * 4), chain;
-    build_mip_chain(c, img, tex->width, tex->height, srgb, &chain, levels);
-    HIPCHK(c, own.alloc_image(d, chain.size()));
-    HIPCHK(c, hipMemcpy(*d, chain.data(), chain.size(), hipMemcpyHostToDevice));
-    *w = tex->width; *h = tex->height;
-    return ZR_OK;
-}
-
-static int zr_set_skydome_impl(zr_ctx* c, const XkVertex* v, uint32_t nv, const uint32_t* idx, uint32_t ni, const zr_image* tex)
-{
-    if (!c) return ZR_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, zr_sync_all(c));
-    c->sky_mesh = ZrMesh(); c->sky_obj = ZrSceneObject(); c->sky_set = false; c->scene_dirty = true;      // (releasing the old ones)
-    if (!tex || !tex->rgba8) return ZR_OK;
-    ARGCHK(c, v && idx && nv > 0 && ni > 0 && ni % 3 == 0);
-    for (uint32_t i = 0; i < ni; ++i) if (idx[i] >= nv) return zr_fail(c, ZR_ERR_ARG, "index out of range");
-    c->sky_mesh.v.assign(v, v + nv); c->sky_mesh.idx.assign(idx, idx + ni);
-    ZrSceneObject& o = c->sky_obj;
-    o.mesh = 0; o.instanced = false; o.n_inst = 1;
-    for (int t = 0; t < 7; ++t) o.texel[t] = 0xFFFFFFFFu;
-    o.bc_linear[0] = o.bc_linear[1] = o.bc_linear[2] = 1.0f;
-    int rc = upload_texture(c, o.mem, tex, true, &o.d_tex[0], &o.tex_w[0], &o.tex_h[0], &o.tex_levels[0]);   // sRGB by default, ZE:5860
-    if (rc) return rc;
-    HIPCHK(c, o.mem.alloc(&o.d_inst, 1));
-    zr_launch_instance_prep(nullptr, o.d_inst, 1, 0u, c->stream);
-    HIPCHK(c, zr_sync_all(c));
-    c->sky_set = true;
-    return ZR_OK;
-}
 extern "C" int zr_set_skydome(zr_ctx* c, const XkVertex* v, uint32_t nv, const uint32_t* idx, uint32_t ni, const zr_image* tex)
 {
-    return zr_guard(c, [&]() { return zr_set_skydome_impl(c, v, nv, idx, ni, tex); });
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, zr_sync_all(c));
+        c->sky_mesh = ZrMesh(); c->sky_obj = ZrSceneObject(); c->sky_set = false; c->scene_dirty = true;      // (releasing the old ones)
+        if (!tex || !tex->rgba8) return ZR_OK;
+        ARGCHK(c, v && idx && nv > 0 && ni > 0 && ni % 3 == 0);
+        for (uint32_t i = 0; i < ni; ++i) if (idx[i] >= nv) return zr_fail(c, ZR_ERR_ARG, "index out of range");
+        c->sky_mesh.v.assign(v, v + nv); c->sky_mesh.idx.assign(idx, idx + ni);
+        ZrSceneObject& o = c->sky_obj;
+        o.mesh = 0; o.instanced = false; o.n_inst = 1;
+        for (int t = 0; t < 7; ++t) o.texel[t] = 0xFFFFFFFFu;
+        o.bc_linear[0] = o.bc_linear[1] = o.bc_linear[2] = 1.0f;
+        int rc = upload_image(c, o.mem, tex->rgba8, tex->width, tex->height, true, &o.d_tex[0], &o.tex_w[0], &o.tex_h[0], &o.tex_levels[0]);   // sRGB by default, ZE:5860
+        if (rc) return rc;
+        HIPCHK(c, o.mem.alloc(&o.d_inst, 1));
+        zr_launch_instance_prep(nullptr, o.d_inst, 1, 0u, c->stream);
+        HIPCHK(c, zr_sync_all(c));
+        c->sky_set = true;
+        return ZR_OK;
+    });
 }
 
-static int zr_set_background_impl(zr_ctx* c, const zr_image* tex)
-{
-    if (!c) return ZR_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, zr_sync_all(c));
-    c->bg_mem.release(); c->d_bg = nullptr; c->bg_set = false;
-    if (!tex || !tex->rgba8) return ZR_OK;
-    int rc = upload_texture(c, c->bg_mem, tex, true, &c->d_bg, &c->bg_w, &c->bg_h, &c->bg_levels);
-    if (rc) return rc;
-    c->bg_set = true;
-    return ZR_OK;
-}
 extern "C" int zr_set_background(zr_ctx* c, const zr_image* tex)
 {
-    return zr_guard(c, [&]() { return zr_set_background_impl(c, tex); });
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, zr_sync_all(c));
+        c->bg_mem.release(); c->d_bg = nullptr; c->bg_set = false;
+        if (!tex || !tex->rgba8) return ZR_OK;
+        int rc = upload_image(c, c->bg_mem, tex->rgba8, tex->width, tex->height, true, &c->d_bg, &c->bg_w, &c->bg_h, &c->bg_levels);
+        if (rc) return rc;
+        c->bg_set = true;
+        return ZR_OK;
+    });
 }
 
 extern "C" int zr_set_sky_flags(zr_ctx* c, int sky, int bg)
 {
     if (!c) return ZR_ERR_ARG;
-    if ((sky != 0) != c->sky_enabled) c->scene_dirty = true;
-    c->sky_enabled = sky != 0; c->bg_enabled = bg != 0;
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        if ((sky != 0) != c->sky_enabled) c->scene_dirty = true;
+        c->sky_enabled = sky != 0; c->bg_enabled = bg != 0;
+        return ZR_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ cubemap
 
-static int zr_set_cubemap_impl(zr_ctx* c, const uint8_t* const faces[6], uint32_t dim)
-{
-    if (!c) return ZR_ERR_ARG;
-    static const uint8_t grey[4] = { 127, 127, 127, 255 };
-    if (!faces) dim = 1;
-    ARGCHK(c, dim > 0 && dim <= 16384);
-    if (faces) for (int f = 0; f < 6; ++f) ARGCHK(c, faces[f] != nullptr);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, zr_sync_all(c));
-    c->cube_mem.release();
-    memset(&c->cube, 0, sizeof c->cube);
-    uint32_t levels = 1; for (uint32_t d = dim; d > 1; d >>= 1) levels++;      // floor(log2(dim)) + 1, ZE:6887
-    if (levels > 16) return zr_fail(c, ZR_ERR_ARG, "cubemap too large");
-    std::vector<std::vector<uint8_t>> lv(levels);
-    const size_t fsz = (size_t)dim * dim * 4;
-    lv[0].resize(fsz * 6);
-    for (int f = 0; f < 6; ++f) { if (faces) memcpy(lv[0].data() + fsz * f, faces[f], fsz); else memcpy(lv[0].data() + fsz * f, grey, 4); }
-    uint32_t d = dim;
-    for (uint32_t l = 1; l < levels; ++l) {        // RHIGenerateMipmaps: vkCmdBlitImage LINEAR from level l-1 (2x2 box, linear light)
-        const uint32_t nd = d > 1 ? d >> 1 : 1;
-        lv[l].resize((size_t)nd * nd * 4 * 6);
-        for (int f = 0; f < 6; ++f) {
-            const uint8_t* src = lv[l - 1].data() + (size_t)d * d * 4 * f;
-            uint8_t* dst = lv[l].data() + (size_t)nd * nd * 4 * f;
-            for (uint32_t y = 0; y < nd; ++y) for (uint32_t x = 0; x < nd; ++x) {
-                const uint32_t x0 = 2 * x, x1 = (2 * x + 1 < d) ? 2 * x + 1 : d - 1, y0 = 2 * y, y1 = (2 * y + 1 < d) ? 2 * y + 1 : d - 1;
-                const uint8_t* p00 = src + ((size_t)y0 * d + x0) * 4; const uint8_t* p10 = src + ((size_t)y0 * d + x1) * 4;
-                const uint8_t* p01 = src + ((size_t)y1 * d + x0) * 4; const uint8_t* p11 = src + ((size_t)y1 * d + x1) * 4;
-                for (int ch = 0; ch < 3; ++ch) {
-                    const float a = (c->lut[p00[ch]] + c->lut[p10[ch]]) + (c->lut[p01[ch]] + c->lut[p11[ch]]);
-                    dst[((size_t)y * nd + x) * 4 + ch] = srgb_encode8(a * 0.25f);
-                }
-                const uint32_t al = (uint32_t)p00[3] + p10[3] + p01[3] + p11[3];
-                dst[((size_t)y * nd + x) * 4 + 3] = (uint8_t)((al + 2) >> 2);
-            }
-        }
-        d = nd;
-    }
-    for (uint32_t l = 0; l < levels; ++l) {
-        uint8_t* p = nullptr;
-        HIPCHK(c, upload(c->cube_mem, &p, lv[l]));
-        c->cube.levels[l] = p;
-    }
-    c->cube_dim = dim; c->cube_levels = levels;
-    c->view.LightsCount[3] = (int32_t)levels;       // CubemapMaxMips, ZE:4308
-    c->view_dirty = true;
-    return ZR_OK;
-}
 extern "C" int zr_set_cubemap(zr_ctx* c, const uint8_t* const faces[6], uint32_t dim)
 {
-    return zr_guard(c, [&]() { return zr_set_cubemap_impl(c, faces, dim); });
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        static const uint8_t grey[4] = { 127, 127, 127, 255 };
+        if (!faces) dim = 1;
+        ARGCHK(c, dim > 0 && dim <= 16384);
+        if (faces) for (int f = 0; f < 6; ++f) ARGCHK(c, faces[f] != nullptr);
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, zr_sync_all(c));
+        c->cube_mem.release();
+        memset(&c->cube, 0, sizeof c->cube);
+        uint32_t levels = 1; for (uint32_t d = dim; d > 1; d >>= 1) levels++;      // floor(log2(dim)) + 1, ZE:6887
+        if (levels > 16) return zr_fail(c, ZR_ERR_ARG, "cubemap too large");
+        std::vector<std::vector<uint8_t>> lv(levels);
+        const size_t fsz = (size_t)dim * dim * 4;
+        lv[0].resize(fsz * 6);
+        for (int f = 0; f < 6; ++f) { if (faces) memcpy(lv[0].data() + fsz * f, faces[f], fsz); else memcpy(lv[0].data() + fsz * f, grey, 4); }
+        uint32_t d = dim;
+        for (uint32_t l = 1; l < levels; ++l) {        // RHIGenerateMipmaps: vkCmdBlitImage LINEAR from level l-1 (2x2 box, linear light)
+            const uint32_t nd = d > 1 ? d >> 1 : 1;
+            lv[l].resize((size_t)nd * nd * 4 * 6);
+            for (int f = 0; f < 6; ++f) {
+                const uint8_t* src = lv[l - 1].data() + (size_t)d * d * 4 * f;
+                uint8_t* dst = lv[l].data() + (size_t)nd * nd * 4 * f;
+                for (uint32_t y = 0; y < nd; ++y) for (uint32_t x = 0; x < nd; ++x) {
+                    const uint32_t x0 = 2 * x, x1 = (2 * x + 1 < d) ? 2 * x + 1 : d - 1, y0 = 2 * y, y1 = (2 * y + 1 < d) ? 2 * y + 1 : d - 1;
+                    const uint8_t* p00 = src + ((size_t)y0 * d + x0) * 4; const uint8_t* p10 = src + ((size_t)y0 * d + x1) * 4;
+                    const uint8_t* p01 = src + ((size_t)y1 * d + x0) * 4; const uint8_t* p11 = src + ((size_t)y1 * d + x1) * 4;
+                    for (int ch = 0; ch < 3; ++ch) {
+                        const float a = (c->lut[p00[ch]] + c->lut[p10[ch]]) + (c->lut[p01[ch]] + c->lut[p11[ch]]);
+                        dst[((size_t)y * nd + x) * 4 + ch] = srgb_encode8(a * 0.25f);
+                    }
+                    const uint32_t al = (uint32_t)p00[3] + p10[3] + p01[3] + p11[3];
+                    dst[((size_t)y * nd + x) * 4 + 3] = (uint8_t)((al + 2) >> 2);
+                }
+            }
+            d = nd;
+        }
+        for (uint32_t l = 0; l < levels; ++l) {
+            uint8_t* p = nullptr;
+            HIPCHK(c, upload(c->cube_mem, &p, lv[l]));
+            c->cube.levels[l] = p;
+        }
+        c->cube_dim = dim; c->cube_levels = levels;
+        c->view.LightsCount[3] = (int32_t)levels;       // CubemapMaxMips, ZE:4308
+        c->view_dirty = true;
+        return ZR_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ uniforms
@@ -925,99 +909,112 @@ extern "C" int zr_update_uniforms(zr_ctx* c, const zr_camera* cam, const XkLight
                                   uint32_t n_point, const XkLight* spot, uint32_t n_spot, float roll_stage, float roll_light, float time)
 {
     if (!c) return ZR_ERR_ARG;
-    ARGCHK(c, cam && n_dir <= XK_MAX_DIRECTIONAL_LIGHTS_NUM && n_point <= XK_MAX_POINT_LIGHTS_NUM && n_spot <= XK_MAX_SPOT_LIGHTS_NUM);
-    ARGCHK(c, (n_dir == 0 || dir) && (n_point == 0 || point) && (n_spot == 0 || spot));
-    // both geometry passes' kernel arguments are fixed when a frame begins (zr_render_shadow / zr_render_geometry): uniforms set between the
-    // stages of a frame would reach its lighting pass only
-    if (c->stage != 0) return zr_fail(c, ZR_ERR_STATE, "zr_update_uniforms between the stages of a frame (finish it with zr_render_lighting first)");
-    XkView* V = &c->view;
-    c->view_dirty = true;
-    for (uint32_t i = 0; i < n_dir; ++i) V->DirectionalLights[i] = dir[i];
-    for (uint32_t i = 0; i < n_point; ++i) V->PointLights[i] = point[i];
-    for (uint32_t i = 0; i < n_spot; ++i) V->SpotLights[i] = spot[i];
-    V->LightsCount[0] = (int32_t)n_dir; V->LightsCount[1] = (int32_t)n_point; V->LightsCount[2] = (int32_t)n_spot;
-    V->LightsCount[3] = (int32_t)c->cube_levels;
+    return zr_guard(c, [&]() -> int {
+        ARGCHK(c, cam && n_dir <= XK_MAX_DIRECTIONAL_LIGHTS_NUM && n_point <= XK_MAX_POINT_LIGHTS_NUM && n_spot <= XK_MAX_SPOT_LIGHTS_NUM);
+        ARGCHK(c, (n_dir == 0 || dir) && (n_point == 0 || point) && (n_spot == 0 || spot));
+        // both geometry passes' kernel arguments are fixed when a frame begins (zr_render_shadow / zr_render_geometry): uniforms set between the
+        // stages of a frame would reach its lighting pass only
+        if (c->stage != 0) return zr_fail(c, ZR_ERR_STATE, "zr_update_uniforms between the stages of a frame (finish it with zr_render_lighting first)");
+        XkView* V = &c->view;
+        c->view_dirty = true;
+        for (uint32_t i = 0; i < n_dir; ++i) V->DirectionalLights[i] = dir[i];
+        for (uint32_t i = 0; i < n_point; ++i) V->PointLights[i] = point[i];
+        for (uint32_t i = 0; i < n_spot; ++i) V->SpotLights[i] = spot[i];
+        V->LightsCount[0] = (int32_t)n_dir; V->LightsCount[1] = (int32_t)n_point; V->LightsCount[2] = (int32_t)n_spot;
+        V->LightsCount[3] = (int32_t)c->cube_levels;
 
-    const zf3 pos = zr3(cam->Position[0], cam->Position[1], cam->Position[2]);
-    const zf3 look = zr3(cam->Lookat[0], cam->Lookat[1], cam->Lookat[2]);
-    const zf3 up = zr3(0.0f, 0.0f, 1.0f);
-    const zf3 lightPos = zr3(V->DirectionalLights[0].Position[0], V->DirectionalLights[0].Position[1], V->DirectionalLights[0].Position[2]);
-    float l2w[16], sview[16], sproj[16], cview[16], cproj[16];
-    rotate_z(roll_stage, l2w);
-    look_at_rh(lightPos, zr3(0.0f, 0.0f, 0.0f), up, sview);
-    perspective_rh_zo(radiansf(cam->FOV), 1.0f, cam->zNear, cam->zFar, sproj);
-    sproj[5] *= -1.0f;
-    look_at_rh(pos, look, up, cview);
-    perspective_rh_zo(radiansf(cam->FOV), (float)c->W / (float)c->H, cam->zNear, cam->zFar, cproj);
-    memcpy(c->cam.Model, l2w, 64); memcpy(c->cam.View, cview, 64); memcpy(c->cam.Proj, cproj, 64);
-    c->cam.Proj[5] *= -1.0f;
-    zr_mat4_mul(cproj, cview, V->ViewProjSpace);
-    zr_mat4_mul(sproj, sview, V->ShadowmapSpace);
-    memcpy(V->LocalToWorld, l2w, 64);
-    V->CameraInfo[0] = pos.x; V->CameraInfo[1] = pos.y; V->CameraInfo[2] = pos.z; V->CameraInfo[3] = cam->FOV;
-    V->ViewportInfo[0] = (float)c->W; V->ViewportInfo[1] = (float)c->H; V->ViewportInfo[2] = 0.0f; V->ViewportInfo[3] = 0.0f;
-    const uint32_t N = n_point;
-    for (uint32_t i = 0; i < N; ++i) {           // point lights ride a spiral, JSON positions are overwritten (ZE:4637-4646)
-        const float deg = ((float)i / (float)N) * 360.0f - roll_light * 100.0f;
-        const float distance = ((float)i / (float)N) * 5.0f + 2.5f;
-        V->PointLights[i].Position[0] = sinf(radiansf(deg)) * distance;
-        V->PointLights[i].Position[1] = cosf(radiansf(deg)) * distance;
-        V->PointLights[i].Position[2] = 1.5f;
-        V->PointLights[i].Position[3] = 1.0f;
-    }
-    V->Time = time; V->zNear = cam->zNear; V->zFar = cam->zFar;
-    memcpy(c->shadow.Model, l2w, 64); memcpy(c->shadow.View, sview, 64); memcpy(c->shadow.Proj, sproj, 64);
-    c->frame_valid = true;
-    return ZR_OK;
+        const zf3 pos = zr3(cam->Position[0], cam->Position[1], cam->Position[2]);
+        const zf3 look = zr3(cam->Lookat[0], cam->Lookat[1], cam->Lookat[2]);
+        const zf3 up = zr3(0.0f, 0.0f, 1.0f);
+        const zf3 lightPos = zr3(V->DirectionalLights[0].Position[0], V->DirectionalLights[0].Position[1], V->DirectionalLights[0].Position[2]);
+        float l2w[16], sview[16], sproj[16], cview[16], cproj[16];
+        rotate_z(roll_stage, l2w);
+        look_at_rh(lightPos, zr3(0.0f, 0.0f, 0.0f), up, sview);
+        perspective_rh_zo(radiansf(cam->FOV), 1.0f, cam->zNear, cam->zFar, sproj);
+        sproj[5] *= -1.0f;
+        look_at_rh(pos, look, up, cview);
+        perspective_rh_zo(radiansf(cam->FOV), (float)c->W / (float)c->H, cam->zNear, cam->zFar, cproj);
+        memcpy(c->cam.Model, l2w, 64); memcpy(c->cam.View, cview, 64); memcpy(c->cam.Proj, cproj, 64);
+        c->cam.Proj[5] *= -1.0f;
+        zr_mat4_mul(cproj, cview, V->ViewProjSpace);
+        zr_mat4_mul(sproj, sview, V->ShadowmapSpace);
+        memcpy(V->LocalToWorld, l2w, 64);
+        V->CameraInfo[0] = pos.x; V->CameraInfo[1] = pos.y; V->CameraInfo[2] = pos.z; V->CameraInfo[3] = cam->FOV;
+        V->ViewportInfo[0] = (float)c->W; V->ViewportInfo[1] = (float)c->H; V->ViewportInfo[2] = 0.0f; V->ViewportInfo[3] = 0.0f;
+        const uint32_t N = n_point;
+        for (uint32_t i = 0; i < N; ++i) {           // point lights ride a spiral, JSON positions are overwritten (ZE:4637-4646)
+            const float deg = ((float)i / (float)N) * 360.0f - roll_light * 100.0f;
+            const float distance = ((float)i / (float)N) * 5.0f + 2.5f;
+            V->PointLights[i].Position[0] = sinf(radiansf(deg)) * distance;
+            V->PointLights[i].Position[1] = cosf(radiansf(deg)) * distance;
+            V->PointLights[i].Position[2] = 1.5f;
+            V->PointLights[i].Position[3] = 1.0f;
+        }
+        V->Time = time; V->zNear = cam->zNear; V->zFar = cam->zFar;
+        memcpy(c->shadow.Model, l2w, 64); memcpy(c->shadow.View, sview, 64); memcpy(c->shadow.Proj, sproj, 64);
+        c->frame_valid = true;
+        return ZR_OK;
+    });
 }
 
 extern "C" int zr_set_frame(zr_ctx* c, const XkUniformBufferMVP* cam, const XkUniformBufferMVP* sh, const XkView* v)
 {
     if (!c) return ZR_ERR_ARG;
-    ARGCHK(c, cam && sh && v);
-    ARGCHK(c, v->LightsCount[0] >= 0 && v->LightsCount[0] <= XK_MAX_DIRECTIONAL_LIGHTS_NUM && v->LightsCount[1] >= 0 &&
-              v->LightsCount[1] <= XK_MAX_POINT_LIGHTS_NUM);
-    if (c->stage != 0) return zr_fail(c, ZR_ERR_STATE, "zr_set_frame between the stages of a frame (finish it with zr_render_lighting first)");
-    c->cam = *cam; c->shadow = *sh; c->view = *v; c->view_dirty = true;
-    c->frame_valid = true;
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        ARGCHK(c, cam && sh && v);
+        ARGCHK(c, v->LightsCount[0] >= 0 && v->LightsCount[0] <= XK_MAX_DIRECTIONAL_LIGHTS_NUM && v->LightsCount[1] >= 0 &&
+                  v->LightsCount[1] <= XK_MAX_POINT_LIGHTS_NUM);
+        if (c->stage != 0) return zr_fail(c, ZR_ERR_STATE, "zr_set_frame between the stages of a frame (finish it with zr_render_lighting first)");
+        c->cam = *cam; c->shadow = *sh; c->view = *v; c->view_dirty = true;
+        c->frame_valid = true;
+        return ZR_OK;
+    });
 }
 extern "C" int zr_get_frame(zr_ctx* c, XkUniformBufferMVP* cam, XkUniformBufferMVP* sh, XkView* v)
 {
     if (!c) return ZR_ERR_ARG;
-    if (cam) *cam = c->cam;
-    if (sh) *sh = c->shadow;
-    if (v) *v = c->view;
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        if (cam) *cam = c->cam;
+        if (sh) *sh = c->shadow;
+        if (v) *v = c->view;
+        return ZR_OK;
+    });
 }
-extern "C" int zr_set_debug_view(zr_ctx* c, uint32_t s) { if (!c) return ZR_ERR_ARG; c->debug_view = s; return ZR_OK; }
+extern "C" int zr_set_debug_view(zr_ctx* c, uint32_t s) { if (!c) return ZR_ERR_ARG; return zr_guard(c, [&]() -> int { c->debug_view = s; return ZR_OK; }); }
 
-// Forward variant (SH/Base.frag): the resolve additionally keeps each pixel's winning primitive id (one more plane per GBuffer copy,
-// allocated on first use), and the lighting step runs k_forward on those instead of k_lighting on the GBuffer.
-static int zr_set_shading_impl(zr_ctx* c, uint32_t mode)
+// The winner planes: one per GBuffer copy, made on first use (every pixel "none"; pixels of other ranks' tiles stay so).  The resolve keeps
+// each pixel's winning primitive id in them while the forward variant shades from them or id capture reads them (`what`: the caller, for the message).
+static int set_winner_planes(zr_ctx* c, bool forward, bool id_capture, const char* what)
 {
-    if (!c) return ZR_ERR_ARG;
-    if (mode != ZR_SHADING_DEFERRED && mode != ZR_SHADING_FORWARD) return zr_fail(c, ZR_ERR_ARG, "zr_set_shading: unknown mode");
-    if (c->stage != 0) return zr_fail(c, ZR_ERR_STATE, "zr_set_shading between the stages of a frame");
-    if (mode == c->shading) return ZR_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    // frames in flight read / write the planes this call swaps in or out
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->cam_s) HIPCHK(c, hipStreamSynchronize(c->cam_s));
     const size_t n = (size_t)c->W * c->H;
-    for (int b = 0; b < 2; ++b) {
-        if (mode == ZR_SHADING_FORWARD && !c->d_prim_b[b]) {
-            if (c->own.alloc(&c->d_prim_b[b], n) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "zr_set_shading: out of device memory");
-            HIPCHK(c, zr_fill_sync({ { c->d_prim_b[b], 0xFF, n * 4 } }));
+    for (FrameCopy& F : c->fc) {
+        if ((forward || id_capture) && !F.prim_plane) {
+            if (c->own.alloc(&F.prim_plane, n) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, std::string(what) + ": out of device memory");
+            HIPCHK(c, zr_fill_sync({ { F.prim_plane, 0xFF, n * 4 } }));
         }
-        c->Gb[b].prim = (mode == ZR_SHADING_FORWARD || c->id_capture) ? c->d_prim_b[b] : nullptr;      // (id capture: zr_set_id_capture)
+        F.G.prim = (forward || id_capture) ? F.prim_plane : nullptr;
     }
-    c->shading = mode;
     return ZR_OK;
 }
+
+// Forward variant (SH/Base.frag): the resolve additionally keeps each pixel's winning primitive id (set_winner_planes), and the lighting
+// step runs k_forward on those instead of k_lighting on the GBuffer.
 extern "C" int zr_set_shading(zr_ctx* c, uint32_t mode)
 {
-    return zr_guard(c, [&]() { return zr_set_shading_impl(c, mode); });
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        if (mode != ZR_SHADING_DEFERRED && mode != ZR_SHADING_FORWARD) return zr_fail(c, ZR_ERR_ARG, "zr_set_shading: unknown mode");
+        if (c->stage != 0) return zr_fail(c, ZR_ERR_STATE, "zr_set_shading between the stages of a frame");
+        if (mode == c->shading) return ZR_OK;
+        HIPCHK(c, hipSetDevice(c->device));
+        // frames in flight read / write the planes this call swaps in or out
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->cam_s) HIPCHK(c, hipStreamSynchronize(c->cam_s));
+        const int rc = set_winner_planes(c, mode == ZR_SHADING_FORWARD, c->id_capture, "zr_set_shading");
+        if (rc) return rc;
+        c->shading = mode;
+        return ZR_OK;
+    });
 }
 
 static bool finite16(const float* m) { for (int i = 0; i < 16; ++i) if (!std::isfinite(m[i])) return false; return true; }
@@ -1109,7 +1106,7 @@ static bool build_pass(const zr_ctx* c, const XkUniformBufferMVP& u, int mode, Z
 
 // ------------------------------------------------------------------------------------------------ the frame
 
-static inline float* shadow_buf(zr_ctx* c) { return c->d_shadow_ext ? c->d_shadow_ext : c->d_shadow; }
+static inline float* shadow_buf(zr_ctx* c) { return c->d_shadow_ext ? c->d_shadow_ext : c->fc[c->fcur].shadow; }
 
 // count -> scan -> fill of the shadow pass's meshlet bins, from the cull's rects.  Z.phase 1 (occlusion culling): only the
 // meshlet-instances flagged last frame are binned.
@@ -1213,15 +1210,15 @@ static int frame_begin(zr_ctx* c, hipStream_t s)
     if (c->view.LightsCount[3] != (int32_t)c->cube_levels) { c->view.LightsCount[3] = (int32_t)c->cube_levels; c->view_dirty = true; }
     c->ids_frame = false; c->ids_this = c->id_capture;      // (the frame enqueued last is about to be this one)
     if (c->id_capture) { rc = ids_prepare(c); if (rc) return rc; }
-    const int par = (int)(c->frame_no & 1u);
-    c->G = c->Gb[par]; c->d_shadow = c->d_shadow_b[par]; c->d_view = c->d_view_b[par]; c->d_empty_rgba = c->d_empty_b[par];
+    c->fcur = (int)(c->frame_no & 1u);
+    FrameCopy& F = c->fc[c->fcur];
     // (two lanes: this frame's copies of the double-buffered resources were last read by the lighting pass of two frames ago, on the
     // host's stream.  Nothing else ties the lanes together here: the shadow pipeline keeps statistics of its own)
     if (s != c->stream && c->frame_no >= 2) HIPCHK(c, hipStreamWaitEvent(s, c->ev_end[(c->frame_no - 2) % zr_ctx::END_RING], 0));
     // ... and by an identity census enqueued against them since (zr_instance_coverage_async, on the host's stream)
-    if (c->ids_wait[par]) { if (s != c->stream) HIPCHK(c, hipStreamWaitEvent(s, c->ev_ids[par], 0)); c->ids_wait[par] = false; }
+    if (F.ids_wait) { if (s != c->stream) HIPCHK(c, hipStreamWaitEvent(s, F.ev_ids, 0)); F.ids_wait = false; }
     // this frame's draw table; instance updates since the last frame of this parity go into its planes (zr_instances_host.cpp)
-    rc = zr_instances_frame(c, s, par);
+    rc = zr_instances_frame(c, s, c->fcur);
     if (rc) return rc;
     c->timing_now = c->timing_interval != 0 && c->frame_no % c->timing_interval == 0;     // pass events cost ~6 us of stream bubble each
     hipEvent_t* ev = c->timing_now ? c->evr[c->sample_no % zr_ctx::EV_RING] : nullptr;
@@ -1240,7 +1237,7 @@ static int frame_begin(zr_ctx* c, hipStream_t s)
     }
     const XkView* src = nullptr;
     uint32_t k = 0;
-    if (c->view_uploaded[par] != c->view_version) {        // pinned ring slot: reused only after the kernel that read it last has run
+    if (F.view_uploaded != c->view_version) {        // pinned ring slot: reused only after the kernel that read it last has run
         k = c->view_slot++ % zr_ctx::VIEW_RING;
         HIPCHK(c, hipEventSynchronize(c->view_ev[k]));
         memcpy(&c->h_view_ring[k], &c->view, sizeof(XkView));
@@ -1250,8 +1247,8 @@ static int frame_begin(zr_ctx* c, hipStream_t s)
     // zeroes the camera lane's statistics (the sticky overflow latch survives) and - when the camera list is rebuilt - its length; uploads
     // XkView.  The SHADOW list's length lives in the shadow pipeline's block and is reset on that pipeline's own stream (shadow_pass):
     // the previous frame's shadow pipeline may still be walking it while this kernel runs on the camera lane.
-    zr_launch_frame_begin(c->d_stats, src, c->d_view, rebuild & 2u, s);
-    if (src) { HIPCHK(c, hipEventRecord(c->view_ev[k], s)); c->view_uploaded[par] = c->view_version; }
+    zr_launch_frame_begin(c->d_stats, src, F.view, rebuild & 2u, s);
+    if (src) { HIPCHK(c, hipEventRecord(c->view_ev[k], s)); F.view_uploaded = c->view_version; }
     return ZR_OK;
 }
 
@@ -1262,9 +1259,9 @@ static int shadow_pass(zr_ctx* c, hipStream_t s)
     const ZrPass& P = c->pass[0];      // (built by frame_begin)
     c->last_work[0] = P.n_work;
     // clear depth 1.0 (ZE:3248): the previous frame's lighting pass already did it for the internal double-buffered map
-    const int spar = (int)(c->frame_no & 1u);
-    if (c->d_shadow_ext || !c->shadow_cleared[spar]) zr_launch_fill32((uint32_t*)shadow_buf(c), 0x3F800000u, (size_t)c->SD * c->SD, s);
-    c->shadow_cleared[spar] = false;
+    FrameCopy& F = c->fc[c->fcur];
+    if (c->d_shadow_ext || !F.shadow_cleared) zr_launch_fill32((uint32_t*)shadow_buf(c), 0x3F800000u, (size_t)c->SD * c->SD, s);
+    F.shadow_cleared = false;
     ZrHiz Z; memset(&Z, 0, sizeof Z);
     // occlusion culling (k_shadow_occlusion): the first launch draws what was not hidden last frame, the rest is tested against the map.
     // It pays when casters pile up behind each other: the test + the late launch cost what a quarter of config 3's rasteriser does
@@ -1335,15 +1332,14 @@ static int gbuffer_pass(zr_ctx* c, hipStream_t s)
         if (ev) { HIPCHK(c, hipEventRecord(ev[4], s)); HIPCHK(c, hipEventRecord(ev[5], s)); }
     }
     {   // the overlay plane (skydome pixels) is written only when a skydome is drawn, or once more to wipe one that was
-        const int par = (int)(c->frame_no & 1u);
         const bool sky = c->sky_set && c->sky_enabled;
-        P.write_overlay = (sky || c->overlay_dirty[par]) ? 1u : 0u;
-        c->overlay_dirty[par] = sky;
+        P.write_overlay = (sky || c->fc[c->fcur].overlay_dirty) ? 1u : 0u;
+        c->fc[c->fcur].overlay_dirty = sky;
         P.sky_keys = nullptr; P.sky_object = c->sky_object;
         if (sky && c->d_sky_keys) { zr_launch_sky_tiles(P, c->d_objs, c->d_owned, c->n_owned, c->d_sky_keys, s); P.sky_keys = c->d_sky_keys; }
     }
     if (ev) HIPCHK(c, hipEventRecord(ev[6], s));
-    zr_launch_resolve_gbuffer(P, c->d_objs, c->d_owned, c->n_owned, c->d_vis, c->G, c->d_lut, c->d_unorm_lut, Z.vis_now, c->d_stats, s, vis_mark);
+    zr_launch_resolve_gbuffer(P, c->d_objs, c->d_owned, c->n_owned, c->d_vis, c->fc[c->fcur].G, c->d_lut, c->d_unorm_lut, Z.vis_now, c->d_stats, s, vis_mark);
     c->vis_mark_prev = vis_mark;
     if (ev) HIPCHK(c, hipEventRecord(ev[7], s));
     if (P.n_work != 0) {     // the next frame's buckets, from this frame's counts: nothing on this lane waits for it
@@ -1355,29 +1351,29 @@ static int gbuffer_pass(zr_ctx* c, hipStream_t s)
     return ZR_OK;
 }
 
-static int zr_render_shadow_impl(zr_ctx* c)
-{
-    if (!c) return ZR_ERR_ARG;
-    c->camera_on_lane = false;
-    int rc = frame_begin(c, c->stream);
-    if (rc == ZR_OK) rc = shadow_pass(c, c->stream);
-    if (rc == ZR_OK) HIPCHK(c, hipEventRecord(c->ev_join, c->stream));
-    if (rc == ZR_OK) c->stage = 1;
-    return rc;
-}
 extern "C" int zr_render_shadow(zr_ctx* c)
 {
-    return zr_guard(c, [&]() { return zr_render_shadow_impl(c); });
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        c->camera_on_lane = false;
+        int rc = frame_begin(c, c->stream);
+        if (rc == ZR_OK) rc = shadow_pass(c, c->stream);
+        if (rc == ZR_OK) HIPCHK(c, hipEventRecord(c->ev_join, c->stream));
+        if (rc == ZR_OK) c->stage = 1;
+        return rc;
+    });
 }
 
 extern "C" int zr_render_gbuffer(zr_ctx* c)
 {
     if (!c) return ZR_ERR_ARG;
-    if (c->stage != 1) return zr_fail(c, ZR_ERR_STATE, "zr_render_gbuffer out of order");
-    HIPCHK(c, hipSetDevice(c->device));
-    const int rc = gbuffer_pass(c, c->stream);
-    if (rc == ZR_OK) c->stage = 2;
-    return rc;
+    return zr_guard(c, [&]() -> int {
+        if (c->stage != 1) return zr_fail(c, ZR_ERR_STATE, "zr_render_gbuffer out of order");
+        HIPCHK(c, hipSetDevice(c->device));
+        const int rc = gbuffer_pass(c, c->stream);
+        if (rc == ZR_OK) c->stage = 2;
+        return rc;
+    });
 }
 
 // Both geometry passes of a frame.  Two lanes (unless ZR_FLAG_SERIAL_PASSES): the camera pipeline on cam_s; the shadow pipeline on
@@ -1411,21 +1407,19 @@ static int geometry_passes(zr_ctx* c)
     return rc;
 }
 
-static int zr_render_geometry_impl(zr_ctx* c)
-{
-    if (!c) return ZR_ERR_ARG;
-    return geometry_passes(c);
-}
 extern "C" int zr_render_geometry(zr_ctx* c)
 {
-    return zr_guard(c, [&]() { return zr_render_geometry_impl(c); });
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int { return geometry_passes(c); });
 }
 
 extern "C" int zr_stream_wait_shadow(zr_ctx* c, void* hip_stream)
 {
     if (!c) return ZR_ERR_ARG;
-    HIPCHK(c, hipStreamWaitEvent((hipStream_t)hip_stream, c->ev_join, 0));
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        HIPCHK(c, hipStreamWaitEvent((hipStream_t)hip_stream, c->ev_join, 0));
+        return ZR_OK;
+    });
 }
 
 static void light_params(const zr_ctx* c, ZrLightParams* Lp)
@@ -1438,7 +1432,7 @@ static void light_params(const zr_ctx* c, ZrLightParams* Lp)
     L.packed_out = (c->cfg.tile_world > 1 || (c->cfg.flags & ZR_FLAG_PACKED_TILES)) ? 1u : 0u;
     L.debug_skip = c->env_skip_light;
     L.bg_enabled = (c->bg_set && c->bg_enabled) ? 1u : 0u;
-    L.has_overlay = c->overlay_dirty[c->frame_no & 1u] ? 1u : 0u;      // set by this frame's gbuffer pass
+    L.has_overlay = c->fc[c->fcur].overlay_dirty ? 1u : 0u;     // set by this frame's gbuffer pass
     { const int32_t np = c->view.LightsCount[1]; L.light_list = (np >= c->env_light_list_min && np <= XK_MAX_POINT_LIGHTS_NUM) ? 1u : 0u; }
     L.bg.data = c->d_bg; L.bg.w = c->bg_w; L.bg.h = c->bg_h; L.bg.levels = c->bg_levels; L.bg._pad = 0;
 }
@@ -1452,7 +1446,7 @@ static int empty_pixel_pass(zr_ctx* c, hipStream_t s)
     if (c->debug_view == 6u || c->env_no_empty_px || c->shading == ZR_SHADING_FORWARD) return ZR_OK;      // (forward: an empty pixel is the clear colour)
     ZrLightParams L; light_params(c, &L);
     L.W = 1; L.H = 1; L.tiles_x = 1; L.packed_out = 0; L.bg_enabled = 0;
-    zr_launch_lighting(L, c->d_view, c->d_sowned, 1, c->Gclear, shadow_buf(c), c->cube, c->d_lut, c->d_unorm_lut, c->d_empty_rgba, s);
+    zr_launch_lighting(L, c->fc[c->fcur].view, c->d_sowned, 1, c->Gclear, shadow_buf(c), c->cube, c->d_lut, c->d_unorm_lut, c->fc[c->fcur].empty_rgba, s);
     HIPCHK(c, hipGetLastError());
     c->empty_ready = true;
     return ZR_OK;
@@ -1462,20 +1456,21 @@ static int lighting_pass(zr_ctx* c, hipStream_t s)
 {
     hipEvent_t* ev = c->timing_now ? c->evr[c->sample_no % zr_ctx::EV_RING] : nullptr;
     ZrLightParams L; light_params(c, &L);
-    L.empty_rgba = c->empty_ready ? c->d_empty_rgba : nullptr;
+    const FrameCopy& F = c->fc[c->fcur];
+    L.empty_rgba = c->empty_ready ? F.empty_rgba : nullptr;
     // The next frame's shadow pass follows on this stream and rasterises into the OTHER copy of the map, which nothing reads or
     // writes while this pass runs: clear it here.
-    const int npar = (int)((c->frame_no + 1u) & 1u);
-    if (c->n_owned && s == c->stream) { L.clear_next = (uint32_t*)c->d_shadow_b[npar]; L.clear_n = c->SD * c->SD; c->shadow_cleared[npar] = true; }
+    FrameCopy& next = c->fc[c->fcur ^ 1];
+    if (c->n_owned && s == c->stream) { L.clear_next = (uint32_t*)next.shadow; L.clear_n = c->SD * c->SD; next.shadow_cleared = true; }
     uint32_t* const frame_out = L.packed_out ? (c->d_tiles_ext ? c->d_tiles_ext : c->d_tiles) : c->d_color;
     if (c->shading == ZR_SHADING_FORWARD) {
         // Base.frag over the winners the resolve recorded, with this frame's camera block (frame_begin built it; the overlay fields play no part)
         if (L.clear_next) { zr_launch_fill32(L.clear_next, 0x3F800000u, L.clear_n, s); L.clear_next = nullptr; }
-        zr_launch_forward(c->pass[1], L, c->d_view, c->d_objs, c->d_owned, c->n_owned, c->G, shadow_buf(c), c->cube, c->d_lut, c->d_unorm_lut, frame_out, s);
+        zr_launch_forward(c->pass[1], L, F.view, c->d_objs, c->d_owned, c->n_owned, F.G, shadow_buf(c), c->cube, c->d_lut, c->d_unorm_lut, frame_out, s);
     } else {
-        zr_launch_lighting(L, c->d_view, c->d_owned, c->n_owned, c->G, shadow_buf(c), c->cube, c->d_lut, c->d_unorm_lut, frame_out, s);
+        zr_launch_lighting(L, F.view, c->d_owned, c->n_owned, F.G, shadow_buf(c), c->cube, c->d_lut, c->d_unorm_lut, frame_out, s);
         if (c->debug_view == 9u)        // GBufferVis mosaic over the lit frame (needs the whole GBuffer: single-rank contexts only)
-            zr_launch_gbuffer_vis(L, c->d_view, c->G, shadow_buf(c), c->cube, c->d_lut, c->d_color, s);
+            zr_launch_gbuffer_vis(L, F.view, F.G, shadow_buf(c), c->cube, c->d_lut, c->d_color, s);
     }
     if (ev) HIPCHK(c, hipEventRecord(ev[8], s));
     HIPCHK(c, hipEventRecord(c->ev_end[c->frame_no % zr_ctx::END_RING], s));      // this frame's GBuffer / shadow map / uniforms copies are free again
@@ -1489,15 +1484,17 @@ static int lighting_pass(zr_ctx* c, hipStream_t s)
 extern "C" int zr_render_lighting(zr_ctx* c)
 {
     if (!c) return ZR_ERR_ARG;
-    if (c->stage != 2) return zr_fail(c, ZR_ERR_STATE, "zr_render_lighting out of order");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t ls = c->stream;
-    // The one wait of the host's stream per frame: the camera lane's GBuffer - and, ahead of it on that lane, this frame's k_frame_begin,
-    // whose uniforms the empty-pixel pass below reads (the shadow pipeline before it needed nothing of them and did not wait).
-    if (c->camera_on_lane) HIPCHK(c, hipStreamWaitEvent(ls, c->ev_cam, 0));
-    int rc = empty_pixel_pass(c, ls);              // the shadow map (possibly reduced over ranks by the host) is final only now
-    if (rc == ZR_OK) rc = lighting_pass(c, ls);
-    return rc;
+    return zr_guard(c, [&]() -> int {
+        if (c->stage != 2) return zr_fail(c, ZR_ERR_STATE, "zr_render_lighting out of order");
+        HIPCHK(c, hipSetDevice(c->device));
+        hipStream_t ls = c->stream;
+        // The one wait of the host's stream per frame: the camera lane's GBuffer - and, ahead of it on that lane, this frame's k_frame_begin,
+        // whose uniforms the empty-pixel pass below reads (the shadow pipeline before it needed nothing of them and did not wait).
+        if (c->camera_on_lane) HIPCHK(c, hipStreamWaitEvent(ls, c->ev_cam, 0));
+        int rc = empty_pixel_pass(c, ls);              // the shadow map (possibly reduced over ranks by the host) is final only now
+        if (rc == ZR_OK) rc = lighting_pass(c, ls);
+        return rc;
+    });
 }
 
 // RecordCommandBuffer (ZE:3160-3744) + vkQueueSubmit (ZE:2014): shadow -> deferred scene -> deferred lighting, with two
@@ -1506,19 +1503,17 @@ extern "C" int zr_render_lighting(zr_ctx* c)
 // frame's lighting.  zr_render therefore runs two lanes: the camera pipeline on the library's high-priority stream cam_s, and
 // shadow pipeline -> lighting on the host's stream.  Whatever the host enqueues on its stream after zr_render is ordered after
 // the finished frame, as before.  ZR_FLAG_SERIAL_PASSES keeps everything on the one stream, as the staged entry points do.
-static int zr_render_impl(zr_ctx* c)
-{
-    if (!c) return ZR_ERR_ARG;
-    c->in_render = true;
-    int rc = geometry_passes(c);
-    if (rc == ZR_OK) rc = zr_render_lighting(c);
-    c->in_render = false;
-    if (rc != ZR_OK) c->stage = 0;
-    return rc;
-}
 extern "C" int zr_render(zr_ctx* c)
 {
-    return zr_guard(c, [&]() { return zr_render_impl(c); });
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        c->in_render = true;
+        int rc = geometry_passes(c);
+        if (rc == ZR_OK) rc = zr_render_lighting(c);
+        c->in_render = false;
+        if (rc != ZR_OK) c->stage = 0;
+        return rc;
+    });
 }
 
 // Multi-GPU shadow pass: this context draws instances i with i % world == rank (non-instanced draws count as instance 0).
@@ -1526,10 +1521,12 @@ extern "C" int zr_render(zr_ctx* c)
 extern "C" int zr_set_shadow_partition(zr_ctx* c, uint32_t rank, uint32_t world)
 {
     if (!c) return ZR_ERR_ARG;
-    ARGCHK(c, world >= 1 && rank < world);
-    if (world > 1 && c->stile_world > 1) return zr_fail(c, ZR_ERR_STATE, "zr_set_shadow_partition: the map is already owned by tiles (zr_set_shadow_tiles)");
-    c->shadow_rank = rank; c->shadow_world = world;
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        ARGCHK(c, world >= 1 && rank < world);
+        if (world > 1 && c->stile_world > 1) return zr_fail(c, ZR_ERR_STATE, "zr_set_shadow_partition: the map is already owned by tiles (zr_set_shadow_tiles)");
+        c->shadow_rank = rank; c->shadow_world = world;
+        return ZR_OK;
+    });
 }
 
 // Multi-GPU shadow pass, second form: the MAP is owned by light-space super-tiles exactly as the frame is owned by screen super-tiles
@@ -1537,158 +1534,167 @@ extern "C" int zr_set_shadow_partition(zr_ctx* c, uint32_t rank, uint32_t world)
 // (rank-local work list, instance- and meshlet-level rejects before any vertex work) - drawn whole, so its owned tiles are bit for
 // bit the single-GPU map's - and the ranks exchange their tiles with ONE all-gather: zr_shadow_pack -> all-gather -> zr_shadow_unpack.
 // No reduction: every texel has one owner.  rank 0 / world 1 = the whole map (default).
-static int zr_set_shadow_tiles_impl(zr_ctx* c, uint32_t rank, uint32_t world)
-{
-    if (!c) return ZR_ERR_ARG;
-    ARGCHK(c, world >= 1 && rank < world);
-    if (c->stage != 0) return zr_fail(c, ZR_ERR_STATE, "zr_set_shadow_tiles between the stages of a frame");
-    if (world > 1 && c->shadow_world > 1) return zr_fail(c, ZR_ERR_STATE, "zr_set_shadow_tiles: the casters are already split by instance (zr_set_shadow_partition)");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, zr_sync_all(c));
-    c->stile_mem.release(); c->d_sowned_rank = c->d_stile_map = nullptr;
-    c->stile_rank = 0; c->stile_world = 1; c->s_slots_per_rank = c->sn_tiles; c->n_sowned_rank = 0;
-    c->list_valid[0] = false;
-    if (world == 1) return ZR_OK;
-    std::vector<uint32_t> owned, map(c->sn_tiles), counts(world, 0u);
-    for (uint32_t t = 0; t < c->sn_tiles; ++t) {
-        const uint32_t o = zr_tile_owner(t % c->stiles_x, t / c->stiles_x, world);
-        map[t] = counts[o]++;
-        if (o == rank) owned.push_back(t);
-    }
-    uint32_t spr = 0;
-    for (uint32_t n : counts) spr = std::max(spr, n);
-    for (uint32_t t = 0; t < c->sn_tiles; ++t) map[t] += zr_tile_owner(t % c->stiles_x, t / c->stiles_x, world) * spr;
-    HIPCHK(c, upload(c->stile_mem, &c->d_sowned_rank, owned)); HIPCHK(c, upload(c->stile_mem, &c->d_stile_map, map));
-    c->stile_rank = rank; c->stile_world = world; c->s_slots_per_rank = spr; c->n_sowned_rank = (uint32_t)owned.size();
-    return ZR_OK;
-}
 extern "C" int zr_set_shadow_tiles(zr_ctx* c, uint32_t rank, uint32_t world)
 {
-    return zr_guard(c, [&]() { return zr_set_shadow_tiles_impl(c, rank, world); });
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        ARGCHK(c, world >= 1 && rank < world);
+        if (c->stage != 0) return zr_fail(c, ZR_ERR_STATE, "zr_set_shadow_tiles between the stages of a frame");
+        if (world > 1 && c->shadow_world > 1) return zr_fail(c, ZR_ERR_STATE, "zr_set_shadow_tiles: the casters are already split by instance (zr_set_shadow_partition)");
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, zr_sync_all(c));
+        c->stile_mem.release(); c->d_sowned_rank = c->d_stile_map = nullptr;
+        c->stile_rank = 0; c->stile_world = 1; c->s_slots_per_rank = c->sn_tiles; c->n_sowned_rank = 0;
+        c->list_valid[0] = false;
+        if (world == 1) return ZR_OK;
+        const ZrTilePartition P = zr_partition(c->stiles_x, c->stiles_y, world, rank);
+        HIPCHK(c, upload(c->stile_mem, &c->d_sowned_rank, P.owned)); HIPCHK(c, upload(c->stile_mem, &c->d_stile_map, P.map));
+        c->stile_rank = rank; c->stile_world = world; c->s_slots_per_rank = P.slots_per_rank; c->n_sowned_rank = (uint32_t)P.owned.size();
+        return ZR_OK;
+    });
 }
 // bytes of one rank's packed share (slots_per_rank tiles of 32 x 32 floats; the all-gathered buffer holds world times that)
 extern "C" int zr_shadow_tiles_bytes(zr_ctx* c, size_t* bytes_per_rank)
 {
     if (!c || !bytes_per_rank) return ZR_ERR_ARG;
-    *bytes_per_rank = (size_t)(c->stile_world > 1 ? c->s_slots_per_rank : c->sn_tiles) * ZR_TILE * ZR_TILE * 4;
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        *bytes_per_rank = (size_t)(c->stile_world > 1 ? c->s_slots_per_rank : c->sn_tiles) * ZR_TILE * ZR_TILE * 4;
+        return ZR_OK;
+    });
 }
 // The owned tiles of the map just rasterised -> packed_dev (slot k = the k-th owned tile, unused slots keep depth 1.0), on `hip_stream`
 // (NULL = the render stream, behind the shadow pass).
 extern "C" int zr_shadow_pack(zr_ctx* c, void* packed_dev, void* hip_stream)
 {
     if (!c) return ZR_ERR_ARG;
-    ARGCHK(c, packed_dev != nullptr);
-    if (c->stile_world <= 1) return zr_fail(c, ZR_ERR_STATE, "zr_shadow_pack: the shadow map is not owned by tiles (zr_set_shadow_tiles)");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    zr_launch_pack_tiles((const uint32_t*)shadow_buf(c), c->d_sowned_rank, c->n_sowned_rank, (uint32_t*)packed_dev, c->SD, c->SD, c->stiles_x, 0x3F800000u, s);
-    HIPCHK(c, hipGetLastError());
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        ARGCHK(c, packed_dev != nullptr);
+        if (c->stile_world <= 1) return zr_fail(c, ZR_ERR_STATE, "zr_shadow_pack: the shadow map is not owned by tiles (zr_set_shadow_tiles)");
+        HIPCHK(c, hipSetDevice(c->device));
+        hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+        zr_launch_pack_tiles((const uint32_t*)shadow_buf(c), c->d_sowned_rank, c->n_sowned_rank, (uint32_t*)packed_dev, c->SD, c->SD, c->stiles_x, 0x3F800000u, s);
+        HIPCHK(c, hipGetLastError());
+        return ZR_OK;
+    });
 }
 // The all-gathered buffer (world x bytes_per_rank, rank-major) -> this frame's shadow map, every tile from its owner, on `hip_stream`
 // (NULL = the render stream: call it before zr_render_lighting).
 extern "C" int zr_shadow_unpack(zr_ctx* c, const void* gathered_dev, void* hip_stream)
 {
     if (!c) return ZR_ERR_ARG;
-    ARGCHK(c, gathered_dev != nullptr);
-    if (c->stile_world <= 1) return zr_fail(c, ZR_ERR_STATE, "zr_shadow_unpack: the shadow map is not owned by tiles (zr_set_shadow_tiles)");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    zr_launch_untile((const uint32_t*)gathered_dev, c->d_stile_map, (uint32_t*)shadow_buf(c), c->SD, c->SD, c->stiles_x, c->sn_tiles, s);
-    HIPCHK(c, hipGetLastError());
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        ARGCHK(c, gathered_dev != nullptr);
+        if (c->stile_world <= 1) return zr_fail(c, ZR_ERR_STATE, "zr_shadow_unpack: the shadow map is not owned by tiles (zr_set_shadow_tiles)");
+        HIPCHK(c, hipSetDevice(c->device));
+        hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+        zr_launch_untile((const uint32_t*)gathered_dev, c->d_stile_map, (uint32_t*)shadow_buf(c), c->SD, c->SD, c->stiles_x, c->sn_tiles, s);
+        HIPCHK(c, hipGetLastError());
+        return ZR_OK;
+    });
 }
 
 // Caller-owned shadow map (float[shadow_dim^2], e.g. a torch tensor RCCL reduces in place); NULL = the internal one.
 extern "C" int zr_set_shadow_buffer(zr_ctx* c, void* ptr)
 {
     if (!c) return ZR_ERR_ARG;
-    c->d_shadow_ext = (float*)ptr;
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        c->d_shadow_ext = (float*)ptr;
+        return ZR_OK;
+    });
+}
+
+// The shadow pipeline's block: its slot-0 counters and its overflow latch belong to the frame's statistics
+static void merge_shadow_stats(zr_ctx* c, const ZrDevStats& sh)
+{
+    ZrDevStats& h = c->h_stats;
+    h.survivors[0] = sh.survivors[0]; h.bin_entries[0] = sh.bin_entries[0]; h.n_chunks[0] = sh.n_chunks[0];
+    h.n_slow[0] = sh.n_slow[0]; h.n_vis_work[0] = sh.n_vis_work[0];
+    // (k_shadow_occlusion tallies in 32 partial sums; survivors of the cull = drawn by the first launch + left out + drawn late)
+    h.shadow_occluded = 0; for (uint32_t v : sh.covered_part) h.shadow_occluded += v;
+    h.shadow_late = sh.shadow_late;
+    h.survivors[0] += h.shadow_occluded + h.shadow_late;
+    h.overflow |= sh.overflow;
+    if (!h.overflow_sticky) h.overflow_sticky = sh.overflow_sticky;      // (a ZR_OVF_* code: the camera lane's, else the pipeline's)
 }
 
 extern "C" int zr_finish(zr_ctx* c)
 {
     if (!c) return ZR_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, zr_sync_all(c));
-    if (c->rendered) {
-        HIPCHK(c, hipMemcpy(&c->h_stats, c->d_stats, sizeof(ZrDevStats), hipMemcpyDeviceToHost));
-        {   // the shadow pipeline's block: its slot-0 counters and its overflow latch belong to the frame's statistics
+    return zr_guard(c, [&]() -> int {
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, zr_sync_all(c));
+        if (c->rendered) {
+            HIPCHK(c, hipMemcpy(&c->h_stats, c->d_stats, sizeof(ZrDevStats), hipMemcpyDeviceToHost));
             ZrDevStats sh;
             HIPCHK(c, hipMemcpy(&sh, c->d_sstats, sizeof(ZrDevStats), hipMemcpyDeviceToHost));
-            c->h_stats.survivors[0] = sh.survivors[0]; c->h_stats.bin_entries[0] = sh.bin_entries[0]; c->h_stats.n_chunks[0] = sh.n_chunks[0];
-            c->h_stats.n_slow[0] = sh.n_slow[0]; c->h_stats.n_vis_work[0] = sh.n_vis_work[0];
-            // (k_shadow_occlusion tallies in 32 partial sums; survivors of the cull = drawn by the first launch + left out + drawn late)
-            c->h_stats.shadow_occluded = 0; for (uint32_t v : sh.covered_part) c->h_stats.shadow_occluded += v;
-            c->h_stats.shadow_late = sh.shadow_late;
-            c->h_stats.survivors[0] += c->h_stats.shadow_occluded + c->h_stats.shadow_late;
-            c->h_stats.overflow |= sh.overflow;
-            if (!c->h_stats.overflow_sticky) c->h_stats.overflow_sticky = sh.overflow_sticky;      // (a ZR_OVF_* code: the camera lane's, else the pipeline's)
+            merge_shadow_stats(c, sh);
+            c->h_stats.covered_shadow = 0;
+            if (c->h_stats.overflow_sticky) {     // latched by ANY frame since the last zr_finish, not only the newest one
+                HIPCHK(c, zr_fill_sync({ { &c->d_stats->overflow_sticky, 0, sizeof(uint32_t) }, { &c->d_sstats->overflow_sticky, 0, sizeof(uint32_t) } }));
+                c->h_stats.overflow = 1u;
+                static const char* const what[] = { "?", "shadow bin entries", "slow-triangle list (zr_set_limits)", "camera work-unit table", "triangle-record arrays (zr_set_limits)",
+                                                    "late shadow bin entries" };
+                const uint32_t code = c->h_stats.overflow_sticky < 6u ? c->h_stats.overflow_sticky : 0u;
+                char msg[160];
+                snprintf(msg, sizeof msg, "tile bin list overflow (%s): a frame since the last zr_finish is incomplete", what[code]);
+                return zr_fail(c, ZR_ERR_OVERFLOW, msg);
+            }
         }
-        c->h_stats.covered_shadow = 0;
-        if (c->h_stats.overflow_sticky) {     // latched by ANY frame since the last zr_finish, not only the newest one
-            HIPCHK(c, zr_fill_sync({ { &c->d_stats->overflow_sticky, 0, sizeof(uint32_t) }, { &c->d_sstats->overflow_sticky, 0, sizeof(uint32_t) } }));
-            c->h_stats.overflow = 1u;
-            static const char* const what[] = { "?", "shadow bin entries", "slow-triangle list (zr_set_limits)", "camera work-unit table", "triangle-record arrays (zr_set_limits)",
-                                                "late shadow bin entries" };
-            const uint32_t code = c->h_stats.overflow_sticky < 6u ? c->h_stats.overflow_sticky : 0u;
-            char msg[160];
-            snprintf(msg, sizeof msg, "tile bin list overflow (%s): a frame since the last zr_finish is incomplete", what[code]);
-            return zr_fail(c, ZR_ERR_OVERFLOW, msg);
-        }
-    }
-    return ZR_OK;
+        return ZR_OK;
+    });
 }
 
 // Mean per-pass GPU time over the last `last_n` frames (<= EV_RING), from hipEvents recorded on the render stream.
 extern "C" int zr_get_pass_times_avg(zr_ctx* c, uint32_t last_n, float ms[ZR_PASS_COUNT])
 {
     if (!c || !ms) return ZR_ERR_ARG;
-    if (!c->rendered) return zr_fail(c, ZR_ERR_STATE, "nothing rendered yet");
-    int rc = zr_finish(c);
-    if (rc && rc != ZR_ERR_OVERFLOW) return rc;
-    if (last_n == 0) last_n = 1;
-    if (last_n > (uint32_t)zr_ctx::EV_RING) last_n = zr_ctx::EV_RING;
-    if (c->sample_no == 0) return zr_fail(c, ZR_ERR_STATE, "no timed frame yet (zr_set_timing_interval)");
-    if ((uint64_t)last_n > c->sample_no) last_n = (uint32_t)c->sample_no;
-    double acc[ZR_PASS_COUNT] = { 0 };
-    for (uint32_t k = 0; k < last_n; ++k) {
-        hipEvent_t* ev = c->evr[(c->sample_no - 1 - k) % zr_ctx::EV_RING];
-        float t[ZR_PASS_COUNT] = { 0 };
-        (void)hipEventElapsedTime(&t[ZR_PASS_CULL_SHADOW], ev[0], ev[1]);
-        (void)hipEventElapsedTime(&t[ZR_PASS_SHADOW], ev[1], ev[2]);
-        (void)hipEventElapsedTime(&t[ZR_PASS_CULL_CAMERA], ev[9], ev[3]);
-        (void)hipEventElapsedTime(&t[ZR_PASS_GBUFFER], ev[3], ev[4]);
-        (void)hipEventElapsedTime(&t[ZR_PASS_HIZ], ev[4], ev[5]);
-        (void)hipEventElapsedTime(&t[ZR_PASS_GBUFFER2], ev[5], ev[6]);
-        (void)hipEventElapsedTime(&t[ZR_PASS_RESOLVE], ev[6], ev[7]);
-        (void)hipEventElapsedTime(&t[ZR_PASS_LIGHTING], ev[7], ev[8]);
-        (void)hipEventElapsedTime(&t[ZR_PASS_TOTAL], ev[0], ev[8]);
-        for (int i = 0; i < ZR_PASS_COUNT; ++i) acc[i] += t[i];
-    }
-    for (int i = 0; i < ZR_PASS_COUNT; ++i) ms[i] = (float)(acc[i] / last_n);
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        if (!c->rendered) return zr_fail(c, ZR_ERR_STATE, "nothing rendered yet");
+        int rc = zr_finish(c);
+        if (rc && rc != ZR_ERR_OVERFLOW) return rc;
+        if (last_n == 0) last_n = 1;
+        if (last_n > (uint32_t)zr_ctx::EV_RING) last_n = zr_ctx::EV_RING;
+        if (c->sample_no == 0) return zr_fail(c, ZR_ERR_STATE, "no timed frame yet (zr_set_timing_interval)");
+        if ((uint64_t)last_n > c->sample_no) last_n = (uint32_t)c->sample_no;
+        double acc[ZR_PASS_COUNT] = { 0 };
+        for (uint32_t k = 0; k < last_n; ++k) {
+            hipEvent_t* ev = c->evr[(c->sample_no - 1 - k) % zr_ctx::EV_RING];
+            float t[ZR_PASS_COUNT] = { 0 };
+            (void)hipEventElapsedTime(&t[ZR_PASS_CULL_SHADOW], ev[0], ev[1]);
+            (void)hipEventElapsedTime(&t[ZR_PASS_SHADOW], ev[1], ev[2]);
+            (void)hipEventElapsedTime(&t[ZR_PASS_CULL_CAMERA], ev[9], ev[3]);
+            (void)hipEventElapsedTime(&t[ZR_PASS_GBUFFER], ev[3], ev[4]);
+            (void)hipEventElapsedTime(&t[ZR_PASS_HIZ], ev[4], ev[5]);
+            (void)hipEventElapsedTime(&t[ZR_PASS_GBUFFER2], ev[5], ev[6]);
+            (void)hipEventElapsedTime(&t[ZR_PASS_RESOLVE], ev[6], ev[7]);
+            (void)hipEventElapsedTime(&t[ZR_PASS_LIGHTING], ev[7], ev[8]);
+            (void)hipEventElapsedTime(&t[ZR_PASS_TOTAL], ev[0], ev[8]);
+            for (int i = 0; i < ZR_PASS_COUNT; ++i) acc[i] += t[i];
+        }
+        for (int i = 0; i < ZR_PASS_COUNT; ++i) ms[i] = (float)(acc[i] / last_n);
+        return ZR_OK;
+    });
 }
-extern "C" int zr_get_pass_times(zr_ctx* c, float ms[ZR_PASS_COUNT]) { return zr_get_pass_times_avg(c, 1, ms); }
+extern "C" int zr_get_pass_times(zr_ctx* c, float ms[ZR_PASS_COUNT]) { return zr_guard(c, [&]() -> int { return zr_get_pass_times_avg(c, 1, ms); }); }
 
 // Begin-to-end GPU time (first kernel of the camera lane to the end of the lighting pass) of each of the last `n` timed frames,
 // newest first; returns how many were written.  With two frames in flight this latency is longer than the frame period.
 extern "C" int zr_get_frame_latencies(zr_ctx* c, uint32_t n, float* ms)
 {
     if (!c || !ms) return ZR_ERR_ARG;
-    if (!c->rendered) return zr_fail(c, ZR_ERR_STATE, "nothing rendered yet");
-    int rc = zr_finish(c);
-    if (rc && rc != ZR_ERR_OVERFLOW) return rc;
-    if (n > (uint32_t)zr_ctx::EV_RING) n = zr_ctx::EV_RING;
-    if ((uint64_t)n > c->sample_no) n = (uint32_t)c->sample_no;
-    for (uint32_t k = 0; k < n; ++k) {
-        hipEvent_t* ev = c->evr[(c->sample_no - 1 - k) % zr_ctx::EV_RING];
-        ms[k] = 0.0f;
-        (void)hipEventElapsedTime(&ms[k], ev[0], ev[8]);
-    }
-    return (int)n;
+    return zr_guard(c, [&]() -> int {
+        if (!c->rendered) return zr_fail(c, ZR_ERR_STATE, "nothing rendered yet");
+        int rc = zr_finish(c);
+        if (rc && rc != ZR_ERR_OVERFLOW) return rc;
+        if (n > (uint32_t)zr_ctx::EV_RING) n = zr_ctx::EV_RING;
+        if ((uint64_t)n > c->sample_no) n = (uint32_t)c->sample_no;
+        for (uint32_t k = 0; k < n; ++k) {
+            hipEvent_t* ev = c->evr[(c->sample_no - 1 - k) % zr_ctx::EV_RING];
+            ms[k] = 0.0f;
+            (void)hipEventElapsedTime(&ms[k], ev[0], ev[8]);
+        }
+        return (int)n;
+    });
 }
 
 // GPU time between the ends of consecutive frames (the frame period the GPU sustained) for the last `n` frames, newest first;
@@ -1696,18 +1702,20 @@ extern "C" int zr_get_frame_latencies(zr_ctx* c, uint32_t n, float* ms)
 extern "C" int zr_get_frame_periods(zr_ctx* c, uint32_t n, float* ms)
 {
     if (!c || !ms) return ZR_ERR_ARG;
-    if (!c->rendered) return zr_fail(c, ZR_ERR_STATE, "nothing rendered yet");
-    int rc = zr_finish(c);
-    if (rc && rc != ZR_ERR_OVERFLOW) return rc;
-    const uint64_t have = c->frame_no > 0 ? c->frame_no - 1 : 0;
-    if (n > (uint32_t)zr_ctx::END_RING - 1u) n = zr_ctx::END_RING - 1;
-    if ((uint64_t)n > have) n = (uint32_t)have;
-    for (uint32_t k = 0; k < n; ++k) {
-        const uint64_t f = c->frame_no - 1 - k;
-        ms[k] = 0.0f;
-        (void)hipEventElapsedTime(&ms[k], c->ev_end[(f - 1) % zr_ctx::END_RING], c->ev_end[f % zr_ctx::END_RING]);
-    }
-    return (int)n;
+    return zr_guard(c, [&]() -> int {
+        if (!c->rendered) return zr_fail(c, ZR_ERR_STATE, "nothing rendered yet");
+        int rc = zr_finish(c);
+        if (rc && rc != ZR_ERR_OVERFLOW) return rc;
+        const uint64_t have = c->frame_no > 0 ? c->frame_no - 1 : 0;
+        if (n > (uint32_t)zr_ctx::END_RING - 1u) n = zr_ctx::END_RING - 1;
+        if ((uint64_t)n > have) n = (uint32_t)have;
+        for (uint32_t k = 0; k < n; ++k) {
+            const uint64_t f = c->frame_no - 1 - k;
+            ms[k] = 0.0f;
+            (void)hipEventElapsedTime(&ms[k], c->ev_end[(f - 1) % zr_ctx::END_RING], c->ev_end[f % zr_ctx::END_RING]);
+        }
+        return (int)n;
+    });
 }
 
 // Per-pass hipEvents are recorded on every interval-th frame (default 1 = every frame, 0 = never).  Each record is a small
@@ -1715,8 +1723,10 @@ extern "C" int zr_get_frame_periods(zr_ctx* c, uint32_t n, float* ms)
 extern "C" int zr_set_timing_interval(zr_ctx* c, uint32_t interval)
 {
     if (!c) return ZR_ERR_ARG;
-    c->timing_interval = interval;
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        c->timing_interval = interval;
+        return ZR_OK;
+    });
 }
 
 extern "C" uint32_t zr_abi_version(void) { return ZR_ABI_VERSION; }
@@ -1726,41 +1736,40 @@ extern "C" uint32_t zr_abi_version(void) { return ZR_ABI_VERSION; }
 extern "C" int zr_get_stats(zr_ctx* c, zr_stats* out_user, size_t bytes)
 {
     if (!c || !out_user) return ZR_ERR_ARG;
-    ARGCHK(c, bytes >= offsetof(zr_stats, round1_survivors) && bytes % 4 == 0);      // (the first release's struct ended there)
-    zr_stats out_full; zr_stats* out = &out_full;
-    int rc = zr_finish(c);
-    if (c->rendered && (rc == ZR_OK || rc == ZR_ERR_OVERFLOW)) {      // shadow coverage is a statistic, counted on demand
-        ZrDevStats z; (void)hipMemcpy(&z, c->d_stats, sizeof z, hipMemcpyDeviceToHost);
-        uint32_t zero = 0;
-        (void)hipMemcpy(&c->d_stats->covered_shadow, &zero, 4, hipMemcpyHostToDevice);
-        zr_launch_count_shadow((const uint32_t*)(c->d_shadow_ext ? c->d_shadow_ext : c->d_shadow), (size_t)c->SD * c->SD, c->d_stats, c->stream);
-        (void)hipStreamSynchronize(c->stream);
-        const ZrDevStats keep = c->h_stats;      // (zr_finish merged the shadow pipeline's block into it)
-        (void)hipMemcpy(&c->h_stats, c->d_stats, sizeof(ZrDevStats), hipMemcpyDeviceToHost);
-        c->h_stats.survivors[0] = keep.survivors[0]; c->h_stats.bin_entries[0] = keep.bin_entries[0]; c->h_stats.n_chunks[0] = keep.n_chunks[0];
-        c->h_stats.n_slow[0] = keep.n_slow[0]; c->h_stats.overflow |= keep.overflow;
-        c->h_stats.shadow_occluded = keep.shadow_occluded; c->h_stats.shadow_late = keep.shadow_late;
-    }
+    return zr_guard(c, [&]() -> int {
+        ARGCHK(c, bytes >= offsetof(zr_stats, round1_survivors) && bytes % 4 == 0);      // (the first release's struct ended there)
+        zr_stats out_full; zr_stats* out = &out_full;
+        int rc = zr_finish(c);
+        if (c->rendered && (rc == ZR_OK || rc == ZR_ERR_OVERFLOW)) {      // shadow coverage is a statistic, counted on demand
+            ZrDevStats z; (void)hipMemcpy(&z, c->d_stats, sizeof z, hipMemcpyDeviceToHost);
+            uint32_t zero = 0;
+            (void)hipMemcpy(&c->d_stats->covered_shadow, &zero, 4, hipMemcpyHostToDevice);
+            zr_launch_count_shadow((const uint32_t*)shadow_buf(c), (size_t)c->SD * c->SD, c->d_stats, c->stream);
+            (void)hipStreamSynchronize(c->stream);
+            // (the count is the one word of the block that changed since zr_finish read it and merged the shadow pipeline's into it)
+            (void)hipMemcpy(&c->h_stats.covered_shadow, &c->d_stats->covered_shadow, 4, hipMemcpyDeviceToHost);
+        }
 #ifdef ZR_DIAG
-    if (getenv("ZR_DUMP_STATS")) {     // diagnostics: the raw device block
-        const ZrDevStats& h = c->h_stats;
-        fprintf(stderr, "zr stats: survivors %u %u %u  bin_entries %u %u %u  n_sel %u %u %u  n_slow %u %u %u  hiz_culled %u  n_chunks %u %u %u  overflow records %u %u\n",
-                h.survivors[0], h.survivors[1], h.survivors[2], h.bin_entries[0], h.bin_entries[1], h.bin_entries[2], h.n_sel[0], h.n_sel[1], h.n_sel[2],
-                h.n_slow[0], h.n_slow[1], h.n_slow[2], h.hiz_culled, h.n_chunks[0], h.n_chunks[1], h.n_chunks[2], h.pool_used[1], h.pool_used[2]);
-    }
+        if (getenv("ZR_DUMP_STATS")) {     // diagnostics: the raw device block
+            const ZrDevStats& h = c->h_stats;
+            fprintf(stderr, "zr stats: survivors %u %u %u  bin_entries %u %u %u  n_sel %u %u %u  n_slow %u %u %u  hiz_culled %u  n_chunks %u %u %u  overflow records %u %u\n",
+                    h.survivors[0], h.survivors[1], h.survivors[2], h.bin_entries[0], h.bin_entries[1], h.bin_entries[2], h.n_sel[0], h.n_sel[1], h.n_sel[2],
+                    h.n_slow[0], h.n_slow[1], h.n_slow[2], h.hiz_culled, h.n_chunks[0], h.n_chunks[1], h.n_chunks[2], h.pool_used[1], h.pool_used[2]);
+        }
 #endif
-    memset(out, 0, sizeof *out);
-    for (int i = 0; i < 2; ++i) {
-        out->work_items[i] = c->last_work[i]; out->survivors[i] = c->h_stats.survivors[i]; out->bin_entries[i] = c->h_stats.bin_entries[i];
-    }
-    out->survivors[1] += c->h_stats.survivors[2]; out->bin_entries[1] += c->h_stats.bin_entries[2];    // both rounds of the camera pass
-    out->hiz_culled = c->h_stats.hiz_culled; out->round1_survivors = c->last_two_round ? c->h_stats.survivors[1] : 0;
-    out->covered_pixels = 0; for (uint32_t v : c->h_stats.covered_part) out->covered_pixels += v;
-    out->covered_shadow_texels = c->h_stats.covered_shadow; out->overflow = c->h_stats.overflow;
-    out->shadow_occluded = c->h_stats.shadow_occluded; out->shadow_late = c->h_stats.shadow_late;
-    out->hiz_culled_geom = c->h_stats.hiz_culled_geom; out->struct_bytes = (uint32_t)sizeof(zr_stats);
-    memcpy(out_user, out, std::min(bytes, sizeof(zr_stats)));
-    return rc;
+        memset(out, 0, sizeof *out);
+        for (int i = 0; i < 2; ++i) {
+            out->work_items[i] = c->last_work[i]; out->survivors[i] = c->h_stats.survivors[i]; out->bin_entries[i] = c->h_stats.bin_entries[i];
+        }
+        out->survivors[1] += c->h_stats.survivors[2]; out->bin_entries[1] += c->h_stats.bin_entries[2];    // both rounds of the camera pass
+        out->hiz_culled = c->h_stats.hiz_culled; out->round1_survivors = c->last_two_round ? c->h_stats.survivors[1] : 0;
+        out->covered_pixels = 0; for (uint32_t v : c->h_stats.covered_part) out->covered_pixels += v;
+        out->covered_shadow_texels = c->h_stats.covered_shadow; out->overflow = c->h_stats.overflow;
+        out->shadow_occluded = c->h_stats.shadow_occluded; out->shadow_late = c->h_stats.shadow_late;
+        out->hiz_culled_geom = c->h_stats.hiz_culled_geom; out->struct_bytes = (uint32_t)sizeof(zr_stats);
+        memcpy(out_user, out, std::min(bytes, sizeof(zr_stats)));
+        return rc;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ read-back
@@ -1768,31 +1777,38 @@ extern "C" int zr_get_stats(zr_ctx* c, zr_stats* out_user, size_t bytes)
 extern "C" int zr_read_color(zr_ctx* c, uint8_t* dst, size_t bytes)
 {
     if (!c) return ZR_ERR_ARG;
-    ARGCHK(c, dst && bytes == (size_t)c->W * c->H * 4);
-    int rc = zr_finish(c);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpy(dst, c->d_color, bytes, hipMemcpyDeviceToHost));
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        ARGCHK(c, dst && bytes == (size_t)c->W * c->H * 4);
+        int rc = zr_finish(c);
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpy(dst, c->d_color, bytes, hipMemcpyDeviceToHost));
+        return ZR_OK;
+    });
 }
 extern "C" int zr_read_gbuffer(zr_ctx* c, int target, void* dst, size_t bytes)
 {
     if (!c) return ZR_ERR_ARG;
-    const void* src[6] = { c->G.depth, c->G.scene_color, c->G.gA, c->G.gB, c->G.gC, c->G.gD };
-    ARGCHK(c, dst && target >= 0 && target < 6);
-    ARGCHK(c, bytes == (size_t)c->W * c->H * (target == 5 ? 8 : 4));
-    int rc = zr_finish(c);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpy(dst, src[target], bytes, hipMemcpyDeviceToHost));
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        const GBufferPtrs& G = c->fc[c->fcur].G;
+        const void* src[6] = { G.depth, G.scene_color, G.gA, G.gB, G.gC, G.gD };
+        ARGCHK(c, dst && target >= 0 && target < 6);
+        ARGCHK(c, bytes == (size_t)c->W * c->H * (target == 5 ? 8 : 4));
+        int rc = zr_finish(c);
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpy(dst, src[target], bytes, hipMemcpyDeviceToHost));
+        return ZR_OK;
+    });
 }
 extern "C" int zr_read_shadowmap(zr_ctx* c, float* dst, size_t bytes)
 {
     if (!c) return ZR_ERR_ARG;
-    ARGCHK(c, dst && bytes == (size_t)c->SD * c->SD * 4);
-    int rc = zr_finish(c);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpy(dst, c->d_shadow_ext ? c->d_shadow_ext : c->d_shadow, bytes, hipMemcpyDeviceToHost));
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        ARGCHK(c, dst && bytes == (size_t)c->SD * c->SD * 4);
+        int rc = zr_finish(c);
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpy(dst, shadow_buf(c), bytes, hipMemcpyDeviceToHost));
+        return ZR_OK;
+    });
 }
 
 // The frame enqueued last, copied into caller-owned DEVICE buffers in stream order (no host synchronisation): what a host with two frames
@@ -1802,36 +1818,30 @@ extern "C" int zr_read_shadowmap(zr_ctx* c, float* dst, size_t bytes)
 extern "C" int zr_copy_frame_async(zr_ctx* c, void* color_dev, void* shadow_dev)
 {
     if (!c) return ZR_ERR_ARG;
-    if (!c->rendered || c->stage != 0) return zr_fail(c, ZR_ERR_STATE, "zr_copy_frame_async: no finished frame enqueued");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (color_dev) HIPCHK(c, hipMemcpyAsync(color_dev, c->d_color, (size_t)c->W * c->H * 4, hipMemcpyDeviceToDevice, c->stream));
-    if (shadow_dev) HIPCHK(c, hipMemcpyAsync(shadow_dev, shadow_buf(c), (size_t)c->SD * c->SD * 4, hipMemcpyDeviceToDevice, c->stream));
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        if (!c->rendered || c->stage != 0) return zr_fail(c, ZR_ERR_STATE, "zr_copy_frame_async: no finished frame enqueued");
+        HIPCHK(c, hipSetDevice(c->device));
+        if (color_dev) HIPCHK(c, hipMemcpyAsync(color_dev, c->d_color, (size_t)c->W * c->H * 4, hipMemcpyDeviceToDevice, c->stream));
+        if (shadow_dev) HIPCHK(c, hipMemcpyAsync(shadow_dev, shadow_buf(c), (size_t)c->SD * c->SD * 4, hipMemcpyDeviceToDevice, c->stream));
+        return ZR_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ object identity (zelda_render.h)
 
-static int zr_set_id_capture_impl(zr_ctx* c, int enable)
-{
-    if (!c) return ZR_ERR_ARG;
-    if (c->stage != 0) return zr_fail(c, ZR_ERR_STATE, "zr_set_id_capture between the stages of a frame");
-    const bool on = enable != 0;
-    if (on == c->id_capture) return ZR_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t n = (size_t)c->W * c->H;
-    for (int b = 0; b < 2; ++b) {
-        if (on && !c->d_prim_b[b]) {             // the forward variant's planes, allocated as zr_set_shading does
-            if (c->own.alloc(&c->d_prim_b[b], n) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "zr_set_id_capture: out of device memory");
-            HIPCHK(c, zr_fill_sync({ { c->d_prim_b[b], 0xFF, n * 4 } }));      // (pixels of other ranks' tiles stay "none")
-        }
-        c->Gb[b].prim = (on || c->shading == ZR_SHADING_FORWARD) ? c->d_prim_b[b] : nullptr;
-    }
-    c->id_capture = on;
-    return ZR_OK;
-}
 extern "C" int zr_set_id_capture(zr_ctx* c, int enable)
 {
-    return zr_guard(c, [&]() { return zr_set_id_capture_impl(c, enable); });
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        if (c->stage != 0) return zr_fail(c, ZR_ERR_STATE, "zr_set_id_capture between the stages of a frame");
+        const bool on = enable != 0;
+        if (on == c->id_capture) return ZR_OK;
+        HIPCHK(c, hipSetDevice(c->device));
+        const int rc = set_winner_planes(c, c->shading == ZR_SHADING_FORWARD, on, "zr_set_id_capture");      // (no drain: frames in flight keep what they were enqueued with)
+        if (rc) return rc;
+        c->id_capture = on;
+        return ZR_OK;
+    });
 }
 
 // The frame enqueued last kept its winners and still describes the scene; `sync`: finish it first (its overflow is the query's error).
@@ -1845,9 +1855,9 @@ static int ids_ready(zr_ctx* c, const char* what, bool sync)
 }
 static ZrIdsArgs ids_args(zr_ctx* c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h)
 {
-    const int last = (int)((c->frame_no - 1u) & 1u);          // the copy the frame enqueued last wrote
+    const FrameCopy& F = c->fc[c->fcur];                      // (stage 0: the copy the frame enqueued last wrote)
     ZrIdsArgs A; memset(&A, 0, sizeof A);
-    A.prim = c->d_prim_b[last]; A.depth = c->Gb[last].depth;
+    A.prim = F.prim_plane; A.depth = F.G.depth;
     A.draws = c->d_ids_draws; A.n_draws = c->ids_n_draws;
     A.W = c->W; A.x0 = x0; A.y0 = y0; A.w = w; A.h = h;
     A.counts = c->d_ids_counts; A.keys = c->d_ids_keys; A.hit_list = c->d_ids_list; A.n_hits = c->d_ids_n;
@@ -1857,54 +1867,54 @@ static ZrIdsArgs ids_args(zr_ctx* c, uint32_t x0, uint32_t y0, uint32_t w, uint3
 extern "C" int zr_read_ids(zr_ctx* c, int kind, void* dst, size_t bytes)
 {
     if (!c) return ZR_ERR_ARG;
-    ARGCHK(c, dst && (kind == ZR_IDS_PRIMITIVE || kind == ZR_IDS_OBJECT));
-    ARGCHK(c, bytes == (size_t)c->W * c->H * (kind == ZR_IDS_OBJECT ? 8 : 4));
-    int rc = ids_ready(c, "zr_read_ids", true);
-    if (rc) return rc;
-    const ZrIdsArgs A0 = ids_args(c, 0, 0, c->W, c->H);
-    if (kind == ZR_IDS_PRIMITIVE) { HIPCHK(c, hipMemcpy(dst, A0.prim, bytes, hipMemcpyDeviceToHost)); return ZR_OK; }
-    if (!c->d_ids_obj) HIPCHK(c, c->own.alloc(&c->d_ids_obj, (size_t)c->W * c->H));
-    ZrIdsArgs A = A0; A.obj_plane = c->d_ids_obj;
-    zr_launch_id_census(A, ZR_IDS_OBJECTS, c->stream);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(dst, c->d_ids_obj, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        ARGCHK(c, dst && (kind == ZR_IDS_PRIMITIVE || kind == ZR_IDS_OBJECT));
+        ARGCHK(c, bytes == (size_t)c->W * c->H * (kind == ZR_IDS_OBJECT ? 8 : 4));
+        int rc = ids_ready(c, "zr_read_ids", true);
+        if (rc) return rc;
+        const ZrIdsArgs A0 = ids_args(c, 0, 0, c->W, c->H);
+        if (kind == ZR_IDS_PRIMITIVE) { HIPCHK(c, hipMemcpy(dst, A0.prim, bytes, hipMemcpyDeviceToHost)); return ZR_OK; }
+        if (!c->d_ids_obj) HIPCHK(c, c->own.alloc(&c->d_ids_obj, (size_t)c->W * c->H));
+        ZrIdsArgs A = A0; A.obj_plane = c->d_ids_obj;
+        zr_launch_id_census(A, ZR_IDS_OBJECTS, c->stream);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(dst, c->d_ids_obj, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return ZR_OK;
+    });
 }
 
-static int zr_pick_impl(zr_ctx* c, uint32_t x, uint32_t y, uint32_t w, uint32_t h, zr_hit* hits, uint32_t cap, uint32_t* n)
-{
-    if (!c) return ZR_ERR_ARG;
-    ARGCHK(c, n && w > 0 && h > 0 && (hits || cap == 0));
-    *n = 0;
-    int rc = ids_ready(c, "zr_pick", true);
-    if (rc) return rc;
-    if (x >= c->W || y >= c->H) return ZR_OK;                  // wholly outside the frame
-    ZrIdsArgs A = ids_args(c, x, y, std::min(w, c->W - x), std::min(h, c->H - y));
-    zr_launch_id_census(A, ZR_IDS_PICK, c->stream);
-    HIPCHK(c, hipGetLastError());
-    uint32_t total = 0;
-    HIPCHK(c, hipMemcpyAsync(&total, c->d_ids_n, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (total > c->ids_n_slots) return zr_fail(c, ZR_ERR_DEVICE, "zr_pick: hit list longer than the slot count");
-    std::vector<zr_hit> all(total);
-    zr_launch_id_hits(A, total, c->d_ids_hits, c->stream);       // (also clears the listed slots)
-    HIPCHK(c, hipGetLastError());
-    if (total) HIPCHK(c, hipMemcpyAsync(all.data(), c->d_ids_hits, sizeof(zr_hit) * total, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_ids_n, 0, 4, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::sort(all.begin(), all.end(), [](const zr_hit& a, const zr_hit& b) {
-        if (a.depth != b.depth) return a.depth < b.depth;
-        if (a.object != b.object) return a.object < b.object;
-        return a.instance < b.instance;
-    });
-    if (total) memcpy(hits, all.data(), sizeof(zr_hit) * std::min(total, cap));
-    *n = total;
-    return ZR_OK;
-}
 extern "C" int zr_pick(zr_ctx* c, uint32_t x, uint32_t y, uint32_t w, uint32_t h, zr_hit* hits, uint32_t cap, uint32_t* n)
 {
-    return zr_guard(c, [&]() { return zr_pick_impl(c, x, y, w, h, hits, cap, n); });
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        ARGCHK(c, n && w > 0 && h > 0 && (hits || cap == 0));
+        *n = 0;
+        int rc = ids_ready(c, "zr_pick", true);
+        if (rc) return rc;
+        if (x >= c->W || y >= c->H) return ZR_OK;                  // wholly outside the frame
+        ZrIdsArgs A = ids_args(c, x, y, std::min(w, c->W - x), std::min(h, c->H - y));
+        zr_launch_id_census(A, ZR_IDS_PICK, c->stream);
+        HIPCHK(c, hipGetLastError());
+        uint32_t total = 0;
+        HIPCHK(c, hipMemcpyAsync(&total, c->d_ids_n, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (total > c->ids_n_slots) return zr_fail(c, ZR_ERR_DEVICE, "zr_pick: hit list longer than the slot count");
+        std::vector<zr_hit> all(total);
+        zr_launch_id_hits(A, total, c->d_ids_hits, c->stream);       // (also clears the listed slots)
+        HIPCHK(c, hipGetLastError());
+        if (total) HIPCHK(c, hipMemcpyAsync(all.data(), c->d_ids_hits, sizeof(zr_hit) * total, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d_ids_n, 0, 4, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        std::sort(all.begin(), all.end(), [](const zr_hit& a, const zr_hit& b) {
+            if (a.depth != b.depth) return a.depth < b.depth;
+            if (a.object != b.object) return a.object < b.object;
+            return a.instance < b.instance;
+        });
+        if (total) memcpy(hits, all.data(), sizeof(zr_hit) * std::min(total, cap));
+        *n = total;
+        return ZR_OK;
+    });
 }
 
 static size_t ids_slot_bytes(const zr_ctx* c)
@@ -1926,26 +1936,29 @@ static int ids_coverage(zr_ctx* c, uint32_t* counts_dev, size_t bytes)
 extern "C" int zr_instance_coverage(zr_ctx* c, uint32_t* counts, size_t bytes)
 {
     if (!c) return ZR_ERR_ARG;
-    ARGCHK(c, (counts || bytes == 0) && bytes == ids_slot_bytes(c));
-    int rc = ids_ready(c, "zr_instance_coverage", true);
-    if (rc == ZR_OK) rc = ids_coverage(c, c->d_ids_cov, bytes);
-    if (rc) return rc;
-    if (bytes) HIPCHK(c, hipMemcpyAsync(counts, c->d_ids_cov, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        ARGCHK(c, (counts || bytes == 0) && bytes == ids_slot_bytes(c));
+        int rc = ids_ready(c, "zr_instance_coverage", true);
+        if (rc == ZR_OK) rc = ids_coverage(c, c->d_ids_cov, bytes);
+        if (rc) return rc;
+        if (bytes) HIPCHK(c, hipMemcpyAsync(counts, c->d_ids_cov, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return ZR_OK;
+    });
 }
 extern "C" int zr_instance_coverage_async(zr_ctx* c, void* counts_dev, size_t bytes)
 {
     if (!c) return ZR_ERR_ARG;
-    ARGCHK(c, (counts_dev || bytes == 0) && bytes == ids_slot_bytes(c));
-    int rc = ids_ready(c, "zr_instance_coverage_async", false);
-    if (rc == ZR_OK) rc = ids_coverage(c, (uint32_t*)counts_dev, bytes);
-    if (rc) return rc;
-    // the census reads the winner plane of copy `last`: the frame that writes that copy next (the one after next) waits for it
-    const int last = (int)((c->frame_no - 1u) & 1u);
-    HIPCHK(c, hipEventRecord(c->ev_ids[last], c->stream));
-    c->ids_wait[last] = true;
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        ARGCHK(c, (counts_dev || bytes == 0) && bytes == ids_slot_bytes(c));
+        int rc = ids_ready(c, "zr_instance_coverage_async", false);
+        if (rc == ZR_OK) rc = ids_coverage(c, (uint32_t*)counts_dev, bytes);
+        if (rc) return rc;
+        // the census reads the last frame's winner plane: the frame that writes that copy next (the one after next) waits for it
+        HIPCHK(c, hipEventRecord(c->fc[c->fcur].ev_ids, c->stream));
+        c->fc[c->fcur].ids_wait = true;
+        return ZR_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ multi-GPU tiles
@@ -1953,34 +1966,42 @@ extern "C" int zr_instance_coverage_async(zr_ctx* c, void* counts_dev, size_t by
 extern "C" int zr_tiles_device_buffer(zr_ctx* c, void** p, size_t* bytes)
 {
     if (!c || !p || !bytes) return ZR_ERR_ARG;
-    *p = c->d_tiles; *bytes = (size_t)c->slots_per_rank * ZR_TILE * ZR_TILE * 4;
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        *p = c->d_tiles; *bytes = (size_t)c->slots_per_rank * ZR_TILE * ZR_TILE * 4;
+        return ZR_OK;
+    });
 }
 // Lets the caller own the packed tile buffer (e.g. a torch tensor handed to RCCL; two of them alternate so that frame k's
 // all-gather overlaps frame k+1's rendering).  ptr must hold zr_tiles_device_buffer's byte count; NULL = internal buffer.
 extern "C" int zr_set_tiles_buffer(zr_ctx* c, void* ptr)
 {
     if (!c) return ZR_ERR_ARG;
-    c->d_tiles_ext = (uint32_t*)ptr;
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        c->d_tiles_ext = (uint32_t*)ptr;
+        return ZR_OK;
+    });
 }
 
 extern "C" int zr_read_tiles(zr_ctx* c, uint8_t* dst, size_t bytes)
 {
     if (!c) return ZR_ERR_ARG;
-    ARGCHK(c, dst && bytes == (size_t)c->slots_per_rank * ZR_TILE * ZR_TILE * 4);
-    int rc = zr_finish(c);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpy(dst, c->d_tiles_ext ? c->d_tiles_ext : c->d_tiles, bytes, hipMemcpyDeviceToHost));
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        ARGCHK(c, dst && bytes == (size_t)c->slots_per_rank * ZR_TILE * ZR_TILE * 4);
+        int rc = zr_finish(c);
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpy(dst, c->d_tiles_ext ? c->d_tiles_ext : c->d_tiles, bytes, hipMemcpyDeviceToHost));
+        return ZR_OK;
+    });
 }
 extern "C" int zr_composite(zr_ctx* c, const void* gathered)
 {
     if (!c) return ZR_ERR_ARG;
-    ARGCHK(c, gathered != nullptr);
-    HIPCHK(c, hipSetDevice(c->device));
-    zr_launch_untile((const uint32_t*)gathered, c->d_tile_map, c->d_color, c->W, c->H, c->tiles_x, c->n_tiles, c->stream);
-    HIPCHK(c, hipGetLastError());
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        ARGCHK(c, gathered != nullptr);
+        HIPCHK(c, hipSetDevice(c->device));
+        zr_launch_untile((const uint32_t*)gathered, c->d_tile_map, c->d_color, c->W, c->H, c->tiles_x, c->n_tiles, c->stream);
+        HIPCHK(c, hipGetLastError());
+        return ZR_OK;
+    });
 }
-extern "C" int zr_color_device_ptr(zr_ctx* c, void** p) { if (!c || !p) return ZR_ERR_ARG; *p = c->d_color; return ZR_OK; }
+extern "C" int zr_color_device_ptr(zr_ctx* c, void** p) { if (!c || !p) return ZR_ERR_ARG; return zr_guard(c, [&]() -> int { *p = c->d_color; return ZR_OK; }); }

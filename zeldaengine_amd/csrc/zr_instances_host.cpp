@@ -11,9 +11,6 @@
 
 #include "zr_ctx.h"
 
-#define HIPCHK(c, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) \
-    return zr_fail((c), ZR_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); } while (0)
-
 static int inst_init_ctx(zr_ctx* c)
 {
     if (c->ev_scatter) return ZR_OK;
@@ -83,64 +80,59 @@ static int inst_enqueue(zr_ctx* c, ZrSceneObject& o, hipStream_t x, const uint32
     return ZR_OK;
 }
 
-static int zr_object_set_instances_impl(zr_ctx* c, uint32_t index, uint32_t first, const XkInstanceData* data, uint32_t n)
-{
-    if (!c) return ZR_ERR_ARG;
-    ZrSceneObject* o = nullptr;
-    int rc = inst_object(c, index, first, n, "zr_object_set_instances", &o);
-    if (rc) return rc;
-    if (n == 0) return ZR_OK;
-    if (!data) return zr_fail(c, ZR_ERR_ARG, "zr_object_set_instances: no data");
-    HIPCHK(c, hipSetDevice(c->device));
-    rc = inst_init_ctx(c);
-    if (rc) return rc;
-    // the camera lane: an update that follows frame k is then ordered behind frame k's camera pipeline and ahead of frame k + 1's, with no
-    // extra wait on the host's stream, where frame k's lighting runs
-    hipStream_t x = c->cam_s ? c->cam_s : c->stream;
-    zr_ctx::InstStage& r = c->inst_ring[c->inst_slot++ % zr_ctx::INST_RING];
-    HIPCHK(c, hipEventSynchronize(r.ev));          // the copy and the scatter that used this slot last are done
-    if (r.cap < n) {
-        r.mem.release(); r.h = nullptr; r.d = nullptr;
-        r.cap = 0;
-        size_t cap = 4096; while (cap < n) cap *= 2;
-        HIPCHK(c, r.mem.host(&r.h, cap));
-        HIPCHK(c, r.mem.alloc(&r.d, cap));
-        r.cap = cap;
-    }
-    memcpy(r.h, data, (size_t)n * sizeof(XkInstanceData));
-    HIPCHK(c, hipMemcpyAsync(r.d, r.h, (size_t)n * sizeof(XkInstanceData), hipMemcpyHostToDevice, x));
-    rc = inst_enqueue(c, *o, x, nullptr, r.d, first, n);
-    if (rc) return rc;
-    HIPCHK(c, hipEventRecord(r.ev, x));
-    if (!o->host_stale) memcpy(o->inst.data() + first, data, (size_t)n * sizeof(XkInstanceData));      // (else the read-back brings it)
-    return ZR_OK;
-}
 extern "C" int zr_object_set_instances(zr_ctx* c, uint32_t index, uint32_t first, const XkInstanceData* data, uint32_t n)
 {
-    return zr_guard(c, [&]() { return zr_object_set_instances_impl(c, index, first, data, n); });
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        ZrSceneObject* o = nullptr;
+        int rc = inst_object(c, index, first, n, "zr_object_set_instances", &o);
+        if (rc) return rc;
+        if (n == 0) return ZR_OK;
+        if (!data) return zr_fail(c, ZR_ERR_ARG, "zr_object_set_instances: no data");
+        HIPCHK(c, hipSetDevice(c->device));
+        rc = inst_init_ctx(c);
+        if (rc) return rc;
+        // the camera lane: an update that follows frame k is then ordered behind frame k's camera pipeline and ahead of frame k + 1's, with no
+        // extra wait on the host's stream, where frame k's lighting runs
+        hipStream_t x = c->cam_s ? c->cam_s : c->stream;
+        zr_ctx::InstStage& r = c->inst_ring[c->inst_slot++ % zr_ctx::INST_RING];
+        HIPCHK(c, hipEventSynchronize(r.ev));          // the copy and the scatter that used this slot last are done
+        if (r.cap < n) {
+            r.mem.release(); r.h = nullptr; r.d = nullptr;
+            r.cap = 0;
+            size_t cap = 4096; while (cap < n) cap *= 2;
+            HIPCHK(c, r.mem.host(&r.h, cap));
+            HIPCHK(c, r.mem.alloc(&r.d, cap));
+            r.cap = cap;
+        }
+        memcpy(r.h, data, (size_t)n * sizeof(XkInstanceData));
+        HIPCHK(c, hipMemcpyAsync(r.d, r.h, (size_t)n * sizeof(XkInstanceData), hipMemcpyHostToDevice, x));
+        rc = inst_enqueue(c, *o, x, nullptr, r.d, first, n);
+        if (rc) return rc;
+        HIPCHK(c, hipEventRecord(r.ev, x));
+        if (!o->host_stale) memcpy(o->inst.data() + first, data, (size_t)n * sizeof(XkInstanceData));      // (else the read-back brings it)
+        return ZR_OK;
+    });
 }
 
-static int zr_object_update_instances_async_impl(zr_ctx* c, uint32_t index, uint32_t first, const uint32_t* idx_dev,
-                                                 const XkInstanceData* data_dev, uint32_t n, void* hip_stream)
-{
-    if (!c) return ZR_ERR_ARG;
-    ZrSceneObject* o = nullptr;
-    int rc = inst_object(c, index, first, n, "zr_object_update_instances_async", &o);
-    if (rc) return rc;
-    if (n == 0) return ZR_OK;
-    if (!data_dev || ((uintptr_t)data_dev & 3u) || ((uintptr_t)idx_dev & 3u))
-        return zr_fail(c, ZR_ERR_ARG, "zr_object_update_instances_async: data_dev missing, or a buffer not 4-byte aligned");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t x = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    rc = inst_enqueue(c, *o, x, idx_dev, data_dev, first, n);
-    if (rc) return rc;
-    o->host_stale = true;
-    return ZR_OK;
-}
 extern "C" int zr_object_update_instances_async(zr_ctx* c, uint32_t index, uint32_t first, const uint32_t* idx_dev,
                                                 const XkInstanceData* data_dev, uint32_t n, void* hip_stream)
 {
-    return zr_guard(c, [&]() { return zr_object_update_instances_async_impl(c, index, first, idx_dev, data_dev, n, hip_stream); });
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        ZrSceneObject* o = nullptr;
+        int rc = inst_object(c, index, first, n, "zr_object_update_instances_async", &o);
+        if (rc) return rc;
+        if (n == 0) return ZR_OK;
+        if (!data_dev || ((uintptr_t)data_dev & 3u) || ((uintptr_t)idx_dev & 3u))
+            return zr_fail(c, ZR_ERR_ARG, "zr_object_update_instances_async: data_dev missing, or a buffer not 4-byte aligned");
+        HIPCHK(c, hipSetDevice(c->device));
+        hipStream_t x = hip_stream ? (hipStream_t)hip_stream : c->stream;
+        rc = inst_enqueue(c, *o, x, idx_dev, data_dev, first, n);
+        if (rc) return rc;
+        o->host_stale = true;
+        return ZR_OK;
+    });
 }
 
 int zr_instances_sync_host(zr_ctx* c, ZrSceneObject& o)

@@ -320,7 +320,7 @@ int world_uniforms(zr_ctx* c, const ZrWorld& w, float roll_stage, float roll_lig
                               L[2].data(), (uint32_t)L[2].size(), roll_stage, roll_light, time);
 }
 
-// No C++ exception crosses the ABI: an allocation failure while instantiating a world becomes an error code.
+// What instantiating a world throws becomes the world-load path's own codes ([WORLD] ..., ZR_ERR_STATE), inside the entry point's zr_guard.
 int apply_world_guarded(zr_ctx* c, const ZrWorld& w)
 {
     try { return apply_world(c, w); }
@@ -356,22 +356,26 @@ void jstr(std::string& o, const std::string& s)
 extern "C" int zr_profab_register(zr_ctx* c, const char* name, uint32_t mesh_id, const zr_material* mat)
 {
     if (!c || !name) return ZR_ERR_ARG;
-    if (mesh_id >= c->meshes.size()) return zr_fail(c, ZR_ERR_ARG, "bad mesh id");
-    ZrProfab pf; pf.mesh = mesh_id;
-    int rc = zr_material_prepare(c, mat, &pf.mat);
-    if (rc) return rc;
-    c->profabs[name].push_back(pf);
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        if (mesh_id >= c->meshes.size()) return zr_fail(c, ZR_ERR_ARG, "bad mesh id");
+        ZrProfab pf; pf.mesh = mesh_id;
+        int rc = zr_material_prepare(c, mat, &pf.mat);
+        if (rc) return rc;
+        c->profabs[name].push_back(pf);
+        return ZR_OK;
+    });
 }
 
 extern "C" int zr_world_load_json(zr_ctx* c, const char* utf8, size_t len)
 {
     if (!c || !utf8) return ZR_ERR_ARG;
-    ZrWorld w; std::string err;
-    if (!world_parse(utf8, len, w, err)) return zr_fail(c, ZR_ERR_PARSE, err);
-    (void)hipSetDevice(c->device);
-    if (zr_sync_all(c) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "world load: device synchronisation failed");
-    return apply_world_guarded(c, w);
+    return zr_guard(c, [&]() -> int {
+        ZrWorld w; std::string err;
+        if (!world_parse(utf8, len, w, err)) return zr_fail(c, ZR_ERR_PARSE, err);
+        (void)hipSetDevice(c->device);
+        if (zr_sync_all(c) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "world load: device synchronisation failed");
+        return apply_world_guarded(c, w);
+    });
 }
 
 // XkWorld::Save (ZE:1149-1263), PrettyWriter layout (4-space indent).  The engine writes OverrideCubemap from
@@ -430,13 +434,15 @@ static std::string world_to_json(const ZrWorld& w)
 extern "C" int zr_world_save_json(zr_ctx* c, char* dst, size_t cap, size_t* len)
 {
     if (!c || !len) return ZR_ERR_ARG;
-    const std::string o = world_to_json(c->world);
-    *len = o.size();
-    if (dst) {
-        if (cap < o.size()) return zr_fail(c, ZR_ERR_ARG, "buffer too small");
-        memcpy(dst, o.data(), o.size());
-    }
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        const std::string o = world_to_json(c->world);
+        *len = o.size();
+        if (dst) {
+            if (cap < o.size()) return zr_fail(c, ZR_ERR_ARG, "buffer too small");
+            memcpy(dst, o.data(), o.size());
+        }
+        return ZR_OK;
+    });
 }
 
 // Context-free Load -> Save: parses a livelink payload / World.json with the same strictness as zr_world_load_json and
@@ -445,15 +451,17 @@ extern "C" int zr_world_save_json(zr_ctx* c, char* dst, size_t cap, size_t* len)
 extern "C" int zr_world_json_normalize(const char* utf8, size_t len_in, char* dst, size_t cap, size_t* len)
 {
     if (!utf8 || !len) return ZR_ERR_ARG;
-    ZrWorld w; std::string err;
-    const bool ok = world_parse(utf8, len_in, w, err);
-    const std::string o = ok ? world_to_json(w) : err;
-    *len = o.size();
-    if (dst) {
-        if (cap < o.size()) return ZR_ERR_ARG;
-        memcpy(dst, o.data(), o.size());
-    }
-    return ok ? ZR_OK : ZR_ERR_PARSE;
+    return zr_guard(nullptr, [&]() -> int {
+        ZrWorld w; std::string err;
+        const bool ok = world_parse(utf8, len_in, w, err);
+        const std::string o = ok ? world_to_json(w) : err;
+        *len = o.size();
+        if (dst) {
+            if (cap < o.size()) return ZR_ERR_ARG;
+            memcpy(dst, o.data(), o.size());
+        }
+        return ok ? ZR_OK : ZR_ERR_PARSE;
+    });
 }
 
 // UpdateWorld + UpdateUniformBuffer (ZE:4294-4308, 4585-4664) from the loaded world's camera and lights: what the engine does every
@@ -461,29 +469,35 @@ extern "C" int zr_world_json_normalize(const char* utf8, size_t len_in, char* ds
 extern "C" int zr_world_update_uniforms(zr_ctx* c, float roll_stage, float roll_light, float time)
 {
     if (!c) return ZR_ERR_ARG;
-    if (!c->world.loaded) return zr_fail(c, ZR_ERR_STATE, "no world loaded");
-    return world_uniforms(c, c->world, roll_stage, roll_light, time);
+    return zr_guard(c, [&]() -> int {
+        if (!c->world.loaded) return zr_fail(c, ZR_ERR_STATE, "no world loaded");
+        return world_uniforms(c, c->world, roll_stage, roll_light, time);
+    });
 }
 
 extern "C" int zr_world_get_camera(zr_ctx* c, zr_camera* out)
 {
     if (!c || !out) return ZR_ERR_ARG;
-    *out = c->world.MainCamera;
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        *out = c->world.MainCamera;
+        return ZR_OK;
+    });
 }
 
-extern "C" int zr_object_count(zr_ctx* c, uint32_t* n) { if (!c || !n) return ZR_ERR_ARG; *n = (uint32_t)c->objects.size(); return ZR_OK; }
+extern "C" int zr_object_count(zr_ctx* c, uint32_t* n) { if (!c || !n) return ZR_ERR_ARG; return zr_guard(c, [&]() -> int { *n = (uint32_t)c->objects.size(); return ZR_OK; }); }
 
 extern "C" int zr_object_get_instances(zr_ctx* c, uint32_t index, uint32_t* mesh_id, XkInstanceData* dst, uint32_t* n)
 {
     if (!c || !n) return ZR_ERR_ARG;
-    if (index >= c->objects.size()) return zr_fail(c, ZR_ERR_ARG, "bad object index");
-    const ZrSceneObject& o = c->objects[index];
-    if (mesh_id) *mesh_id = o.mesh;
-    *n = o.instanced ? o.n_inst : 0;
-    if (dst && o.instanced && o.host_stale) { int rc = zr_instances_sync_host(c, c->objects[index]); if (rc) return rc; }
-    if (dst && o.instanced) memcpy(dst, o.inst.data(), sizeof(XkInstanceData) * o.n_inst);
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        if (index >= c->objects.size()) return zr_fail(c, ZR_ERR_ARG, "bad object index");
+        const ZrSceneObject& o = c->objects[index];
+        if (mesh_id) *mesh_id = o.mesh;
+        *n = o.instanced ? o.n_inst : 0;
+        if (dst && o.instanced && o.host_stale) { int rc = zr_instances_sync_host(c, c->objects[index]); if (rc) return rc; }
+        if (dst && o.instanced) memcpy(dst, o.inst.data(), sizeof(XkInstanceData) * o.n_inst);
+        return ZR_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ C-ABI: livelink
@@ -493,7 +507,8 @@ extern "C" int zr_object_get_instances(zr_ctx* c, uint32_t index, uint32_t* mesh
 #define XK_LIVELINK_IDLE_MS 2000
 static void livelink_thread(zr_ctx* c)
 {
-    std::vector<char> buf(XK_LIVELINK_RECV_MAX);
+    std::vector<char> buf;
+    try { buf.resize(XK_LIVELINK_RECV_MAX); } catch (...) { fprintf(stderr, "[Socket] out of memory: not serving\n"); return; }
     while (c->ll_run.load()) {
         struct pollfd pfd = { c->ll_listen_fd, POLLIN, 0 };
         const int pr = poll(&pfd, 1, 100);
@@ -501,24 +516,26 @@ static void livelink_thread(zr_ctx* c)
         const int cs = accept(c->ll_listen_fd, nullptr, nullptr);
         if (cs < 0) { fprintf(stderr, "[Socket] accept failed\n"); continue; }      // keep listening, ZE:1676-1679
         ssize_t n = -2;                                                                // -2: timed out / stopping
-        for (int waited = 0; waited < XK_LIVELINK_IDLE_MS && c->ll_run.load(); waited += 100) {
-            struct pollfd cfd = { cs, POLLIN, 0 };
-            const int cr = poll(&cfd, 1, 100);
-            if (cr < 0) { n = -1; break; }
-            if (cr > 0) { n = recv(cs, buf.data(), buf.size(), 0); break; }            // ONE recv per connection, ZE:1683
-        }
-        if (n > 0) {
-            ZrWorld w; std::string err;
-            if (world_parse(buf.data(), (size_t)n, w, err)) {
-                std::lock_guard<std::mutex> g(c->ll_mutex);
-                c->ll_world = std::move(w); c->ll_pending = true;                    // World.bReloadScene = true, ZE:4290
-            } else {
-                // the engine throws on the socket thread here (ZE:1071-1073) and dies; the library logs and keeps serving
-                fprintf(stderr, "%s\n", err.c_str());
+        try {       // (nothing may leave this thread: an exception here would end the host's process)
+            for (int waited = 0; waited < XK_LIVELINK_IDLE_MS && c->ll_run.load(); waited += 100) {
+                struct pollfd cfd = { cs, POLLIN, 0 };
+                const int cr = poll(&cfd, 1, 100);
+                if (cr < 0) { n = -1; break; }
+                if (cr > 0) { n = recv(cs, buf.data(), buf.size(), 0); break; }            // ONE recv per connection, ZE:1683
             }
-        } else if (n == 0) fprintf(stdout, "[Socket] Connection closing...\n");
-        else if (n == -2) fprintf(stderr, "[Socket] client sent nothing: dropped\n");
-        else fprintf(stderr, "[Socket] recv failed\n");
+            if (n > 0) {
+                ZrWorld w; std::string err;
+                if (world_parse(buf.data(), (size_t)n, w, err)) {
+                    std::lock_guard<std::mutex> g(c->ll_mutex);
+                    c->ll_world = std::move(w); c->ll_pending = true;                    // World.bReloadScene = true, ZE:4290
+                } else {
+                    // the engine throws on the socket thread here (ZE:1071-1073) and dies; the library logs and keeps serving
+                    fprintf(stderr, "%s\n", err.c_str());
+                }
+            } else if (n == 0) fprintf(stdout, "[Socket] Connection closing...\n");
+            else if (n == -2) fprintf(stderr, "[Socket] client sent nothing: dropped\n");
+            else fprintf(stderr, "[Socket] recv failed\n");
+        } catch (...) { fprintf(stderr, "[Socket] payload dropped: out of memory or an unexpected exception\n"); }
         shutdown(cs, SHUT_WR);                                                        // no payload is ever sent back, ZE:1699
         close(cs);
     }
@@ -529,50 +546,58 @@ static void livelink_thread(zr_ctx* c)
 extern "C" int zr_livelink_bind_any(zr_ctx* c, int any)
 {
     if (!c) return ZR_ERR_ARG;
-    c->ll_bind_any = any != 0;
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        c->ll_bind_any = any != 0;
+        return ZR_OK;
+    });
 }
 
 extern "C" int zr_livelink_serve(zr_ctx* c, uint16_t port)
 {
     if (!c) return ZR_ERR_ARG;
-    if (c->ll_run.load()) return zr_fail(c, ZR_ERR_STATE, "livelink already serving");
-    const int fd = socket(AF_INET, SOCK_STREAM, IPPROTO_TCP);
-    if (fd < 0) return zr_fail(c, ZR_ERR_IO, "[Socket] socket failed");
-    int one = 1; setsockopt(fd, SOL_SOCKET, SO_REUSEADDR, &one, sizeof one);
-    struct sockaddr_in a; memset(&a, 0, sizeof a);
-    a.sin_family = AF_INET; a.sin_addr.s_addr = htonl(c->ll_bind_any ? INADDR_ANY : INADDR_LOOPBACK); a.sin_port = htons(port);
-    if (bind(fd, (struct sockaddr*)&a, sizeof a) < 0) { close(fd); return zr_fail(c, ZR_ERR_IO, "[Socket] bind failed"); }
-    if (listen(fd, SOMAXCONN) < 0) { close(fd); return zr_fail(c, ZR_ERR_IO, "[Socket] listen failed"); }
-    socklen_t al = sizeof a;
-    if (getsockname(fd, (struct sockaddr*)&a, &al) == 0) c->ll_port = ntohs(a.sin_port);
-    c->ll_listen_fd = fd; c->ll_run.store(true);
-    c->ll_thread = std::thread(livelink_thread, c);
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        if (c->ll_run.load()) return zr_fail(c, ZR_ERR_STATE, "livelink already serving");
+        const int fd = socket(AF_INET, SOCK_STREAM, IPPROTO_TCP);
+        if (fd < 0) return zr_fail(c, ZR_ERR_IO, "[Socket] socket failed");
+        int one = 1; setsockopt(fd, SOL_SOCKET, SO_REUSEADDR, &one, sizeof one);
+        struct sockaddr_in a; memset(&a, 0, sizeof a);
+        a.sin_family = AF_INET; a.sin_addr.s_addr = htonl(c->ll_bind_any ? INADDR_ANY : INADDR_LOOPBACK); a.sin_port = htons(port);
+        if (bind(fd, (struct sockaddr*)&a, sizeof a) < 0) { close(fd); return zr_fail(c, ZR_ERR_IO, "[Socket] bind failed"); }
+        if (listen(fd, SOMAXCONN) < 0) { close(fd); return zr_fail(c, ZR_ERR_IO, "[Socket] listen failed"); }
+        socklen_t al = sizeof a;
+        if (getsockname(fd, (struct sockaddr*)&a, &al) == 0) c->ll_port = ntohs(a.sin_port);
+        c->ll_listen_fd = fd; c->ll_run.store(true);
+        c->ll_thread = std::thread(livelink_thread, c);
+        return ZR_OK;
+    });
 }
 
-extern "C" int zr_livelink_port(zr_ctx* c, uint16_t* port) { if (!c || !port) return ZR_ERR_ARG; *port = c->ll_port; return ZR_OK; }
+extern "C" int zr_livelink_port(zr_ctx* c, uint16_t* port) { if (!c || !port) return ZR_ERR_ARG; return zr_guard(c, [&]() -> int { *port = c->ll_port; return ZR_OK; }); }
 
 extern "C" int zr_livelink_poll(zr_ctx* c, int* reloaded)
 {
     if (!c) return ZR_ERR_ARG;
-    if (reloaded) *reloaded = 0;
-    ZrWorld w; bool have = false;
-    { std::lock_guard<std::mutex> g(c->ll_mutex); if (c->ll_pending) { w = std::move(c->ll_world); c->ll_pending = false; have = true; } }
-    if (!have) return ZR_OK;
-    (void)hipSetDevice(c->device);
-    if (zr_sync_all(c) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "livelink: device synchronisation failed");   // "wait all fences" on both lanes before CreateEngineScene, ZE:1943-1951
-    int rc = apply_world_guarded(c, w);
-    if (rc == ZR_OK && reloaded) *reloaded = 1;
-    return rc;
+    return zr_guard(c, [&]() -> int {
+        if (reloaded) *reloaded = 0;
+        ZrWorld w; bool have = false;
+        { std::lock_guard<std::mutex> g(c->ll_mutex); if (c->ll_pending) { w = std::move(c->ll_world); c->ll_pending = false; have = true; } }
+        if (!have) return ZR_OK;
+        (void)hipSetDevice(c->device);
+        if (zr_sync_all(c) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "livelink: device synchronisation failed");   // "wait all fences" on both lanes before CreateEngineScene, ZE:1943-1951
+        int rc = apply_world_guarded(c, w);
+        if (rc == ZR_OK && reloaded) *reloaded = 1;
+        return rc;
+    });
 }
 
 extern "C" int zr_livelink_stop(zr_ctx* c)
 {
     if (!c) return ZR_ERR_ARG;
-    if (!c->ll_run.load()) return ZR_OK;
-    c->ll_run.store(false);
-    if (c->ll_thread.joinable()) c->ll_thread.join();
-    if (c->ll_listen_fd >= 0) { close(c->ll_listen_fd); c->ll_listen_fd = -1; }
-    return ZR_OK;
+    return zr_guard(c, [&]() -> int {
+        if (!c->ll_run.load()) return ZR_OK;
+        c->ll_run.store(false);
+        if (c->ll_thread.joinable()) c->ll_thread.join();
+        if (c->ll_listen_fd >= 0) { close(c->ll_listen_fd); c->ll_listen_fd = -1; }
+        return ZR_OK;
+    });
 }
