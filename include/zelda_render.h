@@ -173,6 +173,21 @@ int  zr_object_set_instances(zr_ctx* ctx, uint32_t index, uint32_t first, const 
  * of its values.  Both buffers 4-byte aligned.  No host synchronisation (zr_object_get_instances reads back with one). */
 int  zr_object_update_instances_async(zr_ctx* ctx, uint32_t index, uint32_t first, const uint32_t* idx_dev,
                                       const XkInstanceData* data_dev, uint32_t n, void* hip_stream);
+/* Deforming meshes.  Replace vertices [first, first + n) of mesh `mesh_id`, all 44 bytes of each XkVertex.  The
+ * vertex count, the index buffer and the meshlet partition are fixed: only the values move; bounding spheres, normal cones and boxes are
+ * refitted by the library.  Takes effect with the next zr_render; frames already enqueued still draw the old shape; every object that
+ * uses the mesh sees it.  `v` may be reused when the call returns.  The scene does not change (the identity queries go on describing
+ * the last frame).  A mesh no frame has used yet: the host copy is rewritten (and the bounds of meshlets already attached follow).
+ * Between the stages of a frame: ZR_ERR_STATE; a bad mesh id, a range beyond the vertex count, n > 0 with v == NULL: ZR_ERR_ARG, and
+ * the context is unchanged.  The skydome's mesh has no id: zr_set_skydome replaces it. */
+int  zr_mesh_set_vertices(zr_ctx* ctx, uint32_t mesh_id, uint32_t first, const XkVertex* v, uint32_t n);
+/* The same from caller-owned DEVICE memory, in the order of hip_stream (NULL = the render stream).  The library reads v_dev only inside
+ * hip_stream's order: a caller may overwrite it with work enqueued on hip_stream after this call.  v_dev 4-byte aligned (else
+ * ZR_ERR_ARG).  No host synchronisation.  A mesh no frame has used yet has no device copy: ZR_ERR_STATE (use zr_mesh_set_vertices). */
+int  zr_mesh_update_vertices_async(zr_ctx* ctx, uint32_t mesh_id, uint32_t first, const XkVertex* v_dev, uint32_t n, void* hip_stream);
+/* Copy out the mesh's current vertices (dst may be NULL; *n = the vertex count).  After a device-form update this and
+ * zr_mesh_get_meshlets read back with one synchronisation. */
+int  zr_mesh_get_vertices(zr_ctx* ctx, uint32_t mesh_id, XkVertex* dst, uint32_t* n);
 /* 6 RGBA8 sRGB faces in Vulkan layer order +X,-X,+Y,-Y,+Z,-Z (RHICreateTextureCubeResource ZE:5908-6150);
  * mips are generated like RHIGenerateMipmaps (ZE:6348-6433).  faces == NULL: built-in 1x1 grey. */
 int  zr_set_cubemap(zr_ctx* ctx, const uint8_t* const faces[6], uint32_t dim);

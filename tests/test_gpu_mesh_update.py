@@ -1,0 +1,396 @@
+"""Deforming meshes between frames (zr_mesh_set_vertices, zr_mesh_update_vertices_async), bit for bit.
+
+What a context draws after a vertex update must equal what a context built with the final vertices draws: every buffer that depends on
+vertex values is refitted on the device (positions, the resolve's records, boxes, bounding spheres, normal cones, the whole-mesh sphere),
+the work lists are rebuilt, the visibility history, the bucket plan and the shadow flags are kept (the frame does not depend on them),
+and with two frames in flight an update reaches only the frames enqueued after it.  Every comparison of frames is exact.
+"""
+import numpy as np
+import pytest
+
+from parity_util import compare_all
+from test_gpu_instance_update import H, SD, W, _check_queued, _frame, _grab, _instances, _same, _uniforms
+from zeldaengine_amd import abi, dist as zdist, scenes
+
+pytestmark = pytest.mark.gpu
+
+TERRAIN, SPHERE = 1, 2                       # mesh ids (creation order: the ground plane is mesh 0)
+
+
+def _meshes():
+    return scenes.uv_sphere(8, 5), scenes.grid_plane(12.0, 48, 0.02)
+
+
+def _scene(r, inst, sphere_v=None, terrain_v=None):
+    (sv, si), (tv, ti) = _meshes()
+    r.set_cubemap(scenes.synthetic_cubemap(16))
+    r.object_add(r.mesh_create(*scenes.grid_plane(40.0, 4, 0.0)))
+    terrain = r.mesh_create(tv if terrain_v is None else terrain_v, ti)
+    sphere = r.mesh_create(sv if sphere_v is None else sphere_v, si)
+    assert (terrain, sphere) == (TERRAIN, SPHERE)
+    r.object_add(terrain)
+    r.object_add(sphere, None, inst)
+
+
+def _deform_sphere(v, k=1.0):
+    """Stretched to 2.5 k times its radius along x; the upper part turned inside out: positions mirrored in y with the winding (the index
+    buffer) unchanged, so every triangle up there faces the other way and the cones of the old shape would cull what is now visible."""
+    new = v.copy()
+    new["Position"][:, 0] *= np.float32(2.5 * k)
+    up = v["Position"][:, 2] > 0.0
+    new["Position"][up, 1] *= np.float32(-1.0)
+    return new
+
+
+def _deform_terrain(v, k=1.0, at=0.0):
+    """A ridge along y, 1.2 k high: far above the box of the flat grid (z = 0.02)."""
+    new = v.copy()
+    x = v["Position"][:, 0].astype(np.float64)
+    new["Position"][:, 2] += (1.2 * k * np.exp(-(x - at) ** 2 / 0.8)).astype(np.float32)
+    return new
+
+
+def _fresh(gpu_engine, inst, u, sv, tv, flags=0, capture=False):
+    b = gpu_engine.Renderer(W, H, SD, flags=flags)
+    _scene(b, inst, sv, tv)
+    if capture:
+        b.set_id_capture(True)
+    _frame(b, u)
+    out = _grab(b)
+    extra = (b.pick(0, 0, W, H), b.instance_coverage()) if capture else None
+    b.close()
+    return out, extra
+
+
+def _dev(v):
+    import torch
+    return torch.from_numpy(v.view(np.uint8).reshape(-1, 44).copy()).to(torch.device("cuda", 0))
+
+
+@pytest.mark.parametrize("flags", [0, abi.FLAG_SHADOW_OCCLUSION, abi.FLAG_NO_HIZ, abi.FLAG_NO_FRUSTUM_CULL | abi.FLAG_NO_CONE_CULL])
+def test_deformed_meshes_match_a_fresh_context(gpu_engine, flags):
+    """Lists, plan and history stand (two frames), both meshes are deformed through the host form: the next frame and the one after it
+    equal a new context's.  Stale spheres, boxes or cones would cull the stretched ends, the ridge and the part turned inside out."""
+    inst, u = _instances(), _uniforms()
+    (sv, _), (tv, _) = _meshes()
+    a = gpu_engine.Renderer(W, H, SD, flags=flags)
+    _scene(a, inst)
+    for _ in range(2):
+        _frame(a, u)
+    before = _grab(a)
+    assert before[3]["work_items"][1] >= 65536
+    new_s, new_t = _deform_sphere(sv), _deform_terrain(tv)
+    assert np.abs(new_s["Position"][:, 0]).max() >= 2.0 * np.abs(sv["Position"][:, 0]).max()
+    assert new_t["Position"][:, 2].max() > tv["Position"][:, 2].max() + 1.0
+    a.mesh_set_vertices(SPHERE, new_s)
+    a.mesh_set_vertices(TERRAIN, new_t)
+    _frame(a, u)
+    moved = _grab(a)
+    _frame(a, u)
+    again = _grab(a)
+    a.close()
+    fresh, _ = _fresh(gpu_engine, inst, u, new_s, new_t, flags)
+    assert not np.array_equal(before[0], fresh[0])                   # the update shows
+    _same(moved, fresh, "frame after the update")
+    _same(again, fresh, "the frame after that")
+
+
+def test_updates_through_both_forms_match_the_oracle(gpu_engine, oracle_lib):
+    """A small instanced scene whose mesh is updated once through the host form and once through the device form: every target equals
+    the CPU oracle's frame of the final vertices, and zr_mesh_get_vertices returns their bytes."""
+    import torch
+    cfg = scenes.config3(64, 256, 144)
+    g = gpu_engine.Renderer(cfg["width"], cfg["height"], 256)
+    gpu_engine.load_scene(g, cfg)
+    g.render(); g.render()
+    v, idx = cfg["objects"][0]["mesh"]
+    new = v.copy()
+    half = len(v) // 2
+    new["Position"][:half, 0] *= np.float32(1.8)
+    new["Normal"][:half, 1] += np.float32(0.25)
+    new["TexCoord"][:half] *= np.float32(0.5)
+    g.mesh_set_vertices(0, new[:half])
+    new["Position"][half:, 2] += np.float32(0.3) * np.sin(new["Position"][half:, 0] * np.float32(9.0))
+    new["Position"][half:, 1] *= np.float32(-1.0)
+    data = _dev(new[half:])
+    torch.cuda.synchronize()
+    g.mesh_update_vertices_async(0, data, first=half)
+    g.render()
+    g.finish()
+    assert np.array_equal(g.mesh_get_vertices(0).view(np.uint8), new.view(np.uint8))
+    cfg["objects"][0]["mesh"] = (new, idx)
+    o = oracle_lib.Oracle(cfg["width"], cfg["height"], 256)
+    oracle_lib.load_scene(o, cfg)
+    o.render()
+    assert o.covered_pixels() > 100
+    diffs = compare_all(o, g)
+    assert all(x == 0 for x in diffs.values()), diffs
+    g.close()
+
+
+def _steps(frames):
+    (sv, _), (tv, _) = _meshes()
+    return [(_deform_sphere(sv, 0.5 + 0.08 * i), _deform_terrain(tv, 0.3 + 0.06 * i, -3.0 + 0.45 * i)) for i in range(frames)]
+
+
+def _serial_frames(gpu_engine, steps, flags):
+    """The reference: one stream, both meshes set before every frame, finish() after it."""
+    inst, u = _instances(), _uniforms()
+    ref = gpu_engine.Renderer(W, H, SD, flags=flags | abi.FLAG_SERIAL_PASSES)
+    _scene(ref, inst)
+    want = []
+    for new_s, new_t in steps:
+        ref.mesh_set_vertices(SPHERE, new_s)
+        ref.mesh_set_vertices(TERRAIN, new_t)
+        _frame(ref, u)
+        ref.finish()
+        want.append((ref.color().copy(), ref.shadowmap().view(np.uint32).copy()))
+    assert ref.stats()["work_items"][0] >= 65536
+    ref.close()
+    return want
+
+
+@pytest.mark.parametrize("form,flags", [("host", 0), ("device", 0), ("host", abi.FLAG_SHADOW_OCCLUSION)])
+def test_updates_between_queued_frames(gpu_engine, form, flags):
+    """14 frames back to back, each after an update of both meshes, copied out on the device; no finish() until all are enqueued.
+    Every frame equals the serial context's: an update reaches the frames after it and none before (two frames in flight, two sets)."""
+    import torch
+    FRAMES = 14
+    inst, u = _instances(), _uniforms()
+    steps = _steps(FRAMES)
+    want = _serial_frames(gpu_engine, steps, flags)
+    assert not np.array_equal(want[0][0], want[-1][0])
+    g = gpu_engine.Renderer(W, H, SD, flags=flags)
+    _scene(g, inst)
+    dev = torch.device("cuda", 0)
+    got = [(torch.zeros(W * H, dtype=torch.int32, device=dev), torch.zeros(SD * SD, dtype=torch.int32, device=dev)) for _ in range(FRAMES)]
+    tensors = [(_dev(s), _dev(t)) for s, t in steps] if form == "device" else None
+    if form == "device":                   # (a mesh has a device copy from its first frame on)
+        _frame(g, u)
+    torch.cuda.synchronize()
+    for i in range(FRAMES):
+        if form == "host":
+            g.mesh_set_vertices(SPHERE, steps[i][0])
+            g.mesh_set_vertices(TERRAIN, steps[i][1][100:2000], 100)
+            g.mesh_set_vertices(TERRAIN, steps[i][1][:100])
+            g.mesh_set_vertices(TERRAIN, steps[i][1][2000:], 2000)
+        else:
+            g.mesh_update_vertices_async(SPHERE, tensors[i][0])
+            g.mesh_update_vertices_async(TERRAIN, tensors[i][1])
+        _frame(g, u)
+        g.copy_frame_async(got[i][0].data_ptr(), got[i][1].data_ptr())
+    g.finish()
+    assert g.stats()["overflow"] == 0
+    _check_queued(got, want)
+    assert np.array_equal(g.mesh_get_vertices(TERRAIN).view(np.uint8), steps[-1][1].view(np.uint8))
+    assert np.array_equal(g.mesh_get_vertices(SPHERE).view(np.uint8), steps[-1][0].view(np.uint8))
+    g.close()
+
+
+def test_device_update_from_a_torch_stream(gpu_engine):
+    """The device form fed from a tensor that a torch kernel writes on a side stream, with no host synchronisation between the torch
+    work and the call; the tensor is overwritten behind the call on that stream.  The frame equals the host form's of the same bytes."""
+    import torch
+    inst, u = _instances(), _uniforms()
+    (_, _), (tv, _) = _meshes()
+    dev = torch.device("cuda", 0)
+    g = gpu_engine.Renderer(W, H, SD)
+    _scene(g, inst)
+    _frame(g, u); _frame(g, u)
+    base = torch.from_numpy(tv.view(np.float32).reshape(-1, 11).copy()).to(dev)
+    keep = torch.empty_like(base)
+    ts = torch.cuda.Stream(device=dev)
+    torch.cuda.synchronize()
+    with torch.cuda.stream(ts):
+        d = base.clone()
+        for _ in range(20):                  # (enough work that the call below comes before the values exist)
+            d[:, 2] = d[:, 2] * 0.9 + 0.11 * torch.cos(d[:, 0] * 1.7) ** 2
+        keep.copy_(d)
+        g.mesh_update_vertices_async(TERRAIN, d, stream=ts)
+        d.fill_(1e9)                         # overwritten behind the call, on its stream
+    _frame(g, u)
+    got = _grab(g)
+    ts.synchronize()
+    final = keep.cpu().numpy().view(abi.XkVertex).reshape(-1)
+    assert final["Position"][:, 2].max() > 0.3
+    assert np.array_equal(g.mesh_get_vertices(TERRAIN).view(np.uint8), final.view(np.uint8))
+    g.close()
+    h = gpu_engine.Renderer(W, H, SD)
+    _scene(h, inst)
+    _frame(h, u); _frame(h, u)
+    h.mesh_set_vertices(TERRAIN, final)
+    _frame(h, u)
+    _same(got, _grab(h), "device form from a torch stream against the host form")
+    h.close()
+
+
+def _check_bounds(ml, mv, mt, v, what):
+    """float64: every meshlet vertex within its sphere (relative margin 1e-5, as zr_mesh_set_meshlets allows); for a cutoff < 1 every
+    triangle normal n has dot(n, axis) >= sqrt(1 - cutoff^2) - 1e-6; every cutoff in (0, 1]."""
+    pos = v["Position"].astype(np.float64)
+    assert len(ml) > 0
+    for i, m in enumerate(ml):
+        vi = mv[m["VertexOffset"]:m["VertexOffset"] + m["VertexCount"]]
+        d = np.linalg.norm(pos[vi] - m["BoundsCenter"].astype(np.float64), axis=1)
+        assert (d <= float(m["BoundsRadius"]) * (1.0 + 1e-5) + 1e-30).all(), "%s: meshlet %d: a vertex %.9g from the centre, radius %.9g" % (
+            what, i, d.max(), m["BoundsRadius"])
+        cut = float(m["ConeCutoff"])
+        assert 0.0 < cut <= 1.0, "%s: meshlet %d: cutoff %r" % (what, i, cut)
+        if cut < 1.0:
+            tri = mt[m["TriangleOffset"]:m["TriangleOffset"] + 3 * m["TriangleCount"]].reshape(-1, 3)
+            p = pos[vi[tri]]
+            n = np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])
+            ln = np.linalg.norm(n, axis=1)
+            n = n[ln > 0] / ln[ln > 0, None]
+            dp = n @ m["ConeAxis"].astype(np.float64)
+            assert (dp >= np.sqrt(1.0 - cut * cut) - 1e-6).all(), "%s: meshlet %d: a normal at %.9g of the axis, cutoff %.9g" % (what, i, dp.min(), cut)
+
+
+def test_refitted_bounds_are_sound(gpu_engine):
+    """After a device-form update the meshlets and vertices are read back: once before any frame (the host's statement of the bounds, from
+    the vertices read back) and once after a frame (the records k_mesh_refit wrote).  Both are sound; whether they are equal is printed
+    (DESIGN.md §5 reports it)."""
+    import torch
+    inst, u = _instances(), _uniforms()
+    (sv, _), (tv, _) = _meshes()
+    g = gpu_engine.Renderer(W, H, SD)
+    _scene(g, inst)
+    _frame(g, u); _frame(g, u)
+    news = {SPHERE: _deform_sphere(sv), TERRAIN: _deform_terrain(tv)}
+    tensors = {k: _dev(x) for k, x in news.items()}
+    torch.cuda.synchronize()
+    for k, t in tensors.items():
+        g.mesh_update_vertices_async(k, t)
+    host = {k: g.mesh_get_meshlets(k) for k in news}
+    _frame(g, u)
+    g.finish()
+    assert g.stats()["overflow"] == 0
+    for k, new in news.items():
+        v = g.mesh_get_vertices(k)
+        assert np.array_equal(v.view(np.uint8), new.view(np.uint8))
+        ml, mv, mt = g.mesh_get_meshlets(k)
+        assert np.array_equal(mv, host[k][1]) and np.array_equal(mt, host[k][2])
+        for f in ("VertexOffset", "VertexCount", "TriangleOffset", "TriangleCount"):
+            assert np.array_equal(ml[f], host[k][0][f])
+        _check_bounds(ml, mv, mt, v, "mesh %d, refitted on the device" % k)
+        _check_bounds(host[k][0], mv, mt, v, "mesh %d, host statement" % k)
+        same = np.array_equal(ml.view(np.uint8), host[k][0].view(np.uint8))
+        print("mesh %d: %d meshlets, device refit %s the host statement" % (k, len(ml), "EQUALS" if same else "DIFFERS FROM"))
+    g.close()
+
+
+def test_identity_queries_follow_a_deformed_mesh(gpu_engine):
+    """An update leaves the scene as it is: the identity queries keep describing the last frame (scene_gen unchanged, no ZR_ERR_STATE);
+    after the next frame pick and the instance coverage equal a fresh context's."""
+    inst, u = _instances(), _uniforms()
+    (sv, _), (tv, _) = _meshes()
+    g = gpu_engine.Renderer(W, H, SD)
+    _scene(g, inst)
+    g.set_id_capture(True)
+    _frame(g, u); _frame(g, u)
+    g.finish()
+    cov_before = g.instance_coverage()
+    hits_before = g.pick(0, 0, W, H)
+    new_s, new_t = _deform_sphere(sv), _deform_terrain(tv)
+    g.mesh_set_vertices(SPHERE, new_s)
+    g.mesh_set_vertices(TERRAIN, new_t)
+    assert np.array_equal(g.instance_coverage(), cov_before)         # (no frame since the update: the answer is the last frame's)
+    again = g.pick(0, 0, W, H)
+    assert again[1] == hits_before[1] and np.array_equal(again[0].view(np.uint8), hits_before[0].view(np.uint8))
+    _frame(g, u)
+    g.finish()
+    hits, cov = g.pick(0, 0, W, H), g.instance_coverage()
+    assert int(cov.sum()) == g.stats()["covered_pixels"]
+    g.close()
+    _, (want_hits, want_cov) = _fresh(gpu_engine, inst, u, new_s, new_t, capture=True)
+    assert np.array_equal(cov, want_cov) and not np.array_equal(cov, cov_before)
+    assert hits[1] == want_hits[1] and np.array_equal(hits[0].view(np.uint8), want_hits[0].view(np.uint8))
+
+
+def test_bad_updates_are_refused_and_change_nothing(gpu_engine):
+    """Every refusal of the header, each followed by a frame that equals the frame before it; an update holding a NaN position is taken
+    (ZR_OK, no overflow) and a following finite update brings the frame back to a fresh context's."""
+    import torch
+    from zeldaengine_amd.engine import ZeldaRenderError
+    inst, u = _instances(), _uniforms()
+    (sv, si), (tv, _) = _meshes()
+    g = gpu_engine.Renderer(W, H, SD)
+    _scene(g, inst)
+    _frame(g, u); _frame(g, u)
+    base = _grab(g)
+    new_s = _deform_sphere(sv)
+    data = _dev(new_s)
+    odd = torch.zeros(44 * 4 + 8, dtype=torch.uint8, device=data.device)
+    torch.cuda.synchronize()
+    unused = g.mesh_create(sv, si)                                   # a mesh no frame has used
+    calls = [(lambda: g.mesh_set_vertices(99, new_s), abi.ERR_ARG),                                    # no such mesh
+             (lambda: g.mesh_update_vertices_async(99, data), abi.ERR_ARG),
+             (lambda: g.mesh_set_vertices(SPHERE, new_s, 1), abi.ERR_ARG),                             # [1, nv + 1)
+             (lambda: g.mesh_update_vertices_async(SPHERE, data, first=len(sv) - 2), abi.ERR_ARG),
+             (lambda: g._chk(g.L.zr_mesh_set_vertices(g.h, SPHERE, 0, None, 4)), abi.ERR_ARG),         # n > 0, no data
+             (lambda: g.mesh_update_vertices_async(SPHERE, 0, n=4), abi.ERR_ARG),
+             (lambda: g.mesh_update_vertices_async(SPHERE, odd.data_ptr() + 2, n=4), abi.ERR_ARG),     # misaligned
+             (lambda: g.mesh_update_vertices_async(unused, data), abi.ERR_STATE)]                      # not uploaded
+    for k, (call, code) in enumerate(calls):
+        with pytest.raises(ZeldaRenderError) as e:
+            call()
+        assert e.value.code == code, (k, e.value)
+        if code == abi.ERR_STATE:
+            assert "zr_mesh_set_vertices" in str(e.value)
+        _frame(g, u)
+        _same(_grab(g), base, "the frame after refusal %d" % k)
+    g.mesh_set_vertices(unused, new_s)                               # (the host form takes it: the host copy is rewritten)
+    assert np.array_equal(g.mesh_get_vertices(unused).view(np.uint8), new_s.view(np.uint8))
+    cam, d, p, s = u
+    g.update_uniforms(cam, d, p, s, 0.0, 0.0, 1.0)
+    g.render_shadow()
+    for call in (lambda: g.mesh_set_vertices(SPHERE, new_s), lambda: g.mesh_update_vertices_async(SPHERE, data)):
+        with pytest.raises(ZeldaRenderError) as e:
+            call()
+        assert e.value.code == abi.ERR_STATE
+    g.render_gbuffer(); g.render_lighting()
+    _frame(g, u)
+    # (images only: the statistics block of a frame that follows a staged frame counts differently, with or without updates)
+    _same(_grab(g), base, "after updates refused between the stages", stats=False)
+    assert np.array_equal(g.mesh_get_vertices(SPHERE).view(np.uint8), sv.view(np.uint8))
+    bad = new_s.copy()
+    bad["Position"][7, 1] = np.float32("nan")
+    g.mesh_set_vertices(SPHERE, bad)
+    _frame(g, u)
+    g.finish()
+    assert g.stats()["overflow"] == 0
+    ml = g.mesh_get_meshlets(SPHERE)[0]
+    assert np.isinf(ml["BoundsRadius"]).any() and (ml["ConeCutoff"][np.isinf(ml["BoundsRadius"])] == 1.0).all()
+    g.mesh_set_vertices(SPHERE, new_s)
+    _frame(g, u)
+    got = _grab(g)
+    g.close()
+    fresh, _ = _fresh(gpu_engine, inst, u, new_s, tv)
+    _same(got, fresh, "a finite update after one with a NaN")
+
+
+def test_rank_contexts_take_the_same_update(gpu_engine):
+    """tile_world = 4: every rank takes the same update; the ranks' owned tiles equal the single context's frame."""
+    inst, u = _instances(), _uniforms()
+    (sv, _), (tv, _) = _meshes()
+    new_s, new_t = _deform_sphere(sv), _deform_terrain(tv)
+    single = gpu_engine.Renderer(W, H, SD)
+    _scene(single, inst)
+    _frame(single, u); _frame(single, u)
+    single.mesh_set_vertices(SPHERE, new_s)
+    single.mesh_set_vertices(TERRAIN, new_t)
+    _frame(single, u)
+    want = _grab(single)[0]
+    single.close()
+    world = 4
+    for r in range(world):
+        g = gpu_engine.Renderer(W, H, SD, tile_rank=r, tile_world=world)
+        _scene(g, inst)
+        _frame(g, u); _frame(g, u)
+        g.mesh_set_vertices(SPHERE, new_s)
+        g.mesh_set_vertices(TERRAIN, new_t)
+        _frame(g, u)
+        g.finish()
+        assert g.stats()["overflow"] == 0
+        assert np.array_equal(g.read_tiles(), zdist.pack_tiles(want, r, world)), "rank %d" % r
+        g.close()

@@ -82,6 +82,10 @@ struct ZrMesh {
     float center[3] = { 0, 0, 0 }; float radius = 0;
     XkVertex* d_v = nullptr; ZrRVertex* d_rv = nullptr; ZrRVertex* d_rt = nullptr; uint32_t* d_idx = nullptr; XkMeshlet* d_meshlets = nullptr;
     float4* d_mpos = nullptr; float4* d_mbox = nullptr; uint2* d_mtri = nullptr; uint32_t* d_tri_meshlet = nullptr;
+    // Vertex updates (zr_mesh_update_host.cpp), set up at the mesh's first update: upd.set[0] = the buffers above, set[1] their parity-1
+    // twins, upd.raw what the update calls write.  stale[p]: set p is older than raw (the next frame of parity p refits it);
+    // v_stale = a device-form update came after `v`; ml_stale = ms.meshlets' bounds are not yet the device's of the current vertices.
+    ZrMeshState upd = {}; bool stale[2] = { false, false }, v_stale = false, ml_stale = false;
 };
 
 // Host form of one material: per slot either a constant texel or an RGBA8 image (mips are built at zr_object_add).
@@ -164,7 +168,7 @@ struct zr_ctx {
     hipEvent_t ev_scatter = nullptr, ev_apply = nullptr; hipStream_t scatter_s = nullptr, apply_s = nullptr;
     bool scatter_wait[2] = { false, false }, apply_done = false, inst_dual = false;      // scatter_wait[p]: the next frame of parity p waits for ev_scatter
     static constexpr int INST_RING = 4;
-    struct InstStage { ZrOwn mem; XkInstanceData* h = nullptr; XkInstanceData* d = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; } inst_ring[INST_RING];
+    struct InstStage { ZrOwn mem; uint8_t* h = nullptr; uint8_t* d = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; } inst_ring[INST_RING];      // cap: bytes
     uint32_t inst_slot = 0;
     // this frame's two geometry passes (0 shadow, 1 camera), built at frame begin; the passes' work lists (k_cull_instances) are kept
     // while the pass block and the scene stand still: list_key = the block the list on the device was built from
@@ -280,6 +284,14 @@ int zr_fail(zr_ctx* c, int code, const std::string& msg);      // records the me
 int zr_instances_frame(zr_ctx* c, hipStream_t s, int par);       // frame head: this frame's draw table, the updates that are due
 int zr_instances_table(zr_ctx* c);                               // finalize_scene: the parity-1 table of a new draw table
 int zr_instances_sync_host(zr_ctx* c, ZrSceneObject& o);         // zr_object_get_instances after a device-form update
+int zr_update_begin(zr_ctx* c, hipStream_t x);                   // an update's scatter on x: behind the last apply / refit and the last update
+int zr_update_end(zr_ctx* c, hipStream_t x);                     // ... and the frames of both parities behind it
+int zr_update_stage(zr_ctx* c, hipStream_t x, const void* src, size_t bytes, void** dev, hipEvent_t* ev);      // the pinned staging ring
+// zr_mesh_update_host.cpp
+bool zr_mesh_update_due(const zr_ctx* c, int par);               // some mesh's set of this parity is stale
+int zr_mesh_update_frame(zr_ctx* c, hipStream_t s, int par);     // frame head (zr_instances_frame): refit them, point the table at them
+bool zr_mesh_update_table(zr_ctx* c);                            // finalize_scene: new draw tables; true = the scene needs the parity-1 table
+int zr_mesh_sync_host(zr_ctx* c, ZrMesh& m, bool meshlets);      // zr_mesh_get_vertices / _get_meshlets after an update
 // No exception crosses the C-ABI: every exported function that returns a status runs its body through this, behind nothing but its
 // bare argument checks (tests/test_abi_and_symbols.py holds the sources to it).
 template <typename F> static inline int zr_guard(zr_ctx* c, F&& body) noexcept

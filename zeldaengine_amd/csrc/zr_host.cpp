@@ -401,7 +401,8 @@ extern "C" int zr_mesh_get_meshlets(zr_ctx* c, uint32_t mesh_id, XkMeshlet* ml, 
     if (!c) return ZR_ERR_ARG;
     return zr_guard(c, [&]() -> int {
         ARGCHK(c, mesh_id < c->meshes.size());
-        const ZrMesh& m = c->meshes[mesh_id];
+        ZrMesh& m = c->meshes[mesh_id];
+        if (ml) { int rc = zr_mesh_sync_host(c, m, true); if (rc) return rc; }      // (after vertex updates: the bounds of the current vertices)
         if (nm) *nm = (uint32_t)m.ms.meshlets.size();
         if (nmv) *nmv = m.ms.mverts.size();
         if (nmt) *nmt = m.ms.mtris.size();

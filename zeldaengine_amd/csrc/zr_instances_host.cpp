@@ -6,6 +6,9 @@
 // the last frame that read plane p has finished.  So a frame already enqueued keeps the values it was enqueued with, and no update waits
 // for a frame.  Raw values are written by k_instance_scatter and read by k_instance_apply: every scatter is ordered after the last apply
 // (ev_apply), and every apply after the last scatter (ev_scatter).
+//
+// Vertex updates (zr_mesh_update_host.cpp) keep the same contract with the same events, tables and staging ring: their scatter is
+// bracketed by zr_update_begin / zr_update_end, their refit runs in zr_instances_frame beside the applies.
 #include <algorithm>
 #include <cstring>
 
@@ -38,13 +41,58 @@ static int inst_init_object(zr_ctx* c, ZrSceneObject& o, hipStream_t x)
     HIPCHK(c, hipMemsetAsync(S.count, 0, 2 * sizeof(uint32_t), x));
     // (plane 0 is written only by applies of this object, and there has been none)
     HIPCHK(c, hipMemcpyAsync(S.plane[1], o.d_inst, n * sizeof(ZrInstance), hipMemcpyDeviceToDevice, x));
+    return ZR_OK;
+}
+
+// An update's scatter on stream x, first half: the context's update state; the parity-1 draw table; x behind the last apply (it read
+// the raw values) and the last update (updates land in call order)
+int zr_update_begin(zr_ctx* c, hipStream_t x)
+{
+    int rc = inst_init_ctx(c);
+    if (rc) return rc;
     if (!c->inst_dual && !c->scene_dirty) {
-        // the parity-1 draw table: table 0 as it stands (nothing writes it); the frame head points it at the parity-1 planes.  (A dirty
-        // scene gets both tables from finalize_scene, before its next frame.)
+        // the parity-1 draw table: table 0 as it stands (nothing writes it); the frame head points it at the parity-1 planes and mesh
+        // sets.  (A dirty scene gets both tables from finalize_scene, before its next frame.)
         HIPCHK(c, c->tables.alloc(&c->d_objs_b[1], c->n_objs));
         HIPCHK(c, hipMemcpyAsync(c->d_objs_b[1], c->d_objs_b[0], (size_t)c->n_objs * sizeof(ZrObject), hipMemcpyDeviceToDevice, x));
         c->inst_dual = true;
     }
+    if (c->apply_done && c->apply_s != x) HIPCHK(c, hipStreamWaitEvent(x, c->ev_apply, 0));
+    if (c->scatter_s && c->scatter_s != x) HIPCHK(c, hipStreamWaitEvent(x, c->ev_scatter, 0));
+    return ZR_OK;
+}
+
+// ... second half, behind the scatter kernel: the next frame of either parity waits for it
+int zr_update_end(zr_ctx* c, hipStream_t x)
+{
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev_scatter, x));
+    c->scatter_s = x; c->scatter_wait[0] = c->scatter_wait[1] = true;
+    // The passes' work lists (k_cull_instances) hold the instances that passed the whole-mesh test: rebuilt by the next frame.  The visibility
+    // history, the bucket plan and the shadow flags stay: the frame does not depend on them (DESIGN.md §5).
+    c->list_valid[0] = c->list_valid[1] = false;
+    return ZR_OK;
+}
+
+// Host data through the pinned staging ring: `bytes` of src copied to a device slot on x (*dev); the caller records *ev behind the
+// kernel that reads the slot.  src may be reused on return.
+int zr_update_stage(zr_ctx* c, hipStream_t x, const void* src, size_t bytes, void** dev, hipEvent_t* ev)
+{
+    int rc = inst_init_ctx(c);
+    if (rc) return rc;
+    zr_ctx::InstStage& r = c->inst_ring[c->inst_slot++ % zr_ctx::INST_RING];
+    HIPCHK(c, hipEventSynchronize(r.ev));          // the copy and the scatter that used this slot last are done
+    if (r.cap < bytes) {
+        r.mem.release(); r.h = nullptr; r.d = nullptr;
+        r.cap = 0;
+        size_t cap = 4096 * sizeof(XkInstanceData); while (cap < bytes) cap *= 2;
+        HIPCHK(c, r.mem.host(&r.h, cap));
+        HIPCHK(c, r.mem.alloc(&r.d, cap));
+        r.cap = cap;
+    }
+    memcpy(r.h, src, bytes);
+    HIPCHK(c, hipMemcpyAsync(r.d, r.h, bytes, hipMemcpyHostToDevice, x));
+    *dev = r.d; *ev = r.ev;
     return ZR_OK;
 }
 
@@ -66,17 +114,12 @@ static int inst_enqueue(zr_ctx* c, ZrSceneObject& o, hipStream_t x, const uint32
 {
     int rc = inst_init_ctx(c);
     if (rc == ZR_OK) rc = inst_init_object(c, o, x);
+    if (rc == ZR_OK) rc = zr_update_begin(c, x);
     if (rc) return rc;
-    if (c->apply_done && c->apply_s != x) HIPCHK(c, hipStreamWaitEvent(x, c->ev_apply, 0));       // it read the raw values
-    if (c->scatter_s && c->scatter_s != x) HIPCHK(c, hipStreamWaitEvent(x, c->ev_scatter, 0));    // updates land in call order
     zr_launch_instance_scatter(idx, data, first, n, o.upd, x);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_scatter, x));
-    c->scatter_s = x; c->scatter_wait[0] = c->scatter_wait[1] = true;
+    rc = zr_update_end(c, x);
+    if (rc) return rc;
     for (auto& p : o.pending) p = (uint32_t)std::min<uint64_t>(o.n_inst, (uint64_t)p + n);
-    // The passes' work lists (k_cull_instances) hold the instances that passed the whole-mesh test: rebuilt by the next frame.  The visibility
-    // history, the bucket plan and the shadow flags stay: the frame does not depend on them (DESIGN.md §5).
-    c->list_valid[0] = c->list_valid[1] = false;
     return ZR_OK;
 }
 
@@ -90,26 +133,15 @@ extern "C" int zr_object_set_instances(zr_ctx* c, uint32_t index, uint32_t first
         if (n == 0) return ZR_OK;
         if (!data) return zr_fail(c, ZR_ERR_ARG, "zr_object_set_instances: no data");
         HIPCHK(c, hipSetDevice(c->device));
-        rc = inst_init_ctx(c);
-        if (rc) return rc;
         // the camera lane: an update that follows frame k is then ordered behind frame k's camera pipeline and ahead of frame k + 1's, with no
         // extra wait on the host's stream, where frame k's lighting runs
         hipStream_t x = c->cam_s ? c->cam_s : c->stream;
-        zr_ctx::InstStage& r = c->inst_ring[c->inst_slot++ % zr_ctx::INST_RING];
-        HIPCHK(c, hipEventSynchronize(r.ev));          // the copy and the scatter that used this slot last are done
-        if (r.cap < n) {
-            r.mem.release(); r.h = nullptr; r.d = nullptr;
-            r.cap = 0;
-            size_t cap = 4096; while (cap < n) cap *= 2;
-            HIPCHK(c, r.mem.host(&r.h, cap));
-            HIPCHK(c, r.mem.alloc(&r.d, cap));
-            r.cap = cap;
-        }
-        memcpy(r.h, data, (size_t)n * sizeof(XkInstanceData));
-        HIPCHK(c, hipMemcpyAsync(r.d, r.h, (size_t)n * sizeof(XkInstanceData), hipMemcpyHostToDevice, x));
-        rc = inst_enqueue(c, *o, x, nullptr, r.d, first, n);
+        void* staged = nullptr; hipEvent_t ev = nullptr;
+        rc = zr_update_stage(c, x, data, (size_t)n * sizeof(XkInstanceData), &staged, &ev);
         if (rc) return rc;
-        HIPCHK(c, hipEventRecord(r.ev, x));
+        rc = inst_enqueue(c, *o, x, nullptr, (const XkInstanceData*)staged, first, n);
+        if (rc) return rc;
+        HIPCHK(c, hipEventRecord(ev, x));
         if (!o->host_stale) memcpy(o->inst.data() + first, data, (size_t)n * sizeof(XkInstanceData));      // (else the read-back brings it)
         return ZR_OK;
     });
@@ -152,6 +184,7 @@ int zr_instances_table(zr_ctx* c)
     c->inst_reader[0] = c->inst_reader[1] = 0;      // (nothing is in flight)
     bool any = false;
     for (auto& o : c->objects) { o.tab1 = false; any |= o.upd.plane[1] != nullptr; }
+    any |= zr_mesh_update_table(c);      // (meshes with a second set: both tables get their pointers and spheres from the next refits)
     if (!any) return ZR_OK;
     HIPCHK(c, c->tables.alloc(&c->d_objs_b[1], c->n_objs));
     HIPCHK(c, hipMemcpy(c->d_objs_b[1], c->d_objs_b[0], (size_t)c->n_objs * sizeof(ZrObject), hipMemcpyDeviceToDevice));
@@ -168,6 +201,8 @@ int zr_instances_frame(zr_ctx* c, hipStream_t s, int par)
     }
     bool work = false;
     for (const auto& o : c->objects) work |= o.pending[par] != 0 || (par == 1 && o.upd.plane[1] && !o.tab1);
+    const bool refit = zr_mesh_update_due(c, par);
+    work |= refit;
     if (c->scatter_wait[par]) {       // the raw values and lists as the last update left them
         if (c->scatter_s != s) HIPCHK(c, hipStreamWaitEvent(s, c->ev_scatter, 0));
         c->scatter_wait[par] = false;
@@ -189,6 +224,7 @@ int zr_instances_frame(zr_ctx* c, hipStream_t s, int par)
                 o.pending[par] = 0;
             }
         }
+        if (refit) { const int rc = zr_mesh_update_frame(c, s, par); if (rc) return rc; }      // this parity's set of every stale mesh
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipEventRecord(c->ev_apply, s));
         c->apply_s = s; c->apply_done = true;

@@ -8,6 +8,7 @@
 // meshlet, bounds that enclose, and a normal cone per meshoptimizer's published definition
 // (cutoff = sqrt(1 - mindp^2), 1 when the cone is wider than ~84 degrees).
 #include "zr_meshlet.h"
+#include "zr_bounds.h"
 
 #include <algorithm>
 #include <cmath>
@@ -28,62 +29,8 @@ typedef std::vector<std::vector<uint32_t>> Partition;       // triangle indices 
 
 void zr_meshlet_bounds(const XkVertex* verts, const uint32_t* mv, uint32_t nv, const uint8_t* mt, uint32_t nt, XkMeshlet* out)
 {
-    // bounding sphere: Ritter's two-pass sphere over the meshlet's vertices, then inflated to enclose exactly
-    V3 c = { 0, 0, 0 };
-    double r = 0;
-    if (nv) {
-        V3 p0 = pos(verts[mv[0]]);
-        uint32_t a = 0, b = 0; double best = -1;
-        for (uint32_t i = 0; i < nv; ++i) { V3 d = pos(verts[mv[i]]) - p0; double l = dot(d, d); if (l > best) { best = l; a = i; } }
-        V3 pa = pos(verts[mv[a]]); best = -1;
-        for (uint32_t i = 0; i < nv; ++i) { V3 d = pos(verts[mv[i]]) - pa; double l = dot(d, d); if (l > best) { best = l; b = i; } }
-        V3 pb = pos(verts[mv[b]]);
-        c = (pa + pb) * 0.5; r = std::sqrt(best) * 0.5;
-        for (uint32_t i = 0; i < nv; ++i) {
-            V3 d = pos(verts[mv[i]]) - c; double l = std::sqrt(dot(d, d));
-            if (l > r) { double nr = (r + l) * 0.5; c = c + d * ((nr - r) / l); r = nr; }
-        }
-        float cf[3] = { (float)c.x, (float)c.y, (float)c.z };
-        double rr = 0;
-        for (uint32_t i = 0; i < nv; ++i) {
-            const float* p = verts[mv[i]].Position;
-            double dx = (double)p[0] - cf[0], dy = (double)p[1] - cf[1], dz = (double)p[2] - cf[2];
-            rr = std::max(rr, std::sqrt(dx * dx + dy * dy + dz * dz));
-        }
-        r = rr;
-    }
-    out->BoundsCenter[0] = (float)c.x; out->BoundsCenter[1] = (float)c.y; out->BoundsCenter[2] = (float)c.z;
-    out->BoundsRadius = std::nextafter((float)(r * (1.0 + 1e-6)), INFINITY);
-
-    // normal cone
-    V3 axis = { 0, 0, 0 };
-    std::vector<V3> n(nt);
-    for (uint32_t t = 0; t < nt; ++t) {
-        V3 a = pos(verts[mv[mt[3 * t]]]), b = pos(verts[mv[mt[3 * t + 1]]]), d = pos(verts[mv[mt[3 * t + 2]]]);
-        V3 nn = cross(b - a, d - a);
-        double l = std::sqrt(dot(nn, nn));
-        n[t] = l > 0 ? nn * (1.0 / l) : V3{ 0, 0, 0 };
-        axis = axis + n[t];
-    }
-    double al = std::sqrt(dot(axis, axis));
-    double mindp = 1.0;
-    if (al > 0) {
-        axis = axis * (1.0 / al);
-        for (uint32_t t = 0; t < nt; ++t) mindp = std::min(mindp, dot(n[t], axis));
-    } else { axis = { 1, 0, 0 }; mindp = -1.0; }
-    out->ConeAxis[0] = (float)axis.x; out->ConeAxis[1] = (float)axis.y; out->ConeAxis[2] = (float)axis.z;
-    // degenerate cluster (cone wider than a hemisphere, or nearly so): cutoff 1 = never culled
-    out->ConeCutoff = (mindp <= 0.1) ? 1.0f : std::nextafter((float)std::sqrt(1.0 - mindp * mindp), 2.0f);
-    // apex: meshoptimizer backs the centre off along the axis far enough to see every triangle's back side
-    double maxt = 0;
-    if (mindp > 0.1)
-        for (uint32_t t = 0; t < nt; ++t) {
-            V3 a = pos(verts[mv[mt[3 * t]]]);
-            double dc = dot(c - a, n[t]), dn = dot(axis, n[t]);
-            if (dn > 1e-12) maxt = std::max(maxt, dc / dn);
-        }
-    V3 apex = c - axis * maxt;
-    out->ConeApex[0] = (float)apex.x; out->ConeApex[1] = (float)apex.y; out->ConeApex[2] = (float)apex.z;
+    // (the statement itself: zr_bounds.h, shared with the device's refit after a vertex update)
+    zr_meshlet_bounds_of(verts, mv, nv, [mt](uint32_t t, uint32_t k) -> uint32_t { return mt[3u * t + k]; }, nt, out);
 }
 
 // Candidate 1: greedy growth over the vertex adjacency (what round 1 and 2 shipped).  Fills a cluster to the vertex limit and reseeds

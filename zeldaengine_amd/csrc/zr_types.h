@@ -207,12 +207,28 @@ struct ZrInstanceState {
     uint32_t n_inst;
 };
 
+// Device state of a mesh whose vertices have been updated (zr_mesh_update.hip): the raw vertices (what the update calls write), the
+// flattened meshlet vertex indices, and per frame parity a set of everything a frame reads that depends on vertex values.  A frame reads
+// the set of its parity through the draw table of its parity; indices, mtri and tri_meshlet do not depend on values and are shared.
+struct ZrMeshSet {
+    XkVertex* verts; ZrRVertex* rverts; ZrRVertex* rtris; XkMeshlet* meshlets; float4* mpos; float4* mbox;
+    uint32_t* acc;                   // the refit's whole-mesh reduction: [0..2] least, [3..5] greatest corner (ordered-integer floats),
+                                     // [6..7] the greatest distance from the box centre (float64 bits); reset by k_table_set_mesh
+};
+struct ZrMeshState {
+    XkVertex* raw; const uint32_t* mverts; const uint32_t* indices; const uint2* mtri;
+    uint32_t n_verts, n_tris, n_meshlets;
+    ZrMeshSet set[2];
+};
+
 // launchers: each defined in the .hip of its pass (zr_cull / zr_shadow / zr_camera / zr_resolve / zr_lighting / zr_forward / zr_frame /
 // zr_instances)
 void zr_launch_instance_prep(const XkInstanceData* in, ZrInstance* out, uint32_t n, uint32_t instanced, hipStream_t s);
 void zr_launch_instance_scatter(const uint32_t* idx, const XkInstanceData* data, uint32_t first, uint32_t n, const ZrInstanceState& S, hipStream_t s);
 void zr_launch_instance_apply(const ZrInstanceState& S, uint32_t par, uint32_t bound, hipStream_t s);
 void zr_launch_table_set_inst(ZrObject* tab, uint32_t draw, const ZrInstance* plane, hipStream_t s);
+void zr_launch_vertex_scatter(const XkVertex* src, uint32_t first, uint32_t n, const ZrMeshState& S, hipStream_t s);
+void zr_launch_mesh_refit(const ZrMeshState& S, uint32_t par, ZrObject* tab, uint32_t n_objs, hipStream_t s);
 void zr_launch_bin_count(const ZrPass& P, const uint32_t* work, const uint32_t* rects, uint32_t* tile_count, const ZrHiz& Z, const ZrDevStats* stats,
                          hipStream_t s);
 void zr_launch_hiz_build(const unsigned long long* vis64, uint32_t W, uint32_t H, const ZrHiz& Z, const uint32_t* regions, uint32_t n_regions, hipStream_t s);

@@ -55,6 +55,9 @@ def lib():
         "zr_object_get_instances": [vp, u32, C.POINTER(u32), vp, C.POINTER(u32)],
         "zr_object_set_instances": [vp, u32, u32, vp, u32],
         "zr_object_update_instances_async": [vp, u32, u32, vp, vp, u32, vp],
+        "zr_mesh_set_vertices": [vp, u32, u32, vp, u32],
+        "zr_mesh_update_vertices_async": [vp, u32, u32, vp, u32, vp],
+        "zr_mesh_get_vertices": [vp, u32, vp, C.POINTER(u32)],
         "zr_set_cubemap": [vp, vp, u32],
         "zr_set_skydome": [vp, vp, u32, vp, u32, vp],
         "zr_set_background": [vp, vp],
@@ -345,6 +348,34 @@ class Renderer:
         h = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
         self._chk(self.L.zr_object_update_instances_async(self.h, index, first, C.c_void_p(idx.data_ptr()) if idx is not None else None,
                                                           C.c_void_p(data.data_ptr()) if n else None, n, C.c_void_p(h) if h else None))
+
+    def mesh_set_vertices(self, mesh, verts, first=0):
+        """Replace vertices [first, first + len(verts)) of `mesh` (an abi.XkVertex array) from the next frame on (zr_mesh_set_vertices);
+        frames already enqueued keep the old shape.  Counts, indices and the meshlet partition stay; the bounds are refitted."""
+        verts = np.ascontiguousarray(verts)
+        assert verts.dtype == abi.XkVertex
+        self._chk(self.L.zr_mesh_set_vertices(self.h, mesh, first, _ptr(verts), verts.size))
+
+    def mesh_update_vertices_async(self, mesh, data, first=0, stream=None, n=None):
+        """The same from device memory, in the order of `stream` (a torch.cuda.Stream or a HIP stream handle; None = the render stream):
+        data = a contiguous CUDA tensor holding whole XkVertex records (e.g. float32 [n, 11]), or a device pointer with `n` vertices.
+        It may be overwritten by work enqueued on `stream` afterwards (zr_mesh_update_vertices_async)."""
+        if hasattr(data, "data_ptr"):
+            assert data.is_cuda and data.is_contiguous() and data.numel() * data.element_size() % abi.XkVertex.itemsize == 0
+            n = data.numel() * data.element_size() // abi.XkVertex.itemsize
+            ptr = data.data_ptr()
+        else:
+            assert n is not None, "a raw device pointer needs n, the number of vertices"
+            ptr = int(data) if data else 0
+        h = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        self._chk(self.L.zr_mesh_update_vertices_async(self.h, mesh, first, C.c_void_p(ptr) if ptr else None, n, C.c_void_p(h) if h else None))
+
+    def mesh_get_vertices(self, mesh):
+        n = C.c_uint32()
+        self._chk(self.L.zr_mesh_get_vertices(self.h, mesh, None, C.byref(n)))
+        verts = np.zeros(n.value, dtype=abi.XkVertex)
+        self._chk(self.L.zr_mesh_get_vertices(self.h, mesh, _ptr(verts), C.byref(n)))
+        return verts
 
     def set_cubemap(self, faces):
         if faces is None:
