@@ -63,11 +63,14 @@ typedef struct zr_ctx zr_ctx;
 #define ZR_FLAG_MESHLET_BINS   128u /* reserved: zr_create answers it with ZR_ERR_UNSUPPORTED */
 #define ZR_FLAG_NO_RECT_CULL    64u /* tile_world > 1: do not reject meshlets by the rank's owned screen region before stage B (parity A/B) */
 #define ZR_FLAG_NO_LIST_REUSE  256u /* rebuild the passes' instance-level work lists every frame instead of only when camera / light matrices or the
-                                     * scene change (parity A/B; the lists are an acceleration structure, never pixels) */
+                                     * scene change (parity A/B; the lists are an acceleration structure, never pixels) - and draw the
+                                     * shadow map every frame instead of keeping it while its light and casters stand still (zr_render) */
 #define ZR_FLAG_NO_SHADOW_OCCLUSION 512u /* shadow pass: draw every survivor of the cull instead of leaving out what the map's own depths already hide
                                      * (parity A/B: the map is the same bit for bit either way) */
 #define ZR_FLAG_SHADOW_OCCLUSION 1024u  /* ... and the opposite: occlusion-cull the shadow pass of a scene of any size (by default only from one
-                                     * meshlet-instance per five texels of the map on, where it pays) */
+                                     * meshlet-instance per five texels of the map on, where it pays).  The flag forces a variant of the
+                                     * PASS for A/B, so the pass runs: such a context draws its shadow map every frame, still light or
+                                     * not (its shadow_occluded / shadow_late are every frame's own); automatic occlusion keeps the map */
 
 typedef struct zr_config {
     uint32_t width, height;   /* swapchain extent, ZE:78-79 (default 1920x1080) */
@@ -222,7 +225,13 @@ int  zr_set_shading(zr_ctx* ctx, uint32_t mode);
  * the lighting pass go to the render stream (zr_set_stream), the camera pipeline to a stream of the library's own that the
  * lighting pass waits for; so work the host enqueues on the render stream afterwards is ordered after the finished frame, and
  * up to two frames are in flight (the next frame's camera pipeline runs next to this frame's lighting), as in the reference
- * (MAX_FRAMES_IN_FLIGHT, ZE:77).  zr_finish and the read-back entry points wait for everything. */
+ * (MAX_FRAMES_IN_FLIGHT, ZE:77).  zr_finish and the read-back entry points wait for everything.
+ * The shadow map is KEPT while the shadow pass's matrices (light, stage), the casters (objects, instances, vertices, meshlets, limits) and
+ * the map's buffer stand still: such a frame enqueues no shadow pipeline at all and lights from the map of the last drawn pass - the same
+ * map bit for bit.  The pass's statistics (zr_get_stats slot 0, shadow_occluded, shadow_late) then stay those of the last drawn pass, its
+ * pass times read exactly 0, and zr_read_shadowmap / zr_copy_frame_async return the kept map.  Every entry point (zr_render, the staged
+ * calls, zr_render_geometry) decides alike.  Drawn every frame: a tile- or instance-partitioned map, a caller-owned one
+ * (zr_set_shadow_buffer), contexts with ZR_FLAG_NO_LIST_REUSE or ZR_FLAG_SHADOW_OCCLUSION. */
 int  zr_render(zr_ctx* ctx);
 /* The same frame in three stages (zr_render = all three, in this order), so that a multi-GPU host can place its
  * collectives between them: shadow pass | deferred-scene pass (cull, raster, GBuffer write) | deferred-lighting pass. */

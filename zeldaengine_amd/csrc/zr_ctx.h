@@ -130,14 +130,15 @@ struct ZrWorld {
 struct ZrProfab { uint32_t mesh; ZrMaterialHost mat; };
 
 // Two frames in flight (the reference does: MAX_FRAMES_IN_FLIGHT, ZE:77): what a lighting pass reads is double-buffered, and this is one
-// copy of it.  Frame N uses copy N & 1 (zr_ctx::fcur, set at frame begin, so the read-back entry points see the frame rendered last).
+// copy of it.  Frame N uses copy N & 1 (zr_ctx::fcur, set at frame begin, so the read-back entry points see the frame rendered last) -
+// of everything but the shadow map: which copy holds the current map is zr_ctx::smap, and it changes only when a shadow pass is drawn.
 struct FrameCopy {
     GBufferPtrs G = {};                  // G.prim: the winner plane below, while the resolve keeps it (forward variant, id capture), else null
     float* shadow = nullptr; XkView* view = nullptr;
     uint32_t* empty_rgba = nullptr;      // the colour the lighting shader gives a pixel that holds every target's clear value, this frame
     uint32_t* prim_plane = nullptr;      // winner ids (zr_set_shading, zr_set_id_capture), made on first use
     bool overlay_dirty = false;          // G.overlay may hold skydome pixels of an earlier frame
-    bool shadow_cleared = false;         // `shadow` already holds depth 1.0 (cleared by the previous lighting pass)
+    bool shadow_cleared = false;         // `shadow` already holds depth 1.0 (cleared by a lighting pass since it was last drawn into)
     uint64_t view_uploaded = 0;          // which version of the uniforms `view` holds
     // a census enqueued against this copy (zr_instance_coverage_async): the frame that writes it next waits for it
     hipEvent_t ev_ids = nullptr; bool ids_wait = false;
@@ -174,6 +175,15 @@ struct zr_ctx {
     // while the pass block and the scene stand still: list_key = the block the list on the device was built from
     ZrPass pass[2]; bool pass_live[2] = { false, false }, list_reuse[2] = { false, false }, list_valid[2] = { false, false };
     ZrPass list_key[2];
+    // The shadow MAP is kept as well, one level up: while the shadow pass's block, the casters (caster_epoch) and the map's buffer stand
+    // still, the map of the last drawn pass is the map this frame would draw, bit for bit, and shadow_pass launches nothing.
+    // caster_epoch: bumped (zr_casters_changed) by every call that can change what the shadow pass would draw or where - objects, instances,
+    // vertices, meshlets, limits, the map's buffer or partition, the host's stream.  smap: the copy (fc[smap].shadow) that holds the
+    // current map; a drawn pass targets the other one and flips it.  smap_key / smap_epoch: what that map was drawn from (smap_valid:
+    // there is one).  shadow_keep: this frame keeps it (frame_begin).  shadow_draws: passes drawn so far (k_shadow_occlusion's retest turn).
+    uint64_t caster_epoch = 0, smap_epoch = 0, shadow_draws = 0;
+    int smap = 0; bool smap_valid = false, shadow_keep = false;
+    ZrPass smap_key;
 
     XkUniformBufferMVP cam, shadow; XkView view; bool frame_valid = false;
     uint32_t debug_view = 0;
@@ -218,9 +228,11 @@ struct zr_ctx {
     uint64_t view_version = 1;           // of the uniforms (FrameCopy::view_uploaded: the version a device copy holds)
     // Two frames in flight: the camera pipeline runs on `cam_s`, the shadow pipeline and the lighting pass on the host's `stream`;
     // frame N + 1's camera pipeline overlaps frame N's lighting.  What a lighting pass reads is therefore double-buffered: fc[fcur] is
-    // the current frame's copy - at stage 0 the one the frame enqueued last wrote - and fc[fcur ^ 1] the next frame's.
+    // the current frame's copy - at stage 0 the one the frame enqueued last wrote - and fc[fcur ^ 1] the next frame's.  (The shadow map's
+    // two copies live in fc[] too, but are picked by `smap`, not by the frame's parity.)
     FrameCopy fc[2]; int fcur = 0;
     hipStream_t cam_s = nullptr; bool camera_on_lane = false;
+    hipStream_t gbuf_s = nullptr;        // the stream the last deferred-scene pass was enqueued on (frame_begin: a change of it is a wait)
     bool in_render = false;
     hipEvent_t ev_join = nullptr, ev_cam = nullptr;
     unsigned long long* d_sky_keys = nullptr; uint32_t sky_object = 0;      // the skydome's key plane (k_sky_tiles) and its draw record
@@ -267,6 +279,7 @@ struct zr_ctx {
 
     hipEvent_t evr[EV_RING][10] = {}; uint64_t frame_no = 0; bool rendered = false;
     uint32_t timing_interval = 1; bool timing_now = true; uint64_t sample_no = 0;    // pass events every interval-th frame
+    bool ev_kept[EV_RING] = {};          // the sample's frame kept its shadow map: its shadow durations are 0, not the gap between two records
 
     // world + livelink + the content tree (zr_assets.cpp)
     std::string asset_root; bool assets_on = false;     // directory holding Profabs/ and Content/ (the engine's working directory)
@@ -277,6 +290,9 @@ struct zr_ctx {
 };
 
 int zr_fail(zr_ctx* c, int code, const std::string& msg);      // records the message (never throws), returns code
+// What the shadow pass would draw, or where, may have changed: the next frame draws its map (see zr_ctx::caster_epoch).  The device forms
+// of the updates call it when they enqueue: their kernels are stream-ordered ahead of the next frame.
+static inline void zr_casters_changed(zr_ctx* c) { c->caster_epoch++; }
 #define HIPCHK(c, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) \
     return zr_fail((c), ZR_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); } while (0)
 #define ARGCHK(c, cond) do { if (!(cond)) return zr_fail((c), ZR_ERR_ARG, "bad argument: " #cond); } while (0)

@@ -82,6 +82,7 @@ void zr_dist_destroy(zr_ctx* c)
     if (d->comm_s) (void)hipStreamSynchronize(d->comm_s);
     if (d->comm && d->CommDestroy) (void)d->CommDestroy(d->comm);
     if (d->shadow && c->d_shadow_ext == d->shadow) { c->d_shadow_ext = nullptr; c->shadow_rank = 0; c->shadow_world = 1; }      // back to the whole map
+    zr_casters_changed(c);            // (whatever map the context goes on with is drawn afresh)
     if (d->shadow_tiles && c->stile_world > 1) (void)zr_set_shadow_tiles(c, 0, 1);      // back to the whole map
     if (c->d_tiles_ext == d->tiles[0] || c->d_tiles_ext == d->tiles[1]) c->d_tiles_ext = nullptr;
     delete d;                         // (its owner releases the buffers, the events and the stream)
@@ -164,6 +165,7 @@ extern "C" int zr_dist_connect(zr_ctx* c, const void* id, size_t bytes)
         }
         // only a connected context draws a share of the shadow casters: a host that keeps using a context whose bring-up failed through
         // plain zr_render must get the whole map
+        zr_casters_changed(c);
         if (d->split_shadow) { c->d_shadow_ext = d->shadow; c->shadow_rank = d->rank; c->shadow_world = d->world; }
         if (d->shadow_tiles) { const int rc = zr_set_shadow_tiles(c, d->rank, d->world); if (rc != ZR_OK) return rc; }
         return ZR_OK;

@@ -278,6 +278,7 @@ extern "C" int zr_set_stream(zr_ctx* c, void* s)
         hipStream_t ns = s ? (hipStream_t)s : c->own_stream;
         // frames in flight are ordered by their place on the host's stream (frame_begin relies on it): a change of stream drains them
         if (ns != c->stream && c->rendered) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, zr_sync_all(c)); }
+        if (ns != c->stream) zr_casters_changed(c);      // (the kept map's two copies are ordered by their place on the host's stream too)
         c->stream = ns;
         return ZR_OK;
     });
@@ -354,7 +355,7 @@ extern "C" int zr_mesh_set_meshlets(zr_ctx* c, uint32_t mesh_id, const XkMeshlet
             }
             base += d.TriangleCount;
         }
-        m.has_meshlets = true;
+        m.has_meshlets = true; zr_casters_changed(c);
         return ZR_OK;
     });
 }
@@ -370,7 +371,7 @@ extern "C" int zr_mesh_build_meshlets(zr_ctx* c, uint32_t mesh_id, uint32_t max_
         ZrMesh& m = c->meshes[mesh_id];
         if (m.uploaded) return zr_fail(c, ZR_ERR_STATE, "mesh already in use by a rendered scene");
         zr_build_meshlets(m.v.data(), (uint32_t)m.v.size(), m.idx.data(), (uint32_t)m.idx.size(), max_v, max_t, cone_weight, &m.ms);
-        m.has_meshlets = true;
+        m.has_meshlets = true; zr_casters_changed(c);
         return ZR_OK;
     });
 }
@@ -533,7 +534,7 @@ int zr_object_add_internal(zr_ctx* c, uint32_t mesh_id, const ZrMaterialHost& ma
     zr_launch_instance_prep(o.d_raw, o.d_inst, o.n_inst, o.instanced ? 1u : 0u, c->stream);
     HIPCHK(c, zr_sync_all(c));
     c->objects.push_back(std::move(o));
-    c->scene_dirty = true; c->scene_gen++;
+    c->scene_dirty = true; c->scene_gen++; zr_casters_changed(c);
     return ZR_OK;
 }
 
@@ -560,6 +561,7 @@ extern "C" int zr_set_limits(zr_ctx* c, uint32_t record_chunks, uint32_t slow_tr
         if (record_chunks > ZR_MAX_RECORD_CHUNKS) return zr_fail(c, ZR_ERR_ARG, "zr_set_limits: record_chunks above (2^30 - 1) / 256");
         c->limit_record_chunks = record_chunks; c->limit_slow_triangles = slow_triangles;
         c->work_capacity = 0; c->scene_dirty = true;          // the pools are re-made by the next frame
+        zr_casters_changed(c);                                // (the shadow bins and the slow list with them)
         return ZR_OK;
     });
 }
@@ -568,7 +570,8 @@ extern "C" int zr_set_bucket_share(zr_ctx* c, uint32_t percent)
 {
     if (!c || percent < 1u || percent > 100u) return ZR_ERR_ARG;
     return zr_guard(c, [&]() -> int {
-        c->bucket_pct = percent;          // (k_plan's argument from the next plan on; a frame that overflows its buckets is the same frame)
+        c->bucket_pct = percent;          // (k_plan's argument from the next plan on; a frame that overflows its buckets is the same frame.
+                                          // The camera pass's record buckets only: the shadow bins know nothing of it, the map is kept)
         return ZR_OK;
     });
 }
@@ -578,7 +581,7 @@ static void drop_draw_tables(zr_ctx* c) { c->tables.release(); c->d_objs_b[0] = 
 // (every object and mesh releases its device memory as it goes)
 static void free_scene(zr_ctx* c)
 {
-    c->objects.clear(); c->scene_gen++;
+    c->objects.clear(); c->scene_gen++; zr_casters_changed(c);
     c->meshes.clear();
     c->profabs.clear();
     drop_draw_tables(c);
@@ -772,6 +775,7 @@ static int finalize_scene(zr_ctx* c)
     if (c->n_work) HIPCHK(c, hipMemsetAsync(c->d_sflag, 1, c->n_work, c->stream));      // shadow pass: everything is drawn in the first launch
     c->sflag_history = false;
     c->list_valid[0] = c->list_valid[1] = false;      // ... and neither do the passes' work lists
+    zr_casters_changed(c);                            // ... nor the kept shadow map: new draw table, maybe new pools
     c->scene_dirty = false;
     return ZR_OK;
 }
@@ -1107,7 +1111,16 @@ static bool build_pass(const zr_ctx* c, const XkUniformBufferMVP& u, int mode, Z
 
 // ------------------------------------------------------------------------------------------------ the frame
 
-static inline float* shadow_buf(zr_ctx* c) { return c->d_shadow_ext ? c->d_shadow_ext : c->fc[c->fcur].shadow; }
+// The current shadow map: during a drawn shadow pass the one being drawn, else the one the last drawn pass left (zr_ctx::smap).
+static inline float* shadow_buf(zr_ctx* c) { return c->d_shadow_ext ? c->d_shadow_ext : c->fc[c->smap].shadow; }
+// Contexts whose map is never kept (every frame draws it): the host reduces or gathers a partitioned or caller-owned map in place;
+// ZR_FLAG_NO_LIST_REUSE asks to recompute what standing inputs would let the library keep; ZR_FLAG_SHADOW_OCCLUSION forces a variant of
+// the pass for A/B, whose per-frame history statistics are what its callers read.
+static inline bool shadow_keepable(const zr_ctx* c)
+{
+    return !c->d_shadow_ext && c->cfg.tile_world <= 1u && c->shadow_world <= 1u && c->stile_world <= 1u &&
+           !(c->cfg.flags & (ZR_FLAG_NO_LIST_REUSE | ZR_FLAG_SHADOW_OCCLUSION));
+}
 
 // count -> scan -> fill of the shadow pass's meshlet bins, from the cull's rects.  Z.phase 1 (occlusion culling): only the
 // meshlet-instances flagged last frame are binned.
@@ -1216,6 +1229,12 @@ static int frame_begin(zr_ctx* c, hipStream_t s)
     // (two lanes: this frame's copies of the double-buffered resources were last read by the lighting pass of two frames ago, on the
     // host's stream.  Nothing else ties the lanes together here: the shadow pipeline keeps statistics of its own)
     if (s != c->stream && c->frame_no >= 2) HIPCHK(c, hipStreamWaitEvent(s, c->ev_end[(c->frame_no - 2) % zr_ctx::END_RING], 0));
+    // Consecutive camera pipelines share the key buffer, the triangle records, the plan and the camera lane's statistics, and are ordered
+    // by running on ONE stream.  A frame on the lane that follows a frame of the staged entry points (its camera pipeline ran on the host's
+    // stream) waits for that frame's end instead.  (The other way round the host's stream has waited for the whole lane, k_plan included,
+    // before that frame's lighting pass: ev_cam.)
+    if (s != c->stream && c->frame_no >= 1 && c->gbuf_s && c->gbuf_s != s)
+        HIPCHK(c, hipStreamWaitEvent(s, c->ev_end[(c->frame_no - 1) % zr_ctx::END_RING], 0));
     // ... and by an identity census enqueued against them since (zr_instance_coverage_async, on the host's stream)
     if (F.ids_wait) { if (s != c->stream) HIPCHK(c, hipStreamWaitEvent(s, F.ev_ids, 0)); F.ids_wait = false; }
     // this frame's draw table; instance updates since the last frame of this parity go into its planes (zr_instances_host.cpp)
@@ -1236,6 +1255,8 @@ static int frame_begin(zr_ctx* c, hipStream_t s)
         // (the list counts as standing only once its k_cull_instances has been enqueued: shadow_pass / gbuffer_pass set list_valid)
         if (P.use_worklist && P.n_work != 0 && !c->list_reuse[slot]) { rebuild |= 1u << slot; c->list_key[slot] = P; c->list_valid[slot] = false; }
     }
+    // ... and the shadow pass's map as a whole while, beyond that, no caster changed and the map stays where it is (shadow_pass)
+    c->shadow_keep = shadow_keepable(c) && c->smap_valid && c->smap_epoch == c->caster_epoch && memcmp(&c->smap_key, &c->pass[0], sizeof(ZrPass)) == 0;
     const XkView* src = nullptr;
     uint32_t k = 0;
     if (F.view_uploaded != c->view_version) {        // pinned ring slot: reused only after the kernel that read it last has run
@@ -1258,9 +1279,22 @@ static int shadow_pass(zr_ctx* c, hipStream_t s)
 {
     hipEvent_t* ev = c->timing_now ? c->evr[c->sample_no % zr_ctx::EV_RING] : nullptr;
     const ZrPass& P = c->pass[0];      // (built by frame_begin)
+    if (ev) c->ev_kept[c->sample_no % zr_ctx::EV_RING] = c->shadow_keep;
+    if (c->shadow_keep) {
+        // The map of the last drawn pass is this frame's, bit for bit: nothing is launched.  Its statistics block, last_work[0] and the
+        // occlusion flags stay as that pass left them; a timed frame records its two events all the same (no elapsed-time call meets an
+        // unrecorded one), and the sample counts as 0 (zr_get_pass_times_avg).
+        if (ev) { HIPCHK(c, hipEventRecord(ev[1], s)); HIPCHK(c, hipEventRecord(ev[2], s)); }
+        return ZR_OK;
+    }
     c->last_work[0] = P.n_work;
-    // clear depth 1.0 (ZE:3248): the previous frame's lighting pass already did it for the internal double-buffered map
-    FrameCopy& F = c->fc[c->fcur];
+    c->smap_valid = false;             // (until the whole pass is enqueued)
+    // The pass draws into the copy that does NOT hold the current map and makes it the current one: from here on shadow_buf() is the map
+    // being drawn.  No event guards the flip: everything that reads or writes either copy - this pipeline, the lighting passes and their
+    // fused clear, the read-backs and copies - is enqueued on the host's stream, in frame order.
+    if (!c->d_shadow_ext) c->smap ^= 1;
+    // clear depth 1.0 (ZE:3248): a lighting pass since the copy's last draw already did it for the internal double-buffered map
+    FrameCopy& F = c->fc[c->smap];
     if (c->d_shadow_ext || !F.shadow_cleared) zr_launch_fill32((uint32_t*)shadow_buf(c), 0x3F800000u, (size_t)c->SD * c->SD, s);
     F.shadow_cleared = false;
     ZrHiz Z; memset(&Z, 0, sizeof Z);
@@ -1281,12 +1315,14 @@ static int shadow_pass(zr_ctx* c, hipStream_t s)
     raster(c, P, s, occl ? 1 : 0);
     if (occl) {
         zr_launch_shadow_occlusion(P, c->d_objs, c->sc[0].work, c->sc[0].rects, c->d_spxrect, c->d_szmin, c->d_sflag, (const uint32_t*)shadow_buf(c),
-                                   c->sb.bins, c->d_sstats, c->shadow_blocks * 8u, c->sflag_history ? (uint32_t)(c->frame_no & 3u) : 4u, s);
+                                   c->sb.bins, c->d_sstats, c->shadow_blocks * 8u, c->sflag_history ? (uint32_t)(c->shadow_draws & 3u) : 4u, s);      // (a turn per pass DRAWN: kept frames test nothing)
         c->sflag_history = true;
         raster(c, P, s, 2);
     }
     if (ev) HIPCHK(c, hipEventRecord(ev[2], s));
     HIPCHK(c, hipGetLastError());
+    c->shadow_draws++;
+    c->smap_key = P; c->smap_epoch = c->caster_epoch; c->smap_valid = true;
     return ZR_OK;
 }
 
@@ -1296,6 +1332,7 @@ static int gbuffer_pass(zr_ctx* c, hipStream_t s)
     hipEvent_t* ev = c->timing_now ? c->evr[c->sample_no % zr_ctx::EV_RING] : nullptr;
     if (ev) HIPCHK(c, hipEventRecord(ev[9], s));
     ZrPass P = c->pass[1];             // (built by frame_begin; the overlay fields are set below)
+    c->gbuf_s = s;
     c->last_work[1] = P.n_work;
     // Two-pass occlusion culling: round 1 draws the meshlet-instances that owned a pixel last frame, a Hi-Z pyramid of the
     // result rejects what it hides, round 2 draws the rest.  The depth test decides every pixel either way, so the frame does
@@ -1459,10 +1496,10 @@ static int lighting_pass(zr_ctx* c, hipStream_t s)
     ZrLightParams L; light_params(c, &L);
     const FrameCopy& F = c->fc[c->fcur];
     L.empty_rgba = c->empty_ready ? F.empty_rgba : nullptr;
-    // The next frame's shadow pass follows on this stream and rasterises into the OTHER copy of the map, which nothing reads or
-    // writes while this pass runs: clear it here.
-    FrameCopy& next = c->fc[c->fcur ^ 1];
-    if (c->n_owned && s == c->stream) { L.clear_next = (uint32_t*)next.shadow; L.clear_n = c->SD * c->SD; next.shadow_cleared = true; }
+    // The next DRAWN shadow pass follows on this stream and rasterises into the OTHER copy of the map, which nothing reads or
+    // writes while this pass runs: clear it here - once; a run of frames that keep their map finds it clear and writes nothing.
+    FrameCopy& next = c->fc[c->smap ^ 1];
+    if (c->n_owned && s == c->stream && !c->d_shadow_ext && !next.shadow_cleared) { L.clear_next = (uint32_t*)next.shadow; L.clear_n = c->SD * c->SD; next.shadow_cleared = true; }
     uint32_t* const frame_out = L.packed_out ? (c->d_tiles_ext ? c->d_tiles_ext : c->d_tiles) : c->d_color;
     if (c->shading == ZR_SHADING_FORWARD) {
         // Base.frag over the winners the resolve recorded, with this frame's camera block (frame_begin built it; the overlay fields play no part)
@@ -1525,7 +1562,7 @@ extern "C" int zr_set_shadow_partition(zr_ctx* c, uint32_t rank, uint32_t world)
     return zr_guard(c, [&]() -> int {
         ARGCHK(c, world >= 1 && rank < world);
         if (world > 1 && c->stile_world > 1) return zr_fail(c, ZR_ERR_STATE, "zr_set_shadow_partition: the map is already owned by tiles (zr_set_shadow_tiles)");
-        c->shadow_rank = rank; c->shadow_world = world;
+        c->shadow_rank = rank; c->shadow_world = world; zr_casters_changed(c);
         return ZR_OK;
     });
 }
@@ -1546,7 +1583,7 @@ extern "C" int zr_set_shadow_tiles(zr_ctx* c, uint32_t rank, uint32_t world)
         HIPCHK(c, zr_sync_all(c));
         c->stile_mem.release(); c->d_sowned_rank = c->d_stile_map = nullptr;
         c->stile_rank = 0; c->stile_world = 1; c->s_slots_per_rank = c->sn_tiles; c->n_sowned_rank = 0;
-        c->list_valid[0] = false;
+        c->list_valid[0] = false; zr_casters_changed(c);
         if (world == 1) return ZR_OK;
         const ZrTilePartition P = zr_partition(c->stiles_x, c->stiles_y, world, rank);
         HIPCHK(c, upload(c->stile_mem, &c->d_sowned_rank, P.owned)); HIPCHK(c, upload(c->stile_mem, &c->d_stile_map, P.map));
@@ -1599,7 +1636,7 @@ extern "C" int zr_set_shadow_buffer(zr_ctx* c, void* ptr)
 {
     if (!c) return ZR_ERR_ARG;
     return zr_guard(c, [&]() -> int {
-        c->d_shadow_ext = (float*)ptr;
+        c->d_shadow_ext = (float*)ptr; zr_casters_changed(c);
         return ZR_OK;
     });
 }
@@ -1670,6 +1707,8 @@ extern "C" int zr_get_pass_times_avg(zr_ctx* c, uint32_t last_n, float ms[ZR_PAS
             (void)hipEventElapsedTime(&t[ZR_PASS_RESOLVE], ev[6], ev[7]);
             (void)hipEventElapsedTime(&t[ZR_PASS_LIGHTING], ev[7], ev[8]);
             (void)hipEventElapsedTime(&t[ZR_PASS_TOTAL], ev[0], ev[8]);
+            // (a frame that kept its shadow map ran no shadow pipeline: exactly 0, not the gap between two back-to-back records)
+            if (c->ev_kept[(c->sample_no - 1 - k) % zr_ctx::EV_RING]) t[ZR_PASS_CULL_SHADOW] = t[ZR_PASS_SHADOW] = 0.0f;
             for (int i = 0; i < ZR_PASS_COUNT; ++i) acc[i] += t[i];
         }
         for (int i = 0; i < ZR_PASS_COUNT; ++i) ms[i] = (float)(acc[i] / last_n);

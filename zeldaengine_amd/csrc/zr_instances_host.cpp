@@ -71,6 +71,9 @@ int zr_update_end(zr_ctx* c, hipStream_t x)
     // The passes' work lists (k_cull_instances) hold the instances that passed the whole-mesh test: rebuilt by the next frame.  The visibility
     // history, the bucket plan and the shadow flags stay: the frame does not depend on them.
     c->list_valid[0] = c->list_valid[1] = false;
+    // The kept shadow map goes too: a caster moved (instances) or changed shape (vertices - the lists are instance-level and would not
+    // have needed rebuilding for that, the map does).  Said at enqueue time: x orders the scatter ahead of the next frame.
+    zr_casters_changed(c);
     return ZR_OK;
 }
 

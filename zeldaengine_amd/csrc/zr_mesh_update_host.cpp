@@ -73,7 +73,7 @@ static int mesh_enqueue(zr_ctx* c, ZrMesh& m, hipStream_t x, const XkVertex* src
     if (rc == ZR_OK) rc = zr_update_begin(c, x);
     if (rc) return rc;
     zr_launch_vertex_scatter(src, first, n, m.upd, x);
-    rc = zr_update_end(c, x);      // (the whole-mesh sphere moves: the passes' work lists are rebuilt; history, plan and flags stay)
+    rc = zr_update_end(c, x);      // (the whole-mesh sphere moves: the passes' work lists are rebuilt, the shadow map is drawn again; history, plan and flags stay)
     if (rc) return rc;
     m.stale[0] = m.stale[1] = true; m.ml_stale = true;
     return ZR_OK;
@@ -99,6 +99,7 @@ extern "C" int zr_mesh_set_vertices(zr_ctx* c, uint32_t mesh_id, uint32_t first,
             // meshlets already attached follow the vertices here.
             memcpy(m->v.data() + first, v, (size_t)n * sizeof(XkVertex));
             if (m->has_meshlets) host_bounds(*m);
+            zr_casters_changed(c);
             return ZR_OK;
         }
         HIPCHK(c, hipSetDevice(c->device));

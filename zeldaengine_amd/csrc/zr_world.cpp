@@ -276,7 +276,7 @@ int apply_world(zr_ctx* c, const ZrWorld& w)
     int rc = ZR_OK;
     {
         auto keep_m = std::move(c->meshes); auto keep_p = std::move(c->profabs);
-        c->objects.clear(); c->scene_dirty = true; c->scene_gen++;      // (each object releases its device memory)
+        c->objects.clear(); c->scene_dirty = true; c->scene_gen++; zr_casters_changed(c);      // (each object releases its device memory)
         c->meshes = std::move(keep_m); c->profabs = std::move(keep_p);
     }
     c->world = w;
