@@ -191,6 +191,26 @@ int  zr_mesh_update_vertices_async(zr_ctx* ctx, uint32_t mesh_id, uint32_t first
 /* Copy out the mesh's current vertices (dst may be NULL; *n = the vertex count).  After a device-form update this and
  * zr_mesh_get_meshlets read back with one synchronisation. */
 int  zr_mesh_get_vertices(zr_ctx* ctx, uint32_t mesh_id, XkVertex* dst, uint32_t* n);
+/* Changing textures.  Replace the image of material slot `slot` (0..6: bc, m, r, n, ao, ev, ms) of object `index`
+ * (add order).  Same width and height as the image the slot holds; all mip levels and the packed material follow, built on the GPU to
+ * the bytes zr_object_add would have built.  Takes effect with the next zr_render; frames already enqueued still sample the old image.
+ * `img->rgba8` may be reused when the call returns.  The scene does not change: work lists, plan, visibility history, the kept shadow
+ * map and the identity queries all stand.  An image that happens to be constant stays an image (no collapse on update).
+ * Between the stages of a frame: ZR_ERR_STATE; a bad object index, slot > 6, null or misaligned data, or a size other than the slot's:
+ * ZR_ERR_ARG; a slot that holds no image - zr_object_add collapsed a constant image to its texel, or took the engine default -:
+ * ZR_ERR_STATE (a slot meant to change must be added with a non-constant image of its final size).  The context is unchanged by a
+ * refused call.  Out of scope: promoting a constant slot to an image, changing an image's size, updating a sub-rectangle; the
+ * skydome, the background and the cubemap (zr_set_skydome / zr_set_background / zr_set_cubemap replace those). */
+int  zr_object_set_texture(zr_ctx* ctx, uint32_t index, uint32_t slot, const zr_image* img);
+/* The same from caller-owned DEVICE memory (width * height * 4 bytes RGBA8, row-major, 4-byte aligned) in the order of hip_stream
+ * (NULL = the render stream); read only inside that order: a caller may overwrite it with work enqueued on hip_stream after this
+ * call.  No host synchronisation. */
+int  zr_object_update_texture_async(zr_ctx* ctx, uint32_t index, uint32_t slot, const void* rgba8_dev, uint32_t width, uint32_t height,
+                                    void* hip_stream);
+/* Copy out mip level `level` of the slot's current image (dst may be NULL; *w, *h = that level's size, *levels = the chain's length;
+ * cap = the room at dst in bytes).  After an update this reads back with one synchronisation.  A slot without an image: ZR_ERR_STATE. */
+int  zr_object_get_texture(zr_ctx* ctx, uint32_t index, uint32_t slot, uint32_t level, uint8_t* dst, size_t cap, uint32_t* w, uint32_t* h,
+                           uint32_t* levels);
 /* 6 RGBA8 sRGB faces in Vulkan layer order +X,-X,+Y,-Y,+Z,-Z (RHICreateTextureCubeResource ZE:5908-6150);
  * mips are generated like RHIGenerateMipmaps (ZE:6348-6433).  faces == NULL: built-in 1x1 grey. */
 int  zr_set_cubemap(zr_ctx* ctx, const uint8_t* const faces[6], uint32_t dim);

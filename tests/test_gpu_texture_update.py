@@ -1,0 +1,413 @@
+"""Changing material textures between frames (zr_object_set_texture, zr_object_update_texture_async), byte for byte.
+
+The mip chain the GPU builds from a new image is the oracle's chain at every level; what an updated context draws equals what a context
+built with the final images draws and what the CPU oracle draws; with two frames in flight an update reaches only the frames enqueued
+after it; lists, plan, history, the kept shadow map and the identity queries stand.  Every comparison is exact.
+"""
+import numpy as np
+import pytest
+
+from parity_util import compare_all
+from zeldaengine_amd import abi, dist as zdist, scenes
+
+pytestmark = pytest.mark.gpu
+
+W, H, SD, N = 320, 180, 512, 3000
+EYE, TARGET = np.array([12.0, -9.0, 7.0], np.float32), np.array([0.0, 0.0, 0.5], np.float32)
+PLANE, SPHERES = 0, 1                        # object indices (add order)
+
+
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to(torch.device("cuda", 0))
+
+
+# ------------------------------------------------------------------------------------------------ chains
+
+def _noise(w, h, seed):
+    return np.random.default_rng(seed).integers(0, 256, (h, w, 4), dtype=np.uint8)
+
+
+def _pair_sweep():
+    """512 x 512: texels (2x, y) and (2x + 1, y) hold a = x mod 256 and b = (y / 2) mod 256 in all three colour channels, rows 2j and
+    2j + 1 are equal: level 1 encodes every average of two decoded values (65 536 encode inputs), the levels above add more."""
+    y, x = np.mgrid[0:512, 0:512]
+    a, b = (x // 2) % 256, (y // 2) % 256
+    img = np.zeros((512, 512, 4), np.uint8)
+    img[..., :3] = np.where(x % 2 == 0, a, b)[..., None]
+    img[..., 3] = 255
+    return img
+
+
+def _check_chain(got, want, what):
+    assert len(got) == len(want), "%s: %d levels, the oracle has %d" % (what, len(got), len(want))
+    for l, (g, o) in enumerate(zip(got, want)):
+        assert g.shape == o.shape, "%s: level %d is %r, the oracle's %r" % (what, l, g.shape, o.shape)
+        assert np.array_equal(g, o), "%s: level %d, %d texels differ" % (what, l, int((g != o).any(axis=2).sum()))
+
+
+@pytest.fixture(scope="module")
+def oracle(oracle_lib):
+    o = oracle_lib.Oracle(8, 8, 8)
+    yield o
+    o.close()
+
+
+@pytest.mark.parametrize("w,h", [(8, 8), (5, 3), (1, 7), (7, 1), (64, 64), (65, 33), (128, 32)])
+def test_chains_equal_the_oracle_level_by_level(gpu_engine, oracle, w, h):
+    """Slot 0 (sRGB) and slot 3 (linear) of one object, updated through the host form, then through the device form: every level of the
+    chain read back equals oracle.tex_mips, with the same level count.  (Both slots have one size: the object has the packed form, whose
+    bytes the same kernels write - the frame tests below read those.)"""
+    import torch
+    r = gpu_engine.Renderer(64, 64, 64)
+    images = [None] * 7
+    images[0], images[3] = _noise(w, h, 1), _noise(w, h, 2)
+    mat, keep = abi.make_material(images)
+    r.object_add(r.mesh_create(*scenes.grid_plane(4.0, 2, 0.0)), mat)
+    for slot in (0, 3):        # (never updated: what zr_object_add built on the host)
+        _check_chain(r.object_get_texture(0, slot), oracle.tex_mips(images[slot], slot == 0), "slot %d as added" % slot)
+    for slot in (0, 3):
+        img = _noise(w, h, 10 + slot)
+        r.object_set_texture(0, slot, img)
+        _check_chain(r.object_get_texture(0, slot), oracle.tex_mips(img, slot == 0), "slot %d, host form" % slot)
+        img = _noise(w, h, 20 + slot)
+        t = _dev(img)
+        torch.cuda.synchronize()
+        r.object_update_texture_async(0, slot, t)
+        _check_chain(r.object_get_texture(0, slot), oracle.tex_mips(img, slot == 0), "slot %d, device form" % slot)
+    r.close()
+
+
+def test_pair_sweep_chain_equals_the_oracle(gpu_engine, oracle):
+    """Every average of two decoded sRGB values goes through the encode (the kernels' threshold search against the host's pow)."""
+    r = gpu_engine.Renderer(64, 64, 64)
+    images = [None] * 7
+    images[0] = _noise(512, 512, 3)
+    mat, keep = abi.make_material(images)
+    r.object_add(r.mesh_create(*scenes.grid_plane(4.0, 2, 0.0)), mat)
+    img = _pair_sweep()
+    r.object_set_texture(0, 0, img)
+    _check_chain(r.object_get_texture(0, 0), oracle.tex_mips(img, True), "pair sweep")
+    r.close()
+
+
+# ------------------------------------------------------------------------------------------------ frames
+
+def _variant(img, k):
+    """Another non-constant image of the same size: shifted, channels 0..2 inverted where k is odd."""
+    out = np.roll(img, (3 + k, 5 + 2 * k), axis=(0, 1)).copy()
+    if k & 1:
+        out[..., :3] = 255 - out[..., :3]
+    return out
+
+
+def _materials(mixed):
+    """The spheres' 64 x 64 material (mixed: its ambient-occlusion slot at 32 x 32, so no packed form) and the plane's 32 x 32 one."""
+    sph, pla = scenes.synthetic_material(64), scenes.synthetic_material(32)
+    if mixed:
+        sph[4] = pla[4]
+    return sph, pla
+
+
+def _final(sph, pla):
+    """The images after the update: slots 0, 3 and 6 (base colour, normal, mask) of the spheres, slot 2 of the plane."""
+    sph, pla = list(sph), list(pla)
+    for k, slot in enumerate((0, 3, 6)):
+        sph[slot] = _variant(sph[slot], k)
+    sph[6][..., 0] = 255                      # (mask r = 1: lit everywhere, as the material it replaces)
+    pla[2] = _variant(pla[2], 1)
+    return sph, pla
+
+
+def _scene(r, sph, pla, n=N):
+    r.set_cubemap(scenes.synthetic_cubemap(16))
+    keep = []
+    m, k = abi.make_material(pla); keep.append(k)
+    r.object_add(r.mesh_create(*scenes.grid_plane(40.0, 4, 0.0)), m)
+    m, k = abi.make_material(sph); keep.append(k)
+    r.object_add(r.mesh_create(*scenes.uv_sphere(8, 5)), m, scenes.generate_instances(n, 1.0, 14.0, 0.05, 0.4, seed=11))
+    return keep
+
+
+def _uniforms():
+    w = scenes.sample_world()
+    d, _, s = scenes.lights_from_world(w)
+    w["PointLights"] = scenes.sample_point_lights(4)
+    _, p, _ = scenes.lights_from_world(w)
+    return abi.make_camera(tuple(EYE.tolist()), tuple(TARGET.tolist()), fov=50.0), d, p, s
+
+
+def _frame(r, u):
+    cam, d, p, s = u
+    r.update_uniforms(cam, d, p, s, 0.0, 0.0, 1.0)
+    r.render()
+
+
+def _grab(r):
+    r.finish()
+    st = r.stats()
+    assert st["overflow"] == 0, st
+    return r.color().copy(), [r.gbuffer(t).copy() for t in range(6)], r.shadowmap().view(np.uint32).copy(), st
+
+
+def _same(a, b, what):
+    assert np.array_equal(a[0], b[0]), "%s: colour, %d pixels differ" % (what, int((a[0] != b[0]).any(axis=2).sum()))
+    for t in range(6):
+        assert np.array_equal(a[1][t].view(np.uint8), b[1][t].view(np.uint8)), "%s: GBuffer target %d" % (what, t)
+    assert np.array_equal(a[2], b[2]), "%s: shadow map" % what
+    assert a[3]["covered_pixels"] == b[3]["covered_pixels"], what
+
+
+@pytest.mark.parametrize("mixed", [False, True], ids=["packed", "mixed_sizes"])
+@pytest.mark.parametrize("forward", [False, True], ids=["deferred", "forward"])
+def test_updated_context_equals_a_fresh_one(gpu_engine, forward, mixed):
+    """Two frames, three slots of the spheres and one of the plane replaced (host and device form), two more frames: both equal a new
+    context's frame of the final images in colour and in every GBuffer target; the frame before the update differs."""
+    import torch
+    u = _uniforms()
+    sph, pla = _materials(mixed)
+    sph2, pla2 = _final(sph, pla)
+    a = gpu_engine.Renderer(W, H, SD)
+    a.set_shading(forward)
+    keep = _scene(a, sph, pla)
+    _frame(a, u); _frame(a, u)
+    before = _grab(a)
+    a.object_set_texture(SPHERES, 0, sph2[0])
+    t = _dev(sph2[3])
+    torch.cuda.synchronize()
+    a.object_update_texture_async(SPHERES, 3, t)
+    a.object_set_texture(SPHERES, 6, sph2[6])
+    a.object_set_texture(PLANE, 2, pla2[2])
+    _frame(a, u)
+    first = _grab(a)
+    _frame(a, u)
+    second = _grab(a)
+    a.close()
+    b = gpu_engine.Renderer(W, H, SD)
+    b.set_shading(forward)
+    keep = _scene(b, sph2, pla2)
+    _frame(b, u)
+    fresh = _grab(b)
+    b.close()
+    assert before[3]["covered_pixels"] > W * H // 4
+    assert not np.array_equal(before[0], fresh[0]) and not np.array_equal(before[1][4], fresh[1][4])      # the update shows
+    _same(first, fresh, "frame after the update")
+    _same(second, fresh, "the frame after that")
+    del keep
+
+
+def test_updates_through_both_forms_match_the_oracle(gpu_engine, oracle_lib):
+    """A small textured instanced scene after one host-form and one device-form update: every target equals the CPU oracle's frame of
+    the final materials."""
+    import torch
+    cfg = scenes.config3(64, 256, 144)
+    images = scenes.synthetic_material(64)
+    mat, keep = abi.make_material(images)
+    cfg["objects"][0]["material"] = mat
+    g = gpu_engine.Renderer(cfg["width"], cfg["height"], 256)
+    gpu_engine.load_scene(g, cfg)
+    g.render(); g.render()
+    final = list(images)
+    final[0], final[2] = _variant(images[0], 1), _variant(images[2], 2)
+    g.object_set_texture(0, 0, final[0])
+    t = _dev(final[2])
+    torch.cuda.synchronize()
+    g.object_update_texture_async(0, 2, t)
+    g.render()
+    g.finish()
+    mat2, keep2 = abi.make_material(final)
+    cfg["objects"][0]["material"] = mat2
+    o = oracle_lib.Oracle(cfg["width"], cfg["height"], 256)
+    oracle_lib.load_scene(o, cfg)
+    o.render()
+    assert o.covered_pixels() > 100
+    diffs = compare_all(o, g)
+    assert all(v == 0 for v in diffs.values()), diffs
+    g.close(); o.close()
+
+
+# ------------------------------------------------------------------------------------------------ frames in flight
+
+FRAMES = 8
+
+
+def _steps(sph):
+    """Frame i's image of the spheres' base colour"""
+    return [_variant(sph[0], i + 2) for i in range(FRAMES)]
+
+
+def _serial_frames(gpu_engine, forward, sph, pla, steps, u):
+    """The reference: one stream, the image set before every frame, finish() after it."""
+    ref = gpu_engine.Renderer(W, H, SD, flags=abi.FLAG_SERIAL_PASSES)
+    ref.set_shading(forward)
+    keep = _scene(ref, sph, pla)
+    want = []
+    for img in steps:
+        ref.object_set_texture(SPHERES, 0, img)
+        _frame(ref, u)
+        ref.finish()
+        want.append(ref.color().copy())
+    ref.close()
+    del keep
+    assert any(not np.array_equal(want[0], x) for x in want[1:])
+    return want
+
+
+@pytest.mark.parametrize("device_form", [False, True], ids=["host_form", "device_form"])
+@pytest.mark.parametrize("forward", [False, True], ids=["deferred", "forward"])
+def test_updates_between_queued_frames(gpu_engine, forward, device_form):
+    """Frames back to back, each after an update, copied out on the device; no finish() until all are enqueued.  Every frame equals the
+    serial context's frame of the image that was current when it was enqueued: the chain is rewritten in place, so the update waits for
+    the readers of the frame before it - the resolve on the camera lane, and in forward shading the shading pass on the render stream.
+    The device form comes from a torch side stream, its source tensor overwritten on that stream straight after the call."""
+    import torch
+    u = _uniforms()
+    sph, pla = _materials(False)
+    steps = _steps(sph)
+    want = _serial_frames(gpu_engine, forward, sph, pla, steps, u)
+    g = gpu_engine.Renderer(W, H, SD)
+    g.set_shading(forward)
+    keep = _scene(g, sph, pla)
+    dev = torch.device("cuda", 0)
+    got = [torch.zeros(W * H, dtype=torch.int32, device=dev) for _ in range(FRAMES)]
+    ts = torch.cuda.Stream(device=dev)
+    torch.cuda.synchronize()
+    for i in range(FRAMES):
+        if device_form:
+            with torch.cuda.stream(ts):
+                t = torch.from_numpy(steps[i]).pin_memory().to(dev, non_blocking=True)
+                g.object_update_texture_async(SPHERES, 0, t, stream=ts)
+                t.fill_(0x5A)                                                      # overwritten behind the call, on its stream
+        else:
+            g.object_set_texture(SPHERES, 0, steps[i])
+        _frame(g, u)
+        g.copy_frame_async(got[i].data_ptr(), None)
+    g.finish()
+    ts.synchronize()
+    assert g.stats()["overflow"] == 0
+    for i in range(FRAMES):
+        c = got[i].cpu().numpy().view(np.uint8).reshape(H, W, 4)
+        assert np.array_equal(c, want[i]), "colour of queued frame %d: %d pixels differ" % (i, int((c != want[i]).any(axis=2).sum()))
+    _check_chain(g.object_get_texture(SPHERES, 0)[:1], [steps[-1]], "the image after the last update")
+    g.close()
+    del keep
+
+
+# ------------------------------------------------------------------------------------------------ what stands, refusals, ranks
+
+def test_a_texture_update_leaves_lists_shadow_map_and_ids_standing(gpu_engine):
+    """With a still light the frame after a texture update keeps its shadow map (no shadow pass runs), the shadow pipeline's statistics
+    and the camera pass's work items and survivors are the frame's before, and so are pick and the instance coverage."""
+    u = _uniforms()
+    sph, pla = _materials(False)
+    g = gpu_engine.Renderer(W, H, SD)
+    keep = _scene(g, sph, pla)
+    g.set_id_capture(True)
+    for _ in range(3):
+        _frame(g, u)
+    g.finish()
+    assert g.pass_times(1)["shadow"] == 0.0      # (the map already stands before the update)
+    st0, cov0 = g.stats(), g.instance_coverage()
+    hits0, total0 = g.pick(W // 2 - 20, H // 2 - 20, 40, 40)
+    g.object_set_texture(SPHERES, 0, _variant(sph[0], 1))
+    g.object_set_texture(PLANE, 3, _variant(pla[3], 2))
+    # (no frame since the update: the queries answer for the frame before it)
+    assert np.array_equal(g.instance_coverage(), cov0)
+    _frame(g, u)
+    g.finish()
+    assert g.pass_times(1)["shadow"] == 0.0
+    st1 = g.stats()
+    for key in ("work_items", "survivors"):      # slot 0: the shadow pipeline's (it did not run), slot 1: the camera pass's
+        assert st1[key] == st0[key], (key, st0, st1)
+    assert st1["bin_entries"][0] == st0["bin_entries"][0]
+    for key in ("covered_pixels", "covered_shadow_texels", "shadow_occluded", "shadow_late", "overflow"):
+        assert st1[key] == st0[key], (key, st0, st1)
+    assert np.array_equal(g.instance_coverage(), cov0) and int(cov0.sum()) == st1["covered_pixels"]
+    hits1, total1 = g.pick(W // 2 - 20, H // 2 - 20, 40, 40)
+    assert total1 == total0 and total0 > 1 and np.array_equal(hits1, hits0)
+    g.close()
+    del keep
+
+
+def test_bad_updates_are_refused_and_change_nothing(gpu_engine):
+    """Every refusal of the header's table returns its code with a message that names the cause, and the next frame is the frame
+    without the calls."""
+    import torch
+    from zeldaengine_amd.engine import ZeldaRenderError
+    u = _uniforms()
+    sph, pla = _materials(False)
+    pla = list(pla)
+    pla[1] = np.full((32, 32, 4), 77, np.uint8)      # a constant image: zr_object_add collapses it
+    pla[5] = None                                    # the engine default
+    g = gpu_engine.Renderer(W, H, SD)
+    keep = _scene(g, sph, pla)
+    _frame(g, u)
+    good, small = _variant(sph[0], 1), _variant(pla[0], 1)
+    t = _dev(good)
+    torch.cuda.synchronize()
+    odd = t.reshape(-1)[1:1 + 64 * 63 * 4].reshape(63, 64, 4)      # one byte past a 4-byte boundary
+    calls = [(lambda: g.object_set_texture(7, 0, good), -1, "object"),                            # no such object
+             (lambda: g.object_set_texture(SPHERES, 7, good), -1, "slot"),
+             (lambda: g.object_update_texture_async(SPHERES, 7, t), -1, "slot"),
+             (lambda: g.object_set_texture(SPHERES, 0, small), -1, "32 x 32"),                    # another size than the slot's
+             (lambda: g.object_update_texture_async(SPHERES, 0, _dev(small)), -1, "32 x 32"),
+             (lambda: g._chk(g.L.zr_object_set_texture(g.h, SPHERES, 0, None)), -1, "missing"),                # no image at all
+             (lambda: g.object_update_texture_async(SPHERES, 0, odd), -1, "aligned"),
+             (lambda: g.object_set_texture(PLANE, 1, small), -6, "holds no image"),               # collapsed to a constant
+             (lambda: g.object_update_texture_async(PLANE, 1, _dev(small)), -6, "non-constant image of its final size"),
+             (lambda: g.object_set_texture(PLANE, 5, small), -6, "holds no image")]               # the engine default
+    for call, code, word in calls:
+        with pytest.raises(ZeldaRenderError) as e:
+            call()
+        assert e.value.code == code and word in str(e.value), (code, word, str(e.value))
+    cam, d, p, s = u
+    g.update_uniforms(cam, d, p, s, 0.0, 0.0, 1.0)
+    g.render_shadow()
+    for call in (lambda: g.object_set_texture(SPHERES, 0, good), lambda: g.object_update_texture_async(SPHERES, 0, t)):
+        with pytest.raises(ZeldaRenderError) as e:
+            call()
+        assert e.value.code == -6 and "between the stages" in str(e.value)
+    g.render_gbuffer(); g.render_lighting()
+    _frame(g, u)
+    g.finish()
+    got = (g.color().copy(), [g.gbuffer(k).copy() for k in range(6)])
+    _check_chain(g.object_get_texture(SPHERES, 0)[:1], [sph[0]], "the image after refused updates")
+    g.close()
+    b = gpu_engine.Renderer(W, H, SD)
+    keep = _scene(b, sph, pla)
+    _frame(b, u)
+    b.finish()
+    assert np.array_equal(got[0], b.color()), "colour after refused updates"
+    for k in range(6):
+        assert np.array_equal(got[1][k].view(np.uint8), b.gbuffer(k).view(np.uint8)), "GBuffer target %d after refused updates" % k
+    b.close()
+    del keep
+
+
+def test_rank_contexts_take_the_same_update(gpu_engine):
+    """tile_world = 2: every rank applies the same updates; its owned tiles equal the single context's frame."""
+    u = _uniforms()
+    sph, pla = _materials(False)
+    sph2, pla2 = _final(sph, pla)
+
+    def run(r):
+        keep = _scene(r, sph, pla)
+        _frame(r, u); _frame(r, u)
+        for slot in (0, 3, 6):
+            r.object_set_texture(SPHERES, slot, sph2[slot])
+        r.object_set_texture(PLANE, 2, pla2[2])
+        _frame(r, u)
+        r.finish()
+        return keep
+
+    single = gpu_engine.Renderer(W, H, SD)
+    keep = run(single)
+    want = single.color().copy()
+    single.close()
+    world = 2
+    for rank in range(world):
+        g = gpu_engine.Renderer(W, H, SD, tile_rank=rank, tile_world=world)
+        keep = run(g)
+        assert np.array_equal(g.read_tiles(), zdist.pack_tiles(want, rank, world)), "rank %d" % rank
+        g.close()
+    del keep

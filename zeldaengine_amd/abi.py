@@ -41,6 +41,17 @@ class Material(C.Structure):
     _fields_ = [("tex", Image * 7)]
 
 
+TEXTURE_SLOTS = ("bc", "m", "r", "n", "ao", "ev", "ms")      # the material's slots in order (zr_material::tex, zr_object_set_texture)
+# the texture-update entries of include/zelda_render.h (engine.lib() binds them with the rest)
+vp_, u32_ = C.c_void_p, C.c_uint32
+TEXTURE_UPDATE_SIGNATURES = {
+    "zr_object_set_texture": [vp_, u32_, u32_, C.POINTER(Image)],
+    "zr_object_update_texture_async": [vp_, u32_, u32_, vp_, u32_, u32_, vp_],
+    "zr_object_get_texture": [vp_, u32_, u32_, u32_, vp_, C.c_size_t, C.POINTER(u32_), C.POINTER(u32_), C.POINTER(u32_)],
+}
+del vp_, u32_
+
+
 class Camera(C.Structure):
     _fields_ = [("Position", C.c_float * 3), ("Lookat", C.c_float * 3), ("Speed", C.c_float), ("FOV", C.c_float),
                 ("zNear", C.c_float), ("zFar", C.c_float)]

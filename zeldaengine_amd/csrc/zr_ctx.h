@@ -171,6 +171,10 @@ struct zr_ctx {
     static constexpr int INST_RING = 4;
     struct InstStage { ZrOwn mem; uint8_t* h = nullptr; uint8_t* d = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; } inst_ring[INST_RING];      // cap: bytes
     uint32_t inst_slot = 0;
+    // Texture updates (zr_texture_update_host.cpp) rewrite a slot's mip chain and the packed material IN PLACE: ev_tex follows the last
+    // one (on tex_s); an update waits for the end of the frame enqueued last, the next frame's first stream waits for ev_tex (tex_wait).
+    // d_srgb_thr: the 256 sRGB encode thresholds (zr_srgb.h).  Made at the first update.
+    hipEvent_t ev_tex = nullptr; hipStream_t tex_s = nullptr; bool tex_wait = false; float* d_srgb_thr = nullptr;
     // this frame's two geometry passes (0 shadow, 1 camera), built at frame begin; the passes' work lists (k_cull_instances) are kept
     // while the pass block and the scene stand still: list_key = the block the list on the device was built from
     ZrPass pass[2]; bool pass_live[2] = { false, false }, list_reuse[2] = { false, false }, list_valid[2] = { false, false };
@@ -308,6 +312,8 @@ bool zr_mesh_update_due(const zr_ctx* c, int par);               // some mesh's 
 int zr_mesh_update_frame(zr_ctx* c, hipStream_t s, int par);     // frame head (zr_instances_frame): refit them, point the table at them
 bool zr_mesh_update_table(zr_ctx* c);                            // finalize_scene: new draw tables; true = the scene needs the parity-1 table
 int zr_mesh_sync_host(zr_ctx* c, ZrMesh& m, bool meshlets);      // zr_mesh_get_vertices / _get_meshlets after an update
+// zr_texture_update_host.cpp
+int zr_texture_frame(zr_ctx* c, hipStream_t s);                  // frame head: s behind the last texture update
 // No exception crosses the C-ABI: every exported function that returns a status runs its body through this, behind nothing but its
 // bare argument checks (tests/test_abi_and_symbols.py holds the sources to it).
 template <typename F> static inline int zr_guard(zr_ctx* c, F&& body) noexcept

@@ -6,6 +6,7 @@
 // zr_create fails.
 #include "zr_ctx.h"
 #include "zr_math.h"
+#include "zr_srgb.h"
 
 #include <algorithm>
 #include <cmath>
@@ -28,6 +29,7 @@ hipError_t zr_sync_all(zr_ctx* c)
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // (the host's stream may have been made to wait for the lanes)
     if (e == hipSuccess) e = zr_dist_sync(c);           // the native multi-GPU host's collective stream, if any
     if (e == hipSuccess && c->ev_scatter) e = hipEventSynchronize(c->ev_scatter);      // the last instance update (on a caller's stream)
+    if (e == hipSuccess && c->ev_tex) e = hipEventSynchronize(c->ev_tex);              // the last texture update (likewise)
     return e;
 }
 
@@ -41,14 +43,7 @@ float zr_srgb_decode8(uint32_t c)
     double l = (x <= 0.04045) ? x / 12.92 : pow((x + 0.055) / 1.055, 2.4);
     return (float)l;
 }
-static uint8_t srgb_encode8(float l)
-{
-    double x = (double)l;
-    if (!(x > 0.0)) x = 0.0;
-    if (x > 1.0) x = 1.0;
-    double s = (x <= 0.0031308) ? 12.92 * x : 1.055 * pow(x, 1.0 / 2.4) - 0.055;
-    return (uint8_t)floor(s * 255.0 + 0.5);
-}
+// srgb_encode8: zr_srgb.h (the texture updates build their threshold table from the same function)
 
 // ------------------------------------------------------------------------------------------------ lifetime
 
@@ -1239,6 +1234,8 @@ static int frame_begin(zr_ctx* c, hipStream_t s)
     if (F.ids_wait) { if (s != c->stream) HIPCHK(c, hipStreamWaitEvent(s, F.ev_ids, 0)); F.ids_wait = false; }
     // this frame's draw table; instance updates since the last frame of this parity go into its planes (zr_instances_host.cpp)
     rc = zr_instances_frame(c, s, c->fcur);
+    if (rc) return rc;
+    rc = zr_texture_frame(c, s);          // ... and behind the last texture update (zr_texture_update_host.cpp)
     if (rc) return rc;
     c->timing_now = c->timing_interval != 0 && c->frame_no % c->timing_interval == 0;     // pass events cost ~6 us of stream bubble each
     hipEvent_t* ev = c->timing_now ? c->evr[c->sample_no % zr_ctx::EV_RING] : nullptr;

@@ -221,6 +221,21 @@ struct ZrMeshState {
     ZrMeshSet set[2];
 };
 
+// One texture update (zr_texture_update.hip): a slot's RGBA8 mip chain, rewritten in place from a new level 0, and - when the object
+// has the packed form - the slot's bytes of the packed chain (16 B per texel of the same chain layout).
+struct ZrTexUpdate {
+    uint32_t* chain;                 // the slot's chain (level l at texel off[l])
+    uint8_t*  packed;                // the packed material's chain, or null
+    const float* srgb_lut;           // [256] sRGB decode; unorm_lut: [256] c / 255 (the resolve's tables)
+    const float* unorm_lut;
+    const float* srgb_thr;           // [256] encode thresholds (zr_srgb.h)
+    uint32_t w, h, levels, srgb;     // level 0's size; srgb: channels 0..2 are sRGB (slot 0)
+    uint32_t pk_ch, pk_n;            // the slot's first byte in a packed texel (ZR_PK_*) and how many of its channels live there
+    uint32_t off[16];                // first texel of level l in the chain
+    float    kx[16], ky[16];         // level l's source step: (float)w(l-1) / (float)w(l), as build_mip_chain forms it (IEEE quotients of the host)
+};
+void zr_launch_texture_update(const ZrTexUpdate& U, const uint32_t* src, hipStream_t s);
+
 // launchers: each defined in the .hip of its pass (zr_cull / zr_shadow / zr_camera / zr_resolve / zr_lighting / zr_forward / zr_frame /
 // zr_instances)
 void zr_launch_instance_prep(const XkInstanceData* in, ZrInstance* out, uint32_t n, uint32_t instanced, hipStream_t s);

@@ -58,6 +58,7 @@ def lib():
         "zr_mesh_set_vertices": [vp, u32, u32, vp, u32],
         "zr_mesh_update_vertices_async": [vp, u32, u32, vp, u32, vp],
         "zr_mesh_get_vertices": [vp, u32, vp, C.POINTER(u32)],
+        **abi.TEXTURE_UPDATE_SIGNATURES,
         "zr_set_cubemap": [vp, vp, u32],
         "zr_set_skydome": [vp, vp, u32, vp, u32, vp],
         "zr_set_background": [vp, vp],
@@ -376,6 +377,35 @@ class Renderer:
         verts = np.zeros(n.value, dtype=abi.XkVertex)
         self._chk(self.L.zr_mesh_get_vertices(self.h, mesh, _ptr(verts), C.byref(n)))
         return verts
+
+    def object_set_texture(self, index, slot, image):
+        """Replace the image of material slot `slot` (0..6, abi.TEXTURE_SLOTS) of object `index` with a uint8 [h, w, 4] array of the
+        slot's own size, from the next frame on (zr_object_set_texture); frames already enqueued keep the old image.  Every mip level and
+        the packed material follow on the GPU."""
+        img = np.ascontiguousarray(image, dtype=np.uint8)
+        assert img.ndim == 3 and img.shape[2] == 4
+        im = abi.Image(img.ctypes.data, img.shape[1], img.shape[0])
+        self._chk(self.L.zr_object_set_texture(self.h, index, slot, C.byref(im)))
+
+    def object_update_texture_async(self, index, slot, data, stream=None):
+        """The same from a contiguous CUDA uint8 tensor [h, w, 4], in the order of `stream` (a torch.cuda.Stream or a HIP stream handle;
+        None = the render stream).  It may be overwritten by work enqueued on `stream` afterwards (zr_object_update_texture_async)."""
+        assert data.is_cuda and data.is_contiguous() and data.element_size() == 1 and data.dim() == 3 and data.shape[2] == 4
+        h = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        self._chk(self.L.zr_object_update_texture_async(self.h, index, slot, C.c_void_p(data.data_ptr()), data.shape[1], data.shape[0],
+                                                        C.c_void_p(h) if h else None))
+
+    def object_get_texture(self, index, slot):
+        """The slot's current mip chain: a list of uint8 [h, w, 4] arrays, level 0 first (zr_object_get_texture)."""
+        w, h, n = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._chk(self.L.zr_object_get_texture(self.h, index, slot, 0, None, 0, C.byref(w), C.byref(h), C.byref(n)))
+        out = []
+        for level in range(n.value):
+            self._chk(self.L.zr_object_get_texture(self.h, index, slot, level, None, 0, C.byref(w), C.byref(h), C.byref(n)))
+            a = np.zeros((h.value, w.value, 4), dtype=np.uint8)
+            self._chk(self.L.zr_object_get_texture(self.h, index, slot, level, _ptr(a), a.nbytes, C.byref(w), C.byref(h), C.byref(n)))
+            out.append(a)
+        return out
 
     def set_cubemap(self, faces):
         if faces is None:
