@@ -11,6 +11,9 @@ HBM bytes, exactly as MI355X_MICROARCH.md (HBM section) prescribes: FETCH_SIZE a
 do not fit one), are in KiB, and on gfx950 FETCH_SIZE counts 64 B per 128 B read request, i.e. half the bytes of a coalesced
 stream (calibrated on k_count_shadow: a 4 MiB dword-per-lane read reports 2056 KiB), so bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024.
 Per-frame totals = sum over every dispatch of the frame's kernels / number of frames in that run (= dispatches of k_resolve_gbuffer).
+A frame that keeps its shadow map and resolves on the host's stream runs k_mark ahead of the resolve (the visibility history, on the
+camera lane): a frame kernel like the others, one launch per such frame; the GBuffer-write pass of bench.py's `roofline` counts its time
+with the resolve's (ZR_PASS_RESOLVE).
 
 Issue / wait accounting per kernel (SQ counters, one --pmc pass; the guide: SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_* count
 quad-cycles summed over waves, and WAIT_ANY + WAIT_INST_ANY + ACTIVE_INST_ANY ~ WAVE_CYCLES):
@@ -155,6 +158,9 @@ for k in sorted(set(fetch) | set(write) | set(valu)):
               "SQ_INSTS_VALU": (sum(v) / len(v) if v else None)}
     if k in issue:
         out[k]["issue"] = issue[k]
+if "k_mark" in out:
+    out["k_mark"]["note"] = ("the visibility history of a frame whose resolve runs on the host's stream (camera lane, ahead of ev_cam); its time is "
+                             "part of ZR_PASS_RESOLVE; launches_per_frame < 1: the frames that drew their shadow map ran none")
 if "k_lighting" in out:
     out["k_lighting"]["note"] = "two launches per frame: the full-screen pass + the one-pixel empty-colour pre-launch (the means are over both)"
 

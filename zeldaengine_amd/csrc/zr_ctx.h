@@ -239,12 +239,22 @@ struct zr_ctx {
     hipStream_t gbuf_s = nullptr;        // the stream the last deferred-scene pass was enqueued on (frame_begin: a change of it is a wait)
     bool in_render = false;
     hipEvent_t ev_join = nullptr, ev_cam = nullptr;
+    // The resolve's lane (zr_host.cpp: resolve_on_host_lane): a zr_render frame that keeps its shadow map leaves its resolve to the host's
+    // stream, ahead of its lighting pass; the camera lane marks the visibility history itself (k_mark) and goes on to the next frame.
+    // resolve_deferred: the frame being enqueued does so, resolve_P / resolve_mark what its resolve is launched with.  ev_cam then sits
+    // AHEAD of the lane's k_plan: plan_behind_cam says so to the next frame, which - if its camera pipeline runs on the host's stream -
+    // waits for the lane's end first (ev_lane, recorded only then).
+    bool resolve_deferred = false, plan_behind_cam = false; ZrPass resolve_P; uint32_t resolve_mark = 0;
+    hipEvent_t ev_lane = nullptr;
     unsigned long long* d_sky_keys = nullptr; uint32_t sky_object = 0;      // the skydome's key plane (k_sky_tiles) and its draw record
     // End of every frame's lighting pass, one (timing-enabled) event per frame in a ring: the next-but-one frame waits for it before
     // it reuses the double-buffered copies, and consecutive ones give the per-frame GPU period (zr_get_frame_periods) for free.
     static constexpr int END_RING = 512;
     hipEvent_t ev_end[END_RING] = {};
-    unsigned long long* d_vis = nullptr; uint32_t raster_blocks = 2048, shadow_blocks = 2048;
+    // The key buffer, one per frame parity like the FrameCopy resources (both hold the empty key between frames: the resolve resets what
+    // it reads): frame N's rounds, Hi-Z build, k_mark and resolve use copy N & 1, so a resolve on the host's stream is not in the next
+    // frame's way; the frame after that waits for ev_end[N] before it touches anything of this parity.
+    unsigned long long* d_vis[2] = { nullptr, nullptr }; uint32_t raster_blocks = 2048, shadow_blocks = 2048;
     uint4* d_slow0 = nullptr; uint32_t slow0_cap = 1u << 18;      // shadow pass: triangles for the clipper (k_tile_slow)
     uint32_t work_capacity = 0, bin_capacity = 0; bool any_images = false, mixed_images = false;
     uint32_t limit_record_chunks = 0, limit_slow_triangles = 0;      // zr_set_limits (0 = defaults)
@@ -261,6 +271,10 @@ struct zr_ctx {
     // The shadow pipeline's statistics / work counters (slot 0) live in a block of their own: the pipeline resets what it counts itself
     // (k_scan), so it does not wait for the camera lane's k_frame_begin, and the camera lane does not wait for it.
     ZrDevStats* d_sstats = nullptr; uint32_t list_rebuild_mask = 0;
+    // A resolve on the host's stream tallies its covered pixels into a block of its frame copy (only covered_part is used), zeroed on that
+    // stream: the next frame's k_frame_begin zeroes d_stats on the camera lane while it may still be counting.  cov_block: where the
+    // resolve of the frame enqueued last counted (d_stats, or one of these).
+    ZrDevStats* d_rstats[2] = { nullptr, nullptr }; ZrDevStats* cov_block = nullptr;
     uint64_t last_work[2] = { 0, 0 };
 
     // object identity of the last frame (zr_set_id_capture, zr_ids.hip).  The winner planes are FrameCopy::prim_plane, shared with the forward variant.
@@ -281,8 +295,10 @@ struct zr_ctx {
     ZrMesh sky_mesh; ZrSceneObject sky_obj; bool sky_set = false, sky_enabled = true;
     ZrOwn bg_mem; uint8_t* d_bg = nullptr; uint32_t bg_w = 0, bg_h = 0, bg_levels = 0; bool bg_set = false, bg_enabled = true;
 
-    hipEvent_t evr[EV_RING][10] = {}; uint64_t frame_no = 0; bool rendered = false;
+    // slots 0..9: see zr_get_pass_times_avg; 10 = end of k_mark (camera lane), 11 = start of a resolve on the host's stream
+    hipEvent_t evr[EV_RING][12] = {}; uint64_t frame_no = 0; bool rendered = false;
     uint32_t timing_interval = 1; bool timing_now = true; uint64_t sample_no = 0;    // pass events every interval-th frame
+    bool ev_moved[EV_RING] = {};         // the sample's frame resolved on the host's stream: ZR_PASS_RESOLVE is k_mark's time + the resolve's
     bool ev_kept[EV_RING] = {};          // the sample's frame kept its shadow map: its shadow durations are 0, not the gap between two records
 
     // world + livelink + the content tree (zr_assets.cpp)

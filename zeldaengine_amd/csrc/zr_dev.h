@@ -7,6 +7,7 @@
 //                    k_shadow_occlusion, k_count_shadow
 //   zr_camera.hip    camera pass, triangle-level binning: k_hiz_build, k_select, k_geom<HIZ, COUNT>, k_plan, k_tile, k_sky_tiles
 //   zr_resolve.hip   k_resolve_gbuffer: BaseScene.frag per pixel from the key buffer into the SoA GBuffer planes
+//                    k_mark: the visibility history alone, for a frame whose resolve runs on the host's stream
 //   zr_lighting.hip  k_lighting (BaseLighting.frag), k_gbuffer_vis (debug view 9)
 //   zr_forward.hip   k_forward: the forward variant, Base.frag
 //   zr_frame.hip     k_frame_begin, fills, k_untile / k_pack_tiles (multi-GPU composite)

@@ -81,6 +81,19 @@ static ZrTilePartition zr_partition(uint32_t tiles_x, uint32_t tiles_y, uint32_t
     return P;
 }
 
+// Schedule constants that are re-measured whenever the balance of the two lanes changes ("The schedule"): the camera lane's
+// stream priority (0 lowest, 1 normal, 2 highest), k_tile's persistent grid in workgroups per CU, and whether a frame that draws its
+// shadow map records ev_cam ahead of its k_plan too (a frame that resolves on the host's stream always does).
+#ifndef ZR_CAM_PRIORITY
+#define ZR_CAM_PRIORITY 0
+#endif
+#ifndef ZR_TILE_WG_PER_CU
+#define ZR_TILE_WG_PER_CU 12u
+#endif
+#ifndef ZR_EV_CAM_AHEAD_OF_PLAN
+#define ZR_EV_CAM_AHEAD_OF_PLAN 0
+#endif
+
 // zr_create's device half, straight through: it returns at the first failure, and the caller releases the partial context as
 // zr_destroy releases any other
 static int create_device_state(zr_ctx* c)
@@ -100,6 +113,8 @@ static int create_device_state(zr_ctx* c)
     }
     HIPCHK(c, A.alloc(&c->d_color, n)); HIPCHK(c, A.alloc(&c->d_stats, 1));
     HIPCHK(c, A.alloc(&c->d_sstats, 1));       // the shadow pipeline's own block (see zr_ctx.h)
+    for (auto& r : c->d_rstats) HIPCHK(c, A.alloc(&r, 1));      // ... and a host-lane resolve's, per frame copy
+    c->cov_block = c->d_stats;
     HIPCHK(c, A.alloc(&c->d_lut, 256));
     HIPCHK(c, hipMemcpy(c->d_lut, c->lut, sizeof c->lut, hipMemcpyHostToDevice));
     {
@@ -157,12 +172,13 @@ static int create_device_state(zr_ctx* c)
         // took from the host lane what it saved itself (5 300 Mpixel/s), at the lowest the host lane keeps its share (5 540; normal: 5 470).
         int least = 0, greatest = 0;
         (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-        HIPCHK(c, A.stream(&c->cam_s, least));
+        HIPCHK(c, A.stream(&c->cam_s, ZR_CAM_PRIORITY == 2 ? greatest : ZR_CAM_PRIORITY == 1 ? (least + greatest) / 2 : least));
     }
     HIPCHK(c, A.event(&c->ev_cam, hipEventDisableTiming)); HIPCHK(c, A.event(&c->ev_join, hipEventDisableTiming));
-    HIPCHK(c, A.alloc(&c->d_vis, n));
-    { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) c->raster_blocks = (uint32_t)prop.multiProcessorCount * 12u; }      // k_tile's persistent grid (6 workgroups fit a CU: two rounds of them; A/B 4 / 6 / 8 / 12 / 16 / 32 per CU -> 5 133 / 5 250 / 5 294 / 5 344 / 5 327 / 5 277 Mpixel/s)
-    c->shadow_blocks = c->raster_blocks / 12u * 8u;      // the shadow rasteriser's persistent grid stays at 8 per CU
+    HIPCHK(c, A.event(&c->ev_lane, hipEventDisableTiming));
+    for (auto& v : c->d_vis) HIPCHK(c, A.alloc(&v, n));
+    { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) c->raster_blocks = (uint32_t)prop.multiProcessorCount * ZR_TILE_WG_PER_CU; }      // k_tile's persistent grid (6 workgroups fit a CU: two rounds of them; A/B 4 / 6 / 8 / 12 / 16 / 32 per CU -> 5 133 / 5 250 / 5 294 / 5 344 / 5 327 / 5 277 Mpixel/s)
+    c->shadow_blocks = c->raster_blocks / ZR_TILE_WG_PER_CU * 8u;      // the shadow rasteriser's persistent grid stays at 8 per CU
     c->slow0_cap = std::max<uint32_t>(c->slow0_cap, 128u * c->sn_tiles);      // (a clipped triangle is listed once per tile of its meshlet)
     HIPCHK(c, A.alloc(&c->d_slow0, 4ull * c->slow0_cap));
 #ifdef ZR_DIAG
@@ -189,11 +205,12 @@ static int create_device_state(zr_ctx* c)
     }
     HIPCHK(c, zr_fill_sync({ { c->fc[0].G.overlay, 0, n * 4 }, { c->fc[1].G.overlay, 0, n * 4 },
                              { c->d_stats, 0, sizeof(ZrDevStats) }, { c->d_sstats, 0, sizeof(ZrDevStats) }, { c->d_color, 0, n * 4 },
+                             { c->d_rstats[0], 0, sizeof(ZrDevStats) }, { c->d_rstats[1], 0, sizeof(ZrDevStats) },
                              { c->d_tiles, 0, (size_t)c->slots_per_rank * ZR_TILE * ZR_TILE * 4 },
                              { c->sb.tile_count, 0, mt * 4 },       // k_bin_count counts into zeroes (k_scan zeroes the counts
                              { c->sb.tile_cursor, 0, mt * 4 },      // and the cursors again for the fill and the next frame)
                              { c->d_hiz, 0, hiz_texels * sizeof(float) } }));      // texels over other ranks' regions stay 0 ("hidden")
-    zr_launch_fill64(c->d_vis, (unsigned long long)0x3F800000u << 32 | ZR_EMPTY_PRIM, n, c->stream);
+    for (auto& v : c->d_vis) zr_launch_fill64(v, (unsigned long long)0x3F800000u << 32 | ZR_EMPTY_PRIM, n, c->stream);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     // The runtime backs an event with a signal on its FIRST record and grows that pool in batches, which blocks the host for
     // milliseconds at unpredictable frames of a short run: record every event once now.
@@ -1150,7 +1167,7 @@ static void tri_raster(zr_ctx* c, const ZrPass& P, const ZrHiz& Z, int slot, hip
     }
     zr_launch_geom(P, Z, c->tb, c->d_stats, slot, false, s);
     // (the frame's last round also draws the slow triangles of both rounds: k_tile<LAST>)
-    zr_launch_tile(P, c->tb, c->d_stats, slot, c->d_vis, c->raster_blocks, s, last, c->d_owned, c->n_owned);
+    zr_launch_tile(P, c->tb, c->d_stats, slot, c->d_vis[c->fcur], c->raster_blocks, s, last, c->d_owned, c->n_owned);
 }
 // the shadow rasteriser over the bins (stage: see zr_launch_raster_chunks)
 static void raster(zr_ctx* c, const ZrPass& P, hipStream_t s, int stage)
@@ -1204,9 +1221,9 @@ static int ids_prepare(zr_ctx* c)
     return ZR_OK;
 }
 
-// Start of a frame on stream s: pick this frame's copies of the double-buffered resources, make s wait until the lighting pass
-// that last read them (two frames ago) and the previous frame's shadow pipeline (it shares d_stats) are done, reset the
-// statistics, upload the uniforms if this copy does not hold them yet.
+// Start of a frame on stream s: pick this frame's copies of the double-buffered resources (key buffer included), make s wait until the
+// frame that last used them (two frames ago: its resolve, if that ran on the host's stream, and its lighting pass) is done, reset the
+// camera lane's statistics, upload the uniforms if this copy does not hold them yet.
 static int frame_begin(zr_ctx* c, hipStream_t s)
 {
     if (!c->frame_valid) return zr_fail(c, ZR_ERR_STATE, "no frame uniforms: call zr_update_uniforms or zr_set_frame first");
@@ -1221,15 +1238,19 @@ static int frame_begin(zr_ctx* c, hipStream_t s)
     if (c->id_capture) { rc = ids_prepare(c); if (rc) return rc; }
     c->fcur = (int)(c->frame_no & 1u);
     FrameCopy& F = c->fc[c->fcur];
-    // (two lanes: this frame's copies of the double-buffered resources were last read by the lighting pass of two frames ago, on the
-    // host's stream.  Nothing else ties the lanes together here: the shadow pipeline keeps statistics of its own)
+    // (two lanes: this frame's copies of the double-buffered resources were last used two frames ago, on the host's stream: read by the
+    // lighting pass, and before it the keys reset and the GBuffer written by the resolve where that ran there.  Nothing else ties the lanes
+    // together here: the shadow pipeline and a host-lane resolve keep statistics of their own)
     if (s != c->stream && c->frame_no >= 2) HIPCHK(c, hipStreamWaitEvent(s, c->ev_end[(c->frame_no - 2) % zr_ctx::END_RING], 0));
-    // Consecutive camera pipelines share the key buffer, the triangle records, the plan and the camera lane's statistics, and are ordered
-    // by running on ONE stream.  A frame on the lane that follows a frame of the staged entry points (its camera pipeline ran on the host's
-    // stream) waits for that frame's end instead.  (The other way round the host's stream has waited for the whole lane, k_plan included,
-    // before that frame's lighting pass: ev_cam.)
+    // Consecutive camera pipelines share the triangle records, the plan and the camera lane's statistics (the key buffer is one of a pair,
+    // like F), and are ordered by running on ONE stream.  A frame on the lane that follows a frame of the staged entry points (its camera
+    // pipeline ran on the host's stream) waits for that frame's end instead.  The other way round the host's stream has waited for ev_cam
+    // before that frame's lighting pass: the whole lane, k_plan included - unless that frame resolved on the host's stream, whose ev_cam
+    // sits ahead of k_plan; then this frame's camera pipeline, if it runs on the host's stream, waits for the lane's end here.
     if (s != c->stream && c->frame_no >= 1 && c->gbuf_s && c->gbuf_s != s)
         HIPCHK(c, hipStreamWaitEvent(s, c->ev_end[(c->frame_no - 1) % zr_ctx::END_RING], 0));
+    if (c->plan_behind_cam && s == c->stream && c->cam_s) { HIPCHK(c, hipEventRecord(c->ev_lane, c->cam_s)); HIPCHK(c, hipStreamWaitEvent(s, c->ev_lane, 0)); }
+    c->plan_behind_cam = false;
     // ... and by an identity census enqueued against them since (zr_instance_coverage_async, on the host's stream)
     if (F.ids_wait) { if (s != c->stream) HIPCHK(c, hipStreamWaitEvent(s, F.ev_ids, 0)); F.ids_wait = false; }
     // this frame's draw table; instance updates since the last frame of this parity go into its planes (zr_instances_host.cpp)
@@ -1323,8 +1344,20 @@ static int shadow_pass(zr_ctx* c, hipStream_t s)
     return ZR_OK;
 }
 
-// deferred-scene pass (ZE:3417-3480): cull + bin + raster + resolve of the owned tiles, on stream s
-static int gbuffer_pass(zr_ctx* c, hipStream_t s)
+// Where the frame's resolve runs.  Nothing later on the camera lane of the same frame needs its planes: only the same frame's lighting
+// pass reads them, on the host's stream.  In a frame that keeps its shadow map that stream has nothing else to do, and the camera lane's
+// chain of launches is the frame's period: the resolve then goes to the host's stream, ahead of the lighting pass, and k_mark leaves the
+// next frame's camera lane the visibility history.  Only zr_render does this (a host may read the GBuffer after zr_render_geometry, and
+// the staged entry points run on one stream anyway), only on two lanes, and not with a skydome (its key plane is single-buffered).
+// (shadow_keep already implies an unpartitioned context: shadow_keepable.)
+static inline bool resolve_on_host_lane(const zr_ctx* c, bool lanes)
+{
+    return lanes && c->in_render && c->shadow_keep && !(c->sky_set && c->sky_enabled);
+}
+
+// deferred-scene pass (ZE:3417-3480): cull + bin + raster + resolve of the owned tiles, on stream s.  defer_resolve: see above - the
+// resolve is left to zr_render_lighting (deferred_resolve), the lane ends k_mark -> ev_cam -> k_plan.
+static int gbuffer_pass(zr_ctx* c, hipStream_t s, bool defer_resolve = false)
 {
     hipEvent_t* ev = c->timing_now ? c->evr[c->sample_no % zr_ctx::EV_RING] : nullptr;
     if (ev) HIPCHK(c, hipEventRecord(ev[9], s));
@@ -1356,7 +1389,7 @@ static int gbuffer_pass(zr_ctx* c, hipStream_t s)
         if (ev) HIPCHK(c, hipEventRecord(ev[3], s));
         tri_raster(c, P, Z, 1, s, false, count_first);
         if (ev) HIPCHK(c, hipEventRecord(ev[4], s));
-        zr_launch_hiz_build(c->d_vis, c->W, c->H, Z, c->d_hiz_regions, c->n_hiz_regions, s);
+        zr_launch_hiz_build(c->d_vis[c->fcur], c->W, c->H, Z, c->d_hiz_regions, c->n_hiz_regions, s);
         Z.phase = 2;
         tri_select(c, P, Z, 2, s);
         if (ev) HIPCHK(c, hipEventRecord(ev[5], s));
@@ -1373,11 +1406,22 @@ static int gbuffer_pass(zr_ctx* c, hipStream_t s)
         P.sky_keys = nullptr; P.sky_object = c->sky_object;
         if (sky && c->d_sky_keys) { zr_launch_sky_tiles(P, c->d_objs, c->d_owned, c->n_owned, c->d_sky_keys, s); P.sky_keys = c->d_sky_keys; }
     }
-    if (ev) HIPCHK(c, hipEventRecord(ev[6], s));
-    zr_launch_resolve_gbuffer(P, c->d_objs, c->d_owned, c->n_owned, c->d_vis, c->fc[c->fcur].G, c->d_lut, c->d_unorm_lut, Z.vis_now, c->d_stats, s, vis_mark);
+    if (ev) { HIPCHK(c, hipEventRecord(ev[6], s)); c->ev_moved[c->sample_no % zr_ctx::EV_RING] = defer_resolve; }
+    c->resolve_deferred = defer_resolve;
+    if (defer_resolve) {
+        // the history now, the planes later: the host's stream waits for everything up to here and resolves from the same keys
+        zr_launch_mark(P, c->d_objs, c->d_owned, c->n_owned, c->d_vis[c->fcur], Z.vis_now, s, vis_mark);
+        if (ev) HIPCHK(c, hipEventRecord(ev[10], s));
+        c->resolve_P = P; c->resolve_mark = vis_mark;
+        HIPCHK(c, hipEventRecord(c->ev_cam, s)); c->camera_on_lane = true; c->plan_behind_cam = true;
+    } else {
+        zr_launch_resolve_gbuffer(P, c->d_objs, c->d_owned, c->n_owned, c->d_vis[c->fcur], c->fc[c->fcur].G, c->d_lut, c->d_unorm_lut, Z.vis_now, c->d_stats, s, vis_mark);
+        c->cov_block = c->d_stats;
+        if (ev) HIPCHK(c, hipEventRecord(ev[7], s));
+        if (ZR_EV_CAM_AHEAD_OF_PLAN && c->in_render && s != c->stream) { HIPCHK(c, hipEventRecord(c->ev_cam, s)); c->camera_on_lane = true; c->plan_behind_cam = true; }
+    }
     c->vis_mark_prev = vis_mark;
-    if (ev) HIPCHK(c, hipEventRecord(ev[7], s));
-    if (P.n_work != 0) {     // the next frame's buckets, from this frame's counts: nothing on this lane waits for it
+    if (P.n_work != 0) {     // the next frame's buckets, from this frame's counts: nothing of this frame waits for it
         zr_launch_plan(c->tb, c->d_owned, c->n_owned, c->d_stats, false, c->bucket_pct, s);
         c->plan_valid = true; c->plan_two_round = two;
     }
@@ -1413,8 +1457,9 @@ extern "C" int zr_render_gbuffer(zr_ctx* c)
 
 // Both geometry passes of a frame.  Two lanes (unless ZR_FLAG_SERIAL_PASSES): the camera pipeline on cam_s; the shadow pipeline on
 // the host's stream, where the lighting pass will follow.  The next frame's camera pipeline starts as soon as this one's is
-// through, next to this frame's lighting; its shadow pipeline follows the lighting.  Never more than two kernels side by side:
-// a third only takes occupancy from the other two (measured).
+// through, next to this frame's lighting; its shadow pipeline follows the lighting.  A frame that keeps its shadow map has no shadow
+// pipeline: in zr_render its resolve takes that place on the host's stream (resolve_on_host_lane), next to the next frame's camera
+// pipeline.  Never more than two kernels side by side: a third only takes occupancy from the other two (measured).
 static int geometry_passes(zr_ctx* c)
 {
     const bool lanes = !(c->cfg.flags & ZR_FLAG_SERIAL_PASSES) && c->cam_s != nullptr;
@@ -1429,8 +1474,10 @@ static int geometry_passes(zr_ctx* c)
         if (rc != ZR_OK) return rc;
         rc = shadow_pass(c, c->stream);
         if (rc == ZR_OK && !c->in_render) HIPCHK(c, hipEventRecord(c->ev_join, c->stream));      // (zr_stream_wait_shadow: a host that puts a collective behind the shadow pass)
-        if (rc == ZR_OK) rc = gbuffer_pass(c, c->cam_s);
-        if (rc == ZR_OK) { HIPCHK(c, hipEventRecord(c->ev_cam, c->cam_s)); c->camera_on_lane = true; }
+        const bool defer = resolve_on_host_lane(c, lanes);
+        if (rc == ZR_OK) rc = gbuffer_pass(c, c->cam_s, defer);
+        // (a deferred resolve: ev_cam is already recorded, behind k_mark and ahead of k_plan - the lighting lane does not wait for the plan)
+        if (rc == ZR_OK && !c->camera_on_lane) { HIPCHK(c, hipEventRecord(c->ev_cam, c->cam_s)); c->camera_on_lane = true; }
     } else {
         rc = frame_begin(c, c->stream);
         if (rc != ZR_OK) return rc;
@@ -1487,6 +1534,21 @@ static int empty_pixel_pass(zr_ctx* c, hipStream_t s)
     return ZR_OK;
 }
 
+// The resolve of a frame whose camera lane left it to the host's stream (gbuffer_pass), behind the wait for ev_cam: same launch, same
+// keys; the history is already marked (vis_now = nullptr) and the coverage tally goes to the frame copy's own block, zeroed here.
+static int deferred_resolve(zr_ctx* c, hipStream_t s)
+{
+    hipEvent_t* ev = c->timing_now ? c->evr[c->sample_no % zr_ctx::EV_RING] : nullptr;
+    ZrDevStats* const tally = c->d_rstats[c->fcur];
+    zr_launch_fill32(tally->covered_part, 0u, 32, s);
+    if (ev) HIPCHK(c, hipEventRecord(ev[11], s));
+    zr_launch_resolve_gbuffer(c->resolve_P, c->d_objs, c->d_owned, c->n_owned, c->d_vis[c->fcur], c->fc[c->fcur].G, c->d_lut, c->d_unorm_lut, nullptr, tally, s, c->resolve_mark);
+    if (ev) HIPCHK(c, hipEventRecord(ev[7], s));
+    c->cov_block = tally; c->resolve_deferred = false;
+    HIPCHK(c, hipGetLastError());
+    return ZR_OK;
+}
+
 static int lighting_pass(zr_ctx* c, hipStream_t s)
 {
     hipEvent_t* ev = c->timing_now ? c->evr[c->sample_no % zr_ctx::EV_RING] : nullptr;
@@ -1523,10 +1585,12 @@ extern "C" int zr_render_lighting(zr_ctx* c)
         if (c->stage != 2) return zr_fail(c, ZR_ERR_STATE, "zr_render_lighting out of order");
         HIPCHK(c, hipSetDevice(c->device));
         hipStream_t ls = c->stream;
-        // The one wait of the host's stream per frame: the camera lane's GBuffer - and, ahead of it on that lane, this frame's k_frame_begin,
-        // whose uniforms the empty-pixel pass below reads (the shadow pipeline before it needed nothing of them and did not wait).
+        // The one wait of the host's stream per frame: the camera lane's GBuffer (or, where the resolve follows here, its keys and history
+        // marks: ev_cam is then recorded ahead of the lane's k_plan) - and, ahead of it on that lane, this frame's k_frame_begin, whose
+        // uniforms the empty-pixel pass below reads (the shadow pipeline before it needed nothing of them and did not wait).
         if (c->camera_on_lane) HIPCHK(c, hipStreamWaitEvent(ls, c->ev_cam, 0));
-        int rc = empty_pixel_pass(c, ls);              // the shadow map (possibly reduced over ranks by the host) is final only now
+        int rc = c->resolve_deferred ? deferred_resolve(c, ls) : ZR_OK;
+        if (rc == ZR_OK) rc = empty_pixel_pass(c, ls); // the shadow map (possibly reduced over ranks by the host) is final only now
         if (rc == ZR_OK) rc = lighting_pass(c, ls);
         return rc;
     });
@@ -1538,6 +1602,8 @@ extern "C" int zr_render_lighting(zr_ctx* c)
 // frame's lighting.  zr_render therefore runs two lanes: the camera pipeline on the library's high-priority stream cam_s, and
 // shadow pipeline -> lighting on the host's stream.  Whatever the host enqueues on its stream after zr_render is ordered after
 // the finished frame, as before.  ZR_FLAG_SERIAL_PASSES keeps everything on the one stream, as the staged entry points do.
+// A frame that keeps its shadow map resolves on the host's stream (resolve_on_host_lane): camera lane ... -> k_tile -> k_mark -> ev_cam
+// -> k_plan, host's stream wait -> k_resolve_gbuffer -> one-pixel launch -> k_lighting -> ev_end.
 extern "C" int zr_render(zr_ctx* c)
 {
     if (!c) return ZR_ERR_ARG;
@@ -1660,6 +1726,8 @@ extern "C" int zr_finish(zr_ctx* c)
         HIPCHK(c, zr_sync_all(c));
         if (c->rendered) {
             HIPCHK(c, hipMemcpy(&c->h_stats, c->d_stats, sizeof(ZrDevStats), hipMemcpyDeviceToHost));
+            if (c->cov_block != c->d_stats)       // the newest frame's resolve ran on the host's stream and counted into its own block
+                HIPCHK(c, hipMemcpy(c->h_stats.covered_part, c->cov_block->covered_part, sizeof c->h_stats.covered_part, hipMemcpyDeviceToHost));
             ZrDevStats sh;
             HIPCHK(c, hipMemcpy(&sh, c->d_sstats, sizeof(ZrDevStats), hipMemcpyDeviceToHost));
             merge_shadow_stats(c, sh);
@@ -1701,7 +1769,13 @@ extern "C" int zr_get_pass_times_avg(zr_ctx* c, uint32_t last_n, float ms[ZR_PAS
             (void)hipEventElapsedTime(&t[ZR_PASS_GBUFFER], ev[3], ev[4]);
             (void)hipEventElapsedTime(&t[ZR_PASS_HIZ], ev[4], ev[5]);
             (void)hipEventElapsedTime(&t[ZR_PASS_GBUFFER2], ev[5], ev[6]);
-            (void)hipEventElapsedTime(&t[ZR_PASS_RESOLVE], ev[6], ev[7]);
+            if (c->ev_moved[(c->sample_no - 1 - k) % zr_ctx::EV_RING]) {
+                // the resolve on the host's stream: k_mark on the camera lane + the resolve itself, each between two records on the stream
+                // it ran on (never across the wait between the lanes)
+                float tm = 0.0f, tr = 0.0f;
+                (void)hipEventElapsedTime(&tm, ev[6], ev[10]); (void)hipEventElapsedTime(&tr, ev[11], ev[7]);
+                t[ZR_PASS_RESOLVE] = tm + tr;
+            } else (void)hipEventElapsedTime(&t[ZR_PASS_RESOLVE], ev[6], ev[7]);
             (void)hipEventElapsedTime(&t[ZR_PASS_LIGHTING], ev[7], ev[8]);
             (void)hipEventElapsedTime(&t[ZR_PASS_TOTAL], ev[0], ev[8]);
             // (a frame that kept its shadow map ran no shadow pipeline: exactly 0, not the gap between two back-to-back records)

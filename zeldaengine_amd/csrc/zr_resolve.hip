@@ -1,5 +1,7 @@
 // zr_resolve.hip — k_resolve_gbuffer: BaseScene.frag per pixel from the frame's key buffer into the SoA GBuffer planes (28 B / px,
-// formats ZE:2807-2843), coalesced row stores; marks the meshlet-instances that own a pixel (next frame's round 1).
+// formats ZE:2807-2843), coalesced row stores; marks the meshlet-instances that own a pixel (next frame's round 1) - unless k_mark
+// did that ahead of it: the history is all the next frame's camera lane needs of the resolve, and a frame whose resolve runs on the
+// other lane (zr_host.cpp: gbuffer_pass) takes it from the keys alone.
 #include "zr_dev.h"
 #include "zr_surface.h"
 
@@ -68,7 +70,38 @@ __global__ __launch_bounds__(TB, TB == 64 ? ZR_RESOLVE_IMG_WAVES : 1) void k_res
     if (threadIdx.x == 0 && covered_s) atomicAdd(&stats->covered_part[blockIdx.x & 31u], covered_s);
 }
 
-// ------------------------------------------------------------------------------------------------ launcher (C++ linkage, used by zr_host.cpp)
+// The visibility history without the resolve: what pixel_geom does for vis_now and nothing else - key -> primitive -> meshlet-instance
+// -> this frame's stamp, same indices, same value.  Reads the keys, writes none.  A thread per pixel, row-major in the tile as in the
+// resolve, so a row of 16 lanes is 16 neighbouring pixels: a lane whose meshlet-instance is its left neighbour's leaves the store to it.
+__global__ __launch_bounds__(256) void k_mark(ZrPass P, const ZrObject* __restrict__ objs, const uint32_t* __restrict__ owned_tiles,
+                                              const unsigned long long* __restrict__ vis64, uint8_t* __restrict__ vis_now, uint32_t vis_mark)
+{
+    const uint32_t i = threadIdx.x + (blockIdx.x % (TILE_PIX / 256u)) * 256u;
+    const uint32_t tile = owned_tiles[blockIdx.x / (TILE_PIX / 256u)];
+    const int px = (int)(tile % P.tiles_x) * TILE + (int)(i & (TILE - 1)), py = (int)(tile / P.tiles_x) * TILE + (int)(i / TILE);
+    uint32_t mi = 0xFFFFFFFFu;          // the pixel's meshlet-instance (none: off the target, or an empty pixel)
+    if (px < (int)P.W && py < (int)P.H) {
+        const uint32_t prim = (uint32_t)vis64[(size_t)py * P.W + (size_t)px];
+        if (prim != ZR_EMPTY_PRIM) {
+            const ZrObject* __restrict__ O = objs + find_object_prim(objs, (int)P.n_objects, prim);
+            const uint32_t local = prim - O->prim_base;
+            const uint32_t inst_i = local / O->n_tris, tri = local - inst_i * O->n_tris;
+            mi = O->work_base + inst_i * O->n_meshlets + ld_global(O->tri_meshlet + tri);
+        }
+    }
+    // (row_shr:1 - the first lane of a row has no source and keeps a value no index equals: it always stores its own)
+    const uint32_t left = (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFEu, (int)mi, 0x111, 0xF, 0xF, false);
+    if (mi != 0xFFFFFFFFu && mi != left) vis_now[mi] = (uint8_t)vis_mark;
+}
+
+// ------------------------------------------------------------------------------------------------ launchers (C++ linkage, used by zr_host.cpp)
+
+void zr_launch_mark(const ZrPass& P, const ZrObject* objs, const uint32_t* owned_tiles, uint32_t n_owned, const unsigned long long* vis64,
+                    uint8_t* vis_now, hipStream_t s, uint32_t vis_mark)
+{
+    if (n_owned == 0 || vis_now == nullptr) return;
+    hipLaunchKernelGGL(k_mark, dim3(n_owned * (TILE_PIX / 256u)), dim3(256), 0, s, P, objs, owned_tiles, vis64, vis_now, vis_mark);
+}
 
 void zr_launch_resolve_gbuffer(const ZrPass& P, const ZrObject* objs, const uint32_t* owned_tiles, uint32_t n_owned,
                                unsigned long long* vis64, const GBufferPtrs& G, const float* srgb_lut, const float* unorm_lut, uint8_t* vis_now,

@@ -304,6 +304,8 @@ void zr_launch_shadow_occlusion(const ZrPass& P, const ZrObject* objs, const uin
 void zr_launch_raster_chunks(const ZrPass& P, const ZrObject* objs, const uint4* chunk_tab, const ZrBinEntry* bins, ZrDevStats* stats, int slot,
                              uint32_t* shadow_bits, uint32_t n_blocks, hipStream_t s, uint4* slow, uint32_t slow_cap, const uint32_t* tiles,
                              uint32_t n_tiles, int stage);
+void zr_launch_mark(const ZrPass& P, const ZrObject* objs, const uint32_t* owned_tiles, uint32_t n_owned, const unsigned long long* vis64,
+                    uint8_t* vis_now, hipStream_t s, uint32_t vis_mark);
 void zr_launch_resolve_gbuffer(const ZrPass& P, const ZrObject* objs, const uint32_t* owned_tiles, uint32_t n_owned,
                                unsigned long long* vis64, const GBufferPtrs& G, const float* srgb_lut, const float* unorm_lut, uint8_t* vis_now,
                                ZrDevStats* stats, hipStream_t s, uint32_t vis_mark = 1u);
