@@ -176,6 +176,37 @@ int  zr_object_set_instances(zr_ctx* ctx, uint32_t index, uint32_t first, const 
  * of its values.  Both buffers 4-byte aligned.  No host synchronisation (zr_object_get_instances reads back with one). */
 int  zr_object_update_instances_async(zr_ctx* ctx, uint32_t index, uint32_t first, const uint32_t* idx_dev,
                                       const XkInstanceData* data_dev, uint32_t n, void* hip_stream);
+/* Hiding and showing.  An instance is drawn iff its object is visible AND its own byte is nonzero; the two states are
+ * independent (hiding an object and showing it again keeps its instance bytes), and zr_object_add starts everything visible.  A hidden
+ * instance is absent from every pass and every entry point that draws - the shadow map, the camera pass, deferred and forward shading,
+ * all debug views; zr_render, the staged calls, zr_render_geometry, rank contexts, zr_dist_frame - and the frame is, byte for byte, the
+ * frame of a context built with only the shown objects and instances, in the same order.  Takes effect with the next zr_render; frames
+ * already enqueued still draw the old state (two frames stay in flight, the host is never synchronised).  The scene does not change:
+ * primitive ids, object and instance numbering and coverage slots are those of the full scene (a hidden instance keeps its slot,
+ * zr_instance_coverage reads 0 there), the shadow partition by i % world keeps using the full scene's instance index, and the identity
+ * queries go on describing the last frame until the next one is rendered.  zr_object_set_instances / zr_object_update_instances_async on
+ * a hidden instance move it and leave it hidden; either order of a move and a hide between two frames gives the same result.
+ * zr_object_get_instances returns hidden instances too.  zr_stats: covered_pixels, covered_shadow_texels, survivors and bin_entries
+ * describe what was drawn; work_items still counts hidden meshlet-instances (they are tested, and rejected first).  zr_scene_clear and
+ * world loads start over, with everything visible.
+ * Between the stages of a frame: ZR_ERR_STATE.  A bad object index, the per-instance forms on a non-instanced object, a range beyond the
+ * instance count, n > 0 with a null buffer, a misaligned idx_dev: ZR_ERR_ARG, and the context is unchanged.  n == 0, or a
+ * zr_object_set_visible that flips nothing: ZR_OK, and nothing changes (the kept shadow map stays kept).
+ * Whole object (any object, instanced or not); visible != 0 shows it: */
+int  zr_object_set_visible(zr_ctx* ctx, uint32_t index, int visible);
+/* Instances [first, first + n) of instanced object `index`: visible[i] == 0 hides, != 0 shows.  `visible` may be reused when the call
+ * returns.  Works before the scene's first frame. */
+int  zr_object_set_instance_visibility(zr_ctx* ctx, uint32_t index, uint32_t first, const uint8_t* visible, uint32_t n);
+/* The same from caller-owned DEVICE memory, in the order of hip_stream (NULL = the render stream): visible_dev[i] applies to instance
+ * idx_dev[i] (idx_dev NULL = instances first .. first + n - 1; with idx_dev the indices are the object's own and `first` only enters the
+ * range check).  Both buffers are read only inside hip_stream's order: a caller may overwrite them with work enqueued on hip_stream
+ * after this call.  Device indices >= the object's instance count are ignored; an index listed twice in one call gets one of its values.
+ * idx_dev 4-byte aligned, visible_dev bytes.  No host synchronisation.  A scene no frame has used yet: ZR_ERR_STATE (use the host form). */
+int  zr_object_update_instance_visibility_async(zr_ctx* ctx, uint32_t index, uint32_t first, const uint32_t* idx_dev,
+                                                const uint8_t* visible_dev, uint32_t n, void* hip_stream);
+/* Copy out: *object_visible, and one byte (0 / 1) per instance (any pointer may be NULL; *n = the instance count, 0 for a non-instanced
+ * draw).  After a device-form update this reads back with one synchronisation. */
+int  zr_object_get_visibility(zr_ctx* ctx, uint32_t index, int* object_visible, uint8_t* dst, uint32_t* n);
 /* Deforming meshes.  Replace vertices [first, first + n) of mesh `mesh_id`, all 44 bytes of each XkVertex.  The
  * vertex count, the index buffer and the meshlet partition are fixed: only the values move; bounding spheres, normal cones and boxes are
  * refitted by the library.  Takes effect with the next zr_render; frames already enqueued still draw the old shape; every object that

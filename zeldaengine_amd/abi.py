@@ -49,6 +49,13 @@ TEXTURE_UPDATE_SIGNATURES = {
     "zr_object_update_texture_async": [vp_, u32_, u32_, vp_, u32_, u32_, vp_],
     "zr_object_get_texture": [vp_, u32_, u32_, u32_, vp_, C.c_size_t, C.POINTER(u32_), C.POINTER(u32_), C.POINTER(u32_)],
 }
+# hiding and showing (include/zelda_render.h, "Hiding and showing"); merged into engine.lib()'s table like the texture block
+VISIBILITY_SIGNATURES = {
+    "zr_object_set_visible": [vp_, u32_, C.c_int],
+    "zr_object_set_instance_visibility": [vp_, u32_, u32_, vp_, u32_],
+    "zr_object_update_instance_visibility_async": [vp_, u32_, u32_, vp_, vp_, u32_, vp_],
+    "zr_object_get_visibility": [vp_, u32_, C.POINTER(C.c_int), vp_, C.POINTER(u32_)],
+}
 del vp_, u32_
 
 

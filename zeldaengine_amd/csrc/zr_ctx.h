@@ -105,6 +105,11 @@ struct ZrSceneObject {
     // pending[p]: an upper bound of list p's length on the device; tab1 = the parity-1 draw table points at plane[1];
     // host_stale = a device-form update came after `inst` (zr_object_get_instances reads back); draw = the record in the draw table.
     ZrInstanceState upd = {}; uint32_t pending[2] = { 0, 0 }; bool tab1 = false, host_stale = false; uint32_t draw = 0;
+    // Visibility (zr_instances_host.cpp): hidden = the whole object (ZR_OBJ_HIDDEN in the draw record), flag_pending[p] = the parity-p
+    // table does not hold it yet; vis = the host copy of upd.vis (empty: never touched, every instance shown), vis_stale = a device-form
+    // update came after it (zr_object_get_visibility reads back).
+    bool hidden = false, flag_pending[2] = { false, false }, vis_stale = false;
+    std::vector<uint8_t> vis;
     uint32_t texel[7]; float bc_linear[3];
     uint8_t* d_tex[8] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };   // [7]: the packed material (ZrObject::packed)
     uint32_t tex_w[8] = { 0 }, tex_h[8] = { 0 }, tex_levels[8] = { 0 };

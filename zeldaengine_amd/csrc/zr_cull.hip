@@ -91,7 +91,8 @@ __device__ __forceinline__ bool sphere_reaches_owned_tile(const ZrPass& P, zf3 c
 
 // Level 1 of the cull hierarchy: one lane per instance, whole-mesh bounding sphere against the frustum (same inflated
 // bounds as the meshlet test, so it is conservative).  The meshlet-instances of the surviving instances are appended to
-// work[]; one atomic per wave reserves the range.  Also applies the shadow-pass filters (skydome, instance partition).
+// work[]; one atomic per wave reserves the range.  Also applies the shadow-pass filters (skydome, instance partition) and drops
+// hidden objects and instances.
 #define ZR_CI_THREADS 1024u
 #define ZR_CI_PER 4u                        // instances per thread: one reservation per 4 096 instances
 // instance g (global ordinal) against the pass's instance-level tests; nm / wbase: its meshlet-instances, co / radius: its bounding sphere
@@ -106,8 +107,11 @@ __device__ __forceinline__ bool instance_test(const ZrPass& P, const ZrObject* _
     // the skydome is not a shadow caster (ZE:4709-4720); with N GPUs each draws every N-th instance into its own copy of
     // the shadow map and the copies are min-reduced (depth test LESS_OR_EQUAL is a min, so the split is exact)
     if (MODE == ZR_MODE_SHADOW && ((O->flags & ZR_OBJ_SKY) || inst_i % P.inst_world != P.inst_rank)) vis = false;
+    // hidden (zr_object_set_visible, zr_object_set_instance_visibility): gone from every pass, whatever the culling flags say - so the
+    // record is loaded even when no other test needs it
+    const ZrInstance I = ld_record(O->inst + inst_i);
+    if ((O->flags & ZR_OBJ_HIDDEN) || zr_f2u(I._pad[0]) != 0u) vis = false;
     if (vis && (P.frustum_ok | P.rect_cull | P.sphere_ok)) {
-        const ZrInstance I = ld_record(O->inst + inst_i);
         const bool instanced = O->instanced != 0;
         co = vs_position(zr3(O->mesh_center[0], O->mesh_center[1], O->mesh_center[2]), I, instanced);
         radius = O->mesh_radius * (instanced ? __builtin_fabsf(I.s) : 1.0f);
@@ -199,6 +203,8 @@ __device__ __forceinline__ bool cull_stage_a(const ZrPass& P, const ZrObject* __
     it.sph_c = vs_position(zr3(bs.x, bs.y, bs.z), I, instanced != 0); it.sph_r = bs.w * (instanced ? __builtin_fabsf(I.s) : 1.0f);
     // the skydome is not a shadow caster (ZE:4709-4720); with N GPUs each draws every N-th instance (see k_cull_instances)
     if (MODE == ZR_MODE_SHADOW && ((O->flags & ZR_OBJ_SKY) || inst_i % P.inst_world != P.inst_rank)) alive = false;
+    // hidden objects and instances: one flag test and one compare on the record just loaded, ahead of every other test
+    if ((O->flags & ZR_OBJ_HIDDEN) || zr_f2u(I._pad[0]) != 0u) alive = false;
     if (alive && (P.frustum_ok | P.cone_ok | P.rect_cull)) {
         const zf3 co = vs_position(zr3(bs.x, bs.y, bs.z), I, instanced != 0);
         const zf4 cw4 = zr_mat4_point(P.M, co);

@@ -765,7 +765,7 @@ static int finalize_scene(zr_ctx* c)
     };
     for (int pass = 0; pass < 2; ++pass)                 // non-instanced draws, then instanced draws (ZE:3445-3476)
         for (auto& o : c->objects)
-            if ((int)o.instanced == pass) emit(o, c->meshes[o.mesh], 0u);
+            if ((int)o.instanced == pass) emit(o, c->meshes[o.mesh], o.hidden ? ZR_OBJ_HIDDEN : 0u);
     // The skydome is the table's last record but no work item of the shadow or the deferred-scene pass: it is drawn after the lighting
     // quad (ZE:3681-3691), depth-tested against the scene and colour only - k_sky_tiles + the resolve.
     const uint64_t scene_work = work, scene_inst = inst_total;

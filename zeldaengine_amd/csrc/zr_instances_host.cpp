@@ -1,11 +1,16 @@
 // zr_instances_host.cpp — moving instances between frames: zr_object_set_instances (host data, through a pinned staging ring) and
-// zr_object_update_instances_async (caller-owned device data, in the order of the caller's stream).  Kernels: zr_instances.hip.
+// zr_object_update_instances_async (caller-owned device data, in the order of the caller's stream); hiding and showing them, and whole
+// objects: zr_object_set_instance_visibility, zr_object_update_instance_visibility_async, zr_object_set_visible.  Kernels: zr_instances.hip.
 //
 // Ordering ("Moving instances").  A frame of parity p reads the draw table and the instance planes of parity p; an update
 // writes only the raw values and the stale lists, and the records of plane p are rebuilt at the head of the next frame of parity p, after
 // the last frame that read plane p has finished.  So a frame already enqueued keeps the values it was enqueued with, and no update waits
 // for a frame.  Raw values are written by k_instance_scatter and read by k_instance_apply: every scatter is ordered after the last apply
 // (ev_apply), and every apply after the last scatter (ev_scatter).
+//
+// Visibility rides on all of it ("Hiding and showing"): an instance's byte is scattered like a raw value and lands in the
+// record's hidden word with the same apply; an object's ZR_OBJ_HIDDEN flag is written into the draw table of each parity at the head of
+// that parity's next frame, behind the same waits.
 //
 // Vertex updates (zr_mesh_update_host.cpp) keep the same contract with the same events, tables and staging ring: their scatter is
 // bracketed by zr_update_begin / zr_update_end, their refit runs in zr_instances_frame beside the applies.
@@ -33,12 +38,14 @@ static int inst_init_object(zr_ctx* c, ZrSceneObject& o, hipStream_t x)
     ZrOwn mem;                          // (the object's once both are made)
     hipError_t e = mem.alloc(&S.plane[1], n);
     if (e == hipSuccess) e = mem.alloc(&S.dirty, 3 * n + 2);
+    if (e == hipSuccess) e = mem.alloc(&S.vis, n);
     if (e != hipSuccess) return zr_fail(c, ZR_ERR_OOM, std::string("instance update state: ") + hipGetErrorString(e));
     o.mem.adopt(std::move(mem));
     S.list[0] = S.dirty + n; S.list[1] = S.dirty + 2 * n; S.count = S.dirty + 3 * n;
     o.upd = S; o.pending[0] = o.pending[1] = 0; o.tab1 = false;
     HIPCHK(c, hipMemsetAsync(S.dirty, 0, n * sizeof(uint32_t), x));
     HIPCHK(c, hipMemsetAsync(S.count, 0, 2 * sizeof(uint32_t), x));
+    HIPCHK(c, hipMemsetAsync(S.vis, 1, n, x));      // (every instance shown: the records so far say so)
     // (plane 0 is written only by applies of this object, and there has been none)
     HIPCHK(c, hipMemcpyAsync(S.plane[1], o.d_inst, n * sizeof(ZrInstance), hipMemcpyDeviceToDevice, x));
     return ZR_OK;
@@ -112,14 +119,17 @@ static int inst_object(zr_ctx* c, uint32_t index, uint32_t first, uint32_t n, co
     return ZR_OK;
 }
 
-// k_instance_scatter of (idx, data) on stream x, behind the last apply and the last update
-static int inst_enqueue(zr_ctx* c, ZrSceneObject& o, hipStream_t x, const uint32_t* idx, const XkInstanceData* data, uint32_t first, uint32_t n)
+// k_instance_scatter of (idx, data) - or, with `visible`, k_visibility_scatter of (idx, visible) - on stream x, behind the last apply and
+// the last update
+static int inst_enqueue(zr_ctx* c, ZrSceneObject& o, hipStream_t x, const uint32_t* idx, const XkInstanceData* data, uint32_t first, uint32_t n,
+                        const uint8_t* visible = nullptr)
 {
     int rc = inst_init_ctx(c);
     if (rc == ZR_OK) rc = inst_init_object(c, o, x);
     if (rc == ZR_OK) rc = zr_update_begin(c, x);
     if (rc) return rc;
-    zr_launch_instance_scatter(idx, data, first, n, o.upd, x);
+    if (visible) zr_launch_visibility_scatter(idx, visible, first, n, o.upd, x);
+    else zr_launch_instance_scatter(idx, data, first, n, o.upd, x);
     rc = zr_update_end(c, x);
     if (rc) return rc;
     for (auto& p : o.pending) p = (uint32_t)std::min<uint64_t>(o.n_inst, (uint64_t)p + n);
@@ -170,6 +180,98 @@ extern "C" int zr_object_update_instances_async(zr_ctx* c, uint32_t index, uint3
     });
 }
 
+// ------------------------------------------------------------------------------------------------ hiding and showing
+
+extern "C" int zr_object_set_instance_visibility(zr_ctx* c, uint32_t index, uint32_t first, const uint8_t* visible, uint32_t n)
+{
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        ZrSceneObject* o = nullptr;
+        int rc = inst_object(c, index, first, n, "zr_object_set_instance_visibility", &o);
+        if (rc) return rc;
+        if (n == 0) return ZR_OK;
+        if (!visible) return zr_fail(c, ZR_ERR_ARG, "zr_object_set_instance_visibility: no data");
+        HIPCHK(c, hipSetDevice(c->device));
+        hipStream_t x = c->cam_s ? c->cam_s : c->stream;      // (the camera lane, as zr_object_set_instances)
+        void* staged = nullptr; hipEvent_t ev = nullptr;
+        rc = zr_update_stage(c, x, visible, n, &staged, &ev);
+        if (rc) return rc;
+        rc = inst_enqueue(c, *o, x, nullptr, nullptr, first, n, (const uint8_t*)staged);
+        if (rc) return rc;
+        HIPCHK(c, hipEventRecord(ev, x));
+        if (!o->vis_stale) {      // (else the read-back brings it)
+            if (o->vis.empty()) o->vis.assign(o->n_inst, 1);
+            for (uint32_t i = 0; i < n; ++i) o->vis[first + i] = visible[i] ? 1 : 0;
+        }
+        return ZR_OK;
+    });
+}
+
+extern "C" int zr_object_update_instance_visibility_async(zr_ctx* c, uint32_t index, uint32_t first, const uint32_t* idx_dev,
+                                                          const uint8_t* visible_dev, uint32_t n, void* hip_stream)
+{
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        ZrSceneObject* o = nullptr;
+        int rc = inst_object(c, index, first, n, "zr_object_update_instance_visibility_async", &o);
+        if (rc) return rc;
+        if (n == 0) return ZR_OK;
+        if (!visible_dev || ((uintptr_t)idx_dev & 3u))
+            return zr_fail(c, ZR_ERR_ARG, "zr_object_update_instance_visibility_async: visible_dev missing, or idx_dev not 4-byte aligned");
+        if (c->scene_dirty) return zr_fail(c, ZR_ERR_STATE, "zr_object_update_instance_visibility_async: no frame has used this scene yet (use zr_object_set_instance_visibility)");
+        HIPCHK(c, hipSetDevice(c->device));
+        hipStream_t x = hip_stream ? (hipStream_t)hip_stream : c->stream;
+        rc = inst_enqueue(c, *o, x, idx_dev, nullptr, first, n, visible_dev);
+        if (rc) return rc;
+        o->vis_stale = true;
+        return ZR_OK;
+    });
+}
+
+extern "C" int zr_object_set_visible(zr_ctx* c, uint32_t index, int visible)
+{
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        if (c->stage != 0) return zr_fail(c, ZR_ERR_STATE, "zr_object_set_visible between the stages of a frame (finish it with zr_render_lighting first)");
+        if (index >= c->objects.size()) return zr_fail(c, ZR_ERR_ARG, "zr_object_set_visible: bad object index");
+        ZrSceneObject& o = c->objects[index];
+        if (o.hidden == !visible) return ZR_OK;      // (no flip: nothing changes, the shadow map stays kept)
+        if (c->scene_dirty) { o.hidden = !visible; return ZR_OK; }      // finalize_scene writes the flag into the tables it makes
+        // The draw table of each parity gets the flag at the head of that parity's next frame (zr_instances_frame), behind the same waits
+        // as an instance apply; nothing is scattered, but the frames follow this point of x like any update: the parity-1 table may
+        // just have been made on it.
+        HIPCHK(c, hipSetDevice(c->device));
+        hipStream_t x = c->cam_s ? c->cam_s : c->stream;
+        int rc = zr_update_begin(c, x);
+        if (rc == ZR_OK) rc = zr_update_end(c, x);
+        if (rc) return rc;
+        o.hidden = !visible; o.flag_pending[0] = o.flag_pending[1] = true;
+        return ZR_OK;
+    });
+}
+
+extern "C" int zr_object_get_visibility(zr_ctx* c, uint32_t index, int* object_visible, uint8_t* dst, uint32_t* n)
+{
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        if (index >= c->objects.size()) return zr_fail(c, ZR_ERR_ARG, "zr_object_get_visibility: bad object index");
+        ZrSceneObject& o = c->objects[index];
+        if (object_visible) *object_visible = o.hidden ? 0 : 1;
+        if (n) *n = o.instanced ? o.n_inst : 0u;
+        if (!dst || !o.instanced) return ZR_OK;
+        if (o.vis_stale) {
+            HIPCHK(c, hipSetDevice(c->device));
+            if (c->ev_scatter) HIPCHK(c, hipEventSynchronize(c->ev_scatter));      // the last update has landed in the bytes
+            o.vis.resize(o.n_inst);
+            HIPCHK(c, hipMemcpy(o.vis.data(), o.upd.vis, o.n_inst, hipMemcpyDeviceToHost));
+            o.vis_stale = false;
+        }
+        if (o.vis.empty()) memset(dst, 1, o.n_inst);
+        else memcpy(dst, o.vis.data(), o.n_inst);
+        return ZR_OK;
+    });
+}
+
 int zr_instances_sync_host(zr_ctx* c, ZrSceneObject& o)
 {
     HIPCHK(c, hipSetDevice(c->device));
@@ -186,7 +288,7 @@ int zr_instances_table(zr_ctx* c)
     c->inst_dual = false;
     c->inst_reader[0] = c->inst_reader[1] = 0;      // (nothing is in flight)
     bool any = false;
-    for (auto& o : c->objects) { o.tab1 = false; any |= o.upd.plane[1] != nullptr; }
+    for (auto& o : c->objects) { o.tab1 = false; o.flag_pending[0] = o.flag_pending[1] = false; any |= o.upd.plane[1] != nullptr; }      // (table 0 holds every flag)
     any |= zr_mesh_update_table(c);      // (meshes with a second set: both tables get their pointers and spheres from the next refits)
     if (!any) return ZR_OK;
     HIPCHK(c, c->tables.alloc(&c->d_objs_b[1], c->n_objs));
@@ -203,7 +305,7 @@ int zr_instances_frame(zr_ctx* c, hipStream_t s, int par)
         return ZR_OK;
     }
     bool work = false;
-    for (const auto& o : c->objects) work |= o.pending[par] != 0 || (par == 1 && o.upd.plane[1] && !o.tab1);
+    for (const auto& o : c->objects) work |= o.pending[par] != 0 || o.flag_pending[par] || (par == 1 && o.upd.plane[1] && !o.tab1);
     const bool refit = zr_mesh_update_due(c, par);
     work |= refit;
     if (c->scatter_wait[par]) {       // the raw values and lists as the last update left them
@@ -221,6 +323,7 @@ int zr_instances_frame(zr_ctx* c, hipStream_t s, int par)
         for (auto& o : c->objects) {
             if (o.draw >= c->n_objs) return zr_fail(c, ZR_ERR_STATE, "instance update: object outside the draw table");
             if (par == 1 && o.upd.plane[1] && !o.tab1) { zr_launch_table_set_inst(c->d_objs_b[1], o.draw, o.upd.plane[1], s); o.tab1 = true; }
+            if (o.flag_pending[par]) { zr_launch_table_set_hidden(c->d_objs_b[par], o.draw, o.hidden ? 1u : 0u, s); o.flag_pending[par] = false; }
             if (o.pending[par]) {
                 zr_launch_instance_apply(o.upd, (uint32_t)par, o.pending[par], s);
                 HIPCHK(c, hipMemsetAsync(o.upd.count + par, 0, sizeof(uint32_t), s));

@@ -15,9 +15,11 @@
 
 enum { ZR_MODE_GBUFFER = 0, ZR_MODE_SHADOW = 1 };
 #define ZR_OBJ_SKY 1u                        // the skydome draw: camera pass only, unlit, written to the overlay plane
+#define ZR_OBJ_HIDDEN 2u                     // zr_object_set_visible(0): the culls reject every work item of the draw
 
 // Per-instance transform, prepared once at zr_object_add from XkInstanceData (32 B -> 64 B):
 // R = mat3(MakeRotMatrix(InstanceRotation)) column-major, t = InstancePosition, s = InstancePScale.
+// _pad[0]: all bits 0 = shown (what zr_object_add writes), anything else = hidden (k_instance_apply; the culls compare the bits).
 struct ZrInstance {
     float R[9];
     float t[3];
@@ -196,10 +198,12 @@ struct GBufferPtrs {
 // Cubemap mip chain, level l = 6 faces of (dim >> l)^2 RGBA8 sRGB texels, face-major.
 struct CubeDesc { const uint8_t* levels[16]; };
 
-// Device state of an instanced object that has been updated (zr_instances.hip): raw values, the two parity planes, per parity the list
-// of instances whose record in that plane is stale (dirty: bit p = on list p; count[p] = length of list p).
+// Device state of an instanced object that has been updated (zr_instances.hip): raw values, a visibility byte per instance (0 = hidden),
+// the two parity planes, per parity the list of instances whose record in that plane is stale (dirty: bit p = on list p; count[p] =
+// length of list p).
 struct ZrInstanceState {
     XkInstanceData* raw;
+    uint8_t* vis;
     ZrInstance* plane[2];
     uint32_t* dirty;
     uint32_t* list[2];
@@ -242,6 +246,8 @@ void zr_launch_instance_prep(const XkInstanceData* in, ZrInstance* out, uint32_t
 void zr_launch_instance_scatter(const uint32_t* idx, const XkInstanceData* data, uint32_t first, uint32_t n, const ZrInstanceState& S, hipStream_t s);
 void zr_launch_instance_apply(const ZrInstanceState& S, uint32_t par, uint32_t bound, hipStream_t s);
 void zr_launch_table_set_inst(ZrObject* tab, uint32_t draw, const ZrInstance* plane, hipStream_t s);
+void zr_launch_visibility_scatter(const uint32_t* idx, const uint8_t* visible, uint32_t first, uint32_t n, const ZrInstanceState& S, hipStream_t s);
+void zr_launch_table_set_hidden(ZrObject* tab, uint32_t draw, uint32_t hidden, hipStream_t s);
 void zr_launch_vertex_scatter(const XkVertex* src, uint32_t first, uint32_t n, const ZrMeshState& S, hipStream_t s);
 void zr_launch_mesh_refit(const ZrMeshState& S, uint32_t par, ZrObject* tab, uint32_t n_objs, hipStream_t s);
 void zr_launch_bin_count(const ZrPass& P, const uint32_t* work, const uint32_t* rects, uint32_t* tile_count, const ZrHiz& Z, const ZrDevStats* stats,

@@ -59,6 +59,7 @@ def lib():
         "zr_mesh_update_vertices_async": [vp, u32, u32, vp, u32, vp],
         "zr_mesh_get_vertices": [vp, u32, vp, C.POINTER(u32)],
         **abi.TEXTURE_UPDATE_SIGNATURES,
+        **abi.VISIBILITY_SIGNATURES,
         "zr_set_cubemap": [vp, vp, u32],
         "zr_set_skydome": [vp, vp, u32, vp, u32, vp],
         "zr_set_background": [vp, vp],
@@ -349,6 +350,47 @@ class Renderer:
         h = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
         self._chk(self.L.zr_object_update_instances_async(self.h, index, first, C.c_void_p(idx.data_ptr()) if idx is not None else None,
                                                           C.c_void_p(data.data_ptr()) if n else None, n, C.c_void_p(h) if h else None))
+
+    def object_set_visible(self, index, visible=True):
+        """Show or hide object `index` as a whole (instanced or not) from the next frame on (zr_object_set_visible); its instances'
+        own bytes stay as they are."""
+        self._chk(self.L.zr_object_set_visible(self.h, index, 1 if visible else 0))
+
+    def object_set_instance_visibility(self, index, visible, first=0):
+        """Show (nonzero) or hide (0) instances [first, first + len(visible)) of instanced object `index` from the next frame on
+        (zr_object_set_instance_visibility); frames already enqueued keep the old state."""
+        vis = np.ascontiguousarray(np.asarray(visible) != 0, dtype=np.uint8)
+        self._chk(self.L.zr_object_set_instance_visibility(self.h, index, first, _ptr(vis), vis.size))
+
+    def object_update_instance_visibility_async(self, index, visible, idx=None, first=0, stream=None, n=None):
+        """The same from device memory, in the order of `stream` (a torch.cuda.Stream or a HIP stream handle; None = the render stream):
+        visible = a contiguous CUDA tensor of n one-byte elements (uint8 or bool), idx = None (instances first .. first + n - 1) or
+        int32 [n] (the object's own indices; those >= its instance count are ignored) - or raw device pointers with `n`.  Both may be
+        overwritten by work enqueued on `stream` afterwards (zr_object_update_instance_visibility_async)."""
+        if hasattr(visible, "data_ptr"):
+            assert visible.is_cuda and visible.is_contiguous() and visible.element_size() == 1
+            n = visible.numel()
+            vptr = visible.data_ptr() if n else 0
+        else:
+            assert n is not None, "a raw device pointer needs n, the number of instances"
+            vptr = int(visible) if visible else 0
+        if idx is not None and hasattr(idx, "data_ptr"):
+            assert idx.is_cuda and idx.is_contiguous() and idx.element_size() == 4 and idx.numel() == n
+            iptr = idx.data_ptr()
+        else:
+            iptr = int(idx) if idx else 0
+        h = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        self._chk(self.L.zr_object_update_instance_visibility_async(self.h, index, first, C.c_void_p(iptr) if iptr else None,
+                                                                    C.c_void_p(vptr) if vptr else None, n, C.c_void_p(h) if h else None))
+
+    def object_get_visibility(self, index):
+        """(object visible, uint8 array of one byte per instance - None for a non-instanced draw) (zr_object_get_visibility)."""
+        n, ov = C.c_uint32(), C.c_int()
+        self._chk(self.L.zr_object_get_visibility(self.h, index, C.byref(ov), None, C.byref(n)))
+        vis = np.zeros(n.value, dtype=np.uint8)
+        if n.value:
+            self._chk(self.L.zr_object_get_visibility(self.h, index, C.byref(ov), _ptr(vis), C.byref(n)))
+        return bool(ov.value), (vis if n.value else None)
 
     def mesh_set_vertices(self, mesh, verts, first=0):
         """Replace vertices [first, first + len(verts)) of `mesh` (an abi.XkVertex array) from the next frame on (zr_mesh_set_vertices);
