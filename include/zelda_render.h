@@ -451,6 +451,67 @@ int  zr_livelink_port(zr_ctx* ctx, uint16_t* port);
 int  zr_livelink_poll(zr_ctx* ctx, int* reloaded);  /* DrawFrame's bReloadScene pickup, ZE:1943-1951 */
 int  zr_livelink_stop(zr_ctx* ctx);
 
+/* --- a world applied as a difference ("Reloading a world") ---
+ * zr_world_update_json changes only what differs from the live scene.  Afterwards everything observable - every frame byte for byte,
+ * covered_pixels / covered_shadow_texels, object order and count, zr_object_get_instances, zr_object_get_visibility (everything shown),
+ * the identities of zr_read_ids / zr_pick / zr_instance_coverage (ZR_ERR_STATE until the next frame, as after a load),
+ * zr_world_save_json, zr_world_get_camera - equals that of a NEW context of the same configuration, registered Profabs and asset root
+ * after zr_world_load_json of the same payload.  Only the time differs, and what the frame loop keeps: objects and their textures on the
+ * device, the visibility history, the work lists, the record plan and the kept shadow map.
+ *
+ * Files are taken as unchanged while their names are unchanged (the Profab cache assumes that too): an edited image under an old name
+ * needs zr_world_load_json.
+ *
+ * Matching rules.  Every object made by a world load or update remembers where it came from: Profab name, index of the model in that
+ * Profab's list, and "material as the Profab gave it" (zr_object_set_texture and zr_object_update_texture_async clear that; objects
+ * of zr_object_add have no such record and are dropped, as a load drops them).  The target list is the one a load would build: the
+ * payload's Objects in order, each Profab's models in order, instances from GenerateInstance seeded PCG32(1234 + index in Objects) -
+ * so inserting or removing an entry re-seeds the later ones, as a load does.  Each target takes the first unused live object of the
+ * same (name, model index):
+ *   - same instancing and count, host copy of the instances bit-equal and current: kept untouched;
+ *   - same count, other values (or values last written by zr_object_update_instances_async): replaced through the instance-update
+ *     path of zr_object_set_instances (objects_reinstanced);
+ *   - other count, or instanced <-> not instanced: instance buffers and update state re-made, the material's device memory stays
+ *     (objects_reinstanced);
+ *   - material no longer as the Profab gave it: rebuilt from the Profab (materials_rebuilt).
+ * Every kept object is shown again, with every instance; meshes keep what zr_mesh_set_vertices did to them, as across a load.  The
+ * objects are put in target order by moving them: no kept object's device memory is copied or freed.  Cubemap, skydome and background
+ * are re-read only if their names or flags differ or the host replaced them with zr_set_* since the world named them; one the world no
+ * longer names is dropped.  Camera and lights go the way of zr_world_update_uniforms.
+ *
+ * When nothing but camera or lights differs, scene_changed == 0: the call enqueues, frees and synchronises nothing, and the work lists,
+ * the plan, the histories and the kept shadow map stand or fall by their own keys (a payload that moves only MainCamera.Position /
+ * Lookat keeps the shadow map; FOV, zNear, zFar or the first directional light redraw it).  When objects are added, removed, resized or
+ * reordered the call synchronises, rebuilds the draw table itself and carries the visibility marks and shadow flags of the kept
+ * meshlet-instances to their new work-item numbers (history_items).
+ *
+ * Errors: ZR_ERR_STATE between the stages of a frame; ZR_ERR_PARSE, bad names (ZR_ERR_ARG) and missing files (ZR_ERR_IO) are found
+ * before anything is changed, so a refused call leaves the context as it was (Profabs read from disk on the way stay cached).  On a
+ * context that never loaded a world the update is a load. */
+typedef struct zr_world_delta {
+    uint32_t struct_bytes;       /* sizeof as the LIBRARY knows it */
+    uint32_t differs;            /* ZR_WORLD_DIFF_* bits of the payload against the live world */
+    uint32_t scene_changed;      /* 0: no object, instance, material, sky or background was touched (uniforms at most) */
+    uint32_t objects_kept;       /* live objects that stayed, device memory and all (instances bit-equal) */
+    uint32_t objects_reinstanced;/* kept material and mesh, instance values or count replaced */
+    uint32_t objects_added, objects_removed;
+    uint32_t materials_rebuilt;  /* kept objects whose material was rebuilt from the Profab (see rules) */
+    uint32_t history_items;      /* meshlet-instances whose visibility / shadow marks were carried to new numbers */
+    uint32_t reserved[3];        /* 0 */
+} zr_world_delta;
+#define ZR_WORLD_DIFF_CAMERA 1u
+#define ZR_WORLD_DIFF_LIGHTS 2u
+#define ZR_WORLD_DIFF_SKY 4u        /* skydome / cubemap names or flags */
+#define ZR_WORLD_DIFF_BACKGROUND 8u
+#define ZR_WORLD_DIFF_OBJECTS 16u
+/* out may be NULL; bytes = the caller's sizeof(zr_world_delta) (passed like zr_stats: the struct grows only at its end) */
+int  zr_world_update_json(zr_ctx* ctx, const char* utf8, size_t len, zr_world_delta* out, size_t bytes);
+int  zr_world_update_file(zr_ctx* ctx, const char* path, zr_world_delta* out, size_t bytes);   /* as zr_world_load_file */
+/* Context-free, pure host code: which parts of two payloads differ (ZR_WORLD_DIFF_* into *differs); a malformed one: ZR_ERR_PARSE. */
+int  zr_world_json_diff(const char* a, size_t len_a, const char* b, size_t len_b, uint32_t* differs);
+/* zr_livelink_poll applies payloads with the update instead of the load; default 0 = the load. */
+int  zr_livelink_set_incremental(zr_ctx* ctx, int on);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,9 @@
 //
 //   zelda_headless --root DIR [--world FILE.json] [--livelink PORT [--wait-ms MS]] [--meshlet FILE.meshlet --profab NAME]
 //                  [--size WxH] [--shadow N] [--frames N] [--roll-light-step F] [--debug-view V] [--out FRAME.ppm] [--device D]
-//                  [--pick X,Y[,W,H]]
+//                  [--pick X,Y[,W,H]] [--incremental]
+// --incremental applies livelink payloads as a difference from the live scene (zr_livelink_set_incremental): a payload that only moves
+// the camera or a light keeps every object, the visibility history and the shadow map.
 // --pick keeps the last frame's per-pixel winners (zr_set_id_capture) and prints what zr_pick finds in the rectangle (default 1 x 1),
 // one JSON line per hit, nearest first - what an editor does on a click.
 #include "../include/zelda_render.h"
@@ -33,7 +35,7 @@ int main(int argc, char** argv)
     uint32_t W = 1920, H = 1080, SD = 1024, frames = 1, debug_view = 0;
     int port = -1, wait_ms = 10000, device = 0;
     float roll_step = 0.0f;
-    bool pick = false; uint32_t px = 0, py = 0, pw = 1, ph = 1;
+    bool pick = false, incremental = false; uint32_t px = 0, py = 0, pw = 1, ph = 1;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
@@ -50,6 +52,7 @@ int main(int argc, char** argv)
         else if (a == "--wait-ms") wait_ms = atoi(next());
         else if (a == "--device") device = atoi(next());
         else if (a == "--roll-light-step") roll_step = (float)atof(next());
+        else if (a == "--incremental") incremental = true;
         else if (a == "--pick") {
             const int got = sscanf(next(), "%u,%u,%u,%u", &px, &py, &pw, &ph);
             if (got != 2 && got != 4) { fprintf(stderr, "--pick X,Y[,W,H]\n"); return 2; }
@@ -73,6 +76,7 @@ int main(int argc, char** argv)
         if ((rc = zr_world_load_file(c, world.c_str()))) return fail(c, "zr_world_load_file", rc);
         have_world = true;
     }
+    if (incremental && (rc = zr_livelink_set_incremental(c, 1))) return fail(c, "zr_livelink_set_incremental", rc);
     if (port >= 0) {
         if ((rc = zr_livelink_serve(c, (uint16_t)port))) return fail(c, "zr_livelink_serve", rc);
         uint16_t p = 0; zr_livelink_port(c, &p);

@@ -76,6 +76,16 @@ class Stats(C.Structure):
                 ("hiz_culled_geom", C.c_uint32), ("struct_bytes", C.c_uint32)]
 
 
+class WorldDelta(C.Structure):
+    """ctypes mirror of zr_world_delta: what zr_world_update_json did (passed with its size, like zr_stats)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("differs", C.c_uint32), ("scene_changed", C.c_uint32), ("objects_kept", C.c_uint32),
+                ("objects_reinstanced", C.c_uint32), ("objects_added", C.c_uint32), ("objects_removed", C.c_uint32),
+                ("materials_rebuilt", C.c_uint32), ("history_items", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+# ZR_WORLD_DIFF_*: the bits of WorldDelta.differs and of engine.world_json_diff
+WORLD_DIFF_CAMERA, WORLD_DIFF_LIGHTS, WORLD_DIFF_SKY, WORLD_DIFF_BACKGROUND, WORLD_DIFF_OBJECTS = 1, 2, 4, 8, 16
+
 ABI_VERSION = 7      # ZR_ABI_VERSION of include/zelda_render.h
 
 # object identity of the last frame (zr_read_ids / zr_pick)

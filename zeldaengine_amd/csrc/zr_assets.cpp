@@ -462,6 +462,60 @@ int zr_world_apply_overrides(zr_ctx* c, const ZrWorld& w)
     return ZR_OK;
 }
 
+// The same for zr_world_update_json, in two steps.  The plan checks every name the world gives (as the load does) and reads the files of
+// the items asked for (plan->which) into host memory; it changes nothing, so a refused update leaves the context as it was.
+int zr_world_plan_overrides(zr_ctx* c, const ZrWorld& w, ZrOverridePlan* plan)
+{
+    if (!c->assets_on) { plan->which = plan->clear = 0; return ZR_OK; }
+    if (w.OverrideCubemap) for (const std::string& n : w.CubemapFileNames) if (!zr_payload_name_ok(n)) return zr_fail(c, ZR_ERR_ARG, "[WORLD] file names in a world must be relative to the content tree: " + n);
+    if (w.OverrideSkydome && !zr_payload_name_ok(w.SkydomeFileName)) return zr_fail(c, ZR_ERR_ARG, "[WORLD] file names in a world must be relative to the content tree: " + w.SkydomeFileName);
+    if (w.OverrideBackground && !zr_payload_name_ok(w.BackgroundFileName)) return zr_fail(c, ZR_ERR_ARG, "[WORLD] file names in a world must be relative to the content tree: " + w.BackgroundFileName);
+    if (plan->which & 1u) {
+        for (int f = 0; f < 6; ++f) {
+            zr_image im;
+            if (!load_image(c, zr_asset_search(c, w.CubemapFileNames[f]), &plan->cube_px[f], &im)) return ZR_ERR_IO;
+            if (im.width != im.height || (f && im.width != plan->cube_dim)) return zr_fail(c, ZR_ERR_IO, "[WORLD] cubemap faces must be square and of one size: " + w.CubemapFileNames[f]);
+            plan->cube_dim = im.width;
+        }
+    }
+    if (plan->which & 2u) {
+        zr_image im; std::string err;
+        if (!load_image(c, zr_asset_search(c, w.SkydomeFileName), &plan->sky_px, &im)) return ZR_ERR_IO;
+        plan->sky_w = im.width; plan->sky_h = im.height;
+        if (!zr_obj_ingest(zr_asset_search(c, "Content/Models/skydome.obj"), &plan->sky_v, &plan->sky_idx, &err)) return zr_fail(c, ZR_ERR_IO, err);
+    }
+    if (plan->which & 4u) {
+        zr_image im;
+        if (!load_image(c, zr_asset_search(c, w.BackgroundFileName), &plan->bg_px, &im)) return ZR_ERR_IO;
+        plan->bg_w = im.width; plan->bg_h = im.height;
+    }
+    return ZR_OK;
+}
+
+int zr_world_commit_overrides(zr_ctx* c, ZrOverridePlan& plan)
+{
+    if (plan.which & 1u) {
+        const uint8_t* faces[6];
+        for (int f = 0; f < 6; ++f) faces[f] = plan.cube_px[f].data();
+        const int rc = zr_set_cubemap(c, faces, plan.cube_dim);
+        if (rc) return rc;
+        c->world_named[0] = true;
+    } else if (plan.clear & 1u) { const int rc = zr_set_cubemap(c, nullptr, 0); if (rc) return rc; }
+    if (plan.which & 2u) {
+        const zr_image im = { plan.sky_px.data(), plan.sky_w, plan.sky_h };
+        const int rc = zr_set_skydome(c, plan.sky_v.data(), (uint32_t)plan.sky_v.size(), plan.sky_idx.data(), (uint32_t)plan.sky_idx.size(), &im);
+        if (rc) return rc;
+        c->world_named[1] = true;
+    } else if (plan.clear & 2u) { const int rc = zr_set_skydome(c, nullptr, 0, nullptr, 0, nullptr); if (rc) return rc; }
+    if (plan.which & 4u) {
+        const zr_image im = { plan.bg_px.data(), plan.bg_w, plan.bg_h };
+        const int rc = zr_set_background(c, &im);
+        if (rc) return rc;
+        c->world_named[2] = true;
+    } else if (plan.clear & 4u) { const int rc = zr_set_background(c, nullptr); if (rc) return rc; }
+    return ZR_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ World.json on disk
 
 // XkWorld::Load() from FilePath (ZE:1057-1068; default "Content/World.json", ZE:1027)
@@ -475,6 +529,20 @@ extern "C" int zr_world_load_file(zr_ctx* c, const char* path)
         std::stringstream ss; ss << in.rdbuf();
         const std::string text = ss.str();
         return zr_world_load_json(c, text.data(), text.size());
+    });
+}
+
+// ... applied as a difference (zr_world_update_json)
+extern "C" int zr_world_update_file(zr_ctx* c, const char* path, zr_world_delta* out, size_t bytes)
+{
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        const std::string full = rooted(c, path ? path : "Content/World.json");
+        std::ifstream in(full, std::ios::binary);
+        if (!in) return zr_fail(c, ZR_ERR_IO, "[WORLD] cannot open " + full);
+        std::stringstream ss; ss << in.rdbuf();
+        const std::string text = ss.str();
+        return zr_world_update_json(c, text.data(), text.size(), out, bytes);
     });
 }
 

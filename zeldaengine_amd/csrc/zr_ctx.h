@@ -96,7 +96,9 @@ struct ZrMaterialHost {
 };
 
 struct ZrSceneObject {
-    ZrOwn mem;                           // the device memory below: instance records, raw values, update state, material images
+    ZrOwn mem;                           // the device memory below: instance records, raw values, update state
+    ZrOwn tex_mem;                       // ... and the material's images (d_tex[]): an owner of their own, so that a world update can
+                                         // re-make an object's instance buffers and keep its material where it is
     uint32_t mesh = 0, n_inst = 1; bool instanced = false;
     std::vector<XkInstanceData> inst;    // host copy (zr_object_get_instances)
     ZrInstance* d_inst = nullptr;        // the instance records: what every frame reads until an update, then the parity-0 plane
@@ -114,6 +116,13 @@ struct ZrSceneObject {
     uint8_t* d_tex[8] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };   // [7]: the packed material (ZrObject::packed)
     uint32_t tex_w[8] = { 0 }, tex_h[8] = { 0 }, tex_levels[8] = { 0 };
     bool mixed_sizes = false;            // image slots of different sizes: no packed form
+    // Where a world load or update made the object from (zr_world.cpp: the matching rules of zr_world_update_json): the Profab's name and
+    // the model's index in its list; mat_pristine = the material is still as the Profab gave it (zr_object_set_texture and
+    // zr_object_update_texture_async clear it).  Objects of zr_object_add have from_world = false.
+    std::string profab; uint32_t profab_model = 0; bool from_world = false, mat_pristine = false;
+    // The work-item numbers the frame loop's history (d_visflag, d_sflag) knows the object's meshlet-instances by: written by
+    // finalize_scene, read by the next one that carries the history (work_valid: there are some).
+    uint32_t work_base = 0, work_inst = 0, work_meshlets = 0; bool work_valid = false;
 };
 
 // XkWorld (ZE:1025-1291) as parsed from JSON
@@ -269,6 +278,14 @@ struct zr_ctx {
     // shadow pass occlusion culling (k_shadow_occlusion): the cull's box + least depth per work item, "not hidden last frame" per meshlet-instance
     uint2* d_spxrect = nullptr; float* d_szmin = nullptr; uint8_t* d_sflag = nullptr;
     bool sflag_history = false;          // the flags come from a frame of this scene (else: all set, and the first test takes every item)
+    // A world update (zr_world.cpp) that adds, removes, resizes or reorders objects asks the next finalize_scene to carry the visibility
+    // marks and the shadow flags of the kept draws to their new work-item numbers (k_history_carry) instead of forgetting them;
+    // history_items: how many meshlet-instances the last finalize_scene carried.
+    bool history_remap = false; uint64_t history_items = 0;
+    // k_shadow_occlusion tests a flagged item every fourth drawn pass, on the turn (work id + shadow_draws + sflag_turn) & 3.  A carry
+    // that moves the items' work ids by d adds -d here, so that an item keeps its turn; where the kept draws move by different amounts
+    // (mod 4), the amount most items move by.  shadow_draws itself stays what it counts.
+    uint32_t sflag_turn = 0;
     float* d_hiz = nullptr; ZrHiz hiz = {}; int vis_cur = 0; bool vis_history = false, last_two_round = false;
     uint32_t vis_mark_prev = 0;          // the stamp the resolve wrote into last frame's visibility marks (ZrHiz::vis_stamp)
     uint32_t* d_hiz_regions = nullptr; uint32_t n_hiz_regions = 0;      // the 64 x 64 pixel regions over owned tiles (k_hiz_build)
@@ -309,6 +326,10 @@ struct zr_ctx {
     // world + livelink + the content tree (zr_assets.cpp)
     std::string asset_root; bool assets_on = false;     // directory holding Profabs/ and Content/ (the engine's working directory)
     ZrWorld world;
+    // the cubemap [0], the skydome [1] and the background [2] are the ones `world` names (set by a world load or update through the
+    // content tree; cleared when the host replaces them with zr_set_cubemap / zr_set_skydome / zr_set_background)
+    bool world_named[3] = { false, false, false };
+    bool ll_incremental = false;         // zr_livelink_poll applies payloads with the update (zr_livelink_set_incremental)
     std::map<std::string, std::vector<ZrProfab>> profabs;
     std::mutex ll_mutex; std::thread ll_thread; std::atomic<bool> ll_run{ false };
     int ll_listen_fd = -1; bool ll_pending = false, ll_bind_any = false; ZrWorld ll_world; uint16_t ll_port = 0;
@@ -356,3 +377,19 @@ hipError_t zr_dist_sync(zr_ctx* c);
 std::string zr_asset_search(const zr_ctx* c, const std::string& name);
 int zr_profab_from_disk(zr_ctx* c, const std::string& name, int* found);
 int zr_world_apply_overrides(zr_ctx* c, const ZrWorld& w);
+// ... in two steps, for zr_world_update_json: everything that can be refused (names, files) is read into the plan and nothing is
+// changed; the commit sets what the plan holds.  which: bit k = re-read item k (0 cubemap, 1 skydome, 2 background), clear: bit k = the
+// world no longer names item k, drop it (the state of a context that never had it).
+struct ZrOverridePlan {
+    unsigned which = 0, clear = 0;
+    std::vector<uint8_t> cube_px[6]; uint32_t cube_dim = 0;
+    std::vector<uint8_t> sky_px; uint32_t sky_w = 0, sky_h = 0; std::vector<XkVertex> sky_v; std::vector<uint32_t> sky_idx;
+    std::vector<uint8_t> bg_px; uint32_t bg_w = 0, bg_h = 0;
+};
+int zr_world_plan_overrides(zr_ctx* c, const ZrWorld& w, ZrOverridePlan* plan);
+int zr_world_commit_overrides(zr_ctx* c, ZrOverridePlan& plan);
+// zr_host.cpp, for zr_world_update_json: an object's instance buffers / material re-made in place (the caller has synchronised), and
+// the scene finalised now instead of by the next frame
+int zr_object_remake_instances(zr_ctx* c, ZrSceneObject& o, const XkInstanceData* inst, uint32_t n_inst);
+int zr_object_remake_material(zr_ctx* c, ZrSceneObject& o, const ZrMaterialHost& mat);
+int zr_scene_finalize(zr_ctx* c);

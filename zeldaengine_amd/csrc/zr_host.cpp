@@ -505,18 +505,18 @@ static int upload_image(zr_ctx* c, ZrOwn& own, const uint8_t* rgba8, uint32_t iw
     return upload_bytes(c, own, *chain, d);
 }
 
-int zr_object_add_internal(zr_ctx* c, uint32_t mesh_id, const ZrMaterialHost& mat, const XkInstanceData* inst, uint32_t n_inst)
+// The material's images of `o`: mip chains and the packed form, into o.tex_mem (released first: a world update rebuilds a material here)
+int zr_object_remake_material(zr_ctx* c, ZrSceneObject& o, const ZrMaterialHost& mat)
 {
-    ZrSceneObject o;
-    o.mesh = mesh_id; o.instanced = n_inst > 0; o.n_inst = n_inst ? n_inst : 1;
+    o.tex_mem.release();
+    for (int t = 0; t < 8; ++t) { o.d_tex[t] = nullptr; o.tex_w[t] = o.tex_h[t] = o.tex_levels[t] = 0; }
+    o.mixed_sizes = false;
     memcpy(o.texel, mat.texel, sizeof o.texel); memcpy(o.bc_linear, mat.bc_linear, sizeof o.bc_linear);
-    if (n_inst) o.inst.assign(inst, inst + n_inst);
-    HIPCHK(c, hipSetDevice(c->device));
-    std::vector<uint8_t> chains[7];         // (a failure below drops `o`, and with it what it has made)
+    std::vector<uint8_t> chains[7];
     int lead = -1;                                          // first slot that holds an image
     for (int t = 0; t < 7; ++t) {
         if (mat.image[t].empty()) continue;
-        int rc = upload_image(c, o.mem, mat.image[t].data(), mat.w[t], mat.h[t], t == 0, &o.d_tex[t], &o.tex_w[t], &o.tex_h[t], &o.tex_levels[t], &chains[t]);
+        int rc = upload_image(c, o.tex_mem, mat.image[t].data(), mat.w[t], mat.h[t], t == 0, &o.d_tex[t], &o.tex_w[t], &o.tex_h[t], &o.tex_levels[t], &chains[t]);
         if (rc) return rc;
         if (lead < 0) lead = t;
         else if (mat.w[t] != mat.w[lead] || mat.h[t] != mat.h[lead]) o.mixed_sizes = true;
@@ -534,16 +534,40 @@ int zr_object_add_internal(zr_ctx* c, uint32_t mesh_id, const ZrMaterialHost& ma
                 for (int ch = 0; ch < k.n; ++ch)
                     pk[i * 16 + (size_t)k.ch + (size_t)ch] = image ? src[i * 4 + (size_t)ch] : (uint8_t)(mat.texel[k.slot] >> (8 * ch));
         }
-        int rc = upload_bytes(c, o.mem, pk, &o.d_tex[7]);
+        int rc = upload_bytes(c, o.tex_mem, pk, &o.d_tex[7]);
         if (rc) return rc;
         o.tex_w[7] = mat.w[lead]; o.tex_h[7] = mat.h[lead]; o.tex_levels[7] = o.tex_levels[lead];
     }
+    return ZR_OK;
+}
+
+// The instance buffers of `o` from n_inst values (0: one identity record, not instanced), into o.mem (released first, and with it the
+// update and visibility state: a world update re-makes an object of another instance count here).  Enqueued on the host's stream.
+int zr_object_remake_instances(zr_ctx* c, ZrSceneObject& o, const XkInstanceData* inst, uint32_t n_inst)
+{
+    o.mem.release();
+    o.d_inst = nullptr; o.d_raw = nullptr; o.upd = {}; o.pending[0] = o.pending[1] = 0; o.tab1 = false; o.host_stale = false;
+    o.flag_pending[0] = o.flag_pending[1] = false; o.vis_stale = false; o.vis.clear();
+    o.instanced = n_inst > 0; o.n_inst = n_inst ? n_inst : 1;
+    o.inst.clear();
+    if (n_inst) o.inst.assign(inst, inst + n_inst);
     HIPCHK(c, o.mem.alloc(&o.d_inst, o.n_inst));
     if (n_inst) {                       // (kept: the authoritative values of zr_object_set_instances / zr_object_update_instances_async)
         HIPCHK(c, o.mem.alloc(&o.d_raw, n_inst));
         HIPCHK(c, hipMemcpyAsync(o.d_raw, inst, sizeof(XkInstanceData) * n_inst, hipMemcpyHostToDevice, c->stream));
     }
     zr_launch_instance_prep(o.d_raw, o.d_inst, o.n_inst, o.instanced ? 1u : 0u, c->stream);
+    return ZR_OK;
+}
+
+int zr_object_add_internal(zr_ctx* c, uint32_t mesh_id, const ZrMaterialHost& mat, const XkInstanceData* inst, uint32_t n_inst)
+{
+    ZrSceneObject o;
+    o.mesh = mesh_id;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = zr_object_remake_material(c, o, mat);         // (a failure below drops `o`, and with it what it has made)
+    if (rc == ZR_OK) rc = zr_object_remake_instances(c, o, inst, n_inst);
+    if (rc) return rc;
     HIPCHK(c, zr_sync_all(c));
     c->objects.push_back(std::move(o));
     c->scene_dirty = true; c->scene_gen++; zr_casters_changed(c);
@@ -684,6 +708,7 @@ static int make_work_pools(zr_ctx* c, uint32_t cap_w)
     ZrOwn& P = c->pools;
     P.release();
     c->work_capacity = 0; c->plan_valid = false;
+    for (auto& o : c->objects) o.work_valid = false;      // (the history lived in the pools: finalize_scene reads it before it comes here)
     for (auto& sc : c->sc) sc = {};
     c->sb.bins = nullptr; c->sb.chunk_tab = nullptr; c->tb = {};
     c->d_pxrect = nullptr; c->d_zmin = nullptr; c->d_visflag[0] = c->d_visflag[1] = nullptr; c->d_spxrect = nullptr; c->d_szmin = nullptr; c->d_sflag = nullptr;
@@ -735,6 +760,7 @@ static int finalize_scene(zr_ctx* c)
     if (sky) { int rc = upload_mesh(c, c->sky_mesh); if (rc) return rc; }
     std::vector<ZrObject> tab;
     uint64_t work = 0, prim = 0, inst_total = 0;
+    const uint32_t old_work = c->n_work;      // (the numbering the history on the device was written in)
     auto emit = [&](ZrSceneObject& o, const ZrMesh& m, uint32_t flags) {
         ZrObject d; memset(&d, 0, sizeof d);
         o.draw = (uint32_t)tab.size();
@@ -778,19 +804,68 @@ static int finalize_scene(zr_ctx* c)
     { int rc = zr_instances_table(c); if (rc) return rc; }      // (objects with updated instances: the parity-1 table, n_objs records)
     c->sky_object = sky ? (uint32_t)tab.size() - 1u : 0u;
     if (sky && !c->d_sky_keys) HIPCHK(c, c->own.alloc(&c->d_sky_keys, (size_t)c->W * c->H));
+    // A world update asked for the history to be carried (zr_ctx::history_remap): per kept draw the old work range and the new base; where
+    // the instance count changed, the common prefix of instances.  The old planes are copied out first: ranges overlap when a base shifts
+    // by less than a draw's length, in either direction, and make_work_pools releases the planes themselves.
+    std::vector<ZrHistoryRange> ranges;
+    uint64_t carried = 0;
+    if (c->history_remap && old_work && c->d_visflag[0] && c->d_visflag[1] && c->d_sflag)
+        for (const auto& o : c->objects) {
+            const ZrObject& d = tab[o.draw];
+            if (!o.work_valid || o.work_meshlets != d.n_meshlets) continue;
+            const uint64_t count = (uint64_t)std::min(o.work_inst, d.n_inst) * d.n_meshlets;
+            if (count == 0 || (uint64_t)o.work_base + count > old_work || (uint64_t)d.work_base + count > scene_work) continue;
+            ranges.push_back({ d.work_base, o.work_base, (uint32_t)count, 0u });
+            carried += count;
+        }
+    c->history_remap = false;
+    std::sort(ranges.begin(), ranges.end(), [](const ZrHistoryRange& a, const ZrHistoryRange& b) { return a.new_base < b.new_base; });
+    ZrOwn scratch;                      // (released when this returns, after the stream has drained)
+    ZrHistoryCarry H = {};
+    if (!ranges.empty()) {
+        const size_t plane = ((size_t)old_work + 255u) & ~(size_t)255u;
+        uint8_t* old = nullptr; ZrHistoryRange* d_ranges = nullptr;
+        HIPCHK(c, scratch.alloc(&old, 3 * plane)); HIPCHK(c, upload(scratch, &d_ranges, ranges));
+        const uint8_t* from[3] = { c->d_visflag[0], c->d_visflag[1], c->d_sflag };
+        for (int k = 0; k < 3; ++k) { HIPCHK(c, hipMemcpyAsync(old + k * plane, from[k], old_work, hipMemcpyDeviceToDevice, c->stream)); H.src[k] = old + k * plane; }
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        H.ranges = d_ranges; H.n_ranges = (uint32_t)ranges.size(); H.n_old = old_work; H.n_new = c->n_work;
+    }
     if (c->n_work > c->work_capacity) { int rc = make_work_pools(c, c->n_work); if (rc) return rc; }
     c->any_images = c->mixed_images = false;
     for (const ZrObject& d : tab) for (int t = 0; t < 7; ++t) if (d.tex[t].data) c->any_images = true;
     for (const auto& o : c->objects) if (o.mixed_sizes) c->mixed_images = true;      // (the skydome's one image is sampled by itself)
-    c->vis_history = false;         // work item numbering changed: last frame's visibility says nothing about this scene
-    c->plan_valid = false;          // ... and neither do its per-tile record counts: the next frame counts before it draws (tri_raster)
-    if (c->n_work) HIPCHK(c, hipMemsetAsync(c->d_sflag, 1, c->n_work, c->stream));      // shadow pass: everything is drawn in the first launch
-    c->sflag_history = false;
+    if (H.n_ranges) {
+        // The marks and flags of the kept draws under their new numbers, stamp 0 and flag 1 everywhere else: vis_history, sflag_history,
+        // vis_mark_prev, vis_cur and shadow_draws stay as they are, and so does the plan (per tile, not per work item) unless the pools
+        // were re-made.  The camera lane reads the planes: the host waits for the carry.
+        H.dst[0] = c->d_visflag[0]; H.dst[1] = c->d_visflag[1]; H.dst[2] = c->d_sflag;
+        zr_launch_history_carry(H, c->stream);
+        uint64_t moved[4] = { 0, 0, 0, 0 };      // the shadow flags' retest turn follows the items (zr_ctx::sflag_turn)
+        for (const ZrHistoryRange& r : ranges) moved[(r.new_base - r.old_base) & 3u] += r.count;
+        uint32_t d = 0;
+        for (uint32_t k = 1; k < 4u; ++k) if (moved[k] > moved[d]) d = k;
+        c->sflag_turn = (c->sflag_turn + 4u - d) & 3u;
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else {
+        c->vis_history = false;         // work item numbering changed: last frame's visibility says nothing about this scene
+        c->plan_valid = false;          // ... and neither do its per-tile record counts: the next frame counts before it draws (tri_raster)
+        if (c->n_work) HIPCHK(c, hipMemsetAsync(c->d_sflag, 1, c->n_work, c->stream));      // shadow pass: everything is drawn in the first launch
+        c->sflag_history = false;
+    }
+    c->history_items = carried;
+    for (auto& o : c->objects) {        // the numbers the history knows the objects by from here on
+        const ZrObject& d = tab[o.draw];
+        o.work_base = d.work_base; o.work_inst = d.n_inst; o.work_meshlets = d.n_meshlets; o.work_valid = true;
+    }
     c->list_valid[0] = c->list_valid[1] = false;      // ... and neither do the passes' work lists
     zr_casters_changed(c);                            // ... nor the kept shadow map: new draw table, maybe new pools
     c->scene_dirty = false;
     return ZR_OK;
 }
+
+int zr_scene_finalize(zr_ctx* c) { return finalize_scene(c); }
 
 // ------------------------------------------------------------------------------------------------ skydome + background
 
@@ -801,6 +876,7 @@ extern "C" int zr_set_skydome(zr_ctx* c, const XkVertex* v, uint32_t nv, const u
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, zr_sync_all(c));
         c->sky_mesh = ZrMesh(); c->sky_obj = ZrSceneObject(); c->sky_set = false; c->scene_dirty = true;      // (releasing the old ones)
+        c->world_named[1] = false;
         if (!tex || !tex->rgba8) return ZR_OK;
         ARGCHK(c, v && idx && nv > 0 && ni > 0 && ni % 3 == 0);
         for (uint32_t i = 0; i < ni; ++i) if (idx[i] >= nv) return zr_fail(c, ZR_ERR_ARG, "index out of range");
@@ -825,7 +901,7 @@ extern "C" int zr_set_background(zr_ctx* c, const zr_image* tex)
     return zr_guard(c, [&]() -> int {
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, zr_sync_all(c));
-        c->bg_mem.release(); c->d_bg = nullptr; c->bg_set = false;
+        c->bg_mem.release(); c->d_bg = nullptr; c->bg_set = false; c->world_named[2] = false;
         if (!tex || !tex->rgba8) return ZR_OK;
         int rc = upload_image(c, c->bg_mem, tex->rgba8, tex->width, tex->height, true, &c->d_bg, &c->bg_w, &c->bg_h, &c->bg_levels);
         if (rc) return rc;
@@ -856,7 +932,7 @@ extern "C" int zr_set_cubemap(zr_ctx* c, const uint8_t* const faces[6], uint32_t
         if (faces) for (int f = 0; f < 6; ++f) ARGCHK(c, faces[f] != nullptr);
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, zr_sync_all(c));
-        c->cube_mem.release();
+        c->cube_mem.release(); c->world_named[0] = false;
         memset(&c->cube, 0, sizeof c->cube);
         uint32_t levels = 1; for (uint32_t d = dim; d > 1; d >>= 1) levels++;      // floor(log2(dim)) + 1, ZE:6887
         if (levels > 16) return zr_fail(c, ZR_ERR_ARG, "cubemap too large");
@@ -1333,7 +1409,7 @@ static int shadow_pass(zr_ctx* c, hipStream_t s)
     raster(c, P, s, occl ? 1 : 0);
     if (occl) {
         zr_launch_shadow_occlusion(P, c->d_objs, c->sc[0].work, c->sc[0].rects, c->d_spxrect, c->d_szmin, c->d_sflag, (const uint32_t*)shadow_buf(c),
-                                   c->sb.bins, c->d_sstats, c->shadow_blocks * 8u, c->sflag_history ? (uint32_t)(c->shadow_draws & 3u) : 4u, s);      // (a turn per pass DRAWN: kept frames test nothing)
+                                   c->sb.bins, c->d_sstats, c->shadow_blocks * 8u, c->sflag_history ? (uint32_t)((c->shadow_draws + c->sflag_turn) & 3u) : 4u, s);      // (a turn per pass DRAWN: kept frames test nothing)
         c->sflag_history = true;
         raster(c, P, s, 2);
     }

@@ -74,6 +74,7 @@ static int tex_enqueue(zr_ctx* c, ZrSceneObject& o, uint32_t slot, const void* s
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev_tex, x));
     c->tex_s = x; c->tex_wait = true;
+    o.mat_pristine = false;             // (a world update rebuilds the material from its Profab)
     return ZR_OK;
 }
 

@@ -240,6 +240,18 @@ struct ZrTexUpdate {
 };
 void zr_launch_texture_update(const ZrTexUpdate& U, const uint32_t* src, hipStream_t s);
 
+// Carrying the frame loop's per-work-item history across a renumbering (zr_world_update.hip, finalize_scene): per kept draw the bytes
+// [old_base, old_base + count) of the old numbering become [new_base, new_base + count) of the new one.  Ranges are sorted by new_base
+// and disjoint there.  src[]: copies of the old planes (both visibility planes, the shadow flags), n_old bytes each; dst[]: the live
+// planes, n_new bytes each.  What no range covers gets fill[]: stamp 0 ("no frame's stamp is 0"), shadow flag 1.
+struct ZrHistoryRange { uint32_t new_base, old_base, count, _pad; };
+struct ZrHistoryCarry {
+    const ZrHistoryRange* ranges; uint32_t n_ranges;
+    uint32_t n_old, n_new;
+    const uint8_t* src[3]; uint8_t* dst[3];
+};
+void zr_launch_history_carry(const ZrHistoryCarry& H, hipStream_t s);
+
 // launchers: each defined in the .hip of its pass (zr_cull / zr_shadow / zr_camera / zr_resolve / zr_lighting / zr_forward / zr_frame /
 // zr_instances)
 void zr_launch_instance_prep(const XkInstanceData* in, ZrInstance* out, uint32_t n, uint32_t instanced, hipStream_t s);

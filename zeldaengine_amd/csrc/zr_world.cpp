@@ -14,6 +14,7 @@
 #include <sys/socket.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -270,6 +271,12 @@ void generate_instances(const ZrObjectDesc& d, uint64_t seed, std::vector<XkInst
 
 int world_uniforms(zr_ctx* c, const ZrWorld& w, float roll_stage, float roll_light, float time);
 
+// where a world's object came from (the matching rules of zr_world_update_json, include/zelda_render.h)
+void world_tag(ZrSceneObject& o, const std::string& profab, uint32_t model)
+{
+    o.profab = profab; o.profab_model = model; o.from_world = true; o.mat_pristine = true;
+}
+
 int apply_world(zr_ctx* c, const ZrWorld& w)
 {
     // CreateEngineScene (ZE:4250-4267): drop the render objects, keep meshes and registered Profabs
@@ -294,12 +301,19 @@ int apply_world(zr_ctx* c, const ZrWorld& w)
         if (it == c->profabs.end()) continue;      // no such Profab directory: the engine finds no models and draws nothing
         std::vector<XkInstanceData> inst;
         if (d.InstanceCount > 1) generate_instances(d, 1234u + oi, inst);
-        for (const ZrProfab& pf : it->second) {
+        for (size_t mi = 0; mi < it->second.size(); ++mi) {
+            const ZrProfab& pf = it->second[mi];
             rc = zr_object_add_internal(c, pf.mesh, pf.mat, inst.empty() ? nullptr : inst.data(), (uint32_t)inst.size());
             if (rc) break;
+            world_tag(c->objects.back(), d.ProfabName, (uint32_t)mi);
         }
     }
     if (rc) return rc;
+    if (c->assets_on) {                 // (what zr_world_apply_overrides set is the world's: zr_world_update_json re-reads it only when its name changes)
+        if (w.OverrideCubemap) c->world_named[0] = true;
+        if (w.OverrideSkydome) c->world_named[1] = true;
+        if (w.OverrideBackground) c->world_named[2] = true;
+    }
     return world_uniforms(c, w, 0.0f, 0.0f, 0.0f);
 }
 
@@ -325,6 +339,216 @@ int apply_world_guarded(zr_ctx* c, const ZrWorld& w)
 {
     try { return apply_world(c, w); }
     catch (const std::bad_alloc&) { return zr_fail(c, ZR_ERR_OOM, "[WORLD] out of host memory while building the scene"); }
+    catch (const std::exception& e) { return zr_fail(c, ZR_ERR_STATE, std::string("[WORLD] ") + e.what()); }
+}
+
+// ------------------------------------------------------------------------------------------------ a world applied as a difference
+
+bool same_bits(float a, float b) { return memcmp(&a, &b, sizeof a) == 0; }
+bool same_lights(const std::vector<ZrLightDesc>& a, const std::vector<ZrLightDesc>& b)
+{
+    return a.size() == b.size() && (a.empty() || memcmp(a.data(), b.data(), a.size() * sizeof(ZrLightDesc)) == 0);
+}
+bool same_desc(const ZrObjectDesc& a, const ZrObjectDesc& b)
+{
+    return a.RenderFlags == b.RenderFlags && a.ProfabName == b.ProfabName && a.InstanceCount == b.InstanceCount &&
+           same_bits(a.MinRadius, b.MinRadius) && same_bits(a.MaxRadius, b.MaxRadius) && same_bits(a.MinRotYaw, b.MinRotYaw) &&
+           same_bits(a.MaxRotYaw, b.MaxRotYaw) && same_bits(a.MinRotRoll, b.MinRotRoll) && same_bits(a.MaxRotRoll, b.MaxRotRoll) &&
+           same_bits(a.MinRotPitch, b.MinRotPitch) && same_bits(a.MaxRotPitch, b.MaxRotPitch) && same_bits(a.MinPScale, b.MinPScale) &&
+           same_bits(a.MaxPScale, b.MaxPScale);
+}
+bool same_cube_names(const ZrWorld& a, const ZrWorld& b)
+{
+    for (int i = 0; i < 6; ++i) if (a.CubemapFileNames[i] != b.CubemapFileNames[i]) return false;
+    return true;
+}
+
+// ZR_WORLD_DIFF_*: which parts of two parsed worlds differ (values compared as the bits the parser made of them)
+uint32_t world_diff(const ZrWorld& a, const ZrWorld& b)
+{
+    uint32_t d = 0;
+    if (memcmp(&a.MainCamera, &b.MainCamera, sizeof(zr_camera)) != 0) d |= ZR_WORLD_DIFF_CAMERA;
+    if (!same_lights(a.DirectionalLights, b.DirectionalLights) || !same_lights(a.PointLights, b.PointLights) || !same_lights(a.SpotLights, b.SpotLights))
+        d |= ZR_WORLD_DIFF_LIGHTS;
+    if (a.EnableSkydome != b.EnableSkydome || a.OverrideSkydome != b.OverrideSkydome || a.SkydomeFileName != b.SkydomeFileName ||
+        a.OverrideCubemap != b.OverrideCubemap || !same_cube_names(a, b)) d |= ZR_WORLD_DIFF_SKY;
+    if (a.EnableBackground != b.EnableBackground || a.OverrideBackground != b.OverrideBackground || a.BackgroundFileName != b.BackgroundFileName)
+        d |= ZR_WORLD_DIFF_BACKGROUND;
+    bool objs = a.ObjectDescs.size() == b.ObjectDescs.size();
+    for (size_t i = 0; objs && i < a.ObjectDescs.size(); ++i) objs = same_desc(a.ObjectDescs[i], b.ObjectDescs[i]);
+    if (!objs) d |= ZR_WORLD_DIFF_OBJECTS;
+    return d;
+}
+
+// One entry of the target list (what apply_world would build) and what becomes of it: the live object it takes (-1: none, it is added)
+struct WorldTarget {
+    uint32_t desc, model; int live;
+    enum Act { Add, Keep, Reinstance, Resize } act;
+    bool rebuild_material, show;
+};
+
+// zr_world_update_json behind its parse.  Two phases: the plan reads files, resolves Profabs and matches targets with live objects and
+// changes nothing a frame can see; the commit cannot be refused any more (a device failure aside).
+int update_world(zr_ctx* c, const ZrWorld& w, zr_world_delta& D)
+{
+    D.differs = world_diff(c->world, w);
+    // ---- plan: cubemap, skydome, background - re-read only under a new name, or when the host replaced what the world had named
+    ZrOverridePlan plan;
+    if (c->assets_on) {
+        const ZrWorld& o = c->world;
+        const bool cube_same = c->world_named[0] && o.OverrideCubemap && same_cube_names(o, w);
+        const bool sky_same = c->world_named[1] && o.OverrideSkydome && o.SkydomeFileName == w.SkydomeFileName;
+        const bool bg_same = c->world_named[2] && o.OverrideBackground && o.BackgroundFileName == w.BackgroundFileName;
+        if (w.OverrideCubemap) { if (!cube_same) plan.which |= 1u; } else if (c->world_named[0]) plan.clear |= 1u;
+        if (w.OverrideSkydome) { if (!sky_same) plan.which |= 2u; } else if (c->world_named[1]) plan.clear |= 2u;
+        if (w.OverrideBackground) { if (!bg_same) plan.which |= 4u; } else if (c->world_named[2]) plan.clear |= 4u;
+    }
+    int rc = zr_world_plan_overrides(c, w, &plan);
+    if (rc) return rc;
+    // ---- plan: the target list
+    std::vector<std::vector<XkInstanceData>> inst(w.ObjectDescs.size());
+    std::vector<WorldTarget> T;
+    std::vector<char> used(c->objects.size(), 0);
+    bool any_reinstance = false, any_show = false, structural = false;
+    for (size_t oi = 0; oi < w.ObjectDescs.size(); ++oi) {
+        const ZrObjectDesc& d = w.ObjectDescs[oi];
+        auto it = c->profabs.find(d.ProfabName);
+        if (it == c->profabs.end() && c->assets_on) {          // (read into the Profab cache: nothing a frame sees)
+            int found = 0;
+            rc = zr_profab_from_disk(c, d.ProfabName, &found);
+            if (rc) return rc;
+            it = c->profabs.find(d.ProfabName);
+        }
+        if (it == c->profabs.end()) continue;
+        if (d.InstanceCount > 1) generate_instances(d, 1234u + oi, inst[oi]);
+        const uint32_t want_n = inst[oi].empty() ? 1u : (uint32_t)inst[oi].size();
+        for (size_t mi = 0; mi < it->second.size(); ++mi) {
+            WorldTarget t = { (uint32_t)oi, (uint32_t)mi, -1, WorldTarget::Add, false, false };
+            for (size_t li = 0; li < c->objects.size(); ++li) {
+                const ZrSceneObject& o = c->objects[li];
+                if (used[li] || !o.from_world || o.profab_model != mi || o.mesh != it->second[mi].mesh || o.profab != d.ProfabName) continue;
+                used[li] = 1; t.live = (int)li;
+                break;
+            }
+            if (t.live >= 0) {
+                const ZrSceneObject& o = c->objects[(size_t)t.live];
+                if (o.instanced != !inst[oi].empty() || o.n_inst != want_n) t.act = WorldTarget::Resize;
+                else if (!o.instanced || (!o.host_stale && memcmp(o.inst.data(), inst[oi].data(), sizeof(XkInstanceData) * want_n) == 0)) t.act = WorldTarget::Keep;
+                else t.act = WorldTarget::Reinstance;
+                t.rebuild_material = !o.mat_pristine;
+                t.show = o.hidden || o.vis_stale;
+                for (uint8_t v : o.vis) if (!v) t.show = true;
+            }
+            switch (t.act) {
+            case WorldTarget::Add: D.objects_added++; structural = true; break;
+            case WorldTarget::Keep: if (!t.rebuild_material) D.objects_kept++; break;
+            case WorldTarget::Reinstance: D.objects_reinstanced++; any_reinstance = true; break;
+            case WorldTarget::Resize: D.objects_reinstanced++; structural = true; break;
+            }
+            if (t.rebuild_material) { D.materials_rebuilt++; structural = true; }
+            any_show |= t.show;
+            if (t.live != (int)T.size()) structural = true;      // (the object is not where the target list wants it)
+            T.push_back(t);
+        }
+    }
+    for (char u : used) if (!u) { D.objects_removed++; structural = true; }
+    const bool flags_change = c->sky_enabled != w.EnableSkydome || c->bg_enabled != w.EnableBackground;
+    D.scene_changed = (structural || any_reinstance || any_show || plan.which || plan.clear || flags_change) ? 1u : 0u;
+
+    // ---- commit.  The identities of the last frame go with the old world, as after a load; the identity table itself stands while the
+    // objects and their order do.
+    const bool ids_table_current = c->ids_table_gen == c->scene_gen;
+    c->scene_gen++;
+    if (!structural && ids_table_current) c->ids_table_gen = c->scene_gen;
+    if (!D.scene_changed) {             // camera and lights at most: the uniforms, nothing else
+        c->world = w;
+        return world_uniforms(c, w, 0.0f, 0.0f, 0.0f);
+    }
+    // kept objects that stay the size they are: new values through the instance-update path, shown again through the visibility path
+    for (const WorldTarget& t : T) {
+        if (t.live < 0 || t.act == WorldTarget::Resize) continue;
+        ZrSceneObject& o = c->objects[(size_t)t.live];
+        if (t.act == WorldTarget::Reinstance) {
+            o.host_stale = false;       // (every value is replaced: the host copy is the payload's from here on)
+            rc = zr_object_set_instances(c, (uint32_t)t.live, 0, inst[t.desc].data(), o.n_inst);
+            if (rc) return rc;
+        }
+        if (t.show) {
+            if (o.hidden) { rc = zr_object_set_visible(c, (uint32_t)t.live, 1); if (rc) return rc; }
+            if (o.instanced && (o.vis_stale || !o.vis.empty())) {
+                const std::vector<uint8_t> ones(o.n_inst, 1);
+                rc = zr_object_set_instance_visibility(c, (uint32_t)t.live, 0, ones.data(), o.n_inst);
+                if (rc) return rc;
+                o.vis.clear(); o.vis_stale = false;
+            }
+        }
+    }
+    if (structural) {
+        // objects come, go, change size or place: behind everything in flight, and the next draw table carries the history over
+        c->scene_dirty = true; c->history_remap = true; zr_casters_changed(c);
+        if (zr_sync_all(c) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "world update: device synchronisation failed");
+        for (WorldTarget& t : T) {
+            const ZrObjectDesc& d = w.ObjectDescs[t.desc];
+            const ZrProfab& pf = c->profabs.find(d.ProfabName)->second[t.model];
+            const std::vector<XkInstanceData>& in = inst[t.desc];
+            if (t.act == WorldTarget::Add) {
+                rc = zr_object_add_internal(c, pf.mesh, pf.mat, in.empty() ? nullptr : in.data(), (uint32_t)in.size());
+                if (rc) return rc;
+                t.live = (int)c->objects.size() - 1;
+                world_tag(c->objects.back(), d.ProfabName, t.model);
+                continue;
+            }
+            ZrSceneObject& o = c->objects[(size_t)t.live];
+            if (t.act == WorldTarget::Resize) {
+                rc = zr_object_remake_instances(c, o, in.empty() ? nullptr : in.data(), (uint32_t)in.size());
+                if (rc) return rc;
+                o.hidden = false;
+            }
+            if (t.rebuild_material) {
+                rc = zr_object_remake_material(c, o, pf.mat);
+                if (rc) return rc;
+                o.mat_pristine = true;
+            }
+        }
+        if (zr_sync_all(c) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "world update: device synchronisation failed");
+        std::vector<ZrSceneObject> next;      // the target order, by moving: no kept object's device memory is copied or freed
+        next.reserve(T.size());
+        for (const WorldTarget& t : T) next.push_back(std::move(c->objects[(size_t)t.live]));
+        c->objects.swap(next);                // (what is left in `next` was removed: it releases its device memory here)
+    }
+    rc = zr_world_commit_overrides(c, plan);
+    if (rc) return rc;
+    c->world = w;
+    zr_set_sky_flags(c, w.EnableSkydome ? 1 : 0, w.EnableBackground ? 1 : 0);
+    rc = world_uniforms(c, w, 0.0f, 0.0f, 0.0f);
+    if (rc) return rc;
+    if (c->scene_dirty) {               // the draw table now, not at the next frame: the history is carried here (history_items)
+        c->history_remap = true;
+        rc = zr_scene_finalize(c);
+        if (rc) return rc;
+        D.history_items = (uint32_t)std::min<uint64_t>(c->history_items, 0xFFFFFFFFull);
+    }
+    return ZR_OK;
+}
+
+int update_world_guarded(zr_ctx* c, const ZrWorld& w, zr_world_delta& D)
+{
+    memset(&D, 0, sizeof D);
+    D.struct_bytes = (uint32_t)sizeof D;
+    if (c->stage != 0) return zr_fail(c, ZR_ERR_STATE, "zr_world_update_json between the stages of a frame (finish it with zr_render_lighting first)");
+    if (hipSetDevice(c->device) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "world update: no usable device");
+    try {
+        if (!c->world.loaded) {         // nothing to differ from: the update is a load
+            D.differs = world_diff(c->world, w); D.scene_changed = 1u;
+            if (zr_sync_all(c) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "world update: device synchronisation failed");
+            const uint32_t before = (uint32_t)c->objects.size();
+            const int rc = apply_world(c, w);
+            if (rc == ZR_OK) { D.objects_removed = before; D.objects_added = (uint32_t)c->objects.size(); }
+            return rc;
+        }
+        return update_world(c, w, D);
+    }
+    catch (const std::bad_alloc&) { return zr_fail(c, ZR_ERR_OOM, "[WORLD] out of host memory while updating the scene"); }
     catch (const std::exception& e) { return zr_fail(c, ZR_ERR_STATE, std::string("[WORLD] ") + e.what()); }
 }
 
@@ -375,6 +599,40 @@ extern "C" int zr_world_load_json(zr_ctx* c, const char* utf8, size_t len)
         (void)hipSetDevice(c->device);
         if (zr_sync_all(c) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "world load: device synchronisation failed");
         return apply_world_guarded(c, w);
+    });
+}
+
+// The world applied as a difference: the matching rules and the contract are in include/zelda_render.h.
+extern "C" int zr_world_update_json(zr_ctx* c, const char* utf8, size_t len, zr_world_delta* out, size_t bytes)
+{
+    if (!c || !utf8) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        ZrWorld w; std::string err;
+        if (!world_parse(utf8, len, w, err)) return zr_fail(c, ZR_ERR_PARSE, err);
+        zr_world_delta D;
+        const int rc = update_world_guarded(c, w, D);
+        if (out) memcpy(out, &D, std::min(bytes, sizeof D));
+        return rc;
+    });
+}
+
+extern "C" int zr_world_json_diff(const char* a, size_t len_a, const char* b, size_t len_b, uint32_t* differs)
+{
+    if (!a || !b || !differs) return ZR_ERR_ARG;
+    return zr_guard(nullptr, [&]() -> int {
+        ZrWorld wa, wb; std::string err;
+        if (!world_parse(a, len_a, wa, err) || !world_parse(b, len_b, wb, err)) return ZR_ERR_PARSE;
+        *differs = world_diff(wa, wb);
+        return ZR_OK;
+    });
+}
+
+extern "C" int zr_livelink_set_incremental(zr_ctx* c, int on)
+{
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        c->ll_incremental = on != 0;
+        return ZR_OK;
     });
 }
 
@@ -582,6 +840,12 @@ extern "C" int zr_livelink_poll(zr_ctx* c, int* reloaded)
         ZrWorld w; bool have = false;
         { std::lock_guard<std::mutex> g(c->ll_mutex); if (c->ll_pending) { w = std::move(c->ll_world); c->ll_pending = false; have = true; } }
         if (!have) return ZR_OK;
+        if (c->ll_incremental) {        // zr_livelink_set_incremental: only what differs from the live scene
+            zr_world_delta D;
+            const int rc = update_world_guarded(c, w, D);
+            if (rc == ZR_OK && reloaded) *reloaded = 1;
+            return rc;
+        }
         (void)hipSetDevice(c->device);
         if (zr_sync_all(c) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "livelink: device synchronisation failed");   // "wait all fences" on both lanes before CreateEngineScene, ZE:1943-1951
         int rc = apply_world_guarded(c, w);

@@ -122,6 +122,10 @@ def lib():
         "zr_livelink_port": [vp, C.POINTER(C.c_uint16)],
         "zr_livelink_poll": [vp, C.POINTER(C.c_int)],
         "zr_livelink_stop": [vp],
+        "zr_world_update_json": [vp, C.c_char_p, sz, C.POINTER(abi.WorldDelta), sz],
+        "zr_world_update_file": [vp, C.c_char_p, C.POINTER(abi.WorldDelta), sz],
+        "zr_world_json_diff": [C.c_char_p, sz, C.c_char_p, sz, C.POINTER(u32)],
+        "zr_livelink_set_incremental": [vp, C.c_int],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -229,6 +233,23 @@ def world_json_normalize(text):
     if rc:
         raise ZeldaRenderError(rc, out)
     return out
+
+
+def world_json_diff(a, b):
+    """Context-free: which parts of two world payloads differ, as abi.WORLD_DIFF_* bits (host code only).  A malformed payload raises
+    ZeldaRenderError(ZR_ERR_PARSE)."""
+    L = lib()
+    ba = a.encode() if isinstance(a, str) else bytes(a)
+    bb = b.encode() if isinstance(b, str) else bytes(b)
+    d = C.c_uint32()
+    rc = L.zr_world_json_diff(ba, len(ba), bb, len(bb), C.byref(d))
+    if rc:
+        raise ZeldaRenderError(rc, "zr_world_json_diff: a payload does not parse")
+    return d.value
+
+
+def _delta_dict(d):
+    return {k: getattr(d, k) for k, _ in abi.WorldDelta._fields_ if k not in ("struct_bytes", "reserved")}
 
 
 class Renderer:
@@ -699,6 +720,23 @@ class Renderer:
     def world_load_json(self, text):
         b = text.encode() if isinstance(text, str) else bytes(text)
         self._chk(self.L.zr_world_load_json(self.h, b, len(b)))
+
+    def world_update_json(self, text):
+        """zr_world_update_json: the payload applied as a difference from the live scene; returns zr_world_delta as a dict
+        (differs, scene_changed, objects_kept, objects_reinstanced, objects_added, objects_removed, materials_rebuilt, history_items)."""
+        b = text.encode() if isinstance(text, str) else bytes(text)
+        d = abi.WorldDelta()
+        self._chk(self.L.zr_world_update_json(self.h, b, len(b), C.byref(d), C.sizeof(d)))
+        return _delta_dict(d)
+
+    def world_update_file(self, path=None):
+        d = abi.WorldDelta()
+        self._chk(self.L.zr_world_update_file(self.h, os.fsencode(path) if path is not None else None, C.byref(d), C.sizeof(d)))
+        return _delta_dict(d)
+
+    def livelink_set_incremental(self, on=True):
+        """zr_livelink_poll applies payloads with zr_world_update_json instead of zr_world_load_json."""
+        self._chk(self.L.zr_livelink_set_incremental(self.h, int(bool(on))))
 
     def set_asset_root(self, path):
         """The engine's working directory (Profabs/, Content/): world loads then resolve Profabs and sky / cubemap / background files."""
