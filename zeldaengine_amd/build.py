@@ -14,9 +14,8 @@ OUT = os.path.join(HERE, "libzelda_render.so")
 KERNELS = ["zr_cull.hip", "zr_shadow.hip", "zr_camera.hip", "zr_resolve.hip", "zr_lighting.hip", "zr_forward.hip", "zr_frame.hip",
            "zr_ids.hip", "zr_instances.hip", "zr_mesh_update.hip", "zr_texture_update.hip",
            "zr_world_update.hip"]      # one per pass (+ the identity queries, the instance, vertex and texture updates, the world update's history carry)
-SOURCES = KERNELS + ["zr_host.cpp", "zr_instances_host.cpp", "zr_mesh_update_host.cpp", "zr_texture_update_host.cpp", "zr_world.cpp", "zr_meshlet.cpp", "zr_assets.cpp", "zr_dist.cpp"]
-HEADERS = ["zr_math.h", "zr_types.h", "zr_ctx.h", "zr_meshlet.h", "zr_bounds.h", "zr_srgb.h", "zr_dev.h", "zr_raster.h", "zr_texture.h", "zr_surface.h", "zr_shade.h", "zr_ids.h",
-           "../../include/zelda_abi.h", "../../include/zelda_render.h"]
+SOURCES = KERNELS + ["zr_context.cpp", "zr_scene.cpp", "zr_frame_host.cpp", "zr_readback.cpp", "zr_update.cpp", "zr_instances_host.cpp", "zr_mesh_update_host.cpp",
+                     "zr_texture_update_host.cpp", "zr_world.cpp", "zr_meshlet.cpp", "zr_assets.cpp", "zr_dist.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-D__HIP_PLATFORM_AMD__"]
 
@@ -39,7 +38,7 @@ def needs_build():
     if not os.path.exists(OUT):
         return True
     t = os.path.getmtime(OUT)
-    return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in SOURCES + HEADERS)
+    return any(os.path.getmtime(d) > t for src in SOURCES for d in _deps(os.path.join(CSRC, src)))
 
 
 def build(force=False, verbose=False, out=None, extra_flags=()):

@@ -789,7 +789,7 @@ __global__ __launch_bounds__(256) void k_sky_tiles(ZrPass P, const ZrObject* __r
     }
 }
 
-// ------------------------------------------------------------------------------------------------ launchers (C++ linkage, used by zr_host.cpp)
+// ------------------------------------------------------------------------------------------------ launchers (C++ linkage, used by zr_frame_host.cpp)
 
 void zr_launch_hiz_build(const unsigned long long* vis64, uint32_t W, uint32_t H, const ZrHiz& Z, const uint32_t* regions, uint32_t n_regions, hipStream_t s)
 {

@@ -1,7 +1,8 @@
-// zr_ctx.h — internal context shared by zr_host.cpp (renderer) and zr_world.cpp (JSON world + livelink).
+// zr_ctx.h — the internal context and the helpers that the host's translation units share ("Where the host code lives").
 #pragma once
 
 #include <atomic>
+#include <functional>
 #include <initializer_list>
 #include <map>
 #include <mutex>
@@ -73,6 +74,13 @@ static inline hipError_t zr_fill_sync(std::initializer_list<ZrFill> fills)
     return hipDeviceSynchronize();
 }
 
+template <typename T> static hipError_t upload(ZrOwn& own, T** d, const std::vector<T>& h)
+{
+    hipError_t e = own.alloc(d, h.size());
+    if (e != hipSuccess) return e;
+    return h.empty() ? hipSuccess : hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
 struct ZrMesh {
     ZrOwn mem;                           // the device buffers below (made by upload_mesh)
     std::vector<XkVertex> v;
@@ -121,9 +129,22 @@ struct ZrSceneObject {
     // zr_object_update_texture_async clear it).  Objects of zr_object_add have from_world = false.
     std::string profab; uint32_t profab_model = 0; bool from_world = false, mat_pristine = false;
     // The work-item numbers the frame loop's history (d_visflag, d_sflag) knows the object's meshlet-instances by: written by
-    // finalize_scene, read by the next one that carries the history (work_valid: there are some).
+    // zr_scene_finalize, read by the next one that carries the history (work_valid: there are some).
     uint32_t work_base = 0, work_inst = 0, work_meshlets = 0; bool work_valid = false;
 };
+
+// First byte and channel count of each material slot in the packed texel (ZR_PK_*): the scene upload packs by it, a texture update rewrites by it.
+static const struct { uint32_t ch, n; } kSlotPack[7] = { { ZR_PK_BC, 3 }, { ZR_PK_ME, 1 }, { ZR_PK_RO, 1 }, { ZR_PK_NO, 3 }, { ZR_PK_AO, 1 }, { ZR_PK_EM, 3 }, { ZR_PK_MS, 1 } };
+// A mip chain (RHIGenerateMipmaps, ZE:6348-6433): every level half the one before, never below 1; level `level` of a w x h chain and the
+// texels ahead of it (the levels lie one behind the other).
+static inline uint32_t zr_mip_next(uint32_t d) { return d > 1 ? d >> 1 : 1; }
+struct ZrMipLevel { uint32_t w, h; size_t off; };
+static inline ZrMipLevel zr_mip_level(uint32_t w, uint32_t h, uint32_t level)
+{
+    ZrMipLevel L = { w, h, 0 };
+    for (uint32_t l = 0; l < level; ++l) { L.off += (size_t)L.w * L.h; L.w = zr_mip_next(L.w); L.h = zr_mip_next(L.h); }
+    return L;
+}
 
 // XkWorld (ZE:1025-1291) as parsed from JSON
 struct ZrLightDesc { float Position[3]; uint32_t Type; float Color[3]; float Intensity; float Direction[3]; float Radius; float ExtraData[4]; };
@@ -173,22 +194,25 @@ struct zr_ctx {
     std::vector<ZrSceneObject> objects;
     bool scene_dirty = true;
     ZrObject* d_objs = nullptr; uint32_t n_objs = 0, n_work = 0;     // d_objs: the draw table of the frame enqueued last (an alias)
-    // Draw tables: [0] made by finalize_scene (every object's d_inst), [1] the parity-1 table, once an instance has been updated: it
+    // Draw tables: [0] made by zr_scene_finalize (every object's d_inst), [1] the parity-1 table, once an instance has been updated: it
     // differs only where an updated object points at its parity-1 plane.  A frame reads the table and the planes of its parity.
     ZrObject* d_objs_b[2] = { nullptr, nullptr }; ZrOwn tables;
-    // Instance updates (zr_instances_host.cpp): inst_reader[p] = 1 + the last frame that read the table / planes of parity p (0: none);
-    // ev_scatter follows the last update (on scatter_s), ev_apply the last frame-head apply (on apply_s); a pinned staging ring for the
-    // host form.  Made at the first update: a scene that never moves an instance has none of it.
-    uint64_t inst_reader[2] = { 0, 0 };
-    hipEvent_t ev_scatter = nullptr, ev_apply = nullptr; hipStream_t scatter_s = nullptr, apply_s = nullptr;
-    bool scatter_wait[2] = { false, false }, apply_done = false, inst_dual = false;      // scatter_wait[p]: the next frame of parity p waits for ev_scatter
-    static constexpr int INST_RING = 4;
-    struct InstStage { ZrOwn mem; uint8_t* h = nullptr; uint8_t* d = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; } inst_ring[INST_RING];      // cap: bytes
-    uint32_t inst_slot = 0;
-    // Texture updates (zr_texture_update_host.cpp) rewrite a slot's mip chain and the packed material IN PLACE: ev_tex follows the last
-    // one (on tex_s); an update waits for the end of the frame enqueued last, the next frame's first stream waits for ev_tex (tex_wait).
-    // d_srgb_thr: the 256 sRGB encode thresholds (zr_srgb.h).  Made at the first update.
-    hipEvent_t ev_tex = nullptr; hipStream_t tex_s = nullptr; bool tex_wait = false; float* d_srgb_thr = nullptr;
+    // What orders the between-frames updates against the frames in flight (zr_update.cpp; DESIGN.md §5, "Moving instances").
+    struct Update {
+        // Instance, visibility and vertex updates: reader[p] = 1 + the last frame that read the table / planes of parity p (0: none);
+        // ev_scatter follows the last update (on scatter_s), ev_apply the last frame-head apply (on apply_s); a pinned staging ring for the
+        // host form.  Made at the first update: a scene that never moves an instance has none of it.
+        uint64_t reader[2] = { 0, 0 };
+        hipEvent_t ev_scatter = nullptr, ev_apply = nullptr; hipStream_t scatter_s = nullptr, apply_s = nullptr;
+        bool scatter_wait[2] = { false, false }, apply_done = false, dual = false;      // scatter_wait[p]: the next frame of parity p waits for ev_scatter; dual: two draw tables exist
+        static constexpr int RING = 4;
+        struct Stage { ZrOwn mem; uint8_t* h = nullptr; uint8_t* d = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; } ring[RING];      // cap: bytes
+        uint32_t slot = 0;
+        // Texture updates (zr_texture_update_host.cpp) rewrite a slot's mip chain and the packed material IN PLACE: ev_tex follows the last
+        // one (on tex_s); an update waits for the end of the frame enqueued last, the next frame's first stream waits for ev_tex (tex_wait).
+        // d_srgb_thr: the 256 sRGB encode thresholds (zr_srgb.h).  Made at the first update.
+        hipEvent_t ev_tex = nullptr; hipStream_t tex_s = nullptr; bool tex_wait = false; float* d_srgb_thr = nullptr;
+    } upd;
     // this frame's two geometry passes (0 shadow, 1 camera), built at frame begin; the passes' work lists (k_cull_instances) are kept
     // while the pass block and the scene stand still: list_key = the block the list on the device was built from
     ZrPass pass[2]; bool pass_live[2] = { false, false }, list_reuse[2] = { false, false }, list_valid[2] = { false, false };
@@ -253,7 +277,7 @@ struct zr_ctx {
     hipStream_t gbuf_s = nullptr;        // the stream the last deferred-scene pass was enqueued on (frame_begin: a change of it is a wait)
     bool in_render = false;
     hipEvent_t ev_join = nullptr, ev_cam = nullptr;
-    // The resolve's lane (zr_host.cpp: resolve_on_host_lane): a zr_render frame that keeps its shadow map leaves its resolve to the host's
+    // The resolve's lane (zr_frame_host.cpp: resolve_on_host_lane): a zr_render frame that keeps its shadow map leaves its resolve to the host's
     // stream, ahead of its lighting pass; the camera lane marks the visibility history itself (k_mark) and goes on to the next frame.
     // resolve_deferred: the frame being enqueued does so, resolve_P / resolve_mark what its resolve is launched with.  ev_cam then sits
     // AHEAD of the lane's k_plan: plan_behind_cam says so to the next frame, which - if its camera pipeline runs on the host's stream -
@@ -278,9 +302,9 @@ struct zr_ctx {
     // shadow pass occlusion culling (k_shadow_occlusion): the cull's box + least depth per work item, "not hidden last frame" per meshlet-instance
     uint2* d_spxrect = nullptr; float* d_szmin = nullptr; uint8_t* d_sflag = nullptr;
     bool sflag_history = false;          // the flags come from a frame of this scene (else: all set, and the first test takes every item)
-    // A world update (zr_world.cpp) that adds, removes, resizes or reorders objects asks the next finalize_scene to carry the visibility
+    // A world update (zr_world.cpp) that adds, removes, resizes or reorders objects asks the next zr_scene_finalize to carry the visibility
     // marks and the shadow flags of the kept draws to their new work-item numbers (k_history_carry) instead of forgetting them;
-    // history_items: how many meshlet-instances the last finalize_scene carried.
+    // history_items: how many meshlet-instances the last zr_scene_finalize carried.
     bool history_remap = false; uint64_t history_items = 0;
     // k_shadow_occlusion tests a flagged item every fourth drawn pass, on the turn (work id + shadow_draws + sflag_turn) & 3.  A carry
     // that moves the items' work ids by d adds -d here, so that an item keeps its turn; where the kept draws move by different amounts
@@ -302,11 +326,16 @@ struct zr_ctx {
     // object identity of the last frame (zr_set_id_capture, zr_ids.hip).  The winner planes are FrameCopy::prim_plane, shared with the forward variant.
     bool id_capture = false;             // the next frames keep their winner plane (FrameCopy::G.prim set)
     bool ids_frame = false, ids_this = false;      // the frame enqueued last kept it / the frame being enqueued does
-    uint64_t scene_gen = 0, ids_gen = 0, ids_table_gen = ~0ull;      // objects added or cleared; the scene of the last frame / of the table
-    ZrOwn ids_table, ids_pool;           // d_ids_draws; the slot pools (d_ids_counts ... d_ids_hits)
-    ZrIdsDraw* d_ids_draws = nullptr; uint32_t ids_n_draws = 0, ids_n_slots = 0, ids_slot_cap = 0;
-    uint32_t *d_ids_counts = nullptr, *d_ids_cov = nullptr, *d_ids_list = nullptr, *d_ids_n = nullptr;
-    unsigned long long* d_ids_keys = nullptr; zr_hit* d_ids_hits = nullptr; uint2* d_ids_obj = nullptr;
+    uint64_t scene_gen = 0;              // objects added or cleared
+    // The queries' own state (zr_readback.cpp): gen / table_gen = the scene (scene_gen) of the last frame / of the table; table owns
+    // draws, pool the slot arrays (counts ... hits)
+    struct Ids {
+        uint64_t gen = 0, table_gen = ~0ull;
+        ZrOwn table, pool;
+        ZrIdsDraw* draws = nullptr; uint32_t n_draws = 0, n_slots = 0, slot_cap = 0;
+        uint32_t *counts = nullptr, *cov = nullptr, *list = nullptr, *n = nullptr;
+        unsigned long long* keys = nullptr; zr_hit* hits = nullptr; uint2* obj = nullptr;
+    } ids;
 
     ZrOwn cube_mem; CubeDesc cube = {}; uint32_t cube_dim = 0, cube_levels = 0;
     float lut[256]; float* d_lut = nullptr;
@@ -317,11 +346,19 @@ struct zr_ctx {
     ZrMesh sky_mesh; ZrSceneObject sky_obj; bool sky_set = false, sky_enabled = true;
     ZrOwn bg_mem; uint8_t* d_bg = nullptr; uint32_t bg_w = 0, bg_h = 0, bg_levels = 0; bool bg_set = false, bg_enabled = true;
 
-    // slots 0..9: see zr_get_pass_times_avg; 10 = end of k_mark (camera lane), 11 = start of a resolve on the host's stream
-    hipEvent_t evr[EV_RING][12] = {}; uint64_t frame_no = 0; bool rendered = false;
+    // One timed frame's events, in the order of the frame graph (zr_get_pass_times_avg reads the passes off them): frame_begin; the shadow
+    // pipeline's bins filled, its map drawn; the camera pipeline's start, its cull, round 1, Hi-Z build + k_select, round 2 + skydome; the
+    // end of k_mark (camera lane) and the start of the resolve where that runs on the host's stream; the resolve's end, the lighting's.
+    enum TimedEvent { EV_BEGIN, EV_SHADOW_BINS, EV_SHADOW, EV_CULL, EV_ROUND1, EV_HIZ, EV_ROUND2, EV_RESOLVE, EV_LIGHTING, EV_CAMERA,
+                      EV_MARK, EV_HOST_RESOLVE, EV_COUNT };
+    struct TimedFrame {
+        hipEvent_t ev[EV_COUNT] = {};
+        bool moved = false;              // the frame resolved on the host's stream: ZR_PASS_RESOLVE is k_mark's time + the resolve's
+        bool kept = false;               // the frame kept its shadow map: its shadow durations are 0, not the gap between two records
+    } timed[EV_RING];
+    uint64_t frame_no = 0; bool rendered = false;
     uint32_t timing_interval = 1; bool timing_now = true; uint64_t sample_no = 0;    // pass events every interval-th frame
-    bool ev_moved[EV_RING] = {};         // the sample's frame resolved on the host's stream: ZR_PASS_RESOLVE is k_mark's time + the resolve's
-    bool ev_kept[EV_RING] = {};          // the sample's frame kept its shadow map: its shadow durations are 0, not the gap between two records
+    TimedFrame* timed_frame() { return timing_now ? &timed[sample_no % EV_RING] : nullptr; }      // this frame's sample, or null
 
     // world + livelink + the content tree (zr_assets.cpp)
     std::string asset_root; bool assets_on = false;     // directory holding Profabs/ and Content/ (the engine's working directory)
@@ -336,26 +373,35 @@ struct zr_ctx {
 };
 
 int zr_fail(zr_ctx* c, int code, const std::string& msg);      // records the message (never throws), returns code
+// ZR_OK at stage 0, else the refusal "<what> between the stages of a frame" (hint: "... (finish it with zr_render_lighting first)")
+int zr_stage_idle(zr_ctx* c, const char* what, bool hint = true);
 // What the shadow pass would draw, or where, may have changed: the next frame draws its map (see zr_ctx::caster_epoch).  The device forms
 // of the updates call it when they enqueue: their kernels are stream-ordered ahead of the next frame.
 static inline void zr_casters_changed(zr_ctx* c) { c->caster_epoch++; }
 #define HIPCHK(c, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) \
     return zr_fail((c), ZR_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); } while (0)
 #define ARGCHK(c, cond) do { if (!(cond)) return zr_fail((c), ZR_ERR_ARG, "bad argument: " #cond); } while (0)
-// zr_instances_host.cpp
-int zr_instances_frame(zr_ctx* c, hipStream_t s, int par);       // frame head: this frame's draw table, the updates that are due
-int zr_instances_table(zr_ctx* c);                               // finalize_scene: the parity-1 table of a new draw table
-int zr_instances_sync_host(zr_ctx* c, ZrSceneObject& o);         // zr_object_get_instances after a device-form update
+// zr_update.cpp: what orders the between-frames updates against the frames in flight (zr_ctx::upd)
 int zr_update_begin(zr_ctx* c, hipStream_t x);                   // an update's scatter on x: behind the last apply / refit and the last update
 int zr_update_end(zr_ctx* c, hipStream_t x);                     // ... and the frames of both parities behind it
-int zr_update_stage(zr_ctx* c, hipStream_t x, const void* src, size_t bytes, void** dev, hipEvent_t* ev);      // the pinned staging ring
+int zr_update_tex_begin(zr_ctx* c, hipStream_t x);               // a texture update on x: behind the frame enqueued last and the last update
+int zr_update_tex_end(zr_ctx* c, hipStream_t x);                 // ... and the next frame behind it
+hipStream_t zr_update_lane(const zr_ctx* c);                     // the stream a host-form update is enqueued on
+// the host form: `bytes` of src through the pinned staging ring, enqueue(staged, lane), the slot's event behind it
+int zr_update_host_form(zr_ctx* c, const void* src, size_t bytes, const std::function<int(const void*, hipStream_t)>& enqueue);
+int zr_update_frame(zr_ctx* c, hipStream_t s, int par);          // frame head: this frame's draw table, the updates that are due
+int zr_update_table(zr_ctx* c);                                  // zr_scene_finalize: the parity-1 table of a new draw table
+void zr_drop_draw_tables(zr_ctx* c);
+hipError_t zr_update_sync(zr_ctx* c);                            // zr_sync_all: the last updates (on callers' streams)
+// zr_instances_host.cpp
+bool zr_instances_due(const zr_ctx* c, int par);                 // some object's table, flag or plane of this parity is behind
+int zr_instances_apply(zr_ctx* c, hipStream_t s, int par);       // frame head (zr_update_frame): bring them up to date
+int zr_instances_sync_host(zr_ctx* c, ZrSceneObject& o);         // zr_object_get_instances after a device-form update
 // zr_mesh_update_host.cpp
 bool zr_mesh_update_due(const zr_ctx* c, int par);               // some mesh's set of this parity is stale
-int zr_mesh_update_frame(zr_ctx* c, hipStream_t s, int par);     // frame head (zr_instances_frame): refit them, point the table at them
-bool zr_mesh_update_table(zr_ctx* c);                            // finalize_scene: new draw tables; true = the scene needs the parity-1 table
+int zr_mesh_update_frame(zr_ctx* c, hipStream_t s, int par);     // frame head (zr_update_frame): refit them, point the table at them
+bool zr_mesh_update_table(zr_ctx* c);                            // zr_scene_finalize: new draw tables; true = the scene needs the parity-1 table
 int zr_mesh_sync_host(zr_ctx* c, ZrMesh& m, bool meshlets);      // zr_mesh_get_vertices / _get_meshlets after an update
-// zr_texture_update_host.cpp
-int zr_texture_frame(zr_ctx* c, hipStream_t s);                  // frame head: s behind the last texture update
 // No exception crosses the C-ABI: every exported function that returns a status runs its body through this, behind nothing but its
 // bare argument checks (tests/test_abi_and_symbols.py holds the sources to it).
 template <typename F> static inline int zr_guard(zr_ctx* c, F&& body) noexcept
@@ -365,8 +411,19 @@ template <typename F> static inline int zr_guard(zr_ctx* c, F&& body) noexcept
     catch (const std::exception& e) { return zr_fail(c, ZR_ERR_IO, e.what()); }
     catch (...) { return zr_fail(c, ZR_ERR_IO, "unexpected exception"); }
 }
+// zr_context.cpp
 hipError_t zr_sync_all(zr_ctx* c);     // every stream the library enqueues on
-// helpers implemented in zr_host.cpp and used by zr_world.cpp
+// Tile ownership (zr_tile_owner) of a grid of tiles among `world` ranks: the tiles `rank` owns, in increasing index = its slots in the
+// packed buffer; map: tile -> owner * slots_per_rank + slot (k_untile); slots_per_rank: the most tiles any rank owns.
+struct ZrTilePartition { std::vector<uint32_t> owned, map; uint32_t slots_per_rank = 0; };
+ZrTilePartition zr_partition(uint32_t tiles_x, uint32_t tiles_y, uint32_t world, uint32_t rank);
+// zr_frame_host.cpp
+// The current shadow map: during a drawn shadow pass the one being drawn, else the one the last drawn pass left (zr_ctx::smap).
+static inline float* shadow_buf(zr_ctx* c) { return c->d_shadow_ext ? c->d_shadow_ext : c->fc[c->smap].shadow; }
+int set_winner_planes(zr_ctx* c, bool forward, bool id_capture, const char* what);      // zr_set_shading, zr_set_id_capture
+// zr_readback.cpp
+int ids_prepare(zr_ctx* c);            // frame_begin of a captured frame: the census's draw table
+// zr_scene.cpp, also used by zr_world.cpp
 float zr_srgb_decode8(uint32_t c);
 int zr_material_prepare(zr_ctx* c, const zr_material* mat, ZrMaterialHost* out);
 int zr_object_add_internal(zr_ctx* c, uint32_t mesh_id, const ZrMaterialHost& mat, const XkInstanceData* inst, uint32_t n_inst);
@@ -388,7 +445,7 @@ struct ZrOverridePlan {
 };
 int zr_world_plan_overrides(zr_ctx* c, const ZrWorld& w, ZrOverridePlan* plan);
 int zr_world_commit_overrides(zr_ctx* c, ZrOverridePlan& plan);
-// zr_host.cpp, for zr_world_update_json: an object's instance buffers / material re-made in place (the caller has synchronised), and
+// zr_scene.cpp, for zr_world_update_json: an object's instance buffers / material re-made in place (the caller has synchronised), and
 // the scene finalised now instead of by the next frame
 int zr_object_remake_instances(zr_ctx* c, ZrSceneObject& o, const XkInstanceData* inst, uint32_t n_inst);
 int zr_object_remake_material(zr_ctx* c, ZrSceneObject& o, const ZrMaterialHost& mat);

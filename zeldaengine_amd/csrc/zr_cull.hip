@@ -382,7 +382,7 @@ __global__ __launch_bounds__(256) void k_cull_box(ZrPass P, const ZrObject* __re
     }
 }
 
-// ------------------------------------------------------------------------------------------------ launchers (C++ linkage, used by zr_host.cpp)
+// ------------------------------------------------------------------------------------------------ launchers (C++ linkage, used by zr_frame_host.cpp)
 
 void zr_launch_instance_prep(const XkInstanceData* in, ZrInstance* out, uint32_t n, uint32_t instanced, hipStream_t s)
 {

@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void k_forward(ZrPass P, ZrLightParams L, cons
     else out[p] = rgba;
 }
 
-// ------------------------------------------------------------------------------------------------ launcher (C++ linkage, used by zr_host.cpp)
+// ------------------------------------------------------------------------------------------------ launcher (C++ linkage, used by zr_frame_host.cpp)
 
 void zr_launch_forward(const ZrPass& P, const ZrLightParams& L, const XkView* view, const ZrObject* objs, const uint32_t* owned_tiles, uint32_t n_owned,
                        const GBufferPtrs& G, const float* shadowmap, const CubeDesc& C, const float* lut, const float* unorm_lut, uint32_t* out, hipStream_t s)

@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void k_pack_tiles(const uint32_t* __restrict__
     }
 }
 
-// ------------------------------------------------------------------------------------------------ launchers (C++ linkage, used by zr_host.cpp)
+// ------------------------------------------------------------------------------------------------ launchers (C++ linkage, used by the host's .cpp files)
 
 void zr_launch_frame_begin(ZrDevStats* stats, const XkView* view_src_pinned, XkView* view_dst, uint32_t rebuild_lists, hipStream_t s)
 {

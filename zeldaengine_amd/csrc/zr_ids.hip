@@ -86,7 +86,7 @@ __global__ __launch_bounds__(256) void k_id_hits(ZrIdsArgs A, uint32_t n, zr_hit
     A.counts[s] = 0u; A.keys[s] = ~0ull;
 }
 
-// ------------------------------------------------------------------------------------------------ launchers (C++ linkage, used by zr_host.cpp)
+// ------------------------------------------------------------------------------------------------ launchers (C++ linkage, used by zr_readback.cpp)
 
 void zr_launch_id_census(const ZrIdsArgs& A, int mode, hipStream_t s)
 {

@@ -266,7 +266,7 @@ __global__ __launch_bounds__(256) void k_gbuffer_vis(ZrLightParams L, const XkVi
     out[(size_t)py * L.W + px] = zr_unorm(o.x, 255.0f) | zr_unorm(o.y, 255.0f) << 8 | zr_unorm(o.z, 255.0f) << 16 | 255u << 24;
 }
 
-// ------------------------------------------------------------------------------------------------ launchers (C++ linkage, used by zr_host.cpp)
+// ------------------------------------------------------------------------------------------------ launchers (C++ linkage, used by zr_frame_host.cpp)
 
 void zr_launch_lighting(const ZrLightParams& L, const XkView* view, const uint32_t* owned_tiles, uint32_t n_owned,
                         const GBufferPtrs& G, const float* shadowmap, const CubeDesc& C, const float* lut, const float* unorm_lut,

@@ -20,7 +20,7 @@ __global__ void k_vertex_scatter(const uint32_t* __restrict__ src, uint32_t* __r
     if (k < (size_t)n_verts * 11u) raw[k] = src[j];
 }
 
-// the resolve's record of one vertex: upload_mesh's statement (zr_host.cpp), bit for bit
+// the resolve's record of one vertex: upload_mesh's statement (zr_scene.cpp), bit for bit
 __device__ __forceinline__ void put_rvertex(ZrRVertex* dst, const XkVertex& x)
 {
     const zf3 n = zr_normalize(zr3(x.Normal[0], x.Normal[1], x.Normal[2]));

@@ -2,11 +2,11 @@
 // zr_mesh_update_vertices_async (caller-owned device data, in the order of the caller's stream) and zr_mesh_get_vertices.
 // Kernels: zr_mesh_update.hip.
 //
-// Ordering: the contract at the top of zr_instances_host.cpp, with the same events, tables and ring.  A frame of parity p reads the
-// draw table and the mesh set of parity p; an update writes only the raw vertices (k_vertex_scatter, bracketed by zr_update_begin /
-// zr_update_end) and marks both sets stale here on the host; set p is refitted at the head of the next frame of parity p
-// (zr_mesh_update_frame, called by zr_instances_frame behind its waits: the last scatter, the last frame that read parity p, the last
-// refit), and ev_apply follows the refit.  The vertex count, the index buffer and the meshlet partition never change.
+// Ordering: zr_update.cpp, with the same events, tables and ring as the instance updates.  A frame of parity p reads the draw table and
+// the mesh set of parity p; an update writes only the raw vertices (k_vertex_scatter, bracketed by zr_update_begin / zr_update_end) and
+// marks both sets stale here on the host; set p is refitted at the head of the next frame of parity p (zr_mesh_update_frame, called by
+// zr_update_frame behind its waits: the last scatter, the last frame that read parity p, the last refit), and ev_apply follows the
+// refit.  The vertex count, the index buffer and the meshlet partition never change.
 #include <cmath>
 #include <cstring>
 
@@ -49,14 +49,14 @@ static int mesh_init(zr_ctx* c, ZrMesh& m, hipStream_t x)
     HIPCHK(c, hipMemcpyAsync(mverts, m.ms.mverts.data(), nmv * sizeof(uint32_t), hipMemcpyHostToDevice, x));
     m.mem.adopt(std::move(mem));
     m.upd = S;
-    // every frame so far may have read set 0, the one enqueued last among them: set 0's first refit waits for it (zr_instances_frame)
-    c->inst_reader[0] = std::max<uint64_t>(c->inst_reader[0], c->frame_no);
+    // every frame so far may have read set 0, the one enqueued last among them: set 0's first refit waits for it (zr_update_frame)
+    c->upd.reader[0] = std::max<uint64_t>(c->upd.reader[0], c->frame_no);
     return ZR_OK;
 }
 
 static int mesh_range(zr_ctx* c, uint32_t mesh_id, uint32_t first, uint32_t n, const char* what, ZrMesh** out)
 {
-    if (c->stage != 0) return zr_fail(c, ZR_ERR_STATE, std::string(what) + " between the stages of a frame (finish it with zr_render_lighting first)");
+    if (int rc = zr_stage_idle(c, what)) return rc;
     if (mesh_id >= c->meshes.size()) return zr_fail(c, ZR_ERR_ARG, std::string(what) + ": bad mesh id");
     ZrMesh& m = c->meshes[mesh_id];
     if ((uint64_t)first + n > m.v.size())
@@ -103,13 +103,10 @@ extern "C" int zr_mesh_set_vertices(zr_ctx* c, uint32_t mesh_id, uint32_t first,
             return ZR_OK;
         }
         HIPCHK(c, hipSetDevice(c->device));
-        hipStream_t x = c->cam_s ? c->cam_s : c->stream;      // the camera lane, as zr_object_set_instances
-        void* staged = nullptr; hipEvent_t ev = nullptr;
-        rc = zr_update_stage(c, x, v, (size_t)n * sizeof(XkVertex), &staged, &ev);
+        rc = zr_update_host_form(c, v, (size_t)n * sizeof(XkVertex), [&](const void* staged, hipStream_t x) {
+            return mesh_enqueue(c, *m, x, (const XkVertex*)staged, first, n);
+        });
         if (rc) return rc;
-        rc = mesh_enqueue(c, *m, x, (const XkVertex*)staged, first, n);
-        if (rc) return rc;
-        HIPCHK(c, hipEventRecord(ev, x));
         if (!m->v_stale) memcpy(m->v.data() + first, v, (size_t)n * sizeof(XkVertex));      // (else the read-back brings it)
         return ZR_OK;
     });
@@ -157,14 +154,14 @@ int zr_mesh_sync_host(zr_ctx* c, ZrMesh& m, bool meshlets)
     if (!m.upd.raw || (!m.v_stale && !(meshlets && m.ml_stale))) return ZR_OK;
     HIPCHK(c, hipSetDevice(c->device));
     if (m.v_stale) {
-        if (c->ev_scatter) HIPCHK(c, hipEventSynchronize(c->ev_scatter));      // the last update has landed in the raw values
+        if (c->upd.ev_scatter) HIPCHK(c, hipEventSynchronize(c->upd.ev_scatter));      // the last update has landed in the raw values
         HIPCHK(c, hipMemcpy(m.v.data(), m.upd.raw, m.v.size() * sizeof(XkVertex), hipMemcpyDeviceToHost));
         m.v_stale = false;
     }
     if (meshlets && m.ml_stale) {
         const int p = !m.stale[0] ? 0 : !m.stale[1] ? 1 : -1;
         if (p >= 0) {
-            if (c->ev_apply) HIPCHK(c, hipEventSynchronize(c->ev_apply));      // (ev_apply covers every refit)
+            if (c->upd.ev_apply) HIPCHK(c, hipEventSynchronize(c->upd.ev_apply));      // (ev_apply covers every refit)
             HIPCHK(c, hipMemcpy(m.ms.meshlets.data(), m.upd.set[p].meshlets, m.ms.meshlets.size() * sizeof(XkMeshlet), hipMemcpyDeviceToHost));
             m.ml_stale = false;
         } else host_bounds(m);      // (ml_stale stays: once a frame has refitted a set, the next read-back takes the device's records)
@@ -178,7 +175,7 @@ bool zr_mesh_update_due(const zr_ctx* c, int par)
     return false;
 }
 
-// zr_instances_frame on stream s, behind its waits: set `par` of every stale mesh from the raw vertices, the table of this parity at it
+// zr_update_frame on stream s, behind its waits: set `par` of every stale mesh from the raw vertices, the table of this parity at it
 int zr_mesh_update_frame(zr_ctx* c, hipStream_t s, int par)
 {
     for (auto& m : c->meshes) {
@@ -189,7 +186,7 @@ int zr_mesh_update_frame(zr_ctx* c, hipStream_t s, int par)
     return ZR_OK;
 }
 
-// finalize_scene made table 0 from set 0 and the host's spheres (zr_instances_table copies it to table 1): the next refit of each parity
+// zr_scene_finalize made table 0 from set 0 and the host's spheres (zr_update_table copies it to table 1): the next refit of each parity
 // writes this parity's pointers and the current sphere into them.  Nothing is in flight.
 bool zr_mesh_update_table(zr_ctx* c)
 {

@@ -1,7 +1,7 @@
 // zr_resolve.hip — k_resolve_gbuffer: BaseScene.frag per pixel from the frame's key buffer into the SoA GBuffer planes (28 B / px,
 // formats ZE:2807-2843), coalesced row stores; marks the meshlet-instances that own a pixel (next frame's round 1) - unless k_mark
 // did that ahead of it: the history is all the next frame's camera lane needs of the resolve, and a frame whose resolve runs on the
-// other lane (zr_host.cpp: gbuffer_pass) takes it from the keys alone.
+// other lane (zr_frame_host.cpp: gbuffer_pass) takes it from the keys alone.
 #include "zr_dev.h"
 #include "zr_surface.h"
 
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void k_mark(ZrPass P, const ZrObject* __restri
     if (mi != 0xFFFFFFFFu && mi != left) vis_now[mi] = (uint8_t)vis_mark;
 }
 
-// ------------------------------------------------------------------------------------------------ launchers (C++ linkage, used by zr_host.cpp)
+// ------------------------------------------------------------------------------------------------ launchers (C++ linkage, used by zr_frame_host.cpp)
 
 void zr_launch_mark(const ZrPass& P, const ZrObject* objs, const uint32_t* owned_tiles, uint32_t n_owned, const unsigned long long* vis64,
                     uint8_t* vis_now, hipStream_t s, uint32_t vis_mark)

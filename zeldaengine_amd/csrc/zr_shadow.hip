@@ -470,7 +470,7 @@ __global__ void k_count_shadow(const uint32_t* __restrict__ bits, size_t n, ZrDe
     if ((threadIdx.x & 63u) == 0 && c) atomicAdd(&stats->covered_shadow, c);
 }
 
-// ------------------------------------------------------------------------------------------------ launchers (C++ linkage, used by zr_host.cpp)
+// ------------------------------------------------------------------------------------------------ launchers (C++ linkage, used by zr_frame_host.cpp)
 
 void zr_launch_bin_count(const ZrPass& P, const uint32_t* work, const uint32_t* rects, uint32_t* tile_count, const ZrHiz& Z, const ZrDevStats* stats,
                          hipStream_t s)

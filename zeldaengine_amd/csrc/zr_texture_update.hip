@@ -5,7 +5,7 @@
 //   k_tex_level0   a lane per texel: the new image into level 0
 //   k_tex_mip      a lane per destination texel: level l from level l - 1 (four 32-bit loads, one 32-bit store)
 //   k_tex_tail     one workgroup: from the first level of at most 64 x 64 texels on, every remaining level through LDS
-// The statement is build_mip_chain (zr_host.cpp), byte for byte: the same fmaf sequence and clamped indices; decode through the two
+// The statement is build_mip_chain (zr_scene.cpp), byte for byte: the same fmaf sequence and clamped indices; decode through the two
 // 256-entry tables the resolve uses; the linear encode is zr_unorm, the sRGB encode a search of the host's own thresholds (zr_srgb.h) -
 // no pow and no division on the device (the levels' steps come as the host's quotients).  Ordering against frames: the host file.
 #include "zr_dev.h"

@@ -240,7 +240,7 @@ struct ZrTexUpdate {
 };
 void zr_launch_texture_update(const ZrTexUpdate& U, const uint32_t* src, hipStream_t s);
 
-// Carrying the frame loop's per-work-item history across a renumbering (zr_world_update.hip, finalize_scene): per kept draw the bytes
+// Carrying the frame loop's per-work-item history across a renumbering (zr_world_update.hip, zr_scene_finalize): per kept draw the bytes
 // [old_base, old_base + count) of the old numbering become [new_base, new_base + count) of the new one.  Ranges are sorted by new_base
 // and disjoint there.  src[]: copies of the old planes (both visibility planes, the shadow flags), n_old bytes each; dst[]: the live
 // planes, n_new bytes each.  What no range covers gets fill[]: stamp 0 ("no frame's stamp is 0"), shadow flag 1.

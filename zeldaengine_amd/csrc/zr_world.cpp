@@ -457,9 +457,9 @@ int update_world(zr_ctx* c, const ZrWorld& w, zr_world_delta& D)
 
     // ---- commit.  The identities of the last frame go with the old world, as after a load; the identity table itself stands while the
     // objects and their order do.
-    const bool ids_table_current = c->ids_table_gen == c->scene_gen;
+    const bool ids_table_current = c->ids.table_gen == c->scene_gen;
     c->scene_gen++;
-    if (!structural && ids_table_current) c->ids_table_gen = c->scene_gen;
+    if (!structural && ids_table_current) c->ids.table_gen = c->scene_gen;
     if (!D.scene_changed) {             // camera and lights at most: the uniforms, nothing else
         c->world = w;
         return world_uniforms(c, w, 0.0f, 0.0f, 0.0f);
@@ -535,7 +535,7 @@ int update_world_guarded(zr_ctx* c, const ZrWorld& w, zr_world_delta& D)
 {
     memset(&D, 0, sizeof D);
     D.struct_bytes = (uint32_t)sizeof D;
-    if (c->stage != 0) return zr_fail(c, ZR_ERR_STATE, "zr_world_update_json between the stages of a frame (finish it with zr_render_lighting first)");
+    if (int rc = zr_stage_idle(c, "zr_world_update_json")) return rc;
     if (hipSetDevice(c->device) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, "world update: no usable device");
     try {
         if (!c->world.loaded) {         // nothing to differ from: the update is a load

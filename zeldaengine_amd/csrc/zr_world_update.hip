@@ -3,7 +3,7 @@
 // A work item is work_base + instance * n_meshlets + meshlet.  When a world update adds, removes, resizes or reorders objects the kept
 // draws get new bases; what the frame loop had learnt about their meshlet-instances - one byte each in the two visibility planes
 // (d_visflag: the stamp of the frame that saw it win a pixel) and in the shadow flags (d_sflag: not hidden in the map drawn last) - is
-// moved to the new numbers instead of being forgotten.  finalize_scene copies the old planes out first (ranges overlap when a base shifts
+// moved to the new numbers instead of being forgotten.  zr_scene_finalize copies the old planes out first (ranges overlap when a base shifts
 // by less than a draw's length, in either direction; a scene that outgrew its pools gets new planes altogether), so k_history_carry is a
 // gather from those copies into the live planes: one lane per 4 output bytes, a whole dword at a time where source and destination are
 // aligned alike inside one range, byte by byte where they are not.  Bytes no range covers get stamp 0 ("no frame's stamp is 0": not seen,
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void k_history_carry(ZrHistoryCarry H)
     }
 }
 
-// (a table of no ranges launches nothing: finalize_scene then forgets the history, as it does without a remap)
+// (a table of no ranges launches nothing: zr_scene_finalize then forgets the history, as it does without a remap)
 void zr_launch_history_carry(const ZrHistoryCarry& H, hipStream_t s)
 {
     if (H.n_ranges == 0 || H.n_new == 0) return;
