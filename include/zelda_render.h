@@ -282,7 +282,15 @@ int  zr_set_shading(zr_ctx* ctx, uint32_t mode);
  * map bit for bit.  The pass's statistics (zr_get_stats slot 0, shadow_occluded, shadow_late) then stay those of the last drawn pass, its
  * pass times read exactly 0, and zr_read_shadowmap / zr_copy_frame_async return the kept map.  Every entry point (zr_render, the staged
  * calls, zr_render_geometry) decides alike.  Drawn every frame: a tile- or instance-partitioned map, a caller-owned one
- * (zr_set_shadow_buffer), contexts with ZR_FLAG_NO_LIST_REUSE or ZR_FLAG_SHADOW_OCCLUSION. */
+ * (zr_set_shadow_buffer), contexts with ZR_FLAG_NO_LIST_REUSE or ZR_FLAG_SHADOW_OCCLUSION.
+ * Round 2 of the camera pass is kept likewise while the camera pass's matrices (camera, stage) and what it draws (objects, instances,
+ * vertices, meshlets, visibility, limits, bucket share, skydome) stand still: from the third frame of such a rest on, a frame draws
+ * round 1 - what owned a pixel of the frame before, which is all that can own one now - and enqueues no Hi-Z build and no second
+ * round; the GBuffer is the same bit for bit.  Its statistics (survivors, hiz_culled, hiz_culled_geom, bin_entries) stay those of the last
+ * drawn round 2, ZR_PASS_HIZ and ZR_PASS_GBUFFER2 read exactly 0.  Every entry point decides alike; never kept: contexts with
+ * ZR_FLAG_NO_LIST_REUSE (and ZR_FLAG_NO_HIZ has no second round to keep).  A frame that ran out of record room (ZR_ERR_OVERFLOW from
+ * zr_finish) is incomplete, and so is every frame of the rest that keeps round 2 behind it - each reports the overflow again - until
+ * zr_finish has reported it: the frame after that draws both rounds again. */
 int  zr_render(zr_ctx* ctx);
 /* The same frame in three stages (zr_render = all three, in this order), so that a multi-GPU host can place its
  * collectives between them: shadow pass | deferred-scene pass (cull, raster, GBuffer write) | deferred-lighting pass. */

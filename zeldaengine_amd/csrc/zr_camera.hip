@@ -472,9 +472,13 @@ void k_geom(ZrPass P, const ZrBinEntry* __restrict__ sel, ZrHiz Z, ZrTriBins B, 
 // whatever its tile's cursor says).  Also what used to be k_tile's first duty: the cursors are zero again for the next frame.
 // ONE workgroup, after the resolve: the camera lane has nothing to do until the next frame begins, nothing waits for this launch.
 // `exact`: the counts come from a count-only run of the very round that follows - the buckets are the counts themselves, nothing can spill.
+// `round2` (ZR_PLAN_*): a frame that drew both rounds leaves round 2's per-tile counts and its words of the statistics block in
+// B.r2_count / B.r2_stats; a frame that kept round 2 - its round-2 cursors are zero, k_frame_begin zeroed the statistics - plans with
+// those counts and reports those words: the plan is no tighter and the statistics are no other than after the round as last drawn.
 __global__ __launch_bounds__(1024) void k_plan(ZrTriBins B, const uint32_t* __restrict__ owned_tiles, uint32_t n_owned, uint32_t unit, ZrDevStats* __restrict__ stats,
-                                               uint32_t exact, uint32_t bucket_pct)
+                                               uint32_t exact, uint32_t bucket_pct, uint32_t round2)
 {
+    const bool kept = round2 == ZR_PLAN_KEPT_ROUND2;
     __shared__ uint32_t wtot[16], cwtot[16];
     __shared__ unsigned long long gsum[16];
     __shared__ uint32_t nsum[16][2];
@@ -486,7 +490,7 @@ __global__ __launch_bounds__(1024) void k_plan(ZrTriBins B, const uint32_t* __re
     unsigned long long want = 0;
     uint32_t n0 = 0, n1 = 0;
     for (uint32_t j = b; j < e; ++j) {
-        const uint32_t t = owned_tiles[j], a0 = c0[t * ZR_TSTRIDE], a1 = c1[t * ZR_TSTRIDE], c = max(a0, a1);
+        const uint32_t t = owned_tiles[j], a0 = c0[t * ZR_TSTRIDE], a1 = kept ? B.r2_count[t] : c1[t * ZR_TSTRIDE], c = max(a0, a1);
         want += exact ? (unsigned long long)c : (unsigned long long)c + (c >> 2) + ZR_BUCKET_SLACK;
         n0 += a0; n1 += a1;
     }
@@ -503,13 +507,23 @@ __global__ __launch_bounds__(1024) void k_plan(ZrTriBins B, const uint32_t* __re
         for (uint32_t i = 0; i < 16u; ++i) { r0 += nsum[i][0]; r1 += nsum[i][1]; }
         for (uint32_t i = 0; i < ZR_OVER_SECTIONS; ++i) { o0 += B.over_cursor[i]; o1 += B.over_cursor[ZR_OVER_SECTIONS + i]; }
         stats->bin_entries[1] = r0; stats->bin_entries[2] = r1;
-        stats->pool_used[1] = o0; stats->pool_used[2] = o1;      // (pool_used: the rounds' overflow records)
+        stats->pool_used[1] = o0; stats->pool_used[2] = o1;      // (pool_used: the rounds' overflow records; a kept round 2 spilled nothing)
+        if (round2 == ZR_PLAN_DREW_ROUND2) {
+            B.r2_stats[0] = stats->survivors[2]; B.r2_stats[1] = stats->hiz_culled; B.r2_stats[2] = stats->hiz_culled_geom;
+            B.r2_stats[3] = stats->n_sel[2]; B.r2_stats[4] = stats->n_slow[2]; B.r2_stats[5] = stats->n_chunks[2];
+            B.r2_stats[6] = stats->overflow; B.r2_stats[7] = stats->overflow_sticky;
+        } else if (kept) {
+            stats->survivors[2] = B.r2_stats[0]; stats->hiz_culled = B.r2_stats[1]; stats->hiz_culled_geom = B.r2_stats[2];
+            stats->n_sel[2] = B.r2_stats[3]; stats->n_slow[2] = B.r2_stats[4]; stats->n_chunks[2] = B.r2_stats[5];
+            // (the frame whose round 2 ran full was incomplete, and so is every frame that stands on its key buffer)
+            if (B.r2_stats[6]) { stats->overflow = 1u; stats->overflow_sticky = B.r2_stats[7]; }
+        }
     }
     const bool shrink = all > (unsigned long long)B.bucket_max;
     // pass 2: buckets and units (one scan of each)
     uint32_t s = 0, cs = 0;
     for (uint32_t j = b; j < e; ++j) {
-        const uint32_t t = owned_tiles[j], c = max(c0[t * ZR_TSTRIDE], c1[t * ZR_TSTRIDE]);
+        const uint32_t t = owned_tiles[j], c = max(c0[t * ZR_TSTRIDE], kept ? B.r2_count[t] : c1[t * ZR_TSTRIDE]);
         unsigned long long cap = exact ? (unsigned long long)c : (unsigned long long)c + (c >> 2) + ZR_BUCKET_SLACK;
         if (shrink) cap = cap * B.bucket_max / all;
         if (bucket_pct != 100u) cap = cap * bucket_pct / 100u;      // (zr_set_bucket_share)
@@ -526,7 +540,7 @@ __global__ __launch_bounds__(1024) void k_plan(ZrTriBins B, const uint32_t* __re
     for (uint32_t i = 0; i < 16u; ++i) { if (i < wv) { wpre += wtot[i]; cwpre += cwtot[i]; } ctot += cwtot[i]; rtot += wtot[i]; }
     uint32_t run = wpre + incl - s, crun = cwpre + cincl - cs;
     for (uint32_t j = b; j < e; ++j) {
-        const uint32_t t = owned_tiles[j], c = max(c0[t * ZR_TSTRIDE], c1[t * ZR_TSTRIDE]);
+        const uint32_t t = owned_tiles[j], c = max(c0[t * ZR_TSTRIDE], kept ? B.r2_count[t] : c1[t * ZR_TSTRIDE]);
         unsigned long long cap = exact ? (unsigned long long)c : (unsigned long long)c + (c >> 2) + ZR_BUCKET_SLACK;
         if (shrink) cap = cap * B.bucket_max / all;
         if (bucket_pct != 100u) cap = cap * bucket_pct / 100u;      // (zr_set_bucket_share)
@@ -535,6 +549,7 @@ __global__ __launch_bounds__(1024) void k_plan(ZrTriBins B, const uint32_t* __re
         for (uint32_t k = 0; k < nu; ++k)
             if (crun + k < B.unit_cap) B.unit_tab[crun + k] = make_uint4(t, k, nu, 0u);
         run += (uint32_t)cap; crun += nu;
+        if (round2 == ZR_PLAN_DREW_ROUND2) B.r2_count[t] = c1[t * ZR_TSTRIDE];
         c0[t * ZR_TSTRIDE] = 0u; c1[t * ZR_TSTRIDE] = 0u;
     }
     if (tid == 0) {
@@ -810,9 +825,10 @@ void zr_launch_geom(const ZrPass& P, const ZrHiz& Z, const ZrTriBins& B, ZrDevSt
     } else if (Z.phase == 2u) hipLaunchKernelGGL((k_geom<true, false>), g, b, 0, s, P, B.sel, Z, B, stats, slot);
     else hipLaunchKernelGGL((k_geom<false, false>), g, b, 0, s, P, B.sel, Z, B, stats, slot);
 }
-void zr_launch_plan(const ZrTriBins& B, const uint32_t* owned_tiles, uint32_t n_owned, ZrDevStats* stats, bool exact, uint32_t bucket_pct, hipStream_t s)
+void zr_launch_plan(const ZrTriBins& B, const uint32_t* owned_tiles, uint32_t n_owned, ZrDevStats* stats, bool exact, uint32_t bucket_pct, hipStream_t s,
+                    uint32_t round2)
 {
-    hipLaunchKernelGGL(k_plan, dim3(1), dim3(1024), 0, s, B, owned_tiles, n_owned, ZR_TCHUNK * ZR_TBATCHES, stats, exact ? 1u : 0u, bucket_pct);
+    hipLaunchKernelGGL(k_plan, dim3(1), dim3(1024), 0, s, B, owned_tiles, n_owned, ZR_TCHUNK * ZR_TBATCHES, stats, exact ? 1u : 0u, bucket_pct, round2);
 }
 void zr_launch_tile(const ZrPass& P, const ZrTriBins& B, ZrDevStats* stats, int slot, unsigned long long* vis64, uint32_t n_blocks, hipStream_t s, bool last,
                     const uint32_t* owned_tiles, uint32_t n_owned)

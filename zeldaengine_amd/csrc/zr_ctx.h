@@ -226,6 +226,21 @@ struct zr_ctx {
     uint64_t caster_epoch = 0, smap_epoch = 0, shadow_draws = 0;
     int smap = 0; bool smap_valid = false, shadow_keep = false;
     ZrPass smap_key;
+    // Round 2 of the camera pass is kept the same way (zr_frame_host.cpp: camera_keepable, gbuffer_pass).  Round 1 draws the
+    // meshlet-instances that owned a pixel of the previous frame's final key buffer; when this frame's camera-pass inputs are that
+    // frame's bit for bit, whatever owned no pixel then owns none now: the key buffer behind round 1 is already the frame's, and the
+    // frame enqueues no Hi-Z build, no k_select and no second round.  camera_epoch: bumped (zr_camera_changed, and with every
+    // zr_casters_changed: a caster is drawn by the camera too) by every call that can change what the camera pass draws, its work
+    // numbering or its record layout.  cam_prev_key / cam_prev_epoch: the camera block and the epoch of the frame enqueued last
+    // (cam_prev_valid: it left a visibility history); cam_same: this frame's are the same (frame_begin; frame_cam_epoch: the epoch it
+    // began at).  r2_settled: the frame enqueued last drew both rounds or kept round 2 AND was itself cam_same, so the history its
+    // round 1 went by was the standing view's own - only then are round 2's statistics and per-tile counts, which a keeping frame
+    // reports and plans with, those a drawn round 2 would give now (the frame after a camera cut draws round 2 from a stale history: tens
+    // of millions of records at config 4 where the settled frame has a few; the frame after it draws both rounds once more, and the
+    // rest of the rest keeps).  round2_keep: this frame may keep (gbuffer_pass also wants a two-round frame with a usable plan).
+    uint64_t camera_epoch = 0, cam_prev_epoch = 0, frame_cam_epoch = 0;
+    bool cam_prev_valid = false, cam_same = false, r2_settled = false, round2_keep = false;
+    ZrPass cam_prev_key;
 
     XkUniformBufferMVP cam, shadow; XkView view; bool frame_valid = false;
     uint32_t debug_view = 0;
@@ -355,6 +370,7 @@ struct zr_ctx {
         hipEvent_t ev[EV_COUNT] = {};
         bool moved = false;              // the frame resolved on the host's stream: ZR_PASS_RESOLVE is k_mark's time + the resolve's
         bool kept = false;               // the frame kept its shadow map: its shadow durations are 0, not the gap between two records
+        bool kept_round2 = false;        // the frame kept round 2 of the camera pass: ZR_PASS_HIZ and ZR_PASS_GBUFFER2 are 0 likewise
     } timed[EV_RING];
     uint64_t frame_no = 0; bool rendered = false;
     uint32_t timing_interval = 1; bool timing_now = true; uint64_t sample_no = 0;    // pass events every interval-th frame
@@ -377,7 +393,10 @@ int zr_fail(zr_ctx* c, int code, const std::string& msg);      // records the me
 int zr_stage_idle(zr_ctx* c, const char* what, bool hint = true);
 // What the shadow pass would draw, or where, may have changed: the next frame draws its map (see zr_ctx::caster_epoch).  The device forms
 // of the updates call it when they enqueue: their kernels are stream-ordered ahead of the next frame.
-static inline void zr_casters_changed(zr_ctx* c) { c->caster_epoch++; }
+static inline void zr_casters_changed(zr_ctx* c) { c->caster_epoch++; c->camera_epoch++; }
+// What the camera pass draws, how its work items are numbered or where its records go may have changed, the casters apart: the next
+// frame draws round 2 (see zr_ctx::camera_epoch).
+static inline void zr_camera_changed(zr_ctx* c) { c->camera_epoch++; }
 #define HIPCHK(c, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) \
     return zr_fail((c), ZR_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); } while (0)
 #define ARGCHK(c, cond) do { if (!(cond)) return zr_fail((c), ZR_ERR_ARG, "bad argument: " #cond); } while (0)

@@ -252,6 +252,13 @@ static inline bool shadow_keepable(const zr_ctx* c)
            !(c->cfg.flags & (ZR_FLAG_NO_LIST_REUSE | ZR_FLAG_SHADOW_OCCLUSION));
 }
 
+// Contexts that never keep round 2 of the camera pass (every two-round frame draws it): ZR_FLAG_NO_LIST_REUSE, as above.  A rank of a
+// tile-partitioned frame keeps it like any other context: the statement is per pixel, and a rank's key buffer holds its own tiles only.
+static inline bool camera_keepable(const zr_ctx* c)
+{
+    return !(c->cfg.flags & ZR_FLAG_NO_LIST_REUSE);
+}
+
 // count -> scan -> fill of the shadow pass's meshlet bins, from the cull's rects.  Z.phase 1 (occlusion culling): only the
 // meshlet-instances flagged last frame are binned.
 static void shadow_bin(zr_ctx* c, const ZrPass& P, const ZrHiz& Z, hipStream_t s)
@@ -350,6 +357,11 @@ static int frame_begin(zr_ctx* c, hipStream_t s)
     }
     // ... and the shadow pass's map as a whole while, beyond that, no caster changed and the map stays where it is (shadow_pass)
     c->shadow_keep = shadow_keepable(c) && c->smap_valid && c->smap_epoch == c->caster_epoch && memcmp(&c->smap_key, &c->pass[0], sizeof(ZrPass)) == 0;
+    // ... and round 2 of the camera pass while the frame enqueued last drew or kept it from this very block, on a history of this very
+    // block, and nothing the pass draws changed since (gbuffer_pass)
+    c->frame_cam_epoch = c->camera_epoch;
+    c->cam_same = c->cam_prev_valid && c->cam_prev_epoch == c->camera_epoch && memcmp(&c->cam_prev_key, &c->pass[1], sizeof(ZrPass)) == 0;
+    c->round2_keep = camera_keepable(c) && c->cam_same && c->r2_settled;
     const XkView* src = nullptr;
     uint32_t k = 0;
     if (F.view_uploaded != c->view_version) {        // pinned ring slot: reused only after the kernel that read it last has run
@@ -441,6 +453,7 @@ static int gbuffer_pass(zr_ctx* c, hipStream_t s, bool defer_resolve = false)
     ZrPass P = c->pass[1];             // (built by frame_begin; the overlay fields are set below)
     c->gbuf_s = s;
     c->last_work[1] = P.n_work;
+    c->r2_settled = c->cam_prev_valid = false;      // (until the whole pass is enqueued; frame_begin has read them)
     // Two-pass occlusion culling: round 1 draws the meshlet-instances that owned a pixel last frame, a Hi-Z pyramid of the
     // result rejects what it hides, round 2 draws the rest.  The depth test decides every pixel either way, so the frame does
     // not depend on the history; without one (first frame of a scene) or with ZR_FLAG_NO_HIZ everything is drawn at once.
@@ -461,7 +474,17 @@ static int gbuffer_pass(zr_ctx* c, hipStream_t s, bool defer_resolve = false)
     const bool two = c->last_two_round;
     // (the record buckets are planned from the previous frame: see tri_raster)
     const bool count_first = !c->plan_valid || (!two && c->plan_two_round);
-    if (two) {
+    // Round 2 kept (zr_ctx::camera_epoch): the inputs are the previous frame's bit for bit, so round 1 - what owned a pixel of that frame -
+    // leaves this frame's key buffer, and round 1 is the frame's last round: its k_tile draws the slow triangles.  The statistics and the
+    // plan are those of round 2 as last drawn (k_plan); a timed frame records its events all the same and counts 0 for both passes.
+    const bool keep = two && c->round2_keep && !count_first;
+    if (ev) T->kept_round2 = keep;
+    if (keep) {
+        Z.phase = 1;
+        if (ev) HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_CULL], s));
+        tri_raster(c, P, Z, 1, s, true, false);
+        if (ev) { HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_ROUND1], s)); HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_HIZ], s)); }
+    } else if (two) {
         Z.phase = 1;
         if (ev) HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_CULL], s));
         tri_raster(c, P, Z, 1, s, false, count_first);
@@ -499,9 +522,11 @@ static int gbuffer_pass(zr_ctx* c, hipStream_t s, bool defer_resolve = false)
     }
     c->vis_mark_prev = vis_mark;
     if (P.n_work != 0) {     // the next frame's buckets, from this frame's counts: nothing of this frame waits for it
-        zr_launch_plan(c->tb, c->d_owned, c->n_owned, c->d_stats, false, c->bucket_pct, s);
+        zr_launch_plan(c->tb, c->d_owned, c->n_owned, c->d_stats, false, c->bucket_pct, s, keep ? ZR_PLAN_KEPT_ROUND2 : two ? ZR_PLAN_DREW_ROUND2 : ZR_PLAN_ONE_ROUND);
         c->plan_valid = true; c->plan_two_round = two;
     }
+    c->r2_settled = two && c->cam_same;
+    c->cam_prev_key = c->pass[1]; c->cam_prev_epoch = c->frame_cam_epoch; c->cam_prev_valid = hiz_on;
     if (hiz_on) { c->vis_history = true; c->vis_cur ^= 1; } else c->vis_history = false;
     HIPCHK(c, hipGetLastError());
     return ZR_OK;

@@ -39,6 +39,9 @@ extern "C" int zr_finish(zr_ctx* c)
             if (c->h_stats.overflow_sticky) {     // latched by ANY frame since the last zr_finish, not only the newest one
                 HIPCHK(c, zr_fill_sync({ { &c->d_stats->overflow_sticky, 0, sizeof(uint32_t) }, { &c->d_sstats->overflow_sticky, 0, sizeof(uint32_t) } }));
                 c->h_stats.overflow = 1u;
+                // (a frame that ran full may have left an incomplete key buffer, and a rest would stand on it: the next frame draws round 2
+                // again, from buckets planned from this frame's counts, and heals as it did before round 2 was ever kept)
+                zr_camera_changed(c);
                 static const char* const what[] = { "?", "shadow bin entries", "slow-triangle list (zr_set_limits)", "camera work-unit table", "triangle-record arrays (zr_set_limits)",
                                                     "late shadow bin entries" };
                 const uint32_t code = c->h_stats.overflow_sticky < 6u ? c->h_stats.overflow_sticky : 0u;
@@ -85,6 +88,7 @@ extern "C" int zr_get_pass_times_avg(zr_ctx* c, uint32_t last_n, float ms[ZR_PAS
             (void)hipEventElapsedTime(&t[ZR_PASS_TOTAL], ev[zr_ctx::EV_BEGIN], ev[zr_ctx::EV_LIGHTING]);
             // (a frame that kept its shadow map ran no shadow pipeline: exactly 0, not the gap between two back-to-back records)
             if (T.kept) t[ZR_PASS_CULL_SHADOW] = t[ZR_PASS_SHADOW] = 0.0f;
+            if (T.kept_round2) t[ZR_PASS_HIZ] = t[ZR_PASS_GBUFFER2] = 0.0f;      // (likewise: no Hi-Z build, no k_select, no second round)
             for (int i = 0; i < ZR_PASS_COUNT; ++i) acc[i] += t[i];
         }
         for (int i = 0; i < ZR_PASS_COUNT; ++i) ms[i] = (float)(acc[i] / last_n);

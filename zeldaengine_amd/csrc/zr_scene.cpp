@@ -334,6 +334,7 @@ extern "C" int zr_set_bucket_share(zr_ctx* c, uint32_t percent)
     return zr_guard(c, [&]() -> int {
         c->bucket_pct = percent;          // (k_plan's argument from the next plan on; a frame that overflows its buckets is the same frame.
                                           // The camera pass's record buckets only: the shadow bins know nothing of it, the map is kept)
+        zr_camera_changed(c);             // (where the records go: round 2 is drawn again, pool_used is the new layout's)
         return ZR_OK;
     });
 }
@@ -462,6 +463,7 @@ static int make_work_pools(zr_ctx* c, uint32_t cap_w)
     HIPCHK(c, P.alloc(&T.cursor, (size_t)2 * c->n_tiles * ZR_TSTRIDE));
     HIPCHK(c, P.alloc(&T.over_cursor, 2 * ZR_OVER_SECTIONS)); HIPCHK(c, P.alloc(&T.n_units, 1));
     HIPCHK(c, P.alloc(&T.unit_tab, T.unit_cap)); HIPCHK(c, P.alloc(&T.wave_culled, T.n_waves)); HIPCHK(c, P.alloc(&T.slow, 4ull * T.slow_cap));
+    HIPCHK(c, P.alloc(&T.r2_count, c->n_tiles)); HIPCHK(c, P.alloc(&T.r2_stats, ZR_R2_WORDS));
     HIPCHK(c, P.alloc(&c->d_pxrect, cap_w)); HIPCHK(c, P.alloc(&c->d_zmin, cap_w));
     HIPCHK(c, P.alloc(&c->d_visflag[0], cap_w)); HIPCHK(c, P.alloc(&c->d_visflag[1], cap_w));
     HIPCHK(c, P.alloc(&c->d_spxrect, cap_w)); HIPCHK(c, P.alloc(&c->d_szmin, cap_w)); HIPCHK(c, P.alloc(&c->d_sflag, cap_w));
@@ -469,7 +471,7 @@ static int make_work_pools(zr_ctx* c, uint32_t cap_w)
     // frame's k_plan would wipe the plan - every record then overflows into sections of capacity 0)
     HIPCHK(c, zr_fill_sync({ { T.tile_base, 0, (size_t)c->n_tiles * 4 }, { T.tile_cap, 0, (size_t)c->n_tiles * 4 },
                              { T.cursor, 0, (size_t)2 * c->n_tiles * ZR_TSTRIDE * 4 }, { T.over_cursor, 0, 2 * ZR_OVER_SECTIONS * 4 },
-                             { T.n_units, 0, 4 }, { T.plan, 0, 8 },
+                             { T.n_units, 0, 4 }, { T.plan, 0, 8 }, { T.r2_count, 0, (size_t)c->n_tiles * 4 }, { T.r2_stats, 0, ZR_R2_WORDS * 4 },
                              { c->d_visflag[0], 0, cap_w }, { c->d_visflag[1], 0, cap_w } }));      // (no frame's stamp is 0)
     c->work_capacity = cap_w;              // every buffer is there
     return ZR_OK;

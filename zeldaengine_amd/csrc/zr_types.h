@@ -285,8 +285,14 @@ struct ZrTriBins {
     uint32_t  n_tiles;
     uint32_t  n_waves;               // waves of the k_geom grid
     uint32_t* wave_culled;           // per wave: meshlets it dropped behind the Hi-Z pyramid (round 2)
+    // A frame that keeps round 2 (zr_ctx::camera_epoch) reports and plans with what the last drawn round 2 left (k_plan, ZR_PLAN_*):
+    uint32_t* r2_count;              // [n_tiles] the records round 2 appended to each tile
+    uint32_t* r2_stats;              // [ZR_R2_WORDS] the words of the statistics block that round 2's kernels write
     uint4*    slow; uint32_t slow_cap;      // 4 x uint4 per slow triangle: three clip-space vertices, (prim, tile rect, 0, 0)
 };
+#define ZR_R2_WORDS 8u                // survivors[2], hiz_culled, hiz_culled_geom, n_sel[2], n_slow[2], n_chunks[2], overflow, its ZR_OVF_* code
+// k_plan and round 2: the frame drew one round / drew both (k_plan stashes round 2's counts and statistics) / kept round 2 (k_plan puts them back)
+enum { ZR_PLAN_ONE_ROUND = 0, ZR_PLAN_DREW_ROUND2 = 1, ZR_PLAN_KEPT_ROUND2 = 2 };
 #define ZR_OVER_SECTIONS 64u          // sections of the overflow region (a power of two)
 #ifndef ZR_TSTRIDE
 #define ZR_TSTRIDE 4u                 // words between the per-tile record cursors of neighbouring tiles
@@ -302,7 +308,8 @@ struct ZrTriBins {
 void zr_launch_select(const ZrPass& P, const ZrObject* objs, const uint32_t* work, const uint32_t* rects, const ZrHiz& Z, const ZrTriBins& B, ZrDevStats* stats,
                       int slot, hipStream_t s);
 void zr_launch_geom(const ZrPass& P, const ZrHiz& Z, const ZrTriBins& B, ZrDevStats* stats, int slot, bool count_only, hipStream_t s);
-void zr_launch_plan(const ZrTriBins& B, const uint32_t* owned_tiles, uint32_t n_owned, ZrDevStats* stats, bool exact, uint32_t bucket_pct, hipStream_t s);
+void zr_launch_plan(const ZrTriBins& B, const uint32_t* owned_tiles, uint32_t n_owned, ZrDevStats* stats, bool exact, uint32_t bucket_pct, hipStream_t s,
+                    uint32_t round2 = ZR_PLAN_ONE_ROUND);
 void zr_launch_tile(const ZrPass& P, const ZrTriBins& B, ZrDevStats* stats, int slot, unsigned long long* vis64, uint32_t n_blocks, hipStream_t s, bool last,
                     const uint32_t* owned_tiles, uint32_t n_owned);
 void zr_launch_cull_box(const ZrPass& P, const ZrObject* objs, uint32_t* work, uint32_t* rects, const ZrHiz& Z, ZrDevStats* stats,
