@@ -290,7 +290,18 @@ int  zr_set_shading(zr_ctx* ctx, uint32_t mode);
  * drawn round 2, ZR_PASS_HIZ and ZR_PASS_GBUFFER2 read exactly 0.  Every entry point decides alike; never kept: contexts with
  * ZR_FLAG_NO_LIST_REUSE (and ZR_FLAG_NO_HIZ has no second round to keep).  A frame that ran out of record room (ZR_ERR_OVERFLOW from
  * zr_finish) is incomplete, and so is every frame of the rest that keeps round 2 behind it - each reports the overflow again - until
- * zr_finish has reported it: the frame after that draws both rounds again. */
+ * zr_finish has reported it: the frame after that draws both rounds again.
+ * The WHOLE camera pass, and the GBuffer with it, is kept one step further: when, beyond the above, nothing the GBuffer write reads
+ * changed (material textures: zr_object_set_texture / zr_object_update_texture_async; the winner plane of zr_set_shading and
+ * zr_set_id_capture) and both internal GBuffer copies were written from these very inputs - from the third frame after the last such
+ * change on - a frame enqueues, on the render stream alone: the uniform upload, the shadow pipeline if the map is drawn, and the
+ * lighting pass (with its one-pixel pre-launch); where zr_render keeps the shadow map too (a map at least two frames old), the upload and the pre-launch go to the
+ * library's own, otherwise idle stream beside the previous frame's lighting pass, and the render stream waits for them.  The GBuffer, the
+ * visibility history, the record plan and every camera-pass statistic (covered_pixels included) stay those of the last drawn frame, so
+ * zr_get_stats, zr_read_gbuffer, the identity queries and zr_copy_frame_async answer as on a drawn frame; ZR_PASS_CULL_CAMERA,
+ * ZR_PASS_GBUFFER, ZR_PASS_HIZ, ZR_PASS_GBUFFER2 and ZR_PASS_RESOLVE read exactly 0.  Lights, debug view, background and cubemap are
+ * inputs of the lighting pass and end nothing.  Never kept whole: a context that draws a skydome (its round 2 is still kept), and
+ * whatever never keeps round 2. */
 int  zr_render(zr_ctx* ctx);
 /* The same frame in three stages (zr_render = all three, in this order), so that a multi-GPU host can place its
  * collectives between them: shadow pass | deferred-scene pass (cull, raster, GBuffer write) | deferred-lighting pass. */

@@ -1,0 +1,487 @@
+"""The whole camera pass and its GBuffer are kept while camera and scene stand still (csrc/zr_frame_host.cpp: frame_begin, camera_keep).
+
+The lighting pass reads the GBuffer planes and the frame's uniforms, nothing else of the camera pipeline.  When this frame's camera-pass
+inputs and everything the resolve reads beyond them are the last two frames', both GBuffer copies already hold this frame's planes:
+the frame launches no cull, no round, no k_mark, no k_plan and no resolve, resets no statistics, and lights its parity's copy.  The
+observable is the pass time: such a frame reports exactly 0.0 for "cull_camera", "gbuffer", "hiz", "gbuffer2" and "resolve" (the library
+stores 0) and a lighting time above 0.  Whatever is kept must be what would have been drawn: every frame here is compared bit for bit -
+six planes, map, colour - with the CPU oracle, its statistics with those of a ZR_FLAG_NO_LIST_REUSE twin, which draws everything every
+frame; sequences queued without a host synchronisation are compared with the twin's frames.
+
+Scenes, helpers and statistics keys are those of test_gpu_round2_keep.py: the pile (160 x 90, a 128^2 map) and the crowd (384 x 216, a
+256^2 map).  Timing interval 1; the point lights ride their spiral in every sequence.
+"""
+import copy
+import json
+import math
+
+import numpy as np
+import pytest
+
+from test_gpu_resolve_lane import STAT_KEYS
+from test_gpu_round2_keep import BOX, SPHERES, Checker, Stage, _dev, _kept, _not_vacuous, _render, _same
+from zeldaengine_amd import abi, scenes
+
+pytestmark = pytest.mark.gpu
+
+CAMERA_PASSES = ("cull_camera", "gbuffer", "hiz", "gbuffer2", "resolve")
+
+
+def _whole(t):
+    """the frame kept its whole camera pass"""
+    return all(t[k] == 0.0 for k in CAMERA_PASSES) and t["lighting"] > 0.0
+
+
+def _keys(st):
+    return {k: st[k] for k in STAT_KEYS}
+
+
+class ViewChecker(Checker):
+    """Checker with the lighting pass's own switches: debug view, background image, forward shading."""
+
+    def __init__(self, oracle_lib):
+        super().__init__(oracle_lib)
+        self.view, self.bg, self.forward = 0, None, False
+
+    def frame(self, st, i):
+        if self.o is None or self.key is None or self.key[0] != st.version:
+            self.o = self.lib.Oracle(st.W, st.H, st.SD)
+            st.populate(self.o, oracle=True)
+            self.key = None
+        self.o.set_shading(self.forward)
+        if self.bg is not None:
+            self.o.set_background(self.bg)
+        # (the oracle draws the background over the empty pixels with its scene pass: a new image is a new key)
+        key = (st.version, st.light, st.roll_stage, st.cam, st.view_ulps, self.forward, id(self.bg))
+        st.uniforms(self.o, i)
+        self.o.render(self.view, 7 if key != self.key else 4)
+        self.key = key
+        return self.o
+
+
+# ------------------------------------------------------------------------------------------------ 1. a still run
+
+@pytest.mark.parametrize("kind,flags", [("crowd", 0), ("pile", 0), ("pile", abi.FLAG_SERIAL_PASSES)])
+def test_still_camera_keeps_the_camera_pass(oracle_lib, gpu_engine, kind, flags):
+    """Eight frames, camera and scene still, the point lights moving: one round, both rounds, six frames that keep everything."""
+    st = Stage(kind)
+    if kind == "pile":          # (as in test_gpu_round2_keep.py: the shadow slots of the statistics compare like the camera's)
+        flags |= abi.FLAG_NO_SHADOW_OCCLUSION
+    g = st.renderer(gpu_engine, flags)
+    twin = st.renderer(gpu_engine, flags | abi.FLAG_NO_LIST_REUSE)
+    chk = Checker(oracle_lib)
+    times, colours = [], []
+    for i in range(8):
+        t = _render(g, st, i)
+        tt = _render(twin, st, i)
+        _same(chk.frame(st, i), g, "%s frame %d" % (kind, i))
+        sg, sw = g.stats(), twin.stats()
+        print("frame", i, {k: t[k] for k in CAMERA_PASSES + ("lighting",)}, _keys(sg))
+        assert _keys(sg) == _keys(sw), "statistics of frame %d" % i
+        assert sg["overflow"] == 0
+        assert tt["resolve"] > 0.0 and tt["gbuffer"] > 0.0, "the twin kept something on frame %d" % i
+        if i == 0:
+            assert sg["round1_survivors"] == 0
+        if i >= 2:              # not vacuous: what is kept is a two-round pass that covered pixels and rejected work
+            assert sg["covered_pixels"] > 0 and sg["round1_survivors"] > 0 and sg["hiz_culled"] > 0, sg
+        times.append(t); colours.append(g.color().copy())
+    assert times[0]["resolve"] > 0.0 and times[0]["gbuffer"] > 0.0, times[0]
+    assert times[1]["hiz"] > 0.0 and times[1]["gbuffer2"] > 0.0 and times[1]["resolve"] > 0.0, times[1]
+    assert [_whole(t) for t in times] == [False, False] + [True] * 6, times
+    assert not np.array_equal(colours[3], colours[6])          # the point lights did move
+    g.close(); twin.close()
+
+
+# ------------------------------------------------------------------------------------------------ 2. every change ends the keep
+
+def test_every_change_ends_the_keep(oracle_lib, gpu_engine):
+    """Rest (kept) - change - two frames that are not kept - kept, for every way the camera pass's result or the resolved surface can
+    change.  After a surface-only change both frames resolve again (each GBuffer copy once) and the third keeps."""
+    import torch
+    st = Stage("pile")
+    st.box_image = np.random.default_rng(4).integers(0, 256, (16, 16, 4), dtype=np.uint8)
+    g = st.renderer(gpu_engine)
+    chk = ViewChecker(oracle_lib)
+
+    def camera_one_ulp():
+        st.view_ulps += 1
+
+    def roll_stage():
+        st.roll_stage = 0.3
+
+    def moved():
+        new = st.inst.copy()
+        new["InstancePosition"][:60, 2] += np.float32(2.5); new["InstancePScale"][:60] *= np.float32(1.5)
+        st.inst = new; st.version += 1
+        return new
+
+    def set_instances():
+        g.object_set_instances(SPHERES, moved()[:60])
+
+    def update_instances_async():
+        g.object_update_instances_async(SPHERES, _dev(moved()[:60], 32))
+
+    def deformed():
+        v, idx = st.sphere
+        v = v.copy(); v["Position"][:, 2] *= np.float32(1.3)
+        st.sphere = (v, idx); st.version += 1
+        return v
+
+    def set_vertices():
+        g.mesh_set_vertices(SPHERES, deformed())
+
+    def update_vertices_async():
+        g.mesh_update_vertices_async(SPHERES, _dev(deformed(), 44))
+
+    def instance_visibility():
+        st.shown = (np.arange(len(st.inst)) % 3) != 0; st.version += 1
+        g.object_set_instance_visibility(SPHERES, st.shown)
+
+    def object_visibility():
+        st.box_shown = False; st.version += 1
+        g.object_set_visible(BOX, False)
+
+    def object_visible_again():
+        st.box_shown = True; st.version += 1
+        g.object_set_visible(BOX, True)
+
+    def object_add():
+        g.object_add(g.mesh_create(*scenes.box((1.0, 1.0, 1.0), (2.0, 1.0, 3.0))))
+        st.extra = True; st.version += 1
+
+    def clear_and_reload():
+        st.inst = scenes.generate_instances(250, 0.5, 7.0, 0.2, 0.6, seed=8); st.shown = None; st.box_shown = True; st.extra = False; st.version += 1
+        g.scene_clear(); st.populate(g)
+
+    def set_limits():
+        g.set_limits(8192, 4096)
+
+    # surface only: the camera pass's inputs stand, the resolve's do not
+    def object_set_texture():
+        st.box_image = 255 - st.box_image; st.version += 1
+        g.object_set_texture(BOX, 0, st.box_image)
+
+    def object_update_texture_async():
+        st.box_image = np.roll(st.box_image, 5, axis=1).copy(); st.version += 1
+        t = torch.from_numpy(st.box_image).to(torch.device("cuda", 0))
+        torch.cuda.synchronize()
+        g.object_update_texture_async(BOX, 0, t)
+        g.finish()                  # (the tensor may go once the update has run)
+
+    def id_capture_on():
+        g.set_id_capture(True)
+
+    def id_capture_off():
+        g.set_id_capture(False)
+
+    def shading_forward():
+        g.set_shading(True); chk.forward = True
+
+    def shading_back():
+        g.set_shading(False); chk.forward = False
+
+    def skydome_on():               # (last: a context that draws a skydome never keeps its resolve)
+        st.sky = True; st.version += 1
+        g.set_skydome(*scenes.sky_dome(20.48, 16, 8), scenes.synthetic_sky_image(64, 32))
+
+    surface = ("object_set_texture", "object_update_texture_async", "id_capture_on", "id_capture_off", "shading_forward", "shading_back")
+    i = 0
+    for _ in range(2):
+        assert not _whole(_render(g, st, i))
+        i += 1
+    _not_vacuous(g.stats())
+    for change in (camera_one_ulp, roll_stage, set_instances, update_instances_async, set_vertices, update_vertices_async, instance_visibility,
+                   object_visibility, object_visible_again, object_add, clear_and_reload, set_limits, object_set_texture,
+                   object_update_texture_async, id_capture_on, id_capture_off, shading_forward, shading_back, skydome_on):
+        name = change.__name__
+        t = _render(g, st, i)
+        assert _whole(t), "%s: the still frame before it drew something (%r)" % (name, t)
+        _same(chk.frame(st, i), g, "still frame before " + name)
+        change()
+        for k in (1, 2):
+            i += 1
+            t = _render(g, st, i)
+            assert not _whole(t) and t["resolve"] > 0.0, "%s: frame %d after it kept a stale GBuffer (%r)" % (name, k, t)
+            if name in surface:     # (the visibility stands: round 2 stays kept, the planes are resolved again)
+                assert _kept(t) and t["gbuffer"] > 0.0, "%s: frame %d after it (%r)" % (name, k, t)
+            _same(chk.frame(st, i), g, "frame %d after %s" % (k, name))
+        i += 1
+        t = _render(g, st, i)
+        if name == "skydome_on":
+            assert _kept(t) and t["resolve"] > 0.0 and t["gbuffer"] > 0.0, t
+        else:
+            assert _whole(t), "%s: the third frame after it drew something again (%r)" % (name, t)
+        _same(chk.frame(st, i), g, "third frame after " + name)
+        assert g.stats()["overflow"] == 0
+        i += 1
+    g.close()
+
+
+def test_lighting_inputs_do_not_end_the_keep(oracle_lib, gpu_engine):
+    """Debug views 0 - 8 and a new background on a resting context: every frame keeps its camera pass and is the oracle's."""
+    st = Stage("pile")
+    g = st.renderer(gpu_engine)
+    chk = ViewChecker(oracle_lib)
+    for i in range(3):
+        t = _render(g, st, i)
+    assert _whole(t)
+    i = 3
+    for view in list(range(9)) + [0]:
+        g.set_debug_view(view); chk.view = view
+        if view == 4:
+            chk.bg = scenes.synthetic_sky_image(48, 32)
+            g.set_background(chk.bg)
+        t = _render(g, st, i)
+        assert _whole(t), (view, t)
+        _same(chk.frame(st, i), g, "debug view %d" % view)
+        i += 1
+    g.close()
+
+
+def test_a_world_update_ends_the_keep(oracle_lib, gpu_engine):
+    from test_gpu_tiles_world import _oracle_from_renderer, _register_sample_profabs
+    W, H, SD = 160, 120, 128
+    cube = scenes.synthetic_cubemap(16)
+    g = gpu_engine.Renderer(W, H, SD)
+    g.set_cubemap(cube)
+    ids = _register_sample_profabs(g)
+    meshes = {ids["terrain"]: scenes.grid_plane(20.0, 4, 0.0), ids["rock_01"]: scenes.box((0.5, 0.5, 0.5), (0, 0, 0.5)), ids["grass_01"]: scenes.uv_sphere()}
+    w = copy.deepcopy(scenes.sample_world())
+    w["Objects"][3]["InstanceCount"] = 700
+
+    def frame(what, whole):
+        g.render(); g.finish()
+        t = g.pass_times(1)
+        assert _whole(t) == whole, (what, t)
+        o = _oracle_from_renderer(oracle_lib, g, meshes, W, H, SD, cube)
+        o.render()
+        _same(o, g, what)
+        o.close()
+
+    g.world_load_json(json.dumps(w))
+    g.render(); g.finish()
+    frame("second frame of the world", False)
+    frame("still frame", True)
+    w["Objects"][2]["InstanceCount"] = 90
+    d = g.world_update_json(json.dumps(w))
+    assert d["scene_changed"] == 1, d
+    frame("frame after the update", False)
+    frame("second frame after the update", False)
+    frame("third frame after the update", True)
+    g.close()
+
+
+# ------------------------------------------------------------------------------------------------ 3. beside drawn and kept maps
+
+def test_kept_camera_pass_beside_drawn_shadow_maps(oracle_lib, gpu_engine):
+    """The light moves every other frame: the camera pass is kept on frames that draw their map and on frames that keep it, through
+    zr_render and through the staged entry points."""
+    st = Stage("pile")
+    g, s = st.renderer(gpu_engine), st.renderer(gpu_engine)
+    chk = Checker(oracle_lib)
+    for i in range(8):
+        st.light = (6.0 + 0.4 * (i // 2), 0.3 * (i // 2), 14.0)
+        t, ts = _render(g, st, i), _render(s, st, i, "staged")
+        assert (t["shadow"] > 0.0) == (ts["shadow"] > 0.0) == (i % 2 == 0), (i, t, ts)
+        assert _whole(t) == _whole(ts) == (i >= 2), (i, t, ts)
+        _same(chk.frame(st, i), g, "zr_render, frame %d" % i)
+        _same(chk.o, s, "staged, frame %d" % i)
+        assert _keys(g.stats()) == _keys(s.stats()), i
+    g.close(); s.close()
+
+
+def test_gbuffer_read_between_geometry_and_lighting(oracle_lib, gpu_engine):
+    """zr_render_geometry, a GBuffer read-back, zr_render_lighting: a kept frame's planes are there before its lighting pass."""
+    st = Stage("pile")
+    g = st.renderer(gpu_engine)
+    chk = Checker(oracle_lib)
+    for i in range(6):
+        st.light = (6.0 + 0.4 * (i // 2), 0.3 * (i // 2), 14.0)
+        st.uniforms(g, i)
+        g.render_geometry()
+        planes = [g.gbuffer(t).copy() for t in range(6)]
+        g.render_lighting(); g.finish()
+        t = g.pass_times(1)
+        assert _whole(t) == (i >= 2), (i, t)
+        o = chk.frame(st, i)
+        for k in range(6):
+            assert np.array_equal(o.gbuffer(k).view(np.uint8), planes[k].view(np.uint8)), "plane %d read before the lighting pass of frame %d" % (k, i)
+        _same(o, g, "frame %d" % i)
+    g.close()
+
+
+# ------------------------------------------------------------------------------------------------ 4. frames in flight
+
+def test_frames_in_flight_rest_cut_rest(gpu_engine):
+    """No finish() between the frames: four resting frames, a 30 degree camera cut, two more frames, a rest of three, each copied out in
+    stream order and compared with the same sequence on the twin; the keep pattern is read from summed pass times afterwards."""
+    import torch
+    dev = torch.device("cuda", 0)
+    out = {}
+    N = 10
+    for flags in (abi.FLAG_NO_LIST_REUSE, 0):
+        st = Stage("crowd")
+        r = st.renderer(gpu_engine, flags)
+        col = [torch.zeros(st.W * st.H, dtype=torch.int32, device=dev) for _ in range(N)]
+        sha = [torch.zeros(st.SD * st.SD, dtype=torch.int32, device=dev) for _ in range(N)]
+        torch.cuda.synchronize()
+        for k in range(N):
+            if k == 4:
+                (x, y, z), look = st.cam
+                a = math.radians(30.0)
+                st.cam = (x * math.cos(a) - y * math.sin(a), x * math.sin(a) + y * math.cos(a), z), look
+            st.uniforms(r, k)
+            r.render()
+            r.copy_frame_async(col[k].data_ptr(), sha[k].data_ptr())
+        r.finish()
+        stats = r.stats()
+        assert stats["overflow"] == 0
+        sums = [n * sum(r.pass_times(n)[p] for p in CAMERA_PASSES) for n in range(1, N + 1)]      # S(n): the sum over the last n frames
+        out[flags] = ([c.cpu().numpy() for c in col], [x.cpu().numpy() for x in sha], sums, stats, [r.gbuffer(t).copy() for t in range(6)])
+        r.close()
+    got, ref = out[0], out[abi.FLAG_NO_LIST_REUSE]
+    for k in range(N):
+        assert np.array_equal(got[1][k], ref[1][k]), "shadow map of queued frame %d" % k
+        assert np.array_equal(got[0][k], ref[0][k]), "colour of queued frame %d: %d pixels differ" % (k, int((got[0][k] != ref[0][k]).sum()))
+    assert not np.array_equal(got[0][2], got[0][3]) and not np.array_equal(got[0][8], got[0][9])
+    assert all(np.array_equal(a.view(np.uint8), b.view(np.uint8)) for a, b in zip(got[4], ref[4])), "GBuffer of the last queued frame"
+    assert _keys(got[3]) == _keys(ref[3])
+    _not_vacuous(got[3])
+    per = [got[2][n] - (got[2][n - 1] if n else 0.0) for n in range(N)][::-1]      # per frame, oldest first
+    print("camera-pass ms per queued frame, keeping:", per)
+    # frames 0, 1 drawn; 2, 3 kept; 4 (the cut), 5 drawn; 6 .. 9 kept.  (A drawn frame's five passes hold kernels: far above 1e-3 ms.)
+    assert got[2][3] == 0.0 and got[2][4] > 1e-3 and got[2][5] > got[2][4] + 1e-3, got[2]
+    assert abs(got[2][7] - got[2][5]) < 1e-6 and got[2][8] > got[2][7] + 1e-3 and got[2][9] > got[2][8] + 1e-3, got[2]
+    refper = [ref[2][n] - (ref[2][n - 1] if n else 0.0) for n in range(N)]
+    assert all(x > 1e-3 for x in refper), ref[2]
+
+
+# ------------------------------------------------------------------------------------------------ 5. a rest longer than the stamp period
+
+def test_rest_longer_than_the_stamp_period(oracle_lib, gpu_engine):
+    """260 kept frames (the visibility stamps have a period of 255), then a camera step that changes round 1's list: the stamps count
+    passes drawn, so the frames after the rest find the history a run of drawn frames would have left."""
+    st = Stage("pile")
+    g = st.renderer(gpu_engine, abi.FLAG_NO_SHADOW_OCCLUSION)
+    twin = st.renderer(gpu_engine, abi.FLAG_NO_SHADOW_OCCLUSION | abi.FLAG_NO_LIST_REUSE)
+    chk = Checker(oracle_lib)
+    for i in range(2):
+        _render(g, st, i); _render(twin, st, i)
+    for i in range(2, 262):
+        st.uniforms(g, i)
+        g.render()
+    g.finish()
+    t = g.pass_times(64)
+    assert _whole(t), t
+    _same(chk.frame(st, 261), g, "the last frame of the rest")
+    st.uniforms(twin, 261); twin.render(); twin.finish()
+    assert _keys(g.stats()) == _keys(twin.stats())
+    (x, y, z), look = st.cam
+    a = math.radians(20.0)
+    st.cam = (x * math.cos(a) - y * math.sin(a), x * math.sin(a) + y * math.cos(a), z), look
+    before = g.stats()["round1_survivors"]
+    for i in (262, 263):
+        t = _render(g, st, i); _render(twin, st, i)
+        assert not _whole(t) and t["gbuffer2"] > 0.0, (i, t)
+        _same(chk.frame(st, i), g, "frame %d after the rest" % (i - 261))
+        assert _keys(g.stats()) == _keys(twin.stats()), i
+        assert g.stats()["round1_survivors"] > 0
+    assert g.stats()["round1_survivors"] != before          # (the step did change what round 1 draws)
+    g.close(); twin.close()
+
+
+# ------------------------------------------------------------------------------------------------ 6. overflow
+
+def test_overflow_ends_the_keep(oracle_lib, gpu_engine):
+    """Record arrays too small for the frame.  The host learns of the latch only from finish(): frames 2 and 3 of the rest keep (they
+    launch nothing that could set or clear it), finish() still reports what frames 0 and 1 latched, and the frame after that report
+    keeps nothing."""
+    st = Stage("pile")
+    g = st.renderer(gpu_engine)
+    g.set_limits(8, 0)
+    for i in range(4):
+        st.uniforms(g, i)
+        g.render()
+    with pytest.raises(gpu_engine.ZeldaRenderError) as e:
+        g.finish()                      # the latch survived the two kept frames behind the frames that set it
+    assert e.value.code == abi.ERR_OVERFLOW, e.value
+    sums = [n * sum(g.pass_times(n)[p] for p in CAMERA_PASSES) for n in (1, 2, 3)]      # (the report cleared the latch: these finish clean)
+    assert sums[0] == 0.0 and sums[1] == 0.0 and sums[2] > 1e-3, sums      # frames 3 and 2 kept, frame 1 drawn
+    g.finish()                          # ... and kept frames set nothing: clean
+    st.uniforms(g, 4)
+    g.render()
+    t = g.pass_times(1)                 # (reads the times whether or not this frame ran full again)
+    assert not _whole(t) and t["resolve"] > 0.0 and t["gbuffer"] > 0.0 and t["gbuffer2"] > 0.0, t
+    g.set_limits(0, 0)                  # the default pools: whole again, and kept again
+    chk = Checker(oracle_lib)
+    for i in range(5, 8):
+        t = _render(g, st, i)
+    assert _whole(t) and g.stats()["overflow"] == 0, t
+    _same(chk.frame(st, 7), g, "after the overflow")
+    g.close()
+
+
+def test_identity_queries_on_kept_frames(gpu_engine):
+    """Id capture on: the winner planes of both GBuffer copies are kept with the rest, so the identity queries and the statistics of a
+    kept frame are those of a twin that draws every frame."""
+    st = Stage("pile")
+    g, twin = st.renderer(gpu_engine), st.renderer(gpu_engine, abi.FLAG_NO_LIST_REUSE)
+    for r in (g, twin):
+        r.set_id_capture(True)
+    for i in range(6):
+        t = _render(g, st, i); _render(twin, st, i)
+        assert _whole(t) == (i >= 2), (i, t)
+        for kind in (abi.IDS_PRIMITIVE, abi.IDS_OBJECT):
+            assert np.array_equal(g.read_ids(kind), twin.read_ids(kind)), (i, kind)
+        assert np.array_equal(g.instance_coverage(), twin.instance_coverage()), i
+        (hg, ng), (hw, nw) = g.pick(0, 0, st.W, st.H), twin.pick(0, 0, st.W, st.H)
+        key = lambda h: sorted(zip(h["object"].tolist(), h["instance"].tolist(), h["pixels"].tolist()))
+        assert ng == nw and ng > 10 and key(hg) == key(hw), i
+        sg, sw = g.stats(), twin.stats()
+        for k in ("round1_survivors", "hiz_culled", "hiz_culled_geom", "covered_pixels"):
+            assert sg[k] == sw[k], (i, k, sg, sw)
+        assert sg["survivors"][1] == sw["survivors"][1] and sg["bin_entries"][1] == sw["bin_entries"][1] and sg["overflow"] == 0, (i, sg, sw)
+    g.close(); twin.close()
+
+
+# ------------------------------------------------------------------------------------------------ 7. partitioned
+
+def test_tile_partitioned_ranks_keep(oracle_lib, gpu_engine):
+    """Ranks 0 and 1 of a two-rank tile partition on one GPU: both keep, and each rank's owned tiles are the unpartitioned context's."""
+    from zeldaengine_amd import dist as zdist
+    st = Stage("pile")
+    whole = st.renderer(gpu_engine)
+    ranks = []
+    for r in range(2):
+        g = gpu_engine.Renderer(st.W, st.H, st.SD, tile_rank=r, tile_world=2)
+        st.populate(g)
+        ranks.append(g)
+    chk = Checker(oracle_lib)
+    for i in range(5):
+        tw = _render(whole, st, i)
+        assert _whole(tw) == (i >= 2), (i, tw)
+        want = whole.color()
+        if i == 4:
+            _same(chk.frame(st, i), whole, "unpartitioned, frame %d" % i)
+        for k, g in enumerate(ranks):
+            t = _render(g, st, i)
+            assert _whole(t) == (i >= 2), (i, k, t)
+            assert np.array_equal(g.read_tiles(), zdist.pack_tiles(want, k, 2)), "frame %d rank %d" % (i, k)
+            assert g.stats()["overflow"] == 0 and (i < 1 or g.stats()["round1_survivors"] > 0)
+    for g in ranks + [whole]:
+        g.close()
+
+
+# ------------------------------------------------------------------------------------------------ 8. never kept
+
+@pytest.mark.parametrize("what", ["skydome", "no_list_reuse"])
+def test_contexts_that_never_keep(oracle_lib, gpu_engine, what):
+    st = Stage("pile")
+    st.sky = what == "skydome"
+    g = st.renderer(gpu_engine, abi.FLAG_NO_LIST_REUSE if what == "no_list_reuse" else 0)
+    chk = Checker(oracle_lib)
+    for i in range(5):
+        t = _render(g, st, i)
+        assert t["resolve"] > 0.0 and t["gbuffer"] > 0.0 and not _whole(t), (i, t)
+        _same(chk.frame(st, i), g, "%s, frame %d" % (what, i))
+    g.close()

@@ -10,7 +10,8 @@ equals the workload it is running.
 HBM bytes, exactly as MI355X_MICROARCH.md (HBM section) prescribes: FETCH_SIZE and WRITE_SIZE come from separate --pmc passes (they
 do not fit one), are in KiB, and on gfx950 FETCH_SIZE counts 64 B per 128 B read request, i.e. half the bytes of a coalesced
 stream (calibrated on k_count_shadow: a 4 MiB dword-per-lane read reports 2056 KiB), so bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024.
-Per-frame totals = sum over every dispatch of the frame's kernels / number of frames in that run (= dispatches of k_resolve_gbuffer).
+Per-frame totals = sum over every dispatch of the frame's kernels / number of frames in that run (= dispatches of k_lighting / 2: the pass and its
+one-pixel pre-launch; a frame that keeps its whole camera pass runs no k_resolve_gbuffer).
 A frame that keeps its shadow map and resolves on the host's stream runs k_mark ahead of the resolve (the visibility history, on the
 camera lane): a frame kernel like the others, one launch per such frame; the GBuffer-write pass of bench.py's `roofline` counts its time
 with the resolve's (ZR_PASS_RESOLVE).
@@ -59,6 +60,11 @@ def short(name):
         if n.startswith(base) and base != "k_calib":
             n = base
     return n
+
+
+def n_frames(a):
+    """frames of a run: every frame lights once behind its one-pixel pre-launch (a frame that keeps its camera pass runs no resolve)"""
+    return len(a.get("k_lighting", [])) // 2 or len(a.get("k_resolve_gbuffer", [])) or 1
 
 
 def counters(dirs):
@@ -151,10 +157,10 @@ out = {}
 for k in sorted(set(fetch) | set(write) | set(valu)):
     f, w, v = fetch.get(k, []), write.get(k, []), valu.get(k, [])
     mf, mw = (sum(f) / len(f) if f else 0.0), (sum(w) / len(w) if w else 0.0)
-    nfr = len(fetch.get("k_resolve_gbuffer", [])) or 1
+    nfr = n_frames(fetch)
     out[k] = {"FETCH_SIZE_KiB": mf, "WRITE_SIZE_KiB": mw, "hbm_bytes_per_launch": int((2 * mf + mw) * 1024),
               "launches_per_frame": round(len(f) / nfr, 3),
-              "hbm_bytes_per_frame": int((2 * sum(f) / nfr + sum(w) / (len(write.get("k_resolve_gbuffer", [])) or 1)) * 1024),
+              "hbm_bytes_per_frame": int((2 * sum(f) / nfr + sum(w) / (n_frames(write))) * 1024),
               "SQ_INSTS_VALU": (sum(v) / len(v) if v else None)}
     if k in issue:
         out[k]["issue"] = issue[k]
@@ -166,7 +172,7 @@ if "k_lighting" in out:
 
 
 def per_frame(a, scale):
-    frames = len(a.get("k_resolve_gbuffer", [])) or 1
+    frames = n_frames(a)
     return sum(sum(v) for k, v in a.items() if is_frame_kernel(k)) * scale / frames, frames
 
 

@@ -175,6 +175,7 @@ struct FrameCopy {
     bool overlay_dirty = false;          // G.overlay may hold skydome pixels of an earlier frame
     bool shadow_cleared = false;         // `shadow` already holds depth 1.0 (cleared by a lighting pass since it was last drawn into)
     uint64_t view_uploaded = 0;          // which version of the uniforms `view` holds
+    uint64_t g_gen = 0;                  // the run of equal inputs (zr_ctx::g_gen) G was last resolved in (0: never)
     // a census enqueued against this copy (zr_instance_coverage_async): the frame that writes it next waits for it
     hipEvent_t ev_ids = nullptr; bool ids_wait = false;
 };
@@ -223,7 +224,7 @@ struct zr_ctx {
     // vertices, meshlets, limits, the map's buffer or partition, the host's stream.  smap: the copy (fc[smap].shadow) that holds the
     // current map; a drawn pass targets the other one and flips it.  smap_key / smap_epoch: what that map was drawn from (smap_valid:
     // there is one).  shadow_keep: this frame keeps it (frame_begin).  shadow_draws: passes drawn so far (k_shadow_occlusion's retest turn).
-    uint64_t caster_epoch = 0, smap_epoch = 0, shadow_draws = 0;
+    uint64_t caster_epoch = 0, smap_epoch = 0, shadow_draws = 0, smap_frame = 0;      // smap_frame: the frame (frame_no) that drew the current map
     int smap = 0; bool smap_valid = false, shadow_keep = false;
     ZrPass smap_key;
     // Round 2 of the camera pass is kept the same way (zr_frame_host.cpp: camera_keepable, gbuffer_pass).  Round 1 draws the
@@ -241,6 +242,15 @@ struct zr_ctx {
     uint64_t camera_epoch = 0, cam_prev_epoch = 0, frame_cam_epoch = 0;
     bool cam_prev_valid = false, cam_same = false, r2_settled = false, round2_keep = false;
     ZrPass cam_prev_key;
+    // The camera pass is kept WHOLE, its GBuffer with it, one level further (zr_frame_host.cpp: frame_begin).  The lighting pass reads only
+    // the GBuffer planes and the frame's XkView; the planes depend on the camera pass's inputs and on what the resolve reads beyond them:
+    // surface_epoch, bumped (zr_surface_changed) by every texture update and by the winner planes coming or going (materials, draw
+    // records and the skydome change through the scene, which bumps camera_epoch).  g_gen counts the runs of frames whose camera block and
+    // two epochs are the same; FrameCopy::g_gen is the run a copy was last resolved in.  When both copies were resolved in this frame's run
+    // they are equal bit for bit, and camera_keep frames launch nothing of the camera pipeline: no cull, round, k_mark, k_plan or
+    // resolve, no statistics reset, nothing on the camera lane.  cam_draws: camera passes drawn so far (the visibility stamp's turn).
+    uint64_t surface_epoch = 0, surf_prev_epoch = 0, g_gen = 1, cam_draws = 0;
+    bool camera_keep = false, head_on_lane = false;      // head_on_lane: this kept frame's upload and one-pixel launch run on the camera lane (ZR_KEPT_HEAD_ON_LANE builds)
 
     XkUniformBufferMVP cam, shadow; XkView view; bool frame_valid = false;
     uint32_t debug_view = 0;
@@ -371,6 +381,7 @@ struct zr_ctx {
         bool moved = false;              // the frame resolved on the host's stream: ZR_PASS_RESOLVE is k_mark's time + the resolve's
         bool kept = false;               // the frame kept its shadow map: its shadow durations are 0, not the gap between two records
         bool kept_round2 = false;        // the frame kept round 2 of the camera pass: ZR_PASS_HIZ and ZR_PASS_GBUFFER2 are 0 likewise
+        bool kept_camera = false;        // the frame kept its whole camera pass: ZR_PASS_CULL_CAMERA, _GBUFFER and _RESOLVE are 0 as well
     } timed[EV_RING];
     uint64_t frame_no = 0; bool rendered = false;
     uint32_t timing_interval = 1; bool timing_now = true; uint64_t sample_no = 0;    // pass events every interval-th frame
@@ -397,6 +408,8 @@ static inline void zr_casters_changed(zr_ctx* c) { c->caster_epoch++; c->camera_
 // What the camera pass draws, how its work items are numbered or where its records go may have changed, the casters apart: the next
 // frame draws round 2 (see zr_ctx::camera_epoch).
 static inline void zr_camera_changed(zr_ctx* c) { c->camera_epoch++; }
+// What the resolve reads beyond the camera pass's inputs may have changed: the next two frames resolve again (see zr_ctx::surface_epoch).
+static inline void zr_surface_changed(zr_ctx* c) { c->surface_epoch++; }
 #define HIPCHK(c, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) \
     return zr_fail((c), ZR_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); } while (0)
 #define ARGCHK(c, cond) do { if (!(cond)) return zr_fail((c), ZR_ERR_ARG, "bad argument: " #cond); } while (0)

@@ -12,7 +12,7 @@ __global__ __launch_bounds__(256) void k_frame_begin(uint32_t* __restrict__ stat
                                                      uint32_t* __restrict__ n_vis_camera, uint32_t rebuild_lists)
 {
     const uint32_t i0 = blockIdx.x * 256u + threadIdx.x;
-    if (blockIdx.x == 0) for (uint32_t i = threadIdx.x; i < n_stats; i += 256u) stats[i] = 0u;
+    if (blockIdx.x == 0 && stats) for (uint32_t i = threadIdx.x; i < n_stats; i += 256u) stats[i] = 0u;      // (null: the frame keeps its camera pass and that pass's statistics)
     // the passes' work lists (k_cull_instances) stand while camera / light matrices and scene do: only a list about to be rebuilt starts from 0
     // (the shadow pass's length sits in the shadow pipeline's own block and is reset on that pipeline's stream, see shadow_pass)
     if (blockIdx.x == 0 && threadIdx.x == 1u && (rebuild_lists & 2u)) *n_vis_camera = 0u;
@@ -62,7 +62,7 @@ void zr_launch_frame_begin(ZrDevStats* stats, const XkView* view_src_pinned, XkV
 {
     static_assert(sizeof(XkView) % 4 == 0 && offsetof(ZrDevStats, overflow_sticky) % 4 == 0, "dword copies");
     hipLaunchKernelGGL(k_frame_begin, dim3(view_src_pinned ? 16 : 1), dim3(256), 0, s, (uint32_t*)stats, (uint32_t)(offsetof(ZrDevStats, overflow_sticky) / 4),
-                       (const uint32_t*)view_src_pinned, (uint32_t*)view_dst, (uint32_t)(sizeof(XkView) / 4), &stats->n_vis_work[1], rebuild_lists);
+                       (const uint32_t*)view_src_pinned, (uint32_t*)view_dst, (uint32_t)(sizeof(XkView) / 4), stats ? &stats->n_vis_work[1] : nullptr, stats ? rebuild_lists : 0u);
 }
 void zr_launch_fill32(uint32_t* p, uint32_t v, size_t n, hipStream_t s)
 {

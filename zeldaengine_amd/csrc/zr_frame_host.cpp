@@ -16,6 +16,12 @@
 #ifndef ZR_EV_CAM_AHEAD_OF_PLAN
 #define ZR_EV_CAM_AHEAD_OF_PLAN 0
 #endif
+// ... and where the head of a zr_render frame that keeps camera pass and shadow map runs - the uniform upload and the one-pixel launch, some
+// 15 us of latency ahead of k_lighting: 0 in series on the host's stream, 1 on the idle camera lane beside the previous frame's lighting
+// pass, at the price of one event crossing (DESIGN.md section 7 has both, measured: 17 470 / 19 240 Mpixel/s).
+#ifndef ZR_KEPT_HEAD_ON_LANE
+#define ZR_KEPT_HEAD_ON_LANE 1
+#endif
 
 // ------------------------------------------------------------------------------------------------ uniforms
 
@@ -131,6 +137,7 @@ int set_winner_planes(zr_ctx* c, bool forward, bool id_capture, const char* what
         }
         F.G.prim = (forward || id_capture) ? F.prim_plane : nullptr;
     }
+    zr_surface_changed(c);      // (a copy resolved without the plane does not hold it: no kept GBuffer across the swap)
     return ZR_OK;
 }
 
@@ -301,6 +308,33 @@ static void raster(zr_ctx* c, const ZrPass& P, hipStream_t s, int stage)
                             c->stile_world >= 4u ? c->shadow_blocks / 2u : c->shadow_blocks, s, c->d_slow0, c->slow0_cap, c->d_sowned, c->sn_tiles, stage);
 }
 
+// What a frame keeps of the frame before, decided once its two pass blocks are built (frame_begin) and before anything is enqueued;
+// rebuild: the work lists this frame rebuilds, lane: its camera pipeline would run on the library's own stream.
+static void keep_decisions(zr_ctx* c, uint32_t rebuild, bool lane)
+{
+    // the shadow pass's map as a whole while its block stands, no caster changed and the map stays where it is (shadow_pass)
+    c->shadow_keep = shadow_keepable(c) && c->smap_valid && c->smap_epoch == c->caster_epoch && memcmp(&c->smap_key, &c->pass[0], sizeof(ZrPass)) == 0;
+    // round 2 of the camera pass while the frame enqueued last drew or kept it from this very block, on a history of this very block, and
+    // nothing the pass draws changed since (gbuffer_pass)
+    c->frame_cam_epoch = c->camera_epoch;
+    c->cam_same = c->cam_prev_valid && c->cam_prev_epoch == c->camera_epoch && memcmp(&c->cam_prev_key, &c->pass[1], sizeof(ZrPass)) == 0;
+    c->round2_keep = camera_keepable(c) && c->cam_same && c->r2_settled;
+    // the camera pass as a whole, GBuffer included, while beyond that nothing the resolve reads changed (surface_epoch) and both copies
+    // of the GBuffer were resolved from these very inputs (g_gen: which run of equal inputs this frame belongs to): after two drawn frames
+    // of one run the copies are the same bit for bit, and the frame lights its parity's copy.  Not with a skydome or while a copy still
+    // waits for its overlay wipe (the sky key plane is single-buffered, see resolve_on_host_lane).  Such a frame enqueues nothing of the
+    // camera pipeline and touches nothing of the lane's.
+    if (!c->cam_same || c->surf_prev_epoch != c->surface_epoch) c->g_gen++;
+    c->surf_prev_epoch = c->surface_epoch;
+    const bool settled = c->round2_keep && !(rebuild & 2u) && c->vis_history && c->plan_valid && c->pass[1].n_work != 0 && !(c->cfg.flags & ZR_FLAG_NO_HIZ);
+    const bool copies = c->fc[0].g_gen == c->g_gen && c->fc[1].g_gen == c->g_gen && !c->fc[0].overlay_dirty && !c->fc[1].overlay_dirty;
+    c->camera_keep = settled && copies && !(c->sky_set && c->sky_enabled);
+    // Its head - upload and one-pixel launch - runs on the idle lane where zr_render keeps the map too (ZR_KEPT_HEAD_ON_LANE).  The one-pixel
+    // launch reads the map, and the lane has waited for the end of frame_no - 2 only: the map must have been drawn by that frame or an
+    // earlier one (a map drawn by the frame before, on the host's stream, is behind nothing the lane has waited for).
+    c->head_on_lane = ZR_KEPT_HEAD_ON_LANE && c->camera_keep && c->in_render && c->shadow_keep && lane && c->smap_frame + 2 <= c->frame_no;
+}
+
 // The frame in three stages so that a multi-GPU host can put collectives between them (zeldaengine_amd/dist.py):
 //   zr_render_shadow    shadow pass (ZE:3239-3393) of this rank's share of the instances
 //   zr_render_gbuffer   deferred-scene pass (ZE:3417-3480): cull + bin + raster + resolve of the owned tiles
@@ -323,27 +357,6 @@ static int frame_begin(zr_ctx* c, hipStream_t s)
     if (c->id_capture) { rc = ids_prepare(c); if (rc) return rc; }
     c->fcur = (int)(c->frame_no & 1u);
     FrameCopy& F = c->fc[c->fcur];
-    // (two lanes: this frame's copies of the double-buffered resources were last used two frames ago, on the host's stream: read by the
-    // lighting pass, and before it the keys reset and the GBuffer written by the resolve where that ran there.  Nothing else ties the lanes
-    // together here: the shadow pipeline and a host-lane resolve keep statistics of their own)
-    if (s != c->stream && c->frame_no >= 2) HIPCHK(c, hipStreamWaitEvent(s, c->ev_end[(c->frame_no - 2) % zr_ctx::END_RING], 0));
-    // Consecutive camera pipelines share the triangle records, the plan and the camera lane's statistics (the key buffer is one of a pair,
-    // like F), and are ordered by running on ONE stream.  A frame on the lane that follows a frame of the staged entry points (its camera
-    // pipeline ran on the host's stream) waits for that frame's end instead.  The other way round the host's stream has waited for ev_cam
-    // before that frame's lighting pass: the whole lane, k_plan included - unless that frame resolved on the host's stream, whose ev_cam
-    // sits ahead of k_plan; then this frame's camera pipeline, if it runs on the host's stream, waits for the lane's end here.
-    if (s != c->stream && c->frame_no >= 1 && c->gbuf_s && c->gbuf_s != s)
-        HIPCHK(c, hipStreamWaitEvent(s, c->ev_end[(c->frame_no - 1) % zr_ctx::END_RING], 0));
-    if (c->plan_behind_cam && s == c->stream && c->cam_s) { HIPCHK(c, hipEventRecord(c->ev_lane, c->cam_s)); HIPCHK(c, hipStreamWaitEvent(s, c->ev_lane, 0)); }
-    c->plan_behind_cam = false;
-    // ... and by an identity census enqueued against them since (zr_instance_coverage_async, on the host's stream)
-    if (F.ids_wait) { if (s != c->stream) HIPCHK(c, hipStreamWaitEvent(s, F.ev_ids, 0)); F.ids_wait = false; }
-    // this frame's draw table; the updates since the last frame of this parity go into its planes and sets, s behind the last texture update
-    rc = zr_update_frame(c, s, c->fcur);
-    if (rc) return rc;
-    c->timing_now = c->timing_interval != 0 && c->frame_no % c->timing_interval == 0;     // pass events cost ~6 us of stream bubble each
-    if (zr_ctx::TimedFrame* T = c->timed_frame()) HIPCHK(c, hipEventRecord(T->ev[zr_ctx::EV_BEGIN], s));
-    if (c->view_dirty) { c->view_version++; c->view_dirty = false; }
     // the frame's two geometry passes; a pass's work list on the device is rebuilt only when its block or the scene changed
     uint32_t rebuild = 0;
     for (int slot = 0; slot < 2; ++slot) {
@@ -355,13 +368,30 @@ static int frame_begin(zr_ctx* c, hipStream_t s)
         // (the list counts as standing only once its k_cull_instances has been enqueued: shadow_pass / gbuffer_pass set list_valid)
         if (P.use_worklist && P.n_work != 0 && !c->list_reuse[slot]) { rebuild |= 1u << slot; c->list_key[slot] = P; c->list_valid[slot] = false; }
     }
-    // ... and the shadow pass's map as a whole while, beyond that, no caster changed and the map stays where it is (shadow_pass)
-    c->shadow_keep = shadow_keepable(c) && c->smap_valid && c->smap_epoch == c->caster_epoch && memcmp(&c->smap_key, &c->pass[0], sizeof(ZrPass)) == 0;
-    // ... and round 2 of the camera pass while the frame enqueued last drew or kept it from this very block, on a history of this very
-    // block, and nothing the pass draws changed since (gbuffer_pass)
-    c->frame_cam_epoch = c->camera_epoch;
-    c->cam_same = c->cam_prev_valid && c->cam_prev_epoch == c->camera_epoch && memcmp(&c->cam_prev_key, &c->pass[1], sizeof(ZrPass)) == 0;
-    c->round2_keep = camera_keepable(c) && c->cam_same && c->r2_settled;
+    keep_decisions(c, rebuild, s != c->stream);
+    if (c->camera_keep && !c->head_on_lane) s = c->stream;
+    // (two lanes: this frame's copies of the double-buffered resources were last used two frames ago, on the host's stream: read by the
+    // lighting pass, and before it the keys reset and the GBuffer written by the resolve where that ran there.  Nothing else ties the lanes
+    // together here: the shadow pipeline and a host-lane resolve keep statistics of their own)
+    if (s != c->stream && c->frame_no >= 2) HIPCHK(c, hipStreamWaitEvent(s, c->ev_end[(c->frame_no - 2) % zr_ctx::END_RING], 0));
+    // Consecutive camera pipelines share the triangle records, the plan and the camera lane's statistics (the key buffer is one of a pair,
+    // like F), and are ordered by running on ONE stream.  A frame on the lane that follows a frame of the staged entry points (its camera
+    // pipeline ran on the host's stream) waits for that frame's end instead.  The other way round the host's stream has waited for ev_cam
+    // before that frame's lighting pass: the whole lane, k_plan included - unless that frame resolved on the host's stream, whose ev_cam
+    // sits ahead of k_plan; then this frame's camera pipeline, if it runs on the host's stream, waits for the lane's end here.
+    if (s != c->stream && c->frame_no >= 1 && c->gbuf_s && c->gbuf_s != s)
+        HIPCHK(c, hipStreamWaitEvent(s, c->ev_end[(c->frame_no - 1) % zr_ctx::END_RING], 0));
+    // (a frame that keeps its camera pass touches nothing of the lane's: the wait, and the census's below, are left to the next drawn frame)
+    if (!c->camera_keep && c->plan_behind_cam && s == c->stream && c->cam_s) { HIPCHK(c, hipEventRecord(c->ev_lane, c->cam_s)); HIPCHK(c, hipStreamWaitEvent(s, c->ev_lane, 0)); }
+    if (!c->camera_keep) c->plan_behind_cam = false;
+    // ... and by an identity census enqueued against them since (zr_instance_coverage_async, on the host's stream)
+    if (F.ids_wait && !c->camera_keep) { if (s != c->stream) HIPCHK(c, hipStreamWaitEvent(s, F.ev_ids, 0)); F.ids_wait = false; }
+    // this frame's draw table; the updates since the last frame of this parity go into its planes and sets, s behind the last texture update
+    rc = zr_update_frame(c, s, c->fcur);
+    if (rc) return rc;
+    c->timing_now = c->timing_interval != 0 && c->frame_no % c->timing_interval == 0;     // pass events cost ~6 us of stream bubble each
+    if (zr_ctx::TimedFrame* T = c->timed_frame()) HIPCHK(c, hipEventRecord(T->ev[zr_ctx::EV_BEGIN], s));
+    if (c->view_dirty) { c->view_version++; c->view_dirty = false; }
     const XkView* src = nullptr;
     uint32_t k = 0;
     if (F.view_uploaded != c->view_version) {        // pinned ring slot: reused only after the kernel that read it last has run
@@ -374,7 +404,8 @@ static int frame_begin(zr_ctx* c, hipStream_t s)
     // zeroes the camera lane's statistics (the sticky overflow latch survives) and - when the camera list is rebuilt - its length; uploads
     // XkView.  The SHADOW list's length lives in the shadow pipeline's block and is reset on that pipeline's own stream (shadow_pass):
     // the previous frame's shadow pipeline may still be walking it while this kernel runs on the camera lane.
-    zr_launch_frame_begin(c->d_stats, src, F.view, rebuild & 2u, s);
+    // (a frame that keeps its camera pass keeps that pass's statistics: an upload, or nothing)
+    if (!c->camera_keep || src) zr_launch_frame_begin(c->camera_keep ? nullptr : c->d_stats, src, F.view, c->camera_keep ? 0u : rebuild & 2u, s);
     if (src) { HIPCHK(c, hipEventRecord(c->view_ev[k], s)); F.view_uploaded = c->view_version; }
     return ZR_OK;
 }
@@ -428,7 +459,7 @@ static int shadow_pass(zr_ctx* c, hipStream_t s)
     if (ev) HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_SHADOW], s));
     HIPCHK(c, hipGetLastError());
     c->shadow_draws++;
-    c->smap_key = P; c->smap_epoch = c->caster_epoch; c->smap_valid = true;
+    c->smap_key = P; c->smap_epoch = c->caster_epoch; c->smap_valid = true; c->smap_frame = c->frame_no;
     return ZR_OK;
 }
 
@@ -449,7 +480,17 @@ static int gbuffer_pass(zr_ctx* c, hipStream_t s, bool defer_resolve = false)
 {
     zr_ctx::TimedFrame* const T = c->timed_frame();
     hipEvent_t* const ev = T ? T->ev : nullptr;
-    if (ev) HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_CAMERA], s));
+    if (ev) { T->kept_camera = c->camera_keep; HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_CAMERA], s)); }
+    if (c->camera_keep) {
+        // The camera pass kept whole (frame_begin): both GBuffer copies, the key buffers, the visibility history and its stamp, the plan,
+        // the statistics block and cov_block stay as the last drawn frame left them, and nothing is launched.  A timed frame records the
+        // pass's events all the same, on the stream that lights it, and counts 0 for the cull, both rounds, Hi-Z and the resolve.
+        if (ev) {
+            T->kept_round2 = true; T->moved = false;
+            for (int e : { zr_ctx::EV_CULL, zr_ctx::EV_ROUND1, zr_ctx::EV_HIZ, zr_ctx::EV_ROUND2, zr_ctx::EV_RESOLVE }) HIPCHK(c, hipEventRecord(ev[e], s));
+        }
+        return ZR_OK;
+    }
     ZrPass P = c->pass[1];             // (built by frame_begin; the overlay fields are set below)
     c->gbuf_s = s;
     c->last_work[1] = P.n_work;
@@ -463,7 +504,8 @@ static int gbuffer_pass(zr_ctx* c, hipStream_t s, bool defer_resolve = false)
     Z.pxrect = hiz_on ? c->d_pxrect : nullptr; Z.zmin = hiz_on ? c->d_zmin : nullptr;
     Z.vis_prev = c->d_visflag[c->vis_cur ^ 1]; Z.vis_now = hiz_on ? c->d_visflag[c->vis_cur] : nullptr;
     // visibility marks are frame stamps (1 .. 255): the resolve writes this frame's, the culls compare with last frame's - nothing is cleared
-    const uint32_t vis_mark = 1u + (uint32_t)(c->frame_no % 255u);
+    // (a stamp per pass DRAWN: a rest of any length leaves the stamps as an uninterrupted run of drawn frames would)
+    const uint32_t vis_mark = 1u + (uint32_t)(c->cam_draws % 255u);
     Z.vis_stamp = c->vis_mark_prev;
     Z.phase = 0;
     static_assert(ZR_TILE == 32, "the triangle-binned camera pass is written for 32 x 32 tiles");
@@ -516,11 +558,11 @@ static int gbuffer_pass(zr_ctx* c, hipStream_t s, bool defer_resolve = false)
         HIPCHK(c, hipEventRecord(c->ev_cam, s)); c->camera_on_lane = true; c->plan_behind_cam = true;
     } else {
         zr_launch_resolve_gbuffer(P, c->d_objs, c->d_owned, c->n_owned, c->d_vis[c->fcur], c->fc[c->fcur].G, c->d_lut, c->d_unorm_lut, Z.vis_now, c->d_stats, s, vis_mark);
-        c->cov_block = c->d_stats;
+        c->cov_block = c->d_stats; c->fc[c->fcur].g_gen = c->g_gen;
         if (ev) HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_RESOLVE], s));
         if (ZR_EV_CAM_AHEAD_OF_PLAN && c->in_render && s != c->stream) { HIPCHK(c, hipEventRecord(c->ev_cam, s)); c->camera_on_lane = true; c->plan_behind_cam = true; }
     }
-    c->vis_mark_prev = vis_mark;
+    c->vis_mark_prev = vis_mark; c->cam_draws++;
     if (P.n_work != 0) {     // the next frame's buckets, from this frame's counts: nothing of this frame waits for it
         zr_launch_plan(c->tb, c->d_owned, c->n_owned, c->d_stats, false, c->bucket_pct, s, keep ? ZR_PLAN_KEPT_ROUND2 : two ? ZR_PLAN_DREW_ROUND2 : ZR_PLAN_ONE_ROUND);
         c->plan_valid = true; c->plan_two_round = two;
@@ -557,6 +599,7 @@ extern "C" int zr_render_gbuffer(zr_ctx* c)
     });
 }
 
+static int empty_pixel_pass(zr_ctx* c, hipStream_t s);
 // Both geometry passes of a frame.  Two lanes (unless ZR_FLAG_SERIAL_PASSES): the camera pipeline on cam_s; the shadow pipeline on
 // the host's stream, where the lighting pass will follow.  The next frame's camera pipeline starts as soon as this one's is
 // through, next to this frame's lighting; its shadow pipeline follows the lighting.  A frame that keeps its shadow map has no shadow
@@ -577,9 +620,13 @@ static int geometry_passes(zr_ctx* c)
         rc = shadow_pass(c, c->stream);
         if (rc == ZR_OK && !c->in_render) HIPCHK(c, hipEventRecord(c->ev_join, c->stream));      // (zr_stream_wait_shadow: a host that puts a collective behind the shadow pass)
         const bool defer = resolve_on_host_lane(c, lanes);
-        if (rc == ZR_OK) rc = gbuffer_pass(c, c->cam_s, defer);
+        if (rc == ZR_OK) rc = gbuffer_pass(c, c->camera_keep ? c->stream : c->cam_s, defer);      // (kept whole: its events only, where the frame is lit)
         // (a deferred resolve: ev_cam is already recorded, behind k_mark and ahead of k_plan - the lighting lane does not wait for the plan)
-        if (rc == ZR_OK && !c->camera_on_lane) { HIPCHK(c, hipEventRecord(c->ev_cam, c->cam_s)); c->camera_on_lane = true; }
+        if (rc == ZR_OK && c->head_on_lane) {      // (ZR_KEPT_HEAD_ON_LANE: the one-pixel launch behind the upload, the host's stream behind both)
+            rc = empty_pixel_pass(c, c->cam_s);
+            if (rc == ZR_OK) { HIPCHK(c, hipEventRecord(c->ev_cam, c->cam_s)); c->camera_on_lane = true; }
+        }
+        if (rc == ZR_OK && !c->camera_on_lane && !c->camera_keep) { HIPCHK(c, hipEventRecord(c->ev_cam, c->cam_s)); c->camera_on_lane = true; }
     } else {
         rc = frame_begin(c, c->stream);
         if (rc != ZR_OK) return rc;
@@ -647,7 +694,7 @@ static int deferred_resolve(zr_ctx* c, hipStream_t s)
     if (ev) HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_HOST_RESOLVE], s));
     zr_launch_resolve_gbuffer(c->resolve_P, c->d_objs, c->d_owned, c->n_owned, c->d_vis[c->fcur], c->fc[c->fcur].G, c->d_lut, c->d_unorm_lut, nullptr, tally, s, c->resolve_mark);
     if (ev) HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_RESOLVE], s));
-    c->cov_block = tally; c->resolve_deferred = false;
+    c->cov_block = tally; c->resolve_deferred = false; c->fc[c->fcur].g_gen = c->g_gen;
     HIPCHK(c, hipGetLastError());
     return ZR_OK;
 }
@@ -694,7 +741,7 @@ extern "C" int zr_render_lighting(zr_ctx* c)
         // uniforms the empty-pixel pass below reads (the shadow pipeline before it needed nothing of them and did not wait).
         if (c->camera_on_lane) HIPCHK(c, hipStreamWaitEvent(ls, c->ev_cam, 0));
         int rc = c->resolve_deferred ? deferred_resolve(c, ls) : ZR_OK;
-        if (rc == ZR_OK) rc = empty_pixel_pass(c, ls); // the shadow map (possibly reduced over ranks by the host) is final only now
+        if (rc == ZR_OK && !c->head_on_lane) rc = empty_pixel_pass(c, ls); // the shadow map (possibly reduced over ranks by the host) is final only now
         if (rc == ZR_OK) rc = lighting_pass(c, ls);
         return rc;
     });
@@ -708,6 +755,9 @@ extern "C" int zr_render_lighting(zr_ctx* c)
 // the finished frame, as before.  ZR_FLAG_SERIAL_PASSES keeps everything on the one stream, as the staged entry points do.
 // A frame that keeps its shadow map resolves on the host's stream (resolve_on_host_lane): camera lane ... -> k_tile -> k_mark -> ev_cam
 // -> k_plan, host's stream wait -> k_resolve_gbuffer -> one-pixel launch -> k_lighting -> ev_end.
+// A frame that keeps its whole camera pass (frame_begin: camera_keep) has no camera pipeline: host's stream upload -> [shadow pipeline] ->
+// one-pixel launch -> k_lighting -> ev_end, over the GBuffer copy of its parity as the last two drawn frames left both; where it keeps its
+// map too (and has kept it for a frame), upload -> one-pixel launch -> ev_cam run on the lane beside the previous frame's k_lighting, and the host's stream waits for ev_cam.
 extern "C" int zr_render(zr_ctx* c)
 {
     if (!c) return ZR_ERR_ARG;

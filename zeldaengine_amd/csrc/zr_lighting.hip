@@ -6,10 +6,11 @@
 
 // BaseLighting.frag:147-254 for every pixel of the owned tiles (the full-screen quad of ZE:3531-3540)
 template <bool LIGHT_LIST, bool BACKGROUND, int TB, int PPT>      // PPT: pixels per thread, 4 or 1 (as in k_resolve_gbuffer)
-// (compiled for exactly ZR_LIGHT_WAVES = 5 waves per SIMD: 96 VGPRs and 24 bytes of scratch.  Left to itself the allocator takes 127 registers.
-// Rounds 4 - 5 ran it at 4 waves (97 VGPRs): beside a camera lane that filled the whole period, a fifth wave cost that lane more than it gave
-// this pass.  Since the camera lane lost its scans and index passes (round 6) the frame's period is THIS lane's, and the fifth wave pays:
-// 4 / 5 / 6 waves: 5 548 / 5 670 / 5 420 Mpixel/s)
+// (compiled for exactly ZR_LIGHT_WAVES waves per SIMD; left to itself the allocator takes 127 registers.  Rounds 4 - 5 ran it at 4 waves
+// (97 VGPRs): beside a camera lane that filled the whole period, a fifth wave cost that lane more than it gave this pass.  With that lane's
+// scans and index passes gone (round 6) the frame's period was THIS lane's, and the fifth wave paid: 4 / 5 / 6 waves 5 548 / 5 670 / 5 420
+// Mpixel/s.  On a frame that keeps its camera pass the kernel runs alone, and a sixth pays: 16 770 / 17 470 / 19 363, the moving-camera
+// loop, where the lane is still there, the same within its margin)
 __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(ZR_LIGHT_WAVES, ZR_LIGHT_WAVES))) void k_lighting(ZrLightParams L, const XkView* __restrict__ view,
                                                   const uint32_t* __restrict__ owned_tiles, GBufferPtrs G,
                                                   const float* __restrict__ shadowmap, CubeDesc C,

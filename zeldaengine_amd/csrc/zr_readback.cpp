@@ -89,6 +89,7 @@ extern "C" int zr_get_pass_times_avg(zr_ctx* c, uint32_t last_n, float ms[ZR_PAS
             // (a frame that kept its shadow map ran no shadow pipeline: exactly 0, not the gap between two back-to-back records)
             if (T.kept) t[ZR_PASS_CULL_SHADOW] = t[ZR_PASS_SHADOW] = 0.0f;
             if (T.kept_round2) t[ZR_PASS_HIZ] = t[ZR_PASS_GBUFFER2] = 0.0f;      // (likewise: no Hi-Z build, no k_select, no second round)
+            if (T.kept_camera) t[ZR_PASS_CULL_CAMERA] = t[ZR_PASS_GBUFFER] = t[ZR_PASS_RESOLVE] = 0.0f;      // (the whole camera pass kept: nothing of it ran)
             for (int i = 0; i < ZR_PASS_COUNT; ++i) acc[i] += t[i];
         }
         for (int i = 0; i < ZR_PASS_COUNT; ++i) ms[i] = (float)(acc[i] / last_n);

@@ -81,12 +81,13 @@ int zr_update_tex_begin(zr_ctx* c, hipStream_t x)
 }
 
 // ... second half, behind the kernel: the next frame's first stream waits for it.  No list, plan, history or shadow map depends on a
-// texel: nothing else is invalidated.
+// texel: of what the frames keep, only the GBuffer is invalidated.
 int zr_update_tex_end(zr_ctx* c, hipStream_t x)
 {
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->upd.ev_tex, x));
     c->upd.tex_s = x; c->upd.tex_wait = true;
+    zr_surface_changed(c);      // (the GBuffer does: the next two frames resolve again, whatever else they keep)
     return ZR_OK;
 }
 
