@@ -1,4 +1,4 @@
-"""The whole camera pass and its GBuffer are kept while camera and scene stand still (csrc/zr_frame_host.cpp: frame_begin, camera_keep).
+"""The whole camera pass and its GBuffer are kept while camera and scene stand still (csrc/zr_frame_plan.h: ZrFramePlan::camera_keep).
 
 The lighting pass reads the GBuffer planes and the frame's uniforms, nothing else of the camera pipeline.  When this frame's camera-pass
 inputs and everything the resolve reads beyond them are the last two frames', both GBuffer copies already hold this frame's planes:

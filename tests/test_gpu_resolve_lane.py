@@ -1,4 +1,4 @@
-"""The resolve's lane (zr_render, csrc/zr_frame_host.cpp: resolve_on_host_lane).
+"""The resolve's lane (zr_render, csrc/zr_frame_plan.h: ZrFramePlan::resolve_deferred).
 
 A zr_render frame that keeps its shadow map leaves k_resolve_gbuffer to the host's stream, ahead of its lighting pass, next to the NEXT
 frame's camera lane; the camera lane marks the visibility history itself (k_mark) and the key buffer is one of a pair.  Every other frame -

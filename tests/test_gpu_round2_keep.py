@@ -1,4 +1,4 @@
-"""Round 2 of the camera pass is kept while camera and scene stand still (zr_render, csrc/zr_frame_host.cpp: gbuffer_pass).
+"""Round 2 of the camera pass is kept while camera and scene stand still (zr_render, csrc/zr_frame_plan.h: ZrFramePlan::rounds; csrc/zr_frame_host.cpp: gbuffer_pass).
 
 Round 1 draws what owned a pixel of the previous frame; when this frame's camera-pass inputs are that frame's bit for bit, nothing else
 can own one now, and the frame enqueues no Hi-Z build, no k_select and no second round.  The observable is the pass time: a frame that

@@ -62,7 +62,7 @@ ZrTilePartition zr_partition(uint32_t tiles_x, uint32_t tiles_y, uint32_t world,
 
 // Schedule constants that are re-measured whenever the balance of the two lanes changes ("The schedule"): the camera lane's
 // stream priority (0 lowest, 1 normal, 2 highest) and k_tile's persistent grid in workgroups per CU.  (The third, ZR_EV_CAM_AHEAD_OF_PLAN,
-// is zr_frame_host.cpp's.)
+// is zr_frame_plan.h's.)
 #ifndef ZR_CAM_PRIORITY
 #define ZR_CAM_PRIORITY 0
 #endif

@@ -13,6 +13,7 @@
 #include <utility>
 #include <vector>
 
+#include "zr_frame_plan.h"
 #include "zr_ids.h"
 #include "zr_meshlet.h"
 #include "zr_types.h"
@@ -175,7 +176,7 @@ struct FrameCopy {
     bool overlay_dirty = false;          // G.overlay may hold skydome pixels of an earlier frame
     bool shadow_cleared = false;         // `shadow` already holds depth 1.0 (cleared by a lighting pass since it was last drawn into)
     uint64_t view_uploaded = 0;          // which version of the uniforms `view` holds
-    uint64_t g_gen = 0;                  // the run of equal inputs (zr_ctx::g_gen) G was last resolved in (0: never)
+    uint64_t g_gen = 0;                  // the run of equal inputs (ZrFramePlan::g_gen) G was last resolved in (0: never)
     // a census enqueued against this copy (zr_instance_coverage_async): the frame that writes it next waits for it
     hipEvent_t ev_ids = nullptr; bool ids_wait = false;
 };
@@ -214,43 +215,23 @@ struct zr_ctx {
         // d_srgb_thr: the 256 sRGB encode thresholds (zr_srgb.h).  Made at the first update.
         hipEvent_t ev_tex = nullptr; hipStream_t tex_s = nullptr; bool tex_wait = false; float* d_srgb_thr = nullptr;
     } upd;
-    // this frame's two geometry passes (0 shadow, 1 camera), built at frame begin; the passes' work lists (k_cull_instances) are kept
-    // while the pass block and the scene stand still: list_key = the block the list on the device was built from
-    ZrPass pass[2]; bool pass_live[2] = { false, false }, list_reuse[2] = { false, false }, list_valid[2] = { false, false };
-    ZrPass list_key[2];
-    // The shadow MAP is kept as well, one level up: while the shadow pass's block, the casters (caster_epoch) and the map's buffer stand
-    // still, the map of the last drawn pass is the map this frame would draw, bit for bit, and shadow_pass launches nothing.
-    // caster_epoch: bumped (zr_casters_changed) by every call that can change what the shadow pass would draw or where - objects, instances,
-    // vertices, meshlets, limits, the map's buffer or partition, the host's stream.  smap: the copy (fc[smap].shadow) that holds the
-    // current map; a drawn pass targets the other one and flips it.  smap_key / smap_epoch: what that map was drawn from (smap_valid:
-    // there is one).  shadow_keep: this frame keeps it (frame_begin).  shadow_draws: passes drawn so far (k_shadow_occlusion's retest turn).
-    uint64_t caster_epoch = 0, smap_epoch = 0, shadow_draws = 0, smap_frame = 0;      // smap_frame: the frame (frame_no) that drew the current map
-    int smap = 0; bool smap_valid = false, shadow_keep = false;
-    ZrPass smap_key;
-    // Round 2 of the camera pass is kept the same way (zr_frame_host.cpp: camera_keepable, gbuffer_pass).  Round 1 draws the
-    // meshlet-instances that owned a pixel of the previous frame's final key buffer; when this frame's camera-pass inputs are that
-    // frame's bit for bit, whatever owned no pixel then owns none now: the key buffer behind round 1 is already the frame's, and the
-    // frame enqueues no Hi-Z build, no k_select and no second round.  camera_epoch: bumped (zr_camera_changed, and with every
-    // zr_casters_changed: a caster is drawn by the camera too) by every call that can change what the camera pass draws, its work
-    // numbering or its record layout.  cam_prev_key / cam_prev_epoch: the camera block and the epoch of the frame enqueued last
-    // (cam_prev_valid: it left a visibility history); cam_same: this frame's are the same (frame_begin; frame_cam_epoch: the epoch it
-    // began at).  r2_settled: the frame enqueued last drew both rounds or kept round 2 AND was itself cam_same, so the history its
-    // round 1 went by was the standing view's own - only then are round 2's statistics and per-tile counts, which a keeping frame
-    // reports and plans with, those a drawn round 2 would give now (the frame after a camera cut draws round 2 from a stale history: tens
-    // of millions of records at config 4 where the settled frame has a few; the frame after it draws both rounds once more, and the
-    // rest of the rest keeps).  round2_keep: this frame may keep (gbuffer_pass also wants a two-round frame with a usable plan).
-    uint64_t camera_epoch = 0, cam_prev_epoch = 0, frame_cam_epoch = 0;
-    bool cam_prev_valid = false, cam_same = false, r2_settled = false, round2_keep = false;
-    ZrPass cam_prev_key;
-    // The camera pass is kept WHOLE, its GBuffer with it, one level further (zr_frame_host.cpp: frame_begin).  The lighting pass reads only
-    // the GBuffer planes and the frame's XkView; the planes depend on the camera pass's inputs and on what the resolve reads beyond them:
-    // surface_epoch, bumped (zr_surface_changed) by every texture update and by the winner planes coming or going (materials, draw
-    // records and the skydome change through the scene, which bumps camera_epoch).  g_gen counts the runs of frames whose camera block and
-    // two epochs are the same; FrameCopy::g_gen is the run a copy was last resolved in.  When both copies were resolved in this frame's run
-    // they are equal bit for bit, and camera_keep frames launch nothing of the camera pipeline: no cull, round, k_mark, k_plan or
-    // resolve, no statistics reset, nothing on the camera lane.  cam_draws: camera passes drawn so far (the visibility stamp's turn).
-    uint64_t surface_epoch = 0, surf_prev_epoch = 0, g_gen = 1, cam_draws = 0;
-    bool camera_keep = false, head_on_lane = false;      // head_on_lane: this kept frame's upload and one-pixel launch run on the camera lane (ZR_KEPT_HEAD_ON_LANE builds)
+    // The frame schedule (zr_frame_plan.h): what the frame being enqueued does - decided once, at frame begin, from `facts`; the staged
+    // entry points span three calls - and what the frames enqueued so far left behind.  The pass blocks the carry's validity bits speak
+    // of live here: list_key[] = the block each pass's work list on the device was built from, smap_key = the block the current shadow
+    // map was drawn from, cam_prev_key = the camera block of the frame enqueued last.
+    ZrFrameFacts facts; ZrFramePlan plan; ZrFrameCarry carry;
+    ZrPass list_key[2] = {}, smap_key = {}, cam_prev_key = {};
+    // this frame's two geometry passes (0 shadow, 1 camera), built at frame begin
+    ZrPass pass[2]; bool pass_live[2] = { false, false };
+    // The epochs the keeps go by.  caster_epoch: bumped (zr_casters_changed) by every call that can change what the shadow pass would draw
+    // or where - objects, instances, vertices, meshlets, limits, the map's buffer or partition, the host's stream.  camera_epoch: bumped
+    // (zr_camera_changed, and with every zr_casters_changed: a caster is drawn by the camera too) by every call that can change what the
+    // camera pass draws, its work numbering or its record layout.  surface_epoch: bumped (zr_surface_changed) by what the resolve reads
+    // beyond that - every texture update, the winner planes coming or going.
+    uint64_t caster_epoch = 0, camera_epoch = 0, surface_epoch = 0;
+    // smap: the copy (fc[smap].shadow) that holds the current shadow map; a drawn pass targets the other one and flips it.  shadow_draws /
+    // cam_draws: passes drawn so far (k_shadow_occlusion's retest turn, the visibility stamp's turn).
+    int smap = 0; uint64_t shadow_draws = 0, cam_draws = 0;
 
     XkUniformBufferMVP cam, shadow; XkView view; bool frame_valid = false;
     uint32_t debug_view = 0;
@@ -280,7 +261,6 @@ struct zr_ctx {
     struct ShadowBins { uint32_t *tile_count = nullptr, *tile_offset = nullptr, *tile_cursor = nullptr, *chunk_offset = nullptr;
                         ZrBinEntry* bins = nullptr; uint4* chunk_tab = nullptr; } sb;
     uint32_t bucket_pct = 100;                              // zr_set_bucket_share: every planned bucket at that share of its size
-    bool plan_valid = false, plan_two_round = false;      // the record buckets' plan (k_plan): made at all / by a frame that drew two rounds
     ZrTriBins tb = {};                    // triangle-binned camera pass: selection list, records (as emitted / in tile order), slow list
     uint32_t chunk_capacity = 0;         // raster work units the chunk table holds: bin_capacity / ZR_CHUNK + tiles
     uint32_t n_inst_total = 0;
@@ -298,16 +278,11 @@ struct zr_ctx {
     // the current frame's copy - at stage 0 the one the frame enqueued last wrote - and fc[fcur ^ 1] the next frame's.  (The shadow map's
     // two copies live in fc[] too, but are picked by `smap`, not by the frame's parity.)
     FrameCopy fc[2]; int fcur = 0;
-    hipStream_t cam_s = nullptr; bool camera_on_lane = false;
-    hipStream_t gbuf_s = nullptr;        // the stream the last deferred-scene pass was enqueued on (frame_begin: a change of it is a wait)
-    bool in_render = false;
+    hipStream_t cam_s = nullptr;
     hipEvent_t ev_join = nullptr, ev_cam = nullptr;
-    // The resolve's lane (zr_frame_host.cpp: resolve_on_host_lane): a zr_render frame that keeps its shadow map leaves its resolve to the host's
-    // stream, ahead of its lighting pass; the camera lane marks the visibility history itself (k_mark) and goes on to the next frame.
-    // resolve_deferred: the frame being enqueued does so, resolve_P / resolve_mark what its resolve is launched with.  ev_cam then sits
-    // AHEAD of the lane's k_plan: plan_behind_cam says so to the next frame, which - if its camera pipeline runs on the host's stream -
-    // waits for the lane's end first (ev_lane, recorded only then).
-    bool resolve_deferred = false, plan_behind_cam = false; ZrPass resolve_P; uint32_t resolve_mark = 0;
+    // A resolve left to the host's stream (ZrFramePlan::resolve_deferred): what it is launched with.  ev_lane: the lane's end, recorded
+    // only where a frame waits for it (ZrFramePlan::wait_lane_end).
+    ZrPass resolve_P; uint32_t resolve_mark = 0;
     hipEvent_t ev_lane = nullptr;
     unsigned long long* d_sky_keys = nullptr; uint32_t sky_object = 0;      // the skydome's key plane (k_sky_tiles) and its draw record
     // End of every frame's lighting pass, one (timing-enabled) event per frame in a ring: the next-but-one frame waits for it before
@@ -326,7 +301,6 @@ struct zr_ctx {
     uint2* d_pxrect = nullptr; float* d_zmin = nullptr; uint8_t* d_visflag[2] = { nullptr, nullptr };
     // shadow pass occlusion culling (k_shadow_occlusion): the cull's box + least depth per work item, "not hidden last frame" per meshlet-instance
     uint2* d_spxrect = nullptr; float* d_szmin = nullptr; uint8_t* d_sflag = nullptr;
-    bool sflag_history = false;          // the flags come from a frame of this scene (else: all set, and the first test takes every item)
     // A world update (zr_world.cpp) that adds, removes, resizes or reorders objects asks the next zr_scene_finalize to carry the visibility
     // marks and the shadow flags of the kept draws to their new work-item numbers (k_history_carry) instead of forgetting them;
     // history_items: how many meshlet-instances the last zr_scene_finalize carried.
@@ -335,13 +309,13 @@ struct zr_ctx {
     // that moves the items' work ids by d adds -d here, so that an item keeps its turn; where the kept draws move by different amounts
     // (mod 4), the amount most items move by.  shadow_draws itself stays what it counts.
     uint32_t sflag_turn = 0;
-    float* d_hiz = nullptr; ZrHiz hiz = {}; int vis_cur = 0; bool vis_history = false, last_two_round = false;
+    float* d_hiz = nullptr; ZrHiz hiz = {}; int vis_cur = 0; bool last_two_round = false;
     uint32_t vis_mark_prev = 0;          // the stamp the resolve wrote into last frame's visibility marks (ZrHiz::vis_stamp)
     uint32_t* d_hiz_regions = nullptr; uint32_t n_hiz_regions = 0;      // the 64 x 64 pixel regions over owned tiles (k_hiz_build)
     ZrDevStats* d_stats = nullptr; ZrDevStats h_stats = {};
     // The shadow pipeline's statistics / work counters (slot 0) live in a block of their own: the pipeline resets what it counts itself
     // (k_scan), so it does not wait for the camera lane's k_frame_begin, and the camera lane does not wait for it.
-    ZrDevStats* d_sstats = nullptr; uint32_t list_rebuild_mask = 0;
+    ZrDevStats* d_sstats = nullptr;
     // A resolve on the host's stream tallies its covered pixels into a block of its frame copy (only covered_part is used), zeroed on that
     // stream: the next frame's k_frame_begin zeroes d_stats on the camera lane while it may still be counting.  cov_block: where the
     // resolve of the frame enqueued last counted (d_stats, or one of these).
@@ -402,7 +376,7 @@ struct zr_ctx {
 int zr_fail(zr_ctx* c, int code, const std::string& msg);      // records the message (never throws), returns code
 // ZR_OK at stage 0, else the refusal "<what> between the stages of a frame" (hint: "... (finish it with zr_render_lighting first)")
 int zr_stage_idle(zr_ctx* c, const char* what, bool hint = true);
-// What the shadow pass would draw, or where, may have changed: the next frame draws its map (see zr_ctx::caster_epoch).  The device forms
+// What the shadow pass would draw, or where, may have changed: the next frame draws its map (see zr_ctx::caster_epoch, zr_frame_plan).  The device forms
 // of the updates call it when they enqueue: their kernels are stream-ordered ahead of the next frame.
 static inline void zr_casters_changed(zr_ctx* c) { c->caster_epoch++; c->camera_epoch++; }
 // What the camera pass draws, how its work items are numbered or where its records go may have changed, the casters apart: the next
@@ -410,6 +384,18 @@ static inline void zr_casters_changed(zr_ctx* c) { c->caster_epoch++; c->camera_
 static inline void zr_camera_changed(zr_ctx* c) { c->camera_epoch++; }
 // What the resolve reads beyond the camera pass's inputs may have changed: the next two frames resolve again (see zr_ctx::surface_epoch).
 static inline void zr_surface_changed(zr_ctx* c) { c->surface_epoch++; }
+// What the frames so far left on the device says nothing about the frames to come: the passes' work lists, the record buckets' plan, the
+// visibility marks, the shadow pass's occlusion flags (ZrFrameCarry) - the next frame rebuilds, counts first, draws in one round.
+enum : uint32_t { ZR_HIST_SHADOW_LIST = 1u, ZR_HIST_CAMERA_LIST = 2u, ZR_HIST_LISTS = 3u, ZR_HIST_PLAN = 4u, ZR_HIST_VISIBILITY = 8u, ZR_HIST_SHADOW_FLAGS = 16u };
+static inline void zr_history_forgotten(zr_ctx* c, uint32_t what)
+{
+    ZrFrameCarry& k = c->carry;
+    if (what & ZR_HIST_SHADOW_LIST) k.list_valid[0] = false;
+    if (what & ZR_HIST_CAMERA_LIST) k.list_valid[1] = false;
+    if (what & ZR_HIST_PLAN) k.plan_valid = false;
+    if (what & ZR_HIST_VISIBILITY) k.vis_history = false;
+    if (what & ZR_HIST_SHADOW_FLAGS) k.sflag_history = false;
+}
 #define HIPCHK(c, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) \
     return zr_fail((c), ZR_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); } while (0)
 #define ARGCHK(c, cond) do { if (!(cond)) return zr_fail((c), ZR_ERR_ARG, "bad argument: " #cond); } while (0)

@@ -10,18 +10,12 @@
 #include <cmath>
 #include <cstring>
 
-// A schedule constant, re-measured whenever the balance of the two lanes changes ("The schedule"; the others:
-// zr_context.cpp): whether a frame that draws its shadow map records ev_cam ahead of its k_plan too (a frame that resolves on the host's
-// stream always does).
-#ifndef ZR_EV_CAM_AHEAD_OF_PLAN
-#define ZR_EV_CAM_AHEAD_OF_PLAN 0
-#endif
-// ... and where the head of a zr_render frame that keeps camera pass and shadow map runs - the uniform upload and the one-pixel launch, some
-// 15 us of latency ahead of k_lighting: 0 in series on the host's stream, 1 on the idle camera lane beside the previous frame's lighting
-// pass, at the price of one event crossing (DESIGN.md section 7 has both, measured: 17 470 / 19 240 Mpixel/s).
-#ifndef ZR_KEPT_HEAD_ON_LANE
-#define ZR_KEPT_HEAD_ON_LANE 1
-#endif
+// What the schedule reads under its own names (zr_frame_plan.h is plain C++ and sees neither header) is what the library means by them.
+static_assert(ZRP_NO_HIZ == ZR_FLAG_NO_HIZ && ZRP_SERIAL_PASSES == ZR_FLAG_SERIAL_PASSES && ZRP_NO_LIST_REUSE == ZR_FLAG_NO_LIST_REUSE &&
+              ZRP_NO_SHADOW_OCCLUSION == ZR_FLAG_NO_SHADOW_OCCLUSION && ZRP_SHADOW_OCCLUSION == ZR_FLAG_SHADOW_OCCLUSION &&
+              ZRP_SHADING_FORWARD == ZR_SHADING_FORWARD, "zr_frame_plan.h: flags");
+static_assert((int)ZR_ROUNDS_ONE == ZR_PLAN_ONE_ROUND && (int)ZR_ROUNDS_TWO == ZR_PLAN_DREW_ROUND2 && (int)ZR_ROUNDS_TWO_KEPT == ZR_PLAN_KEPT_ROUND2, "zr_frame_plan.h: rounds");
+static_assert(ZR_TILE == 32, "the triangle-binned camera pass and the shadow pass's occlusion culling are written for 32 x 32 tiles");
 
 // ------------------------------------------------------------------------------------------------ uniforms
 
@@ -249,22 +243,21 @@ static bool build_pass(const zr_ctx* c, const XkUniformBufferMVP& u, int mode, Z
 }
 
 // ------------------------------------------------------------------------------------------------ the frame
+//
+// What a frame does is decided once, by zr_frame_plan() (zr_frame_plan.h), when the frame begins; everything below does what the plan says
+// on the stream the plan names, and tells zr_frame_carry() when a stage is enqueued.
 
-// Contexts whose map is never kept (every frame draws it): the host reduces or gathers a partitioned or caller-owned map in place;
-// ZR_FLAG_NO_LIST_REUSE asks to recompute what standing inputs would let the library keep; ZR_FLAG_SHADOW_OCCLUSION forces a variant of
-// the pass for A/B, whose per-frame history statistics are what its callers read.
-static inline bool shadow_keepable(const zr_ctx* c)
-{
-    return !c->d_shadow_ext && c->cfg.tile_world <= 1u && c->shadow_world <= 1u && c->stile_world <= 1u &&
-           !(c->cfg.flags & (ZR_FLAG_NO_LIST_REUSE | ZR_FLAG_SHADOW_OCCLUSION));
-}
+static inline hipStream_t lane_stream(const zr_ctx* c, ZrLane lane) { return lane == ZR_LANE_CAM ? c->cam_s : c->stream; }
 
-// Contexts that never keep round 2 of the camera pass (every two-round frame draws it): ZR_FLAG_NO_LIST_REUSE, as above.  A rank of a
-// tile-partitioned frame keeps it like any other context: the statement is per pixel, and a rank's key buffer holds its own tiles only.
-static inline bool camera_keepable(const zr_ctx* c)
+// A timed frame's events `which` on s, in order (an untimed frame: nothing).  A kept pass records its events all the same - no elapsed-time
+// call meets an unrecorded one - on the stream that lights the frame, and its sample counts as 0 (zr_get_pass_times_avg).
+static int timed_events(zr_ctx* c, hipStream_t s, std::initializer_list<int> which)
 {
-    return !(c->cfg.flags & ZR_FLAG_NO_LIST_REUSE);
+    if (zr_ctx::TimedFrame* const T = c->timed_frame())
+        for (int e : which) HIPCHK(c, hipEventRecord(T->ev[e], s));
+    return ZR_OK;
 }
+#define TIMED(c, s, ...) do { if (int _rc = timed_events((c), (s), { __VA_ARGS__ })) return _rc; } while (0)
 
 // count -> scan -> fill of the shadow pass's meshlet bins, from the cull's rects.  Z.phase 1 (occlusion culling): only the
 // meshlet-instances flagged last frame are binned.
@@ -287,9 +280,8 @@ static void tri_select(zr_ctx* c, const ZrPass& P, const ZrHiz& Z, int slot, hip
     zr_launch_select(P, c->d_objs, c->sc[1].work, c->sc[1].rects, Z, c->tb, c->d_stats, slot, s);
 }
 // One round of the triangle-binned camera pass: triangles -> records in their tiles' buckets (k_geom), tile raster (k_tile).  The buckets were
-// laid out by the previous frame's k_plan; `count_first`: there is no usable plan (first frame of a scene, or the last plan was made by a
-// two-round frame and this round draws everything) - k_geom runs once more ahead of the round, counting only, and k_plan lays the buckets
-// out from that.
+// laid out by the previous frame's k_plan; `count_first` (ZrFramePlan): k_geom runs once more ahead of the round, counting only, and k_plan
+// lays the buckets out from that.
 static void tri_raster(zr_ctx* c, const ZrPass& P, const ZrHiz& Z, int slot, hipStream_t s, bool last, bool count_first)
 {
     if (P.n_work == 0) return;          // nothing to draw: the pass is its clear
@@ -308,42 +300,15 @@ static void raster(zr_ctx* c, const ZrPass& P, hipStream_t s, int stage)
                             c->stile_world >= 4u ? c->shadow_blocks / 2u : c->shadow_blocks, s, c->d_slow0, c->slow0_cap, c->d_sowned, c->sn_tiles, stage);
 }
 
-// What a frame keeps of the frame before, decided once its two pass blocks are built (frame_begin) and before anything is enqueued;
-// rebuild: the work lists this frame rebuilds, lane: its camera pipeline would run on the library's own stream.
-static void keep_decisions(zr_ctx* c, uint32_t rebuild, bool lane)
-{
-    // the shadow pass's map as a whole while its block stands, no caster changed and the map stays where it is (shadow_pass)
-    c->shadow_keep = shadow_keepable(c) && c->smap_valid && c->smap_epoch == c->caster_epoch && memcmp(&c->smap_key, &c->pass[0], sizeof(ZrPass)) == 0;
-    // round 2 of the camera pass while the frame enqueued last drew or kept it from this very block, on a history of this very block, and
-    // nothing the pass draws changed since (gbuffer_pass)
-    c->frame_cam_epoch = c->camera_epoch;
-    c->cam_same = c->cam_prev_valid && c->cam_prev_epoch == c->camera_epoch && memcmp(&c->cam_prev_key, &c->pass[1], sizeof(ZrPass)) == 0;
-    c->round2_keep = camera_keepable(c) && c->cam_same && c->r2_settled;
-    // the camera pass as a whole, GBuffer included, while beyond that nothing the resolve reads changed (surface_epoch) and both copies
-    // of the GBuffer were resolved from these very inputs (g_gen: which run of equal inputs this frame belongs to): after two drawn frames
-    // of one run the copies are the same bit for bit, and the frame lights its parity's copy.  Not with a skydome or while a copy still
-    // waits for its overlay wipe (the sky key plane is single-buffered, see resolve_on_host_lane).  Such a frame enqueues nothing of the
-    // camera pipeline and touches nothing of the lane's.
-    if (!c->cam_same || c->surf_prev_epoch != c->surface_epoch) c->g_gen++;
-    c->surf_prev_epoch = c->surface_epoch;
-    const bool settled = c->round2_keep && !(rebuild & 2u) && c->vis_history && c->plan_valid && c->pass[1].n_work != 0 && !(c->cfg.flags & ZR_FLAG_NO_HIZ);
-    const bool copies = c->fc[0].g_gen == c->g_gen && c->fc[1].g_gen == c->g_gen && !c->fc[0].overlay_dirty && !c->fc[1].overlay_dirty;
-    c->camera_keep = settled && copies && !(c->sky_set && c->sky_enabled);
-    // Its head - upload and one-pixel launch - runs on the idle lane where zr_render keeps the map too (ZR_KEPT_HEAD_ON_LANE).  The one-pixel
-    // launch reads the map, and the lane has waited for the end of frame_no - 2 only: the map must have been drawn by that frame or an
-    // earlier one (a map drawn by the frame before, on the host's stream, is behind nothing the lane has waited for).
-    c->head_on_lane = ZR_KEPT_HEAD_ON_LANE && c->camera_keep && c->in_render && c->shadow_keep && lane && c->smap_frame + 2 <= c->frame_no;
-}
-
 // The frame in three stages so that a multi-GPU host can put collectives between them (zeldaengine_amd/dist.py):
 //   zr_render_shadow    shadow pass (ZE:3239-3393) of this rank's share of the instances
 //   zr_render_gbuffer   deferred-scene pass (ZE:3417-3480): cull + bin + raster + resolve of the owned tiles
 //   zr_render_lighting  deferred-lighting pass (ZE:3531-3540) [+ skydome / background overlay]
 // zr_render = all three.
-// Start of a frame on stream s: pick this frame's copies of the double-buffered resources (key buffer included), make s wait until the
-// frame that last used them (two frames ago: its resolve, if that ran on the host's stream, and its lighting pass) is done, reset the
-// camera lane's statistics, upload the uniforms if this copy does not hold them yet.
-static int frame_begin(zr_ctx* c, hipStream_t s)
+// Start of a frame: build its two pass blocks, gather what the schedule reads and plan the frame (c->facts, c->plan); then its head, on the
+// plan's stream: pick this frame's copies of the double-buffered resources (key buffer included), wait for whoever used them last, reset
+// the camera lane's statistics, upload the uniforms if this copy does not hold them yet.
+static int frame_begin(zr_ctx* c, ZrEntry entry)
 {
     if (!c->frame_valid) return zr_fail(c, ZR_ERR_STATE, "no frame uniforms: call zr_update_uniforms or zr_set_frame first");
     if (c->stage != 0) return zr_fail(c, ZR_ERR_STATE, "zr_render_shadow out of order");
@@ -357,40 +322,41 @@ static int frame_begin(zr_ctx* c, hipStream_t s)
     if (c->id_capture) { rc = ids_prepare(c); if (rc) return rc; }
     c->fcur = (int)(c->frame_no & 1u);
     FrameCopy& F = c->fc[c->fcur];
-    // the frame's two geometry passes; a pass's work list on the device is rebuilt only when its block or the scene changed
-    uint32_t rebuild = 0;
-    for (int slot = 0; slot < 2; ++slot) {
+
+    ZrFrameFacts& f = c->facts;
+    f.flags = c->cfg.flags; f.tile_world = c->cfg.tile_world; f.shadow_world = c->shadow_world; f.stile_world = c->stile_world;
+    f.map_external = c->d_shadow_ext != nullptr; f.sky = c->sky_set && c->sky_enabled; f.shading = c->shading; f.SD = c->SD;
+    f.entry = entry; f.has_lane = c->cam_s != nullptr; f.frame_no = c->frame_no;
+    f.caster_epoch = c->caster_epoch; f.camera_epoch = c->camera_epoch; f.surface_epoch = c->surface_epoch;
+    for (int slot = 0; slot < 2; ++slot) {      // the frame's two geometry passes
         ZrPass& P = c->pass[slot];
         c->pass_live[slot] = build_pass(c, slot == 0 ? c->shadow : c->cam, slot == 0 ? ZR_MODE_SHADOW : ZR_MODE_GBUFFER, &P);
         if (!c->pass_live[slot]) P.n_work = 0;      // no finite vertex: the pass is its clear
-        c->list_reuse[slot] = P.use_worklist && P.n_work != 0 && c->list_valid[slot] && memcmp(&c->list_key[slot], &P, sizeof P) == 0 &&
-                              !(c->cfg.flags & ZR_FLAG_NO_LIST_REUSE);
-        // (the list counts as standing only once its k_cull_instances has been enqueued: shadow_pass / gbuffer_pass set list_valid)
-        if (P.use_worklist && P.n_work != 0 && !c->list_reuse[slot]) { rebuild |= 1u << slot; c->list_key[slot] = P; c->list_valid[slot] = false; }
+        f.n_work[slot] = P.n_work; f.use_worklist[slot] = P.use_worklist != 0;
+        f.block_is_list[slot] = memcmp(&c->list_key[slot], &P, sizeof P) == 0;
     }
-    keep_decisions(c, rebuild, s != c->stream);
-    if (c->camera_keep && !c->head_on_lane) s = c->stream;
-    // (two lanes: this frame's copies of the double-buffered resources were last used two frames ago, on the host's stream: read by the
-    // lighting pass, and before it the keys reset and the GBuffer written by the resolve where that ran there.  Nothing else ties the lanes
-    // together here: the shadow pipeline and a host-lane resolve keep statistics of their own)
-    if (s != c->stream && c->frame_no >= 2) HIPCHK(c, hipStreamWaitEvent(s, c->ev_end[(c->frame_no - 2) % zr_ctx::END_RING], 0));
-    // Consecutive camera pipelines share the triangle records, the plan and the camera lane's statistics (the key buffer is one of a pair,
-    // like F), and are ordered by running on ONE stream.  A frame on the lane that follows a frame of the staged entry points (its camera
-    // pipeline ran on the host's stream) waits for that frame's end instead.  The other way round the host's stream has waited for ev_cam
-    // before that frame's lighting pass: the whole lane, k_plan included - unless that frame resolved on the host's stream, whose ev_cam
-    // sits ahead of k_plan; then this frame's camera pipeline, if it runs on the host's stream, waits for the lane's end here.
-    if (s != c->stream && c->frame_no >= 1 && c->gbuf_s && c->gbuf_s != s)
-        HIPCHK(c, hipStreamWaitEvent(s, c->ev_end[(c->frame_no - 1) % zr_ctx::END_RING], 0));
-    // (a frame that keeps its camera pass touches nothing of the lane's: the wait, and the census's below, are left to the next drawn frame)
-    if (!c->camera_keep && c->plan_behind_cam && s == c->stream && c->cam_s) { HIPCHK(c, hipEventRecord(c->ev_lane, c->cam_s)); HIPCHK(c, hipStreamWaitEvent(s, c->ev_lane, 0)); }
-    if (!c->camera_keep) c->plan_behind_cam = false;
-    // ... and by an identity census enqueued against them since (zr_instance_coverage_async, on the host's stream)
-    if (F.ids_wait && !c->camera_keep) { if (s != c->stream) HIPCHK(c, hipStreamWaitEvent(s, F.ev_ids, 0)); F.ids_wait = false; }
+    for (int i = 0; i < 2; ++i) { f.copy_gen[i] = c->fc[i].g_gen; f.copy_overlay[i] = c->fc[i].overlay_dirty; f.copy_ids_wait[i] = c->fc[i].ids_wait; }
+    f.shadow_is_map = memcmp(&c->smap_key, &c->pass[0], sizeof(ZrPass)) == 0;
+    f.camera_is_prev = memcmp(&c->cam_prev_key, &c->pass[1], sizeof(ZrPass)) == 0;
+    const ZrFramePlan& p = c->plan = zr_frame_plan(f, c->carry);
+    c->carry = zr_frame_carry(c->carry, f, p, ZR_STAGE_HEAD);
+    if (p.shadow_list_rebuild) c->list_key[0] = c->pass[0];
+    if (p.camera_list_rebuild) c->list_key[1] = c->pass[1];
+
+    const hipStream_t s = lane_stream(c, p.head);
+    if (p.wait_end2) HIPCHK(c, hipStreamWaitEvent(s, c->ev_end[(c->frame_no - 2) % zr_ctx::END_RING], 0));
+    if (p.wait_end1) HIPCHK(c, hipStreamWaitEvent(s, c->ev_end[(c->frame_no - 1) % zr_ctx::END_RING], 0));
+    if (p.wait_lane_end) { HIPCHK(c, hipEventRecord(c->ev_lane, c->cam_s)); HIPCHK(c, hipStreamWaitEvent(s, c->ev_lane, 0)); }
+    if (p.wait_ids) HIPCHK(c, hipStreamWaitEvent(s, F.ev_ids, 0));
+    if (p.ids_taken) F.ids_wait = false;
     // this frame's draw table; the updates since the last frame of this parity go into its planes and sets, s behind the last texture update
     rc = zr_update_frame(c, s, c->fcur);
     if (rc) return rc;
     c->timing_now = c->timing_interval != 0 && c->frame_no % c->timing_interval == 0;     // pass events cost ~6 us of stream bubble each
-    if (zr_ctx::TimedFrame* T = c->timed_frame()) HIPCHK(c, hipEventRecord(T->ev[zr_ctx::EV_BEGIN], s));
+    if (zr_ctx::TimedFrame* T = c->timed_frame()) {
+        HIPCHK(c, hipEventRecord(T->ev[zr_ctx::EV_BEGIN], s));
+        T->kept = p.shadow_keep; T->kept_round2 = p.rounds == ZR_ROUNDS_TWO_KEPT; T->kept_camera = p.camera_keep; T->moved = p.resolve_deferred;
+    }
     if (c->view_dirty) { c->view_version++; c->view_dirty = false; }
     const XkView* src = nullptr;
     uint32_t k = 0;
@@ -400,32 +366,21 @@ static int frame_begin(zr_ctx* c, hipStream_t s)
         memcpy(&c->h_view_ring[k], &c->view, sizeof(XkView));
         src = &c->h_view_ring[k];
     }
-    c->list_rebuild_mask = rebuild;
     // zeroes the camera lane's statistics (the sticky overflow latch survives) and - when the camera list is rebuilt - its length; uploads
     // XkView.  The SHADOW list's length lives in the shadow pipeline's block and is reset on that pipeline's own stream (shadow_pass):
     // the previous frame's shadow pipeline may still be walking it while this kernel runs on the camera lane.
     // (a frame that keeps its camera pass keeps that pass's statistics: an upload, or nothing)
-    if (!c->camera_keep || src) zr_launch_frame_begin(c->camera_keep ? nullptr : c->d_stats, src, F.view, c->camera_keep ? 0u : rebuild & 2u, s);
+    if (p.reset_stats || src) zr_launch_frame_begin(p.reset_stats ? c->d_stats : nullptr, src, F.view, p.reset_camera_list ? 2u : 0u, s);
     if (src) { HIPCHK(c, hipEventRecord(c->view_ev[k], s)); F.view_uploaded = c->view_version; }
     return ZR_OK;
 }
 
-// shadow pass (ZE:3239-3393) of this rank's share of the instances, on stream s
-static int shadow_pass(zr_ctx* c, hipStream_t s)
+// shadow pass (ZE:3239-3393) of this rank's share of the instances, drawn on stream s
+static int shadow_draw(zr_ctx* c, hipStream_t s)
 {
-    zr_ctx::TimedFrame* const T = c->timed_frame();
-    hipEvent_t* const ev = T ? T->ev : nullptr;
+    const ZrFramePlan& p = c->plan;
     const ZrPass& P = c->pass[0];      // (built by frame_begin)
-    if (ev) T->kept = c->shadow_keep;
-    if (c->shadow_keep) {
-        // The map of the last drawn pass is this frame's, bit for bit: nothing is launched.  Its statistics block, last_work[0] and the
-        // occlusion flags stay as that pass left them; a timed frame records its two events all the same (no elapsed-time call meets an
-        // unrecorded one), and the sample counts as 0 (zr_get_pass_times_avg).
-        if (ev) { HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_SHADOW_BINS], s)); HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_SHADOW], s)); }
-        return ZR_OK;
-    }
     c->last_work[0] = P.n_work;
-    c->smap_valid = false;             // (until the whole pass is enqueued)
     // The pass draws into the copy that does NOT hold the current map and makes it the current one: from here on shadow_buf() is the map
     // being drawn.  No event guards the flip: everything that reads or writes either copy - this pipeline, the lighting passes and their
     // fused clear, the read-backs and copies - is enqueued on the host's stream, in frame order.
@@ -435,112 +390,80 @@ static int shadow_pass(zr_ctx* c, hipStream_t s)
     if (c->d_shadow_ext || !F.shadow_cleared) zr_launch_fill32((uint32_t*)shadow_buf(c), 0x3F800000u, (size_t)c->SD * c->SD, s);
     F.shadow_cleared = false;
     ZrHiz Z; memset(&Z, 0, sizeof Z);
-    // occlusion culling (k_shadow_occlusion): the first launch draws what was not hidden last frame, the rest is tested against the map.
-    // It pays when casters pile up behind each other: the test + the late launch cost what a quarter of config 3's rasteriser does
-    // (0.1 meshlet-instances per texel: 25 % hidden, frame 2.7 % slower); the same spheres at 0.21 / 0.31 / 0.52 per texel: frame 2 /
-    // 8 / 10.5 % faster (tools/occlusion_threshold.py); 1 M instances (10 per texel): 10 % - on by itself from one per five texels.
-    const bool occl = !(c->cfg.flags & ZR_FLAG_NO_SHADOW_OCCLUSION) && P.n_work != 0 && ZR_TILE == 32 && c->SD >= 4u &&
-                      ((c->cfg.flags & ZR_FLAG_SHADOW_OCCLUSION) || 5ull * P.n_work >= (uint64_t)c->SD * c->SD);
-    if (occl) { Z.pxrect = c->d_spxrect; Z.zmin = c->d_szmin; Z.vis_prev = c->d_sflag; Z.vis_stamp = 1u; Z.phase = 1u; }      // (the pass's own flags are 0 / 1)
+    if (p.shadow_occlusion) { Z.pxrect = c->d_spxrect; Z.zmin = c->d_szmin; Z.vis_prev = c->d_sflag; Z.vis_stamp = 1u; Z.phase = 1u; }      // (the pass's own flags are 0 / 1)
     // a rebuilt work list starts from length 0 - zeroed HERE, in stream order behind the previous frame's shadow pipeline (k_cull_instances
     // grows it, every later kernel of the pipeline reads it)
-    if (c->list_rebuild_mask & 1u) zr_launch_fill32(&c->d_sstats->n_vis_work[0], 0u, 1, s);
-    zr_launch_cull_box(P, c->d_objs, c->sc[0].work, c->sc[0].rects, Z, c->d_sstats, 0, s, nullptr, nullptr, c->list_reuse[0]);
-    if (c->list_rebuild_mask & 1u) c->list_valid[0] = true;
+    if (p.shadow_list_rebuild) zr_launch_fill32(&c->d_sstats->n_vis_work[0], 0u, 1, s);
+    zr_launch_cull_box(P, c->d_objs, c->sc[0].work, c->sc[0].rects, Z, c->d_sstats, 0, s, nullptr, nullptr, p.shadow_list_reuse);
     shadow_bin(c, P, Z, s);
-    if (ev) HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_SHADOW_BINS], s));
-    raster(c, P, s, occl ? 1 : 0);
-    if (occl) {
+    TIMED(c, s, zr_ctx::EV_SHADOW_BINS);
+    raster(c, P, s, p.shadow_occlusion ? 1 : 0);
+    if (p.shadow_occlusion) {
         zr_launch_shadow_occlusion(P, c->d_objs, c->sc[0].work, c->sc[0].rects, c->d_spxrect, c->d_szmin, c->d_sflag, (const uint32_t*)shadow_buf(c),
-                                   c->sb.bins, c->d_sstats, c->shadow_blocks * 8u, c->sflag_history ? (uint32_t)((c->shadow_draws + c->sflag_turn) & 3u) : 4u, s);      // (a turn per pass DRAWN: kept frames test nothing)
-        c->sflag_history = true;
+                                   c->sb.bins, c->d_sstats, c->shadow_blocks * 8u, c->carry.sflag_history ? (uint32_t)((c->shadow_draws + c->sflag_turn) & 3u) : 4u, s);      // (a turn per pass DRAWN: kept frames test nothing)
         raster(c, P, s, 2);
     }
-    if (ev) HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_SHADOW], s));
+    TIMED(c, s, zr_ctx::EV_SHADOW);
     HIPCHK(c, hipGetLastError());
     c->shadow_draws++;
-    c->smap_key = P; c->smap_epoch = c->caster_epoch; c->smap_valid = true; c->smap_frame = c->frame_no;
+    c->smap_key = P; c->carry = zr_frame_carry(c->carry, c->facts, p, ZR_STAGE_SHADOW);
     return ZR_OK;
 }
 
-// Where the frame's resolve runs.  Nothing later on the camera lane of the same frame needs its planes: only the same frame's lighting
-// pass reads them, on the host's stream.  In a frame that keeps its shadow map that stream has nothing else to do, and the camera lane's
-// chain of launches is the frame's period: the resolve then goes to the host's stream, ahead of the lighting pass, and k_mark leaves the
-// next frame's camera lane the visibility history.  Only zr_render does this (a host may read the GBuffer after zr_render_geometry, and
-// the staged entry points run on one stream anyway), only on two lanes, and not with a skydome (its key plane is single-buffered).
-// (shadow_keep already implies an unpartitioned context: shadow_keepable.)
-static inline bool resolve_on_host_lane(const zr_ctx* c, bool lanes)
+// The frame's shadow stage: the pass drawn, or kept - the map of the last drawn pass is this frame's, bit for bit: nothing is launched, and
+// its statistics block, last_work[0] and the occlusion flags stay as that pass left them.
+static int shadow_pass(zr_ctx* c)
 {
-    return lanes && c->in_render && c->shadow_keep && !(c->sky_set && c->sky_enabled);
+    const ZrFramePlan& p = c->plan;
+    if (p.shadow == ZR_LANE_NONE) TIMED(c, c->stream, zr_ctx::EV_SHADOW_BINS, zr_ctx::EV_SHADOW);
+    else if (int rc = shadow_draw(c, lane_stream(c, p.shadow))) return rc;
+    if (p.ev_join) HIPCHK(c, hipEventRecord(c->ev_join, c->stream));
+    return ZR_OK;
 }
 
-// deferred-scene pass (ZE:3417-3480): cull + bin + raster + resolve of the owned tiles, on stream s.  defer_resolve: see above - the
-// resolve is left to zr_render_lighting (deferred_resolve), the lane ends k_mark -> ev_cam -> k_plan.
-static int gbuffer_pass(zr_ctx* c, hipStream_t s, bool defer_resolve = false)
+// deferred-scene pass (ZE:3417-3480): cull + bin + raster + resolve of the owned tiles, on the plan's stream.  Where the plan leaves the
+// resolve to zr_render_lighting (deferred_resolve), the lane ends k_mark -> ev_cam -> k_plan.
+static int gbuffer_pass(zr_ctx* c)
 {
-    zr_ctx::TimedFrame* const T = c->timed_frame();
-    hipEvent_t* const ev = T ? T->ev : nullptr;
-    if (ev) { T->kept_camera = c->camera_keep; HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_CAMERA], s)); }
-    if (c->camera_keep) {
-        // The camera pass kept whole (frame_begin): both GBuffer copies, the key buffers, the visibility history and its stamp, the plan,
-        // the statistics block and cov_block stay as the last drawn frame left them, and nothing is launched.  A timed frame records the
-        // pass's events all the same, on the stream that lights it, and counts 0 for the cull, both rounds, Hi-Z and the resolve.
-        if (ev) {
-            T->kept_round2 = true; T->moved = false;
-            for (int e : { zr_ctx::EV_CULL, zr_ctx::EV_ROUND1, zr_ctx::EV_HIZ, zr_ctx::EV_ROUND2, zr_ctx::EV_RESOLVE }) HIPCHK(c, hipEventRecord(ev[e], s));
-        }
+    const ZrFramePlan& p = c->plan;
+    if (p.camera == ZR_LANE_NONE) {
+        // The camera pass kept whole: both GBuffer copies, the key buffers, the visibility history and its stamp, the plan, the statistics
+        // block and cov_block stay as the last drawn frame left them, and nothing is launched.
+        TIMED(c, lane_stream(c, p.lighting), zr_ctx::EV_CAMERA, zr_ctx::EV_CULL, zr_ctx::EV_ROUND1, zr_ctx::EV_HIZ, zr_ctx::EV_ROUND2, zr_ctx::EV_RESOLVE);
         return ZR_OK;
     }
+    const hipStream_t s = lane_stream(c, p.camera);
+    TIMED(c, s, zr_ctx::EV_CAMERA);
     ZrPass P = c->pass[1];             // (built by frame_begin; the overlay fields are set below)
-    c->gbuf_s = s;
     c->last_work[1] = P.n_work;
-    c->r2_settled = c->cam_prev_valid = false;      // (until the whole pass is enqueued; frame_begin has read them)
-    // Two-pass occlusion culling: round 1 draws the meshlet-instances that owned a pixel last frame, a Hi-Z pyramid of the
-    // result rejects what it hides, round 2 draws the rest.  The depth test decides every pixel either way, so the frame does
-    // not depend on the history; without one (first frame of a scene) or with ZR_FLAG_NO_HIZ everything is drawn at once.
-    const bool hiz_on = !(c->cfg.flags & ZR_FLAG_NO_HIZ) && P.n_work != 0;
+    // Two-pass occlusion culling (ZrFramePlan::rounds).  The depth test decides every pixel either way, so the frame does not depend on
+    // the history.
     ZrHiz Z = c->hiz;
     Z.tiles_x = c->tiles_x; Z.tile_rank = c->cfg.tile_rank; Z.tile_world = c->cfg.tile_world;
-    Z.pxrect = hiz_on ? c->d_pxrect : nullptr; Z.zmin = hiz_on ? c->d_zmin : nullptr;
-    Z.vis_prev = c->d_visflag[c->vis_cur ^ 1]; Z.vis_now = hiz_on ? c->d_visflag[c->vis_cur] : nullptr;
+    Z.pxrect = p.hiz_on ? c->d_pxrect : nullptr; Z.zmin = p.hiz_on ? c->d_zmin : nullptr;
+    Z.vis_prev = c->d_visflag[c->vis_cur ^ 1]; Z.vis_now = p.hiz_on ? c->d_visflag[c->vis_cur] : nullptr;
     // visibility marks are frame stamps (1 .. 255): the resolve writes this frame's, the culls compare with last frame's - nothing is cleared
     // (a stamp per pass DRAWN: a rest of any length leaves the stamps as an uninterrupted run of drawn frames would)
     const uint32_t vis_mark = 1u + (uint32_t)(c->cam_draws % 255u);
     Z.vis_stamp = c->vis_mark_prev;
     Z.phase = 0;
-    static_assert(ZR_TILE == 32, "the triangle-binned camera pass is written for 32 x 32 tiles");
-    c->last_two_round = hiz_on && c->vis_history;
+    c->last_two_round = p.rounds != ZR_ROUNDS_ONE;
     // (the cull kernel also compacts round 1's list - the survivors that owned a pixel last frame, or all of them)
-    zr_launch_cull_box(P, c->d_objs, c->sc[1].work, c->sc[1].rects, Z, c->d_stats, 1, s, c->tb.sel, c->last_two_round ? Z.vis_prev : nullptr, c->list_reuse[1]);
-    if (c->list_rebuild_mask & 2u) c->list_valid[1] = true;
-    const bool two = c->last_two_round;
-    // (the record buckets are planned from the previous frame: see tri_raster)
-    const bool count_first = !c->plan_valid || (!two && c->plan_two_round);
-    // Round 2 kept (zr_ctx::camera_epoch): the inputs are the previous frame's bit for bit, so round 1 - what owned a pixel of that frame -
-    // leaves this frame's key buffer, and round 1 is the frame's last round: its k_tile draws the slow triangles.  The statistics and the
-    // plan are those of round 2 as last drawn (k_plan); a timed frame records its events all the same and counts 0 for both passes.
-    const bool keep = two && c->round2_keep && !count_first;
-    if (ev) T->kept_round2 = keep;
-    if (keep) {
-        Z.phase = 1;
-        if (ev) HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_CULL], s));
-        tri_raster(c, P, Z, 1, s, true, false);
-        if (ev) { HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_ROUND1], s)); HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_HIZ], s)); }
-    } else if (two) {
-        Z.phase = 1;
-        if (ev) HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_CULL], s));
-        tri_raster(c, P, Z, 1, s, false, count_first);
-        if (ev) HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_ROUND1], s));
+    zr_launch_cull_box(P, c->d_objs, c->sc[1].work, c->sc[1].rects, Z, c->d_stats, 1, s, c->tb.sel, c->last_two_round ? Z.vis_prev : nullptr, p.camera_list_reuse);
+    TIMED(c, s, zr_ctx::EV_CULL);
+    if (c->last_two_round) Z.phase = 1;
+    // Round 2 kept: round 1 - what owned a pixel of the previous frame - leaves this frame's key buffer, and round 1 is the frame's last
+    // round: its k_tile draws the slow triangles.  The statistics and the plan are those of round 2 as last drawn (k_plan).
+    tri_raster(c, P, Z, 1, s, p.rounds != ZR_ROUNDS_TWO, p.count_first);
+    TIMED(c, s, zr_ctx::EV_ROUND1);
+    if (p.rounds == ZR_ROUNDS_TWO) {
         zr_launch_hiz_build(c->d_vis[c->fcur], c->W, c->H, Z, c->d_hiz_regions, c->n_hiz_regions, s);
         Z.phase = 2;
         tri_select(c, P, Z, 2, s);
-        if (ev) HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_HIZ], s));
+        TIMED(c, s, zr_ctx::EV_HIZ);
         tri_raster(c, P, Z, 2, s, true, false);
-    } else {
-        if (ev) HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_CULL], s));
-        tri_raster(c, P, Z, 1, s, true, count_first);
-        if (ev) { HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_ROUND1], s)); HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_HIZ], s)); }
-    }
+    } else
+        TIMED(c, s, zr_ctx::EV_HIZ);
     {   // the overlay plane (skydome pixels) is written only when a skydome is drawn, or once more to wipe one that was
         const bool sky = c->sky_set && c->sky_enabled;
         P.write_overlay = (sky || c->fc[c->fcur].overlay_dirty) ? 1u : 0u;
@@ -548,43 +471,25 @@ static int gbuffer_pass(zr_ctx* c, hipStream_t s, bool defer_resolve = false)
         P.sky_keys = nullptr; P.sky_object = c->sky_object;
         if (sky && c->d_sky_keys) { zr_launch_sky_tiles(P, c->d_objs, c->d_owned, c->n_owned, c->d_sky_keys, s); P.sky_keys = c->d_sky_keys; }
     }
-    if (ev) { HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_ROUND2], s)); T->moved = defer_resolve; }
-    c->resolve_deferred = defer_resolve;
-    if (defer_resolve) {
+    TIMED(c, s, zr_ctx::EV_ROUND2);
+    if (p.resolve_deferred) {
         // the history now, the planes later: the host's stream waits for everything up to here and resolves from the same keys
         zr_launch_mark(P, c->d_objs, c->d_owned, c->n_owned, c->d_vis[c->fcur], Z.vis_now, s, vis_mark);
-        if (ev) HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_MARK], s));
+        TIMED(c, s, zr_ctx::EV_MARK);
         c->resolve_P = P; c->resolve_mark = vis_mark;
-        HIPCHK(c, hipEventRecord(c->ev_cam, s)); c->camera_on_lane = true; c->plan_behind_cam = true;
     } else {
         zr_launch_resolve_gbuffer(P, c->d_objs, c->d_owned, c->n_owned, c->d_vis[c->fcur], c->fc[c->fcur].G, c->d_lut, c->d_unorm_lut, Z.vis_now, c->d_stats, s, vis_mark);
-        c->cov_block = c->d_stats; c->fc[c->fcur].g_gen = c->g_gen;
-        if (ev) HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_RESOLVE], s));
-        if (ZR_EV_CAM_AHEAD_OF_PLAN && c->in_render && s != c->stream) { HIPCHK(c, hipEventRecord(c->ev_cam, s)); c->camera_on_lane = true; c->plan_behind_cam = true; }
+        c->cov_block = c->d_stats; c->fc[c->fcur].g_gen = p.g_gen;
+        TIMED(c, s, zr_ctx::EV_RESOLVE);
     }
+    if (p.ev_cam == ZR_EVCAM_BEHIND_MARK || p.ev_cam == ZR_EVCAM_BEHIND_RESOLVE) HIPCHK(c, hipEventRecord(c->ev_cam, s));
     c->vis_mark_prev = vis_mark; c->cam_draws++;
-    if (P.n_work != 0) {     // the next frame's buckets, from this frame's counts: nothing of this frame waits for it
-        zr_launch_plan(c->tb, c->d_owned, c->n_owned, c->d_stats, false, c->bucket_pct, s, keep ? ZR_PLAN_KEPT_ROUND2 : two ? ZR_PLAN_DREW_ROUND2 : ZR_PLAN_ONE_ROUND);
-        c->plan_valid = true; c->plan_two_round = two;
-    }
-    c->r2_settled = two && c->cam_same;
-    c->cam_prev_key = c->pass[1]; c->cam_prev_epoch = c->frame_cam_epoch; c->cam_prev_valid = hiz_on;
-    if (hiz_on) { c->vis_history = true; c->vis_cur ^= 1; } else c->vis_history = false;
+    // the next frame's buckets, from this frame's counts: nothing of this frame waits for it
+    if (P.n_work != 0) zr_launch_plan(c->tb, c->d_owned, c->n_owned, c->d_stats, false, c->bucket_pct, s, p.rounds);
+    if (p.hiz_on) c->vis_cur ^= 1;
     HIPCHK(c, hipGetLastError());
+    c->cam_prev_key = c->pass[1]; c->carry = zr_frame_carry(c->carry, c->facts, p, ZR_STAGE_CAMERA);
     return ZR_OK;
-}
-
-extern "C" int zr_render_shadow(zr_ctx* c)
-{
-    if (!c) return ZR_ERR_ARG;
-    return zr_guard(c, [&]() -> int {
-        c->camera_on_lane = false;
-        int rc = frame_begin(c, c->stream);
-        if (rc == ZR_OK) rc = shadow_pass(c, c->stream);
-        if (rc == ZR_OK) HIPCHK(c, hipEventRecord(c->ev_join, c->stream));
-        if (rc == ZR_OK) c->stage = 1;
-        return rc;
-    });
 }
 
 extern "C" int zr_render_gbuffer(zr_ctx* c)
@@ -593,55 +498,10 @@ extern "C" int zr_render_gbuffer(zr_ctx* c)
     return zr_guard(c, [&]() -> int {
         if (c->stage != 1) return zr_fail(c, ZR_ERR_STATE, "zr_render_gbuffer out of order");
         HIPCHK(c, hipSetDevice(c->device));
-        const int rc = gbuffer_pass(c, c->stream);
+        const int rc = gbuffer_pass(c);
         if (rc == ZR_OK) c->stage = 2;
         return rc;
     });
-}
-
-static int empty_pixel_pass(zr_ctx* c, hipStream_t s);
-// Both geometry passes of a frame.  Two lanes (unless ZR_FLAG_SERIAL_PASSES): the camera pipeline on cam_s; the shadow pipeline on
-// the host's stream, where the lighting pass will follow.  The next frame's camera pipeline starts as soon as this one's is
-// through, next to this frame's lighting; its shadow pipeline follows the lighting.  A frame that keeps its shadow map has no shadow
-// pipeline: in zr_render its resolve takes that place on the host's stream (resolve_on_host_lane), next to the next frame's camera
-// pipeline.  Never more than two kernels side by side: a third only takes occupancy from the other two (measured).
-static int geometry_passes(zr_ctx* c)
-{
-    const bool lanes = !(c->cfg.flags & ZR_FLAG_SERIAL_PASSES) && c->cam_s != nullptr;
-    int rc;
-    c->camera_on_lane = false;
-    if (lanes) {
-        // Every event record / wait is a barrier packet, worth 5-10 us of bubble on the stream it sits on, and the host's stream
-        // (lighting -> shadow pipeline -> lighting ...) is the lane the frame rate hangs on: it waits for the camera lane once per frame
-        // (before the lighting pass) and for nothing else.  The shadow pipeline needs nothing of frame_begin's - its matrices are kernel
-        // arguments, its statistics a block of its own that it resets itself, work-list length included.
-        rc = frame_begin(c, c->cam_s);
-        if (rc != ZR_OK) return rc;
-        rc = shadow_pass(c, c->stream);
-        if (rc == ZR_OK && !c->in_render) HIPCHK(c, hipEventRecord(c->ev_join, c->stream));      // (zr_stream_wait_shadow: a host that puts a collective behind the shadow pass)
-        const bool defer = resolve_on_host_lane(c, lanes);
-        if (rc == ZR_OK) rc = gbuffer_pass(c, c->camera_keep ? c->stream : c->cam_s, defer);      // (kept whole: its events only, where the frame is lit)
-        // (a deferred resolve: ev_cam is already recorded, behind k_mark and ahead of k_plan - the lighting lane does not wait for the plan)
-        if (rc == ZR_OK && c->head_on_lane) {      // (ZR_KEPT_HEAD_ON_LANE: the one-pixel launch behind the upload, the host's stream behind both)
-            rc = empty_pixel_pass(c, c->cam_s);
-            if (rc == ZR_OK) { HIPCHK(c, hipEventRecord(c->ev_cam, c->cam_s)); c->camera_on_lane = true; }
-        }
-        if (rc == ZR_OK && !c->camera_on_lane && !c->camera_keep) { HIPCHK(c, hipEventRecord(c->ev_cam, c->cam_s)); c->camera_on_lane = true; }
-    } else {
-        rc = frame_begin(c, c->stream);
-        if (rc != ZR_OK) return rc;
-        rc = shadow_pass(c, c->stream);
-        if (rc == ZR_OK) HIPCHK(c, hipEventRecord(c->ev_join, c->stream));
-        if (rc == ZR_OK) rc = gbuffer_pass(c, c->stream);
-    }
-    if (rc == ZR_OK) c->stage = 2;
-    return rc;
-}
-
-extern "C" int zr_render_geometry(zr_ctx* c)
-{
-    if (!c) return ZR_ERR_ARG;
-    return zr_guard(c, [&]() -> int { return geometry_passes(c); });
 }
 
 extern "C" int zr_stream_wait_shadow(zr_ctx* c, void* hip_stream)
@@ -671,45 +531,79 @@ static void light_params(const zr_ctx* c, ZrLightParams* Lp)
 // The lighting shader's colour for a pixel that still holds every target's clear value: one launch of the lighting kernel over a
 // one-pixel GBuffer.  It needs the finished shadow map (PCF at world position 0) and the frame's uniforms, nothing else.  View 6
 // (the quad's interpolated vertex colour) depends on the pixel position, so it goes without.
-static int empty_pixel_pass(zr_ctx* c, hipStream_t s)
+static int empty_pixel_pass(zr_ctx* c)
 {
     c->empty_ready = false;
-    if (c->debug_view == 6u || c->env_no_empty_px || c->shading == ZR_SHADING_FORWARD) return ZR_OK;      // (forward: an empty pixel is the clear colour)
+    if (c->plan.one_pixel == ZR_LANE_NONE || c->debug_view == 6u || c->env_no_empty_px) return ZR_OK;
     ZrLightParams L; light_params(c, &L);
     L.W = 1; L.H = 1; L.tiles_x = 1; L.packed_out = 0; L.bg_enabled = 0;
-    zr_launch_lighting(L, c->fc[c->fcur].view, c->d_sowned, 1, c->Gclear, shadow_buf(c), c->cube, c->d_lut, c->d_unorm_lut, c->fc[c->fcur].empty_rgba, s);
+    zr_launch_lighting(L, c->fc[c->fcur].view, c->d_sowned, 1, c->Gclear, shadow_buf(c), c->cube, c->d_lut, c->d_unorm_lut, c->fc[c->fcur].empty_rgba,
+                       lane_stream(c, c->plan.one_pixel));
     HIPCHK(c, hipGetLastError());
     c->empty_ready = true;
     return ZR_OK;
 }
 
+// Both geometry passes of a frame.  Two lanes (zr_frame_plan): the camera pipeline on cam_s; the shadow pipeline on the host's stream,
+// where the lighting pass will follow.  The next frame's camera pipeline starts as soon as this one's is through, next to this frame's
+// lighting; its shadow pipeline follows the lighting.  The shadow pipeline needs nothing of the head's - its matrices are kernel
+// arguments, its statistics a block of its own that it resets itself, work-list length included.  A frame that keeps its shadow map has no
+// shadow pipeline: in zr_render its resolve takes that place on the host's stream, next to the next frame's camera pipeline.  Never more
+// than two kernels side by side: a third only takes occupancy from the other two (measured).
+static int geometry_passes(zr_ctx* c, ZrEntry entry)
+{
+    const ZrFramePlan& p = c->plan;
+    int rc = frame_begin(c, entry);
+    if (rc == ZR_OK) rc = shadow_pass(c);
+    if (rc == ZR_OK) rc = gbuffer_pass(c);
+    if (rc == ZR_OK && p.one_pixel == ZR_LANE_CAM) rc = empty_pixel_pass(c);      // (a kept frame's head on the lane: behind the upload)
+    if (rc == ZR_OK && (p.ev_cam == ZR_EVCAM_BEHIND_ONE_PIXEL || p.ev_cam == ZR_EVCAM_LANE_END)) HIPCHK(c, hipEventRecord(c->ev_cam, c->cam_s));
+    if (rc == ZR_OK) c->stage = 2;
+    return rc;
+}
+
+extern "C" int zr_render_shadow(zr_ctx* c)
+{
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        int rc = frame_begin(c, ZR_ENTRY_STAGED);
+        if (rc == ZR_OK) rc = shadow_pass(c);
+        if (rc == ZR_OK) c->stage = 1;
+        return rc;
+    });
+}
+
+extern "C" int zr_render_geometry(zr_ctx* c)
+{
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int { return geometry_passes(c, ZR_ENTRY_GEOMETRY); });
+}
+
 // The resolve of a frame whose camera lane left it to the host's stream (gbuffer_pass), behind the wait for ev_cam: same launch, same
 // keys; the history is already marked (vis_now = nullptr) and the coverage tally goes to the frame copy's own block, zeroed here.
-static int deferred_resolve(zr_ctx* c, hipStream_t s)
+static int deferred_resolve(zr_ctx* c)
 {
-    zr_ctx::TimedFrame* const T = c->timed_frame();
-    hipEvent_t* const ev = T ? T->ev : nullptr;
+    const hipStream_t s = lane_stream(c, c->plan.resolve);
     ZrDevStats* const tally = c->d_rstats[c->fcur];
     zr_launch_fill32(tally->covered_part, 0u, 32, s);
-    if (ev) HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_HOST_RESOLVE], s));
+    TIMED(c, s, zr_ctx::EV_HOST_RESOLVE);
     zr_launch_resolve_gbuffer(c->resolve_P, c->d_objs, c->d_owned, c->n_owned, c->d_vis[c->fcur], c->fc[c->fcur].G, c->d_lut, c->d_unorm_lut, nullptr, tally, s, c->resolve_mark);
-    if (ev) HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_RESOLVE], s));
-    c->cov_block = tally; c->resolve_deferred = false; c->fc[c->fcur].g_gen = c->g_gen;
+    TIMED(c, s, zr_ctx::EV_RESOLVE);
+    c->cov_block = tally; c->fc[c->fcur].g_gen = c->plan.g_gen;
     HIPCHK(c, hipGetLastError());
     return ZR_OK;
 }
 
-static int lighting_pass(zr_ctx* c, hipStream_t s)
+static int lighting_pass(zr_ctx* c)
 {
-    zr_ctx::TimedFrame* const T = c->timed_frame();
-    hipEvent_t* const ev = T ? T->ev : nullptr;
+    const hipStream_t s = lane_stream(c, c->plan.lighting);
     ZrLightParams L; light_params(c, &L);
     const FrameCopy& F = c->fc[c->fcur];
     L.empty_rgba = c->empty_ready ? F.empty_rgba : nullptr;
     // The next DRAWN shadow pass follows on this stream and rasterises into the OTHER copy of the map, which nothing reads or
     // writes while this pass runs: clear it here - once; a run of frames that keep their map finds it clear and writes nothing.
     FrameCopy& next = c->fc[c->smap ^ 1];
-    if (c->n_owned && s == c->stream && !c->d_shadow_ext && !next.shadow_cleared) { L.clear_next = (uint32_t*)next.shadow; L.clear_n = c->SD * c->SD; next.shadow_cleared = true; }
+    if (c->n_owned && !c->d_shadow_ext && !next.shadow_cleared) { L.clear_next = (uint32_t*)next.shadow; L.clear_n = c->SD * c->SD; next.shadow_cleared = true; }
     uint32_t* const frame_out = L.packed_out ? (c->d_tiles_ext ? c->d_tiles_ext : c->d_tiles) : c->d_color;
     if (c->shading == ZR_SHADING_FORWARD) {
         // Base.frag over the winners the resolve recorded, with this frame's camera block (frame_begin built it; the overlay fields play no part)
@@ -720,7 +614,7 @@ static int lighting_pass(zr_ctx* c, hipStream_t s)
         if (c->debug_view == 9u)        // GBufferVis mosaic over the lit frame (needs the whole GBuffer: single-rank contexts only)
             zr_launch_gbuffer_vis(L, F.view, F.G, shadow_buf(c), c->cube, c->d_lut, c->d_color, s);
     }
-    if (ev) HIPCHK(c, hipEventRecord(ev[zr_ctx::EV_LIGHTING], s));
+    TIMED(c, s, zr_ctx::EV_LIGHTING);
     HIPCHK(c, hipEventRecord(c->ev_end[c->frame_no % zr_ctx::END_RING], s));      // this frame's GBuffer / shadow map / uniforms copies are free again
     HIPCHK(c, hipGetLastError());
     if (c->timing_now) c->sample_no++;
@@ -735,14 +629,14 @@ extern "C" int zr_render_lighting(zr_ctx* c)
     return zr_guard(c, [&]() -> int {
         if (c->stage != 2) return zr_fail(c, ZR_ERR_STATE, "zr_render_lighting out of order");
         HIPCHK(c, hipSetDevice(c->device));
-        hipStream_t ls = c->stream;
+        const ZrFramePlan& p = c->plan;
         // The one wait of the host's stream per frame: the camera lane's GBuffer (or, where the resolve follows here, its keys and history
         // marks: ev_cam is then recorded ahead of the lane's k_plan) - and, ahead of it on that lane, this frame's k_frame_begin, whose
         // uniforms the empty-pixel pass below reads (the shadow pipeline before it needed nothing of them and did not wait).
-        if (c->camera_on_lane) HIPCHK(c, hipStreamWaitEvent(ls, c->ev_cam, 0));
-        int rc = c->resolve_deferred ? deferred_resolve(c, ls) : ZR_OK;
-        if (rc == ZR_OK && !c->head_on_lane) rc = empty_pixel_pass(c, ls); // the shadow map (possibly reduced over ranks by the host) is final only now
-        if (rc == ZR_OK) rc = lighting_pass(c, ls);
+        if (p.host_waits_ev_cam) HIPCHK(c, hipStreamWaitEvent(lane_stream(c, p.lighting), c->ev_cam, 0));
+        int rc = p.resolve_deferred ? deferred_resolve(c) : ZR_OK;
+        if (rc == ZR_OK && p.one_pixel != ZR_LANE_CAM) rc = empty_pixel_pass(c); // the shadow map (possibly reduced over ranks by the host) is final only now
+        if (rc == ZR_OK) rc = lighting_pass(c);
         return rc;
     });
 }
@@ -753,19 +647,17 @@ extern "C" int zr_render_lighting(zr_ctx* c)
 // frame's lighting.  zr_render therefore runs two lanes: the camera pipeline on the library's high-priority stream cam_s, and
 // shadow pipeline -> lighting on the host's stream.  Whatever the host enqueues on its stream after zr_render is ordered after
 // the finished frame, as before.  ZR_FLAG_SERIAL_PASSES keeps everything on the one stream, as the staged entry points do.
-// A frame that keeps its shadow map resolves on the host's stream (resolve_on_host_lane): camera lane ... -> k_tile -> k_mark -> ev_cam
-// -> k_plan, host's stream wait -> k_resolve_gbuffer -> one-pixel launch -> k_lighting -> ev_end.
-// A frame that keeps its whole camera pass (frame_begin: camera_keep) has no camera pipeline: host's stream upload -> [shadow pipeline] ->
-// one-pixel launch -> k_lighting -> ev_end, over the GBuffer copy of its parity as the last two drawn frames left both; where it keeps its
-// map too (and has kept it for a frame), upload -> one-pixel launch -> ev_cam run on the lane beside the previous frame's k_lighting, and the host's stream waits for ev_cam.
+// A frame that keeps its shadow map resolves on the host's stream: camera lane ... -> k_tile -> k_mark -> ev_cam -> k_plan, host's stream
+// wait -> k_resolve_gbuffer -> one-pixel launch -> k_lighting -> ev_end.
+// A frame that keeps its whole camera pass has no camera pipeline: host's stream upload -> [shadow pipeline] -> one-pixel launch ->
+// k_lighting -> ev_end, over the GBuffer copy of its parity as the last two drawn frames left both; where it keeps its map too (and has
+// kept it for a frame), upload -> one-pixel launch -> ev_cam run on the lane beside the previous frame's k_lighting, and the host's stream waits for ev_cam.
 extern "C" int zr_render(zr_ctx* c)
 {
     if (!c) return ZR_ERR_ARG;
     return zr_guard(c, [&]() -> int {
-        c->in_render = true;
-        int rc = geometry_passes(c);
+        int rc = geometry_passes(c, ZR_ENTRY_RENDER);
         if (rc == ZR_OK) rc = zr_render_lighting(c);
-        c->in_render = false;
         if (rc != ZR_OK) c->stage = 0;
         return rc;
     });
@@ -800,7 +692,7 @@ extern "C" int zr_set_shadow_tiles(zr_ctx* c, uint32_t rank, uint32_t world)
         HIPCHK(c, zr_sync_all(c));
         c->stile_mem.release(); c->d_sowned_rank = c->d_stile_map = nullptr;
         c->stile_rank = 0; c->stile_world = 1; c->s_slots_per_rank = c->sn_tiles; c->n_sowned_rank = 0;
-        c->list_valid[0] = false; zr_casters_changed(c);
+        zr_history_forgotten(c, ZR_HIST_SHADOW_LIST); zr_casters_changed(c);
         if (world == 1) return ZR_OK;
         const ZrTilePartition P = zr_partition(c->stiles_x, c->stiles_y, world, rank);
         HIPCHK(c, upload(c->stile_mem, &c->d_sowned_rank, P.owned)); HIPCHK(c, upload(c->stile_mem, &c->d_stile_map, P.map));

@@ -433,7 +433,7 @@ static int make_work_pools(zr_ctx* c, uint32_t cap_w)
 {
     ZrOwn& P = c->pools;
     P.release();
-    c->work_capacity = 0; c->plan_valid = false;
+    c->work_capacity = 0; zr_history_forgotten(c, ZR_HIST_PLAN);
     for (auto& o : c->objects) o.work_valid = false;      // (the history lived in the pools: zr_scene_finalize reads it before it comes here)
     for (auto& sc : c->sc) sc = {};
     c->sb.bins = nullptr; c->sb.chunk_tab = nullptr; c->tb = {};
@@ -576,17 +576,17 @@ int zr_scene_finalize(zr_ctx* c)
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
     } else {
-        c->vis_history = false;         // work item numbering changed: last frame's visibility says nothing about this scene
-        c->plan_valid = false;          // ... and neither do its per-tile record counts: the next frame counts before it draws (tri_raster)
+        // work item numbering changed: last frame's visibility says nothing about this scene, and neither do its per-tile record counts
+        // (the next frame counts before it draws: tri_raster) or the shadow flags
+        zr_history_forgotten(c, ZR_HIST_VISIBILITY | ZR_HIST_PLAN | ZR_HIST_SHADOW_FLAGS);
         if (c->n_work) HIPCHK(c, hipMemsetAsync(c->d_sflag, 1, c->n_work, c->stream));      // shadow pass: everything is drawn in the first launch
-        c->sflag_history = false;
     }
     c->history_items = carried;
     for (auto& o : c->objects) {        // the numbers the history knows the objects by from here on
         const ZrObject& d = tab[o.draw];
         o.work_base = d.work_base; o.work_inst = d.n_inst; o.work_meshlets = d.n_meshlets; o.work_valid = true;
     }
-    c->list_valid[0] = c->list_valid[1] = false;      // ... and neither do the passes' work lists
+    zr_history_forgotten(c, ZR_HIST_LISTS);           // ... and neither do the passes' work lists
     zr_casters_changed(c);                            // ... nor the kept shadow map: new draw table, maybe new pools
     c->scene_dirty = false;
     return ZR_OK;

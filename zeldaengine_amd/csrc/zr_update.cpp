@@ -62,7 +62,7 @@ int zr_update_end(zr_ctx* c, hipStream_t x)
     c->upd.scatter_s = x; c->upd.scatter_wait[0] = c->upd.scatter_wait[1] = true;
     // The passes' work lists (k_cull_instances) hold the instances that passed the whole-mesh test: rebuilt by the next frame.  The visibility
     // history, the bucket plan and the shadow flags stay: the frame does not depend on them.
-    c->list_valid[0] = c->list_valid[1] = false;
+    zr_history_forgotten(c, ZR_HIST_LISTS);
     // The kept shadow map goes too: a caster moved (instances) or changed shape (vertices - the lists are instance-level and would not
     // have needed rebuilding for that, the map does).  Said at enqueue time: x orders the scatter ahead of the next frame.
     zr_casters_changed(c);
