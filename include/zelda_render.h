@@ -335,6 +335,39 @@ int  zr_read_shadowmap(zr_ctx* ctx, float* dst, size_t bytes);        /* dim*dim
  * zr_render puts on the render stream - what a presenting host with two frames in flight uses instead of zr_read_color. */
 int  zr_copy_frame_async(zr_ctx* ctx, void* color_dev, void* shadow_dev);
 
+/* --- delivering changes ("Delivering to a remote client"; DESIGN.md §5, "Delivering changes") ---
+ * The frame as the 32 x 32 tiles that differ from what was delivered last: what a host that ships frames to a remote client sends instead
+ * of W*H*4 bytes.  The context keeps ONE delivered copy of the frame - what the client holds.  A delivery compares the frame enqueued last
+ * with that copy tile by tile, lists every tile in which any byte of any pixel inside the frame differs, in increasing tile index
+ * t = ty * ceil(W/32) + tx (the numbering of zr_tile_partition), and makes the delivered copy the frame.  The k-th listed tile's pixels
+ * are at pixels + k * 4096: 32 rows of 32 RGBA8 pixels, tile pixel (x, y) = frame pixel (tx*32 + x, ty*32 + y), pixels outside the frame
+ * 0.  Applying a delivery to the client's copy gives exactly zr_read_color's bytes.  The comparison is against the last DELIVERY, not the
+ * previous frame: frames rendered without a delivery in between are skipped over.  The first delivery after zr_set_frame_delta(ctx, 1)
+ * and after zr_frame_delta_reset (a new client) lists every tile and sets full.
+ * Buffers are always full-sized (no truncation case): total_tiles uint32 and total_tiles * 4096 bytes; only the first n_tiles entries
+ * and slots are written, what lies behind them is left untouched. */
+typedef struct zr_frame_delta {   /* 16 bytes */
+    uint32_t n_tiles;      /* tiles listed by this delivery */
+    uint32_t total_tiles;  /* ceil(W/32) * ceil(H/32) */
+    uint32_t full;         /* 1: first delivery after enable / reset - every tile is listed */
+    uint32_t serial;       /* deliveries since enable, this one included (a client notices a lost one) */
+} zr_frame_delta;
+/* enable != 0 allocates the delivered copy, the host form's packed buffer and list, and the marks; 0 releases them.  A context that
+ * never enables it allocates nothing and its frames enqueue what they always did.  ZR_ERR_UNSUPPORTED where the lighting pass does not
+ * write the row-major frame itself (tile_world > 1, ZR_FLAG_PACKED_TILES); between the stages of a frame: ZR_ERR_STATE. */
+int  zr_set_frame_delta(zr_ctx* ctx, int enable);
+int  zr_frame_delta_reset(zr_ctx* ctx);             /* the next delivery is a full one again (serial goes on counting) */
+/* Host form: zr_finish first (its error is passed on, as by zr_read_color), then the header, then n_tiles * 4 and n_tiles * 4096 bytes -
+ * a frame at rest costs a 16-byte copy.  cap_tiles == total_tiles and bytes == total_tiles * 4096, else ZR_ERR_ARG; out_bytes = the
+ * caller's sizeof(zr_frame_delta) (passed like zr_stats). */
+int  zr_read_frame_delta(zr_ctx* ctx, uint32_t* tiles, uint32_t cap_tiles, uint8_t* pixels, size_t bytes, zr_frame_delta* out, size_t out_bytes);
+/* Device form, into caller-owned DEVICE buffers (16 bytes of header; total_tiles uint32; total_tiles * 4096 bytes, 16-byte aligned):
+ * synchronises nothing, ordered on the render stream exactly as zr_copy_frame_async's colour copy - behind the lighting pass of the
+ * frame enqueued last, ahead of whatever the next zr_render enqueues.  The two forms may be mixed: they share the delivered copy in
+ * stream order.
+ * Both: ZR_ERR_STATE while delta is off, before the first finished frame, and between the stages of a frame. */
+int  zr_copy_frame_delta_async(zr_ctx* ctx, void* header_dev, void* tiles_dev, void* pixels_dev);
+
 /* --- object identity of the last frame (which object won each pixel: picking, box selection, per-instance coverage) ---
  * What is reported is the deferred-scene pass's depth-test winner, i.e. what the GBuffer holds: the same in deferred and forward
  * shading and in every debug view.  The skydome and the background are not objects: they never appear and never hide a scene winner.

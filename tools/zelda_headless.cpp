@@ -7,9 +7,12 @@
 //
 //   zelda_headless --root DIR [--world FILE.json] [--livelink PORT [--wait-ms MS]] [--meshlet FILE.meshlet --profab NAME]
 //                  [--size WxH] [--shadow N] [--frames N] [--roll-light-step F] [--debug-view V] [--out FRAME.ppm] [--device D]
-//                  [--pick X,Y[,W,H]] [--incremental]
+//                  [--pick X,Y[,W,H]] [--incremental] [--delta]
 // --incremental applies livelink payloads as a difference from the live scene (zr_livelink_set_incremental): a payload that only moves
 // the camera or a light keeps every object, the visibility history and the shadow map.
+// --delta delivers every frame the way a host with a remote client does (zr_read_frame_delta): only the 32 x 32 tiles that differ from
+// what was delivered last leave the GPU and are applied to a client copy of the frame; it prints `delta <tiles>/<total>` per frame, and
+// --out is written from the client copy.
 // --pick keeps the last frame's per-pixel winners (zr_set_id_capture) and prints what zr_pick finds in the rectangle (default 1 x 1),
 // one JSON line per hit, nearest first - what an editor does on a click.
 #include "../include/zelda_render.h"
@@ -35,7 +38,7 @@ int main(int argc, char** argv)
     uint32_t W = 1920, H = 1080, SD = 1024, frames = 1, debug_view = 0;
     int port = -1, wait_ms = 10000, device = 0;
     float roll_step = 0.0f;
-    bool pick = false, incremental = false; uint32_t px = 0, py = 0, pw = 1, ph = 1;
+    bool pick = false, incremental = false, delta = false; uint32_t px = 0, py = 0, pw = 1, ph = 1;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
@@ -53,6 +56,7 @@ int main(int argc, char** argv)
         else if (a == "--device") device = atoi(next());
         else if (a == "--roll-light-step") roll_step = (float)atof(next());
         else if (a == "--incremental") incremental = true;
+        else if (a == "--delta") delta = true;
         else if (a == "--pick") {
             const int got = sscanf(next(), "%u,%u,%u,%u", &px, &py, &pw, &ph);
             if (got != 2 && got != 4) { fprintf(stderr, "--pick X,Y[,W,H]\n"); return 2; }
@@ -90,12 +94,28 @@ int main(int argc, char** argv)
     if (!have_world) { fprintf(stderr, "zelda_headless: no world (give --world FILE or send one to --livelink PORT)\n"); zr_destroy(c); return 1; }
 
     if (pick && (rc = zr_set_id_capture(c, 1))) return fail(c, "zr_set_id_capture", rc);
+    // --delta: the client's copy of the frame, and full-sized buffers for a delivery (only the listed tiles are written and moved)
+    const uint32_t T = ZR_TILE, tiles_x = (W + T - 1) / T, total = tiles_x * ((H + T - 1) / T);
+    std::vector<uint8_t> client, slots; std::vector<uint32_t> list;
+    if (delta) {
+        client.assign((size_t)W * H * 4, 0); slots.resize((size_t)total * T * T * 4); list.resize(total);
+        if ((rc = zr_set_frame_delta(c, 1))) return fail(c, "zr_set_frame_delta", rc);
+    }
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t f = 0; f < frames; ++f) {
         int reloaded = 0;
         if (port >= 0 && (rc = zr_livelink_poll(c, &reloaded))) return fail(c, "zr_livelink_poll", rc);
         if ((rc = zr_world_update_uniforms(c, 0.0f, roll_step * (float)f, 0.016f * (float)f))) return fail(c, "zr_world_update_uniforms", rc);
         if ((rc = zr_render(c))) return fail(c, "zr_render", rc);
+        if (!delta) continue;
+        zr_frame_delta d;
+        if ((rc = zr_read_frame_delta(c, list.data(), total, slots.data(), slots.size(), &d, sizeof d))) return fail(c, "zr_read_frame_delta", rc);
+        for (uint32_t k = 0; k < d.n_tiles; ++k) {        // the client's apply loop: the rows of each listed tile that lie inside the frame
+            const uint32_t x0 = list[k] % tiles_x * T, y0 = list[k] / tiles_x * T, w = W - x0 < T ? W - x0 : T, h = H - y0 < T ? H - y0 : T;
+            for (uint32_t y = 0; y < h; ++y)
+                memcpy(&client[((size_t)(y0 + y) * W + x0) * 4], &slots[((size_t)k * T + y) * T * 4], (size_t)w * 4);
+        }
+        printf("delta %u/%u\n", d.n_tiles, d.total_tiles);
     }
     if ((rc = zr_finish(c))) return fail(c, "zr_finish", rc);
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -115,7 +135,8 @@ int main(int argc, char** argv)
     }
     if (!out.empty()) {
         std::vector<uint8_t> rgba((size_t)W * H * 4);
-        if ((rc = zr_read_color(c, rgba.data(), rgba.size()))) return fail(c, "zr_read_color", rc);
+        if (delta) rgba = client;
+        else if ((rc = zr_read_color(c, rgba.data(), rgba.size()))) return fail(c, "zr_read_color", rc);
         FILE* fp = fopen(out.c_str(), "wb");
         if (!fp) { fprintf(stderr, "zelda_headless: cannot write %s\n", out.c_str()); zr_destroy(c); return 1; }
         fprintf(fp, "P6\n%u %u\n255\n", W, H);

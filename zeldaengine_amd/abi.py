@@ -56,6 +56,13 @@ VISIBILITY_SIGNATURES = {
     "zr_object_update_instance_visibility_async": [vp_, u32_, u32_, vp_, vp_, u32_, vp_],
     "zr_object_get_visibility": [vp_, u32_, C.POINTER(C.c_int), vp_, C.POINTER(u32_)],
 }
+# delivering changes (include/zelda_render.h, "delivering changes")
+FRAME_DELTA_SIGNATURES = {
+    "zr_set_frame_delta": [vp_, C.c_int],
+    "zr_frame_delta_reset": [vp_],
+    "zr_read_frame_delta": [vp_, vp_, u32_, vp_, C.c_size_t, vp_, C.c_size_t],
+    "zr_copy_frame_delta_async": [vp_, vp_, vp_, vp_],
+}
 del vp_, u32_
 
 
@@ -82,6 +89,14 @@ class WorldDelta(C.Structure):
                 ("objects_reinstanced", C.c_uint32), ("objects_added", C.c_uint32), ("objects_removed", C.c_uint32),
                 ("materials_rebuilt", C.c_uint32), ("history_items", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
+
+class FrameDelta(C.Structure):
+    """ctypes mirror of zr_frame_delta: the 16-byte header of a delivery (passed with its size, like zr_stats)"""
+    _fields_ = [("n_tiles", C.c_uint32), ("total_tiles", C.c_uint32), ("full", C.c_uint32), ("serial", C.c_uint32)]
+
+
+assert C.sizeof(FrameDelta) == 16
+TILE_BYTES = TILE * TILE * 4      # one slot of a delivery
 
 # ZR_WORLD_DIFF_*: the bits of WorldDelta.differs and of engine.world_json_diff
 WORLD_DIFF_CAMERA, WORLD_DIFF_LIGHTS, WORLD_DIFF_SKY, WORLD_DIFF_BACKGROUND, WORLD_DIFF_OBJECTS = 1, 2, 4, 8, 16

@@ -336,6 +336,16 @@ struct zr_ctx {
         unsigned long long* keys = nullptr; zr_hit* hits = nullptr; uint2* obj = nullptr;
     } ids;
 
+    // Delivering changes (zr_delta_host.cpp, zr_delta.hip): all of it made by zr_set_frame_delta(1) through `mem`, released by
+    // zr_set_frame_delta(0).  delivered = what the client holds; flags = a byte per tile, rewritten by every delivery (nothing to clear on
+    // the stream); packed / list / header = the host form's device buffers, h_header its pinned landing place.  full: the next delivery
+    // lists every tile; serial: deliveries since enable.
+    struct Delta {
+        ZrOwn mem; bool on = false, full = true; uint32_t serial = 0;
+        uint32_t *delivered = nullptr, *list = nullptr, *header = nullptr; uint8_t *packed = nullptr, *flags = nullptr;
+        zr_frame_delta* h_header = nullptr;
+    } delta;
+
     ZrOwn cube_mem; CubeDesc cube = {}; uint32_t cube_dim = 0, cube_levels = 0;
     float lut[256]; float* d_lut = nullptr;
     float* d_unorm_lut = nullptr;        // [0..255] = c / 255, [256..1279] = c / 1023 (IEEE quotients, computed on the host)

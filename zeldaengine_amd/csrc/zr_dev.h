@@ -11,6 +11,7 @@
 //   zr_lighting.hip  k_lighting (BaseLighting.frag), k_gbuffer_vis (debug view 9)
 //   zr_forward.hip   k_forward: the forward variant, Base.frag
 //   zr_frame.hip     k_frame_begin, fills, k_untile / k_pack_tiles (multi-GPU composite)
+//   zr_delta.hip     k_delta_mark, k_delta_pack: the frame as the tiles that differ from the last delivery
 //   zr_raster.h      the rasteriser proper (raster_sub, the clipper, k_tile_slow): shared by the shadow and the camera pass
 //   zr_texture.h     texture(sampler2D): mips, trilinear, anisotropic; zr_surface.h: interpolation, ComputeNormal, BaseScene.frag's body
 //   zr_shade.h       Common.glsl's BxDF, PCF, cubemap sampling and the body BaseLighting.frag and Base.frag share

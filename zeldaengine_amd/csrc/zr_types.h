@@ -348,3 +348,7 @@ void zr_launch_untile(const uint32_t* gathered, const uint32_t* tile_map, uint32
                       uint32_t n_tiles, hipStream_t s);
 void zr_launch_pack_tiles(const uint32_t* plane, const uint32_t* tiles, uint32_t n_tiles, uint32_t* packed, uint32_t W, uint32_t H, uint32_t tiles_x,
                           uint32_t pad, hipStream_t s);
+// zr_delta.hip: one delivery of the tiles of `frame` that differ from `delivered` (which becomes the frame); flags: a byte per tile, in
+// whole 64-bit words, the padding 0; packed: 16-byte aligned
+void zr_launch_frame_delta(const uint32_t* frame, uint32_t* delivered, uint8_t* flags, uint32_t* header, uint32_t* list, void* packed,
+                           uint32_t W, uint32_t H, uint32_t tiles_x, uint32_t n_tiles, uint32_t full, uint32_t serial, hipStream_t s);

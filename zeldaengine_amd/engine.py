@@ -60,6 +60,7 @@ def lib():
         "zr_mesh_get_vertices": [vp, u32, vp, C.POINTER(u32)],
         **abi.TEXTURE_UPDATE_SIGNATURES,
         **abi.VISIBILITY_SIGNATURES,
+        **abi.FRAME_DELTA_SIGNATURES,
         "zr_set_cubemap": [vp, vp, u32],
         "zr_set_skydome": [vp, vp, u32, vp, u32, vp],
         "zr_set_background": [vp, vp],
@@ -624,6 +625,38 @@ class Renderer:
     def copy_frame_async(self, color_dev=None, shadow_dev=None):
         """The frame enqueued last -> caller-owned device buffers (addresses), in stream order, no host synchronisation."""
         self._chk(self.L.zr_copy_frame_async(self.h, C.c_void_p(color_dev) if color_dev else None, C.c_void_p(shadow_dev) if shadow_dev else None))
+
+    # ---- delivering changes: the frame as the tiles that differ from what was delivered last
+    def set_frame_delta(self, on=True):
+        """Keep a delivered copy of the frame and deliver differences against it (default off; allocates on enable)."""
+        self._chk(self.L.zr_set_frame_delta(self.h, 1 if on else 0))
+
+    def frame_delta_reset(self):
+        """A new client: the next delivery lists every tile again."""
+        self._chk(self.L.zr_frame_delta_reset(self.h))
+
+    def frame_delta_tiles(self):
+        """How many 32 x 32 tiles the frame has: the size every delivery's buffers are made for."""
+        return ((self.W + abi.TILE - 1) // abi.TILE) * ((self.H + abi.TILE - 1) // abi.TILE)
+
+    def read_frame_delta(self, tiles=None, pixels=None):
+        """One delivery to the host: (tiles[n] uint32 ascending, pixels[n, 32, 32, 4] uint8, header dict).  tiles / pixels: full-sized
+        buffers to deliver into (uint32[total], uint8[total, 32, 32, 4]); only their first n entries are written."""
+        total = self.frame_delta_tiles()
+        if tiles is None:
+            tiles = np.zeros(total, dtype=np.uint32)
+        if pixels is None:
+            pixels = np.zeros((total, abi.TILE, abi.TILE, 4), dtype=np.uint8)
+        assert tiles.dtype == np.uint32 and pixels.dtype == np.uint8 and tiles.flags.c_contiguous and pixels.flags.c_contiguous
+        h = abi.FrameDelta()
+        self._chk(self.L.zr_read_frame_delta(self.h, _ptr(tiles), tiles.size, _ptr(pixels), pixels.nbytes, C.byref(h), C.sizeof(h)))
+        header = {k: int(getattr(h, k)) for k, _ in abi.FrameDelta._fields_}
+        return tiles[:h.n_tiles], pixels.reshape(-1, abi.TILE, abi.TILE, 4)[:h.n_tiles], header
+
+    def copy_frame_delta_async(self, header_dev, tiles_dev, pixels_dev):
+        """One delivery into caller-owned device buffers (addresses: 16 bytes, total uint32, total * 4096 bytes), on the render stream,
+        without a host sync."""
+        self._chk(self.L.zr_copy_frame_delta_async(self.h, C.c_void_p(header_dev), C.c_void_p(tiles_dev), C.c_void_p(pixels_dev)))
 
     # ---- object identity of the last frame
     def set_id_capture(self, on=True):
