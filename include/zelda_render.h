@@ -352,7 +352,8 @@ typedef struct zr_frame_delta {   /* 16 bytes */
     uint32_t full;         /* 1: first delivery after enable / reset - every tile is listed */
     uint32_t serial;       /* deliveries since enable, this one included (a client notices a lost one) */
 } zr_frame_delta;
-/* enable != 0 allocates the delivered copy, the host form's packed buffer and list, and the marks; 0 releases them.  A context that
+/* enable != 0 allocates the delivered copy, the host form's packed buffer and list, and the marks; 0 releases them
+ * (enable == ZR_FRAME_DELTA_PACKED: the compressed forms below as well; every other value behaves as 1).  A context that
  * never enables it allocates nothing and its frames enqueue what they always did.  ZR_ERR_UNSUPPORTED where the lighting pass does not
  * write the row-major frame itself (tile_world > 1, ZR_FLAG_PACKED_TILES); between the stages of a frame: ZR_ERR_STATE. */
 int  zr_set_frame_delta(zr_ctx* ctx, int enable);
@@ -367,6 +368,47 @@ int  zr_read_frame_delta(zr_ctx* ctx, uint32_t* tiles, uint32_t cap_tiles, uint8
  * stream order.
  * Both: ZR_ERR_STATE while delta is off, before the first finished frame, and between the stages of a frame. */
 int  zr_copy_frame_delta_async(zr_ctx* ctx, void* header_dev, void* tiles_dev, void* pixels_dev);
+
+/* --- delivering changes, compressed ("Delivering changes": the record format) ---
+ * zr_set_frame_delta(ctx, ZR_FRAME_DELTA_PACKED) enables the raw forms above and two packed ones beside them, which list the same tiles
+ * but deliver each as a losslessly compressed RECORD instead of 4 096 bytes, encoded on the GPU behind the lighting pass: only the
+ * compressed bytes cross a link.  Going between 1 and ZR_FRAME_DELTA_PACKED while on synchronises and makes or releases the packed forms'
+ * buffers alone: the delivered copy, full and serial stand.  All four forms share them in stream order and may be mixed freely.
+ * A record is a multiple of 8 bytes and at most 4 104:
+ *   bytes 0..3  tile pixel (0, 0), RGBA     4..5  u16: the record's length in 8-byte words     6..7  u16 mode: 0 coded, 1 raw
+ *   mode 0:  8..39  64 width nibbles, group g in byte g / 2, even g in the low nibble;  40..  the groups' payloads, in group order
+ *   mode 1:  8..4103  the tile's 4 096 bytes as a raw slot has them - taken exactly when the coded record would be longer than 4 104
+ * Per channel a value is predicted by the one to its left, in column 0 by the one above; pixel (0, 0) is the header's.  The residual
+ * r = (p - pred) mod 256 is zigzagged: z = 2r for r < 128, else 2 (255 - r) + 1.  The tile is 16 blocks of 8 x 8 pixels (block = by * 4 + bx);
+ * group g = block * 4 + channel has 64 values, value i = block pixel (i & 7, i >> 3), and a width b (0..8) = the bit length of its largest
+ * z.  Its payload is b little-endian 64-bit words, bit i of word k = bit k of value i: a coded record is 40 + 8 * sum(b) bytes, a tile of one
+ * colour 40.  The stream is the records of the listed tiles in list order, back to back; record k is stream[offsets[k] .. offsets[k + 1]),
+ * offsets[0] = 0 and offsets[n_tiles] = bytes.  List, offsets and stream are the same from run to run. */
+#define ZR_FRAME_DELTA_PACKED 3
+#define ZR_FRAME_DELTA_RECORD_MAX 4104u   /* bytes of the longest record */
+typedef struct zr_frame_delta_packed {   /* 32 bytes */
+    uint32_t n_tiles, total_tiles, full, serial;   /* as zr_frame_delta */
+    uint32_t bytes;        /* length of the stream */
+    uint32_t raw_tiles;    /* records in mode 1 */
+    uint32_t reserved[2];  /* 0 */
+} zr_frame_delta_packed;
+/* Host form: zr_finish first, then the header, then n_tiles * 4, (n_tiles + 1) * 4 and `bytes` bytes (at rest: the 32-byte header, and
+ * offsets[0] = 0).  Capacities are always full: cap_tiles == total_tiles, cap_offsets == total_tiles + 1, cap_bytes == total_tiles * 4104,
+ * else ZR_ERR_ARG; what lies behind the written part is left untouched.  out_bytes = the caller's sizeof(zr_frame_delta_packed). */
+int  zr_read_frame_delta_packed(zr_ctx* ctx, uint32_t* tiles, uint32_t cap_tiles, uint32_t* offsets, uint32_t cap_offsets, uint8_t* stream, size_t cap_bytes,
+                                zr_frame_delta_packed* out, size_t out_bytes);
+/* Device form, into caller-owned DEVICE buffers of those capacities (32 bytes of header; stream_dev 16-byte aligned, the others 4-byte):
+ * ordered and unsynchronised exactly as zr_copy_frame_delta_async.
+ * Both: ZR_ERR_STATE while packed delivery is not enabled, whatever the arguments; the other refusals are those of the raw forms, in
+ * their order (arguments first). */
+int  zr_copy_frame_delta_packed_async(zr_ctx* ctx, void* header_dev, void* tiles_dev, void* offsets_dev, void* stream_dev);
+/* The client's side, context-free host code: a packed delivery (n listed tiles, n + 1 offsets, `bytes` of stream) applied to the client's
+ * width * height * 4 copy of the frame; only pixels inside the frame are touched.  The input is taken as hostile and checked as a whole
+ * before anything is written - ZR_ERR_PARSE for: a tile index >= the frame's tiles or not ascending; offsets that do not start at 0, do
+ * not ascend or run past `bytes`; a record whose length word disagrees with its offsets or with 40 + 8 * sum(b), or that is longer than
+ * 4 104 bytes; a width nibble above 8; an unknown mode.  Never reads beyond tiles[n), offsets[n] and stream[bytes). */
+int  zr_frame_delta_decode(const uint32_t* tiles, const uint32_t* offsets, uint32_t n, const uint8_t* stream, size_t bytes, uint32_t width, uint32_t height,
+                           uint8_t* client_rgba8);
 
 /* --- object identity of the last frame (which object won each pixel: picking, box selection, per-instance coverage) ---
  * What is reported is the deferred-scene pass's depth-test winner, i.e. what the GBuffer holds: the same in deferred and forward

@@ -7,12 +7,14 @@
 //
 //   zelda_headless --root DIR [--world FILE.json] [--livelink PORT [--wait-ms MS]] [--meshlet FILE.meshlet --profab NAME]
 //                  [--size WxH] [--shadow N] [--frames N] [--roll-light-step F] [--debug-view V] [--out FRAME.ppm] [--device D]
-//                  [--pick X,Y[,W,H]] [--incremental] [--delta]
+//                  [--pick X,Y[,W,H]] [--incremental] [--delta | --delta-packed]
 // --incremental applies livelink payloads as a difference from the live scene (zr_livelink_set_incremental): a payload that only moves
 // the camera or a light keeps every object, the visibility history and the shadow map.
 // --delta delivers every frame the way a host with a remote client does (zr_read_frame_delta): only the 32 x 32 tiles that differ from
 // what was delivered last leave the GPU and are applied to a client copy of the frame; it prints `delta <tiles>/<total>` per frame, and
 // --out is written from the client copy.
+// --delta-packed does the same through the compressed form (zr_read_frame_delta_packed): the listed tiles leave the GPU as records of the
+// tile codec and zr_frame_delta_decode applies them to the client copy; it prints `delta-packed <tiles>/<total> tiles <bytes> bytes (<raw> raw)`.
 // --pick keeps the last frame's per-pixel winners (zr_set_id_capture) and prints what zr_pick finds in the rectangle (default 1 x 1),
 // one JSON line per hit, nearest first - what an editor does on a click.
 #include "../include/zelda_render.h"
@@ -38,7 +40,7 @@ int main(int argc, char** argv)
     uint32_t W = 1920, H = 1080, SD = 1024, frames = 1, debug_view = 0;
     int port = -1, wait_ms = 10000, device = 0;
     float roll_step = 0.0f;
-    bool pick = false, incremental = false, delta = false; uint32_t px = 0, py = 0, pw = 1, ph = 1;
+    bool pick = false, incremental = false, delta = false, packed = false; uint32_t px = 0, py = 0, pw = 1, ph = 1;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
@@ -57,6 +59,7 @@ int main(int argc, char** argv)
         else if (a == "--roll-light-step") roll_step = (float)atof(next());
         else if (a == "--incremental") incremental = true;
         else if (a == "--delta") delta = true;
+        else if (a == "--delta-packed") delta = packed = true;
         else if (a == "--pick") {
             const int got = sscanf(next(), "%u,%u,%u,%u", &px, &py, &pw, &ph);
             if (got != 2 && got != 4) { fprintf(stderr, "--pick X,Y[,W,H]\n"); return 2; }
@@ -96,10 +99,11 @@ int main(int argc, char** argv)
     if (pick && (rc = zr_set_id_capture(c, 1))) return fail(c, "zr_set_id_capture", rc);
     // --delta: the client's copy of the frame, and full-sized buffers for a delivery (only the listed tiles are written and moved)
     const uint32_t T = ZR_TILE, tiles_x = (W + T - 1) / T, total = tiles_x * ((H + T - 1) / T);
-    std::vector<uint8_t> client, slots; std::vector<uint32_t> list;
+    std::vector<uint8_t> client, slots; std::vector<uint32_t> list, offsets;
     if (delta) {
-        client.assign((size_t)W * H * 4, 0); slots.resize((size_t)total * T * T * 4); list.resize(total);
-        if ((rc = zr_set_frame_delta(c, 1))) return fail(c, "zr_set_frame_delta", rc);
+        client.assign((size_t)W * H * 4, 0); slots.resize((size_t)total * (packed ? ZR_FRAME_DELTA_RECORD_MAX : T * T * 4)); list.resize(total);
+        offsets.resize((size_t)total + 1);
+        if ((rc = zr_set_frame_delta(c, packed ? ZR_FRAME_DELTA_PACKED : 1))) return fail(c, "zr_set_frame_delta", rc);
     }
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t f = 0; f < frames; ++f) {
@@ -108,6 +112,15 @@ int main(int argc, char** argv)
         if ((rc = zr_world_update_uniforms(c, 0.0f, roll_step * (float)f, 0.016f * (float)f))) return fail(c, "zr_world_update_uniforms", rc);
         if ((rc = zr_render(c))) return fail(c, "zr_render", rc);
         if (!delta) continue;
+        if (packed) {                                     // the records cross the link; the client's side is the library's decoder
+            zr_frame_delta_packed d;
+            if ((rc = zr_read_frame_delta_packed(c, list.data(), total, offsets.data(), total + 1, slots.data(), slots.size(), &d, sizeof d)))
+                return fail(c, "zr_read_frame_delta_packed", rc);
+            if ((rc = zr_frame_delta_decode(list.data(), offsets.data(), d.n_tiles, slots.data(), d.bytes, W, H, client.data())))
+                return fail(c, "zr_frame_delta_decode", rc);
+            printf("delta-packed %u/%u tiles %u bytes (%u raw)\n", d.n_tiles, d.total_tiles, d.bytes, d.raw_tiles);
+            continue;
+        }
         zr_frame_delta d;
         if ((rc = zr_read_frame_delta(c, list.data(), total, slots.data(), slots.size(), &d, sizeof d))) return fail(c, "zr_read_frame_delta", rc);
         for (uint32_t k = 0; k < d.n_tiles; ++k) {        // the client's apply loop: the rows of each listed tile that lie inside the frame

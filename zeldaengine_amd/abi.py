@@ -62,6 +62,9 @@ FRAME_DELTA_SIGNATURES = {
     "zr_frame_delta_reset": [vp_],
     "zr_read_frame_delta": [vp_, vp_, u32_, vp_, C.c_size_t, vp_, C.c_size_t],
     "zr_copy_frame_delta_async": [vp_, vp_, vp_, vp_],
+    "zr_read_frame_delta_packed": [vp_, vp_, u32_, vp_, u32_, vp_, C.c_size_t, vp_, C.c_size_t],
+    "zr_copy_frame_delta_packed_async": [vp_, vp_, vp_, vp_, vp_],
+    "zr_frame_delta_decode": [vp_, vp_, u32_, vp_, C.c_size_t, u32_, u32_, vp_],
 }
 del vp_, u32_
 
@@ -95,8 +98,15 @@ class FrameDelta(C.Structure):
     _fields_ = [("n_tiles", C.c_uint32), ("total_tiles", C.c_uint32), ("full", C.c_uint32), ("serial", C.c_uint32)]
 
 
-assert C.sizeof(FrameDelta) == 16
+class FrameDeltaPacked(C.Structure):
+    """ctypes mirror of zr_frame_delta_packed: the 32-byte header of a packed delivery (passed with its size, like zr_stats)"""
+    _fields_ = FrameDelta._fields_ + [("bytes", C.c_uint32), ("raw_tiles", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+assert C.sizeof(FrameDelta) == 16 and C.sizeof(FrameDeltaPacked) == 32
 TILE_BYTES = TILE * TILE * 4      # one slot of a delivery
+FRAME_DELTA_PACKED = 3            # ZR_FRAME_DELTA_PACKED: zr_set_frame_delta's value that enables the packed forms as well
+RECORD_MAX_BYTES = 8 + TILE_BYTES      # ZR_FRAME_DELTA_RECORD_MAX: the longest record of a packed delivery
 
 # ZR_WORLD_DIFF_*: the bits of WorldDelta.differs and of engine.world_json_diff
 WORLD_DIFF_CAMERA, WORLD_DIFF_LIGHTS, WORLD_DIFF_SKY, WORLD_DIFF_BACKGROUND, WORLD_DIFF_OBJECTS = 1, 2, 4, 8, 16

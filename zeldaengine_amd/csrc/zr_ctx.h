@@ -339,11 +339,17 @@ struct zr_ctx {
     // Delivering changes (zr_delta_host.cpp, zr_delta.hip): all of it made by zr_set_frame_delta(1) through `mem`, released by
     // zr_set_frame_delta(0).  delivered = what the client holds; flags = a byte per tile, rewritten by every delivery (nothing to clear on
     // the stream); packed / list / header = the host form's device buffers, h_header its pinned landing place.  full: the next delivery
-    // lists every tile; serial: deliveries since enable.
+    // lists every tile; serial: deliveries since enable.  codec: what ZR_FRAME_DELTA_PACKED adds, through codec_mem - lens = a listed
+    // tile's record length, rewritten by every packed delivery; header / offsets / stream / h_header = the packed host form's buffers (it
+    // shares `list`).  Going between the raw and the packed forms makes or releases these alone.
     struct Delta {
-        ZrOwn mem; bool on = false, full = true; uint32_t serial = 0;
+        ZrOwn mem, codec_mem; bool on = false, full = true; uint32_t serial = 0;
         uint32_t *delivered = nullptr, *list = nullptr, *header = nullptr; uint8_t *packed = nullptr, *flags = nullptr;
         zr_frame_delta* h_header = nullptr;
+        struct Codec {
+            bool on = false; uint16_t* lens = nullptr; uint32_t *header = nullptr, *offsets = nullptr; uint8_t* stream = nullptr;
+            zr_frame_delta_packed* h_header = nullptr;
+        } codec;
     } delta;
 
     ZrOwn cube_mem; CubeDesc cube = {}; uint32_t cube_dim = 0, cube_levels = 0;

@@ -1,12 +1,29 @@
 // zr_delta_host.cpp — delivering a frame as the tiles that changed since the last delivery, behind the C-ABI (zelda_render.h,
 // "delivering changes"): the state (zr_ctx::delta), the host form and the device form.  A delivery is not a stage of the frame: it is two
 // launches (zr_delta.hip) on the render stream behind the lighting pass of the frame enqueued last, where zr_copy_frame_async's copy
-// goes, and the frame schedule knows nothing of it.
+// goes, and the frame schedule knows nothing of it.  The packed forms (zr_set_frame_delta(ctx, ZR_FRAME_DELTA_PACKED)) deliver the same list
+// with every tile as a record of the tile codec: three launches, buffers of their own beside the raw forms', the same delivered copy.
+// zr_frame_delta_decode is the client's side of them and needs no context (zr_delta_codec.h).
 #include "zr_ctx.h"
+#include "zr_delta_codec.h"
 
 #include <cstring>
 
 static constexpr size_t kTileBytes = (size_t)ZR_TILE * ZR_TILE * 4;
+static_assert(sizeof(zr_frame_delta_packed) == 32 && kZrCodecTile == ZR_TILE, "the packed header is eight words; the codec's tile is the frame's");
+
+// What the packed forms need beyond the raw forms' buffers, made into `mem`: the lengths (16 bits per tile, in whole 16-byte words, the
+// padding 0), and the host form's header, offsets and stream with its pinned landing place
+static int delta_make_packed(zr_ctx* c, ZrOwn& mem, zr_ctx::Delta::Codec& P)
+{
+    if ((uint64_t)c->n_tiles * kZrCodecRawBytes > 0xFFFFFFFFull)
+        return zr_fail(c, ZR_ERR_UNSUPPORTED, "zr_set_frame_delta: the frame's packed stream would not fit 32-bit offsets");
+    const size_t len_words = ((size_t)c->n_tiles + 7u) / 8u * 8u;
+    HIPCHK(c, mem.alloc(&P.lens, len_words)); HIPCHK(c, mem.alloc(&P.header, 8)); HIPCHK(c, mem.alloc(&P.offsets, (size_t)c->n_tiles + 1u));
+    HIPCHK(c, mem.alloc(&P.stream, (size_t)c->n_tiles * kZrCodecRawBytes)); HIPCHK(c, mem.host(&P.h_header, 1));
+    HIPCHK(c, zr_fill_sync({ { P.lens, 0, len_words * 2 }, { P.header, 0, 32 } }));
+    return ZR_OK;
+}
 
 extern "C" int zr_set_frame_delta(zr_ctx* c, int enable)
 {
@@ -14,13 +31,20 @@ extern "C" int zr_set_frame_delta(zr_ctx* c, int enable)
     return zr_guard(c, [&]() -> int {
         if (int rc = zr_stage_idle(c, "zr_set_frame_delta", false)) return rc;
         zr_ctx::Delta& D = c->delta;
-        const bool on = enable != 0;
-        if (on == D.on) return ZR_OK;
+        const bool on = enable != 0, codec = enable == ZR_FRAME_DELTA_PACKED;
+        if (on == D.on && (!on || codec == D.codec.on)) return ZR_OK;
         HIPCHK(c, hipSetDevice(c->device));
         if (!on) {
             HIPCHK(c, zr_sync_all(c));           // (deliveries in flight read and write what is released here)
             D.mem.release();
             D = zr_ctx::Delta();
+            return ZR_OK;
+        }
+        if (D.on) {                              // between the raw and the packed forms: the delivered copy, full and serial stand
+            HIPCHK(c, zr_sync_all(c));
+            ZrOwn pmem; zr_ctx::Delta::Codec P;
+            if (codec) { if (int rc = delta_make_packed(c, pmem, P)) return rc; P.on = true; }
+            D.codec_mem = std::move(pmem); D.codec = P;
             return ZR_OK;
         }
         if (c->cfg.tile_world > 1 || (c->cfg.flags & ZR_FLAG_PACKED_TILES))
@@ -32,6 +56,9 @@ extern "C" int zr_set_frame_delta(zr_ctx* c, int enable)
         HIPCHK(c, mem.alloc(&delivered, n)); HIPCHK(c, mem.alloc(&packed, (size_t)c->n_tiles * kTileBytes)); HIPCHK(c, mem.alloc(&list, c->n_tiles));
         HIPCHK(c, mem.alloc(&header, 4)); HIPCHK(c, mem.alloc(&flags, flag_bytes)); HIPCHK(c, mem.host(&h_header, 1));
         HIPCHK(c, zr_fill_sync({ { delivered, 0, n * 4 }, { flags, 0, flag_bytes }, { header, 0, 16 } }));
+        ZrOwn pmem; zr_ctx::Delta::Codec P;
+        if (codec) { if (int rc = delta_make_packed(c, pmem, P)) return rc; P.on = true; }
+        D.codec_mem = std::move(pmem); D.codec = P;
         D.mem = std::move(mem);
         D.delivered = delivered; D.packed = packed; D.list = list; D.header = header; D.flags = flags; D.h_header = h_header;
         D.on = true; D.full = true; D.serial = 0;
@@ -104,5 +131,76 @@ extern "C" int zr_copy_frame_delta_async(zr_ctx* c, void* header_dev, void* tile
         if (int rc = delta_ready(c, "zr_copy_frame_delta_async")) return rc;
         HIPCHK(c, hipSetDevice(c->device));
         return delta_enqueue(c, (uint32_t*)header_dev, (uint32_t*)tiles_dev, pixels_dev);
+    });
+}
+
+// ------------------------------------------------------------------------------------------------ the packed forms
+
+// Packed delivery is enabled: asked before the arguments are looked at, so that a host in mode 1 hears ZR_ERR_STATE whatever it passed
+static int delta_packed_enabled(zr_ctx* c, const char* what)
+{
+    if (c->delta.on && c->delta.codec.on) return ZR_OK;
+    return zr_fail(c, ZR_ERR_STATE, std::string(what) + ": packed delivery is not enabled (zr_set_frame_delta with ZR_FRAME_DELTA_PACKED)");
+}
+
+static int delta_enqueue_packed(zr_ctx* c, uint32_t* header_dev, uint32_t* list_dev, uint32_t* offsets_dev, void* stream_dev)
+{
+    zr_ctx::Delta& D = c->delta;
+    const uint32_t serial = D.serial + 1u;
+    zr_launch_frame_delta_packed(c->d_color, D.delivered, D.flags, D.codec.lens, header_dev, list_dev, offsets_dev, stream_dev, c->W, c->H, c->tiles_x, c->n_tiles,
+                                 D.full ? 1u : 0u, serial, c->stream);
+    HIPCHK(c, hipGetLastError());
+    D.serial = serial; D.full = false;
+    return ZR_OK;
+}
+
+extern "C" int zr_read_frame_delta_packed(zr_ctx* c, uint32_t* tiles, uint32_t cap_tiles, uint32_t* offsets, uint32_t cap_offsets, uint8_t* stream, size_t cap_bytes,
+                                          zr_frame_delta_packed* out, size_t out_bytes)
+{
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        if (int rc = delta_packed_enabled(c, "zr_read_frame_delta_packed")) return rc;
+        ARGCHK(c, tiles && offsets && stream && out && out_bytes >= sizeof(zr_frame_delta_packed));
+        ARGCHK(c, cap_tiles == c->n_tiles && cap_offsets == c->n_tiles + 1u && cap_bytes == (size_t)c->n_tiles * kZrCodecRawBytes);
+        int rc = delta_ready(c, "zr_read_frame_delta_packed");
+        if (rc == ZR_OK) rc = zr_finish(c);
+        const zr_ctx::Delta::Codec& P = c->delta.codec;
+        if (rc == ZR_OK) rc = delta_enqueue_packed(c, P.header, c->delta.list, P.offsets, P.stream);
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(P.h_header, P.header, sizeof(zr_frame_delta_packed), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        const zr_frame_delta_packed h = *P.h_header;
+        if (h.n_tiles > c->n_tiles || h.bytes > cap_bytes) return zr_fail(c, ZR_ERR_DEVICE, "zr_read_frame_delta_packed: more listed than the frame has");
+        offsets[0] = 0u;
+        if (h.n_tiles) {                         // the compressed bytes are all that cross the link
+            HIPCHK(c, hipMemcpyAsync(tiles, c->delta.list, (size_t)h.n_tiles * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(offsets, P.offsets, ((size_t)h.n_tiles + 1u) * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(stream, P.stream, h.bytes, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+        memcpy(out, &h, sizeof h);
+        return ZR_OK;
+    });
+}
+
+extern "C" int zr_copy_frame_delta_packed_async(zr_ctx* c, void* header_dev, void* tiles_dev, void* offsets_dev, void* stream_dev)
+{
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        if (int rc = delta_packed_enabled(c, "zr_copy_frame_delta_packed_async")) return rc;
+        ARGCHK(c, header_dev && tiles_dev && offsets_dev && stream_dev);
+        ARGCHK(c, (uintptr_t)header_dev % 4 == 0 && (uintptr_t)tiles_dev % 4 == 0 && (uintptr_t)offsets_dev % 4 == 0 && (uintptr_t)stream_dev % 16 == 0);
+        if (int rc = delta_ready(c, "zr_copy_frame_delta_packed_async")) return rc;
+        HIPCHK(c, hipSetDevice(c->device));
+        return delta_enqueue_packed(c, (uint32_t*)header_dev, (uint32_t*)tiles_dev, (uint32_t*)offsets_dev, stream_dev);
+    });
+}
+
+extern "C" int zr_frame_delta_decode(const uint32_t* tiles, const uint32_t* offsets, uint32_t n, const uint8_t* stream, size_t bytes, uint32_t width, uint32_t height,
+                                     uint8_t* client_rgba8)
+{
+    if (!offsets || !client_rgba8 || !width || !height || (n && (!tiles || !stream))) return ZR_ERR_ARG;
+    return zr_guard(nullptr, [&]() -> int {
+        return zr_codec_apply(tiles, offsets, n, stream, bytes, width, height, client_rgba8) ? ZR_OK : ZR_ERR_PARSE;
     });
 }

@@ -352,3 +352,7 @@ void zr_launch_pack_tiles(const uint32_t* plane, const uint32_t* tiles, uint32_t
 // whole 64-bit words, the padding 0; packed: 16-byte aligned
 void zr_launch_frame_delta(const uint32_t* frame, uint32_t* delivered, uint8_t* flags, uint32_t* header, uint32_t* list, void* packed,
                            uint32_t W, uint32_t H, uint32_t tiles_x, uint32_t n_tiles, uint32_t full, uint32_t serial, hipStream_t s);
+// ... and one packed delivery (zr_delta_codec.h): header 8 words, offsets n_tiles + 1, stream 16-byte aligned with room for n_tiles records
+// of 4 104 bytes; lens: 16 bits per tile in whole 16-byte words, the padding 0
+void zr_launch_frame_delta_packed(const uint32_t* frame, uint32_t* delivered, uint8_t* flags, uint16_t* lens, uint32_t* header, uint32_t* list, uint32_t* offsets,
+                                  void* stream, uint32_t W, uint32_t H, uint32_t tiles_x, uint32_t n_tiles, uint32_t full, uint32_t serial, hipStream_t s);

@@ -249,6 +249,20 @@ def world_json_diff(a, b):
     return d.value
 
 
+def frame_delta_decode(tiles, offsets, stream, client):
+    """zr_frame_delta_decode, the client's side of a packed delivery (host code only): tiles uint32[n], offsets uint32[n + 1], stream
+    uint8[>= offsets[n]] applied in place to client, an (H, W, 4) uint8 copy of the frame.  A malformed delivery raises
+    ZeldaRenderError(ZR_ERR_PARSE) and writes nothing."""
+    tiles, offsets = np.ascontiguousarray(tiles, dtype=np.uint32), np.ascontiguousarray(offsets, dtype=np.uint32)
+    stream = np.ascontiguousarray(stream, dtype=np.uint8)
+    assert client.dtype == np.uint8 and client.ndim == 3 and client.shape[2] == 4 and client.flags.c_contiguous and client.flags.writeable
+    assert offsets.size == tiles.size + 1
+    rc = lib().zr_frame_delta_decode(_ptr(tiles), _ptr(offsets), tiles.size, _ptr(stream), stream.size, client.shape[1], client.shape[0], _ptr(client))
+    if rc:
+        raise ZeldaRenderError(rc, "zr_frame_delta_decode: the delivery is malformed")
+    return client
+
+
 def _delta_dict(d):
     return {k: getattr(d, k) for k, _ in abi.WorldDelta._fields_ if k not in ("struct_bytes", "reserved")}
 
@@ -628,8 +642,9 @@ class Renderer:
 
     # ---- delivering changes: the frame as the tiles that differ from what was delivered last
     def set_frame_delta(self, on=True):
-        """Keep a delivered copy of the frame and deliver differences against it (default off; allocates on enable)."""
-        self._chk(self.L.zr_set_frame_delta(self.h, 1 if on else 0))
+        """Keep a delivered copy of the frame and deliver differences against it (default off; allocates on enable).
+        on = abi.FRAME_DELTA_PACKED enables the packed forms as well."""
+        self._chk(self.L.zr_set_frame_delta(self.h, int(on)))
 
     def frame_delta_reset(self):
         """A new client: the next delivery lists every tile again."""
@@ -657,6 +672,28 @@ class Renderer:
         """One delivery into caller-owned device buffers (addresses: 16 bytes, total uint32, total * 4096 bytes), on the render stream,
         without a host sync."""
         self._chk(self.L.zr_copy_frame_delta_async(self.h, C.c_void_p(header_dev), C.c_void_p(tiles_dev), C.c_void_p(pixels_dev)))
+
+    def read_frame_delta_packed(self, tiles=None, offsets=None, stream=None):
+        """One packed delivery to the host: (tiles[n] uint32 ascending, offsets[n + 1] uint32, stream[bytes] uint8, header dict).  tiles /
+        offsets / stream: full-sized buffers to deliver into (uint32[total], uint32[total + 1], uint8[total * abi.RECORD_MAX_BYTES]);
+        only their first n, n + 1 and `bytes` entries are written."""
+        total = self.frame_delta_tiles()
+        tiles = np.zeros(total, dtype=np.uint32) if tiles is None else tiles
+        offsets = np.zeros(total + 1, dtype=np.uint32) if offsets is None else offsets
+        stream = np.zeros(total * abi.RECORD_MAX_BYTES, dtype=np.uint8) if stream is None else stream
+        assert tiles.dtype == np.uint32 and offsets.dtype == np.uint32 and stream.dtype == np.uint8
+        assert tiles.flags.c_contiguous and offsets.flags.c_contiguous and stream.flags.c_contiguous
+        h = abi.FrameDeltaPacked()
+        self._chk(self.L.zr_read_frame_delta_packed(self.h, _ptr(tiles), tiles.size, _ptr(offsets), offsets.size, _ptr(stream), stream.nbytes,
+                                                    C.byref(h), C.sizeof(h)))
+        header = {k: int(getattr(h, k)) for k, _ in abi.FrameDeltaPacked._fields_ if k != "reserved"}
+        return tiles[:h.n_tiles], offsets[:h.n_tiles + 1], stream.reshape(-1)[:h.bytes], header
+
+    def copy_frame_delta_packed_async(self, header_dev, tiles_dev, offsets_dev, stream_dev):
+        """One packed delivery into caller-owned device buffers (addresses: 32 bytes, total uint32, total + 1 uint32, total *
+        abi.RECORD_MAX_BYTES bytes 16-byte aligned), on the render stream, without a host sync."""
+        self._chk(self.L.zr_copy_frame_delta_packed_async(self.h, C.c_void_p(header_dev), C.c_void_p(tiles_dev), C.c_void_p(offsets_dev),
+                                                          C.c_void_p(stream_dev)))
 
     # ---- object identity of the last frame
     def set_id_capture(self, on=True):
