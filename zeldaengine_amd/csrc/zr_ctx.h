@@ -17,6 +17,7 @@
 #include "zr_ids.h"
 #include "zr_meshlet.h"
 #include "zr_types.h"
+#include "zr_world_doc.h"
 
 // The owner of one lifetime's HIP resources: device memory, pinned host memory, events and streams are made through it, and it frees
 // what it made, newest first, on release() and when it is destroyed.  The kernel-argument structs keep their raw pointers: views into
@@ -147,22 +148,6 @@ static inline ZrMipLevel zr_mip_level(uint32_t w, uint32_t h, uint32_t level)
     return L;
 }
 
-// XkWorld (ZE:1025-1291) as parsed from JSON
-struct ZrLightDesc { float Position[3]; uint32_t Type; float Color[3]; float Intensity; float Direction[3]; float Radius; float ExtraData[4]; };
-struct ZrObjectDesc {
-    uint32_t RenderFlags = 0; std::string ProfabName; uint32_t InstanceCount = 0;
-    float MinRadius = 0, MaxRadius = 0, MinRotYaw = 0, MaxRotYaw = 0, MinRotRoll = 0, MaxRotRoll = 0,
-          MinRotPitch = 0, MaxRotPitch = 0, MinPScale = 0, MaxPScale = 0;
-};
-struct ZrWorld {
-    bool EnableSkydome = true, OverrideSkydome = false; std::string SkydomeFileName;
-    bool OverrideCubemap = false; std::string CubemapFileNames[6];
-    bool EnableBackground = false, OverrideBackground = false; std::string BackgroundFileName;
-    zr_camera MainCamera;
-    std::vector<ZrLightDesc> DirectionalLights, PointLights, SpotLights;
-    std::vector<ZrObjectDesc> ObjectDescs;
-    bool loaded = false;
-};
 struct ZrProfab { uint32_t mesh; ZrMaterialHost mat; };
 
 // Two frames in flight (the reference does: MAX_FRAMES_IN_FLIGHT, ZE:77): what a lighting pass reads is double-buffered, and this is one
@@ -464,6 +449,10 @@ int zr_object_add_internal(zr_ctx* c, uint32_t mesh_id, const ZrMaterialHost& ma
 // zr_dist.cpp
 void zr_dist_destroy(zr_ctx* c);
 hipError_t zr_dist_sync(zr_ctx* c);
+// zr_world.cpp, for zr_livelink_poll: a parsed world instantiated / applied as a difference, what either throws turned into the world
+// path's own codes
+int zr_apply_world_guarded(zr_ctx* c, const ZrWorld& w);
+int zr_update_world_guarded(zr_ctx* c, const ZrWorld& w, zr_world_delta& D);
 // zr_assets.cpp
 std::string zr_asset_search(const zr_ctx* c, const std::string& name);
 int zr_profab_from_disk(zr_ctx* c, const std::string& name, int* found);
