@@ -82,6 +82,22 @@ def test_host_sources_are_split_by_concern_and_share_their_idioms():
     assert not long, long
 
 
+def test_kernel_files_share_their_steps():
+    """The steps the kernels that draw geometry share exist once (zr_dev.h, zr_raster.h): a work item's record (bin_entry), the empty
+    key, a tile's context in tile-relative coordinates; the arms nothing instantiated are gone; the two pass files did not grow."""
+    csrc = os.path.join(ROOT, "zeldaengine_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
+
+    def count(s):
+        return sum(t.count(s) for t in text.values())
+    assert count("be.counts =") == 1
+    assert count("<< 32 | ZR_EMPTY_PRIM") == 1
+    assert count("T.px0 = 0") == 1
+    assert count("find_object_work(objs, (int)P.n_objects") <= 2
+    assert count("k_tile_slow") == 0 and count("vis_clear") == 0
+    assert text["zr_shadow.hip"].count("\n") <= 517 and text["zr_camera.hip"].count("\n") <= 842
+
+
 def test_no_gpu_means_loud_failure_not_fallback():
     """Without a HIP device zr_create fails with ZR_ERR_DEVICE and Renderer raises: there is no CPU path in the product."""
     import torch

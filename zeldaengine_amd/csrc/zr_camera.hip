@@ -1,5 +1,5 @@
 // zr_camera.hip — the camera pass (deferred-scene pass, ZE:3417-3480) as triangle-level binning: k_hiz_build, k_select, k_geom<HIZ>,
-// k_plan, k_tile<MODE, LAST>, k_sky_tiles.  See zr_dev.h for the map of the kernel files.
+// k_plan, k_tile<LAST>, k_sky_tiles.  See zr_dev.h for the map of the kernel files.
 #include "zr_dev.h"
 #include "zr_raster.h"
 
@@ -119,15 +119,7 @@ __global__ __launch_bounds__(256) void k_select(ZrPass P, const ZrObject* __rest
     for (int j = 0; j < 4; ++j) {
         if (!take[j]) continue;
         // the work id is decoded here, lane-parallel: k_geom's wave starts every load of the meshlet from this one record
-        const ZrObject* __restrict__ O = objs + find_object_work(objs, (int)P.n_objects, w[j]);
-        const uint32_t local = w[j] - O->work_base;
-        const uint32_t inst_i = local / O->n_meshlets, mi = local - inst_i * O->n_meshlets;
-        const XkMeshlet* __restrict__ ml = O->meshlets + mi;
-        ZrBinEntry be;
-        const uint4 mh = ld_global((const uint4*)ml);            // VertexOffset, VertexCount, TriangleOffset, TriangleCount
-        be.mpos = O->mpos + mh.x; be.mtri = O->mtri + ld_global(&ml->BindlessContext); be.inst = O->inst + inst_i;
-        be.counts = mh.y | mh.w << 8 | (O->instanced ? 1u << 16 : 0u);
-        be.prim_base = O->prim_base + inst_i * O->n_tris;
+        const ZrBinEntry be = bin_entry(objs, (int)P.n_objects, w[j]);
         sel[wbase[j * 4 + (int)wv] + (uint32_t)__popcll(m[j] & ((1ull << lane) - 1ull))] = be;
     }
     if (threadIdx.x == 0 && nocc) atomicAdd(&stats->hiz_culled, nocc);
@@ -138,7 +130,7 @@ __global__ __launch_bounds__(256) void k_select(ZrPass P, const ZrObject* __rest
 // 64 px - that reaches the tile has its vertices within [-16384, 24576] sub-pixel units of it) with their depth bits, and the primitive id:
 //   plane A: (X0 | Y0 << 16, z0, X1 | Y1 << 16, z1)      plane B: (X2 | Y2 << 16, z2, prim, 0)
 // TILE BUCKETS.  Every tile owns a stretch [tile_base, tile_base + tile_cap) of the record arrays, laid out by k_plan at the end of the
-// PREVIOUS frame from that frame's own per-tile counts (+ 25 % + 32): k_geom appends a meshlet's records for a tile with ONE returning add on
+// PREVIOUS frame from that frame's own per-tile counts (+ 25 % + ZR_BUCKET_SLACK): k_geom appends a meshlet's records for a tile with ONE returning add on
 // the tile's cursor, k_tile reads its tile's stretch as one contiguous run.  No scan and no index list sit between the two kernels (they
 // were k_scan_tri + k_index: two launches, 33 us per frame alone, on the camera lane's critical path, and a 20 MB index list).  What does
 // not fit its bucket - the camera moved, a tile got busier than last frame - goes to ONE overflow region (in ZR_OVER_SECTIONS sections, by
@@ -153,22 +145,9 @@ __device__ __forceinline__ uint32_t pk_sub16(uint32_t a, uint32_t b)      // (a.
     uint32_t o; __builtin_memcpy(&o, &r, 4);
     return o;
 }
-struct RecTri { SV a, b, c; uint32_t prim; };
-__device__ __forceinline__ RecTri rec_load(const uint4 qa, const uint4 qb)
-{
-    RecTri t;
-    t.a.X = (int)(short)(qa.x & 0xFFFFu); t.a.Y = (int)qa.x >> 16; t.a.z = zr_u2f(qa.y); t.a.rw = 0.0f;
-    t.b.X = (int)(short)(qa.z & 0xFFFFu); t.b.Y = (int)qa.z >> 16; t.b.z = zr_u2f(qa.w); t.b.rw = 0.0f;
-    t.c.X = (int)(short)(qb.x & 0xFFFFu); t.c.Y = (int)qb.x >> 16; t.c.z = zr_u2f(qb.y); t.c.rw = 0.0f;
-    t.prim = qb.z;
-    return t;
-}
-// the tiles a drawn triangle's clipped pixel box reaches, packed tx0 | ty0 << 8 | tx1 << 16 | ty1 << 24; ZR_NO_TILES: draws nothing
+__device__ __forceinline__ RecTri rec_load(const uint4 qa, const uint4 qb) { return tri_unpack(qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z); }
+// the tiles a drawn triangle's clipped pixel box reaches (a TileRect word); ZR_NO_TILES: draws nothing
 #define ZR_NO_TILES 0x0000FFFFu          // tx0 = ty0 = 255 > tx1 = ty1 = 0: touches no tile
-__device__ __forceinline__ bool rect_has(uint32_t r, int tx, int ty)
-{
-    return (int)(r & 255u) <= tx && tx <= (int)((r >> 16) & 255u) && (int)((r >> 8) & 255u) <= ty && ty <= (int)(r >> 24);
-}
 
 // Max depth already in the key buffer (per the pyramid Z) over the pixel blocks a snapped box touches: 4 x 4 blocks for a box under 16
 // pixels, else 8 x 8 (blocks of other ranks' tiles hold 0).  A triangle whose least vertex depth lies behind it cannot win a pixel.
@@ -218,38 +197,25 @@ void k_geom(ZrPass P, const ZrBinEntry* __restrict__ sel, ZrHiz Z, ZrTriBins B, 
     for (uint32_t i = wave_id; i < n; i += n_waves) {
         const ZrBinEntry be = nx;
         if (i + n_waves < n) nx = ld_record(sel + (i + n_waves));
-        const float4* __restrict__ mp = be.mpos;
-        const uint2* __restrict__ tw = be.mtri;
-        const ZrInstance* __restrict__ ip = be.inst;
-        const uint32_t counts = be.counts, pbase = be.prim_base;
-        const uint32_t vcount = counts & 255u, tcount = (counts >> 8) & 255u;
-        const bool instanced = (counts >> 16) & 1u;
-        uint2 tri_w[2];
-        tri_w[0] = lane < tcount ? ld_global(tw + lane) : make_uint2(0u, 0u);
-        tri_w[1] = lane + WAVE < tcount ? ld_global(tw + lane + WAVE) : make_uint2(0u, 0u);
-        const float4 pp = lane < vcount ? ld_global(mp + lane) : make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-        const ZrInstance I = ld_record(ip);
-
-        lds_fence();   // this wave's previous readers are done with its staging area
-        bool flagged;
+        const MeshletHead H = meshlet_head(P.PVM, be, lane);
+        const uint32_t tcount = H.tcount, pbase = H.pbase;
+        const uint2 tri_w[2] = { H.tri_w[0], H.tri_w[1] };
+        const zf4 c = H.c;
+        const float FM = 3.402823466e38f, gb = ZR_GUARD * c.w;
+        const bool fin = __builtin_fabsf(c.x) <= FM && __builtin_fabsf(c.y) <= FM && __builtin_fabsf(c.z) <= FM && __builtin_fabsf(c.w) <= FM;
+        const bool odd = !fin || c.x < -c.w || c.x > c.w || c.y < -c.w || c.y > c.w || c.z < 0.0f || c.z > c.w ||
+                         !(c.w > 0.0f) || __builtin_fabsf(c.x) > gb || __builtin_fabsf(c.y) > gb;
+        const bool flagged = __ballot(lane < H.vcount && odd) != 0ull;
         int lo2 = 0x7FFF7FFF, hi2 = (int)0x80008000, zb = 0x7FFFFFFF;      // this lane's share of the meshlet's pixel box / least depth
-        {
-            const zf4 c = zr_mat4_point(P.PVM, vs_position(zr3(pp.x, pp.y, pp.z), I, instanced));
-            const float FM = 3.402823466e38f, gb = ZR_GUARD * c.w;
-            const bool fin = __builtin_fabsf(c.x) <= FM && __builtin_fabsf(c.y) <= FM && __builtin_fabsf(c.z) <= FM && __builtin_fabsf(c.w) <= FM;
-            const bool odd = !fin || c.x < -c.w || c.x > c.w || c.y < -c.w || c.y > c.w || c.z < 0.0f || c.z > c.w ||
-                             !(c.w > 0.0f) || __builtin_fabsf(c.x) > gb || __builtin_fabsf(c.y) > gb;
-            flagged = __ballot(lane < vcount && odd) != 0ull;
-            if (lane < vcount) {
-                const uint32_t f = flagged ? vertex_flags(c) : 0u;
-                SV sv; sv.X = 0; sv.Y = 0; sv.z = 0.0f; sv.rw = 0.0f;
-                if (!(f & 129u)) sv = project(c, P.hw, P.hh);
-                vstage[wv][lane] = make_int4(sv.X, sv.Y, (int)zr_f2u(sv.z), (int)f);      // snapped x, y (absolute), depth, clip flags
-                if (pyramid && !flagged) {
-                    lo2 = (clamp16((sv.X - 128 + 255) >> 8) & 0xFFFF) | (clamp16((sv.Y - 128 + 255) >> 8) << 16);
-                    hi2 = (clamp16((sv.X - 128) >> 8) & 0xFFFF) | (clamp16((sv.Y - 128) >> 8) << 16);
-                    zb = (int)zr_f2u(sv.z + 0.0f);
-                }
+        if (lane < H.vcount) {
+            const uint32_t f = flagged ? vertex_flags(c) : 0u;
+            SV sv; sv.X = 0; sv.Y = 0; sv.z = 0.0f; sv.rw = 0.0f;
+            if (!(f & 129u)) sv = project(c, P.hw, P.hh);
+            vstage[wv][lane] = make_int4(sv.X, sv.Y, (int)zr_f2u(sv.z), (int)f);      // snapped x, y (absolute), depth, clip flags
+            if (pyramid && !flagged) {
+                lo2 = (clamp16((sv.X - 128 + 255) >> 8) & 0xFFFF) | (clamp16((sv.Y - 128 + 255) >> 8) << 16);
+                hi2 = (clamp16((sv.X - 128) >> 8) & 0xFFFF) | (clamp16((sv.Y - 128) >> 8) << 16);
+                zb = (int)zr_f2u(sv.z + 0.0f);
             }
         }
         bool hz_local = false;           // wave-uniform: hzs[wv] holds this meshlet's 4 x 4-pixel blocks, (hz_x0, hz_y0) the first one
@@ -303,7 +269,7 @@ void k_geom(ZrPass P, const ZrBinEntry* __restrict__ sel, ZrHiz Z, ZrTriBins B, 
                     const int bx0 = max((imin3(r0.x, r1.x, r2.x) - 128 + 255) >> 8, 0), bx1 = min((imax3(r0.x, r1.x, r2.x) - 128) >> 8, (int)P.W - 1);
                     const int by0 = max((imin3(r0.y, r1.y, r2.y) - 128 + 255) >> 8, 0), by1 = min((imax3(r0.y, r1.y, r2.y) - 128) >> 8, (int)P.H - 1);
                     cls = (A < 0 && bx0 <= bx1 && by0 <= by1) ? 2 : 0;
-                    if (cls == 2) slow_rect = (uint32_t)(bx0 / TILE) | (uint32_t)(by0 / TILE) << 8 | (uint32_t)(bx1 / TILE) << 16 | (uint32_t)(by1 / TILE) << 24;
+                    if (cls == 2) slow_rect = rect_of_pixels(bx0, by0, bx1, by1);
                 }
                 if (cls == 2) is_slow = true;
                 else if (cls == 1) {
@@ -338,15 +304,15 @@ void k_geom(ZrPass P, const ZrBinEntry* __restrict__ sel, ZrHiz Z, ZrTriBins B, 
                     if (pos_r < B.slow_cap / 2u) {
                         const uint32_t li[3] = { i0, i1, i2 };
                         for (int k = 0; k < 3; ++k) {
-                            const float4 pk = ld_global(mp + li[k]);
-                            const zf4 cc = zr_mat4_point(P.PVM, vs_position(zr3(pk.x, pk.y, pk.z), I, instanced));
+                            const float4 pk = ld_global(H.mp + li[k]);
+                            const zf4 cc = zr_mat4_point(P.PVM, vs_position(zr3(pk.x, pk.y, pk.z), H.I, H.instanced));
                             B.slow[4u * pos + (uint32_t)k] = make_uint4(zr_f2u(cc.x), zr_f2u(cc.y), zr_f2u(cc.z), zr_f2u(cc.w));
                         }
                         B.slow[4u * pos + 3u] = make_uint4(prim, slow_rect, 0u, 0u);
                     } else { stats->overflow = 1u; stats->overflow_sticky = ZR_OVF_SLOW; }
                 }
             }
-            if (alive && !hidden) trect[round] = (uint32_t)(x0 / TILE) | (uint32_t)(y0 / TILE) << 8 | (uint32_t)(x1 / TILE) << 16 | (uint32_t)(y1 / TILE) << 24;
+            if (alive && !hidden) trect[round] = rect_of_pixels(x0, y0, x1, y1);
         }
         // ---- the meshlet's own rectangle of tiles (a small triangle spans at most 3 x 3; the meshlet's usually 1 .. 4 tiles in all)
         const unsigned long long any = __ballot(trect[0] != ZR_NO_TILES || trect[1] != ZR_NO_TILES);
@@ -576,7 +542,7 @@ __global__ __launch_bounds__(1024) void k_plan(ZrTriBins B, const uint32_t* __re
 // round 1's in the first half of the list, round 2's in the second) - the usual frame has none, and as a kernel of its own that check
 // cost the camera lane 25-50 us of waiting for room beside the shadow rasteriser - and fold k_geom's per-wave Hi-Z tallies into the
 // statistics.  The clipper is inlined under this kernel's own register budget (it spills; the path is rare).
-template <int MODE, bool LAST>
+template <bool LAST>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8)))
 void k_tile(ZrPass P, ZrTriBins B, ZrDevStats* __restrict__ stats, int slot,
             unsigned long long* __restrict__ vis64, const uint32_t* __restrict__ owned_tiles, uint32_t n_owned)
@@ -605,21 +571,16 @@ void k_tile(ZrPass P, ZrTriBins B, ZrDevStats* __restrict__ stats, int slot,
             uh[0] = ct.x; uh[1] = min(n_in - lo, len); uh[2] = B.tile_base[ct.x] + lo;
             uh[3] = (ct.y == 0u && n_all > tcap) ? min(B.over_cursor[ri * ZR_OVER_SECTIONS + (ct.x & (ZR_OVER_SECTIONS - 1u))], sec_cap) : 0u;
         }
-        for (uint32_t i = tid; i < TILE_PIX; i += 256u) keys64[i] = (unsigned long long)0x3F800000u << 32 | ZR_EMPTY_PRIM;
+        keys_clear(keys64, tid, 256u);
         __syncthreads();
         const uint32_t tile = wave_uniform(uh[0]), n_own = wave_uniform(uh[1]), rec0 = wave_uniform(uh[2]), n_sift = wave_uniform(uh[3]);
         const uint32_t n_unit = n_own + n_sift;
         if (n_unit == 0u) {           // nothing for this unit (an empty tile keeps its one unit): the next one
-            if (first) { first = false; __syncthreads(); unit += gridDim.x; continue; }
-            if (tid == 0) cur_unit = 2u * gridDim.x + atomicAdd(&stats->chunk_counter[slot], 1u);
-            __syncthreads();
-            unit = cur_unit;
-            __syncthreads();
+            unit = claim_unit(first, unit, &stats->chunk_counter[slot], &cur_unit, tid);
             continue;
         }
-        const int tpx0 = (int)(tile % P.tiles_x) * TILE, tpy0 = (int)(tile / P.tiles_x) * TILE;
-        TileCtx T;
-        T.px0 = 0; T.py0 = 0; T.W = (int)P.W - tpx0; T.H = (int)P.H - tpy0;
+        int tpx0, tpy0;
+        const TileCtx T = tile_ctx(P, tile, tpx0, tpy0);
         const int wx1 = min(TILE - 1, T.W - 1), wy1 = min(TILE - 1, T.H - 1);
         // The unit's batches of <= ZR_TCHUNK records go into the same keys (one clear and one merge per unit, not per batch): first the unit's
         // share of the bucket, one contiguous run; then - a tile's first unit, when the tile got more than its bucket holds - the tile's
@@ -685,7 +646,7 @@ void k_tile(ZrPass P, ZrTriBins B, ZrDevStats* __restrict__ stats, int slot,
             if (b < n_batches && j < n_live) {
                 const uint4 a4 = srecA[j], b4 = srecB[j];
                 const RecTri t = rec_load(a4, b4);
-                raster_sub<MODE, true, true>(t.a, t.b, t.c, t.prim, T, keys64, nullptr, b4.w);
+                raster_sub<ZR_MODE_GBUFFER, true, true>(t.a, t.b, t.c, t.prim, T, keys64, nullptr, b4.w);
             }
         }
         __syncthreads();      // (the next batch rewrites hist / srec; the merge below reads the keys)
@@ -713,20 +674,8 @@ void k_tile(ZrPass P, ZrTriBins B, ZrDevStats* __restrict__ stats, int slot,
                 else __syncthreads();      // (this stretch of the section held other tiles' records only; ocnt / omore are rewritten next)
             }
         }
-        for (uint32_t i = tid; i < TILE_PIX; i += 256u) {
-            const int px = tpx0 + (int)(i & (TILE - 1)), py = tpy0 + (int)(i / TILE);
-            if (px >= (int)P.W || py >= (int)P.H) continue;
-            const size_t p = (size_t)py * P.W + (size_t)px;
-            const unsigned long long k = keys64[i];
-            if ((uint32_t)k != ZR_EMPTY_PRIM) atomicMin(&vis64[p], k);      // (no read-and-compare first: the key buffer is empty but for this tile's other units)
-        }
-        // the second unit of a workgroup is fixed too (b + grid): when the grid's first units end together, 2 048 claims on one
-        // counter would queue up for ~10 ns apiece; only later units (hot frames) come from the counter
-        if (first) { first = false; __syncthreads(); unit += gridDim.x; continue; }
-        if (tid == 0) cur_unit = 2u * gridDim.x + atomicAdd(&stats->chunk_counter[slot], 1u);
-        __syncthreads();
-        unit = cur_unit;
-        __syncthreads();      // (cur_unit is rewritten by the next claim)
+        keys_merge<false>(P, tpx0, tpy0, keys64, vis64, tid, 256u);      // (no read-and-compare first: the key buffer is empty but for this tile's other units)
+        unit = claim_unit(first, unit, &stats->chunk_counter[slot], &cur_unit, tid);
     }
     if (LAST) {
         if (slot == 2) {        // the meshlets round 2's k_geom dropped behind the pyramid: per-wave counts, strided over this grid
@@ -741,32 +690,22 @@ void k_tile(ZrPass P, ZrTriBins B, ZrDevStats* __restrict__ stats, int slot,
         __syncthreads();
         for (uint32_t ti = blockIdx.x; ti < n_owned; ti += gridDim.x) {
             const uint32_t tile = owned_tiles[ti];
-            for (uint32_t i = tid; i < TILE_PIX; i += 256u) keys64[i] = (unsigned long long)0x3F800000u << 32 | ZR_EMPTY_PRIM;
+            keys_clear(keys64, tid, 256u);
             __syncthreads();
-            const int tpx0 = (int)(tile % P.tiles_x) * TILE, tpy0 = (int)(tile / P.tiles_x) * TILE;
-            TileCtx T;
-            T.px0 = 0; T.py0 = 0; T.W = (int)P.W - tpx0; T.H = (int)P.H - tpy0;
+            int tpx0, tpy0;
+            const TileCtx T = tile_ctx(P, tile, tpx0, tpy0);
             const uint32_t ttx = tile % P.tiles_x, tty = tile / P.tiles_x;
             for (uint32_t jj = tid; jj < n_a + n_b; jj += 256u) {
                 const uint32_t j = jj < n_a ? jj : half_cap + (jj - n_a);
                 const uint4 q3 = B.slow[4u * j + 3u];
-                // the tiles the triangle's snapped box reaches (k_geom), or all of them
+                // the tiles the triangle's snapped box reaches (k_geom), or all of them (spelled out: through rect_has the branches fold differently)
                 if (ttx < (q3.y & 255u) || tty < ((q3.y >> 8) & 255u) || ttx > ((q3.y >> 16) & 255u) || tty > (q3.y >> 24)) continue;
-                const uint4 q0 = B.slow[4u * j], q1 = B.slow[4u * j + 1u], q2 = B.slow[4u * j + 2u];
                 zf4 c0, c1, c2;
-                c0.x = zr_u2f(q0.x); c0.y = zr_u2f(q0.y); c0.z = zr_u2f(q0.z); c0.w = zr_u2f(q0.w);
-                c1.x = zr_u2f(q1.x); c1.y = zr_u2f(q1.y); c1.z = zr_u2f(q1.z); c1.w = zr_u2f(q1.w);
-                c2.x = zr_u2f(q2.x); c2.y = zr_u2f(q2.y); c2.z = zr_u2f(q2.z); c2.w = zr_u2f(q2.w);
-                raster_clipped_body<MODE>(c0, c1, c2, q3.x, T, P.hw, P.hh, tpx0 * 256, tpy0 * 256, keys64, nullptr);
+                slow_read(B.slow, j, c0, c1, c2);
+                raster_clipped_body<ZR_MODE_GBUFFER>(c0, c1, c2, q3.x, T, P.hw, P.hh, tpx0 * 256, tpy0 * 256, keys64, nullptr);
             }
             __syncthreads();
-            for (uint32_t i = tid; i < TILE_PIX; i += 256u) {
-                const int px = tpx0 + (int)(i & (TILE - 1)), py = tpy0 + (int)(i / TILE);
-                if (px >= (int)P.W || py >= (int)P.H) continue;
-                const size_t p = (size_t)py * P.W + (size_t)px;
-                const unsigned long long k = keys64[i];
-                if ((uint32_t)k != ZR_EMPTY_PRIM && k < vis64[p]) atomicMin(&vis64[p], k);
-            }
+            keys_merge<true>(P, tpx0, tpy0, keys64, vis64, tid, 256u);
             __syncthreads();
         }
     }
@@ -781,12 +720,11 @@ __global__ __launch_bounds__(256) void k_sky_tiles(ZrPass P, const ZrObject* __r
 {
     __shared__ unsigned long long keys64[TILE_PIX];
     const uint32_t tid = threadIdx.x, tile = owned_tiles[blockIdx.x];
-    for (uint32_t i = tid; i < TILE_PIX; i += 256u) keys64[i] = (unsigned long long)0x3F800000u << 32 | ZR_EMPTY_PRIM;
+    keys_clear(keys64, tid, 256u);
     __syncthreads();
     const ZrObject* __restrict__ O = objs + P.sky_object;
-    const int tpx0 = (int)(tile % P.tiles_x) * TILE, tpy0 = (int)(tile / P.tiles_x) * TILE;
-    TileCtx T;
-    T.px0 = 0; T.py0 = 0; T.W = (int)P.W - tpx0; T.H = (int)P.H - tpy0;
+    int tpx0, tpy0;
+    const TileCtx T = tile_ctx(P, tile, tpx0, tpy0);
     const ZrInstance I = O->inst[0];
     for (uint32_t t = tid; t < O->n_tris; t += 256u) {
         zf4 c[3];
@@ -833,8 +771,8 @@ void zr_launch_plan(const ZrTriBins& B, const uint32_t* owned_tiles, uint32_t n_
 void zr_launch_tile(const ZrPass& P, const ZrTriBins& B, ZrDevStats* stats, int slot, unsigned long long* vis64, uint32_t n_blocks, hipStream_t s, bool last,
                     const uint32_t* owned_tiles, uint32_t n_owned)
 {
-    if (last) hipLaunchKernelGGL((k_tile<ZR_MODE_GBUFFER, true>), dim3(n_blocks), dim3(256), 0, s, P, B, stats, slot, vis64, owned_tiles, n_owned);
-    else hipLaunchKernelGGL((k_tile<ZR_MODE_GBUFFER, false>), dim3(n_blocks), dim3(256), 0, s, P, B, stats, slot, vis64, owned_tiles, n_owned);
+    if (last) hipLaunchKernelGGL(k_tile<true>, dim3(n_blocks), dim3(256), 0, s, P, B, stats, slot, vis64, owned_tiles, n_owned);
+    else hipLaunchKernelGGL(k_tile<false>, dim3(n_blocks), dim3(256), 0, s, P, B, stats, slot, vis64, owned_tiles, n_owned);
 }
 void zr_launch_sky_tiles(const ZrPass& P, const ZrObject* objs, const uint32_t* owned_tiles, uint32_t n_owned, unsigned long long* sky64, hipStream_t s)
 {

@@ -186,7 +186,7 @@ static int create_device_state(zr_ctx* c)
                              { c->sb.tile_count, 0, mt * 4 },       // k_bin_count counts into zeroes (k_scan zeroes the counts
                              { c->sb.tile_cursor, 0, mt * 4 },      // and the cursors again for the fill and the next frame)
                              { c->d_hiz, 0, hiz_texels * sizeof(float) } }));      // texels over other ranks' regions stay 0 ("hidden")
-    for (auto& v : c->d_vis) zr_launch_fill64(v, (unsigned long long)0x3F800000u << 32 | ZR_EMPTY_PRIM, n, c->stream);
+    for (auto& v : c->d_vis) zr_launch_fill64(v, ZR_EMPTY_KEY, n, c->stream);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     // The runtime backs an event with a signal on its FIRST record and grows that pool in batches, which blocks the host for
     // milliseconds at unpredictable frames of a short run: record every event once now.

@@ -278,7 +278,7 @@ struct zr_ctx {
     // it reads): frame N's rounds, Hi-Z build, k_mark and resolve use copy N & 1, so a resolve on the host's stream is not in the next
     // frame's way; the frame after that waits for ev_end[N] before it touches anything of this parity.
     unsigned long long* d_vis[2] = { nullptr, nullptr }; uint32_t raster_blocks = 2048, shadow_blocks = 2048;
-    uint4* d_slow0 = nullptr; uint32_t slow0_cap = 1u << 18;      // shadow pass: triangles for the clipper (k_tile_slow)
+    uint4* d_slow0 = nullptr; uint32_t slow0_cap = 1u << 18;      // shadow pass: triangles for the clipper (k_shadow_slow)
     uint32_t work_capacity = 0, bin_capacity = 0; bool any_images = false, mixed_images = false;
     uint32_t limit_record_chunks = 0, limit_slow_triangles = 0;      // zr_set_limits (0 = defaults)
     // two-pass Hi-Z occlusion culling of the camera pass: per work item pixel bbox + least depth (written by the cull),

@@ -75,7 +75,7 @@ template <int MODE>
 __device__ __forceinline__ uint32_t pack_tile_rect(int px0, int py0, int px1, int py1)
 {
     if (MODE == ZR_MODE_SHADOW) { px1 = max(px0, px1 - ZR_SHADOW_APRON); py1 = max(py0, py1 - ZR_SHADOW_APRON); }
-    return (uint32_t)(px0 / TILE) | (uint32_t)(py0 / TILE) << 8 | (uint32_t)(px1 / TILE) << 16 | (uint32_t)(py1 / TILE) << 24;
+    return rect_of_pixels(px0, py0, px1, py1);
 }
 __device__ __forceinline__ bool sphere_reaches_owned_tile(const ZrPass& P, zf3 co, float ri)
 {
@@ -181,11 +181,10 @@ struct CullItem {
 };
 template <int MODE, bool WORKLIST>
 __device__ __forceinline__ bool cull_stage_a(const ZrPass& P, const ZrObject* __restrict__ objs, const uint32_t* __restrict__ work,
-                                             uint8_t* __restrict__ vis_clear, uint32_t k, CullItem& it)
+                                             uint32_t k, CullItem& it)
 {
     bool alive = true;
     const uint32_t w = WORKLIST ? work[k] : k;
-    (void)vis_clear;                                     // (visibility marks are frame stamps: nothing to clear, see ZrHiz::vis_stamp)
     const ZrObject* __restrict__ O = objs + find_object_work(objs, (int)P.n_objects, w);
     const uint32_t local = w - O->work_base, nm = O->n_meshlets;
     const uint32_t inst_i = local / nm, m = local - inst_i * nm;
@@ -246,7 +245,7 @@ __device__ __forceinline__ bool cull_stage_a(const ZrPass& P, const ZrObject* __
 template <int MODE, bool WORKLIST>
 __global__ __launch_bounds__(256) void k_cull_box(ZrPass P, const ZrObject* __restrict__ objs, const uint32_t* __restrict__ work,
                                                   uint32_t* __restrict__ rects, uint2* __restrict__ pxrect, float* __restrict__ zmin,
-                                                  uint8_t* __restrict__ vis_clear, ZrDevStats* __restrict__ stats, int slot,
+                                                  ZrDevStats* __restrict__ stats, int slot,
                                                   ZrBinEntry* __restrict__ sel, const uint8_t* __restrict__ vis_prev, uint32_t vis_stamp)
 {
     // sel != nullptr (camera pass): the survivors that round 1 draws - all of them, or with vis_prev those that owned a pixel last
@@ -263,7 +262,7 @@ __global__ __launch_bounds__(256) void k_cull_box(ZrPass P, const ZrObject* __re
         it.O = nullptr; it.w = 0;
         uint32_t r = ZR_RECT_CULLED; uint2 pr = make_uint2(0u, 0u); float zm = -1.0f;
         const uint32_t r_all = (P.tiles_x - 1u) << 16 | (P.tiles_y - 1u) << 24;          // every tile: extents unknown
-        if (k < n && cull_stage_a<MODE, WORKLIST>(P, objs, work, vis_clear, k, it)) {
+        if (k < n && cull_stage_a<MODE, WORKLIST>(P, objs, work, k, it)) {
             const float4 lo = ld_global(it.O->mbox + 2u * it.m), hi = ld_global(it.O->mbox + 2u * it.m + 1u);
             const float FM = 3.402823466e38f, U = 9.5367431640625e-7f;           // 8 ulps
             bool fin = true, clip = false;
@@ -370,11 +369,7 @@ __global__ __launch_bounds__(256) void k_cull_box(ZrPass P, const ZrObject* __re
             }
             __syncthreads();
             if (take) {
-                const ZrObject* __restrict__ O = it.O;
-                ZrBinEntry be;
-                be.mpos = it.mposv; be.mtri = O->mtri + it.tri_base; be.inst = O->inst + it.inst_i;
-                be.counts = it.vcount | it.tcount << 8 | (it.instanced ? 1u << 16 : 0u);
-                be.prim_base = O->prim_base + it.inst_i * O->n_tris;
+                const ZrBinEntry be = bin_entry(it.O, it.inst_i, it.mposv, it.tri_base, it.vcount, it.tcount, it.instanced);
                 sel[wbase[wv] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = be;
             }
             __syncthreads();      // wcount / wbase are reused by the next stretch
@@ -398,12 +393,12 @@ void zr_launch_cull_box(const ZrPass& P, const ZrObject* objs, uint32_t* work, u
     if (P.mode == ZR_MODE_GBUFFER) {
         if (P.use_worklist) {
             if (!reuse_list) hipLaunchKernelGGL(k_cull_instances<ZR_MODE_GBUFFER>, gi, bi, 0, s, P, objs, work, stats, slot);
-            hipLaunchKernelGGL((k_cull_box<ZR_MODE_GBUFFER, true>), g, b, 0, s, P, objs, work, rects, Z.pxrect, Z.zmin, Z.vis_now, stats, slot, sel, vis_prev, vis_stamp);
-        } else hipLaunchKernelGGL((k_cull_box<ZR_MODE_GBUFFER, false>), g, b, 0, s, P, objs, work, rects, Z.pxrect, Z.zmin, Z.vis_now, stats, slot, sel, vis_prev, vis_stamp);
+            hipLaunchKernelGGL((k_cull_box<ZR_MODE_GBUFFER, true>), g, b, 0, s, P, objs, work, rects, Z.pxrect, Z.zmin, stats, slot, sel, vis_prev, vis_stamp);
+        } else hipLaunchKernelGGL((k_cull_box<ZR_MODE_GBUFFER, false>), g, b, 0, s, P, objs, work, rects, Z.pxrect, Z.zmin, stats, slot, sel, vis_prev, vis_stamp);
     } else {
         if (P.use_worklist) {
             if (!reuse_list) hipLaunchKernelGGL(k_cull_instances<ZR_MODE_SHADOW>, gi, bi, 0, s, P, objs, work, stats, slot);
-            hipLaunchKernelGGL((k_cull_box<ZR_MODE_SHADOW, true>), g, b, 0, s, P, objs, work, rects, Z.pxrect, Z.zmin, (uint8_t*)nullptr, stats, slot, (ZrBinEntry*)nullptr, (const uint8_t*)nullptr, vis_stamp);
-        } else hipLaunchKernelGGL((k_cull_box<ZR_MODE_SHADOW, false>), g, b, 0, s, P, objs, work, rects, Z.pxrect, Z.zmin, (uint8_t*)nullptr, stats, slot, (ZrBinEntry*)nullptr, (const uint8_t*)nullptr, vis_stamp);
+            hipLaunchKernelGGL((k_cull_box<ZR_MODE_SHADOW, true>), g, b, 0, s, P, objs, work, rects, Z.pxrect, Z.zmin, stats, slot, (ZrBinEntry*)nullptr, (const uint8_t*)nullptr, vis_stamp);
+        } else hipLaunchKernelGGL((k_cull_box<ZR_MODE_SHADOW, false>), g, b, 0, s, P, objs, work, rects, Z.pxrect, Z.zmin, stats, slot, (ZrBinEntry*)nullptr, (const uint8_t*)nullptr, vis_stamp);
     }
 }

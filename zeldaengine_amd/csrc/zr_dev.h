@@ -2,17 +2,20 @@
 // (Base.vert / BaseInstanced.vert / Shadowmap*.vert), wave reductions on the DPP network, the Hi-Z tests, the per-pixel kernels' grid shape.
 //
 // The render path is one .hip per pass; each compiles alone (-fno-gpu-rdc), what they share is header-only and inlined:
-//   zr_cull.hip      k_instance_prep, k_cull_instances, k_cull_box<MODE>
-//   zr_shadow.hip    shadow pass, meshlet-level binning: k_bin_count / k_scan / k_bin_fill, k_raster_chunks<LATE>,
-//                    k_shadow_occlusion, k_count_shadow
-//   zr_camera.hip    camera pass, triangle-level binning: k_hiz_build, k_select, k_geom<HIZ, COUNT>, k_plan, k_tile, k_sky_tiles
+//   zr_cull.hip      k_instance_prep, k_cull_instances<MODE>, k_cull_box<MODE, WORKLIST>
+//   zr_shadow.hip    shadow pass, meshlet-level binning: k_bin_count / k_scan / k_bin_fill, k_raster_chunks<LATE>, k_shadow_slow,
+//                    k_shadow_occlusion<WORKLIST>, k_count_shadow
+//   zr_camera.hip    camera pass, triangle-level binning: k_hiz_build, k_select, k_geom<HIZ, COUNT>, k_plan, k_tile<LAST>, k_sky_tiles
 //   zr_resolve.hip   k_resolve_gbuffer: BaseScene.frag per pixel from the key buffer into the SoA GBuffer planes
 //                    k_mark: the visibility history alone, for a frame whose resolve runs on the host's stream
 //   zr_lighting.hip  k_lighting (BaseLighting.frag), k_gbuffer_vis (debug view 9)
 //   zr_forward.hip   k_forward: the forward variant, Base.frag
 //   zr_frame.hip     k_frame_begin, fills, k_untile / k_pack_tiles (multi-GPU composite)
 //   zr_delta.hip     k_delta_mark, k_delta_pack: the frame as the tiles that differ from the last delivery
-//   zr_raster.h      the rasteriser proper (raster_sub, the clipper, k_tile_slow): shared by the shadow and the camera pass
+//   zr_raster.h      the rasteriser proper (raster_sub, the clipper) and the steps of the kernels that own a tile's keys (tile context,
+//                    queued / recorded triangle, keys' clear and merge, slow-triangle record, unit claim): shadow and camera pass
+//   zr_dev.h (this)  also the steps the cull, select and bin kernels and the rasterising waves share: the tile rectangle (TileRect), a work
+//                    item's self-contained record (bin_entry), the LDS histogram over a rect's tiles, the meshlet head (meshlet_head)
 //   zr_texture.h     texture(sampler2D): mips, trilinear, anisotropic; zr_surface.h: interpolation, ComputeNormal, BaseScene.frag's body
 //   zr_shade.h       Common.glsl's BxDF, PCF, cubemap sampling and the body BaseLighting.frag and Base.frag share
 //
@@ -45,7 +48,7 @@
 #define RW (ZR_TILE >= 64 ? 8 : 4)          // waves per rasteriser workgroup: one 64x64 tile's keys (32 KB) are shared by 8 waves
 #define RTHREADS (RW * WAVE)
 #ifndef ZR_RASTER_WAVES_DEFER
-#define ZR_RASTER_WAVES_DEFER 6              // waves per SIMD the shadow rasteriser is compiled for (the clipper is not in its loop: k_tile_slow)
+#define ZR_RASTER_WAVES_DEFER 6              // waves per SIMD the shadow rasteriser is compiled for (the clipper is not in its loop: k_shadow_slow)
 #endif
 // Diagnostic work-skipping switches (attribution of kernel time) exist only in -DZR_DIAG builds: the product library has none.
 #ifdef ZR_DIAG
@@ -174,6 +177,82 @@ __device__ __forceinline__ SV project(zf4 c, float hw, float hh)
     s.Y = (int)__builtin_floorf(__builtin_fmaf(ys, 256.0f, 0.5f));
     s.z = c.z * s.rw;
     return s;
+}
+
+// ------------------------------------------------------------------------------------------------ steps the geometry kernels share
+
+// A rectangle of tiles in one word: tx0 | ty0 << 8 | tx1 << 16 | ty1 << 24 (the cull's rects, a triangle's tiles, a slow triangle's reach).
+struct TileRect { uint32_t tx0, ty0, tx1, ty1; };
+__device__ __forceinline__ TileRect rect_unpack(uint32_t r) { TileRect R; R.tx0 = r & 255u; R.ty0 = (r >> 8) & 255u; R.tx1 = (r >> 16) & 255u; R.ty1 = r >> 24; return R; }
+// ... of the tiles a pixel box (inside the target) reaches
+__device__ __forceinline__ uint32_t rect_of_pixels(int px0, int py0, int px1, int py1)
+{
+    return (uint32_t)(px0 / TILE) | (uint32_t)(py0 / TILE) << 8 | (uint32_t)(px1 / TILE) << 16 | (uint32_t)(py1 / TILE) << 24;
+}
+__device__ __forceinline__ bool rect_has(uint32_t r, int tx, int ty)
+{
+    return (int)(r & 255u) <= tx && tx <= (int)((r >> 16) & 255u) && (int)((r >> 8) & 255u) <= ty && ty <= (int)(r >> 24);
+}
+
+// The LDS histogram over the tiles of the shadow map (k_bin_count, k_bin_fill; 1024 threads): zeroed, then every listed rect adds one
+// to each of its tiles (the callers' barriers stand between the two and after; a culled item has no rect to add).
+__device__ __forceinline__ void hist_clear(uint32_t* hist, uint32_t n_tiles)
+{
+    for (uint32_t i = threadIdx.x; i < n_tiles; i += 1024u) hist[i] = 0;
+}
+__device__ __forceinline__ void hist_add_rect(uint32_t* hist, const TileRect& R, uint32_t tiles_x)
+{
+    for (uint32_t ty = R.ty0; ty <= R.ty1; ++ty)
+        for (uint32_t tx = R.tx0; tx <= R.tx1; ++tx) atomicAdd(&hist[ty * tiles_x + tx], 1u);
+}
+
+// One meshlet-instance as the self-contained record the rasterising waves start from (ZrBinEntry): from the parts of the meshlet's
+// header (the cull has them at hand), or from work item w alone: find the object, split into instance and meshlet, load the header.
+__device__ __forceinline__ ZrBinEntry bin_entry(const ZrObject* O, uint32_t inst_i, const float4* mpos, uint32_t tri_base, uint32_t vcount, uint32_t tcount,
+                                               uint32_t instanced)
+{
+    ZrBinEntry be;
+    be.mpos = mpos; be.mtri = O->mtri + tri_base; be.inst = O->inst + inst_i;
+    be.counts = vcount | tcount << 8 | (instanced ? 1u << 16 : 0u);
+    be.prim_base = O->prim_base + inst_i * O->n_tris;
+    return be;
+}
+__device__ __forceinline__ ZrBinEntry bin_entry(const ZrObject* objs, int n_objects, uint32_t w)
+{
+    const ZrObject* __restrict__ O = objs + find_object_work(objs, n_objects, w);
+    const uint32_t local = w - O->work_base;
+    const uint32_t inst_i = local / O->n_meshlets, m = local - inst_i * O->n_meshlets;
+    const XkMeshlet* __restrict__ ml = O->meshlets + m;
+    const uint4 mh = ld_global((const uint4*)ml);            // VertexOffset, VertexCount, TriangleOffset, TriangleCount
+    return bin_entry(O, inst_i, O->mpos + mh.x, ld_global(&ml->BindlessContext), mh.y, mh.w, O->instanced);
+}
+
+// The head of a meshlet in a rasterising wave (k_raster_chunks, k_geom), from its record (wave-uniform): both rounds' triangle words, the
+// lane's vertex and the instance are requested together, before anything waits; the vertex is transformed.  Almost every meshlet has no
+// vertex outside the frustum at all: the callers take one wave-wide vote over ten comparisons (each a 64-lane mask by itself); only a
+// FLAGGED meshlet pays for the per-vertex flag words and the per-triangle classification.  (The vote, the flags and the projection stay
+// with the callers, around what each stages of its vertex: inlined from here the compiler folds their branches differently.)
+struct MeshletHead {
+    const float4* mp; ZrInstance I; bool instanced;      // (what a slow triangle's vertices are transformed from again)
+    uint32_t vcount, tcount, pbase;
+    uint2 tri_w[2];
+    zf4 c;              // lanes below vcount: the lane's vertex in clip space
+};
+__device__ __forceinline__ MeshletHead meshlet_head(const float* PVM, const ZrBinEntry& be, uint32_t lane)
+{
+    MeshletHead H;
+    H.mp = be.mpos; H.pbase = be.prim_base;
+    const uint2* tw = be.mtri;
+    H.vcount = be.counts & 255u; H.tcount = (be.counts >> 8) & 255u;
+    H.instanced = (be.counts >> 16) & 1u;
+    H.tri_w[0] = lane < H.tcount ? ld_global(tw + lane) : make_uint2(0u, 0u);
+    H.tri_w[1] = lane + WAVE < H.tcount ? ld_global(tw + lane + WAVE) : make_uint2(0u, 0u);
+    const float4 pp = lane < H.vcount ? ld_global(H.mp + lane) : make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+    H.I = ld_record(be.inst);
+
+    lds_fence();   // this wave's previous readers are done with its staging area
+    H.c = zr_mat4_point(PVM, vs_position(zr3(pp.x, pp.y, pp.z), H.I, H.instanced));
+    return H;
 }
 
 // Multi-GPU ownership of a tile (zelda_render.h: zr_tile_owner)

@@ -271,7 +271,7 @@ static void shadow_bin(zr_ctx* c, const ZrPass& P, const ZrHiz& Z, hipStream_t s
     // 0.779 -> 0.752 ms; 32 / 16 entries: 0.88 / 1.05 ms; 256: 0.754).  Units only get bigger here: the chunk table's capacity holds.
     const uint32_t chunk = c->stile_world >= 4u ? 2u * ZR_CHUNK : ZR_CHUNK;
     zr_launch_scan(sb.tile_count, sb.tile_offset, sb.tile_cursor, sb.chunk_offset, sb.chunk_tab, c->chunk_capacity, c->sn_tiles, c->bin_capacity,
-                   c->d_sstats, 0, s, chunk);
+                   c->d_sstats, s, chunk);
     zr_launch_bin_fill(P, c->d_objs, work, rects, sb.tile_offset, sb.tile_cursor, sb.bins, Z, c->d_sstats, s);
 }
 // Which meshlet-instances round 2 of the camera pass draws (k_select: timed with the Hi-Z build; round 1's list comes from the cull).
@@ -296,7 +296,7 @@ static void tri_raster(zr_ctx* c, const ZrPass& P, const ZrHiz& Z, int slot, hip
 // the shadow rasteriser over the bins (stage: see zr_launch_raster_chunks)
 static void raster(zr_ctx* c, const ZrPass& P, hipStream_t s, int stage)
 {
-    zr_launch_raster_chunks(P, c->d_objs, c->sb.chunk_tab, c->sb.bins, c->d_sstats, 0, (uint32_t*)shadow_buf(c),
+    zr_launch_raster_chunks(P, c->d_objs, c->sb.chunk_tab, c->sb.bins, c->d_sstats, (uint32_t*)shadow_buf(c),
                             c->stile_world >= 4u ? c->shadow_blocks / 2u : c->shadow_blocks, s, c->d_slow0, c->slow0_cap, c->d_sowned, c->sn_tiles, stage);
 }
 

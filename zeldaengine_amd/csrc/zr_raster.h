@@ -1,6 +1,8 @@
 // zr_raster.h — the rasteriser proper: exact integer edge functions with the top-left rule over a tile's LDS keys (raster_sub), the
-// near-plane / guard-band clipper (raster_clipped) and the kernel that draws a round's slow triangles (k_tile_slow).  Shared by the
-// shadow pass (zr_shadow.hip) and the camera pass (zr_camera.hip).  Raster state: ZE:5094-5201, 3247-3287; rules: DESIGN.md §4.
+// near-plane / guard-band clipper (raster_clipped), and the steps every kernel that owns a tile's keys takes: the tile's context
+// (tile_ctx), a queued or recorded triangle (tri_unpack), the keys' clear and merge (keys_clear, keys_merge), the slow-triangle record
+// (slow_read), the claim of a persistent workgroup's next unit (claim_unit).  Shared by the shadow pass (zr_shadow.hip)
+// and the camera pass (zr_camera.hip).  Raster state: ZE:5094-5201, 3247-3287; rules: DESIGN.md §4.
 #pragma once
 #include "zr_dev.h"
 
@@ -9,13 +11,13 @@ struct TileCtx {
     int W, H;                     // target extent
 };
 
-// Cheap per-triangle rejection, identical in effect to raster_sub's box test: no pixel centre of the tile's key window inside the
-// snapped bounding box.  (Its caller is the shadow rasteriser, which is two-sided: the rare degenerate triangles are left to raster_sub.)
-template <int MODE>
+// Cheap per-triangle rejection of the shadow rasteriser, identical in effect to raster_sub's box test: no texel centre of the window
+// inside the snapped bounding box.  (The pass is two-sided: the rare degenerate triangles are left to raster_sub.)
 __device__ __forceinline__ bool tri_prefilter(int X0, int Y0, int X1, int Y1, int X2, int Y2, const TileCtx& T)
 {
-    const int x0 = max((imin3(X0, X1, X2) - 128 + 255) >> 8, T.px0), x1 = min((imax3(X0, X1, X2) - 128) >> 8, min(T.px0 + SPAN(MODE) - 1, T.W - 1));
-    const int y0 = max((imin3(Y0, Y1, Y2) - 128 + 255) >> 8, T.py0), y1 = min((imax3(Y0, Y1, Y2) - 128) >> 8, min(T.py0 + SPAN(MODE) - 1, T.H - 1));
+    constexpr int WIN = SPAN(ZR_MODE_SHADOW);
+    const int x0 = max((imin3(X0, X1, X2) - 128 + 255) >> 8, T.px0), x1 = min((imax3(X0, X1, X2) - 128) >> 8, min(T.px0 + WIN - 1, T.W - 1));
+    const int y0 = max((imin3(Y0, Y1, Y2) - 128 + 255) >> 8, T.py0), y1 = min((imax3(Y0, Y1, Y2) - 128) >> 8, min(T.py0 + WIN - 1, T.H - 1));
     return x0 <= x1 && y0 <= y1;
 }
 
@@ -204,8 +206,7 @@ __device__ __forceinline__ void raster_clipped_body(zf4 c0, zf4 c1, zf4 c2, uint
         sp = sn;
     }
 }
-// (a call in the rasterisers' loops - their register budget must not carry the clipper's; inlined in k_tile_slow, whose own budget is set
-// so that it finds room beside the shadow rasteriser)
+// (a call in k_shadow_slow and k_sky_tiles; k_tile<LAST> inlines the body under its own register budget)
 template <int MODE>
 __device__ __noinline__ void raster_clipped(zf4 c0, zf4 c1, zf4 c2, uint32_t prim, TileCtx T, float hw, float hh, int ox, int oy,
                                             unsigned long long* keys64, uint32_t* keys32)
@@ -213,73 +214,96 @@ __device__ __noinline__ void raster_clipped(zf4 c0, zf4 c1, zf4 c2, uint32_t pri
     raster_clipped_body<MODE>(c0, c1, c2, prim, T, hw, hh, ox, oy, keys64, keys32);
 }
 
-// The slow triangles of the round (they need the clipper, or have an edge of 64 px or more): every owned tile tries every one of
-// them through raster_clipped.  A SMALL persistent grid (ZR_SLOW_BLOCKS workgroups stride over the owned tiles): the usual round has no
-// slow triangle, and this launch sits on the camera lane's critical path - as one workgroup per owned tile (2 040 at 1080p, 8 KB of LDS
-// each) it cost 35 us beside the shadow rasteriser just to find room and return; a few dozen workgroups come and go like k_scan_tri's one.
-#ifndef ZR_SLOW_BLOCKS
-#define ZR_SLOW_BLOCKS 256u
-#endif
-template <int MODE, bool BY_TILE>
-__global__ __launch_bounds__(256) void k_tile_slow(ZrPass P, const uint32_t* __restrict__ owned_tiles, uint32_t n_owned, const uint4* __restrict__ slow,
-                                                   uint32_t slow_cap, ZrDevStats* __restrict__ stats, int slot,
-                                                   unsigned long long* __restrict__ vis64, uint32_t* __restrict__ shadow_bits,
-                                                   const uint32_t* __restrict__ wave_culled, uint32_t n_waves)
+
+// ------------------------------------------------------------------------------------------------ what the kernels that own a tile's keys share
+
+// A tile in TILE-RELATIVE coordinates (origin = the tile's first pixel, (tpx0, tpy0) in the target): edge functions, depth planes and
+// bounding boxes are built from coordinate differences, so the integers and floats are the ones absolute coordinates give.
+__device__ __forceinline__ TileCtx tile_ctx(const ZrPass& P, uint32_t tile, int& tpx0, int& tpy0)
 {
-    __shared__ unsigned long long keys64[MODE == ZR_MODE_GBUFFER ? TILE_PIX : 1];
-    __shared__ uint32_t keys32[MODE == ZR_MODE_SHADOW ? SPAN_PIX(MODE) : 1];
-    // camera pass: round 1's triangles sit in the first half of the list, round 2's in the second; one launch after round 2 draws both
-    // (slot = 2), or round 1's alone in a one-round frame (slot = 1)
-    const uint32_t half = BY_TILE ? slow_cap : slow_cap / 2u;
-    const uint32_t n_a = min(stats->n_slow[BY_TILE ? slot : 1], half), n_b = (!BY_TILE && slot == 2) ? min(stats->n_slow[2], half) : 0u;
-    if (!BY_TILE && slot == 2 && wave_culled) {
-        // the meshlets round 2's k_geom dropped behind the pyramid: the per-wave counts, strided over this grid (one atomic per wave of
-        // THAT kernel on one address would queue up for ~10 ns apiece and hold its end)
-        uint32_t nc = 0;
-        for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n_waves; i += gridDim.x * 256u) nc += wave_culled[i];
-        nc = (uint32_t)wave_sum((int)nc);
-        if ((threadIdx.x & 63u) == 0u && nc) { atomicAdd(&stats->hiz_culled, nc); atomicAdd(&stats->hiz_culled_geom, nc); atomicSub(&stats->survivors[2], nc); }
+    tpx0 = (int)(tile % P.tiles_x) * TILE; tpy0 = (int)(tile / P.tiles_x) * TILE;
+    TileCtx T;
+    T.px0 = 0; T.py0 = 0; T.W = (int)P.W - tpx0; T.H = (int)P.H - tpy0;
+    return T;
+}
+
+// A small triangle as the shadow rasteriser's queue and the camera pass's records hold it: per vertex X | Y << 16 (tile-relative, int16
+// each) and the depth's bits; the primitive id.
+struct RecTri { SV a, b, c; uint32_t prim; };
+__device__ __forceinline__ SV sv_unpack(uint32_t xy, uint32_t z)
+{
+    SV s;
+    s.X = (int)(short)(xy & 0xFFFFu); s.Y = (int)xy >> 16; s.z = zr_u2f(z); s.rw = 0.0f;
+    return s;
+}
+__device__ __forceinline__ RecTri tri_unpack(uint32_t xy0, uint32_t z0, uint32_t xy1, uint32_t z1, uint32_t xy2, uint32_t z2, uint32_t prim)
+{
+    RecTri t;
+    t.a = sv_unpack(xy0, z0); t.b = sv_unpack(xy1, z1); t.c = sv_unpack(xy2, z2); t.prim = prim;
+    return t;
+}
+
+// The LDS keys of a tile (64-bit: depth << 32 | prim) or of a shadow window (32-bit: depth), `threads` threads: cleared to "nothing
+// drawn", and the touched ones merged into the key buffer / the map with atomic min: the merge IS the depth write.
+// COMPARE: the texel is read first and the atomic issued only for a key that lowers it (a list drawn into a buffer that already holds
+// the frame); without, every touched key goes out (k_tile's units: the key buffer is empty but for this tile's other units).
+__device__ __forceinline__ void keys_clear(unsigned long long* keys64, uint32_t tid, uint32_t threads)
+{
+    for (uint32_t i = tid; i < TILE_PIX; i += threads) keys64[i] = ZR_EMPTY_KEY;
+}
+__device__ __forceinline__ void keys_clear(uint32_t* keys32, uint32_t tid, uint32_t threads)
+{
+    for (uint32_t i = tid; i < (uint32_t)SPAN_PIX(ZR_MODE_SHADOW); i += threads) keys32[i] = 0x3F800000u;
+}
+template <bool COMPARE>
+__device__ __forceinline__ void keys_merge(const ZrPass& P, int tpx0, int tpy0, const unsigned long long* keys64, unsigned long long* vis64,
+                                           uint32_t tid, uint32_t threads)
+{
+    for (uint32_t i = tid; i < TILE_PIX; i += threads) {
+        const int px = tpx0 + (int)(i & (TILE - 1)), py = tpy0 + (int)(i / TILE);
+        if (px >= (int)P.W || py >= (int)P.H) continue;
+        const size_t p = (size_t)py * P.W + (size_t)px;
+        const unsigned long long k = keys64[i];
+        if ((uint32_t)k != ZR_EMPTY_PRIM && (!COMPARE || k < vis64[p])) atomicMin(&vis64[p], k);
     }
-    if (n_a + n_b == 0u) return;
-    const uint32_t tid = threadIdx.x;
-    for (uint32_t ti = blockIdx.x; ti < n_owned; ti += gridDim.x) {
-        const uint32_t tile = owned_tiles[ti];
-        for (uint32_t i = tid; i < (uint32_t)SPAN_PIX(MODE); i += 256u) {
-            if (MODE == ZR_MODE_GBUFFER) keys64[i] = (unsigned long long)0x3F800000u << 32 | ZR_EMPTY_PRIM;
-            else keys32[i] = 0x3F800000u;
-        }
-        __syncthreads();
-        const int tpx0 = (int)(tile % P.tiles_x) * TILE, tpy0 = (int)(tile / P.tiles_x) * TILE;
-        TileCtx T;
-        T.px0 = 0; T.py0 = 0; T.W = (int)P.W - tpx0; T.H = (int)P.H - tpy0;
-        for (uint32_t jj = tid; jj < n_a + n_b; jj += 256u) {
-            const uint32_t j = jj < n_a ? jj : half + (jj - n_a);
-            const uint4 q3 = slow[4u * j + 3u];
-            if (BY_TILE && q3.y != tile) continue;          // (the meshlet-binned rasteriser lists a triangle once per tile of its meshlet)
-            if (!BY_TILE) {                                 // camera pass: the tiles the triangle's snapped box reaches (k_geom), or all of them
-                const uint32_t ttx = tile % P.tiles_x, tty = tile / P.tiles_x;
-                if (ttx < (q3.y & 255u) || tty < ((q3.y >> 8) & 255u) || ttx > ((q3.y >> 16) & 255u) || tty > (q3.y >> 24)) continue;
-            }
-            const uint4 q0 = slow[4u * j], q1 = slow[4u * j + 1u], q2 = slow[4u * j + 2u];
-            zf4 c0, c1, c2;
-            c0.x = zr_u2f(q0.x); c0.y = zr_u2f(q0.y); c0.z = zr_u2f(q0.z); c0.w = zr_u2f(q0.w);
-            c1.x = zr_u2f(q1.x); c1.y = zr_u2f(q1.y); c1.z = zr_u2f(q1.z); c1.w = zr_u2f(q1.w);
-            c2.x = zr_u2f(q2.x); c2.y = zr_u2f(q2.y); c2.z = zr_u2f(q2.z); c2.w = zr_u2f(q2.w);
-            raster_clipped<MODE>(c0, c1, c2, q3.x, T, P.hw, P.hh, tpx0 * 256, tpy0 * 256, keys64, keys32);
-        }
-        __syncthreads();
-        for (uint32_t i = tid; i < (uint32_t)SPAN_PIX(MODE); i += 256u) {
-            const int px = tpx0 + (int)(i % (uint32_t)SPAN(MODE)), py = tpy0 + (int)(i / (uint32_t)SPAN(MODE));
-            if (px >= (int)P.W || py >= (int)P.H) continue;
-            const size_t p = (size_t)py * P.W + (size_t)px;
-            if (MODE == ZR_MODE_GBUFFER) {
-                const unsigned long long k = keys64[i];
-                if ((uint32_t)k != ZR_EMPTY_PRIM && k < vis64[p]) atomicMin(&vis64[p], k);
-            } else {
-                const uint32_t k = keys32[i];
-                if (k != 0x3F800000u && k < shadow_bits[p]) atomicMin(&shadow_bits[p], k);
-            }
-        }
-        __syncthreads();      // the keys are cleared again for the next tile
+}
+// (a key still at its clear value 1.0 cannot lower the map, whose texels never exceed 1.0: its texel is not even read - the untouched
+// four fifths of a window's 1 936 texels were 15 MB of the shadow pass's 25 MB of reads, profiles/r06_shadow_tcc.txt)
+__device__ __forceinline__ void keys_merge(const ZrPass& P, int tpx0, int tpy0, const uint32_t* keys32, uint32_t* shadow_bits,
+                                           uint32_t tid, uint32_t threads)
+{
+    constexpr uint32_t WIN = SPAN(ZR_MODE_SHADOW);
+    for (uint32_t i = tid; i < WIN * WIN; i += threads) {
+        const int px = tpx0 + (int)(i % WIN), py = tpy0 + (int)(i / WIN);
+        if (px >= (int)P.W || py >= (int)P.H) continue;
+        const size_t p = (size_t)py * P.W + (size_t)px;
+        const uint32_t k = keys32[i];
+        if (k != 0x3F800000u && k < shadow_bits[p]) atomicMin(&shadow_bits[p], k);
     }
+}
+
+// A SLOW triangle (it needs the clipper, or has an edge of 64 px or more) is not drawn where it is found but listed: 4 x uint4 - its three
+// clip-space vertices and (prim, where, 0, 0); `where` is the tile whose list named it (shadow pass) or the rectangle of tiles it can
+// touch (camera pass).  Record j's vertices, for a kernel that tries it on a tile through the clipper (the fourth word is the caller's:
+// it decides whether to):
+__device__ __forceinline__ void slow_read(const uint4* slow, uint32_t j, zf4& c0, zf4& c1, zf4& c2)
+{
+    const uint4 q0 = slow[4u * j], q1 = slow[4u * j + 1u], q2 = slow[4u * j + 2u];
+    c0.x = zr_u2f(q0.x); c0.y = zr_u2f(q0.y); c0.z = zr_u2f(q0.z); c0.w = zr_u2f(q0.w);
+    c1.x = zr_u2f(q1.x); c1.y = zr_u2f(q1.y); c1.z = zr_u2f(q1.z); c1.w = zr_u2f(q1.w);
+    c2.x = zr_u2f(q2.x); c2.y = zr_u2f(q2.y); c2.z = zr_u2f(q2.z); c2.w = zr_u2f(q2.w);
+}
+
+// The next work unit of a persistent workgroup.  The first two are its own index and that + the grid (no atomic: an empty pass costs
+// nothing, and when the grid's first units end together, a claim apiece on one counter would queue up for ~10 ns each); later ones come
+// from the counter, through *s_next in LDS (rewritten by the next claim: hence the barrier after it is read).  The unit is claimed only
+// when the last one is done: claiming early costs more in tail balance than the atomic's latency.
+__device__ __forceinline__ uint32_t claim_unit(bool& first, uint32_t unit, uint32_t* counter, uint32_t* s_next, uint32_t tid)
+{
+    if (first) { first = false; __syncthreads(); return unit + gridDim.x; }
+    if (tid == 0) *s_next = 2u * gridDim.x + atomicAdd(counter, 1u);
+    __syncthreads();
+    const uint32_t next = *s_next;
+    __syncthreads();
+    return next;
 }

@@ -40,11 +40,11 @@ __global__ __launch_bounds__(TB, TB == 64 ? ZR_RESOLVE_IMG_WAVES : 1) void k_res
     for (uint32_t q = 0; q < (uint32_t)PPT; ++q) {
         const uint32_t i = tid + q * T;
         const int px = tx0 + (int)(i & (TILE - 1)), py = ty0 + (int)(i / TILE);
-        keys[q] = (unsigned long long)0x3F800000u << 32 | ZR_EMPTY_PRIM;
+        keys[q] = ZR_EMPTY_KEY;
         if (px < (int)P.W && py < (int)P.H) {
             const size_t p = (size_t)py * P.W + (size_t)px;
             keys[q] = vis64[p];
-            vis64[p] = (unsigned long long)0x3F800000u << 32 | ZR_EMPTY_PRIM;
+            vis64[p] = ZR_EMPTY_KEY;
         }
     }
 #pragma unroll

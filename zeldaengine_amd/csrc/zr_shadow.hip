@@ -1,6 +1,7 @@
 // zr_shadow.hip — the shadow pass (ZE:3239-3393) as meshlet-level binning: k_bin_count / k_scan / k_bin_fill (per-tile lists of
-// self-contained 32-byte meshlet records), k_raster_chunks<LATE> (persistent workgroups, a 44 x 44 key window in LDS),
-// k_shadow_occlusion (the map as a running minimum hides casters), k_count_shadow.  See zr_dev.h for the map of the kernel files.
+// self-contained 32-byte meshlet records), k_raster_chunks<LATE> (persistent workgroups, a 44 x 44 key window in LDS), k_shadow_slow (the
+// triangles it left to the clipper), k_shadow_occlusion (the map as a running minimum hides casters), k_count_shadow.  See zr_dev.h for
+// the map of the kernel files.
 #include "zr_dev.h"
 #include "zr_raster.h"
 
@@ -15,17 +16,13 @@ __global__ __launch_bounds__(1024) void k_bin_count(ZrPass P, const uint32_t* __
     const uint32_t n_tiles = P.tiles_x * P.tiles_y;
     const uint32_t n_vis = P.use_worklist ? stats->n_vis_work[0] : P.n_work;
     if (blockIdx.x * 1024u >= n_vis) return;            // the grid is sized for every meshlet-instance of the scene
-    for (uint32_t i = threadIdx.x; i < n_tiles; i += 1024u) hist[i] = 0;
+    hist_clear(hist, n_tiles);
     __syncthreads();
     const uint32_t w = blockIdx.x * 1024u + threadIdx.x;
     if (w < n_vis) {
         uint32_t r = rects[w];
         if (r != ZR_RECT_CULLED && Z.phase && Z.vis_prev[P.use_worklist ? work[w] : w] != (uint8_t)Z.vis_stamp) r = ZR_RECT_CULLED;
-        if (r != ZR_RECT_CULLED) {
-            const uint32_t tx0 = r & 255u, ty0 = (r >> 8) & 255u, tx1 = (r >> 16) & 255u, ty1 = r >> 24;
-            for (uint32_t ty = ty0; ty <= ty1; ++ty)
-                for (uint32_t tx = tx0; tx <= tx1; ++tx) atomicAdd(&hist[ty * P.tiles_x + tx], 1u);
-        }
+        if (r != ZR_RECT_CULLED) hist_add_rect(hist, rect_unpack(r), P.tiles_x);
     }
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < n_tiles; i += 1024u) { const uint32_t c = hist[i]; if (c) atomicAdd(&tile_count[i], c); }
@@ -37,7 +34,7 @@ __global__ __launch_bounds__(1024) void k_bin_count(ZrPass P, const uint32_t* __
 __global__ __launch_bounds__(1024) void k_scan(uint32_t* __restrict__ tile_count, uint32_t* __restrict__ tile_offset,
                                                uint32_t* __restrict__ tile_cursor, uint32_t* __restrict__ chunk_offset,
                                                uint4* __restrict__ chunk_tab, uint32_t chunk_cap,
-                                               uint32_t n, uint32_t capacity, ZrDevStats* __restrict__ stats, int slot, uint32_t chunk)
+                                               uint32_t n, uint32_t capacity, ZrDevStats* __restrict__ stats, uint32_t chunk)
 {
     __shared__ uint32_t part[1024];
     __shared__ uint32_t cpart[1024];
@@ -75,20 +72,18 @@ __global__ __launch_bounds__(1024) void k_scan(uint32_t* __restrict__ tile_count
         run += c; crun += nu;
         tile_count[i] = 0; tile_cursor[i] = 0;
     }
-    if (slot == 0 && tid < 32u) stats->covered_part[tid] = 0;      // shadow pipeline: k_shadow_occlusion's tally (32 partial sums)
+    if (tid < 32u) stats->covered_part[tid] = 0;      // k_shadow_occlusion's tally (32 partial sums)
     if (tid == 1023) {
         tile_offset[n] = part[1023];
         chunk_offset[n] = cpart[1023];
-        stats->bin_entries[slot] = part[1023];
-        stats->n_chunks[slot] = min(cpart[1023], chunk_cap);
-        stats->chunk_counter[slot] = 0;
+        stats->bin_entries[0] = part[1023];
+        stats->n_chunks[0] = min(cpart[1023], chunk_cap);
+        stats->chunk_counter[0] = 0;
         // what the kernels after this one accumulate for the pass starts from zero here: the shadow pipeline's block is not touched by
         // k_frame_begin (the pipeline does not wait for the camera lane)
-        stats->survivors[slot] = 0; stats->n_slow[slot] = 0;
-        // (the shadow pass launches this with slot 0 only; the other branches keep the kernel's code as it was measured)
-        if (slot == 0) stats->overflow = part[1023] > capacity ? 1u : 0u;      // the pipeline's own block: reset here
-        else if (part[1023] > capacity) stats->overflow = 1u;
-        if (slot == 0) { stats->n_chunks[1] = 0; stats->chunk_counter[1] = 0; stats->shadow_late = 0; }      // (k_shadow_occlusion's late units)
+        stats->survivors[0] = 0; stats->n_slow[0] = 0;
+        stats->overflow = part[1023] > capacity ? 1u : 0u;
+        stats->n_chunks[1] = 0; stats->chunk_counter[1] = 0; stats->shadow_late = 0;      // (k_shadow_occlusion's late units)
         if (part[1023] > capacity) stats->overflow_sticky = ZR_OVF_BINS;
     }
 }
@@ -105,7 +100,7 @@ __global__ __launch_bounds__(1024) void k_bin_fill(ZrPass P, const ZrObject* __r
     const uint32_t n_tiles = P.tiles_x * P.tiles_y;
     const uint32_t n_vis = P.use_worklist ? stats->n_vis_work[0] : P.n_work;
     if (blockIdx.x * 1024u >= n_vis) return;
-    for (uint32_t i = threadIdx.x; i < n_tiles; i += 1024u) hist[i] = 0;
+    hist_clear(hist, n_tiles);
     if (threadIdx.x == 0) tot = 0;
     __syncthreads();
     const uint32_t k = blockIdx.x * 1024u + threadIdx.x;
@@ -114,10 +109,8 @@ __global__ __launch_bounds__(1024) void k_bin_fill(ZrPass P, const ZrObject* __r
         r = rects[k]; w = P.use_worklist ? work[k] : k;
         if (r != ZR_RECT_CULLED && Z.phase && Z.vis_prev[w] != (uint8_t)Z.vis_stamp) r = ZR_RECT_CULLED;      // (as in k_bin_count)
     }
-    const uint32_t tx0 = r & 255u, ty0 = (r >> 8) & 255u, tx1 = (r >> 16) & 255u, ty1 = r >> 24;
-    if (r != ZR_RECT_CULLED)
-        for (uint32_t ty = ty0; ty <= ty1; ++ty)
-            for (uint32_t tx = tx0; tx <= tx1; ++tx) atomicAdd(&hist[ty * P.tiles_x + tx], 1u);
+    const TileRect R = rect_unpack(r);
+    if (r != ZR_RECT_CULLED) hist_add_rect(hist, R, P.tiles_x);
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < n_tiles; i += 1024u) {
         const uint32_t c = hist[i];
@@ -126,17 +119,9 @@ __global__ __launch_bounds__(1024) void k_bin_fill(ZrPass P, const ZrObject* __r
     __syncthreads();
     if (r != ZR_RECT_CULLED) {
         // decode the work id once; every tile of the rect gets the same self-contained record
-        const ZrObject* __restrict__ O = objs + find_object_work(objs, (int)P.n_objects, w);
-        const uint32_t local = w - O->work_base;
-        const uint32_t inst_i = local / O->n_meshlets, m = local - inst_i * O->n_meshlets;
-        const XkMeshlet* __restrict__ ml = O->meshlets + m;
-        ZrBinEntry be;
-        const uint4 mh = ld_global((const uint4*)ml);            // VertexOffset, VertexCount, TriangleOffset, TriangleCount
-        be.mpos = O->mpos + mh.x; be.mtri = O->mtri + ld_global(&ml->BindlessContext); be.inst = O->inst + inst_i;
-        be.counts = mh.y | mh.w << 8 | (O->instanced ? 1u << 16 : 0u);
-        be.prim_base = O->prim_base + inst_i * O->n_tris;
-        for (uint32_t ty = ty0; ty <= ty1; ++ty)
-            for (uint32_t tx = tx0; tx <= tx1; ++tx) {
+        const ZrBinEntry be = bin_entry(objs, (int)P.n_objects, w);
+        for (uint32_t ty = R.ty0; ty <= R.ty1; ++ty)
+            for (uint32_t tx = R.tx0; tx <= R.tx1; ++tx) {
                 const uint32_t pos = atomicAdd(&hist[ty * P.tiles_x + tx], 1u);
                 if (pos < P.bin_capacity) bins[pos] = be;
             }
@@ -147,27 +132,35 @@ __global__ __launch_bounds__(1024) void k_bin_fill(ZrPass P, const ZrObject* __r
     if (threadIdx.x == 0 && tot) atomicAdd(&stats->survivors[0], tot);
 }
 
+// The shadow rasteriser's per-wave ring of surviving triangles, SoA in LDS: 3 x (tile-relative X | Y << 16, z) + prim, QCAP words apart.
+// This lane's entry, at q, drawn into the window's keys:
+__device__ __forceinline__ void queue_draw(const int* q, const TileCtx& T, uint32_t* keys32)
+{
+    const RecTri t = tri_unpack((uint32_t)q[0 * QCAP], (uint32_t)q[1 * QCAP], (uint32_t)q[2 * QCAP], (uint32_t)q[3 * QCAP], (uint32_t)q[4 * QCAP],
+                                (uint32_t)q[5 * QCAP], (uint32_t)q[6 * QCAP]);
+    raster_sub<ZR_MODE_SHADOW, true>(t.a, t.b, t.c, t.prim, T, nullptr, keys32);
+}
+
 // Persistent chunk rasteriser.  A chunk = up to ZR_CHUNK consecutive entries of ONE tile's bin list, so a hot tile is
 // spread over many workgroups and the pass is bounded by total work, not by the fullest tile.  Every workgroup pulls
 // chunk ids from one device counter until they run out (each wave reaches the exit test).  Per chunk: clear the
 // window's LDS keys, 4 waves rasterise the chunk's meshlets into them (ds_min), then the touched keys are merged into
 // the shadow map in HBM (float bits as uint) with global atomic min: the merge IS the LESS_OR_EQUAL depth write.
 // Triangles that need the clipper (or the 64-bit walk) are not rasterised here but appended, with their tile, to `slow` for
-// k_tile_slow: without the call to raster_clipped in its loop the kernel needs half the registers, i.e. twice the waves per SIMD
+// k_shadow_slow: without the call to raster_clipped in its loop the kernel needs half the registers, i.e. twice the waves per SIMD
 // fit - next to each other and next to the other lane's kernels.
 // LATE (after k_shadow_occlusion): unit u is the ONE entry bins[bin_capacity - 1 - u], its tile in the record's prim_base
-// (the shadow pass has no use for a primitive id); the units are counted in slot 1 of the pipeline's block, slow triangles stay in `slot`.
+// (the shadow pass has no use for a primitive id); the units are counted in slot 1 of the pipeline's block, slow triangles stay in slot 0.
 template <bool LATE>
 __global__ __launch_bounds__(RTHREADS) __attribute__((amdgpu_waves_per_eu(ZR_RASTER_WAVES_DEFER)))
 void k_raster_chunks(ZrPass P, const ZrObject* __restrict__ objs, const uint4* __restrict__ chunk_tab,
-                     const ZrBinEntry* __restrict__ bins, ZrDevStats* __restrict__ stats, int slot,
+                     const ZrBinEntry* __restrict__ bins, ZrDevStats* __restrict__ stats,
                      uint32_t* __restrict__ shadow_bits, uint4* __restrict__ slow, uint32_t slow_cap)
 {
-    constexpr uint32_t WIN = SPAN(ZR_MODE_SHADOW), WIN_PIX = WIN * WIN;      // the key window: edge, texels
-    __shared__ uint32_t keys32[WIN_PIX];
+    __shared__ uint32_t keys32[SPAN_PIX(ZR_MODE_SHADOW)];      // the key window
     __shared__ int4 vstage[RW][WAVE];
-    // per-wave ring of surviving triangles, SoA: 3 x (tile-relative X | Y << 16, z) + prim.  Only small triangles (edges under 64 px)
-    // that reach the tile are queued, so a relative coordinate lies within [-16384, 24576] sub-pixel units and fits 16 bits.
+    // per-wave ring of surviving triangles (queue_draw).  Only small triangles (edges under 64 px) that reach the tile are queued, so a
+    // relative coordinate lies within [-16384, 24576] sub-pixel units and fits 16 bits.
     __shared__ int queue[RW][7][QCAP];
     __shared__ uint32_t cur_chunk;
 
@@ -175,28 +168,22 @@ void k_raster_chunks(ZrPass P, const ZrObject* __restrict__ objs, const uint4* _
     // then live in SGPRs and are fetched with scalar loads - some 30 VGPRs less in the hot loop (one more wave per SIMD, and this
     // kernel waits on dependent loads most of the time)
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = wave_uniform(tid >> 6);
-    const int cslot = LATE ? 1 : slot;
-    const uint32_t n_chunks = LATE ? min(stats->n_chunks[1], P.bin_capacity - min(stats->bin_entries[slot], P.bin_capacity)) : stats->n_chunks[slot];
+    const uint32_t n_chunks = LATE ? min(stats->n_chunks[1], P.bin_capacity - min(stats->bin_entries[0], P.bin_capacity)) : stats->n_chunks[0];
 
-    // the first two chunks of a workgroup are its own index and that + the grid (no atomic: an empty pass costs nothing), later ones
-    // come from the counter
     uint32_t chunk = blockIdx.x;
     bool first = true;
     for (;;) {
         if (chunk >= n_chunks) break;
-        for (uint32_t i = tid; i < WIN_PIX; i += RTHREADS) keys32[i] = 0x3F800000u;
+        keys_clear(keys32, tid, RTHREADS);
         __syncthreads();
         // this work unit: (tile, first entry, end) as k_scan laid it out: one load, not a search over the tiles' chunk offsets
         uint4 ct;
         if (LATE) { const uint32_t idx = P.bin_capacity - 1u - chunk; ct = make_uint4(((const uint4*)bins)[2u * idx + 1u].w, idx, idx + 1u, 0u); }
         else ct = chunk_tab[chunk];
         const uint32_t tile = ct.x, beg = ct.y, end = min(ct.z, P.bin_capacity);
-        // Everything below works in TILE-RELATIVE coordinates (origin = the tile's first pixel): edge functions, depth planes and
-        // bounding boxes are built from coordinate differences, so the integers and floats are the ones absolute coordinates give.
-        const int tpx0 = (int)(tile % P.tiles_x) * TILE, tpy0 = (int)(tile / P.tiles_x) * TILE;
+        int tpx0, tpy0;
+        const TileCtx T = tile_ctx(P, tile, tpx0, tpy0);
         const int ox = tpx0 * 256, oy = tpy0 * 256;
-        TileCtx T;
-        T.px0 = 0; T.py0 = 0; T.W = (int)P.W - tpx0; T.H = (int)P.H - tpy0;
 
         uint32_t qhead = 0, qn = 0;
         // The next entry's 32-byte record is fetched (vector loads, vmcnt-ordered) while the current one is processed; every
@@ -207,37 +194,24 @@ void k_raster_chunks(ZrPass P, const ZrObject* __restrict__ objs, const uint4* _
         for (uint32_t e = beg + wv; e < end; e += RW) {
             const uint4 r0 = n0, r1 = n1;
             if (e + RW < end) { n0 = rec[2u * (e + RW)]; n1 = rec[2u * (e + RW) + 1u]; }
-            const float4* __restrict__ mp = (const float4*)(((unsigned long long)wave_uniform(r0.y) << 32) | wave_uniform(r0.x));
-            const uint2* __restrict__ tw = (const uint2*)(((unsigned long long)wave_uniform(r0.w) << 32) | wave_uniform(r0.z));
-            const ZrInstance* __restrict__ ip = (const ZrInstance*)(((unsigned long long)wave_uniform(r1.y) << 32) | wave_uniform(r1.x));
-            const uint32_t counts = wave_uniform(r1.z), pbase = wave_uniform(r1.w);
-            const uint32_t vcount = counts & 255u, tcount = (counts >> 8) & 255u;
-            const bool instanced = (counts >> 16) & 1u;
-
-            // both rounds' triangle words and the vertex are requested together, before anything waits
-            uint2 tri_w[2];
-            tri_w[0] = lane < tcount ? ld_global(tw + lane) : make_uint2(0u, 0u);
-            tri_w[1] = lane + WAVE < tcount ? ld_global(tw + lane + WAVE) : make_uint2(0u, 0u);
-            const float4 pp = lane < vcount ? ld_global(mp + lane) : make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-            const ZrInstance I = ld_record(ip);
-
-            lds_fence();   // this wave's previous readers are done with its staging area
-            // Almost every meshlet has no vertex outside the frustum at all: that is one wave-wide vote over ten comparisons (each a
-            // 64-lane mask by itself); only a flagged meshlet pays for the per-vertex flag words and the per-triangle classification.
-            bool flagged;
-            {
-                const zf4 c = zr_mat4_point(P.PVM, vs_position(zr3(pp.x, pp.y, pp.z), I, instanced));
-                const float FM = 3.402823466e38f, gb = ZR_GUARD * c.w;
-                const bool fin = __builtin_fabsf(c.x) <= FM && __builtin_fabsf(c.y) <= FM && __builtin_fabsf(c.z) <= FM && __builtin_fabsf(c.w) <= FM;
-                const bool odd = !fin || c.x < -c.w || c.x > c.w || c.y < -c.w || c.y > c.w || c.z < 0.0f || c.z > c.w ||
-                                 !(c.w > 0.0f) || __builtin_fabsf(c.x) > gb || __builtin_fabsf(c.y) > gb;
-                flagged = __ballot(lane < vcount && odd) != 0ull;
-                if (lane < vcount) {
-                    const uint32_t f = flagged ? vertex_flags(c) : 0u;
-                    SV s; s.X = 0; s.Y = 0; s.z = 0.0f; s.rw = 0.0f;
-                    if (!(f & 129u)) s = project(c, P.hw, P.hh);
-                    vstage[wv][lane] = make_int4(s.X - ox, s.Y - oy, (int)zr_f2u(s.z), (int)f);      // snapped x, y (tile-relative), depth, clip flags
-                }
+            const ZrBinEntry be = { (const float4*)(((unsigned long long)wave_uniform(r0.y) << 32) | wave_uniform(r0.x)),
+                                    (const uint2*)(((unsigned long long)wave_uniform(r0.w) << 32) | wave_uniform(r0.z)),
+                                    (const ZrInstance*)(((unsigned long long)wave_uniform(r1.y) << 32) | wave_uniform(r1.x)),
+                                    wave_uniform(r1.z), wave_uniform(r1.w) };      // the record's words, made known-uniform
+            const MeshletHead H = meshlet_head(P.PVM, be, lane);
+            const uint32_t tcount = H.tcount;
+            const uint2 tri_w[2] = { H.tri_w[0], H.tri_w[1] };
+            const zf4 c = H.c;
+            const float FM = 3.402823466e38f, gb = ZR_GUARD * c.w;
+            const bool fin = __builtin_fabsf(c.x) <= FM && __builtin_fabsf(c.y) <= FM && __builtin_fabsf(c.z) <= FM && __builtin_fabsf(c.w) <= FM;
+            const bool odd = !fin || c.x < -c.w || c.x > c.w || c.y < -c.w || c.y > c.w || c.z < 0.0f || c.z > c.w ||
+                             !(c.w > 0.0f) || __builtin_fabsf(c.x) > gb || __builtin_fabsf(c.y) > gb;
+            const bool flagged = __ballot(lane < H.vcount && odd) != 0ull;
+            if (lane < H.vcount) {
+                const uint32_t f = flagged ? vertex_flags(c) : 0u;
+                SV s; s.X = 0; s.Y = 0; s.z = 0.0f; s.rw = 0.0f;
+                if (!(f & 129u)) s = project(c, P.hw, P.hh);
+                vstage[wv][lane] = make_int4(s.X - ox, s.Y - oy, (int)zr_f2u(s.z), (int)f);      // snapped x, y (tile-relative), depth, clip flags
             }
             lds_fence();
 
@@ -250,7 +224,7 @@ void k_raster_chunks(ZrPass P, const ZrObject* __restrict__ objs, const uint4* _
                 const uint32_t t = t0 + lane;
                 bool alive = false;
                 int4 r0 = make_int4(0, 0, 0, 0), r1 = r0, r2 = r0;
-                const uint32_t prim = pbase + tri_w[round].y;
+                const uint32_t prim = H.pbase + tri_w[round].y;
                 if (t < tcount) {
                     const uint32_t i0 = tri_w[round].x & 255u, i1 = (tri_w[round].x >> 8) & 255u, i2 = (tri_w[round].x >> 16) & 255u;
                     r0 = vstage[wv][i0]; r1 = vstage[wv][i1]; r2 = vstage[wv][i2];
@@ -259,16 +233,16 @@ void k_raster_chunks(ZrPass P, const ZrObject* __restrict__ objs, const uint4* _
                     // (it leaves a triangle that needs no clipping as it is, so the pixels are the same) - but only for the windows its
                     // snapped box reaches: a ground triangle under a 2048^2 map is met in thousands of tiles' lists and touches a few
                     if (cls == 1 && !tri_is_small(r0.x, r0.y, r1.x, r1.y, r2.x, r2.y))
-                        cls = tri_prefilter<ZR_MODE_SHADOW>(r0.x, r0.y, r1.x, r1.y, r2.x, r2.y, T) ? 2 : 0;
-                    if (cls == 1) alive = tri_prefilter<ZR_MODE_SHADOW>(r0.x, r0.y, r1.x, r1.y, r2.x, r2.y, T);
+                        cls = tri_prefilter(r0.x, r0.y, r1.x, r1.y, r2.x, r2.y, T) ? 2 : 0;
+                    if (cls == 1) alive = tri_prefilter(r0.x, r0.y, r1.x, r1.y, r2.x, r2.y, T);
                     else if (cls == 2) {
-                        zf4 cc[3];
+                        zf4 cc[3];      // (transformed before the place is claimed; k_geom's writer claims first: see DESIGN App. A)
                         const uint32_t li[3] = { i0, i1, i2 };
                         for (int k = 0; k < 3; ++k) {
-                            const float4 pk = ld_global(mp + li[k]);
-                            cc[k] = zr_mat4_point(P.PVM, vs_position(zr3(pk.x, pk.y, pk.z), I, instanced));
+                            const float4 pk = ld_global(H.mp + li[k]);
+                            cc[k] = zr_mat4_point(P.PVM, vs_position(zr3(pk.x, pk.y, pk.z), H.I, H.instanced));
                         }
-                        const uint32_t pos = atomicAdd(&stats->n_slow[slot], 1u);          // rare: one atomic apiece does
+                        const uint32_t pos = atomicAdd(&stats->n_slow[0], 1u);          // rare: one atomic apiece does
                         if (pos < slow_cap) {
                             for (int k = 0; k < 3; ++k) slow[4u * pos + (uint32_t)k] = make_uint4(zr_f2u(cc[k].x), zr_f2u(cc[k].y), zr_f2u(cc[k].z), zr_f2u(cc[k].w));
                             slow[4u * pos + 3u] = make_uint4(prim, tile, 0u, 0u);
@@ -288,46 +262,56 @@ void k_raster_chunks(ZrPass P, const ZrObject* __restrict__ objs, const uint4* _
                 if (ZR_DIAG_SKIP(P.debug_skip) >= 1u) { qhead = (qhead + qn) & (QCAP - 1u); qn = 0; }
                 if (qn >= WAVE) {
                     lds_fence();
-                    const int* q = &queue[wv][0][(qhead + lane) & (QCAP - 1u)];
-                    SV a, b, c;
-                    a.X = (short)q[0 * QCAP]; a.Y = q[0 * QCAP] >> 16; a.z = zr_u2f((uint32_t)q[1 * QCAP]); a.rw = 0.0f;
-                    b.X = (short)q[2 * QCAP]; b.Y = q[2 * QCAP] >> 16; b.z = zr_u2f((uint32_t)q[3 * QCAP]); b.rw = 0.0f;
-                    c.X = (short)q[4 * QCAP]; c.Y = q[4 * QCAP] >> 16; c.z = zr_u2f((uint32_t)q[5 * QCAP]); c.rw = 0.0f;
-                    raster_sub<ZR_MODE_SHADOW, true>(a, b, c, (uint32_t)q[6 * QCAP], T, nullptr, keys32);
+                    queue_draw(&queue[wv][0][(qhead + lane) & (QCAP - 1u)], T, keys32);
                     qhead = (qhead + WAVE) & (QCAP - 1u); qn -= WAVE;
                 }
             }
         }
         if (qn) {      // flush the tail of this chunk
             lds_fence();
-            if (lane < qn) {
-                const int* q = &queue[wv][0][(qhead + lane) & (QCAP - 1u)];
-                SV a, b, c;
-                a.X = (short)q[0 * QCAP]; a.Y = q[0 * QCAP] >> 16; a.z = zr_u2f((uint32_t)q[1 * QCAP]); a.rw = 0.0f;
-                b.X = (short)q[2 * QCAP]; b.Y = q[2 * QCAP] >> 16; b.z = zr_u2f((uint32_t)q[3 * QCAP]); b.rw = 0.0f;
-                c.X = (short)q[4 * QCAP]; c.Y = q[4 * QCAP] >> 16; c.z = zr_u2f((uint32_t)q[5 * QCAP]); c.rw = 0.0f;
-                raster_sub<ZR_MODE_SHADOW, true>(a, b, c, (uint32_t)q[6 * QCAP], T, nullptr, keys32);
-            }
+            if (lane < qn) queue_draw(&queue[wv][0][(qhead + lane) & (QCAP - 1u)], T, keys32);
             qhead = (qhead + qn) & (QCAP - 1u); qn = 0;
         }
         __syncthreads();
-
-        // merge the touched keys into HBM
-        for (uint32_t i = tid; i < WIN_PIX; i += RTHREADS) {
-            const int px = tpx0 + (int)(i % WIN), py = tpy0 + (int)(i / WIN);
-            if (px >= (int)P.W || py >= (int)P.H) continue;
-            const size_t p = (size_t)py * P.W + (size_t)px;
-            // (a key still at its clear value 1.0 cannot lower the map, whose texels never exceed 1.0: its texel is not even read - the
-            // untouched four fifths of a window's 1 936 texels were 15 MB of the pass's 25 MB of reads, profiles/r06_shadow_tcc.txt)
-            const uint32_t k = keys32[i];
-            if (k != 0x3F800000u && k < shadow_bits[p]) atomicMin(&shadow_bits[p], k);
-        }
-        // (the next unit is claimed only when this one is done: claiming early costs more in tail balance than the atomic's latency)
-        // ... and the second unit of a workgroup is fixed like the first (b + grid): claims on one counter queue up for ~10 ns apiece
+        keys_merge(P, tpx0, tpy0, keys32, shadow_bits, tid, RTHREADS);
+        // the next unit, as claim_unit (zr_raster.h) hands them out, but for its last barrier: the keys are re-cleared, behind one, at the
+        // top of the loop (spelled out: through the helper the kernel's scalar registers are allocated differently)
         if (first) { first = false; __syncthreads(); chunk += gridDim.x; continue; }
-        if (tid == 0) cur_chunk = 2u * gridDim.x + atomicAdd(&stats->chunk_counter[cslot], 1u);
-        __syncthreads();   // keys are re-cleared at the top of the loop
+        if (tid == 0) cur_chunk = 2u * gridDim.x + atomicAdd(&stats->chunk_counter[LATE ? 1 : 0], 1u);
+        __syncthreads();
         chunk = cur_chunk;
+    }
+}
+
+// The slow triangles of the pass (they need the clipper, or have an edge of 64 px or more): every tile draws the ones its list named
+// through raster_clipped.  A SMALL persistent grid (ZR_SLOW_BLOCKS workgroups stride over the tiles): the usual pass has no slow triangle,
+// and as one workgroup per tile the launch cost tens of microseconds just to find room beside the other lane's kernels and return.
+#ifndef ZR_SLOW_BLOCKS
+#define ZR_SLOW_BLOCKS 256u
+#endif
+__global__ __launch_bounds__(256) void k_shadow_slow(ZrPass P, const uint32_t* __restrict__ tiles, uint32_t n_tiles, const uint4* __restrict__ slow,
+                                                     uint32_t slow_cap, ZrDevStats* __restrict__ stats, uint32_t* __restrict__ shadow_bits)
+{
+    __shared__ uint32_t keys32[SPAN_PIX(ZR_MODE_SHADOW)];
+    const uint32_t n_slow = min(stats->n_slow[0], slow_cap);
+    if (n_slow == 0u) return;
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t ti = blockIdx.x; ti < n_tiles; ti += gridDim.x) {
+        const uint32_t tile = tiles[ti];
+        keys_clear(keys32, tid, 256u);
+        __syncthreads();
+        int tpx0, tpy0;
+        const TileCtx T = tile_ctx(P, tile, tpx0, tpy0);
+        for (uint32_t j = tid; j < n_slow; j += 256u) {
+            const uint4 q3 = slow[4u * j + 3u];
+            if (q3.y != tile) continue;          // (the rasteriser lists a triangle once per tile of its meshlet)
+            zf4 c0, c1, c2;
+            slow_read(slow, j, c0, c1, c2);
+            raster_clipped<ZR_MODE_SHADOW>(c0, c1, c2, q3.x, T, P.hw, P.hh, tpx0 * 256, tpy0 * 256, nullptr, keys32);
+        }
+        __syncthreads();
+        keys_merge(P, tpx0, tpy0, keys32, shadow_bits, tid, 256u);
+        __syncthreads();      // the keys are cleared again for the next tile
     }
 }
 
@@ -431,18 +415,11 @@ __global__ __launch_bounds__(256) void k_shadow_occlusion(ZrPass P, const ZrObje
         if (live && !flagged && !hidden) {
             // late: one self-contained record per (tile, meshlet-instance), as k_bin_fill writes them, with the tile in prim_base
             ++n_late;
-            const ZrObject* __restrict__ O = objs + find_object_work(objs, (int)P.n_objects, w);
-            const uint32_t local = w - O->work_base;
-            const uint32_t inst_i = local / O->n_meshlets, m = local - inst_i * O->n_meshlets;
-            const XkMeshlet* __restrict__ ml = O->meshlets + m;
-            ZrBinEntry be;
-            const uint4 mh = ld_global((const uint4*)ml);            // VertexOffset, VertexCount, TriangleOffset, TriangleCount
-            be.mpos = O->mpos + mh.x; be.mtri = O->mtri + ld_global(&ml->BindlessContext); be.inst = O->inst + inst_i;
-            be.counts = mh.y | mh.w << 8 | (O->instanced ? 1u << 16 : 0u);
+            ZrBinEntry be = bin_entry(objs, (int)P.n_objects, w);
             const uint32_t room = P.bin_capacity - min(stats->bin_entries[0], P.bin_capacity);      // above the first launch's entries
-            const uint32_t tx0 = r & 255u, ty0 = (r >> 8) & 255u, tx1 = (r >> 16) & 255u, ty1 = r >> 24;
-            for (uint32_t ty = ty0; ty <= ty1; ++ty)
-                for (uint32_t tx = tx0; tx <= tx1; ++tx) {
+            const TileRect R = rect_unpack(r);
+            for (uint32_t ty = R.ty0; ty <= R.ty1; ++ty)
+                for (uint32_t tx = R.tx0; tx <= R.tx1; ++tx) {
                     const uint32_t pos = atomicAdd(&stats->n_chunks[1], 1u);      // (late entries are few; a light that jumps pays ~10 ns apiece here)
                     be.prim_base = ty * P.tiles_x + tx;
                     if (pos < room) bins[P.bin_capacity - 1u - pos] = be;
@@ -480,10 +457,10 @@ void zr_launch_bin_count(const ZrPass& P, const uint32_t* work, const uint32_t* 
     hipLaunchKernelGGL(k_bin_count, dim3((P.n_work + 1023) / 1024), dim3(1024), n_tiles * sizeof(uint32_t), s, P, work, rects, tile_count, Z, stats);
 }
 void zr_launch_scan(uint32_t* tile_count, uint32_t* tile_offset, uint32_t* tile_cursor, uint32_t* chunk_offset, uint4* chunk_tab,
-                    uint32_t chunk_cap, uint32_t n, uint32_t capacity, ZrDevStats* stats, int slot, hipStream_t s,
+                    uint32_t chunk_cap, uint32_t n, uint32_t capacity, ZrDevStats* stats, hipStream_t s,
                     uint32_t chunk)
 {
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, tile_count, tile_offset, tile_cursor, chunk_offset, chunk_tab, chunk_cap, n, capacity, stats, slot, chunk);
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, tile_count, tile_offset, tile_cursor, chunk_offset, chunk_tab, chunk_cap, n, capacity, stats, chunk);
 }
 void zr_launch_bin_fill(const ZrPass& P, const ZrObject* objs, const uint32_t* work, const uint32_t* rects, const uint32_t* tile_offset,
                         uint32_t* tile_cursor, ZrBinEntry* bins, const ZrHiz& Z, ZrDevStats* stats, hipStream_t s)
@@ -493,14 +470,13 @@ void zr_launch_bin_fill(const ZrPass& P, const ZrObject* objs, const uint32_t* w
     hipLaunchKernelGGL(k_bin_fill, dim3((P.n_work + 1023) / 1024), dim3(1024), n_tiles * sizeof(uint32_t), s, P, objs, work, rects,
                        tile_offset, tile_cursor, bins, Z, stats);
 }
-void zr_launch_raster_chunks(const ZrPass& P, const ZrObject* objs, const uint4* chunk_tab, const ZrBinEntry* bins, ZrDevStats* stats, int slot,
+void zr_launch_raster_chunks(const ZrPass& P, const ZrObject* objs, const uint4* chunk_tab, const ZrBinEntry* bins, ZrDevStats* stats,
                              uint32_t* shadow_bits, uint32_t n_blocks, hipStream_t s, uint4* slow, uint32_t slow_cap, const uint32_t* tiles,
                              uint32_t n_tiles, int stage)
 {
-    if (stage == 2) hipLaunchKernelGGL(k_raster_chunks<true>, dim3(n_blocks), dim3(RTHREADS), 0, s, P, objs, chunk_tab, bins, stats, slot, shadow_bits, slow, slow_cap);
-    else hipLaunchKernelGGL(k_raster_chunks<false>, dim3(n_blocks), dim3(RTHREADS), 0, s, P, objs, chunk_tab, bins, stats, slot, shadow_bits, slow, slow_cap);
-    if (n_tiles && stage != 1) hipLaunchKernelGGL((k_tile_slow<ZR_MODE_SHADOW, true>), dim3(std::min<uint32_t>(n_tiles, ZR_SLOW_BLOCKS)), dim3(256), 0, s, P, tiles, n_tiles, slow, slow_cap, stats, slot,
-                                    (unsigned long long*)nullptr, shadow_bits, (const uint32_t*)nullptr, 0u);
+    if (stage == 2) hipLaunchKernelGGL(k_raster_chunks<true>, dim3(n_blocks), dim3(RTHREADS), 0, s, P, objs, chunk_tab, bins, stats, shadow_bits, slow, slow_cap);
+    else hipLaunchKernelGGL(k_raster_chunks<false>, dim3(n_blocks), dim3(RTHREADS), 0, s, P, objs, chunk_tab, bins, stats, shadow_bits, slow, slow_cap);
+    if (n_tiles && stage != 1) hipLaunchKernelGGL(k_shadow_slow, dim3(std::min<uint32_t>(n_tiles, ZR_SLOW_BLOCKS)), dim3(256), 0, s, P, tiles, n_tiles, slow, slow_cap, stats, shadow_bits);
 }
 void zr_launch_shadow_occlusion(const ZrPass& P, const ZrObject* objs, const uint32_t* work, const uint32_t* rects, const uint2* pxrect,
                                 const float* zmin, uint8_t* flags, const uint32_t* shadow_bits, ZrBinEntry* bins, ZrDevStats* stats,

@@ -7,6 +7,7 @@
 #include "../../include/zelda_render.h"
 
 #define ZR_EMPTY_PRIM 0xFFFFFFFFu
+#define ZR_EMPTY_KEY ((unsigned long long)0x3F800000u << 32 | ZR_EMPTY_PRIM)      // a pixel of the key buffer nothing has won: depth 1.0, no primitive
 #define ZR_GUARD 4.0f                       // guard band, multiples of w
 #define ZR_RECT_CULLED 0xFFFFFFFFu
 #ifndef ZR_CHUNK
@@ -266,7 +267,7 @@ void zr_launch_bin_count(const ZrPass& P, const uint32_t* work, const uint32_t* 
                          hipStream_t s);
 void zr_launch_hiz_build(const unsigned long long* vis64, uint32_t W, uint32_t H, const ZrHiz& Z, const uint32_t* regions, uint32_t n_regions, hipStream_t s);
 void zr_launch_scan(uint32_t* tile_count, uint32_t* tile_offset, uint32_t* tile_cursor, uint32_t* chunk_offset, uint4* chunk_tab,
-                    uint32_t chunk_cap, uint32_t n, uint32_t capacity, ZrDevStats* stats, int slot, hipStream_t s,
+                    uint32_t chunk_cap, uint32_t n, uint32_t capacity, ZrDevStats* stats, hipStream_t s,
                     uint32_t chunk = ZR_CHUNK);
 // triangle-binned camera pass, per round: [k_select ->] k_geom -> k_tile; once per frame, after the resolve: k_plan (the next frame's buckets)
 struct ZrTriBins {
@@ -324,9 +325,9 @@ void zr_launch_fill64(unsigned long long* p, unsigned long long v, size_t n, hip
 void zr_launch_shadow_occlusion(const ZrPass& P, const ZrObject* objs, const uint32_t* work, const uint32_t* rects, const uint2* pxrect,
                                 const float* zmin, uint8_t* flags, const uint32_t* shadow_bits, ZrBinEntry* bins, ZrDevStats* stats,
                                 uint32_t n_blocks, uint32_t retest, hipStream_t s);
-// the shadow rasteriser over the bins, then k_tile_slow for the clipped triangles it listed in `slow`.  stage 0: everything; 1: the
-// flagged share only (k_tile_slow waits); 2: the late list, then k_tile_slow
-void zr_launch_raster_chunks(const ZrPass& P, const ZrObject* objs, const uint4* chunk_tab, const ZrBinEntry* bins, ZrDevStats* stats, int slot,
+// the shadow rasteriser over the bins, then k_shadow_slow for the clipped triangles it listed in `slow`.  stage 0: everything; 1: the
+// flagged share only (k_shadow_slow waits); 2: the late list, then k_shadow_slow
+void zr_launch_raster_chunks(const ZrPass& P, const ZrObject* objs, const uint4* chunk_tab, const ZrBinEntry* bins, ZrDevStats* stats,
                              uint32_t* shadow_bits, uint32_t n_blocks, hipStream_t s, uint4* slow, uint32_t slow_cap, const uint32_t* tiles,
                              uint32_t n_tiles, int stage);
 void zr_launch_mark(const ZrPass& P, const ZrObject* objs, const uint32_t* owned_tiles, uint32_t n_owned, const unsigned long long* vis64,
