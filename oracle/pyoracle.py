@@ -82,6 +82,17 @@ def lib(literal=False):
         L.zo_kat_tex_mip.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p]
         L.zo_kat_cube_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
         L.zo_kat_cube_mip.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        # the batch forms (tests/device_function_cases.py): tables of word records in, word records out
+        L.zo_kat_set_shadowmap.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.zo_kat_cube_sample_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.zo_kat_pcf_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.zo_kat_shade_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.zo_kat_shadow_tap_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        L.zo_kat_sincos_intcast.argtypes = [C.c_float, C.c_void_p]
+        for n in ("zo_kat_set_shadowmap", "zo_kat_sincos_intcast"):
+            getattr(L, n).restype = C.c_int
+        for n in ("zo_kat_cube_sample_batch", "zo_kat_pcf_batch", "zo_kat_shade_batch", "zo_kat_shadow_tap_batch"):
+            getattr(L, n).restype = None
         _lib = _libs[path] = L
     return _lib
 

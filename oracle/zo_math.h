@@ -31,9 +31,29 @@ typedef struct { float x, y, z, w; } zo_v4;
 static inline uint32_t zo_f2u(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
 static inline float zo_u2f(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
 
+/* min / max of the shader math (clamp, saturate, max(x, 0), the UNORM stores).  C's fminf / fmaxf leave two things to the library: the sign
+ * of a zero when the operands are zeros of opposite sign, and a signalling NaN (glibc returns a NaN for it, where a quiet NaN yields
+ * the other operand).  The contract is what gfx950's v_max_f32 / v_min_f32 do, which is IEEE 754-2019 maximumNumber / minimumNumber: a
+ * NaN of either kind yields the other operand (NaN only if both are), max(-0, +0) = +0 and min(-0, +0) = -0 in either order. */
+static inline float zo_fmaxf(float a, float b)
+{
+    if (a != a) return b;
+    if (b != b) return a;
+    if (a == b) return signbit(a) ? b : a;
+    return a > b ? a : b;
+}
+static inline float zo_fminf(float a, float b)
+{
+    if (a != a) return b;
+    if (b != b) return a;
+    if (a == b) return signbit(a) ? a : b;
+    return a < b ? a : b;
+}
+
 /* ---- transcendental kernels (all fp32, fixed op order) ---- */
 
-/* sin and cos of x (radians).  k = rint(x*2/pi); r = x - k*pi/2 in three fma steps. */
+/* sin and cos of x (radians).  k = rint(x*2/pi); r = x - k*pi/2 in three fma steps.  Accurate for |x| up to ~1e5; beyond, still one
+   value per input (csrc/zr_math.h: zr_sincos states the domain). */
 static inline void zo_sincosf(float x, float* s, float* c)
 {
     float k = rintf(x * 0.636619772367581343f);
@@ -47,7 +67,10 @@ static inline void zo_sincosf(float x, float* s, float* c)
     float pc = fmaf(r2, 2.443315711809948e-5f, -1.388731625493765e-3f);
     pc = fmaf(r2, pc, 4.166664568298827e-2f);
     float cs = fmaf(r2 * r2, pc, fmaf(r2, -0.5f, 1.0f));
-    int q = ((int)k) & 3;
+    /* k mod 4 in float: exact for every finite k, where a cast of k to int is undefined from |k| = 2^31 (x ~ 3.37e9).  From 2^25 on k is
+       a multiple of 4: quadrant 0.  Non-finite k (x = +-inf, NaN): quadrant 0, and both results are NaN. */
+    float kq = k - 4.0f * floorf(k * 0.25f);
+    int q = (kq > 0.0f) ? (int)kq : 0;
     float so = (q & 1) ? cs : sn;
     float co = (q & 1) ? sn : cs;
     if (q == 1 || q == 2) co = -co;
@@ -108,8 +131,8 @@ static inline float zo_powf(float x, float y) { return zo_exp2f(y * zo_log2f(x))
 static inline float zo_pow5f(float x) { float x2 = x * x; float x4 = x2 * x2; return x4 * x; }
 
 /* ---- GLSL helpers, fixed op order ---- */
-static inline float zo_saturate(float t) { return fminf(fmaxf(t, 0.0f), 1.0f); }            /* Common.glsl:23 */
-static inline float zo_clampf(float t, float a, float b) { return fminf(fmaxf(t, a), b); }
+static inline float zo_saturate(float t) { return zo_fminf(zo_fmaxf(t, 0.0f), 1.0f); }            /* Common.glsl:23 */
+static inline float zo_clampf(float t, float a, float b) { return zo_fminf(zo_fmaxf(t, a), b); }
 static inline zo_v3 zo_v3make(float x, float y, float z) { zo_v3 r = { x, y, z }; return r; }
 static inline zo_v3 zo_add(zo_v3 a, zo_v3 b) { return zo_v3make(a.x + b.x, a.y + b.y, a.z + b.z); }
 static inline zo_v3 zo_sub(zo_v3 a, zo_v3 b) { return zo_v3make(a.x - b.x, a.y - b.y, a.z - b.z); }
@@ -229,7 +252,7 @@ static inline float zo_f16_to_f32(uint16_t h)
 /* float -> UNORM with N bits: NaN -> 0, clamp, round half up on c*max+0.5 (fixed evaluation) */
 static inline uint32_t zo_unorm(float c, float maxv)
 {
-    c = fminf(fmaxf(c, 0.0f), 1.0f);
+    c = zo_fminf(zo_fmaxf(c, 0.0f), 1.0f);
     return (uint32_t)floorf(fmaf(c, maxv, 0.5f));
 }
 

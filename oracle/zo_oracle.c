@@ -268,7 +268,7 @@ int zo_set_cubemap(zo_ctx* c, const uint8_t* const faces[6], uint32_t dim)
 
 static int zo_idx_clamp(float f, int hi)          /* NaN-safe float -> clamped int */
 {
-    f = fminf(fmaxf(f, 0.0f), (float)hi);
+    f = zo_fminf(zo_fmaxf(f, 0.0f), (float)hi);
     return (int)f;
 }
 
@@ -305,7 +305,7 @@ static zo_v3 zo_cube_sample(const zo_ctx* c, zo_v3 R, float lod)
     zo_v3 st = zo_div_scalar(zo_v3make(sc, tc, 0.0f), ma);     /* (sc, tc) / ma */
     float s = fmaf(st.x, 0.5f, 0.5f), t = fmaf(st.y, 0.5f, 0.5f);
     float maxl = (float)(c->cube_levels - 1);
-    float l = fminf(fmaxf(lod, 0.0f), maxl);
+    float l = zo_fminf(zo_fmaxf(lod, 0.0f), maxl);
     float fl = floorf(l);
     int l0 = (int)fl, l1 = l0 + 1 < c->cube_levels ? l0 + 1 : c->cube_levels - 1;
     float w = l - fl;
@@ -456,14 +456,16 @@ typedef struct { int32_t X, Y; float z, rw; } zo_sv;      /* snapped screen vert
 static int zo_finite4(zo_v4 a)
 { return fabsf(a.x) <= 3.402823466e38f && fabsf(a.y) <= 3.402823466e38f && fabsf(a.z) <= 3.402823466e38f && fabsf(a.w) <= 3.402823466e38f; }
 
+/* float -> int of a snapped coordinate, defined for every float (csrc/zr_dev.h: snap_to_int): NaN -> -2^31, the rest clamped to the ints a float holds */
+static int32_t zo_snap_to_int(float f) { return (int32_t)zo_fminf(zo_fmaxf(f, -2147483648.0f), 2147483520.0f); }
 static zo_sv zo_project(zo_v4 c, float hw, float hh)
 {
     zo_sv s;
     s.rw = 1.0f / c.w;                       /* perspective divide: one IEEE reciprocal, then multiplies */
     float nx = c.x * s.rw, ny = c.y * s.rw;
     float xs = fmaf(nx, hw, hw), ys = fmaf(ny, hh, hh);
-    s.X = (int32_t)floorf(fmaf(xs, 256.0f, 0.5f));
-    s.Y = (int32_t)floorf(fmaf(ys, 256.0f, 0.5f));
+    s.X = zo_snap_to_int(floorf(fmaf(xs, 256.0f, 0.5f)));
+    s.Y = zo_snap_to_int(floorf(fmaf(ys, 256.0f, 0.5f)));
     s.z = c.z * s.rw;
     return s;
 }
@@ -561,8 +563,8 @@ static int zo_tri_setup(const zo_sv v[3], int cull_back, zo_setup* s)
     s->z0 = v[0].z;
     s->gx = fmaf(s->a2, dz2, s->a1 * dz1);
     s->gy = fmaf(s->b2, dz2, s->b1 * dz1);
-    s->zlo = fminf(fminf(v[0].z, v[1].z), v[2].z);
-    s->zhi = fmaxf(fmaxf(v[0].z, v[1].z), v[2].z);
+    s->zlo = zo_fminf(zo_fminf(v[0].z, v[1].z), v[2].z);
+    s->zhi = zo_fmaxf(zo_fmaxf(v[0].z, v[1].z), v[2].z);
     s->minX = v[0].X < v[1].X ? (v[0].X < v[2].X ? v[0].X : v[2].X) : (v[1].X < v[2].X ? v[1].X : v[2].X);
     s->maxX = v[0].X > v[1].X ? (v[0].X > v[2].X ? v[0].X : v[2].X) : (v[1].X > v[2].X ? v[1].X : v[2].X);
     s->minY = v[0].Y < v[1].Y ? (v[0].Y < v[2].Y ? v[0].Y : v[2].Y) : (v[1].Y < v[2].Y ? v[1].Y : v[2].Y);
@@ -586,7 +588,7 @@ static float zo_depth_at(const zo_setup* s, int32_t Px, int32_t Py)
     float z = fmaf(s->gy, fy, fmaf(s->gx, fx, s->z0));
     /* the exact interpolant lies within the vertex depths; keep the rounded plane equation there too (a stated rule of
        this restatement: it bounds every fragment of a triangle by its vertices, which occlusion culling relies on) */
-    z = fminf(fmaxf(z, s->zlo), s->zhi);
+    z = zo_fminf(zo_fmaxf(z, s->zlo), s->zhi);
     return z + 0.0f;
 }
 
@@ -595,8 +597,8 @@ static float zo_depth_at(const zo_setup* s, int32_t Px, int32_t Py)
    it counts as 1, the far-clipped polygon's largest depth */
 static float zo_depth_bias(const zo_setup* s, const zo_sv v[3])
 {
-    float m = fmaxf(fabsf(s->gx), fabsf(s->gy)) * 256.0f;
-    float zm = fmaxf(fmaxf(fabsf(v[0].z), fabsf(v[1].z)), fabsf(v[2].z));
+    float m = zo_fmaxf(fabsf(s->gx), fabsf(s->gy)) * 256.0f;
+    float zm = zo_fmaxf(zo_fmaxf(fabsf(v[0].z), fabsf(v[1].z)), fabsf(v[2].z));
     zm = zm > 1.0f ? 1.0f : zm;
     uint32_t e = zo_f2u(zm) & 0x7F800000u;
     float r = (e > (23u << 23) && e < 0x7F800000u) ? zo_u2f(e - (23u << 23)) : 0.0f;
@@ -621,7 +623,7 @@ static void zo_raster_sub(const zo_target* T, const zo_sv v[3], uint32_t prim)
         if (!(z >= 0.0f && z <= 1.0f)) continue;             /* depth clip (depthClampEnable = FALSE, ZE:5100) */
         size_t p = (size_t)y * T->W + (size_t)x;
         if (T->shadow) {
-            float zb = fminf(fmaxf(z + bias, 0.0f), 1.0f);
+            float zb = zo_fminf(zo_fmaxf(z + bias, 0.0f), 1.0f);
             if (zb <= T->depth[p]) T->depth[p] = zb;          /* LESS_OR_EQUAL, ZE:5141-5145 */
         } else if (z < T->depth[p]) {                         /* LESS */
             T->depth[p] = z; T->vis[p] = prim;
@@ -814,12 +816,12 @@ static void zo_tex_trilinear(const zo_ctx* c, const zo_tex* t, int srgb, float l
 static void zo_aniso_setup(float ax, float ay, float bx, float by, int levels, int* Nout, float* lambda_out, int* xmajor_out)
 {
     float rx2 = fmaf(ax, ax, ay * ay), ry2 = fmaf(bx, bx, by * by);
-    float rmax2 = fmaxf(rx2, ry2), rmin2 = fminf(rx2, ry2);
+    float rmax2 = zo_fmaxf(rx2, ry2), rmin2 = zo_fminf(rx2, ry2);
     int N = 1;                                            /* least N with N^2 * Pmin^2 >= Pmax^2, at most maxAniso */
     while (N < ZO_MAX_ANISO && (float)(N * N) * rmin2 < rmax2) ++N;
     float lambda = 0.5f * zo_log2f(rmax2);
     if (N > 1) lambda = lambda - zo_log2f((float)N);
-    *lambda_out = fminf(fmaxf(lambda, 0.0f), (float)(levels - 1));
+    *lambda_out = zo_fminf(zo_fmaxf(lambda, 0.0f), (float)(levels - 1));
     *Nout = N; *xmajor_out = rx2 >= ry2;
 }
 void zo_kat_aniso(float ax, float ay, float bx, float by, int levels, float out[3])
@@ -943,13 +945,13 @@ static void zo_resolve_gbuffer(zo_ctx* c, const float* PVM)
         zo_tex_sample(c, &o->tex[5], 0, f0.u, f0.v, s1, t1, s2, t2, em); zo_tex_sample(c, &o->tex[6], 0, f0.u, f0.v, s1, t1, s2, t2, ms);
 
         zo_v3 Nw = zo_compute_normal(pos_dx, pos_dy, s1, t1, s2, t2, f0.N, zo_v3make(nm[0], nm[1], nm[2]));
-        float Rough = fmaxf(0.01f, ro[0]);
+        float Rough = zo_fmaxf(0.01f, ro[0]);
         if (c->forward) {      /* Base.frag:48-60: the same fetches and ComputeNormal, kept as floats; fragColor interpolated like the rest */
             zo_fsurf* F = &c->fwd[p];
             const XkVertex* v0 = &m->v[m->idx[3 * tri]]; const XkVertex* v1 = &m->v[m->idx[3 * tri + 1u]]; const XkVertex* v2 = &m->v[m->idx[3 * tri + 2u]];
             F->BaseColor = zo_v3make(bc[0], bc[1], bc[2]);
             F->Metallic = zo_saturate(me[0]);
-            F->Roughness = fmaxf(0.01f, zo_saturate(ro[0]));
+            F->Roughness = zo_fmaxf(0.01f, zo_saturate(ro[0]));
             F->Normal = Nw;
             F->AmbientOcclution = zo_v3make(ao[0], ao[1], ao[2]);
             F->P = f0.P;
@@ -996,13 +998,13 @@ static float zo_D_GGX(float NdotH, float r)                                     
 }
 static float zo_ReflectionMip(float r, float maxmip)                                                         /* :191 */
 {
-    float level_from_1x1 = fmaf(-1.2f, zo_log2f(fmaxf(r, 0.001f)), 1.0f);
+    float level_from_1x1 = fmaf(-1.2f, zo_log2f(zo_fmaxf(r, 0.001f)), 1.0f);
     return (maxmip - 1.0f) - level_from_1x1;
 }
 static void zo_EnvBRDFApproxLazarov(float r, float NoV, float AB[2])                                         /* :201 */
 {
     float rx = fmaf(r, -1.0f, 1.0f), ry = fmaf(r, -0.0275f, 0.0425f), rz = fmaf(r, -0.572f, 1.04f), rw = fmaf(r, 0.022f, -0.04f);
-    float a004 = fmaf(fminf(rx * rx, zo_exp2f(-9.28f * NoV)), rx, ry);
+    float a004 = fmaf(zo_fminf(rx * rx, zo_exp2f(-9.28f * NoV)), rx, ry);
     AB[0] = fmaf(-1.04f, a004, rz); AB[1] = fmaf(1.04f, a004, rw);
 }
 
@@ -1133,7 +1135,7 @@ static zo_v3 zo_gbuffer_vis(const zo_ctx* c, uint32_t px, uint32_t py, zo_v3 Fin
     zo_gtexel g; zo_gbuffer_sample(c, UVx, UVy, 3.0f / (1.0f - ERx), 3.0f / (1.0f - ERy), &g);
     zo_v3 BaseColor = zo_v3make(g.c[0], g.c[1], g.c[2]);
     float Metallic = zo_saturate(g.b[0]);
-    float Roughness = fmaxf(0.01f, zo_saturate(g.b[2]));
+    float Roughness = zo_fmaxf(0.01f, zo_saturate(g.b[2]));
     zo_v3 Normal = zo_v3make(fmaf(g.a[0], 2.0f, -1.0f), fmaf(g.a[1], 2.0f, -1.0f), fmaf(g.a[2], 2.0f, -1.0f));
     float AO = zo_saturate(g.c[3]);
     zo_v3 N = zo_normalize(Normal);
@@ -1200,13 +1202,21 @@ static zo_lit zo_shade(const zo_ctx* c, const float* SB, zo_v3 cam, float dxy, z
         float ndotl = zo_clampf(zo_dot(Nn, L), 0.0f, 1.0f);
         float k = ndotl * Lt->Color[3];
         zo_v3 rad = zo_v3make(k * Lt->Color[0], k * Lt->Color[1], k * Lt->Color[2]);
+        float dist = ZO_IS_LITERAL ? sqrtf(d2) : (d2 > 0.0f ? d2 * rd : 0.0f);      /* distance(): literal = its own sqrt */
+        float falloff = Lt->Direction[3];
+        float att = isdir ? 1.0f : 1.0f - zo_clampf(dist, 0.0f, falloff) / falloff;   /* remap(dist,0,falloff,0,1), :43-47 */
+        /* A light whose radiance factor is exactly 0 - N.L clamps to 0, or a point light at or beyond its falloff - adds nothing,
+           whatever its BxDF evaluates to.  The GLSL would add 0 * bxdf, which is NaN where the BxDF is NaN or infinite (D_GGX is 0 / 0 at
+           roughness 0 with N.H = 1; the attenuation is NaN for a falloff of 0) and Direct otherwise; the contract takes Direct in every
+           case, which is what lets the kernel skip such a light (csrc/zr_shade.h).  Only for finite colour and intensity: 0 * inf is
+           NaN in both.  (oracle/CONTRACT.md row 8; the literal build keeps the GLSL's sum.) */
+        int lfinite = fabsf(Lt->Color[0]) <= 3.402823466e38f && fabsf(Lt->Color[1]) <= 3.402823466e38f &&
+                      fabsf(Lt->Color[2]) <= 3.402823466e38f && fabsf(Lt->Color[3]) <= 3.402823466e38f;
+        if (!ZO_IS_LITERAL && lfinite && (ndotl == 0.0f || att == 0.0f)) continue;
         if (isdir) {
             Direct = zo_v3make(fmaf(rad.x * bx.x, ShadowFactor, Direct.x), fmaf(rad.y * bx.y, ShadowFactor, Direct.y),
                                fmaf(rad.z * bx.z, ShadowFactor, Direct.z));
         } else {
-            float dist = ZO_IS_LITERAL ? sqrtf(d2) : (d2 > 0.0f ? d2 * rd : 0.0f);      /* distance(): literal = its own sqrt */
-            float falloff = Lt->Direction[3];
-            float att = 1.0f - zo_clampf(dist, 0.0f, falloff) / falloff;   /* remap(dist,0,falloff,0,1), :43-47 */
             rad = zo_scale(rad, att);
             Direct = zo_v3make(fmaf(rad.x, bx.x, Direct.x), fmaf(rad.y, bx.y, Direct.y), fmaf(rad.z, bx.z, Direct.z));
         }
@@ -1257,7 +1267,7 @@ static void zo_lighting(zo_ctx* c, uint32_t debug_view)
                                  fmaf((float)(A & 1023u) / 1023.0f, 2.0f, -1.0f));
         float AOc = (float)(C >> 24) / 255.0f;
         float Mask = (float)(sc >> 24) / 255.0f;
-        Roughness = fmaxf(0.01f, Roughness);
+        Roughness = zo_fmaxf(0.01f, Roughness);
         float AO = zo_saturate(AOc);
         zo_v3 N = zo_normalize(Normal);
         zo_v3 P = zo_v3make(zo_f16_to_f32((uint16_t)D), zo_f16_to_f32((uint16_t)(D >> 16)), zo_f16_to_f32((uint16_t)(D >> 32)));
@@ -1592,4 +1602,142 @@ int zo_kat_cube_mip(zo_ctx* c, int level, uint8_t* out)                         
     uint32_t d = c->cube_dim >> level; if (!d) d = 1;
     memcpy(out, c->cube[level], (size_t)d * d * 4 * 6);
     return (int)d;
+}
+
+/* ------------------------------------------------------------------ batch KAT exports
+ *
+ * One call per table of cases (tests/device_function_cases.py): case i is a fixed number of 32-bit words in and out, floats as their
+ * bits, in the layout of tests/device_probe/probe.hip, whose kernels run the product's copy of the same function on the GPU. */
+#define ZO_BATCH(name, NIN, NOUT, BODY)                                                       \
+    void zo_kat_##name##_batch(const uint32_t* in, uint32_t* out, uint32_t n)                 \
+    {                                                                                         \
+        for (uint32_t i = 0; i < n; ++i) {                                                    \
+            const uint32_t* a = in + (size_t)i * (NIN); uint32_t* o = out + (size_t)i * (NOUT); \
+            float f[NIN]; memcpy(f, a, sizeof f); (void)a; (void)f;                           \
+            BODY                                                                              \
+        }                                                                                     \
+    }
+static void zo_put3(uint32_t* o, zo_v3 v) { o[0] = zo_f2u(v.x); o[1] = zo_f2u(v.y); o[2] = zo_f2u(v.z); }
+static zo_xform zo_xform_of_record(const float* r) { zo_xform x; memcpy(x.R, r, 36); memcpy(x.t, r + 9, 12); x.s = r[12]; return x; }   /* a 16-word ZrInstance */
+
+ZO_BATCH(rsqrt, 1, 1, o[0] = zo_f2u(zo_rsqrt(f[0]));)
+ZO_BATCH(sincos, 1, 2, float s; float c; zo_sincosf(f[0], &s, &c); o[0] = zo_f2u(s); o[1] = zo_f2u(c);)
+ZO_BATCH(exp2, 1, 1, o[0] = zo_f2u(zo_exp2f(f[0]));)
+ZO_BATCH(log2, 1, 1, o[0] = zo_f2u(zo_log2f(f[0]));)
+ZO_BATCH(pow, 2, 1, o[0] = zo_f2u(zo_powf(f[0], f[1]));)
+ZO_BATCH(pow5, 1, 1, o[0] = zo_f2u(zo_pow5f(f[0]));)
+ZO_BATCH(saturate, 1, 1, o[0] = zo_f2u(zo_saturate(f[0]));)
+ZO_BATCH(clamp, 3, 1, o[0] = zo_f2u(zo_clampf(f[0], f[1], f[2]));)
+ZO_BATCH(unorm, 2, 1, o[0] = zo_unorm(f[0], f[1]);)
+ZO_BATCH(f16_to_f32, 1, 1, o[0] = zo_f2u(zo_f16_to_f32((uint16_t)a[0]));)
+ZO_BATCH(f32_to_f16, 1, 1, o[0] = zo_f32_to_f16(f[0]);)
+ZO_BATCH(unorm8, 1, 1, o[0] = zo_f2u(zo_unorm8_scale((float)(a[0] & 255u)));)
+ZO_BATCH(div, 2, 1, o[0] = zo_f2u(f[0] / f[1]);)
+ZO_BATCH(sqrt, 1, 1, o[0] = zo_f2u(sqrtf(f[0]));)
+ZO_BATCH(dot, 6, 1, o[0] = zo_f2u(zo_dot(zo_v3make(f[0], f[1], f[2]), zo_v3make(f[3], f[4], f[5])));)
+ZO_BATCH(cross, 6, 3, zo_put3(o, zo_cross(zo_v3make(f[0], f[1], f[2]), zo_v3make(f[3], f[4], f[5])));)
+ZO_BATCH(normalize, 3, 3, zo_put3(o, zo_normalize(zo_v3make(f[0], f[1], f[2])));)
+ZO_BATCH(tangent_normal, 3, 3, zo_v3 t = zo_normalize(zo_v3make(f[0], f[1], f[2]));
+         zo_put3(o, zo_normalize(zo_v3make(fmaf(2.0f, t.x, -1.0f), fmaf(2.0f, t.y, -1.0f), fmaf(2.0f, t.z, -1.0f))));)
+ZO_BATCH(mat4_point, 19, 4, zo_v4 r = zo_mat4_point(f, zo_v3make(f[16], f[17], f[18]));
+         o[0] = zo_f2u(r.x); o[1] = zo_f2u(r.y); o[2] = zo_f2u(r.z); o[3] = zo_f2u(r.w);)
+/* the 16-word instance record of one XkInstanceData: R (zo_make_rot), t, s, three zero words */
+ZO_BATCH(instance_record, 8, 16, XkInstanceData d; memcpy(&d, f, sizeof d); zo_object ob; memset(&ob, 0, sizeof ob); ob.inst = &d;
+         zo_xform x; zo_xform_make(&ob, 0, &x); memset(o, 0, 64); memcpy(o, x.R, 36); memcpy(o + 9, x.t, 12); memcpy(o + 12, &x.s, 4);)
+ZO_BATCH(vs_position, 19, 3, XkVertex v; memset(&v, 0, sizeof v); memcpy(v.Position, f, 12); zo_xform x = zo_xform_of_record(f + 3);
+         zo_put3(o, zo_vs_position(&v, &x, 1));)
+ZO_BATCH(vs_normal, 36, 3, XkVertex v; memset(&v, 0, sizeof v); memcpy(v.Normal, f, 12); zo_xform x = zo_xform_of_record(f + 3);
+         zo_put3(o, zo_vs_normal(&v, &x, a[35] != 0u, f + 19));)
+ZO_BATCH(classify, 12, 1, zo_v4 c[3]; memcpy(c, f, sizeof c); o[0] = (uint32_t)zo_classify(c);)
+ZO_BATCH(project, 6, 4, zo_v4 c; memcpy(&c, f, sizeof c); zo_sv s = zo_project(c, f[4], f[5]);
+         o[0] = (uint32_t)s.X; o[1] = (uint32_t)s.Y; o[2] = zo_f2u(s.z); o[3] = zo_f2u(s.rw);)
+ZO_BATCH(F_Schlick, 3, 1, o[0] = zo_f2u(zo_F_Schlick(f[0], f[1], f[2]));)
+ZO_BATCH(Fr_DisneyDiffuse, 4, 1, o[0] = zo_f2u(zo_Fr_DisneyDiffuse(f[0], f[1], f[2], f[3]));)
+ZO_BATCH(V_SmithGGXCorrelated, 3, 1, o[0] = zo_f2u(zo_V_SmithGGXCorrelated(f[0], f[1], f[2]));)
+ZO_BATCH(D_GGX, 2, 1, o[0] = zo_f2u(zo_D_GGX(f[0], f[1]));)
+
+/* zo_shadow_tap over a caller-supplied square map: case = sx, sy, sz, sw, ox, oy */
+void zo_kat_shadow_tap_batch(const uint32_t* in, uint32_t* out, uint32_t n, const float* map, uint32_t dim)
+{
+    zo_ctx c; memset(&c, 0, sizeof c);
+    c.SD = dim; c.shadowmap = (float*)map;       /* read only */
+    for (uint32_t i = 0; i < n; ++i) {
+        float f[6]; memcpy(f, in + (size_t)i * 6, sizeof f);
+        out[i] = zo_f2u(zo_shadow_tap(&c, f[0], f[1], f[2], f[3], f[4], f[5]));
+    }
+}
+/* zo_sincosf as it stood before its quadrant was taken in float: ((int)k) & 3, whose cast is undefined for |k| >= 2^31.  Kept so that
+ * tests/test_device_function_tables.py can show that no bit moved where the cast was defined.  Returns 0 for a case it cannot evaluate. */
+int zo_kat_sincos_intcast(float x, float out[2])
+{
+    float k = rintf(x * 0.636619772367581343f);
+    if (!(fabsf(k) < 2147483648.0f)) return 0;
+    float r = fmaf(-k, 1.5703125f, x);
+    r = fmaf(-k, 4.837512969970703125e-4f, r);
+    r = fmaf(-k, 7.54978995489188216e-8f, r);
+    float r2 = r * r;
+    float ps = fmaf(r2, -1.9515295891e-4f, 8.3321608736e-3f);
+    ps = fmaf(r2, ps, -1.6666654611e-1f);
+    float sn = fmaf(r2 * r, ps, r);
+    float pc = fmaf(r2, 2.443315711809948e-5f, -1.388731625493765e-3f);
+    pc = fmaf(r2, pc, 4.166664568298827e-2f);
+    float cs = fmaf(r2 * r2, pc, fmaf(r2, -0.5f, 1.0f));
+    int q = ((int)k) & 3;
+    float so = (q & 1) ? cs : sn;
+    float co = (q & 1) ? sn : cs;
+    if (q == 1 || q == 2) co = -co;
+    if (q >= 2) so = -so;
+    out[0] = so; out[1] = co;
+    return 1;
+}
+
+/* ---- the functions that read a context: its cubemap (zo_set_cubemap), its XkView (zo_set_frame), its shadow map (below) */
+
+/* hand the context a shadow map of its own edge (zo_create's SD) in place of a rendered one */
+int zo_kat_set_shadowmap(zo_ctx* c, const float* map, uint32_t dim)
+{
+    if (!c || !map || dim != c->SD) return -1;
+    memcpy(c->shadowmap, map, (size_t)dim * dim * sizeof(float));
+    return 0;
+}
+/* case = R.xyz, lod -> rgb */
+void zo_kat_cube_sample_batch(zo_ctx* c, const uint32_t* in, uint32_t* out, uint32_t n)
+{
+    for (uint32_t i = 0; i < n; ++i) {
+        float f[4]; memcpy(f, in + (size_t)i * 4, sizeof f);
+        zo_put3(out + (size_t)i * 3, zo_cube_sample(c, zo_v3make(f[0], f[1], f[2]), f[3]));
+    }
+}
+/* case = P.xyz -> ShadowFactor (zo_pcf over the context's shadow map) */
+void zo_kat_pcf_batch(zo_ctx* c, const float* SB, float dxy, const uint32_t* in, uint32_t* out, uint32_t n)
+{
+    for (uint32_t i = 0; i < n; ++i) {
+        float f[3]; memcpy(f, in + (size_t)i * 3, sizeof f);
+        out[i] = zo_f2u(zo_pcf(c, SB, zo_v3make(f[0], f[1], f[2]), dxy));
+    }
+}
+/* case = cam, BaseColor, Metallic, Roughness, N, AO, P, 8 words of point-light mask -> Direct, Indirect, RefC, ShadowFactor (zo_shade).
+ * use_mask: the frame's point lights are exactly those whose bit is set (bit i of word i / 32, i < nPoint), in ascending order -
+ * what a tile's light list is to the lighting pass. */
+void zo_kat_shade_batch(zo_ctx* c, const float* SB, float dxy, int use_mask, const uint32_t* in, uint32_t* out, uint32_t n)
+{
+    zo_ctx* t = (zo_ctx*)malloc(sizeof *t);
+    if (!t) return;
+    *t = *c;                                   /* a shallow copy: only its view is rewritten */
+    const uint32_t nPoint = (uint32_t)c->view.LightsCount[1];
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t* a = in + (size_t)i * 23;
+        float f[15]; memcpy(f, a, sizeof f);
+        if (use_mask) {
+            uint32_t k = 0;
+            for (uint32_t li = 0; li < nPoint && li < 256u; ++li)
+                if ((a[15 + (li >> 5)] >> (li & 31u)) & 1u) t->view.PointLights[k++] = c->view.PointLights[li];
+            t->view.LightsCount[1] = (int32_t)k;
+        }
+        zo_lit r = zo_shade(t, SB, zo_v3make(f[0], f[1], f[2]), dxy, zo_v3make(f[3], f[4], f[5]), f[6], f[7], zo_v3make(f[8], f[9], f[10]),
+                            f[11], zo_v3make(f[12], f[13], f[14]));
+        uint32_t* o = out + (size_t)i * 10;
+        zo_put3(o, r.Direct); zo_put3(o + 3, r.Indirect); zo_put3(o + 6, r.RefC); o[9] = zo_f2u(r.ShadowFactor);
+    }
+    free(t);
 }

@@ -76,6 +76,22 @@ int   zo_kat_tex_sample(zo_ctx*, const uint8_t* rgba8, uint32_t w, uint32_t h, i
 int   zo_kat_tex_mip(zo_ctx*, const uint8_t* rgba8, uint32_t w, uint32_t h, int srgb, int level, uint8_t* out);
 int   zo_kat_cube_sample(zo_ctx*, const float dir[3], float lod, float out[3]);
 int   zo_kat_cube_mip(zo_ctx*, int level, uint8_t* out);
+/* batch forms: n cases of fixed-size word records (floats as their bits), one call per table; layouts in zo_oracle.c and in
+   tests/device_probe/probe.hip, which runs the product's copy of each function on the GPU */
+#define ZO_BATCH_DECL(name) void zo_kat_##name##_batch(const uint32_t* in, uint32_t* out, uint32_t n)
+ZO_BATCH_DECL(rsqrt); ZO_BATCH_DECL(sincos); ZO_BATCH_DECL(exp2); ZO_BATCH_DECL(log2); ZO_BATCH_DECL(pow); ZO_BATCH_DECL(pow5);
+ZO_BATCH_DECL(saturate); ZO_BATCH_DECL(clamp); ZO_BATCH_DECL(unorm); ZO_BATCH_DECL(f16_to_f32); ZO_BATCH_DECL(f32_to_f16);
+ZO_BATCH_DECL(unorm8); ZO_BATCH_DECL(div); ZO_BATCH_DECL(sqrt); ZO_BATCH_DECL(dot); ZO_BATCH_DECL(cross); ZO_BATCH_DECL(normalize);
+ZO_BATCH_DECL(tangent_normal); ZO_BATCH_DECL(mat4_point); ZO_BATCH_DECL(instance_record); ZO_BATCH_DECL(vs_position);
+ZO_BATCH_DECL(vs_normal); ZO_BATCH_DECL(classify); ZO_BATCH_DECL(project); ZO_BATCH_DECL(F_Schlick); ZO_BATCH_DECL(Fr_DisneyDiffuse);
+ZO_BATCH_DECL(V_SmithGGXCorrelated); ZO_BATCH_DECL(D_GGX);
+void  zo_kat_shadow_tap_batch(const uint32_t* in, uint32_t* out, uint32_t n, const float* map, uint32_t dim);
+/* the functions that read a context: its cubemap (zo_set_cubemap), its XkView (zo_set_frame) and a caller-supplied shadow map */
+int   zo_kat_set_shadowmap(zo_ctx*, const float* map, uint32_t dim);       /* dim must be the context's SD */
+void  zo_kat_cube_sample_batch(zo_ctx*, const uint32_t* in, uint32_t* out, uint32_t n);
+void  zo_kat_pcf_batch(zo_ctx*, const float* SB, float dxy, const uint32_t* in, uint32_t* out, uint32_t n);
+void  zo_kat_shade_batch(zo_ctx*, const float* SB, float dxy, int use_mask, const uint32_t* in, uint32_t* out, uint32_t n);
+int   zo_kat_sincos_intcast(float x, float out[2]);     /* zo_sincosf's earlier quadrant, ((int)k) & 3; 0 where that cast is undefined */
 
 #ifdef __cplusplus
 }

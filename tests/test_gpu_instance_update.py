@@ -138,6 +138,53 @@ def test_updates_through_both_forms_match_the_oracle(gpu_engine, oracle_lib):
     g.close()
 
 
+@pytest.mark.parametrize("flags", [0, abi.FLAG_NO_CONE_CULL], ids=["culled", "no_cone_cull"])
+def test_instances_turned_by_1e10_radians_match_the_oracle(gpu_engine, oracle_lib, flags):
+    """Angles far outside zr_sincos's domain (|k| >= 2^31: a cast of k to int is undefined there, and x86 and gfx950 gave different
+    quadrants) among ordinary instances, through zr_object_add (k_instance_prep) and through an update (k_instance_apply).  The sines
+    are finite values of no meaning, so each such instance is scaled back to about its usual size; they cover pixels, and the frame equals the
+    oracle's.
+
+    Such a record is no rotation, and the culls' bounding-sphere and normal-cone tests take R for one (zr_cull.hip): they are skipped for it
+    (zr_dev.h: is_rotation).  Before that the cone cull dropped meshlets that face the eye: 78 pixels of 36 864 differed with the culls on,
+    none with the cone cull off - hence the two flag sets."""
+    import ctypes as C
+    cfg = scenes.config3(64, 256, 144)
+    inst = cfg["objects"][0]["instances"]
+    L = oracle_lib.lib()
+    odd = {10: (1e10, 0.3, -0.2), 20: (0.1, -1e10, 0.0), 33: (0.0, 0.2, 5e9), 40: (3.4e9, 0.1, 0.2)}
+    for k, e in odd.items():
+        e = np.array(e, dtype=np.float32)
+        r9 = np.zeros(9, dtype=np.float32)
+        L.zo_kat_rotmat(e.ctypes.data_as(C.c_void_p), r9.ctypes.data_as(C.c_void_p))
+        assert np.isfinite(r9).all() and np.abs(r9).max() > 10.0                 # far from a rotation
+        inst["InstanceRotation"][k] = e
+        inst["InstancePScale"][k] = np.float32(2.0) * inst["InstancePScale"][k] / np.abs(r9).max()
+    start = inst.copy()
+    start["InstanceRotation"][40] = (0.0, 0.0, 0.0)
+    cfg["objects"][0]["instances"] = start
+    g = gpu_engine.Renderer(cfg["width"], cfg["height"], 256, flags=flags)
+    gpu_engine.load_scene(g, cfg)
+    g.render(); g.render()
+    g.object_set_instances(0, inst)                                              # instance 40 turns through k_instance_apply
+    g.render()
+    g.finish()
+    cfg["objects"][0]["instances"] = inst
+    o = oracle_lib.Oracle(cfg["width"], cfg["height"], 256)
+    oracle_lib.load_scene(o, cfg)
+    o.render()
+    diffs = compare_all(o, g)
+    assert all(v == 0 for v in diffs.values()), diffs
+    g.close()
+    hidden = inst.copy()
+    hidden["InstancePScale"][list(odd)] = 0.0
+    cfg["objects"][0]["instances"] = hidden
+    p = oracle_lib.Oracle(cfg["width"], cfg["height"], 256)
+    oracle_lib.load_scene(p, cfg)
+    p.render()
+    assert int((p.color() != o.color()).any(axis=2).sum()) > 20, "the turned instances cover no pixels: the case shows nothing"
+
+
 def _step_range(inst, i):
     """Frame i's host-form update: a contiguous range of moved instances (a different one every frame)."""
     rng = np.random.default_rng(100 + i)

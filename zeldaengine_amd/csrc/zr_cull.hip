@@ -111,7 +111,8 @@ __device__ __forceinline__ bool instance_test(const ZrPass& P, const ZrObject* _
     // record is loaded even when no other test needs it
     const ZrInstance I = ld_record(O->inst + inst_i);
     if ((O->flags & ZR_OBJ_HIDDEN) || zr_f2u(I._pad[0]) != 0u) vis = false;
-    if (vis && (P.frustum_ok | P.rect_cull | P.sphere_ok)) {
+    // (a record whose R is not a rotation - angles outside zr_sincos's domain - has no bounding sphere: zr_dev.h, is_rotation)
+    if (vis && (P.frustum_ok | P.rect_cull | P.sphere_ok) && (O->instanced == 0 || is_rotation(I.R))) {
         const bool instanced = O->instanced != 0;
         co = vs_position(zr3(O->mesh_center[0], O->mesh_center[1], O->mesh_center[2]), I, instanced);
         radius = O->mesh_radius * (instanced ? __builtin_fabsf(I.s) : 1.0f);
@@ -178,6 +179,7 @@ struct CullItem {
     uint32_t vcount, instanced, m, inst_i, w, tcount, tri_base;
     ZrInstance I;
     zf3 sph_c; float sph_r;       // the meshlet's bounding sphere after the instance transform (object space of PVM)
+    bool rot_ok;                  // ... which exists only where the instance's R is a rotation (zr_dev.h: is_rotation)
 };
 template <int MODE, bool WORKLIST>
 __device__ __forceinline__ bool cull_stage_a(const ZrPass& P, const ZrObject* __restrict__ objs, const uint32_t* __restrict__ work,
@@ -200,11 +202,12 @@ __device__ __forceinline__ bool cull_stage_a(const ZrPass& P, const ZrObject* __
     const uint32_t instanced = O->instanced != 0 ? 1u : 0u;
     it.instanced = instanced;
     it.sph_c = vs_position(zr3(bs.x, bs.y, bs.z), I, instanced != 0); it.sph_r = bs.w * (instanced ? __builtin_fabsf(I.s) : 1.0f);
+    it.rot_ok = !instanced || is_rotation(I.R);
     // the skydome is not a shadow caster (ZE:4709-4720); with N GPUs each draws every N-th instance (see k_cull_instances)
     if (MODE == ZR_MODE_SHADOW && ((O->flags & ZR_OBJ_SKY) || inst_i % P.inst_world != P.inst_rank)) alive = false;
     // hidden objects and instances: one flag test and one compare on the record just loaded, ahead of every other test
     if ((O->flags & ZR_OBJ_HIDDEN) || zr_f2u(I._pad[0]) != 0u) alive = false;
-    if (alive && (P.frustum_ok | P.cone_ok | P.rect_cull)) {
+    if (alive && it.rot_ok && (P.frustum_ok | P.cone_ok | P.rect_cull)) {
         const zf3 co = vs_position(zr3(bs.x, bs.y, bs.z), I, instanced != 0);
         const zf4 cw4 = zr_mat4_point(P.M, co);
         const zf3 cw = zr3(cw4.x, cw4.y, cw4.z);
@@ -282,7 +285,10 @@ __global__ __launch_bounds__(256) void k_cull_box(ZrPass P, const ZrObject* __re
             // of the two affine maps (instance: |s p| + |t|; PVM: |row| . |position| + |translation| + |result|)
             const float pm = __builtin_fmaxf(__builtin_fabsf(lo.x), __builtin_fabsf(hi.x)) + __builtin_fmaxf(__builtin_fabsf(lo.y), __builtin_fabsf(hi.y)) +
                              __builtin_fmaxf(__builtin_fabsf(lo.z), __builtin_fabsf(hi.z));
-            mag = it.instanced ? __builtin_fmaf(3.0f * __builtin_fabsf(it.I.s), pm, __builtin_fabsf(it.I.t[0]) + __builtin_fabsf(it.I.t[1]) + __builtin_fabsf(it.I.t[2])) : pm;
+            // (|R| <= 1 entry by entry for a rotation; any other matrix enters with its largest entry)
+            float rmx = 1.0f;
+            if (!it.rot_ok) for (int q = 0; q < 9; ++q) rmx = __builtin_fmaxf(rmx, __builtin_fabsf(it.I.R[q]));
+            mag = it.instanced ? __builtin_fmaf((3.0f * __builtin_fabsf(it.I.s)) * rmx, pm, __builtin_fabsf(it.I.t[0]) + __builtin_fabsf(it.I.t[1]) + __builtin_fabsf(it.I.t[2])) : pm;
             const float ew = U * (mag + 1.0f);
             const float ex = __builtin_fmaf(ew, rs_x, U * (mx + __builtin_fabsf(P.PVM[12]))), ey = __builtin_fmaf(ew, rs_y, U * (my + __builtin_fabsf(P.PVM[13])));
             const float ez = __builtin_fmaf(ew, rs_z, U * (mz + __builtin_fabsf(P.PVM[14]))), eW = __builtin_fmaf(ew, rs_w, U * (mw + __builtin_fabsf(P.PVM[15])));
@@ -323,7 +329,7 @@ __global__ __launch_bounds__(256) void k_cull_box(ZrPass P, const ZrObject* __re
                     int px1 = (int)__builtin_floorf(nxh + px_e - 0.5f), py1 = (int)__builtin_floorf(nyh + py_e - 0.5f);
                     px0 = max(px0, 0); py0 = max(py0, 0); px1 = min(px1, (int)P.W - 1); py1 = min(py1, (int)P.H - 1);
                     zm = __builtin_fmaxf(zl - z_e, 0.0f);
-                    if (P.sphere_ok) {      // the bounding sphere bounds the same vertices: the tighter of the two on every side
+                    if (P.sphere_ok && it.rot_ok) {      // the bounding sphere bounds the same vertices: the tighter of the two on every side
                         int sx0, sy0, sx1, sy1; float dn;
                         if (sphere_bounds(P, it.sph_c, it.sph_r, sx0, sy0, sx1, sy1, dn)) {
                             px0 = max(px0, sx0); py0 = max(py0, sy0); px1 = min(px1, sx1); py1 = min(py1, sy1);

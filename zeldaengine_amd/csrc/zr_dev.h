@@ -128,6 +128,18 @@ __device__ __forceinline__ ZrInstance instance_record(const XkInstanceData& d)
     return I;
 }
 
+// The culls' bounding-sphere and normal-cone tests take an instance's R for a rotation (the sphere's radius is radius * |s|, the cone's
+// axis is turned by R).  R is a product of matrices built from zr_sincos: inside its domain a rotation to 1e-6, outside it (zr_math.h)
+// any finite matrix or NaN.  Columns orthonormal within 1e-4 - well inside the tests' margins (the radius is inflated by 1e-3, the cone
+// widened by 0.02) - else the record gets no sphere or cone test; the box test is affine in R and holds for any matrix.
+__device__ __forceinline__ bool is_rotation(const float* R)
+{
+    const zf3 a = zr3(R[0], R[1], R[2]), b = zr3(R[3], R[4], R[5]), c = zr3(R[6], R[7], R[8]);
+    const float T = 1e-4f;
+    return __builtin_fabsf(zr_dot(a, a) - 1.0f) <= T && __builtin_fabsf(zr_dot(b, b) - 1.0f) <= T && __builtin_fabsf(zr_dot(c, c) - 1.0f) <= T &&
+           __builtin_fabsf(zr_dot(a, b)) <= T && __builtin_fabsf(zr_dot(a, c)) <= T && __builtin_fabsf(zr_dot(b, c)) <= T;     // NaN: false
+}
+
 // Base.vert:26 / BaseInstanced.vert:70 / Shadowmap*.vert: object-space position fed to PVM
 __device__ __forceinline__ zf3 vs_position(zf3 p, const ZrInstance& I, bool instanced)
 {
@@ -167,14 +179,18 @@ __device__ __forceinline__ int classify(uint32_t f0, uint32_t f1, uint32_t f2)
     return ((f0 | f1 | f2) & 128u) ? 2 : 1;
 }
 
+// float -> int of a snapped coordinate.  A corner that classify() lets through has |x|, |y| <= 4 w, but for a denormal w the reciprocal
+// below is +inf and the products are +-inf or NaN; a cast of those is undefined (x86 and gfx950 give different values).  Clamping to the
+// ints a float can hold defines it: NaN -> -2^31 (zr_math.h: max(NaN, a) = a), +-inf and anything beyond -> -2^31 / 2^31 - 128.
+__device__ __forceinline__ int snap_to_int(float f) { return (int)__builtin_fminf(__builtin_fmaxf(f, -2147483648.0f), 2147483520.0f); }
 __device__ __forceinline__ SV project(zf4 c, float hw, float hh)
 {
     SV s;
     s.rw = 1.0f / c.w;                     // one IEEE reciprocal, then multiplies (the perspective divide)
     const float nx = c.x * s.rw, ny = c.y * s.rw;
     const float xs = __builtin_fmaf(nx, hw, hw), ys = __builtin_fmaf(ny, hh, hh);
-    s.X = (int)__builtin_floorf(__builtin_fmaf(xs, 256.0f, 0.5f));
-    s.Y = (int)__builtin_floorf(__builtin_fmaf(ys, 256.0f, 0.5f));
+    s.X = snap_to_int(__builtin_floorf(__builtin_fmaf(xs, 256.0f, 0.5f)));
+    s.Y = snap_to_int(__builtin_floorf(__builtin_fmaf(ys, 256.0f, 0.5f)));
     s.z = c.z * s.rw;
     return s;
 }

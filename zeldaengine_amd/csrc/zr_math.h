@@ -67,6 +67,10 @@ ZR_HD zf3 zr_tangent_space_normal(zf3 texN)
     const zf3 n = zr_normalize(texN);
     return zr_normalize(zr3(__builtin_fmaf(2.0f, n.x, -1.0f), __builtin_fmaf(2.0f, n.y, -1.0f), __builtin_fmaf(2.0f, n.z, -1.0f)));
 }
+// min / max (clamp, saturate, max(x, 0), the UNORM stores): __builtin_fminf / __builtin_fmaxf compile to v_min_f32 / v_max_f32, i.e. IEEE
+// 754-2019 minimumNumber / maximumNumber - a NaN of either kind (signalling too) yields the other operand, max(-0, +0) = +0 and
+// min(-0, +0) = -0 in either order.  That is the contract; the CPU oracle spells it out (zo_fminf / zo_fmaxf), because C's library
+// functions differ on both points.  So saturate(NaN) = 0 and clamp(NaN, a, b) = a.
 ZR_HD float zr_saturate(float t) { return __builtin_fminf(__builtin_fmaxf(t, 0.0f), 1.0f); }   // SH/Common.glsl:23
 ZR_HD float zr_clamp(float t, float a, float b) { return __builtin_fminf(__builtin_fmaxf(t, a), b); }
 
@@ -103,7 +107,11 @@ ZR_HD void zr_mat3_mul(const float* A, const float* B, float* C)
 
 // ---- transcendental kernels: Cody-Waite reduction + short minimax polynomials -----------------------------
 
-// sin/cos for the per-instance rotation (MakeRotMatrix, SH/Common.glsl:60-87); |x| up to ~1e5 rad
+// sin/cos for the per-instance rotation (MakeRotMatrix, SH/Common.glsl:60-87).  Domain: |x| up to ~1e5 rad (3e-7 absolute to 700, the
+// three-step reduction's error grows with |k| beyond; DESIGN.md section 4 has the table).  Outside it the result is still ONE value
+// per input on every target: the quadrant k mod 4 is taken in float, k - 4 floor(k / 4), which is exact for every finite k (a cast
+// of k to int is undefined from |k| = 2^31, x ~ 3.37e9, and x86 and gfx950 lower it differently); k at or above 2^25 is a multiple
+// of 4, so huge angles get quadrant 0 and finite values of no meaning.  x = +-inf or NaN: quadrant 0, and both results are NaN.
 ZR_HD void zr_sincos(float x, float& s, float& c)
 {
     float k = __builtin_rintf(x * 0.636619772367581343f);
@@ -117,7 +125,8 @@ ZR_HD void zr_sincos(float x, float& s, float& c)
     float pc = __builtin_fmaf(r2, 2.443315711809948e-5f, -1.388731625493765e-3f);
     pc = __builtin_fmaf(r2, pc, 4.166664568298827e-2f);
     float cs = __builtin_fmaf(r2 * r2, pc, __builtin_fmaf(r2, -0.5f, 1.0f));
-    int q = ((int)k) & 3;
+    const float kq = k - 4.0f * __builtin_floorf(k * 0.25f);
+    const int q = (kq > 0.0f) ? (int)kq : 0;
     float so = (q & 1) ? cs : sn;
     float co = (q & 1) ? sn : cs;
     if (q == 1 || q == 2) co = -co;

@@ -188,7 +188,9 @@ __device__ __forceinline__ void shade_surface(const ZrLightParams& L, const XkVi
         const zf3 lp = zr3(Lt->Position[0], Lt->Position[1], Lt->Position[2]);
         // A light whose radiance factor is exactly 0 adds fma(0, bxdf, Direct) = Direct: skip its BxDF.  That is the
         // case beyond a point light's radius (attenuation 1 - clamp(d, 0, r) / r = 0) and for N.L <= 0.  The skip
-        // needs finite colour * intensity (0 * finite = 0); the test is wave-uniform per light.
+        // needs finite colour * intensity (0 * finite = 0); the test is wave-uniform per light.  Where the BxDF is NaN or
+        // infinite (D_GGX at roughness 0 with N.H = 1), or the attenuation is NaN (falloff 0) while N.L is 0, the shader's
+        // literal sum would be NaN; the contract is the skip, and the CPU oracle states the same (row 8 of its CONTRACT.md).
         const bool lfinite = __builtin_fabsf(Lt->Color[0]) <= 3.402823466e38f && __builtin_fabsf(Lt->Color[1]) <= 3.402823466e38f &&
                              __builtin_fabsf(Lt->Color[2]) <= 3.402823466e38f && __builtin_fabsf(Lt->Color[3]) <= 3.402823466e38f;
         float att = 1.0f;
