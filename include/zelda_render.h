@@ -301,7 +301,17 @@ int  zr_set_shading(zr_ctx* ctx, uint32_t mode);
  * zr_get_stats, zr_read_gbuffer, the identity queries and zr_copy_frame_async answer as on a drawn frame; ZR_PASS_CULL_CAMERA,
  * ZR_PASS_GBUFFER, ZR_PASS_HIZ, ZR_PASS_GBUFFER2 and ZR_PASS_RESOLVE read exactly 0.  Lights, debug view, background and cubemap are
  * inputs of the lighting pass and end nothing.  Never kept whole: a context that draws a skydome (its round 2 is still kept), and
- * whatever never keeps round 2. */
+ * whatever never keeps round 2.
+ * The lighting pass of a frame that keeps BOTH its camera pass and its shadow map keeps, per pixel, what the point lights do not feed:
+ * the shadow factor (the 25 PCF taps), the directional lights' share of the direct term and the reflection.  The first such frame
+ * computes them as ever and stores them as exact fp32 in a plane of 32 bytes per pixel, made then (no room for it: the context never
+ * keeps, and that is no error); every later one loads them and computes only the point lights, the indirect term and the compose - the
+ * frame is the same bit for bit, in every debug view.  The plane stands while that GBuffer and that map stand and, compared byte for
+ * byte, the shadow matrix, the camera position, the directional lights in use and their count, the cubemap (zr_set_cubemap and a
+ * world's override replace it) and its mip count do; anything else - the point lights, the debug view, the background, the time -
+ * ends nothing, except that a frame whose empty-pixel shortcut is off (debug view 6) needs a plane filled by such a frame.  When it no
+ * longer stands, the next frame that rests fills it again.  Deferred shading only; never with ZR_FLAG_NO_LIST_REUSE, never on a context
+ * whose map is never kept.  zr_get_light_keep tells what the last frame did. */
 int  zr_render(zr_ctx* ctx);
 /* The same frame in three stages (zr_render = all three, in this order), so that a multi-GPU host can place its
  * collectives between them: shadow pass | deferred-scene pass (cull, raster, GBuffer write) | deferred-lighting pass. */
@@ -323,6 +333,17 @@ int  zr_get_frame_periods(zr_ctx* ctx, uint32_t n, float* ms);     /* GPU ms bet
 int  zr_set_timing_interval(zr_ctx* ctx, uint32_t interval);  /* pass events on every interval-th frame (default 1, 0 = never) */
 /* bytes = sizeof(zr_stats) of the caller's header: the library writes min(bytes, its own size), so an older host is never overrun. */
 int  zr_get_stats(zr_ctx* ctx, zr_stats* out, size_t bytes);
+/* What the lighting pass of the frame enqueued last did with the plane of standing terms (see zr_render), and how many frames of the
+ * context did each so far.  bytes = sizeof(zr_light_keep) of the caller's header, as with zr_get_stats. */
+#define ZR_LIGHT_PLANE_IGNORED 0u   /* computed everything, stored nothing: a drawn frame, forward shading, a context that never keeps */
+#define ZR_LIGHT_PLANE_FILLED  1u   /* computed everything and stored the standing terms */
+#define ZR_LIGHT_PLANE_READ    2u   /* loaded the standing terms */
+typedef struct zr_light_keep {
+    uint32_t last, _pad;         /* ZR_LIGHT_PLANE_* of the last frame */
+    uint64_t ignored, filled, read;
+    uint64_t plane_bytes;        /* device memory the plane takes (0: not made) */
+} zr_light_keep;
+int  zr_get_light_keep(zr_ctx* ctx, zr_light_keep* out, size_t bytes);
 
 /* --- read-back (there is no swapchain; replaces vkQueuePresentKHR ZE:2030) --- */
 int  zr_read_color(zr_ctx* ctx, uint8_t* rgba8, size_t bytes);         /* W*H*4 row-major, top-left origin */

@@ -46,6 +46,7 @@ SHORT = {"k_raster_chunks<0, false>": "k_raster<GBUFFER>", "k_raster_chunks<0, t
          "k_raster_chunks<0, false, false>": "k_raster<GBUFFER>", "k_raster_chunks<0, true, false>": "k_raster<GBUFFER,HiZ>",
          "k_tile_slow<0, false>": "k_tile_slow<GBUFFER>", "k_tile_slow<1, true>": "k_tile_slow<SHADOW>",
          "k_tile<0, false>": "k_tile<0>", "k_tile<0, true>": "k_tile<0>",      # (the frame's last round also draws the slow triangles)
+         "k_tile<false>": "k_tile<0>", "k_tile<true>": "k_tile<0>", "k_shadow_slow": "k_tile_slow<SHADOW>",      # (the same two since the rasterisers' unused arms went: <LAST>; the shadow pass's clipper)
          "k_geom<false, false>": "k_geom<false>", "k_geom<true, false>": "k_geom<true>",      # (<.., true>: the count-only run of a frame without a bucket plan)
          "k_geom<false, true>": "k_geom<false,count>", "k_geom<true, true>": "k_geom<true,count>",
          "k_cull_box<0, false>": "k_cull_box<GBUFFER>", "k_cull_box<1, false>": "k_cull_box<SHADOW>",

@@ -266,7 +266,7 @@ extern "C" int zr_set_stream(zr_ctx* c, void* s)
         hipStream_t ns = s ? (hipStream_t)s : c->own_stream;
         // frames in flight are ordered by their place on the host's stream (frame_begin relies on it): a change of stream drains them
         if (ns != c->stream && c->rendered) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, zr_sync_all(c)); }
-        if (ns != c->stream) zr_casters_changed(c);      // (the kept map's two copies are ordered by their place on the host's stream too)
+        if (ns != c->stream) { zr_casters_changed(c); zr_history_forgotten(c, ZR_HIST_LIGHT_PLANE); }      // (the kept map's two copies, and the lighting pass's plane, are ordered by their place on the host's stream too)
         c->stream = ns;
         return ZR_OK;
     });

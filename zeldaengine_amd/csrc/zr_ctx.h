@@ -338,6 +338,17 @@ struct zr_ctx {
     } delta;
 
     ZrOwn cube_mem; CubeDesc cube = {}; uint32_t cube_dim = 0, cube_levels = 0;
+    uint64_t cube_gen = 0;               // of the cubemap's contents: bumped whenever they are replaced (zr_set_cubemap, which a world's override goes through)
+    // The lighting pass's plane of standing terms (zr_lighting_host.cpp; ZrFramePlan::light_keep): 32 bytes per pixel, made at the first
+    // fill through `own` (alloc_failed: it could not be, and the context never keeps).  ONE plane: every lighting pass of the context is
+    // enqueued on the host's stream, in frame order, so a fill is through before the next frame reads, and a read before the next fill.
+    // now / key: the standing uniforms of the frame being enqueued / of the fill (ZrFrameFacts::light_uniforms_same).  last, count[]:
+    // what the lighting pass enqueued last did with the plane (ZR_LIGHT_PLANE_*), and how often each happened (zr_get_light_keep).
+    struct LightKey {
+        float SB[16], cam[3]; uint32_t SD, n_dir, max_mips, cube_dim, cube_levels, debug_skip;
+        XkLight dir[XK_MAX_DIRECTIONAL_LIGHTS_NUM];
+    };
+    struct LightKeep { float4* plane = nullptr; bool alloc_failed = false; LightKey now = {}, key = {}; uint32_t last = 0; uint64_t count[3] = { 0, 0, 0 }; } lk;
     float lut[256]; float* d_lut = nullptr;
     float* d_unorm_lut = nullptr;        // [0..255] = c / 255, [256..1279] = c / 1023 (IEEE quotients, computed on the host)
 
@@ -387,7 +398,8 @@ static inline void zr_camera_changed(zr_ctx* c) { c->camera_epoch++; }
 static inline void zr_surface_changed(zr_ctx* c) { c->surface_epoch++; }
 // What the frames so far left on the device says nothing about the frames to come: the passes' work lists, the record buckets' plan, the
 // visibility marks, the shadow pass's occlusion flags (ZrFrameCarry) - the next frame rebuilds, counts first, draws in one round.
-enum : uint32_t { ZR_HIST_SHADOW_LIST = 1u, ZR_HIST_CAMERA_LIST = 2u, ZR_HIST_LISTS = 3u, ZR_HIST_PLAN = 4u, ZR_HIST_VISIBILITY = 8u, ZR_HIST_SHADOW_FLAGS = 16u };
+enum : uint32_t { ZR_HIST_SHADOW_LIST = 1u, ZR_HIST_CAMERA_LIST = 2u, ZR_HIST_LISTS = 3u, ZR_HIST_PLAN = 4u, ZR_HIST_VISIBILITY = 8u, ZR_HIST_SHADOW_FLAGS = 16u,
+                  ZR_HIST_LIGHT_PLANE = 32u };      // ... and the lighting pass's plane: the next resting frame fills it
 static inline void zr_history_forgotten(zr_ctx* c, uint32_t what)
 {
     ZrFrameCarry& k = c->carry;
@@ -396,6 +408,7 @@ static inline void zr_history_forgotten(zr_ctx* c, uint32_t what)
     if (what & ZR_HIST_PLAN) k.plan_valid = false;
     if (what & ZR_HIST_VISIBILITY) k.vis_history = false;
     if (what & ZR_HIST_SHADOW_FLAGS) k.sflag_history = false;
+    if (what & ZR_HIST_LIGHT_PLANE) k.light_valid = false;
 }
 #define HIPCHK(c, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) \
     return zr_fail((c), ZR_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); } while (0)
@@ -437,9 +450,24 @@ hipError_t zr_sync_all(zr_ctx* c);     // every stream the library enqueues on
 struct ZrTilePartition { std::vector<uint32_t> owned, map; uint32_t slots_per_rank = 0; };
 ZrTilePartition zr_partition(uint32_t tiles_x, uint32_t tiles_y, uint32_t world, uint32_t rank);
 // zr_frame_host.cpp
+static inline hipStream_t lane_stream(const zr_ctx* c, ZrLane lane) { return lane == ZR_LANE_CAM ? c->cam_s : c->stream; }
+// A timed frame's events `which` on s, in order (an untimed frame: nothing).  A kept pass records its events all the same - no elapsed-time
+// call meets an unrecorded one - on the stream that lights the frame, and its sample counts as 0 (zr_get_pass_times_avg).
+static inline int timed_events(zr_ctx* c, hipStream_t s, std::initializer_list<int> which)
+{
+    if (zr_ctx::TimedFrame* const T = c->timed_frame())
+        for (int e : which) HIPCHK(c, hipEventRecord(T->ev[e], s));
+    return ZR_OK;
+}
+#define TIMED(c, s, ...) do { if (int _rc = timed_events((c), (s), { __VA_ARGS__ })) return _rc; } while (0)
 // The current shadow map: during a drawn shadow pass the one being drawn, else the one the last drawn pass left (zr_ctx::smap).
 static inline float* shadow_buf(zr_ctx* c) { return c->d_shadow_ext ? c->d_shadow_ext : c->fc[c->smap].shadow; }
 int set_winner_planes(zr_ctx* c, bool forward, bool id_capture, const char* what);      // zr_set_shading, zr_set_id_capture
+// zr_lighting_host.cpp: the lighting stage
+void zr_light_facts(zr_ctx* c, ZrFrameFacts* f);       // frame_begin: what the plan reads about the plane
+bool zr_light_plane_make(zr_ctx* c);                   // frame_begin, a frame planned to fill: the plane exists (false: it cannot, ever)
+int empty_pixel_pass(zr_ctx* c);
+int lighting_pass(zr_ctx* c);
 // zr_readback.cpp
 int ids_prepare(zr_ctx* c);            // frame_begin of a captured frame: the census's draw table
 // zr_scene.cpp, also used by zr_world.cpp

@@ -358,9 +358,18 @@ __device__ __forceinline__ bool hiz_occluded(const ZrHiz& Z, uint2 pr, float zmi
 #ifndef ZR_LIGHT_WAVES
 #define ZR_LIGHT_WAVES 6             // waves per SIMD k_lighting is compiled for (see the note at the kernel)
 #endif
-#ifndef ZR_PIXELS_PER_THREAD
-#define ZR_PIXELS_PER_THREAD 1       // of k_resolve_gbuffer and k_lighting: 1, 2 or 4 (a tile is 1 024 pixels; workgroups per tile follow)
+// ... and the same two for the variant that reads a pixel's standing terms from the kept plane (k_lighting, ZR_LIGHT_KEPT): it holds no PCF
+// rows and no cubemap texels, so it fits more waves (DESIGN.md section 7 has the variants tried)
+#ifndef ZR_LIGHT_KEPT_TB
+#define ZR_LIGHT_KEPT_TB 512
 #endif
+#ifndef ZR_LIGHT_KEPT_WAVES
+#define ZR_LIGHT_KEPT_WAVES 8
+#endif
+#ifndef ZR_PIXELS_PER_THREAD
+#define ZR_PIXELS_PER_THREAD 1     // of k_resolve_gbuffer and k_lighting: 1, 2 or 4 (a tile is 1 024 pixels; workgroups per tile follow)
+#endif
+static_assert(TILE_PIX / ZR_PIXELS_PER_THREAD >= ZR_LIGHT_KEPT_TB, "a tile's threads must fill at least one workgroup");
 static_assert(TILE_PIX / ZR_PIXELS_PER_THREAD >= ZR_LIGHT_TB && TILE_PIX / ZR_PIXELS_PER_THREAD >= 256, "a tile's threads must fill at least one workgroup");
 #ifndef ZR_RESOLVE_TB
 #define ZR_RESOLVE_TB 256

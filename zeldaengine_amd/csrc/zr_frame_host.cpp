@@ -247,18 +247,6 @@ static bool build_pass(const zr_ctx* c, const XkUniformBufferMVP& u, int mode, Z
 // What a frame does is decided once, by zr_frame_plan() (zr_frame_plan.h), when the frame begins; everything below does what the plan says
 // on the stream the plan names, and tells zr_frame_carry() when a stage is enqueued.
 
-static inline hipStream_t lane_stream(const zr_ctx* c, ZrLane lane) { return lane == ZR_LANE_CAM ? c->cam_s : c->stream; }
-
-// A timed frame's events `which` on s, in order (an untimed frame: nothing).  A kept pass records its events all the same - no elapsed-time
-// call meets an unrecorded one - on the stream that lights the frame, and its sample counts as 0 (zr_get_pass_times_avg).
-static int timed_events(zr_ctx* c, hipStream_t s, std::initializer_list<int> which)
-{
-    if (zr_ctx::TimedFrame* const T = c->timed_frame())
-        for (int e : which) HIPCHK(c, hipEventRecord(T->ev[e], s));
-    return ZR_OK;
-}
-#define TIMED(c, s, ...) do { if (int _rc = timed_events((c), (s), { __VA_ARGS__ })) return _rc; } while (0)
-
 // count -> scan -> fill of the shadow pass's meshlet bins, from the cull's rects.  Z.phase 1 (occlusion culling): only the
 // meshlet-instances flagged last frame are binned.
 static void shadow_bin(zr_ctx* c, const ZrPass& P, const ZrHiz& Z, hipStream_t s)
@@ -338,7 +326,10 @@ static int frame_begin(zr_ctx* c, ZrEntry entry)
     for (int i = 0; i < 2; ++i) { f.copy_gen[i] = c->fc[i].g_gen; f.copy_overlay[i] = c->fc[i].overlay_dirty; f.copy_ids_wait[i] = c->fc[i].ids_wait; }
     f.shadow_is_map = memcmp(&c->smap_key, &c->pass[0], sizeof(ZrPass)) == 0;
     f.camera_is_prev = memcmp(&c->cam_prev_key, &c->pass[1], sizeof(ZrPass)) == 0;
-    const ZrFramePlan& p = c->plan = zr_frame_plan(f, c->carry);
+    zr_light_facts(c, &f);
+    c->plan = zr_frame_plan(f, c->carry);
+    if (c->plan.light_fill && !zr_light_plane_make(c)) { f.light_plane_ok = false; c->plan = zr_frame_plan(f, c->carry); }      // (no room for it: plan again, without)
+    const ZrFramePlan& p = c->plan;
     c->carry = zr_frame_carry(c->carry, f, p, ZR_STAGE_HEAD);
     if (p.shadow_list_rebuild) c->list_key[0] = c->pass[0];
     if (p.camera_list_rebuild) c->list_key[1] = c->pass[1];
@@ -513,37 +504,6 @@ extern "C" int zr_stream_wait_shadow(zr_ctx* c, void* hip_stream)
     });
 }
 
-static void light_params(const zr_ctx* c, ZrLightParams* Lp)
-{
-    ZrLightParams& L = *Lp; memset(&L, 0, sizeof L);
-    static const float Bias[16] = { 0.5f, 0, 0, 0, 0, 0.5f, 0, 0, 0, 0, 1, 0, 0.5f, 0.5f, 0, 1 };
-    zr_mat4_mul(Bias, c->view.ShadowmapSpace, L.SB);
-    L.W = c->W; L.H = c->H; L.SD = c->SD; L.tiles_x = c->tiles_x; L.debug_view = c->debug_view;
-    L.cube_dim = c->cube_dim; L.cube_levels = c->cube_levels; L.tile_world = c->cfg.tile_world;
-    L.packed_out = (c->cfg.tile_world > 1 || (c->cfg.flags & ZR_FLAG_PACKED_TILES)) ? 1u : 0u;
-    L.debug_skip = c->env_skip_light;
-    L.bg_enabled = (c->bg_set && c->bg_enabled) ? 1u : 0u;
-    L.has_overlay = c->fc[c->fcur].overlay_dirty ? 1u : 0u;     // set by this frame's gbuffer pass
-    { const int32_t np = c->view.LightsCount[1]; L.light_list = (np >= c->env_light_list_min && np <= XK_MAX_POINT_LIGHTS_NUM) ? 1u : 0u; }
-    L.bg.data = c->d_bg; L.bg.w = c->bg_w; L.bg.h = c->bg_h; L.bg.levels = c->bg_levels; L.bg._pad = 0;
-}
-
-// The lighting shader's colour for a pixel that still holds every target's clear value: one launch of the lighting kernel over a
-// one-pixel GBuffer.  It needs the finished shadow map (PCF at world position 0) and the frame's uniforms, nothing else.  View 6
-// (the quad's interpolated vertex colour) depends on the pixel position, so it goes without.
-static int empty_pixel_pass(zr_ctx* c)
-{
-    c->empty_ready = false;
-    if (c->plan.one_pixel == ZR_LANE_NONE || c->debug_view == 6u || c->env_no_empty_px) return ZR_OK;
-    ZrLightParams L; light_params(c, &L);
-    L.W = 1; L.H = 1; L.tiles_x = 1; L.packed_out = 0; L.bg_enabled = 0;
-    zr_launch_lighting(L, c->fc[c->fcur].view, c->d_sowned, 1, c->Gclear, shadow_buf(c), c->cube, c->d_lut, c->d_unorm_lut, c->fc[c->fcur].empty_rgba,
-                       lane_stream(c, c->plan.one_pixel));
-    HIPCHK(c, hipGetLastError());
-    c->empty_ready = true;
-    return ZR_OK;
-}
-
 // Both geometry passes of a frame.  Two lanes (zr_frame_plan): the camera pipeline on cam_s; the shadow pipeline on the host's stream,
 // where the lighting pass will follow.  The next frame's camera pipeline starts as soon as this one's is through, next to this frame's
 // lighting; its shadow pipeline follows the lighting.  The shadow pipeline needs nothing of the head's - its matrices are kernel
@@ -591,35 +551,6 @@ static int deferred_resolve(zr_ctx* c)
     TIMED(c, s, zr_ctx::EV_RESOLVE);
     c->cov_block = tally; c->fc[c->fcur].g_gen = c->plan.g_gen;
     HIPCHK(c, hipGetLastError());
-    return ZR_OK;
-}
-
-static int lighting_pass(zr_ctx* c)
-{
-    const hipStream_t s = lane_stream(c, c->plan.lighting);
-    ZrLightParams L; light_params(c, &L);
-    const FrameCopy& F = c->fc[c->fcur];
-    L.empty_rgba = c->empty_ready ? F.empty_rgba : nullptr;
-    // The next DRAWN shadow pass follows on this stream and rasterises into the OTHER copy of the map, which nothing reads or
-    // writes while this pass runs: clear it here - once; a run of frames that keep their map finds it clear and writes nothing.
-    FrameCopy& next = c->fc[c->smap ^ 1];
-    if (c->n_owned && !c->d_shadow_ext && !next.shadow_cleared) { L.clear_next = (uint32_t*)next.shadow; L.clear_n = c->SD * c->SD; next.shadow_cleared = true; }
-    uint32_t* const frame_out = L.packed_out ? (c->d_tiles_ext ? c->d_tiles_ext : c->d_tiles) : c->d_color;
-    if (c->shading == ZR_SHADING_FORWARD) {
-        // Base.frag over the winners the resolve recorded, with this frame's camera block (frame_begin built it; the overlay fields play no part)
-        if (L.clear_next) { zr_launch_fill32(L.clear_next, 0x3F800000u, L.clear_n, s); L.clear_next = nullptr; }
-        zr_launch_forward(c->pass[1], L, F.view, c->d_objs, c->d_owned, c->n_owned, F.G, shadow_buf(c), c->cube, c->d_lut, c->d_unorm_lut, frame_out, s);
-    } else {
-        zr_launch_lighting(L, F.view, c->d_owned, c->n_owned, F.G, shadow_buf(c), c->cube, c->d_lut, c->d_unorm_lut, frame_out, s);
-        if (c->debug_view == 9u)        // GBufferVis mosaic over the lit frame (needs the whole GBuffer: single-rank contexts only)
-            zr_launch_gbuffer_vis(L, F.view, F.G, shadow_buf(c), c->cube, c->d_lut, c->d_color, s);
-    }
-    TIMED(c, s, zr_ctx::EV_LIGHTING);
-    HIPCHK(c, hipEventRecord(c->ev_end[c->frame_no % zr_ctx::END_RING], s));      // this frame's GBuffer / shadow map / uniforms copies are free again
-    HIPCHK(c, hipGetLastError());
-    if (c->timing_now) c->sample_no++;
-    c->rendered = true; c->frame_no++; c->stage = 0;
-    c->ids_frame = c->ids_this; c->ids.gen = c->scene_gen;
     return ZR_OK;
 }
 

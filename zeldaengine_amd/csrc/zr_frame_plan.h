@@ -38,7 +38,7 @@ enum ZrEvCam : uint8_t {
     ZR_EVCAM_BEHIND_ONE_PIXEL,      // a kept frame's head on the lane: behind upload and one-pixel launch
     ZR_EVCAM_LANE_END               // behind the whole camera pipeline, k_plan included
 };
-enum ZrStage : uint8_t { ZR_STAGE_HEAD, ZR_STAGE_SHADOW, ZR_STAGE_CAMERA };      // the stages that leave something in the carry
+enum ZrStage : uint8_t { ZR_STAGE_HEAD, ZR_STAGE_SHADOW, ZR_STAGE_CAMERA, ZR_STAGE_LIGHTING };      // the stages that leave something in the carry
 
 // Everything the decision reads, as values (frame_begin gathers them once the frame's two pass blocks are built).
 struct ZrFrameFacts {
@@ -62,6 +62,12 @@ struct ZrFrameFacts {
     // overlay plane, a census enqueued against it that its next writer waits for
     uint64_t copy_gen[2] = { 0, 0 };
     bool copy_overlay[2] = { false, false }, copy_ids_wait[2] = { false, false };
+    // The lighting pass's plane of standing terms (ZrFramePlan::light_keep).  light_plane_ok: the context can have one (false: it could
+    // not be allocated - and every context that never asked).  light_uniforms_same: the standing uniforms, compared by the caller byte
+    // for byte, are those of the fill.  cube_gen: the cubemap's contents (bumped whenever they are replaced).  light_empty_px: the frame's
+    // lighting pass takes the empty-pixel shortcut (off: debug view 6, a diagnostic switch), and those pixels touch no plane.
+    bool light_plane_ok = false, light_uniforms_same = false, light_empty_px = true;
+    uint64_t cube_gen = 0;
 };
 
 // What the frames enqueued so far left behind, and nothing else.  (The ZrPass keys that go with it - smap_key, cam_prev_key, list_key[] -
@@ -82,6 +88,10 @@ struct ZrFrameCarry {
     // The last camera pipeline: the lane it ran on (NONE: there was none yet), and whether its ev_cam sat AHEAD of its k_plan - then a
     // camera pipeline on the host's stream waits for the lane's end first.
     ZrLane gbuf_lane = ZR_LANE_NONE; bool plan_behind_cam = false;
+    // The lighting pass's plane: it holds the standing terms of a fill that was enqueued completely, and what that fill read - the run of
+    // equal camera-pass inputs its GBuffer copy belonged to, the drawing frame of its shadow map, the cubemap's generation (its uniforms
+    // stay beside the carry, like the pass blocks) - and whether it wrote every pixel (light_all_px: the shortcut was off).
+    bool light_valid = false, light_all_px = false; uint64_t light_g_gen = 0, light_smap_frame = 0, light_cube_gen = 0;
 };
 
 // What this frame does.  Made once (frame_begin), read by every stage, changed by none.
@@ -104,6 +114,9 @@ struct ZrFramePlan {
     bool wait_end2 = false, wait_end1 = false, wait_lane_end = false, wait_ids = false, ids_taken = false;
     ZrEvCam ev_cam = ZR_EVCAM_NONE; bool host_waits_ev_cam = false;
     bool ev_join = false;                  // recorded behind the shadow stage (zr_stream_wait_shadow)
+    // lighting pass: the standing terms of every pixel are read from the plane / computed as ever and stored into it (neither: the pass
+    // ignores the plane)
+    bool light_keep = false, light_fill = false;
 };
 
 static inline ZrFramePlan zr_frame_plan(const ZrFrameFacts& f, const ZrFrameCarry& k)
@@ -215,6 +228,21 @@ static inline ZrFramePlan zr_frame_plan(const ZrFrameFacts& f, const ZrFrameCarr
     p.host_waits_ev_cam = p.ev_cam != ZR_EVCAM_NONE;      // (wherever it is recorded, it is recorded on the lane)
     // ev_join (zr_stream_wait_shadow: a host that puts a collective behind the shadow pass): not in zr_render's own two-lane frames
     p.ev_join = !(lanes && render);
+
+    // The lighting pass keeps, per pixel, what the moving point lights do not feed: ShadowFactor, Direct over the directional lights, RefC.
+    // Their inputs are the pixel's GBuffer values, the shadow map, and a few hundred bytes of uniforms plus the cubemap.  A frame that keeps
+    // its camera pass lights a GBuffer copy that is, bit for bit, every other copy of the same run (g_gen); a frame that keeps its map
+    // lights from the map of one drawing frame (smap_frame; never a caller-owned or partitioned map: those are drawn every frame).  When
+    // the plane was filled from that run, that map, these uniforms and this cubemap, the pass reads it; when the frame rests but the plane
+    // does not match, the pass fills it - a resting frame by definition, so the moving-camera and moving-light loops never pay the stores.
+    // The plane holds what a fill wrote: with the empty-pixel shortcut on, not the pixels that took it, and those are the same pixels on
+    // every frame of the run - but a frame whose shortcut is off reads every pixel, and needs a fill that wrote them all.  All lighting
+    // passes of a context run in order on the host's stream (p.lighting), so one plane serves the frames in flight.  Deferred shading
+    // only; never with ZR_FLAG_NO_LIST_REUSE, as above.
+    const bool light_rest = f.light_plane_ok && !(f.flags & ZRP_NO_LIST_REUSE) && f.shading != ZRP_SHADING_FORWARD && p.camera_keep && p.shadow_keep;
+    const bool light_match = k.light_valid && k.light_g_gen == p.g_gen && k.light_smap_frame == k.smap_frame && f.light_uniforms_same &&
+                             k.light_cube_gen == f.cube_gen && (k.light_all_px || f.light_empty_px);
+    p.light_keep = light_rest && light_match; p.light_fill = light_rest && !light_match;
     return p;
 }
 
@@ -231,6 +259,7 @@ static inline ZrFrameCarry zr_frame_carry(const ZrFrameCarry& before, const ZrFr
         if (p.camera_list_rebuild) k.list_valid[1] = false;
         if (!p.shadow_keep) k.smap_valid = false;
         if (!p.camera_keep) { k.r2_settled = k.cam_prev_valid = false; k.plan_behind_cam = false; }      // (the head has waited for the lane's end where it had to)
+        if (p.light_fill) k.light_valid = false;
         break;
     case ZR_STAGE_SHADOW:          // a drawn pass: the map is this frame's
         if (p.shadow_list_rebuild) k.list_valid[0] = true;
@@ -244,6 +273,12 @@ static inline ZrFrameCarry zr_frame_carry(const ZrFrameCarry& before, const ZrFr
         if (f.n_work[1] != 0) { k.plan_valid = true; k.plan_two_round = p.rounds != ZR_ROUNDS_ONE; }      // (k_plan ran: the next frame's buckets)
         k.r2_settled = p.rounds != ZR_ROUNDS_ONE && p.cam_same;
         k.cam_prev_epoch = f.camera_epoch; k.cam_prev_valid = k.vis_history = p.hiz_on;
+        break;
+    case ZR_STAGE_LIGHTING:        // a pass that filled the plane: it is this frame's
+        if (p.light_fill) {
+            k.light_valid = true; k.light_all_px = !f.light_empty_px;
+            k.light_g_gen = p.g_gen; k.light_smap_frame = k.smap_frame; k.light_cube_gen = f.cube_gen;
+        }
         break;
     }
     return k;

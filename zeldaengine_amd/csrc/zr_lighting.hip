@@ -5,17 +5,21 @@
 #include "zr_shade.h"
 
 // BaseLighting.frag:147-254 for every pixel of the owned tiles (the full-screen quad of ZE:3531-3540)
-template <bool LIGHT_LIST, bool BACKGROUND, int TB, int PPT>      // PPT: pixels per thread, 4 or 1 (as in k_resolve_gbuffer)
+// MODE (ZrLightMode): FILL also stores the pixel's standing terms - Direct after the directional lights, ShadowFactor, RefC, exact fp32 - into
+// the context's plane; KEPT loads them instead of running shade_standing (no PCF, no directional BxDF, no cubemap) and goes on as ever: the
+// point lights, Indirect, compose, gamma, the debug views.  Pixels that take the empty-pixel shortcut touch the plane in neither mode.
+template <bool LIGHT_LIST, bool BACKGROUND, int TB, int PPT, uint32_t MODE>      // PPT: pixels per thread, 4 or 1 (as in k_resolve_gbuffer)
 // (compiled for exactly ZR_LIGHT_WAVES waves per SIMD; left to itself the allocator takes 127 registers.  Rounds 4 - 5 ran it at 4 waves
 // (97 VGPRs): beside a camera lane that filled the whole period, a fifth wave cost that lane more than it gave this pass.  With that lane's
 // scans and index passes gone (round 6) the frame's period was THIS lane's, and the fifth wave paid: 4 / 5 / 6 waves 5 548 / 5 670 / 5 420
 // Mpixel/s.  On a frame that keeps its camera pass the kernel runs alone, and a sixth pays: 16 770 / 17 470 / 19 363, the moving-camera
-// loop, where the lane is still there, the same within its margin)
-__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(ZR_LIGHT_WAVES, ZR_LIGHT_WAVES))) void k_lighting(ZrLightParams L, const XkView* __restrict__ view,
+// loop, where the lane is still there, the same within its margin.  The KEPT variant is compiled for
+// ZR_LIGHT_KEPT_WAVES: it needs far fewer registers.)
+__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(MODE == ZR_LIGHT_KEPT ? ZR_LIGHT_KEPT_WAVES : ZR_LIGHT_WAVES, MODE == ZR_LIGHT_KEPT ? ZR_LIGHT_KEPT_WAVES : ZR_LIGHT_WAVES))) void k_lighting(ZrLightParams L, const XkView* __restrict__ view,
                                                   const uint32_t* __restrict__ owned_tiles, GBufferPtrs G,
                                                   const float* __restrict__ shadowmap, CubeDesc C,
                                                   const float* __restrict__ srgb_lut, const float* __restrict__ unorm_lut,
-                                                  uint32_t* __restrict__ out)
+                                                  uint32_t* __restrict__ out, float4* __restrict__ plane)
 {
     // UNORM loads are IEEE quotients c / 255 and c / 1023: 14 per pixel, served from an LDS copy of the host-built table
     __shared__ float tl[512];            // [0, 256) sRGB decode (24 cubemap fetches per pixel), [256, 512) c / 255: tex_decode's layout
@@ -131,8 +135,20 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(ZR_LIGHT_WAV
         const zf3 N = zr_normalize(Normal);
         const zf3 Pw = zr3(f16_to_f32_hw(D.x & 0xFFFFu), f16_to_f32_hw(D.x >> 16), f16_to_f32_hw(D.y & 0xFFFFu));
         zf3 Direct, Indirect, RefC; float ShadowFactor;
-        shade_surface<use_mask>(L, view, shadowmap, C, slut, lmask, nDir, nPoint, maxmips, dxy, cam, BaseColor, Metallic, Roughness, N, AO, Pw,
-                                Direct, Indirect, RefC, ShadowFactor);
+        if constexpr (MODE == ZR_LIGHT_KEPT) {      // the standing terms as the fill stored them: two 16-byte loads
+            const float4 ka = plane[p], kb = plane[(size_t)L.W * L.H + p];
+            Direct = zr3(ka.x, ka.y, ka.z); ShadowFactor = ka.w; RefC = zr3(kb.x, kb.y, kb.z);
+            shade_points<use_mask>(L, view, lmask, nDir, nPoint, cam, BaseColor, Metallic, Roughness, N, Pw, Direct);
+            Indirect = shade_indirect(BaseColor, Metallic, AO, ShadowFactor);
+        } else if constexpr (MODE == ZR_LIGHT_FILL) {
+            shade_standing(L, view, shadowmap, C, slut, nDir, maxmips, dxy, cam, BaseColor, Metallic, Roughness, N, AO, Pw, Direct, RefC, ShadowFactor);
+            plane[p] = make_float4(Direct.x, Direct.y, Direct.z, ShadowFactor);
+            plane[(size_t)L.W * L.H + p] = make_float4(RefC.x, RefC.y, RefC.z, 0.0f);
+            shade_points<use_mask>(L, view, lmask, nDir, nPoint, cam, BaseColor, Metallic, Roughness, N, Pw, Direct);
+            Indirect = shade_indirect(BaseColor, Metallic, AO, ShadowFactor);
+        } else
+            shade_surface<use_mask>(L, view, shadowmap, C, slut, lmask, nDir, nPoint, maxmips, dxy, cam, BaseColor, Metallic, Roughness, N, AO, Pw,
+                                    Direct, Indirect, RefC, ShadowFactor);
 
         zf3 Final = ((Direct + Indirect) + RefC) * Mask;
         Final = zr3(zr_pow(Final.x, 0.4545f), zr_pow(Final.y, 0.4545f), zr_pow(Final.z, 0.4545f));
@@ -271,14 +287,19 @@ __global__ __launch_bounds__(256) void k_gbuffer_vis(ZrLightParams L, const XkVi
 
 void zr_launch_lighting(const ZrLightParams& L, const XkView* view, const uint32_t* owned_tiles, uint32_t n_owned,
                         const GBufferPtrs& G, const float* shadowmap, const CubeDesc& C, const float* lut, const float* unorm_lut,
-                        uint32_t* out, hipStream_t s)
+                        uint32_t* out, hipStream_t s, ZrLightMode mode, float4* plane)
 {
     if (n_owned == 0) return;
+    if (!plane) mode = ZR_LIGHT_PLAIN;      // (no plane: nothing to fill or to read)
     // with several point lights each tile first builds its light list (L.light_list: decided on the host from the light count)
-#define ZR_LAUNCH_LIGHTING(LL, BG) hipLaunchKernelGGL((k_lighting<LL, BG, ZR_LIGHT_TB, ZR_PIXELS_PER_THREAD>), dim3(n_owned * (TILE_PIX / ZR_PIXELS_PER_THREAD / ZR_LIGHT_TB)), dim3(ZR_LIGHT_TB), 0, s, L, view, owned_tiles, G, shadowmap, C, lut, unorm_lut, out)
+#define ZR_LAUNCH_LIGHTING_TB(LL, BG, TB, MODE) hipLaunchKernelGGL((k_lighting<LL, BG, TB, ZR_PIXELS_PER_THREAD, MODE>), dim3(n_owned * (TILE_PIX / ZR_PIXELS_PER_THREAD / TB)), dim3(TB), 0, s, L, view, owned_tiles, G, shadowmap, C, lut, unorm_lut, out, plane)
+#define ZR_LAUNCH_LIGHTING(LL, BG) do { if (mode == ZR_LIGHT_KEPT) ZR_LAUNCH_LIGHTING_TB(LL, BG, ZR_LIGHT_KEPT_TB, ZR_LIGHT_KEPT); \
+                                        else if (mode == ZR_LIGHT_FILL) ZR_LAUNCH_LIGHTING_TB(LL, BG, ZR_LIGHT_TB, ZR_LIGHT_FILL); \
+                                        else ZR_LAUNCH_LIGHTING_TB(LL, BG, ZR_LIGHT_TB, ZR_LIGHT_PLAIN); } while (0)
     if (L.light_list) { if (L.bg_enabled) ZR_LAUNCH_LIGHTING(true, true); else ZR_LAUNCH_LIGHTING(true, false); }
     else { if (L.bg_enabled) ZR_LAUNCH_LIGHTING(false, true); else ZR_LAUNCH_LIGHTING(false, false); }
 #undef ZR_LAUNCH_LIGHTING
+#undef ZR_LAUNCH_LIGHTING_TB
 }
 void zr_launch_gbuffer_vis(const ZrLightParams& L, const XkView* view, const GBufferPtrs& G, const float* shadowmap, const CubeDesc& C,
                            const float* lut, uint32_t* out, hipStream_t s)

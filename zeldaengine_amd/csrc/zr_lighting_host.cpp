@@ -1,0 +1,131 @@
+// zr_lighting_host.cpp — the lighting stage of a frame (zr_frame_host.cpp has the stages before it): the pass's uniforms, the one-pixel
+// launch, the pass itself, and the plane of standing terms a resting frame's pass reads instead of computing them (zr_frame_plan.h decides:
+// ZrFramePlan::light_keep / light_fill; DESIGN.md section 5, "The schedule").
+#include "zr_ctx.h"
+#include "zr_math.h"
+
+#include <cstring>
+
+static void light_params(const zr_ctx* c, ZrLightParams* Lp)
+{
+    ZrLightParams& L = *Lp; memset(&L, 0, sizeof L);
+    static const float Bias[16] = { 0.5f, 0, 0, 0, 0, 0.5f, 0, 0, 0, 0, 1, 0, 0.5f, 0.5f, 0, 1 };
+    zr_mat4_mul(Bias, c->view.ShadowmapSpace, L.SB);
+    L.W = c->W; L.H = c->H; L.SD = c->SD; L.tiles_x = c->tiles_x; L.debug_view = c->debug_view;
+    L.cube_dim = c->cube_dim; L.cube_levels = c->cube_levels; L.tile_world = c->cfg.tile_world;
+    L.packed_out = (c->cfg.tile_world > 1 || (c->cfg.flags & ZR_FLAG_PACKED_TILES)) ? 1u : 0u;
+    L.debug_skip = c->env_skip_light;
+    L.bg_enabled = (c->bg_set && c->bg_enabled) ? 1u : 0u;
+    L.has_overlay = c->fc[c->fcur].overlay_dirty ? 1u : 0u;     // set by this frame's gbuffer pass
+    { const int32_t np = c->view.LightsCount[1]; L.light_list = (np >= c->env_light_list_min && np <= XK_MAX_POINT_LIGHTS_NUM) ? 1u : 0u; }
+    L.bg.data = c->d_bg; L.bg.w = c->bg_w; L.bg.h = c->bg_h; L.bg.levels = c->bg_levels; L.bg._pad = 0;
+}
+
+// Whether the frame's lighting pass takes the empty-pixel shortcut (empty_pixel_pass below).
+static bool empty_px_on(const zr_ctx* c) { return c->shading != ZR_SHADING_FORWARD && c->debug_view != 6u && !c->env_no_empty_px; }
+
+// The standing uniforms: everything shade_standing (zr_shade.h) reads that is neither the pixel's GBuffer values, the shadow map nor the
+// cubemap's texels - L.SB, SD, the camera position, LightsCount[0] and [3], the directional light records in use, the cubemap's shape,
+// debug_skip.  Unused records are zero, so that two keys compare byte for byte.
+static void light_key(const zr_ctx* c, zr_ctx::LightKey* K)
+{
+    ZrLightParams L; light_params(c, &L);
+    memset(K, 0, sizeof *K);
+    memcpy(K->SB, L.SB, sizeof K->SB); memcpy(K->cam, c->view.CameraInfo, sizeof K->cam);
+    K->SD = L.SD; K->max_mips = (uint32_t)c->view.LightsCount[3]; K->cube_dim = L.cube_dim; K->cube_levels = L.cube_levels; K->debug_skip = L.debug_skip;
+    const int32_t nd = c->view.LightsCount[0];
+    K->n_dir = (uint32_t)nd;
+    for (int32_t i = 0; i < nd && i < XK_MAX_DIRECTIONAL_LIGHTS_NUM; ++i) K->dir[i] = c->view.DirectionalLights[i];
+}
+
+void zr_light_facts(zr_ctx* c, ZrFrameFacts* f)
+{
+    light_key(c, &c->lk.now);
+    f->light_plane_ok = !c->lk.alloc_failed;
+    f->light_uniforms_same = c->lk.plane != nullptr && memcmp(&c->lk.now, &c->lk.key, sizeof c->lk.key) == 0;
+    f->cube_gen = c->cube_gen;
+    f->light_empty_px = empty_px_on(c);
+}
+
+// The plane is made when the first frame is planned to fill it: 32 B x W x H (66 MB at 1080p, 265 MB at 2160p), through the context's
+// owner.  No room: the context simply never keeps - that is no error.
+bool zr_light_plane_make(zr_ctx* c)
+{
+    if (c->lk.plane) return true;
+    if (!c->lk.alloc_failed && c->own.alloc(&c->lk.plane, 2 * (size_t)c->W * c->H) != hipSuccess) {
+        (void)hipGetLastError();      // (the refusal is not the frame's error)
+        c->lk.plane = nullptr; c->lk.alloc_failed = true;
+    }
+    return c->lk.plane != nullptr;
+}
+
+// The lighting shader's colour for a pixel that still holds every target's clear value: one launch of the lighting kernel over a
+// one-pixel GBuffer.  It needs the finished shadow map (PCF at world position 0) and the frame's uniforms, nothing else.  View 6
+// (the quad's interpolated vertex colour) depends on the pixel position, so it goes without.  It never fills and never reads the plane.
+int empty_pixel_pass(zr_ctx* c)
+{
+    c->empty_ready = false;
+    if (c->plan.one_pixel == ZR_LANE_NONE || !empty_px_on(c)) return ZR_OK;
+    ZrLightParams L; light_params(c, &L);
+    L.W = 1; L.H = 1; L.tiles_x = 1; L.packed_out = 0; L.bg_enabled = 0;
+    zr_launch_lighting(L, c->fc[c->fcur].view, c->d_sowned, 1, c->Gclear, shadow_buf(c), c->cube, c->d_lut, c->d_unorm_lut, c->fc[c->fcur].empty_rgba,
+                       lane_stream(c, c->plan.one_pixel));
+    HIPCHK(c, hipGetLastError());
+    c->empty_ready = true;
+    return ZR_OK;
+}
+
+int lighting_pass(zr_ctx* c)
+{
+    const ZrFramePlan& p = c->plan;
+    const hipStream_t s = lane_stream(c, p.lighting);
+    ZrLightParams L; light_params(c, &L);
+    const FrameCopy& F = c->fc[c->fcur];
+    L.empty_rgba = c->empty_ready ? F.empty_rgba : nullptr;
+    // The next DRAWN shadow pass follows on this stream and rasterises into the OTHER copy of the map, which nothing reads or
+    // writes while this pass runs: clear it here - once; a run of frames that keep their map finds it clear and writes nothing.
+    FrameCopy& next = c->fc[c->smap ^ 1];
+    if (c->n_owned && !c->d_shadow_ext && !next.shadow_cleared) { L.clear_next = (uint32_t*)next.shadow; L.clear_n = c->SD * c->SD; next.shadow_cleared = true; }
+    uint32_t* const frame_out = L.packed_out ? (c->d_tiles_ext ? c->d_tiles_ext : c->d_tiles) : c->d_color;
+    // What the plan decided about the plane holds unless the debug view or the cubemap changed between the stages of the frame (the
+    // staged entry points: neither call is refused there): then this pass ignores the plane, and the next resting frame fills it.
+    ZrLightMode mode = p.light_keep ? ZR_LIGHT_KEPT : p.light_fill ? ZR_LIGHT_FILL : ZR_LIGHT_PLAIN;
+    if (mode != ZR_LIGHT_PLAIN && (c->facts.cube_gen != c->cube_gen || c->facts.light_empty_px != c->empty_ready || !c->lk.plane || c->shading == ZR_SHADING_FORWARD)) {
+        mode = ZR_LIGHT_PLAIN; zr_history_forgotten(c, ZR_HIST_LIGHT_PLANE);
+    }
+    if (c->shading == ZR_SHADING_FORWARD) {
+        // Base.frag over the winners the resolve recorded, with this frame's camera block (frame_begin built it; the overlay fields play no part)
+        if (L.clear_next) { zr_launch_fill32(L.clear_next, 0x3F800000u, L.clear_n, s); L.clear_next = nullptr; }
+        zr_launch_forward(c->pass[1], L, F.view, c->d_objs, c->d_owned, c->n_owned, F.G, shadow_buf(c), c->cube, c->d_lut, c->d_unorm_lut, frame_out, s);
+    } else {
+        zr_launch_lighting(L, F.view, c->d_owned, c->n_owned, F.G, shadow_buf(c), c->cube, c->d_lut, c->d_unorm_lut, frame_out, s, mode, c->lk.plane);
+        if (c->debug_view == 9u)        // GBufferVis mosaic over the lit frame (needs the whole GBuffer: single-rank contexts only)
+            zr_launch_gbuffer_vis(L, F.view, F.G, shadow_buf(c), c->cube, c->d_lut, c->d_color, s);
+    }
+    TIMED(c, s, zr_ctx::EV_LIGHTING);
+    HIPCHK(c, hipEventRecord(c->ev_end[c->frame_no % zr_ctx::END_RING], s));      // this frame's GBuffer / shadow map / uniforms copies are free again
+    HIPCHK(c, hipGetLastError());
+    if (mode == ZR_LIGHT_FILL) { c->lk.key = c->lk.now; c->carry = zr_frame_carry(c->carry, c->facts, p, ZR_STAGE_LIGHTING); }
+    c->lk.last = (uint32_t)mode; c->lk.count[mode]++;
+    if (c->timing_now) c->sample_no++;
+    c->rendered = true; c->frame_no++; c->stage = 0;
+    c->ids_frame = c->ids_this; c->ids.gen = c->scene_gen;
+    return ZR_OK;
+}
+
+static_assert(ZR_LIGHT_PLANE_IGNORED == (uint32_t)ZR_LIGHT_PLAIN && ZR_LIGHT_PLANE_FILLED == (uint32_t)ZR_LIGHT_FILL && ZR_LIGHT_PLANE_READ == (uint32_t)ZR_LIGHT_KEPT,
+              "zelda_render.h: what a lighting pass did with the plane");
+
+extern "C" int zr_get_light_keep(zr_ctx* c, zr_light_keep* out, size_t bytes)
+{
+    if (!c || !out) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        zr_light_keep k;
+        memset(&k, 0, sizeof k);
+        k.last = c->rendered ? c->lk.last : ZR_LIGHT_PLANE_IGNORED;
+        k.ignored = c->lk.count[ZR_LIGHT_PLAIN]; k.filled = c->lk.count[ZR_LIGHT_FILL]; k.read = c->lk.count[ZR_LIGHT_KEPT];
+        k.plane_bytes = c->lk.plane ? 32ull * c->W * c->H : 0ull;
+        memcpy(out, &k, bytes < sizeof k ? bytes : sizeof k);
+        return ZR_OK;
+    });
+}

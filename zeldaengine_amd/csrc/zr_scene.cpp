@@ -657,7 +657,7 @@ extern "C" int zr_set_cubemap(zr_ctx* c, const uint8_t* const faces[6], uint32_t
         if (faces) for (int f = 0; f < 6; ++f) ARGCHK(c, faces[f] != nullptr);
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, zr_sync_all(c));
-        c->cube_mem.release(); c->world_named[0] = false;
+        c->cube_mem.release(); c->world_named[0] = false; c->cube_gen++;      // (what the lighting pass kept of the old texels is void)
         memset(&c->cube, 0, sizeof c->cube);
         uint32_t levels = 1; for (uint32_t d = dim; d > 1; d >>= 1) levels++;      // floor(log2(dim)) + 1, ZE:6887
         if (levels > 16) return zr_fail(c, ZR_ERR_ARG, "cubemap too large");

@@ -92,15 +92,108 @@ __device__ __forceinline__ float shadow_tap(const float* __restrict__ S, int SD,
 // directional then the point lights, (2) the lambert indirect term, (3) the image-based reflection.  Inputs as the shader holds them at that
 // point (N: normalize(Normal) of the unpacked GBufferA in the deferred shader, ComputeNormal()'s result in the forward one).
 // USE_MASK: the point lights are the set bits of lmask (the tile's light list, k_lighting), walked in ascending order.
-template <bool USE_MASK>
-__device__ __forceinline__ void shade_surface(const ZrLightParams& L, const XkView* __restrict__ view, const float* __restrict__ shadowmap,
-                                              const CubeDesc& C, const float* __restrict__ slut, const uint32_t* lmask,
-                                              uint32_t nDir, uint32_t nPoint, float maxmips, float dxy, zf3 cam,
-                                              zf3 BaseColor, float Metallic, float Roughness, zf3 N, float AO, zf3 Pw,
-                                              zf3& Direct, zf3& Indirect, zf3& RefC, float& ShadowFactor)
+//
+// The body is three functions.  shade_standing: everything no point light feeds - ShadowFactor, Direct over the directional lights (they
+// come first in the accumulation order), RefC.  shade_points: continues that same Direct over the point lights.  shade_indirect: four
+// multiplications.  A lighting pass that kept a pixel's standing terms (k_lighting, kept mode) runs the last two alone.  Each part forms
+// what it needs of the pixel's basis (view vector, N.V, the re-normalised N, the diffuse colour) from the same operands by the same
+// operations: the bits are those of the one body.  shade_surface is the three in sequence, except that it walks both runs of lights in one
+// loop, as the shader does: two loops in a row are two inlined copies of the BxDF, which cost k_lighting 7 registers and a spill.
+struct ShadeBasis { zf3 Vv, Nn, DiffuseColor; float NdotV; };
+__device__ __forceinline__ ShadeBasis shade_basis(zf3 cam, zf3 BaseColor, float Metallic, zf3 N, zf3 Pw)
 {
-    const zf3 Vv = zr_normalize(cam - Pw);
-    const float NdotV = zr_saturate(zr_dot(N, Vv));
+    ShadeBasis b;
+    b.Vv = zr_normalize(cam - Pw);
+    b.NdotV = zr_saturate(zr_dot(N, b.Vv));
+    b.Nn = zr_normalize(N);                              // Apply*Light and refract() re-normalise N
+    b.DiffuseColor = BaseColor * (1.0f - Metallic);
+    return b;
+}
+
+// (1) Direct over the lights in the shader's order: directional, then point (with a tile list: only its set bits, ascending).  DIRS / POINTS:
+// which of the two runs the call walks - the one loop of shade_surface (both), or the halves of shade_standing and shade_points, each a
+// loop that knows its kind of light at compile time.
+template <bool USE_MASK, bool DIRS, bool POINTS>
+__device__ __forceinline__ void shade_lights(const ZrLightParams& L, const XkView* __restrict__ view, const uint32_t* lmask, uint32_t nDir, uint32_t nPoint,
+                                             const ShadeBasis& basis, zf3 N, float Roughness, zf3 Pw, float ShadowFactor, zf3& Direct)
+{
+    const zf3& Vv = basis.Vv; const zf3& Nn = basis.Nn; const zf3& DiffuseColor = basis.DiffuseColor; const float NdotV = basis.NdotV;
+    const uint32_t n_lights = (ZR_DIAG_SKIP(L.debug_skip) & 2u) ? 0u : (POINTS ? nDir + nPoint : nDir);
+    uint32_t mword = 0u, mnext = 0u;       // remaining bits of the current mask word, index of the next word
+    for (uint32_t li = DIRS ? 0u : nDir; li < n_lights; ++li) {
+        if (USE_MASK && POINTS && li >= nDir) {
+            while (mword == 0u && mnext * 32u < nPoint) mword = lmask[mnext++];
+            if (mword == 0u) break;
+            const uint32_t b = (uint32_t)__builtin_ctz(mword);
+            mword &= mword - 1u;
+            li = nDir + (mnext - 1u) * 32u + b;
+            if (li >= n_lights) break;
+        }
+        const bool isdir = !POINTS || (DIRS && li < nDir);
+        const XkLight* __restrict__ Lt = isdir ? &view->DirectionalLights[li] : &view->PointLights[li - nDir];
+        const zf3 lp = zr3(Lt->Position[0], Lt->Position[1], Lt->Position[2]);
+        // A light whose radiance factor is exactly 0 adds fma(0, bxdf, Direct) = Direct: skip its BxDF.  That is the
+        // case beyond a point light's radius (attenuation 1 - clamp(d, 0, r) / r = 0) and for N.L <= 0.  The skip
+        // needs finite colour * intensity (0 * finite = 0); the test is wave-uniform per light.  Where the BxDF is NaN or
+        // infinite (D_GGX at roughness 0 with N.H = 1), or the attenuation is NaN (falloff 0) while N.L is 0, the shader's
+        // literal sum would be NaN; the contract is the skip, and the CPU oracle states the same (row 8 of its CONTRACT.md).
+        const bool lfinite = __builtin_fabsf(Lt->Color[0]) <= 3.402823466e38f && __builtin_fabsf(Lt->Color[1]) <= 3.402823466e38f &&
+                             __builtin_fabsf(Lt->Color[2]) <= 3.402823466e38f && __builtin_fabsf(Lt->Color[3]) <= 3.402823466e38f;
+        float att = 1.0f;
+        zf3 Lv;
+        if (!isdir) {
+            const float falloff = Lt->Direction[3];
+            // far outside the radius (1e-6 relative margin on the squared distance covers every rounding in dist): the exact
+            // test below would give att == 0, so the distance and the quotient need not be formed
+            const zf3 dl = lp - Pw;
+            const float d2 = zr_dot(dl, dl);
+            if (lfinite && falloff > 0.0f && d2 > (falloff * falloff) * 1.000001f) continue;
+            // distance(light_pos, position) and normalize(light_pos - position) share ONE inversesqrt: length = d2 * inversesqrt(d2)
+            // (0 for d2 = 0; GLSL derives sqrt's precision from inversesqrt's), direction = dl * inversesqrt(d2)
+            const float rd = zr_rsqrt(d2);
+            const float dist = d2 > 0.0f ? d2 * rd : 0.0f;
+            // remap(dist, 0, falloff, 0, 1), SH/Common.glsl:43-47.  The quotient stays an IEEE division: falloff / falloff must be
+            // exactly 1 beyond the radius (the tile light lists and the skips around here rest on att == 0 there)
+            att = 1.0f - zr_clamp(dist, 0.0f, falloff) / falloff;
+            if (lfinite && att == 0.0f) continue;
+            Lv = dl * rd;
+        } else Lv = zr_normalize(zr3(Lt->Direction[0], Lt->Direction[1], Lt->Direction[2]));
+        // ApplyDirectionalLight / ApplyPointLight (SH/Common.glsl:364-372, 399-416)
+        const float ndotl = zr_clamp(zr_dot(Nn, Lv), 0.0f, 1.0f);
+        if (lfinite && ndotl == 0.0f) continue;
+        const zf3 Hh = zr_normalize(Vv + Lv);
+        const float LdotH = zr_saturate(zr_dot(Lv, Hh)), NdotH = zr_saturate(zr_dot(N, Hh)), NdotL = zr_saturate(zr_dot(N, Lv));
+        // DefaultLitBxDF (SH/Common.glsl:259-282): F0 = 0.04, F90 = saturate(50 * 0.04)
+        const float F = F_Schlick(0.04f, zr_saturate(50.0f * 0.04f), LdotH);
+        const float Vis = V_SmithGGXCorrelated(NdotV, NdotL, Roughness);
+        const float Dg = D_GGX(NdotH, Roughness);
+        const float Fr = (F * Dg) * Vis;
+        const float Fd = Fr_DisneyDiffuse(NdotV, NdotL, LdotH, Roughness);
+        const zf3 bx = zr3(__builtin_fmaf(DiffuseColor.x * (1.0f - F), Fd, Fr), __builtin_fmaf(DiffuseColor.y * (1.0f - F), Fd, Fr),
+                           __builtin_fmaf(DiffuseColor.z * (1.0f - F), Fd, Fr));
+        const float k = ndotl * Lt->Color[3];
+        zf3 rad = zr3(k * Lt->Color[0], k * Lt->Color[1], k * Lt->Color[2]);
+        if (isdir) {
+            Direct = zr3(__builtin_fmaf(rad.x * bx.x, ShadowFactor, Direct.x), __builtin_fmaf(rad.y * bx.y, ShadowFactor, Direct.y),
+                         __builtin_fmaf(rad.z * bx.z, ShadowFactor, Direct.z));
+        } else {
+            rad = rad * att;
+            Direct = zr3(__builtin_fmaf(rad.x, bx.x, Direct.x), __builtin_fmaf(rad.y, bx.y, Direct.y), __builtin_fmaf(rad.z, bx.z, Direct.z));
+        }
+    }
+}
+
+// The PCF factor, Direct, the image-based reflection.  LIGHTS 1: Direct over the directional lights only (shade_standing); 2: over all of
+// them in ONE loop (shade_surface: one copy of the BxDF in the kernels that keep nothing, as they have always had it).
+template <bool USE_MASK, int LIGHTS>
+__device__ __forceinline__ void shade_body(const ZrLightParams& L, const XkView* __restrict__ view, const float* __restrict__ shadowmap,
+                                           const CubeDesc& C, const float* __restrict__ slut, const uint32_t* lmask,
+                                           uint32_t nDir, uint32_t nPoint, float maxmips, float dxy, zf3 cam,
+                                           zf3 BaseColor, float Metallic, float Roughness, zf3 N, float AO, zf3 Pw,
+                                           zf3& Direct, zf3& RefC, float& ShadowFactor)
+{
+    const ShadeBasis basis = shade_basis(cam, BaseColor, Metallic, N, Pw);
+    const zf3& Vv = basis.Vv; const zf3& Nn = basis.Nn; const float NdotV = basis.NdotV;
 
     const zf4 s4 = zr_mat4_point(L.SB, Pw);
     // shadowCoord / shadowCoord.w (SH/Common.glsl:296): IEEE divisions - the PCF comparison below is the shader's one discontinuity,
@@ -169,76 +262,8 @@ __device__ __forceinline__ void shade_surface(const ZrLightParams& L, const XkVi
     ShadowFactor = sum * 0.04f;       // ShadowFactor / Count (25 taps)
 
     Direct = zr3(0.0f, 0.0f, 0.0f);
-    const zf3 Nn = zr_normalize(N);                      // Apply*Light and refract() re-normalise N
-    const zf3 DiffuseColor = BaseColor * (1.0f - Metallic);
-    // lights in the shader's order: directional, then point (with a tile list: only its set bits, ascending)
-    const uint32_t n_lights = (ZR_DIAG_SKIP(L.debug_skip) & 2u) ? 0u : nDir + nPoint;
-    uint32_t mword = 0u, mnext = 0u;       // remaining bits of the current mask word, index of the next word
-    for (uint32_t li = 0; li < n_lights; ++li) {
-        if (USE_MASK && li >= nDir) {
-            while (mword == 0u && mnext * 32u < nPoint) mword = lmask[mnext++];
-            if (mword == 0u) break;
-            const uint32_t b = (uint32_t)__builtin_ctz(mword);
-            mword &= mword - 1u;
-            li = nDir + (mnext - 1u) * 32u + b;
-            if (li >= n_lights) break;
-        }
-        const bool isdir = li < nDir;
-        const XkLight* __restrict__ Lt = isdir ? &view->DirectionalLights[li] : &view->PointLights[li - nDir];
-        const zf3 lp = zr3(Lt->Position[0], Lt->Position[1], Lt->Position[2]);
-        // A light whose radiance factor is exactly 0 adds fma(0, bxdf, Direct) = Direct: skip its BxDF.  That is the
-        // case beyond a point light's radius (attenuation 1 - clamp(d, 0, r) / r = 0) and for N.L <= 0.  The skip
-        // needs finite colour * intensity (0 * finite = 0); the test is wave-uniform per light.  Where the BxDF is NaN or
-        // infinite (D_GGX at roughness 0 with N.H = 1), or the attenuation is NaN (falloff 0) while N.L is 0, the shader's
-        // literal sum would be NaN; the contract is the skip, and the CPU oracle states the same (row 8 of its CONTRACT.md).
-        const bool lfinite = __builtin_fabsf(Lt->Color[0]) <= 3.402823466e38f && __builtin_fabsf(Lt->Color[1]) <= 3.402823466e38f &&
-                             __builtin_fabsf(Lt->Color[2]) <= 3.402823466e38f && __builtin_fabsf(Lt->Color[3]) <= 3.402823466e38f;
-        float att = 1.0f;
-        zf3 Lv;
-        if (!isdir) {
-            const float falloff = Lt->Direction[3];
-            // far outside the radius (1e-6 relative margin on the squared distance covers every rounding in dist): the exact
-            // test below would give att == 0, so the distance and the quotient need not be formed
-            const zf3 dl = lp - Pw;
-            const float d2 = zr_dot(dl, dl);
-            if (lfinite && falloff > 0.0f && d2 > (falloff * falloff) * 1.000001f) continue;
-            // distance(light_pos, position) and normalize(light_pos - position) share ONE inversesqrt: length = d2 * inversesqrt(d2)
-            // (0 for d2 = 0; GLSL derives sqrt's precision from inversesqrt's), direction = dl * inversesqrt(d2)
-            const float rd = zr_rsqrt(d2);
-            const float dist = d2 > 0.0f ? d2 * rd : 0.0f;
-            // remap(dist, 0, falloff, 0, 1), SH/Common.glsl:43-47.  The quotient stays an IEEE division: falloff / falloff must be
-            // exactly 1 beyond the radius (the tile light lists and the skips around here rest on att == 0 there)
-            att = 1.0f - zr_clamp(dist, 0.0f, falloff) / falloff;
-            if (lfinite && att == 0.0f) continue;
-            Lv = dl * rd;
-        } else Lv = zr_normalize(zr3(Lt->Direction[0], Lt->Direction[1], Lt->Direction[2]));
-        // ApplyDirectionalLight / ApplyPointLight (SH/Common.glsl:364-372, 399-416)
-        const float ndotl = zr_clamp(zr_dot(Nn, Lv), 0.0f, 1.0f);
-        if (lfinite && ndotl == 0.0f) continue;
-        const zf3 Hh = zr_normalize(Vv + Lv);
-        const float LdotH = zr_saturate(zr_dot(Lv, Hh)), NdotH = zr_saturate(zr_dot(N, Hh)), NdotL = zr_saturate(zr_dot(N, Lv));
-        // DefaultLitBxDF (SH/Common.glsl:259-282): F0 = 0.04, F90 = saturate(50 * 0.04)
-        const float F = F_Schlick(0.04f, zr_saturate(50.0f * 0.04f), LdotH);
-        const float Vis = V_SmithGGXCorrelated(NdotV, NdotL, Roughness);
-        const float Dg = D_GGX(NdotH, Roughness);
-        const float Fr = (F * Dg) * Vis;
-        const float Fd = Fr_DisneyDiffuse(NdotV, NdotL, LdotH, Roughness);
-        const zf3 bx = zr3(__builtin_fmaf(DiffuseColor.x * (1.0f - F), Fd, Fr), __builtin_fmaf(DiffuseColor.y * (1.0f - F), Fd, Fr),
-                           __builtin_fmaf(DiffuseColor.z * (1.0f - F), Fd, Fr));
-        const float k = ndotl * Lt->Color[3];
-        zf3 rad = zr3(k * Lt->Color[0], k * Lt->Color[1], k * Lt->Color[2]);
-        if (isdir) {
-            Direct = zr3(__builtin_fmaf(rad.x * bx.x, ShadowFactor, Direct.x), __builtin_fmaf(rad.y * bx.y, ShadowFactor, Direct.y),
-                         __builtin_fmaf(rad.z * bx.z, ShadowFactor, Direct.z));
-        } else {
-            rad = rad * att;
-            Direct = zr3(__builtin_fmaf(rad.x, bx.x, Direct.x), __builtin_fmaf(rad.y, bx.y, Direct.y), __builtin_fmaf(rad.z, bx.z, Direct.z));
-        }
-    }
-    // (2) indirect, BaseLighting.frag:210
-    Indirect = zr3((((DiffuseColor.x * ZR_INV_PI) * AO) * 0.3f) * ShadowFactor,
-                             (((DiffuseColor.y * ZR_INV_PI) * AO) * 0.3f) * ShadowFactor,
-                             (((DiffuseColor.z * ZR_INV_PI) * AO) * 0.3f) * ShadowFactor);
+    if (LIGHTS == 1) shade_lights<false, true, false>(L, view, lmask, nDir, nPoint, basis, N, Roughness, Pw, ShadowFactor, Direct);
+    if (LIGHTS == 2) shade_lights<USE_MASK, true, true>(L, view, lmask, nDir, nPoint, basis, N, Roughness, Pw, ShadowFactor, Direct);
     // (3) reflection, :213-221
     const zf3 bcl = zr3(zr_clamp(BaseColor.x, 0.04f, 1.0f), zr_clamp(BaseColor.y, 0.04f, 1.0f), zr_clamp(BaseColor.z, 0.04f, 1.0f));
     const float dsf0 = (0.04f * 2.0f) * 0.5f;
@@ -265,4 +290,46 @@ __device__ __forceinline__ void shade_surface(const ZrLightParams& L, const XkVi
     const zf3 RL = (ZR_DIAG_SKIP(L.debug_skip) & 4u) ? zr3(0.0f, 0.0f, 0.0f) : cube_sample(C, slut, L.cube_dim, (int)L.cube_levels, R, MIPS) * 10.0f;
     const float RV = zr_saturate((zr_pow(NdotV + AO, Roughness * Roughness) - 1.0f) + AO);   // GetSpecularOcclusion :226
     RefC = zr3((RL.x * RV) * RBRDF.x, (RL.y * RV) * RBRDF.y, (RL.z * RV) * RBRDF.z);
+}
+
+// The standing part: everything no point light feeds.  Its inputs: the pixel's GBuffer values, the shadow map, L.SB / SD, the camera
+// position, LightsCount[0] and [3], the directional light records, the cubemap, debug_skip.
+__device__ __forceinline__ void shade_standing(const ZrLightParams& L, const XkView* __restrict__ view, const float* __restrict__ shadowmap,
+                                               const CubeDesc& C, const float* __restrict__ slut,
+                                               uint32_t nDir, float maxmips, float dxy, zf3 cam,
+                                               zf3 BaseColor, float Metallic, float Roughness, zf3 N, float AO, zf3 Pw,
+                                               zf3& Direct, zf3& RefC, float& ShadowFactor)
+{
+    shade_body<false, 1>(L, view, shadowmap, C, slut, nullptr, nDir, 0u, maxmips, dxy, cam, BaseColor, Metallic, Roughness, N, AO, Pw, Direct, RefC, ShadowFactor);
+}
+
+// The point-light part: continues the Direct shade_standing left over the point lights, in ascending order - with a tile list only its set
+// bits - with the same skips.  (A point light's term has no shadow factor.)
+template <bool USE_MASK>
+__device__ __forceinline__ void shade_points(const ZrLightParams& L, const XkView* __restrict__ view, const uint32_t* lmask, uint32_t nDir, uint32_t nPoint,
+                                             zf3 cam, zf3 BaseColor, float Metallic, float Roughness, zf3 N, zf3 Pw, zf3& Direct)
+{
+    const ShadeBasis basis = shade_basis(cam, BaseColor, Metallic, N, Pw);
+    shade_lights<USE_MASK, false, true>(L, view, lmask, nDir, nPoint, basis, N, Roughness, Pw, 0.0f, Direct);
+}
+
+// (2) indirect, BaseLighting.frag:210
+__device__ __forceinline__ zf3 shade_indirect(zf3 BaseColor, float Metallic, float AO, float ShadowFactor)
+{
+    const zf3 DiffuseColor = BaseColor * (1.0f - Metallic);
+    return zr3((((DiffuseColor.x * ZR_INV_PI) * AO) * 0.3f) * ShadowFactor,
+               (((DiffuseColor.y * ZR_INV_PI) * AO) * 0.3f) * ShadowFactor,
+               (((DiffuseColor.z * ZR_INV_PI) * AO) * 0.3f) * ShadowFactor);
+}
+
+// The three in sequence, with the two runs of lights walked by one loop (shade_body).
+template <bool USE_MASK>
+__device__ __forceinline__ void shade_surface(const ZrLightParams& L, const XkView* __restrict__ view, const float* __restrict__ shadowmap,
+                                              const CubeDesc& C, const float* __restrict__ slut, const uint32_t* lmask,
+                                              uint32_t nDir, uint32_t nPoint, float maxmips, float dxy, zf3 cam,
+                                              zf3 BaseColor, float Metallic, float Roughness, zf3 N, float AO, zf3 Pw,
+                                              zf3& Direct, zf3& Indirect, zf3& RefC, float& ShadowFactor)
+{
+    shade_body<USE_MASK, 2>(L, view, shadowmap, C, slut, lmask, nDir, nPoint, maxmips, dxy, cam, BaseColor, Metallic, Roughness, N, AO, Pw, Direct, RefC, ShadowFactor);
+    Indirect = shade_indirect(BaseColor, Metallic, AO, ShadowFactor);
 }

@@ -337,9 +337,13 @@ void zr_launch_resolve_gbuffer(const ZrPass& P, const ZrObject* objs, const uint
                                ZrDevStats* stats, hipStream_t s, uint32_t vis_mark = 1u);
 void zr_launch_sky_tiles(const ZrPass& P, const ZrObject* objs, const uint32_t* owned_tiles, uint32_t n_owned, unsigned long long* sky64, hipStream_t s);
 void zr_launch_count_shadow(const uint32_t* bits, size_t n, ZrDevStats* stats, hipStream_t s);
+// What the lighting pass does with the context's plane of standing terms (zr_lighting_host.cpp): nothing; shade as ever and store each
+// pixel's terms; load them instead of computing them.  The plane: W * H float4 (Direct over the directional lights, ShadowFactor), then
+// W * H float4 (RefC, 0).
+enum ZrLightMode : uint32_t { ZR_LIGHT_PLAIN = 0u, ZR_LIGHT_FILL = 1u, ZR_LIGHT_KEPT = 2u };
 void zr_launch_lighting(const ZrLightParams& L, const XkView* view, const uint32_t* owned_tiles, uint32_t n_owned,
                         const GBufferPtrs& G, const float* shadowmap, const CubeDesc& C, const float* lut, const float* unorm_lut,
-                        uint32_t* out, hipStream_t s);
+                        uint32_t* out, hipStream_t s, ZrLightMode mode = ZR_LIGHT_PLAIN, float4* plane = nullptr);
 // forward variant (SH/Base.frag): shades the winners recorded in G.prim with the camera pass's own parameter block
 void zr_launch_forward(const ZrPass& P, const ZrLightParams& L, const XkView* view, const ZrObject* objs, const uint32_t* owned_tiles, uint32_t n_owned,
                        const GBufferPtrs& G, const float* shadowmap, const CubeDesc& C, const float* lut, const float* unorm_lut, uint32_t* out, hipStream_t s);

@@ -83,6 +83,7 @@ def lib():
         "zr_get_frame_latencies": [vp, u32, vp],
         "zr_get_frame_periods": [vp, u32, vp],
         "zr_get_stats": [vp, C.POINTER(abi.Stats), sz],
+        "zr_get_light_keep": [vp, C.POINTER(abi.LightKeep), sz],
         "zr_read_color": [vp, vp, sz],
         "zr_read_gbuffer": [vp, C.c_int, vp, sz],
         "zr_read_shadowmap": [vp, vp, sz],
@@ -619,6 +620,14 @@ class Renderer:
                 "covered_pixels": int(s.covered_pixels), "covered_shadow_texels": int(s.covered_shadow_texels), "overflow": int(s.overflow),
                 "hiz_culled": int(s.hiz_culled), "hiz_culled_geom": int(s.hiz_culled_geom), "round1_survivors": int(s.round1_survivors),
                 "shadow_occluded": int(s.shadow_occluded), "shadow_late": int(s.shadow_late)}
+
+    def light_keep(self):
+        """What the last frame's lighting pass did with the plane of standing terms ("ignored" / "filled" / "read": zr_get_light_keep), and
+        how many frames did each so far."""
+        k = abi.LightKeep()
+        self._chk(self.L.zr_get_light_keep(self.h, C.byref(k), C.sizeof(k)))
+        return {"last": ("ignored", "filled", "read")[int(k.last)], "ignored": int(k.ignored), "filled": int(k.filled), "read": int(k.read),
+                "plane_bytes": int(k.plane_bytes)}
 
     # ---- read-back
     def color(self):
