@@ -311,7 +311,11 @@ int  zr_set_shading(zr_ctx* ctx, uint32_t mode);
  * world's override replace it) and its mip count do; anything else - the point lights, the debug view, the background, the time -
  * ends nothing, except that a frame whose empty-pixel shortcut is off (debug view 6) needs a plane filled by such a frame.  When it no
  * longer stands, the next frame that rests fills it again.  Deferred shading only; never with ZR_FLAG_NO_LIST_REUSE, never on a context
- * whose map is never kept.  zr_get_light_keep tells what the last frame did. */
+ * whose map is never kept.  zr_get_light_keep tells what the last frame did.
+ * A frame that loads them is ONE kernel launch when it has at most 64 point lights, its empty-pixel shortcut is on and its debug view
+ * is not 9: what it reads of the uniforms travels as a kernel argument, the colour of the pixels nothing was drawn to - it moves with
+ * the point lights - is computed inside the launch, and nothing is uploaded; the device copy of the uniforms is brought up to date by
+ * the next frame that reads it (zr_light_keep::read_by_arg counts such frames).  The frame is the same bit for bit. */
 int  zr_render(zr_ctx* ctx);
 /* The same frame in three stages (zr_render = all three, in this order), so that a multi-GPU host can place its
  * collectives between them: shadow pass | deferred-scene pass (cull, raster, GBuffer write) | deferred-lighting pass. */
@@ -342,6 +346,8 @@ typedef struct zr_light_keep {
     uint32_t last, _pad;         /* ZR_LIGHT_PLANE_* of the last frame */
     uint64_t ignored, filled, read;
     uint64_t plane_bytes;        /* device memory the plane takes (0: not made) */
+    uint64_t read_by_arg;        /* of `read`: the passes that were the frame's ONE launch - their uniforms kernel arguments, no upload,
+                                  * no one-pixel launch, no event wait (at most 64 point lights, the empty-pixel shortcut on, not view 9) */
 } zr_light_keep;
 int  zr_get_light_keep(zr_ctx* ctx, zr_light_keep* out, size_t bytes);
 

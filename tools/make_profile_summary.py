@@ -10,8 +10,9 @@ equals the workload it is running.
 HBM bytes, exactly as MI355X_MICROARCH.md (HBM section) prescribes: FETCH_SIZE and WRITE_SIZE come from separate --pmc passes (they
 do not fit one), are in KiB, and on gfx950 FETCH_SIZE counts 64 B per 128 B read request, i.e. half the bytes of a coalesced
 stream (calibrated on k_count_shadow: a 4 MiB dword-per-lane read reports 2056 KiB), so bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024.
-Per-frame totals = sum over every dispatch of the frame's kernels / number of frames in that run (= dispatches of k_lighting / 2: the pass and its
-one-pixel pre-launch; a frame that keeps its whole camera pass runs no k_resolve_gbuffer).
+Per-frame totals = sum over every dispatch of the frame's kernels / number of frames in that run.  Every frame has exactly one
+full-screen shading launch - k_lighting over more than its one-pixel pre-launch's grid, k_lighting_rest (a resting frame's ONE launch:
+no pre-launch, no k_frame_begin) or k_forward - and those are what is counted (the dispatch's Grid_Size tells a pre-launch apart).
 A frame that keeps its shadow map and resolves on the host's stream runs k_mark ahead of the resolve (the visibility history, on the
 camera lane): a frame kernel like the others, one launch per such frame; the GBuffer-write pass of bench.py's `roofline` counts its time
 with the resolve's (ZR_PASS_RESOLVE).
@@ -57,15 +58,20 @@ SHORT = {"k_raster_chunks<0, false>": "k_raster<GBUFFER>", "k_raster_chunks<0, t
 def short(name):
     n = name.split("(")[0].replace("void ", "").strip()
     n = SHORT.get(n, n)
-    for base in ("k_lighting", "k_resolve_gbuffer", "k_calib"):
+    for base in ("k_lighting_rest", "k_lighting", "k_resolve_gbuffer", "k_calib"):      # (k_lighting_rest first: a row of its own)
         if n.startswith(base) and base != "k_calib":
             n = base
+            break
     return n
 
 
-def n_frames(a):
-    """frames of a run: every frame lights once behind its one-pixel pre-launch (a frame that keeps its camera pass runs no resolve)"""
-    return len(a.get("k_lighting", [])) // 2 or len(a.get("k_resolve_gbuffer", [])) or 1
+ONE_PIXEL_GRID = 1024       # threads of k_lighting's one-pixel pre-launch (one tile's 1 024 pixels, a pixel per thread): not a frame
+FRAMES = defaultdict(int)   # per counter: the run's full-screen shading launches
+
+
+def n_frames(counter):
+    """frames of the run that collected `counter`: its full-screen shading launches (module docstring)"""
+    return FRAMES.get(counter, 0) or 1
 
 
 def counters(dirs):
@@ -74,7 +80,10 @@ def counters(dirs):
     for d in dirs:
         for f in glob.glob(d + "/**/*counter_collection.csv", recursive=True):
             for r in csv.DictReader(open(f)):
-                acc[r["Counter_Name"]][short(r["Kernel_Name"])].append(float(r["Counter_Value"]))
+                k = short(r["Kernel_Name"])
+                acc[r["Counter_Name"]][k].append(float(r["Counter_Value"]))
+                if k == "k_lighting_rest" or k.startswith("k_forward") or (k == "k_lighting" and int(r["Grid_Size"]) > ONE_PIXEL_GRID):
+                    FRAMES[r["Counter_Name"]] += 1
     return acc
 
 
@@ -158,10 +167,10 @@ out = {}
 for k in sorted(set(fetch) | set(write) | set(valu)):
     f, w, v = fetch.get(k, []), write.get(k, []), valu.get(k, [])
     mf, mw = (sum(f) / len(f) if f else 0.0), (sum(w) / len(w) if w else 0.0)
-    nfr = n_frames(fetch)
+    nfr = n_frames("FETCH_SIZE")
     out[k] = {"FETCH_SIZE_KiB": mf, "WRITE_SIZE_KiB": mw, "hbm_bytes_per_launch": int((2 * mf + mw) * 1024),
               "launches_per_frame": round(len(f) / nfr, 3),
-              "hbm_bytes_per_frame": int((2 * sum(f) / nfr + sum(w) / (n_frames(write))) * 1024),
+              "hbm_bytes_per_frame": int((2 * sum(f) / nfr + sum(w) / n_frames("WRITE_SIZE")) * 1024),
               "SQ_INSTS_VALU": (sum(v) / len(v) if v else None)}
     if k in issue:
         out[k]["issue"] = issue[k]
@@ -169,18 +178,21 @@ if "k_mark" in out:
     out["k_mark"]["note"] = ("the visibility history of a frame whose resolve runs on the host's stream (camera lane, ahead of ev_cam); its time is "
                              "part of ZR_PASS_RESOLVE; launches_per_frame < 1: the frames that drew their shadow map ran none")
 if "k_lighting" in out:
-    out["k_lighting"]["note"] = "two launches per frame: the full-screen pass + the one-pixel empty-colour pre-launch (the means are over both)"
+    out["k_lighting"]["note"] = ("the full-screen pass of the frames that draw, fill or fall back, and the one-pixel empty-colour pre-launch of each of "
+                                 "them (the means are over both); a resting frame's one launch is the row k_lighting_rest")
+if "k_lighting_rest" in out:
+    out["k_lighting_rest"]["note"] = "a resting frame's ONE launch: no pre-launch and no k_frame_begin beside it (launches_per_frame: the share of resting frames)"
 
 
-def per_frame(a, scale):
-    frames = n_frames(a)
+def per_frame(counter, scale):
+    a, frames = acc.get(counter, {}), n_frames(counter)
     return sum(sum(v) for k, v in a.items() if is_frame_kernel(k)) * scale / frames, frames
 
 
-fb, nf = per_frame(fetch, 2048.0)
-wb, nw = per_frame(write, 1024.0)
-vi, nv = per_frame(valu, 1.0)
-va, _ = per_frame(acc.get("SQ_ACTIVE_INST_VALU", {}), 1.0)
+fb, nf = per_frame("FETCH_SIZE", 2048.0)
+wb, nw = per_frame("WRITE_SIZE", 1024.0)
+vi, nv = per_frame("SQ_INSTS_VALU", 1.0)
+va, _ = per_frame("SQ_ACTIVE_INST_VALU", 1.0)
 summary = {"tag": tag, "workload": bench["config"]["workload"], "lib_sha16": bench["config"].get("lib_sha16"), "bench_value_under_rocprof": bench["value"],
            "frames": {"fetch_pass": nf, "write_pass": nw, "sq_pass": nv},
            "hbm_bytes_per_frame": int(fb + wb), "valu_insts_per_frame": int(vi), "valu_active_quads_per_frame": int(va), "kernels": out,

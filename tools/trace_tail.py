@@ -17,8 +17,14 @@ def short(n):
     return n.split("(")[0].replace("void ", "").strip()
 
 
-# a frame starts at k_frame_begin
-starts = [i for i, r in enumerate(rows) if short(r["Kernel_Name"]) == "k_frame_begin"]
+# a frame starts at k_frame_begin - or, where the last frames have none (a resting frame is ONE launch, k_lighting_rest), at that launch
+def anchors(name):
+    return [i for i, r in enumerate(rows) if short(r["Kernel_Name"]).startswith(name)]
+
+
+starts = anchors("k_frame_begin")
+if anchors("k_lighting_rest") and (not starts or anchors("k_lighting_rest")[-1] > starts[-1] + 8):
+    starts = anchors("k_lighting_rest")
 starts = starts[-frames - 1:]
 acc = defaultdict(lambda: [0.0, 0.0, 0])
 order = []
@@ -26,7 +32,7 @@ for a, b in zip(starts[:-1], starts[1:]):
     for j in range(a, b):
         key = (j - a, short(rows[j]["Kernel_Name"]))
         dur = (int(rows[j]["End_Timestamp"]) - int(rows[j]["Start_Timestamp"])) / 1e3
-        gap = (int(rows[j]["Start_Timestamp"]) - int(rows[j - 1]["End_Timestamp"])) / 1e3 if j > a else 0.0
+        gap = (int(rows[j]["Start_Timestamp"]) - int(rows[j - 1]["End_Timestamp"])) / 1e3 if j > 0 else 0.0      # (a frame's first: to the frame before)
         if key not in acc:
             order.append(key)
         acc[key][0] += dur; acc[key][1] += gap; acc[key][2] += 1

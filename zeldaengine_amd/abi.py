@@ -89,7 +89,7 @@ class Stats(C.Structure):
 class LightKeep(C.Structure):
     """ctypes mirror of zr_light_keep: what the lighting passes did with the plane of standing terms (passed with its size, like zr_stats)"""
     _fields_ = [("last", C.c_uint32), ("_pad", C.c_uint32), ("ignored", C.c_uint64), ("filled", C.c_uint64), ("read", C.c_uint64),
-                ("plane_bytes", C.c_uint64)]
+                ("plane_bytes", C.c_uint64), ("read_by_arg", C.c_uint64)]
 
 
 LIGHT_PLANE_IGNORED, LIGHT_PLANE_FILLED, LIGHT_PLANE_READ = 0, 1, 2      # ZR_LIGHT_PLANE_*: LightKeep.last

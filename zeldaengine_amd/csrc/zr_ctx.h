@@ -348,7 +348,10 @@ struct zr_ctx {
         float SB[16], cam[3]; uint32_t SD, n_dir, max_mips, cube_dim, cube_levels, debug_skip;
         XkLight dir[XK_MAX_DIRECTIONAL_LIGHTS_NUM];
     };
-    struct LightKeep { float4* plane = nullptr; bool alloc_failed = false; LightKey now = {}, key = {}; uint32_t last = 0; uint64_t count[3] = { 0, 0, 0 }; } lk;
+    // rest: the fill's slot and records (ZrRestRecord, zr_types.h), made with the plane in an allocation of their own (null: no room - the
+    // context keeps, but never in one launch); by_arg: the passes that ran as the one launch (ZrFramePlan::light_args).
+    struct LightKeep { float4* plane = nullptr; float4* rest = nullptr; bool alloc_failed = false; LightKey now = {}, key = {}; uint32_t last = 0;
+                       uint64_t count[3] = { 0, 0, 0 }, by_arg = 0; } lk;
     float lut[256]; float* d_lut = nullptr;
     float* d_unorm_lut = nullptr;        // [0..255] = c / 255, [256..1279] = c / 1023 (IEEE quotients, computed on the host)
 
@@ -463,6 +466,9 @@ static inline int timed_events(zr_ctx* c, hipStream_t s, std::initializer_list<i
 // The current shadow map: during a drawn shadow pass the one being drawn, else the one the last drawn pass left (zr_ctx::smap).
 static inline float* shadow_buf(zr_ctx* c) { return c->d_shadow_ext ? c->d_shadow_ext : c->fc[c->smap].shadow; }
 int set_winner_planes(zr_ctx* c, bool forward, bool id_capture, const char* what);      // zr_set_shading, zr_set_id_capture
+// The frame's device copy of XkView brought up to date on s, and the camera lane's statistics zeroed where the plan says so (frame_begin;
+// lighting_pass, for a frame planned as one launch that turns out to read XkView after all).
+int zr_frame_uniforms(zr_ctx* c, hipStream_t s, bool reset_stats, bool reset_camera_list);
 // zr_lighting_host.cpp: the lighting stage
 void zr_light_facts(zr_ctx* c, ZrFrameFacts* f);       // frame_begin: what the plan reads about the plane
 bool zr_light_plane_make(zr_ctx* c);                   // frame_begin, a frame planned to fill: the plane exists (false: it cannot, ever)

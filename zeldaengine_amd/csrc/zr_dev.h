@@ -366,6 +366,17 @@ __device__ __forceinline__ bool hiz_occluded(const ZrHiz& Z, uint2 pr, float zmi
 #ifndef ZR_LIGHT_KEPT_WAVES
 #define ZR_LIGHT_KEPT_WAVES 8
 #endif
+// What k_lighting_rest takes from the fill's records instead of the GBuffer, each switchable for A/B ("The resting
+// frame in one launch", has each measured on its own): the tile light list's box (0: every workgroup rebuilds it from its pixels'
+// scene_color and gD, wave reductions and an LDS merge, as k_lighting does), the empty pixels' GBuffer words left unfetched (0: every
+// pixel fetches its 24 bytes and finds itself empty again).  (Leaving the sRGB table out where no background is sampled was the third:
+// it showed in no counter and not in the frame rate, and was taken out again - App. A.)
+#ifndef ZR_REST_BOX_FROM_RECORDS
+#define ZR_REST_BOX_FROM_RECORDS 1
+#endif
+#ifndef ZR_REST_SKIP_EMPTY_LOADS
+#define ZR_REST_SKIP_EMPTY_LOADS 1
+#endif
 #ifndef ZR_PIXELS_PER_THREAD
 #define ZR_PIXELS_PER_THREAD 1     // of k_resolve_gbuffer and k_lighting: 1, 2 or 4 (a tile is 1 024 pixels; workgroups per tile follow)
 #endif

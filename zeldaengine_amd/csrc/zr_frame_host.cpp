@@ -349,6 +349,24 @@ static int frame_begin(zr_ctx* c, ZrEntry entry)
         T->kept = p.shadow_keep; T->kept_round2 = p.rounds == ZR_ROUNDS_TWO_KEPT; T->kept_camera = p.camera_keep; T->moved = p.resolve_deferred;
     }
     if (c->view_dirty) { c->view_version++; c->view_dirty = false; }
+    if (p.light_args) {
+        // One launch: its uniforms travel as arguments.  No ring slot, no upload, no k_frame_begin - and F.view_uploaded stays as it is: the
+        // next frame that reads F.view finds it stale and uploads.  The ring's slots paced the host to VIEW_RING frames ahead of the
+        // device; without them that bound is kept by hand.
+#ifdef ZR_AB_REST_EV_END_EVERY      // A/B ONLY: the last recorded event at least VIEW_RING frames back
+        if (c->frame_no >= 2u * ZR_AB_REST_EV_END_EVERY + zr_ctx::VIEW_RING)
+            HIPCHK(c, hipEventSynchronize(c->ev_end[((c->frame_no - zr_ctx::VIEW_RING) / ZR_AB_REST_EV_END_EVERY * ZR_AB_REST_EV_END_EVERY) % zr_ctx::END_RING]));
+        return ZR_OK;
+#endif
+        if (c->frame_no >= (uint64_t)zr_ctx::VIEW_RING) HIPCHK(c, hipEventSynchronize(c->ev_end[(c->frame_no - zr_ctx::VIEW_RING) % zr_ctx::END_RING]));
+        return ZR_OK;
+    }
+    return zr_frame_uniforms(c, s, p.reset_stats, p.reset_camera_list);
+}
+
+int zr_frame_uniforms(zr_ctx* c, hipStream_t s, bool reset_stats, bool reset_camera_list)
+{
+    FrameCopy& F = c->fc[c->fcur];
     const XkView* src = nullptr;
     uint32_t k = 0;
     if (F.view_uploaded != c->view_version) {        // pinned ring slot: reused only after the kernel that read it last has run
@@ -361,7 +379,7 @@ static int frame_begin(zr_ctx* c, ZrEntry entry)
     // XkView.  The SHADOW list's length lives in the shadow pipeline's block and is reset on that pipeline's own stream (shadow_pass):
     // the previous frame's shadow pipeline may still be walking it while this kernel runs on the camera lane.
     // (a frame that keeps its camera pass keeps that pass's statistics: an upload, or nothing)
-    if (p.reset_stats || src) zr_launch_frame_begin(p.reset_stats ? c->d_stats : nullptr, src, F.view, p.reset_camera_list ? 2u : 0u, s);
+    if (reset_stats || src) zr_launch_frame_begin(reset_stats ? c->d_stats : nullptr, src, F.view, reset_camera_list ? 2u : 0u, s);
     if (src) { HIPCHK(c, hipEventRecord(c->view_ev[k], s)); F.view_uploaded = c->view_version; }
     return ZR_OK;
 }

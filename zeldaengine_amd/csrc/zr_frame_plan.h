@@ -68,6 +68,10 @@ struct ZrFrameFacts {
     // lighting pass takes the empty-pixel shortcut (off: debug view 6, a diagnostic switch), and those pixels touch no plane.
     bool light_plane_ok = false, light_uniforms_same = false, light_empty_px = true;
     uint64_t cube_gen = 0;
+    // A frame that reads the plane can be ONE launch (ZrFramePlan::light_args): at most ZR_REST_ARG_LIGHTS point lights, the empty-pixel
+    // shortcut on, the fill's records and slot exist, and nothing behind the pass reads XkView (debug view 9 does).
+    // light_slot: the context has (or, with its first fill, gets) the slot a fill's one-pixel launch writes for such frames.
+    bool light_by_arg = false, light_slot = false;
 };
 
 // What the frames enqueued so far left behind, and nothing else.  (The ZrPass keys that go with it - smap_key, cam_prev_key, list_key[] -
@@ -117,6 +121,10 @@ struct ZrFramePlan {
     // lighting pass: the standing terms of every pixel are read from the plane / computed as ever and stored into it (neither: the pass
     // ignores the plane)
     bool light_keep = false, light_fill = false;
+    // light_args: a pass that reads the plane takes its moving uniforms as kernel arguments and computes the empty pixel's colour itself
+    // (k_lighting_rest).  The frame is that one launch on the host's stream: no uniform upload, no one-pixel launch, no event, nothing on
+    // the lane.  The device copy of XkView stays as stale as it was: the next frame that reads it uploads it.
+    bool light_args = false;
 };
 
 static inline ZrFramePlan zr_frame_plan(const ZrFrameFacts& f, const ZrFrameCarry& k)
@@ -196,14 +204,35 @@ static inline ZrFramePlan zr_frame_plan(const ZrFrameFacts& f, const ZrFrameCarr
     p.resolve_deferred = !p.camera_keep && lanes && render && p.shadow_keep && !f.sky;
     p.resolve = p.camera_keep ? ZR_LANE_NONE : p.resolve_deferred ? ZR_LANE_HOST : p.camera;
 
+    // The lighting pass keeps, per pixel, what the moving point lights do not feed: ShadowFactor, Direct over the directional lights, RefC.
+    // Their inputs are the pixel's GBuffer values, the shadow map, and a few hundred bytes of uniforms plus the cubemap.  A frame that keeps
+    // its camera pass lights a GBuffer copy that is, bit for bit, every other copy of the same run (g_gen); a frame that keeps its map
+    // lights from the map of one drawing frame (smap_frame; never a caller-owned or partitioned map: those are drawn every frame).  When
+    // the plane was filled from that run, that map, these uniforms and this cubemap, the pass reads it; when the frame rests but the plane
+    // does not match, the pass fills it - a resting frame by definition, so the moving-camera and moving-light loops never pay the stores.
+    // The plane holds what a fill wrote: with the empty-pixel shortcut on, not the pixels that took it, and those are the same pixels on
+    // every frame of the run - but a frame whose shortcut is off reads every pixel, and needs a fill that wrote them all.  All lighting
+    // passes of a context run in order on the host's stream (p.lighting), so one plane serves the frames in flight.  Deferred shading
+    // only; never with ZR_FLAG_NO_LIST_REUSE, as above.
+    const bool light_rest = f.light_plane_ok && !(f.flags & ZRP_NO_LIST_REUSE) && f.shading != ZRP_SHADING_FORWARD && p.camera_keep && p.shadow_keep;
+    const bool light_match = k.light_valid && k.light_g_gen == p.g_gen && k.light_smap_frame == k.smap_frame && f.light_uniforms_same &&
+                             k.light_cube_gen == f.cube_gen && (k.light_all_px || f.light_empty_px);
+    p.light_keep = light_rest && light_match; p.light_fill = light_rest && !light_match;
+    p.light_args = p.light_keep && f.light_by_arg;
+
     // The head of a frame that keeps its camera pass has nothing to reset and runs where the frame is lit - or, where zr_render keeps the
     // map too (ZR_KEPT_HEAD_ON_LANE), on the idle lane, one-pixel launch included.  That launch reads the map, and the lane has waited for
     // the end of frame_no - 2 only: the map must have been drawn by that frame or an earlier one (a map drawn by the frame before, on the
     // host's stream, is behind nothing the lane has waited for).
-    const bool head_on_lane = kZrKeptHeadOnLane && p.camera_keep && render && p.shadow_keep && lanes && k.smap_frame + 2 <= f.frame_no;
+    // A frame that is one launch (light_args) has no head at all: nothing to upload, nothing to launch ahead of the pass.  A frame that
+    // fills the plane of a context with a slot (light_slot) fills the slot from its one-pixel launch, and the lighting pass of the frame
+    // before may still be reading it: its head stays on the host's stream, behind that pass (one frame per rest).  A context without a
+    // slot fills as it always did, head on the lane.
+    const bool head_on_lane = kZrKeptHeadOnLane && p.camera_keep && render && p.shadow_keep && lanes && k.smap_frame + 2 <= f.frame_no &&
+                              !p.light_args && !(p.light_fill && f.light_slot);
     p.head = p.camera_keep ? (head_on_lane ? ZR_LANE_CAM : ZR_LANE_HOST) : p.camera;
     // (the forward variant has no one-pixel launch: an empty pixel is the clear colour)
-    p.one_pixel = f.shading == ZRP_SHADING_FORWARD ? ZR_LANE_NONE : head_on_lane ? ZR_LANE_CAM : ZR_LANE_HOST;
+    p.one_pixel = f.shading == ZRP_SHADING_FORWARD || p.light_args ? ZR_LANE_NONE : head_on_lane ? ZR_LANE_CAM : ZR_LANE_HOST;
 
     // Waits at the head.  On the lane: this frame's copies of the double-buffered resources were last used two frames ago, on the host's
     // stream (read by the lighting pass, and before it the keys reset and the GBuffer written by the resolve where that ran there).
@@ -229,20 +258,6 @@ static inline ZrFramePlan zr_frame_plan(const ZrFrameFacts& f, const ZrFrameCarr
     // ev_join (zr_stream_wait_shadow: a host that puts a collective behind the shadow pass): not in zr_render's own two-lane frames
     p.ev_join = !(lanes && render);
 
-    // The lighting pass keeps, per pixel, what the moving point lights do not feed: ShadowFactor, Direct over the directional lights, RefC.
-    // Their inputs are the pixel's GBuffer values, the shadow map, and a few hundred bytes of uniforms plus the cubemap.  A frame that keeps
-    // its camera pass lights a GBuffer copy that is, bit for bit, every other copy of the same run (g_gen); a frame that keeps its map
-    // lights from the map of one drawing frame (smap_frame; never a caller-owned or partitioned map: those are drawn every frame).  When
-    // the plane was filled from that run, that map, these uniforms and this cubemap, the pass reads it; when the frame rests but the plane
-    // does not match, the pass fills it - a resting frame by definition, so the moving-camera and moving-light loops never pay the stores.
-    // The plane holds what a fill wrote: with the empty-pixel shortcut on, not the pixels that took it, and those are the same pixels on
-    // every frame of the run - but a frame whose shortcut is off reads every pixel, and needs a fill that wrote them all.  All lighting
-    // passes of a context run in order on the host's stream (p.lighting), so one plane serves the frames in flight.  Deferred shading
-    // only; never with ZR_FLAG_NO_LIST_REUSE, as above.
-    const bool light_rest = f.light_plane_ok && !(f.flags & ZRP_NO_LIST_REUSE) && f.shading != ZRP_SHADING_FORWARD && p.camera_keep && p.shadow_keep;
-    const bool light_match = k.light_valid && k.light_g_gen == p.g_gen && k.light_smap_frame == k.smap_frame && f.light_uniforms_same &&
-                             k.light_cube_gen == f.cube_gen && (k.light_all_px || f.light_empty_px);
-    p.light_keep = light_rest && light_match; p.light_fill = light_rest && !light_match;
     return p;
 }
 

@@ -4,6 +4,74 @@
 #include "zr_surface.h"
 #include "zr_shade.h"
 
+// A pixel nothing was drawn to: every target's clear value (ZE:3427-3433)
+__device__ __forceinline__ bool light_pixel_empty(uint32_t sc, uint32_t A, uint32_t B, uint32_t Cc, uint2 D)
+{
+    return sc == 0xFF000000u && A == 0u && B == 0xFF000000u && Cc == 0xFF000000u && D.x == 0u && D.y == 0x3C000000u;
+}
+
+// The per-pixel steps k_lighting and k_lighting_rest share.  light_decode: the GBuffer's words as the shader's inputs (u8 / u10: the LDS
+// copies of c / 255 and c / 1023).  light_compose: FinalColor, gamma, the debug-view switch, packed RGBA8.  light_emit: what every path
+// ends with - the skydome / background drawn over the lit quad in view 0 (ZE:3681-3699), then the store (tl: tex_decode's LDS table).
+struct LitPixel { zf3 BaseColor, Normal, N, Pw; float Metallic, Roughness, AO, Mask; };
+__device__ __forceinline__ LitPixel light_decode(const float* u8, const float* u10, uint32_t sc, uint32_t A, uint32_t B, uint32_t Cc, uint2 D)
+{
+    LitPixel q;
+    q.BaseColor = zr3(u8[Cc & 255u], u8[(Cc >> 8) & 255u], u8[(Cc >> 16) & 255u]);
+    q.Metallic = zr_saturate(u8[B & 255u]);
+    q.Roughness = zr_saturate(u8[(B >> 16) & 255u]);
+    q.Normal = zr3(__builtin_fmaf(u10[(A >> 20) & 1023u], 2.0f, -1.0f), __builtin_fmaf(u10[(A >> 10) & 1023u], 2.0f, -1.0f),
+                   __builtin_fmaf(u10[A & 1023u], 2.0f, -1.0f));
+    q.AO = zr_saturate(u8[Cc >> 24]);
+    q.Mask = u8[sc >> 24];
+    q.Roughness = __builtin_fmaxf(0.01f, q.Roughness);
+    q.N = zr_normalize(q.Normal);
+    q.Pw = zr3(f16_to_f32_hw(D.x & 0xFFFFu), f16_to_f32_hw(D.x >> 16), f16_to_f32_hw(D.y & 0xFFFFu));
+    return q;
+}
+__device__ __forceinline__ uint32_t light_compose(const ZrLightParams& L, const LitPixel& q, zf3 Direct, zf3 Indirect, zf3 RefC, float ShadowFactor, int px, int py)
+{
+    zf3 Final = ((Direct + Indirect) + RefC) * q.Mask;
+    Final = zr3(zr_pow(Final.x, 0.4545f), zr_pow(Final.y, 0.4545f), zr_pow(Final.z, 0.4545f));
+    zf3 o;
+    switch (L.debug_view) {
+    case 0: o = Final; break;
+    case 1: o = zr3(zr_pow(q.BaseColor.x, 0.4545f), zr_pow(q.BaseColor.y, 0.4545f), zr_pow(q.BaseColor.z, 0.4545f)); break;
+    case 2: o = zr3(q.Metallic, q.Metallic, q.Metallic); break;
+    case 3: o = zr3(q.Roughness, q.Roughness, q.Roughness); break;
+    case 4: o = q.Normal; break;
+    case 5: o = zr3(q.AO, q.AO, q.AO); break;
+    case 7: o = RefC; break;
+    case 8: o = zr3(ShadowFactor, ShadowFactor, ShadowFactor); break;
+    case 9: o = Final; break;       // GBufferVis: k_gbuffer_vis then overwrites the eight mosaic cells
+    case 6: {   // fragColor of the full-screen quad: Background.vert:10-17 vertex colours over its two triangles
+        const float u = ((float)px + 0.5f) / (float)L.W, v = ((float)py + 0.5f) / (float)L.H;
+        o = v >= u ? zr3(1.0f - v, u, v - u) : zr3(1.0f - u, v, u - v);
+        break;
+    }
+    default: o = Final * ShadowFactor; break;
+    }
+    return zr_unorm(o.x, 255.0f) | zr_unorm(o.y, 255.0f) << 8 | zr_unorm(o.z, 255.0f) << 16 | 255u << 24;
+}
+template <bool BACKGROUND>
+__device__ __forceinline__ void light_emit(const ZrLightParams& L, const GBufferPtrs& G, const float* tl, uint32_t* __restrict__ out, uint32_t rgba,
+                                           int px, int py, size_t p, uint32_t tile_slot, uint32_t i)
+{
+    if (L.debug_view == 0u) {
+        const uint32_t ov = L.has_overlay ? G.overlay[p] : 0u;
+        if (ov) rgba = ov;
+        else if (BACKGROUND && L.bg_enabled && 1.0f <= G.depth[p]) {
+            const float u = ((float)px + 0.5f) / (float)L.W, v = ((float)py + 0.5f) / (float)L.H;
+            const float one4[4] = { 1.0f, 1.0f, 1.0f, 1.0f };
+            const zf4 bgc = tex_sample<2>(L.bg, one4, true, tl, u, v, 1.0f / (float)L.W, 0.0f, 0.0f, 1.0f / (float)L.H);
+            rgba = zr_unorm(zr_pow(bgc.x, 0.4545f), 255.0f) | zr_unorm(zr_pow(bgc.y, 0.4545f), 255.0f) << 8 |
+                   zr_unorm(zr_pow(bgc.z, 0.4545f), 255.0f) << 16 | 255u << 24;
+        }
+    }
+    if (L.packed_out) out[(size_t)tile_slot * TILE_PIX + i] = rgba;
+    else out[p] = rgba;
+}
+
 // BaseLighting.frag:147-254 for every pixel of the owned tiles (the full-screen quad of ZE:3531-3540)
 // MODE (ZrLightMode): FILL also stores the pixel's standing terms - Direct after the directional lights, ShadowFactor, RefC, exact fp32 - into
 // the context's plane; KEPT loads them instead of running shade_standing (no PCF, no directional BxDF, no cubemap) and goes on as ever: the
@@ -19,7 +87,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(MODE == ZR_L
                                                   const uint32_t* __restrict__ owned_tiles, GBufferPtrs G,
                                                   const float* __restrict__ shadowmap, CubeDesc C,
                                                   const float* __restrict__ srgb_lut, const float* __restrict__ unorm_lut,
-                                                  uint32_t* __restrict__ out, float4* __restrict__ plane)
+                                                  uint32_t* __restrict__ out, float4* __restrict__ plane, float4* __restrict__ rest)
 {
     // UNORM loads are IEEE quotients c / 255 and c / 1023: 14 per pixel, served from an LDS copy of the host-built table
     __shared__ float tl[512];            // [0, 256) sRGB decode (24 cubemap fetches per pixel), [256, 512) c / 255: tex_decode's layout
@@ -49,13 +117,19 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(MODE == ZR_L
     __shared__ float bbp[LIGHT_LIST ? WAVES : 1][6];
     __shared__ uint32_t lmask[LIGHT_LIST ? XK_MAX_POINT_LIGHTS_NUM / 32 : 1];
     constexpr bool use_mask = LIGHT_LIST;
-    if constexpr (LIGHT_LIST) {
+    // The fill also records, per wave (one pixel per thread: 64 consecutive pixels of the tile), that box and which of its pixels hold every
+    // target's clear value (ZrRestRecord): the GBuffer stands for the whole rest, and the resting frame's launch (k_lighting_rest) reads
+    // the records instead of the GBuffer.
+    constexpr bool RECORDS = MODE == ZR_LIGHT_FILL && PPT == 1;
+    if constexpr (LIGHT_LIST || RECORDS) {
         float lo[3] = { __builtin_inff(), __builtin_inff(), __builtin_inff() }, hi[3] = { -__builtin_inff(), -__builtin_inff(), -__builtin_inff() };
         bool odd = false;                    // a non-finite position: keep every light
+        bool empty = false;
         for (uint32_t i = tid; i < TILE_PIX; i += T) {
             const int px = tx0 + (int)(i & (TILE - 1)), py = ty0 + (int)(i / TILE);
             if (px >= (int)L.W || py >= (int)L.H) continue;
             const size_t p = (size_t)py * L.W + (size_t)px;
+            if constexpr (RECORDS) empty = light_pixel_empty(G.scene_color[p], G.gA[p], G.gB[p], G.gC[p], G.gD[p]);
             if ((G.scene_color[p] >> 24) == 0u) continue;
             const uint2 D = G.gD[p];
             const float q[3] = { f16_to_f32_hw(D.x & 0xFFFFu), f16_to_f32_hw(D.x >> 16), f16_to_f32_hw(D.y & 0xFFFFu) };
@@ -66,34 +140,31 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(MODE == ZR_L
         }
         for (int a = 0; a < 3; ++a) { lo[a] = wave_fmin(lo[a]); hi[a] = wave_fmax(hi[a]); }
         const bool wodd = __ballot(odd) != 0ull;
-        if ((threadIdx.x & 63u) == 0u) {
-            float* o = bbp[threadIdx.x >> 6];
-            o[0] = wodd ? -__builtin_inff() : lo[0]; o[1] = wodd ? -__builtin_inff() : lo[1]; o[2] = wodd ? -__builtin_inff() : lo[2];
-            o[3] = wodd ? __builtin_inff() : hi[0]; o[4] = wodd ? __builtin_inff() : hi[1]; o[5] = wodd ? __builtin_inff() : hi[2];
-        }
-        for (uint32_t i = threadIdx.x; i < XK_MAX_POINT_LIGHTS_NUM / 32; i += (uint32_t)TB) lmask[i] = 0u;
-        __syncthreads();
-        float blo[3], bhi[3];
-        for (int a = 0; a < 3; ++a) {
-            blo[a] = bbp[0][a]; bhi[a] = bbp[0][3 + a];
-            for (uint32_t w = 1; w < WAVES; ++w) { blo[a] = __builtin_fminf(blo[a], bbp[w][a]); bhi[a] = __builtin_fmaxf(bhi[a], bbp[w][3 + a]); }
-        }
-        for (uint32_t li = threadIdx.x; li < nPoint; li += (uint32_t)TB) {
-            const XkLight* __restrict__ Lt = &view->PointLights[li];
-            const bool lfinite = __builtin_fabsf(Lt->Color[0]) <= 3.402823466e38f && __builtin_fabsf(Lt->Color[1]) <= 3.402823466e38f &&
-                                 __builtin_fabsf(Lt->Color[2]) <= 3.402823466e38f && __builtin_fabsf(Lt->Color[3]) <= 3.402823466e38f;
-            const float falloff = Lt->Direction[3];
-            bool keep = true;
-            if (lfinite && falloff > 0.0f) {
-                zf3 e;      // per axis: how far the light lies outside the box (0 inside); |lp - P| is at least that for every P in it
-                e.x = __builtin_fmaxf(0.0f, __builtin_fmaxf(blo[0] - Lt->Position[0], Lt->Position[0] - bhi[0]));
-                e.y = __builtin_fmaxf(0.0f, __builtin_fmaxf(blo[1] - Lt->Position[1], Lt->Position[1] - bhi[1]));
-                e.z = __builtin_fmaxf(0.0f, __builtin_fmaxf(blo[2] - Lt->Position[2], Lt->Position[2] - bhi[2]));
-                if (zr_dot(e, e) > (falloff * falloff) * 1.000001f) keep = false;
+        if constexpr (RECORDS) {
+            const unsigned long long em = __ballot(empty);
+            if (rest != nullptr && (threadIdx.x & 63u) == 0u) {
+                ZrRestRecord* r = (ZrRestRecord*)(rest + ZR_REST_SLOT) + ((size_t)tile_slot * ZR_REST_RECORDS_PER_TILE + (tid >> 6));
+                for (int a = 0; a < 3; ++a) { r->lo[a] = wodd ? -__builtin_inff() : lo[a]; r->hi[a] = wodd ? __builtin_inff() : hi[a]; }
+                r->empty[0] = (uint32_t)em; r->empty[1] = (uint32_t)(em >> 32);
             }
-            if (keep) atomicOr(&lmask[li >> 5], 1u << (li & 31u));
         }
-        __syncthreads();
+        if constexpr (LIGHT_LIST) {
+            if ((threadIdx.x & 63u) == 0u) {
+                float* o = bbp[threadIdx.x >> 6];
+                o[0] = wodd ? -__builtin_inff() : lo[0]; o[1] = wodd ? -__builtin_inff() : lo[1]; o[2] = wodd ? -__builtin_inff() : lo[2];
+                o[3] = wodd ? __builtin_inff() : hi[0]; o[4] = wodd ? __builtin_inff() : hi[1]; o[5] = wodd ? __builtin_inff() : hi[2];
+            }
+            for (uint32_t i = threadIdx.x; i < XK_MAX_POINT_LIGHTS_NUM / 32; i += (uint32_t)TB) lmask[i] = 0u;
+            __syncthreads();
+            float blo[3], bhi[3];
+            for (int a = 0; a < 3; ++a) {
+                blo[a] = bbp[0][a]; bhi[a] = bbp[0][3 + a];
+                for (uint32_t w = 1; w < WAVES; ++w) { blo[a] = __builtin_fminf(blo[a], bbp[w][a]); bhi[a] = __builtin_fmaxf(bhi[a], bbp[w][3 + a]); }
+            }
+            for (uint32_t li = threadIdx.x; li < nPoint; li += (uint32_t)TB)
+                if (light_listed(ViewLight{ &view->PointLights[li] }, blo, bhi)) atomicOr(&lmask[li >> 5], 1u << (li & 31u));
+            __syncthreads();
+        }
     }
 
     for (uint32_t i = tid; i < TILE_PIX; i += T) {
@@ -102,6 +173,9 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(MODE == ZR_L
         const size_t p = (size_t)py * L.W + (size_t)px;
         const uint32_t sc = G.scene_color[p], A = G.gA[p], B = G.gB[p], Cc = G.gC[p];
         const uint2 D = G.gD[p];
+        // A pixel nothing was drawn to holds the clear values of every target (ZE:3427-3433), so the shader computes the same
+        // colour for all of them: it was computed once (zr_launch_lighting's one-pixel pre-launch of this very kernel).
+        // (light_pixel_empty() spelt out: as a call behind the null test it changes the plain instantiations' code)
         // what every path ends with: the skydome / background drawn over the lit quad in view 0 (ZE:3681-3699), then the store
         auto emit = [&](uint32_t rgba) {
             if (L.debug_view == 0u) {
@@ -118,61 +192,134 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(MODE == ZR_L
             if (L.packed_out) out[(size_t)tile_slot * TILE_PIX + i] = rgba;
             else out[p] = rgba;
         };
-        // A pixel nothing was drawn to holds the clear values of every target (ZE:3427-3433), so the shader computes the same
-        // colour for all of them: it was computed once (zr_launch_lighting's one-pixel pre-launch of this very kernel).
         if (L.empty_rgba != nullptr && sc == 0xFF000000u && A == 0u && B == 0xFF000000u && Cc == 0xFF000000u && D.x == 0u && D.y == 0x3C000000u) {
             emit(*L.empty_rgba);
             continue;
         }
-        const zf3 BaseColor = zr3(u8[Cc & 255u], u8[(Cc >> 8) & 255u], u8[(Cc >> 16) & 255u]);
-        const float Metallic = zr_saturate(u8[B & 255u]);
-        float Roughness = zr_saturate(u8[(B >> 16) & 255u]);
-        const zf3 Normal = zr3(__builtin_fmaf(u10[(A >> 20) & 1023u], 2.0f, -1.0f), __builtin_fmaf(u10[(A >> 10) & 1023u], 2.0f, -1.0f),
-                               __builtin_fmaf(u10[A & 1023u], 2.0f, -1.0f));
-        const float AO = zr_saturate(u8[Cc >> 24]);
-        const float Mask = u8[sc >> 24];
-        Roughness = __builtin_fmaxf(0.01f, Roughness);
-        const zf3 N = zr_normalize(Normal);
-        const zf3 Pw = zr3(f16_to_f32_hw(D.x & 0xFFFFu), f16_to_f32_hw(D.x >> 16), f16_to_f32_hw(D.y & 0xFFFFu));
+        const LitPixel q = light_decode(u8, u10, sc, A, B, Cc, D);
         zf3 Direct, Indirect, RefC; float ShadowFactor;
         if constexpr (MODE == ZR_LIGHT_KEPT) {      // the standing terms as the fill stored them: two 16-byte loads
             const float4 ka = plane[p], kb = plane[(size_t)L.W * L.H + p];
             Direct = zr3(ka.x, ka.y, ka.z); ShadowFactor = ka.w; RefC = zr3(kb.x, kb.y, kb.z);
-            shade_points<use_mask>(L, view, lmask, nDir, nPoint, cam, BaseColor, Metallic, Roughness, N, Pw, Direct);
-            Indirect = shade_indirect(BaseColor, Metallic, AO, ShadowFactor);
+            shade_points<use_mask>(L, view, lmask, nDir, nPoint, cam, q.BaseColor, q.Metallic, q.Roughness, q.N, q.Pw, Direct);
+            Indirect = shade_indirect(q.BaseColor, q.Metallic, q.AO, ShadowFactor);
         } else if constexpr (MODE == ZR_LIGHT_FILL) {
-            shade_standing(L, view, shadowmap, C, slut, nDir, maxmips, dxy, cam, BaseColor, Metallic, Roughness, N, AO, Pw, Direct, RefC, ShadowFactor);
+            shade_standing(L, view, shadowmap, C, slut, nDir, maxmips, dxy, cam, q.BaseColor, q.Metallic, q.Roughness, q.N, q.AO, q.Pw, Direct, RefC, ShadowFactor);
             plane[p] = make_float4(Direct.x, Direct.y, Direct.z, ShadowFactor);
             plane[(size_t)L.W * L.H + p] = make_float4(RefC.x, RefC.y, RefC.z, 0.0f);
-            shade_points<use_mask>(L, view, lmask, nDir, nPoint, cam, BaseColor, Metallic, Roughness, N, Pw, Direct);
-            Indirect = shade_indirect(BaseColor, Metallic, AO, ShadowFactor);
+            shade_points<use_mask>(L, view, lmask, nDir, nPoint, cam, q.BaseColor, q.Metallic, q.Roughness, q.N, q.Pw, Direct);
+            Indirect = shade_indirect(q.BaseColor, q.Metallic, q.AO, ShadowFactor);
         } else
-            shade_surface<use_mask>(L, view, shadowmap, C, slut, lmask, nDir, nPoint, maxmips, dxy, cam, BaseColor, Metallic, Roughness, N, AO, Pw,
+            shade_surface<use_mask>(L, view, shadowmap, C, slut, lmask, nDir, nPoint, maxmips, dxy, cam, q.BaseColor, q.Metallic, q.Roughness, q.N, q.AO, q.Pw,
                                     Direct, Indirect, RefC, ShadowFactor);
-
-        zf3 Final = ((Direct + Indirect) + RefC) * Mask;
-        Final = zr3(zr_pow(Final.x, 0.4545f), zr_pow(Final.y, 0.4545f), zr_pow(Final.z, 0.4545f));
-        zf3 o;
-        switch (L.debug_view) {
-        case 0: o = Final; break;
-        case 1: o = zr3(zr_pow(BaseColor.x, 0.4545f), zr_pow(BaseColor.y, 0.4545f), zr_pow(BaseColor.z, 0.4545f)); break;
-        case 2: o = zr3(Metallic, Metallic, Metallic); break;
-        case 3: o = zr3(Roughness, Roughness, Roughness); break;
-        case 4: o = Normal; break;
-        case 5: o = zr3(AO, AO, AO); break;
-        case 7: o = RefC; break;
-        case 8: o = zr3(ShadowFactor, ShadowFactor, ShadowFactor); break;
-        case 9: o = Final; break;       // GBufferVis: k_gbuffer_vis then overwrites the eight mosaic cells
-        case 6: {   // fragColor of the full-screen quad: Background.vert:10-17 vertex colours over its two triangles
-            const float u = ((float)px + 0.5f) / (float)L.W, v = ((float)py + 0.5f) / (float)L.H;
-            o = v >= u ? zr3(1.0f - v, u, v - u) : zr3(1.0f - u, v, u - v);
-            break;
-        }
-        default: o = Final * ShadowFactor; break;
-        }
-        emit(zr_unorm(o.x, 255.0f) | zr_unorm(o.y, 255.0f) << 8 | zr_unorm(o.z, 255.0f) << 16 | 255u << 24);
+        emit(light_compose(L, q, Direct, Indirect, RefC, ShadowFactor, px, py));
     }
 }
+
+// The resting frame in one launch: what k_lighting<.., ZR_LIGHT_KEPT> computes, bit for bit, for a frame that uploads nothing and launches
+// nothing else ("The schedule").
+//  - The moving uniforms - camera position, light counts, the point lights - are the argument R (zr_shade.h, LightRef).
+//  - What the GBuffer decides was recorded by the fill (ZrRestRecord, one per wave): the workgroup merges its waves' boxes (min / max are
+//    exact: the tile's list is k_lighting's), each wave tests the lights against the box itself - a ballot, no LDS list, no barrier -
+//    and knows its empty pixels without fetching their 24 GBuffer bytes.
+//  - The colour of a pixel that holds every target's clear value moves with the point lights, so it is computed here, by the thread that
+//    owns the workgroup's first such pixel: that pixel shaded like any other, its standing terms from the slot the fill's one-pixel
+//    launch wrote (rest[0], rest[1]) instead of plane[p], parked in LDS behind one barrier whose condition the records make uniform.
+//    Every workgroup that holds an empty pixel computes the same colour: none waits for another.
+// One pixel per thread only (the records are per wave of such a kernel); other builds keep the pass that reads XkView.
+#if ZR_PIXELS_PER_THREAD == 1
+template <bool LIGHT_LIST, bool BACKGROUND, int TB>
+__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(ZR_LIGHT_KEPT_WAVES, ZR_LIGHT_KEPT_WAVES)))
+void k_lighting_rest(ZrLightParams L, ZrRestArgs R, const uint32_t* __restrict__ owned_tiles, GBufferPtrs G, const float* __restrict__ srgb_lut,
+                     const float* __restrict__ unorm_lut, uint32_t* __restrict__ out, const float4* __restrict__ plane, const float4* __restrict__ rest)
+{
+    static_assert(sizeof(ZrLightParams) + sizeof(ZrRestArgs) + sizeof(GBufferPtrs) + 6 * sizeof(void*) + 256 /* the hidden arguments */ < 4096,
+                  "k_lighting_rest: the argument block");
+    __shared__ float tl[512];            // as in k_lighting
+    __shared__ float u10[1024];
+    __shared__ uint32_t empty_px;
+    float* const slut = tl; float* const u8 = tl + 256;
+    constexpr uint32_t PARTS = TILE_PIX / (uint32_t)TB, WAVES = (uint32_t)TB / 64u, NONE = 0xFFFFFFFFu;
+    const uint32_t part = blockIdx.x % PARTS, tile_slot = blockIdx.x / PARTS;
+    const uint32_t i = threadIdx.x + part * (uint32_t)TB;      // the thread's pixel among the tile's
+    for (uint32_t k = threadIdx.x; k < 256u; k += (uint32_t)TB) { u8[k] = unorm_lut[k]; slut[k] = srgb_lut[k]; }
+    for (uint32_t k = threadIdx.x; k < 1024u; k += (uint32_t)TB) u10[k] = unorm_lut[256u + k];
+    __syncthreads();
+    if (L.clear_next) {      // as in k_lighting
+        const uint32_t per = (L.clear_n + gridDim.x - 1u) / gridDim.x, b = blockIdx.x * per;
+        for (uint32_t k = threadIdx.x; k < per && b + k < L.clear_n; k += (uint32_t)TB) L.clear_next[b + k] = 0x3F800000u;
+    }
+    const uint32_t tile = owned_tiles[tile_slot];
+    const int tx0 = (int)(tile % L.tiles_x) * TILE, ty0 = (int)(tile / L.tiles_x) * TILE;
+    const zf3 cam = zr3(R.cam[0], R.cam[1], R.cam[2]);
+
+    // the workgroup's records: the tile's box, the first empty pixel (thread number, or NONE), this wave's empty pixels
+    const ZrRestRecord* __restrict__ rec = (const ZrRestRecord*)(rest + ZR_REST_SLOT) + ((size_t)tile_slot * ZR_REST_RECORDS_PER_TILE + part * WAVES);
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    float blo[3] = { __builtin_inff(), __builtin_inff(), __builtin_inff() }, bhi[3] = { -__builtin_inff(), -__builtin_inff(), -__builtin_inff() };
+    uint32_t first = NONE;
+    unsigned long long mine = 0ull;
+#pragma unroll 1      // (a record at a time: unrolled, the eight records' 64 scalar registers spill)
+    for (uint32_t w = 0; w < WAVES; ++w) {
+        if constexpr (LIGHT_LIST && ZR_REST_BOX_FROM_RECORDS)
+            for (int a = 0; a < 3; ++a) { blo[a] = __builtin_fminf(blo[a], rec[w].lo[a]); bhi[a] = __builtin_fmaxf(bhi[a], rec[w].hi[a]); }
+        const unsigned long long em = (unsigned long long)rec[w].empty[0] | (unsigned long long)rec[w].empty[1] << 32;
+        if (em != 0ull && first == NONE) first = w * 64u + (uint32_t)__builtin_ctzll(em);
+        if (w == wave) mine = em;
+    }
+    const int px = tx0 + (int)(i & (TILE - 1)), py = ty0 + (int)(i / TILE);
+    const bool inside = px < (int)L.W && py < (int)L.H;
+    const size_t p = (size_t)py * L.W + (size_t)px;
+#if !ZR_REST_BOX_FROM_RECORDS      // (A/B: the box as k_lighting builds it)
+    __shared__ float bbp[LIGHT_LIST ? WAVES : 1][6];
+    if constexpr (LIGHT_LIST) {
+        float lo[3] = { __builtin_inff(), __builtin_inff(), __builtin_inff() }, hi[3] = { -__builtin_inff(), -__builtin_inff(), -__builtin_inff() };
+        bool odd = false;
+        if (inside && (G.scene_color[p] >> 24) != 0u) {
+            const uint2 D = G.gD[p];
+            const float q[3] = { f16_to_f32_hw(D.x & 0xFFFFu), f16_to_f32_hw(D.x >> 16), f16_to_f32_hw(D.y & 0xFFFFu) };
+            for (int a = 0; a < 3; ++a) { if (!(__builtin_fabsf(q[a]) <= 3.402823466e38f)) odd = true; lo[a] = q[a]; hi[a] = q[a]; }
+        }
+        for (int a = 0; a < 3; ++a) { lo[a] = wave_fmin(lo[a]); hi[a] = wave_fmax(hi[a]); }
+        const bool wodd = __ballot(odd) != 0ull;
+        if ((threadIdx.x & 63u) == 0u)
+            for (int a = 0; a < 3; ++a) { bbp[threadIdx.x >> 6][a] = wodd ? -__builtin_inff() : lo[a]; bbp[threadIdx.x >> 6][3 + a] = wodd ? __builtin_inff() : hi[a]; }
+        __syncthreads();
+        for (int a = 0; a < 3; ++a)
+            for (uint32_t w = 0; w < WAVES; ++w) { blo[a] = __builtin_fminf(blo[a], bbp[w][a]); bhi[a] = __builtin_fmaxf(bhi[a], bbp[w][3 + a]); }
+    }
+#endif
+    unsigned long long amask = 0ull;      // the tile's light list (at most ZR_REST_ARG_LIGHTS = 64 lights: a lane each)
+    if constexpr (LIGHT_LIST) {
+        const uint32_t li = threadIdx.x & 63u;
+        amask = __ballot(li < R.nPoint && light_listed(ArgLight{ &R.pt[li < R.nPoint ? li : 0u] }, blo, bhi));
+    }
+
+    const bool is_empty = ((mine >> (threadIdx.x & 63u)) & 1ull) != 0ull, owner = threadIdx.x == first;
+#if ZR_REST_SKIP_EMPTY_LOADS
+    if (inside && (!is_empty || owner)) {
+        const uint32_t sc = G.scene_color[p], A = G.gA[p], B = G.gB[p], Cc = G.gC[p];
+        const uint2 D = G.gD[p];
+#else      // (A/B: every pixel fetches its words and finds itself empty again, as k_lighting does)
+    const uint32_t sc = inside ? G.scene_color[p] : 0u, A = inside ? G.gA[p] : 0u, B = inside ? G.gB[p] : 0u, Cc = inside ? G.gC[p] : 0u;
+    const uint2 D = inside ? G.gD[p] : make_uint2(0u, 0u);
+    if (inside && (!light_pixel_empty(sc, A, B, Cc, D) || owner)) {
+#endif
+        const LitPixel q = light_decode(u8, u10, sc, A, B, Cc, D);
+        const float4 ka = owner ? rest[0] : plane[p], kb = owner ? rest[1] : plane[(size_t)L.W * L.H + p];
+        zf3 Direct = zr3(ka.x, ka.y, ka.z); const float ShadowFactor = ka.w; const zf3 RefC = zr3(kb.x, kb.y, kb.z);
+        shade_points_arg<LIGHT_LIST>(L, R, amask, cam, q.BaseColor, q.Metallic, q.Roughness, q.N, q.Pw, Direct);
+        const zf3 Indirect = shade_indirect(q.BaseColor, q.Metallic, q.AO, ShadowFactor);
+        const uint32_t rgba = light_compose(L, q, Direct, Indirect, RefC, ShadowFactor, px, py);
+        if (owner) empty_px = rgba;
+        else light_emit<BACKGROUND>(L, G, tl, out, rgba, px, py, p, tile_slot, i);
+    }
+    if (first != NONE) {      // (the same for every thread of the workgroup: read from its records)
+        __syncthreads();
+        if (inside && is_empty) light_emit<BACKGROUND>(L, G, tl, out, empty_px, px, py, p, tile_slot, i);
+    }
+}
+#endif
 
 // GBufferVis (SH/BaseLighting.frag:42-145, SPEC_CONSTANTS 9).  Runs after k_lighting has written FinalColor everywhere: the
 // lighting quad samples every GBuffer target again at UV = fragTexCoord * 3 / (1 - EmptyRatio) through LINEAR / REPEAT samplers
@@ -287,12 +434,13 @@ __global__ __launch_bounds__(256) void k_gbuffer_vis(ZrLightParams L, const XkVi
 
 void zr_launch_lighting(const ZrLightParams& L, const XkView* view, const uint32_t* owned_tiles, uint32_t n_owned,
                         const GBufferPtrs& G, const float* shadowmap, const CubeDesc& C, const float* lut, const float* unorm_lut,
-                        uint32_t* out, hipStream_t s, ZrLightMode mode, float4* plane)
+                        uint32_t* out, hipStream_t s, ZrLightMode mode, float4* plane, float4* rest)
 {
     if (n_owned == 0) return;
     if (!plane) mode = ZR_LIGHT_PLAIN;      // (no plane: nothing to fill or to read)
+    if (mode != ZR_LIGHT_FILL) rest = nullptr;
     // with several point lights each tile first builds its light list (L.light_list: decided on the host from the light count)
-#define ZR_LAUNCH_LIGHTING_TB(LL, BG, TB, MODE) hipLaunchKernelGGL((k_lighting<LL, BG, TB, ZR_PIXELS_PER_THREAD, MODE>), dim3(n_owned * (TILE_PIX / ZR_PIXELS_PER_THREAD / TB)), dim3(TB), 0, s, L, view, owned_tiles, G, shadowmap, C, lut, unorm_lut, out, plane)
+#define ZR_LAUNCH_LIGHTING_TB(LL, BG, TB, MODE) hipLaunchKernelGGL((k_lighting<LL, BG, TB, ZR_PIXELS_PER_THREAD, MODE>), dim3(n_owned * (TILE_PIX / ZR_PIXELS_PER_THREAD / TB)), dim3(TB), 0, s, L, view, owned_tiles, G, shadowmap, C, lut, unorm_lut, out, plane, rest)
 #define ZR_LAUNCH_LIGHTING(LL, BG) do { if (mode == ZR_LIGHT_KEPT) ZR_LAUNCH_LIGHTING_TB(LL, BG, ZR_LIGHT_KEPT_TB, ZR_LIGHT_KEPT); \
                                         else if (mode == ZR_LIGHT_FILL) ZR_LAUNCH_LIGHTING_TB(LL, BG, ZR_LIGHT_TB, ZR_LIGHT_FILL); \
                                         else ZR_LAUNCH_LIGHTING_TB(LL, BG, ZR_LIGHT_TB, ZR_LIGHT_PLAIN); } while (0)
@@ -300,6 +448,18 @@ void zr_launch_lighting(const ZrLightParams& L, const XkView* view, const uint32
     else { if (L.bg_enabled) ZR_LAUNCH_LIGHTING(false, true); else ZR_LAUNCH_LIGHTING(false, false); }
 #undef ZR_LAUNCH_LIGHTING
 #undef ZR_LAUNCH_LIGHTING_TB
+}
+bool zr_lighting_rest_available() { return ZR_PIXELS_PER_THREAD == 1; }
+void zr_launch_lighting_rest(const ZrLightParams& L, const ZrRestArgs& R, const uint32_t* owned_tiles, uint32_t n_owned, const GBufferPtrs& G,
+                             const float* lut, const float* unorm_lut, uint32_t* out, hipStream_t s, const float4* plane, const float4* rest)
+{
+#if ZR_PIXELS_PER_THREAD == 1
+    if (n_owned == 0) return;
+#define ZR_LAUNCH_REST(LL, BG) hipLaunchKernelGGL((k_lighting_rest<LL, BG, ZR_LIGHT_KEPT_TB>), dim3(n_owned * (TILE_PIX / ZR_LIGHT_KEPT_TB)), dim3(ZR_LIGHT_KEPT_TB), 0, s, L, R, owned_tiles, G, lut, unorm_lut, out, plane, rest)
+    if (L.light_list) { if (L.bg_enabled) ZR_LAUNCH_REST(true, true); else ZR_LAUNCH_REST(true, false); }
+    else { if (L.bg_enabled) ZR_LAUNCH_REST(false, true); else ZR_LAUNCH_REST(false, false); }
+#undef ZR_LAUNCH_REST
+#endif
 }
 void zr_launch_gbuffer_vis(const ZrLightParams& L, const XkView* view, const GBufferPtrs& G, const float* shadowmap, const CubeDesc& C,
                            const float* lut, uint32_t* out, hipStream_t s)

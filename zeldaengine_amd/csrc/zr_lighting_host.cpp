@@ -45,10 +45,15 @@ void zr_light_facts(zr_ctx* c, ZrFrameFacts* f)
     f->light_uniforms_same = c->lk.plane != nullptr && memcmp(&c->lk.now, &c->lk.key, sizeof c->lk.key) == 0;
     f->cube_gen = c->cube_gen;
     f->light_empty_px = empty_px_on(c);
+    // (the slot is made with the plane, by the first frame planned to fill: a context that has neither yet counts as one that gets it)
+    f->light_slot = zr_lighting_rest_available() && (c->lk.rest != nullptr || (c->lk.plane == nullptr && !c->lk.alloc_failed));
+    const int32_t np = c->view.LightsCount[1];
+    f->light_by_arg = zr_lighting_rest_available() && np >= 0 && np <= ZR_REST_ARG_LIGHTS && f->light_empty_px && c->lk.rest != nullptr && c->debug_view != 9u;
 }
 
 // The plane is made when the first frame is planned to fill it: 32 B x W x H (66 MB at 1080p, 265 MB at 2160p), through the context's
-// owner.  No room: the context simply never keeps - that is no error.
+// owner.  No room: the context simply never keeps - that is no error.  With it, in an allocation of their own, the slot and the records
+// of the one-launch resting frame (ZrRestRecord: 512 B per owned tile); no room for those: the context keeps as a context without them.
 bool zr_light_plane_make(zr_ctx* c)
 {
     if (c->lk.plane) return true;
@@ -56,23 +61,46 @@ bool zr_light_plane_make(zr_ctx* c)
         (void)hipGetLastError();      // (the refusal is not the frame's error)
         c->lk.plane = nullptr; c->lk.alloc_failed = true;
     }
+    if (c->lk.plane && !c->lk.rest && zr_lighting_rest_available() &&
+        c->own.alloc(&c->lk.rest, ZR_REST_SLOT + (size_t)c->n_owned * ZR_REST_RECORDS_PER_TILE * (sizeof(ZrRestRecord) / sizeof(float4))) != hipSuccess) {
+        (void)hipGetLastError();
+        c->lk.rest = nullptr;
+    }
     return c->lk.plane != nullptr;
 }
 
 // The lighting shader's colour for a pixel that still holds every target's clear value: one launch of the lighting kernel over a
 // one-pixel GBuffer.  It needs the finished shadow map (PCF at world position 0) and the frame's uniforms, nothing else.  View 6
-// (the quad's interpolated vertex colour) depends on the pixel position, so it goes without.  It never fills and never reads the plane.
+// (the quad's interpolated vertex colour) depends on the pixel position, so it goes without.  It never reads the plane.  In a frame that
+// fills the plane it fills too, the same kernel over a plane of its own: the slot (zr_ctx::LightKeep::rest, W = H = 1: rest[0], rest[1])
+// then holds the cleared pixel's standing terms, which the one-launch resting frames shade it from - whether or not this frame's shortcut
+// is on (a fill in debug view 6 serves the views after it).
 int empty_pixel_pass(zr_ctx* c)
 {
     c->empty_ready = false;
-    if (c->plan.one_pixel == ZR_LANE_NONE || !empty_px_on(c)) return ZR_OK;
+    const bool fill_slot = c->plan.light_fill && c->lk.rest != nullptr;
+    if (c->plan.one_pixel == ZR_LANE_NONE || (!empty_px_on(c) && !fill_slot)) return ZR_OK;
     ZrLightParams L; light_params(c, &L);
     L.W = 1; L.H = 1; L.tiles_x = 1; L.packed_out = 0; L.bg_enabled = 0;
     zr_launch_lighting(L, c->fc[c->fcur].view, c->d_sowned, 1, c->Gclear, shadow_buf(c), c->cube, c->d_lut, c->d_unorm_lut, c->fc[c->fcur].empty_rgba,
-                       lane_stream(c, c->plan.one_pixel));
+                       lane_stream(c, c->plan.one_pixel), fill_slot ? ZR_LIGHT_FILL : ZR_LIGHT_PLAIN, fill_slot ? c->lk.rest : nullptr);
     HIPCHK(c, hipGetLastError());
-    c->empty_ready = true;
+    c->empty_ready = empty_px_on(c);
     return ZR_OK;
+}
+
+// What k_lighting_rest takes instead of XkView (ZrRestArgs).
+static void rest_args(const zr_ctx* c, ZrRestArgs* R)
+{
+    const XkView& V = c->view;
+    memset(R, 0, sizeof *R);
+    memcpy(R->cam, V.CameraInfo, sizeof R->cam);
+    R->nDir = (uint32_t)V.LightsCount[0]; R->nPoint = (uint32_t)V.LightsCount[1];
+    for (uint32_t i = 0; i < R->nPoint && i < ZR_REST_ARG_LIGHTS; ++i) {
+        memcpy(R->pt[i].color, V.PointLights[i].Color, sizeof R->pt[i].color);
+        memcpy(R->pt[i].pos_falloff, V.PointLights[i].Position, 3 * sizeof(float));
+        R->pt[i].pos_falloff[3] = V.PointLights[i].Direction[3];
+    }
 }
 
 int lighting_pass(zr_ctx* c)
@@ -89,20 +117,32 @@ int lighting_pass(zr_ctx* c)
     uint32_t* const frame_out = L.packed_out ? (c->d_tiles_ext ? c->d_tiles_ext : c->d_tiles) : c->d_color;
     // What the plan decided about the plane holds unless the debug view or the cubemap changed between the stages of the frame (the
     // staged entry points: neither call is refused there): then this pass ignores the plane, and the next resting frame fills it.
+    // A frame planned as one launch (light_args) had no one-pixel launch and uploaded nothing: when it is demoted, or the view now is 9
+    // (k_gbuffer_vis reads XkView), it shades every pixel itself and gets its uniforms here, on this stream.
     ZrLightMode mode = p.light_keep ? ZR_LIGHT_KEPT : p.light_fill ? ZR_LIGHT_FILL : ZR_LIGHT_PLAIN;
-    if (mode != ZR_LIGHT_PLAIN && (c->facts.cube_gen != c->cube_gen || c->facts.light_empty_px != c->empty_ready || !c->lk.plane || c->shading == ZR_SHADING_FORWARD)) {
-        mode = ZR_LIGHT_PLAIN; zr_history_forgotten(c, ZR_HIST_LIGHT_PLANE);
+    const bool shortcut_as_planned = p.light_args ? empty_px_on(c) : c->facts.light_empty_px == c->empty_ready;
+    bool by_arg = p.light_args && c->lk.rest != nullptr && c->debug_view != 9u && c->view.LightsCount[1] >= 0 && c->view.LightsCount[1] <= ZR_REST_ARG_LIGHTS;
+    if (mode != ZR_LIGHT_PLAIN && (c->facts.cube_gen != c->cube_gen || !shortcut_as_planned || !c->lk.plane || c->shading == ZR_SHADING_FORWARD || (p.light_args && !by_arg))) {
+        mode = ZR_LIGHT_PLAIN; by_arg = false; zr_history_forgotten(c, ZR_HIST_LIGHT_PLANE);
     }
+    if (p.light_args && !by_arg) { if (int rc = zr_frame_uniforms(c, s, false, false)) return rc; }
     if (c->shading == ZR_SHADING_FORWARD) {
         // Base.frag over the winners the resolve recorded, with this frame's camera block (frame_begin built it; the overlay fields play no part)
         if (L.clear_next) { zr_launch_fill32(L.clear_next, 0x3F800000u, L.clear_n, s); L.clear_next = nullptr; }
         zr_launch_forward(c->pass[1], L, F.view, c->d_objs, c->d_owned, c->n_owned, F.G, shadow_buf(c), c->cube, c->d_lut, c->d_unorm_lut, frame_out, s);
+    } else if (by_arg) {
+        ZrRestArgs R; rest_args(c, &R);
+        zr_launch_lighting_rest(L, R, c->d_owned, c->n_owned, F.G, c->d_lut, c->d_unorm_lut, frame_out, s, c->lk.plane, c->lk.rest);
+        c->lk.by_arg++;
     } else {
-        zr_launch_lighting(L, F.view, c->d_owned, c->n_owned, F.G, shadow_buf(c), c->cube, c->d_lut, c->d_unorm_lut, frame_out, s, mode, c->lk.plane);
+        zr_launch_lighting(L, F.view, c->d_owned, c->n_owned, F.G, shadow_buf(c), c->cube, c->d_lut, c->d_unorm_lut, frame_out, s, mode, c->lk.plane, c->lk.rest);
         if (c->debug_view == 9u)        // GBufferVis mosaic over the lit frame (needs the whole GBuffer: single-rank contexts only)
             zr_launch_gbuffer_vis(L, F.view, F.G, shadow_buf(c), c->cube, c->d_lut, c->d_color, s);
     }
     TIMED(c, s, zr_ctx::EV_LIGHTING);
+#ifdef ZR_AB_REST_EV_END_EVERY      // A/B ONLY (whether the record's packet shows in a resting period): other frames' waits would go stale
+    if (!by_arg || c->frame_no % ZR_AB_REST_EV_END_EVERY == 0)
+#endif
     HIPCHK(c, hipEventRecord(c->ev_end[c->frame_no % zr_ctx::END_RING], s));      // this frame's GBuffer / shadow map / uniforms copies are free again
     HIPCHK(c, hipGetLastError());
     if (mode == ZR_LIGHT_FILL) { c->lk.key = c->lk.now; c->carry = zr_frame_carry(c->carry, c->facts, p, ZR_STAGE_LIGHTING); }
@@ -125,6 +165,7 @@ extern "C" int zr_get_light_keep(zr_ctx* c, zr_light_keep* out, size_t bytes)
         k.last = c->rendered ? c->lk.last : ZR_LIGHT_PLANE_IGNORED;
         k.ignored = c->lk.count[ZR_LIGHT_PLAIN]; k.filled = c->lk.count[ZR_LIGHT_FILL]; k.read = c->lk.count[ZR_LIGHT_KEPT];
         k.plane_bytes = c->lk.plane ? 32ull * c->W * c->H : 0ull;
+        k.read_by_arg = c->lk.by_arg;
         memcpy(out, &k, bytes < sizeof k ? bytes : sizeof k);
         return ZR_OK;
     });

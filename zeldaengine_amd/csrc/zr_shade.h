@@ -113,15 +113,66 @@ __device__ __forceinline__ ShadeBasis shade_basis(zf3 cam, zf3 BaseColor, float 
 // (1) Direct over the lights in the shader's order: directional, then point (with a tile list: only its set bits, ascending).  DIRS / POINTS:
 // which of the two runs the call walks - the one loop of shade_surface (both), or the halves of shade_standing and shade_points, each a
 // loop that knows its kind of light at compile time.
-template <bool USE_MASK, bool DIRS, bool POINTS>
-__device__ __forceinline__ void shade_lights(const ZrLightParams& L, const XkView* __restrict__ view, const uint32_t* lmask, uint32_t nDir, uint32_t nPoint,
-                                             const ShadeBasis& basis, zf3 N, float Roughness, zf3 Pw, float ShadowFactor, zf3& Direct)
+//
+// A light is read through an accessor: ViewLight - the record in XkView - or ArgLight: the record in the kernel's argument (BYARG: the
+// resting frame's one launch, k_lighting_rest; point lights only), R->pt[], indexed by the wave-uniform light number - scalar loads,
+// nothing of the record in the pixel's vector load chain - and the tile's list is then `amask`, 64 bits in registers.
+struct ViewLight {
+    const XkLight* __restrict__ Lt;
+    __device__ __forceinline__ float pos(int k) const { return Lt->Position[k]; }
+    __device__ __forceinline__ float color(int k) const { return Lt->Color[k]; }
+    __device__ __forceinline__ float dir(int k) const { return Lt->Direction[k]; }
+    __device__ __forceinline__ float falloff() const { return Lt->Direction[3]; }
+};
+struct ArgLight {
+    const ZrRestLight* a;
+    __device__ __forceinline__ float pos(int k) const { return a->pos_falloff[k]; }
+    __device__ __forceinline__ float color(int k) const { return a->color[k]; }
+    __device__ __forceinline__ float dir(int) const { return 0.0f; }      // (never a directional light)
+    __device__ __forceinline__ float falloff() const { return a->pos_falloff[3]; }
+};
+// The tile light list's test (k_lighting): false when the light's sphere of influence misses the box [blo, bhi] of the tile's world
+// positions - every pixel's own exact test in shade_lights would then skip it.
+template <typename LIGHT>
+__device__ __forceinline__ bool light_listed(const LIGHT Lt, const float* blo, const float* bhi)
 {
+    const bool lfinite = __builtin_fabsf(Lt.color(0)) <= 3.402823466e38f && __builtin_fabsf(Lt.color(1)) <= 3.402823466e38f &&
+                         __builtin_fabsf(Lt.color(2)) <= 3.402823466e38f && __builtin_fabsf(Lt.color(3)) <= 3.402823466e38f;
+    const float falloff = Lt.falloff();
+    bool keep = true;
+    if (lfinite && falloff > 0.0f) {
+        zf3 e;      // per axis: how far the light lies outside the box (0 inside); |lp - P| is at least that for every P in it
+        e.x = __builtin_fmaxf(0.0f, __builtin_fmaxf(blo[0] - Lt.pos(0), Lt.pos(0) - bhi[0]));
+        e.y = __builtin_fmaxf(0.0f, __builtin_fmaxf(blo[1] - Lt.pos(1), Lt.pos(1) - bhi[1]));
+        e.z = __builtin_fmaxf(0.0f, __builtin_fmaxf(blo[2] - Lt.pos(2), Lt.pos(2) - bhi[2]));
+        if (zr_dot(e, e) > (falloff * falloff) * 1.000001f) keep = false;
+    }
+    return keep;
+}
+template <bool BYARG>
+__device__ __forceinline__ auto light_at(const XkView* __restrict__ view, const ZrRestArgs* R, bool isdir, uint32_t li, uint32_t nDir)
+{
+    if constexpr (BYARG) return ArgLight{ &R->pt[__builtin_amdgcn_readfirstlane((int)(li - nDir))] };      // (uniform already: made provably so)
+    else return ViewLight{ isdir ? &view->DirectionalLights[li] : &view->PointLights[li - nDir] };
+}
+template <bool USE_MASK, bool DIRS, bool POINTS, bool BYARG = false>
+__device__ __forceinline__ void shade_lights(const ZrLightParams& L, const XkView* __restrict__ view, const uint32_t* lmask, uint32_t nDir, uint32_t nPoint,
+                                             const ShadeBasis& basis, zf3 N, float Roughness, zf3 Pw, float ShadowFactor, zf3& Direct,
+                                             const ZrRestArgs* R = nullptr, unsigned long long amask = 0ull)
+{
+    static_assert(!BYARG || (POINTS && !DIRS), "only the point lights travel by argument");
     const zf3& Vv = basis.Vv; const zf3& Nn = basis.Nn; const zf3& DiffuseColor = basis.DiffuseColor; const float NdotV = basis.NdotV;
     const uint32_t n_lights = (ZR_DIAG_SKIP(L.debug_skip) & 2u) ? 0u : (POINTS ? nDir + nPoint : nDir);
     uint32_t mword = 0u, mnext = 0u;       // remaining bits of the current mask word, index of the next word
     for (uint32_t li = DIRS ? 0u : nDir; li < n_lights; ++li) {
-        if (USE_MASK && POINTS && li >= nDir) {
+        if constexpr (BYARG) {
+            if (USE_MASK) {
+                if (amask == 0ull) break;
+                li = nDir + (uint32_t)__builtin_ctzll(amask);
+                amask &= amask - 1ull;
+                if (li >= n_lights) break;
+            }
+        } else if (USE_MASK && POINTS && li >= nDir) {
             while (mword == 0u && mnext * 32u < nPoint) mword = lmask[mnext++];
             if (mword == 0u) break;
             const uint32_t b = (uint32_t)__builtin_ctz(mword);
@@ -130,19 +181,19 @@ __device__ __forceinline__ void shade_lights(const ZrLightParams& L, const XkVie
             if (li >= n_lights) break;
         }
         const bool isdir = !POINTS || (DIRS && li < nDir);
-        const XkLight* __restrict__ Lt = isdir ? &view->DirectionalLights[li] : &view->PointLights[li - nDir];
-        const zf3 lp = zr3(Lt->Position[0], Lt->Position[1], Lt->Position[2]);
+        const auto Lt = light_at<BYARG>(view, R, isdir, li, nDir);
+        const zf3 lp = zr3(Lt.pos(0), Lt.pos(1), Lt.pos(2));
         // A light whose radiance factor is exactly 0 adds fma(0, bxdf, Direct) = Direct: skip its BxDF.  That is the
         // case beyond a point light's radius (attenuation 1 - clamp(d, 0, r) / r = 0) and for N.L <= 0.  The skip
         // needs finite colour * intensity (0 * finite = 0); the test is wave-uniform per light.  Where the BxDF is NaN or
         // infinite (D_GGX at roughness 0 with N.H = 1), or the attenuation is NaN (falloff 0) while N.L is 0, the shader's
         // literal sum would be NaN; the contract is the skip, and the CPU oracle states the same (row 8 of its CONTRACT.md).
-        const bool lfinite = __builtin_fabsf(Lt->Color[0]) <= 3.402823466e38f && __builtin_fabsf(Lt->Color[1]) <= 3.402823466e38f &&
-                             __builtin_fabsf(Lt->Color[2]) <= 3.402823466e38f && __builtin_fabsf(Lt->Color[3]) <= 3.402823466e38f;
+        const bool lfinite = __builtin_fabsf(Lt.color(0)) <= 3.402823466e38f && __builtin_fabsf(Lt.color(1)) <= 3.402823466e38f &&
+                             __builtin_fabsf(Lt.color(2)) <= 3.402823466e38f && __builtin_fabsf(Lt.color(3)) <= 3.402823466e38f;
         float att = 1.0f;
         zf3 Lv;
         if (!isdir) {
-            const float falloff = Lt->Direction[3];
+            const float falloff = Lt.falloff();
             // far outside the radius (1e-6 relative margin on the squared distance covers every rounding in dist): the exact
             // test below would give att == 0, so the distance and the quotient need not be formed
             const zf3 dl = lp - Pw;
@@ -157,7 +208,7 @@ __device__ __forceinline__ void shade_lights(const ZrLightParams& L, const XkVie
             att = 1.0f - zr_clamp(dist, 0.0f, falloff) / falloff;
             if (lfinite && att == 0.0f) continue;
             Lv = dl * rd;
-        } else Lv = zr_normalize(zr3(Lt->Direction[0], Lt->Direction[1], Lt->Direction[2]));
+        } else Lv = zr_normalize(zr3(Lt.dir(0), Lt.dir(1), Lt.dir(2)));
         // ApplyDirectionalLight / ApplyPointLight (SH/Common.glsl:364-372, 399-416)
         const float ndotl = zr_clamp(zr_dot(Nn, Lv), 0.0f, 1.0f);
         if (lfinite && ndotl == 0.0f) continue;
@@ -171,8 +222,8 @@ __device__ __forceinline__ void shade_lights(const ZrLightParams& L, const XkVie
         const float Fd = Fr_DisneyDiffuse(NdotV, NdotL, LdotH, Roughness);
         const zf3 bx = zr3(__builtin_fmaf(DiffuseColor.x * (1.0f - F), Fd, Fr), __builtin_fmaf(DiffuseColor.y * (1.0f - F), Fd, Fr),
                            __builtin_fmaf(DiffuseColor.z * (1.0f - F), Fd, Fr));
-        const float k = ndotl * Lt->Color[3];
-        zf3 rad = zr3(k * Lt->Color[0], k * Lt->Color[1], k * Lt->Color[2]);
+        const float k = ndotl * Lt.color(3);
+        zf3 rad = zr3(k * Lt.color(0), k * Lt.color(1), k * Lt.color(2));
         if (isdir) {
             Direct = zr3(__builtin_fmaf(rad.x * bx.x, ShadowFactor, Direct.x), __builtin_fmaf(rad.y * bx.y, ShadowFactor, Direct.y),
                          __builtin_fmaf(rad.z * bx.z, ShadowFactor, Direct.z));
@@ -311,6 +362,14 @@ __device__ __forceinline__ void shade_points(const ZrLightParams& L, const XkVie
 {
     const ShadeBasis basis = shade_basis(cam, BaseColor, Metallic, N, Pw);
     shade_lights<USE_MASK, false, true>(L, view, lmask, nDir, nPoint, basis, N, Roughness, Pw, 0.0f, Direct);
+}
+// ... with the lights and the tile's list by argument (shade_lights, BYARG)
+template <bool USE_MASK>
+__device__ __forceinline__ void shade_points_arg(const ZrLightParams& L, const ZrRestArgs& R, unsigned long long amask, zf3 cam,
+                                                 zf3 BaseColor, float Metallic, float Roughness, zf3 N, zf3 Pw, zf3& Direct)
+{
+    const ShadeBasis basis = shade_basis(cam, BaseColor, Metallic, N, Pw);
+    shade_lights<USE_MASK, false, true, true>(L, nullptr, nullptr, R.nDir, R.nPoint, basis, N, Roughness, Pw, 0.0f, Direct, &R, amask);
 }
 
 // (2) indirect, BaseLighting.frag:210

@@ -341,9 +341,28 @@ void zr_launch_count_shadow(const uint32_t* bits, size_t n, ZrDevStats* stats, h
 // pixel's terms; load them instead of computing them.  The plane: W * H float4 (Direct over the directional lights, ShadowFactor), then
 // W * H float4 (RefC, 0).
 enum ZrLightMode : uint32_t { ZR_LIGHT_PLAIN = 0u, ZR_LIGHT_FILL = 1u, ZR_LIGHT_KEPT = 2u };
+// A resting frame in one launch (k_lighting_rest): what a KEPT pass reads of XkView - the camera position, the two light counts and, of
+// each point light, Color, Position[0..2] and Direction[3] (the falloff) - travels as a kernel argument, so the frame uploads nothing.
+// Up to ZR_REST_ARG_LIGHTS point lights; more take the pass that reads XkView.
+#define ZR_REST_ARG_LIGHTS 64
+struct ZrRestLight { float color[4]; float pos_falloff[4]; };
+struct ZrRestArgs { float cam[3]; uint32_t nDir, nPoint, _pad[3]; ZrRestLight pt[ZR_REST_ARG_LIGHTS]; };
+// What the GBuffer decides for a resting frame, recorded by the fill: per 64 consecutive pixels of a tile (one wave's, 16 records a tile,
+// record tile_slot * 16 + pixel / 64) the bounding box of the world positions the tile light list goes by (pixels with Mask = 0 skipped;
+// -inf / +inf when a position is not finite) and which of them hold every target's clear value.  ZR_REST_SLOT float4 ahead of the
+// records hold the standing terms of such a pixel (the fill's one-pixel launch: its plane[0], plane[1]).
+struct ZrRestRecord { float lo[3], hi[3]; uint32_t empty[2]; };
+#define ZR_REST_SLOT 2u
+#define ZR_REST_RECORDS_PER_TILE 16u
+static_assert(sizeof(ZrRestRecord) == 32 && sizeof(ZrRestLight) == 32 && sizeof(ZrRestArgs) == 32 + 32 * ZR_REST_ARG_LIGHTS, "zr_types.h: the resting frame's records");
+// rest (FILL): the slot-and-records buffer the fill writes its records into, or null (the one-pixel launch: the slot is its plane)
 void zr_launch_lighting(const ZrLightParams& L, const XkView* view, const uint32_t* owned_tiles, uint32_t n_owned,
                         const GBufferPtrs& G, const float* shadowmap, const CubeDesc& C, const float* lut, const float* unorm_lut,
-                        uint32_t* out, hipStream_t s, ZrLightMode mode = ZR_LIGHT_PLAIN, float4* plane = nullptr);
+                        uint32_t* out, hipStream_t s, ZrLightMode mode = ZR_LIGHT_PLAIN, float4* plane = nullptr, float4* rest = nullptr);
+// The KEPT pass with its uniforms by argument and the empty pixel's colour computed in the launch ("The schedule").
+bool zr_lighting_rest_available();      // (a build with one pixel per thread)
+void zr_launch_lighting_rest(const ZrLightParams& L, const ZrRestArgs& R, const uint32_t* owned_tiles, uint32_t n_owned, const GBufferPtrs& G,
+                             const float* lut, const float* unorm_lut, uint32_t* out, hipStream_t s, const float4* plane, const float4* rest);
 // forward variant (SH/Base.frag): shades the winners recorded in G.prim with the camera pass's own parameter block
 void zr_launch_forward(const ZrPass& P, const ZrLightParams& L, const XkView* view, const ZrObject* objs, const uint32_t* owned_tiles, uint32_t n_owned,
                        const GBufferPtrs& G, const float* shadowmap, const CubeDesc& C, const float* lut, const float* unorm_lut, uint32_t* out, hipStream_t s);

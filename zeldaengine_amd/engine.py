@@ -627,7 +627,7 @@ class Renderer:
         k = abi.LightKeep()
         self._chk(self.L.zr_get_light_keep(self.h, C.byref(k), C.sizeof(k)))
         return {"last": ("ignored", "filled", "read")[int(k.last)], "ignored": int(k.ignored), "filled": int(k.filled), "read": int(k.read),
-                "plane_bytes": int(k.plane_bytes)}
+                "plane_bytes": int(k.plane_bytes), "read_by_arg": int(k.read_by_arg)}
 
     # ---- read-back
     def color(self):
