@@ -39,6 +39,7 @@ def lib(literal=False):
         L.zo_mesh_create.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.zo_object_add.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32]
         L.zo_scene_clear.argtypes = [C.c_void_p]
+        L.zo_object_set_texture.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.zo_set_cubemap.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.zo_set_skydome.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
         L.zo_set_background.argtypes = [C.c_void_p, C.c_void_p]
@@ -89,6 +90,10 @@ def lib(literal=False):
         L.zo_kat_shade_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32]
         L.zo_kat_shadow_tap_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.zo_kat_sincos_intcast.argtypes = [C.c_float, C.c_void_p]
+        L.zo_kat_set_image.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int]
+        L.zo_kat_tex_image_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.zo_kat_tex_material_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.zo_kat_tex_image_batch.restype = L.zo_kat_tex_material_batch.restype = None
         for n in ("zo_kat_set_shadowmap", "zo_kat_sincos_intcast"):
             getattr(L, n).restype = C.c_int
         for n in ("zo_kat_cube_sample_batch", "zo_kat_pcf_batch", "zo_kat_shade_batch", "zo_kat_shadow_tap_batch"):
@@ -132,6 +137,14 @@ class Oracle:
         r = self.L.zo_object_add(self.h, mesh, mat, _ptr(inst) if n else None, n)
         assert r >= 0
         return r
+
+    def object_set_texture(self, obj, slot, image):
+        """Renderer.object_set_texture / object_update_texture_async: another (h, w, 4) image of the slot's size.  The slot stays an image:
+        one whose texels are all equal is filtered like any other (only object_add collapses it)."""
+        from zeldaengine_amd import abi
+        img = np.ascontiguousarray(image, dtype=np.uint8)
+        im = abi.Image(img.ctypes.data, img.shape[1], img.shape[0])
+        assert self.L.zo_object_set_texture(self.h, obj, slot, C.byref(im)) == 0
 
     def scene_clear(self):
         self.L.zo_scene_clear(self.h)

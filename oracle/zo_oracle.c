@@ -54,6 +54,8 @@ struct zo_ctx {
     uint32_t* overlay; float* main_depth; uint32_t* sky_vis;
     /* forward variant (SH/Base.frag; the engine built with ENABLE_DEFERRED_SHADING false, ZE:93): the fragment's unquantised inputs */
     int forward; struct zo_fsurf* fwd;
+    /* the images of the per-call sampler exports (zo_kat_set_image): one per material slot */
+    zo_tex kat_tex[7];
 };
 /* what Base.frag:48-60 holds before it lights the fragment: nothing has been through a render-target format */
 typedef struct zo_fsurf { zo_v3 BaseColor; float Metallic, Roughness; zo_v3 Normal, AmbientOcclution, P, VertexColor; } zo_fsurf;
@@ -133,6 +135,7 @@ void zo_destroy(zo_ctx* c)
     free(c->depth); free(c->scene_color); free(c->gA); free(c->gB); free(c->gC); free(c->gD);
     free(c->vis); free(c->color); free(c->shadowmap); free(c->overlay); free(c->main_depth); free(c->sky_vis); free(c->fwd);
     zo_set_skydome(c, NULL, 0, NULL, 0, NULL); zo_set_background(c, NULL);
+    for (int t = 0; t < 7; ++t) for (int l = 0; l < c->kat_tex[t].levels; ++l) free(c->kat_tex[t].mip[l]);
     free(c);
 }
 
@@ -206,6 +209,21 @@ int zo_object_add(zo_ctx* c, int mesh, const zo_material* mat, const XkInstanceD
     }
     c->order_valid = 0;
     return c->n_objects++;
+}
+
+/* zr_object_set_texture / zr_object_update_texture_async: another image of the same size into a slot that holds an image.  The slot stays
+ * an image whatever its texels are: a texture update does not look at them (the device form cannot), so an image whose texels are all
+ * equal is filtered like any other from here on - only zo_object_add collapses one (oracle/CONTRACT.md, "a constant image"). */
+int zo_object_set_texture(zo_ctx* c, int object, int slot, const zo_image* im)
+{
+    if (!c || object < 0 || object >= c->n_objects || slot < 0 || slot >= 7 || !im || !im->rgba8) return -1;
+    zo_tex* tx = &c->objects[object].tex[slot];
+    if (tx->constant || tx->w != im->width || tx->h != im->height) return -1;
+    for (int l = 0; l < tx->levels; ++l) free(tx->mip[l]);
+    size_t n = (size_t)tx->w * tx->h * 4;
+    tx->px = (uint8_t*)malloc(n); memcpy(tx->px, im->rgba8, n);
+    zo_build_mips(c, tx, slot == 0);
+    return 0;
 }
 
 /* Draw order of the deferred-scene pass: all non-instanced draws, then all instanced draws (ZE:3445-3476). */
@@ -830,14 +848,21 @@ void zo_kat_aniso(float ax, float ay, float bx, float by, int levels, float out[
     zo_aniso_setup(ax, ay, bx, by, levels, &N, &l, &xm);
     out[0] = (float)N; out[1] = l; out[2] = (float)xm;
 }
+/* the footprint of a w x h image with `levels` mips under the derivatives: tap count, level of detail, the major axis' derivative */
+static void zo_tex_footprint(uint32_t w, uint32_t h, int levels, float dudx, float dvdx, float dudy, float dvdy, int* N, float* lambda, float* du, float* dv)
+{
+    float W = (float)w, H = (float)h;
+    int xmajor;
+    zo_aniso_setup(dudx * W, dvdx * H, dudy * W, dvdy * H, levels, N, lambda, &xmajor);
+    *du = xmajor ? dudx : dudy; *dv = xmajor ? dvdx : dvdy;
+}
 static void zo_tex_sample(const zo_ctx* c, const zo_tex* t, int srgb, float u, float v, float dudx, float dvdx, float dudy, float dvdy, float out[4])
 {
-    if (t->constant) { zo_tex_fetch(c, t, srgb, 0, 0, 0, out); zo_tex_finish(srgb, out); return; }
-    float W = (float)t->w, H = (float)t->h;
-    int N, xmajor; float lambda;
-    zo_aniso_setup(dudx * W, dvdx * H, dudy * W, dvdy * H, t->levels, &N, &lambda, &xmajor);
+    /* an image that zo_object_add found to hold one texel throughout IS that texel (CONTRACT.md row 9); the literal reading filters it */
+    if (t->constant && !ZO_IS_LITERAL) { zo_tex_fetch(c, t, srgb, 0, 0, 0, out); zo_tex_finish(srgb, out); return; }
+    int N; float lambda, du, dv;
+    zo_tex_footprint(t->w, t->h, t->levels, dudx, dvdx, dudy, dvdy, &N, &lambda, &du, &dv);
     if (N == 1) { zo_tex_trilinear(c, t, srgb, lambda, u, v, out); zo_tex_finish(srgb, out); return; }
-    float du = xmajor ? dudx : dudy, dv = xmajor ? dvdx : dvdy;
     float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     for (int i = 1; i <= N; ++i) {
         float off = (float)i / (float)(N + 1) - 0.5f;
@@ -850,7 +875,8 @@ static void zo_tex_sample(const zo_ctx* c, const zo_tex* t, int srgb, float u, f
 }
 
 /* ComputeNormal(fragPosition, fragTexCoord, fragNormal, texNormal), SH/Common.glsl:113-127 */
-static zo_v3 zo_compute_normal(zo_v3 pos_dx, zo_v3 pos_dy, float s1, float t1, float s2, float t2, zo_v3 fragN, zo_v3 texN)
+/* ... from the tangent-space normal ts = normalize(2 normalize(texNormal) - 1) on (:125-126) */
+static zo_v3 zo_compute_normal_ts(zo_v3 pos_dx, zo_v3 pos_dy, float s1, float t1, float s2, float t2, zo_v3 fragN, zo_v3 ts)
 {
     float det = fmaf(s1, t2, -(s2 * t1));
     zo_v3 T = zo_div_scalar(zo_v3make(fmaf(t2, pos_dx.x, -(t1 * pos_dy.x)),     /* vec3 / scalar */
@@ -859,12 +885,16 @@ static zo_v3 zo_compute_normal(zo_v3 pos_dx, zo_v3 pos_dy, float s1, float t1, f
     zo_v3 N = zo_normalize(fragN);
     T = zo_normalize(zo_sub(T, zo_scale(N, zo_dot(N, T))));
     zo_v3 B = zo_normalize(zo_cross(N, T));
-    zo_v3 n = zo_normalize(texN);
-    zo_v3 ts = zo_normalize(zo_v3make(fmaf(2.0f, n.x, -1.0f), fmaf(2.0f, n.y, -1.0f), fmaf(2.0f, n.z, -1.0f)));
     zo_v3 w = zo_v3make(fmaf(N.x, ts.z, fmaf(B.x, ts.y, T.x * ts.x)),
                         fmaf(N.y, ts.z, fmaf(B.y, ts.y, T.y * ts.x)),
                         fmaf(N.z, ts.z, fmaf(B.z, ts.y, T.z * ts.x)));
     return zo_normalize(w);
+}
+static zo_v3 zo_compute_normal(zo_v3 pos_dx, zo_v3 pos_dy, float s1, float t1, float s2, float t2, zo_v3 fragN, zo_v3 texN)
+{
+    zo_v3 n = zo_normalize(texN);
+    zo_v3 ts = zo_normalize(zo_v3make(fmaf(2.0f, n.x, -1.0f), fmaf(2.0f, n.y, -1.0f), fmaf(2.0f, n.z, -1.0f)));
+    return zo_compute_normal_ts(pos_dx, pos_dy, s1, t1, s2, t2, fragN, ts);
 }
 
 static void zo_clear_gbuffer(zo_ctx* c)
@@ -1741,3 +1771,72 @@ void zo_kat_shade_batch(zo_ctx* c, const float* SB, float dxy, int use_mask, con
     }
     free(t);
 }
+
+/* ---- the sampler and the surface stage, call by call (csrc/zr_texture.h, zr_surface.h) */
+
+/* case = w, h, levels (integers), dudx, dvdx, dudy, dvdy -> N (integer), lambda, du, dv */
+ZO_BATCH(tex_footprint, 7, 4, int N; float l; float du; float dv;
+         zo_tex_footprint(a[0], a[1], (int)a[2], f[3], f[4], f[5], f[6], &N, &l, &du, &dv);
+         o[0] = (uint32_t)N; o[1] = zo_f2u(l); o[2] = zo_f2u(du); o[3] = zo_f2u(dv);)
+/* Slot `slot` of the context's sampler images: an RGBA8 image with its mip chain (slot 0 filtered as sRGB in zo_kat_tex_material_batch), or
+ * none (rgba8 NULL).  as_image: an image whose texels are all equal stays an image and is filtered (what a texture update leaves in a
+ * slot, oracle/CONTRACT.md); otherwise it collapses to its texel as in zo_object_add.  Returns the level count, -1 for a bad argument. */
+int zo_kat_set_image(zo_ctx* c, int slot, const uint8_t* rgba8, uint32_t w, uint32_t h, int srgb, int as_image)
+{
+    if (!c || slot < 0 || slot >= 7) return -1;
+    zo_tex_free(&c->kat_tex[slot]);
+    if (!rgba8) return 0;
+    if (w == 0 || h == 0 || w > 16384 || h > 16384) return -1;
+    zo_image im; memset(&im, 0, sizeof im);
+    im.rgba8 = rgba8; im.width = w; im.height = h;
+    zo_tex_from_image(c, &c->kat_tex[slot], &im, srgb);
+    if (as_image) c->kat_tex[slot].constant = 0;
+    return c->kat_tex[slot].levels;
+}
+/* case = u, v, dudx, dvdx, dudy, dvdy -> rgba of slot `slot`, sampled as sRGB or UNORM */
+void zo_kat_tex_image_batch(zo_ctx* c, int slot, int srgb, const uint32_t* in, uint32_t* out, uint32_t n)
+{
+    if (slot < 0 || slot >= 7 || !c->kat_tex[slot].px) return;
+    for (uint32_t i = 0; i < n; ++i) {
+        float f[6], r[4]; memcpy(f, in + (size_t)i * 6, sizeof f);
+        zo_tex_sample(c, &c->kat_tex[slot], srgb, f[0], f[1], f[2], f[3], f[4], f[5], r);
+        memcpy(out + (size_t)i * 4, r, sizeof r);
+    }
+}
+/* the same case -> the seven slots' rgba, slot 0 as sRGB (BaseScene.frag:30-36); every slot must be set */
+void zo_kat_tex_material_batch(zo_ctx* c, const uint32_t* in, uint32_t* out, uint32_t n)
+{
+    for (int t = 0; t < 7; ++t) if (!c->kat_tex[t].px) return;
+    for (uint32_t i = 0; i < n; ++i) {
+        float f[6], r[4]; memcpy(f, in + (size_t)i * 6, sizeof f);
+        for (int t = 0; t < 7; ++t) {
+            zo_tex_sample(c, &c->kat_tex[t], t == 0, f[0], f[1], f[2], f[3], f[4], f[5], r);
+            memcpy(out + (size_t)i * 28 + (size_t)t * 4, r, sizeof r);
+        }
+    }
+}
+/* case = X0, Y0 (integers), a1, b1, a2, b2, rw0, rw1, rw2, px, py (integers) -> b */
+ZO_BATCH(bary_screen, 11, 3, zo_setup s; memset(&s, 0, sizeof s); s.X0 = (int32_t)a[0]; s.Y0 = (int32_t)a[1];
+         s.a1 = f[2]; s.b1 = f[3]; s.a2 = f[4]; s.b2 = f[5];
+         zo_sv sv[3]; memset(sv, 0, sizeof sv); sv[0].rw = f[6]; sv[1].rw = f[7]; sv[2].rw = f[8];
+         float b[3]; zo_bary_screen(&s, sv, (int32_t)a[9], (int32_t)a[10], b); memcpy(o, b, sizeof b);)
+/* case = three clip-space corners, hw, hh, px, py (integers) -> b */
+ZO_BATCH(bary_homog, 16, 3, zo_v4 cc[3]; memcpy(cc, f, sizeof cc);
+         float b[3]; zo_bary_homog(cc, f[12], f[13], (int32_t)a[14], (int32_t)a[15], b); memcpy(o, b, sizeof b);)
+/* case = b, three vec3 attributes A0 A1 A2 -> the interpolated vec3, then the scalar interpolated from (A0.x, A1.y, A2.z) */
+void zo_kat_interp_batch(const uint32_t* in, uint32_t* out, uint32_t n)
+{
+    for (uint32_t i = 0; i < n; ++i) {
+        float f[12]; memcpy(f, in + (size_t)i * 12, sizeof f);
+        zo_v3 A[3]; memcpy(A, f + 3, sizeof A);
+        float uv[3][2]; memset(uv, 0, sizeof uv);
+        uv[0][0] = A[0].x; uv[1][0] = A[1].y; uv[2][0] = A[2].z;
+        zo_varyings r = zo_interp(f, A, A, uv);
+        zo_put3(out + (size_t)i * 4, r.P); out[(size_t)i * 4 + 3] = zo_f2u(r.u);
+    }
+}
+/* case = pos_dx, pos_dy, s1, t1, s2, t2, fragN, ts -> the world-space normal */
+ZO_BATCH(compute_normal, 16, 3, zo_put3(o, zo_compute_normal_ts(zo_v3make(f[0], f[1], f[2]), zo_v3make(f[3], f[4], f[5]), f[6], f[7], f[8], f[9],
+                                                                zo_v3make(f[10], f[11], f[12]), zo_v3make(f[13], f[14], f[15])));)
+/* case = M, p, a flag the oracle does not read (the product's identity short cut) -> (M * vec4(p, 1)).xyz */
+ZO_BATCH(model_point, 20, 3, zo_v4 r = zo_mat4_point(f, zo_v3make(f[16], f[17], f[18])); zo_put3(o, zo_v3make(r.x, r.y, r.z));)

@@ -29,6 +29,7 @@ int     zo_mesh_create(zo_ctx*, const XkVertex* v, uint32_t nv, const uint32_t* 
 int     zo_object_add(zo_ctx*, int mesh, const zo_material* mat, const XkInstanceData* inst, uint32_t n_inst);
 void    zo_scene_clear(zo_ctx*);
 int     zo_set_cubemap(zo_ctx*, const uint8_t* const faces[6], uint32_t dim);
+int     zo_object_set_texture(zo_ctx*, int object, int slot, const zo_image* image);   /* same size, into a slot that holds an image */
 int     zo_set_skydome(zo_ctx*, const XkVertex* v, uint32_t nv, const uint32_t* idx, uint32_t ni, const zo_image* tex);
 int     zo_set_background(zo_ctx*, const zo_image* tex);
 void    zo_set_sky_flags(zo_ctx*, int enable_skydome, int enable_background);
@@ -91,6 +92,12 @@ int   zo_kat_set_shadowmap(zo_ctx*, const float* map, uint32_t dim);       /* di
 void  zo_kat_cube_sample_batch(zo_ctx*, const uint32_t* in, uint32_t* out, uint32_t n);
 void  zo_kat_pcf_batch(zo_ctx*, const float* SB, float dxy, const uint32_t* in, uint32_t* out, uint32_t n);
 void  zo_kat_shade_batch(zo_ctx*, const float* SB, float dxy, int use_mask, const uint32_t* in, uint32_t* out, uint32_t n);
+/* the sampler and the surface stage (csrc/zr_texture.h, zr_surface.h): the sampler reads the context's images, one per material slot */
+ZO_BATCH_DECL(tex_footprint); ZO_BATCH_DECL(bary_screen); ZO_BATCH_DECL(bary_homog); ZO_BATCH_DECL(interp); ZO_BATCH_DECL(compute_normal);
+ZO_BATCH_DECL(model_point);
+int   zo_kat_set_image(zo_ctx*, int slot, const uint8_t* rgba8, uint32_t w, uint32_t h, int srgb, int as_image);
+void  zo_kat_tex_image_batch(zo_ctx*, int slot, int srgb, const uint32_t* in, uint32_t* out, uint32_t n);
+void  zo_kat_tex_material_batch(zo_ctx*, const uint32_t* in, uint32_t* out, uint32_t n);
 int   zo_kat_sincos_intcast(float x, float out[2]);     /* zo_sincosf's earlier quadrant, ((int)k) & 3; 0 where that cast is undefined */
 
 #ifdef __cplusplus

@@ -671,3 +671,411 @@ def shade_all_ones(table):
 
 # (nDir, nPoint, poison): every pair of counts with finite lights; the NaN-making lights in three views of their own
 SHADE_VIEWS = [(nd, npt, False) for nd in (0, 1, 2) for npt in (0, 1, 31, 32, 33, 64, 256)] + [(2, 1, True), (1, 33, True), (0, 256, True)]
+
+
+# ------------------------------------------------------------------------------------------------------------------ the sampler (zr_texture.h)
+# tex_footprint reads its case alone.  tex_image, tex_material and tex_packed read a material's images besides the case: a Textures holds
+# seven slots, the GPU test hands them to the probe (zp_run_textures) and to an oracle context (zo_kat_set_image), whose mip chains both use.
+
+PROBE_FUNCTIONS += ["tex_footprint", "tex_image", "tex_material", "tex_packed", "bary_screen", "bary_homog", "interp", "compute_normal",
+                    "model_point", "f32_to_f16_hw", "f16_to_f32_hw"]
+WORDS.update({"tex_footprint": (7, 4), "tex_image": (6, 4), "tex_material": (6, 28), "tex_packed": (6, 13), "bary_screen": (11, 3),
+              "bary_homog": (16, 3), "interp": (12, 4), "compute_normal": (16, 3), "model_point": (20, 3), "f32_to_f16_hw": (1, 1),
+              "f16_to_f32_hw": (1, 1)})
+FLOAT_WORDS.update({n: [True] * WORDS[n][1] for n in PROBE_FUNCTIONS[-11:]})
+FLOAT_WORDS.update({"tex_footprint": [False, True, True, True], "f32_to_f16_hw": [False]})
+TABLE_OF.update({"interp": "vectors12", "f32_to_f16_hw": "f32_to_f16", "f16_to_f32_hw": "f16_codes"})
+# the oracle's export where it is not zo_kat_<name>_batch: the half conversions are the existing batches
+ORACLE_OF = {"f32_to_f16_hw": "f32_to_f16", "f16_to_f32_hw": "f16_to_f32"}
+_oracle_batch_plain = oracle_batch
+
+
+def oracle_batch(L, name, table, shadow_map=None):     # noqa: F811
+    if name in ORACLE_OF:
+        assert WORDS[ORACLE_OF[name]] == WORDS[name]
+        return _oracle_batch_plain(L, ORACLE_OF[name], table)
+    return _oracle_batch_plain(L, name, table, shadow_map)
+
+
+def vectors12():
+    return vectors(12)
+
+
+# (w, h) of the single-image runs.  16384 is the largest side the product's host accepts.
+IMAGE_SETS = [(1, 1), (1, 16), (16, 1), (2, 2), (33, 7), (48, 20), (64, 64), (128, 4), (16384, 1), (1, 16384)]
+MAX_ANISO = 16
+
+
+def levels_of(w, h):
+    return int(max(w, h)).bit_length()
+
+
+def level_size(w, h, level):
+    return max(1, w >> level), max(1, h >> level)
+
+
+def noise_image(w, h, seed=0):
+    """(h, w, 4) random RGBA8 with the codes 0 and 255 present where there is room"""
+    rng = np.random.default_rng(20270 + 131 * w + h + seed)
+    im = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
+    if w * h >= 2:
+        im.reshape(-1, 4)[0] = 0
+        im.reshape(-1, 4)[-1] = 255
+    return im
+
+
+def _f32(x):
+    return np.asarray(x, dtype=np.float32)
+
+
+def _pow2_below(x):
+    """the power of two 2^-k nearest 1 / x from below (a float with one mantissa bit)"""
+    return np.float32(2.0 ** -int(np.ceil(np.log2(x))))
+
+
+def footprint_breakpoints(w, h):
+    """(rows of dudx, dvdx, dudy, dvdy, N, major, ulps): for N = 1..16 a footprint whose Pmax^2 / Pmin^2 is EXACTLY N^2 - the major axis
+    along u with derivative N h t, the minor along v with derivative w t, t a power of two: both products with the image's size are
+    N w h t and w h t, exact in float32, and so are their squares and N^2 times the lesser (test_device_function_tables.py checks this in
+    rational arithmetic) - then the same with the major derivative moved by -2..2 ulp.  Either screen axis as the major one; N = 1 is the
+    tie rx2 == ry2, which goes to x."""
+    rows = []
+    for t in (_pow2_below(w * h), np.float32(_pow2_below(w * h) * np.float32(8.0))):
+        for N in range(1, MAX_ANISO + 1):
+            major, minor = np.float32(np.float32(N * h) * t), np.float32(np.float32(w) * t)
+            for d in range(-2, 3):
+                m = u2f(np.array([int(f2u(major)[0]) + d], dtype=U))[0]
+                rows.append((m, 0.0, 0.0, minor, N, 0, d))            # x is the major axis: (dudx, dvdx) = (major, 0), (dudy, dvdy) = (0, minor)
+                rows.append((0.0, minor, m, 0.0, N, 1, d))            # y is
+    return np.array(rows, dtype=np.float64)
+
+
+@functools.lru_cache(maxsize=None)
+def footprints(w, h):
+    """the derivative quadruples (dudx, dvdx, dudy, dvdy) of an image set's tables, as float32 rows"""
+    rng = np.random.default_rng(20271 + 131 * w + h)
+    L = levels_of(w, h)
+    W, H = np.float64(w), np.float64(h)
+    rows = [footprint_breakpoints(w, h)[:, :4].astype(np.float32)]
+    sp = []
+    d = np.float32(1.0 / 64)
+    sp += [(d, 0, 0, 0), (0, d, 0, 0), (0, 0, d, 0), (0, 0, 0, d), (0, 0, 0, 0), (-0.0, 0, 0, -0.0), (-d, -0.0, 0, d)]     # rmin2 = 0 (N = 16); both 0; -0
+    # lambda on every integer of the chain (and one below, one above) +- 2 ulp: an isotropic footprint of 2^l texels, and a 4:1 one of 4 * 2^l
+    for l in range(-1, L + 1):
+        for du in u2f(around(np.float32(2.0 ** l / W), 2)):
+            sp += [(du, 0, 0, np.float32(2.0 ** l / H)), (0, np.float32(2.0 ** l / H), du, 0)]
+        for du in u2f(around(np.float32(4.0 * 2.0 ** l / W), 2)):
+            sp += [(du, 0, 0, np.float32(2.0 ** l / H))]
+    # denormal products (squares that underflow), products that overflow
+    for a in (1e-19, 1e-20, 1e-22, 1e-23, 1e-30, 1e-40):
+        sp += [(a, 0, 0, a), (a, a, 0, 1e-21), (0, 1e-22, a, 0), (a, 0, 0, 0.01)]
+    for a in (3e38, -3e38, 1e19, 2e19):
+        sp += [(a, 0, 0, a), (a, 0, 0, 0.01), (0.01, 0, 0, a), (a, a, a, a), (0, a, 1e-3, 0)]
+    for s in (np.inf, -np.inf, np.nan):
+        for k in range(4):
+            for base in ((0.01, 0.0, 0.0, 0.02), (0.0, 0.0, 0.0, 0.0), (0.05, 0.01, -0.01, 0.002)):
+                v = list(base)
+                v[k] = s
+                sp.append(tuple(v))
+    sp += [(np.inf, 0, 0, np.inf), (np.nan, np.nan, np.nan, np.nan), (np.inf, np.inf, np.inf, np.inf)]
+    rows.append(np.array(sp, dtype=np.float32))
+    # ordinary footprints: a scale from an eighth of a texel to beyond the whole image, any direction, ratios from 1 to beyond 16
+    n = 1500
+    scale = 2.0 ** rng.uniform(-3.0, L + 0.5, n)
+    ang = rng.uniform(0, 2 * np.pi, n)
+    ratio = rng.choice([1.0, 1.2, 1.37, 1.8, 2.4, 2.9, 3.6, 4.5, 5.5, 6.4, 7.5, 8.6, 9.5, 10.4, 11.3, 12.5, 13.6, 14.4, 15.6, 17.0, 40.0], n)
+    major = np.stack([np.cos(ang) / W, np.sin(ang) / H], axis=1) * scale[:, None]
+    minor = np.stack([-np.sin(ang) / W, np.cos(ang) / H], axis=1) * (scale / ratio)[:, None]
+    swap = (np.arange(n) % 2 == 0)[:, None]
+    rows.append(np.concatenate([np.where(swap, minor, major), np.where(swap, major, minor)], axis=1).astype(np.float32))
+    f = np.concatenate(rows).astype(np.float32)
+    f.setflags(write=False)
+    return f
+
+
+def tex_footprint(w, h):
+    f = footprints(w, h)
+    head = np.tile(np.array([w, h, levels_of(w, h)], dtype=U), (len(f), 1))
+    return np.concatenate([head, f2u(f).reshape(-1, 4)], axis=1)
+
+
+def _axis_coordinates(n, rng):
+    """coordinates along an axis of n texels: every texel centre and every texel edge k / n +- 1 ulp of levels 0 and 1; 0, 1, -0; the
+    largest negative float (u - floor(u) rounds to exactly 1); values in [-3, 4]; 2^23 + 0.5, 1e30, 3e38; +-inf, NaN"""
+    out = []
+    for m in (n, max(1, n >> 1)):
+        k = np.arange(m + 1, dtype=np.float64)
+        out.append(f2u(((k[:-1] + 0.5) / m).astype(np.float32)))
+        out.append(around((k / m).astype(np.float32), 1))
+    out.append(np.array([0, 0x3F800000, 0x80000000, 0x80000001, 0x3F7FFFFF, 0xBF800000, 0x3F000000], dtype=U))
+    out.append(f2u(rng.uniform(-3.0, 4.0, 400).astype(np.float32)))
+    out.append(f2u(np.array([2.0 ** 23 + 0.5, -(2.0 ** 23 + 0.5), 1e30, -1e30, 3e38, np.inf, -np.inf, np.nan, 1e-40, -1e-40], dtype=np.float32)))
+    return np.unique(np.concatenate(out))
+
+
+WRAP_COORDS = np.array([0, 0x80000000, 0x80000001, 0x3F7FFFFF, 0x3F800000, 0x3F000000], dtype=U)     # 0, -0, -tiny, 1 - ulp, 1, 0.5
+
+
+@functools.lru_cache(maxsize=None)
+def tex_cases(w, h, cap=250000):
+    """cases u, v, dudx, dvdx, dudy, dvdy for a w x h image: every coordinate of _axis_coordinates on either axis and every footprint of
+    footprints() at least once, paired by a seeded shuffle; then the wrap block - the coordinates next to 0 and 1 on both axes under a
+    single-tap footprint on every level of the chain, so that both wraps of both axes are reached on every level."""
+    rng = np.random.default_rng(20272 + 131 * w + h)
+    cu, cv, f = _axis_coordinates(w, rng), _axis_coordinates(h, rng), f2u(footprints(w, h)).reshape(-1, 4)
+    n = min(cap - 2000, max(len(cu), len(cv), len(f), 6000) * 2)
+    assert n >= max(len(cu), len(cv), len(f)), (w, h)
+
+    def spread(m):
+        return rng.permutation(np.concatenate([np.arange(m), rng.integers(0, m, n - m)]))
+    body = np.concatenate([cu[spread(len(cu))].reshape(-1, 1), cv[spread(len(cv))].reshape(-1, 1), f[spread(len(f))]], axis=1)
+    wrap = []
+    for l in range(levels_of(w, h)):
+        for lam in (l, l + 0.5):
+            fp = f2u(np.array([2.0 ** lam / w, 0, 0, 2.0 ** lam / h], dtype=np.float32))
+            for a in WRAP_COORDS:
+                for b in WRAP_COORDS:
+                    wrap.append(np.concatenate([[a, b], fp]))
+    t = np.concatenate([body, np.array(wrap, dtype=U)]).astype(U)
+    assert len(t) <= cap
+    t.setflags(write=False)
+    return t
+
+
+def tap_addresses(w, h, case_bits, lam):
+    """for single-tap cases (N = 1): the level pair and, on level l0, floor(x) and floor(y) of zr_texture.h's addressing (x = fma(u - floor u, w_l, -0.5)),
+    restated for the coverage claims only.  Returns l0, l1, fx, fy, w_l0, h_l0."""
+    L = levels_of(w, h)
+    c = u2f(case_bits[:, :2]).reshape(-1, 2)
+    with np.errstate(all="ignore"):
+        l0 = np.floor(lam).astype(np.int64)
+        l1 = np.minimum(l0 + 1, L - 1)
+        wl, hl = np.maximum(1, w >> l0), np.maximum(1, h >> l0)
+        r = (c - np.floor(c)).astype(np.float32).astype(np.float64)
+        x = (r[:, 0] * wl - 0.5).astype(np.float32)          # the product is exact in float64: one rounding, as the fma
+        y = (r[:, 1] * hl - 0.5).astype(np.float32)
+        return l0, l1, np.floor(x), np.floor(y), wl, hl
+
+
+class Textures:
+    """A material's seven slots: an (h, w, 4) uint8 image, a 4-tuple of codes (a constant slot), or None (the engine's default texel is
+    not needed here: a constant of zeros).  Slot 0 is sRGB, the others UNORM, as BaseScene.frag samples them."""
+
+    def __init__(self, slots):
+        assert len(slots) == 7
+        self.slots = [np.ascontiguousarray(s, dtype=np.uint8) if s is not None else np.zeros(4, np.uint8) for s in slots]
+
+    def is_image(self, s):
+        return self.slots[s].ndim == 3
+
+    def oracle(self, pyoracle):
+        """an oracle context holding the slots; every image stays an image (as_image), every constant is a 1 x 1 image that collapses.
+        Leaves the chains (the oracle's), the decode table and the decoded constants for the probe."""
+        o = pyoracle.Oracle(8, 8, 8)
+        L = o.L
+        self.lut = np.array([L.zo_kat_srgb8_to_linear(c) for c in range(256)], dtype=np.float32)
+        self.chains, self.constants = [None] * 7, np.zeros((7, 4), dtype=np.float32)
+        for s, im in enumerate(self.slots):
+            if self.is_image(s):
+                h, w = im.shape[:2]
+                assert L.zo_kat_set_image(o.h, s, im.ctypes.data, w, h, int(s == 0), 1) == levels_of(w, h)
+                mips = o.tex_mips(im, s == 0)
+                assert len(mips) == levels_of(w, h) and all(m.shape[:2] == level_size(w, h, l)[::-1] for l, m in enumerate(mips))
+                self.chains[s] = np.concatenate([m.ravel() for m in mips])
+            else:
+                assert L.zo_kat_set_image(o.h, s, im.ctypes.data, 1, 1, int(s == 0), 0) == 1
+                zero = np.zeros((1, 6), dtype=U)
+                self.constants[s] = u2f(self.oracle_image(o, s, zero, srgb=(s == 0)))[0]
+        return o
+
+    def oracle_image(self, o, slot, table, srgb):
+        table = np.ascontiguousarray(table, dtype=U)
+        out = np.zeros((len(table), 4), dtype=U)
+        o.L.zo_kat_tex_image_batch(o.h, slot, int(srgb), table.ctypes.data, out.ctypes.data, len(table))
+        return out
+
+    def oracle_material(self, o, table):
+        table = np.ascontiguousarray(table, dtype=U)
+        out = np.zeros((len(table), 28), dtype=U)
+        o.L.zo_kat_tex_material_batch(o.h, table.ctypes.data, out.ctypes.data, len(table))
+        return out
+
+
+def single_image(w, h, srgb, seed=0):
+    """a Textures whose only image sits in slot 0 (sampled as sRGB) or slot 1 (UNORM); returns it and the slot"""
+    slot = 0 if srgb else 1
+    s = [None] * 7
+    s[slot] = noise_image(w, h, seed)
+    return Textures(s), slot
+
+
+# The material sets.  Slots equal in w and h but not in levels cannot exist: the level count is a function of the size
+# (floor(log2(max(w, h))) + 1, on the product's host as in the oracle), so that row of the grouping test has no case.
+def material_one_size(w, h):
+    return Textures([noise_image(w, h, seed=s) for s in range(7)])
+
+
+def material_three_sizes():
+    """64 x 64, 33 x 7 and 16 x 1 across the slots, constant slots between them: three grouping turns"""
+    return Textures([noise_image(64, 64, 0), (10, 200, 30, 255), noise_image(33, 7, 2), noise_image(64, 64, 3), (255, 0, 128, 7), noise_image(16, 1, 5),
+                     noise_image(33, 7, 6)])
+
+
+def material_lead_not_zero():
+    """slot 0 constant: the first group is led by slot 1; two sizes, two turns"""
+    return Textures([(180, 90, 45, 255), noise_image(48, 20, 1), noise_image(48, 20, 2), (128, 128, 255, 255), noise_image(2, 2, 4), None, noise_image(2, 2, 6)])
+
+
+def material_cases(tex, cap=60000):
+    """the cases of a material: the tables of its distinct image sizes, thinned to `cap` rows in all"""
+    sizes = sorted({tex.slots[s].shape[1::-1] for s in range(7) if tex.is_image(s)})
+    parts = []
+    for w, h in sizes:
+        t = tex_cases(w, h)
+        k = max(1, -(-len(t) * len(sizes) // cap))
+        parts.append(t[::k])
+    return np.concatenate(parts)
+
+
+# ------------------------------------------------------------------------------------------------------------------ the surface stage (zr_surface.h)
+
+def compute_normal():
+    """pos_dx, pos_dy, s1, t1, s2, t2, fragN, ts.  The determinant s1 t2 - s2 t1 exactly 0 by constant UVs, by collinear UVs (0.25, 0.5) /
+    (0.5, 1) and, with it non-zero, a zero position derivative; denormal; of either sign; T parallel to N; fragN zero, denormal, infinite,
+    NaN; ts = (0, 0, 1), the default normal map's; 2 000 ordinary fragments (derivatives of a hundredth, a unit normal, a tangent-space
+    normal in the upper hemisphere); then generic vectors."""
+    uvs = [(0, 0, 0, 0), (0.25, 0.5, 0.5, 1.0), (-0.25, 0.5, 0.5, -1.0), (0.01, 0.0, 0.0, 0.01), (0.0, 0.01, 0.01, 0.0), (0.013, -0.004, 0.002, 0.009),
+           (1e-20, 0, 0, 1e-20), (1e-20, 0, 0, -1e-20), (1e-23, 0, 0, 1e-23), (0.0, 0.0, 0.0, 1.0), (1.0, 0.0, 0.0, 1.0), (3e38, 0, 0, 3e38)]
+    pds = [((0.01, 0.0, 0.002), (0.0, 0.01, 0.001)), ((0, 0, 0), (0, 0, 0)), ((0, 0, 0), (0.0, 0.01, 0.001)), ((0.5, 0.25, -0.125), (0.0, 0.0, 0.0)),
+           ((1e-30, 0, 0), (0, 1e-30, 0))]
+    ns = [(0, 0, 1), (0.3, -0.5, 0.8), (0.5, 0.25, -0.125), (0.01, 0.0, 0.002), (0, 0, 0), (1e-40, 0, 0), (1e-30, 1e-30, 0), (np.inf, 0, 0),
+          (np.nan, 0, 1), (0, 0, -3e38)]
+    tss = [(0, 0, 1), (0.3, -0.2, 0.93), (-0.0, 0.0, 1.0), (1, 0, 0)]
+    rows = [pdx + pdy + uv + n + ts for uv in uvs for pdx, pdy in pds for n in ns for ts in tss]
+    rng = np.random.default_rng(20276)
+    n = 2000
+    nrm = rng.normal(size=(n, 3))
+    tsn = rng.normal(size=(n, 3)) * (0.4, 0.4, 1.0)
+    tsn[:, 2] = np.abs(tsn[:, 2]) + 0.2
+    plain = np.concatenate([rng.uniform(-0.02, 0.02, (n, 6)), rng.uniform(-0.02, 0.02, (n, 4)), nrm / np.linalg.norm(nrm, axis=1, keepdims=True),
+                            tsn / np.linalg.norm(tsn, axis=1, keepdims=True)], axis=1).astype(np.float32)
+    return np.concatenate([f2u(np.array(rows, dtype=np.float32)).reshape(-1, 16), f2u(plain).reshape(-1, 16), vectors(16)])
+
+
+PROJECT_TARGETS = ((640.0, 360.0), (0.5, 0.5), (2048.0, 2048.0), (127.5, 72.5))        # project()'s (hw, hh) blocks, in its order
+MAX_PIXEL = 16383
+PROJECT_SATURATED = 1 << 30       # |X| or |Y| from here on: project() has clamped an infinite coordinate
+
+
+def bary_screen(L):
+    """X0, Y0, a1, b1, a2, b2, rw0, rw1, rw2, px, py.  The set-ups are pixel_geom's, formed (here, in float32, from integer differences that
+    float32 holds exactly) from triples of project()'s results over its own table - a fast-path triangle holds only such corners; pixels
+    around the first corner and at 0 and 16383, each with its quad partners px ^ 1 and py ^ 1; then rw sums that are 0, denormal, huge.
+    Corners whose project() saturates are left out: a denormal w makes rw infinite and snaps X, Y to INT_MIN (320 of the table's 5 984
+    rows, all with w = 2^-149), and px * 256 + 128 - X0 then leaves int in the product's bary_screen as in the oracle's - signed overflow,
+    undefined on both sides, so there is nothing to compare.  The coverage test asserts the bound on what remains."""
+    rng = np.random.default_rng(20273)
+    sv = oracle_batch(L, "project", project())
+    per = len(sv) // len(PROJECT_TARGETS)
+    rows = []
+    for b in range(len(PROJECT_TARGETS)):
+        blk = sv[b * per:(b + 1) * per]
+        X, Y, rw = blk[:, 0].astype(np.int32).astype(np.int64), blk[:, 1].astype(np.int32).astype(np.int64), u2f(blk[:, 3])
+        keep = (np.abs(X) < PROJECT_SATURATED) & (np.abs(Y) < PROJECT_SATURATED)
+        X, Y, rw, n = X[keep], Y[keep], rw[keep], int(keep.sum())
+        i = rng.integers(0, n, (1500, 3))
+        x, y = X[i], Y[i]
+        A = (x[:, 1] - x[:, 0]) * (y[:, 2] - y[:, 0]) - (x[:, 2] - x[:, 0]) * (y[:, 1] - y[:, 0])
+        with np.errstate(all="ignore"):
+            invA = np.float32(1.0) / A.astype(np.float32)
+            a1, b1 = (y[:, 2] - y[:, 0]).astype(np.float32) * invA, (x[:, 0] - x[:, 2]).astype(np.float32) * invA
+            a2, b2 = (y[:, 0] - y[:, 1]).astype(np.float32) * invA, (x[:, 1] - x[:, 0]).astype(np.float32) * invA
+        r = rw[i].copy()
+        kind = np.arange(len(i)) % 12
+        for k, v in ((8, (0.0, 0.0, 0.0)), (9, (1e-40, 1e-41, 0.0)), (10, (3e38, 3e38, 3e38)), (11, (1.0, -1.0, 0.0))):
+            r[kind == k] = np.array(v, dtype=np.float32)
+        px = np.clip((x[:, 0] >> 8) + rng.integers(-3, 4, len(i)), 0, MAX_PIXEL)
+        py = np.clip((y[:, 0] >> 8) + rng.integers(-3, 4, len(i)), 0, MAX_PIXEL)
+        px[kind == 1], py[kind == 1] = 0, 0
+        px[kind == 2], py[kind == 2] = MAX_PIXEL, MAX_PIXEL
+        head = np.column_stack([x[:, 0].astype(np.int32).view(U), y[:, 0].astype(np.int32).view(U), f2u(a1), f2u(b1), f2u(a2), f2u(b2), f2u(r).reshape(-1, 3)])
+        for qx, qy in ((px, py), (px ^ 1, py), (px, py ^ 1)):
+            rows.append(np.column_stack([head, qx.astype(U), qy.astype(U)]))
+    return np.concatenate(rows).astype(U)
+
+
+def bary_homog():
+    """three clip-space corners from clip_vertices() (w <= 0 on one and on two of them among the triples), hw, hh, px, py with the quad
+    partners; three equal corners (every k is 0: the denominator is 0)"""
+    rng = np.random.default_rng(20274)
+    v = clip_vertices()
+    rows = []
+    for hw, hh in PROJECT_TARGETS:
+        i = rng.integers(0, len(v), (1500, 3))
+        i[::50, 1] = i[::50, 0]
+        i[::50, 2] = i[::50, 0]
+        tri = np.concatenate([v[i[:, 0]], v[i[:, 1]], v[i[:, 2]]], axis=1)
+        px = rng.integers(0, max(1, int(2 * hw)), len(i))
+        py = rng.integers(0, max(1, int(2 * hh)), len(i))
+        px[1::50], py[1::50] = MAX_PIXEL, MAX_PIXEL
+        t = np.tile(f2u(np.array([hw, hh], dtype=np.float32)), (len(i), 1))
+        for qx, qy in ((px, py), (px ^ 1, py), (px, py ^ 1)):
+            rows.append(np.column_stack([tri, t, qx.astype(U), qy.astype(U)]))
+    return np.concatenate(rows).astype(U)
+
+
+def stage_roll(angle=0.37):
+    """glm::rotate(mat4(1), angle, z) with a translation, column-major"""
+    c, s = np.float32(np.cos(angle)), np.float32(np.sin(angle))
+    return np.array([c, s, 0, 0, -s, c, 0, 0, 0, 0, 1, 0, 0.5, -2.0, 0.25, 1], dtype=np.float32)
+
+
+def model_point():
+    """M, p, m_identity.  The flag is what the host sets when M is bit for bit the identity, and the short cut p + 0 is M * vec4(p, 1)
+    for a p whose components are all finite or all NaN: flag 1 rows hold exactly that.  Through the matrix an infinite component gives
+    inf * 0 = NaN, and one NaN component makes all three NaN, where the short cut keeps the others; neither reaches it.  Its callers pass
+    the position of a corner of a triangle that won a pixel (classify() lets only finite clip coordinates through, so the position is
+    finite) and normalize(normal) - finite, all NaN, or NaN with zeros from an infinite component, whose only reader, compute_normal,
+    normalises first and so sees NaN either way.  Flag 0: the identity over every p, a stage roll, an identity whose
+    translation is -0 (not the identity bit for bit), generic matrices."""
+    g = generic()
+    fin = g[np.isfinite(u2f(g))]
+    nan = g[np.isnan(u2f(g))]
+    rng = np.random.default_rng(20275)
+
+    def rows(M, p, flag):
+        return np.concatenate([np.tile(f2u(M), (len(p), 1)), p, np.full((len(p), 1), flag, dtype=U)], axis=1)
+    p1 = np.concatenate([np.stack([fin, rng.permutation(fin), rng.permutation(fin)], axis=1), np.stack([nan, rng.permutation(nan), rng.permutation(nan)], axis=1)])
+    p0 = np.stack([g, rng.permutation(g), rng.permutation(g)], axis=1)
+    neg0 = IDENTITY.copy()
+    neg0[12:15] = -0.0
+    v = vectors(19)
+    return np.concatenate([rows(IDENTITY, p1, 1), rows(IDENTITY, p0, 0), rows(stage_roll(), p0[::4], 0), rows(neg0, p0[::4], 0),
+                           np.concatenate([v, np.zeros((len(v), 1), dtype=U)], axis=1)]).astype(U)
+
+
+# ---- a constant image that is still an image (oracle/CONTRACT.md, "a constant image")
+CONSTANT_CODES = (1, 37, 90, 143, 201, 254)
+CONSTANT_SIDE = 4
+
+
+def constant_image_cases():
+    """u, v inside the image and NaN, under the exact-breakpoint footprints of every N in 1..16 (x the major axis)"""
+    bp = footprint_breakpoints(CONSTANT_SIDE, CONSTANT_SIDE)
+    f = f2u(bp[(bp[:, 5] == 0) & (bp[:, 6] == 0), :4].astype(np.float32)).reshape(-1, 4)
+    uv = np.array([[0x3E99999A, 0x3F333333], [NAN_Q, 0x3F333333], [0x3E99999A, INF]], dtype=U)          # (0.3, 0.7), a NaN u, an infinite v
+    return np.concatenate([np.concatenate([np.tile(c, (len(f), 1)), f], axis=1) for c in uv]).astype(U)
+
+
+def constant_image(code, pyoracle, table):
+    """a Textures whose slot 0 is a 4 x 4 image of (code, 255 - code, code / 2, 255) throughout; the oracle's samples of `table` with the
+    slot kept an image (filtered) and collapsed to its texel"""
+    im = np.empty((CONSTANT_SIDE, CONSTANT_SIDE, 4), np.uint8)
+    im[:] = (code, 255 - code, code // 2, 255)
+    tex = Textures([im] + [None] * 6)
+    o = tex.oracle(pyoracle)
+    filtered = tex.oracle_image(o, 0, table, True)
+    assert o.L.zo_kat_set_image(o.h, 0, im.ctypes.data, CONSTANT_SIDE, CONSTANT_SIDE, 1, 0) == levels_of(CONSTANT_SIDE, CONSTANT_SIDE)
+    collapsed = tex.oracle_image(o, 0, table, True)
+    o.close()
+    return tex, filtered, collapsed

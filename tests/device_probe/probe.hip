@@ -4,6 +4,8 @@
 //
 // A case is IN[fn] 32-bit words in and OUT[fn] words out (floats as their bits); thread i handles case i, bounds-checked against n.
 #include "../../zeldaengine_amd/csrc/zr_shade.h"
+#include "../../zeldaengine_amd/csrc/zr_surface.h"
+#include "../../zeldaengine_amd/csrc/zr_ctx.h"          // kSlotPack: where each material slot's channels sit in a packed texel
 
 #include <cstring>
 
@@ -16,19 +18,23 @@ enum {
     ZP_DIV, ZP_SQRT, ZP_DOT, ZP_CROSS, ZP_NORMALIZE, ZP_TANGENT_NORMAL, ZP_MAT4_POINT,
     ZP_INSTANCE_RECORD, ZP_VS_POSITION, ZP_VS_NORMAL, ZP_CLASSIFY, ZP_PROJECT,
     ZP_F_SCHLICK, ZP_FR_DISNEY, ZP_V_SMITH, ZP_D_GGX, ZP_SHADOW_TAP,
-    ZP_CUBE_SAMPLE, ZP_PCF_TAPS, ZP_SHADE, ZP_SHADE_MASKED, ZP_COUNT
+    ZP_CUBE_SAMPLE, ZP_PCF_TAPS, ZP_SHADE, ZP_SHADE_MASKED,
+    ZP_TEX_FOOTPRINT, ZP_TEX_IMAGE, ZP_TEX_MATERIAL, ZP_TEX_PACKED, ZP_BARY_SCREEN, ZP_BARY_HOMOG, ZP_INTERP, ZP_COMPUTE_NORMAL, ZP_MODEL_POINT,
+    ZP_F32_TO_F16_HW, ZP_F16_TO_F32_HW, ZP_COUNT
 };
-//                                      rsq sc ex lg pw p5 sat cl un h2f f2h u8 div sq dot cr nrm tsn m4p  inst vsp vsn cls prj  Fs Fd Vs Dg tap cube pcf shade masked
-constexpr int zp_in(int fn)  { constexpr int t[ZP_COUNT] = { 1, 1, 1, 1, 2, 1, 1,  3, 2, 1,  1,  1, 2,  1, 6,  6, 3,  3,  19,  8,   19, 36, 12, 6,   3, 4, 3, 2, 6, 4, 3, 23, 23 }; return t[fn]; }
-constexpr int zp_out(int fn) { constexpr int t[ZP_COUNT] = { 1, 2, 1, 1, 1, 1, 1,  1, 1, 1,  1,  1, 1,  1, 1,  3, 3,  3,  4,   16,  3,  3,  1,  4,   1, 1, 1, 1, 1, 3, 1, 10, 10 }; return t[fn]; }
+//                                      rsq sc ex lg pw p5 sat cl un h2f f2h u8 div sq dot cr nrm tsn m4p  inst vsp vsn cls prj  Fs Fd Vs Dg tap cube pcf shade masked fp img mat pk  bs  bh  ip  cn  mp  f2h h2f
+constexpr int zp_in(int fn)  { constexpr int t[ZP_COUNT] = { 1, 1, 1, 1, 2, 1, 1,  3, 2, 1,  1,  1, 2,  1, 6,  6, 3,  3,  19,  8,   19, 36, 12, 6,   3, 4, 3, 2, 6, 4, 3, 23, 23,   7, 6,  6,  6,  11, 16, 12, 16, 20, 1,  1 }; return t[fn]; }
+constexpr int zp_out(int fn) { constexpr int t[ZP_COUNT] = { 1, 2, 1, 1, 1, 1, 1,  1, 1, 1,  1,  1, 1,  1, 1,  3, 3,  3,  4,   16,  3,  3,  1,  4,   1, 1, 1, 1, 1, 3, 1, 10, 10,   4, 4,  28, 13, 3,  3,  4,  3,  3,  1,  1 }; return t[fn]; }
 
 // What the functions that read more than their case are handed (device pointers): the shadow map, the cubemap's mip chain and its sRGB
-// decode table, the frame's XkView, and the lighting pass's uniforms as k_lighting holds them.
+// decode table, the frame's XkView, and the lighting pass's uniforms as k_lighting holds them; for the sampler a draw record whose material
+// slots (and packed form) hold the run's images, and which slot tex_image samples, as sRGB or UNORM.
 struct ZpDev {
     const float* map; int SD;
     CubeDesc cube; const float* lut;
     const XkView* view; ZrLightParams L;
     uint32_t nDir, nPoint; float maxmips, dxy;
+    const ZrObject* obj; int slot, srgb;
 };
 
 __device__ __forceinline__ void put3(uint32_t* o, zf3 v) { o[0] = zr_f2u(v.x); o[1] = zr_f2u(v.y); o[2] = zr_f2u(v.z); }
@@ -109,7 +115,47 @@ __global__ void k_probe(const uint32_t* __restrict__ in, uint32_t* __restrict__ 
                                              zr3(f[3], f[4], f[5]), f[6], f[7], zr3(f[8], f[9], f[10]), f[11], zr3(f[12], f[13], f[14]),
                                              Direct, Indirect, RefC, SF);
         put3(o, Direct); put3(o + 3, Indirect); put3(o + 6, RefC); o[9] = zr_f2u(SF);
-    }
+    } else if constexpr (FN == ZP_TEX_FOOTPRINT) {      // w, h, levels of an image (no texel is read), then dudx, dvdx, dudy, dvdy
+        ZrTex T;
+        T.data = nullptr; T.w = a[0]; T.h = a[1]; T.levels = a[2]; T._pad = 0u;
+        const TexFootprint F = tex_footprint(T, f[3], f[4], f[5], f[6]);
+        o[0] = (uint32_t)F.N; o[1] = zr_f2u(F.lambda); o[2] = zr_f2u(F.du); o[3] = zr_f2u(F.dv);
+    } else if constexpr (FN == ZP_TEX_IMAGE) {          // u, v, dudx, dvdx, dudy, dvdy; a slot without an image takes the constant arm
+        const zf4 r = tex_sample<1>(D.obj->tex[D.slot], D.obj->texc[D.slot], D.srgb != 0, D.lut, f[0], f[1], f[2], f[3], f[4], f[5]);
+        o[0] = zr_f2u(r.x); o[1] = zr_f2u(r.y); o[2] = zr_f2u(r.z); o[3] = zr_f2u(r.w);
+    } else if constexpr (FN == ZP_TEX_MATERIAL) {
+        zf4 ms[ZR_MATERIAL_SLOTS];
+        tex_sample_material(D.obj, D.lut, f[0], f[1], f[2], f[3], f[4], f[5], ms);
+#pragma unroll
+        for (int s = 0; s < ZR_MATERIAL_SLOTS; ++s) { o[4 * s] = zr_f2u(ms[s].x); o[4 * s + 1] = zr_f2u(ms[s].y); o[4 * s + 2] = zr_f2u(ms[s].z); o[4 * s + 3] = zr_f2u(ms[s].w); }
+    } else if constexpr (FN == ZP_TEX_PACKED) {
+        float pk[ZR_PK_CHANNELS];
+        tex_sample_packed(D.obj->packed, D.lut, f[0], f[1], f[2], f[3], f[4], f[5], pk);
+#pragma unroll
+        for (int k = 0; k < ZR_PK_CHANNELS; ++k) o[k] = zr_f2u(pk[k]);
+    } else if constexpr (FN == ZP_BARY_SCREEN) {        // a FastSetup as pixel_geom fills it, px, py
+        FastSetup fs;
+        fs.X0 = (int)a[0]; fs.Y0 = (int)a[1]; fs.a1 = f[2]; fs.b1 = f[3]; fs.a2 = f[4]; fs.b2 = f[5]; fs.rw0 = f[6]; fs.rw1 = f[7]; fs.rw2 = f[8];
+        const Bary b = bary_screen(fs, (int)a[9], (int)a[10]);
+        o[0] = zr_f2u(b.b0); o[1] = zr_f2u(b.b1); o[2] = zr_f2u(b.b2);
+    } else if constexpr (FN == ZP_BARY_HOMOG) {         // three clip-space corners, hw, hh, px, py
+        zf4 c[3];
+        __builtin_memcpy(c, f, sizeof c);
+        const Bary b = bary_homog(c, f[12], f[13], (int)a[14], (int)a[15]);
+        o[0] = zr_f2u(b.b0); o[1] = zr_f2u(b.b1); o[2] = zr_f2u(b.b2);
+    } else if constexpr (FN == ZP_INTERP) {             // b, three vec3 attributes: interp3 of them, interp1 of (A0.x, A1.y, A2.z)
+        Bary b; b.b0 = f[0]; b.b1 = f[1]; b.b2 = f[2];
+        put3(o, interp3(b, zr3(f[3], f[4], f[5]), zr3(f[6], f[7], f[8]), zr3(f[9], f[10], f[11])));
+        o[3] = zr_f2u(interp1(b, f[3], f[7], f[11]));
+    } else if constexpr (FN == ZP_COMPUTE_NORMAL) {     // pos_dx, pos_dy, s1, t1, s2, t2, fragN, ts
+        put3(o, compute_normal(zr3(f[0], f[1], f[2]), zr3(f[3], f[4], f[5]), f[6], f[7], f[8], f[9], zr3(f[10], f[11], f[12]), zr3(f[13], f[14], f[15])));
+    } else if constexpr (FN == ZP_MODEL_POINT) {        // M, p, m_identity
+        ZrPass P;
+        __builtin_memcpy(P.M, f, sizeof P.M);
+        P.m_identity = a[19];
+        put3(o, model_point(P, zr3(f[16], f[17], f[18])));
+    } else if constexpr (FN == ZP_F32_TO_F16_HW) o[0] = f32_to_f16_hw(f[0]);
+    else if constexpr (FN == ZP_F16_TO_F32_HW) o[0] = zr_f2u(f16_to_f32_hw(a[0]));
 }
 
 namespace {
@@ -157,6 +203,7 @@ extern "C" int zp_run_scene(int fn, const void* in, void* out, uint32_t n, const
 {
     if (hip_error) *hip_error = 0;
     if (fn < 0 || fn >= ZP_COUNT || !in || !out || n == 0u || n > (1u << 22)) return ZP_ERR_ARG;
+    if (fn == ZP_TEX_IMAGE || fn == ZP_TEX_MATERIAL || fn == ZP_TEX_PACKED) return ZP_ERR_ARG;           // zp_run_textures
     const bool shade = fn == ZP_SHADE || fn == ZP_SHADE_MASKED;
     const bool need_map = fn == ZP_SHADOW_TAP || fn == ZP_PCF_TAPS || shade, need_cube = fn == ZP_CUBE_SAMPLE || shade;
     if ((need_map || need_cube) && !sc) return ZP_ERR_ARG;
@@ -202,3 +249,86 @@ extern "C" int zp_run_scene(int fn, const void* in, void* out, uint32_t n, const
     return ZP_OK;
 }
 extern "C" int zp_run(int fn, const void* in, void* out, uint32_t n) { return zp_run_scene(fn, in, out, n, nullptr, nullptr); }
+
+// ---- the sampler (zr_texture.h): its images travel beside the table, as a material's seven slots.
+// A slot is an image - its whole mip chain as the product holds it, level after level, `bytes` long - or, chain == nullptr, the constant
+// `constant` (what the host decodes once into ZrObject::texc).  tex_image samples slot `image_slot` as sRGB (srgb != 0) or UNORM;
+// tex_material samples all seven; tex_packed samples the packed form, which this function lays out from the chains by the product's
+// kSlotPack, as zr_object_remake_material does.  What the product's host refuses is refused here (ZP_ERR_ARG): a side of 0 or above
+// 16384, a level count that is not the chain's, more than 16 levels, and a packed form over images of different sizes - so no table can
+// hand the kernels an image the product could not hold.
+struct zp_slot { const uint8_t* chain; uint64_t bytes; uint32_t w, h, levels, texel; float constant[4]; };
+struct zp_textures { zp_slot slot[ZR_MATERIAL_SLOTS]; const float* lut; int32_t image_slot, srgb; };
+
+static bool chain_ok(const zp_slot& s)
+{
+    if (s.w == 0u || s.h == 0u || s.w > 16384u || s.h > 16384u || s.levels == 0u || s.levels > 16u) return false;
+    uint32_t m = s.w > s.h ? s.w : s.h, levels = 1;
+    while (m > 1u) { m >>= 1; ++levels; }
+    uint64_t bytes = 0;
+    for (uint32_t l = 0; l < levels; ++l) { uint32_t lw = s.w >> l, lh = s.h >> l; if (!lw) lw = 1; if (!lh) lh = 1; bytes += (uint64_t)lw * lh * 4u; }
+    return levels == s.levels && bytes == s.bytes;
+}
+
+extern "C" int zp_run_textures(int fn, const void* in, void* out, uint32_t n, const zp_textures* tx, int* hip_error)
+{
+    if (hip_error) *hip_error = 0;
+    if ((fn != ZP_TEX_IMAGE && fn != ZP_TEX_MATERIAL && fn != ZP_TEX_PACKED) || !in || !out || !tx || !tx->lut || n == 0u || n > (1u << 22)) return ZP_ERR_ARG;
+    if (fn == ZP_TEX_IMAGE && (tx->image_slot < 0 || tx->image_slot >= ZR_MATERIAL_SLOTS)) return ZP_ERR_ARG;
+    int lead = -1;
+    for (int s = 0; s < ZR_MATERIAL_SLOTS; ++s) {
+        const zp_slot& sl = tx->slot[s];
+        if (!sl.chain) continue;
+        if (!chain_ok(sl)) return ZP_ERR_ARG;
+        if (lead < 0) lead = s;
+        else if (fn == ZP_TEX_PACKED && (sl.w != tx->slot[lead].w || sl.h != tx->slot[lead].h)) return ZP_ERR_ARG;
+    }
+    if (fn == ZP_TEX_PACKED && lead < 0) return ZP_ERR_ARG;
+    ZrObject O;
+    memset(&O, 0, sizeof O);
+    ZpDev D;
+    memset(&D, 0, sizeof D);
+    const size_t bin = (size_t)n * zp_in(fn) * 4, bout = (size_t)n * zp_out(fn) * 4;
+    DevBuf din, dout, dlut, dobj, dpk, dtex[ZR_MATERIAL_SLOTS];
+    hipError_t e = upload(din, in, bin);
+    if (e == hipSuccess) e = hipMalloc(&dout.p, bout);
+    if (e == hipSuccess) e = hipMemset(dout.p, 0xCD, bout);
+    if (e == hipSuccess) e = upload(dlut, tx->lut, 256 * 4);
+    for (int s = 0; s < ZR_MATERIAL_SLOTS && e == hipSuccess; ++s) {
+        const zp_slot& sl = tx->slot[s];
+        memcpy(O.texc[s], sl.constant, sizeof sl.constant);
+        O.texel[s] = sl.texel;
+        if (!sl.chain) { O.const_slots |= 1u << s; continue; }
+        e = upload(dtex[s], sl.chain, (size_t)sl.bytes);
+        O.tex[s].data = (const uint8_t*)dtex[s].p; O.tex[s].w = sl.w; O.tex[s].h = sl.h; O.tex[s].levels = sl.levels;
+    }
+    if (e == hipSuccess && fn == ZP_TEX_PACKED) {
+        const size_t n_texels = (size_t)tx->slot[lead].bytes / 4;
+        std::vector<uint8_t> pk(n_texels * 16, 0);
+        for (int s = 0; s < ZR_MATERIAL_SLOTS; ++s) {
+            const auto& k = kSlotPack[s];
+            const uint8_t* src = tx->slot[s].chain;
+            for (size_t i = 0; i < n_texels; ++i)
+                for (uint32_t ch = 0; ch < k.n; ++ch) pk[i * 16 + k.ch + ch] = src ? src[i * 4 + ch] : (uint8_t)(tx->slot[s].texel >> (8 * ch));
+        }
+        e = upload(dpk, pk.data(), pk.size());
+        O.packed.data = (const uint8_t*)dpk.p; O.packed.w = tx->slot[lead].w; O.packed.h = tx->slot[lead].h; O.packed.levels = tx->slot[lead].levels;
+    }
+    if (e == hipSuccess) e = upload(dobj, &O, sizeof O);
+    D.obj = (const ZrObject*)dobj.p; D.lut = (const float*)dlut.p; D.slot = tx->image_slot; D.srgb = tx->srgb;
+    if (e == hipSuccess) e = dispatch<0>(fn, (const uint32_t*)din.p, (uint32_t*)dout.p, n, D);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, dout.p, bout, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        if (hip_error) *hip_error = (int)e;
+        return ZP_ERR_HIP;
+    }
+    return ZP_OK;
+}
+// where slot `slot`'s channels sit in tex_packed's 13 result words (the product's kSlotPack): first channel and count
+extern "C" int zp_slot_pack(int slot, uint32_t* first, uint32_t* count)
+{
+    if (slot < 0 || slot >= ZR_MATERIAL_SLOTS || !first || !count) return ZP_ERR_ARG;
+    *first = kSlotPack[slot].ch; *count = kSlotPack[slot].n;
+    return ZP_OK;
+}

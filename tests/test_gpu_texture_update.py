@@ -226,6 +226,61 @@ def test_updates_through_both_forms_match_the_oracle(gpu_engine, oracle_lib):
     g.close(); o.close()
 
 
+@pytest.mark.parametrize("forward", [False, True], ids=["deferred", "forward"])
+def test_a_constant_image_set_into_a_slot_is_filtered_like_any_image(gpu_engine, oracle_lib, forward):
+    """A texture update does not look at the texels it is given (the device form cannot), so a slot that holds an image keeps holding one
+    when the new image's texels are all equal, and the kernels filter it: N equal decoded texels averaged, not the texel itself.  In the
+    sRGB slot the two differ by an ulp for many codes and tap counts, which the GBuffer's 8 bits absorb and the forward pass does not.
+    The rule (oracle/CONTRACT.md, "a constant image"): only object_add collapses a constant image; the oracle's object_set_texture keeps
+    the slot an image.  Instanced spheres and a plane seen at a grazing angle (anisotropic footprints), base colour and roughness of the
+    spheres and the base colour of the plane set to constant images through both forms: every target equals the oracle's, bit for bit.
+    For the record the frame is also compared with an oracle whose scene was built with the constant images (collapsed by object_add)."""
+    import torch
+    cfg = scenes.config3(64, 256, 144)
+    images = scenes.synthetic_material(64)
+    mat, keep = abi.make_material(images)
+    cfg["objects"][0]["material"] = mat
+    cfg["objects"].insert(0, {"mesh": scenes.grid_plane(40.0, 4, 0.0), "material": mat})       # (non-instanced: object 0 in add order)
+    flat = [np.empty((64, 64, 4), np.uint8) for _ in range(3)]
+    flat[0][:] = (143, 77, 201, 255)
+    flat[1][:] = (90, 90, 90, 255)
+    flat[2][:] = (31, 250, 6, 255)
+    g = gpu_engine.Renderer(cfg["width"], cfg["height"], 256)
+    g.set_shading(forward)
+    gpu_engine.load_scene(g, cfg)
+    g.render()
+    g.object_set_texture(SPHERES, 0, flat[0])
+    t = _dev(flat[1])
+    torch.cuda.synchronize()
+    g.object_update_texture_async(SPHERES, 2, t)
+    g.object_set_texture(PLANE, 0, flat[2])
+    g.render()
+    g.finish()
+    o = oracle_lib.Oracle(cfg["width"], cfg["height"], 256)
+    o.set_shading(forward)
+    oracle_lib.load_scene(o, cfg)
+    o.object_set_texture(SPHERES, 0, flat[0])
+    o.object_set_texture(SPHERES, 2, flat[1])
+    o.object_set_texture(PLANE, 0, flat[2])
+    o.render()
+    assert o.covered_pixels() > 1000
+    diffs = compare_all(o, g)
+    # the same images handed to object_add, which collapses them: what the oracle drew before it had object_set_texture
+    final_s, final_p = list(images), list(images)
+    final_s[0], final_s[2], final_p[0] = flat[0], flat[1], flat[2]
+    ms, ks = abi.make_material(final_s)
+    mp, kp = abi.make_material(final_p)
+    cfg["objects"][0]["material"], cfg["objects"][1]["material"] = mp, ms
+    c = oracle_lib.Oracle(cfg["width"], cfg["height"], 256)
+    c.set_shading(forward)
+    oracle_lib.load_scene(c, cfg)
+    c.render()
+    print("constant images, %s: against the filtering oracle %r; against the collapsing oracle %r" % ("forward" if forward else "deferred", diffs, compare_all(c, g)))
+    assert all(v == 0 for v in diffs.values()), diffs
+    g.close(); o.close(); c.close()
+    del keep, ks, kp
+
+
 # ------------------------------------------------------------------------------------------------ frames in flight
 
 FRAMES = 8
