@@ -437,6 +437,42 @@ int  zr_copy_frame_delta_packed_async(zr_ctx* ctx, void* header_dev, void* tiles
 int  zr_frame_delta_decode(const uint32_t* tiles, const uint32_t* offsets, uint32_t n, const uint8_t* stream, size_t bytes, uint32_t width, uint32_t height,
                            uint8_t* client_rgba8);
 
+/* --- delivering a scaled frame ("Delivering a scaled frame"; DESIGN.md §5, "Delivering a scaled frame") ---
+ * The frame box-filtered by an integer factor `scale` (1 .. 8) in linear light, on the GPU behind the lighting pass, before any byte
+ * crosses a link: what a host sends a client whose window is smaller than the frame, a thumbnail - and, from a context created at twice
+ * the extent and delivered at scale 2, an anti-aliased picture.  The scaled extent is Wd = ceil(W/scale), Hd = ceil(H/scale).  Output
+ * pixel (X, Y) covers the frame pixels X*scale <= x < min(W, (X+1)*scale), Y*scale <= y < min(H, (Y+1)*scale): n of them, fewer than
+ * scale*scale in the last column and row - edge blocks average the pixels that exist.  Integer arithmetic throughout, so the kernel, the
+ * host statement below and a client's own code agree byte for byte:
+ *   T[c] = floor(65535 * L(c/255) + 1/2), L the sRGB EOTF (v/12.92 for v <= 0.04045, else ((v + 0.055)/1.055)^2.4) in float64
+ *   R, G, B each:  S = the block's sum of T[p]; the result is the number of k in 1..255 with 2*S >= (T[k-1] + T[k]) * n - the byte whose
+ *                  T is nearest the block's mean, ties upward
+ *   A:             floor((2 * sum + n) / (2 * n))
+ * A block of one colour yields that colour, and scale 1 is the identity.  Picking and the identity queries stay in the context's own
+ * pixels: (x, y) of a scaled frame is the rectangle (x*scale, y*scale, scale, scale) of zr_pick.
+ * Refusals, the context unchanged: ZR_ERR_ARG for scale 0 or above 8, a null pointer, a wrong byte count, a color_dev that is not
+ * 4-byte aligned; ZR_ERR_UNSUPPORTED where the lighting pass does not write the row-major frame itself (tile_world > 1,
+ * ZR_FLAG_PACKED_TILES: the cases of zr_set_frame_delta); ZR_ERR_STATE before the first finished frame and between the stages of one. */
+int  zr_frame_scaled_extent(uint32_t width, uint32_t height, uint32_t scale, uint32_t* w, uint32_t* h);      /* context-free */
+/* The host statement of the filter, context-free host code: what a client or a test compares with.  bytes == Wd*Hd*4. */
+int  zr_frame_downscale(const uint8_t* rgba8, uint32_t width, uint32_t height, uint32_t scale, uint8_t* dst, size_t bytes);
+/* Host form: zr_finish first (its error is passed on, as by zr_read_color), one launch into a buffer the context makes at first use
+ * (for scale 2, the largest output; released by zr_destroy), then Wd*Hd*4 bytes to the host - row-major, top-left origin. */
+int  zr_read_color_scaled(zr_ctx* ctx, uint32_t scale, uint8_t* rgba8, size_t bytes);
+/* Device form, straight into a caller-owned DEVICE buffer of Wd*Hd*4 bytes (4-byte aligned): synchronises nothing, ordered on the render
+ * stream exactly as zr_copy_frame_async's colour copy - behind the lighting pass of the frame enqueued last, ahead of whatever the next
+ * zr_render enqueues.  Two frames stay in flight. */
+int  zr_copy_frame_scaled_async(zr_ctx* ctx, uint32_t scale, void* color_dev);
+/* Deltas of the scaled frame.  zr_set_frame_delta_scale sets the scale the deliveries of changes work at (default 1: the frame itself);
+ * callable only while delta is off (ZR_ERR_STATE while it is on), kept across zr_set_frame_delta(ctx, 0).  Above 1, zr_set_frame_delta
+ * sizes everything for (Wd, Hd) and makes one scaled-frame buffer; every delivery, in all four forms, first filters the frame into it
+ * and then compares, lists and encodes the SCALED frame: total_tiles = ceil(Wd/32) * ceil(Hd/32), the capacities, the list order, the
+ * record format and zr_frame_delta_decode (the caller passes Wd, Hd) all follow from the scaled extent, and applying a delivery gives
+ * exactly zr_read_color_scaled's bytes.  At scale 1 nothing differs in buffers, launches or bytes.
+ * zr_get_frame_delta_extent answers for the current scale whether delta is on or off. */
+int  zr_set_frame_delta_scale(zr_ctx* ctx, uint32_t scale);
+int  zr_get_frame_delta_extent(zr_ctx* ctx, uint32_t* width, uint32_t* height, uint32_t* total_tiles, uint32_t* scale);
+
 /* --- object identity of the last frame (which object won each pixel: picking, box selection, per-instance coverage) ---
  * What is reported is the deferred-scene pass's depth-test winner, i.e. what the GBuffer holds: the same in deferred and forward
  * shading and in every debug view.  The skydome and the background are not objects: they never appear and never hide a scene winner.

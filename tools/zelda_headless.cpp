@@ -7,7 +7,7 @@
 //
 //   zelda_headless --root DIR [--world FILE.json] [--livelink PORT [--wait-ms MS]] [--meshlet FILE.meshlet --profab NAME]
 //                  [--size WxH] [--shadow N] [--frames N] [--roll-light-step F] [--debug-view V] [--out FRAME.ppm] [--device D]
-//                  [--pick X,Y[,W,H]] [--incremental] [--delta | --delta-packed]
+//                  [--pick X,Y[,W,H]] [--incremental] [--delta | --delta-packed] [--scale S]
 // --incremental applies livelink payloads as a difference from the live scene (zr_livelink_set_incremental): a payload that only moves
 // the camera or a light keeps every object, the visibility history and the shadow map.
 // --delta delivers every frame the way a host with a remote client does (zr_read_frame_delta): only the 32 x 32 tiles that differ from
@@ -15,6 +15,9 @@
 // --out is written from the client copy.
 // --delta-packed does the same through the compressed form (zr_read_frame_delta_packed): the listed tiles leave the GPU as records of the
 // tile codec and zr_frame_delta_decode applies them to the client copy; it prints `delta-packed <tiles>/<total> tiles <bytes> bytes (<raw> raw)`.
+// --scale S (1..8) delivers the frame box-filtered by S in linear light (zelda_render.h, "delivering a scaled frame"): with --delta or
+// --delta-packed it is the delta scale (zr_set_frame_delta_scale) and the client copy has the scaled extent; without them every frame is
+// read with zr_read_color_scaled and it prints `scaled <Wd>x<Hd>` per frame.  --out writes the client copy at the scaled extent.
 // --pick keeps the last frame's per-pixel winners (zr_set_id_capture) and prints what zr_pick finds in the rectangle (default 1 x 1),
 // one JSON line per hit, nearest first - what an editor does on a click.
 #include "../include/zelda_render.h"
@@ -37,7 +40,7 @@ static int fail(zr_ctx* c, const char* what, int rc)
 int main(int argc, char** argv)
 {
     std::string root = ".", world, meshlet, profab = "meshlet", out;
-    uint32_t W = 1920, H = 1080, SD = 1024, frames = 1, debug_view = 0;
+    uint32_t W = 1920, H = 1080, SD = 1024, frames = 1, debug_view = 0, scale = 0;
     int port = -1, wait_ms = 10000, device = 0;
     float roll_step = 0.0f;
     bool pick = false, incremental = false, delta = false, packed = false; uint32_t px = 0, py = 0, pw = 1, ph = 1;
@@ -60,6 +63,7 @@ int main(int argc, char** argv)
         else if (a == "--incremental") incremental = true;
         else if (a == "--delta") delta = true;
         else if (a == "--delta-packed") delta = packed = true;
+        else if (a == "--scale") scale = (uint32_t)atoi(next());
         else if (a == "--pick") {
             const int got = sscanf(next(), "%u,%u,%u,%u", &px, &py, &pw, &ph);
             if (got != 2 && got != 4) { fprintf(stderr, "--pick X,Y[,W,H]\n"); return 2; }
@@ -98,10 +102,17 @@ int main(int argc, char** argv)
 
     if (pick && (rc = zr_set_id_capture(c, 1))) return fail(c, "zr_set_id_capture", rc);
     // --delta: the client's copy of the frame, and full-sized buffers for a delivery (only the listed tiles are written and moved)
-    const uint32_t T = ZR_TILE, tiles_x = (W + T - 1) / T, total = tiles_x * ((H + T - 1) / T);
+    // DW x DH: what is delivered - the frame, or with --scale the scaled one (with --delta: the delta scale's extent, in `total` tiles)
+    uint32_t DW = W, DH = H, total = 0, delta_scale = 1;
+    const uint32_t scaled = delta ? 0u : scale;           // without --delta: the scale every frame is read at (0: frames are not read)
     std::vector<uint8_t> client, slots; std::vector<uint32_t> list, offsets;
+    if (scale && (rc = zr_frame_scaled_extent(W, H, scale, &DW, &DH))) return fail(c, "zr_frame_scaled_extent (--scale 1..8)", rc);
+    if (scaled) client.assign((size_t)DW * DH * 4, 0);
+    if (scale && delta && (rc = zr_set_frame_delta_scale(c, scale))) return fail(c, "zr_set_frame_delta_scale", rc);
+    if (delta && (rc = zr_get_frame_delta_extent(c, &DW, &DH, &total, &delta_scale))) return fail(c, "zr_get_frame_delta_extent", rc);
+    const uint32_t T = ZR_TILE, tiles_x = (DW + T - 1) / T;
     if (delta) {
-        client.assign((size_t)W * H * 4, 0); slots.resize((size_t)total * (packed ? ZR_FRAME_DELTA_RECORD_MAX : T * T * 4)); list.resize(total);
+        client.assign((size_t)DW * DH * 4, 0); slots.resize((size_t)total * (packed ? ZR_FRAME_DELTA_RECORD_MAX : T * T * 4)); list.resize(total);
         offsets.resize((size_t)total + 1);
         if ((rc = zr_set_frame_delta(c, packed ? ZR_FRAME_DELTA_PACKED : 1))) return fail(c, "zr_set_frame_delta", rc);
     }
@@ -111,12 +122,16 @@ int main(int argc, char** argv)
         if (port >= 0 && (rc = zr_livelink_poll(c, &reloaded))) return fail(c, "zr_livelink_poll", rc);
         if ((rc = zr_world_update_uniforms(c, 0.0f, roll_step * (float)f, 0.016f * (float)f))) return fail(c, "zr_world_update_uniforms", rc);
         if ((rc = zr_render(c))) return fail(c, "zr_render", rc);
+        if (!delta && scaled) {                           // the scaled frame is all that crosses the link
+            if ((rc = zr_read_color_scaled(c, scaled, client.data(), client.size()))) return fail(c, "zr_read_color_scaled", rc);
+            printf("scaled %ux%u\n", DW, DH);
+        }
         if (!delta) continue;
         if (packed) {                                     // the records cross the link; the client's side is the library's decoder
             zr_frame_delta_packed d;
             if ((rc = zr_read_frame_delta_packed(c, list.data(), total, offsets.data(), total + 1, slots.data(), slots.size(), &d, sizeof d)))
                 return fail(c, "zr_read_frame_delta_packed", rc);
-            if ((rc = zr_frame_delta_decode(list.data(), offsets.data(), d.n_tiles, slots.data(), d.bytes, W, H, client.data())))
+            if ((rc = zr_frame_delta_decode(list.data(), offsets.data(), d.n_tiles, slots.data(), d.bytes, DW, DH, client.data())))
                 return fail(c, "zr_frame_delta_decode", rc);
             printf("delta-packed %u/%u tiles %u bytes (%u raw)\n", d.n_tiles, d.total_tiles, d.bytes, d.raw_tiles);
             continue;
@@ -124,9 +139,9 @@ int main(int argc, char** argv)
         zr_frame_delta d;
         if ((rc = zr_read_frame_delta(c, list.data(), total, slots.data(), slots.size(), &d, sizeof d))) return fail(c, "zr_read_frame_delta", rc);
         for (uint32_t k = 0; k < d.n_tiles; ++k) {        // the client's apply loop: the rows of each listed tile that lie inside the frame
-            const uint32_t x0 = list[k] % tiles_x * T, y0 = list[k] / tiles_x * T, w = W - x0 < T ? W - x0 : T, h = H - y0 < T ? H - y0 : T;
+            const uint32_t x0 = list[k] % tiles_x * T, y0 = list[k] / tiles_x * T, w = DW - x0 < T ? DW - x0 : T, h = DH - y0 < T ? DH - y0 : T;
             for (uint32_t y = 0; y < h; ++y)
-                memcpy(&client[((size_t)(y0 + y) * W + x0) * 4], &slots[((size_t)k * T + y) * T * 4], (size_t)w * 4);
+                memcpy(&client[((size_t)(y0 + y) * DW + x0) * 4], &slots[((size_t)k * T + y) * T * 4], (size_t)w * 4);
         }
         printf("delta %u/%u\n", d.n_tiles, d.total_tiles);
     }
@@ -147,14 +162,14 @@ int main(int argc, char** argv)
                    h.object, h.instance, h.pixels, h.triangle, h.x, h.y, (double)h.depth);
     }
     if (!out.empty()) {
-        std::vector<uint8_t> rgba((size_t)W * H * 4);
-        if (delta) rgba = client;
+        std::vector<uint8_t> rgba((size_t)DW * DH * 4);
+        if (delta || scaled) rgba = client;
         else if ((rc = zr_read_color(c, rgba.data(), rgba.size()))) return fail(c, "zr_read_color", rc);
         FILE* fp = fopen(out.c_str(), "wb");
         if (!fp) { fprintf(stderr, "zelda_headless: cannot write %s\n", out.c_str()); zr_destroy(c); return 1; }
-        fprintf(fp, "P6\n%u %u\n255\n", W, H);
-        std::vector<uint8_t> rgb((size_t)W * H * 3);
-        for (size_t i = 0; i < (size_t)W * H; ++i) { rgb[3 * i] = rgba[4 * i]; rgb[3 * i + 1] = rgba[4 * i + 1]; rgb[3 * i + 2] = rgba[4 * i + 2]; }
+        fprintf(fp, "P6\n%u %u\n255\n", DW, DH);
+        std::vector<uint8_t> rgb((size_t)DW * DH * 3);
+        for (size_t i = 0; i < (size_t)DW * DH; ++i) { rgb[3 * i] = rgba[4 * i]; rgb[3 * i + 1] = rgba[4 * i + 1]; rgb[3 * i + 2] = rgba[4 * i + 2]; }
         fwrite(rgb.data(), 1, rgb.size(), fp);
         fclose(fp);
     }

@@ -66,6 +66,16 @@ FRAME_DELTA_SIGNATURES = {
     "zr_copy_frame_delta_packed_async": [vp_, vp_, vp_, vp_, vp_],
     "zr_frame_delta_decode": [vp_, vp_, u32_, vp_, C.c_size_t, u32_, u32_, vp_],
 }
+# delivering a scaled frame (include/zelda_render.h, "delivering a scaled frame")
+FRAME_SCALE_SIGNATURES = {
+    "zr_frame_scaled_extent": [u32_, u32_, u32_, C.POINTER(u32_), C.POINTER(u32_)],
+    "zr_frame_downscale": [vp_, u32_, u32_, u32_, vp_, C.c_size_t],
+    "zr_read_color_scaled": [vp_, u32_, vp_, C.c_size_t],
+    "zr_copy_frame_scaled_async": [vp_, u32_, vp_],
+    "zr_set_frame_delta_scale": [vp_, u32_],
+    "zr_get_frame_delta_extent": [vp_, C.POINTER(u32_), C.POINTER(u32_), C.POINTER(u32_), C.POINTER(u32_)],
+}
+FRAME_SCALE_MAX = 8               # the largest factor of the scaled forms
 del vp_, u32_
 
 

@@ -327,15 +327,20 @@ struct zr_ctx {
     // lists every tile; serial: deliveries since enable.  codec: what ZR_FRAME_DELTA_PACKED adds, through codec_mem - lens = a listed
     // tile's record length, rewritten by every packed delivery; header / offsets / stream / h_header = the packed host form's buffers (it
     // shares `list`).  Going between the raw and the packed forms makes or releases these alone.
+    // scale: zr_set_frame_delta_scale's factor (1: the frame itself), set while delta is off and kept across the switch; above 1 all of
+    // the above is sized for the scaled extent (zr_delta_extent) and `scaled` is the frame every delivery filters first (zr_scale.hip).
     struct Delta {
-        ZrOwn mem, codec_mem; bool on = false, full = true; uint32_t serial = 0;
-        uint32_t *delivered = nullptr, *list = nullptr, *header = nullptr; uint8_t *packed = nullptr, *flags = nullptr;
+        ZrOwn mem, codec_mem; bool on = false, full = true; uint32_t serial = 0, scale = 1;
+        uint32_t *delivered = nullptr, *list = nullptr, *header = nullptr, *scaled = nullptr; uint8_t *packed = nullptr, *flags = nullptr;
         zr_frame_delta* h_header = nullptr;
         struct Codec {
             bool on = false; uint16_t* lens = nullptr; uint32_t *header = nullptr, *offsets = nullptr; uint8_t* stream = nullptr;
             zr_frame_delta_packed* h_header = nullptr;
         } codec;
     } delta;
+    // Delivering a scaled frame (zr_scale_host.cpp): where zr_read_color_scaled's kernel writes, made at its first use through `own`
+    // for scale 2, the largest output (scale 1 is read from the frame itself)
+    uint32_t* d_scaled = nullptr;
 
     ZrOwn cube_mem; CubeDesc cube = {}; uint32_t cube_dim = 0, cube_levels = 0;
     uint64_t cube_gen = 0;               // of the cubemap's contents: bumped whenever they are replaced (zr_set_cubemap, which a world's override goes through)
@@ -388,6 +393,13 @@ struct zr_ctx {
     int ll_listen_fd = -1; bool ll_pending = false, ll_bind_any = false; ZrWorld ll_world; uint16_t ll_port = 0;
 };
 
+// What the deliveries of changes compare, list and size their buffers for: the frame at the delta scale (zr_ctx::Delta::scale), in tiles
+struct ZrDeltaExtent { uint32_t W, H, tiles_x, n_tiles; };
+static inline ZrDeltaExtent zr_delta_extent(const zr_ctx* c)
+{
+    const uint32_t s = c->delta.scale, W = (c->W + s - 1u) / s, H = (c->H + s - 1u) / s, tx = (W + ZR_TILE - 1u) / ZR_TILE;
+    return { W, H, tx, tx * ((H + ZR_TILE - 1u) / ZR_TILE) };
+}
 int zr_fail(zr_ctx* c, int code, const std::string& msg);      // records the message (never throws), returns code
 // ZR_OK at stage 0, else the refusal "<what> between the stages of a frame" (hint: "... (finish it with zr_render_lighting first)")
 int zr_stage_idle(zr_ctx* c, const char* what, bool hint = true);

@@ -24,41 +24,16 @@
 
 static_assert(TILE == 32, "a thread per four pixels of a row: 8 threads per row, 32 rows, 256 threads per tile");
 
-// The calling thread's four pixels (px .. px + 3, py) of a plane; 0 where they lie outside it.  VEC: W % 4 == 0, so px < W puts all four
-// inside and the address on a 16-byte boundary.
-template <bool VEC> __device__ __forceinline__ uint4 delta_load4(const uint32_t* __restrict__ plane, uint32_t W, uint32_t H, uint32_t px, uint32_t py)
-{
-    uint4 v = make_uint4(0u, 0u, 0u, 0u);
-    if (py >= H || px >= W) return v;
-    const uint32_t* p = plane + (size_t)py * W + px;
-    if (VEC) return *reinterpret_cast<const uint4*>(p);
-    v.x = p[0];
-    if (px + 1u < W) v.y = p[1];
-    if (px + 2u < W) v.z = p[2];
-    if (px + 3u < W) v.w = p[3];
-    return v;
-}
-template <bool VEC> __device__ __forceinline__ void delta_store4(uint32_t* __restrict__ plane, uint32_t W, uint32_t H, uint32_t px, uint32_t py, uint4 v)
-{
-    if (py >= H || px >= W) return;
-    uint32_t* p = plane + (size_t)py * W + px;
-    if (VEC) { *reinterpret_cast<uint4*>(p) = v; return; }
-    p[0] = v.x;
-    if (px + 1u < W) p[1] = v.y;
-    if (px + 2u < W) p[2] = v.z;
-    if (px + 3u < W) p[3] = v.w;
-}
-
 template <bool VEC> __global__ __launch_bounds__(256) void k_delta_mark(const uint32_t* __restrict__ frame, uint32_t* __restrict__ delivered,
                                                                         uint8_t* __restrict__ flags, uint32_t W, uint32_t H, uint32_t tiles_x, uint32_t full)
 {
     const uint32_t tile = blockIdx.x, t = threadIdx.x;
     const uint32_t px = (tile % tiles_x) * TILE + (t & 7u) * 4u, py = (tile / tiles_x) * TILE + (t >> 3);
-    const uint4 f = delta_load4<VEC>(frame, W, H, px, py), d = delta_load4<VEC>(delivered, W, H, px, py);
+    const uint4 f = plane_load4<VEC>(frame, W, H, px, py), d = plane_load4<VEC>(delivered, W, H, px, py);
     const bool differs = ((f.x ^ d.x) | (f.y ^ d.y) | (f.z ^ d.z) | (f.w ^ d.w)) != 0u;
     const int any = __syncthreads_or(differs ? 1 : 0);
     if (t == 0u) flags[tile] = (any || full) ? 1u : 0u;
-    if (differs) delta_store4<VEC>(delivered, W, H, px, py, f);
+    if (differs) plane_store4<VEC>(delivered, W, H, px, py, f);
 }
 
 // flags: one byte per tile, 0 or 1, read eight at a time (the array is padded to whole 64-bit words, the padding 0).  Tile 0's slot is 0
@@ -89,7 +64,7 @@ template <bool VEC> __global__ __launch_bounds__(256) void k_delta_pack(const ui
     }
     if (t == 0u) list[slot] = tile;
     const uint32_t px = (tile % tiles_x) * TILE + (t & 7u) * 4u, py = (tile / tiles_x) * TILE + (t >> 3);
-    packed[(size_t)slot * (TILE_PIX / 4) + t] = delta_load4<VEC>(frame, W, H, px, py);
+    packed[(size_t)slot * (TILE_PIX / 4) + t] = plane_load4<VEC>(frame, W, H, px, py);
 }
 
 // ------------------------------------------------------------------------------------------------ the packed delivery
@@ -102,7 +77,7 @@ template <bool VEC> __device__ __forceinline__ void codec_stage(uint32_t* __rest
                                                                 uint32_t tiles_x, uint32_t tile, uint32_t t)
 {
     const uint32_t x = (tile % tiles_x) * TILE + (t & 7u) * 4u, y = (tile / tiles_x) * TILE + (t >> 3);
-    *reinterpret_cast<uint4*>(px + (t >> 3) * CODEC_ROW + (t & 7u) * 4u) = delta_load4<VEC>(frame, W, H, x, y);
+    *reinterpret_cast<uint4*>(px + (t >> 3) * CODEC_ROW + (t & 7u) * 4u) = plane_load4<VEC>(frame, W, H, x, y);
 }
 
 // A wave's share of the staged tile: block row `wave`, the lane one pixel of each of its four blocks.  z[bx]: the pixel's zigzagged

@@ -4,6 +4,8 @@
 // goes, and the frame schedule knows nothing of it.  The packed forms (zr_set_frame_delta(ctx, ZR_FRAME_DELTA_PACKED)) deliver the same list
 // with every tile as a record of the tile codec: three launches, buffers of their own beside the raw forms', the same delivered copy.
 // zr_frame_delta_decode is the client's side of them and needs no context (zr_delta_codec.h).
+// At a delta scale above 1 (zr_set_frame_delta_scale, zr_scale_host.cpp) all of it is made for the scaled extent (zr_delta_extent), and
+// every delivery first filters the frame into `scaled` (zr_scale.hip) and then runs the same launches on that.
 #include "zr_ctx.h"
 #include "zr_delta_codec.h"
 
@@ -16,11 +18,12 @@ static_assert(sizeof(zr_frame_delta_packed) == 32 && kZrCodecTile == ZR_TILE, "t
 // padding 0), and the host form's header, offsets and stream with its pinned landing place
 static int delta_make_packed(zr_ctx* c, ZrOwn& mem, zr_ctx::Delta::Codec& P)
 {
-    if ((uint64_t)c->n_tiles * kZrCodecRawBytes > 0xFFFFFFFFull)
+    const ZrDeltaExtent E = zr_delta_extent(c);
+    if ((uint64_t)E.n_tiles * kZrCodecRawBytes > 0xFFFFFFFFull)
         return zr_fail(c, ZR_ERR_UNSUPPORTED, "zr_set_frame_delta: the frame's packed stream would not fit 32-bit offsets");
-    const size_t len_words = ((size_t)c->n_tiles + 7u) / 8u * 8u;
-    HIPCHK(c, mem.alloc(&P.lens, len_words)); HIPCHK(c, mem.alloc(&P.header, 8)); HIPCHK(c, mem.alloc(&P.offsets, (size_t)c->n_tiles + 1u));
-    HIPCHK(c, mem.alloc(&P.stream, (size_t)c->n_tiles * kZrCodecRawBytes)); HIPCHK(c, mem.host(&P.h_header, 1));
+    const size_t len_words = ((size_t)E.n_tiles + 7u) / 8u * 8u;
+    HIPCHK(c, mem.alloc(&P.lens, len_words)); HIPCHK(c, mem.alloc(&P.header, 8)); HIPCHK(c, mem.alloc(&P.offsets, (size_t)E.n_tiles + 1u));
+    HIPCHK(c, mem.alloc(&P.stream, (size_t)E.n_tiles * kZrCodecRawBytes)); HIPCHK(c, mem.host(&P.h_header, 1));
     HIPCHK(c, zr_fill_sync({ { P.lens, 0, len_words * 2 }, { P.header, 0, 32 } }));
     return ZR_OK;
 }
@@ -36,8 +39,10 @@ extern "C" int zr_set_frame_delta(zr_ctx* c, int enable)
         HIPCHK(c, hipSetDevice(c->device));
         if (!on) {
             HIPCHK(c, zr_sync_all(c));           // (deliveries in flight read and write what is released here)
+            const uint32_t scale = D.scale;      // (zr_set_frame_delta_scale's: kept across the switch)
             D.mem.release();
             D = zr_ctx::Delta();
+            D.scale = scale;
             return ZR_OK;
         }
         if (D.on) {                              // between the raw and the packed forms: the delivered copy, full and serial stand
@@ -49,18 +54,22 @@ extern "C" int zr_set_frame_delta(zr_ctx* c, int enable)
         }
         if (c->cfg.tile_world > 1 || (c->cfg.flags & ZR_FLAG_PACKED_TILES))
             return zr_fail(c, ZR_ERR_UNSUPPORTED, "zr_set_frame_delta: this context's lighting pass writes packed tiles, not the frame (tile_world > 1, ZR_FLAG_PACKED_TILES)");
-        const size_t n = (size_t)c->W * c->H, flag_bytes = ((size_t)c->n_tiles + 7u) / 8u * 8u;      // (k_delta_pack reads the flags eight at a time)
+        // everything is made for the delivered extent: the frame's own, or at a delta scale above 1 the scaled frame's, which every
+        // delivery then filters into `scaled` first (zr_scale.hip)
+        const ZrDeltaExtent E = zr_delta_extent(c);
+        const size_t n = (size_t)E.W * E.H, flag_bytes = ((size_t)E.n_tiles + 7u) / 8u * 8u;      // (k_delta_pack reads the flags eight at a time)
         ZrOwn mem;
-        uint32_t *delivered = nullptr, *list = nullptr, *header = nullptr; uint8_t *packed = nullptr, *flags = nullptr;
+        uint32_t *delivered = nullptr, *list = nullptr, *header = nullptr, *scaled = nullptr; uint8_t *packed = nullptr, *flags = nullptr;
         zr_frame_delta* h_header = nullptr;
-        HIPCHK(c, mem.alloc(&delivered, n)); HIPCHK(c, mem.alloc(&packed, (size_t)c->n_tiles * kTileBytes)); HIPCHK(c, mem.alloc(&list, c->n_tiles));
+        if (D.scale > 1u) HIPCHK(c, mem.alloc(&scaled, n));
+        HIPCHK(c, mem.alloc(&delivered, n)); HIPCHK(c, mem.alloc(&packed, (size_t)E.n_tiles * kTileBytes)); HIPCHK(c, mem.alloc(&list, E.n_tiles));
         HIPCHK(c, mem.alloc(&header, 4)); HIPCHK(c, mem.alloc(&flags, flag_bytes)); HIPCHK(c, mem.host(&h_header, 1));
         HIPCHK(c, zr_fill_sync({ { delivered, 0, n * 4 }, { flags, 0, flag_bytes }, { header, 0, 16 } }));
         ZrOwn pmem; zr_ctx::Delta::Codec P;
         if (codec) { if (int rc = delta_make_packed(c, pmem, P)) return rc; P.on = true; }
         D.codec_mem = std::move(pmem); D.codec = P;
         D.mem = std::move(mem);
-        D.delivered = delivered; D.packed = packed; D.list = list; D.header = header; D.flags = flags; D.h_header = h_header;
+        D.delivered = delivered; D.scaled = scaled; D.packed = packed; D.list = list; D.header = header; D.flags = flags; D.h_header = h_header;
         D.on = true; D.full = true; D.serial = 0;
         return ZR_OK;
     });
@@ -85,12 +94,22 @@ extern "C" int zr_frame_delta_reset(zr_ctx* c)
     });
 }
 
+// What a delivery compares and lists: the frame, or at a delta scale above 1 the frame filtered into `scaled` first, on the render stream
+static const uint32_t* delta_frame(zr_ctx* c)
+{
+    const zr_ctx::Delta& D = c->delta;
+    if (D.scale <= 1u) return c->d_color;
+    zr_launch_frame_scale(c->d_color, D.scaled, c->W, c->H, D.scale, c->stream);
+    return D.scaled;
+}
+
 // One delivery on the render stream; full and serial are the host's to know, the kernels only write them into the header
 static int delta_enqueue(zr_ctx* c, uint32_t* header_dev, uint32_t* list_dev, void* packed_dev)
 {
     zr_ctx::Delta& D = c->delta;
+    const ZrDeltaExtent E = zr_delta_extent(c);
     const uint32_t serial = D.serial + 1u;
-    zr_launch_frame_delta(c->d_color, D.delivered, D.flags, header_dev, list_dev, packed_dev, c->W, c->H, c->tiles_x, c->n_tiles, D.full ? 1u : 0u, serial,
+    zr_launch_frame_delta(delta_frame(c), D.delivered, D.flags, header_dev, list_dev, packed_dev, E.W, E.H, E.tiles_x, E.n_tiles, D.full ? 1u : 0u, serial,
                           c->stream);
     HIPCHK(c, hipGetLastError());
     D.serial = serial; D.full = false;
@@ -101,8 +120,9 @@ extern "C" int zr_read_frame_delta(zr_ctx* c, uint32_t* tiles, uint32_t cap_tile
 {
     if (!c) return ZR_ERR_ARG;
     return zr_guard(c, [&]() -> int {
+        const ZrDeltaExtent E = zr_delta_extent(c);
         ARGCHK(c, tiles && pixels && out && out_bytes >= sizeof(zr_frame_delta));
-        ARGCHK(c, cap_tiles == c->n_tiles && bytes == (size_t)c->n_tiles * kTileBytes);
+        ARGCHK(c, cap_tiles == E.n_tiles && bytes == (size_t)E.n_tiles * kTileBytes);
         int rc = delta_ready(c, "zr_read_frame_delta");
         if (rc == ZR_OK) rc = zr_finish(c);
         if (rc == ZR_OK) rc = delta_enqueue(c, c->delta.header, c->delta.list, c->delta.packed);
@@ -111,7 +131,7 @@ extern "C" int zr_read_frame_delta(zr_ctx* c, uint32_t* tiles, uint32_t cap_tile
         HIPCHK(c, hipMemcpyAsync(D.h_header, D.header, sizeof(zr_frame_delta), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         const zr_frame_delta h = *D.h_header;
-        if (h.n_tiles > c->n_tiles) return zr_fail(c, ZR_ERR_DEVICE, "zr_read_frame_delta: more tiles listed than the frame has");
+        if (h.n_tiles > E.n_tiles) return zr_fail(c, ZR_ERR_DEVICE, "zr_read_frame_delta: more tiles listed than the frame has");
         if (h.n_tiles) {
             HIPCHK(c, hipMemcpyAsync(tiles, D.list, (size_t)h.n_tiles * 4, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipMemcpyAsync(pixels, D.packed, (size_t)h.n_tiles * kTileBytes, hipMemcpyDeviceToHost, c->stream));
@@ -146,8 +166,9 @@ static int delta_packed_enabled(zr_ctx* c, const char* what)
 static int delta_enqueue_packed(zr_ctx* c, uint32_t* header_dev, uint32_t* list_dev, uint32_t* offsets_dev, void* stream_dev)
 {
     zr_ctx::Delta& D = c->delta;
+    const ZrDeltaExtent E = zr_delta_extent(c);
     const uint32_t serial = D.serial + 1u;
-    zr_launch_frame_delta_packed(c->d_color, D.delivered, D.flags, D.codec.lens, header_dev, list_dev, offsets_dev, stream_dev, c->W, c->H, c->tiles_x, c->n_tiles,
+    zr_launch_frame_delta_packed(delta_frame(c), D.delivered, D.flags, D.codec.lens, header_dev, list_dev, offsets_dev, stream_dev, E.W, E.H, E.tiles_x, E.n_tiles,
                                  D.full ? 1u : 0u, serial, c->stream);
     HIPCHK(c, hipGetLastError());
     D.serial = serial; D.full = false;
@@ -160,8 +181,9 @@ extern "C" int zr_read_frame_delta_packed(zr_ctx* c, uint32_t* tiles, uint32_t c
     if (!c) return ZR_ERR_ARG;
     return zr_guard(c, [&]() -> int {
         if (int rc = delta_packed_enabled(c, "zr_read_frame_delta_packed")) return rc;
+        const ZrDeltaExtent E = zr_delta_extent(c);
         ARGCHK(c, tiles && offsets && stream && out && out_bytes >= sizeof(zr_frame_delta_packed));
-        ARGCHK(c, cap_tiles == c->n_tiles && cap_offsets == c->n_tiles + 1u && cap_bytes == (size_t)c->n_tiles * kZrCodecRawBytes);
+        ARGCHK(c, cap_tiles == E.n_tiles && cap_offsets == E.n_tiles + 1u && cap_bytes == (size_t)E.n_tiles * kZrCodecRawBytes);
         int rc = delta_ready(c, "zr_read_frame_delta_packed");
         if (rc == ZR_OK) rc = zr_finish(c);
         const zr_ctx::Delta::Codec& P = c->delta.codec;
@@ -170,7 +192,7 @@ extern "C" int zr_read_frame_delta_packed(zr_ctx* c, uint32_t* tiles, uint32_t c
         HIPCHK(c, hipMemcpyAsync(P.h_header, P.header, sizeof(zr_frame_delta_packed), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         const zr_frame_delta_packed h = *P.h_header;
-        if (h.n_tiles > c->n_tiles || h.bytes > cap_bytes) return zr_fail(c, ZR_ERR_DEVICE, "zr_read_frame_delta_packed: more listed than the frame has");
+        if (h.n_tiles > E.n_tiles || h.bytes > cap_bytes) return zr_fail(c, ZR_ERR_DEVICE, "zr_read_frame_delta_packed: more listed than the frame has");
         offsets[0] = 0u;
         if (h.n_tiles) {                         // the compressed bytes are all that cross the link
             HIPCHK(c, hipMemcpyAsync(tiles, c->delta.list, (size_t)h.n_tiles * 4, hipMemcpyDeviceToHost, c->stream));

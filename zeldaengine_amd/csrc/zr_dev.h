@@ -322,6 +322,31 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)      // inclusive
 __device__ __forceinline__ float lane_bcast(float v, uint32_t src) { return zr_u2f((uint32_t)__builtin_amdgcn_readlane((int)zr_f2u(v), (int)src)); }
 __device__ __forceinline__ uint32_t lane_bcast(uint32_t v, uint32_t src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)src); }
 
+// The calling thread's four pixels (px .. px + 3, py) of a row-major W x H plane (zr_delta.hip, zr_scale.hip); 0 where they lie outside
+// it.  VEC: W % 4 == 0 and px % 4 == 0, so px < W puts all four inside and the address on a 16-byte boundary.
+template <bool VEC> __device__ __forceinline__ uint4 plane_load4(const uint32_t* __restrict__ plane, uint32_t W, uint32_t H, uint32_t px, uint32_t py)
+{
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (py >= H || px >= W) return v;
+    const uint32_t* p = plane + (size_t)py * W + px;
+    if (VEC) return *reinterpret_cast<const uint4*>(p);
+    v.x = p[0];
+    if (px + 1u < W) v.y = p[1];
+    if (px + 2u < W) v.z = p[2];
+    if (px + 3u < W) v.w = p[3];
+    return v;
+}
+template <bool VEC> __device__ __forceinline__ void plane_store4(uint32_t* __restrict__ plane, uint32_t W, uint32_t H, uint32_t px, uint32_t py, uint4 v)
+{
+    if (py >= H || px >= W) return;
+    uint32_t* p = plane + (size_t)py * W + px;
+    if (VEC) { *reinterpret_cast<uint4*>(p) = v; return; }
+    p[0] = v.x;
+    if (px + 1u < W) p[1] = v.y;
+    if (px + 2u < W) p[2] = v.z;
+    if (px + 3u < W) p[3] = v.w;
+}
+
 // Conservative occlusion test of one meshlet-instance against the pyramid: true when every pixel of its snapped bounding box
 // already holds a depth smaller than the least depth the meshlet can produce, i.e. its fragments would all fail LESS.
 __device__ __forceinline__ bool hiz_occluded(const ZrHiz& Z, uint2 pr, float zmin)

@@ -380,3 +380,5 @@ void zr_launch_frame_delta(const uint32_t* frame, uint32_t* delivered, uint8_t* 
 // of 4 104 bytes; lens: 16 bits per tile in whole 16-byte words, the padding 0
 void zr_launch_frame_delta_packed(const uint32_t* frame, uint32_t* delivered, uint8_t* flags, uint16_t* lens, uint32_t* header, uint32_t* list, uint32_t* offsets,
                                   void* stream, uint32_t W, uint32_t H, uint32_t tiles_x, uint32_t n_tiles, uint32_t full, uint32_t serial, hipStream_t s);
+// zr_scale.hip: `frame` (W x H, 16-byte aligned) box-filtered by s (1 .. 8) in linear light into dst (ceil(W / s) x ceil(H / s), 4-byte aligned)
+void zr_launch_frame_scale(const uint32_t* frame, uint32_t* dst, uint32_t W, uint32_t H, uint32_t s, hipStream_t st);

@@ -61,6 +61,7 @@ def lib():
         **abi.TEXTURE_UPDATE_SIGNATURES,
         **abi.VISIBILITY_SIGNATURES,
         **abi.FRAME_DELTA_SIGNATURES,
+        **abi.FRAME_SCALE_SIGNATURES,
         "zr_set_cubemap": [vp, vp, u32],
         "zr_set_skydome": [vp, vp, u32, vp, u32, vp],
         "zr_set_background": [vp, vp],
@@ -262,6 +263,29 @@ def frame_delta_decode(tiles, offsets, stream, client):
     if rc:
         raise ZeldaRenderError(rc, "zr_frame_delta_decode: the delivery is malformed")
     return client
+
+
+def frame_scaled_extent(w, h, s):
+    """zr_frame_scaled_extent: (ceil(w / s), ceil(h / s)) for s in 1..8"""
+    wd, hd = C.c_uint32(), C.c_uint32()
+    rc = lib().zr_frame_scaled_extent(w, h, s, C.byref(wd), C.byref(hd))
+    if rc:
+        raise ZeldaRenderError(rc, "zr_frame_scaled_extent: bad argument")
+    return wd.value, hd.value
+
+
+def frame_downscale(img, s):
+    """zr_frame_downscale, the host statement of the scaled forms' filter (host code only): img (H, W, 4) uint8 box-filtered by s in
+    linear light -> (ceil(H / s), ceil(W / s), 4) uint8"""
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    assert img.ndim == 3 and img.shape[2] == 4
+    h, w = img.shape[:2]
+    wd, hd = frame_scaled_extent(w, h, s)
+    out = np.zeros((hd, wd, 4), dtype=np.uint8)
+    rc = lib().zr_frame_downscale(_ptr(img), w, h, s, _ptr(out), out.nbytes)
+    if rc:
+        raise ZeldaRenderError(rc, "zr_frame_downscale: bad argument")
+    return out
 
 
 def _delta_dict(d):
@@ -660,8 +684,31 @@ class Renderer:
         self._chk(self.L.zr_frame_delta_reset(self.h))
 
     def frame_delta_tiles(self):
-        """How many 32 x 32 tiles the frame has: the size every delivery's buffers are made for."""
-        return ((self.W + abi.TILE - 1) // abi.TILE) * ((self.H + abi.TILE - 1) // abi.TILE)
+        """How many 32 x 32 tiles the delivered frame has - the frame, at a delta scale above 1 the scaled one: the size every delivery's
+        buffers are made for."""
+        return self.frame_delta_extent()[2]
+
+    def set_frame_delta_scale(self, s):
+        """The scale the deliveries of changes work at (default 1; only while delta is off, kept across set_frame_delta(False))."""
+        self._chk(self.L.zr_set_frame_delta_scale(self.h, s))
+
+    def frame_delta_extent(self):
+        """zr_get_frame_delta_extent: (width, height, total_tiles, scale) of what the deliveries of changes deliver."""
+        w, h, t, s = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._chk(self.L.zr_get_frame_delta_extent(self.h, C.byref(w), C.byref(h), C.byref(t), C.byref(s)))
+        return w.value, h.value, t.value, s.value
+
+    # ---- delivering a scaled frame: box-filtered by an integer factor in linear light, on the GPU
+    def color_scaled(self, s):
+        """zr_read_color_scaled: the frame filtered by s (1..8) -> (ceil(H / s), ceil(W / s), 4) uint8"""
+        out = np.zeros((-(-self.H // max(s, 1)), -(-self.W // max(s, 1)), 4), dtype=np.uint8)
+        self._chk(self.L.zr_read_color_scaled(self.h, s, _ptr(out), out.nbytes))
+        return out
+
+    def copy_frame_scaled_async(self, s, color_dev):
+        """The frame enqueued last filtered by s -> a caller-owned device buffer (address, 4-byte aligned, ceil(W / s) * ceil(H / s) * 4
+        bytes), in stream order, no host synchronisation."""
+        self._chk(self.L.zr_copy_frame_scaled_async(self.h, s, C.c_void_p(color_dev) if color_dev else None))
 
     def read_frame_delta(self, tiles=None, pixels=None):
         """One delivery to the host: (tiles[n] uint32 ascending, pixels[n, 32, 32, 4] uint8, header dict).  tiles / pixels: full-sized
