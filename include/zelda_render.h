@@ -473,6 +473,61 @@ int  zr_copy_frame_scaled_async(zr_ctx* ctx, uint32_t scale, void* color_dev);
 int  zr_set_frame_delta_scale(zr_ctx* ctx, uint32_t scale);
 int  zr_get_frame_delta_extent(zr_ctx* ctx, uint32_t* width, uint32_t* height, uint32_t* total_tiles, uint32_t* scale);
 
+/* --- highlighting a selection ("Highlighting a selection"; DESIGN.md §5, "Highlighting a selection") ---
+ * The frame delivered with a set of instances marked: an outer outline round them and, optionally, a fill over them, drawn on the GPU
+ * behind the lighting pass from the winner plane of the identity queries below (zr_set_id_capture), before any byte crosses a link.
+ * The frame itself is never marked: zr_read_color, zr_copy_frame_async, zr_color_device_ptr, the scaled forms and the deltas of a context
+ * with highlight delivery off deliver what they always did.
+ * The set is one flag per slot of zr_instance_coverage (objects in add order, then their instances in order; a non-instanced object has
+ * one slot: first = 0, n = 1).  It is host state: changing it draws nothing, ends no rest and touches no frame; a delivery enqueued
+ * before a change delivers the old set, even while still in flight.  It is cleared whenever the object list changes (zr_object_add,
+ * zr_scene_clear, a world load, a world update that adds, removes, resizes or reorders objects).
+ * The rule, integer arithmetic throughout, so the kernels, the host statement below and a client's own code agree byte for byte:
+ *   M(x, y) = 1 iff the frame's winner at (x, y) - what zr_read_ids reports - is a scene primitive whose slot is in the set; the
+ *             skydome, the background, empty pixels and pixels outside the frame have M = 0
+ *   M = 1:                                                  R, G, B blended with `fill`
+ *   M = 0 and some M = 1 within |dx| <= radius, |dy| <= radius:  R, G, B blended with `outline` (an outer outline, over whatever is there)
+ *   otherwise the pixel, and A always, stays
+ *   blend(p, q, a) = floor((p*(255 - a) + q*a + 127) / 255) per channel, on the frame's gamma-encoded bytes
+ * An empty set, and radius 0 with fill opacity 0, are the identity.  At a scale above 1 the highlighted frame is filtered afterwards
+ * (zr_frame_downscale of it): the radius is in the context's own pixels.
+ * Refusals, the context unchanged, arguments first: ZR_ERR_ARG for a null pointer, a wrong count, a scale outside 1..8, a misaligned
+ * destination, an object or range out of bounds, a radius above 8, a non-zero reserved; ZR_ERR_UNSUPPORTED where the lighting pass does
+ * not write the row-major frame (tile_world > 1, ZR_FLAG_PACKED_TILES); ZR_ERR_STATE for the cases of zr_pick - no finished frame,
+ * between the stages of one, the last frame rendered without id capture, the scene changed after it.  A highlighted delivery needs a
+ * captured frame whatever the set holds. */
+typedef struct zr_highlight_style {   /* 16 bytes */
+    uint8_t  outline[4];   /* R, G, B, opacity 0..255 */
+    uint8_t  fill[4];      /* R, G, B, opacity 0..255 (0: selected pixels stay as they are) */
+    uint32_t radius;       /* outline width in frame pixels, 0..8 (0: no outline) */
+    uint32_t reserved;     /* 0, else ZR_ERR_ARG */
+} zr_highlight_style;      /* default: outline {255, 160, 0, 255}, fill {255, 160, 0, 0}, radius 2 */
+/* Arguments as for zr_object_set_instance_visibility: on[i] != 0 puts instance first + i of `object` into the set, 0 takes it out. */
+int  zr_highlight_set(zr_ctx* ctx, uint32_t object, uint32_t first, const uint8_t* on, uint32_t n);
+int  zr_highlight_clear(zr_ctx* ctx);
+/* One byte per slot; bytes = the slot count = zr_instance_coverage's byte count / 4. */
+int  zr_highlight_get(zr_ctx* ctx, uint8_t* dst, size_t bytes);
+/* bytes = the caller's sizeof(zr_highlight_style) (passed like zr_stats) */
+int  zr_set_highlight_style(zr_ctx* ctx, const zr_highlight_style* style, size_t bytes);
+int  zr_get_highlight_style(zr_ctx* ctx, zr_highlight_style* style, size_t bytes);
+/* Host form: zr_finish first (its error is passed on), two launches (and the filter at a scale above 1) into buffers the context makes
+ * at first use, then Wd*Hd*4 bytes to the host. */
+int  zr_read_color_highlighted(zr_ctx* ctx, uint32_t scale, uint8_t* rgba8, size_t bytes);
+/* Device form, into a caller-owned DEVICE buffer of Wd*Hd*4 bytes (4-byte aligned): synchronises nothing, ordered on the render stream
+ * exactly as zr_copy_frame_scaled_async.  It reads the last frame's winner plane: the frame after next waits for it before it rewrites
+ * that plane (as for zr_instance_coverage_async). */
+int  zr_copy_frame_highlighted_async(zr_ctx* ctx, uint32_t scale, void* color_dev);
+/* Deltas of the highlighted frame: callable only while delta is off (ZR_ERR_STATE while it is on), kept across zr_set_frame_delta(ctx, 0).
+ * While on, every delivery of changes, in all four forms and at any delta scale, highlights, then filters, then compares and lists:
+ * extents, capacities, list order and record format stay, applying a delivery gives exactly zr_read_color_highlighted(ctx, delta scale)'s
+ * bytes, a frame at rest with an unchanged set lists 0 tiles, and changing the set lists the tiles whose highlighted bytes differ.
+ * Every delivery then has the refusals above. */
+int  zr_set_frame_delta_highlight(zr_ctx* ctx, int on);
+/* The host statement of the rule over a byte-per-pixel mask (non-zero = highlighted), context-free host code: what a client or a test
+ * compares with.  style_bytes = the caller's sizeof(zr_highlight_style); bytes == width*height*4. */
+int  zr_frame_highlight(const uint8_t* rgba8, const uint8_t* mask, uint32_t width, uint32_t height, const zr_highlight_style* style, size_t style_bytes,
+                        uint8_t* dst, size_t bytes);
+
 /* --- object identity of the last frame (which object won each pixel: picking, box selection, per-instance coverage) ---
  * What is reported is the deferred-scene pass's depth-test winner, i.e. what the GBuffer holds: the same in deferred and forward
  * shading and in every debug view.  The skydome and the background are not objects: they never appear and never hide a scene winner.

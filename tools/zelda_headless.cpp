@@ -7,7 +7,7 @@
 //
 //   zelda_headless --root DIR [--world FILE.json] [--livelink PORT [--wait-ms MS]] [--meshlet FILE.meshlet --profab NAME]
 //                  [--size WxH] [--shadow N] [--frames N] [--roll-light-step F] [--debug-view V] [--out FRAME.ppm] [--device D]
-//                  [--pick X,Y[,W,H]] [--incremental] [--delta | --delta-packed] [--scale S]
+//                  [--pick X,Y[,W,H] [--highlight]] [--incremental] [--delta | --delta-packed] [--scale S]
 // --incremental applies livelink payloads as a difference from the live scene (zr_livelink_set_incremental): a payload that only moves
 // the camera or a light keeps every object, the visibility history and the shadow map.
 // --delta delivers every frame the way a host with a remote client does (zr_read_frame_delta): only the 32 x 32 tiles that differ from
@@ -20,6 +20,10 @@
 // read with zr_read_color_scaled and it prints `scaled <Wd>x<Hd>` per frame.  --out writes the client copy at the scaled extent.
 // --pick keeps the last frame's per-pixel winners (zr_set_id_capture) and prints what zr_pick finds in the rectangle (default 1 x 1),
 // one JSON line per hit, nearest first - what an editor does on a click.
+// --highlight (with --pick) shows the selection: the pick is made after the first frame, its hits go into the highlight set
+// (zr_highlight_set) and every following frame is delivered highlighted (zelda_render.h, "highlighting a selection") through whichever of
+// --delta, --delta-packed and --scale is chosen - zr_set_frame_delta_highlight, or zr_read_color_highlighted at the scale, which prints
+// `highlighted <Wd>x<Hd>` per frame.  --out writes the highlighted picture.
 #include "../include/zelda_render.h"
 
 #include <chrono>
@@ -43,7 +47,7 @@ int main(int argc, char** argv)
     uint32_t W = 1920, H = 1080, SD = 1024, frames = 1, debug_view = 0, scale = 0;
     int port = -1, wait_ms = 10000, device = 0;
     float roll_step = 0.0f;
-    bool pick = false, incremental = false, delta = false, packed = false; uint32_t px = 0, py = 0, pw = 1, ph = 1;
+    bool pick = false, incremental = false, delta = false, packed = false, highlight = false; uint32_t px = 0, py = 0, pw = 1, ph = 1;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
@@ -64,6 +68,7 @@ int main(int argc, char** argv)
         else if (a == "--delta") delta = true;
         else if (a == "--delta-packed") delta = packed = true;
         else if (a == "--scale") scale = (uint32_t)atoi(next());
+        else if (a == "--highlight") highlight = true;
         else if (a == "--pick") {
             const int got = sscanf(next(), "%u,%u,%u,%u", &px, &py, &pw, &ph);
             if (got != 2 && got != 4) { fprintf(stderr, "--pick X,Y[,W,H]\n"); return 2; }
@@ -71,6 +76,7 @@ int main(int argc, char** argv)
         }
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
+    if (highlight && !pick) { fprintf(stderr, "--highlight needs --pick X,Y[,W,H]\n"); return 2; }
     zr_config cfg; memset(&cfg, 0, sizeof cfg);
     cfg.width = W; cfg.height = H; cfg.shadow_dim = SD; cfg.debug_view = debug_view; cfg.device = device; cfg.tile_world = 1;
     zr_ctx* c = nullptr;
@@ -107,7 +113,8 @@ int main(int argc, char** argv)
     const uint32_t scaled = delta ? 0u : scale;           // without --delta: the scale every frame is read at (0: frames are not read)
     std::vector<uint8_t> client, slots; std::vector<uint32_t> list, offsets;
     if (scale && (rc = zr_frame_scaled_extent(W, H, scale, &DW, &DH))) return fail(c, "zr_frame_scaled_extent (--scale 1..8)", rc);
-    if (scaled) client.assign((size_t)DW * DH * 4, 0);
+    if (scaled || (highlight && !delta)) client.assign((size_t)DW * DH * 4, 0);
+    if (highlight && delta && (rc = zr_set_frame_delta_highlight(c, 1))) return fail(c, "zr_set_frame_delta_highlight", rc);
     if (scale && delta && (rc = zr_set_frame_delta_scale(c, scale))) return fail(c, "zr_set_frame_delta_scale", rc);
     if (delta && (rc = zr_get_frame_delta_extent(c, &DW, &DH, &total, &delta_scale))) return fail(c, "zr_get_frame_delta_extent", rc);
     const uint32_t T = ZR_TILE, tiles_x = (DW + T - 1) / T;
@@ -116,13 +123,32 @@ int main(int argc, char** argv)
         offsets.resize((size_t)total + 1);
         if ((rc = zr_set_frame_delta(c, packed ? ZR_FRAME_DELTA_PACKED : 1))) return fail(c, "zr_set_frame_delta", rc);
     }
+    // --pick: what zr_pick finds in the rectangle, printed; with --highlight the hits go into the highlight set
+    auto do_pick = [&]() -> int {
+        uint32_t n = 0;
+        if ((rc = zr_pick(c, px, py, pw, ph, nullptr, 0, &n))) return rc;
+        std::vector<zr_hit> hits(n);
+        if (n && (rc = zr_pick(c, px, py, pw, ph, hits.data(), n, &n))) return rc;
+        for (const zr_hit& h : hits) {
+            printf("{\"object\": %u, \"instance\": %u, \"pixels\": %u, \"triangle\": %u, \"x\": %u, \"y\": %u, \"depth\": %.9g}\n",
+                   h.object, h.instance, h.pixels, h.triangle, h.x, h.y, (double)h.depth);
+            const uint8_t on = 1;
+            if (highlight && (rc = zr_highlight_set(c, h.object, h.instance, &on, 1))) return rc;
+        }
+        return 0;
+    };
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t f = 0; f < frames; ++f) {
         int reloaded = 0;
         if (port >= 0 && (rc = zr_livelink_poll(c, &reloaded))) return fail(c, "zr_livelink_poll", rc);
         if ((rc = zr_world_update_uniforms(c, 0.0f, roll_step * (float)f, 0.016f * (float)f))) return fail(c, "zr_world_update_uniforms", rc);
         if ((rc = zr_render(c))) return fail(c, "zr_render", rc);
-        if (!delta && scaled) {                           // the scaled frame is all that crosses the link
+        if (highlight && f == 0 && do_pick()) return fail(c, "zr_pick / zr_highlight_set", rc);      // the click: from here on the selection shows
+        if (!delta && highlight) {                        // the highlighted frame, at the scale, is all that crosses the link
+            if ((rc = zr_read_color_highlighted(c, scale ? scale : 1u, client.data(), client.size()))) return fail(c, "zr_read_color_highlighted", rc);
+            printf("highlighted %ux%u\n", DW, DH);
+        }
+        else if (!delta && scaled) {                           // the scaled frame is all that crosses the link
             if ((rc = zr_read_color_scaled(c, scaled, client.data(), client.size()))) return fail(c, "zr_read_color_scaled", rc);
             printf("scaled %ux%u\n", DW, DH);
         }
@@ -152,18 +178,10 @@ int main(int argc, char** argv)
     uint32_t n_obj = 0; zr_object_count(c, &n_obj);
     printf("frames %u  %.3f ms/frame  objects %u  meshlet-instances %llu  camera survivors %llu  covered pixels %llu\n", frames, ms / frames, n_obj,
            (unsigned long long)st.work_items[1], (unsigned long long)st.survivors[1], (unsigned long long)st.covered_pixels);
-    if (pick) {
-        uint32_t n = 0;
-        if ((rc = zr_pick(c, px, py, pw, ph, nullptr, 0, &n))) return fail(c, "zr_pick", rc);
-        std::vector<zr_hit> hits(n);
-        if (n && (rc = zr_pick(c, px, py, pw, ph, hits.data(), n, &n))) return fail(c, "zr_pick", rc);
-        for (const zr_hit& h : hits)
-            printf("{\"object\": %u, \"instance\": %u, \"pixels\": %u, \"triangle\": %u, \"x\": %u, \"y\": %u, \"depth\": %.9g}\n",
-                   h.object, h.instance, h.pixels, h.triangle, h.x, h.y, (double)h.depth);
-    }
+    if (pick && !highlight && do_pick()) return fail(c, "zr_pick", rc);
     if (!out.empty()) {
         std::vector<uint8_t> rgba((size_t)DW * DH * 4);
-        if (delta || scaled) rgba = client;
+        if (delta || scaled || highlight) rgba = client;
         else if ((rc = zr_read_color(c, rgba.data(), rgba.size()))) return fail(c, "zr_read_color", rc);
         FILE* fp = fopen(out.c_str(), "wb");
         if (!fp) { fprintf(stderr, "zelda_headless: cannot write %s\n", out.c_str()); zr_destroy(c); return 1; }

@@ -76,7 +76,33 @@ FRAME_SCALE_SIGNATURES = {
     "zr_get_frame_delta_extent": [vp_, C.POINTER(u32_), C.POINTER(u32_), C.POINTER(u32_), C.POINTER(u32_)],
 }
 FRAME_SCALE_MAX = 8               # the largest factor of the scaled forms
+
+
+class HighlightStyle(C.Structure):
+    """ctypes mirror of zr_highlight_style (16 bytes, passed with its size, like zr_stats)"""
+    _fields_ = [("outline", C.c_uint8 * 4), ("fill", C.c_uint8 * 4), ("radius", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(HighlightStyle) == 16
+HIGHLIGHT_RADIUS_MAX = 8          # the widest outline
+# highlighting a selection (include/zelda_render.h, "highlighting a selection")
+HIGHLIGHT_SIGNATURES = {
+    "zr_highlight_set": [vp_, u32_, u32_, vp_, u32_],
+    "zr_highlight_clear": [vp_],
+    "zr_highlight_get": [vp_, vp_, C.c_size_t],
+    "zr_set_highlight_style": [vp_, C.POINTER(HighlightStyle), C.c_size_t],
+    "zr_get_highlight_style": [vp_, C.POINTER(HighlightStyle), C.c_size_t],
+    "zr_read_color_highlighted": [vp_, u32_, vp_, C.c_size_t],
+    "zr_copy_frame_highlighted_async": [vp_, u32_, vp_],
+    "zr_set_frame_delta_highlight": [vp_, C.c_int],
+    "zr_frame_highlight": [vp_, vp_, u32_, u32_, C.POINTER(HighlightStyle), C.c_size_t, vp_, C.c_size_t],
+}
 del vp_, u32_
+
+
+def make_highlight_style(outline=(255, 160, 0, 255), fill=(255, 160, 0, 0), radius=2):
+    """zr_highlight_style from (R, G, B, opacity) tuples and the outline's width; the defaults are the library's"""
+    return HighlightStyle((C.c_uint8 * 4)(*outline), (C.c_uint8 * 4)(*fill), radius, 0)
 
 
 class Camera(C.Structure):

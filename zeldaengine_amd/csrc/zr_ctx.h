@@ -341,6 +341,17 @@ struct zr_ctx {
     // Delivering a scaled frame (zr_scale_host.cpp): where zr_read_color_scaled's kernel writes, made at its first use through `own`
     // for scale 2, the largest output (scale 1 is read from the frame itself)
     uint32_t* d_scaled = nullptr;
+    // Highlighting a selection (zr_highlight_host.cpp, zr_highlight.hip).  set: a byte per slot, host state, cleared when scene_gen moves
+    // (set_gen: the scene it was sized for); dirty: the device bitset `bits` (a bit per slot; bits_mem, re-made when the slot count
+    // outgrows bits_words) is older than it - the next highlighted delivery stages it on the render stream first, so deliveries in
+    // flight keep the set they were enqueued with.  plane (ceil(W / 64) * H words) and frame (W * H) are made at first use through `own`.
+    // delta: zr_set_frame_delta_highlight - the deliveries of changes deliver the highlighted frame.
+    struct Highlight {
+        std::vector<uint8_t> set; uint64_t set_gen = ~0ull; bool dirty = true, delta = false;
+        zr_highlight_style style = { { 255, 160, 0, 255 }, { 255, 160, 0, 0 }, 2u, 0u };
+        ZrOwn bits_mem; uint32_t* bits = nullptr; size_t bits_words = 0;
+        unsigned long long* plane = nullptr; uint32_t* frame = nullptr;
+    } hl;
 
     ZrOwn cube_mem; CubeDesc cube = {}; uint32_t cube_dim = 0, cube_levels = 0;
     uint64_t cube_gen = 0;               // of the cubemap's contents: bumped whenever they are replaced (zr_set_cubemap, which a world's override goes through)
@@ -436,6 +447,8 @@ int zr_update_tex_end(zr_ctx* c, hipStream_t x);                 // ... and the 
 hipStream_t zr_update_lane(const zr_ctx* c);                     // the stream a host-form update is enqueued on
 // the host form: `bytes` of src through the pinned staging ring, enqueue(staged, lane), the slot's event behind it
 int zr_update_host_form(zr_ctx* c, const void* src, size_t bytes, const std::function<int(const void*, hipStream_t)>& enqueue);
+// ... on stream x instead of the lane (the highlight set rides the render stream, between the deliveries that read it)
+int zr_update_host_form_on(zr_ctx* c, hipStream_t x, const void* src, size_t bytes, const std::function<int(const void*, hipStream_t)>& enqueue);
 int zr_update_frame(zr_ctx* c, hipStream_t s, int par);          // frame head: this frame's draw table, the updates that are due
 int zr_update_table(zr_ctx* c);                                  // zr_scene_finalize: the parity-1 table of a new draw table
 void zr_drop_draw_tables(zr_ctx* c);
@@ -488,6 +501,16 @@ int empty_pixel_pass(zr_ctx* c);
 int lighting_pass(zr_ctx* c);
 // zr_readback.cpp
 int ids_prepare(zr_ctx* c);            // frame_begin of a captured frame: the census's draw table
+// The frame enqueued last kept its winners and still describes the scene (else the refusal, in `what`'s name); sync: finish it first
+int ids_ready(zr_ctx* c, const char* what, bool sync);
+ZrIdsArgs ids_args(zr_ctx* c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h);      // the census's arguments for a rectangle of that frame
+size_t ids_slot_count(const zr_ctx* c);                                              // the slots of zr_instance_coverage
+// zr_scale_host.cpp: the context's lighting pass writes the row-major frame, and the frame enqueued last is a finished one
+int scale_ready(zr_ctx* c, const char* what);
+// zr_highlight_host.cpp: a highlighted delivery may be enqueued (the refusals of scale_ready, then of ids_ready); the frame enqueued
+// last highlighted into dst (null: the context's own buffer, which is returned in *out), on the render stream
+int zr_highlight_ready(zr_ctx* c, const char* what);
+int zr_highlight_enqueue(zr_ctx* c, uint32_t* dst, const uint32_t** out);
 // zr_scene.cpp, also used by zr_world.cpp
 float zr_srgb_decode8(uint32_t c);
 int zr_material_prepare(zr_ctx* c, const zr_material* mat, ZrMaterialHost* out);

@@ -6,6 +6,7 @@
 // zr_frame_delta_decode is the client's side of them and needs no context (zr_delta_codec.h).
 // At a delta scale above 1 (zr_set_frame_delta_scale, zr_scale_host.cpp) all of it is made for the scaled extent (zr_delta_extent), and
 // every delivery first filters the frame into `scaled` (zr_scale.hip) and then runs the same launches on that.
+// With highlight delivery on (zr_set_frame_delta_highlight, zr_highlight_host.cpp) the frame is highlighted ahead of all that.
 #include "zr_ctx.h"
 #include "zr_delta_codec.h"
 
@@ -81,7 +82,7 @@ static int delta_ready(zr_ctx* c, const char* what)
     if (!c->delta.on) return zr_fail(c, ZR_ERR_STATE, std::string(what) + ": frame delta is off (zr_set_frame_delta)");
     if (int rc = zr_stage_idle(c, what)) return rc;
     if (!c->rendered) return zr_fail(c, ZR_ERR_STATE, std::string(what) + ": no finished frame enqueued");
-    return ZR_OK;
+    return c->hl.delta ? zr_highlight_ready(c, what) : ZR_OK;      // (a highlighted delivery needs a captured frame)
 }
 
 extern "C" int zr_frame_delta_reset(zr_ctx* c)
@@ -94,13 +95,18 @@ extern "C" int zr_frame_delta_reset(zr_ctx* c)
     });
 }
 
-// What a delivery compares and lists: the frame, or at a delta scale above 1 the frame filtered into `scaled` first, on the render stream
-static const uint32_t* delta_frame(zr_ctx* c)
+// What a delivery compares and lists (*frame): the frame - with highlight delivery on, the frame highlighted into the context's buffer
+// first - or at a delta scale above 1 that filtered into `scaled`, on the render stream
+static int delta_frame(zr_ctx* c, const uint32_t** frame)
 {
     const zr_ctx::Delta& D = c->delta;
-    if (D.scale <= 1u) return c->d_color;
-    zr_launch_frame_scale(c->d_color, D.scaled, c->W, c->H, D.scale, c->stream);
-    return D.scaled;
+    *frame = c->d_color;
+    if (c->hl.delta)
+        if (int rc = zr_highlight_enqueue(c, nullptr, frame)) return rc;
+    if (D.scale <= 1u) return ZR_OK;
+    zr_launch_frame_scale(*frame, D.scaled, c->W, c->H, D.scale, c->stream);
+    *frame = D.scaled;
+    return ZR_OK;
 }
 
 // One delivery on the render stream; full and serial are the host's to know, the kernels only write them into the header
@@ -109,7 +115,9 @@ static int delta_enqueue(zr_ctx* c, uint32_t* header_dev, uint32_t* list_dev, vo
     zr_ctx::Delta& D = c->delta;
     const ZrDeltaExtent E = zr_delta_extent(c);
     const uint32_t serial = D.serial + 1u;
-    zr_launch_frame_delta(delta_frame(c), D.delivered, D.flags, header_dev, list_dev, packed_dev, E.W, E.H, E.tiles_x, E.n_tiles, D.full ? 1u : 0u, serial,
+    const uint32_t* frame = nullptr;
+    if (int rc = delta_frame(c, &frame)) return rc;
+    zr_launch_frame_delta(frame, D.delivered, D.flags, header_dev, list_dev, packed_dev, E.W, E.H, E.tiles_x, E.n_tiles, D.full ? 1u : 0u, serial,
                           c->stream);
     HIPCHK(c, hipGetLastError());
     D.serial = serial; D.full = false;
@@ -168,7 +176,9 @@ static int delta_enqueue_packed(zr_ctx* c, uint32_t* header_dev, uint32_t* list_
     zr_ctx::Delta& D = c->delta;
     const ZrDeltaExtent E = zr_delta_extent(c);
     const uint32_t serial = D.serial + 1u;
-    zr_launch_frame_delta_packed(delta_frame(c), D.delivered, D.flags, D.codec.lens, header_dev, list_dev, offsets_dev, stream_dev, E.W, E.H, E.tiles_x, E.n_tiles,
+    const uint32_t* frame = nullptr;
+    if (int rc = delta_frame(c, &frame)) return rc;
+    zr_launch_frame_delta_packed(frame, D.delivered, D.flags, D.codec.lens, header_dev, list_dev, offsets_dev, stream_dev, E.W, E.H, E.tiles_x, E.n_tiles,
                                  D.full ? 1u : 0u, serial, c->stream);
     HIPCHK(c, hipGetLastError());
     D.serial = serial; D.full = false;

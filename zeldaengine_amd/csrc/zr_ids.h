@@ -26,3 +26,9 @@ struct ZrIdsArgs {
 void zr_launch_id_census(const ZrIdsArgs& A, int mode, hipStream_t s);
 // the listed slots -> zr_hit records (unsorted), and those slots cleared for the next query
 void zr_launch_id_hits(const ZrIdsArgs& A, uint32_t n, zr_hit* out, hipStream_t s);
+// zr_highlight.hip: the winner plane resolved against the set (a bit per slot) into bit_plane, ceil(W / 64) 64-bit words per row; and
+// `frame` (16-byte aligned) outlined and filled by it into dst (4-byte aligned), both W x H
+void zr_launch_highlight_mask(const uint32_t* prim_plane, const ZrIdsDraw* draws, uint32_t n_draws, const uint32_t* set_bits, unsigned long long* bit_plane, uint32_t W,
+                              uint32_t H, hipStream_t st);
+void zr_launch_highlight_apply(const uint32_t* frame, const unsigned long long* bit_plane, uint32_t* dst, uint32_t W, uint32_t H, const zr_highlight_style& style,
+                               hipStream_t st);

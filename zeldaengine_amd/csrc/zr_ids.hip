@@ -2,16 +2,7 @@
 // (zr_set_id_capture).  k_id_census maps every pixel of a rectangle to its (object, instance) slot and counts, per slot, the pixels it
 // won and (picking) its nearest pixel; k_id_hits turns the slots a pick touched into zr_hit records and clears them again.
 // Integer atomics only: every result is independent of arrival order, bit for bit.
-#include "zr_dev.h"
-#include "zr_ids.h"
-
-// the draw that holds primitive p (draws[] is sorted by prim_base; the sentinel is never returned for a scene primitive)
-__device__ __forceinline__ uint32_t find_draw(const ZrIdsDraw* __restrict__ draws, uint32_t n, uint32_t p)
-{
-    uint32_t lo = 0, hi = n - 1u;
-    while (lo < hi) { const uint32_t mid = (lo + hi + 1u) >> 1; if (draws[mid].prim_base <= p) lo = mid; else hi = mid - 1u; }
-    return lo;
-}
+#include "zr_ids_dev.h"      // find_draw, the wave's one-search shortcut, primitive -> instance: shared with zr_highlight.hip
 
 // One lane per pixel of the rectangle, row-major: a wave reads 64 consecutive pixels of a row (256 B of the plane).
 // Per wave, the lanes that share a slot are aggregated before any atomic (one add, and one 64-bit min when picking, per distinct slot):
@@ -27,21 +18,14 @@ __global__ __launch_bounds__(256) void k_id_census(ZrIdsArgs A)
         p = (A.y0 + ry) * A.W + A.x0 + rx;
         prim = A.prim[p];
     }
-    const bool hit = prim < A.draws[A.n_draws].prim_base;      // (the sentinel: the scene's primitive count; ZR_EMPTY_PRIM is above it)
+    const bool hit = ids_scene_prim(A.draws, A.n_draws, prim);
     const unsigned long long hm = __ballot(hit);
     if (hm == 0ull) {          // (wave-uniform)
         if (MODE == ZR_IDS_OBJECTS && in) A.obj_plane[p] = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
         return;
     }
-    // primitive -> draw: when every lane's primitive lies in the draw of the first lane that has one (the common case), one search
-    // for the whole wave; else each lane searches its own
-    const uint32_t p0 = __shfl(prim, __ffsll((long long)hm) - 1);
-    uint32_t d = find_draw(A.draws, A.n_draws, p0);
-    const uint32_t lo0 = A.draws[d].prim_base, hi0 = A.draws[d + 1u].prim_base;
-    if (__ballot(hit && (prim < lo0 || prim >= hi0)) != 0ull && hit) d = find_draw(A.draws, A.n_draws, prim);
-    const ZrIdsDraw D = A.draws[d];
-    const uint32_t local = hit ? prim - D.prim_base : 0u;
-    const uint32_t inst = local / D.n_tris;
+    const ZrIdsDraw D = A.draws[ids_wave_draw(A.draws, A.n_draws, prim, hit, hm)];
+    const uint32_t inst = ids_instance(D, ids_local(D, prim, hit));
     if (MODE == ZR_IDS_OBJECTS) {
         if (in) A.obj_plane[p] = hit ? make_uint2(D.object, inst) : make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
         return;
@@ -78,7 +62,7 @@ __global__ __launch_bounds__(256) void k_id_hits(ZrIdsArgs A, uint32_t n, zr_hit
     const unsigned long long key = A.keys[s];
     const uint32_t p = (uint32_t)key, prim = A.prim[p];
     const ZrIdsDraw D = A.draws[find_draw(A.draws, A.n_draws, prim)];
-    const uint32_t local = prim - D.prim_base, inst = local / D.n_tris;
+    const uint32_t local = ids_local(D, prim, true), inst = ids_instance(D, local);
     zr_hit h;
     h.object = D.object; h.instance = inst; h.pixels = A.counts[s]; h.triangle = local - inst * D.n_tris;
     h.y = p / A.W; h.x = p - h.y * A.W; h.depth = __uint_as_float((uint32_t)(key >> 32)); h.reserved = 0u;

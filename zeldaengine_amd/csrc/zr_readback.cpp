@@ -305,7 +305,7 @@ extern "C" int zr_set_id_capture(zr_ctx* c, int enable)
 }
 
 // The frame enqueued last kept its winners and still describes the scene; `sync`: finish it first (its overflow is the query's error).
-static int ids_ready(zr_ctx* c, const char* what, bool sync)
+int ids_ready(zr_ctx* c, const char* what, bool sync)
 {
     if (!c->rendered || c->stage != 0) return zr_fail(c, ZR_ERR_STATE, std::string(what) + ": no finished frame enqueued");
     if (!c->ids_frame) return zr_fail(c, ZR_ERR_STATE, std::string(what) + ": the last frame was rendered without id capture (zr_set_id_capture)");
@@ -313,7 +313,7 @@ static int ids_ready(zr_ctx* c, const char* what, bool sync)
     HIPCHK(c, hipSetDevice(c->device));
     return sync ? zr_finish(c) : ZR_OK;
 }
-static ZrIdsArgs ids_args(zr_ctx* c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h)
+ZrIdsArgs ids_args(zr_ctx* c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h)
 {
     const FrameCopy& F = c->fc[c->fcur];                      // (stage 0: the copy the frame enqueued last wrote)
     ZrIdsArgs A; memset(&A, 0, sizeof A);
@@ -377,12 +377,13 @@ extern "C" int zr_pick(zr_ctx* c, uint32_t x, uint32_t y, uint32_t w, uint32_t h
     });
 }
 
-static size_t ids_slot_bytes(const zr_ctx* c)
+size_t ids_slot_count(const zr_ctx* c)
 {
     size_t slots = 0;
     for (const auto& o : c->objects) slots += o.n_inst;      // (n_inst = max(1, instances))
-    return 4 * slots;
+    return slots;
 }
+static size_t ids_slot_bytes(const zr_ctx* c) { return 4 * ids_slot_count(c); }
 // The whole-frame census into a count array on the device (cleared first), on the host's stream.
 static int ids_coverage(zr_ctx* c, uint32_t* counts_dev, size_t bytes)
 {

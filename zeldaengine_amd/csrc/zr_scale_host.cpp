@@ -28,7 +28,7 @@ extern "C" int zr_frame_downscale(const uint8_t* rgba8, uint32_t width, uint32_t
 }
 
 // The context's lighting pass writes the row-major frame, and the frame enqueued last is a finished one
-static int scale_ready(zr_ctx* c, const char* what)
+int scale_ready(zr_ctx* c, const char* what)
 {
     if (c->cfg.tile_world > 1 || (c->cfg.flags & ZR_FLAG_PACKED_TILES))
         return zr_fail(c, ZR_ERR_UNSUPPORTED, std::string(what) + ": this context's lighting pass writes packed tiles, not the frame (tile_world > 1, ZR_FLAG_PACKED_TILES)");

@@ -119,7 +119,11 @@ static int update_stage(zr_ctx* c, hipStream_t x, const void* src, size_t bytes,
 
 int zr_update_host_form(zr_ctx* c, const void* src, size_t bytes, const std::function<int(const void*, hipStream_t)>& enqueue)
 {
-    hipStream_t x = zr_update_lane(c);
+    return zr_update_host_form_on(c, zr_update_lane(c), src, bytes, enqueue);
+}
+
+int zr_update_host_form_on(zr_ctx* c, hipStream_t x, const void* src, size_t bytes, const std::function<int(const void*, hipStream_t)>& enqueue)
+{
     void* staged = nullptr; hipEvent_t ev = nullptr;
     int rc = update_stage(c, x, src, bytes, &staged, &ev);
     if (rc == ZR_OK) rc = enqueue(staged, x);

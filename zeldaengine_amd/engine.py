@@ -62,6 +62,7 @@ def lib():
         **abi.VISIBILITY_SIGNATURES,
         **abi.FRAME_DELTA_SIGNATURES,
         **abi.FRAME_SCALE_SIGNATURES,
+        **abi.HIGHLIGHT_SIGNATURES,
         "zr_set_cubemap": [vp, vp, u32],
         "zr_set_skydome": [vp, vp, u32, vp, u32, vp],
         "zr_set_background": [vp, vp],
@@ -285,6 +286,27 @@ def frame_downscale(img, s):
     rc = lib().zr_frame_downscale(_ptr(img), w, h, s, _ptr(out), out.nbytes)
     if rc:
         raise ZeldaRenderError(rc, "zr_frame_downscale: bad argument")
+    return out
+
+
+def _style(style):
+    """an abi.HighlightStyle from one, from None (the default) or from a dict of make_highlight_style's arguments"""
+    if isinstance(style, abi.HighlightStyle):
+        return style
+    return abi.make_highlight_style(**(style or {}))
+
+
+def frame_highlight(img, mask, style=None):
+    """zr_frame_highlight, the host statement of the highlight rule (host code only): img (H, W, 4) uint8, mask (H, W) non-zero where
+    highlighted, style an abi.HighlightStyle (None: the default) -> (H, W, 4) uint8"""
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+    assert img.ndim == 3 and img.shape[2] == 4 and mask.shape == img.shape[:2]
+    st = _style(style)
+    out = np.zeros_like(img)
+    rc = lib().zr_frame_highlight(_ptr(img), _ptr(mask), img.shape[1], img.shape[0], C.byref(st), C.sizeof(st), _ptr(out), out.nbytes)
+    if rc:
+        raise ZeldaRenderError(rc, "zr_frame_highlight: bad argument")
     return out
 
 
@@ -709,6 +731,47 @@ class Renderer:
         """The frame enqueued last filtered by s -> a caller-owned device buffer (address, 4-byte aligned, ceil(W / s) * ceil(H / s) * 4
         bytes), in stream order, no host synchronisation."""
         self._chk(self.L.zr_copy_frame_scaled_async(self.h, s, C.c_void_p(color_dev) if color_dev else None))
+
+    # ---- highlighting a selection: an outline round, and a fill over, a set of instances in the delivered frame
+    def highlight_set(self, obj, on=True, first=0):
+        """zr_highlight_set: instances first .. of object `obj` into (non-zero) or out of (0) the set; on: a flag per instance, or one
+        flag for a non-instanced object / the single instance `first`"""
+        on = np.ascontiguousarray(np.atleast_1d(np.asarray(on)) != 0, dtype=np.uint8)
+        self._chk(self.L.zr_highlight_set(self.h, obj, first, _ptr(on), on.size))
+
+    def highlight_clear(self):
+        self._chk(self.L.zr_highlight_clear(self.h))
+
+    def highlight_get(self):
+        """The set, a byte per slot of instance_coverage"""
+        out = np.zeros(self.instance_slots()[1], dtype=np.uint8)
+        self._chk(self.L.zr_highlight_get(self.h, _ptr(out) if out.size else None, out.nbytes))
+        return out
+
+    def set_highlight_style(self, style=None, **kw):
+        """zr_set_highlight_style: an abi.HighlightStyle, or make_highlight_style's arguments (outline=, fill=, radius=)"""
+        st = _style(style if style is not None else kw)
+        self._chk(self.L.zr_set_highlight_style(self.h, C.byref(st), C.sizeof(st)))
+
+    def highlight_style(self):
+        st = abi.HighlightStyle()
+        self._chk(self.L.zr_get_highlight_style(self.h, C.byref(st), C.sizeof(st)))
+        return st
+
+    def color_highlighted(self, s=1):
+        """zr_read_color_highlighted: the frame with the set outlined and filled, filtered by s (1..8) -> (ceil(H / s), ceil(W / s), 4) uint8"""
+        out = np.zeros((-(-self.H // max(s, 1)), -(-self.W // max(s, 1)), 4), dtype=np.uint8)
+        self._chk(self.L.zr_read_color_highlighted(self.h, s, _ptr(out), out.nbytes))
+        return out
+
+    def copy_frame_highlighted_async(self, s, color_dev):
+        """The frame enqueued last, highlighted and filtered by s -> a caller-owned device buffer (address, 4-byte aligned, ceil(W / s) *
+        ceil(H / s) * 4 bytes), in stream order, no host synchronisation."""
+        self._chk(self.L.zr_copy_frame_highlighted_async(self.h, s, C.c_void_p(color_dev) if color_dev else None))
+
+    def set_frame_delta_highlight(self, on=True):
+        """The deliveries of changes deliver the highlighted frame (default off; only while delta is off, kept across set_frame_delta(False))."""
+        self._chk(self.L.zr_set_frame_delta_highlight(self.h, 1 if on else 0))
 
     def read_frame_delta(self, tiles=None, pixels=None):
         """One delivery to the host: (tiles[n] uint32 ascending, pixels[n, 32, 32, 4] uint8, header dict).  tiles / pixels: full-sized
