@@ -402,6 +402,18 @@ __device__ __forceinline__ bool hiz_occluded(const ZrHiz& Z, uint2 pr, float zmi
 #ifndef ZR_REST_SKIP_EMPTY_LOADS
 #define ZR_REST_SKIP_EMPTY_LOADS 1
 #endif
+// How k_lighting_rest is set up, each switchable for A/B ("The resting frame's set-up", has each measured on its own).
+// RECORDS_ONE_TRIP: a part's eight records arrive as one vector load per lane behind one wait, the box by row reductions on the DPP
+// network (0: a scalar load and a wait per record).  LIGHT_WHOLE: a light's eight dwords are read before any of them is compared - the
+// tile list's test from an LDS copy staged with the tables, the light loop by one scalar load (0: a field at a time, each load behind
+// the comparison before it).  (A persistent grid, the empty pixel's colour kept across a workgroup's parts and the next part's records
+// requested ahead were measured with these two and showed nothing or lost: taken out again - App. A.)
+#ifndef ZR_REST_RECORDS_ONE_TRIP
+#define ZR_REST_RECORDS_ONE_TRIP 1
+#endif
+#ifndef ZR_REST_LIGHT_WHOLE
+#define ZR_REST_LIGHT_WHOLE 1
+#endif
 #ifndef ZR_PIXELS_PER_THREAD
 #define ZR_PIXELS_PER_THREAD 1     // of k_resolve_gbuffer and k_lighting: 1, 2 or 4 (a tile is 1 024 pixels; workgroups per tile follow)
 #endif

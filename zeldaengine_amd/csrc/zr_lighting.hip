@@ -226,8 +226,23 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(MODE == ZR_L
 //    owns the workgroup's first such pixel: that pixel shaded like any other, its standing terms from the slot the fill's one-pixel
 //    launch wrote (rest[0], rest[1]) instead of plane[p], parked in LDS behind one barrier whose condition the records make uniform.
 //    Every workgroup that holds an empty pixel computes the same colour: none waits for another.
+//  - Set-up is by round trips, not by loops of them.  The 1 536 table floats, an LDS copy of the light records and the part's records
+//    are all requested before the first of them is waited for.  The part's eight records arrive as ONE dword per lane, laid out so
+//    that half a row of 16 lanes holds one field of every record: the box is three DPP steps of min and three of max, the masks are lane
+//    reads.  A light's record arrives whole (zr_shade.h, ArgLight): the list's test reads the lane's light from the LDS copy, the light
+//    loop by one scalar load of eight dwords.
 // One pixel per thread only (the records are per wave of such a kernel); other builds keep the pass that reads XkView.
 #if ZR_PIXELS_PER_THREAD == 1
+// Of a part's WAVES (at most 8) records a dword per lane: lane 8 f + w of a wave holds field f of record w % WAVES (fields 0 - 2 lo,
+// 3 - 5 hi, 6 - 7 empty): the eight lanes of a field are half a DPP row.
+template <uint32_t WAVES>
+__device__ __forceinline__ uint32_t rest_records_fetch(const float4* __restrict__ rest, uint32_t first_record)
+{
+    constexpr uint32_t RECW = (uint32_t)(sizeof(ZrRestRecord) / 4u);
+    const uint32_t* __restrict__ w = (const uint32_t*)(rest + ZR_REST_SLOT) + (size_t)first_record * RECW;      // (wave-uniform; the lane's offset is 32 bits)
+    return w[((threadIdx.x & 7u) % WAVES) * RECW + ((threadIdx.x >> 3) & 7u)];
+}
+
 template <bool LIGHT_LIST, bool BACKGROUND, int TB>
 __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(ZR_LIGHT_KEPT_WAVES, ZR_LIGHT_KEPT_WAVES)))
 void k_lighting_rest(ZrLightParams L, ZrRestArgs R, const uint32_t* __restrict__ owned_tiles, GBufferPtrs G, const float* __restrict__ srgb_lut,
@@ -235,38 +250,77 @@ void k_lighting_rest(ZrLightParams L, ZrRestArgs R, const uint32_t* __restrict__
 {
     static_assert(sizeof(ZrLightParams) + sizeof(ZrRestArgs) + sizeof(GBufferPtrs) + 6 * sizeof(void*) + 256 /* the hidden arguments */ < 4096,
                   "k_lighting_rest: the argument block");
-    __shared__ float tl[512];            // as in k_lighting
-    __shared__ float u10[1024];
-    __shared__ uint32_t empty_px;
-    float* const slut = tl; float* const u8 = tl + 256;
     constexpr uint32_t PARTS = TILE_PIX / (uint32_t)TB, WAVES = (uint32_t)TB / 64u, NONE = 0xFFFFFFFFu;
+    static_assert((WAVES <= 8u || !ZR_REST_RECORDS_ONE_TRIP) && 1536u % (uint32_t)TB == 0u, "k_lighting_rest: a part's records are a dword per lane");
+    __shared__ float tab[1536];          // k_lighting's tl (sRGB decode, then c / 255: tex_decode's layout) and u10, in one piece
+    __shared__ uint32_t empty_px;
+    constexpr bool STAGED = LIGHT_LIST && ZR_REST_LIGHT_WHOLE;      // the light records' LDS copy, for the tile list's test (a lane per light)
+    __shared__ ZrRestLight lpt[STAGED ? ZR_REST_ARG_LIGHTS : 1];
+    float* const tl = tab; float* const u8 = tab + 256; float* const u10 = tab + 512;
     const uint32_t part = blockIdx.x % PARTS, tile_slot = blockIdx.x / PARTS;
     const uint32_t i = threadIdx.x + part * (uint32_t)TB;      // the thread's pixel among the tile's
-    for (uint32_t k = threadIdx.x; k < 256u; k += (uint32_t)TB) { u8[k] = unorm_lut[k]; slut[k] = srgb_lut[k]; }
-    for (uint32_t k = threadIdx.x; k < 1024u; k += (uint32_t)TB) u10[k] = unorm_lut[256u + k];
+    const uint32_t first_record = tile_slot * ZR_REST_RECORDS_PER_TILE + part * WAVES;
+    uint32_t rec = 0u;
+    {   // every load is issued before the first is waited for
+        constexpr uint32_t NT = 1536u / (uint32_t)TB, LW = ZR_REST_ARG_LIGHTS * (uint32_t)(sizeof(ZrRestLight) / 4u), NL = STAGED ? (LW + (uint32_t)TB - 1u) / (uint32_t)TB : 0u;
+        float tv[NT], lv[NL ? NL : 1u];
+#pragma unroll
+        for (uint32_t k = 0; k < NT; ++k) { const uint32_t j = threadIdx.x + k * (uint32_t)TB; tv[k] = j < 256u ? srgb_lut[j] : unorm_lut[j - 256u]; }
+#pragma unroll
+        for (uint32_t k = 0; k < NL; ++k) { const uint32_t j = threadIdx.x + k * (uint32_t)TB; lv[k] = ((const float*)R.pt)[LW % (uint32_t)TB == 0u || j < LW ? j : 0u]; }
+        if (ZR_REST_RECORDS_ONE_TRIP) rec = rest_records_fetch<WAVES>(rest, first_record);
+#pragma unroll
+        for (uint32_t k = 0; k < NT; ++k) tab[threadIdx.x + k * (uint32_t)TB] = tv[k];
+#pragma unroll
+        for (uint32_t k = 0; k < NL; ++k) { const uint32_t j = threadIdx.x + k * (uint32_t)TB; if (LW % (uint32_t)TB == 0u || j < LW) ((float*)lpt)[j] = lv[k]; }
+    }
+    const uint32_t tile = owned_tiles[tile_slot];
     __syncthreads();
     if (L.clear_next) {      // as in k_lighting
         const uint32_t per = (L.clear_n + gridDim.x - 1u) / gridDim.x, b = blockIdx.x * per;
         for (uint32_t k = threadIdx.x; k < per && b + k < L.clear_n; k += (uint32_t)TB) L.clear_next[b + k] = 0x3F800000u;
     }
-    const uint32_t tile = owned_tiles[tile_slot];
     const int tx0 = (int)(tile % L.tiles_x) * TILE, ty0 = (int)(tile / L.tiles_x) * TILE;
     const zf3 cam = zr3(R.cam[0], R.cam[1], R.cam[2]);
 
     // the workgroup's records: the tile's box, the first empty pixel (thread number, or NONE), this wave's empty pixels
-    const ZrRestRecord* __restrict__ rec = (const ZrRestRecord*)(rest + ZR_REST_SLOT) + ((size_t)tile_slot * ZR_REST_RECORDS_PER_TILE + part * WAVES);
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     float blo[3] = { __builtin_inff(), __builtin_inff(), __builtin_inff() }, bhi[3] = { -__builtin_inff(), -__builtin_inff(), -__builtin_inff() };
     uint32_t first = NONE;
     unsigned long long mine = 0ull;
-#pragma unroll 1      // (a record at a time: unrolled, the eight records' 64 scalar registers spill)
+#if ZR_REST_RECORDS_ONE_TRIP
+    if constexpr (LIGHT_LIST && ZR_REST_BOX_FROM_RECORDS) {
+        // row_shr 1, 2, 4 fold exactly eight lanes into the last of them: lane 8 f + 7 holds field f over the records (min / max are exact
+        // in any order; the fill's -inf / +inf for a non-finite position pass through as they did)
+        int lo, hi;
+        { const int idn = 0x7F800000; int r = (int)rec; ZR_DPP_STEP(op_fmin, 0x111, 0xF); ZR_DPP_STEP(op_fmin, 0x112, 0xF); ZR_DPP_STEP(op_fmin, 0x114, 0xF); lo = r; }
+        { const int idn = (int)0xFF800000; int r = (int)rec; ZR_DPP_STEP(op_fmax, 0x111, 0xF); ZR_DPP_STEP(op_fmax, 0x112, 0xF); ZR_DPP_STEP(op_fmax, 0x114, 0xF); hi = r; }
+        for (int a = 0; a < 3; ++a) { blo[a] = zr_u2f((uint32_t)__builtin_amdgcn_readlane(lo, 8 * a + 7)); bhi[a] = zr_u2f((uint32_t)__builtin_amdgcn_readlane(hi, 8 * (3 + a) + 7)); }
+    }
+    {   // lanes 48 + w and 56 + w hold the two halves of record w's mask
+        const uint32_t lane = threadIdx.x & 63u;
+        const unsigned long long nz64 = __ballot(lane >= 48u && (lane & 7u) < WAVES && rec != 0u);
+        const uint32_t nz = ((uint32_t)(nz64 >> 48) | (uint32_t)(nz64 >> 56)) & 255u;      // bit w: record w holds an empty pixel
+        if (nz != 0u) {
+            const int w0 = __builtin_ctz(nz);
+            const unsigned long long em = (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 48 + w0) |
+                                          (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 56 + w0) << 32;
+            first = (uint32_t)w0 * 64u + (uint32_t)__builtin_ctzll(em);
+        }
+        mine = (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 48 + (int)wave) |
+               (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 56 + (int)wave) << 32;
+    }
+#else      // (A/B: a record at a time, a scalar load and a wait each)
+    const ZrRestRecord* __restrict__ recs = (const ZrRestRecord*)(rest + ZR_REST_SLOT) + first_record;
+#pragma unroll 1      // (unrolled, the eight records' 64 scalar registers spill)
     for (uint32_t w = 0; w < WAVES; ++w) {
         if constexpr (LIGHT_LIST && ZR_REST_BOX_FROM_RECORDS)
-            for (int a = 0; a < 3; ++a) { blo[a] = __builtin_fminf(blo[a], rec[w].lo[a]); bhi[a] = __builtin_fmaxf(bhi[a], rec[w].hi[a]); }
-        const unsigned long long em = (unsigned long long)rec[w].empty[0] | (unsigned long long)rec[w].empty[1] << 32;
+            for (int a = 0; a < 3; ++a) { blo[a] = __builtin_fminf(blo[a], recs[w].lo[a]); bhi[a] = __builtin_fmaxf(bhi[a], recs[w].hi[a]); }
+        const unsigned long long em = (unsigned long long)recs[w].empty[0] | (unsigned long long)recs[w].empty[1] << 32;
         if (em != 0ull && first == NONE) first = w * 64u + (uint32_t)__builtin_ctzll(em);
         if (w == wave) mine = em;
     }
+#endif
     const int px = tx0 + (int)(i & (TILE - 1)), py = ty0 + (int)(i / TILE);
     const bool inside = px < (int)L.W && py < (int)L.H;
     const size_t p = (size_t)py * L.W + (size_t)px;
@@ -292,7 +346,8 @@ void k_lighting_rest(ZrLightParams L, ZrRestArgs R, const uint32_t* __restrict__
     unsigned long long amask = 0ull;      // the tile's light list (at most ZR_REST_ARG_LIGHTS = 64 lights: a lane each)
     if constexpr (LIGHT_LIST) {
         const uint32_t li = threadIdx.x & 63u;
-        amask = __ballot(li < R.nPoint && light_listed(ArgLight{ &R.pt[li < R.nPoint ? li : 0u] }, blo, bhi));
+        const ZrRestLight* const pt = STAGED ? lpt : R.pt;
+        amask = __ballot(li < R.nPoint && light_listed(ArgLight{ &pt[li < R.nPoint ? li : 0u] }, blo, bhi));
     }
 
     const bool is_empty = ((mine >> (threadIdx.x & 63u)) & 1ull) != 0ull, owner = threadIdx.x == first;

@@ -124,6 +124,18 @@ struct ViewLight {
     __device__ __forceinline__ float dir(int k) const { return Lt->Direction[k]; }
     __device__ __forceinline__ float falloff() const { return Lt->Direction[3]; }
 };
+#if ZR_REST_LIGHT_WHOLE
+// (the record arrives whole: both halves are requested before anything is compared - one 32-byte scalar load at a wave-uniform address,
+// two 16-byte loads per lane otherwise - and the tests run on registers: no load waits behind the comparison before it)
+struct ArgLight {
+    float4_u c, p;
+    __device__ __forceinline__ explicit ArgLight(const ZrRestLight* a) : c(*(const float4_u*)a->color), p(*(const float4_u*)a->pos_falloff) {}
+    __device__ __forceinline__ float pos(int k) const { return p[k]; }
+    __device__ __forceinline__ float color(int k) const { return c[k]; }
+    __device__ __forceinline__ float dir(int) const { return 0.0f; }      // (never a directional light)
+    __device__ __forceinline__ float falloff() const { return p[3]; }
+};
+#else      // (A/B: a field at a time)
 struct ArgLight {
     const ZrRestLight* a;
     __device__ __forceinline__ float pos(int k) const { return a->pos_falloff[k]; }
@@ -131,6 +143,7 @@ struct ArgLight {
     __device__ __forceinline__ float dir(int) const { return 0.0f; }      // (never a directional light)
     __device__ __forceinline__ float falloff() const { return a->pos_falloff[3]; }
 };
+#endif
 // The tile light list's test (k_lighting): false when the light's sphere of influence misses the box [blo, bhi] of the tile's world
 // positions - every pixel's own exact test in shade_lights would then skip it.
 template <typename LIGHT>
