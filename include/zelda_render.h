@@ -124,6 +124,28 @@ void zr_destroy(zr_ctx* ctx);
 const char* zr_last_error(const zr_ctx* ctx);
 /* Render on a caller-owned hipStream_t (NULL = the context's own stream). */
 int  zr_set_stream(zr_ctx* ctx, void* hip_stream);
+/* Replaces RecreateSwapChain (ZE:2311-2330, reached from ZE:1973-1976): a new extent, the same scene, nothing submitted again.
+ * After zr_resize(ctx, W', H') everything observable - every later frame in every debug view and shading mode, the GBuffer targets, the
+ * shadow map, the identity queries, covered_pixels / covered_shadow_texels, zr_world_save_json - is that of a new context with the same
+ * zr_config but for the extent, given the same scene, the same calls and the same last uniforms.  Kept as they are, device memory and
+ * all: meshes, objects (instances, visibility, materials - also what only a device-form update ever wrote), Profabs, the world, cubemap,
+ * skydome, background, the shadow map, streams and staging, limits, bucket share, shading mode, debug view, id capture, timing
+ * interval, livelink, the highlight set and style.  Re-made: whatever is sized by the extent.  Forgotten: every per-pixel history - the
+ * next frame draws its camera pass as a scene's first frame does, while the shadow map stands or falls by its own key, as after a
+ * camera move (a resize with light and casters still enqueues no shadow pipeline).  Until that frame the read-backs, the identity queries
+ * and the deliveries answer as on a context that has rendered no frame.
+ * Uniforms of zr_update_uniforms (and of the world forms, which go through it) are evaluated again for the new extent: Proj,
+ * ViewProjSpace and ViewportInfo are bit-equal to a new context's.  Uniforms last set raw by zr_set_frame stay as given.
+ * While delta is on its buffers are re-made for the new (scaled) extent; scale, highlight flag and packed mode stay, serial goes on
+ * counting, the next delivery is a full one.  A caller-owned tile buffer (zr_set_tiles_buffer) goes back to the internal one, and
+ * zr_color_device_ptr / zr_tiles_device_buffer answer anew.
+ * The call synchronises everything the library has enqueued.  The new set is built beside the old one and swapped in on success: a
+ * resize that cannot allocate reports what zr_create would have and leaves the context rendering at the old extent.
+ * ZR_ERR_ARG (before anything is touched): a zero extent, an edge beyond 255 * ZR_TILE, more than 16 000 tiles.  ZR_ERR_STATE: between
+ * the stages of a frame.  ZR_ERR_UNSUPPORTED: the native multi-GPU host is attached (zr_dist_prepare).  The extent the context already
+ * has: ZR_OK, and nothing happens - no synchronisation, no rest ends. */
+int  zr_resize(zr_ctx* ctx, uint32_t width, uint32_t height);
+int  zr_get_extent(zr_ctx* ctx, uint32_t* width, uint32_t* height);      /* the extent as it is now (either pointer may be NULL) */
 int  zr_tile_size(void);                            /* the ZR_TILE this library was built with */
 uint32_t zr_abi_version(void);                      /* the ZR_ABI_VERSION this library was built with */
 
@@ -457,7 +479,7 @@ int  zr_frame_scaled_extent(uint32_t width, uint32_t height, uint32_t scale, uin
 /* The host statement of the filter, context-free host code: what a client or a test compares with.  bytes == Wd*Hd*4. */
 int  zr_frame_downscale(const uint8_t* rgba8, uint32_t width, uint32_t height, uint32_t scale, uint8_t* dst, size_t bytes);
 /* Host form: zr_finish first (its error is passed on, as by zr_read_color), one launch into a buffer the context makes at first use
- * (for scale 2, the largest output; released by zr_destroy), then Wd*Hd*4 bytes to the host - row-major, top-left origin. */
+ * (for scale 2, the largest output; released by zr_destroy or a zr_resize), then Wd*Hd*4 bytes to the host - row-major, top-left origin. */
 int  zr_read_color_scaled(zr_ctx* ctx, uint32_t scale, uint8_t* rgba8, size_t bytes);
 /* Device form, straight into a caller-owned DEVICE buffer of Wd*Hd*4 bytes (4-byte aligned): synchronises nothing, ordered on the render
  * stream exactly as zr_copy_frame_async's colour copy - behind the lighting pass of the frame enqueued last, ahead of whatever the next
@@ -588,7 +610,7 @@ int  zr_shadow_pack(zr_ctx* ctx, void* packed_dev, void* hip_stream);
 int  zr_shadow_unpack(zr_ctx* ctx, const void* gathered_dev, void* hip_stream);
 /* Caller-owned shadow map, float[shadow_dim^2] device memory (NULL = internal). */
 int  zr_set_shadow_buffer(zr_ctx* ctx, void* dev_ptr);
-/* Packed tile-major RGBA8 of the tiles this rank owns (device pointer, stable until zr_destroy). */
+/* Packed tile-major RGBA8 of the tiles this rank owns (device pointer, stable until zr_destroy or a zr_resize). */
 int  zr_tiles_device_buffer(zr_ctx* ctx, void** dev_ptr, size_t* bytes_per_rank);
 /* Caller-owned packed buffer for the following frames (same size; NULL = the internal one).  Two alternating buffers let
  * frame k's all-gather overlap frame k+1's rendering. */
@@ -596,7 +618,7 @@ int  zr_set_tiles_buffer(zr_ctx* ctx, void* dev_ptr);
 int  zr_read_tiles(zr_ctx* ctx, uint8_t* dst, size_t bytes);             /* host copy of that buffer (tests) */
 /* Scatter the all-gathered buffer (tile_world * bytes_per_rank, rank-major, device pointer) into the frame. */
 int  zr_composite(zr_ctx* ctx, const void* gathered_dev);
-int  zr_color_device_ptr(zr_ctx* ctx, void** dev_ptr);
+int  zr_color_device_ptr(zr_ctx* ctx, void** dev_ptr);                  /* the row-major frame (stable until zr_destroy or a zr_resize) */
 
 /* --- native multi-GPU host: one process per GPU, RCCL over xGMI called by the library itself (no Python, no torch in the frame) ---
  * rank 0 makes the id (zr_dist_unique_id: 128 bytes, ncclGetUniqueId) and hands it to the other ranks by any means; every rank then

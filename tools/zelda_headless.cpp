@@ -7,7 +7,10 @@
 //
 //   zelda_headless --root DIR [--world FILE.json] [--livelink PORT [--wait-ms MS]] [--meshlet FILE.meshlet --profab NAME]
 //                  [--size WxH] [--shadow N] [--frames N] [--roll-light-step F] [--debug-view V] [--out FRAME.ppm] [--device D]
-//                  [--pick X,Y[,W,H] [--highlight]] [--incremental] [--delta | --delta-packed] [--scale S]
+//                  [--pick X,Y[,W,H] [--highlight]] [--incremental] [--delta | --delta-packed] [--scale S] [--resize-at FRAME:WxH]
+// --resize-at FRAME:WxH gives the live context a new extent ahead of frame FRAME (zr_resize), as a host whose window changes size does:
+// nothing is loaded again, it prints `resized <W>x<H>`, and with --delta, --delta-packed or --scale the client copy and the delivery
+// buffers follow the new (scaled) extent - the next delivery is a full one.
 // --incremental applies livelink payloads as a difference from the live scene (zr_livelink_set_incremental): a payload that only moves
 // the camera or a light keeps every object, the visibility history and the shadow map.
 // --delta delivers every frame the way a host with a remote client does (zr_read_frame_delta): only the 32 x 32 tiles that differ from
@@ -48,6 +51,7 @@ int main(int argc, char** argv)
     int port = -1, wait_ms = 10000, device = 0;
     float roll_step = 0.0f;
     bool pick = false, incremental = false, delta = false, packed = false, highlight = false; uint32_t px = 0, py = 0, pw = 1, ph = 1;
+    uint32_t resize_at = 0xFFFFFFFFu, RW = 0, RH = 0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
@@ -69,6 +73,7 @@ int main(int argc, char** argv)
         else if (a == "--delta-packed") delta = packed = true;
         else if (a == "--scale") scale = (uint32_t)atoi(next());
         else if (a == "--highlight") highlight = true;
+        else if (a == "--resize-at") { if (sscanf(next(), "%u:%ux%u", &resize_at, &RW, &RH) != 3) { fprintf(stderr, "--resize-at FRAME:WxH\n"); return 2; } }
         else if (a == "--pick") {
             const int got = sscanf(next(), "%u,%u,%u,%u", &px, &py, &pw, &ph);
             if (got != 2 && got != 4) { fprintf(stderr, "--pick X,Y[,W,H]\n"); return 2; }
@@ -117,10 +122,13 @@ int main(int argc, char** argv)
     if (highlight && delta && (rc = zr_set_frame_delta_highlight(c, 1))) return fail(c, "zr_set_frame_delta_highlight", rc);
     if (scale && delta && (rc = zr_set_frame_delta_scale(c, scale))) return fail(c, "zr_set_frame_delta_scale", rc);
     if (delta && (rc = zr_get_frame_delta_extent(c, &DW, &DH, &total, &delta_scale))) return fail(c, "zr_get_frame_delta_extent", rc);
-    const uint32_t T = ZR_TILE, tiles_x = (DW + T - 1) / T;
-    if (delta) {
+    const uint32_t T = ZR_TILE; uint32_t tiles_x = (DW + T - 1) / T;
+    auto size_delivery = [&]() {        // the client copy and a delivery's buffers for DW x DH in `total` tiles
         client.assign((size_t)DW * DH * 4, 0); slots.resize((size_t)total * (packed ? ZR_FRAME_DELTA_RECORD_MAX : T * T * 4)); list.resize(total);
         offsets.resize((size_t)total + 1);
+    };
+    if (delta) {
+        size_delivery();
         if ((rc = zr_set_frame_delta(c, packed ? ZR_FRAME_DELTA_PACKED : 1))) return fail(c, "zr_set_frame_delta", rc);
     }
     // --pick: what zr_pick finds in the rectangle, printed; with --highlight the hits go into the highlight set
@@ -140,6 +148,16 @@ int main(int argc, char** argv)
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t f = 0; f < frames; ++f) {
         int reloaded = 0;
+        if (f == resize_at) {           // the window changed size: a new extent, the same scene (delta state, selection and history of the map stay)
+            if ((rc = zr_resize(c, RW, RH)) || (rc = zr_get_extent(c, &W, &H))) return fail(c, "zr_resize", rc);
+            DW = W; DH = H;
+            if (scale && (rc = zr_frame_scaled_extent(W, H, scale, &DW, &DH))) return fail(c, "zr_frame_scaled_extent", rc);
+            if (delta && (rc = zr_get_frame_delta_extent(c, &DW, &DH, &total, &delta_scale))) return fail(c, "zr_get_frame_delta_extent", rc);
+            tiles_x = (DW + T - 1) / T;
+            if (delta) size_delivery();
+            else if (!client.empty()) client.assign((size_t)DW * DH * 4, 0);
+            printf("resized %ux%u\n", W, H);
+        }
         if (port >= 0 && (rc = zr_livelink_poll(c, &reloaded))) return fail(c, "zr_livelink_poll", rc);
         if ((rc = zr_world_update_uniforms(c, 0.0f, roll_step * (float)f, 0.016f * (float)f))) return fail(c, "zr_world_update_uniforms", rc);
         if ((rc = zr_render(c))) return fail(c, "zr_render", rc);

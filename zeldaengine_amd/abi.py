@@ -97,6 +97,11 @@ HIGHLIGHT_SIGNATURES = {
     "zr_set_frame_delta_highlight": [vp_, C.c_int],
     "zr_frame_highlight": [vp_, vp_, u32_, u32_, C.POINTER(HighlightStyle), C.c_size_t, vp_, C.c_size_t],
 }
+# the extent of a live context (include/zelda_render.h, "lifetime")
+EXTENT_SIGNATURES = {
+    "zr_resize": [vp_, u32_, u32_],
+    "zr_get_extent": [vp_, C.POINTER(u32_), C.POINTER(u32_)],
+}
 del vp_, u32_
 
 

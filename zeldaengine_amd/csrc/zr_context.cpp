@@ -71,7 +71,9 @@ ZrTilePartition zr_partition(uint32_t tiles_x, uint32_t tiles_y, uint32_t world,
 #endif
 
 // zr_create's device half, straight through: it returns at the first failure, and the caller releases the partial context as
-// zr_destroy releases any other
+// zr_destroy releases any other.  This is the context's half - what no extent sizes: streams, events, the shadow map's two copies, the
+// uniforms' copies, the statistics blocks, the look-up tables, the map's tile list, the clear pixel; the extent's half is
+// zr_extent_create (zr_resize.cpp), which zr_resize goes through again.
 static int create_device_state(zr_ctx* c)
 {
     ZrOwn& A = c->own;
@@ -80,14 +82,10 @@ static int create_device_state(zr_ctx* c)
     for (auto& fr : c->timed) for (auto& e : fr.ev) HIPCHK(c, A.event(&e));
     for (auto& e : c->ev_end) HIPCHK(c, A.event(&e));
     for (FrameCopy& F : c->fc) HIPCHK(c, A.event(&F.ev_ids, hipEventDisableTiming));
-    const size_t n = (size_t)c->W * c->H;
     for (FrameCopy& F : c->fc) {        // two frames in flight: see zr_ctx.h
-        GBufferPtrs& G = F.G;
-        HIPCHK(c, A.alloc(&G.depth, n)); HIPCHK(c, A.alloc(&G.scene_color, n)); HIPCHK(c, A.alloc(&G.gA, n)); HIPCHK(c, A.alloc(&G.gB, n));
-        HIPCHK(c, A.alloc(&G.gC, n)); HIPCHK(c, A.alloc(&G.gD, n)); HIPCHK(c, A.alloc(&G.overlay, n));
         HIPCHK(c, A.alloc(&F.shadow, (size_t)c->SD * c->SD)); HIPCHK(c, A.alloc(&F.view, 1)); HIPCHK(c, A.alloc(&F.empty_rgba, 1));
     }
-    HIPCHK(c, A.alloc(&c->d_color, n)); HIPCHK(c, A.alloc(&c->d_stats, 1));
+    HIPCHK(c, A.alloc(&c->d_stats, 1));
     HIPCHK(c, A.alloc(&c->d_sstats, 1));       // the shadow pipeline's own block (see zr_ctx.h)
     for (auto& r : c->d_rstats) HIPCHK(c, A.alloc(&r, 1));      // ... and a host-lane resolve's, per frame copy
     c->cov_block = c->d_stats;
@@ -105,19 +103,12 @@ static int create_device_state(zr_ctx* c)
         HIPCHK(c, hipMemcpy(c->d_unorm_lut, ul.data(), ul.size() * 4, hipMemcpyHostToDevice));
     }
 
-    // screen tiles: camera target partitioned t % world == rank; the shadow map is rendered whole on every rank
-    c->tiles_x = (c->W + ZR_TILE - 1) / ZR_TILE; c->tiles_y = (c->H + ZR_TILE - 1) / ZR_TILE; c->n_tiles = c->tiles_x * c->tiles_y;
+    // the shadow map is rendered whole on every rank (the screen's tiles: zr_extent_create)
     c->stiles_x = (c->SD + ZR_TILE - 1) / ZR_TILE; c->stiles_y = c->stiles_x; c->sn_tiles = c->stiles_x * c->stiles_y;
-    if (c->n_tiles > 16000u || c->sn_tiles > 16000u) return zr_fail(c, ZR_ERR_ARG, "too many tiles");   // binning histograms (4 B per tile, dynamic) + a few static words must fit the default 64 KB of LDS per workgroup
-    const ZrTilePartition tp = zr_partition(c->tiles_x, c->tiles_y, c->cfg.tile_world, c->cfg.tile_rank);
+    if (c->sn_tiles > 16000u) return zr_fail(c, ZR_ERR_ARG, "too many tiles");   // binning histograms (4 B per tile, dynamic) + a few static words must fit the default 64 KB of LDS per workgroup
     std::vector<uint32_t> sowned(c->sn_tiles);
     for (uint32_t t = 0; t < c->sn_tiles; ++t) sowned[t] = t;
-    c->slots_per_rank = tp.slots_per_rank; c->n_owned = (uint32_t)tp.owned.size();
-    HIPCHK(c, upload(A, &c->d_tile_map, tp.map)); HIPCHK(c, upload(A, &c->d_owned, tp.owned)); HIPCHK(c, upload(A, &c->d_sowned, sowned));
-    HIPCHK(c, A.alloc(&c->d_tiles, (size_t)c->slots_per_rank * ZR_TILE * ZR_TILE));
-    const uint32_t mt = (c->n_tiles > c->sn_tiles ? c->n_tiles : c->sn_tiles) * ZR_TSTRIDE + 1;     // (the bins use the first sn_tiles + 1 words)
-    HIPCHK(c, A.alloc(&c->sb.tile_count, mt)); HIPCHK(c, A.alloc(&c->sb.tile_offset, mt));
-    HIPCHK(c, A.alloc(&c->sb.tile_cursor, mt)); HIPCHK(c, A.alloc(&c->sb.chunk_offset, mt));
+    HIPCHK(c, upload(A, &c->d_sowned, sowned));
     {   // the clear values of ZE:3427-3433, as resolve_pixel writes them for an empty pixel
         HIPCHK(c, A.alloc(&c->d_clear_px, 64));
         uint32_t px[16] = { 0 };
@@ -152,7 +143,6 @@ static int create_device_state(zr_ctx* c)
     }
     HIPCHK(c, A.event(&c->ev_cam, hipEventDisableTiming)); HIPCHK(c, A.event(&c->ev_join, hipEventDisableTiming));
     HIPCHK(c, A.event(&c->ev_lane, hipEventDisableTiming));
-    for (auto& v : c->d_vis) HIPCHK(c, A.alloc(&v, n));
     { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) c->raster_blocks = (uint32_t)prop.multiProcessorCount * ZR_TILE_WG_PER_CU; }      // k_tile's persistent grid (6 workgroups fit a CU: two rounds of them; A/B 4 / 6 / 8 / 12 / 16 / 32 per CU -> 5 133 / 5 250 / 5 294 / 5 344 / 5 327 / 5 277 Mpixel/s)
     c->shadow_blocks = c->raster_blocks / ZR_TILE_WG_PER_CU * 8u;      // the shadow rasteriser's persistent grid stays at 8 per CU
     c->slow0_cap = std::max<uint32_t>(c->slow0_cap, 128u * c->sn_tiles);      // (a clipped triangle is listed once per tile of its meshlet)
@@ -161,33 +151,9 @@ static int create_device_state(zr_ctx* c)
     if (const char* e = getenv("ZR_RASTER_BLOCKS")) c->raster_blocks = (uint32_t)std::max(1, atoi(e));
     if (const char* e = getenv("ZR_SHADOW_BLOCKS")) c->shadow_blocks = (uint32_t)std::max(1, atoi(e));
 #endif
-    size_t hiz_texels = 0;
-    {   // Hi-Z pyramid: level l = max depth per (8 << l)^2 pixel block
-        for (int l = 0; l < 4; ++l) { c->hiz.hw[l] = (c->W + (8u << l) - 1) / (8u << l); c->hiz.hh[l] = (c->H + (8u << l) - 1) / (8u << l); hiz_texels += (size_t)c->hiz.hw[l] * c->hiz.hh[l]; }
-        c->hiz.fw = (c->W + 3u) / 4u; c->hiz.fh = (c->H + 3u) / 4u;
-        hiz_texels += (size_t)c->hiz.fw * c->hiz.fh;
-        HIPCHK(c, A.alloc(&c->d_hiz, hiz_texels));
-        static_assert(ZR_TILE == 32 && ZR_SUPERTILE_SHIFT >= 1, "a 64 x 64 region of the pyramid must lie inside one super-tile");
-        std::vector<uint32_t> regions;
-        for (uint32_t ry = 0; ry < (c->H + 63u) / 64u; ++ry)
-            for (uint32_t rx = 0; rx < (c->W + 63u) / 64u; ++rx)
-                if (zr_tile_owner(rx * 2u, ry * 2u, c->cfg.tile_world) == c->cfg.tile_rank) regions.push_back(rx | ry << 16);
-        c->n_hiz_regions = (uint32_t)regions.size();
-        HIPCHK(c, A.alloc(&c->d_hiz_regions, regions.size()));
-        if (!regions.empty()) HIPCHK(c, hipMemcpy(c->d_hiz_regions, regions.data(), regions.size() * 4, hipMemcpyHostToDevice));
-        float* p = c->d_hiz;
-        for (int l = 0; l < 4; ++l) { c->hiz.lvl[l] = p; p += (size_t)c->hiz.hw[l] * c->hiz.hh[l]; }
-        c->hiz.fine = p;
-    }
-    HIPCHK(c, zr_fill_sync({ { c->fc[0].G.overlay, 0, n * 4 }, { c->fc[1].G.overlay, 0, n * 4 },
-                             { c->d_stats, 0, sizeof(ZrDevStats) }, { c->d_sstats, 0, sizeof(ZrDevStats) }, { c->d_color, 0, n * 4 },
-                             { c->d_rstats[0], 0, sizeof(ZrDevStats) }, { c->d_rstats[1], 0, sizeof(ZrDevStats) },
-                             { c->d_tiles, 0, (size_t)c->slots_per_rank * ZR_TILE * ZR_TILE * 4 },
-                             { c->sb.tile_count, 0, mt * 4 },       // k_bin_count counts into zeroes (k_scan zeroes the counts
-                             { c->sb.tile_cursor, 0, mt * 4 },      // and the cursors again for the fill and the next frame)
-                             { c->d_hiz, 0, hiz_texels * sizeof(float) } }));      // texels over other ranks' regions stay 0 ("hidden")
-    for (auto& v : c->d_vis) zr_launch_fill64(v, ZR_EMPTY_KEY, n, c->stream);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, zr_fill_sync({ { c->d_stats, 0, sizeof(ZrDevStats) }, { c->d_sstats, 0, sizeof(ZrDevStats) },
+                             { c->d_rstats[0], 0, sizeof(ZrDevStats) }, { c->d_rstats[1], 0, sizeof(ZrDevStats) } }));
+    if (int rc = zr_extent_create(c)) return rc;      // everything the extent sizes
     // The runtime backs an event with a signal on its FIRST record and grows that pool in batches, which blocks the host for
     // milliseconds at unpredictable frames of a short run: record every event once now.
     for (auto& fr : c->timed) for (auto& e : fr.ev) HIPCHK(c, hipEventRecord(e, c->stream));

@@ -170,8 +170,12 @@ struct FrameCopy {
 // first, and what later calls add for good), then one owner per group that is re-made or dropped as a whole (work pools, draw tables,
 // ids, skydome, background, cubemap, shadow tiles; the scene's in its meshes and objects; each staging slot).  `own` is declared first,
 // so zr_destroy's `delete` releases it last, after every other owner - and its streams last of all.
+// `ext` owns what is sized by the frame's extent (W, H, a tile count) - what make_extent_state makes (zr_resize.cpp: the GBuffer copies,
+// the key buffers, d_color, the Hi-Z pyramid, the tile tables, d_tiles, the shadow bins' per-tile arrays) and what later calls make at
+// first use (winner planes, the skydome's key plane, the light-keep plane and its records, d_scaled, ids.obj, the highlight's plane and
+// frame).  zr_resize builds a new set beside it and swaps the two.  `pool_tiles` owns the work pools' per-tile parts (make_pool_tiles).
 struct zr_ctx {
-    ZrOwn own;
+    ZrOwn own, ext, pool_tiles;
     zr_config cfg;
     int device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
@@ -219,6 +223,9 @@ struct zr_ctx {
     int smap = 0; uint64_t shadow_draws = 0, cam_draws = 0;
 
     XkUniformBufferMVP cam, shadow; XkView view; bool frame_valid = false;
+    // What of the last zr_update_uniforms depends on the extent - the camera's projection - as it was asked for (valid: no zr_set_frame
+    // since): zr_resize evaluates it again for the new extent (zr_uniforms_reproject).
+    struct Lens { bool valid = false; float fov = 0, zn = 0, zf = 0; } lens;
     uint32_t debug_view = 0;
     uint32_t shading = 0;                           // ZR_SHADING_*: which scene pipeline shades the frame (zr_set_shading)
 
@@ -237,8 +244,9 @@ struct zr_ctx {
     uint32_t *d_sowned_rank = nullptr, *d_stile_map = nullptr; ZrOwn stile_mem;
     uint32_t* d_tiles_ext = nullptr;     // caller-owned packed tile buffer for the next frames (zr_set_tiles_buffer), or null
 
-    // The work pools, sized for work_capacity meshlet-instances by make_work_pools: sc, sb.bins, sb.chunk_tab, tb, d_pxrect, d_zmin,
-    // d_visflag, d_spxrect, d_szmin, d_sflag
+    // The work pools, sized for work_capacity meshlet-instances by make_work_pools: sc, sb.bins, tb, d_pxrect, d_zmin, d_visflag,
+    // d_spxrect, d_szmin, d_sflag - and through `pool_tiles` their per-tile parts: sb.chunk_tab, tb.tile_base / tile_cap / cursor /
+    // r2_count / unit_tab
     ZrOwn pools;
     // the cull's output, one set per geometry pass (0 shadow, 1 camera) so that the two pipelines can run on two streams
     struct CullList { uint32_t *rects = nullptr, *work = nullptr; } sc[2];
@@ -338,13 +346,13 @@ struct zr_ctx {
             zr_frame_delta_packed* h_header = nullptr;
         } codec;
     } delta;
-    // Delivering a scaled frame (zr_scale_host.cpp): where zr_read_color_scaled's kernel writes, made at its first use through `own`
+    // Delivering a scaled frame (zr_scale_host.cpp): where zr_read_color_scaled's kernel writes, made at its first use through `ext`
     // for scale 2, the largest output (scale 1 is read from the frame itself)
     uint32_t* d_scaled = nullptr;
     // Highlighting a selection (zr_highlight_host.cpp, zr_highlight.hip).  set: a byte per slot, host state, cleared when scene_gen moves
     // (set_gen: the scene it was sized for); dirty: the device bitset `bits` (a bit per slot; bits_mem, re-made when the slot count
     // outgrows bits_words) is older than it - the next highlighted delivery stages it on the render stream first, so deliveries in
-    // flight keep the set they were enqueued with.  plane (ceil(W / 64) * H words) and frame (W * H) are made at first use through `own`.
+    // flight keep the set they were enqueued with.  plane (ceil(W / 64) * H words) and frame (W * H) are made at first use through `ext`.
     // delta: zr_set_frame_delta_highlight - the deliveries of changes deliver the highlighted frame.
     struct Highlight {
         std::vector<uint8_t> set; uint64_t set_gen = ~0ull; bool dirty = true, delta = false;
@@ -356,7 +364,7 @@ struct zr_ctx {
     ZrOwn cube_mem; CubeDesc cube = {}; uint32_t cube_dim = 0, cube_levels = 0;
     uint64_t cube_gen = 0;               // of the cubemap's contents: bumped whenever they are replaced (zr_set_cubemap, which a world's override goes through)
     // The lighting pass's plane of standing terms (zr_lighting_host.cpp; ZrFramePlan::light_keep): 32 bytes per pixel, made at the first
-    // fill through `own` (alloc_failed: it could not be, and the context never keeps).  ONE plane: every lighting pass of the context is
+    // fill through `ext` (alloc_failed: it could not be, and the context never keeps at this extent).  ONE plane: every lighting pass of the context is
     // enqueued on the host's stream, in frame order, so a fill is through before the next frame reads, and a read before the next fill.
     // now / key: the standing uniforms of the frame being enqueued / of the fill (ZrFrameFacts::light_uniforms_same).  last, count[]:
     // what the lighting pass enqueued last did with the plane (ZR_LIGHT_PLANE_*), and how often each happened (zr_get_light_keep).
@@ -406,11 +414,12 @@ struct zr_ctx {
 
 // What the deliveries of changes compare, list and size their buffers for: the frame at the delta scale (zr_ctx::Delta::scale), in tiles
 struct ZrDeltaExtent { uint32_t W, H, tiles_x, n_tiles; };
-static inline ZrDeltaExtent zr_delta_extent(const zr_ctx* c)
+static inline ZrDeltaExtent zr_delta_extent_of(uint32_t fw, uint32_t fh, uint32_t s)
 {
-    const uint32_t s = c->delta.scale, W = (c->W + s - 1u) / s, H = (c->H + s - 1u) / s, tx = (W + ZR_TILE - 1u) / ZR_TILE;
+    const uint32_t W = (fw + s - 1u) / s, H = (fh + s - 1u) / s, tx = (W + ZR_TILE - 1u) / ZR_TILE;
     return { W, H, tx, tx * ((H + ZR_TILE - 1u) / ZR_TILE) };
 }
+static inline ZrDeltaExtent zr_delta_extent(const zr_ctx* c) { return zr_delta_extent_of(c->W, c->H, c->delta.scale); }
 int zr_fail(zr_ctx* c, int code, const std::string& msg);      // records the message (never throws), returns code
 // ZR_OK at stage 0, else the refusal "<what> between the stages of a frame" (hint: "... (finish it with zr_render_lighting first)")
 int zr_stage_idle(zr_ctx* c, const char* what, bool hint = true);
@@ -473,6 +482,23 @@ template <typename F> static inline int zr_guard(zr_ctx* c, F&& body) noexcept
 }
 // zr_context.cpp
 hipError_t zr_sync_all(zr_ctx* c);     // every stream the library enqueues on
+// zr_resize.cpp: everything of the context that is sized by the extent, made for W x H beside what the context has (which stays as it is
+// and in use) and, by ZrExtentState::commit, put in its place.  zr_create makes the first set the same way.
+int zr_extent_create(zr_ctx* c);
+// zr_scene.cpp: the work pools' per-tile parts for n_tiles screen tiles, made through `into` and zeroed; *T and *chunk_tab / *chunk_capacity
+// get the new pointers and sizes (T: a copy of c->tb; the rest of it stays).  zr_pool_plan_reset: the pools' few words of plan state zeroed.
+int zr_make_pool_tiles(zr_ctx* c, ZrOwn& into, uint32_t n_tiles, ZrTriBins* T, uint4** chunk_tab, uint32_t* chunk_capacity);
+hipError_t zr_pool_plan_reset(zr_ctx* c);
+// zr_delta_host.cpp: the buffers of the deliveries of changes for a W x H frame at the context's delta scale, made through the two owners
+struct ZrDeltaBuffers {
+    ZrOwn mem, codec_mem;
+    uint32_t *delivered = nullptr, *list = nullptr, *header = nullptr, *scaled = nullptr; uint8_t *packed = nullptr, *flags = nullptr;
+    zr_frame_delta* h_header = nullptr; zr_ctx::Delta::Codec codec;
+};
+int zr_delta_make(zr_ctx* c, uint32_t W, uint32_t H, bool codec, ZrDeltaBuffers* out);
+void zr_delta_commit(zr_ctx* c, ZrDeltaBuffers& B);      // B's buffers become the context's (the old ones are released): full and serial stay
+// zr_frame_host.cpp: the camera's projection, ViewProjSpace and ViewportInfo of the last zr_update_uniforms for the extent as it is now
+void zr_uniforms_reproject(zr_ctx* c);
 // Tile ownership (zr_tile_owner) of a grid of tiles among `world` ranks: the tiles `rank` owns, in increasing index = its slots in the
 // packed buffer; map: tile -> owner * slots_per_rank + slot (k_untile); slots_per_rank: the most tiles any rank owns.
 struct ZrTilePartition { std::vector<uint32_t> owned, map; uint32_t slots_per_rank = 0; };

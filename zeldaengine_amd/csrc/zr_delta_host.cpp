@@ -17,9 +17,8 @@ static_assert(sizeof(zr_frame_delta_packed) == 32 && kZrCodecTile == ZR_TILE, "t
 
 // What the packed forms need beyond the raw forms' buffers, made into `mem`: the lengths (16 bits per tile, in whole 16-byte words, the
 // padding 0), and the host form's header, offsets and stream with its pinned landing place
-static int delta_make_packed(zr_ctx* c, ZrOwn& mem, zr_ctx::Delta::Codec& P)
+static int delta_make_packed(zr_ctx* c, const ZrDeltaExtent& E, ZrOwn& mem, zr_ctx::Delta::Codec& P)
 {
-    const ZrDeltaExtent E = zr_delta_extent(c);
     if ((uint64_t)E.n_tiles * kZrCodecRawBytes > 0xFFFFFFFFull)
         return zr_fail(c, ZR_ERR_UNSUPPORTED, "zr_set_frame_delta: the frame's packed stream would not fit 32-bit offsets");
     const size_t len_words = ((size_t)E.n_tiles + 7u) / 8u * 8u;
@@ -27,6 +26,28 @@ static int delta_make_packed(zr_ctx* c, ZrOwn& mem, zr_ctx::Delta::Codec& P)
     HIPCHK(c, mem.alloc(&P.stream, (size_t)E.n_tiles * kZrCodecRawBytes)); HIPCHK(c, mem.host(&P.h_header, 1));
     HIPCHK(c, zr_fill_sync({ { P.lens, 0, len_words * 2 }, { P.header, 0, 32 } }));
     return ZR_OK;
+}
+
+// Everything is made for the delivered extent: the frame's own, or at a delta scale above 1 the scaled frame's, which every delivery
+// then filters into `scaled` first (zr_scale.hip).  zr_set_frame_delta makes it for the context's extent, zr_resize for the new one.
+int zr_delta_make(zr_ctx* c, uint32_t W, uint32_t H, bool codec, ZrDeltaBuffers* out)
+{
+    ZrDeltaBuffers& B = *out;
+    const ZrDeltaExtent E = zr_delta_extent_of(W, H, c->delta.scale);
+    const size_t n = (size_t)E.W * E.H, flag_bytes = ((size_t)E.n_tiles + 7u) / 8u * 8u;      // (k_delta_pack reads the flags eight at a time)
+    if (c->delta.scale > 1u) HIPCHK(c, B.mem.alloc(&B.scaled, n));
+    HIPCHK(c, B.mem.alloc(&B.delivered, n)); HIPCHK(c, B.mem.alloc(&B.packed, (size_t)E.n_tiles * kTileBytes)); HIPCHK(c, B.mem.alloc(&B.list, E.n_tiles));
+    HIPCHK(c, B.mem.alloc(&B.header, 4)); HIPCHK(c, B.mem.alloc(&B.flags, flag_bytes)); HIPCHK(c, B.mem.host(&B.h_header, 1));
+    HIPCHK(c, zr_fill_sync({ { B.delivered, 0, n * 4 }, { B.flags, 0, flag_bytes }, { B.header, 0, 16 } }));
+    if (codec) { if (int rc = delta_make_packed(c, E, B.codec_mem, B.codec)) return rc; B.codec.on = true; }
+    return ZR_OK;
+}
+void zr_delta_commit(zr_ctx* c, ZrDeltaBuffers& B)
+{
+    zr_ctx::Delta& D = c->delta;
+    D.codec_mem = std::move(B.codec_mem); D.codec = B.codec;
+    D.mem = std::move(B.mem);
+    D.delivered = B.delivered; D.scaled = B.scaled; D.packed = B.packed; D.list = B.list; D.header = B.header; D.flags = B.flags; D.h_header = B.h_header;
 }
 
 extern "C" int zr_set_frame_delta(zr_ctx* c, int enable)
@@ -49,28 +70,15 @@ extern "C" int zr_set_frame_delta(zr_ctx* c, int enable)
         if (D.on) {                              // between the raw and the packed forms: the delivered copy, full and serial stand
             HIPCHK(c, zr_sync_all(c));
             ZrOwn pmem; zr_ctx::Delta::Codec P;
-            if (codec) { if (int rc = delta_make_packed(c, pmem, P)) return rc; P.on = true; }
+            if (codec) { if (int rc = delta_make_packed(c, zr_delta_extent(c), pmem, P)) return rc; P.on = true; }
             D.codec_mem = std::move(pmem); D.codec = P;
             return ZR_OK;
         }
         if (c->cfg.tile_world > 1 || (c->cfg.flags & ZR_FLAG_PACKED_TILES))
             return zr_fail(c, ZR_ERR_UNSUPPORTED, "zr_set_frame_delta: this context's lighting pass writes packed tiles, not the frame (tile_world > 1, ZR_FLAG_PACKED_TILES)");
-        // everything is made for the delivered extent: the frame's own, or at a delta scale above 1 the scaled frame's, which every
-        // delivery then filters into `scaled` first (zr_scale.hip)
-        const ZrDeltaExtent E = zr_delta_extent(c);
-        const size_t n = (size_t)E.W * E.H, flag_bytes = ((size_t)E.n_tiles + 7u) / 8u * 8u;      // (k_delta_pack reads the flags eight at a time)
-        ZrOwn mem;
-        uint32_t *delivered = nullptr, *list = nullptr, *header = nullptr, *scaled = nullptr; uint8_t *packed = nullptr, *flags = nullptr;
-        zr_frame_delta* h_header = nullptr;
-        if (D.scale > 1u) HIPCHK(c, mem.alloc(&scaled, n));
-        HIPCHK(c, mem.alloc(&delivered, n)); HIPCHK(c, mem.alloc(&packed, (size_t)E.n_tiles * kTileBytes)); HIPCHK(c, mem.alloc(&list, E.n_tiles));
-        HIPCHK(c, mem.alloc(&header, 4)); HIPCHK(c, mem.alloc(&flags, flag_bytes)); HIPCHK(c, mem.host(&h_header, 1));
-        HIPCHK(c, zr_fill_sync({ { delivered, 0, n * 4 }, { flags, 0, flag_bytes }, { header, 0, 16 } }));
-        ZrOwn pmem; zr_ctx::Delta::Codec P;
-        if (codec) { if (int rc = delta_make_packed(c, pmem, P)) return rc; P.on = true; }
-        D.codec_mem = std::move(pmem); D.codec = P;
-        D.mem = std::move(mem);
-        D.delivered = delivered; D.scaled = scaled; D.packed = packed; D.list = list; D.header = header; D.flags = flags; D.h_header = h_header;
+        ZrDeltaBuffers B;
+        if (int rc = zr_delta_make(c, c->W, c->H, codec, &B)) return rc;
+        zr_delta_commit(c, B);
         D.on = true; D.full = true; D.serial = 0;
         return ZR_OK;
     });

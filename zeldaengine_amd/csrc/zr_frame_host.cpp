@@ -41,6 +41,20 @@ static void rotate_z(float angle, float* m)
     m[0] = cs; m[1] = sn; m[4] = -sn; m[5] = cs; m[10] = cs + (1.0f - cs); m[15] = 1.0f;
 }
 
+// What of the uniforms depends on the extent, from the lens of the last zr_update_uniforms (zr_ctx::lens) and the camera's View as that
+// call left it: the camera's projection, ViewProjSpace, ViewportInfo.  zr_update_uniforms ends with it, zr_resize calls it again.
+void zr_uniforms_reproject(zr_ctx* c)
+{
+    XkView* V = &c->view;
+    float cproj[16];
+    perspective_rh_zo(radiansf(c->lens.fov), (float)c->W / (float)c->H, c->lens.zn, c->lens.zf, cproj);
+    memcpy(c->cam.Proj, cproj, 64);
+    c->cam.Proj[5] *= -1.0f;
+    zr_mat4_mul(cproj, c->cam.View, V->ViewProjSpace);
+    V->ViewportInfo[0] = (float)c->W; V->ViewportInfo[1] = (float)c->H; V->ViewportInfo[2] = 0.0f; V->ViewportInfo[3] = 0.0f;
+    c->view_dirty = true;
+}
+
 // UpdateWorld (ZE:4294-4308) + UpdateUniformBuffer (ZE:4585-4664) in game mode (editor bars = 0, ZE:4575-4579)
 extern "C" int zr_update_uniforms(zr_ctx* c, const zr_camera* cam, const XkLight* dir, uint32_t n_dir, const XkLight* point,
                                   uint32_t n_point, const XkLight* spot, uint32_t n_spot, float roll_stage, float roll_light, float time)
@@ -64,20 +78,18 @@ extern "C" int zr_update_uniforms(zr_ctx* c, const zr_camera* cam, const XkLight
         const zf3 look = zr3(cam->Lookat[0], cam->Lookat[1], cam->Lookat[2]);
         const zf3 up = zr3(0.0f, 0.0f, 1.0f);
         const zf3 lightPos = zr3(V->DirectionalLights[0].Position[0], V->DirectionalLights[0].Position[1], V->DirectionalLights[0].Position[2]);
-        float l2w[16], sview[16], sproj[16], cview[16], cproj[16];
+        float l2w[16], sview[16], sproj[16], cview[16];
         rotate_z(roll_stage, l2w);
         look_at_rh(lightPos, zr3(0.0f, 0.0f, 0.0f), up, sview);
         perspective_rh_zo(radiansf(cam->FOV), 1.0f, cam->zNear, cam->zFar, sproj);
         sproj[5] *= -1.0f;
         look_at_rh(pos, look, up, cview);
-        perspective_rh_zo(radiansf(cam->FOV), (float)c->W / (float)c->H, cam->zNear, cam->zFar, cproj);
-        memcpy(c->cam.Model, l2w, 64); memcpy(c->cam.View, cview, 64); memcpy(c->cam.Proj, cproj, 64);
-        c->cam.Proj[5] *= -1.0f;
-        zr_mat4_mul(cproj, cview, V->ViewProjSpace);
+        memcpy(c->cam.Model, l2w, 64); memcpy(c->cam.View, cview, 64);
+        c->lens.valid = true; c->lens.fov = cam->FOV; c->lens.zn = cam->zNear; c->lens.zf = cam->zFar;
+        zr_uniforms_reproject(c);       // cam.Proj, ViewProjSpace, ViewportInfo
         zr_mat4_mul(sproj, sview, V->ShadowmapSpace);
         memcpy(V->LocalToWorld, l2w, 64);
         V->CameraInfo[0] = pos.x; V->CameraInfo[1] = pos.y; V->CameraInfo[2] = pos.z; V->CameraInfo[3] = cam->FOV;
-        V->ViewportInfo[0] = (float)c->W; V->ViewportInfo[1] = (float)c->H; V->ViewportInfo[2] = 0.0f; V->ViewportInfo[3] = 0.0f;
         const uint32_t N = n_point;
         for (uint32_t i = 0; i < N; ++i) {           // point lights ride a spiral, JSON positions are overwritten (ZE:4637-4646)
             const float deg = ((float)i / (float)N) * 360.0f - roll_light * 100.0f;
@@ -103,7 +115,7 @@ extern "C" int zr_set_frame(zr_ctx* c, const XkUniformBufferMVP* cam, const XkUn
                   v->LightsCount[1] <= XK_MAX_POINT_LIGHTS_NUM);
         if (int rc = zr_stage_idle(c, "zr_set_frame")) return rc;
         c->cam = *cam; c->shadow = *sh; c->view = *v; c->view_dirty = true;
-        c->frame_valid = true;
+        c->frame_valid = true; c->lens.valid = false;      // (the caller's own: a resize leaves them as given)
         return ZR_OK;
     });
 }
@@ -126,7 +138,7 @@ int set_winner_planes(zr_ctx* c, bool forward, bool id_capture, const char* what
     const size_t n = (size_t)c->W * c->H;
     for (FrameCopy& F : c->fc) {
         if ((forward || id_capture) && !F.prim_plane) {
-            if (c->own.alloc(&F.prim_plane, n) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, std::string(what) + ": out of device memory");
+            if (c->ext.alloc(&F.prim_plane, n) != hipSuccess) return zr_fail(c, ZR_ERR_DEVICE, std::string(what) + ": out of device memory");
             HIPCHK(c, zr_fill_sync({ { F.prim_plane, 0xFF, n * 4 } }));
         }
         F.G.prim = (forward || id_capture) ? F.prim_plane : nullptr;

@@ -135,8 +135,8 @@ static int hl_upload(zr_ctx* c)
 int zr_highlight_enqueue(zr_ctx* c, uint32_t* dst, const uint32_t** out)
 {
     zr_ctx::Highlight& L = c->hl;
-    if (!L.plane) HIPCHK(c, c->own.alloc(&L.plane, (size_t)zr_hl_row_words(c->W) * c->H));
-    if (!dst && !L.frame) HIPCHK(c, c->own.alloc(&L.frame, (size_t)c->W * c->H));
+    if (!L.plane) HIPCHK(c, c->ext.alloc(&L.plane, (size_t)zr_hl_row_words(c->W) * c->H));
+    if (!dst && !L.frame) HIPCHK(c, c->ext.alloc(&L.frame, (size_t)c->W * c->H));
     if (int rc = hl_upload(c)) return rc;
     uint32_t* to = dst ? dst : L.frame;
     const ZrIdsArgs A = ids_args(c, 0, 0, c->W, c->H);
@@ -173,7 +173,7 @@ extern "C" int zr_read_color_highlighted(zr_ctx* c, uint32_t scale, uint8_t* dst
         const uint32_t* src = nullptr;
         if (scale == 1u) rc = zr_highlight_enqueue(c, nullptr, &src);
         else {
-            if (!c->d_scaled) HIPCHK(c, c->own.alloc(&c->d_scaled, (size_t)((c->W + 1u) / 2u) * ((c->H + 1u) / 2u)));
+            if (!c->d_scaled) HIPCHK(c, c->ext.alloc(&c->d_scaled, (size_t)((c->W + 1u) / 2u) * ((c->H + 1u) / 2u)));
             rc = hl_deliver(c, scale, c->d_scaled);
             src = c->d_scaled;
         }

@@ -51,18 +51,18 @@ void zr_light_facts(zr_ctx* c, ZrFrameFacts* f)
     f->light_by_arg = zr_lighting_rest_available() && np >= 0 && np <= ZR_REST_ARG_LIGHTS && f->light_empty_px && c->lk.rest != nullptr && c->debug_view != 9u;
 }
 
-// The plane is made when the first frame is planned to fill it: 32 B x W x H (66 MB at 1080p, 265 MB at 2160p), through the context's
-// owner.  No room: the context simply never keeps - that is no error.  With it, in an allocation of their own, the slot and the records
+// The plane is made when the first frame is planned to fill it: 32 B x W x H (66 MB at 1080p, 265 MB at 2160p), through the extent's
+// owner (zr_ctx::ext: a resize releases it, and the first resting frame at the new extent makes its successor).  No room: the context simply never keeps - that is no error.  With it, in an allocation of their own, the slot and the records
 // of the one-launch resting frame (ZrRestRecord: 512 B per owned tile); no room for those: the context keeps as a context without them.
 bool zr_light_plane_make(zr_ctx* c)
 {
     if (c->lk.plane) return true;
-    if (!c->lk.alloc_failed && c->own.alloc(&c->lk.plane, 2 * (size_t)c->W * c->H) != hipSuccess) {
+    if (!c->lk.alloc_failed && c->ext.alloc(&c->lk.plane, 2 * (size_t)c->W * c->H) != hipSuccess) {
         (void)hipGetLastError();      // (the refusal is not the frame's error)
         c->lk.plane = nullptr; c->lk.alloc_failed = true;
     }
     if (c->lk.plane && !c->lk.rest && zr_lighting_rest_available() &&
-        c->own.alloc(&c->lk.rest, ZR_REST_SLOT + (size_t)c->n_owned * ZR_REST_RECORDS_PER_TILE * (sizeof(ZrRestRecord) / sizeof(float4))) != hipSuccess) {
+        c->ext.alloc(&c->lk.rest, ZR_REST_SLOT + (size_t)c->n_owned * ZR_REST_RECORDS_PER_TILE * (sizeof(ZrRestRecord) / sizeof(float4))) != hipSuccess) {
         (void)hipGetLastError();
         c->lk.rest = nullptr;
     }

@@ -334,7 +334,7 @@ extern "C" int zr_read_ids(zr_ctx* c, int kind, void* dst, size_t bytes)
         if (rc) return rc;
         const ZrIdsArgs A0 = ids_args(c, 0, 0, c->W, c->H);
         if (kind == ZR_IDS_PRIMITIVE) { HIPCHK(c, hipMemcpy(dst, A0.prim, bytes, hipMemcpyDeviceToHost)); return ZR_OK; }
-        if (!c->ids.obj) HIPCHK(c, c->own.alloc(&c->ids.obj, (size_t)c->W * c->H));
+        if (!c->ids.obj) HIPCHK(c, c->ext.alloc(&c->ids.obj, (size_t)c->W * c->H));
         ZrIdsArgs A = A0; A.obj_plane = c->ids.obj;
         zr_launch_id_census(A, ZR_IDS_OBJECTS, c->stream);
         HIPCHK(c, hipGetLastError());

@@ -47,7 +47,7 @@ extern "C" int zr_read_color_scaled(zr_ctx* c, uint32_t scale, uint8_t* dst, siz
         if (rc == ZR_OK) rc = zr_finish(c);
         if (rc) return rc;
         if (scale == 1u) { HIPCHK(c, hipMemcpy(dst, c->d_color, bytes, hipMemcpyDeviceToHost)); return ZR_OK; }
-        if (!c->d_scaled) HIPCHK(c, c->own.alloc(&c->d_scaled, (size_t)zr_scale_extent(c->W, 2u) * zr_scale_extent(c->H, 2u)));
+        if (!c->d_scaled) HIPCHK(c, c->ext.alloc(&c->d_scaled, (size_t)zr_scale_extent(c->W, 2u) * zr_scale_extent(c->H, 2u)));
         zr_launch_frame_scale(c->d_color, c->d_scaled, c->W, c->H, scale, c->stream);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));

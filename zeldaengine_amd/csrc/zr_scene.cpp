@@ -426,13 +426,38 @@ static int upload_mesh(zr_ctx* c, ZrMesh& m)
     return ZR_OK;
 }
 
+// The work pools' per-tile parts (zr_ctx.h): the shadow pass's work-unit table, the camera pass's per-tile bucket tables, cursors, round-2
+// counts and work-unit table - made through `into`, zeroed, and handed back in *T / *chunk_tab / *chunk_capacity.  The context itself is
+// not touched: make_work_pools and zr_resize put the result in place.
+int zr_make_pool_tiles(zr_ctx* c, ZrOwn& into, uint32_t n_tiles, ZrTriBins* T, uint4** chunk_tab, uint32_t* chunk_capacity)
+{
+    *chunk_capacity = c->bin_capacity / ZR_CHUNK + std::max(n_tiles, c->sn_tiles) + 1u;
+    HIPCHK(c, into.alloc(chunk_tab, *chunk_capacity));
+    T->n_tiles = n_tiles;
+    T->unit_cap = T->bucket_max / (ZR_TCHUNK * ZR_TBATCHES) + 2u * n_tiles + 1u;
+    HIPCHK(c, into.alloc(&T->tile_base, n_tiles)); HIPCHK(c, into.alloc(&T->tile_cap, n_tiles));
+    HIPCHK(c, into.alloc(&T->cursor, (size_t)2 * n_tiles * ZR_TSTRIDE));
+    HIPCHK(c, into.alloc(&T->unit_tab, T->unit_cap)); HIPCHK(c, into.alloc(&T->r2_count, n_tiles));
+    // (no plan yet: every bucket is empty - the first frame counts before it draws, see gbuffer_pass.  A fill that landed after the next
+    // frame's k_plan would wipe the plan - every record then overflows into sections of capacity 0)
+    HIPCHK(c, zr_fill_sync({ { T->tile_base, 0, (size_t)n_tiles * 4 }, { T->tile_cap, 0, (size_t)n_tiles * 4 },
+                             { T->cursor, 0, (size_t)2 * n_tiles * ZR_TSTRIDE * 4 }, { T->r2_count, 0, (size_t)n_tiles * 4 } }));
+    return ZR_OK;
+}
+// ... and the few words of plan state that are no tile's: as a scene's first frame finds them
+hipError_t zr_pool_plan_reset(zr_ctx* c)
+{
+    const ZrTriBins& T = c->tb;
+    return zr_fill_sync({ { T.over_cursor, 0, 2 * ZR_OVER_SECTIONS * 4 }, { T.n_units, 0, 4 }, { T.plan, 0, 8 }, { T.r2_stats, 0, ZR_R2_WORDS * 4 } });
+}
+
 // The work pools for cap_w meshlet-instances: the cull's lists, the shadow pass's bins, the camera pass's triangle records, the occlusion
 // tests' boxes and flags.  A failed allocation returns with work_capacity 0 (and the caller's scene_dirty still set): the next frame
 // tries again instead of launching on freed buffers.
 static int make_work_pools(zr_ctx* c, uint32_t cap_w)
 {
     ZrOwn& P = c->pools;
-    P.release();
+    P.release(); c->pool_tiles.release();
     c->work_capacity = 0; zr_history_forgotten(c, ZR_HIST_PLAN);
     for (auto& o : c->objects) o.work_valid = false;      // (the history lived in the pools: zr_scene_finalize reads it before it comes here)
     for (auto& sc : c->sc) sc = {};
@@ -440,9 +465,8 @@ static int make_work_pools(zr_ctx* c, uint32_t cap_w)
     c->d_pxrect = nullptr; c->d_zmin = nullptr; c->d_visflag[0] = c->d_visflag[1] = nullptr; c->d_spxrect = nullptr; c->d_szmin = nullptr; c->d_sflag = nullptr;
     const uint64_t cap = std::max<uint64_t>(1u << 20, 8ull * cap_w);
     c->bin_capacity = (uint32_t)std::min<uint64_t>(cap, 0x3FFFFFFFull);
-    c->chunk_capacity = c->bin_capacity / ZR_CHUNK + std::max(c->n_tiles, c->sn_tiles) + 1u;
     for (auto& sc : c->sc) { HIPCHK(c, P.alloc(&sc.rects, cap_w)); HIPCHK(c, P.alloc(&sc.work, cap_w)); }
-    HIPCHK(c, P.alloc(&c->sb.bins, c->bin_capacity)); HIPCHK(c, P.alloc(&c->sb.chunk_tab, c->chunk_capacity));
+    HIPCHK(c, P.alloc(&c->sb.bins, c->bin_capacity));
     // triangle-binned camera pass: triangle records (32 B) live in per-tile BUCKETS of two 16-byte planes, laid out every frame by
     // k_plan from the previous frame's per-tile counts; what lies behind the last bucket is the frame's overflow region (what a tile gets
     // beyond its bucket).  Sized from the scene: 16 records per meshlet-instance, at least 32 Mi - 1 GB of 288 reserved, touched as far as a frame
@@ -455,24 +479,17 @@ static int make_work_pools(zr_ctx* c, uint32_t cap_w)
     if (c->limit_record_chunks) n_rec = 256ull * c->limit_record_chunks;      // zr_set_limits (a host sizing the planes; the overflow tests)
     if (c->limit_slow_triangles) T.slow_cap = std::max(2u, c->limit_slow_triangles);
     T.n_rec = (uint32_t)n_rec; T.bucket_max = (uint32_t)(n_rec - n_rec / 8u);
-    T.n_tiles = c->n_tiles;
-    T.unit_cap = T.bucket_max / (ZR_TCHUNK * ZR_TBATCHES) + 2u * c->n_tiles + 1u;
+    if (int rc = zr_make_pool_tiles(c, c->pool_tiles, c->n_tiles, &T, &c->sb.chunk_tab, &c->chunk_capacity)) return rc;
     HIPCHK(c, P.alloc(&T.sel, cap_w)); HIPCHK(c, P.alloc(&T.recA, (size_t)n_rec)); HIPCHK(c, P.alloc(&T.recB, (size_t)n_rec));
     HIPCHK(c, P.alloc(&T.over_tile, (size_t)n_rec)); HIPCHK(c, P.alloc(&T.plan, 2));
-    HIPCHK(c, P.alloc(&T.tile_base, c->n_tiles)); HIPCHK(c, P.alloc(&T.tile_cap, c->n_tiles));
-    HIPCHK(c, P.alloc(&T.cursor, (size_t)2 * c->n_tiles * ZR_TSTRIDE));
     HIPCHK(c, P.alloc(&T.over_cursor, 2 * ZR_OVER_SECTIONS)); HIPCHK(c, P.alloc(&T.n_units, 1));
-    HIPCHK(c, P.alloc(&T.unit_tab, T.unit_cap)); HIPCHK(c, P.alloc(&T.wave_culled, T.n_waves)); HIPCHK(c, P.alloc(&T.slow, 4ull * T.slow_cap));
-    HIPCHK(c, P.alloc(&T.r2_count, c->n_tiles)); HIPCHK(c, P.alloc(&T.r2_stats, ZR_R2_WORDS));
+    HIPCHK(c, P.alloc(&T.wave_culled, T.n_waves)); HIPCHK(c, P.alloc(&T.slow, 4ull * T.slow_cap));
+    HIPCHK(c, P.alloc(&T.r2_stats, ZR_R2_WORDS));
     HIPCHK(c, P.alloc(&c->d_pxrect, cap_w)); HIPCHK(c, P.alloc(&c->d_zmin, cap_w));
     HIPCHK(c, P.alloc(&c->d_visflag[0], cap_w)); HIPCHK(c, P.alloc(&c->d_visflag[1], cap_w));
     HIPCHK(c, P.alloc(&c->d_spxrect, cap_w)); HIPCHK(c, P.alloc(&c->d_szmin, cap_w)); HIPCHK(c, P.alloc(&c->d_sflag, cap_w));
-    // (no plan yet: every bucket is empty - the first frame counts before it draws, see gbuffer_pass.  A fill that landed after the next
-    // frame's k_plan would wipe the plan - every record then overflows into sections of capacity 0)
-    HIPCHK(c, zr_fill_sync({ { T.tile_base, 0, (size_t)c->n_tiles * 4 }, { T.tile_cap, 0, (size_t)c->n_tiles * 4 },
-                             { T.cursor, 0, (size_t)2 * c->n_tiles * ZR_TSTRIDE * 4 }, { T.over_cursor, 0, 2 * ZR_OVER_SECTIONS * 4 },
-                             { T.n_units, 0, 4 }, { T.plan, 0, 8 }, { T.r2_count, 0, (size_t)c->n_tiles * 4 }, { T.r2_stats, 0, ZR_R2_WORDS * 4 },
-                             { c->d_visflag[0], 0, cap_w }, { c->d_visflag[1], 0, cap_w } }));      // (no frame's stamp is 0)
+    HIPCHK(c, zr_pool_plan_reset(c));
+    HIPCHK(c, zr_fill_sync({ { c->d_visflag[0], 0, cap_w }, { c->d_visflag[1], 0, cap_w } }));      // (no frame's stamp is 0)
     c->work_capacity = cap_w;              // every buffer is there
     return ZR_OK;
 }
@@ -530,7 +547,7 @@ int zr_scene_finalize(zr_ctx* c)
     c->n_objs = (uint32_t)tab.size(); c->n_work = (uint32_t)scene_work; c->n_inst_total = (uint32_t)scene_inst;
     { int rc = zr_update_table(c); if (rc) return rc; }      // (objects with updated instances: the parity-1 table, n_objs records)
     c->sky_object = sky ? (uint32_t)tab.size() - 1u : 0u;
-    if (sky && !c->d_sky_keys) HIPCHK(c, c->own.alloc(&c->d_sky_keys, (size_t)c->W * c->H));
+    if (sky && !c->d_sky_keys) HIPCHK(c, c->ext.alloc(&c->d_sky_keys, (size_t)c->W * c->H));
     // A world update asked for the history to be carried (zr_ctx::history_remap): per kept draw the old work range and the new base; where
     // the instance count changed, the common prefix of instances.  The old planes are copied out first: ranges overlap when a base shifts
     // by less than a draw's length, in either direction, and make_work_pools releases the planes themselves.

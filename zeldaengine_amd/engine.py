@@ -63,6 +63,7 @@ def lib():
         **abi.FRAME_DELTA_SIGNATURES,
         **abi.FRAME_SCALE_SIGNATURES,
         **abi.HIGHLIGHT_SIGNATURES,
+        **abi.EXTENT_SIGNATURES,
         "zr_set_cubemap": [vp, vp, u32],
         "zr_set_skydome": [vp, vp, u32, vp, u32, vp],
         "zr_set_background": [vp, vp],
@@ -348,6 +349,18 @@ class Renderer:
 
     def __exit__(self, *a):
         self.close()
+
+    def resize(self, width, height):
+        """zr_resize: a new extent, the same scene - nothing is submitted again, and every later frame is a new context's at that extent.
+        Device pointers the context handed out (color_device_ptr, tiles_device_buffer) are void afterwards."""
+        self._chk(self.L.zr_resize(self.h, width, height))
+        self.W, self.H = self.extent()
+
+    def extent(self):
+        """zr_get_extent: (width, height) as the context has them now"""
+        w, h = C.c_uint32(), C.c_uint32()
+        self._chk(self.L.zr_get_extent(self.h, C.byref(w), C.byref(h)))
+        return w.value, h.value
 
     def set_stream(self, hip_stream):
         self._chk(self.L.zr_set_stream(self.h, C.c_void_p(hip_stream)))
