@@ -72,7 +72,8 @@ def test_every_status_entry_point_is_defined_once_behind_the_guard():
 
 def test_host_sources_are_split_by_concern_and_share_their_idioms():
     """The host is one translation unit per concern, none longer than 752 lines (zr_host.cpp is gone), and the idioms every update path
-    used to spell out exist once: the refusal between the stages of a frame (zr_stage_idle) and the host forms' lane (zr_update_lane)."""
+    used to spell out exist once: the refusal between the stages of a frame (zr_stage_idle) and the host forms' lane (zr_update_lane);
+    so do the steps of delivering a frame."""
     csrc = os.path.join(ROOT, "zeldaengine_amd", "csrc")
     text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".cpp", ".h"))}
     assert sum(t.count("between the stages of a frame (finish it") for t in text.values()) == 1
@@ -80,6 +81,16 @@ def test_host_sources_are_split_by_concern_and_share_their_idioms():
     assert not os.path.exists(os.path.join(csrc, "zr_host.cpp"))
     long = {f: t.count("\n") for f, t in text.items() if f.endswith(".cpp") and t.count("\n") > 752}
     assert not long, long
+    # delivering a frame is one path (zr_deliver_host.cpp): one readiness check, one source stage that alone launches the highlight and
+    # the filter, one note of a winner-plane reader, one scale_ok - in no more lines than the three files it came from had (246 + 91 + 205)
+    cpp = {f: t for f, t in text.items() if f.endswith(".cpp")}
+    assert sum(t.count("writes packed tiles, not the frame") for t in text.values()) == 1
+    assert sum(t.count("ids_wait = true") for t in text.values()) == 1
+    for launcher in ("zr_launch_frame_scale(", "zr_launch_highlight_mask(", "zr_launch_highlight_apply("):
+        assert sum(t.count(launcher) for t in cpp.values()) == 1, launcher
+    assert sum(t.count("scale_ok(uint32_t") for t in text.values()) == 1
+    assert not {"zr_delta_host.cpp", "zr_scale_host.cpp"} & set(text)
+    assert text["zr_deliver_host.cpp"].count("\n") + text["zr_highlight_host.cpp"].count("\n") <= 542
 
 
 def test_kernel_files_share_their_steps():

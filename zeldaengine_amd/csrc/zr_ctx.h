@@ -16,6 +16,7 @@
 #include "zr_frame_plan.h"
 #include "zr_ids.h"
 #include "zr_meshlet.h"
+#include "zr_scale.h"
 #include "zr_types.h"
 #include "zr_world_doc.h"
 
@@ -164,6 +165,21 @@ struct FrameCopy {
     uint64_t g_gen = 0;                  // the run of equal inputs (ZrFramePlan::g_gen) G was last resolved in (0: never)
     // a census enqueued against this copy (zr_instance_coverage_async): the frame that writes it next waits for it
     hipEvent_t ev_ids = nullptr; bool ids_wait = false;
+};
+
+// The buffers of the deliveries of changes, through owners of their own.  delivered = what the client holds; flags = a byte per tile,
+// rewritten by every delivery (nothing to clear on the stream); packed / list / header = the host form's device buffers, h_header its
+// pinned landing place; scaled = the filtered frame (delta scale above 1).  codec: what ZR_FRAME_DELTA_PACKED adds, through codec_mem -
+// lens = a listed tile's record length, rewritten by every packed delivery; header / offsets / stream / h_header = the packed host
+// form's buffers (it shares `list`).  Going between the raw and the packed forms makes or releases these alone.
+struct ZrDeltaBuffers {
+    ZrOwn mem, codec_mem;
+    uint32_t *delivered = nullptr, *list = nullptr, *header = nullptr, *scaled = nullptr; uint8_t *packed = nullptr, *flags = nullptr;
+    zr_frame_delta* h_header = nullptr;
+    struct Codec {
+        bool on = false; uint16_t* lens = nullptr; uint32_t *header = nullptr, *offsets = nullptr; uint8_t* stream = nullptr;
+        zr_frame_delta_packed* h_header = nullptr;
+    } codec;
 };
 
 // Every HIP resource of the context is made through the owner of its lifetime: `own` (the context: what zr_create makes, its streams
@@ -329,25 +345,13 @@ struct zr_ctx {
         unsigned long long* keys = nullptr; zr_hit* hits = nullptr; uint2* obj = nullptr;
     } ids;
 
-    // Delivering changes (zr_delta_host.cpp, zr_delta.hip): all of it made by zr_set_frame_delta(1) through `mem`, released by
-    // zr_set_frame_delta(0).  delivered = what the client holds; flags = a byte per tile, rewritten by every delivery (nothing to clear on
-    // the stream); packed / list / header = the host form's device buffers, h_header its pinned landing place.  full: the next delivery
-    // lists every tile; serial: deliveries since enable.  codec: what ZR_FRAME_DELTA_PACKED adds, through codec_mem - lens = a listed
-    // tile's record length, rewritten by every packed delivery; header / offsets / stream / h_header = the packed host form's buffers (it
-    // shares `list`).  Going between the raw and the packed forms makes or releases these alone.
-    // scale: zr_set_frame_delta_scale's factor (1: the frame itself), set while delta is off and kept across the switch; above 1 all of
-    // the above is sized for the scaled extent (zr_delta_extent) and `scaled` is the frame every delivery filters first (zr_scale.hip).
-    struct Delta {
-        ZrOwn mem, codec_mem; bool on = false, full = true; uint32_t serial = 0, scale = 1;
-        uint32_t *delivered = nullptr, *list = nullptr, *header = nullptr, *scaled = nullptr; uint8_t *packed = nullptr, *flags = nullptr;
-        zr_frame_delta* h_header = nullptr;
-        struct Codec {
-            bool on = false; uint16_t* lens = nullptr; uint32_t *header = nullptr, *offsets = nullptr; uint8_t* stream = nullptr;
-            zr_frame_delta_packed* h_header = nullptr;
-        } codec;
-    } delta;
-    // Delivering a scaled frame (zr_scale_host.cpp): where zr_read_color_scaled's kernel writes, made at its first use through `ext`
-    // for scale 2, the largest output (scale 1 is read from the frame itself)
+    // Delivering changes (zr_deliver_host.cpp, zr_delta.hip).  b: the buffers (ZrDeltaBuffers), made by zr_set_frame_delta(1), released by
+    // zr_set_frame_delta(0), re-made beside the old ones by zr_resize.  full: the next delivery lists every tile; serial: deliveries since
+    // enable.  scale: zr_set_frame_delta_scale's factor (1: the frame itself), a setting like hl.delta: set while delta is off and kept;
+    // above 1 the buffers are sized for the scaled extent (zr_delta_extent) and b.scaled is the frame every delivery filters first.
+    struct Delta { bool on = false, full = true; uint32_t serial = 0, scale = 1; ZrDeltaBuffers b; } delta;
+    // Delivering a scaled frame (zr_deliver_host.cpp): where the host forms' filter writes, made at its first use through `ext` for
+    // scale 2, the largest output (scale 1 is read from the frame itself)
     uint32_t* d_scaled = nullptr;
     // Highlighting a selection (zr_highlight_host.cpp, zr_highlight.hip).  set: a byte per slot, host state, cleared when scene_gen moves
     // (set_gen: the scene it was sized for); dirty: the device bitset `bits` (a bit per slot; bits_mem, re-made when the slot count
@@ -416,7 +420,7 @@ struct zr_ctx {
 struct ZrDeltaExtent { uint32_t W, H, tiles_x, n_tiles; };
 static inline ZrDeltaExtent zr_delta_extent_of(uint32_t fw, uint32_t fh, uint32_t s)
 {
-    const uint32_t W = (fw + s - 1u) / s, H = (fh + s - 1u) / s, tx = (W + ZR_TILE - 1u) / ZR_TILE;
+    const uint32_t W = zr_scale_extent(fw, s), H = zr_scale_extent(fh, s), tx = (W + ZR_TILE - 1u) / ZR_TILE;
     return { W, H, tx, tx * ((H + ZR_TILE - 1u) / ZR_TILE) };
 }
 static inline ZrDeltaExtent zr_delta_extent(const zr_ctx* c) { return zr_delta_extent_of(c->W, c->H, c->delta.scale); }
@@ -489,14 +493,9 @@ int zr_extent_create(zr_ctx* c);
 // get the new pointers and sizes (T: a copy of c->tb; the rest of it stays).  zr_pool_plan_reset: the pools' few words of plan state zeroed.
 int zr_make_pool_tiles(zr_ctx* c, ZrOwn& into, uint32_t n_tiles, ZrTriBins* T, uint4** chunk_tab, uint32_t* chunk_capacity);
 hipError_t zr_pool_plan_reset(zr_ctx* c);
-// zr_delta_host.cpp: the buffers of the deliveries of changes for a W x H frame at the context's delta scale, made through the two owners
-struct ZrDeltaBuffers {
-    ZrOwn mem, codec_mem;
-    uint32_t *delivered = nullptr, *list = nullptr, *header = nullptr, *scaled = nullptr; uint8_t *packed = nullptr, *flags = nullptr;
-    zr_frame_delta* h_header = nullptr; zr_ctx::Delta::Codec codec;
-};
+// zr_deliver_host.cpp: the buffers of the deliveries of changes for a W x H frame at the context's delta scale; moved into zr_ctx::Delta::b
+// they become the context's (the old ones are released)
 int zr_delta_make(zr_ctx* c, uint32_t W, uint32_t H, bool codec, ZrDeltaBuffers* out);
-void zr_delta_commit(zr_ctx* c, ZrDeltaBuffers& B);      // B's buffers become the context's (the old ones are released): full and serial stay
 // zr_frame_host.cpp: the camera's projection, ViewProjSpace and ViewportInfo of the last zr_update_uniforms for the extent as it is now
 void zr_uniforms_reproject(zr_ctx* c);
 // Tile ownership (zr_tile_owner) of a grid of tiles among `world` ranks: the tiles `rank` owns, in increasing index = its slots in the
@@ -531,12 +530,10 @@ int ids_prepare(zr_ctx* c);            // frame_begin of a captured frame: the c
 int ids_ready(zr_ctx* c, const char* what, bool sync);
 ZrIdsArgs ids_args(zr_ctx* c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h);      // the census's arguments for a rectangle of that frame
 size_t ids_slot_count(const zr_ctx* c);                                              // the slots of zr_instance_coverage
-// zr_scale_host.cpp: the context's lighting pass writes the row-major frame, and the frame enqueued last is a finished one
-int scale_ready(zr_ctx* c, const char* what);
-// zr_highlight_host.cpp: a highlighted delivery may be enqueued (the refusals of scale_ready, then of ids_ready); the frame enqueued
-// last highlighted into dst (null: the context's own buffer, which is returned in *out), on the render stream
-int zr_highlight_ready(zr_ctx* c, const char* what);
-int zr_highlight_enqueue(zr_ctx* c, uint32_t* dst, const uint32_t** out);
+// A reader of that frame's winner plane was enqueued on the render stream: the frame that writes that copy next (the one after next) waits for it
+int ids_reader_enqueued(zr_ctx* c);
+// zr_highlight_host.cpp: the device bitset brought up to the host's set, on the render stream (a highlighted delivery, ahead of its launches)
+int hl_upload(zr_ctx* c);
 // zr_scene.cpp, also used by zr_world.cpp
 float zr_srgb_decode8(uint32_t c);
 int zr_material_prepare(zr_ctx* c, const zr_material* mat, ZrMaterialHost* out);

@@ -1,8 +1,7 @@
 // zr_highlight_host.cpp — highlighting a selection behind the C-ABI (zelda_render.h, "highlighting a selection"): the set and the style
-// (host state of the context: zr_ctx::hl), the highlighted frame in a host form and a device form, the switch that makes the deliveries
-// of changes carry it (zr_delta_host.cpp), and the context-free host statement of the rule (zr_highlight.h).  Like a scaled frame, a
-// highlighted one is no stage of the frame: two launches (zr_highlight.hip) on the render stream behind the lighting pass of the frame
-// enqueued last, and the frame schedule knows nothing of it.
+// (host state of the context: zr_ctx::hl), the set's way to the device (hl_upload), the switch that makes the deliveries of changes
+// carry the highlight, and the context-free host statement of the rule (zr_highlight.h).  The deliveries themselves - the highlighted
+// frame in a host form and a device form, and the changes - are zr_deliver_host.cpp's: its source stage launches zr_highlight.hip.
 //
 // The set against deliveries in flight.  The set calls change host bytes only.  The first delivery after a change packs them into a
 // bit per slot and sends that through the pinned staging ring ON THE RENDER STREAM into the device bitset, ahead of its own launches:
@@ -12,8 +11,6 @@
 #include "zr_highlight.h"
 
 #include <cstring>
-
-static bool scale_ok(uint32_t s) { return s >= 1u && s <= 8u; }
 
 // The set as the scene stands: when the object list changed since it was sized (scene_gen moved), it is empty, at the new slot count
 static void hl_current(zr_ctx* c)
@@ -100,14 +97,8 @@ extern "C" int zr_frame_highlight(const uint8_t* rgba8, const uint8_t* mask, uin
     });
 }
 
-int zr_highlight_ready(zr_ctx* c, const char* what)
-{
-    if (int rc = scale_ready(c, what)) return rc;
-    return ids_ready(c, what, false);
-}
-
 // The device bitset brought up to the host's set, on the render stream
-static int hl_upload(zr_ctx* c)
+int hl_upload(zr_ctx* c)
 {
     zr_ctx::Highlight& L = c->hl;
     hl_current(c);
@@ -130,68 +121,6 @@ static int hl_upload(zr_ctx* c)
     if (rc) return rc;
     L.dirty = false;
     return ZR_OK;
-}
-
-int zr_highlight_enqueue(zr_ctx* c, uint32_t* dst, const uint32_t** out)
-{
-    zr_ctx::Highlight& L = c->hl;
-    if (!L.plane) HIPCHK(c, c->ext.alloc(&L.plane, (size_t)zr_hl_row_words(c->W) * c->H));
-    if (!dst && !L.frame) HIPCHK(c, c->ext.alloc(&L.frame, (size_t)c->W * c->H));
-    if (int rc = hl_upload(c)) return rc;
-    uint32_t* to = dst ? dst : L.frame;
-    const ZrIdsArgs A = ids_args(c, 0, 0, c->W, c->H);
-    zr_launch_highlight_mask(A.prim, A.draws, A.n_draws, L.bits, L.plane, c->W, c->H, c->stream);
-    zr_launch_highlight_apply(c->d_color, L.plane, to, c->W, c->H, L.style, c->stream);
-    HIPCHK(c, hipGetLastError());
-    // the mask reads the last frame's winner plane: the frame that writes that copy next (the one after next) waits for it
-    HIPCHK(c, hipEventRecord(c->fc[c->fcur].ev_ids, c->stream));
-    c->fc[c->fcur].ids_wait = true;
-    if (out) *out = to;
-    return ZR_OK;
-}
-
-// ... then filtered by `scale` into dst (scale 1: highlighted straight into dst)
-static int hl_deliver(zr_ctx* c, uint32_t scale, uint32_t* dst)
-{
-    if (scale == 1u) return zr_highlight_enqueue(c, dst, nullptr);
-    const uint32_t* hl = nullptr;
-    if (int rc = zr_highlight_enqueue(c, nullptr, &hl)) return rc;
-    zr_launch_frame_scale(hl, dst, c->W, c->H, scale, c->stream);
-    HIPCHK(c, hipGetLastError());
-    return ZR_OK;
-}
-
-extern "C" int zr_read_color_highlighted(zr_ctx* c, uint32_t scale, uint8_t* dst, size_t bytes)
-{
-    if (!c) return ZR_ERR_ARG;
-    return zr_guard(c, [&]() -> int {
-        ARGCHK(c, dst && scale_ok(scale));
-        ARGCHK(c, bytes == (size_t)((c->W + scale - 1u) / scale) * ((c->H + scale - 1u) / scale) * 4u);
-        int rc = zr_highlight_ready(c, "zr_read_color_highlighted");
-        if (rc == ZR_OK) rc = zr_finish(c);
-        if (rc) return rc;
-        const uint32_t* src = nullptr;
-        if (scale == 1u) rc = zr_highlight_enqueue(c, nullptr, &src);
-        else {
-            if (!c->d_scaled) HIPCHK(c, c->ext.alloc(&c->d_scaled, (size_t)((c->W + 1u) / 2u) * ((c->H + 1u) / 2u)));
-            rc = hl_deliver(c, scale, c->d_scaled);
-            src = c->d_scaled;
-        }
-        if (rc) return rc;
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
-        return ZR_OK;
-    });
-}
-
-extern "C" int zr_copy_frame_highlighted_async(zr_ctx* c, uint32_t scale, void* color_dev)
-{
-    if (!c) return ZR_ERR_ARG;
-    return zr_guard(c, [&]() -> int {
-        ARGCHK(c, color_dev && (uintptr_t)color_dev % 4 == 0 && scale_ok(scale));
-        if (int rc = zr_highlight_ready(c, "zr_copy_frame_highlighted_async")) return rc;
-        return hl_deliver(c, scale, (uint32_t*)color_dev);
-    });
 }
 
 extern "C" int zr_set_frame_delta_highlight(zr_ctx* c, int on)

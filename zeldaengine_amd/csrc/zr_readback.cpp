@@ -313,6 +313,12 @@ int ids_ready(zr_ctx* c, const char* what, bool sync)
     HIPCHK(c, hipSetDevice(c->device));
     return sync ? zr_finish(c) : ZR_OK;
 }
+int ids_reader_enqueued(zr_ctx* c)
+{
+    HIPCHK(c, hipEventRecord(c->fc[c->fcur].ev_ids, c->stream));
+    c->fc[c->fcur].ids_wait = true;
+    return ZR_OK;
+}
 ZrIdsArgs ids_args(zr_ctx* c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h)
 {
     const FrameCopy& F = c->fc[c->fcur];                      // (stage 0: the copy the frame enqueued last wrote)
@@ -415,10 +421,7 @@ extern "C" int zr_instance_coverage_async(zr_ctx* c, void* counts_dev, size_t by
         int rc = ids_ready(c, "zr_instance_coverage_async", false);
         if (rc == ZR_OK) rc = ids_coverage(c, (uint32_t*)counts_dev, bytes);
         if (rc) return rc;
-        // the census reads the last frame's winner plane: the frame that writes that copy next (the one after next) waits for it
-        HIPCHK(c, hipEventRecord(c->fc[c->fcur].ev_ids, c->stream));
-        c->fc[c->fcur].ids_wait = true;
-        return ZR_OK;
+        return ids_reader_enqueued(c);      // (the census reads the last frame's winner plane)
     });
 }
 

@@ -146,10 +146,10 @@ extern "C" int zr_resize(zr_ctx* c, uint32_t width, uint32_t height)
         ZrExtentState E;
         ZrDeltaBuffers D;
         int rc = make_extent_state(c, width, height, &E);
-        if (rc == ZR_OK && c->delta.on) rc = zr_delta_make(c, width, height, c->delta.codec.on, &D);
+        if (rc == ZR_OK && c->delta.on) rc = zr_delta_make(c, width, height, c->delta.b.codec.on, &D);
         if (rc) { (void)hipGetLastError(); return rc; }
         commit_extent_state(c, E);
-        if (c->delta.on) { zr_delta_commit(c, D); c->delta.full = true; }      // (serial goes on counting)
+        if (c->delta.on) { c->delta.b = std::move(D); c->delta.full = true; }      // (the old buffers are released; serial goes on counting)
         // Every per-pixel history is forgotten: both GBuffer copies, the camera pass of the frame before and its round-2 keep, the record
         // plan, the camera's work list (a rank's is cut to its tiles), the visibility marks (the next frame draws in one round, as a
         // scene's first frame does), the lighting pass's plane - its key does not hold the extent.  The shadow map, its work list and its

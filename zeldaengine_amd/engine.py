@@ -734,9 +734,14 @@ class Renderer:
         return w.value, h.value, t.value, s.value
 
     # ---- delivering a scaled frame: box-filtered by an integer factor in linear light, on the GPU
+    def _scaled_shape(self, s):
+        """(ceil(H / s), ceil(W / s), 4); s = 0 gets a shape too, so that it reaches the library and comes back as ZR_ERR_ARG"""
+        s = max(s, 1)
+        return -(-self.H // s), -(-self.W // s), 4
+
     def color_scaled(self, s):
         """zr_read_color_scaled: the frame filtered by s (1..8) -> (ceil(H / s), ceil(W / s), 4) uint8"""
-        out = np.zeros((-(-self.H // max(s, 1)), -(-self.W // max(s, 1)), 4), dtype=np.uint8)
+        out = np.zeros(self._scaled_shape(s), dtype=np.uint8)
         self._chk(self.L.zr_read_color_scaled(self.h, s, _ptr(out), out.nbytes))
         return out
 
@@ -773,7 +778,7 @@ class Renderer:
 
     def color_highlighted(self, s=1):
         """zr_read_color_highlighted: the frame with the set outlined and filled, filtered by s (1..8) -> (ceil(H / s), ceil(W / s), 4) uint8"""
-        out = np.zeros((-(-self.H // max(s, 1)), -(-self.W // max(s, 1)), 4), dtype=np.uint8)
+        out = np.zeros(self._scaled_shape(s), dtype=np.uint8)
         self._chk(self.L.zr_read_color_highlighted(self.h, s, _ptr(out), out.nbytes))
         return out
 
