@@ -130,13 +130,13 @@ int  zr_set_stream(zr_ctx* ctx, void* hip_stream);
  * zr_config but for the extent, given the same scene, the same calls and the same last uniforms.  Kept as they are, device memory and
  * all: meshes, objects (instances, visibility, materials - also what only a device-form update ever wrote), Profabs, the world, cubemap,
  * skydome, background, the shadow map, streams and staging, limits, bucket share, shading mode, debug view, id capture, timing
- * interval, livelink, the highlight set and style.  Re-made: whatever is sized by the extent.  Forgotten: every per-pixel history - the
+ * interval, livelink, the highlight set and style, the overlay list and style.  Re-made: whatever is sized by the extent.  Forgotten: every per-pixel history - the
  * next frame draws its camera pass as a scene's first frame does, while the shadow map stands or falls by its own key, as after a
  * camera move (a resize with light and casters still enqueues no shadow pipeline).  Until that frame the read-backs, the identity queries
  * and the deliveries answer as on a context that has rendered no frame.
  * Uniforms of zr_update_uniforms (and of the world forms, which go through it) are evaluated again for the new extent: Proj,
  * ViewProjSpace and ViewportInfo are bit-equal to a new context's.  Uniforms last set raw by zr_set_frame stay as given.
- * While delta is on its buffers are re-made for the new (scaled) extent; scale, highlight flag and packed mode stay, serial goes on
+ * While delta is on its buffers are re-made for the new (scaled) extent; scale, highlight and overlay flags and packed mode stay, serial goes on
  * counting, the next delivery is a full one.  A caller-owned tile buffer (zr_set_tiles_buffer) goes back to the internal one, and
  * zr_color_device_ptr / zr_tiles_device_buffer answer anew.
  * The call synchronises everything the library has enqueued.  The new set is built beside the old one and swapped in on success: a
@@ -549,6 +549,70 @@ int  zr_set_frame_delta_highlight(zr_ctx* ctx, int on);
  * compares with.  style_bytes = the caller's sizeof(zr_highlight_style); bytes == width*height*4. */
 int  zr_frame_highlight(const uint8_t* rgba8, const uint8_t* mask, uint32_t width, uint32_t height, const zr_highlight_style* style, size_t style_bytes,
                         uint8_t* dst, size_t bytes);
+
+/* --- overlaying lines ("Overlaying lines"; DESIGN.md §5, "Overlaying lines") ---
+ * The frame delivered with a list of line segments drawn over it, depth-tested against the frame's own depth plane, on the GPU behind
+ * the lighting pass and before any byte crosses a link: a selection's bounding box, a gizmo's axes, a grid, a light's radius, another
+ * camera's frustum.  The frame itself is never drawn into: zr_read_color, zr_copy_frame_async, the scaled and highlighted forms and the
+ * deltas of a context with overlay delivery off deliver what they always did.  A context that never calls these allocates nothing.
+ * End points are in the space of a non-instanced vertex: they go through the proj * view * model of the frame enqueued LAST (a
+ * zr_set_frame / zr_update_uniforms after that frame does not move the lines), so a box computed from zr_object_get_instances lands on
+ * its instance.  The list is host state and no instance set: it survives zr_object_add, world updates and zr_resize; setting it draws
+ * nothing, ends no rest and touches no frame; a delivery enqueued before a change delivers the old list, even while still in flight.
+ * The rule, segment by segment in list order (csrc/zr_overlay.h states it in full; the kernels, zr_frame_overlay and a client's own
+ * code agree byte for byte):
+ *   clip = PVM * (p, 1) in fp32, every fma explicit; a non-finite component draws nothing
+ *   the segment is clipped against z >= 0, 4w +- x >= 0, 4w +- y >= 0, w - z >= 0 and needs w > 0 at both ends
+ *   both ends are projected and snapped to 1/256 pixel as a triangle's corners are; z = clip.z / clip.w
+ *   X-major iff |dX| >= |dY|: every column whose centre cx = 256x + 128 lies in [Xa, Xb) gets the one row that holds
+ *   Ya + floor((2 (cx - Xa) dY + dX) / (2 dX)) - the line's crossing of the column centre rounded to 1/256 pixel; Y-major alike.  A
+ *   chain a-b, b-c covers the joint once; lines are one context pixel wide
+ *   depth d = za + t (zb - za), t = (cx - Xa) / dX, clamped between za and zb
+ *   visible iff ZR_OVERLAY_XRAY or d - depth_bias <= the frame's depth there (what zr_read_gbuffer(ctx, 0, ..) returns; NaN: hidden)
+ *   visible: R, G, B blended with rgba at opacity rgba[3] (the highlight's blend); hidden: at opacity round(rgba[3] * hidden_opacity / 255)
+ *   A is never changed; a pixel crossed by several segments takes them in list order
+ * At a scale above 1 the overlaid frame is filtered afterwards; with a highlight the order is highlight, overlay, filter.
+ * Refusals, the context unchanged, arguments first: ZR_ERR_ARG for a null pointer, n above ZR_OVERLAY_MAX_SEGMENTS, an unknown flag
+ * bit, a wrong byte count, a scale outside 1..8, a misaligned destination, a negative or non-finite depth_bias, hidden_opacity above 255,
+ * a non-zero reserved; ZR_ERR_UNSUPPORTED where the lighting pass does not write the row-major frame (tile_world > 1,
+ * ZR_FLAG_PACKED_TILES); ZR_ERR_STATE before the first finished frame and between the stages of one - and, with highlight != 0, the
+ * cases of zr_read_color_highlighted. */
+typedef struct zr_overlay_segment {   /* 32 bytes */
+    float    a[3], b[3];   /* the two end points */
+    uint8_t  rgba[4];      /* R, G, B, opacity 0..255 */
+    uint32_t flags;        /* ZR_OVERLAY_XRAY, every other bit 0 */
+} zr_overlay_segment;
+#define ZR_OVERLAY_XRAY 1u             /* not depth-tested */
+#define ZR_OVERLAY_MAX_SEGMENTS 16384u
+typedef struct zr_overlay_style {     /* 16 bytes */
+    float    depth_bias;       /* >= 0, finite: taken off a line's depth before the test */
+    uint32_t hidden_opacity;   /* 0..255: what is left of a segment's opacity where it is hidden (0: hidden parts are not drawn) */
+    uint32_t reserved[2];      /* 0, else ZR_ERR_ARG */
+} zr_overlay_style;        /* default: 0.0f, 0 */
+/* Replaces the list; n = 0 clears it (seg may then be null). */
+int  zr_overlay_set(zr_ctx* ctx, const zr_overlay_segment* seg, uint32_t n);
+/* *n in: the room at dst in segments, out: the list's length; ZR_ERR_ARG when the room is too small (*n is still set).  dst null: the length alone. */
+int  zr_overlay_get(zr_ctx* ctx, zr_overlay_segment* dst, uint32_t* n);
+/* bytes = the caller's sizeof(zr_overlay_style) (passed like zr_stats) */
+int  zr_set_overlay_style(zr_ctx* ctx, const zr_overlay_style* style, size_t bytes);
+int  zr_get_overlay_style(zr_ctx* ctx, zr_overlay_style* style, size_t bytes);
+/* Host form: zr_finish first (its error is passed on), the launches into buffers the context makes at first use, then Wd*Hd*4 bytes to
+ * the host.  highlight != 0: the highlighted frame underneath (it needs a captured frame); 0: no id capture is needed. */
+int  zr_read_color_overlaid(zr_ctx* ctx, uint32_t scale, int highlight, uint8_t* rgba8, size_t bytes);
+/* Device form, into a caller-owned DEVICE buffer of Wd*Hd*4 bytes (4-byte aligned): synchronises nothing, ordered on the render stream
+ * exactly as zr_copy_frame_scaled_async.  It reads the last frame's depth plane: the frame after next waits for it before it rewrites
+ * that plane (as for zr_copy_frame_highlighted_async and the winner plane). */
+int  zr_copy_frame_overlaid_async(zr_ctx* ctx, uint32_t scale, int highlight, void* color_dev);
+/* Deltas of the overlaid frame: callable only while delta is off (ZR_ERR_STATE while it is on), kept across zr_set_frame_delta(ctx, 0).
+ * While on, every delivery of changes, in all four forms and at any delta scale, highlights (where zr_set_frame_delta_highlight is on),
+ * overlays, filters, then compares and lists: applying a delivery gives exactly zr_read_color_overlaid(ctx, delta scale, ..)'s bytes, a
+ * frame at rest with an unchanged list lists 0 tiles, and a changed list lists the tiles whose overlaid bytes differ. */
+int  zr_set_frame_delta_overlay(zr_ctx* ctx, int on);
+/* The host statement of the rule, context-free host code: depth = width*height floats (zr_read_gbuffer's plane 0), pvm = the frame's
+ * proj * view * model, 16 floats column-major; seg may be null when n = 0.  style_bytes = the caller's sizeof(zr_overlay_style);
+ * bytes == width*height*4. */
+int  zr_frame_overlay(const uint8_t* rgba8, const float* depth, uint32_t width, uint32_t height, const float* pvm, const zr_overlay_segment* seg, uint32_t n,
+                      const zr_overlay_style* style, size_t style_bytes, uint8_t* dst, size_t bytes);
 
 /* --- object identity of the last frame (which object won each pixel: picking, box selection, per-instance coverage) ---
  * What is reported is the deferred-scene pass's depth-test winner, i.e. what the GBuffer holds: the same in deferred and forward

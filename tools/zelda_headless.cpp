@@ -8,6 +8,7 @@
 //   zelda_headless --root DIR [--world FILE.json] [--livelink PORT [--wait-ms MS]] [--meshlet FILE.meshlet --profab NAME]
 //                  [--size WxH] [--shadow N] [--frames N] [--roll-light-step F] [--debug-view V] [--out FRAME.ppm] [--device D]
 //                  [--pick X,Y[,W,H] [--highlight]] [--incremental] [--delta | --delta-packed] [--scale S] [--resize-at FRAME:WxH]
+//                  [--overlay FILE] [--overlay-box]
 // --resize-at FRAME:WxH gives the live context a new extent ahead of frame FRAME (zr_resize), as a host whose window changes size does:
 // nothing is loaded again, it prints `resized <W>x<H>`, and with --delta, --delta-packed or --scale the client copy and the delivery
 // buffers follow the new (scaled) extent - the next delivery is a full one.
@@ -27,11 +28,21 @@
 // (zr_highlight_set) and every following frame is delivered highlighted (zelda_render.h, "highlighting a selection") through whichever of
 // --delta, --delta-packed and --scale is chosen - zr_set_frame_delta_highlight, or zr_read_color_highlighted at the scale, which prints
 // `highlighted <Wd>x<Hd>` per frame.  --out writes the highlighted picture.
+// --overlay FILE draws line segments over every delivered frame (zelda_render.h, "overlaying lines"): FILE holds one segment per line,
+// `ax ay az bx by bz r g b a flags` (blank lines and lines that start with # are skipped); the list is set once (zr_overlay_set) and
+// every frame is delivered overlaid through whichever of --delta, --delta-packed, --scale and --highlight is chosen -
+// zr_set_frame_delta_overlay, or zr_read_color_overlaid at the scale, which prints `overlaid <Wd>x<Hd>` per frame.  --out writes the
+// overlaid picture.
+// --overlay-box (with --pick) draws the twelve edges of each picked instance's bounds: the pick is made after the first frame, the box
+// of the mesh's vertices (zr_mesh_get_vertices) is taken through the instance's scale, rotation and position (zr_object_get_instances:
+// the vertex stage's own transform, in double precision) and its edges join the list - yellow, hidden parts at a third - so every
+// following frame shows them; it prints `overlay-box <object> <instance>` per box.
 #include "../include/zelda_render.h"
 
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <thread>
@@ -46,11 +57,11 @@ static int fail(zr_ctx* c, const char* what, int rc)
 
 int main(int argc, char** argv)
 {
-    std::string root = ".", world, meshlet, profab = "meshlet", out;
+    std::string root = ".", world, meshlet, profab = "meshlet", out, overlay;
     uint32_t W = 1920, H = 1080, SD = 1024, frames = 1, debug_view = 0, scale = 0;
     int port = -1, wait_ms = 10000, device = 0;
     float roll_step = 0.0f;
-    bool pick = false, incremental = false, delta = false, packed = false, highlight = false; uint32_t px = 0, py = 0, pw = 1, ph = 1;
+    bool pick = false, incremental = false, delta = false, packed = false, highlight = false, overlay_box = false; uint32_t px = 0, py = 0, pw = 1, ph = 1;
     uint32_t resize_at = 0xFFFFFFFFu, RW = 0, RH = 0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -73,6 +84,8 @@ int main(int argc, char** argv)
         else if (a == "--delta-packed") delta = packed = true;
         else if (a == "--scale") scale = (uint32_t)atoi(next());
         else if (a == "--highlight") highlight = true;
+        else if (a == "--overlay") overlay = next();
+        else if (a == "--overlay-box") overlay_box = true;
         else if (a == "--resize-at") { if (sscanf(next(), "%u:%ux%u", &resize_at, &RW, &RH) != 3) { fprintf(stderr, "--resize-at FRAME:WxH\n"); return 2; } }
         else if (a == "--pick") {
             const int got = sscanf(next(), "%u,%u,%u,%u", &px, &py, &pw, &ph);
@@ -82,6 +95,7 @@ int main(int argc, char** argv)
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     if (highlight && !pick) { fprintf(stderr, "--highlight needs --pick X,Y[,W,H]\n"); return 2; }
+    if (overlay_box && !pick) { fprintf(stderr, "--overlay-box needs --pick X,Y[,W,H]\n"); return 2; }
     zr_config cfg; memset(&cfg, 0, sizeof cfg);
     cfg.width = W; cfg.height = H; cfg.shadow_dim = SD; cfg.debug_view = debug_view; cfg.device = device; cfg.tile_world = 1;
     zr_ctx* c = nullptr;
@@ -112,13 +126,81 @@ int main(int argc, char** argv)
     if (!have_world) { fprintf(stderr, "zelda_headless: no world (give --world FILE or send one to --livelink PORT)\n"); zr_destroy(c); return 1; }
 
     if (pick && (rc = zr_set_id_capture(c, 1))) return fail(c, "zr_set_id_capture", rc);
+    std::vector<zr_overlay_segment> segs;
+    if (!overlay.empty()) {          // --overlay: the list, read once
+        FILE* fp = fopen(overlay.c_str(), "r");
+        if (!fp) { fprintf(stderr, "zelda_headless: cannot read %s\n", overlay.c_str()); zr_destroy(c); return 1; }
+        char line[512];
+        for (unsigned ln = 1; fgets(line, sizeof line, fp); ++ln) {
+            const char* p = line + strspn(line, " \t\r\n");
+            if (!*p || *p == '#') continue;
+            zr_overlay_segment s; unsigned col[4], flags = 0;
+            if (sscanf(p, "%f %f %f %f %f %f %u %u %u %u %u", &s.a[0], &s.a[1], &s.a[2], &s.b[0], &s.b[1], &s.b[2], &col[0], &col[1], &col[2], &col[3], &flags) != 11 ||
+                col[0] > 255 || col[1] > 255 || col[2] > 255 || col[3] > 255) {
+                fprintf(stderr, "zelda_headless: %s:%u: ax ay az bx by bz r g b a flags\n", overlay.c_str(), ln); fclose(fp); zr_destroy(c); return 2;
+            }
+            for (int k = 0; k < 4; ++k) s.rgba[k] = (uint8_t)col[k];
+            s.flags = flags;
+            segs.push_back(s);
+        }
+        fclose(fp);
+        if ((rc = zr_overlay_set(c, segs.data(), (uint32_t)segs.size()))) return fail(c, "zr_overlay_set", rc);
+    }
+    const bool lines = !overlay.empty() || overlay_box;
+    if (overlay_box) {
+        const zr_overlay_style st = { 0.0f, 85u, { 0u, 0u } };
+        if ((rc = zr_set_overlay_style(c, &st, sizeof st))) return fail(c, "zr_set_overlay_style", rc);
+    }
+    // --overlay-box: the twelve edges of one instance's bounds appended to the list
+    auto add_box = [&](uint32_t object, uint32_t instance) -> int {
+        uint32_t mesh = 0, n_inst = 0, n_v = 0;
+        if ((rc = zr_object_get_instances(c, object, &mesh, nullptr, &n_inst))) return rc;
+        std::vector<XkInstanceData> inst(n_inst);
+        if (n_inst && (rc = zr_object_get_instances(c, object, &mesh, inst.data(), &n_inst))) return rc;
+        if ((rc = zr_mesh_get_vertices(c, mesh, nullptr, &n_v))) return rc;
+        std::vector<XkVertex> v(n_v);
+        if (!n_v || (rc = zr_mesh_get_vertices(c, mesh, v.data(), &n_v))) return rc;
+        double lo[3] = { 1e300, 1e300, 1e300 }, hi[3] = { -1e300, -1e300, -1e300 };
+        for (const XkVertex& x : v) for (int k = 0; k < 3; ++k) { lo[k] = std::fmin(lo[k], x.Position[k]); hi[k] = std::fmax(hi[k], x.Position[k]); }
+        // the vertex stage's instance transform: (p * scale) as a row vector times rotMat = mz * my * mx (column-major), plus the position
+        double R[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 }, t[3] = { 0, 0, 0 }, sc = 1.0;
+        if (instance < n_inst) {
+            const XkInstanceData& I = inst[instance];
+            const double ax = I.InstanceRotation[0], ay = I.InstanceRotation[1], az = I.InstanceRotation[2];      // (double: std::cos of a float is cosf)
+            const double cx = std::cos(ax), sx = std::sin(ax), cy = std::cos(ay), sy = std::sin(ay), cz = std::cos(az), sz = std::sin(az);
+            const double mx[9] = { cx, 0, sx, 0, 1, 0, -sx, 0, cx }, my[9] = { cy, sy, 0, -sy, cy, 0, 0, 0, 1 }, mz[9] = { 1, 0, 0, 0, cz, sz, 0, -sz, cz };
+            double zy[9];
+            auto mul = [](const double* A, const double* B, double* C) {
+                for (int cc = 0; cc < 3; ++cc) for (int r = 0; r < 3; ++r) C[cc * 3 + r] = A[r] * B[cc * 3] + A[3 + r] * B[cc * 3 + 1] + A[6 + r] * B[cc * 3 + 2];
+            };
+            mul(mz, my, zy); mul(zy, mx, R);
+            sc = I.InstancePScale;
+            for (int k = 0; k < 3; ++k) t[k] = I.InstancePosition[k];
+        }
+        float corner[8][3];
+        for (int i = 0; i < 8; ++i) {
+            const double p[3] = { ((i & 1) ? hi[0] : lo[0]) * sc, ((i & 2) ? hi[1] : lo[1]) * sc, ((i & 4) ? hi[2] : lo[2]) * sc };
+            for (int j = 0; j < 3; ++j) corner[i][j] = (float)(p[0] * R[j * 3] + p[1] * R[j * 3 + 1] + p[2] * R[j * 3 + 2] + t[j]);
+        }
+        for (int i = 0; i < 8; ++i)
+            for (int b = 1; b < 8; b <<= 1) {
+                if (i & b) continue;
+                zr_overlay_segment s; memset(&s, 0, sizeof s);
+                memcpy(s.a, corner[i], sizeof s.a); memcpy(s.b, corner[i | b], sizeof s.b);
+                s.rgba[0] = 255; s.rgba[1] = 220; s.rgba[2] = 0; s.rgba[3] = 255;
+                segs.push_back(s);
+            }
+        printf("overlay-box %u %u\n", object, instance);
+        return zr_overlay_set(c, segs.data(), (uint32_t)segs.size());
+    };
     // --delta: the client's copy of the frame, and full-sized buffers for a delivery (only the listed tiles are written and moved)
     // DW x DH: what is delivered - the frame, or with --scale the scaled one (with --delta: the delta scale's extent, in `total` tiles)
     uint32_t DW = W, DH = H, total = 0, delta_scale = 1;
     const uint32_t scaled = delta ? 0u : scale;           // without --delta: the scale every frame is read at (0: frames are not read)
     std::vector<uint8_t> client, slots; std::vector<uint32_t> list, offsets;
     if (scale && (rc = zr_frame_scaled_extent(W, H, scale, &DW, &DH))) return fail(c, "zr_frame_scaled_extent (--scale 1..8)", rc);
-    if (scaled || (highlight && !delta)) client.assign((size_t)DW * DH * 4, 0);
+    if (scaled || ((highlight || lines) && !delta)) client.assign((size_t)DW * DH * 4, 0);
+    if (lines && delta && (rc = zr_set_frame_delta_overlay(c, 1))) return fail(c, "zr_set_frame_delta_overlay", rc);
     if (highlight && delta && (rc = zr_set_frame_delta_highlight(c, 1))) return fail(c, "zr_set_frame_delta_highlight", rc);
     if (scale && delta && (rc = zr_set_frame_delta_scale(c, scale))) return fail(c, "zr_set_frame_delta_scale", rc);
     if (delta && (rc = zr_get_frame_delta_extent(c, &DW, &DH, &total, &delta_scale))) return fail(c, "zr_get_frame_delta_extent", rc);
@@ -142,6 +224,7 @@ int main(int argc, char** argv)
                    h.object, h.instance, h.pixels, h.triangle, h.x, h.y, (double)h.depth);
             const uint8_t on = 1;
             if (highlight && (rc = zr_highlight_set(c, h.object, h.instance, &on, 1))) return rc;
+            if (overlay_box && (rc = add_box(h.object, h.instance))) return rc;
         }
         return 0;
     };
@@ -161,8 +244,12 @@ int main(int argc, char** argv)
         if (port >= 0 && (rc = zr_livelink_poll(c, &reloaded))) return fail(c, "zr_livelink_poll", rc);
         if ((rc = zr_world_update_uniforms(c, 0.0f, roll_step * (float)f, 0.016f * (float)f))) return fail(c, "zr_world_update_uniforms", rc);
         if ((rc = zr_render(c))) return fail(c, "zr_render", rc);
-        if (highlight && f == 0 && do_pick()) return fail(c, "zr_pick / zr_highlight_set", rc);      // the click: from here on the selection shows
-        if (!delta && highlight) {                        // the highlighted frame, at the scale, is all that crosses the link
+        if ((highlight || overlay_box) && f == 0 && do_pick()) return fail(c, "zr_pick / zr_highlight_set / zr_overlay_set", rc);      // the click: from here on the selection shows
+        if (!delta && lines) {                            // the overlaid frame (highlighted underneath or not), at the scale
+            if ((rc = zr_read_color_overlaid(c, scale ? scale : 1u, highlight ? 1 : 0, client.data(), client.size()))) return fail(c, "zr_read_color_overlaid", rc);
+            printf("overlaid %ux%u\n", DW, DH);
+        }
+        else if (!delta && highlight) {                   // the highlighted frame, at the scale, is all that crosses the link
             if ((rc = zr_read_color_highlighted(c, scale ? scale : 1u, client.data(), client.size()))) return fail(c, "zr_read_color_highlighted", rc);
             printf("highlighted %ux%u\n", DW, DH);
         }
@@ -196,10 +283,10 @@ int main(int argc, char** argv)
     uint32_t n_obj = 0; zr_object_count(c, &n_obj);
     printf("frames %u  %.3f ms/frame  objects %u  meshlet-instances %llu  camera survivors %llu  covered pixels %llu\n", frames, ms / frames, n_obj,
            (unsigned long long)st.work_items[1], (unsigned long long)st.survivors[1], (unsigned long long)st.covered_pixels);
-    if (pick && !highlight && do_pick()) return fail(c, "zr_pick", rc);
+    if (pick && !highlight && !overlay_box && do_pick()) return fail(c, "zr_pick", rc);
     if (!out.empty()) {
         std::vector<uint8_t> rgba((size_t)DW * DH * 4);
-        if (delta || scaled || highlight) rgba = client;
+        if (delta || scaled || highlight || lines) rgba = client;
         else if ((rc = zr_read_color(c, rgba.data(), rgba.size()))) return fail(c, "zr_read_color", rc);
         FILE* fp = fopen(out.c_str(), "wb");
         if (!fp) { fprintf(stderr, "zelda_headless: cannot write %s\n", out.c_str()); zr_destroy(c); return 1; }

@@ -97,6 +97,35 @@ HIGHLIGHT_SIGNATURES = {
     "zr_set_frame_delta_highlight": [vp_, C.c_int],
     "zr_frame_highlight": [vp_, vp_, u32_, u32_, C.POINTER(HighlightStyle), C.c_size_t, vp_, C.c_size_t],
 }
+
+
+class OverlaySegment(C.Structure):
+    """ctypes mirror of zr_overlay_segment (32 bytes)"""
+    _fields_ = [("a", C.c_float * 3), ("b", C.c_float * 3), ("rgba", C.c_uint8 * 4), ("flags", C.c_uint32)]
+
+
+class OverlayStyle(C.Structure):
+    """ctypes mirror of zr_overlay_style (16 bytes, passed with its size, like zr_stats)"""
+    _fields_ = [("depth_bias", C.c_float), ("hidden_opacity", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+assert C.sizeof(OverlaySegment) == 32 and C.sizeof(OverlayStyle) == 16
+# numpy mirror of zr_overlay_segment: what Renderer.overlay_set takes and overlay_get returns
+OVERLAY_SEGMENT = np.dtype([("a", "<f4", 3), ("b", "<f4", 3), ("rgba", "u1", 4), ("flags", "<u4")])
+assert OVERLAY_SEGMENT.itemsize == 32
+OVERLAY_XRAY = 1                  # ZR_OVERLAY_XRAY: the segment is not depth-tested
+OVERLAY_MAX_SEGMENTS = 16384
+# overlaying lines (include/zelda_render.h, "overlaying lines")
+OVERLAY_SIGNATURES = {
+    "zr_overlay_set": [vp_, vp_, u32_],
+    "zr_overlay_get": [vp_, vp_, C.POINTER(u32_)],
+    "zr_set_overlay_style": [vp_, C.POINTER(OverlayStyle), C.c_size_t],
+    "zr_get_overlay_style": [vp_, C.POINTER(OverlayStyle), C.c_size_t],
+    "zr_read_color_overlaid": [vp_, u32_, C.c_int, vp_, C.c_size_t],
+    "zr_copy_frame_overlaid_async": [vp_, u32_, C.c_int, vp_],
+    "zr_set_frame_delta_overlay": [vp_, C.c_int],
+    "zr_frame_overlay": [vp_, vp_, u32_, u32_, vp_, vp_, u32_, C.POINTER(OverlayStyle), C.c_size_t, vp_, C.c_size_t],
+}
 # the extent of a live context (include/zelda_render.h, "lifetime")
 EXTENT_SIGNATURES = {
     "zr_resize": [vp_, u32_, u32_],
@@ -108,6 +137,22 @@ del vp_, u32_
 def make_highlight_style(outline=(255, 160, 0, 255), fill=(255, 160, 0, 0), radius=2):
     """zr_highlight_style from (R, G, B, opacity) tuples and the outline's width; the defaults are the library's"""
     return HighlightStyle((C.c_uint8 * 4)(*outline), (C.c_uint8 * 4)(*fill), radius, 0)
+
+
+def make_overlay_style(depth_bias=0.0, hidden_opacity=0):
+    """zr_overlay_style; the defaults are the library's"""
+    return OverlayStyle(depth_bias, hidden_opacity, (C.c_uint32 * 2)(0, 0))
+
+
+def make_overlay_segments(segments):
+    """An OVERLAY_SEGMENT array from one, or from rows (ax, ay, az, bx, by, bz, r, g, b, a[, flags])"""
+    if isinstance(segments, np.ndarray) and segments.dtype == OVERLAY_SEGMENT:
+        return np.ascontiguousarray(segments).reshape(-1)
+    rows = [tuple(s) for s in segments]
+    out = np.zeros(len(rows), dtype=OVERLAY_SEGMENT)
+    for i, s in enumerate(rows):
+        out[i]["a"], out[i]["b"], out[i]["rgba"], out[i]["flags"] = s[0:3], s[3:6], s[6:10], s[10] if len(s) > 10 else 0
+    return out
 
 
 class Camera(C.Structure):

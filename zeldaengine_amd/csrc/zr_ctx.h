@@ -16,6 +16,7 @@
 #include "zr_frame_plan.h"
 #include "zr_ids.h"
 #include "zr_meshlet.h"
+#include "zr_overlay.h"
 #include "zr_scale.h"
 #include "zr_types.h"
 #include "zr_world_doc.h"
@@ -163,7 +164,8 @@ struct FrameCopy {
     bool shadow_cleared = false;         // `shadow` already holds depth 1.0 (cleared by a lighting pass since it was last drawn into)
     uint64_t view_uploaded = 0;          // which version of the uniforms `view` holds
     uint64_t g_gen = 0;                  // the run of equal inputs (ZrFramePlan::g_gen) G was last resolved in (0: never)
-    // a census enqueued against this copy (zr_instance_coverage_async): the frame that writes it next waits for it
+    // a reader of this copy enqueued on the render stream - a census or a highlight's mask (the winner plane), an overlay (G.depth): the
+    // frame that writes it next waits for it
     hipEvent_t ev_ids = nullptr; bool ids_wait = false;
 };
 
@@ -189,7 +191,7 @@ struct ZrDeltaBuffers {
 // `ext` owns what is sized by the frame's extent (W, H, a tile count) - what make_extent_state makes (zr_resize.cpp: the GBuffer copies,
 // the key buffers, d_color, the Hi-Z pyramid, the tile tables, d_tiles, the shadow bins' per-tile arrays) and what later calls make at
 // first use (winner planes, the skydome's key plane, the light-keep plane and its records, d_scaled, ids.obj, the highlight's plane and
-// frame).  zr_resize builds a new set beside it and swaps the two.  `pool_tiles` owns the work pools' per-tile parts (make_pool_tiles).
+// frame, the overlay's frame).  zr_resize builds a new set beside it and swaps the two.  `pool_tiles` owns the work pools' per-tile parts (make_pool_tiles).
 struct zr_ctx {
     ZrOwn own, ext, pool_tiles;
     zr_config cfg;
@@ -414,6 +416,19 @@ struct zr_ctx {
     std::map<std::string, std::vector<ZrProfab>> profabs;
     std::mutex ll_mutex; std::thread ll_thread; std::atomic<bool> ll_run{ false };
     int ll_listen_fd = -1; bool ll_pending = false, ll_bind_any = false; ZrWorld ll_world; uint16_t ll_port = 0;
+
+    // Overlaying lines (zr_overlay_host.cpp, zr_overlay.hip).  seg: the list, host state, tied to nothing of the scene; dirty: the device
+    // copy d_seg (through `mem` with the records and rectangles the set-up kernel writes, all sized for `cap` segments and re-made when
+    // the list outgrows them) is older than it - the next overlaid delivery stages it on the render stream first, so deliveries in
+    // flight keep the list they were enqueued with.  frame (W * H) is made at first use through `ext`.  delta: zr_set_frame_delta_overlay.
+    // (Last in the context: what the frame loop touches lies where it lay.)  A context that never sets a list has none of it.  The
+    // camera is cam_prev_key's: the block of the frame enqueued last.
+    struct Overlay {
+        std::vector<zr_overlay_segment> seg; bool dirty = true, delta = false;
+        zr_overlay_style style = { 0.0f, 0u, { 0u, 0u } };
+        ZrOwn mem; zr_overlay_segment* d_seg = nullptr; ZrOvRecord* recs = nullptr; uint32_t* rects = nullptr; size_t cap = 0;
+        uint32_t* frame = nullptr;
+    } ov;
 };
 
 // What the deliveries of changes compare, list and size their buffers for: the frame at the delta scale (zr_ctx::Delta::scale), in tiles
@@ -530,10 +545,23 @@ int ids_prepare(zr_ctx* c);            // frame_begin of a captured frame: the c
 int ids_ready(zr_ctx* c, const char* what, bool sync);
 ZrIdsArgs ids_args(zr_ctx* c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h);      // the census's arguments for a rectangle of that frame
 size_t ids_slot_count(const zr_ctx* c);                                              // the slots of zr_instance_coverage
-// A reader of that frame's winner plane was enqueued on the render stream: the frame that writes that copy next (the one after next) waits for it
+// A reader of that frame's copy - its winner plane (the census, the highlight's mask) or its GBuffer depth (the overlay) - was enqueued on
+// the render stream: the frame that resolves into that copy next (the one after next, where it draws its camera pass) waits for it
 int ids_reader_enqueued(zr_ctx* c);
 // zr_highlight_host.cpp: the device bitset brought up to the host's set, on the render stream (a highlighted delivery, ahead of its launches)
 int hl_upload(zr_ctx* c);
+// zr_overlay_host.cpp: the overlay stage of a delivery on the render stream - the list brought up to date, set up for the camera of the
+// frame enqueued last, drawn over `src` into `dst` (null: the context's scratch frame, made at first use); *out: where the result lies
+int zr_overlay_stage(zr_ctx* c, const uint32_t* src, uint32_t* dst, const uint32_t** out);
+// zr_overlay.hip: the n segments at seg set up for the camera (pvm, hw, hh) of a W x H frame into recs and rects (n each); `frame` (16-byte
+// aligned) with the records drawn over it against `depth` into dst (4-byte aligned), all W x H
+void zr_launch_overlay_setup(const zr_overlay_segment* seg, uint32_t n, const float* pvm, float hw, float hh, uint32_t W, uint32_t H, ZrOvRecord* recs, uint32_t* rects,
+                             hipStream_t st);
+void zr_launch_overlay_apply(const uint32_t* frame, const float* depth, const ZrOvRecord* recs, const uint32_t* rects, uint32_t n, uint32_t* dst, uint32_t W, uint32_t H,
+                             const zr_overlay_style& style, hipStream_t st);
+// zr_deliver_host.cpp: the two whole-frame forms of a delivery (the highlight underneath, the overlay, the filter by `scale`)
+int zr_deliver_to_host(zr_ctx* c, const char* what, bool highlight, bool overlay, uint32_t scale, uint8_t* dst, size_t bytes);
+int zr_deliver_to_device(zr_ctx* c, const char* what, bool highlight, bool overlay, uint32_t scale, void* color_dev);
 // zr_scene.cpp, also used by zr_world.cpp
 float zr_srgb_decode8(uint32_t c);
 int zr_material_prepare(zr_ctx* c, const zr_material* mat, ZrMaterialHost* out);

@@ -1,7 +1,8 @@
 // zr_deliver_host.cpp — delivering the frame enqueued last behind the C-ABI (zelda_render.h, "delivering a scaled frame", "highlighting a
 // selection", "delivering changes").  Every delivery is one path: the SOURCE STAGE (zr_deliver_source: the frame, highlighted or not -
-// zr_highlight.hip - and box-filtered or not - zr_scale.hip) and then a FORM: the whole frame to the host or into a device buffer, or
-// the tiles that changed since the last delivery (zr_delta.hip), raw or as records of the tile codec, each to the host or to the device.
+// zr_highlight.hip - with the overlay's lines over it or not - zr_overlay_host.cpp - and box-filtered or not - zr_scale.hip) and then a
+// FORM: the whole frame to the host or into a device buffer, or the tiles that changed since the last delivery (zr_delta.hip), raw or as
+// records of the tile codec, each to the host or to the device.
 // One check says whether the frame can be delivered (zr_deliver_ready).  No delivery is a stage of the frame: its launches go on the
 // render stream behind the lighting pass of the frame enqueued last, where zr_copy_frame_async's copy goes, and the frame schedule knows
 // nothing of them.  DESIGN.md section 5, "Delivering a frame: one path", has the launches call by call.
@@ -63,8 +64,9 @@ static int zr_deliver_ready(zr_ctx* c, const char* what, bool highlight)
     return ZR_OK;
 }
 
-// What is delivered: the frame enqueued last, highlighted or not, then filtered by `scale` (1: not filtered)
-struct ZrDeliverWhat { bool highlight; uint32_t scale; };
+// What is delivered: the frame enqueued last, highlighted or not, with the lines drawn over it or not (zr_overlay_stage), then filtered
+// by `scale` (1: not filtered)
+struct ZrDeliverWhat { bool highlight, overlay; uint32_t scale; };
 
 // The source stage, on the render stream.  dst: where the result goes, or null: the context's own scratch (hl.frame, d_scaled - both
 // made here at first use, through `ext`); *out: where it lies - c->d_color itself when nothing was to be done.  A caller's dst is
@@ -72,8 +74,9 @@ struct ZrDeliverWhat { bool highlight; uint32_t scale; };
 static int zr_deliver_source(zr_ctx* c, ZrDeliverWhat what, uint32_t* dst, const uint32_t** out)
 {
     zr_ctx::Highlight& L = c->hl;
-    const bool filter = what.scale > 1u || (dst && !what.highlight);
-    uint32_t* const hl_dst = filter ? nullptr : dst;      // (filtered afterwards: highlighted into the scratch frame)
+    const bool overlay = what.overlay && !c->ov.seg.empty();      // (an empty list: no stage)
+    const bool filter = what.scale > 1u || (dst && !what.highlight && !overlay);
+    uint32_t* const hl_dst = filter || overlay ? nullptr : dst;      // (filtered or drawn over afterwards: highlighted into the scratch frame)
     if (what.highlight && !L.plane) HIPCHK(c, c->ext.alloc(&L.plane, (size_t)zr_hl_row_words(c->W) * c->H));
     if (what.highlight && !hl_dst && !L.frame) HIPCHK(c, c->ext.alloc(&L.frame, scaled_pixels(c, 1u)));
     if (filter && !dst && !c->d_scaled) HIPCHK(c, c->ext.alloc(&c->d_scaled, scaled_pixels(c, 2u)));      // (scale 2: the largest output)
@@ -87,6 +90,8 @@ static int zr_deliver_source(zr_ctx* c, ZrDeliverWhat what, uint32_t* dst, const
         if (int rc = ids_reader_enqueued(c)) return rc;      // (the mask read the last frame's winner plane)
         src = to;
     }
+    if (overlay)
+        if (int rc = zr_overlay_stage(c, src, filter ? nullptr : dst, &src)) return rc;
     if (filter) {
         uint32_t* const to = dst ? dst : c->d_scaled;
         zr_launch_frame_scale(src, to, c->W, c->H, what.scale, c->stream);
@@ -100,14 +105,14 @@ static int zr_deliver_source(zr_ctx* c, ZrDeliverWhat what, uint32_t* dst, const
 // ------------------------------------------------------------------------------------------------ the form: the whole frame
 
 // ... to the host: zr_finish first (its overflow is the call's error), and the delivered frame is all that crosses the link
-static int deliver_to_host(zr_ctx* c, const char* what, bool highlight, uint32_t scale, uint8_t* dst, size_t bytes)
+int zr_deliver_to_host(zr_ctx* c, const char* what, bool highlight, bool overlay, uint32_t scale, uint8_t* dst, size_t bytes)
 {
     ARGCHK(c, dst && scale_ok(scale));
     ARGCHK(c, bytes == scaled_pixels(c, scale) * 4u);
     int rc = zr_deliver_ready(c, what, highlight);
     if (rc == ZR_OK) rc = zr_finish(c);
     const uint32_t* src = nullptr;
-    if (rc == ZR_OK) rc = zr_deliver_source(c, { highlight, scale }, nullptr, &src);
+    if (rc == ZR_OK) rc = zr_deliver_source(c, { highlight, overlay, scale }, nullptr, &src);
     if (rc) return rc;
     if (src != c->d_color) HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
@@ -115,36 +120,36 @@ static int deliver_to_host(zr_ctx* c, const char* what, bool highlight, uint32_t
 }
 
 // ... into a caller-owned device buffer, in stream order
-static int deliver_to_device(zr_ctx* c, const char* what, bool highlight, uint32_t scale, void* color_dev)
+int zr_deliver_to_device(zr_ctx* c, const char* what, bool highlight, bool overlay, uint32_t scale, void* color_dev)
 {
     ARGCHK(c, color_dev && (uintptr_t)color_dev % 4 == 0 && scale_ok(scale));
     if (int rc = zr_deliver_ready(c, what, highlight)) return rc;
     const uint32_t* at = nullptr;
-    return zr_deliver_source(c, { highlight, scale }, (uint32_t*)color_dev, &at);
+    return zr_deliver_source(c, { highlight, overlay, scale }, (uint32_t*)color_dev, &at);
 }
 
 extern "C" int zr_read_color_scaled(zr_ctx* c, uint32_t scale, uint8_t* dst, size_t bytes)
 {
     if (!c) return ZR_ERR_ARG;
-    return zr_guard(c, [&]() -> int { return deliver_to_host(c, "zr_read_color_scaled", false, scale, dst, bytes); });
+    return zr_guard(c, [&]() -> int { return zr_deliver_to_host(c, "zr_read_color_scaled", false, false, scale, dst, bytes); });
 }
 
 extern "C" int zr_copy_frame_scaled_async(zr_ctx* c, uint32_t scale, void* color_dev)
 {
     if (!c) return ZR_ERR_ARG;
-    return zr_guard(c, [&]() -> int { return deliver_to_device(c, "zr_copy_frame_scaled_async", false, scale, color_dev); });
+    return zr_guard(c, [&]() -> int { return zr_deliver_to_device(c, "zr_copy_frame_scaled_async", false, false, scale, color_dev); });
 }
 
 extern "C" int zr_read_color_highlighted(zr_ctx* c, uint32_t scale, uint8_t* dst, size_t bytes)
 {
     if (!c) return ZR_ERR_ARG;
-    return zr_guard(c, [&]() -> int { return deliver_to_host(c, "zr_read_color_highlighted", true, scale, dst, bytes); });
+    return zr_guard(c, [&]() -> int { return zr_deliver_to_host(c, "zr_read_color_highlighted", true, false, scale, dst, bytes); });
 }
 
 extern "C" int zr_copy_frame_highlighted_async(zr_ctx* c, uint32_t scale, void* color_dev)
 {
     if (!c) return ZR_ERR_ARG;
-    return zr_guard(c, [&]() -> int { return deliver_to_device(c, "zr_copy_frame_highlighted_async", true, scale, color_dev); });
+    return zr_guard(c, [&]() -> int { return zr_deliver_to_device(c, "zr_copy_frame_highlighted_async", true, false, scale, color_dev); });
 }
 
 // ------------------------------------------------------------------------------------------------ the form: changed tiles - the state
@@ -272,7 +277,7 @@ static int delta_enqueue(zr_ctx* c, const DeltaForm& F)
     const ZrDeltaExtent E = zr_delta_extent(c);
     const uint32_t serial = D.serial + 1u, full = D.full ? 1u : 0u;
     const uint32_t* frame = nullptr;
-    if (int rc = zr_deliver_source(c, { c->hl.delta, D.scale }, D.b.scaled, &frame)) return rc;
+    if (int rc = zr_deliver_source(c, { c->hl.delta, c->ov.delta, D.scale }, D.b.scaled, &frame)) return rc;
     if (F.offsets)
         zr_launch_frame_delta_packed(frame, D.b.delivered, D.b.flags, D.b.codec.lens, F.header, F.list, F.offsets, F.payload, E.W, E.H, E.tiles_x, E.n_tiles, full, serial,
                                      c->stream);

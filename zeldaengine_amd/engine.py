@@ -63,6 +63,7 @@ def lib():
         **abi.FRAME_DELTA_SIGNATURES,
         **abi.FRAME_SCALE_SIGNATURES,
         **abi.HIGHLIGHT_SIGNATURES,
+        **abi.OVERLAY_SIGNATURES,
         **abi.EXTENT_SIGNATURES,
         "zr_set_cubemap": [vp, vp, u32],
         "zr_set_skydome": [vp, vp, u32, vp, u32, vp],
@@ -308,6 +309,31 @@ def frame_highlight(img, mask, style=None):
     rc = lib().zr_frame_highlight(_ptr(img), _ptr(mask), img.shape[1], img.shape[0], C.byref(st), C.sizeof(st), _ptr(out), out.nbytes)
     if rc:
         raise ZeldaRenderError(rc, "zr_frame_highlight: bad argument")
+    return out
+
+
+def _overlay_style(style):
+    """an abi.OverlayStyle from one, from None (the default) or from a dict of make_overlay_style's arguments"""
+    if isinstance(style, abi.OverlayStyle):
+        return style
+    return abi.make_overlay_style(**(style or {}))
+
+
+def frame_overlay(img, depth, pvm, segments, style=None):
+    """zr_frame_overlay, the host statement of the overlay rule (host code only): img (H, W, 4) uint8, depth (H, W) float32, pvm the
+    frame's proj * view * model (16 floats, column-major), segments an abi.OVERLAY_SEGMENT array (or make_overlay_segments' rows),
+    style an abi.OverlayStyle (None: the default) -> (H, W, 4) uint8"""
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    depth = np.ascontiguousarray(depth, dtype=np.float32)
+    pvm = np.ascontiguousarray(np.asarray(pvm, dtype=np.float32).reshape(16))
+    seg = abi.make_overlay_segments(segments)
+    assert img.ndim == 3 and img.shape[2] == 4 and depth.shape == img.shape[:2]
+    st = _overlay_style(style)
+    out = np.zeros_like(img)
+    rc = lib().zr_frame_overlay(_ptr(img), _ptr(depth), img.shape[1], img.shape[0], _ptr(pvm), _ptr(seg) if seg.size else None, seg.size, C.byref(st), C.sizeof(st),
+                                _ptr(out), out.nbytes)
+    if rc:
+        raise ZeldaRenderError(rc, "zr_frame_overlay: bad argument")
     return out
 
 
@@ -786,6 +812,48 @@ class Renderer:
         """The frame enqueued last, highlighted and filtered by s -> a caller-owned device buffer (address, 4-byte aligned, ceil(W / s) *
         ceil(H / s) * 4 bytes), in stream order, no host synchronisation."""
         self._chk(self.L.zr_copy_frame_highlighted_async(self.h, s, C.c_void_p(color_dev) if color_dev else None))
+
+    # ---- overlaying lines: depth-tested segments drawn over the delivered frame
+    def overlay_set(self, segments=None):
+        """zr_overlay_set: replaces the list; an abi.OVERLAY_SEGMENT array, rows (ax, ay, az, bx, by, bz, r, g, b, a[, flags]), or
+        None / empty: cleared"""
+        seg = abi.make_overlay_segments(segments if segments is not None else [])
+        self._chk(self.L.zr_overlay_set(self.h, _ptr(seg) if seg.size else None, seg.size))
+
+    def overlay_get(self):
+        """zr_overlay_get -> an abi.OVERLAY_SEGMENT array"""
+        n = C.c_uint32(0)
+        self._chk(self.L.zr_overlay_get(self.h, None, C.byref(n)))
+        out = np.zeros(n.value, dtype=abi.OVERLAY_SEGMENT)
+        self._chk(self.L.zr_overlay_get(self.h, _ptr(out) if out.size else None, C.byref(n)))
+        return out
+
+    def overlay_style(self, style=None, **kw):
+        """zr_get_overlay_style with no argument -> abi.OverlayStyle; with an abi.OverlayStyle or make_overlay_style's arguments
+        (depth_bias=, hidden_opacity=): zr_set_overlay_style"""
+        if style is None and not kw:
+            st = abi.OverlayStyle()
+            self._chk(self.L.zr_get_overlay_style(self.h, C.byref(st), C.sizeof(st)))
+            return st
+        st = _overlay_style(style if style is not None else kw)
+        self._chk(self.L.zr_set_overlay_style(self.h, C.byref(st), C.sizeof(st)))
+        return st
+
+    def read_color_overlaid(self, s=1, highlight=False):
+        """zr_read_color_overlaid: the frame (highlighted underneath or not) with the list's lines over it, filtered by s (1..8) ->
+        (ceil(H / s), ceil(W / s), 4) uint8"""
+        out = np.zeros(self._scaled_shape(s), dtype=np.uint8)
+        self._chk(self.L.zr_read_color_overlaid(self.h, s, 1 if highlight else 0, _ptr(out), out.nbytes))
+        return out
+
+    def copy_frame_overlaid_async(self, s, highlight, color_dev):
+        """The frame enqueued last, overlaid and filtered by s -> a caller-owned device buffer (address, 4-byte aligned, ceil(W / s) *
+        ceil(H / s) * 4 bytes), in stream order, no host synchronisation."""
+        self._chk(self.L.zr_copy_frame_overlaid_async(self.h, s, 1 if highlight else 0, C.c_void_p(color_dev) if color_dev else None))
+
+    def set_frame_delta_overlay(self, on=True):
+        """The deliveries of changes deliver the overlaid frame (default off; only while delta is off, kept across set_frame_delta(False))."""
+        self._chk(self.L.zr_set_frame_delta_overlay(self.h, 1 if on else 0))
 
     def set_frame_delta_highlight(self, on=True):
         """The deliveries of changes deliver the highlighted frame (default off; only while delta is off, kept across set_frame_delta(False))."""
