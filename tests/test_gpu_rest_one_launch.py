@@ -17,7 +17,7 @@ import pytest
 
 from test_gpu_gbuffer_keep import ViewChecker
 from test_gpu_lighting_keep import LStage, _last, _pair
-from test_gpu_round2_keep import BOX, SPHERES, Checker, _lights, _same
+from test_gpu_round2_keep import BOX, SPHERES, Checker, _lights, _render, _same
 from zeldaengine_amd import abi, scenes
 
 pytestmark = pytest.mark.gpu
@@ -341,8 +341,9 @@ def test_other_modes(gpu_engine, mode):
 # ------------------------------------------------------------------------------------------------ 5. the next map
 
 def test_a_light_that_stops_and_moves_again(oracle_lib, gpu_engine):
-    """The directional light moves for two frames in the middle of a rest.  The map drawn after the rest goes into the copy a resting
-    frame's launch cleared; the frames are the twin's and the oracle's, the map included."""
+    """The directional light moves for two frames in the middle of a rest.  The map drawn after the rest goes into the copy that stood
+    cleared through the rest (by the lighting launch of the frame that drew the map before it); the frames are the twin's and the
+    oracle's, the map included."""
     st = RStage(16)
     g, twin = _pairs(st, gpu_engine)
     chk = Checker(oracle_lib)
@@ -356,3 +357,29 @@ def test_a_light_that_stops_and_moves_again(oracle_lib, gpu_engine):
     assert did[:6] == START + ["read"] * 3 and did[6] == "ignored" and did[7] == "ignored" and did[-1] == "read", did
     assert did.count("filled") == 2 and _by_arg(g) == did.count("read"), (did, g.light_keep())
     g.close(); twin.close()
+
+
+def test_the_map_drawn_after_a_rest_is_a_fresh_contexts(gpu_engine):
+    """96 x 64 (3 x 2 tiles, partial on both edges), a 64^2 map.  A map is drawn, the frame rests - a fill, then three frames of one
+    launch - then the directional light moves twice: each new map is rasterised, without a clear of its own, into the copy a lighting
+    launch cleared slice by slice (light_clear_next_slice) since it was last drawn into.  Map and colour are, byte for byte, those of a
+    fresh context given the final state directly, whose first map is cleared by a fill.  (The host hands the clear to the first
+    lighting pass after a draw: here k_lighting's, before and after the rest.  A frame that is one launch keeps its map, so
+    k_lighting_rest is handed a clear only where that pass could not take it; its call is the same helper.)"""
+    st = RStage(16, size=(96, 64))
+    st.SD = 64
+    g = st.renderer(gpu_engine)
+    did, maps = [], []
+    for i in range(8):
+        if i >= 6:
+            st.light = (6.0 - 0.5 * (i - 5), 0.5, 14.0)
+        _render(g, st, i)
+        did.append(_last(g)); maps.append(g.shadowmap().view(np.uint32).copy())
+    print(did, g.light_keep())
+    assert did == START + ["read"] * 3 + ["ignored"] * 2 and _by_arg(g) == 3, (did, g.light_keep())
+    assert (maps[7] != 0x3F800000).any() and not np.array_equal(maps[7], maps[6]) and not np.array_equal(maps[6], maps[5])
+    fresh = st.renderer(gpu_engine)
+    _render(fresh, st, 7)
+    assert np.array_equal(maps[7], fresh.shadowmap().view(np.uint32)), "%d texels of the map differ" % int((maps[7] != fresh.shadowmap().view(np.uint32)).sum())
+    assert g.color().tobytes() == fresh.color().tobytes(), "%d pixels differ" % int((g.color() != fresh.color()).any(axis=2).sum())
+    g.close(); fresh.close()

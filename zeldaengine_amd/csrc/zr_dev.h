@@ -271,6 +271,10 @@ __device__ __forceinline__ MeshletHead meshlet_head(const float* PVM, const ZrBi
     return H;
 }
 
+// What a colour leaves a shader as: the gamma every .frag applies (pow(c, 0.4545) per channel), the R8G8B8A8_UNORM word with alpha 1
+__device__ __forceinline__ zf3 gamma3(zf3 c) { return zr3(zr_pow(c.x, 0.4545f), zr_pow(c.y, 0.4545f), zr_pow(c.z, 0.4545f)); }
+__device__ __forceinline__ uint32_t pack_rgb8(zf3 c) { return zr_unorm(c.x, 255.0f) | zr_unorm(c.y, 255.0f) << 8 | zr_unorm(c.z, 255.0f) << 16 | 255u << 24; }
+
 // Multi-GPU ownership of a tile (zelda_render.h: zr_tile_owner)
 __device__ __forceinline__ uint32_t tile_owner(uint32_t tx, uint32_t ty, uint32_t world)
 {
@@ -391,28 +395,15 @@ __device__ __forceinline__ bool hiz_occluded(const ZrHiz& Z, uint2 pr, float zmi
 #ifndef ZR_LIGHT_KEPT_WAVES
 #define ZR_LIGHT_KEPT_WAVES 8
 #endif
-// What k_lighting_rest takes from the fill's records instead of the GBuffer, each switchable for A/B ("The resting
-// frame in one launch", has each measured on its own): the tile light list's box (0: every workgroup rebuilds it from its pixels'
-// scene_color and gD, wave reductions and an LDS merge, as k_lighting does), the empty pixels' GBuffer words left unfetched (0: every
-// pixel fetches its 24 bytes and finds itself empty again).  (Leaving the sRGB table out where no background is sampled was the third:
-// it showed in no counter and not in the frame rate, and was taken out again - App. A.)
-#ifndef ZR_REST_BOX_FROM_RECORDS
-#define ZR_REST_BOX_FROM_RECORDS 1
-#endif
-#ifndef ZR_REST_SKIP_EMPTY_LOADS
-#define ZR_REST_SKIP_EMPTY_LOADS 1
-#endif
-// How k_lighting_rest is set up, each switchable for A/B ("The resting frame's set-up", has each measured on its own).
-// RECORDS_ONE_TRIP: a part's eight records arrive as one vector load per lane behind one wait, the box by row reductions on the DPP
-// network (0: a scalar load and a wait per record).  LIGHT_WHOLE: a light's eight dwords are read before any of them is compared - the
-// tile list's test from an LDS copy staged with the tables, the light loop by one scalar load (0: a field at a time, each load behind
-// the comparison before it).  (A persistent grid, the empty pixel's colour kept across a workgroup's parts and the next part's records
-// requested ahead were measured with these two and showed nothing or lost: taken out again - App. A.)
+// What k_lighting_rest takes from the fill's records instead of the GBuffer: the tile light list's box (k_lighting rebuilds it from its
+// pixels' scene_color and gD, wave reductions and an LDS merge) and which pixels are empty, whose 24 GBuffer bytes it does not fetch.
+// How it is set up: a light's eight dwords are read before any of them is compared - the tile list's test from an LDS copy staged with
+// the tables, the light loop by one scalar load - and a part's eight records arrive as one vector load per lane behind one wait, the box
+// by row reductions on the DPP network.  That last one keeps its other arm (0: a scalar load and a wait per record, in a loop): the
+// control build of tests/test_kernel_table_rest_setup.py.  (DESIGN.md section 7 has each of these measured on its own; App. A what was
+// measured with them and taken out again.)
 #ifndef ZR_REST_RECORDS_ONE_TRIP
 #define ZR_REST_RECORDS_ONE_TRIP 1
-#endif
-#ifndef ZR_REST_LIGHT_WHOLE
-#define ZR_REST_LIGHT_WHOLE 1
 #endif
 #ifndef ZR_PIXELS_PER_THREAD
 #define ZR_PIXELS_PER_THREAD 1     // of k_resolve_gbuffer and k_lighting: 1, 2 or 4 (a tile is 1 024 pixels; workgroups per tile follow)

@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void k_forward(ZrPass P, ZrLightParams L, cons
                              (float)(uint32_t)view->LightsCount[3], 1.5f * 1.0f / (float)L.SD, cam,
                              BaseColor, Metallic, Roughness, Normal, AmbientOcclution.x, g.P0, Direct, Indirect, RefC, ShadowFactor);
         zf3 Final = (Direct + Indirect) + RefC;
-        Final = zr3(zr_pow(Final.x, 0.4545f), zr_pow(Final.y, 0.4545f), zr_pow(Final.z, 0.4545f));
+        Final = gamma3(Final);
         zf3 o;
         switch (L.debug_view) {
         case 1: o = BaseColor; break;
@@ -66,21 +66,9 @@ __global__ __launch_bounds__(256) void k_forward(ZrPass P, ZrLightParams L, cons
         case 8: o = zr3(ShadowFactor, ShadowFactor, ShadowFactor); break;
         default: o = Final * ShadowFactor; break;      // cases 0, 9 and default
         }
-        rgba = zr_unorm(o.x, 255.0f) | zr_unorm(o.y, 255.0f) << 8 | zr_unorm(o.z, 255.0f) << 16 | 255u << 24;
+        rgba = pack_rgb8(o);
     }
-    if (L.debug_view == 0u) {            // skydome, then the background quad at depth 1 (ZE:3681-3699)
-        const uint32_t ov = L.has_overlay ? G.overlay[p] : 0u;
-        if (ov) rgba = ov;
-        else if (L.bg_enabled && 1.0f <= G.depth[p]) {
-            const float u = ((float)px + 0.5f) / (float)L.W, v = ((float)py + 0.5f) / (float)L.H;
-            const float one4[4] = { 1.0f, 1.0f, 1.0f, 1.0f };
-            const zf4 bgc = tex_sample<2>(L.bg, one4, true, tl, u, v, 1.0f / (float)L.W, 0.0f, 0.0f, 1.0f / (float)L.H);
-            rgba = zr_unorm(zr_pow(bgc.x, 0.4545f), 255.0f) | zr_unorm(zr_pow(bgc.y, 0.4545f), 255.0f) << 8 |
-                   zr_unorm(zr_pow(bgc.z, 0.4545f), 255.0f) << 16 | 255u << 24;
-        }
-    }
-    if (L.packed_out) out[(size_t)tile_slot * TILE_PIX + i] = rgba;
-    else out[p] = rgba;
+    light_emit<true>(L, G, tl, out, rgba, px, py, p, tile_slot, i);      // skydome, then the background quad at depth 1
 }
 
 // ------------------------------------------------------------------------------------------------ launcher (C++ linkage, used by zr_frame_host.cpp)

@@ -365,11 +365,6 @@ static int frame_begin(zr_ctx* c, ZrEntry entry)
         // One launch: its uniforms travel as arguments.  No ring slot, no upload, no k_frame_begin - and F.view_uploaded stays as it is: the
         // next frame that reads F.view finds it stale and uploads.  The ring's slots paced the host to VIEW_RING frames ahead of the
         // device; without them that bound is kept by hand.
-#ifdef ZR_AB_REST_EV_END_EVERY      // A/B ONLY: the last recorded event at least VIEW_RING frames back
-        if (c->frame_no >= 2u * ZR_AB_REST_EV_END_EVERY + zr_ctx::VIEW_RING)
-            HIPCHK(c, hipEventSynchronize(c->ev_end[((c->frame_no - zr_ctx::VIEW_RING) / ZR_AB_REST_EV_END_EVERY * ZR_AB_REST_EV_END_EVERY) % zr_ctx::END_RING]));
-        return ZR_OK;
-#endif
         if (c->frame_no >= (uint64_t)zr_ctx::VIEW_RING) HIPCHK(c, hipEventSynchronize(c->ev_end[(c->frame_no - zr_ctx::VIEW_RING) % zr_ctx::END_RING]));
         return ZR_OK;
     }

@@ -11,8 +11,8 @@ __device__ __forceinline__ bool light_pixel_empty(uint32_t sc, uint32_t A, uint3
 }
 
 // The per-pixel steps k_lighting and k_lighting_rest share.  light_decode: the GBuffer's words as the shader's inputs (u8 / u10: the LDS
-// copies of c / 255 and c / 1023).  light_compose: FinalColor, gamma, the debug-view switch, packed RGBA8.  light_emit: what every path
-// ends with - the skydome / background drawn over the lit quad in view 0 (ZE:3681-3699), then the store (tl: tex_decode's LDS table).
+// copies of c / 255 and c / 1023).  light_compose: FinalColor, gamma, the debug-view switch, packed RGBA8.  (What every path
+// ends with, light_emit, is k_forward's too: zr_shade.h.)
 struct LitPixel { zf3 BaseColor, Normal, N, Pw; float Metallic, Roughness, AO, Mask; };
 __device__ __forceinline__ LitPixel light_decode(const float* u8, const float* u10, uint32_t sc, uint32_t A, uint32_t B, uint32_t Cc, uint2 D)
 {
@@ -32,11 +32,11 @@ __device__ __forceinline__ LitPixel light_decode(const float* u8, const float* u
 __device__ __forceinline__ uint32_t light_compose(const ZrLightParams& L, const LitPixel& q, zf3 Direct, zf3 Indirect, zf3 RefC, float ShadowFactor, int px, int py)
 {
     zf3 Final = ((Direct + Indirect) + RefC) * q.Mask;
-    Final = zr3(zr_pow(Final.x, 0.4545f), zr_pow(Final.y, 0.4545f), zr_pow(Final.z, 0.4545f));
+    Final = gamma3(Final);
     zf3 o;
     switch (L.debug_view) {
     case 0: o = Final; break;
-    case 1: o = zr3(zr_pow(q.BaseColor.x, 0.4545f), zr_pow(q.BaseColor.y, 0.4545f), zr_pow(q.BaseColor.z, 0.4545f)); break;
+    case 1: o = gamma3(q.BaseColor); break;
     case 2: o = zr3(q.Metallic, q.Metallic, q.Metallic); break;
     case 3: o = zr3(q.Roughness, q.Roughness, q.Roughness); break;
     case 4: o = q.Normal; break;
@@ -51,25 +51,15 @@ __device__ __forceinline__ uint32_t light_compose(const ZrLightParams& L, const 
     }
     default: o = Final * ShadowFactor; break;
     }
-    return zr_unorm(o.x, 255.0f) | zr_unorm(o.y, 255.0f) << 8 | zr_unorm(o.z, 255.0f) << 16 | 255u << 24;
+    return pack_rgb8(o);
 }
-template <bool BACKGROUND>
-__device__ __forceinline__ void light_emit(const ZrLightParams& L, const GBufferPtrs& G, const float* tl, uint32_t* __restrict__ out, uint32_t rgba,
-                                           int px, int py, size_t p, uint32_t tile_slot, uint32_t i)
+// The clear of the next frame's shadow pass (depth 1.0, ZE:3248), a slice per workgroup of the lighting launch: saves a launch
+template <int TB>
+__device__ __forceinline__ void light_clear_next_slice(const ZrLightParams& L)
 {
-    if (L.debug_view == 0u) {
-        const uint32_t ov = L.has_overlay ? G.overlay[p] : 0u;
-        if (ov) rgba = ov;
-        else if (BACKGROUND && L.bg_enabled && 1.0f <= G.depth[p]) {
-            const float u = ((float)px + 0.5f) / (float)L.W, v = ((float)py + 0.5f) / (float)L.H;
-            const float one4[4] = { 1.0f, 1.0f, 1.0f, 1.0f };
-            const zf4 bgc = tex_sample<2>(L.bg, one4, true, tl, u, v, 1.0f / (float)L.W, 0.0f, 0.0f, 1.0f / (float)L.H);
-            rgba = zr_unorm(zr_pow(bgc.x, 0.4545f), 255.0f) | zr_unorm(zr_pow(bgc.y, 0.4545f), 255.0f) << 8 |
-                   zr_unorm(zr_pow(bgc.z, 0.4545f), 255.0f) << 16 | 255u << 24;
-        }
-    }
-    if (L.packed_out) out[(size_t)tile_slot * TILE_PIX + i] = rgba;
-    else out[p] = rgba;
+    if (!L.clear_next) return;
+    const uint32_t per = (L.clear_n + gridDim.x - 1u) / gridDim.x, b = blockIdx.x * per;
+    for (uint32_t i = threadIdx.x; i < per && b + i < L.clear_n; i += (uint32_t)TB) L.clear_next[b + i] = 0x3F800000u;
 }
 
 // BaseLighting.frag:147-254 for every pixel of the owned tiles (the full-screen quad of ZE:3531-3540)
@@ -99,10 +89,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(MODE == ZR_L
     for (uint32_t i = threadIdx.x; i < 256u; i += (uint32_t)TB) { u8[i] = unorm_lut[i]; slut[i] = srgb_lut[i]; }
     for (uint32_t i = threadIdx.x; i < 1024u; i += (uint32_t)TB) u10[i] = unorm_lut[256u + i];
     __syncthreads();
-    if (L.clear_next) {      // the clear of the next frame's shadow pass (depth 1.0, ZE:3248), a slice per workgroup: saves a launch
-        const uint32_t per = (L.clear_n + gridDim.x - 1u) / gridDim.x, b = blockIdx.x * per;
-        for (uint32_t i = threadIdx.x; i < per && b + i < L.clear_n; i += (uint32_t)TB) L.clear_next[b + i] = 0x3F800000u;
-    }
+    light_clear_next_slice<TB>(L);
     const uint32_t tile = owned_tiles[tile_slot];
     const int tx0 = (int)(tile % L.tiles_x) * TILE, ty0 = (int)(tile / L.tiles_x) * TILE;
     const zf3 cam = zr3(view->CameraInfo[0], view->CameraInfo[1], view->CameraInfo[2]);
@@ -176,24 +163,8 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(MODE == ZR_L
         // A pixel nothing was drawn to holds the clear values of every target (ZE:3427-3433), so the shader computes the same
         // colour for all of them: it was computed once (zr_launch_lighting's one-pixel pre-launch of this very kernel).
         // (light_pixel_empty() spelt out: as a call behind the null test it changes the plain instantiations' code)
-        // what every path ends with: the skydome / background drawn over the lit quad in view 0 (ZE:3681-3699), then the store
-        auto emit = [&](uint32_t rgba) {
-            if (L.debug_view == 0u) {
-                const uint32_t ov = L.has_overlay ? G.overlay[p] : 0u;
-                if (ov) rgba = ov;
-                else if (BACKGROUND && L.bg_enabled && 1.0f <= G.depth[p]) {
-                    const float u = ((float)px + 0.5f) / (float)L.W, v = ((float)py + 0.5f) / (float)L.H;
-                    const float one4[4] = { 1.0f, 1.0f, 1.0f, 1.0f };
-                    const zf4 bgc = tex_sample<2>(L.bg, one4, true, tl, u, v, 1.0f / (float)L.W, 0.0f, 0.0f, 1.0f / (float)L.H);
-                    rgba = zr_unorm(zr_pow(bgc.x, 0.4545f), 255.0f) | zr_unorm(zr_pow(bgc.y, 0.4545f), 255.0f) << 8 |
-                           zr_unorm(zr_pow(bgc.z, 0.4545f), 255.0f) << 16 | 255u << 24;
-                }
-            }
-            if (L.packed_out) out[(size_t)tile_slot * TILE_PIX + i] = rgba;
-            else out[p] = rgba;
-        };
         if (L.empty_rgba != nullptr && sc == 0xFF000000u && A == 0u && B == 0xFF000000u && Cc == 0xFF000000u && D.x == 0u && D.y == 0x3C000000u) {
-            emit(*L.empty_rgba);
+            light_emit<BACKGROUND>(L, G, tl, out, *L.empty_rgba, px, py, p, tile_slot, i);
             continue;
         }
         const LitPixel q = light_decode(u8, u10, sc, A, B, Cc, D);
@@ -212,13 +183,13 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(MODE == ZR_L
         } else
             shade_surface<use_mask>(L, view, shadowmap, C, slut, lmask, nDir, nPoint, maxmips, dxy, cam, q.BaseColor, q.Metallic, q.Roughness, q.N, q.AO, q.Pw,
                                     Direct, Indirect, RefC, ShadowFactor);
-        emit(light_compose(L, q, Direct, Indirect, RefC, ShadowFactor, px, py));
+        light_emit<BACKGROUND>(L, G, tl, out, light_compose(L, q, Direct, Indirect, RefC, ShadowFactor, px, py), px, py, p, tile_slot, i);
     }
 }
 
 // The resting frame in one launch: what k_lighting<.., ZR_LIGHT_KEPT> computes, bit for bit, for a frame that uploads nothing and launches
 // nothing else ("The schedule").
-//  - The moving uniforms - camera position, light counts, the point lights - are the argument R (zr_shade.h, LightRef).
+//  - The moving uniforms - camera position, light counts, the point lights - are the argument R (zr_shade.h, ArgLight).
 //  - What the GBuffer decides was recorded by the fill (ZrRestRecord, one per wave): the workgroup merges its waves' boxes (min / max are
 //    exact: the tile's list is k_lighting's), each wave tests the lights against the box itself - a ballot, no LDS list, no barrier -
 //    and knows its empty pixels without fetching their 24 GBuffer bytes.
@@ -254,15 +225,14 @@ void k_lighting_rest(ZrLightParams L, ZrRestArgs R, const uint32_t* __restrict__
     static_assert((WAVES <= 8u || !ZR_REST_RECORDS_ONE_TRIP) && 1536u % (uint32_t)TB == 0u, "k_lighting_rest: a part's records are a dword per lane");
     __shared__ float tab[1536];          // k_lighting's tl (sRGB decode, then c / 255: tex_decode's layout) and u10, in one piece
     __shared__ uint32_t empty_px;
-    constexpr bool STAGED = LIGHT_LIST && ZR_REST_LIGHT_WHOLE;      // the light records' LDS copy, for the tile list's test (a lane per light)
-    __shared__ ZrRestLight lpt[STAGED ? ZR_REST_ARG_LIGHTS : 1];
+    __shared__ ZrRestLight lpt[LIGHT_LIST ? ZR_REST_ARG_LIGHTS : 1];      // the light records' LDS copy, for the tile list's test (a lane per light)
     float* const tl = tab; float* const u8 = tab + 256; float* const u10 = tab + 512;
     const uint32_t part = blockIdx.x % PARTS, tile_slot = blockIdx.x / PARTS;
     const uint32_t i = threadIdx.x + part * (uint32_t)TB;      // the thread's pixel among the tile's
     const uint32_t first_record = tile_slot * ZR_REST_RECORDS_PER_TILE + part * WAVES;
     uint32_t rec = 0u;
     {   // every load is issued before the first is waited for
-        constexpr uint32_t NT = 1536u / (uint32_t)TB, LW = ZR_REST_ARG_LIGHTS * (uint32_t)(sizeof(ZrRestLight) / 4u), NL = STAGED ? (LW + (uint32_t)TB - 1u) / (uint32_t)TB : 0u;
+        constexpr uint32_t NT = 1536u / (uint32_t)TB, LW = ZR_REST_ARG_LIGHTS * (uint32_t)(sizeof(ZrRestLight) / 4u), NL = LIGHT_LIST ? (LW + (uint32_t)TB - 1u) / (uint32_t)TB : 0u;
         float tv[NT], lv[NL ? NL : 1u];
 #pragma unroll
         for (uint32_t k = 0; k < NT; ++k) { const uint32_t j = threadIdx.x + k * (uint32_t)TB; tv[k] = j < 256u ? srgb_lut[j] : unorm_lut[j - 256u]; }
@@ -276,10 +246,7 @@ void k_lighting_rest(ZrLightParams L, ZrRestArgs R, const uint32_t* __restrict__
     }
     const uint32_t tile = owned_tiles[tile_slot];
     __syncthreads();
-    if (L.clear_next) {      // as in k_lighting
-        const uint32_t per = (L.clear_n + gridDim.x - 1u) / gridDim.x, b = blockIdx.x * per;
-        for (uint32_t k = threadIdx.x; k < per && b + k < L.clear_n; k += (uint32_t)TB) L.clear_next[b + k] = 0x3F800000u;
-    }
+    light_clear_next_slice<TB>(L);
     const int tx0 = (int)(tile % L.tiles_x) * TILE, ty0 = (int)(tile / L.tiles_x) * TILE;
     const zf3 cam = zr3(R.cam[0], R.cam[1], R.cam[2]);
 
@@ -289,7 +256,7 @@ void k_lighting_rest(ZrLightParams L, ZrRestArgs R, const uint32_t* __restrict__
     uint32_t first = NONE;
     unsigned long long mine = 0ull;
 #if ZR_REST_RECORDS_ONE_TRIP
-    if constexpr (LIGHT_LIST && ZR_REST_BOX_FROM_RECORDS) {
+    if constexpr (LIGHT_LIST) {
         // row_shr 1, 2, 4 fold exactly eight lanes into the last of them: lane 8 f + 7 holds field f over the records (min / max are exact
         // in any order; the fill's -inf / +inf for a non-finite position pass through as they did)
         int lo, hi;
@@ -310,11 +277,11 @@ void k_lighting_rest(ZrLightParams L, ZrRestArgs R, const uint32_t* __restrict__
         mine = (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 48 + (int)wave) |
                (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 56 + (int)wave) << 32;
     }
-#else      // (A/B: a record at a time, a scalar load and a wait each)
+#else      // (the control build of tests/test_kernel_table_rest_setup.py: a record at a time, a scalar load and a wait each)
     const ZrRestRecord* __restrict__ recs = (const ZrRestRecord*)(rest + ZR_REST_SLOT) + first_record;
 #pragma unroll 1      // (unrolled, the eight records' 64 scalar registers spill)
     for (uint32_t w = 0; w < WAVES; ++w) {
-        if constexpr (LIGHT_LIST && ZR_REST_BOX_FROM_RECORDS)
+        if constexpr (LIGHT_LIST)
             for (int a = 0; a < 3; ++a) { blo[a] = __builtin_fminf(blo[a], recs[w].lo[a]); bhi[a] = __builtin_fmaxf(bhi[a], recs[w].hi[a]); }
         const unsigned long long em = (unsigned long long)recs[w].empty[0] | (unsigned long long)recs[w].empty[1] << 32;
         if (em != 0ull && first == NONE) first = w * 64u + (uint32_t)__builtin_ctzll(em);
@@ -324,42 +291,16 @@ void k_lighting_rest(ZrLightParams L, ZrRestArgs R, const uint32_t* __restrict__
     const int px = tx0 + (int)(i & (TILE - 1)), py = ty0 + (int)(i / TILE);
     const bool inside = px < (int)L.W && py < (int)L.H;
     const size_t p = (size_t)py * L.W + (size_t)px;
-#if !ZR_REST_BOX_FROM_RECORDS      // (A/B: the box as k_lighting builds it)
-    __shared__ float bbp[LIGHT_LIST ? WAVES : 1][6];
-    if constexpr (LIGHT_LIST) {
-        float lo[3] = { __builtin_inff(), __builtin_inff(), __builtin_inff() }, hi[3] = { -__builtin_inff(), -__builtin_inff(), -__builtin_inff() };
-        bool odd = false;
-        if (inside && (G.scene_color[p] >> 24) != 0u) {
-            const uint2 D = G.gD[p];
-            const float q[3] = { f16_to_f32_hw(D.x & 0xFFFFu), f16_to_f32_hw(D.x >> 16), f16_to_f32_hw(D.y & 0xFFFFu) };
-            for (int a = 0; a < 3; ++a) { if (!(__builtin_fabsf(q[a]) <= 3.402823466e38f)) odd = true; lo[a] = q[a]; hi[a] = q[a]; }
-        }
-        for (int a = 0; a < 3; ++a) { lo[a] = wave_fmin(lo[a]); hi[a] = wave_fmax(hi[a]); }
-        const bool wodd = __ballot(odd) != 0ull;
-        if ((threadIdx.x & 63u) == 0u)
-            for (int a = 0; a < 3; ++a) { bbp[threadIdx.x >> 6][a] = wodd ? -__builtin_inff() : lo[a]; bbp[threadIdx.x >> 6][3 + a] = wodd ? __builtin_inff() : hi[a]; }
-        __syncthreads();
-        for (int a = 0; a < 3; ++a)
-            for (uint32_t w = 0; w < WAVES; ++w) { blo[a] = __builtin_fminf(blo[a], bbp[w][a]); bhi[a] = __builtin_fmaxf(bhi[a], bbp[w][3 + a]); }
-    }
-#endif
     unsigned long long amask = 0ull;      // the tile's light list (at most ZR_REST_ARG_LIGHTS = 64 lights: a lane each)
     if constexpr (LIGHT_LIST) {
         const uint32_t li = threadIdx.x & 63u;
-        const ZrRestLight* const pt = STAGED ? lpt : R.pt;
-        amask = __ballot(li < R.nPoint && light_listed(ArgLight{ &pt[li < R.nPoint ? li : 0u] }, blo, bhi));
+        amask = __ballot(li < R.nPoint && light_listed(ArgLight{ &lpt[li < R.nPoint ? li : 0u] }, blo, bhi));
     }
 
     const bool is_empty = ((mine >> (threadIdx.x & 63u)) & 1ull) != 0ull, owner = threadIdx.x == first;
-#if ZR_REST_SKIP_EMPTY_LOADS
     if (inside && (!is_empty || owner)) {
         const uint32_t sc = G.scene_color[p], A = G.gA[p], B = G.gB[p], Cc = G.gC[p];
         const uint2 D = G.gD[p];
-#else      // (A/B: every pixel fetches its words and finds itself empty again, as k_lighting does)
-    const uint32_t sc = inside ? G.scene_color[p] : 0u, A = inside ? G.gA[p] : 0u, B = inside ? G.gB[p] : 0u, Cc = inside ? G.gC[p] : 0u;
-    const uint2 D = inside ? G.gD[p] : make_uint2(0u, 0u);
-    if (inside && (!light_pixel_empty(sc, A, B, Cc, D) || owner)) {
-#endif
         const LitPixel q = light_decode(u8, u10, sc, A, B, Cc, D);
         const float4 ka = owner ? rest[0] : plane[p], kb = owner ? rest[1] : plane[(size_t)L.W * L.H + p];
         zf3 Direct = zr3(ka.x, ka.y, ka.z); const float ShadowFactor = ka.w; const zf3 RefC = zr3(kb.x, kb.y, kb.z);
@@ -448,7 +389,7 @@ __global__ __launch_bounds__(256) void k_gbuffer_vis(ZrLightParams L, const XkVi
         const zf3 N = zr_normalize(Normal);
         const zf3 Pw = zr3(g[16], g[17], g[18]);
         switch (cell) {
-        case 0: o = zr3(zr_pow(BaseColor.x, 0.4545f), zr_pow(BaseColor.y, 0.4545f), zr_pow(BaseColor.z, 0.4545f)); break;
+        case 0: o = gamma3(BaseColor); break;
         case 1: o = zr3(Metallic, Metallic, Metallic); break;
         case 2: o = zr3(Roughness, Roughness, Roughness); break;
         case 3: o = N; break;
@@ -457,16 +398,7 @@ __global__ __launch_bounds__(256) void k_gbuffer_vis(ZrLightParams L, const XkVi
         case 6: {
             const zf3 cam = zr3(view->CameraInfo[0], view->CameraInfo[1], view->CameraInfo[2]);
             const zf3 Vv = zr_normalize(cam - Pw), Nn = zr_normalize(N);
-            const float eta = 1.00f / 1.52f;
-            const float dNI = zr_dot(Nn, Vv);
-            const float kk = __builtin_fmaf(-(eta * eta), __builtin_fmaf(-dNI, dNI, 1.0f), 1.0f);
-            zf3 R;
-            if (kk < 0.0f) R = zr3(0.0f, 0.0f, 0.0f);
-            else {
-                const float q = __builtin_fmaf(eta, dNI, __builtin_sqrtf(kk));
-                R = zr3(__builtin_fmaf(eta, Vv.x, -(q * Nn.x)), __builtin_fmaf(eta, Vv.y, -(q * Nn.y)), __builtin_fmaf(eta, Vv.z, -(q * Nn.z)));
-            }
-            o = cube_sample(C, srgb_lut, L.cube_dim, (int)L.cube_levels, R, 0.0f) * 10.0f;
+            o = cube_sample(C, srgb_lut, L.cube_dim, (int)L.cube_levels, shade_refract(Nn, Vv), 0.0f) * 10.0f;
             break;
         }
         default: {
@@ -482,7 +414,7 @@ __global__ __launch_bounds__(256) void k_gbuffer_vis(ZrLightParams L, const XkVi
         }
         }
     }
-    out[(size_t)py * L.W + px] = zr_unorm(o.x, 255.0f) | zr_unorm(o.y, 255.0f) << 8 | zr_unorm(o.z, 255.0f) << 16 | 255u << 24;
+    out[(size_t)py * L.W + px] = pack_rgb8(o);
 }
 
 // ------------------------------------------------------------------------------------------------ launchers (C++ linkage, used by zr_frame_host.cpp)

@@ -38,6 +38,14 @@ static void light_key(const zr_ctx* c, zr_ctx::LightKey* K)
     for (int32_t i = 0; i < nd && i < XK_MAX_DIRECTIONAL_LIGHTS_NUM; ++i) K->dir[i] = c->view.DirectionalLights[i];
 }
 
+// Whether the point lights fit the one launch (k_lighting_rest): they travel in its argument, its records exist, and the view is not the
+// one k_gbuffer_vis finishes from XkView.
+static bool rest_launch_fits(const zr_ctx* c)
+{
+    const int32_t np = c->view.LightsCount[1];
+    return np >= 0 && np <= ZR_REST_ARG_LIGHTS && c->lk.rest != nullptr && c->debug_view != 9u;
+}
+
 void zr_light_facts(zr_ctx* c, ZrFrameFacts* f)
 {
     light_key(c, &c->lk.now);
@@ -47,8 +55,7 @@ void zr_light_facts(zr_ctx* c, ZrFrameFacts* f)
     f->light_empty_px = empty_px_on(c);
     // (the slot is made with the plane, by the first frame planned to fill: a context that has neither yet counts as one that gets it)
     f->light_slot = zr_lighting_rest_available() && (c->lk.rest != nullptr || (c->lk.plane == nullptr && !c->lk.alloc_failed));
-    const int32_t np = c->view.LightsCount[1];
-    f->light_by_arg = zr_lighting_rest_available() && np >= 0 && np <= ZR_REST_ARG_LIGHTS && f->light_empty_px && c->lk.rest != nullptr && c->debug_view != 9u;
+    f->light_by_arg = zr_lighting_rest_available() && f->light_empty_px && rest_launch_fits(c);
 }
 
 // The plane is made when the first frame is planned to fill it: 32 B x W x H (66 MB at 1080p, 265 MB at 2160p), through the extent's
@@ -121,7 +128,7 @@ int lighting_pass(zr_ctx* c)
     // (k_gbuffer_vis reads XkView), it shades every pixel itself and gets its uniforms here, on this stream.
     ZrLightMode mode = p.light_keep ? ZR_LIGHT_KEPT : p.light_fill ? ZR_LIGHT_FILL : ZR_LIGHT_PLAIN;
     const bool shortcut_as_planned = p.light_args ? empty_px_on(c) : c->facts.light_empty_px == c->empty_ready;
-    bool by_arg = p.light_args && c->lk.rest != nullptr && c->debug_view != 9u && c->view.LightsCount[1] >= 0 && c->view.LightsCount[1] <= ZR_REST_ARG_LIGHTS;
+    bool by_arg = p.light_args && rest_launch_fits(c);
     if (mode != ZR_LIGHT_PLAIN && (c->facts.cube_gen != c->cube_gen || !shortcut_as_planned || !c->lk.plane || c->shading == ZR_SHADING_FORWARD || (p.light_args && !by_arg))) {
         mode = ZR_LIGHT_PLAIN; by_arg = false; zr_history_forgotten(c, ZR_HIST_LIGHT_PLANE);
     }
@@ -140,9 +147,6 @@ int lighting_pass(zr_ctx* c)
             zr_launch_gbuffer_vis(L, F.view, F.G, shadow_buf(c), c->cube, c->d_lut, c->d_color, s);
     }
     TIMED(c, s, zr_ctx::EV_LIGHTING);
-#ifdef ZR_AB_REST_EV_END_EVERY      // A/B ONLY (whether the record's packet shows in a resting period): other frames' waits would go stale
-    if (!by_arg || c->frame_no % ZR_AB_REST_EV_END_EVERY == 0)
-#endif
     HIPCHK(c, hipEventRecord(c->ev_end[c->frame_no % zr_ctx::END_RING], s));      // this frame's GBuffer / shadow map / uniforms copies are free again
     HIPCHK(c, hipGetLastError());
     if (mode == ZR_LIGHT_FILL) { c->lk.key = c->lk.now; c->carry = zr_frame_carry(c->carry, c->facts, p, ZR_STAGE_LIGHTING); }

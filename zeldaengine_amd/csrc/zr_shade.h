@@ -2,6 +2,7 @@
 // shade_surface: the body BaseLighting.frag:174-221 and Base.frag:62-112 share word for word.
 #pragma once
 #include "zr_dev.h"
+#include "zr_texture.h"
 
 __device__ __forceinline__ int idx_clamp(float f, int hi) { f = __builtin_fminf(__builtin_fmaxf(f, 0.0f), (float)hi); return (int)f; }
 
@@ -124,9 +125,8 @@ struct ViewLight {
     __device__ __forceinline__ float dir(int k) const { return Lt->Direction[k]; }
     __device__ __forceinline__ float falloff() const { return Lt->Direction[3]; }
 };
-#if ZR_REST_LIGHT_WHOLE
-// (the record arrives whole: both halves are requested before anything is compared - one 32-byte scalar load at a wave-uniform address,
-// two 16-byte loads per lane otherwise - and the tests run on registers: no load waits behind the comparison before it)
+// (ArgLight's record arrives whole: both halves are requested before anything is compared - one 32-byte scalar load at a wave-uniform
+// address, two 16-byte loads per lane otherwise - and the tests run on registers: no load waits behind the comparison before it)
 struct ArgLight {
     float4_u c, p;
     __device__ __forceinline__ explicit ArgLight(const ZrRestLight* a) : c(*(const float4_u*)a->color), p(*(const float4_u*)a->pos_falloff) {}
@@ -135,22 +135,19 @@ struct ArgLight {
     __device__ __forceinline__ float dir(int) const { return 0.0f; }      // (never a directional light)
     __device__ __forceinline__ float falloff() const { return p[3]; }
 };
-#else      // (A/B: a field at a time)
-struct ArgLight {
-    const ZrRestLight* a;
-    __device__ __forceinline__ float pos(int k) const { return a->pos_falloff[k]; }
-    __device__ __forceinline__ float color(int k) const { return a->color[k]; }
-    __device__ __forceinline__ float dir(int) const { return 0.0f; }      // (never a directional light)
-    __device__ __forceinline__ float falloff() const { return a->pos_falloff[3]; }
-};
-#endif
+// Finite colour and intensity: what the skips of a light that adds exactly 0 need (0 * finite = 0), in the tile list's test and per pixel
+template <typename LIGHT>
+__device__ __forceinline__ bool light_finite(const LIGHT& Lt)
+{
+    return __builtin_fabsf(Lt.color(0)) <= 3.402823466e38f && __builtin_fabsf(Lt.color(1)) <= 3.402823466e38f &&
+           __builtin_fabsf(Lt.color(2)) <= 3.402823466e38f && __builtin_fabsf(Lt.color(3)) <= 3.402823466e38f;
+}
 // The tile light list's test (k_lighting): false when the light's sphere of influence misses the box [blo, bhi] of the tile's world
 // positions - every pixel's own exact test in shade_lights would then skip it.
 template <typename LIGHT>
 __device__ __forceinline__ bool light_listed(const LIGHT Lt, const float* blo, const float* bhi)
 {
-    const bool lfinite = __builtin_fabsf(Lt.color(0)) <= 3.402823466e38f && __builtin_fabsf(Lt.color(1)) <= 3.402823466e38f &&
-                         __builtin_fabsf(Lt.color(2)) <= 3.402823466e38f && __builtin_fabsf(Lt.color(3)) <= 3.402823466e38f;
+    const bool lfinite = light_finite(Lt);
     const float falloff = Lt.falloff();
     bool keep = true;
     if (lfinite && falloff > 0.0f) {
@@ -201,8 +198,7 @@ __device__ __forceinline__ void shade_lights(const ZrLightParams& L, const XkVie
         // needs finite colour * intensity (0 * finite = 0); the test is wave-uniform per light.  Where the BxDF is NaN or
         // infinite (D_GGX at roughness 0 with N.H = 1), or the attenuation is NaN (falloff 0) while N.L is 0, the shader's
         // literal sum would be NaN; the contract is the skip, and the CPU oracle states the same (row 8 of its CONTRACT.md).
-        const bool lfinite = __builtin_fabsf(Lt.color(0)) <= 3.402823466e38f && __builtin_fabsf(Lt.color(1)) <= 3.402823466e38f &&
-                             __builtin_fabsf(Lt.color(2)) <= 3.402823466e38f && __builtin_fabsf(Lt.color(3)) <= 3.402823466e38f;
+        const bool lfinite = light_finite(Lt);
         float att = 1.0f;
         zf3 Lv;
         if (!isdir) {
@@ -245,6 +241,17 @@ __device__ __forceinline__ void shade_lights(const ZrLightParams& L, const XkVie
             Direct = zr3(__builtin_fmaf(rad.x, bx.x, Direct.x), __builtin_fmaf(rad.y, bx.y, Direct.y), __builtin_fmaf(rad.z, bx.z, Direct.z));
         }
     }
+}
+
+// The reflection's lookup vector as the shaders spell it: refract(Vv, Nn, 1.00 / 1.52) of GLSL, 0 on total internal reflection
+__device__ __forceinline__ zf3 shade_refract(zf3 Nn, zf3 Vv)
+{
+    const float eta = 1.00f / 1.52f;
+    const float dNI = zr_dot(Nn, Vv);
+    const float kk = __builtin_fmaf(-(eta * eta), __builtin_fmaf(-dNI, dNI, 1.0f), 1.0f);
+    if (kk < 0.0f) return zr3(0.0f, 0.0f, 0.0f);
+    const float q = __builtin_fmaf(eta, dNI, __builtin_sqrtf(kk));
+    return zr3(__builtin_fmaf(eta, Vv.x, -(q * Nn.x)), __builtin_fmaf(eta, Vv.y, -(q * Nn.y)), __builtin_fmaf(eta, Vv.z, -(q * Nn.z)));
 }
 
 // The PCF factor, Direct, the image-based reflection.  LIGHTS 1: Direct over the directional lights only (shade_standing); 2: over all of
@@ -340,15 +347,7 @@ __device__ __forceinline__ void shade_body(const ZrLightParams& L, const XkView*
     const float ABx = __builtin_fmaf(-1.04f, a004, rz), ABy = __builtin_fmaf(1.04f, a004, rw);
     const float F90 = zr_saturate(50.0f * RSpec.y);
     const zf3 RBRDF = zr3(__builtin_fmaf(RSpec.x, ABx, F90 * ABy), __builtin_fmaf(RSpec.y, ABx, F90 * ABy), __builtin_fmaf(RSpec.z, ABx, F90 * ABy));
-    const float eta = 1.00f / 1.52f;
-    const float dNI = zr_dot(Nn, Vv);
-    const float kk = __builtin_fmaf(-(eta * eta), __builtin_fmaf(-dNI, dNI, 1.0f), 1.0f);
-    zf3 R;
-    if (kk < 0.0f) R = zr3(0.0f, 0.0f, 0.0f);
-    else {
-        const float q = __builtin_fmaf(eta, dNI, __builtin_sqrtf(kk));
-        R = zr3(__builtin_fmaf(eta, Vv.x, -(q * Nn.x)), __builtin_fmaf(eta, Vv.y, -(q * Nn.y)), __builtin_fmaf(eta, Vv.z, -(q * Nn.z)));
-    }
+    const zf3 R = shade_refract(Nn, Vv);
     // ComputeReflectionMipFromRoughness, SH/Common.glsl:191-198
     const float MIPS = (maxmips - 1.0f) - __builtin_fmaf(-1.2f, zr_log2(__builtin_fmaxf(Roughness, 0.001f)), 1.0f);
     const zf3 RL = (ZR_DIAG_SKIP(L.debug_skip) & 4u) ? zr3(0.0f, 0.0f, 0.0f) : cube_sample(C, slut, L.cube_dim, (int)L.cube_levels, R, MIPS) * 10.0f;
@@ -404,4 +403,25 @@ __device__ __forceinline__ void shade_surface(const ZrLightParams& L, const XkVi
 {
     shade_body<USE_MASK, 2>(L, view, shadowmap, C, slut, lmask, nDir, nPoint, maxmips, dxy, cam, BaseColor, Metallic, Roughness, N, AO, Pw, Direct, RefC, ShadowFactor);
     Indirect = shade_indirect(BaseColor, Metallic, AO, ShadowFactor);
+}
+
+// What every shaded pixel ends with, deferred or forward: the skydome / background drawn over it in view 0 (ZE:3681-3699; BACKGROUND: the
+// kernel was built for a frame that has the quad at depth 1), then the store, packed by tile or plain (tl: tex_decode's LDS table; i: the
+// pixel's place in its tile).
+template <bool BACKGROUND>
+__device__ __forceinline__ void light_emit(const ZrLightParams& L, const GBufferPtrs& G, const float* tl, uint32_t* __restrict__ out, uint32_t rgba,
+                                           int px, int py, size_t p, uint32_t tile_slot, uint32_t i)
+{
+    if (L.debug_view == 0u) {
+        const uint32_t ov = L.has_overlay ? G.overlay[p] : 0u;
+        if (ov) rgba = ov;
+        else if (BACKGROUND && L.bg_enabled && 1.0f <= G.depth[p]) {
+            const float u = ((float)px + 0.5f) / (float)L.W, v = ((float)py + 0.5f) / (float)L.H;
+            const float one4[4] = { 1.0f, 1.0f, 1.0f, 1.0f };
+            const zf4 bgc = tex_sample<2>(L.bg, one4, true, tl, u, v, 1.0f / (float)L.W, 0.0f, 0.0f, 1.0f / (float)L.H);
+            rgba = pack_rgb8(gamma3(zr3(bgc.x, bgc.y, bgc.z)));
+        }
+    }
+    if (L.packed_out) out[(size_t)tile_slot * TILE_PIX + i] = rgba;
+    else out[p] = rgba;
 }

@@ -165,8 +165,7 @@ __device__ __forceinline__ bool resolve_pixel(const ZrPass& P, const ZrObject* _
     if (O->flags & ZR_OBJ_SKY) {    // Skydome.frag: texture(skydomeSampler, uv).rgb, gamma - colour only, into the overlay plane: the pass
         // is drawn after the lighting quad (ZE:3681-3691) and no GBuffer attachment is written by it
         const zf4 sk = tex_sample<IMAGES>(O->tex[0], O->texc[0], true, lut, u0, v0, s1, t1, s2, t2);
-        G.overlay[p] = zr_unorm(zr_pow(sk.x, 0.4545f), 255.0f) | zr_unorm(zr_pow(sk.y, 0.4545f), 255.0f) << 8 |
-                       zr_unorm(zr_pow(sk.z, 0.4545f), 255.0f) << 16 | 255u << 24;
+        G.overlay[p] = pack_rgb8(gamma3(zr3(sk.x, sk.y, sk.z)));
         return false;
     }
     if (P.write_overlay) G.overlay[p] = 0u;
