@@ -337,7 +337,18 @@ int  zr_set_shading(zr_ctx* ctx, uint32_t mode);
  * A frame that loads them is ONE kernel launch when it has at most 64 point lights, its empty-pixel shortcut is on and its debug view
  * is not 9: what it reads of the uniforms travels as a kernel argument, the colour of the pixels nothing was drawn to - it moves with
  * the point lights - is computed inside the launch, and nothing is uploaded; the device copy of the uniforms is brought up to date by
- * the next frame that reads it (zr_light_keep::read_by_arg counts such frames).  The frame is the same bit for bit. */
+ * the next frame that reads it (zr_light_keep::read_by_arg counts such frames).  The frame is the same bit for bit.
+ * Such a launch also LEAVES AS THEY STAND the pixels no point light reaches.  It shades the frame in parts of half a tile (32 x 16
+ * pixels); a part whose world-space box - widened to the origin, where a pixel nothing was drawn to is shaded, if it holds one - lies
+ * outside every point light's radius would get, pixel for pixel, the colour the launch before wrote to the same addresses, and once a
+ * launch has written that colour the part returns after its set-up: no GBuffer, plane or frame byte of it moves.  The frame is the
+ * same bit for bit.  The library vouches for the bytes it leaves alone: whatever could change them or the colour they should hold -
+ * any lighting pass that is not such a launch, any difference in the launch's parameters (debug view, background, camera, directional
+ * lights, target, extent), zr_set_background, zr_resize - starts a new generation, in which every part is shaded once before it may
+ * stand again.  Contexts that never leave a pixel alone, and write every pixel of every resting frame as before: those with a
+ * caller-owned tiles buffer (zr_set_tiles_buffer) or the native multi-GPU host, every rank of a tile_world above 1, a context whose frame address zr_color_device_ptr has
+ * handed out (the caller may write through it; until a zr_resize voids it), and every context created with ZR_NO_REST_SETTLE in the
+ * environment.  zr_get_rest_settled counts the parts that stand. */
 int  zr_render(zr_ctx* ctx);
 /* The same frame in three stages (zr_render = all three, in this order), so that a multi-GPU host can place its
  * collectives between them: shadow pass | deferred-scene pass (cull, raster, GBuffer write) | deferred-lighting pass. */
@@ -372,6 +383,13 @@ typedef struct zr_light_keep {
                                   * no one-pixel launch, no event wait (at most 64 point lights, the empty-pixel shortcut on, not view 9) */
 } zr_light_keep;
 int  zr_get_light_keep(zr_ctx* ctx, zr_light_keep* out, size_t bytes);
+/* The parts of a resting frame's one launch (owned tiles x 2) and how many of them stand settled after the frame enqueued last (see
+ * zr_render): 0 unless that frame was such a launch on a context that settles.  Waits for the frame and reads the marks back: for tests
+ * and tools, nothing is counted per frame. */
+int  zr_get_rest_settled(zr_ctx* ctx, uint32_t* parts, uint32_t* settled);
+/* ... and which: standing[p] = 1 where part p (owned tile slot * 2 + the half of the tile, upper first) stands settled, else 0;
+ * bytes = zr_get_rest_settled's parts. */
+int  zr_get_rest_settled_parts(zr_ctx* ctx, uint8_t* standing, size_t bytes);
 
 /* --- read-back (there is no swapchain; replaces vkQueuePresentKHR ZE:2030) --- */
 int  zr_read_color(zr_ctx* ctx, uint8_t* rgba8, size_t bytes);         /* W*H*4 row-major, top-left origin */
@@ -674,7 +692,9 @@ int  zr_shadow_pack(zr_ctx* ctx, void* packed_dev, void* hip_stream);
 int  zr_shadow_unpack(zr_ctx* ctx, const void* gathered_dev, void* hip_stream);
 /* Caller-owned shadow map, float[shadow_dim^2] device memory (NULL = internal). */
 int  zr_set_shadow_buffer(zr_ctx* ctx, void* dev_ptr);
-/* Packed tile-major RGBA8 of the tiles this rank owns (device pointer, stable until zr_destroy or a zr_resize). */
+/* Packed tile-major RGBA8 of the tiles this rank owns.  The caller's to READ: on a single-rank ZR_FLAG_PACKED_TILES context a resting
+ * frame leaves the settled parts of it as they stand (see zr_render); a caller who writes tiles gives the library a buffer of its own
+ * (zr_set_tiles_buffer).  A device pointer, stable until zr_destroy or a zr_resize. */
 int  zr_tiles_device_buffer(zr_ctx* ctx, void** dev_ptr, size_t* bytes_per_rank);
 /* Caller-owned packed buffer for the following frames (same size; NULL = the internal one).  Two alternating buffers let
  * frame k's all-gather overlap frame k+1's rendering. */
@@ -682,7 +702,9 @@ int  zr_set_tiles_buffer(zr_ctx* ctx, void* dev_ptr);
 int  zr_read_tiles(zr_ctx* ctx, uint8_t* dst, size_t bytes);             /* host copy of that buffer (tests) */
 /* Scatter the all-gathered buffer (tile_world * bytes_per_rank, rank-major, device pointer) into the frame. */
 int  zr_composite(zr_ctx* ctx, const void* gathered_dev);
-int  zr_color_device_ptr(zr_ctx* ctx, void** dev_ptr);                  /* the row-major frame (stable until zr_destroy or a zr_resize) */
+/* The row-major frame.  The caller may write through it: from this call on the context's resting frames write every pixel again (see
+ * zr_render). */
+int  zr_color_device_ptr(zr_ctx* ctx, void** dev_ptr);                  /* (stable until zr_destroy or a zr_resize) */
 
 /* --- native multi-GPU host: one process per GPU, RCCL over xGMI called by the library itself (no Python, no torch in the frame) ---
  * rank 0 makes the id (zr_dist_unique_id: 128 bytes, ncclGetUniqueId) and hands it to the other ranks by any means; every rank then

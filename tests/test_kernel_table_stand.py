@@ -1,0 +1,96 @@
+"""k_lighting_stand (csrc/zr_lighting.hip), the resting frame's launch that leaves settled parts alone, from the compiler's own listing
+(hipcc -S for gfx950 with the library's flags, no GPU needed).
+
+  - Its two instantiations (background off / on; the tile list is always built, as a ballot) are compiled for eight waves per SIMD: at
+    most 64 VGPRs, no scratch.  Their rows - and nothing else - are recorded in profiles/r23_a_kernel_table_result.json (the other
+    kernels of the file are held to their own records by tests/test_kernel_table_rest.py and tests/test_kernel_table_rest_setup.py).
+  - The returning path - a part no point light reaches, whose mark stands - leaves ahead of the workgroup's first barrier: the branch
+    that takes it sits behind ONE trip of three vector loads (the part's records, the two halves of the lane's light record; the mark
+    is a scalar load beside them), ahead of every table load, and the block it goes to lies behind the kernel's last s_barrier and
+    runs to s_endpgm: no barrier is met on the way.  A part that shades updates its mark BEHIND the set-up's barrier - every wave of
+    the workgroup has read the mark by then, so none can see its own launch's store and return: no store sits ahead of it.  The same source built with -DZR_STAND_EARLY_EXIT=0 - everything in one trip, the
+    exit behind the set-up's barrier: the order that lost, DESIGN.md App. A - has the table loads ahead of that branch and exactly one
+    barrier, the set-up's, between the kernel's entry and it.
+"""
+import importlib.util
+import json
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "zeldaengine_amd", "csrc", "zr_lighting.hip")
+KERNEL = "k_lighting_stand<false, 512>"
+RECORD = os.path.join(ROOT, "profiles", "r23_a_kernel_table_result.json")
+
+
+def _kernel_table():
+    spec = importlib.util.spec_from_file_location("kernel_table", os.path.join(ROOT, "tools", "kernel_table.py"))
+    kt = importlib.util.module_from_spec(spec); spec.loader.exec_module(kt)
+    return kt
+
+
+def _listing(tmp, extra=()):
+    kt = _kernel_table()
+    out = os.path.join(str(tmp), "l%d.s" % len(extra))
+    subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-x", "hip"] + kt.FLAGS + list(extra) + ["-o", out, SRC], stderr=subprocess.DEVNULL)
+    text = open(out).read()
+    names = re.findall(r"^\s*\.amdhsa_kernel (\S+)", text, re.M)
+    plain = subprocess.run(["c++filt"] + names, capture_output=True, text=True).stdout.split("\n")
+    name = [n for n, d in zip(names, plain) if d.replace("void ", "").startswith(KERNEL)]
+    assert len(name) == 1, plain
+    body = text[text.index("\n" + name[0] + ":"):]
+    return body[:body.index(".Lfunc_end")].split("\n")
+
+
+def _exit_path(lines):
+    """-> (line of the branch that takes the returning path, line of its target's label, lines of every s_barrier, of s_endpgm)"""
+    op = [(n, l.split()) for n, l in enumerate(lines) if l.strip() and l.strip()[0] not in ";."]
+    barriers = [n for n, w in op if w[0] == "s_barrier"]
+    ends = [n for n, w in op if w[0] == "s_endpgm"]
+    assert len(ends) == 1, ends
+    label = {l.split(":")[0]: n for n, l in enumerate(lines) if re.match(r"\.LBB\S+:", l)}
+    # the conditional branches ahead of the kernel's last barrier (the empty colour's) whose target lies behind it: the returning path is
+    # the first such jump (the others, late in the kernel, are those of a part that shades and holds no empty pixel)
+    out = [(n, label[w[1]]) for n, w in op if w[0].startswith("s_cbranch") and n < barriers[-1] and label[w[1]] > barriers[-1]]
+    assert out and len(barriers) == 2, (out, barriers)
+    return out[0][0], out[0][1], barriers, ends[0]
+
+
+def _loads_before(lines, n):
+    return [l.split()[0] for l in lines[:n] if l.strip().startswith("global_load")]
+
+
+def test_eight_waves_no_scratch_and_the_rows_are_the_recorded_ones():
+    rows = _kernel_table().table(SRC, [])
+    want = json.load(open(RECORD))
+    stand = {k: v for k, v in rows.items() if k.startswith("k_lighting_stand<")}
+    assert sorted(stand) == ["k_lighting_stand<false, 512>", "k_lighting_stand<true, 512>"], sorted(rows)
+    for name, r in stand.items():
+        print(name, r)
+        assert r["scratch"] == 0 and r["vgpr"] <= 64, (name, r)
+    assert stand == {k: v for k, v in want.items() if k in stand}, stand
+
+
+def test_the_returning_path_meets_no_barrier(tmp_path):
+    lines = _listing(tmp_path)
+    branch, target, barriers, end = _exit_path(lines)
+    print("branch at", branch, "first barrier at", barriers[0], "target at", target, "last barrier at", barriers[-1], "end at", end)
+    assert branch < barriers[0] and barriers[-1] < target < end
+    loads = _loads_before(lines, branch)
+    assert sorted(loads) == ["global_load_dword", "global_load_dwordx4", "global_load_dwordx4"], loads      # records, the light's two halves
+    waits = [n for n, l in enumerate(lines[:branch]) if l.split()[:1] == ["s_waitcnt"] and "vmcnt" in l]
+    last_load = max(n for n, l in enumerate(lines[:branch]) if l.strip().startswith("global_load"))
+    assert waits and min(waits) > last_load, (waits, last_load)      # one trip: all three are requested before the first is waited for
+    stores = [n for n, l in enumerate(lines[:barriers[0]]) if l.strip().startswith("global_store")]
+    assert not stores, stores      # the mark's update (and every other store of a part that shades) lies behind the set-up's barrier
+
+
+def test_the_other_order_exits_behind_the_set_ups_barrier(tmp_path):
+    lines = _listing(tmp_path, ["-DZR_STAND_EARLY_EXIT=0"])
+    branch, target, barriers, end = _exit_path(lines)
+    print("branch at", branch, "barriers at", barriers, "target at", target)
+    assert len([b for b in barriers if b < branch]) == 1 and barriers[-1] < target < end
+    assert len(_loads_before(lines, branch)) == 6      # ... and the three of the tables

@@ -126,6 +126,11 @@ OVERLAY_SIGNATURES = {
     "zr_set_frame_delta_overlay": [vp_, C.c_int],
     "zr_frame_overlay": [vp_, vp_, u32_, u32_, vp_, vp_, u32_, C.POINTER(OverlayStyle), C.c_size_t, vp_, C.c_size_t],
 }
+# zr_get_rest_settled / zr_get_rest_settled_parts: the parts a resting frame's launch left as they stand (a count; a byte per part)
+REST_SETTLE_SIGNATURES = {
+    "zr_get_rest_settled": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+    "zr_get_rest_settled_parts": [C.c_void_p, C.c_void_p, C.c_size_t],
+}
 # the extent of a live context (include/zelda_render.h, "lifetime")
 EXTENT_SIGNATURES = {
     "zr_resize": [vp_, u32_, u32_],

@@ -129,6 +129,8 @@ static int create_device_state(zr_ctx* c)
         if ((e = getenv("ZR_LIGHT_LIST_MIN"))) c->env_light_list_min = atoi(e);
         c->env_no_empty_px = getenv("ZR_NO_EMPTY_PIXEL") != nullptr;
 #endif
+        // every build: the resting frame through k_lighting_rest, every pixel written (the control of k_lighting_stand's A/B, and its test's)
+        c->lk.settle_off = getenv("ZR_NO_REST_SETTLE") != nullptr;
     }
     HIPCHK(c, A.host(&c->h_view_ring, zr_ctx::VIEW_RING));
     for (auto& e : c->view_ev) HIPCHK(c, A.event(&e, hipEventDisableTiming));

@@ -18,6 +18,7 @@
 #include "zr_meshlet.h"
 #include "zr_overlay.h"
 #include "zr_scale.h"
+#include "zr_settle.h"
 #include "zr_types.h"
 #include "zr_world_doc.h"
 
@@ -380,8 +381,14 @@ struct zr_ctx {
     };
     // rest: the fill's slot and records (ZrRestRecord, zr_types.h), made with the plane in an allocation of their own (null: no room - the
     // context keeps, but never in one launch); by_arg: the passes that ran as the one launch (ZrFramePlan::light_args).
+    // Settling (zr_settle.h; k_lighting_stand): marks = a word per part of the one launch, made with the records and zero-filled (null: no
+    // room, or a build without the launch - the context rests through k_lighting_rest); settle / settle_key = the rule's state and the byte
+    // image of the last stand launch's key; settle_off: ZR_NO_REST_SETTLE was set at zr_create; handed_out: zr_color_device_ptr gave the
+    // frame's address to a caller who may write through it (until a resize voids it) - the library can no longer vouch for the target.
+    struct SettleKey { ZrLightParams L; float cam[3]; uint32_t nDir, n_owned, _pad; const void *out, *plane, *rest, *owned, *marks; };
     struct LightKeep { float4* plane = nullptr; float4* rest = nullptr; bool alloc_failed = false; LightKey now = {}, key = {}; uint32_t last = 0;
-                       uint64_t count[3] = { 0, 0, 0 }, by_arg = 0; } lk;
+                       uint64_t count[3] = { 0, 0, 0 }, by_arg = 0;
+                       uint32_t* marks = nullptr; ZrSettleState settle; SettleKey settle_key = {}; bool settle_off = false, handed_out = false; } lk;
     float lut[256]; float* d_lut = nullptr;
     float* d_unorm_lut = nullptr;        // [0..255] = c / 255, [256..1279] = c / 1023 (IEEE quotients, computed on the host)
 

@@ -315,6 +315,127 @@ void k_lighting_rest(ZrLightParams L, ZrRestArgs R, const uint32_t* __restrict__
         if (inside && is_empty) light_emit<BACKGROUND>(L, G, tl, out, empty_px, px, py, p, tile_slot, i);
     }
 }
+
+// The resting frame's launch on a context whose target only this library writes (zr_settle.h): k_lighting_rest, except that a part no
+// point light reaches leaves its pixels as they stand.  On a resting frame only the point lights move: a pixel none of them reaches gets
+// the colour the launch before wrote to the same address.  marks[part] == gen says that the part's pixels in the target ARE that colour -
+// written by a launch of this generation that found the part out of every light's reach - and the host moves gen on whenever the colour
+// or the target's bytes may have changed behind the kernel's back (gen 0: settling is off, nothing is skipped or marked).
+//  - reach = the tile list's ballot over the part's box.  The fill's box holds the world origin wherever the part holds an empty pixel
+//    (its GBuffer D is the clear value); it is widened to it once more here, since the empty colour's settling rests on it.  reach == 0
+//    exactly when every pixel's own test would skip every light; the same ballot is the light loop's list (always built: a lane a light).
+//  - The part's records, its mark and the lane's light record (from the argument block, two 16-byte loads) are one trip, and a settled
+//    part returns behind it: no table load, no LDS, no barrier.  A part that shades pays a second trip for the tables.
+//    (-DZR_STAND_EARLY_EXIT=0: all of it in one trip and the exit behind the barrier - the losing order, DESIGN.md App. A.)
+//  - settled is the same for every wave of the workgroup: each reads the same records, the same mark, the same lights.
+//  - A part that shades does what k_lighting_rest does, through the same steps; behind the set-up's barrier (every wave has read the mark
+//    by then) thread 0 sets the mark (reach == 0), takes it back (reach != 0 and it stood) or - the steady state - writes nothing.
+#ifndef ZR_STAND_EARLY_EXIT
+#define ZR_STAND_EARLY_EXIT 1
+#endif
+// (-DZR_STAND_WALK_LIST=0: the light loop walks every light instead of the ballot's list, as k_lighting_rest does below four lights -
+// the A/B of keeping that split; the ballot is built either way, the settle test needs it)
+#ifndef ZR_STAND_WALK_LIST
+#define ZR_STAND_WALK_LIST 1
+#endif
+template <bool BACKGROUND, int TB>
+__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(ZR_LIGHT_KEPT_WAVES, ZR_LIGHT_KEPT_WAVES)))
+void k_lighting_stand(ZrLightParams L, ZrRestArgs R, const uint32_t* __restrict__ owned_tiles, GBufferPtrs G, const float* __restrict__ srgb_lut,
+                      const float* __restrict__ unorm_lut, uint32_t* __restrict__ out, const float4* __restrict__ plane, const float4* __restrict__ rest,
+                      uint32_t* marks, uint32_t gen)
+{
+    static_assert(sizeof(ZrLightParams) + sizeof(ZrRestArgs) + sizeof(GBufferPtrs) + 8 * sizeof(void*) + 256 /* the hidden arguments */ < 4096,
+                  "k_lighting_stand: the argument block");
+    constexpr uint32_t PARTS = TILE_PIX / (uint32_t)TB, WAVES = (uint32_t)TB / 64u, NONE = 0xFFFFFFFFu, NT = 1536u / (uint32_t)TB;
+    static_assert(WAVES <= 8u && 1536u % (uint32_t)TB == 0u, "k_lighting_stand: a part's records are a dword per lane");
+    __shared__ float tab[1536];          // k_lighting_rest's
+    __shared__ uint32_t empty_px;
+    float* const tl = tab; float* const u8 = tab + 256; float* const u10 = tab + 512;
+    const uint32_t part = blockIdx.x % PARTS, tile_slot = blockIdx.x / PARTS;
+    const uint32_t i = threadIdx.x + part * (uint32_t)TB;      // the thread's pixel among the tile's
+    const uint32_t lane = threadIdx.x & 63u;
+#if !ZR_STAND_EARLY_EXIT
+    float tv[NT];
+#pragma unroll
+    for (uint32_t k = 0; k < NT; ++k) { const uint32_t j = threadIdx.x + k * (uint32_t)TB; tv[k] = j < 256u ? srgb_lut[j] : unorm_lut[j - 256u]; }
+#endif
+    const uint32_t rec = rest_records_fetch<WAVES>(rest, tile_slot * ZR_REST_RECORDS_PER_TILE + part * WAVES);
+    const ZrRestLight* const lights = R.pt;
+    const ArgLight mine_light{ &lights[lane < R.nPoint ? lane : 0u] };
+    const uint32_t mark = (uint32_t)__builtin_amdgcn_readfirstlane((int)marks[blockIdx.x]);
+#if !ZR_STAND_EARLY_EXIT
+#pragma unroll
+    for (uint32_t k = 0; k < NT; ++k) tab[threadIdx.x + k * (uint32_t)TB] = tv[k];
+    const uint32_t tile = owned_tiles[tile_slot];
+    __syncthreads();
+#endif
+
+    // the workgroup's records, as in k_lighting_rest: the part's box, the first empty pixel (thread number, or NONE), this wave's empty pixels
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    float blo[3], bhi[3];
+    {
+        int lo, hi;
+        { const int idn = 0x7F800000; int r = (int)rec; ZR_DPP_STEP(op_fmin, 0x111, 0xF); ZR_DPP_STEP(op_fmin, 0x112, 0xF); ZR_DPP_STEP(op_fmin, 0x114, 0xF); lo = r; }
+        { const int idn = (int)0xFF800000; int r = (int)rec; ZR_DPP_STEP(op_fmax, 0x111, 0xF); ZR_DPP_STEP(op_fmax, 0x112, 0xF); ZR_DPP_STEP(op_fmax, 0x114, 0xF); hi = r; }
+        for (int a = 0; a < 3; ++a) { blo[a] = zr_u2f((uint32_t)__builtin_amdgcn_readlane(lo, 8 * a + 7)); bhi[a] = zr_u2f((uint32_t)__builtin_amdgcn_readlane(hi, 8 * (3 + a) + 7)); }
+    }
+    uint32_t first = NONE;
+    const unsigned long long nz64 = __ballot(lane >= 48u && (lane & 7u) < WAVES && rec != 0u);
+    const uint32_t nz = ((uint32_t)(nz64 >> 48) | (uint32_t)(nz64 >> 56)) & 255u;      // bit w: record w holds an empty pixel
+    if (nz != 0u) {
+        const int w0 = __builtin_ctz(nz);
+        const unsigned long long em = (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 48 + w0) |
+                                      (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 56 + w0) << 32;
+        first = (uint32_t)w0 * 64u + (uint32_t)__builtin_ctzll(em);
+        for (int a = 0; a < 3; ++a) { blo[a] = __builtin_fminf(blo[a], 0.0f); bhi[a] = __builtin_fmaxf(bhi[a], 0.0f); }      // the empty pixel is shaded at Pw = 0
+    }
+    const unsigned long long mine = (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 48 + (int)wave) |
+                                    (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 56 + (int)wave) << 32;
+    const unsigned long long reach = __ballot(lane < R.nPoint && light_listed(mine_light, blo, bhi));
+    if (gen != 0u && reach == 0ull && mark == gen) { light_clear_next_slice<TB>(L); return; }
+
+#if ZR_STAND_EARLY_EXIT
+    {
+        float tv[NT];
+#pragma unroll
+        for (uint32_t k = 0; k < NT; ++k) { const uint32_t j = threadIdx.x + k * (uint32_t)TB; tv[k] = j < 256u ? srgb_lut[j] : unorm_lut[j - 256u]; }
+#pragma unroll
+        for (uint32_t k = 0; k < NT; ++k) tab[threadIdx.x + k * (uint32_t)TB] = tv[k];
+    }
+    const uint32_t tile = owned_tiles[tile_slot];
+    __syncthreads();
+#endif
+    // The mark's update: behind the set-up's barrier - every wave of the workgroup has read the mark and decided before it arrives there,
+    // so no wave can see this launch's own store and return from a part its siblings shade - and ahead of the pixel, so that nothing of
+    // it lives across the shading.  (The next launch is behind the store by stream order.)
+    if (gen != 0u && threadIdx.x == 0u) {
+        if (reach == 0ull) marks[blockIdx.x] = gen;            // (it did not stand, or the part had returned)
+        else if (mark == gen) marks[blockIdx.x] = 0u;
+    }
+    light_clear_next_slice<TB>(L);
+    const int tx0 = (int)(tile % L.tiles_x) * TILE, ty0 = (int)(tile / L.tiles_x) * TILE;
+    const zf3 cam = zr3(R.cam[0], R.cam[1], R.cam[2]);
+    const int px = tx0 + (int)(i & (TILE - 1)), py = ty0 + (int)(i / TILE);
+    const bool inside = px < (int)L.W && py < (int)L.H;
+    const size_t p = (size_t)py * L.W + (size_t)px;
+    const bool is_empty = ((mine >> lane) & 1ull) != 0ull, owner = threadIdx.x == first;
+    if (inside && (!is_empty || owner)) {
+        const uint32_t sc = G.scene_color[p], A = G.gA[p], B = G.gB[p], Cc = G.gC[p];
+        const uint2 D = G.gD[p];
+        const LitPixel q = light_decode(u8, u10, sc, A, B, Cc, D);
+        const float4 ka = owner ? rest[0] : plane[p], kb = owner ? rest[1] : plane[(size_t)L.W * L.H + p];
+        zf3 Direct = zr3(ka.x, ka.y, ka.z); const float ShadowFactor = ka.w; const zf3 RefC = zr3(kb.x, kb.y, kb.z);
+        shade_points_arg<ZR_STAND_WALK_LIST != 0>(L, R, reach, cam, q.BaseColor, q.Metallic, q.Roughness, q.N, q.Pw, Direct);
+        const zf3 Indirect = shade_indirect(q.BaseColor, q.Metallic, q.AO, ShadowFactor);
+        const uint32_t rgba = light_compose(L, q, Direct, Indirect, RefC, ShadowFactor, px, py);
+        if (owner) empty_px = rgba;
+        else light_emit<BACKGROUND>(L, G, tl, out, rgba, px, py, p, tile_slot, i);
+    }
+    if (first != NONE) {      // (the same for every thread of the workgroup: read from its records)
+        __syncthreads();
+        if (inside && is_empty) light_emit<BACKGROUND>(L, G, tl, out, empty_px, px, py, p, tile_slot, i);
+    }
+}
 #endif
 
 // GBufferVis (SH/BaseLighting.frag:42-145, SPEC_CONSTANTS 9).  Runs after k_lighting has written FinalColor everywhere: the
@@ -446,6 +567,19 @@ void zr_launch_lighting_rest(const ZrLightParams& L, const ZrRestArgs& R, const 
     if (L.light_list) { if (L.bg_enabled) ZR_LAUNCH_REST(true, true); else ZR_LAUNCH_REST(true, false); }
     else { if (L.bg_enabled) ZR_LAUNCH_REST(false, true); else ZR_LAUNCH_REST(false, false); }
 #undef ZR_LAUNCH_REST
+#endif
+}
+// marks: a word per workgroup of the launch (n_owned * zr_lighting_stand_parts()); gen: zr_settle.h's generation, 0 = off
+uint32_t zr_lighting_stand_parts() { return TILE_PIX / ZR_LIGHT_KEPT_TB; }
+void zr_launch_lighting_stand(const ZrLightParams& L, const ZrRestArgs& R, const uint32_t* owned_tiles, uint32_t n_owned, const GBufferPtrs& G,
+                              const float* lut, const float* unorm_lut, uint32_t* out, hipStream_t s, const float4* plane, const float4* rest,
+                              uint32_t* marks, uint32_t gen)
+{
+#if ZR_PIXELS_PER_THREAD == 1
+    if (n_owned == 0) return;
+    const dim3 grid(n_owned * (TILE_PIX / ZR_LIGHT_KEPT_TB)), block(ZR_LIGHT_KEPT_TB);
+    if (L.bg_enabled) hipLaunchKernelGGL((k_lighting_stand<true, ZR_LIGHT_KEPT_TB>), grid, block, 0, s, L, R, owned_tiles, G, lut, unorm_lut, out, plane, rest, marks, gen);
+    else hipLaunchKernelGGL((k_lighting_stand<false, ZR_LIGHT_KEPT_TB>), grid, block, 0, s, L, R, owned_tiles, G, lut, unorm_lut, out, plane, rest, marks, gen);
 #endif
 }
 void zr_launch_gbuffer_vis(const ZrLightParams& L, const XkView* view, const GBufferPtrs& G, const float* shadowmap, const CubeDesc& C,

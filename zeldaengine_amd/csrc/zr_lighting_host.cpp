@@ -73,6 +73,16 @@ bool zr_light_plane_make(zr_ctx* c)
         (void)hipGetLastError();
         c->lk.rest = nullptr;
     }
+    // ... and, with those, the marks of the parts a resting frame leaves as they stand (k_lighting_stand), zero-filled on the stream every
+    // lighting pass runs on; no room: the context rests through k_lighting_rest
+    if (c->lk.rest && !c->lk.marks && !c->lk.settle_off) {
+        const size_t n = (size_t)c->n_owned * zr_lighting_stand_parts();
+        if (c->ext.alloc(&c->lk.marks, n) != hipSuccess || hipMemsetAsync(c->lk.marks, 0, (n ? n : 1) * sizeof(uint32_t), c->stream) != hipSuccess) {
+            (void)hipGetLastError();
+            c->lk.marks = nullptr;
+        }
+        zr_settle_forget(&c->lk.settle);
+    }
     return c->lk.plane != nullptr;
 }
 
@@ -110,6 +120,23 @@ static void rest_args(const zr_ctx* c, ZrRestArgs* R)
     }
 }
 
+// Whether the library can vouch for every writer of the resting frame's target (zr_settle.h): its own buffer (a caller-owned tiles buffer
+// alternates, and the native multi-GPU host's with it), one rank (a rank of several hands its tiles to a collective: out of scope), its
+// address never handed to a caller who may write through it, the marks made, and ZR_NO_REST_SETTLE not set.
+static bool settle_allowed(const zr_ctx* c)
+{
+    return c->lk.marks != nullptr && !c->lk.settle_off && !c->lk.handed_out && c->d_tiles_ext == nullptr && c->dist == nullptr && c->cfg.tile_world <= 1u;
+}
+// The byte image of what a settled part's colour, and where it lies, depend on - everything the launch reads but the point lights and the
+// GBuffer pointers (resting frames alternate between the two copies, which camera_keep guarantees equal) - and the next map's clear.
+static void settle_key(const zr_ctx* c, const ZrLightParams& L, const ZrRestArgs& R, const uint32_t* out, zr_ctx::SettleKey* K)
+{
+    memset(K, 0, sizeof *K);
+    K->L = L; K->L.clear_next = nullptr; K->L.clear_n = 0;
+    memcpy(K->cam, R.cam, sizeof K->cam); K->nDir = R.nDir; K->n_owned = c->n_owned;
+    K->out = out; K->plane = c->lk.plane; K->rest = c->lk.rest; K->owned = c->d_owned; K->marks = c->lk.marks;
+}
+
 int lighting_pass(zr_ctx* c)
 {
     const ZrFramePlan& p = c->plan;
@@ -133,19 +160,29 @@ int lighting_pass(zr_ctx* c)
         mode = ZR_LIGHT_PLAIN; by_arg = false; zr_history_forgotten(c, ZR_HIST_LIGHT_PLANE);
     }
     if (p.light_args && !by_arg) { if (int rc = zr_frame_uniforms(c, s, false, false)) return rc; }
+    bool stood = false;      // the pass is a k_lighting_stand launch: every other pass writes the target behind that kernel's back
     if (c->shading == ZR_SHADING_FORWARD) {
         // Base.frag over the winners the resolve recorded, with this frame's camera block (frame_begin built it; the overlay fields play no part)
         if (L.clear_next) { zr_launch_fill32(L.clear_next, 0x3F800000u, L.clear_n, s); L.clear_next = nullptr; }
         zr_launch_forward(c->pass[1], L, F.view, c->d_objs, c->d_owned, c->n_owned, F.G, shadow_buf(c), c->cube, c->d_lut, c->d_unorm_lut, frame_out, s);
     } else if (by_arg) {
         ZrRestArgs R; rest_args(c, &R);
-        zr_launch_lighting_rest(L, R, c->d_owned, c->n_owned, F.G, c->d_lut, c->d_unorm_lut, frame_out, s, c->lk.plane, c->lk.rest);
+        if (settle_allowed(c)) {
+            zr_ctx::SettleKey K; settle_key(c, L, R, frame_out, &K);
+            ZrSettleFacts sf; sf.stand = true; sf.key_same = memcmp(&K, &c->lk.settle_key, sizeof K) == 0;
+            const ZrSettleStep step = zr_settle_step(c->lk.settle, sf);
+            if (step.wipe) HIPCHK(c, hipMemsetAsync(c->lk.marks, 0, (size_t)c->n_owned * zr_lighting_stand_parts() * sizeof(uint32_t), s));
+            zr_launch_lighting_stand(L, R, c->d_owned, c->n_owned, F.G, c->d_lut, c->d_unorm_lut, frame_out, s, c->lk.plane, c->lk.rest, c->lk.marks, step.gen);
+            c->lk.settle = step.next; c->lk.settle_key = K; stood = true;
+        } else
+            zr_launch_lighting_rest(L, R, c->d_owned, c->n_owned, F.G, c->d_lut, c->d_unorm_lut, frame_out, s, c->lk.plane, c->lk.rest);
         c->lk.by_arg++;
     } else {
         zr_launch_lighting(L, F.view, c->d_owned, c->n_owned, F.G, shadow_buf(c), c->cube, c->d_lut, c->d_unorm_lut, frame_out, s, mode, c->lk.plane, c->lk.rest);
         if (c->debug_view == 9u)        // GBufferVis mosaic over the lit frame (needs the whole GBuffer: single-rank contexts only)
             zr_launch_gbuffer_vis(L, F.view, F.G, shadow_buf(c), c->cube, c->d_lut, c->d_color, s);
     }
+    if (!stood) c->lk.settle = zr_settle_step(c->lk.settle, ZrSettleFacts{}).next;
     TIMED(c, s, zr_ctx::EV_LIGHTING);
     HIPCHK(c, hipEventRecord(c->ev_end[c->frame_no % zr_ctx::END_RING], s));      // this frame's GBuffer / shadow map / uniforms copies are free again
     HIPCHK(c, hipGetLastError());
@@ -171,6 +208,46 @@ extern "C" int zr_get_light_keep(zr_ctx* c, zr_light_keep* out, size_t bytes)
         k.plane_bytes = c->lk.plane ? 32ull * c->W * c->H : 0ull;
         k.read_by_arg = c->lk.by_arg;
         memcpy(out, &k, bytes < sizeof k ? bytes : sizeof k);
+        return ZR_OK;
+    });
+}
+
+// The marks of the frame enqueued last, read back (waits for that frame): out[part] = 1 where the part stands settled - its mark is the
+// current generation.  Nothing stands unless that frame was a stand launch.  For tests and tools: nothing is counted per frame.
+static int settled_parts(zr_ctx* c, std::vector<uint8_t>* out)
+{
+    out->assign((size_t)c->n_owned * zr_lighting_stand_parts(), 0);
+    if (!c->lk.marks || !c->lk.settle.standing || c->lk.settle.gen == 0u || out->empty()) return ZR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = zr_finish(c);
+    if (rc) return rc;
+    std::vector<uint32_t> m(out->size());
+    HIPCHK(c, hipMemcpy(m.data(), c->lk.marks, m.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < m.size(); ++k) (*out)[k] = m[k] == c->lk.settle.gen ? 1 : 0;
+    return ZR_OK;
+}
+extern "C" int zr_get_rest_settled(zr_ctx* c, uint32_t* parts, uint32_t* settled)
+{
+    if (!c || !parts || !settled) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        std::vector<uint8_t> st;
+        int rc = settled_parts(c, &st);
+        if (rc) return rc;
+        *parts = (uint32_t)st.size(); *settled = 0;
+        for (uint8_t v : st) *settled += v;
+        return ZR_OK;
+    });
+}
+// ... and which: a byte per part (owned tile slot * 2 + half), `bytes` of them = zr_get_rest_settled's parts
+extern "C" int zr_get_rest_settled_parts(zr_ctx* c, uint8_t* standing, size_t bytes)
+{
+    if (!c) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int {
+        ARGCHK(c, (standing || bytes == 0) && bytes == (size_t)c->n_owned * zr_lighting_stand_parts());
+        std::vector<uint8_t> st;
+        int rc = settled_parts(c, &st);
+        if (rc) return rc;
+        if (bytes) memcpy(standing, st.data(), bytes);
         return ZR_OK;
     });
 }

@@ -441,7 +441,7 @@ extern "C" int zr_set_tiles_buffer(zr_ctx* c, void* ptr)
 {
     if (!c) return ZR_ERR_ARG;
     return zr_guard(c, [&]() -> int {
-        c->d_tiles_ext = (uint32_t*)ptr;
+        c->d_tiles_ext = (uint32_t*)ptr; zr_settle_forget(&c->lk.settle);
         return ZR_OK;
     });
 }
@@ -464,8 +464,14 @@ extern "C" int zr_composite(zr_ctx* c, const void* gathered)
         ARGCHK(c, gathered != nullptr);
         HIPCHK(c, hipSetDevice(c->device));
         zr_launch_untile((const uint32_t*)gathered, c->d_tile_map, c->d_color, c->W, c->H, c->tiles_x, c->n_tiles, c->stream);
+        zr_settle_forget(&c->lk.settle);      // (it writes the frame: where that is a resting launch's target, nothing stands any more)
         HIPCHK(c, hipGetLastError());
         return ZR_OK;
     });
 }
-extern "C" int zr_color_device_ptr(zr_ctx* c, void** p) { if (!c || !p) return ZR_ERR_ARG; return zr_guard(c, [&]() -> int { *p = c->d_color; return ZR_OK; }); }
+// (the caller may write through it: from here on the context's resting frames write every pixel - zr_ctx::LightKeep::handed_out)
+extern "C" int zr_color_device_ptr(zr_ctx* c, void** p)
+{
+    if (!c || !p) return ZR_ERR_ARG;
+    return zr_guard(c, [&]() -> int { *p = c->d_color; c->lk.handed_out = true; zr_settle_forget(&c->lk.settle); return ZR_OK; });
+}

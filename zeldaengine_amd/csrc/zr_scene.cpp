@@ -644,6 +644,7 @@ extern "C" int zr_set_background(zr_ctx* c, const zr_image* tex)
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, zr_sync_all(c));
         c->bg_mem.release(); c->d_bg = nullptr; c->bg_set = false; c->world_named[2] = false;
+        zr_settle_forget(&c->lk.settle);      // (light_emit reads the image: a new one may lie where the old one lay)
         if (!tex || !tex->rgba8) return ZR_OK;
         int rc = upload_image(c, c->bg_mem, tex->rgba8, tex->width, tex->height, true, &c->d_bg, &c->bg_w, &c->bg_h, &c->bg_levels);
         if (rc) return rc;

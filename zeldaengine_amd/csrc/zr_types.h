@@ -363,6 +363,12 @@ void zr_launch_lighting(const ZrLightParams& L, const XkView* view, const uint32
 bool zr_lighting_rest_available();      // (a build with one pixel per thread)
 void zr_launch_lighting_rest(const ZrLightParams& L, const ZrRestArgs& R, const uint32_t* owned_tiles, uint32_t n_owned, const GBufferPtrs& G,
                              const float* lut, const float* unorm_lut, uint32_t* out, hipStream_t s, const float4* plane, const float4* rest);
+// ... with the parts no point light reaches left as they stand (k_lighting_stand; marks: a word per workgroup, n_owned *
+// zr_lighting_stand_parts() of them; gen: zr_settle.h's generation, 0 = nothing settles)
+uint32_t zr_lighting_stand_parts();
+void zr_launch_lighting_stand(const ZrLightParams& L, const ZrRestArgs& R, const uint32_t* owned_tiles, uint32_t n_owned, const GBufferPtrs& G,
+                              const float* lut, const float* unorm_lut, uint32_t* out, hipStream_t s, const float4* plane, const float4* rest,
+                              uint32_t* marks, uint32_t gen);
 // forward variant (SH/Base.frag): shades the winners recorded in G.prim with the camera pass's own parameter block
 void zr_launch_forward(const ZrPass& P, const ZrLightParams& L, const XkView* view, const ZrObject* objs, const uint32_t* owned_tiles, uint32_t n_owned,
                        const GBufferPtrs& G, const float* shadowmap, const CubeDesc& C, const float* lut, const float* unorm_lut, uint32_t* out, hipStream_t s);

@@ -65,6 +65,7 @@ def lib():
         **abi.HIGHLIGHT_SIGNATURES,
         **abi.OVERLAY_SIGNATURES,
         **abi.EXTENT_SIGNATURES,
+        **abi.REST_SETTLE_SIGNATURES,
         "zr_set_cubemap": [vp, vp, u32],
         "zr_set_skydome": [vp, vp, u32, vp, u32, vp],
         "zr_set_background": [vp, vp],
@@ -713,6 +714,19 @@ class Renderer:
         self._chk(self.L.zr_get_light_keep(self.h, C.byref(k), C.sizeof(k)))
         return {"last": ("ignored", "filled", "read")[int(k.last)], "ignored": int(k.ignored), "filled": int(k.filled), "read": int(k.read),
                 "plane_bytes": int(k.plane_bytes), "read_by_arg": int(k.read_by_arg)}
+
+    def rest_settled(self):
+        """(parts, settled) of the resting frame's one launch (zr_get_rest_settled): how many of its half-tile parts stand settled after
+        the frame enqueued last - no point light reaches them and their pixels are left as they are.  Waits for the frame."""
+        parts, settled = C.c_uint32(), C.c_uint32()
+        self._chk(self.L.zr_get_rest_settled(self.h, C.byref(parts), C.byref(settled)))
+        return int(parts.value), int(settled.value)
+
+    def rest_settled_parts(self):
+        """zr_get_rest_settled_parts: a uint8 per part of the resting frame's launch (owned tile slot * 2 + half), 1 where it stands settled"""
+        out = np.zeros(self.rest_settled()[0], dtype=np.uint8)
+        self._chk(self.L.zr_get_rest_settled_parts(self.h, _ptr(out) if out.size else None, out.nbytes))
+        return out
 
     # ---- read-back
     def color(self):
