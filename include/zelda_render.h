@@ -366,8 +366,18 @@ int  zr_finish(zr_ctx* ctx);                        /* stream sync + overflow ch
 int  zr_get_pass_times(zr_ctx* ctx, float ms[ZR_PASS_COUNT]);              /* last frame */
 int  zr_get_pass_times_avg(zr_ctx* ctx, uint32_t last_n, float ms[ZR_PASS_COUNT]);  /* mean of the last n <= 64 timed frames */
 int  zr_get_frame_latencies(zr_ctx* ctx, uint32_t n, float* ms);   /* begin-to-end GPU ms of the last n timed frames, newest first; returns the count */
-int  zr_get_frame_periods(zr_ctx* ctx, uint32_t n, float* ms);     /* GPU ms between the ends of consecutive frames, last n <= 511 frames, newest first; returns the count */
-int  zr_set_timing_interval(zr_ctx* ctx, uint32_t interval);  /* pass events on every interval-th frame (default 1, 0 = never) */
+/* GPU ms between the ends of consecutive frames, last n <= 511 frames, newest first; returns the count.  Inside a run of frames that
+ * are one launch (see zr_render) only every ZR_REST_END_EVERY-th frame records its end: every frame between two recorded ends reports
+ * the MEAN of its run - the time between the two records over the number of frames - and the sum over a window whose ends are
+ * recorded is exact.  ZR_REST_END_EVERY is read from the environment at zr_create (1 .. 64, default 8; 1: every frame records its end
+ * and reports its own period).  Such frames upload nothing, so nothing but these ends paces the host: it runs at most
+ * 4 + ZR_REST_END_EVERY - 1 frames ahead of the device (11 by default) before zr_render waits. */
+int  zr_get_frame_periods(zr_ctx* ctx, uint32_t n, float* ms);
+/* Pass events on every interval-th frame (default 1, 0 = never).  A record is a small bubble (about 5 us) on the stream it sits on, and
+ * a sampled frame records the events of the stages it runs, no others: 2 where the frame is one launch; 3 where it keeps camera pass and
+ * shadow map otherwise; 5 where it keeps the camera pass and draws the map; 10 where it draws its camera pass (12 where that frame's
+ * resolve runs on the host's stream).  The figures of a stage that did not run read exactly 0. */
+int  zr_set_timing_interval(zr_ctx* ctx, uint32_t interval);
 /* bytes = sizeof(zr_stats) of the caller's header: the library writes min(bytes, its own size), so an older host is never overrun. */
 int  zr_get_stats(zr_ctx* ctx, zr_stats* out, size_t bytes);
 /* What the lighting pass of the frame enqueued last did with the plane of standing terms (see zr_render), and how many frames of the

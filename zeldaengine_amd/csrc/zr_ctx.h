@@ -13,12 +13,14 @@
 #include <utility>
 #include <vector>
 
+#include "zr_frame_end.h"
 #include "zr_frame_plan.h"
 #include "zr_ids.h"
 #include "zr_meshlet.h"
 #include "zr_overlay.h"
 #include "zr_scale.h"
 #include "zr_settle.h"
+#include "zr_timed.h"
 #include "zr_types.h"
 #include "zr_world_doc.h"
 
@@ -282,7 +284,7 @@ struct zr_ctx {
     uint32_t env_skip = 0, env_skip_light = 0; int32_t env_light_list_min = 4; bool env_no_empty_px = false;
     // XkView upload: a pageable-memory hipMemcpyAsync blocks the host until the stream has drained (~0.3 ms per frame here),
     // so the uniforms go through a small ring of pinned copies, and only when they changed
-    static constexpr int VIEW_RING = 4;
+    static constexpr int VIEW_RING = kZrViewRing;
     XkView* h_view_ring = nullptr; hipEvent_t view_ev[VIEW_RING] = {}; uint32_t view_slot = 0; bool view_dirty = true;
     uint64_t view_version = 1;           // of the uniforms (FrameCopy::view_uploaded: the version a device copy holds)
     // Two frames in flight: the camera pipeline runs on `cam_s`, the shadow pipeline and the lighting pass on the host's `stream`;
@@ -297,10 +299,11 @@ struct zr_ctx {
     ZrPass resolve_P; uint32_t resolve_mark = 0;
     hipEvent_t ev_lane = nullptr;
     unsigned long long* d_sky_keys = nullptr; uint32_t sky_object = 0;      // the skydome's key plane (k_sky_tiles) and its draw record
-    // End of every frame's lighting pass, one (timing-enabled) event per frame in a ring: the next-but-one frame waits for it before
-    // it reuses the double-buffered copies, and consecutive ones give the per-frame GPU period (zr_get_frame_periods) for free.
-    static constexpr int END_RING = 512;
-    hipEvent_t ev_end[END_RING] = {};
+    // End of a frame's lighting pass, a ring of (timing-enabled) events: the next-but-one frame waits for it before it reuses the
+    // double-buffered copies, and consecutive ones give the GPU's frame period (zr_get_frame_periods).  Recorded by every frame but those
+    // inside a run of one-launch frames (zr_frame_end.h; `end`: which frame each slot holds, ZR_REST_END_EVERY): read through zr_frame_end().
+    static constexpr int END_RING = kZrEndRing;
+    hipEvent_t ev_end[END_RING] = {}; ZrEndState end;
     // The key buffer, one per frame parity like the FrameCopy resources (both hold the empty key between frames: the resolve resets what
     // it reads): frame N's rounds, Hi-Z build, k_mark and resolve use copy N & 1, so a resolve on the host's stream is not in the next
     // frame's way; the frame after that waits for ev_end[N] before it touches anything of this parity.
@@ -397,17 +400,11 @@ struct zr_ctx {
     ZrMesh sky_mesh; ZrSceneObject sky_obj; bool sky_set = false, sky_enabled = true;
     ZrOwn bg_mem; uint8_t* d_bg = nullptr; uint32_t bg_w = 0, bg_h = 0, bg_levels = 0; bool bg_set = false, bg_enabled = true;
 
-    // One timed frame's events, in the order of the frame graph (zr_get_pass_times_avg reads the passes off them): frame_begin; the shadow
-    // pipeline's bins filled, its map drawn; the camera pipeline's start, its cull, round 1, Hi-Z build + k_select, round 2 + skydome; the
-    // end of k_mark (camera lane) and the start of the resolve where that runs on the host's stream; the resolve's end, the lighting's.
-    enum TimedEvent { EV_BEGIN, EV_SHADOW_BINS, EV_SHADOW, EV_CULL, EV_ROUND1, EV_HIZ, EV_ROUND2, EV_RESOLVE, EV_LIGHTING, EV_CAMERA,
-                      EV_MARK, EV_HOST_RESOLVE, EV_COUNT };
+    // One timed frame: its events (zr_timed.h has their order in the frame graph) and the rule's result for the frame's plan - which of
+    // them this sample recorded, and what zr_get_pass_times_avg reads each figure from.
     struct TimedFrame {
         hipEvent_t ev[EV_COUNT] = {};
-        bool moved = false;              // the frame resolved on the host's stream: ZR_PASS_RESOLVE is k_mark's time + the resolve's
-        bool kept = false;               // the frame kept its shadow map: its shadow durations are 0, not the gap between two records
-        bool kept_round2 = false;        // the frame kept round 2 of the camera pass: ZR_PASS_HIZ and ZR_PASS_GBUFFER2 are 0 likewise
-        bool kept_camera = false;        // the frame kept its whole camera pass: ZR_PASS_CULL_CAMERA, _GBUFFER and _RESOLVE are 0 as well
+        ZrTimedRule rule;
     } timed[EV_RING];
     uint64_t frame_no = 0; bool rendered = false;
     uint32_t timing_interval = 1; bool timing_now = true; uint64_t sample_no = 0;    // pass events every interval-th frame
@@ -524,17 +521,22 @@ void zr_uniforms_reproject(zr_ctx* c);
 // packed buffer; map: tile -> owner * slots_per_rank + slot (k_untile); slots_per_rank: the most tiles any rank owns.
 struct ZrTilePartition { std::vector<uint32_t> owned, map; uint32_t slots_per_rank = 0; };
 ZrTilePartition zr_partition(uint32_t tiles_x, uint32_t tiles_y, uint32_t world, uint32_t rank);
+// zr_update.cpp: the end of frame f < frame_no - f's own event, or where f recorded none a later one of the host's stream, recorded now if
+// need be (zr_frame_end.h); and stream x made to wait for it.  Every reader of zr_ctx::ev_end but the one-launch frames' pacing goes through them.
+int zr_frame_end(zr_ctx* c, uint64_t f, hipEvent_t* ev);
+int zr_wait_frame_end(zr_ctx* c, hipStream_t x, uint64_t f);
 // zr_frame_host.cpp
 static inline hipStream_t lane_stream(const zr_ctx* c, ZrLane lane) { return lane == ZR_LANE_CAM ? c->cam_s : c->stream; }
-// A timed frame's events `which` on s, in order (an untimed frame: nothing).  A kept pass records its events all the same - no elapsed-time
-// call meets an unrecorded one - on the stream that lights the frame, and its sample counts as 0 (zr_get_pass_times_avg).
-static inline int timed_events(zr_ctx* c, hipStream_t s, std::initializer_list<int> which)
+// A timed frame's events `which`, in order, each on the stream the rule names - those of them the frame records (zr_timed.h: a stage the
+// plan does not run records nothing); an untimed frame: nothing.  The passes call it where they always did and decide nothing themselves.
+static inline int timed_events(zr_ctx* c, std::initializer_list<int> which)
 {
     if (zr_ctx::TimedFrame* const T = c->timed_frame())
-        for (int e : which) HIPCHK(c, hipEventRecord(T->ev[e], s));
+        for (int e : which)
+            if (T->rule.records(e)) HIPCHK(c, hipEventRecord(T->ev[e], lane_stream(c, T->rule.lane[e])));
     return ZR_OK;
 }
-#define TIMED(c, s, ...) do { if (int _rc = timed_events((c), (s), { __VA_ARGS__ })) return _rc; } while (0)
+#define TIMED(c, ...) do { if (int _rc = timed_events((c), { __VA_ARGS__ })) return _rc; } while (0)
 // The current shadow map: during a drawn shadow pass the one being drawn, else the one the last drawn pass left (zr_ctx::smap).
 static inline float* shadow_buf(zr_ctx* c) { return c->d_shadow_ext ? c->d_shadow_ext : c->fc[c->smap].shadow; }
 int set_winner_planes(zr_ctx* c, bool forward, bool id_capture, const char* what);      // zr_set_shading, zr_set_id_capture

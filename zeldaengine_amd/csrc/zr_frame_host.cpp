@@ -347,8 +347,8 @@ static int frame_begin(zr_ctx* c, ZrEntry entry)
     if (p.camera_list_rebuild) c->list_key[1] = c->pass[1];
 
     const hipStream_t s = lane_stream(c, p.head);
-    if (p.wait_end2) HIPCHK(c, hipStreamWaitEvent(s, c->ev_end[(c->frame_no - 2) % zr_ctx::END_RING], 0));
-    if (p.wait_end1) HIPCHK(c, hipStreamWaitEvent(s, c->ev_end[(c->frame_no - 1) % zr_ctx::END_RING], 0));
+    if (p.wait_end2 && (rc = zr_wait_frame_end(c, s, c->frame_no - 2)) != ZR_OK) return rc;
+    if (p.wait_end1 && (rc = zr_wait_frame_end(c, s, c->frame_no - 1)) != ZR_OK) return rc;
     if (p.wait_lane_end) { HIPCHK(c, hipEventRecord(c->ev_lane, c->cam_s)); HIPCHK(c, hipStreamWaitEvent(s, c->ev_lane, 0)); }
     if (p.wait_ids) HIPCHK(c, hipStreamWaitEvent(s, F.ev_ids, 0));
     if (p.ids_taken) F.ids_wait = false;
@@ -356,16 +356,14 @@ static int frame_begin(zr_ctx* c, ZrEntry entry)
     rc = zr_update_frame(c, s, c->fcur);
     if (rc) return rc;
     c->timing_now = c->timing_interval != 0 && c->frame_no % c->timing_interval == 0;     // pass events cost ~6 us of stream bubble each
-    if (zr_ctx::TimedFrame* T = c->timed_frame()) {
-        HIPCHK(c, hipEventRecord(T->ev[zr_ctx::EV_BEGIN], s));
-        T->kept = p.shadow_keep; T->kept_round2 = p.rounds == ZR_ROUNDS_TWO_KEPT; T->kept_camera = p.camera_keep; T->moved = p.resolve_deferred;
-    }
+    if (zr_ctx::TimedFrame* T = c->timed_frame()) T->rule = zr_timed_rule(p);      // what this sample records, and what its figures read
+    TIMED(c, EV_BEGIN);
     if (c->view_dirty) { c->view_version++; c->view_dirty = false; }
     if (p.light_args) {
         // One launch: its uniforms travel as arguments.  No ring slot, no upload, no k_frame_begin - and F.view_uploaded stays as it is: the
         // next frame that reads F.view finds it stale and uploads.  The ring's slots paced the host to VIEW_RING frames ahead of the
-        // device; without them that bound is kept by hand.
-        if (c->frame_no >= (uint64_t)zr_ctx::VIEW_RING) HIPCHK(c, hipEventSynchronize(c->ev_end[(c->frame_no - zr_ctx::VIEW_RING) % zr_ctx::END_RING]));
+        // device; without them that bound is kept by hand, on the newest end recorded that far back (zr_frame_end.h: VIEW_RING + every - 1).
+        if (const uint64_t pace = zr_end_pace(&c->end, c->frame_no)) HIPCHK(c, hipEventSynchronize(c->ev_end[(pace - 1) % zr_ctx::END_RING]));
         return ZR_OK;
     }
     return zr_frame_uniforms(c, s, p.reset_stats, p.reset_camera_list);
@@ -412,14 +410,14 @@ static int shadow_draw(zr_ctx* c, hipStream_t s)
     if (p.shadow_list_rebuild) zr_launch_fill32(&c->d_sstats->n_vis_work[0], 0u, 1, s);
     zr_launch_cull_box(P, c->d_objs, c->sc[0].work, c->sc[0].rects, Z, c->d_sstats, 0, s, nullptr, nullptr, p.shadow_list_reuse);
     shadow_bin(c, P, Z, s);
-    TIMED(c, s, zr_ctx::EV_SHADOW_BINS);
+    TIMED(c, EV_SHADOW_BINS);
     raster(c, P, s, p.shadow_occlusion ? 1 : 0);
     if (p.shadow_occlusion) {
         zr_launch_shadow_occlusion(P, c->d_objs, c->sc[0].work, c->sc[0].rects, c->d_spxrect, c->d_szmin, c->d_sflag, (const uint32_t*)shadow_buf(c),
                                    c->sb.bins, c->d_sstats, c->shadow_blocks * 8u, c->carry.sflag_history ? (uint32_t)((c->shadow_draws + c->sflag_turn) & 3u) : 4u, s);      // (a turn per pass DRAWN: kept frames test nothing)
         raster(c, P, s, 2);
     }
-    TIMED(c, s, zr_ctx::EV_SHADOW);
+    TIMED(c, EV_SHADOW);
     HIPCHK(c, hipGetLastError());
     c->shadow_draws++;
     c->smap_key = P; c->carry = zr_frame_carry(c->carry, c->facts, p, ZR_STAGE_SHADOW);
@@ -431,7 +429,7 @@ static int shadow_draw(zr_ctx* c, hipStream_t s)
 static int shadow_pass(zr_ctx* c)
 {
     const ZrFramePlan& p = c->plan;
-    if (p.shadow == ZR_LANE_NONE) TIMED(c, c->stream, zr_ctx::EV_SHADOW_BINS, zr_ctx::EV_SHADOW);
+    if (p.shadow == ZR_LANE_NONE) TIMED(c, EV_SHADOW_BINS, EV_SHADOW);
     else if (int rc = shadow_draw(c, lane_stream(c, p.shadow))) return rc;
     if (p.ev_join) HIPCHK(c, hipEventRecord(c->ev_join, c->stream));
     return ZR_OK;
@@ -444,12 +442,13 @@ static int gbuffer_pass(zr_ctx* c)
     const ZrFramePlan& p = c->plan;
     if (p.camera == ZR_LANE_NONE) {
         // The camera pass kept whole: both GBuffer copies, the key buffers, the visibility history and its stamp, the plan, the statistics
-        // block and cov_block stay as the last drawn frame left them, and nothing is launched.
-        TIMED(c, lane_stream(c, p.lighting), zr_ctx::EV_CAMERA, zr_ctx::EV_CULL, zr_ctx::EV_ROUND1, zr_ctx::EV_HIZ, zr_ctx::EV_ROUND2, zr_ctx::EV_RESOLVE);
+        // block and cov_block stay as the last drawn frame left them, and nothing is launched.  (Where the lighting's span starts:
+        // zr_timed.h - a frame that is one launch records nothing here.)
+        TIMED(c, EV_CAMERA, EV_CULL, EV_ROUND1, EV_HIZ, EV_ROUND2, EV_RESOLVE);
         return ZR_OK;
     }
     const hipStream_t s = lane_stream(c, p.camera);
-    TIMED(c, s, zr_ctx::EV_CAMERA);
+    TIMED(c, EV_CAMERA);
     ZrPass P = c->pass[1];             // (built by frame_begin; the overlay fields are set below)
     c->last_work[1] = P.n_work;
     // Two-pass occlusion culling (ZrFramePlan::rounds).  The depth test decides every pixel either way, so the frame does not depend on
@@ -466,20 +465,20 @@ static int gbuffer_pass(zr_ctx* c)
     c->last_two_round = p.rounds != ZR_ROUNDS_ONE;
     // (the cull kernel also compacts round 1's list - the survivors that owned a pixel last frame, or all of them)
     zr_launch_cull_box(P, c->d_objs, c->sc[1].work, c->sc[1].rects, Z, c->d_stats, 1, s, c->tb.sel, c->last_two_round ? Z.vis_prev : nullptr, p.camera_list_reuse);
-    TIMED(c, s, zr_ctx::EV_CULL);
+    TIMED(c, EV_CULL);
     if (c->last_two_round) Z.phase = 1;
     // Round 2 kept: round 1 - what owned a pixel of the previous frame - leaves this frame's key buffer, and round 1 is the frame's last
     // round: its k_tile draws the slow triangles.  The statistics and the plan are those of round 2 as last drawn (k_plan).
     tri_raster(c, P, Z, 1, s, p.rounds != ZR_ROUNDS_TWO, p.count_first);
-    TIMED(c, s, zr_ctx::EV_ROUND1);
+    TIMED(c, EV_ROUND1);
     if (p.rounds == ZR_ROUNDS_TWO) {
         zr_launch_hiz_build(c->d_vis[c->fcur], c->W, c->H, Z, c->d_hiz_regions, c->n_hiz_regions, s);
         Z.phase = 2;
         tri_select(c, P, Z, 2, s);
-        TIMED(c, s, zr_ctx::EV_HIZ);
+        TIMED(c, EV_HIZ);
         tri_raster(c, P, Z, 2, s, true, false);
     } else
-        TIMED(c, s, zr_ctx::EV_HIZ);
+        TIMED(c, EV_HIZ);
     {   // the overlay plane (skydome pixels) is written only when a skydome is drawn, or once more to wipe one that was
         const bool sky = c->sky_set && c->sky_enabled;
         P.write_overlay = (sky || c->fc[c->fcur].overlay_dirty) ? 1u : 0u;
@@ -487,16 +486,16 @@ static int gbuffer_pass(zr_ctx* c)
         P.sky_keys = nullptr; P.sky_object = c->sky_object;
         if (sky && c->d_sky_keys) { zr_launch_sky_tiles(P, c->d_objs, c->d_owned, c->n_owned, c->d_sky_keys, s); P.sky_keys = c->d_sky_keys; }
     }
-    TIMED(c, s, zr_ctx::EV_ROUND2);
+    TIMED(c, EV_ROUND2);
     if (p.resolve_deferred) {
         // the history now, the planes later: the host's stream waits for everything up to here and resolves from the same keys
         zr_launch_mark(P, c->d_objs, c->d_owned, c->n_owned, c->d_vis[c->fcur], Z.vis_now, s, vis_mark);
-        TIMED(c, s, zr_ctx::EV_MARK);
+        TIMED(c, EV_MARK);
         c->resolve_P = P; c->resolve_mark = vis_mark;
     } else {
         zr_launch_resolve_gbuffer(P, c->d_objs, c->d_owned, c->n_owned, c->d_vis[c->fcur], c->fc[c->fcur].G, c->d_lut, c->d_unorm_lut, Z.vis_now, c->d_stats, s, vis_mark);
         c->cov_block = c->d_stats; c->fc[c->fcur].g_gen = p.g_gen;
-        TIMED(c, s, zr_ctx::EV_RESOLVE);
+        TIMED(c, EV_RESOLVE);
     }
     if (p.ev_cam == ZR_EVCAM_BEHIND_MARK || p.ev_cam == ZR_EVCAM_BEHIND_RESOLVE) HIPCHK(c, hipEventRecord(c->ev_cam, s));
     c->vis_mark_prev = vis_mark; c->cam_draws++;
@@ -571,9 +570,9 @@ static int deferred_resolve(zr_ctx* c)
     const hipStream_t s = lane_stream(c, c->plan.resolve);
     ZrDevStats* const tally = c->d_rstats[c->fcur];
     zr_launch_fill32(tally->covered_part, 0u, 32, s);
-    TIMED(c, s, zr_ctx::EV_HOST_RESOLVE);
+    TIMED(c, EV_HOST_RESOLVE);
     zr_launch_resolve_gbuffer(c->resolve_P, c->d_objs, c->d_owned, c->n_owned, c->d_vis[c->fcur], c->fc[c->fcur].G, c->d_lut, c->d_unorm_lut, nullptr, tally, s, c->resolve_mark);
-    TIMED(c, s, zr_ctx::EV_RESOLVE);
+    TIMED(c, EV_RESOLVE);
     c->cov_block = tally; c->fc[c->fcur].g_gen = c->plan.g_gen;
     HIPCHK(c, hipGetLastError());
     return ZR_OK;

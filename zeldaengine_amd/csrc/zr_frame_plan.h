@@ -101,7 +101,7 @@ struct ZrFrameCarry {
 // What this frame does.  Made once (frame_begin), read by every stage, changed by none.
 struct ZrFramePlan {
     // per stage the lane, or NONE: the head (uniform upload + k_frame_begin), the shadow pipeline, the camera pipeline, the resolve,
-    // the one-pixel launch, the lighting pass.  (A kept pass records its timing events on the stream that lights the frame.)
+    // the one-pixel launch, the lighting pass.  (Which timing events a frame records, and where: zr_timed.h.)
     ZrLane head = ZR_LANE_HOST, shadow = ZR_LANE_HOST, camera = ZR_LANE_HOST, resolve = ZR_LANE_HOST, one_pixel = ZR_LANE_HOST, lighting = ZR_LANE_HOST;
     // shadow pass: the map of the last drawn pass is kept / occlusion culling is on / the work list is rebuilt / reused
     bool shadow_keep = false, shadow_occlusion = false, shadow_list_rebuild = false, shadow_list_reuse = false;

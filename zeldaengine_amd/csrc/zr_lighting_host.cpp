@@ -183,8 +183,12 @@ int lighting_pass(zr_ctx* c)
             zr_launch_gbuffer_vis(L, F.view, F.G, shadow_buf(c), c->cube, c->d_lut, c->d_color, s);
     }
     if (!stood) c->lk.settle = zr_settle_step(c->lk.settle, ZrSettleFacts{}).next;
-    TIMED(c, s, zr_ctx::EV_LIGHTING);
-    HIPCHK(c, hipEventRecord(c->ev_end[c->frame_no % zr_ctx::END_RING], s));      // this frame's GBuffer / shadow map / uniforms copies are free again
+    TIMED(c, EV_LIGHTING);
+    // This frame's GBuffer / shadow map / uniforms copies are free again.  Inside a run of one-launch frames only every few frames say so:
+    // whoever asks for another's end is handed a later one (zr_frame_end.h).
+    const bool end_recorded = zr_end_records(c->end, c->frame_no, p.light_args);
+    if (end_recorded) HIPCHK(c, hipEventRecord(c->ev_end[c->frame_no % zr_ctx::END_RING], s));
+    zr_end_enqueued(&c->end, c->frame_no, p.light_args, end_recorded);
     HIPCHK(c, hipGetLastError());
     if (mode == ZR_LIGHT_FILL) { c->lk.key = c->lk.now; c->carry = zr_frame_carry(c->carry, c->facts, p, ZR_STAGE_LIGHTING); }
     c->lk.last = (uint32_t)mode; c->lk.count[mode]++;

@@ -27,6 +27,9 @@ extern "C" int zr_finish(zr_ctx* c)
     if (!c) return ZR_ERR_ARG;
     return zr_guard(c, [&]() -> int {
         HIPCHK(c, hipSetDevice(c->device));
+        // (a newest frame that recorded no end of its own gets it here, ahead of the wait: the periods' last run ends where the GPU did)
+        hipEvent_t end;
+        if (c->frame_no >= 1) { if (int rc = zr_frame_end(c, c->frame_no - 1, &end)) return rc; }
         HIPCHK(c, zr_sync_all(c));
         if (c->rendered) {
             HIPCHK(c, hipMemcpy(&c->h_stats, c->d_stats, sizeof(ZrDevStats), hipMemcpyDeviceToHost));
@@ -54,6 +57,24 @@ extern "C" int zr_finish(zr_ctx* c)
     });
 }
 
+static_assert(ZRT_CULL_SHADOW == (int)ZR_PASS_CULL_SHADOW && ZRT_SHADOW == (int)ZR_PASS_SHADOW && ZRT_CULL_CAMERA == (int)ZR_PASS_CULL_CAMERA &&
+              ZRT_GBUFFER == (int)ZR_PASS_GBUFFER && ZRT_HIZ == (int)ZR_PASS_HIZ && ZRT_GBUFFER2 == (int)ZR_PASS_GBUFFER2 && ZRT_RESOLVE == (int)ZR_PASS_RESOLVE &&
+              ZRT_LIGHTING == (int)ZR_PASS_LIGHTING && ZRT_COMPOSITE == (int)ZR_PASS_COMPOSITE && ZRT_TOTAL == (int)ZR_PASS_TOTAL && ZRT_COUNT == (int)ZR_PASS_COUNT,
+              "zr_timed.h: the figures are zelda_render.h's ZR_PASS_*");
+// One figure of one sample, by the rule stored with it (zr_timed.h): the sum of its spans, each between two events this sample recorded, or
+// exactly 0 for a stage the frame did not run - an event of another sample, still in the ring's slot, is never asked about.
+static int timed_figure(zr_ctx* c, const zr_ctx::TimedFrame& T, int figure, float* ms)
+{
+    const ZrTimedReading& g = T.rule.fig[figure];
+    *ms = 0.0f;
+    for (int i = 0; i < g.n; ++i) {
+        float t = 0.0f;
+        HIPCHK(c, hipEventElapsedTime(&t, T.ev[g.span[i].from], T.ev[g.span[i].to]));
+        *ms += t;
+    }
+    return ZR_OK;
+}
+
 // Mean per-pass GPU time over the last `last_n` frames (<= EV_RING), from hipEvents recorded on the render stream.
 extern "C" int zr_get_pass_times_avg(zr_ctx* c, uint32_t last_n, float ms[ZR_PASS_COUNT])
 {
@@ -69,28 +90,11 @@ extern "C" int zr_get_pass_times_avg(zr_ctx* c, uint32_t last_n, float ms[ZR_PAS
         double acc[ZR_PASS_COUNT] = { 0 };
         for (uint32_t k = 0; k < last_n; ++k) {
             const zr_ctx::TimedFrame& T = c->timed[(c->sample_no - 1 - k) % zr_ctx::EV_RING];
-            const hipEvent_t* ev = T.ev;
-            float t[ZR_PASS_COUNT] = { 0 };
-            (void)hipEventElapsedTime(&t[ZR_PASS_CULL_SHADOW], ev[zr_ctx::EV_BEGIN], ev[zr_ctx::EV_SHADOW_BINS]);
-            (void)hipEventElapsedTime(&t[ZR_PASS_SHADOW], ev[zr_ctx::EV_SHADOW_BINS], ev[zr_ctx::EV_SHADOW]);
-            (void)hipEventElapsedTime(&t[ZR_PASS_CULL_CAMERA], ev[zr_ctx::EV_CAMERA], ev[zr_ctx::EV_CULL]);
-            (void)hipEventElapsedTime(&t[ZR_PASS_GBUFFER], ev[zr_ctx::EV_CULL], ev[zr_ctx::EV_ROUND1]);
-            (void)hipEventElapsedTime(&t[ZR_PASS_HIZ], ev[zr_ctx::EV_ROUND1], ev[zr_ctx::EV_HIZ]);
-            (void)hipEventElapsedTime(&t[ZR_PASS_GBUFFER2], ev[zr_ctx::EV_HIZ], ev[zr_ctx::EV_ROUND2]);
-            if (T.moved) {
-                // the resolve on the host's stream: k_mark on the camera lane + the resolve itself, each between two records on the stream
-                // it ran on (never across the wait between the lanes)
-                float tm = 0.0f, tr = 0.0f;
-                (void)hipEventElapsedTime(&tm, ev[zr_ctx::EV_ROUND2], ev[zr_ctx::EV_MARK]); (void)hipEventElapsedTime(&tr, ev[zr_ctx::EV_HOST_RESOLVE], ev[zr_ctx::EV_RESOLVE]);
-                t[ZR_PASS_RESOLVE] = tm + tr;
-            } else (void)hipEventElapsedTime(&t[ZR_PASS_RESOLVE], ev[zr_ctx::EV_ROUND2], ev[zr_ctx::EV_RESOLVE]);
-            (void)hipEventElapsedTime(&t[ZR_PASS_LIGHTING], ev[zr_ctx::EV_RESOLVE], ev[zr_ctx::EV_LIGHTING]);
-            (void)hipEventElapsedTime(&t[ZR_PASS_TOTAL], ev[zr_ctx::EV_BEGIN], ev[zr_ctx::EV_LIGHTING]);
-            // (a frame that kept its shadow map ran no shadow pipeline: exactly 0, not the gap between two back-to-back records)
-            if (T.kept) t[ZR_PASS_CULL_SHADOW] = t[ZR_PASS_SHADOW] = 0.0f;
-            if (T.kept_round2) t[ZR_PASS_HIZ] = t[ZR_PASS_GBUFFER2] = 0.0f;      // (likewise: no Hi-Z build, no k_select, no second round)
-            if (T.kept_camera) t[ZR_PASS_CULL_CAMERA] = t[ZR_PASS_GBUFFER] = t[ZR_PASS_RESOLVE] = 0.0f;      // (the whole camera pass kept: nothing of it ran)
-            for (int i = 0; i < ZR_PASS_COUNT; ++i) acc[i] += t[i];
+            for (int i = 0; i < ZR_PASS_COUNT; ++i) {
+                float t = 0.0f;
+                if (int rc2 = timed_figure(c, T, i, &t)) return rc2;
+                acc[i] += t;
+            }
         }
         for (int i = 0; i < ZR_PASS_COUNT; ++i) ms[i] = (float)(acc[i] / last_n);
         return ZR_OK;
@@ -109,17 +113,16 @@ extern "C" int zr_get_frame_latencies(zr_ctx* c, uint32_t n, float* ms)
         if (rc && rc != ZR_ERR_OVERFLOW) return rc;
         if (n > (uint32_t)zr_ctx::EV_RING) n = zr_ctx::EV_RING;
         if ((uint64_t)n > c->sample_no) n = (uint32_t)c->sample_no;
-        for (uint32_t k = 0; k < n; ++k) {
-            const hipEvent_t* ev = c->timed[(c->sample_no - 1 - k) % zr_ctx::EV_RING].ev;
-            ms[k] = 0.0f;
-            (void)hipEventElapsedTime(&ms[k], ev[zr_ctx::EV_BEGIN], ev[zr_ctx::EV_LIGHTING]);
-        }
+        for (uint32_t k = 0; k < n; ++k)
+            if (int rc2 = timed_figure(c, c->timed[(c->sample_no - 1 - k) % zr_ctx::EV_RING], ZR_PASS_TOTAL, &ms[k])) return rc2;
         return (int)n;
     });
 }
 
 // GPU time between the ends of consecutive frames (the frame period the GPU sustained) for the last `n` frames, newest first;
 // returns how many were written (<= END_RING - 1).  Costs nothing extra: the end-of-frame event exists for the double buffering.
+// Frames inside a run of one-launch frames record no end of their own (zr_frame_end.h): every frame between two recorded ends reports
+// the mean of its run, and the sum over a window whose ends are recorded is exact.
 extern "C" int zr_get_frame_periods(zr_ctx* c, uint32_t n, float* ms)
 {
     if (!c || !ms) return ZR_ERR_ARG;
@@ -131,16 +134,19 @@ extern "C" int zr_get_frame_periods(zr_ctx* c, uint32_t n, float* ms)
         if (n > (uint32_t)zr_ctx::END_RING - 1u) n = zr_ctx::END_RING - 1;
         if ((uint64_t)n > have) n = (uint32_t)have;
         for (uint32_t k = 0; k < n; ++k) {
-            const uint64_t f = c->frame_no - 1 - k;
-            ms[k] = 0.0f;
-            (void)hipEventElapsedTime(&ms[k], c->ev_end[(f - 1) % zr_ctx::END_RING], c->ev_end[f % zr_ctx::END_RING]);
+            uint64_t a = 0, b = 0;
+            if (!zr_end_run(c->end, c->frame_no - 1 - k, &a, &b)) return (int)k;      // (its run reaches out of the ring: the frames so far)
+            float run = 0.0f;
+            HIPCHK(c, hipEventElapsedTime(&run, c->ev_end[a % zr_ctx::END_RING], c->ev_end[b % zr_ctx::END_RING]));
+            ms[k] = run / (float)(b - a);
         }
         return (int)n;
     });
 }
 
 // Per-pass hipEvents are recorded on every interval-th frame (default 1 = every frame, 0 = never).  Each record is a small
-// bubble on the render stream (~6 us on MI355X, six per frame), so a host that only wants throughput samples sparsely.
+// bubble on the stream it sits on (~6 us on MI355X; a frame records the events of the stages it runs: zr_timed.h), so a host that only
+// wants throughput samples sparsely.
 extern "C" int zr_set_timing_interval(zr_ctx* c, uint32_t interval)
 {
     if (!c) return ZR_ERR_ARG;

@@ -69,13 +69,30 @@ int zr_update_end(zr_ctx* c, hipStream_t x)
     return ZR_OK;
 }
 
+// "The end of frame f" (f < frame_no), for whoever waits for it: f's own event or, where f recorded none, a later one of the host's stream -
+// recorded now, in the newest frame's name, if nothing behind f was (zr_frame_end.h).
+int zr_frame_end(zr_ctx* c, uint64_t f, hipEvent_t* ev)
+{
+    const ZrEndAsk a = zr_end_ask(&c->end, f, c->frame_no);
+    *ev = c->ev_end[a.frame % zr_ctx::END_RING];
+    if (a.record) HIPCHK(c, hipEventRecord(*ev, c->stream));      // (every lighting pass so far is ahead of this point of the host's stream)
+    return ZR_OK;
+}
+int zr_wait_frame_end(zr_ctx* c, hipStream_t x, uint64_t f)
+{
+    hipEvent_t end;
+    if (int rc = zr_frame_end(c, f, &end)) return rc;
+    HIPCHK(c, hipStreamWaitEvent(x, end, 0));
+    return ZR_OK;
+}
+
 // A texture update's kernel on stream x, first half: the context's state; x behind the readers of the old image - the frame enqueued
 // last, on both lanes (on the render stream its lighting pass is ahead of this point) - and behind the update before
 int zr_update_tex_begin(zr_ctx* c, hipStream_t x)
 {
     int rc = tex_init_ctx(c);
     if (rc) return rc;
-    if (c->frame_no >= 1 && x != c->stream) HIPCHK(c, hipStreamWaitEvent(x, c->ev_end[(c->frame_no - 1) % zr_ctx::END_RING], 0));
+    if (c->frame_no >= 1 && x != c->stream && (rc = zr_wait_frame_end(c, x, c->frame_no - 1)) != ZR_OK) return rc;
     if (c->upd.tex_s && c->upd.tex_s != x) HIPCHK(c, hipStreamWaitEvent(x, c->upd.ev_tex, 0));
     return ZR_OK;
 }
@@ -178,7 +195,7 @@ int zr_update_frame(zr_ctx* c, hipStream_t s, int par)
             // lighting pass - its last reader - is ahead of this point.)
             const uint64_t r = U.reader[par];
             if (r && s != c->stream && (c->frame_no < 2 || r - 1 > c->frame_no - 2))
-                HIPCHK(c, hipStreamWaitEvent(s, c->ev_end[(r - 1) % zr_ctx::END_RING], 0));
+                if (int rc = zr_wait_frame_end(c, s, r - 1)) return rc;
             if (U.apply_done && U.apply_s != s) HIPCHK(c, hipStreamWaitEvent(s, U.ev_apply, 0));      // (ev_apply keeps covering every apply)
             int rc = zr_instances_apply(c, s, par);
             if (rc == ZR_OK && refit) rc = zr_mesh_update_frame(c, s, par);      // this parity's set of every stale mesh
