@@ -11,7 +11,7 @@ HBM bytes, exactly as MI355X_MICROARCH.md (HBM section) prescribes: FETCH_SIZE a
 do not fit one), are in KiB, and on gfx950 FETCH_SIZE counts 64 B per 128 B read request, i.e. half the bytes of a coalesced
 stream (calibrated on k_count_shadow: a 4 MiB dword-per-lane read reports 2056 KiB), so bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024.
 Per-frame totals = sum over every dispatch of the frame's kernels / number of frames in that run.  Every frame has exactly one
-full-screen shading launch - k_lighting over more than its one-pixel pre-launch's grid, k_lighting_rest or k_lighting_stand (a resting
+full-screen shading launch - k_lighting over more than its one-pixel pre-launch's grid, k_lighting_rest, k_lighting_stand or k_lighting_lead (a resting
 frame's ONE launch: no pre-launch, no k_frame_begin; the second leaves the parts no point light reaches as they stand) or k_forward - and those are what is counted (the dispatch's Grid_Size tells a pre-launch apart).
 A frame that keeps its shadow map and resolves on the host's stream runs k_mark ahead of the resolve (the visibility history, on the
 camera lane): a frame kernel like the others, one launch per such frame; the GBuffer-write pass of bench.py's `roofline` counts its time
@@ -58,7 +58,7 @@ SHORT = {"k_raster_chunks<0, false>": "k_raster<GBUFFER>", "k_raster_chunks<0, t
 def short(name):
     n = name.split("(")[0].replace("void ", "").strip()
     n = SHORT.get(n, n)
-    for base in ("k_lighting_stand", "k_lighting_rest", "k_lighting", "k_resolve_gbuffer", "k_calib"):      # (the resting launches first: rows of their own)
+    for base in ("k_lighting_lead", "k_lighting_stand", "k_lighting_rest", "k_lighting", "k_resolve_gbuffer", "k_calib"):      # (the resting launches first: rows of their own)
         if n.startswith(base) and base != "k_calib":
             n = base
             break
@@ -82,7 +82,7 @@ def counters(dirs):
             for r in csv.DictReader(open(f)):
                 k = short(r["Kernel_Name"])
                 acc[r["Counter_Name"]][k].append(float(r["Counter_Value"]))
-                if k in ("k_lighting_rest", "k_lighting_stand") or k.startswith("k_forward") or (k == "k_lighting" and int(r["Grid_Size"]) > ONE_PIXEL_GRID):
+                if k in ("k_lighting_rest", "k_lighting_stand", "k_lighting_lead") or k.startswith("k_forward") or (k == "k_lighting" and int(r["Grid_Size"]) > ONE_PIXEL_GRID):
                     FRAMES[r["Counter_Name"]] += 1
     return acc
 
@@ -179,7 +179,11 @@ if "k_mark" in out:
                              "part of ZR_PASS_RESOLVE; launches_per_frame < 1: the frames that drew their shadow map ran none")
 if "k_lighting" in out:
     out["k_lighting"]["note"] = ("the full-screen pass of the frames that draw, fill or fall back, and the one-pixel empty-colour pre-launch of each of "
-                                 "them (the means are over both); a resting frame's one launch is the row k_lighting_stand or k_lighting_rest")
+                                 "them (the means are over both); a resting frame's one launch is the row k_lighting_lead, k_lighting_stand or k_lighting_rest")
+if "k_lighting_lead" in out:
+    out["k_lighting_lead"]["note"] = ("a resting frame's ONE launch on a context that settles, the part's decision made by the workgroup's first wave: the "
+                                      "parts no point light reaches return behind a barrier and two LDS reads (tools/rest_settled.py has the share); "
+                                      "launches_per_frame: the share of resting frames")
 if "k_lighting_stand" in out:
     out["k_lighting_stand"]["note"] = ("a resting frame's ONE launch on a context that settles: the parts no point light reaches return after their set-up "
                                        "(tools/rest_settled.py has the share); launches_per_frame: the share of resting frames")

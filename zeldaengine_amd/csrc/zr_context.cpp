@@ -131,6 +131,7 @@ static int create_device_state(zr_ctx* c)
 #endif
         // every build: the resting frame through k_lighting_rest, every pixel written (the control of k_lighting_stand's A/B, and its test's)
         c->lk.settle_off = getenv("ZR_NO_REST_SETTLE") != nullptr;
+        c->lk.lead_off = getenv("ZR_NO_LEAD_WAVE") != nullptr;
         // ... and how often a frame inside a run of one-launch frames records its end (zr_frame_end.h; 1: every frame, as all others do)
         c->end.every = ZR_REST_END_EVERY_DEFAULT;
         if (const char* r = getenv("ZR_REST_END_EVERY")) { const int v = atoi(r); c->end.every = v < 1 ? 1u : (uint32_t)v > kZrEndEveryMax ? kZrEndEveryMax : (uint32_t)v; }

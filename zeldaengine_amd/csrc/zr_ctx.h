@@ -391,7 +391,9 @@ struct zr_ctx {
     struct SettleKey { ZrLightParams L; float cam[3]; uint32_t nDir, n_owned, _pad; const void *out, *plane, *rest, *owned, *marks; };
     struct LightKeep { float4* plane = nullptr; float4* rest = nullptr; bool alloc_failed = false; LightKey now = {}, key = {}; uint32_t last = 0;
                        uint64_t count[3] = { 0, 0, 0 }, by_arg = 0;
-                       uint32_t* marks = nullptr; ZrSettleState settle; SettleKey settle_key = {}; bool settle_off = false, handed_out = false; } lk;
+                       uint32_t* marks = nullptr; ZrSettleState settle; SettleKey settle_key = {}; bool settle_off = false, handed_out = false;
+                       bool lead_off = false;      // ZR_NO_LEAD_WAVE was set at zr_create: a settling context rests through k_lighting_stand (k_lighting_lead's control)
+                     } lk;
     float lut[256]; float* d_lut = nullptr;
     float* d_unorm_lut = nullptr;        // [0..255] = c / 255, [256..1279] = c / 1023 (IEEE quotients, computed on the host)
 

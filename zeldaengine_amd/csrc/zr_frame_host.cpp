@@ -578,22 +578,26 @@ static int deferred_resolve(zr_ctx* c)
     return ZR_OK;
 }
 
+// The lighting stage behind the geometry passes.  set_device: the staged entry point's call (zr_render's frame_begin has made the device
+// current for the whole call: once per zr_render).
+static int lighting_stage(zr_ctx* c, bool set_device)
+{
+    if (c->stage != 2) return zr_fail(c, ZR_ERR_STATE, "zr_render_lighting out of order");
+    if (set_device) HIPCHK(c, hipSetDevice(c->device));
+    const ZrFramePlan& p = c->plan;
+    // The one wait of the host's stream per frame: the camera lane's GBuffer (or, where the resolve follows here, its keys and history
+    // marks: ev_cam is then recorded ahead of the lane's k_plan) - and, ahead of it on that lane, this frame's k_frame_begin, whose
+    // uniforms the empty-pixel pass below reads (the shadow pipeline before it needed nothing of them and did not wait).
+    if (p.host_waits_ev_cam) HIPCHK(c, hipStreamWaitEvent(lane_stream(c, p.lighting), c->ev_cam, 0));
+    int rc = p.resolve_deferred ? deferred_resolve(c) : ZR_OK;
+    if (rc == ZR_OK && p.one_pixel != ZR_LANE_CAM) rc = empty_pixel_pass(c); // the shadow map (possibly reduced over ranks by the host) is final only now
+    if (rc == ZR_OK) rc = lighting_pass(c);
+    return rc;
+}
 extern "C" int zr_render_lighting(zr_ctx* c)
 {
     if (!c) return ZR_ERR_ARG;
-    return zr_guard(c, [&]() -> int {
-        if (c->stage != 2) return zr_fail(c, ZR_ERR_STATE, "zr_render_lighting out of order");
-        HIPCHK(c, hipSetDevice(c->device));
-        const ZrFramePlan& p = c->plan;
-        // The one wait of the host's stream per frame: the camera lane's GBuffer (or, where the resolve follows here, its keys and history
-        // marks: ev_cam is then recorded ahead of the lane's k_plan) - and, ahead of it on that lane, this frame's k_frame_begin, whose
-        // uniforms the empty-pixel pass below reads (the shadow pipeline before it needed nothing of them and did not wait).
-        if (p.host_waits_ev_cam) HIPCHK(c, hipStreamWaitEvent(lane_stream(c, p.lighting), c->ev_cam, 0));
-        int rc = p.resolve_deferred ? deferred_resolve(c) : ZR_OK;
-        if (rc == ZR_OK && p.one_pixel != ZR_LANE_CAM) rc = empty_pixel_pass(c); // the shadow map (possibly reduced over ranks by the host) is final only now
-        if (rc == ZR_OK) rc = lighting_pass(c);
-        return rc;
-    });
+    return zr_guard(c, [&]() -> int { return lighting_stage(c, true); });
 }
 
 // RecordCommandBuffer (ZE:3160-3744) + vkQueueSubmit (ZE:2014): shadow -> deferred scene -> deferred lighting, with two
@@ -612,7 +616,7 @@ extern "C" int zr_render(zr_ctx* c)
     if (!c) return ZR_ERR_ARG;
     return zr_guard(c, [&]() -> int {
         int rc = geometry_passes(c, ZR_ENTRY_RENDER);
-        if (rc == ZR_OK) rc = zr_render_lighting(c);
+        if (rc == ZR_OK) rc = lighting_stage(c, false);
         if (rc != ZR_OK) c->stage = 0;
         return rc;
     });

@@ -436,6 +436,107 @@ void k_lighting_stand(ZrLightParams L, ZrRestArgs R, const uint32_t* __restrict_
         if (inside && is_empty) light_emit<BACKGROUND>(L, G, tl, out, empty_px, px, py, p, tile_slot, i);
     }
 }
+// k_lighting_stand with the part's decision made ONCE: by the workgroup's first wave, for its seven siblings.  What a part decides - the
+// box, the first empty pixel, the lights' ballot, whether it stands settled - is the same in every wave (every operand is), and in
+// k_lighting_stand every wave works it out for itself: 88 vector and 67 scalar instructions ahead of the exit, in all 32 640 waves of a
+// 1920 x 1080 launch of which two thirds then return - a third of the kernel's vector issue and two thirds of its scalar issue.  Here wave
+// 0 takes the one trip (records, mark, the lane's light), decides, and leaves in LDS what the others need: the ballot, the first empty
+// pixel, settled or not, and the eight waves' empty-pixel masks (lanes 48 - 63 store their record word as it came).  The others wait at
+// a barrier and read it back: a wave of a settled part runs its slice of the next map's clear and returns behind two LDS reads.
+//  - Values, comparisons and their order are k_lighting_stand's: every bit of every frame is.
+//  - The mark has one reader now, wave 0, so thread 0 updates it right behind its own read: no sibling can see the store.
+//  - A part that shades pays one barrier more than k_lighting_stand (the set-up's second is the tables').
+template <bool BACKGROUND, int TB>
+__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(ZR_LIGHT_KEPT_WAVES, ZR_LIGHT_KEPT_WAVES)))
+void k_lighting_lead(ZrLightParams L, ZrRestArgs R, const uint32_t* __restrict__ owned_tiles, GBufferPtrs G, const float* __restrict__ srgb_lut,
+                     const float* __restrict__ unorm_lut, uint32_t* __restrict__ out, const float4* __restrict__ plane, const float4* __restrict__ rest,
+                     uint32_t* marks, uint32_t gen)
+{
+    static_assert(sizeof(ZrLightParams) + sizeof(ZrRestArgs) + sizeof(GBufferPtrs) + 8 * sizeof(void*) + 256 /* the hidden arguments */ < 4096,
+                  "k_lighting_lead: the argument block");
+    constexpr uint32_t PARTS = TILE_PIX / (uint32_t)TB, WAVES = (uint32_t)TB / 64u, NONE = 0xFFFFFFFFu, NT = 1536u / (uint32_t)TB;
+    static_assert(WAVES <= 8u && 1536u % (uint32_t)TB == 0u, "k_lighting_lead: a part's records are a dword per lane");
+    __shared__ float tab[1536];          // k_lighting_rest's
+    __shared__ uint32_t empty_px;
+    __shared__ uint32_t pub[20];         // wave 0's findings: [0], [1] the ballot, [2] the first empty pixel, [3] settled, [4 + w], [12 + w] the halves of wave w's mask
+    float* const tl = tab; float* const u8 = tab + 256; float* const u10 = tab + 512;
+    const uint32_t part = blockIdx.x % PARTS, tile_slot = blockIdx.x / PARTS;
+    const uint32_t i = threadIdx.x + part * (uint32_t)TB;      // the thread's pixel among the tile's
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (wave == 0u) {      // k_lighting_stand's decision, step for step
+        const uint32_t rec = rest_records_fetch<WAVES>(rest, tile_slot * ZR_REST_RECORDS_PER_TILE + part * WAVES);
+        const ZrRestLight* const lights = R.pt;
+        const ArgLight mine_light{ &lights[lane < R.nPoint ? lane : 0u] };
+        const uint32_t mark = (uint32_t)__builtin_amdgcn_readfirstlane((int)marks[blockIdx.x]);
+        float blo[3], bhi[3];
+        {
+            int lo, hi;
+            { const int idn = 0x7F800000; int r = (int)rec; ZR_DPP_STEP(op_fmin, 0x111, 0xF); ZR_DPP_STEP(op_fmin, 0x112, 0xF); ZR_DPP_STEP(op_fmin, 0x114, 0xF); lo = r; }
+            { const int idn = (int)0xFF800000; int r = (int)rec; ZR_DPP_STEP(op_fmax, 0x111, 0xF); ZR_DPP_STEP(op_fmax, 0x112, 0xF); ZR_DPP_STEP(op_fmax, 0x114, 0xF); hi = r; }
+            for (int a = 0; a < 3; ++a) { blo[a] = zr_u2f((uint32_t)__builtin_amdgcn_readlane(lo, 8 * a + 7)); bhi[a] = zr_u2f((uint32_t)__builtin_amdgcn_readlane(hi, 8 * (3 + a) + 7)); }
+        }
+        uint32_t first = NONE;
+        const unsigned long long nz64 = __ballot(lane >= 48u && (lane & 7u) < WAVES && rec != 0u);
+        const uint32_t nz = ((uint32_t)(nz64 >> 48) | (uint32_t)(nz64 >> 56)) & 255u;      // bit w: record w holds an empty pixel
+        if (nz != 0u) {
+            const int w0 = __builtin_ctz(nz);
+            const unsigned long long em = (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 48 + w0) |
+                                          (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 56 + w0) << 32;
+            first = (uint32_t)w0 * 64u + (uint32_t)__builtin_ctzll(em);
+            for (int a = 0; a < 3; ++a) { blo[a] = __builtin_fminf(blo[a], 0.0f); bhi[a] = __builtin_fmaxf(bhi[a], 0.0f); }      // the empty pixel is shaded at Pw = 0
+        }
+        const unsigned long long reach = __ballot(lane < R.nPoint && light_listed(mine_light, blo, bhi));
+        const bool settled = gen != 0u && reach == 0ull && mark == gen;
+        if (lane >= 48u) pub[4u + (lane - 48u)] = (lane & 7u) < WAVES ? rec : 0u;
+        if (lane == 0u) {
+            pub[0] = (uint32_t)reach; pub[1] = (uint32_t)(reach >> 32); pub[2] = first; pub[3] = settled ? 1u : 0u;
+            if (gen != 0u && !settled) {
+                if (reach == 0ull) marks[blockIdx.x] = gen;            // (it did not stand)
+                else if (mark == gen) marks[blockIdx.x] = 0u;
+            }
+        }
+    }
+    __syncthreads();
+    if (__builtin_amdgcn_readfirstlane((int)pub[3]) != 0) { light_clear_next_slice<TB>(L); return; }
+    const unsigned long long reach = (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)pub[0]) |
+                                     (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)pub[1]) << 32;
+    const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)pub[2]);
+    const unsigned long long mine = (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)pub[4u + wave]) |
+                                    (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)pub[12u + wave]) << 32;
+    {
+        float tv[NT];
+#pragma unroll
+        for (uint32_t k = 0; k < NT; ++k) { const uint32_t j = threadIdx.x + k * (uint32_t)TB; tv[k] = j < 256u ? srgb_lut[j] : unorm_lut[j - 256u]; }
+#pragma unroll
+        for (uint32_t k = 0; k < NT; ++k) tab[threadIdx.x + k * (uint32_t)TB] = tv[k];
+    }
+    const uint32_t tile = owned_tiles[tile_slot];
+    __syncthreads();
+    light_clear_next_slice<TB>(L);
+    const int tx0 = (int)(tile % L.tiles_x) * TILE, ty0 = (int)(tile / L.tiles_x) * TILE;
+    const zf3 cam = zr3(R.cam[0], R.cam[1], R.cam[2]);
+    const int px = tx0 + (int)(i & (TILE - 1)), py = ty0 + (int)(i / TILE);
+    const bool inside = px < (int)L.W && py < (int)L.H;
+    const size_t p = (size_t)py * L.W + (size_t)px;
+    const bool is_empty = ((mine >> lane) & 1ull) != 0ull, owner = threadIdx.x == first;
+    if (inside && (!is_empty || owner)) {
+        const uint32_t sc = G.scene_color[p], A = G.gA[p], B = G.gB[p], Cc = G.gC[p];
+        const uint2 D = G.gD[p];
+        const LitPixel q = light_decode(u8, u10, sc, A, B, Cc, D);
+        const float4 ka = owner ? rest[0] : plane[p], kb = owner ? rest[1] : plane[(size_t)L.W * L.H + p];
+        zf3 Direct = zr3(ka.x, ka.y, ka.z); const float ShadowFactor = ka.w; const zf3 RefC = zr3(kb.x, kb.y, kb.z);
+        shade_points_arg<ZR_STAND_WALK_LIST != 0>(L, R, reach, cam, q.BaseColor, q.Metallic, q.Roughness, q.N, q.Pw, Direct);
+        const zf3 Indirect = shade_indirect(q.BaseColor, q.Metallic, q.AO, ShadowFactor);
+        const uint32_t rgba = light_compose(L, q, Direct, Indirect, RefC, ShadowFactor, px, py);
+        if (owner) empty_px = rgba;
+        else light_emit<BACKGROUND>(L, G, tl, out, rgba, px, py, p, tile_slot, i);
+    }
+    if (first != NONE) {      // (the same for every thread of the workgroup: wave 0's finding)
+        __syncthreads();
+        if (inside && is_empty) light_emit<BACKGROUND>(L, G, tl, out, empty_px, px, py, p, tile_slot, i);
+    }
+}
 #endif
 
 // GBufferVis (SH/BaseLighting.frag:42-145, SPEC_CONSTANTS 9).  Runs after k_lighting has written FinalColor everywhere: the
@@ -580,6 +681,18 @@ void zr_launch_lighting_stand(const ZrLightParams& L, const ZrRestArgs& R, const
     const dim3 grid(n_owned * (TILE_PIX / ZR_LIGHT_KEPT_TB)), block(ZR_LIGHT_KEPT_TB);
     if (L.bg_enabled) hipLaunchKernelGGL((k_lighting_stand<true, ZR_LIGHT_KEPT_TB>), grid, block, 0, s, L, R, owned_tiles, G, lut, unorm_lut, out, plane, rest, marks, gen);
     else hipLaunchKernelGGL((k_lighting_stand<false, ZR_LIGHT_KEPT_TB>), grid, block, 0, s, L, R, owned_tiles, G, lut, unorm_lut, out, plane, rest, marks, gen);
+#endif
+}
+// ... with the part's decision made by the workgroup's first wave (k_lighting_lead): the same arguments, the same marks, the same frame
+void zr_launch_lighting_lead(const ZrLightParams& L, const ZrRestArgs& R, const uint32_t* owned_tiles, uint32_t n_owned, const GBufferPtrs& G,
+                             const float* lut, const float* unorm_lut, uint32_t* out, hipStream_t s, const float4* plane, const float4* rest,
+                             uint32_t* marks, uint32_t gen)
+{
+#if ZR_PIXELS_PER_THREAD == 1
+    if (n_owned == 0) return;
+    const dim3 grid(n_owned * (TILE_PIX / ZR_LIGHT_KEPT_TB)), block(ZR_LIGHT_KEPT_TB);
+    if (L.bg_enabled) hipLaunchKernelGGL((k_lighting_lead<true, ZR_LIGHT_KEPT_TB>), grid, block, 0, s, L, R, owned_tiles, G, lut, unorm_lut, out, plane, rest, marks, gen);
+    else hipLaunchKernelGGL((k_lighting_lead<false, ZR_LIGHT_KEPT_TB>), grid, block, 0, s, L, R, owned_tiles, G, lut, unorm_lut, out, plane, rest, marks, gen);
 #endif
 }
 void zr_launch_gbuffer_vis(const ZrLightParams& L, const XkView* view, const GBufferPtrs& G, const float* shadowmap, const CubeDesc& C,

@@ -172,7 +172,8 @@ int lighting_pass(zr_ctx* c)
             ZrSettleFacts sf; sf.stand = true; sf.key_same = memcmp(&K, &c->lk.settle_key, sizeof K) == 0;
             const ZrSettleStep step = zr_settle_step(c->lk.settle, sf);
             if (step.wipe) HIPCHK(c, hipMemsetAsync(c->lk.marks, 0, (size_t)c->n_owned * zr_lighting_stand_parts() * sizeof(uint32_t), s));
-            zr_launch_lighting_stand(L, R, c->d_owned, c->n_owned, F.G, c->d_lut, c->d_unorm_lut, frame_out, s, c->lk.plane, c->lk.rest, c->lk.marks, step.gen);
+            // (the same frame and the same marks either way: k_lighting_lead decides a part once, k_lighting_stand in each of its waves)
+            (c->lk.lead_off ? zr_launch_lighting_stand : zr_launch_lighting_lead)(L, R, c->d_owned, c->n_owned, F.G, c->d_lut, c->d_unorm_lut, frame_out, s, c->lk.plane, c->lk.rest, c->lk.marks, step.gen);
             c->lk.settle = step.next; c->lk.settle_key = K; stood = true;
         } else
             zr_launch_lighting_rest(L, R, c->d_owned, c->n_owned, F.G, c->d_lut, c->d_unorm_lut, frame_out, s, c->lk.plane, c->lk.rest);

@@ -369,6 +369,10 @@ uint32_t zr_lighting_stand_parts();
 void zr_launch_lighting_stand(const ZrLightParams& L, const ZrRestArgs& R, const uint32_t* owned_tiles, uint32_t n_owned, const GBufferPtrs& G,
                               const float* lut, const float* unorm_lut, uint32_t* out, hipStream_t s, const float4* plane, const float4* rest,
                               uint32_t* marks, uint32_t gen);
+// ... and the part's decision made once, by the workgroup's first wave (k_lighting_lead): the same arguments, the same frame
+void zr_launch_lighting_lead(const ZrLightParams& L, const ZrRestArgs& R, const uint32_t* owned_tiles, uint32_t n_owned, const GBufferPtrs& G,
+                             const float* lut, const float* unorm_lut, uint32_t* out, hipStream_t s, const float4* plane, const float4* rest,
+                             uint32_t* marks, uint32_t gen);
 // forward variant (SH/Base.frag): shades the winners recorded in G.prim with the camera pass's own parameter block
 void zr_launch_forward(const ZrPass& P, const ZrLightParams& L, const XkView* view, const ZrObject* objs, const uint32_t* owned_tiles, uint32_t n_owned,
                        const GBufferPtrs& G, const float* shadowmap, const CubeDesc& C, const float* lut, const float* unorm_lut, uint32_t* out, hipStream_t s);

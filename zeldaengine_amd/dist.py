@@ -119,8 +119,9 @@ class DistributedRenderer:
         """Enqueue one full frame; returns immediately."""
         torch = self.torch
         if self.world == 1:
-            with torch.cuda.stream(self.render_stream):
-                self.r.render()
+            # No stream context: the library never reads torch's current stream.  It enqueues on the stream zr_set_stream gave it
+            # (render_stream's raw handle, set once above), and nothing else of torch runs inside the call.
+            self.r.render()
             return
         import torch.distributed as dist
         b = self.k & 1

@@ -157,6 +157,18 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
 
 
+def _addr(a):
+    return a.ctypes.data if a is not None and a.size else None
+
+
+def uniform_arguments(cam, dir_l, point_l, spot_l):
+    """zr_update_uniforms' pointer and count arguments as plain integers (None: a null pointer), read from the objects at every call: no
+    pointer object, no cast and no kept address that an array's reallocation or another camera object could leave stale.  An empty
+    array or None goes as a null pointer and a count of 0.  Needs no GPU (tests/test_uniform_marshalling.py)."""
+    return (C.addressof(cam), _addr(dir_l), 0 if dir_l is None else len(dir_l), _addr(point_l), 0 if point_l is None else len(point_l),
+            _addr(spot_l), 0 if spot_l is None else len(spot_l))
+
+
 def build_meshlets(verts, idx, max_vertices=64, max_triangles=124, cone_weight=0.2):
     """Context-free clusteriser (host code only; works without a GPU).  Returns (meshlets, mverts, mtris, tri_order)."""
     L = lib()
@@ -605,9 +617,7 @@ class Renderer:
 
     # ---- uniforms
     def update_uniforms(self, cam, dir_l, point_l, spot_l, roll_stage=0.0, roll_light=0.0, time=0.0):
-        self._chk(self.L.zr_update_uniforms(self.h, C.cast(C.pointer(cam), C.c_void_p), _ptr(dir_l), len(dir_l),
-                                            _ptr(point_l), len(point_l), _ptr(spot_l), len(spot_l),
-                                            roll_stage, roll_light, time))
+        self._chk(self.L.zr_update_uniforms(self.h, *uniform_arguments(cam, dir_l, point_l, spot_l), roll_stage, roll_light, time))
 
     def set_frame(self, cam, shadow, view):
         self._chk(self.L.zr_set_frame(self.h, cam.ctypes.data, shadow.ctypes.data, view.ctypes.data))
