@@ -265,11 +265,13 @@ def test_the_moving_camera_sequence_is_the_oracle_s(oracle_lib, gpu_engine):
     o = oracle_lib.Oracle(W, H, SD)
     for r in (g, o):
         _populate(r)
+    import torch
+    cols = [torch.zeros(W * H, dtype=torch.int32, device=torch.device("cuda", 0)) for _ in MOVING_CAMERA]
+    torch.cuda.synchronize()                            # (the zero fills are on torch's stream, the copies on the context's: not ordered otherwise)
     for k, f in enumerate(MOVING_CAMERA):
         _enqueue(g, f, k, lights)
         if k + 1 < len(MOVING_CAMERA):                  # the next frame right behind: this frame's resolve runs beside its camera lane
-            import torch
-            col = torch.zeros(W * H, dtype=torch.int32, device=torch.device("cuda", 0))
+            col = cols[k]
             g.copy_frame_async(col.data_ptr(), None)
             _enqueue(g, MOVING_CAMERA[k + 1], k + 1, lights)
             g.finish()

@@ -80,3 +80,30 @@ def test_frame_shapes_are_k_lighting_stands(gpu_engine, monkeypatch, shape):
         assert settled[1] < settled[0] and settled[3] < settled[2], settled      # frames 5 and 7 against 4 and 6
     for r in (g, stand, twin):
         r.close()
+
+
+@pytest.mark.parametrize("background", [False, True])
+def test_the_three_resting_kernels_write_the_same_frame(gpu_engine, monkeypatch, background):
+    """k_lighting_lead (a default context), k_lighting_stand (ZR_NO_LEAD_WAVE) and k_lighting_rest (ZR_NO_REST_SETTLE) run the same
+    shared steps - the tables, the box, the first empty pixel, the pixel tail - and write the same bytes as each other and as the
+    ZR_FLAG_NO_LIST_REUSE twin, at 33 x 17: parts of sixteen rows and of one, a tile a column wide, threads outside the frame; plain and
+    with a background image (the tail's other instantiation).  The context that never settles reports nothing settled."""
+    size = (33, 17)
+    st = SStage(16, size=size, radius=SWEEP[size][0], rate=SWEEP[size][1])
+    g, stand, twin = _three(st, gpu_engine, monkeypatch)
+    monkeypatch.setenv("ZR_NO_REST_SETTLE", "1")
+    rest = st.renderer(gpu_engine)
+    monkeypatch.delenv("ZR_NO_REST_SETTLE")
+    if background:
+        for r in (g, stand, rest, twin):
+            r.set_background(scenes.synthetic_sky_image(48, 32))
+    for i in range(9):
+        did = _frame(g, stand, twin, st, i, "three kernels")
+        assert _pair(rest, twin, st, i, "three kernels, k_lighting_rest") == did
+        assert rest.color().tobytes() == g.color().tobytes(), i
+        assert rest.rest_settled()[1] == 0
+        if i >= 4:
+            assert did == "read"
+    assert _by_arg(g) == _by_arg(stand) == _by_arg(rest) == 6
+    for r in (g, stand, rest, twin):
+        r.close()

@@ -2,53 +2,34 @@
 for gfx950 with the library's flags, no GPU needed).
 
   - Its two instantiations (background off / on) are compiled for eight waves per SIMD: at most 64 VGPRs, no scratch.  Their rows - and
-    nothing else - are recorded in profiles/r25_a_kernel_table_result.json (the file's other kernels are held to their own records by
+    nothing else - are recorded in profiles/r26_a_kernel_table_result.json (the file's other kernels are held to their own records by
     tests/test_kernel_table_stand.py, tests/test_kernel_table_rest.py and tests/test_kernel_table_rest_setup.py).
   - What the change is for: ahead of the first barrier - the decision, which k_lighting_stand makes in every wave - a wave that is not
     the workgroup's first issues a handful of instructions and no load.  The listing shows it as a branch over the decision ahead of
     every vector load of the kernel.
 """
-import importlib.util
 import json
 import os
-import re
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "zeldaengine_amd", "csrc", "zr_lighting.hip")
-RECORD = os.path.join(ROOT, "profiles", "r25_a_kernel_table_result.json")
+from kernel_listing import ROOT, SRC, kernel_table, labels, listing, ops
 
-
-def _kernel_table():
-    spec = importlib.util.spec_from_file_location("kernel_table", os.path.join(ROOT, "tools", "kernel_table.py"))
-    kt = importlib.util.module_from_spec(spec); spec.loader.exec_module(kt)
-    return kt
+RECORD = os.path.join(ROOT, "profiles", "r26_a_kernel_table_result.json")
 
 
 def test_eight_waves_no_scratch_and_the_rows_are_the_recorded_ones():
-    rows = _kernel_table().table(SRC, [])
+    rows = kernel_table().table(SRC, [])
     want = json.load(open(RECORD))
     lead = {k: v for k, v in rows.items() if k.startswith("k_lighting_lead<")}
     assert sorted(lead) == ["k_lighting_lead<false, 512>", "k_lighting_lead<true, 512>"], sorted(rows)
     for name, r in lead.items():
         print(name, r)
         assert r["scratch"] == 0 and r["vgpr"] <= 64, (name, r)
-    assert lead == want, lead
+    assert lead == {k: v for k, v in want.items() if k in lead}, lead
 
 
 def test_the_other_waves_skip_the_decision_ahead_of_every_load(tmp_path):
-    kt = _kernel_table()
-    out = os.path.join(str(tmp_path), "l.s")
-    subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-x", "hip"] + kt.FLAGS + ["-o", out, SRC], stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    names = re.findall(r"^\s*\.amdhsa_kernel (\S+)", text, re.M)
-    plain = subprocess.run(["c++filt"] + names, capture_output=True, text=True).stdout.split("\n")
-    name = [n for n, d in zip(names, plain) if d.replace("void ", "").startswith("k_lighting_lead<false, 512>")]
-    assert len(name) == 1, plain
-    body = text[text.index("\n" + name[0] + ":"):]
-    lines = body[:body.index(".Lfunc_end")].split("\n")
-    op = [(n, l.split()) for n, l in enumerate(lines) if l.strip() and l.strip()[0] not in ";."]
-    label = {l.split(":")[0]: n for n, l in enumerate(lines) if re.match(r"\.LBB\S+:", l)}
+    lines = listing(tmp_path, "k_lighting_lead<false, 512>")
+    op, label = ops(lines), labels(lines)
     barrier = min(n for n, w in op if w[0] == "s_barrier")
     first_load = min(n for n, w in op if w[0].startswith("global_load"))
     skips = [(n, label[w[1]]) for n, w in op if w[0].startswith("s_cbranch") and n < first_load]

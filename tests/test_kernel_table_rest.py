@@ -7,19 +7,17 @@ at most 64 VGPRs.  The lighting kernels that keep nothing (k_lighting<..., 0>) a
 with it (csrc/zr_shade.h): their rows - registers, scratch, LDS, instruction counts - are the rows of the commit before the change,
 as recorded with that commit in profiles/r14_a_kernel_table_result.json.
 """
-import importlib.util
 import json
 import os
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from kernel_listing import ROOT, kernel_table
 
 
 @pytest.fixture(scope="module")
 def rows():
-    spec = importlib.util.spec_from_file_location("kernel_table", os.path.join(ROOT, "tools", "kernel_table.py"))
-    kt = importlib.util.module_from_spec(spec); spec.loader.exec_module(kt)
+    kt = kernel_table()
     out = {}
     for src in ("zr_lighting.hip", "zr_forward.hip"):
         out.update(kt.table(os.path.join(ROOT, "zeldaengine_amd", "csrc", src), []))

@@ -11,40 +11,23 @@ The listing is held to that, for k_lighting_rest<true, false, 512>:
   - between the workgroup's barrier and the first DPP instruction the records are waited for once, and the fold is six row_shr steps;
   - the light loop holds one scalar load, of eight dwords; the tile list's test reads its light by two 16-byte LDS reads side by side;
   - ahead of the barrier five loads - three of tables, the light records, the part's records - are issued before the first wait on one.
-The instruction counts tools/kernel_table.py reports for the four instantiations are recorded in profiles/r18_a_kernel_table_result.json;
+The instruction counts tools/kernel_table.py reports for the four instantiations are recorded in profiles/r26_a_kernel_table_result.json;
 the table the tool makes now is that file's (registers, scratch and LDS included: at most 64 VGPRs, no scratch).
 """
-import importlib.util
 import json
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "zeldaengine_amd", "csrc", "zr_lighting.hip")
+from kernel_listing import ROOT, SRC, kernel_table, listing as kernel_listing, ops
+
 KERNEL = "k_lighting_rest<true, false, 512>"
-
-
-def _kernel_table():
-    spec = importlib.util.spec_from_file_location("kernel_table", os.path.join(ROOT, "tools", "kernel_table.py"))
-    kt = importlib.util.module_from_spec(spec); spec.loader.exec_module(kt)
-    return kt
 
 
 def _listing(tmp, extra=()):
     """the instruction lines (comments kept) of KERNEL"""
-    kt = _kernel_table()
-    out = os.path.join(str(tmp), "l%d.s" % len(extra))
-    subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-x", "hip"] + kt.FLAGS + list(extra) + ["-o", out, SRC], stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    names = re.findall(r"^\s*\.amdhsa_kernel (\S+)", text, re.M)
-    plain = subprocess.run(["c++filt"] + names, capture_output=True, text=True).stdout.split("\n")
-    name = [n for n, d in zip(names, plain) if d.replace("void ", "").startswith(KERNEL)]
-    assert len(name) == 1, plain
-    body = text[text.index("\n" + name[0] + ":"):]
-    return body[:body.index(".Lfunc_end")].split("\n")
+    return kernel_listing(tmp, KERNEL, extra)
 
 
 def _loops(lines):
@@ -64,7 +47,7 @@ def _loops(lines):
 
 
 def _ops(lines):
-    return [(n, line.split()[0], line) for n, line in enumerate(lines) if line.strip() and line.strip()[0] not in ";." and not line.split()[0].endswith(":")]
+    return [(n, w[0], lines[n]) for n, w in ops(lines) if not w[0].endswith(":")]
 
 
 @pytest.fixture(scope="module")
@@ -126,8 +109,8 @@ def test_the_tables_arrive_in_one_trip(listing):
 
 
 def test_instruction_counts_are_the_recorded_ones():
-    rows = {k: v for k, v in _kernel_table().table(SRC, []).items() if k.startswith("k_lighting_rest<")}
-    want = json.load(open(os.path.join(ROOT, "profiles", "r18_a_kernel_table_result.json")))
+    rows = {k: v for k, v in kernel_table().table(SRC, []).items() if k.startswith("k_lighting_rest<")}
+    want = json.load(open(os.path.join(ROOT, "profiles", "r26_a_kernel_table_result.json")))
     assert len(rows) == 4 and rows == {k: v for k, v in want.items() if k.startswith("k_lighting_rest<")}, rows
     for name, r in rows.items():
         assert r["scratch"] == 0 and r["vgpr"] <= 64, (name, r)

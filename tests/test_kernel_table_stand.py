@@ -2,7 +2,7 @@
 (hipcc -S for gfx950 with the library's flags, no GPU needed).
 
   - Its two instantiations (background off / on; the tile list is always built, as a ballot) are compiled for eight waves per SIMD: at
-    most 64 VGPRs, no scratch.  Their rows - and nothing else - are recorded in profiles/r23_a_kernel_table_result.json (the other
+    most 64 VGPRs, no scratch.  Their rows - and nothing else - are recorded in profiles/r26_a_kernel_table_result.json (the other
     kernels of the file are held to their own records by tests/test_kernel_table_rest.py and tests/test_kernel_table_rest_setup.py).
   - The returning path - a part no point light reaches, whose mark stands - leaves ahead of the workgroup's first barrier: the branch
     that takes it sits behind ONE trip of three vector loads (the part's records, the two halves of the lane's light record; the mark
@@ -12,46 +12,26 @@
     exit behind the set-up's barrier: the order that lost, DESIGN.md App. A - has the table loads ahead of that branch and exactly one
     barrier, the set-up's, between the kernel's entry and it.
 """
-import importlib.util
 import json
 import os
-import re
-import subprocess
 
-import pytest
+from kernel_listing import ROOT, SRC, kernel_table, labels, listing, ops
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "zeldaengine_amd", "csrc", "zr_lighting.hip")
 KERNEL = "k_lighting_stand<false, 512>"
-RECORD = os.path.join(ROOT, "profiles", "r23_a_kernel_table_result.json")
-
-
-def _kernel_table():
-    spec = importlib.util.spec_from_file_location("kernel_table", os.path.join(ROOT, "tools", "kernel_table.py"))
-    kt = importlib.util.module_from_spec(spec); spec.loader.exec_module(kt)
-    return kt
+RECORD = os.path.join(ROOT, "profiles", "r26_a_kernel_table_result.json")
 
 
 def _listing(tmp, extra=()):
-    kt = _kernel_table()
-    out = os.path.join(str(tmp), "l%d.s" % len(extra))
-    subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-x", "hip"] + kt.FLAGS + list(extra) + ["-o", out, SRC], stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    names = re.findall(r"^\s*\.amdhsa_kernel (\S+)", text, re.M)
-    plain = subprocess.run(["c++filt"] + names, capture_output=True, text=True).stdout.split("\n")
-    name = [n for n, d in zip(names, plain) if d.replace("void ", "").startswith(KERNEL)]
-    assert len(name) == 1, plain
-    body = text[text.index("\n" + name[0] + ":"):]
-    return body[:body.index(".Lfunc_end")].split("\n")
+    return listing(tmp, KERNEL, extra)
 
 
 def _exit_path(lines):
     """-> (line of the branch that takes the returning path, line of its target's label, lines of every s_barrier, of s_endpgm)"""
-    op = [(n, l.split()) for n, l in enumerate(lines) if l.strip() and l.strip()[0] not in ";."]
+    op = ops(lines)
     barriers = [n for n, w in op if w[0] == "s_barrier"]
     ends = [n for n, w in op if w[0] == "s_endpgm"]
     assert len(ends) == 1, ends
-    label = {l.split(":")[0]: n for n, l in enumerate(lines) if re.match(r"\.LBB\S+:", l)}
+    label = labels(lines)
     # the conditional branches ahead of the kernel's last barrier (the empty colour's) whose target lies behind it: the returning path is
     # the first such jump (the others, late in the kernel, are those of a part that shades and holds no empty pixel)
     out = [(n, label[w[1]]) for n, w in op if w[0].startswith("s_cbranch") and n < barriers[-1] and label[w[1]] > barriers[-1]]
@@ -64,7 +44,7 @@ def _loads_before(lines, n):
 
 
 def test_eight_waves_no_scratch_and_the_rows_are_the_recorded_ones():
-    rows = _kernel_table().table(SRC, [])
+    rows = kernel_table().table(SRC, [])
     want = json.load(open(RECORD))
     stand = {k: v for k, v in rows.items() if k.startswith("k_lighting_stand<")}
     assert sorted(stand) == ["k_lighting_stand<false, 512>", "k_lighting_stand<true, 512>"], sorted(rows)

@@ -213,6 +213,108 @@ __device__ __forceinline__ uint32_t rest_records_fetch(const float4* __restrict_
     const uint32_t* __restrict__ w = (const uint32_t*)(rest + ZR_REST_SLOT) + (size_t)first_record * RECW;      // (wave-uniform; the lane's offset is 32 bits)
     return w[((threadIdx.x & 7u) % WAVES) * RECW + ((threadIdx.x >> 3) & 7u)];
 }
+// The steps the three resting kernels share, each spelled once (which test holds which: DESIGN.md App. A, "Resting-frame kernels").
+// The 1 536 table floats (k_lighting's tl - sRGB decode, then c / 255: tex_decode's layout - and u10, in one piece): every request is
+// issued before the first store waits for one.  k_lighting_rest and k_lighting_stand's control build put more requests between the two.
+template <int TB>
+__device__ __forceinline__ void rest_tables_request(float (&tv)[1536 / TB], const float* __restrict__ srgb_lut, const float* __restrict__ unorm_lut)
+{
+#pragma unroll
+    for (uint32_t k = 0; k < 1536u / (uint32_t)TB; ++k) { const uint32_t j = threadIdx.x + k * (uint32_t)TB; tv[k] = j < 256u ? srgb_lut[j] : unorm_lut[j - 256u]; }
+}
+template <int TB>
+__device__ __forceinline__ void rest_tables_store(float* tab, const float (&tv)[1536 / TB])
+{
+#pragma unroll
+    for (uint32_t k = 0; k < 1536u / (uint32_t)TB; ++k) tab[threadIdx.x + k * (uint32_t)TB] = tv[k];
+}
+template <int TB>
+__device__ __forceinline__ void rest_tables_load(float* tab, const float* __restrict__ srgb_lut, const float* __restrict__ unorm_lut)
+{
+    float tv[1536 / TB];
+    rest_tables_request<TB>(tv, srgb_lut, unorm_lut);
+    rest_tables_store<TB>(tab, tv);
+}
+// The part's box from its records' dword per lane.  row_shr 1, 2, 4 fold exactly eight lanes into the last of them: lane 8 f + 7 holds
+// field f over the records (min / max are exact in any order; the fill's -inf / +inf for a non-finite position pass through as they did)
+__device__ __forceinline__ void rest_box_fold(uint32_t rec, float* blo, float* bhi)
+{
+    int lo, hi;
+    { const int idn = 0x7F800000; int r = (int)rec; ZR_DPP_STEP(op_fmin, 0x111, 0xF); ZR_DPP_STEP(op_fmin, 0x112, 0xF); ZR_DPP_STEP(op_fmin, 0x114, 0xF); lo = r; }
+    { const int idn = (int)0xFF800000; int r = (int)rec; ZR_DPP_STEP(op_fmax, 0x111, 0xF); ZR_DPP_STEP(op_fmax, 0x112, 0xF); ZR_DPP_STEP(op_fmax, 0x114, 0xF); hi = r; }
+    for (int a = 0; a < 3; ++a) { blo[a] = zr_u2f((uint32_t)__builtin_amdgcn_readlane(lo, 8 * a + 7)); bhi[a] = zr_u2f((uint32_t)__builtin_amdgcn_readlane(hi, 8 * (3 + a) + 7)); }
+}
+// Record w's empty pixels, a bit each: lanes 48 + w and 56 + w hold the two halves
+__device__ __forceinline__ unsigned long long rest_mask_of(uint32_t rec, int w)
+{
+    return (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 48 + w) | (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 56 + w) << 32;
+}
+// The part's first empty pixel (thread number, or REST_NONE).  WIDEN: a part that holds one has its box widened to the world origin - the
+// empty pixel is shaded at Pw = 0, and the empty colour's settling rests on the box holding it.
+constexpr uint32_t REST_NONE = 0xFFFFFFFFu;
+template <uint32_t WAVES, bool WIDEN>
+__device__ __forceinline__ uint32_t rest_first_empty(uint32_t rec, float* blo, float* bhi)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const unsigned long long nz64 = __ballot(lane >= 48u && (lane & 7u) < WAVES && rec != 0u);
+    const uint32_t nz = ((uint32_t)(nz64 >> 48) | (uint32_t)(nz64 >> 56)) & 255u;      // bit w: record w holds an empty pixel
+    uint32_t first = REST_NONE;
+    if (nz != 0u) {
+        const int w0 = __builtin_ctz(nz);
+        first = (uint32_t)w0 * 64u + (uint32_t)__builtin_ctzll(rest_mask_of(rec, w0));
+        if constexpr (WIDEN)
+            for (int a = 0; a < 3; ++a) { blo[a] = __builtin_fminf(blo[a], 0.0f); bhi[a] = __builtin_fmaxf(bhi[a], 0.0f); }
+    }
+    return first;
+}
+// What a part decides, the same in every wave that works it out (every operand is): reach = the tile list's ballot over the part's box,
+// a lane a light; first = its first empty pixel; settled = no light reaches it and its mark stands.
+struct RestDecision { unsigned long long reach; uint32_t first; bool settled; };
+template <uint32_t WAVES>
+__device__ __forceinline__ RestDecision rest_decide(uint32_t rec, uint32_t mark, const ArgLight& mine_light, uint32_t nPoint, uint32_t gen)
+{
+    RestDecision d;
+    float blo[3], bhi[3];
+    rest_box_fold(rec, blo, bhi);
+    d.first = rest_first_empty<WAVES, true>(rec, blo, bhi);
+    d.reach = __ballot((threadIdx.x & 63u) < nPoint && light_listed(mine_light, blo, bhi));
+    d.settled = gen != 0u && d.reach == 0ull && mark == gen;
+    return d;
+}
+// A part's pixels.  What the fill recorded says which are empty (mine: this wave's, a bit per lane); the rest fetch their GBuffer words and
+// are shaded as k_lighting<.., ZR_LIGHT_KEPT> shades them, the lights from R, walked by list (USE_LIST) or all of them.  The colour of
+// an empty pixel is computed by the thread that owns the part's first (first: its thread number, or REST_NONE) - that pixel shaded like
+// any other, its standing terms from the slot the fill's one-pixel launch wrote - and parked in LDS behind one barrier, whose condition
+// is the same for every thread of the workgroup.
+template <bool USE_LIST, bool BACKGROUND>
+__device__ __forceinline__ void rest_shade_part(const ZrLightParams& L, const ZrRestArgs& R, const GBufferPtrs& G, const float* tab, uint32_t* __restrict__ out,
+                                                const float4* __restrict__ plane, const float4* __restrict__ rest, unsigned long long list, uint32_t first,
+                                                unsigned long long mine, uint32_t tile, uint32_t tile_slot, uint32_t i, uint32_t* empty_px)
+{
+    const float* const tl = tab; const float* const u8 = tab + 256; const float* const u10 = tab + 512;
+    const int tx0 = (int)(tile % L.tiles_x) * TILE, ty0 = (int)(tile / L.tiles_x) * TILE;
+    const zf3 cam = zr3(R.cam[0], R.cam[1], R.cam[2]);
+    const int px = tx0 + (int)(i & (TILE - 1)), py = ty0 + (int)(i / TILE);
+    const bool inside = px < (int)L.W && py < (int)L.H;
+    const size_t p = (size_t)py * L.W + (size_t)px;
+    const bool is_empty = ((mine >> (threadIdx.x & 63u)) & 1ull) != 0ull, owner = threadIdx.x == first;
+    if (inside && (!is_empty || owner)) {
+        const uint32_t sc = G.scene_color[p], A = G.gA[p], B = G.gB[p], Cc = G.gC[p];
+        const uint2 D = G.gD[p];
+        const LitPixel q = light_decode(u8, u10, sc, A, B, Cc, D);
+        const float4 ka = owner ? rest[0] : plane[p], kb = owner ? rest[1] : plane[(size_t)L.W * L.H + p];
+        zf3 Direct = zr3(ka.x, ka.y, ka.z); const float ShadowFactor = ka.w; const zf3 RefC = zr3(kb.x, kb.y, kb.z);
+        shade_points_arg<USE_LIST>(L, R, list, cam, q.BaseColor, q.Metallic, q.Roughness, q.N, q.Pw, Direct);
+        const zf3 Indirect = shade_indirect(q.BaseColor, q.Metallic, q.AO, ShadowFactor);
+        const uint32_t rgba = light_compose(L, q, Direct, Indirect, RefC, ShadowFactor, px, py);
+        if (owner) *empty_px = rgba;
+        else light_emit<BACKGROUND>(L, G, tl, out, rgba, px, py, p, tile_slot, i);
+    }
+    if (first != REST_NONE) {
+        __syncthreads();
+        if (inside && is_empty) light_emit<BACKGROUND>(L, G, tl, out, *empty_px, px, py, p, tile_slot, i);
+    }
+}
 
 template <bool LIGHT_LIST, bool BACKGROUND, int TB>
 __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(ZR_LIGHT_KEPT_WAVES, ZR_LIGHT_KEPT_WAVES)))
@@ -221,62 +323,38 @@ void k_lighting_rest(ZrLightParams L, ZrRestArgs R, const uint32_t* __restrict__
 {
     static_assert(sizeof(ZrLightParams) + sizeof(ZrRestArgs) + sizeof(GBufferPtrs) + 6 * sizeof(void*) + 256 /* the hidden arguments */ < 4096,
                   "k_lighting_rest: the argument block");
-    constexpr uint32_t PARTS = TILE_PIX / (uint32_t)TB, WAVES = (uint32_t)TB / 64u, NONE = 0xFFFFFFFFu;
+    constexpr uint32_t PARTS = TILE_PIX / (uint32_t)TB, WAVES = (uint32_t)TB / 64u;
     static_assert((WAVES <= 8u || !ZR_REST_RECORDS_ONE_TRIP) && 1536u % (uint32_t)TB == 0u, "k_lighting_rest: a part's records are a dword per lane");
-    __shared__ float tab[1536];          // k_lighting's tl (sRGB decode, then c / 255: tex_decode's layout) and u10, in one piece
+    __shared__ float tab[1536];          // rest_tables_load's
     __shared__ uint32_t empty_px;
     __shared__ ZrRestLight lpt[LIGHT_LIST ? ZR_REST_ARG_LIGHTS : 1];      // the light records' LDS copy, for the tile list's test (a lane per light)
-    float* const tl = tab; float* const u8 = tab + 256; float* const u10 = tab + 512;
     const uint32_t part = blockIdx.x % PARTS, tile_slot = blockIdx.x / PARTS;
     const uint32_t i = threadIdx.x + part * (uint32_t)TB;      // the thread's pixel among the tile's
     const uint32_t first_record = tile_slot * ZR_REST_RECORDS_PER_TILE + part * WAVES;
     uint32_t rec = 0u;
     {   // every load is issued before the first is waited for
-        constexpr uint32_t NT = 1536u / (uint32_t)TB, LW = ZR_REST_ARG_LIGHTS * (uint32_t)(sizeof(ZrRestLight) / 4u), NL = LIGHT_LIST ? (LW + (uint32_t)TB - 1u) / (uint32_t)TB : 0u;
-        float tv[NT], lv[NL ? NL : 1u];
-#pragma unroll
-        for (uint32_t k = 0; k < NT; ++k) { const uint32_t j = threadIdx.x + k * (uint32_t)TB; tv[k] = j < 256u ? srgb_lut[j] : unorm_lut[j - 256u]; }
+        constexpr uint32_t LW = ZR_REST_ARG_LIGHTS * (uint32_t)(sizeof(ZrRestLight) / 4u), NL = LIGHT_LIST ? (LW + (uint32_t)TB - 1u) / (uint32_t)TB : 0u;
+        float tv[1536 / TB], lv[NL ? NL : 1u];
+        rest_tables_request<TB>(tv, srgb_lut, unorm_lut);
 #pragma unroll
         for (uint32_t k = 0; k < NL; ++k) { const uint32_t j = threadIdx.x + k * (uint32_t)TB; lv[k] = ((const float*)R.pt)[LW % (uint32_t)TB == 0u || j < LW ? j : 0u]; }
         if (ZR_REST_RECORDS_ONE_TRIP) rec = rest_records_fetch<WAVES>(rest, first_record);
-#pragma unroll
-        for (uint32_t k = 0; k < NT; ++k) tab[threadIdx.x + k * (uint32_t)TB] = tv[k];
+        rest_tables_store<TB>(tab, tv);
 #pragma unroll
         for (uint32_t k = 0; k < NL; ++k) { const uint32_t j = threadIdx.x + k * (uint32_t)TB; if (LW % (uint32_t)TB == 0u || j < LW) ((float*)lpt)[j] = lv[k]; }
     }
     const uint32_t tile = owned_tiles[tile_slot];
     __syncthreads();
     light_clear_next_slice<TB>(L);
-    const int tx0 = (int)(tile % L.tiles_x) * TILE, ty0 = (int)(tile / L.tiles_x) * TILE;
-    const zf3 cam = zr3(R.cam[0], R.cam[1], R.cam[2]);
-
-    // the workgroup's records: the tile's box, the first empty pixel (thread number, or NONE), this wave's empty pixels
+    // the workgroup's records: the tile's box, the first empty pixel (thread number, or REST_NONE), this wave's empty pixels
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     float blo[3] = { __builtin_inff(), __builtin_inff(), __builtin_inff() }, bhi[3] = { -__builtin_inff(), -__builtin_inff(), -__builtin_inff() };
-    uint32_t first = NONE;
+    uint32_t first = REST_NONE;
     unsigned long long mine = 0ull;
 #if ZR_REST_RECORDS_ONE_TRIP
-    if constexpr (LIGHT_LIST) {
-        // row_shr 1, 2, 4 fold exactly eight lanes into the last of them: lane 8 f + 7 holds field f over the records (min / max are exact
-        // in any order; the fill's -inf / +inf for a non-finite position pass through as they did)
-        int lo, hi;
-        { const int idn = 0x7F800000; int r = (int)rec; ZR_DPP_STEP(op_fmin, 0x111, 0xF); ZR_DPP_STEP(op_fmin, 0x112, 0xF); ZR_DPP_STEP(op_fmin, 0x114, 0xF); lo = r; }
-        { const int idn = (int)0xFF800000; int r = (int)rec; ZR_DPP_STEP(op_fmax, 0x111, 0xF); ZR_DPP_STEP(op_fmax, 0x112, 0xF); ZR_DPP_STEP(op_fmax, 0x114, 0xF); hi = r; }
-        for (int a = 0; a < 3; ++a) { blo[a] = zr_u2f((uint32_t)__builtin_amdgcn_readlane(lo, 8 * a + 7)); bhi[a] = zr_u2f((uint32_t)__builtin_amdgcn_readlane(hi, 8 * (3 + a) + 7)); }
-    }
-    {   // lanes 48 + w and 56 + w hold the two halves of record w's mask
-        const uint32_t lane = threadIdx.x & 63u;
-        const unsigned long long nz64 = __ballot(lane >= 48u && (lane & 7u) < WAVES && rec != 0u);
-        const uint32_t nz = ((uint32_t)(nz64 >> 48) | (uint32_t)(nz64 >> 56)) & 255u;      // bit w: record w holds an empty pixel
-        if (nz != 0u) {
-            const int w0 = __builtin_ctz(nz);
-            const unsigned long long em = (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 48 + w0) |
-                                          (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 56 + w0) << 32;
-            first = (uint32_t)w0 * 64u + (uint32_t)__builtin_ctzll(em);
-        }
-        mine = (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 48 + (int)wave) |
-               (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 56 + (int)wave) << 32;
-    }
+    if constexpr (LIGHT_LIST) rest_box_fold(rec, blo, bhi);
+    first = rest_first_empty<WAVES, false>(rec, blo, bhi);
+    mine = rest_mask_of(rec, (int)wave);
 #else      // (the control build of tests/test_kernel_table_rest_setup.py: a record at a time, a scalar load and a wait each)
     const ZrRestRecord* __restrict__ recs = (const ZrRestRecord*)(rest + ZR_REST_SLOT) + first_record;
 #pragma unroll 1      // (unrolled, the eight records' 64 scalar registers spill)
@@ -284,36 +362,16 @@ void k_lighting_rest(ZrLightParams L, ZrRestArgs R, const uint32_t* __restrict__
         if constexpr (LIGHT_LIST)
             for (int a = 0; a < 3; ++a) { blo[a] = __builtin_fminf(blo[a], recs[w].lo[a]); bhi[a] = __builtin_fmaxf(bhi[a], recs[w].hi[a]); }
         const unsigned long long em = (unsigned long long)recs[w].empty[0] | (unsigned long long)recs[w].empty[1] << 32;
-        if (em != 0ull && first == NONE) first = w * 64u + (uint32_t)__builtin_ctzll(em);
+        if (em != 0ull && first == REST_NONE) first = w * 64u + (uint32_t)__builtin_ctzll(em);
         if (w == wave) mine = em;
     }
 #endif
-    const int px = tx0 + (int)(i & (TILE - 1)), py = ty0 + (int)(i / TILE);
-    const bool inside = px < (int)L.W && py < (int)L.H;
-    const size_t p = (size_t)py * L.W + (size_t)px;
     unsigned long long amask = 0ull;      // the tile's light list (at most ZR_REST_ARG_LIGHTS = 64 lights: a lane each)
     if constexpr (LIGHT_LIST) {
         const uint32_t li = threadIdx.x & 63u;
         amask = __ballot(li < R.nPoint && light_listed(ArgLight{ &lpt[li < R.nPoint ? li : 0u] }, blo, bhi));
     }
-
-    const bool is_empty = ((mine >> (threadIdx.x & 63u)) & 1ull) != 0ull, owner = threadIdx.x == first;
-    if (inside && (!is_empty || owner)) {
-        const uint32_t sc = G.scene_color[p], A = G.gA[p], B = G.gB[p], Cc = G.gC[p];
-        const uint2 D = G.gD[p];
-        const LitPixel q = light_decode(u8, u10, sc, A, B, Cc, D);
-        const float4 ka = owner ? rest[0] : plane[p], kb = owner ? rest[1] : plane[(size_t)L.W * L.H + p];
-        zf3 Direct = zr3(ka.x, ka.y, ka.z); const float ShadowFactor = ka.w; const zf3 RefC = zr3(kb.x, kb.y, kb.z);
-        shade_points_arg<LIGHT_LIST>(L, R, amask, cam, q.BaseColor, q.Metallic, q.Roughness, q.N, q.Pw, Direct);
-        const zf3 Indirect = shade_indirect(q.BaseColor, q.Metallic, q.AO, ShadowFactor);
-        const uint32_t rgba = light_compose(L, q, Direct, Indirect, RefC, ShadowFactor, px, py);
-        if (owner) empty_px = rgba;
-        else light_emit<BACKGROUND>(L, G, tl, out, rgba, px, py, p, tile_slot, i);
-    }
-    if (first != NONE) {      // (the same for every thread of the workgroup: read from its records)
-        __syncthreads();
-        if (inside && is_empty) light_emit<BACKGROUND>(L, G, tl, out, empty_px, px, py, p, tile_slot, i);
-    }
+    rest_shade_part<LIGHT_LIST, BACKGROUND>(L, R, G, tab, out, plane, rest, amask, first, mine, tile, tile_slot, i, &empty_px);
 }
 
 // The resting frame's launch on a context whose target only this library writes (zr_settle.h): k_lighting_rest, except that a part no
@@ -328,15 +386,10 @@ void k_lighting_rest(ZrLightParams L, ZrRestArgs R, const uint32_t* __restrict__
 //    part returns behind it: no table load, no LDS, no barrier.  A part that shades pays a second trip for the tables.
 //    (-DZR_STAND_EARLY_EXIT=0: all of it in one trip and the exit behind the barrier - the losing order, DESIGN.md App. A.)
 //  - settled is the same for every wave of the workgroup: each reads the same records, the same mark, the same lights.
-//  - A part that shades does what k_lighting_rest does, through the same steps; behind the set-up's barrier (every wave has read the mark
+//  - A part that shades does what k_lighting_rest does, through the same steps (rest_shade_part); behind the set-up's barrier (every wave has read the mark
 //    by then) thread 0 sets the mark (reach == 0), takes it back (reach != 0 and it stood) or - the steady state - writes nothing.
 #ifndef ZR_STAND_EARLY_EXIT
 #define ZR_STAND_EARLY_EXIT 1
-#endif
-// (-DZR_STAND_WALK_LIST=0: the light loop walks every light instead of the ballot's list, as k_lighting_rest does below four lights -
-// the A/B of keeping that split; the ballot is built either way, the settle test needs it)
-#ifndef ZR_STAND_WALK_LIST
-#define ZR_STAND_WALK_LIST 1
 #endif
 template <bool BACKGROUND, int TB>
 __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(ZR_LIGHT_KEPT_WAVES, ZR_LIGHT_KEPT_WAVES)))
@@ -346,62 +399,34 @@ void k_lighting_stand(ZrLightParams L, ZrRestArgs R, const uint32_t* __restrict_
 {
     static_assert(sizeof(ZrLightParams) + sizeof(ZrRestArgs) + sizeof(GBufferPtrs) + 8 * sizeof(void*) + 256 /* the hidden arguments */ < 4096,
                   "k_lighting_stand: the argument block");
-    constexpr uint32_t PARTS = TILE_PIX / (uint32_t)TB, WAVES = (uint32_t)TB / 64u, NONE = 0xFFFFFFFFu, NT = 1536u / (uint32_t)TB;
+    constexpr uint32_t PARTS = TILE_PIX / (uint32_t)TB, WAVES = (uint32_t)TB / 64u;
     static_assert(WAVES <= 8u && 1536u % (uint32_t)TB == 0u, "k_lighting_stand: a part's records are a dword per lane");
-    __shared__ float tab[1536];          // k_lighting_rest's
+    __shared__ float tab[1536];          // rest_tables_load's
     __shared__ uint32_t empty_px;
-    float* const tl = tab; float* const u8 = tab + 256; float* const u10 = tab + 512;
     const uint32_t part = blockIdx.x % PARTS, tile_slot = blockIdx.x / PARTS;
     const uint32_t i = threadIdx.x + part * (uint32_t)TB;      // the thread's pixel among the tile's
     const uint32_t lane = threadIdx.x & 63u;
 #if !ZR_STAND_EARLY_EXIT
-    float tv[NT];
-#pragma unroll
-    for (uint32_t k = 0; k < NT; ++k) { const uint32_t j = threadIdx.x + k * (uint32_t)TB; tv[k] = j < 256u ? srgb_lut[j] : unorm_lut[j - 256u]; }
+    float tv[1536 / TB];
+    rest_tables_request<TB>(tv, srgb_lut, unorm_lut);
 #endif
     const uint32_t rec = rest_records_fetch<WAVES>(rest, tile_slot * ZR_REST_RECORDS_PER_TILE + part * WAVES);
     const ZrRestLight* const lights = R.pt;
     const ArgLight mine_light{ &lights[lane < R.nPoint ? lane : 0u] };
     const uint32_t mark = (uint32_t)__builtin_amdgcn_readfirstlane((int)marks[blockIdx.x]);
 #if !ZR_STAND_EARLY_EXIT
-#pragma unroll
-    for (uint32_t k = 0; k < NT; ++k) tab[threadIdx.x + k * (uint32_t)TB] = tv[k];
+    rest_tables_store<TB>(tab, tv);
     const uint32_t tile = owned_tiles[tile_slot];
     __syncthreads();
 #endif
 
-    // the workgroup's records, as in k_lighting_rest: the part's box, the first empty pixel (thread number, or NONE), this wave's empty pixels
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    float blo[3], bhi[3];
-    {
-        int lo, hi;
-        { const int idn = 0x7F800000; int r = (int)rec; ZR_DPP_STEP(op_fmin, 0x111, 0xF); ZR_DPP_STEP(op_fmin, 0x112, 0xF); ZR_DPP_STEP(op_fmin, 0x114, 0xF); lo = r; }
-        { const int idn = (int)0xFF800000; int r = (int)rec; ZR_DPP_STEP(op_fmax, 0x111, 0xF); ZR_DPP_STEP(op_fmax, 0x112, 0xF); ZR_DPP_STEP(op_fmax, 0x114, 0xF); hi = r; }
-        for (int a = 0; a < 3; ++a) { blo[a] = zr_u2f((uint32_t)__builtin_amdgcn_readlane(lo, 8 * a + 7)); bhi[a] = zr_u2f((uint32_t)__builtin_amdgcn_readlane(hi, 8 * (3 + a) + 7)); }
-    }
-    uint32_t first = NONE;
-    const unsigned long long nz64 = __ballot(lane >= 48u && (lane & 7u) < WAVES && rec != 0u);
-    const uint32_t nz = ((uint32_t)(nz64 >> 48) | (uint32_t)(nz64 >> 56)) & 255u;      // bit w: record w holds an empty pixel
-    if (nz != 0u) {
-        const int w0 = __builtin_ctz(nz);
-        const unsigned long long em = (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 48 + w0) |
-                                      (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 56 + w0) << 32;
-        first = (uint32_t)w0 * 64u + (uint32_t)__builtin_ctzll(em);
-        for (int a = 0; a < 3; ++a) { blo[a] = __builtin_fminf(blo[a], 0.0f); bhi[a] = __builtin_fmaxf(bhi[a], 0.0f); }      // the empty pixel is shaded at Pw = 0
-    }
-    const unsigned long long mine = (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 48 + (int)wave) |
-                                    (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 56 + (int)wave) << 32;
-    const unsigned long long reach = __ballot(lane < R.nPoint && light_listed(mine_light, blo, bhi));
-    if (gen != 0u && reach == 0ull && mark == gen) { light_clear_next_slice<TB>(L); return; }
+    const unsigned long long mine = rest_mask_of(rec, (int)wave);      // this wave's empty pixels
+    const RestDecision d = rest_decide<WAVES>(rec, mark, mine_light, R.nPoint, gen);
+    if (d.settled) { light_clear_next_slice<TB>(L); return; }
 
 #if ZR_STAND_EARLY_EXIT
-    {
-        float tv[NT];
-#pragma unroll
-        for (uint32_t k = 0; k < NT; ++k) { const uint32_t j = threadIdx.x + k * (uint32_t)TB; tv[k] = j < 256u ? srgb_lut[j] : unorm_lut[j - 256u]; }
-#pragma unroll
-        for (uint32_t k = 0; k < NT; ++k) tab[threadIdx.x + k * (uint32_t)TB] = tv[k];
-    }
+    rest_tables_load<TB>(tab, srgb_lut, unorm_lut);
     const uint32_t tile = owned_tiles[tile_slot];
     __syncthreads();
 #endif
@@ -409,32 +434,11 @@ void k_lighting_stand(ZrLightParams L, ZrRestArgs R, const uint32_t* __restrict_
     // so no wave can see this launch's own store and return from a part its siblings shade - and ahead of the pixel, so that nothing of
     // it lives across the shading.  (The next launch is behind the store by stream order.)
     if (gen != 0u && threadIdx.x == 0u) {
-        if (reach == 0ull) marks[blockIdx.x] = gen;            // (it did not stand, or the part had returned)
+        if (d.reach == 0ull) marks[blockIdx.x] = gen;            // (it did not stand, or the part had returned)
         else if (mark == gen) marks[blockIdx.x] = 0u;
     }
     light_clear_next_slice<TB>(L);
-    const int tx0 = (int)(tile % L.tiles_x) * TILE, ty0 = (int)(tile / L.tiles_x) * TILE;
-    const zf3 cam = zr3(R.cam[0], R.cam[1], R.cam[2]);
-    const int px = tx0 + (int)(i & (TILE - 1)), py = ty0 + (int)(i / TILE);
-    const bool inside = px < (int)L.W && py < (int)L.H;
-    const size_t p = (size_t)py * L.W + (size_t)px;
-    const bool is_empty = ((mine >> lane) & 1ull) != 0ull, owner = threadIdx.x == first;
-    if (inside && (!is_empty || owner)) {
-        const uint32_t sc = G.scene_color[p], A = G.gA[p], B = G.gB[p], Cc = G.gC[p];
-        const uint2 D = G.gD[p];
-        const LitPixel q = light_decode(u8, u10, sc, A, B, Cc, D);
-        const float4 ka = owner ? rest[0] : plane[p], kb = owner ? rest[1] : plane[(size_t)L.W * L.H + p];
-        zf3 Direct = zr3(ka.x, ka.y, ka.z); const float ShadowFactor = ka.w; const zf3 RefC = zr3(kb.x, kb.y, kb.z);
-        shade_points_arg<ZR_STAND_WALK_LIST != 0>(L, R, reach, cam, q.BaseColor, q.Metallic, q.Roughness, q.N, q.Pw, Direct);
-        const zf3 Indirect = shade_indirect(q.BaseColor, q.Metallic, q.AO, ShadowFactor);
-        const uint32_t rgba = light_compose(L, q, Direct, Indirect, RefC, ShadowFactor, px, py);
-        if (owner) empty_px = rgba;
-        else light_emit<BACKGROUND>(L, G, tl, out, rgba, px, py, p, tile_slot, i);
-    }
-    if (first != NONE) {      // (the same for every thread of the workgroup: read from its records)
-        __syncthreads();
-        if (inside && is_empty) light_emit<BACKGROUND>(L, G, tl, out, empty_px, px, py, p, tile_slot, i);
-    }
+    rest_shade_part<true, BACKGROUND>(L, R, G, tab, out, plane, rest, d.reach, d.first, mine, tile, tile_slot, i, &empty_px);
 }
 // k_lighting_stand with the part's decision made ONCE: by the workgroup's first wave, for its seven siblings.  What a part decides - the
 // box, the first empty pixel, the lights' ballot, whether it stands settled - is the same in every wave (every operand is), and in
@@ -443,7 +447,7 @@ void k_lighting_stand(ZrLightParams L, ZrRestArgs R, const uint32_t* __restrict_
 // 0 takes the one trip (records, mark, the lane's light), decides, and leaves in LDS what the others need: the ballot, the first empty
 // pixel, settled or not, and the eight waves' empty-pixel masks (lanes 48 - 63 store their record word as it came).  The others wait at
 // a barrier and read it back: a wave of a settled part runs its slice of the next map's clear and returns behind two LDS reads.
-//  - Values, comparisons and their order are k_lighting_stand's: every bit of every frame is.
+//  - Values, comparisons and their order are k_lighting_stand's - rest_decide is the one copy of them -: every bit of every frame is.
 //  - The mark has one reader now, wave 0, so thread 0 updates it right behind its own read: no sibling can see the store.
 //  - A part that shades pays one barrier more than k_lighting_stand (the set-up's second is the tables').
 template <bool BACKGROUND, int TB>
@@ -454,45 +458,26 @@ void k_lighting_lead(ZrLightParams L, ZrRestArgs R, const uint32_t* __restrict__
 {
     static_assert(sizeof(ZrLightParams) + sizeof(ZrRestArgs) + sizeof(GBufferPtrs) + 8 * sizeof(void*) + 256 /* the hidden arguments */ < 4096,
                   "k_lighting_lead: the argument block");
-    constexpr uint32_t PARTS = TILE_PIX / (uint32_t)TB, WAVES = (uint32_t)TB / 64u, NONE = 0xFFFFFFFFu, NT = 1536u / (uint32_t)TB;
+    constexpr uint32_t PARTS = TILE_PIX / (uint32_t)TB, WAVES = (uint32_t)TB / 64u;
     static_assert(WAVES <= 8u && 1536u % (uint32_t)TB == 0u, "k_lighting_lead: a part's records are a dword per lane");
-    __shared__ float tab[1536];          // k_lighting_rest's
+    __shared__ float tab[1536];          // rest_tables_load's
     __shared__ uint32_t empty_px;
     __shared__ uint32_t pub[20];         // wave 0's findings: [0], [1] the ballot, [2] the first empty pixel, [3] settled, [4 + w], [12 + w] the halves of wave w's mask
-    float* const tl = tab; float* const u8 = tab + 256; float* const u10 = tab + 512;
     const uint32_t part = blockIdx.x % PARTS, tile_slot = blockIdx.x / PARTS;
     const uint32_t i = threadIdx.x + part * (uint32_t)TB;      // the thread's pixel among the tile's
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (wave == 0u) {      // k_lighting_stand's decision, step for step
+    if (wave == 0u) {      // k_lighting_stand's trip and rest_decide, once
         const uint32_t rec = rest_records_fetch<WAVES>(rest, tile_slot * ZR_REST_RECORDS_PER_TILE + part * WAVES);
         const ZrRestLight* const lights = R.pt;
         const ArgLight mine_light{ &lights[lane < R.nPoint ? lane : 0u] };
         const uint32_t mark = (uint32_t)__builtin_amdgcn_readfirstlane((int)marks[blockIdx.x]);
-        float blo[3], bhi[3];
-        {
-            int lo, hi;
-            { const int idn = 0x7F800000; int r = (int)rec; ZR_DPP_STEP(op_fmin, 0x111, 0xF); ZR_DPP_STEP(op_fmin, 0x112, 0xF); ZR_DPP_STEP(op_fmin, 0x114, 0xF); lo = r; }
-            { const int idn = (int)0xFF800000; int r = (int)rec; ZR_DPP_STEP(op_fmax, 0x111, 0xF); ZR_DPP_STEP(op_fmax, 0x112, 0xF); ZR_DPP_STEP(op_fmax, 0x114, 0xF); hi = r; }
-            for (int a = 0; a < 3; ++a) { blo[a] = zr_u2f((uint32_t)__builtin_amdgcn_readlane(lo, 8 * a + 7)); bhi[a] = zr_u2f((uint32_t)__builtin_amdgcn_readlane(hi, 8 * (3 + a) + 7)); }
-        }
-        uint32_t first = NONE;
-        const unsigned long long nz64 = __ballot(lane >= 48u && (lane & 7u) < WAVES && rec != 0u);
-        const uint32_t nz = ((uint32_t)(nz64 >> 48) | (uint32_t)(nz64 >> 56)) & 255u;      // bit w: record w holds an empty pixel
-        if (nz != 0u) {
-            const int w0 = __builtin_ctz(nz);
-            const unsigned long long em = (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 48 + w0) |
-                                          (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rec, 56 + w0) << 32;
-            first = (uint32_t)w0 * 64u + (uint32_t)__builtin_ctzll(em);
-            for (int a = 0; a < 3; ++a) { blo[a] = __builtin_fminf(blo[a], 0.0f); bhi[a] = __builtin_fmaxf(bhi[a], 0.0f); }      // the empty pixel is shaded at Pw = 0
-        }
-        const unsigned long long reach = __ballot(lane < R.nPoint && light_listed(mine_light, blo, bhi));
-        const bool settled = gen != 0u && reach == 0ull && mark == gen;
+        const RestDecision d = rest_decide<WAVES>(rec, mark, mine_light, R.nPoint, gen);
         if (lane >= 48u) pub[4u + (lane - 48u)] = (lane & 7u) < WAVES ? rec : 0u;
         if (lane == 0u) {
-            pub[0] = (uint32_t)reach; pub[1] = (uint32_t)(reach >> 32); pub[2] = first; pub[3] = settled ? 1u : 0u;
-            if (gen != 0u && !settled) {
-                if (reach == 0ull) marks[blockIdx.x] = gen;            // (it did not stand)
+            pub[0] = (uint32_t)d.reach; pub[1] = (uint32_t)(d.reach >> 32); pub[2] = d.first; pub[3] = d.settled ? 1u : 0u;
+            if (gen != 0u && !d.settled) {
+                if (d.reach == 0ull) marks[blockIdx.x] = gen;            // (it did not stand)
                 else if (mark == gen) marks[blockIdx.x] = 0u;
             }
         }
@@ -501,41 +486,14 @@ void k_lighting_lead(ZrLightParams L, ZrRestArgs R, const uint32_t* __restrict__
     if (__builtin_amdgcn_readfirstlane((int)pub[3]) != 0) { light_clear_next_slice<TB>(L); return; }
     const unsigned long long reach = (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)pub[0]) |
                                      (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)pub[1]) << 32;
-    const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)pub[2]);
+    const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)pub[2]);      // (the same for every thread of the workgroup: wave 0's finding)
     const unsigned long long mine = (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)pub[4u + wave]) |
                                     (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)pub[12u + wave]) << 32;
-    {
-        float tv[NT];
-#pragma unroll
-        for (uint32_t k = 0; k < NT; ++k) { const uint32_t j = threadIdx.x + k * (uint32_t)TB; tv[k] = j < 256u ? srgb_lut[j] : unorm_lut[j - 256u]; }
-#pragma unroll
-        for (uint32_t k = 0; k < NT; ++k) tab[threadIdx.x + k * (uint32_t)TB] = tv[k];
-    }
+    rest_tables_load<TB>(tab, srgb_lut, unorm_lut);
     const uint32_t tile = owned_tiles[tile_slot];
     __syncthreads();
     light_clear_next_slice<TB>(L);
-    const int tx0 = (int)(tile % L.tiles_x) * TILE, ty0 = (int)(tile / L.tiles_x) * TILE;
-    const zf3 cam = zr3(R.cam[0], R.cam[1], R.cam[2]);
-    const int px = tx0 + (int)(i & (TILE - 1)), py = ty0 + (int)(i / TILE);
-    const bool inside = px < (int)L.W && py < (int)L.H;
-    const size_t p = (size_t)py * L.W + (size_t)px;
-    const bool is_empty = ((mine >> lane) & 1ull) != 0ull, owner = threadIdx.x == first;
-    if (inside && (!is_empty || owner)) {
-        const uint32_t sc = G.scene_color[p], A = G.gA[p], B = G.gB[p], Cc = G.gC[p];
-        const uint2 D = G.gD[p];
-        const LitPixel q = light_decode(u8, u10, sc, A, B, Cc, D);
-        const float4 ka = owner ? rest[0] : plane[p], kb = owner ? rest[1] : plane[(size_t)L.W * L.H + p];
-        zf3 Direct = zr3(ka.x, ka.y, ka.z); const float ShadowFactor = ka.w; const zf3 RefC = zr3(kb.x, kb.y, kb.z);
-        shade_points_arg<ZR_STAND_WALK_LIST != 0>(L, R, reach, cam, q.BaseColor, q.Metallic, q.Roughness, q.N, q.Pw, Direct);
-        const zf3 Indirect = shade_indirect(q.BaseColor, q.Metallic, q.AO, ShadowFactor);
-        const uint32_t rgba = light_compose(L, q, Direct, Indirect, RefC, ShadowFactor, px, py);
-        if (owner) empty_px = rgba;
-        else light_emit<BACKGROUND>(L, G, tl, out, rgba, px, py, p, tile_slot, i);
-    }
-    if (first != NONE) {      // (the same for every thread of the workgroup: wave 0's finding)
-        __syncthreads();
-        if (inside && is_empty) light_emit<BACKGROUND>(L, G, tl, out, empty_px, px, py, p, tile_slot, i);
-    }
+    rest_shade_part<true, BACKGROUND>(L, R, G, tab, out, plane, rest, reach, first, mine, tile, tile_slot, i, &empty_px);
 }
 #endif
 
@@ -659,40 +617,24 @@ void zr_launch_lighting(const ZrLightParams& L, const XkView* view, const uint32
 #undef ZR_LAUNCH_LIGHTING_TB
 }
 bool zr_lighting_rest_available() { return ZR_PIXELS_PER_THREAD == 1; }
-void zr_launch_lighting_rest(const ZrLightParams& L, const ZrRestArgs& R, const uint32_t* owned_tiles, uint32_t n_owned, const GBufferPtrs& G,
-                             const float* lut, const float* unorm_lut, uint32_t* out, hipStream_t s, const float4* plane, const float4* rest)
-{
-#if ZR_PIXELS_PER_THREAD == 1
-    if (n_owned == 0) return;
-#define ZR_LAUNCH_REST(LL, BG) hipLaunchKernelGGL((k_lighting_rest<LL, BG, ZR_LIGHT_KEPT_TB>), dim3(n_owned * (TILE_PIX / ZR_LIGHT_KEPT_TB)), dim3(ZR_LIGHT_KEPT_TB), 0, s, L, R, owned_tiles, G, lut, unorm_lut, out, plane, rest)
-    if (L.light_list) { if (L.bg_enabled) ZR_LAUNCH_REST(true, true); else ZR_LAUNCH_REST(true, false); }
-    else { if (L.bg_enabled) ZR_LAUNCH_REST(false, true); else ZR_LAUNCH_REST(false, false); }
-#undef ZR_LAUNCH_REST
-#endif
-}
+// The resting frame's launch.  which: every pixel (k_lighting_rest), or the parts no point light reaches left as they stand, decided in
+// every wave (k_lighting_stand) or once a part (k_lighting_lead): the same frame, the same marks.
 // marks: a word per workgroup of the launch (n_owned * zr_lighting_stand_parts()); gen: zr_settle.h's generation, 0 = off
 uint32_t zr_lighting_stand_parts() { return TILE_PIX / ZR_LIGHT_KEPT_TB; }
-void zr_launch_lighting_stand(const ZrLightParams& L, const ZrRestArgs& R, const uint32_t* owned_tiles, uint32_t n_owned, const GBufferPtrs& G,
-                              const float* lut, const float* unorm_lut, uint32_t* out, hipStream_t s, const float4* plane, const float4* rest,
-                              uint32_t* marks, uint32_t gen)
-{
-#if ZR_PIXELS_PER_THREAD == 1
-    if (n_owned == 0) return;
-    const dim3 grid(n_owned * (TILE_PIX / ZR_LIGHT_KEPT_TB)), block(ZR_LIGHT_KEPT_TB);
-    if (L.bg_enabled) hipLaunchKernelGGL((k_lighting_stand<true, ZR_LIGHT_KEPT_TB>), grid, block, 0, s, L, R, owned_tiles, G, lut, unorm_lut, out, plane, rest, marks, gen);
-    else hipLaunchKernelGGL((k_lighting_stand<false, ZR_LIGHT_KEPT_TB>), grid, block, 0, s, L, R, owned_tiles, G, lut, unorm_lut, out, plane, rest, marks, gen);
-#endif
-}
-// ... with the part's decision made by the workgroup's first wave (k_lighting_lead): the same arguments, the same marks, the same frame
-void zr_launch_lighting_lead(const ZrLightParams& L, const ZrRestArgs& R, const uint32_t* owned_tiles, uint32_t n_owned, const GBufferPtrs& G,
+void zr_launch_lighting_rest(const ZrLightParams& L, const ZrRestArgs& R, const uint32_t* owned_tiles, uint32_t n_owned, const GBufferPtrs& G,
                              const float* lut, const float* unorm_lut, uint32_t* out, hipStream_t s, const float4* plane, const float4* rest,
-                             uint32_t* marks, uint32_t gen)
+                             ZrRestLaunch which, uint32_t* marks, uint32_t gen)
 {
 #if ZR_PIXELS_PER_THREAD == 1
     if (n_owned == 0) return;
     const dim3 grid(n_owned * (TILE_PIX / ZR_LIGHT_KEPT_TB)), block(ZR_LIGHT_KEPT_TB);
-    if (L.bg_enabled) hipLaunchKernelGGL((k_lighting_lead<true, ZR_LIGHT_KEPT_TB>), grid, block, 0, s, L, R, owned_tiles, G, lut, unorm_lut, out, plane, rest, marks, gen);
-    else hipLaunchKernelGGL((k_lighting_lead<false, ZR_LIGHT_KEPT_TB>), grid, block, 0, s, L, R, owned_tiles, G, lut, unorm_lut, out, plane, rest, marks, gen);
+    constexpr int TB = ZR_LIGHT_KEPT_TB;
+    const bool bg = L.bg_enabled;
+    auto launch = [&](auto kernel, auto... more) { hipLaunchKernelGGL(kernel, grid, block, 0, s, L, R, owned_tiles, G, lut, unorm_lut, out, plane, rest, more...); };
+    if (which == ZR_REST_LEAD) launch(bg ? k_lighting_lead<true, TB> : k_lighting_lead<false, TB>, marks, gen);
+    else if (which == ZR_REST_STAND) launch(bg ? k_lighting_stand<true, TB> : k_lighting_stand<false, TB>, marks, gen);
+    else if (L.light_list) launch(bg ? k_lighting_rest<true, true, TB> : k_lighting_rest<true, false, TB>);
+    else launch(bg ? k_lighting_rest<false, true, TB> : k_lighting_rest<false, false, TB>);
 #endif
 }
 void zr_launch_gbuffer_vis(const ZrLightParams& L, const XkView* view, const GBufferPtrs& G, const float* shadowmap, const CubeDesc& C,

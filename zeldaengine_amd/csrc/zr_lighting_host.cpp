@@ -167,16 +167,17 @@ int lighting_pass(zr_ctx* c)
         zr_launch_forward(c->pass[1], L, F.view, c->d_objs, c->d_owned, c->n_owned, F.G, shadow_buf(c), c->cube, c->d_lut, c->d_unorm_lut, frame_out, s);
     } else if (by_arg) {
         ZrRestArgs R; rest_args(c, &R);
-        if (settle_allowed(c)) {
+        // (the same frame and the same marks either way: k_lighting_lead decides a part once, k_lighting_stand in each of its waves)
+        const ZrRestLaunch which = !settle_allowed(c) ? ZR_REST_EVERY_PIXEL : c->lk.lead_off ? ZR_REST_STAND : ZR_REST_LEAD;
+        uint32_t gen = 0u;
+        if (which != ZR_REST_EVERY_PIXEL) {
             zr_ctx::SettleKey K; settle_key(c, L, R, frame_out, &K);
             ZrSettleFacts sf; sf.stand = true; sf.key_same = memcmp(&K, &c->lk.settle_key, sizeof K) == 0;
             const ZrSettleStep step = zr_settle_step(c->lk.settle, sf);
             if (step.wipe) HIPCHK(c, hipMemsetAsync(c->lk.marks, 0, (size_t)c->n_owned * zr_lighting_stand_parts() * sizeof(uint32_t), s));
-            // (the same frame and the same marks either way: k_lighting_lead decides a part once, k_lighting_stand in each of its waves)
-            (c->lk.lead_off ? zr_launch_lighting_stand : zr_launch_lighting_lead)(L, R, c->d_owned, c->n_owned, F.G, c->d_lut, c->d_unorm_lut, frame_out, s, c->lk.plane, c->lk.rest, c->lk.marks, step.gen);
-            c->lk.settle = step.next; c->lk.settle_key = K; stood = true;
-        } else
-            zr_launch_lighting_rest(L, R, c->d_owned, c->n_owned, F.G, c->d_lut, c->d_unorm_lut, frame_out, s, c->lk.plane, c->lk.rest);
+            gen = step.gen; c->lk.settle = step.next; c->lk.settle_key = K; stood = true;
+        }
+        zr_launch_lighting_rest(L, R, c->d_owned, c->n_owned, F.G, c->d_lut, c->d_unorm_lut, frame_out, s, c->lk.plane, c->lk.rest, which, c->lk.marks, gen);
         c->lk.by_arg++;
     } else {
         zr_launch_lighting(L, F.view, c->d_owned, c->n_owned, F.G, shadow_buf(c), c->cube, c->d_lut, c->d_unorm_lut, frame_out, s, mode, c->lk.plane, c->lk.rest);

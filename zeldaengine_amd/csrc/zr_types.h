@@ -361,18 +361,14 @@ void zr_launch_lighting(const ZrLightParams& L, const XkView* view, const uint32
                         uint32_t* out, hipStream_t s, ZrLightMode mode = ZR_LIGHT_PLAIN, float4* plane = nullptr, float4* rest = nullptr);
 // The KEPT pass with its uniforms by argument and the empty pixel's colour computed in the launch ("The schedule").
 bool zr_lighting_rest_available();      // (a build with one pixel per thread)
-void zr_launch_lighting_rest(const ZrLightParams& L, const ZrRestArgs& R, const uint32_t* owned_tiles, uint32_t n_owned, const GBufferPtrs& G,
-                             const float* lut, const float* unorm_lut, uint32_t* out, hipStream_t s, const float4* plane, const float4* rest);
-// ... with the parts no point light reaches left as they stand (k_lighting_stand; marks: a word per workgroup, n_owned *
-// zr_lighting_stand_parts() of them; gen: zr_settle.h's generation, 0 = nothing settles)
+// which: every pixel shaded (k_lighting_rest), or the parts no point light reaches left as they stand - decided in every wave
+// (k_lighting_stand) or once, by the workgroup's first (k_lighting_lead): the same frame, the same marks.  marks: a word per workgroup,
+// n_owned * zr_lighting_stand_parts() of them; gen: zr_settle.h's generation, 0 = nothing settles (ZR_REST_EVERY_PIXEL reads neither)
+enum ZrRestLaunch : uint32_t { ZR_REST_EVERY_PIXEL = 0, ZR_REST_STAND = 1, ZR_REST_LEAD = 2 };
 uint32_t zr_lighting_stand_parts();
-void zr_launch_lighting_stand(const ZrLightParams& L, const ZrRestArgs& R, const uint32_t* owned_tiles, uint32_t n_owned, const GBufferPtrs& G,
-                              const float* lut, const float* unorm_lut, uint32_t* out, hipStream_t s, const float4* plane, const float4* rest,
-                              uint32_t* marks, uint32_t gen);
-// ... and the part's decision made once, by the workgroup's first wave (k_lighting_lead): the same arguments, the same frame
-void zr_launch_lighting_lead(const ZrLightParams& L, const ZrRestArgs& R, const uint32_t* owned_tiles, uint32_t n_owned, const GBufferPtrs& G,
+void zr_launch_lighting_rest(const ZrLightParams& L, const ZrRestArgs& R, const uint32_t* owned_tiles, uint32_t n_owned, const GBufferPtrs& G,
                              const float* lut, const float* unorm_lut, uint32_t* out, hipStream_t s, const float4* plane, const float4* rest,
-                             uint32_t* marks, uint32_t gen);
+                             ZrRestLaunch which, uint32_t* marks, uint32_t gen);
 // forward variant (SH/Base.frag): shades the winners recorded in G.prim with the camera pass's own parameter block
 void zr_launch_forward(const ZrPass& P, const ZrLightParams& L, const XkView* view, const ZrObject* objs, const uint32_t* owned_tiles, uint32_t n_owned,
                        const GBufferPtrs& G, const float* shadowmap, const CubeDesc& C, const float* lut, const float* unorm_lut, uint32_t* out, hipStream_t s);
