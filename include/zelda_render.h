@@ -679,6 +679,47 @@ int  zr_instance_coverage(zr_ctx* ctx, uint32_t* counts, size_t bytes);
  * sync (the pattern of zr_copy_frame_async).  The frame after next, which reuses that frame's winner plane, waits for it. */
 int  zr_instance_coverage_async(zr_ctx* ctx, void* counts_dev, size_t bytes);
 
+/* --- casting rays ("Casting rays"; DESIGN.md §5, "Casting rays") ---
+ * The nearest triangle along each ray: object, instance, triangle, the ray parameter t, the barycentric weights and the face normal.
+ * Rays see the scene AS THE FRAME ENQUEUED LAST DREW IT, like the identity queries: that frame's draw table, instance records, vertex
+ * sets and model matrix (a corner's world position is the camera pass's own arithmetic, bit for bit); updates made since take effect
+ * with the next zr_render.  Hidden objects and instances are not hit; the skydome is no object and is never hit.  Id capture is not
+ * needed.  A rank context (tile_world > 1) and the native multi-GPU host hold the whole scene and answer like any other context.
+ * The rule (one statement for host and device, csrc/zr_raycast.h): a watertight float32 / float64 test - a ray through a closed
+ * surface cannot slip between two triangles that share an edge; the hit with the least t wins, ties go to the least global primitive
+ * id (ZR_IDS_PRIMITIVE's numbering).  The hit point is origin + t * dir = (1 - u - v) A + u B + v C.  A ray with a non-finite
+ * component, dir == 0, a NaN bound or t_min > t_max hits nothing and is flagged ZR_RAY_INVALID.
+ * Out of scope: an acceleration structure over instances (every ray tests every instance's bounding sphere: fine for an editor's rays
+ * and tens of thousands of instances), the skydome, interpolated normals / UVs / materials, a scene no frame has drawn. */
+typedef struct zr_ray     { float origin[3]; float t_min; float dir[3]; float t_max; } zr_ray;          /* 32 bytes */
+typedef struct zr_ray_hit { uint32_t object, instance;   /* as ZR_IDS_OBJECT; 0xFFFFFFFF both = nothing hit */
+                            uint32_t triangle;           /* draw-order triangle within the instance, as zr_hit::triangle (0xFFFFFFFF: none) */
+                            uint32_t flags;              /* ZR_RAY_HIT | ZR_RAY_HIT_BACK | ZR_RAY_INVALID */
+                            float t, u, v; uint32_t reserved;   /* 0 */
+                            float normal[3]; uint32_t reserved2; } zr_ray_hit;   /* 48 bytes; normal = (B-A) x (C-A), not normalised */
+#define ZR_RAY_HIT       1u   /* hit flag: something was hit */
+#define ZR_RAY_HIT_BACK  2u   /* hit flag: from behind - dir and (B-A) x (C-A) point the same way (the side the camera pass culls) */
+#define ZR_RAY_INVALID   4u   /* hit flag: the ray itself was refused; nothing hit */
+#define ZR_RAY_CULL_BACK 1u   /* query flag: BACK hits do not count */
+#define ZR_RAY_ANY_HIT   2u   /* query flag: only flags & ZR_RAY_HIT is defined (line of sight); every other field reads as a miss */
+#define ZR_RAY_NO_BOUNDS 4u   /* query flag, parity A/B: test every triangle of every shown instance, no sphere or box rejects anything */
+/* n rays, n records (bytes == n * 48).  Calls zr_finish first and passes its error on.  ZR_ERR_ARG: n > 0 with a null pointer, a wrong
+ * byte count, an unknown flag bit, n above 2^24; then ZR_ERR_STATE: no finished frame enqueued (also after zr_resize until the next
+ * frame), the scene changed after the last frame, between the stages of a frame; then n == 0: ZR_OK. */
+int  zr_raycast(zr_ctx* ctx, const zr_ray* rays, uint32_t n, uint32_t flags, zr_ray_hit* hits, size_t bytes);
+/* The same from and into caller-owned DEVICE buffers (16-byte aligned, else ZR_ERR_ARG), stream-ordered on the render stream behind the
+ * frame enqueued last and ahead of whatever the next zr_render puts there, with no host sync (the first cast after the object list
+ * changed builds a small table and drains once).  The frame after next, which rewrites what this launch reads, waits for it. */
+int  zr_raycast_async(zr_ctx* ctx, const void* rays_dev, uint32_t n, uint32_t flags, void* hits_dev);
+/* The world-space ray of the uniforms set last through frame position (px, py) - pixel centres at +0.5, the camera pass's viewport
+ * mapping: origin on the near plane, dir = the far-plane point minus the origin, t_min = 0, t_max = 1; float64 from the inverse of
+ * Proj * View, rounded once.  ZR_ERR_STATE without uniforms or when Proj * View has no inverse. */
+int  zr_camera_ray(zr_ctx* ctx, float px, float py, zr_ray* out);
+/* The rule on the host, context-free: n_rays rays against n_tris triangles of 9 floats (A, B, C), primitive id = the triangle's
+ * index; a hit's object and instance are 0.  Either count may be 0. */
+int  zr_ray_triangles(const zr_ray* rays, uint32_t n_rays, const float* tris /* 9 floats each */, uint32_t n_tris,
+                      uint32_t flags, zr_ray_hit* hits);
+
 /* --- multi-GPU screen-tile partition --- */
 /* Owner of tile (tx, ty) in a world of `world` ranks, and the list of tiles a rank owns in increasing tile index (= its slot order
  * in the packed buffer); slots_per_rank = the largest count over all ranks (every rank contributes that many slots to the all-gather).

@@ -8,7 +8,7 @@
 //   zelda_headless --root DIR [--world FILE.json] [--livelink PORT [--wait-ms MS]] [--meshlet FILE.meshlet --profab NAME]
 //                  [--size WxH] [--shadow N] [--frames N] [--roll-light-step F] [--debug-view V] [--out FRAME.ppm] [--device D]
 //                  [--pick X,Y[,W,H] [--highlight]] [--incremental] [--delta | --delta-packed] [--scale S] [--resize-at FRAME:WxH]
-//                  [--overlay FILE] [--overlay-box]
+//                  [--overlay FILE] [--overlay-box] [--raycast X,Y]
 // --resize-at FRAME:WxH gives the live context a new extent ahead of frame FRAME (zr_resize), as a host whose window changes size does:
 // nothing is loaded again, it prints `resized <W>x<H>`, and with --delta, --delta-packed or --scale the client copy and the delivery
 // buffers follow the new (scaled) extent - the next delivery is a full one.
@@ -24,6 +24,9 @@
 // read with zr_read_color_scaled and it prints `scaled <Wd>x<Hd>` per frame.  --out writes the client copy at the scaled extent.
 // --pick keeps the last frame's per-pixel winners (zr_set_id_capture) and prints what zr_pick finds in the rectangle (default 1 x 1),
 // one JSON line per hit, nearest first - what an editor does on a click.
+// --raycast X,Y casts the camera's ray through the centre of pixel (X, Y) into the scene of the last frame (zr_camera_ray at X + 0.5,
+// Y + 0.5, then zr_raycast; no id capture needed) and prints the hit as one JSON line in --pick's format plus t, the weights, the world
+// position and the face normal - `{"hit": 0}` for a miss.
 // --highlight (with --pick) shows the selection: the pick is made after the first frame, its hits go into the highlight set
 // (zr_highlight_set) and every following frame is delivered highlighted (zelda_render.h, "highlighting a selection") through whichever of
 // --delta, --delta-packed and --scale is chosen - zr_set_frame_delta_highlight, or zr_read_color_highlighted at the scale, which prints
@@ -63,6 +66,7 @@ int main(int argc, char** argv)
     float roll_step = 0.0f;
     bool pick = false, incremental = false, delta = false, packed = false, highlight = false, overlay_box = false; uint32_t px = 0, py = 0, pw = 1, ph = 1;
     uint32_t resize_at = 0xFFFFFFFFu, RW = 0, RH = 0;
+    bool raycast = false; uint32_t rx = 0, ry = 0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
@@ -92,6 +96,7 @@ int main(int argc, char** argv)
             if (got != 2 && got != 4) { fprintf(stderr, "--pick X,Y[,W,H]\n"); return 2; }
             pick = true;
         }
+        else if (a == "--raycast") { if (sscanf(next(), "%u,%u", &rx, &ry) != 2) { fprintf(stderr, "--raycast X,Y\n"); return 2; } raycast = true; }
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     if (highlight && !pick) { fprintf(stderr, "--highlight needs --pick X,Y[,W,H]\n"); return 2; }
@@ -284,6 +289,18 @@ int main(int argc, char** argv)
     printf("frames %u  %.3f ms/frame  objects %u  meshlet-instances %llu  camera survivors %llu  covered pixels %llu\n", frames, ms / frames, n_obj,
            (unsigned long long)st.work_items[1], (unsigned long long)st.survivors[1], (unsigned long long)st.covered_pixels);
     if (pick && !highlight && !overlay_box && do_pick()) return fail(c, "zr_pick", rc);
+    if (raycast) {                                        // the camera's ray through the pixel's centre, into the scene of the last frame
+        zr_ray ray; zr_ray_hit h;
+        if ((rc = zr_camera_ray(c, (float)rx + 0.5f, (float)ry + 0.5f, &ray))) return fail(c, "zr_camera_ray", rc);
+        if ((rc = zr_raycast(c, &ray, 1u, 0u, &h, sizeof h))) return fail(c, "zr_raycast", rc);
+        if (!(h.flags & ZR_RAY_HIT)) printf("{\"hit\": 0, \"x\": %u, \"y\": %u}\n", rx, ry);
+        else
+            printf("{\"hit\": 1, \"object\": %u, \"instance\": %u, \"triangle\": %u, \"x\": %u, \"y\": %u, \"back\": %u, \"t\": %.9g, \"u\": %.9g, \"v\": %.9g, "
+                   "\"position\": [%.9g, %.9g, %.9g], \"normal\": [%.9g, %.9g, %.9g]}\n",
+                   h.object, h.instance, h.triangle, rx, ry, (h.flags & ZR_RAY_HIT_BACK) ? 1u : 0u, (double)h.t, (double)h.u, (double)h.v,
+                   (double)ray.origin[0] + (double)h.t * (double)ray.dir[0], (double)ray.origin[1] + (double)h.t * (double)ray.dir[1],
+                   (double)ray.origin[2] + (double)h.t * (double)ray.dir[2], (double)h.normal[0], (double)h.normal[1], (double)h.normal[2]);
+    }
     if (!out.empty()) {
         std::vector<uint8_t> rgba((size_t)DW * DH * 4);
         if (delta || scaled || highlight || lines) rgba = client;

@@ -131,6 +131,33 @@ REST_SETTLE_SIGNATURES = {
     "zr_get_rest_settled": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
     "zr_get_rest_settled_parts": [C.c_void_p, C.c_void_p, C.c_size_t],
 }
+# casting rays (include/zelda_render.h, "casting rays"): numpy mirrors of zr_ray / zr_ray_hit - what Renderer.raycast takes and returns
+RAY = np.dtype([("origin", "<f4", 3), ("t_min", "<f4"), ("dir", "<f4", 3), ("t_max", "<f4")])
+RAY_RECORD = np.dtype([("object", "<u4"), ("instance", "<u4"), ("triangle", "<u4"), ("flags", "<u4"), ("t", "<f4"), ("u", "<f4"), ("v", "<f4"),
+                    ("reserved", "<u4"), ("normal", "<f4", 3), ("reserved2", "<u4")])
+
+
+class Ray(C.Structure):
+    """ctypes mirror of zr_ray (32 bytes)"""
+    _fields_ = [("origin", C.c_float * 3), ("t_min", C.c_float), ("dir", C.c_float * 3), ("t_max", C.c_float)]
+
+
+class RayHit(C.Structure):
+    """ctypes mirror of zr_ray_hit (48 bytes)"""
+    _fields_ = [("object", C.c_uint32), ("instance", C.c_uint32), ("triangle", C.c_uint32), ("flags", C.c_uint32), ("t", C.c_float), ("u", C.c_float),
+                ("v", C.c_float), ("reserved", C.c_uint32), ("normal", C.c_float * 3), ("reserved2", C.c_uint32)]
+
+
+assert RAY.itemsize == C.sizeof(Ray) == 32 and RAY_RECORD.itemsize == C.sizeof(RayHit) == 48
+RAY_HIT_FLAG, RAY_HIT_BACK, RAY_INVALID = 1, 2, 4            # ZR_RAY_HIT, ZR_RAY_HIT_BACK, ZR_RAY_INVALID: RayHit.flags
+RAY_CULL_BACK, RAY_ANY_HIT, RAY_NO_BOUNDS = 1, 2, 4          # ZR_RAY_CULL_BACK, ZR_RAY_ANY_HIT, ZR_RAY_NO_BOUNDS: the query's flags
+RAY_MAX_RAYS = 1 << 24
+RAYCAST_SIGNATURES = {
+    "zr_raycast": [vp_, vp_, u32_, u32_, vp_, C.c_size_t],
+    "zr_raycast_async": [vp_, vp_, u32_, u32_, vp_],
+    "zr_camera_ray": [vp_, C.c_float, C.c_float, C.POINTER(Ray)],
+    "zr_ray_triangles": [vp_, u32_, vp_, u32_, u32_, vp_],
+}
 # the extent of a live context (include/zelda_render.h, "lifetime")
 EXTENT_SIGNATURES = {
     "zr_resize": [vp_, u32_, u32_],
@@ -142,6 +169,15 @@ del vp_, u32_
 def make_highlight_style(outline=(255, 160, 0, 255), fill=(255, 160, 0, 0), radius=2):
     """zr_highlight_style from (R, G, B, opacity) tuples and the outline's width; the defaults are the library's"""
     return HighlightStyle((C.c_uint8 * 4)(*outline), (C.c_uint8 * 4)(*fill), radius, 0)
+
+
+def make_rays(origins, dirs, t_min=0.0, t_max=np.inf):
+    """A RAY array from (n, 3) origins and directions and bounds (scalars or (n,) arrays)"""
+    o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros(len(o), dtype=RAY)
+    out["origin"], out["dir"] = o, np.asarray(dirs, dtype=np.float32).reshape(-1, 3)
+    out["t_min"], out["t_max"] = t_min, t_max
+    return out
 
 
 def make_overlay_style(depth_bias=0.0, hidden_opacity=0):

@@ -435,6 +435,9 @@ struct zr_ctx {
         ZrOwn mem; zr_overlay_segment* d_seg = nullptr; ZrOvRecord* recs = nullptr; uint32_t* rects = nullptr; size_t cap = 0;
         uint32_t* frame = nullptr;
     } ov;
+    // Casting rays (zr_raycast_host.cpp, zr_raycast.hip): the host form's staging on the device - cap rays in, cap records out - through
+    // an owner of its own, grown on demand
+    struct Rays { ZrOwn mem; zr_ray* rays = nullptr; zr_ray_hit* hits = nullptr; size_t cap = 0; } rays;
 };
 
 // What the deliveries of changes compare, list and size their buffers for: the frame at the delta scale (zr_ctx::Delta::scale), in tiles
@@ -553,12 +556,15 @@ int lighting_pass(zr_ctx* c);
 // zr_readback.cpp
 int ids_prepare(zr_ctx* c);            // frame_begin of a captured frame: the census's draw table
 // The frame enqueued last kept its winners and still describes the scene (else the refusal, in `what`'s name); sync: finish it first
-int ids_ready(zr_ctx* c, const char* what, bool sync);
+// (capture = false: a query that reads no winner plane - a ray cast - asks for the rest)
+int ids_ready(zr_ctx* c, const char* what, bool sync, bool capture = true);
 ZrIdsArgs ids_args(zr_ctx* c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h);      // the census's arguments for a rectangle of that frame
 size_t ids_slot_count(const zr_ctx* c);                                              // the slots of zr_instance_coverage
 // A reader of that frame's copy - its winner plane (the census, the highlight's mask) or its GBuffer depth (the overlay) - was enqueued on
 // the render stream: the frame that resolves into that copy next (the one after next, where it draws its camera pass) waits for it
-int ids_reader_enqueued(zr_ctx* c);
+// (both: the reader read what EITHER parity's next drawn frame may rewrite at its head - the instance planes and mesh sets of a scene that
+// no update has split into parities yet, a ray cast - so both copies note it and the next frame waits as well)
+int ids_reader_enqueued(zr_ctx* c, bool both = false);
 // zr_highlight_host.cpp: the device bitset brought up to the host's set, on the render stream (a highlighted delivery, ahead of its launches)
 int hl_upload(zr_ctx* c);
 // zr_overlay_host.cpp: the overlay stage of a delivery on the render stream - the list brought up to date, set up for the camera of the

@@ -32,3 +32,15 @@ void zr_launch_highlight_mask(const uint32_t* prim_plane, const ZrIdsDraw* draws
                               uint32_t H, hipStream_t st);
 void zr_launch_highlight_apply(const uint32_t* frame, const unsigned long long* bit_plane, uint32_t* dst, uint32_t W, uint32_t H, const zr_highlight_style& style,
                                hipStream_t st);
+
+// zr_raycast.hip: casting rays (zr_raycast.h has the rule).  rays / hits: n_rays records each, 16-byte aligned; objs: the draw table of
+// the frame enqueued last, of which the first n_draws records are the scene's (the skydome's, last, is never visited) with n_inst
+// instances over all of them; draws: the census's table (draw order -> add order); M, m_scale: that frame's model matrix and the
+// bound of its stretch (ZrPass::M, m_scale); flags: ZR_RAY_*, the query's
+struct ZrRayArgs {
+    const zr_ray* rays; zr_ray_hit* hits;
+    const ZrObject* objs; const ZrIdsDraw* draws;
+    uint32_t n_rays, n_draws, n_inst, flags;
+    float M[16]; float m_scale;
+};
+void zr_launch_raycast(const ZrRayArgs& A, hipStream_t s);

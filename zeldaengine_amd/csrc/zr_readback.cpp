@@ -310,19 +310,23 @@ extern "C" int zr_set_id_capture(zr_ctx* c, int enable)
     });
 }
 
-// The frame enqueued last kept its winners and still describes the scene; `sync`: finish it first (its overflow is the query's error).
-int ids_ready(zr_ctx* c, const char* what, bool sync)
+// The frame enqueued last kept its winners (capture; a ray cast needs none) and still describes the scene; `sync`: finish it first (its
+// overflow is the query's error).
+int ids_ready(zr_ctx* c, const char* what, bool sync, bool capture)
 {
     if (!c->rendered || c->stage != 0) return zr_fail(c, ZR_ERR_STATE, std::string(what) + ": no finished frame enqueued");
-    if (!c->ids_frame) return zr_fail(c, ZR_ERR_STATE, std::string(what) + ": the last frame was rendered without id capture (zr_set_id_capture)");
+    if (capture && !c->ids_frame) return zr_fail(c, ZR_ERR_STATE, std::string(what) + ": the last frame was rendered without id capture (zr_set_id_capture)");
     if (c->ids.gen != c->scene_gen) return zr_fail(c, ZR_ERR_STATE, std::string(what) + ": the scene changed after the last frame");
     HIPCHK(c, hipSetDevice(c->device));
     return sync ? zr_finish(c) : ZR_OK;
 }
-int ids_reader_enqueued(zr_ctx* c)
+int ids_reader_enqueued(zr_ctx* c, bool both)
 {
-    HIPCHK(c, hipEventRecord(c->fc[c->fcur].ev_ids, c->stream));
-    c->fc[c->fcur].ids_wait = true;
+    for (int k = 0; k < 2; ++k) {
+        if (!both && k != c->fcur) continue;
+        HIPCHK(c, hipEventRecord(c->fc[k].ev_ids, c->stream));
+        c->fc[k].ids_wait = true;
+    }
     return ZR_OK;
 }
 ZrIdsArgs ids_args(zr_ctx* c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h)

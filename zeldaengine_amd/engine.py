@@ -65,6 +65,7 @@ def lib():
         **abi.HIGHLIGHT_SIGNATURES,
         **abi.OVERLAY_SIGNATURES,
         **abi.EXTENT_SIGNATURES,
+        **abi.RAYCAST_SIGNATURES,
         **abi.REST_SETTLE_SIGNATURES,
         "zr_set_cubemap": [vp, vp, u32],
         "zr_set_skydome": [vp, vp, u32, vp, u32, vp],
@@ -348,6 +349,25 @@ def frame_overlay(img, depth, pvm, segments, style=None):
     if rc:
         raise ZeldaRenderError(rc, "zr_frame_overlay: bad argument")
     return out
+
+
+def _rays(rays):
+    rays = np.ascontiguousarray(rays)
+    if rays.dtype != abi.RAY:
+        raise TypeError("rays: an abi.RAY array (abi.make_rays)")
+    return rays.reshape(-1)
+
+
+def ray_triangles(rays, tris, flags=0):
+    """The ray / triangle rule on the host, context-free (zr_ray_triangles): abi.RAY rays against (n, 3, 3) float32 world triangles ->
+    abi.RAY_RECORD records; a hit's triangle is the index into tris, its object and instance 0."""
+    rays = _rays(rays)
+    tris = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 9)
+    hits = np.zeros(len(rays), dtype=abi.RAY_RECORD)
+    rc = lib().zr_ray_triangles(_ptr(rays), len(rays), _ptr(tris), len(tris), flags, _ptr(hits))
+    if rc != 0:
+        raise ZeldaRenderError(rc, "zr_ray_triangles: bad argument")
+    return hits
 
 
 def _delta_dict(d):
@@ -965,6 +985,28 @@ class Renderer:
         if n_slots is None:
             n_slots = self.instance_slots()[1]
         self._chk(self.L.zr_instance_coverage_async(self.h, C.c_void_p(dev_ptr) if dev_ptr else None, 4 * n_slots))
+
+    # ---- casting rays into the scene of the last frame
+    def raycast(self, rays, flags=0):
+        """The nearest hit of each ray (abi.RAY array, abi.make_rays) in the scene as the frame enqueued last drew it -> abi.RAY_RECORD array.
+        flags: abi.RAY_CULL_BACK | RAY_ANY_HIT | RAY_NO_BOUNDS."""
+        rays = _rays(rays)
+        hits = np.zeros(len(rays), dtype=abi.RAY_RECORD)
+        self._chk(self.L.zr_raycast(self.h, _ptr(rays), len(rays), flags, _ptr(hits), hits.nbytes))
+        return hits
+
+    def raycast_async(self, rays_dev, hits_dev, n, flags=0):
+        """The same from n rays at the device address rays_dev into n records at hits_dev (both 16-byte aligned), on the render stream,
+        without a host sync."""
+        self._chk(self.L.zr_raycast_async(self.h, C.c_void_p(rays_dev) if rays_dev else None, n, flags, C.c_void_p(hits_dev) if hits_dev else None))
+
+    def camera_ray(self, px, py):
+        """The world-space ray of the uniforms set last through frame position (px, py) (pixel centres at +0.5) -> abi.RAY array of one"""
+        r = abi.Ray()
+        self._chk(self.L.zr_camera_ray(self.h, px, py, C.byref(r)))
+        out = np.zeros(1, dtype=abi.RAY)
+        out["origin"], out["dir"], out["t_min"], out["t_max"] = tuple(r.origin), tuple(r.dir), r.t_min, r.t_max
+        return out
 
     # ---- multi-GPU
     def tiles_device_buffer(self):
