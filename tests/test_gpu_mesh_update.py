@@ -248,8 +248,8 @@ def _check_bounds(ml, mv, mt, v, what):
 
 def test_refitted_bounds_are_sound(gpu_engine):
     """After a device-form update the meshlets and vertices are read back: once before any frame (the host's statement of the bounds, from
-    the vertices read back) and once after a frame (the records k_mesh_refit wrote).  Both are sound; whether they are equal is printed
-    (DESIGN.md §5 reports it)."""
+    the vertices read back) and once after a frame (the records k_mesh_refit wrote).  Both are sound, and they are equal in every byte
+    (one statement, correctly rounded operations on both sides)."""
     import torch
     inst, u = _instances(), _uniforms()
     (sv, _), (tv, _) = _meshes()
@@ -274,8 +274,10 @@ def test_refitted_bounds_are_sound(gpu_engine):
             assert np.array_equal(ml[f], host[k][0][f])
         _check_bounds(ml, mv, mt, v, "mesh %d, refitted on the device" % k)
         _check_bounds(host[k][0], mv, mt, v, "mesh %d, host statement" % k)
-        same = np.array_equal(ml.view(np.uint8), host[k][0].view(np.uint8))
-        print("mesh %d: %d meshlets, device refit %s the host statement" % (k, len(ml), "EQUALS" if same else "DIFFERS FROM"))
+        for f in ("BoundsCenter", "BoundsRadius", "ConeApex", "ConeAxis", "ConeCutoff"):
+            a, b = ml[f].view(np.int32).astype(np.int64), host[k][0][f].view(np.int32).astype(np.int64)
+            print("mesh %d, %s: at most %d ulps from the host statement" % (k, f, int(np.abs(a - b).max())))
+        assert np.array_equal(ml.view(np.uint8), host[k][0].view(np.uint8)), "mesh %d: the records k_mesh_refit wrote differ from the host statement" % k
     g.close()
 
 
