@@ -642,6 +642,55 @@ int  zr_set_frame_delta_overlay(zr_ctx* ctx, int on);
 int  zr_frame_overlay(const uint8_t* rgba8, const float* depth, uint32_t width, uint32_t height, const float* pvm, const zr_overlay_segment* seg, uint32_t n,
                       const zr_overlay_style* style, size_t style_bytes, uint8_t* dst, size_t bytes);
 
+/* --- wireframe: the visible triangles' edges drawn over the delivered frame ("Wireframe"; DESIGN.md §5, "Wireframe") ---
+ * "Shaded + wire": the lit frame with the edges of the triangle that won each pixel drawn over it - hidden lines are removed by
+ * construction - on all of the scene or on the highlight set only, on the GPU behind the lighting pass from what the frame enqueued
+ * last left on the device: its winner plane (zr_set_id_capture), draw table, instance records, vertex sets and camera block.  Meshes
+ * deformed and instances moved on the device are followed with no host copy.  The frame itself is never drawn into, and a context that
+ * never asks for the stage enqueues and allocates what it always did.
+ * The rule (csrc/zr_wire.h states it in full; the kernel, zr_frame_wire and a client's own code agree byte for byte).  For a pixel
+ * (x, y) whose winner is a scene primitive with the clip-space corners c0, c1, c2 (the camera pass's own float32 values), in float64:
+ *   Hk = (hw (xk + wk), hh (yk + wk), wk), hw = W / 2, hh = H / 2        homogeneous screen coordinates, pixels
+ *   for the edges (0,1), (1,2), (2,0):  l = Ha x Hb;  s = (lx (x + 0.5) + ly (y + 0.5)) + lz;  n2 = lx lx + ly ly
+ *   on the wire iff for some edge n2 > 0 and s s <= (r r) n2, r = width_256 / 512 (a NaN compares false)
+ * i.e. the pixel centre lies within half the width of an edge's line; the rule holds for corners behind the eye.  A pixel on the wire
+ * has R, G, B blended with rgba at opacity rgba[3] (the highlight's blend), A stays.  With ZR_WIRE_SELECTED only pixels whose instance
+ * is in the highlight set are candidates (an empty set: no wire).  The skydome, the background and empty pixels never get a wire.
+ * Stages of a delivery, in this fixed order: wire, highlight, overlay, then the filter by `scale`.
+ * Refusals, the context unchanged, arguments first: ZR_ERR_ARG for an unknown stage bit, a scale outside 1..8, a null or misaligned
+ * pointer, a wrong byte count, a bad style; ZR_ERR_UNSUPPORTED where the lighting pass does not write the row-major frame
+ * (tile_world > 1, ZR_FLAG_PACKED_TILES); ZR_ERR_STATE before the first finished frame, between the stages of one and - with
+ * ZR_STAGE_WIRE as with ZR_STAGE_HIGHLIGHT - for the cases of zr_pick. */
+typedef struct zr_wire_style {        /* 16 bytes */
+    uint8_t  rgba[4];      /* R, G, B, opacity 0..255 */
+    uint32_t width_256;    /* full line width in 1/256 pixel, 1..4096 */
+    uint32_t flags;        /* ZR_WIRE_SELECTED or 0 */
+    uint32_t reserved;     /* 0, else ZR_ERR_ARG */
+} zr_wire_style;           /* default: {0, 0, 0, 255}, 256, 0 */
+#define ZR_WIRE_SELECTED 1u            /* only the instances of the highlight set (zr_highlight_set) */
+#define ZR_WIRE_WIDTH_MAX 4096u
+#define ZR_STAGE_WIRE      1u
+#define ZR_STAGE_HIGHLIGHT 2u
+#define ZR_STAGE_OVERLAY   4u
+/* bytes = the caller's sizeof(zr_wire_style) (passed like zr_stats).  Kept across zr_resize, zr_scene_clear and world loads. */
+int  zr_set_wire_style(zr_ctx* ctx, const zr_wire_style* style, size_t bytes);
+int  zr_get_wire_style(zr_ctx* ctx, zr_wire_style* style, size_t bytes);
+/* One delivery for every combination of stages (a mask of ZR_STAGE_*): the host form (zr_finish first, Wd*Hd*4 bytes to the host) and
+ * the device form (a caller-owned DEVICE buffer of Wd*Hd*4 bytes, 4-byte aligned, ordered on the render stream as
+ * zr_copy_frame_scaled_async; the frame after next waits before it rewrites what the stages read).  stages = 0, ZR_STAGE_HIGHLIGHT and
+ * ZR_STAGE_HIGHLIGHT | ZR_STAGE_OVERLAY deliver the bytes of zr_read_color_scaled, _highlighted and _overlaid(.., 1, ..). */
+int  zr_read_color_staged(zr_ctx* ctx, uint32_t stages, uint32_t scale, uint8_t* rgba8, size_t bytes);
+int  zr_copy_frame_staged_async(zr_ctx* ctx, uint32_t stages, uint32_t scale, void* color_dev);
+/* Deltas of the wired frame: callable only while delta is off (ZR_ERR_STATE while it is on), kept across zr_set_frame_delta(ctx, 0).
+ * While on, every delivery of changes draws the wire first: applying one gives zr_read_color_staged(ctx, ZR_STAGE_WIRE | .., delta scale). */
+int  zr_set_frame_delta_wire(zr_ctx* ctx, int on);
+/* The host statement of the rule, context-free host code.  prim = width*height winners (zr_read_ids, ZR_IDS_PRIMITIVE); corners = 9
+ * floats per primitive: x, y, w of its three clip-space corners; a winner at or above n_prims is no triangle; selected = n_prims bytes
+ * (non-zero = in the set, read only with ZR_WIRE_SELECTED) or null: every primitive.  style_bytes = the caller's
+ * sizeof(zr_wire_style); bytes == width*height*4; corners may be null when n_prims = 0. */
+int  zr_frame_wire(const uint8_t* rgba8, const uint32_t* prim, uint32_t width, uint32_t height, const float* corners, uint32_t n_prims, const uint8_t* selected,
+                   const zr_wire_style* style, size_t style_bytes, uint8_t* dst, size_t bytes);
+
 /* --- object identity of the last frame (which object won each pixel: picking, box selection, per-instance coverage) ---
  * What is reported is the deferred-scene pass's depth-test winner, i.e. what the GBuffer holds: the same in deferred and forward
  * shading and in every debug view.  The skydome and the background are not objects: they never appear and never hide a scene winner.

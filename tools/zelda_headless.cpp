@@ -8,7 +8,7 @@
 //   zelda_headless --root DIR [--world FILE.json] [--livelink PORT [--wait-ms MS]] [--meshlet FILE.meshlet --profab NAME]
 //                  [--size WxH] [--shadow N] [--frames N] [--roll-light-step F] [--debug-view V] [--out FRAME.ppm] [--device D]
 //                  [--pick X,Y[,W,H] [--highlight]] [--incremental] [--delta | --delta-packed] [--scale S] [--resize-at FRAME:WxH]
-//                  [--overlay FILE] [--overlay-box] [--raycast X,Y]
+//                  [--overlay FILE] [--overlay-box] [--raycast X,Y] [--wire[=WIDTH_256]] [--wire-selected]
 // --resize-at FRAME:WxH gives the live context a new extent ahead of frame FRAME (zr_resize), as a host whose window changes size does:
 // nothing is loaded again, it prints `resized <W>x<H>`, and with --delta, --delta-packed or --scale the client copy and the delivery
 // buffers follow the new (scaled) extent - the next delivery is a full one.
@@ -36,6 +36,10 @@
 // every frame is delivered overlaid through whichever of --delta, --delta-packed, --scale and --highlight is chosen -
 // zr_set_frame_delta_overlay, or zr_read_color_overlaid at the scale, which prints `overlaid <Wd>x<Hd>` per frame.  --out writes the
 // overlaid picture.
+// --wire[=WIDTH_256] draws the visible triangles' edges over every delivered frame (zelda_render.h, "wireframe"; opaque black, WIDTH_256
+// in 1/256 pixel, default 256), first of the stages: through zr_set_frame_delta_wire with --delta, else zr_read_color_staged at the scale
+// with whatever --highlight and --overlay add, which prints `wired <Wd>x<Hd>` per frame.  --wire-selected (with --pick X,Y --highlight)
+// draws it on the picked instances only (ZR_WIRE_SELECTED).  --out writes the wired picture.
 // --overlay-box (with --pick) draws the twelve edges of each picked instance's bounds: the pick is made after the first frame, the box
 // of the mesh's vertices (zr_mesh_get_vertices) is taken through the instance's scale, rotation and position (zr_object_get_instances:
 // the vertex stage's own transform, in double precision) and its edges join the list - yellow, hidden parts at a third - so every
@@ -67,6 +71,7 @@ int main(int argc, char** argv)
     bool pick = false, incremental = false, delta = false, packed = false, highlight = false, overlay_box = false; uint32_t px = 0, py = 0, pw = 1, ph = 1;
     uint32_t resize_at = 0xFFFFFFFFu, RW = 0, RH = 0;
     bool raycast = false; uint32_t rx = 0, ry = 0;
+    bool wire = false, wire_selected = false; uint32_t wire_width = 256;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
@@ -90,6 +95,9 @@ int main(int argc, char** argv)
         else if (a == "--highlight") highlight = true;
         else if (a == "--overlay") overlay = next();
         else if (a == "--overlay-box") overlay_box = true;
+        else if (a == "--wire") wire = true;
+        else if (a.rfind("--wire=", 0) == 0) { wire = true; wire_width = (uint32_t)atoi(a.c_str() + 7); }
+        else if (a == "--wire-selected") wire = wire_selected = true;
         else if (a == "--resize-at") { if (sscanf(next(), "%u:%ux%u", &resize_at, &RW, &RH) != 3) { fprintf(stderr, "--resize-at FRAME:WxH\n"); return 2; } }
         else if (a == "--pick") {
             const int got = sscanf(next(), "%u,%u,%u,%u", &px, &py, &pw, &ph);
@@ -101,6 +109,7 @@ int main(int argc, char** argv)
     }
     if (highlight && !pick) { fprintf(stderr, "--highlight needs --pick X,Y[,W,H]\n"); return 2; }
     if (overlay_box && !pick) { fprintf(stderr, "--overlay-box needs --pick X,Y[,W,H]\n"); return 2; }
+    if (wire_selected && !highlight) { fprintf(stderr, "--wire-selected needs --pick X,Y[,W,H] --highlight\n"); return 2; }
     zr_config cfg; memset(&cfg, 0, sizeof cfg);
     cfg.width = W; cfg.height = H; cfg.shadow_dim = SD; cfg.debug_view = debug_view; cfg.device = device; cfg.tile_world = 1;
     zr_ctx* c = nullptr;
@@ -130,7 +139,11 @@ int main(int argc, char** argv)
     }
     if (!have_world) { fprintf(stderr, "zelda_headless: no world (give --world FILE or send one to --livelink PORT)\n"); zr_destroy(c); return 1; }
 
-    if (pick && (rc = zr_set_id_capture(c, 1))) return fail(c, "zr_set_id_capture", rc);
+    if ((pick || wire) && (rc = zr_set_id_capture(c, 1))) return fail(c, "zr_set_id_capture", rc);
+    if (wire) {
+        const zr_wire_style st = { { 0, 0, 0, 255 }, wire_width, wire_selected ? ZR_WIRE_SELECTED : 0u, 0u };
+        if ((rc = zr_set_wire_style(c, &st, sizeof st))) return fail(c, "zr_set_wire_style (--wire=1..4096)", rc);
+    }
     std::vector<zr_overlay_segment> segs;
     if (!overlay.empty()) {          // --overlay: the list, read once
         FILE* fp = fopen(overlay.c_str(), "r");
@@ -204,7 +217,8 @@ int main(int argc, char** argv)
     const uint32_t scaled = delta ? 0u : scale;           // without --delta: the scale every frame is read at (0: frames are not read)
     std::vector<uint8_t> client, slots; std::vector<uint32_t> list, offsets;
     if (scale && (rc = zr_frame_scaled_extent(W, H, scale, &DW, &DH))) return fail(c, "zr_frame_scaled_extent (--scale 1..8)", rc);
-    if (scaled || ((highlight || lines) && !delta)) client.assign((size_t)DW * DH * 4, 0);
+    if (scaled || ((highlight || lines || wire) && !delta)) client.assign((size_t)DW * DH * 4, 0);
+    if (wire && delta && (rc = zr_set_frame_delta_wire(c, 1))) return fail(c, "zr_set_frame_delta_wire", rc);
     if (lines && delta && (rc = zr_set_frame_delta_overlay(c, 1))) return fail(c, "zr_set_frame_delta_overlay", rc);
     if (highlight && delta && (rc = zr_set_frame_delta_highlight(c, 1))) return fail(c, "zr_set_frame_delta_highlight", rc);
     if (scale && delta && (rc = zr_set_frame_delta_scale(c, scale))) return fail(c, "zr_set_frame_delta_scale", rc);
@@ -250,7 +264,12 @@ int main(int argc, char** argv)
         if ((rc = zr_world_update_uniforms(c, 0.0f, roll_step * (float)f, 0.016f * (float)f))) return fail(c, "zr_world_update_uniforms", rc);
         if ((rc = zr_render(c))) return fail(c, "zr_render", rc);
         if ((highlight || overlay_box) && f == 0 && do_pick()) return fail(c, "zr_pick / zr_highlight_set / zr_overlay_set", rc);      // the click: from here on the selection shows
-        if (!delta && lines) {                            // the overlaid frame (highlighted underneath or not), at the scale
+        if (!delta && wire) {                             // the wired frame, with whatever --highlight and --overlay add, at the scale
+            const uint32_t stages = ZR_STAGE_WIRE | (highlight ? ZR_STAGE_HIGHLIGHT : 0u) | (lines ? ZR_STAGE_OVERLAY : 0u);
+            if ((rc = zr_read_color_staged(c, stages, scale ? scale : 1u, client.data(), client.size()))) return fail(c, "zr_read_color_staged", rc);
+            printf("wired %ux%u\n", DW, DH);
+        }
+        else if (!delta && lines) {                       // the overlaid frame (highlighted underneath or not), at the scale
             if ((rc = zr_read_color_overlaid(c, scale ? scale : 1u, highlight ? 1 : 0, client.data(), client.size()))) return fail(c, "zr_read_color_overlaid", rc);
             printf("overlaid %ux%u\n", DW, DH);
         }
@@ -303,7 +322,7 @@ int main(int argc, char** argv)
     }
     if (!out.empty()) {
         std::vector<uint8_t> rgba((size_t)DW * DH * 4);
-        if (delta || scaled || highlight || lines) rgba = client;
+        if (delta || scaled || highlight || lines || wire) rgba = client;
         else if ((rc = zr_read_color(c, rgba.data(), rgba.size()))) return fail(c, "zr_read_color", rc);
         FILE* fp = fopen(out.c_str(), "wb");
         if (!fp) { fprintf(stderr, "zelda_headless: cannot write %s\n", out.c_str()); zr_destroy(c); return 1; }

@@ -126,6 +126,28 @@ OVERLAY_SIGNATURES = {
     "zr_set_frame_delta_overlay": [vp_, C.c_int],
     "zr_frame_overlay": [vp_, vp_, u32_, u32_, vp_, vp_, u32_, C.POINTER(OverlayStyle), C.c_size_t, vp_, C.c_size_t],
 }
+
+
+class WireStyle(C.Structure):
+    """ctypes mirror of zr_wire_style (16 bytes, passed with its size, like zr_stats)"""
+    _fields_ = [("rgba", C.c_uint8 * 4), ("width_256", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# numpy mirror of zr_wire_style
+WIRE_STYLE = np.dtype([("rgba", "u1", 4), ("width_256", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+assert C.sizeof(WireStyle) == WIRE_STYLE.itemsize == 16
+WIRE_SELECTED = 1                 # ZR_WIRE_SELECTED: only the instances of the highlight set
+WIRE_WIDTH_MAX = 4096             # ZR_WIRE_WIDTH_MAX: the widest line, in 1/256 pixel
+STAGE_WIRE, STAGE_HIGHLIGHT, STAGE_OVERLAY = 1, 2, 4         # ZR_STAGE_*: the stages of a staged delivery, applied in this order
+# the wireframe (include/zelda_render.h, "wireframe")
+WIRE_SIGNATURES = {
+    "zr_set_wire_style": [vp_, C.POINTER(WireStyle), C.c_size_t],
+    "zr_get_wire_style": [vp_, C.POINTER(WireStyle), C.c_size_t],
+    "zr_read_color_staged": [vp_, u32_, u32_, vp_, C.c_size_t],
+    "zr_copy_frame_staged_async": [vp_, u32_, u32_, vp_],
+    "zr_set_frame_delta_wire": [vp_, C.c_int],
+    "zr_frame_wire": [vp_, vp_, u32_, u32_, vp_, u32_, vp_, C.POINTER(WireStyle), C.c_size_t, vp_, C.c_size_t],
+}
 # zr_get_rest_settled / zr_get_rest_settled_parts: the parts a resting frame's launch left as they stand (a count; a byte per part)
 REST_SETTLE_SIGNATURES = {
     "zr_get_rest_settled": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
@@ -169,6 +191,11 @@ del vp_, u32_
 def make_highlight_style(outline=(255, 160, 0, 255), fill=(255, 160, 0, 0), radius=2):
     """zr_highlight_style from (R, G, B, opacity) tuples and the outline's width; the defaults are the library's"""
     return HighlightStyle((C.c_uint8 * 4)(*outline), (C.c_uint8 * 4)(*fill), radius, 0)
+
+
+def make_wire_style(rgba=(0, 0, 0, 255), width_256=256, flags=0):
+    """zr_wire_style from an (R, G, B, opacity) tuple, the full line width in 1/256 pixel and WIRE_SELECTED or 0; the defaults are the library's"""
+    return WireStyle((C.c_uint8 * 4)(*rgba), width_256, flags, 0)
 
 
 def make_rays(origins, dirs, t_min=0.0, t_max=np.inf):

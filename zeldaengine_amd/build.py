@@ -13,9 +13,9 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libzelda_render.so")
 KERNELS = ["zr_cull.hip", "zr_shadow.hip", "zr_camera.hip", "zr_resolve.hip", "zr_lighting.hip", "zr_forward.hip", "zr_frame.hip",
            "zr_ids.hip", "zr_instances.hip", "zr_mesh_update.hip", "zr_texture_update.hip",
-           "zr_world_update.hip", "zr_delta.hip", "zr_scale.hip", "zr_highlight.hip", "zr_overlay.hip", "zr_raycast.hip"]      # one per pass (+ the identity queries, the ray casts, the instance, vertex and texture updates, the world update's history carry, the frame delta, the scaled frame, the highlighted frame, the overlaid frame)
+           "zr_world_update.hip", "zr_delta.hip", "zr_scale.hip", "zr_highlight.hip", "zr_overlay.hip", "zr_raycast.hip", "zr_wire.hip"]      # one per pass (+ the identity queries, the ray casts, the wireframe, the instance, vertex and texture updates, the world update's history carry, the frame delta, the scaled frame, the highlighted frame, the overlaid frame)
 SOURCES = KERNELS + ["zr_context.cpp", "zr_resize.cpp", "zr_scene.cpp", "zr_frame_host.cpp", "zr_lighting_host.cpp", "zr_readback.cpp", "zr_update.cpp", "zr_instances_host.cpp", "zr_mesh_update_host.cpp",
-                     "zr_texture_update_host.cpp", "zr_deliver_host.cpp", "zr_highlight_host.cpp", "zr_overlay_host.cpp", "zr_raycast_host.cpp", "zr_world.cpp", "zr_world_doc.cpp", "zr_livelink.cpp", "zr_meshlet.cpp", "zr_assets.cpp",
+                     "zr_texture_update_host.cpp", "zr_deliver_host.cpp", "zr_highlight_host.cpp", "zr_overlay_host.cpp", "zr_raycast_host.cpp", "zr_wire_host.cpp", "zr_world.cpp", "zr_world_doc.cpp", "zr_livelink.cpp", "zr_meshlet.cpp", "zr_assets.cpp",
                      "zr_asset_files.cpp", "zr_dist.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-D__HIP_PLATFORM_AMD__"]

@@ -438,6 +438,9 @@ struct zr_ctx {
     // Casting rays (zr_raycast_host.cpp, zr_raycast.hip): the host form's staging on the device - cap rays in, cap records out - through
     // an owner of its own, grown on demand
     struct Rays { ZrOwn mem; zr_ray* rays = nullptr; zr_ray_hit* hits = nullptr; size_t cap = 0; } rays;
+    // The wireframe (zr_wire_host.cpp, zr_wire.hip).  style: host state, kept like the highlight's; frame (W * H) is made at first use
+    // through `ext`; delta: zr_set_frame_delta_wire.  A context that never asks for the stage has none of it.
+    struct Wire { zr_wire_style style = { { 0, 0, 0, 255 }, 256u, 0u, 0u }; bool delta = false; uint32_t* frame = nullptr; } wire;
 };
 
 // What the deliveries of changes compare, list and size their buffers for: the frame at the delta scale (zr_ctx::Delta::scale), in tiles
@@ -576,9 +579,15 @@ void zr_launch_overlay_setup(const zr_overlay_segment* seg, uint32_t n, const fl
                              hipStream_t st);
 void zr_launch_overlay_apply(const uint32_t* frame, const float* depth, const ZrOvRecord* recs, const uint32_t* rects, uint32_t n, uint32_t* dst, uint32_t W, uint32_t H,
                              const zr_overlay_style& style, hipStream_t st);
-// zr_deliver_host.cpp: the two whole-frame forms of a delivery (the highlight underneath, the overlay, the filter by `scale`)
-int zr_deliver_to_host(zr_ctx* c, const char* what, bool highlight, bool overlay, uint32_t scale, uint8_t* dst, size_t bytes);
-int zr_deliver_to_device(zr_ctx* c, const char* what, bool highlight, bool overlay, uint32_t scale, void* color_dev);
+// zr_wire_host.cpp: the wire stage of a delivery on the render stream - the edges of the last frame's winners drawn over `src` into `dst`
+// (null: the context's scratch frame, made at first use); *out: where the result lies
+int zr_wire_stage(zr_ctx* c, const uint32_t* src, uint32_t* dst, const uint32_t** out);
+// What is delivered: the frame enqueued last with the stages asked for applied in this order - the wire (zr_wire_stage), the highlight,
+// the overlay's lines (zr_overlay_stage) - then filtered by `scale` (1: not filtered)
+struct ZrDeliverWhat { bool wire, highlight, overlay; uint32_t scale; };
+// zr_deliver_host.cpp: the two whole-frame forms of a delivery
+int zr_deliver_to_host(zr_ctx* c, const char* what, ZrDeliverWhat w, uint8_t* dst, size_t bytes);
+int zr_deliver_to_device(zr_ctx* c, const char* what, ZrDeliverWhat w, void* color_dev);
 // zr_scene.cpp, also used by zr_world.cpp
 float zr_srgb_decode8(uint32_t c);
 int zr_material_prepare(zr_ctx* c, const zr_material* mat, ZrMaterialHost* out);

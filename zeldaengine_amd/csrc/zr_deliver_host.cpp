@@ -53,34 +53,34 @@ static int frame_is_row_major(zr_ctx* c, const char* what)
 
 // The frame enqueued last can be delivered: the lighting pass writes the frame, no frame is between its stages, a finished one is
 // enqueued - and, for a highlighted delivery, it kept its winners and still describes the scene.  The device is current afterwards.
-static int zr_deliver_ready(zr_ctx* c, const char* what, bool highlight)
+static int zr_deliver_ready(zr_ctx* c, const char* what, bool winners)
 {
     if (int rc = frame_is_row_major(c, what)) return rc;
     if (int rc = zr_stage_idle(c, what)) return rc;
     if (!c->rendered) return zr_fail(c, ZR_ERR_STATE, std::string(what) + ": no finished frame enqueued");
-    if (highlight)
+    if (winners)
         if (int rc = ids_ready(c, what, false)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     return ZR_OK;
 }
 
-// What is delivered: the frame enqueued last, highlighted or not, with the lines drawn over it or not (zr_overlay_stage), then filtered
-// by `scale` (1: not filtered)
-struct ZrDeliverWhat { bool highlight, overlay; uint32_t scale; };
-
-// The source stage, on the render stream.  dst: where the result goes, or null: the context's own scratch (hl.frame, d_scaled - both
-// made here at first use, through `ext`); *out: where it lies - c->d_color itself when nothing was to be done.  A caller's dst is
-// always written: where there is neither a highlight nor a factor, by the filter at scale 1, which is a copy.
+// The source stage, on the render stream: what `what` (ZrDeliverWhat, zr_ctx.h) names, in its order.  dst: where the result goes, or
+// null: the context's own scratch - each stage but the last writes its own frame (wire.frame and ov.frame, made by their stages;
+// hl.frame, made here), the filter d_scaled (made here), all at first use, through `ext`; *out: where it lies - c->d_color itself
+// when nothing was to be done.  A caller's dst is always written, by the last stage that runs: where no stage does and there is no
+// factor, by the filter at scale 1, which is a copy.
 static int zr_deliver_source(zr_ctx* c, ZrDeliverWhat what, uint32_t* dst, const uint32_t** out)
 {
     zr_ctx::Highlight& L = c->hl;
     const bool overlay = what.overlay && !c->ov.seg.empty();      // (an empty list: no stage)
-    const bool filter = what.scale > 1u || (dst && !what.highlight && !overlay);
+    const bool filter = what.scale > 1u || (dst && !what.wire && !what.highlight && !overlay);
     uint32_t* const hl_dst = filter || overlay ? nullptr : dst;      // (filtered or drawn over afterwards: highlighted into the scratch frame)
     if (what.highlight && !L.plane) HIPCHK(c, c->ext.alloc(&L.plane, (size_t)zr_hl_row_words(c->W) * c->H));
     if (what.highlight && !hl_dst && !L.frame) HIPCHK(c, c->ext.alloc(&L.frame, scaled_pixels(c, 1u)));
     if (filter && !dst && !c->d_scaled) HIPCHK(c, c->ext.alloc(&c->d_scaled, scaled_pixels(c, 2u)));      // (scale 2: the largest output)
     const uint32_t* src = c->d_color;
+    if (what.wire)
+        if (int rc = zr_wire_stage(c, src, what.highlight || overlay || filter ? nullptr : dst, &src)) return rc;
     if (what.highlight) {
         if (int rc = hl_upload(c)) return rc;
         uint32_t* const to = hl_dst ? hl_dst : L.frame;
@@ -105,14 +105,14 @@ static int zr_deliver_source(zr_ctx* c, ZrDeliverWhat what, uint32_t* dst, const
 // ------------------------------------------------------------------------------------------------ the form: the whole frame
 
 // ... to the host: zr_finish first (its overflow is the call's error), and the delivered frame is all that crosses the link
-int zr_deliver_to_host(zr_ctx* c, const char* what, bool highlight, bool overlay, uint32_t scale, uint8_t* dst, size_t bytes)
+int zr_deliver_to_host(zr_ctx* c, const char* what, ZrDeliverWhat w, uint8_t* dst, size_t bytes)
 {
-    ARGCHK(c, dst && scale_ok(scale));
-    ARGCHK(c, bytes == scaled_pixels(c, scale) * 4u);
-    int rc = zr_deliver_ready(c, what, highlight);
+    ARGCHK(c, dst && scale_ok(w.scale));
+    ARGCHK(c, bytes == scaled_pixels(c, w.scale) * 4u);
+    int rc = zr_deliver_ready(c, what, w.wire || w.highlight);
     if (rc == ZR_OK) rc = zr_finish(c);
     const uint32_t* src = nullptr;
-    if (rc == ZR_OK) rc = zr_deliver_source(c, { highlight, overlay, scale }, nullptr, &src);
+    if (rc == ZR_OK) rc = zr_deliver_source(c, w, nullptr, &src);
     if (rc) return rc;
     if (src != c->d_color) HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
@@ -120,36 +120,36 @@ int zr_deliver_to_host(zr_ctx* c, const char* what, bool highlight, bool overlay
 }
 
 // ... into a caller-owned device buffer, in stream order
-int zr_deliver_to_device(zr_ctx* c, const char* what, bool highlight, bool overlay, uint32_t scale, void* color_dev)
+int zr_deliver_to_device(zr_ctx* c, const char* what, ZrDeliverWhat w, void* color_dev)
 {
-    ARGCHK(c, color_dev && (uintptr_t)color_dev % 4 == 0 && scale_ok(scale));
-    if (int rc = zr_deliver_ready(c, what, highlight)) return rc;
+    ARGCHK(c, color_dev && (uintptr_t)color_dev % 4 == 0 && scale_ok(w.scale));
+    if (int rc = zr_deliver_ready(c, what, w.wire || w.highlight)) return rc;
     const uint32_t* at = nullptr;
-    return zr_deliver_source(c, { highlight, overlay, scale }, (uint32_t*)color_dev, &at);
+    return zr_deliver_source(c, w, (uint32_t*)color_dev, &at);
 }
 
 extern "C" int zr_read_color_scaled(zr_ctx* c, uint32_t scale, uint8_t* dst, size_t bytes)
 {
     if (!c) return ZR_ERR_ARG;
-    return zr_guard(c, [&]() -> int { return zr_deliver_to_host(c, "zr_read_color_scaled", false, false, scale, dst, bytes); });
+    return zr_guard(c, [&]() -> int { return zr_deliver_to_host(c, "zr_read_color_scaled", { false, false, false, scale }, dst, bytes); });
 }
 
 extern "C" int zr_copy_frame_scaled_async(zr_ctx* c, uint32_t scale, void* color_dev)
 {
     if (!c) return ZR_ERR_ARG;
-    return zr_guard(c, [&]() -> int { return zr_deliver_to_device(c, "zr_copy_frame_scaled_async", false, false, scale, color_dev); });
+    return zr_guard(c, [&]() -> int { return zr_deliver_to_device(c, "zr_copy_frame_scaled_async", { false, false, false, scale }, color_dev); });
 }
 
 extern "C" int zr_read_color_highlighted(zr_ctx* c, uint32_t scale, uint8_t* dst, size_t bytes)
 {
     if (!c) return ZR_ERR_ARG;
-    return zr_guard(c, [&]() -> int { return zr_deliver_to_host(c, "zr_read_color_highlighted", true, false, scale, dst, bytes); });
+    return zr_guard(c, [&]() -> int { return zr_deliver_to_host(c, "zr_read_color_highlighted", { false, true, false, scale }, dst, bytes); });
 }
 
 extern "C" int zr_copy_frame_highlighted_async(zr_ctx* c, uint32_t scale, void* color_dev)
 {
     if (!c) return ZR_ERR_ARG;
-    return zr_guard(c, [&]() -> int { return zr_deliver_to_device(c, "zr_copy_frame_highlighted_async", true, false, scale, color_dev); });
+    return zr_guard(c, [&]() -> int { return zr_deliver_to_device(c, "zr_copy_frame_highlighted_async", { false, true, false, scale }, color_dev); });
 }
 
 // ------------------------------------------------------------------------------------------------ the form: changed tiles - the state
@@ -255,11 +255,11 @@ struct DeltaForm {
     void* h_header;
 };
 
-// Delta is on, and the frame enqueued last can be delivered (highlight delivery on: as a highlighted one)
+// Delta is on, and the frame enqueued last can be delivered (wire or highlight delivery on: as such a one)
 static int delta_ready(zr_ctx* c, const char* what)
 {
     if (!c->delta.on) return zr_fail(c, ZR_ERR_STATE, std::string(what) + ": frame delta is off (zr_set_frame_delta)");
-    return zr_deliver_ready(c, what, c->hl.delta);
+    return zr_deliver_ready(c, what, c->wire.delta || c->hl.delta);
 }
 
 // Packed delivery is enabled: asked before the arguments are looked at, so that a host in mode 1 hears ZR_ERR_STATE whatever it passed
@@ -277,7 +277,7 @@ static int delta_enqueue(zr_ctx* c, const DeltaForm& F)
     const ZrDeltaExtent E = zr_delta_extent(c);
     const uint32_t serial = D.serial + 1u, full = D.full ? 1u : 0u;
     const uint32_t* frame = nullptr;
-    if (int rc = zr_deliver_source(c, { c->hl.delta, c->ov.delta, D.scale }, D.b.scaled, &frame)) return rc;
+    if (int rc = zr_deliver_source(c, { c->wire.delta, c->hl.delta, c->ov.delta, D.scale }, D.b.scaled, &frame)) return rc;
     if (F.offsets)
         zr_launch_frame_delta_packed(frame, D.b.delivered, D.b.flags, D.b.codec.lens, F.header, F.list, F.offsets, F.payload, E.W, E.H, E.tiles_x, E.n_tiles, full, serial,
                                      c->stream);

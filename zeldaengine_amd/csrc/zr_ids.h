@@ -44,3 +44,15 @@ struct ZrRayArgs {
     float M[16]; float m_scale;
 };
 void zr_launch_raycast(const ZrRayArgs& A, hipStream_t s);
+
+// zr_wire.hip: the wireframe (zr_wire.h has the rule).  frame (W x H, row-major RGBA8) with the edges of each pixel's winner drawn over
+// it into dst (4-byte aligned); prim, draws, n_draws: the census's (ZrIdsArgs); objs: the draw table of the frame enqueued last, in the
+// same draw order; set_bits: the highlight's bitset for a selected-only style, else null; PVM, hw, hh: that frame's camera block;
+// colour: zr_hl_pack of the style's; tiles_x: the launcher's
+struct ZrWireArgs {
+    const uint32_t* frame; const uint32_t* prim; uint32_t* dst;
+    const ZrIdsDraw* draws; const ZrObject* objs; const uint32_t* set_bits;
+    uint32_t n_draws, W, H, tiles_x, colour, width_256;
+    float PVM[16]; float hw, hh;
+};
+void zr_launch_wire_apply(const ZrWireArgs& A, hipStream_t s);

@@ -116,13 +116,13 @@ int zr_overlay_stage(zr_ctx* c, const uint32_t* src, uint32_t* dst, const uint32
 extern "C" int zr_read_color_overlaid(zr_ctx* c, uint32_t scale, int highlight, uint8_t* dst, size_t bytes)
 {
     if (!c) return ZR_ERR_ARG;
-    return zr_guard(c, [&]() -> int { return zr_deliver_to_host(c, "zr_read_color_overlaid", highlight != 0, true, scale, dst, bytes); });
+    return zr_guard(c, [&]() -> int { return zr_deliver_to_host(c, "zr_read_color_overlaid", { false, highlight != 0, true, scale }, dst, bytes); });
 }
 
 extern "C" int zr_copy_frame_overlaid_async(zr_ctx* c, uint32_t scale, int highlight, void* color_dev)
 {
     if (!c) return ZR_ERR_ARG;
-    return zr_guard(c, [&]() -> int { return zr_deliver_to_device(c, "zr_copy_frame_overlaid_async", highlight != 0, true, scale, color_dev); });
+    return zr_guard(c, [&]() -> int { return zr_deliver_to_device(c, "zr_copy_frame_overlaid_async", { false, highlight != 0, true, scale }, color_dev); });
 }
 
 extern "C" int zr_set_frame_delta_overlay(zr_ctx* c, int on)

@@ -112,7 +112,7 @@ void commit_extent_state(zr_ctx* c, ZrExtentState& E)
     // made at first use, through c->ext: the next use makes them for the new extent
     c->lk.plane = nullptr; c->lk.rest = nullptr; c->lk.alloc_failed = false;
     c->lk.marks = nullptr; c->lk.handed_out = false; zr_settle_forget(&c->lk.settle);      // (the frame's address is void with the old set)
-    c->d_scaled = nullptr; c->ids.obj = nullptr; c->hl.plane = nullptr; c->hl.frame = nullptr; c->ov.frame = nullptr;
+    c->d_scaled = nullptr; c->ids.obj = nullptr; c->hl.plane = nullptr; c->hl.frame = nullptr; c->ov.frame = nullptr; c->wire.frame = nullptr;
     c->d_tiles_ext = nullptr;            // (sized by the old slots_per_rank: back to the internal buffer)
     memset(&c->resolve_P, 0, sizeof c->resolve_P); memset(c->pass, 0, sizeof c->pass); c->pass_live[0] = c->pass_live[1] = false;
     if (E.pools) {

@@ -64,6 +64,7 @@ def lib():
         **abi.FRAME_SCALE_SIGNATURES,
         **abi.HIGHLIGHT_SIGNATURES,
         **abi.OVERLAY_SIGNATURES,
+        **abi.WIRE_SIGNATURES,
         **abi.EXTENT_SIGNATURES,
         **abi.RAYCAST_SIGNATURES,
         **abi.REST_SETTLE_SIGNATURES,
@@ -348,6 +349,33 @@ def frame_overlay(img, depth, pvm, segments, style=None):
                                 _ptr(out), out.nbytes)
     if rc:
         raise ZeldaRenderError(rc, "zr_frame_overlay: bad argument")
+    return out
+
+
+def _wire_style(style):
+    """an abi.WireStyle from one, from None (the default) or from a dict of make_wire_style's arguments"""
+    if isinstance(style, abi.WireStyle):
+        return style
+    return abi.make_wire_style(**(style or {}))
+
+
+def frame_wire(img, prim, corners, style=None, selected=None):
+    """zr_frame_wire, the host statement of the wireframe rule (host code only): img (H, W, 4) uint8, prim (H, W) uint32 winners
+    (read_ids(IDS_PRIMITIVE)), corners (n, 3, 3) float32 - x, y, w of each primitive's three clip-space corners - style an abi.WireStyle
+    (None: the default), selected n flags (read only with WIRE_SELECTED) or None: every primitive -> (H, W, 4) uint8"""
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    prim = np.ascontiguousarray(prim, dtype=np.uint32)
+    corners = np.ascontiguousarray(corners, dtype=np.float32).reshape(-1, 9)
+    assert img.ndim == 3 and img.shape[2] == 4 and prim.shape == img.shape[:2]
+    if selected is not None:
+        selected = np.ascontiguousarray(np.asarray(selected) != 0, dtype=np.uint8).reshape(-1)
+        assert selected.size == len(corners)
+    st = _wire_style(style)
+    out = np.zeros_like(img)
+    rc = lib().zr_frame_wire(_ptr(img), _ptr(prim), img.shape[1], img.shape[0], _ptr(corners) if len(corners) else None, len(corners),
+                             _ptr(selected) if selected is not None and selected.size else None, C.byref(st), C.sizeof(st), _ptr(out), out.nbytes)
+    if rc:
+        raise ZeldaRenderError(rc, "zr_frame_wire: bad argument")
     return out
 
 
@@ -894,6 +922,33 @@ class Renderer:
         """The frame enqueued last, overlaid and filtered by s -> a caller-owned device buffer (address, 4-byte aligned, ceil(W / s) *
         ceil(H / s) * 4 bytes), in stream order, no host synchronisation."""
         self._chk(self.L.zr_copy_frame_overlaid_async(self.h, s, 1 if highlight else 0, C.c_void_p(color_dev) if color_dev else None))
+
+    # ---- the wireframe: the visible triangles' edges drawn over the delivered frame
+    def set_wire_style(self, style=None, **kw):
+        """zr_set_wire_style: an abi.WireStyle, or make_wire_style's arguments (rgba=, width_256=, flags=)"""
+        st = _wire_style(style if style is not None else kw)
+        self._chk(self.L.zr_set_wire_style(self.h, C.byref(st), C.sizeof(st)))
+
+    def wire_style(self):
+        st = abi.WireStyle()
+        self._chk(self.L.zr_get_wire_style(self.h, C.byref(st), C.sizeof(st)))
+        return st
+
+    def read_color_staged(self, stages, s=1):
+        """zr_read_color_staged: the frame with the stages of the mask (abi.STAGE_WIRE | STAGE_HIGHLIGHT | STAGE_OVERLAY) applied in that
+        order, filtered by s (1..8) -> (ceil(H / s), ceil(W / s), 4) uint8"""
+        out = np.zeros(self._scaled_shape(s), dtype=np.uint8)
+        self._chk(self.L.zr_read_color_staged(self.h, stages, s, _ptr(out), out.nbytes))
+        return out
+
+    def copy_frame_staged_async(self, stages, s, color_dev):
+        """The frame enqueued last with the stages of the mask applied, filtered by s -> a caller-owned device buffer (address, 4-byte
+        aligned, ceil(W / s) * ceil(H / s) * 4 bytes), in stream order, no host synchronisation."""
+        self._chk(self.L.zr_copy_frame_staged_async(self.h, stages, s, C.c_void_p(color_dev) if color_dev else None))
+
+    def set_frame_delta_wire(self, on=True):
+        """The deliveries of changes carry the wire (default off; only while delta is off, kept across set_frame_delta(False))."""
+        self._chk(self.L.zr_set_frame_delta_wire(self.h, 1 if on else 0))
 
     def set_frame_delta_overlay(self, on=True):
         """The deliveries of changes deliver the overlaid frame (default off; only while delta is off, kept across set_frame_delta(False))."""
